@@ -20,7 +20,11 @@ sets the streaming launch's frame splits (2 with several passes in flight) and t
 (one per GPU, RCCL rendezvous on 127.0.0.1) without touching the GPU itself and relays rank 0's JSON line.  Under
 `torch.distributed.run` (WORLD_SIZE set) it is a rank and WORLD_SIZE must equal --gpus.
 
-Prints ONE JSON line (rank 0) with
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints ONE JSON line (rank 0):
+the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`) with its `config`, `tokens_checksum` and
+`passes_identical`.  `--dump-outputs DIR` also writes what the last timed step handed its caller (pipeline.PassResult) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+`--full` adds every other measurement and check to the line, after the timed region:
   `roofline`       dominant HBM-bound kernel (decode-step cross-attention), HIP-event timed on its launch stream;
   `roofline_mfma`  the encoder + cross-K/V GEMM set (19.4 TFLOP algorithmic per 64-clip pass) against the dense bf16 MFMA
                    peak, from HIP events around every GEMM launch of a real pass (wipa_profile_begin/end);
@@ -247,6 +251,27 @@ def phase_enc_loop(model, audio, steps: int, pipeline: int) -> None:
             pending[slot] = ev
     for ev in pending.values():
         ev.synchronize()
+
+
+DUMP_FEATURE_SAMPLE = 1 << 20  # encoder-output values --dump-outputs writes: a fixed, seeded sample (4 MB in f32)
+
+
+def dump_outputs(dirname: str, result) -> dict:
+    """--dump-outputs: what the timed path handed its caller for the LAST timed step (one pipeline.PassResult) as .npy files --
+    the token ids (prompt included) and summed log-probabilities in float64 (exact for the ids), and the encoder output
+    (`audio_features`) in float32 as a fixed sample of DUMP_FEATURE_SAMPLE flat positions drawn with seed 0.  Returns
+    {name: shape}."""
+    os.makedirs(dirname, exist_ok=True)
+    feats = result.audio_features.reshape(-1)
+    if feats.numel() > DUMP_FEATURE_SAMPLE:
+        idx = np.random.default_rng(0).integers(0, feats.numel(), size=DUMP_FEATURE_SAMPLE)
+        feats = feats[torch.from_numpy(idx).to(feats.device)]
+    arrays = {"tokens": np.asarray(result.tokens, dtype=np.float64),
+              "sum_logprobs": np.asarray(result.sum_logprobs, dtype=np.float64),
+              "audio_features_sample": feats.float().cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def latest_profile(suffix: str, fallback: str = ""):
@@ -1150,11 +1175,17 @@ def main():
     ap.add_argument("--batch", type=int, default=BATCH)
     ap.add_argument("--pipeline", type=int, default=N_PIPELINE,
                     help="consecutive passes kept in flight: whisper_ipa_amd.pipeline.transcribe_batches(passes_in_flight=...)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-finetune", action="store_true", help="skip the short fine-tune step measurement appended to the default line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other measurement and check of the line: single-pass latency, "
+                         "evaluate-style run, rooflines, CPU baseline + parity, fine-tune step, other configs (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (token ids, summed log-probs, a seeded sample of the encoder "
+                         "output) as DIR/<name>.npy in float64 / float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity legs")
+    ap.add_argument("--no-finetune", action="store_true", help="with --full: skip the short fine-tune step measurement")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the one-pass measurements of BASELINE.json configs[3] (whisper-medium, 256 clips) and configs[4] "
-                         "(whisper-large-v3 fp8, 128 clips) appended to the default line")
+                    help="with --full: skip the measurements of BASELINE.json configs[3] (whisper-medium, 256 clips) and configs[4] "
+                         "(whisper-large-v3 fp8, 128 clips)")
     ap.add_argument("--new-tokens", type=int, default=NEW_TOKENS,
                     help="decode positions per clip: 64 is the benchmark setting (SURVEY.md 8d), 224 the reference's cap (secondary)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"],
@@ -1183,6 +1214,8 @@ def main():
     ap.add_argument("--train-batch", type=int, default=32)
     ap.add_argument("--train-tokens", type=int, default=64)
     args = ap.parse_args()
+    if args.dump_outputs and (args.mode == "train" or args.phase):
+        ap.error("--dump-outputs writes the outputs of the inference benchmark's timed path (not --mode train / --phase)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -1202,7 +1235,6 @@ def main():
     # the streaming-launch setting of the timed region: the pipeline's own rule unless --cross-splits overrides it
     bench_splits = args.cross_splits if args.cross_splits is not None else (PIPELINE_CROSS_SPLITS if args.pipeline >= 2 else 0)
     audio_dev = torch.from_numpy(synthetic_audio(rank * B, B)).cuda()
-    setup = decode_setup(model.num_languages)
     opts = bench_options()
     bench_packed(model, B)
     torch.cuda.synchronize()
@@ -1228,13 +1260,21 @@ def main():
         timed_barrier(dist)
         t0 = time.perf_counter()
         for i in range(args.steps):
-            collected += [r.tokens for r in pipe.submit(audio_dev)]
-        collected += [r.tokens for r in pipe.drain()]
+            for r in pipe.submit(audio_dev):
+                collected.append(r.tokens)
+                last = r
+        for r in pipe.drain():
+            collected.append(r.tokens)
+            last = r
         timed_barrier(dist)
         elapsed = max_over_ranks(dist, time.perf_counter() - t0)
     tokens = collected[-1]
     assert len(collected) == args.steps
     model.cross_splits = bench_splits  # the legs below measure the setting that was timed
+    if rank == 0 and args.dump_outputs:
+        shapes = dump_outputs(args.dump_outputs, last)
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {shapes}")
+    del last  # the last pass's encoder output: not kept through the --full legs
 
     out = None
     absorbed_run = bench_absorbed(model, B)
@@ -1276,6 +1316,7 @@ def main():
             "passes_identical": bool(all(t.shape == collected[0].shape and (t == collected[0]).all() for t in collected)),
         }
         log(f"timed region done: {elapsed:.3f} s for {args.steps} passes")
+    if rank == 0 and args.full:
         # ---- everything below is OUTSIDE the timed region, one pass in flight
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -1319,6 +1360,7 @@ def main():
                 out["roofline_mfma"] = rm
         log("roofline microbenches done")
         if world == 1 and not args.no_cpu_baseline and args.model == "small" and B >= 8:
+            setup = decode_setup(model.num_languages)
             out["cpu_baseline"], ref, xa_ref = cpu_baseline(8)  # ~25 s of host work
             out["parity_vs_cpu"] = parity_vs_cpu(model, audio_dev, single, ref, setup, "lively")
             log("cpu baseline + parity done")
@@ -1360,6 +1402,7 @@ def main():
             oc = optional_leg(out, "other_configs", lambda: other_configs(args))
             if oc is not None:
                 out["other_configs"] = oc
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

@@ -1,11 +1,13 @@
-"""bench.py as the driver runs it, on small models so it takes seconds: the JSON contract, the `--gpus N` launcher
-(rehearsed on ONE GPU: WIPA_BENCH_SHARE_GPU=1 puts every rank on cuda:0 and moves the timing collectives over gloo --
-RCCL refuses two ranks on one device) and `--mode train`.  ``pytest -m gpu``."""
+"""bench.py as the driver runs it, on small models so it takes seconds: the JSON contract, the lean plain line and
+`--dump-outputs`, the legs `--full` adds, the `--gpus N` launcher (rehearsed on ONE GPU: WIPA_BENCH_SHARE_GPU=1 puts every rank
+on cuda:0 and moves the timing collectives over gloo -- RCCL refuses two ranks on one device) and `--mode train`.
+``pytest -m gpu``."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -13,8 +15,8 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(args, share_gpu=False, timeout=900):
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+def _run(args, share_gpu=False, timeout=900, unset=()):
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT") + tuple(unset)}
     if share_gpu:
         env["WIPA_BENCH_SHARE_GPU"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=timeout,
@@ -30,7 +32,7 @@ CONTRACT = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 
 def test_bench_single_rank_contract_and_rooflines():
-    out = _run(["--steps", "3", "--warmup", "1", "--model", "tiny", "--batch", "8", "--pipeline", "2"])
+    out = _run(["--steps", "3", "--warmup", "1", "--model", "tiny", "--batch", "8", "--pipeline", "2", "--full"])
     assert CONTRACT <= set(out)
     assert out["n_gpus"] == 1 and out["steps"] == 3 and out["unit"] == "audio-s/s" and out["value"] > 0 and out["passes_identical"] is True
     assert abs(out["value"] - 8 * 30.0 * 3 / (out["ms_per_step"] * 3e-3)) / out["value"] < 0.02
@@ -57,11 +59,12 @@ def test_bench_single_rank_contract_and_rooflines():
     ds = out["default_splits"]
     assert ds["cross_frame_splits"] == 4 and ds["decode_step_ms"] > 0 and ds["ms_per_pass_single_in_flight"] > 0
     assert ds["streaming_launch"]["workgroups"] == 32 and ds["streaming_launch"]["frac"] > 0
-    one = _run(["--steps", "2", "--warmup", "1", "--model", "tiny", "--batch", "8", "--pipeline", "1", "--no-cpu-baseline"])
+    one = _run(["--steps", "2", "--warmup", "1", "--model", "tiny", "--batch", "8", "--pipeline", "1", "--no-cpu-baseline", "--full"])
     assert one["config"]["cross_frame_splits"] == 4 and "default_splits" not in one and "frame splits" not in one["config"]["workload"]
     # mlx_whisper's projected K / V caches (opt-in): four more GEMM launches, the fused cross block as the roofline kernel, twice
     # the cross bytes, and the same accounting when the absorbed line is read in cached-K/V terms
-    ck = _run(["--steps", "3", "--warmup", "1", "--model", "tiny", "--batch", "8", "--pipeline", "2", "--no-cpu-baseline", "--cross-attention", "cached"])
+    ck = _run(["--steps", "3", "--warmup", "1", "--model", "tiny", "--batch", "8", "--pipeline", "2", "--no-cpu-baseline", "--cross-attention", "cached",
+               "--full"])
     assert ck["config"]["cross_attention"] == "cached" and ck["passes_identical"] is True
     assert "+ cross-K/V projection" in ck["config"]["workload"]
     # cross_attention="auto" decides from (clips, new tokens): long outputs at a small batch take the cached form
@@ -76,9 +79,11 @@ def test_bench_single_rank_contract_and_rooflines():
 def test_bench_experiment_flags_keep_the_ids():
     """The schedule and --new-tokens change when work runs / how long a row is, not the transcription: one pass at a time in the
     same streaming-launch setting gives the checksum of two passes in flight.  The line says which scheduler was timed (the
-    package's, not one of bench.py's own) and on how many hardware queues, and carries the evaluate_model-style run."""
+    package's, not one of bench.py's own) and on how many hardware queues, and carries the evaluate_model-style run (--full).
+    The first run leaves GPU_MAX_HW_QUEUES unset, so the count is the package's own request at import (a value the user set
+    stands instead: tests/test_host_logic.py)."""
     base = ["--steps", "2", "--warmup", "1", "--model", "tiny", "--batch", "8", "--pipeline", "2", "--no-cpu-baseline"]
-    plain = _run(base)
+    plain = _run(base + ["--full"], unset=("GPU_MAX_HW_QUEUES",))
     assert "whisper_ipa_amd.pipeline.TranscribePipeline" in plain["config"]["schedule"] and plain["config"]["hw_queues"] == 8
     ev = plain["evaluate_style"]
     assert ev["unit"] == "audio-s/s" and ev["value"] > 0 and ev["rows_transcribed"] == 8 * ev["batches"] and ev["decode_steps_per_batch"] == 64
@@ -92,6 +97,33 @@ def test_bench_experiment_flags_keep_the_ids():
     for phase in ("enc", "dec"):
         d = _run(base + ["--phase", phase])
         assert d["diagnostic_phase"] == phase and d["ms_per_pass"] > 0 and "metric" not in d and "value" not in d
+
+
+FULL_ONLY = {"roofline", "roofline_mfma", "decode_step", "default_splits", "evaluate_style", "cpu_baseline", "parity_vs_cpu",
+             "parity_vs_cpu_peaky", "finetune_step", "other_configs", "ms_per_pass_single_in_flight", "value_single_in_flight"}
+
+
+def test_bench_plain_line_is_lean_and_dumps_the_last_step(tmp_path):
+    """Without --full the line is the headline only (no leg runs after the timed steps); --dump-outputs writes what the last
+    timed step returned to its caller -- the token ids the checksum is taken over, the summed log-probs, a seeded sample of the
+    encoder output -- and a second run with the same arguments writes the same values."""
+    base = ["--steps", "3", "--warmup", "1", "--model", "tiny", "--batch", "8", "--pipeline", "2"]
+    a = _run(base + ["--dump-outputs", str(tmp_path / "a")])
+    assert CONTRACT <= set(a) and not FULL_ONLY & set(a), set(a)
+    assert a["steps"] == 3 and a["ms_per_step"] > 0 and a["passes_identical"] is True and a["dtype"] == "bf16"
+    assert abs(a["value"] - 8 * 30.0 * 3 / (a["ms_per_step"] * 3e-3)) / a["value"] < 0.02
+    names = ["audio_features_sample.npy", "sum_logprobs.npy", "tokens.npy"]
+    assert sorted(os.listdir(tmp_path / "a")) == names
+    tok = np.load(tmp_path / "a" / "tokens.npy")
+    assert tok.dtype == np.float64 and tok.shape == (8, 4 + 64) and int(tok.sum()) % 1000003 == a["tokens_checksum"]
+    slp = np.load(tmp_path / "a" / "sum_logprobs.npy")
+    assert slp.dtype == np.float64 and slp.shape == (8,) and np.isfinite(slp).all() and (slp < 0).all()
+    feats = np.load(tmp_path / "a" / "audio_features_sample.npy")
+    assert feats.dtype == np.float32 and feats.shape == (1 << 20,) and np.isfinite(feats).all() and feats.std() > 0
+    b = _run(base + ["--dump-outputs", str(tmp_path / "b")])
+    assert b["tokens_checksum"] == a["tokens_checksum"]
+    for name in names:
+        assert np.array_equal(np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)), name
 
 
 def test_bench_gpus_2_launches_two_ranks():

@@ -13,6 +13,8 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the reference's text test split (data/v2_filtered/combined_test_ipa.json), stored verbatim as a fixture
+REFERENCE_TEST_SPLIT = os.path.join(ROOT, "tests", "golden", "combined_test_ipa.json")
 
 
 def test_tokenizer_special_ids_and_framing():
@@ -159,16 +161,14 @@ def test_batch_token_framing(tmp_path):
 
 
 def test_reference_v2_test_split_tokenizes(tmp_path):
-    """the reference's text fixture data/v2_filtered/combined_test_ipa.json, if mounted, goes through
+    """the reference's text fixture data/v2_filtered/combined_test_ipa.json (tests/golden/) goes through
     the loader's framing verbatim (NFC-stable strings, round trip)."""
-    p = "/root/reference/data/v2_filtered/combined_test_ipa.json"
-    if not os.path.exists(p):
-        pytest.skip("reference data not mounted")
+    p = REFERENCE_TEST_SPLIT
     from whisper_ipa_amd.tokenizer import get_tokenizer
     import unicodedata
 
     tok = get_tokenizer(True)
-    data = json.load(open(p))
+    data = json.load(open(p, encoding="utf-8"))
     assert len(data) == 700
     for e in data[:200]:
         s = e["ipa_transcription"]
@@ -822,8 +822,7 @@ def test_native_bpe_matches_the_python_merge_loop(tmp_path):
         assert nat.decode_bytes(got) == piece
     assert nat.decode_bytes([5, 99999]) is None  # unknown id: left to the caller (special tokens)
     tok = Tokenizer(gpt2_byte_ranks(), byte_fallback=True)
-    p = "/root/reference/data/v2_filtered/combined_test_ipa.json"
-    texts = [e["ipa_transcription"] for e in json.load(open(p))[:300]] if os.path.exists(p) else ["kæt n̩ tʰ əː", "ɛ̃ ʃ"]
+    texts = [e["ipa_transcription"] for e in json.load(open(REFERENCE_TEST_SPLIT, encoding="utf-8"))[:300]] + ["kæt n̩ tʰ əː", "ɛ̃ ʃ"]
     for s in texts:
         ids = tok.encode(s)
         assert ids == [i for piece in tok._pat.findall(s) for i in _bpe(tok.ranks, piece.encode("utf-8"))]
@@ -851,6 +850,8 @@ def test_hw_queue_request_and_batch_prefetch(monkeypatch):
     from whisper_ipa_amd.pipeline import _prefetched
 
     assert os.environ.get("GPU_MAX_HW_QUEUES") is not None  # importing the package asked for it (or the user had set it)
+    # before the HIP runtime starts -- also when GPU tests earlier in this process have started it
+    monkeypatch.setattr(torch.cuda, "is_initialized", lambda: False)
     monkeypatch.setitem(RT._hwq, "requested_in_time", None)
     monkeypatch.setenv("GPU_MAX_HW_QUEUES", "6")
     assert RT.request_hw_queues() == 6 and RT.hw_queues() == 6  # the user's value stands
@@ -874,6 +875,32 @@ def test_hw_queue_request_and_batch_prefetch(monkeypatch):
     assert next(it) == 1
     with pytest.raises(OSError):
         next(it)
+
+
+def test_bench_dump_outputs_writes_what_the_caller_received(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last step's PassResult as .npy files -- ids and summed log-probs exactly, in float64; the
+    encoder output in float32, whole when small, else a seeded sample of fixed positions (the same on every call)."""
+    import types
+
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_FEATURE_SAMPLE", 500)
+    g = torch.Generator().manual_seed(3)
+    feats = torch.randn(4, 15, 16, generator=g).to(torch.bfloat16)
+    tokens = np.arange(4 * 68, dtype=np.int64).reshape(4, 68) + 50000
+    res = types.SimpleNamespace(tokens=tokens, sum_logprobs=np.linspace(-9.0, -1.0, 4, dtype=np.float32), audio_features=feats)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), res)
+    assert shapes == {"tokens": [4, 68], "sum_logprobs": [4], "audio_features_sample": [500]}
+    t, s, f = (np.load(tmp_path / "a" / f"{n}.npy") for n in ("tokens", "sum_logprobs", "audio_features_sample"))
+    assert t.dtype == s.dtype == np.float64 and f.dtype == np.float32
+    assert (t == tokens).all() and (s == res.sum_logprobs).all()
+    flat = feats.float().reshape(-1).numpy()
+    assert np.isin(f, flat).all() and len(np.unique(f)) > 250
+    bench.dump_outputs(str(tmp_path / "b"), res)
+    assert np.array_equal(np.load(tmp_path / "b" / "audio_features_sample.npy"), f)
+    monkeypatch.setattr(bench, "DUMP_FEATURE_SAMPLE", feats.numel())
+    bench.dump_outputs(str(tmp_path / "c"), res)
+    assert np.array_equal(np.load(tmp_path / "c" / "audio_features_sample.npy"), flat)
 
 
 def test_bench_optional_legs_do_not_cost_the_line(capsys):

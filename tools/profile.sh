@@ -32,14 +32,14 @@ reduce() {  # raw -> summaries (in $KEEP, under their committed names) + the sma
   du -sh $KEEP | cut -f1
 }
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py --no-cpu-baseline --no-finetune --no-other-configs"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline --no-finetune --no-other-configs"
 case "$MODE" in
 bench)
-  echo "== default bench"; python3 $ROOT/bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || exit 1
+  echo "== default bench"; python3 $ROOT/bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || exit 1
   echo "== kernel trace of the default bench command (the tracer runs the passes in flight one after another: durations, not concurrency)"
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o bench -- python3 $ROOT/bench.py --no-cpu-baseline --no-finetune --no-other-configs --steps 6 > $OUT/kt.log 2>&1 || exit 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o bench -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-finetune --no-other-configs --steps 6 > $OUT/kt.log 2>&1 || exit 1
   echo "== kernel trace, one pass in flight"
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt1 -o bench -- python3 $ROOT/bench.py --no-cpu-baseline --no-finetune --no-other-configs --steps 3 --pipeline 1 > $OUT/kt1.log 2>&1 || exit 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt1 -o bench -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-finetune --no-other-configs --steps 3 --pipeline 1 > $OUT/kt1.log 2>&1 || exit 1
   echo "== counters: streaming kernel of the absorbed cross-attention at $SPLITS frame splits (the dominant kernel of the decode step)"
   rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_x1 -- python3 $ROOT/tools/pmc_cross_absorbed.py > $OUT/pmc_x1.log 2>&1 || exit 1
   rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmc_x2 -- python3 $ROOT/tools/pmc_cross_absorbed.py > $OUT/pmc_x2.log 2>&1 || exit 1
@@ -122,7 +122,7 @@ final)
   cd $ROOT
   timeout -k 10 1000 python -m pytest tests -m gpu -q > $KEEP/final_tests.log 2>&1; tail -3 $KEEP/final_tests.log
   timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $KEEP/final_smoke.log 2>&1; tail -1 $KEEP/final_smoke.log
-  S=$(date +%s); python bench.py > $KEEP/final_bench.json 2> $KEEP/final_bench.err; echo "bench rc=$? wall=$(( $(date +%s) - S )) s"
+  S=$(date +%s); python bench.py --full > $KEEP/final_bench.json 2> $KEEP/final_bench.err; echo "bench rc=$? wall=$(( $(date +%s) - S )) s"
   python3 -c "
 import json; d=json.loads(open('$KEEP/final_bench.json').read().strip().splitlines()[-1])
 print('ms/pass', d['ms_per_step'], 'value', d['value'], 'single', d['ms_per_pass_single_in_flight'], 'evaluate-style', d['evaluate_style']['frac_of_value'],

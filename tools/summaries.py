@@ -46,8 +46,8 @@ def have(*parts):
 
 
 # ---- kernel stats of the default bench command (4 passes in flight) and of --pipeline 1
-for tag, d, cmd in (("default_cmd", "kt", "python3 bench.py --no-cpu-baseline --no-finetune --no-other-configs --steps 6"),
-                    ("pipeline1", "kt1", "python3 bench.py --no-cpu-baseline --no-finetune --no-other-configs --steps 3 --pipeline 1")):
+for tag, d, cmd in (("default_cmd", "kt", "python3 bench.py --full --no-cpu-baseline --no-finetune --no-other-configs --steps 6"),
+                    ("pipeline1", "kt1", "python3 bench.py --full --no-cpu-baseline --no-finetune --no-other-configs --steps 3 --pipeline 1")):
     if not have(d, "bench_kernel_stats.csv"):
         continue
     shutil.copy(os.path.join(SRC, d, "bench_kernel_stats.csv"), os.path.join(DST, f"{ROUND}_bench_{tag}_kernel_stats.csv"))
@@ -215,7 +215,7 @@ for i, (label, pat) in enumerate(cases):
 # (CROSS_TABLE=1 rewrites the table from the sw_*.json runs of `tools/profile.sh cross`)
 if rows and os.environ.get("CROSS_TABLE") == "1":
     with open(os.path.join(DST, f"{ROUND}_cached_vs_absorbed.txt"), "w") as f:
-        f.write("# bench.py --no-cpu-baseline --no-finetune --cross-attention {cached,absorbed} [...]   (MI355X; tools/profile.sh crosseep.sh)\n")
+        f.write("# bench.py --full --no-cpu-baseline --no-finetune --cross-attention {cached,absorbed} [...]   (MI355X; tools/profile.sh crosseep.sh)\n")
         f.write(f"# {'workload':66s} {'cached ms':>10s} {'audio-s/s':>10s} {'absorbed ms':>12s} {'audio-s/s':>10s} {'absorbed vs cached':>19s}\n")
         for label, cm, cv, am, av in rows:
             f.write(f"  {label:66s} {cm:10.2f} {cv:10.0f} {am:12.2f} {av:10.0f} {100 * (av / cv - 1):+18.1f}%\n")
