@@ -313,6 +313,13 @@ int wipa_decode_cross_block(const wipa_cross_block_desc* d, wipa_stream_t s);
  * 1.35 against 1.25 ms; 3: 73.5 ms / 1.26 ms) -- the caller who pipelines passes chooses (wipa_model_cfg.dec_cross_splits).
  * wipa_cross_absorbed_splits(want, Tk) = the count a launch uses: want clamped to 1..4 and to >= two 32-frame tiles per split. */
 int wipa_cross_absorbed_splits(int want, int Tk);
+/* xa residency: the streaming launch loads the first wipa_cross_absorbed_resident_groups(B, d, Tk, n_splits) 16-frame groups of every
+ * split with the default cache policy (they stay in the Infinity Cache for the next layer and step, which stream the same xa) and the
+ * rest non-temporally.  A cache hint only: no result depends on it.  _for(..., budget_bytes) is the rule itself -- a byte budget per
+ * pass (negative: every group), min(groups per split, budget / (B n_splits 16 d 2)); the four-argument form applies the process's
+ * budget (a default per split count, or WIPA_XA_RESIDENT_MB in 10^6 bytes, read once: -1 every group default policy, 0 none). */
+int wipa_cross_absorbed_resident_groups_for(int B, int d, int Tk, int n_splits, int64_t budget_bytes);
+int wipa_cross_absorbed_resident_groups(int B, int d, int Tk, int n_splits);
 size_t wipa_cross_absorbed_scratch_bytes(int B, int d, int Tk);
 int wipa_cross_absorbed_init(int d);
 int wipa_cross_absorbed_attention(const void* q, int64_t q_row_stride, const void* wkT, const void* xa, const void* wv, const float* bv,

@@ -12,6 +12,10 @@
 #   gemm-probe   tools/micro/gemm_loop_probe.hip: the encoder GEMM's loop taken apart, + MFMA-busy counters of every variant
 #   chain-pad    the chain probe and the real decode loops against GPU_MAX_HW_QUEUES x idle padding streams x the library's own streams
 #   group-sweep  tools/group_sweep.py: decode groups x groups in flight
+#   xa-probe     tools/micro/xa_residency_probe.hip: does a default-policy slice of an nt LDS-DMA stream stay in the Infinity Cache
+#   xa-sweep     headline line over xa residency budgets (WIPA_XA_RESIDENT_MB), 4 passes and 1 pass in flight
+#   xa-ab        headline A/B, alternating: every group default policy (-1) against the default budget (PARENT=<dir>: + the parent's build)
+#   xa-trace     kernel traces at -1 and at the default budget: lone durations of the streaming kernel and the skinny GEMMs by grid
 #   final        the tree's final check: pytest -m gpu, smoke(), the default bench line
 # RAW rocprofv3 output stays on the GPU box (/tmp/wipa_prof/$ROUND: a traced bench run is > 64 MiB, more than gpurun copies back);
 # every mode ends by running tools/summaries.py THERE, so what comes back under gpurun_out/$ROUND/ is the summaries (named as they
@@ -128,6 +132,35 @@ import json; d=json.loads(open('$KEEP/final_bench.json').read().strip().splitlin
 print('ms/pass', d['ms_per_step'], 'value', d['value'], 'single', d['ms_per_pass_single_in_flight'], 'evaluate-style', d['evaluate_style']['frac_of_value'],
       'step', d['decode_step']['ms_per_step'], 'roofline', d['roofline']['frac'], 'mfma', d['roofline_mfma']['frac'],
       'parity', d['parity_vs_cpu']['token_match'], d['parity_vs_cpu_peaky']['rows_identical'], 'other', {k: v['ms_per_step'] for k, v in d.get('other_configs', {}).items()})" ;;
-*) echo "usage: bash tools/profile.sh bench|gemm|cross|train-size|gaps|chain-probe|chain-pad|gemm-probe|group-sweep|final   (ROUND=r05 SPLITS=2)"; exit 2 ;;
+xa-probe)
+  hipcc --offload-arch=gfx950 -O3 -o /tmp/xa_residency_probe $ROOT/tools/micro/xa_residency_probe.hip 2>/dev/null || exit 1
+  timeout -k 10 180 /tmp/xa_residency_probe | tee $KEEP/xa_residency_probe.txt ;;
+xa-sweep|xa-ab)
+  # headline line per xa residency budget (WIPA_XA_RESIDENT_MB, 10^6 bytes per pass: -1 = every group default policy = the behaviour
+  # before the policy existed, 0 = every group nt, "dflt" = unset).  xa-sweep: the budgets that picked the default, then one pass in
+  # flight (4 frame splits).  xa-ab: -1 against the default, alternating.  PARENT=<built checkout of the commit before> adds its line.
+  cd $ROOT
+  xa_line() {  # label budget args...
+    local label=$1 mb=$2; shift 2
+    if [ "$mb" = dflt ]; then timeout -k 10 200 python3 bench.py --gpus 1 --steps 20 --warmup 5 "$@" > $OUT/xa_tmp.json 2> $OUT/xa_tmp.err
+    else WIPA_XA_RESIDENT_MB=$mb timeout -k 10 200 python3 bench.py --gpus 1 --steps 20 --warmup 5 "$@" > $OUT/xa_tmp.json 2> $OUT/xa_tmp.err; fi || return 1
+    python3 -c "import json; d = json.loads(open('$OUT/xa_tmp.json').read().strip().splitlines()[-1]); print('$label', '$*', 'ms_per_step', d['ms_per_step'], 'passes_identical', d['passes_identical'], 'tokens_checksum', d['tokens_checksum'])"
+  }
+  F=$KEEP/xa_residency_${MODE#xa-}.txt; : > $F
+  for r in 1 2 3; do
+    if [ -n "$PARENT" ]; then (cd $PARENT && xa_line "parent rep$r" dflt) | tee -a $F || exit 1; fi
+    if [ $MODE = xa-ab ]; then for MB in -1 dflt; do xa_line "MB=$MB rep$r" $MB | tee -a $F || exit 1; done
+    else for MB in -1 0 16 32 48 64 96; do xa_line "MB=$MB rep$r" $MB | tee -a $F || exit 1; done; fi
+  done
+  if [ $MODE = xa-sweep ]; then for r in 1 2 3; do for MB in -1 0 48 148; do xa_line "MB=$MB rep$r" $MB --pipeline 1 | tee -a $F || exit 1; done; done; fi ;;
+xa-trace)
+  # lone durations of the streaming kernel (grids 2x64 and 4x64) and of the skinny GEMMs next to it, every group default policy
+  # against the default budget: a kernel trace of its own per setting (no counters, no other tracing domain)
+  for MB in -1 dflt; do
+    if [ $MB = dflt ]; then timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/xa_kt_$MB -o bench -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-finetune --no-other-configs --steps 6 > $OUT/xa_kt_$MB.log 2>&1
+    else WIPA_XA_RESIDENT_MB=$MB timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/xa_kt_$MB -o bench -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-finetune --no-other-configs --steps 6 > $OUT/xa_kt_$MB.log 2>&1; fi || exit 1
+  done
+  python3 $ROOT/tools/xa_trace_summary.py "all-default=$(find $OUT/xa_kt_-1 -name '*kernel_trace.csv' | head -1)" "budget=$(find $OUT/xa_kt_dflt -name '*kernel_trace.csv' | head -1)" | tee $KEEP/xa_residency_trace.txt ;;
+*) echo "usage: bash tools/profile.sh bench|gemm|cross|train-size|gaps|chain-probe|chain-pad|gemm-probe|group-sweep|xa-probe|xa-sweep|xa-ab|xa-trace|final   (ROUND=r05 SPLITS=2)"; exit 2 ;;
 esac
 echo "== done $MODE"

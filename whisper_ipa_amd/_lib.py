@@ -124,6 +124,8 @@ SIGNATURES = {
     "wipa_decode_self_block": (c_int, [_P(SelfBlockDesc), c_void_p]),
     "wipa_decode_cross_block": (c_int, [_P(CrossBlockDesc), c_void_p]),
     "wipa_cross_absorbed_splits": (c_int, [c_int, c_int]),
+    "wipa_cross_absorbed_resident_groups_for": (c_int, [c_int, c_int, c_int, c_int, c_int64]),
+    "wipa_cross_absorbed_resident_groups": (c_int, [c_int, c_int, c_int, c_int]),
     "wipa_cross_absorbed_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
     "wipa_cross_absorbed_init": (c_int, [c_int]),
     "wipa_cross_absorbed_attention": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_size_t,

@@ -28,6 +28,7 @@
 // are equal up to bf16 noise, and closer to the f32 arithmetic.  bf16 models with <= 16 heads and d in {384, 512, 768, 1024}.
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 
 #include "wipa_common.h"
 
@@ -35,6 +36,9 @@ namespace {
 
 constexpr float NEG_BIG = -1.0e30f;
 constexpr int FT = 32;  // frames per tile
+// xa residency budgets per pass in 10^6 bytes (wipa_cross_absorbed_resident_groups): -1 = every group on the default policy
+constexpr long long XA_RESIDENT_MB_SHARED = 16;  // <= 2 frame splits: several passes in flight share the Infinity Cache
+constexpr long long XA_RESIDENT_MB_LONE = -1;    // 3-4 frame splits: a lone pass, its whole xa fits and stays
 typedef __attribute__((address_space(3))) void* lds_ptr_a;
 typedef int v2i32 __attribute__((ext_vector_type(2)));
 
@@ -45,7 +49,11 @@ struct AbsParams {
     float* part_l;        // [B][S][16]
     float* part_o;        // [B][S][16][D]
     int Tk, n_splits, tiles_per_split, H;
+    int resident_groups;  // the first 16-frame groups of every split that load with the default cache policy; the rest stream nt
 };
+
+// cache policy of an LDS-DMA transfer of xa (the instruction's aux field: an immediate, so a policy is an instantiation)
+constexpr int POLICY_DEFAULT = 0, POLICY_NT = 2;
 
 // chunk swizzle of the LDS tile image: 16-byte chunk c of frame row r sits at chunk c ^ ((r & 7) << 1).  The four rows of a
 // transposed-read block (and the two blocks of a 32-lane half, 4 rows apart) then hit disjoint banks.
@@ -100,13 +108,21 @@ __global__ __launch_bounds__(512, 1) void cross_absorbed_kernel(AbsParams p) {
         drow[i] = off / ROWB;
         dch[i] = ((off % ROWB) >> 4) ^ swz(off / ROWB);
     }
-    auto stage = [&](int t, int buf) {
+    const int res_tiles = p.resident_groups / 2;  // 32-frame tiles: the boundary rounds down to a tile
+    auto stage_as = [&](auto policy, int t, int buf) {
+        constexpr int AUX = decltype(policy)::value;
         const int f0 = (tile0 + t) * FT;
 #pragma unroll
         for (int i = 0; i < NDMA; ++i) {
             const int voff = min(f0 + drow[i], p.Tk - 1) * ROWB + dch[i] * 16;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (lds_ptr_a)(smem + buf * TILE + 1024 * (NDMA * wave + i)), 16, voff, 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (lds_ptr_a)(smem + buf * TILE + 1024 * (NDMA * wave + i)), 16, voff, 0, 0, AUX);
         }
+    };
+    // the split's first res_tiles tiles keep the default policy (they stay in the Infinity Cache for the next layer's and the
+    // next step's launch), the rest stream nt: same bytes, same order, same LDS image
+    auto stage = [&](int t, int buf) {
+        if (t < res_tiles) stage_as(std::integral_constant<int, POLICY_DEFAULT>{}, t, buf);
+        else stage_as(std::integral_constant<int, POLICY_NT>{}, t, buf);
     };
     auto wait_dma = [&](bool one_behind) {  // this wave's transfers of the current tile have landed (one younger tile may fly on)
         if (one_behind) {
@@ -350,7 +366,8 @@ __global__ __launch_bounds__(64 * NW_, 1) void cross_absorbed_v2_kernel(AbsParam
         dma_b[t] = r * ROWB;
     }
     int lane_v = lane;
-    auto stage = [&](int i_local, int slot) {
+    auto stage_as = [&](auto policy, int i_local, int slot) {
+        constexpr int AUX = decltype(policy)::value;
         const int f0 = (g0 + wave + NWV * i_local) * GF;
         if (f0 + GF <= p.Tk) {
 #pragma unroll
@@ -358,7 +375,7 @@ __global__ __launch_bounds__(64 * NW_, 1) void cross_absorbed_v2_kernel(AbsParam
                 const int j = i / PER, t = i % PER;
                 const int sj = (((QR * j) & 7) << 1) << 4;
                 const int voff = (dma_a[t] ^ sj) + dma_b[t];
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (lds_ptr_a)(my + slot * SLOT + 1024 * i), 16, voff, (f0 + QR * j) * ROWB, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (lds_ptr_a)(my + slot * SLOT + 1024 * i), 16, voff, (f0 + QR * j) * ROWB, 0, AUX);
             }
         } else {
             asm volatile("" : "+v"(lane_v));
@@ -368,9 +385,17 @@ __global__ __launch_bounds__(64 * NW_, 1) void cross_absorbed_v2_kernel(AbsParam
                 const int row = off / ROWB;
                 const int ch = ((off - row * ROWB) >> 4) ^ swz(row);
                 const int voff = min(f0 + row, p.Tk - 1) * ROWB + ch * 16;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (lds_ptr_a)(my + slot * SLOT + 1024 * i), 16, voff, 0, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rX, (lds_ptr_a)(my + slot * SLOT + 1024 * i), 16, voff, 0, 0, AUX);
             }
         }
+    };
+    // Residency: the split's first resident_groups groups load with the default policy and stay in the Infinity Cache for the next
+    // layer's and the next step's launch (every layer and step streams the same xa); the rest stream nt and leave the cache to
+    // them and to the decoder weights.  The group index is wave-uniform: a scalar compare picks one of two instantiations of the
+    // same transfers -- same bytes, same order, same LDS image, so no result changes with the boundary.
+    auto stage = [&](int i_local, int slot) {
+        if (wave + NWV * i_local < p.resident_groups) stage_as(std::integral_constant<int, POLICY_DEFAULT>{}, i_local, slot);
+        else stage_as(std::integral_constant<int, POLICY_NT>{}, i_local, slot);
     };
     const unsigned lds_my = (unsigned)(uintptr_t)(lds_ptr_a)my;
     // per-lane LDS addresses (slot 0).  Scores: row l15, k-step ks -> 256 (ks >> 2) + 64 ((ks & 3) ^ t) + 16 (g ^ (sw & 3)): four
@@ -931,7 +956,8 @@ __global__ __launch_bounds__(512) void cross_absorb_prologue_kernel(AbsPrologueP
 template <int D>
 int launch_attn(const AbsParams& p_in, int B, hipStream_t s) {
     const char* e = getenv("WIPA_ABS_KERNEL");
-    const AbsParams& p = p_in;
+    AbsParams p = p_in;
+    p.resident_groups = wipa_cross_absorbed_resident_groups(B, D, p.Tk, p.n_splits);  // every entry point launches through here
     // d = 1024: 64 column tiles are all 256 accumulation registers and a 16-frame group is 32 KiB, so the independent-wave form fits
     // with TWO waves only -- measured slower than the channel-split form there (whisper-medium, 256 clips: 191.5 vs 171.7 us per
     // launch, 845 vs 821 ms per pass); WIPA_ABS_KERNEL=2 selects it for A/B runs
@@ -963,6 +989,38 @@ extern "C" int wipa_cross_absorbed_splits(int want, int Tk) {
     int s = (want >= 1 && want <= 4) ? want : dflt;
     if (s > tiles / 2) s = tiles / 2;
     return s < 1 ? 1 : s;
+}
+
+// Residency of xa in the Infinity Cache (256 MiB, shared by everything in flight).  Every decoder layer of every step streams the
+// SAME xa, so a slice of it that survives in the cache from one launch to the next saves 11 of 12 HBM reads per step; the kernels
+// load the first resident_groups 16-frame groups of every split with the default policy and stream the rest nt (not retained).
+// The rule turns a byte budget PER PASS into groups per split: min(groups per split, budget / (B n_splits 16 d 2)); a budget that
+// covers the pass's whole xa (or a negative one) keeps every group on the default policy.  A pure function of the call's shape,
+// like the split count: never of which clips ride together.  (It cannot change a result in any case: the policy moves no byte.)
+extern "C" int wipa_cross_absorbed_resident_groups_for(int B, int d, int Tk, int n_splits, int64_t budget_bytes) {
+    if (B < 1 || d < 1 || Tk < 1) return 0;
+    const int S = wipa_cross_absorbed_splits(n_splits, Tk);
+    const int tiles = (Tk + FT - 1) / FT;
+    const int gps = 2 * ((tiles + S - 1) / S);  // 16-frame groups per split, as the kernels count them
+    if (budget_bytes < 0 || budget_bytes >= (int64_t)B * Tk * d * 2) return gps;
+    const int64_t g = budget_bytes / ((int64_t)B * S * 16 * d * 2);
+    return g < gps ? (int)g : gps;
+}
+
+// The budget of this process.  The native layer does not know how many passes are in flight; the split count stands in for it:
+// the pipeline asks for 2 splits when several passes are in flight and leaves 4 to a lone pass.  Measured (whisper-small, 64 clips,
+// profiles/xa_residency_sweep.txt, ms per pass, medians): 4 passes in flight, 2 splits: -1: 71.6, 0: 70.1, 16: 69.9, 32: 69.9, 48: 70.4,
+// 64: 70.9, 96: 71.3 -- nt is the gain (the four passes' 590 MB of xa stop evicting the weights they share), a small resident slice
+// is worth another 0.1-0.3 ms and 4 x 48 MB or more crowd the cache again: 16.  One pass in flight, 4 splits: -1: 109.9, 0: 110.3,
+// 148: 110.0 -- the lone pass's 147 MB fit and are re-read from the cache by every layer: everything stays on the default policy.
+// WIPA_XA_RESIDENT_MB (10^6 bytes; read once) overrides both for A/B runs: -1 = every group default policy (the kernels' behaviour
+// before the policy existed), 0 = every group nt.
+extern "C" int wipa_cross_absorbed_resident_groups(int B, int d, int Tk, int n_splits) {
+    static const int64_t env_mb = [] { const char* e = getenv("WIPA_XA_RESIDENT_MB"); return e ? (int64_t)atoll(e) : (int64_t)INT64_MIN; }();
+    const int S = wipa_cross_absorbed_splits(n_splits, Tk);
+    int64_t mb = env_mb;
+    if (mb == INT64_MIN) mb = (S <= 2) ? XA_RESIDENT_MB_SHARED : XA_RESIDENT_MB_LONE;
+    return wipa_cross_absorbed_resident_groups_for(B, d, Tk, S, mb < 0 ? -1 : mb * 1000000);
 }
 
 // sized for four splits whatever a call uses: one state blob serves every dec_cross_splits

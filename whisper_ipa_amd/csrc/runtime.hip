@@ -976,6 +976,8 @@ extern "C" int wipa_decoder_run(const wipa_model_cfg* cfg, const void* const* w,
         return WIPA_OK;
     }
     WIPA_REQUIRE(s != nullptr, "wipa_decoder_run: graph capture needs a non-default stream");
+    // (the streaming launch's resident_groups argument is baked into the captured step too, but needs no term here: it is a function
+    // of B, the width, the frame count and dec_cross_splits -- all in the key -- and of a budget that is constant per process)
     const int variant = cfg->dtype * 2 + t_f32_split + 4 * decode_mode(cfg, B) + 16 * cfg->dec_w_dtype + 64 * cfg->dec_cross_absorbed * (absorbed_block_fused() ? 2 : 1) + 256 * (int)tail_fused() + 512 * (int)absorbed_merge_out() + 1024 * cfg->dec_cross_splits + 8192 * (int)lean_ok;
     auto step_graph = [&](bool lean, hipGraphExec_t* out) -> int {  // kind 0: the full step, 2: the lean one
         hipGraphExec_t exec = nullptr;
