@@ -326,19 +326,19 @@ constexpr int BM = 128, BN = 128, ROWB = 128;  // ROWB: bytes of K per LDS row
 constexpr int TILE_BYTES = BM * ROWB;          // 16 KiB per operand tile
 constexpr int GROUP_M = 8;
 
-// TA / TW (float32 only): the operand arrives K-major -- A as [K][M], W as [K][N] -- and is transposed by the staging pass
-// (16-byte loads along the rows of one k, four 4-byte LDS writes into the usual [row][k] image), so a backward pass can
-// multiply by x^T, dy^T or W^T without a transpose kernel and a second copy in HBM.
-template <typename T, typename OutT, bool TA = false, bool TW = false>
-__global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmParams p) {
-    static_assert(!(TA || TW) || sizeof(T) == 4, "K-major operands: float32 only");
-    extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 buffers][W tile | A tile]
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int wn = wave >> 1, wm = wave & 1;
+// ---------------------------------------------------------------------------------------
+// Pieces shared by the tile kernels.  A kernel body reads: tile_id -> WIPA_TILE_STAGER -> its own K loop -> (dequantisation) ->
+// WIPA_STORE_TILE.  tile_id, frag_lane, tile_rsrc and dma_offset are functions.  The other pieces are macros over the kernel's
+// own locals (p, acc, smem, m0, n0, wave, lane, frow, fsw, fq), because that is what keeps the compiled kernels unchanged: a
+// __forceinline__ function (or a struct with the stager's resources and offsets) goes through the compiler's per-function
+// passes before it is inlined, and every kernel that used one came out with another epilogue layout or address prologue.
 
-    // ---- workgroup -> tile: XCD-contiguous chunks (bijective), then GROUP_M super-rows
+// workgroup -> tile: XCD-contiguous chunks (bijective), then GROUP_M super-rows.  In tiles: callers multiply by their tile size.
+// (tools/micro/gemm_loop_probe.hip restates this mapping on purpose.)
+struct TileId {
+    int m, n;
+};
+__device__ __forceinline__ TileId tile_id(const GemmParams& p) {
     const int nblocks = p.tiles_m * p.tiles_n;
     int id;
     {
@@ -352,9 +352,167 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmParams p) {
     const int first_m = group * GROUP_M;
     const int gm = min(p.tiles_m - first_m, GROUP_M);
     const int in_group = id - group * group_size;
-    const int tile_m = first_m + in_group % gm;
-    const int tile_n = in_group / gm;
-    const int m0 = tile_m * BM, n0 = tile_n * BN;
+    return {first_m + in_group % gm, in_group / gm};
+}
+
+// Lane constants of the MFMA fragment layout: frow = row within a 16-row tile, fq = 16-byte chunk of the 64-byte K step (and the
+// 4-column group of the accumulator), fsw = the read-side chunk swizzle, == ((row >> 1) & 7) for row = 16*x + (lane & 15).
+struct FragLane {
+    int frow, fsw, fq;
+};
+__device__ __forceinline__ FragLane frag_lane(int lane) { return {lane & 15, (lane >> 1) & 7, lane >> 4}; }
+
+// acc[NI][NJ] = 0  ([n tile i][m tile j])
+#define WIPA_ZERO_ACC(NI, NJ) \
+    _Pragma("unroll") for (int i = 0; i < (NI); ++i) _Pragma("unroll") for (int j = 0; j < (NJ); ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f}
+
+// Direct epilogue of one wave's [16*MT rows x 64 columns] block at (m_base, n_base): 4-column stores straight from the MFMA
+// layout.
+#define WIPA_STORE_TILE_DIRECT(OutT, MT, m_base, n_base, coff_dev, vec)                                      \
+    EpiCol cols[4];                                                                                          \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) cols[i] = epi_col(p, (n_base) + 16 * i + 4 * fq);          \
+    _Pragma("unroll") for (int j = 0; j < (MT); ++j) {                                                       \
+        const EpiRow row = epi_row(p, (m_base) + 16 * j + frow, coff_dev);                                   \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) epilogue4<OutT>(p, acc[i][j], row, cols[i], vec);      \
+    }
+
+// Bias + GELU on the MFMA layout, in place and BEFORE the transposing epilogue (which is then compiled without its GELU path:
+// 192 accumulators + those temporaries would spill).  A lane holds columns n_base + 16 i + 4 fq + (0..3).  The dispatcher sends
+// an activation here only with a plain column bias and no column scale.  The bias is spent: p.bias is cleared.
+#define WIPA_BIAS_GELU_MFMA(MT, n_base)                                                                      \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                          \
+        const int n = (n_base) + 16 * i + 4 * fq;                                                            \
+        float b4[4];                                                                                         \
+        _Pragma("unroll") for (int e = 0; e < 4; ++e) b4[e] = (p.bias && n + e < p.N) ? p.bias[n + e] : 0.f; \
+        _Pragma("unroll") for (int j = 0; j < (MT); ++j) {                                                   \
+            const f32x2 g0 = gelu_erf2(f32x2{acc[i][j][0] + b4[0], acc[i][j][1] + b4[1]});                   \
+            const f32x2 g1 = gelu_erf2(f32x2{acc[i][j][2] + b4[2], acc[i][j][3] + b4[3]});                   \
+            acc[i][j] = f32x4{g0.x, g0.y, g1.x, g1.y};                                                       \
+            __builtin_amdgcn_sched_barrier(0); /* one tile at a time: the scheduler would otherwise overlap all 48 and spill */ \
+        }                                                                                                    \
+    }                                                                                                        \
+    p.bias = nullptr;
+
+// Tail of the LDS-DMA tile kernels (8 waves, a wave holds [16*MT rows x 64 columns] at m_base, n_base); ends the kernel.  The
+// last barrier of the K loop has retired every LDS read, so a stage_ok output reuses the buffers as per-wave scratch for
+// epilogue_staged; any other output takes the direct stores.  GELU: where the activation is applied --
+enum { GELU_IN_EPILOGUE, GELU_NONE, GELU_FIRST };  // by epilogue_staged | never compiled in | by WIPA_BIAS_GELU_MFMA ahead of it
+// STAGED_ONLY: the dispatcher sends only stage_ok outputs (no direct path is compiled).
+#define WIPA_STORE_TILE(OutT, MT, GELU, STAGED_ONLY, m_base, n_base)                                         \
+    [[maybe_unused]] const bool vec = p.vec_ok != 0;                                                         \
+    int64_t coff_dev = p.c_offset;                                                                           \
+    if (p.c_offset_dev) coff_dev += *p.c_offset_dev;                                                         \
+    if ((STAGED_ONLY) || p.stage_ok) {                                                                       \
+        if constexpr ((GELU) == GELU_FIRST) {                                                                \
+            WIPA_BIAS_GELU_MFMA(MT, n_base)                                                                  \
+        }                                                                                                    \
+        epilogue_staged<OutT, MT, 0, MT, (GELU) == GELU_IN_EPILOGUE, (GELU) != GELU_FIRST>(p, acc, smem + wave * 4096, m_base, n_base, \
+                                                                                           coff_dev, lane); \
+        return;                                                                                              \
+    }                                                                                                        \
+    if constexpr (!(STAGED_ONLY)) {                                                                          \
+        WIPA_STORE_TILE_DIRECT(OutT, MT, m_base, n_base, coff_dev, vec)                                      \
+    }
+
+// Geometry of an LDS-DMA tile kernel: BM x BN outputs, 8 waves of 64 columns each (WN along N, 8 / WN along M), K-step ROWB
+// bytes, two LDS buffers of [W tile BN rows | A tile BM rows].  ZIP: the stager issues W and A pieces alternately (the
+// 256 x 256 kernels), otherwise all W pieces, then all A pieces.
+template <int BM_, int BN_, bool ZIP_>
+struct TileGeom {
+    static constexpr int BM = BM_, BN = BN_;
+    static constexpr int WN = BN / 64;                            // waves along N
+    static constexpr int MT = BM * WN / 128;                      // 16-row slices per wave
+    static constexpr int W_PIECES = BN / 64, A_PIECES = BM / 64;  // 64-row DMA pieces per operand
+    static constexpr int W_TILE = BN * ROWB;
+    static constexpr int STAGE = W_TILE + BM * ROWB;
+    static constexpr int SMEM = 2 * STAGE;
+    static constexpr bool ZIP = ZIP_;
+    static_assert(W_PIECES <= A_PIECES && (!ZIP || W_PIECES == A_PIECES), "stager loop bounds");
+};
+
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+
+// LDS-DMA staging (global_load_lds, 16 bytes per lane, no VGPR round trip and no ds_write).  The LDS image is lane-linear per
+// 1-KiB piece (8 rows x 128 B), so the bank swizzle (chunk ^ ((row>>1)&7)) is applied to the per-lane SOURCE address and again
+// on the read.  The DMA is the BUFFER form (buffer_load_dwordx4 ... lds): one resource per operand tile (SGPRs), a per-lane
+// 32-bit byte offset computed once, and the K-step as the scalar offset -- no 64-bit VALU address arithmetic per piece in the loop.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const char* base, int row0, int64_t ld_b) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(base + (int64_t)row0 * ld_b), 0, 0x7fffffff, 0x00020000);
+}
+// byte offset of the lane's chunk of tile row `row` (tile at row0 of `rows`; rows past the end repeat the last one): the
+// half-tile cut of gemm_nt256p_kernel.  WIPA_TILE_STAGER spells the same formula with c * 16 (the two spellings compile to
+// different address prologues, so each keeps the one its kernels were built with).
+__device__ __forceinline__ int dma_offset(int row, int lane, int row0, int rows, int64_t ld_b) {
+    return (min(row0 + row, rows - 1) - row0) * (int)ld_b + (((lane & 7) ^ ((row >> 1) & 7)) << 4);
+}
+// WIPA_TILE_STAGER(G) declares stage(kt, buf) -- K-step kt into LDS buffer buf: piece i of an operand covers rows
+// 64*i + 8*wave + (lane>>3); the lane's physical chunk is lane&7.
+#define WIPA_TILE_STAGER(G)                                                                                                               \
+    const __amdgpu_buffer_rsrc_t rW = tile_rsrc(p.W, n0, p.ldw_b);                                                                        \
+    const __amdgpu_buffer_rsrc_t rA = tile_rsrc(p.A, m0, p.lda_b);                                                                        \
+    int oW[G::W_PIECES], oA[G::A_PIECES];                                                                                                 \
+    _Pragma("unroll") for (int i = 0; i < G::A_PIECES; ++i) {                                                                             \
+        const int row = 64 * i + 8 * wave + (lane >> 3);                                                                                  \
+        const int c = (lane & 7) ^ ((row >> 1) & 7);                                                                                      \
+        if (i < G::W_PIECES) oW[i] = (min(n0 + row, p.N - 1) - n0) * (int)p.ldw_b + c * 16;                                               \
+        oA[i] = (min(m0 + row, p.M - 1) - m0) * (int)p.lda_b + c * 16;                                                                    \
+    }                                                                                                                                     \
+    auto stage = [&](int kt, int buf) {                                                                                                   \
+        const int kb = kt * ROWB;                                                                                                         \
+        char* base = smem + buf * G::STAGE + wave * (8 * ROWB);                                                                           \
+        if constexpr (G::ZIP) {                                                                                                           \
+            _Pragma("unroll") for (int i = 0; i < G::W_PIECES; ++i) {                                                                     \
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, (lds_ptr_t)(base + i * 64 * ROWB), 16, oW[i], kb, 0, 0);                     \
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (lds_ptr_t)(base + G::W_TILE + i * 64 * ROWB), 16, oA[i], kb, 0, 0);         \
+            }                                                                                                                             \
+        } else {                                                                                                                          \
+            _Pragma("unroll") for (int i = 0; i < G::W_PIECES; ++i)                                                                       \
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, (lds_ptr_t)(base + i * 64 * ROWB), 16, oW[i], kb, 0, 0);                     \
+            _Pragma("unroll") for (int i = 0; i < G::A_PIECES; ++i)                                                                       \
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (lds_ptr_t)(base + G::W_TILE + i * 64 * ROWB), 16, oA[i], kb, 0, 0);         \
+        }                                                                                                                                 \
+    }
+
+// fp8 tile kernels: a lane (row = lane & 15, k-group = lane >> 4) feeds the 32 bytes k = 32 (lane >> 4) ... + 31 of its row to the
+// 128-element MFMA: two ds_read_b128 at the swizzled chunks 2 fq and 2 fq + 1.
+typedef int v8i32 __attribute__((ext_vector_type(8)));
+typedef int v4i32 __attribute__((ext_vector_type(4)));
+#define WIPA_FP8_FRAG()                                                                                      \
+    const int c0 = ((2 * fq) ^ fsw) << 4, c1 = ((2 * fq + 1) ^ fsw) << 4;                                    \
+    auto frag = [&](const char* row) {                                                                       \
+        const v4i32 lo = *reinterpret_cast<const v4i32*>(row + c0);                                          \
+        const v4i32 hi = *reinterpret_cast<const v4i32*>(row + c1);                                          \
+        return v8i32{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};                                \
+    }
+// fp8 dequantisation: acc[i][j][e] is C[m = m_base + 16 j + frow][n = n_base + 16 i + 4 fq + e].  The per-row scales are powers
+// of two, so acc * a_scale[m] * w_scale[n] is exact.
+#define WIPA_DEQUANT_FP8(MT, m_base, n_base)                                                                 \
+    {                                                                                                        \
+        f32x4 ws[4];                                                                                         \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                      \
+            const int n = (n_base) + 16 * i + 4 * fq;                                                        \
+            _Pragma("unroll") for (int e = 0; e < 4; ++e) ws[i][e] = p.w_scale[min(n + e, p.N - 1)];         \
+        }                                                                                                    \
+        _Pragma("unroll") for (int j = 0; j < (MT); ++j) {                                                   \
+            const float as = p.a_scale[min((m_base) + 16 * j + frow, p.M - 1)];                              \
+            _Pragma("unroll") for (int i = 0; i < 4; ++i) acc[i][j] *= ws[i] * as;                           \
+        }                                                                                                    \
+    }
+
+// TA / TW (float32 only): the operand arrives K-major -- A as [K][M], W as [K][N] -- and is transposed by the staging pass
+// (16-byte loads along the rows of one k, four 4-byte LDS writes into the usual [row][k] image), so a backward pass can
+// multiply by x^T, dy^T or W^T without a transpose kernel and a second copy in HBM.
+template <typename T, typename OutT, bool TA = false, bool TW = false>
+__global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmParams p) {
+    static_assert(!(TA || TW) || sizeof(T) == 4, "K-major operands: float32 only");
+    extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 buffers][W tile | A tile]
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int wn = wave >> 1, wm = wave & 1;
+
+    const TileId tile = tile_id(p);
+    const int m0 = tile.m * BM, n0 = tile.n * BN;
 
     // ---- staging assignment: 4 rows of each operand per thread, one 16-byte chunk each
     const int srow = tid >> 3, schunk = tid & 7;
@@ -414,14 +572,8 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmParams p) {
     };
 
     f32x4 acc[4][4];  // [n tile i][m tile j]
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int frow = lane & 15;
-    const int fsw = (lane >> 1) & 7;  // == ((row >> 1) & 7) for row = 16*x + (lane & 15)
-    const int fq = lane >> 4;
+    WIPA_ZERO_ACC(4, 4);
+    const auto [frow, fsw, fq] = frag_lane(lane);
     // split-K (weight gradients: small M x N, very long K): slice blockIdx.y of k_slices owns a contiguous range of
     // K-steps and writes its partial tile to slab blockIdx.y; the caller adds the slabs in order (wipa_sum_slabs)
     const int nk_all = p.K * (int)sizeof(T) / ROWB;
@@ -488,15 +640,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmParams p) {
     int64_t coff_dev = p.c_offset + (int64_t)kz * p.slab_stride;
     if (p.c_offset_dev) coff_dev += *p.c_offset_dev;
     if (kz > 0) p.bias = nullptr;  // partial slabs: the bias rides on slice 0 only
-    EpiCol cols[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) cols[i] = epi_col(p, n0 + wn * 64 + 16 * i + 4 * fq);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const EpiRow row = epi_row(p, m0 + wm * 64 + 16 * j + frow, coff_dev);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) epilogue4<OutT>(p, acc[i][j], row, cols[i], vec);
-    }
+    WIPA_STORE_TILE_DIRECT(OutT, 4, m0 + wm * 64, n0 + wn * 64, coff_dev, vec)
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1099,16 +1243,12 @@ constexpr int SKINNY_STREAM_MAX_M = 1024;  // ... and up to here for wipa_gemm_d
 // ---------------------------------------------------------------------------------------
 // Large-tile GEMM: 256x256 output tile, 8 waves (2 along M x 4 along N, 128x64 per wave =
 // 8x4 MFMA tiles), K-step 128 bytes, LDS 2 x 64 KiB, one workgroup per CU.  Tiles are staged
-// with LDS-DMA (global_load_lds, 16 bytes per lane, no VGPR round trip and no ds_write):
-// the LDS image is lane-linear per 1-KiB piece (8 rows x 128 B), so the bank swizzle
-// (chunk ^ ((row>>1)&7)) is applied to the per-lane SOURCE address and again on the read.
+// with LDS-DMA (WIPA_TILE_STAGER).
 // Per K-step a wave issues 24 ds_read_b128 for 64 MFMAs (the 128x128 kernel: 16 for 32).
 constexpr int LBM = 256, LBN = 256;
-constexpr int LTILE = LBM * ROWB;  // 32 KiB per operand tile
-constexpr int LSMEM = 4 * LTILE;   // 128 KiB
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
+typedef TileGeom<LBM, LBN, true> L256;
+constexpr int LTILE = L256::W_TILE;  // 32 KiB per operand tile
+constexpr int LSMEM = L256::SMEM;    // 128 KiB
 
 template <typename T, typename OutT, bool SPLIT>  // SPLIT: f32 products as three bf16 MFMA terms
 __global__ __launch_bounds__(512) void gemm_nt256_kernel(GemmParams p) {
@@ -1117,56 +1257,13 @@ __global__ __launch_bounds__(512) void gemm_nt256_kernel(GemmParams p) {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
-
-    const int nblocks = p.tiles_m * p.tiles_n;
-    int id;
-    {
-        const int bid = blockIdx.x;
-        const int q = nblocks >> 3, r = nblocks & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    const int group_size = GROUP_M * p.tiles_n;
-    const int group = id / group_size;
-    const int first_m = group * GROUP_M;
-    const int gm = min(p.tiles_m - first_m, GROUP_M);
-    const int in_group = id - group * group_size;
-    const int tile_m = first_m + in_group % gm;
-    const int tile_n = in_group / gm;
-    const int m0 = tile_m * LBM, n0 = tile_n * LBN;
-
-    // staging: pass i covers rows 64*i + 8*wave + (lane>>3); lane's physical chunk is lane&7.  The DMA is the BUFFER
-    // form (buffer_load_dwordx4 ... lds): one resource per operand tile (SGPRs), a per-lane 32-bit byte offset computed
-    // once, and the K-step as the scalar offset -- no 64-bit VALU address arithmetic per piece in the loop.
-    const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc((void*)(p.W + (int64_t)n0 * p.ldw_b), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)(p.A + (int64_t)m0 * p.lda_b), 0, 0x7fffffff, 0x00020000);
-    int oW[4], oA[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int row = 64 * i + 8 * wave + (lane >> 3);
-        const int c = (lane & 7) ^ ((row >> 1) & 7);
-        oW[i] = (min(n0 + row, p.N - 1) - n0) * (int)p.ldw_b + c * 16;
-        oA[i] = (min(m0 + row, p.M - 1) - m0) * (int)p.lda_b + c * 16;
-    }
-    auto stage = [&](int kt, int buf) {
-        const int kb = kt * ROWB;
-        char* base = smem + buf * (2 * LTILE) + wave * (8 * ROWB);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, (lds_ptr_t)(base + i * 64 * ROWB), 16, oW[i], kb, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (lds_ptr_t)(base + LTILE + i * 64 * ROWB), 16, oA[i], kb, 0, 0);
-        }
-    };
+    const TileId tile = tile_id(p);
+    const int m0 = tile.m * LBM, n0 = tile.n * LBN;
+    WIPA_TILE_STAGER(L256);
 
     f32x4 acc[4][8];  // [n tile i][m tile j]
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int frow = lane & 15;
-    const int fsw = (lane >> 1) & 7;
-    const int fq = lane >> 4;
+    WIPA_ZERO_ACC(4, 8);
+    const auto [frow, fsw, fq] = frag_lane(lane);
     const int nk = p.K * (int)sizeof(T) / ROWB;
 
     stage(0, 0);
@@ -1219,147 +1316,7 @@ __global__ __launch_bounds__(512) void gemm_nt256_kernel(GemmParams p) {
         __syncthreads();
     }
 
-    const bool vec = p.vec_ok != 0;
-    int64_t coff_dev = p.c_offset;
-    if (p.c_offset_dev) coff_dev += *p.c_offset_dev;
-    if (p.stage_ok) {  // the last barrier of the K loop has retired every LDS read: reuse it as per-wave scratch
-        epilogue_staged<OutT, 8>(p, acc, smem + wave * 4096, m0 + wm * 128, n0 + wn * 64, coff_dev, lane);
-        return;
-    }
-    EpiCol cols[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) cols[i] = epi_col(p, n0 + wn * 64 + 16 * i + 4 * fq);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const EpiRow row = epi_row(p, m0 + wm * 128 + 16 * j + frow, coff_dev);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) epilogue4<OutT>(p, acc[i][j], row, cols[i], vec);
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// fp8 x fp8 on the block-scaled matrix instruction (BASELINE.json configs[4]: "fp8-weight inference (CDNA4 fp8 MFMA)").
-// Both operands are OCP e4m3fn codes with one power-of-two scale per row: A [M, K] bytes with a_scale[M] (activations
-// quantised by wipa_layernorm_fp8 / wipa_rowquant_fp8), W [N, K] bytes with w_scale[N] (Whisper.quantize_weights).  Same
-// tiling, LDS image and LDS-DMA staging as gemm_nt256_kernel -- the staging moves bytes -- but a 128-byte K-step is now 128
-// elements, i.e. ONE v_mfma_scale_f32_16x16x128_f8f6f4 per 16 x 16 output tile (scale operands 0: the unscaled form, which
-// runs at twice the bf16 rate on gfx950): a lane (row = lane & 15, k-group = lane >> 4) feeds the 32 bytes k = 32 (lane >> 4)
-// ... + 31 of its row, two ds_read_b128.  Half the staged bytes per FLOP of the bf16 kernel, which is what these tile GEMMs
-// are bound by.  The per-row scales are powers of two, so acc * a_scale[m] * w_scale[n] is exact; the rest of the epilogue
-// (bias, column scale, GELU, f32 residual, remaps) is the shared one.
-typedef int v8i32 __attribute__((ext_vector_type(8)));
-typedef int v4i32 __attribute__((ext_vector_type(4)));
-
-template <typename OutT>
-__global__ __launch_bounds__(512) void gemm_fp8_256_kernel(GemmParams p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 buffers][W tile | A tile]
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 2, wn = wave & 3;
-    const int nblocks = p.tiles_m * p.tiles_n;
-    int id;
-    {
-        const int bid = blockIdx.x;
-        const int q = nblocks >> 3, r = nblocks & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    const int group_size = GROUP_M * p.tiles_n;
-    const int group = id / group_size;
-    const int first_m = group * GROUP_M;
-    const int gm = min(p.tiles_m - first_m, GROUP_M);
-    const int in_group = id - group * group_size;
-    const int tile_m = first_m + in_group % gm;
-    const int tile_n = in_group / gm;
-    const int m0 = tile_m * LBM, n0 = tile_n * LBN;
-
-    const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc((void*)(p.W + (int64_t)n0 * p.ldw_b), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)(p.A + (int64_t)m0 * p.lda_b), 0, 0x7fffffff, 0x00020000);
-    int oW[4], oA[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int row = 64 * i + 8 * wave + (lane >> 3);
-        const int c = (lane & 7) ^ ((row >> 1) & 7);
-        oW[i] = (min(n0 + row, p.N - 1) - n0) * (int)p.ldw_b + c * 16;
-        oA[i] = (min(m0 + row, p.M - 1) - m0) * (int)p.lda_b + c * 16;
-    }
-    auto stage = [&](int kt, int buf) {
-        const int kb = kt * ROWB;
-        char* base = smem + buf * (2 * LTILE) + wave * (8 * ROWB);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, (lds_ptr_t)(base + i * 64 * ROWB), 16, oW[i], kb, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (lds_ptr_t)(base + LTILE + i * 64 * ROWB), 16, oA[i], kb, 0, 0);
-        }
-    };
-    f32x4 acc[4][8];  // [n tile i][m tile j]
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int frow = lane & 15;
-    const int fsw = (lane >> 1) & 7;
-    const int fq = lane >> 4;
-    const int nk = p.K / ROWB;  // one byte per element
-    const int c0 = ((2 * fq) ^ fsw) << 4, c1 = ((2 * fq + 1) ^ fsw) << 4;
-    auto frag = [&](const char* row) {
-        const v4i32 lo = *reinterpret_cast<const v4i32*>(row + c0);
-        const v4i32 hi = *reinterpret_cast<const v4i32*>(row + c1);
-        return v8i32{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    };
-    stage(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-        if (kt + 1 < nk) stage(kt + 1, (kt + 1) & 1);
-        const char* wb = smem + (kt & 1) * (2 * LTILE) + (wn * 64 + frow) * ROWB;
-        const char* ab = smem + (kt & 1) * (2 * LTILE) + LTILE + (wm * 128 + frow) * ROWB;
-        v8i32 fw[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) fw[i] = frag(wb + i * 16 * ROWB);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const v8i32 fx = frag(ab + j * 16 * ROWB);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw[i], fx, acc[i][j], 0, 0, 0, 0, 0, 0);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-    // dequantisation: acc[i][j][e] is C[m = m0 + wm*128 + 16 j + frow][n = n0 + wn*64 + 16 i + 4 fq + e]
-    {
-        f32x4 ws[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int n = n0 + wn * 64 + 16 * i + 4 * fq;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ws[i][e] = p.w_scale[min(n + e, p.N - 1)];
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float as = p.a_scale[min(m0 + wm * 128 + 16 * j + frow, p.M - 1)];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i][j] *= ws[i] * as;
-        }
-    }
-    const bool vec = p.vec_ok != 0;
-    int64_t coff_dev = p.c_offset;
-    if (p.c_offset_dev) coff_dev += *p.c_offset_dev;
-    if (p.stage_ok) {
-        epilogue_staged<OutT, 8>(p, acc, smem + wave * 4096, m0 + wm * 128, n0 + wn * 64, coff_dev, lane);
-        return;
-    }
-    EpiCol cols[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) cols[i] = epi_col(p, n0 + wn * 64 + 16 * i + 4 * fq);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const EpiRow row = epi_row(p, m0 + wm * 128 + 16 * j + frow, coff_dev);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) epilogue4<OutT>(p, acc[i][j], row, cols[i], vec);
-    }
+    WIPA_STORE_TILE(OutT, 8, GELU_IN_EPILOGUE, false, m0 + wm * 128, n0 + wn * 64)
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1388,25 +1345,10 @@ __global__ __launch_bounds__(512) void gemm_nt256p_kernel(GemmParams p) {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
-    const int nblocks = p.tiles_m * p.tiles_n;
-    int id;
-    {
-        const int bid = blockIdx.x;
-        const int q = nblocks >> 3, r = nblocks & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    const int group_size = GROUP_M * p.tiles_n;
-    const int group = id / group_size;
-    const int first_m = group * GROUP_M;
-    const int gm = min(p.tiles_m - first_m, GROUP_M);
-    const int in_group = id - group * group_size;
-    const int tile_m = first_m + in_group % gm;
-    const int tile_n = in_group / gm;
-    const int m0 = tile_m * LBM, n0 = tile_n * LBN;
-
-    const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc((void*)(p.W + (int64_t)n0 * p.ldw_b), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)(p.A + (int64_t)m0 * p.lda_b), 0, 0x7fffffff, 0x00020000);
+    const TileId tile = tile_id(p);
+    const int m0 = tile.m * LBM, n0 = tile.n * LBN;
+    const __amdgpu_buffer_rsrc_t rW = tile_rsrc(p.W, n0, p.ldw_b);
+    const __amdgpu_buffer_rsrc_t rA = tile_rsrc(p.A, m0, p.lda_b);
     // DMA pieces (8 rows x 128 B per wave instruction).  A half x, piece s: rows 128 s + 64 x + 8 wave + (lane >> 3).
     // W half y, piece s: rows 128 s + 64 (wave >> 2) + 32 y + 8 (wave & 3) + (lane >> 3).
     int oA[2][2], oW[2][2];
@@ -1416,8 +1358,8 @@ __global__ __launch_bounds__(512) void gemm_nt256p_kernel(GemmParams p) {
         for (int sp = 0; sp < 2; ++sp) {
             const int ra = 128 * sp + 64 * h + 8 * wave + (lane >> 3);
             const int rw = 128 * sp + 64 * (wave >> 2) + 32 * h + 8 * (wave & 3) + (lane >> 3);
-            oA[h][sp] = (min(m0 + ra, p.M - 1) - m0) * (int)p.lda_b + (((lane & 7) ^ ((ra >> 1) & 7)) << 4);
-            oW[h][sp] = (min(n0 + rw, p.N - 1) - n0) * (int)p.ldw_b + (((lane & 7) ^ ((rw >> 1) & 7)) << 4);
+            oA[h][sp] = dma_offset(ra, lane, m0, p.M, p.lda_b);
+            oW[h][sp] = dma_offset(rw, lane, n0, p.N, p.ldw_b);
         }
     const int rowA = 8 * wave, rowW = 64 * (wave >> 2) + 8 * (wave & 3);  // wave-uniform first rows of the pieces (+ 128 s + 64 x / 32 y)
     auto stage_a = [&](int h, int kt, int buf) {
@@ -1432,13 +1374,8 @@ __global__ __launch_bounds__(512) void gemm_nt256p_kernel(GemmParams p) {
     };
 
     f32x4 acc[4][8];  // [n tile i][m tile j]
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int frow = lane & 15;
-    const int fsw = (lane >> 1) & 7;
-    const int fq = lane >> 4;
+    WIPA_ZERO_ACC(4, 8);
+    const auto [frow, fsw, fq] = frag_lane(lane);
     const int c0 = (fq ^ fsw) << 4, c1 = ((fq + 4) ^ fsw) << 4;
     const int nk = p.K * (int)sizeof(T) / ROWB;  // even (dispatcher)
     const char* wfrag = smem + (wn * 64 + frow) * ROWB;
@@ -1521,22 +1458,7 @@ __global__ __launch_bounds__(512) void gemm_nt256p_kernel(GemmParams p) {
 #undef WIPA_VMCNT
     __syncthreads();  // every LDS read has retired: the epilogue reuses the buffers as per-wave scratch
 
-    const bool vec = p.vec_ok != 0;
-    int64_t coff_dev = p.c_offset;
-    if (p.c_offset_dev) coff_dev += *p.c_offset_dev;
-    if (p.stage_ok) {
-        epilogue_staged<OutT, 8>(p, acc, smem + wave * 4096, m0 + wm * 128, n0 + wn * 64, coff_dev, lane);
-        return;
-    }
-    EpiCol cols[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) cols[i] = epi_col(p, n0 + wn * 64 + 16 * i + 4 * fq);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const EpiRow row = epi_row(p, m0 + wm * 128 + 16 * j + frow, coff_dev);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) epilogue4<OutT>(p, acc[i][j], row, cols[i], vec);
-    }
+    WIPA_STORE_TILE(OutT, 8, GELU_IN_EPILOGUE, false, m0 + wm * 128, n0 + wn * 64)
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1547,15 +1469,8 @@ __global__ __launch_bounds__(512) void gemm_nt256p_kernel(GemmParams p) {
 // quantises badly on 256 CUs: the float32 encoder of a 32-clip fine-tune batch (48 000 x 768) is 375 wide tiles = 1.46 rounds
 // but 750 narrow ones = 2.93, and the f32 MFMA is slow enough that the extra staged bytes per FLOP do not show.
 constexpr int XBM = 384;
-constexpr int XA_TILE = XBM * ROWB;  // 48 KiB
 template <int WN>
-struct X384 {
-    static constexpr int BN = 64 * WN;            // 256 | 128 columns
-    static constexpr int MT = 12 * WN / 4;        // 16-row slices per wave: 12 | 6
-    static constexpr int W_TILE = BN * ROWB;      // 32 | 16 KiB
-    static constexpr int STAGE = W_TILE + XA_TILE;  // 80 | 64 KiB
-    static constexpr int SMEM = 2 * STAGE;          // 160 | 128 KiB
-};
+using X384 = TileGeom<XBM, 64 * WN, false>;  // 256 | 128 columns, 12 | 6 row slices per wave, stage 80 | 64 KiB, LDS 160 | 128 KiB
 
 template <typename T, typename OutT, bool ACT, bool SPLIT, int WN>  // SPLIT (f32 inputs only): products as three bf16 MFMA terms
 __device__ __forceinline__ void gemm_nt384_body(GemmParams p) {
@@ -1566,50 +1481,12 @@ __device__ __forceinline__ void gemm_nt384_body(GemmParams p) {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
-    const int nblocks = p.tiles_m * p.tiles_n;
-    int id;
-    {
-        const int bid = blockIdx.x;
-        const int q = nblocks >> 3, r = nblocks & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    const int group_size = GROUP_M * p.tiles_n;
-    const int group = id / group_size;
-    const int first_m = group * GROUP_M;
-    const int gm = min(p.tiles_m - first_m, GROUP_M);
-    const int in_group = id - group * group_size;
-    const int tile_m = first_m + in_group % gm;
-    const int tile_n = in_group / gm;
-    const int m0 = tile_m * XBM, n0 = tile_n * X::BN;
-
-    const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc((void*)(p.W + (int64_t)n0 * p.ldw_b), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)(p.A + (int64_t)m0 * p.lda_b), 0, 0x7fffffff, 0x00020000);
-    int oW[WN], oA[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        const int row = 64 * i + 8 * wave + (lane >> 3);
-        const int c = (lane & 7) ^ ((row >> 1) & 7);
-        if (i < WN) oW[i] = (min(n0 + row, p.N - 1) - n0) * (int)p.ldw_b + c * 16;
-        oA[i] = (min(m0 + row, p.M - 1) - m0) * (int)p.lda_b + c * 16;
-    }
-    auto stage = [&](int kt, int buf) {
-        const int kb = kt * ROWB;
-        char* base = smem + buf * XSTAGE + wave * (8 * ROWB);
-#pragma unroll
-        for (int i = 0; i < WN; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, (lds_ptr_t)(base + i * 64 * ROWB), 16, oW[i], kb, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 6; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (lds_ptr_t)(base + XW_TILE + i * 64 * ROWB), 16, oA[i], kb, 0, 0);
-    };
+    const TileId tile = tile_id(p);
+    const int m0 = tile.m * XBM, n0 = tile.n * X::BN;
+    WIPA_TILE_STAGER(X);
     f32x4 acc[4][MT];  // [n tile i][m tile j]
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < MT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int frow = lane & 15;
-    const int fsw = (lane >> 1) & 7;
-    const int fq = lane >> 4;
+    WIPA_ZERO_ACC(4, MT);
+    const auto [frow, fsw, fq] = frag_lane(lane);
     const int nk = p.K * (int)sizeof(T) / ROWB;
     stage(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1684,42 +1561,7 @@ __device__ __forceinline__ void gemm_nt384_body(GemmParams p) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
-    const bool vec = p.vec_ok != 0;
-    int64_t coff_dev = p.c_offset;
-    if (p.c_offset_dev) coff_dev += *p.c_offset_dev;
-    if (p.stage_ok) {
-        if constexpr (ACT) {
-            // GELU on the MFMA layout, in place and BEFORE the transposing epilogue (which is compiled without its GELU path:
-            // 192 accumulators + those temporaries would spill).  A lane holds columns n0 + 64 wn + 16 i + 4 fq + (0..3).
-            // The dispatcher sends an activation here only with a plain column bias and no column scale.
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int n = n0 + wn * 64 + 16 * i + 4 * fq;
-                float b4[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) b4[e] = (p.bias && n + e < p.N) ? p.bias[n + e] : 0.f;
-#pragma unroll
-                for (int j = 0; j < MT; ++j) {
-                    const f32x2 g0 = gelu_erf2(f32x2{acc[i][j][0] + b4[0], acc[i][j][1] + b4[1]});
-                    const f32x2 g1 = gelu_erf2(f32x2{acc[i][j][2] + b4[2], acc[i][j][3] + b4[3]});
-                    acc[i][j] = f32x4{g0.x, g0.y, g1.x, g1.y};
-                    __builtin_amdgcn_sched_barrier(0);  // one tile at a time: the scheduler would otherwise overlap all 48 and spill
-                }
-            }
-            p.bias = nullptr;
-        }
-        epilogue_staged<OutT, MT, 0, MT, false, !ACT>(p, acc, smem + wave * 4096, m0 + wm * (16 * MT), n0 + wn * 64, coff_dev, lane);
-        return;
-    }
-    EpiCol cols[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) cols[i] = epi_col(p, n0 + wn * 64 + 16 * i + 4 * fq);
-#pragma unroll
-    for (int j = 0; j < MT; ++j) {
-        const EpiRow row = epi_row(p, m0 + wm * (16 * MT) + 16 * j + frow, coff_dev);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) epilogue4<OutT>(p, acc[i][j], row, cols[i], vec);
-    }
+    WIPA_STORE_TILE(OutT, MT, ACT ? GELU_FIRST : GELU_NONE, false, m0 + wm * (16 * MT), n0 + wn * 64)
 }
 
 template <typename T, typename OutT, bool ACT, bool SPLIT>
@@ -1731,78 +1573,46 @@ __global__ __launch_bounds__(512) void gemm_nt384n_kernel(GemmParams p) {  // 38
     gemm_nt384_body<T, OutT, ACT, SPLIT, 2>(p);
 }
 
-// fp8 x fp8 on the 384 x 256 tile (round 4): gemm_fp8_256_kernel's arithmetic -- one
-// v_mfma_scale_f32_16x16x128_f8f6f4 per 16 x 16 output tile and 128-byte K-step, a fragment = two ds_read_b128 -- in
-// gemm_nt384_body's geometry (8 waves 2 x 4, 192 x 64 per wave, 192 accumulators, (256 + 384) x 128 B = 80 KiB per stage):
-// 1/307 staged byte per FLOP instead of 1/256, and N = 1280 / 5120 grids quantise as for the bf16 kernel.  ACT: bias + GELU on
-// the MFMA layout before the transposing epilogue (compiled without its GELU path, like the bf16 instantiation).
-template <typename OutT, bool ACT>
-__global__ __launch_bounds__(512) void gemm_fp8_384_kernel(GemmParams p) {
-    typedef X384<4> X;
-    constexpr int MT = X::MT, XW_TILE = X::W_TILE, XSTAGE = X::STAGE;
-    extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 buffers][W tile 256 rows | A tile 384 rows]
+// ---------------------------------------------------------------------------------------
+// fp8 x fp8 on the block-scaled matrix instruction (BASELINE.json configs[4]: "fp8-weight inference (CDNA4 fp8 MFMA)").
+// Both operands are OCP e4m3fn codes with one power-of-two scale per row: A [M, K] bytes with a_scale[M] (activations
+// quantised by wipa_layernorm_fp8 / wipa_rowquant_fp8), W [N, K] bytes with w_scale[N] (Whisper.quantize_weights).  Same
+// tiling, LDS image and LDS-DMA staging as gemm_nt256_kernel -- the staging moves bytes -- but a 128-byte K-step is now 128
+// elements, i.e. ONE v_mfma_scale_f32_16x16x128_f8f6f4 per 16 x 16 output tile (scale operands 0: the unscaled form, which
+// runs at twice the bf16 rate on gfx950), fed by WIPA_FP8_FRAG.  Half the staged bytes per FLOP of the bf16 kernel, which is what
+// these tile GEMMs are bound by.  After WIPA_DEQUANT_FP8 the rest of the epilogue (bias, column scale, GELU, f32 residual, remaps)
+// is the shared one.
+//
+// The same arithmetic on the 384 x 256 tile (round 4) in gemm_nt384_body's geometry (8 waves 2 x 4, 192 x 64 per
+// wave, 192 accumulators, (256 + 384) x 128 B = 80 KiB per stage): 1/307 staged byte per FLOP instead of 1/256, and N = 1280 /
+// 5120 grids quantise as for the bf16 kernel.  ACT (that tile only): bias + GELU on the MFMA layout before the transposing
+// epilogue (compiled without its GELU path, like the bf16 instantiation); the dispatcher sends only stage_ok outputs there.
+// Two kernels with the same K loop text: behind one __forceinline__ body (as gemm_nt384_body sits behind its two kernels) the
+// 256 x 256 kernel compiled to other code (10 more VGPRs), so each keeps its own body built from the shared pieces.
+template <typename OutT>
+__global__ __launch_bounds__(512) void gemm_fp8_256_kernel(GemmParams p) {
+    typedef L256 G;
+    constexpr int MT = G::MT;
+    extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 buffers][W tile | A tile]
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
-    const int nblocks = p.tiles_m * p.tiles_n;
-    int id;
-    {
-        const int bid = blockIdx.x;
-        const int q = nblocks >> 3, r = nblocks & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    const int group_size = GROUP_M * p.tiles_n;
-    const int group = id / group_size;
-    const int first_m = group * GROUP_M;
-    const int gm = min(p.tiles_m - first_m, GROUP_M);
-    const int in_group = id - group * group_size;
-    const int tile_m = first_m + in_group % gm;
-    const int tile_n = in_group / gm;
-    const int m0 = tile_m * XBM, n0 = tile_n * X::BN;
-
-    const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc((void*)(p.W + (int64_t)n0 * p.ldw_b), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)(p.A + (int64_t)m0 * p.lda_b), 0, 0x7fffffff, 0x00020000);
-    int oW[4], oA[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        const int row = 64 * i + 8 * wave + (lane >> 3);
-        const int c = (lane & 7) ^ ((row >> 1) & 7);
-        if (i < 4) oW[i] = (min(n0 + row, p.N - 1) - n0) * (int)p.ldw_b + c * 16;
-        oA[i] = (min(m0 + row, p.M - 1) - m0) * (int)p.lda_b + c * 16;
-    }
-    auto stage = [&](int kt, int buf) {
-        const int kb = kt * ROWB;
-        char* base = smem + buf * XSTAGE + wave * (8 * ROWB);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, (lds_ptr_t)(base + i * 64 * ROWB), 16, oW[i], kb, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 6; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (lds_ptr_t)(base + XW_TILE + i * 64 * ROWB), 16, oA[i], kb, 0, 0);
-    };
+    const TileId tile = tile_id(p);
+    const int m0 = tile.m * G::BM, n0 = tile.n * G::BN;
+    WIPA_TILE_STAGER(G);
     f32x4 acc[4][MT];  // [n tile i][m tile j]
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < MT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int frow = lane & 15;
-    const int fsw = (lane >> 1) & 7;
-    const int fq = lane >> 4;
+    WIPA_ZERO_ACC(4, MT);
+    const auto [frow, fsw, fq] = frag_lane(lane);
     const int nk = p.K / ROWB;  // one byte per element
-    const int c0 = ((2 * fq) ^ fsw) << 4, c1 = ((2 * fq + 1) ^ fsw) << 4;
-    auto frag = [&](const char* row) {
-        const v4i32 lo = *reinterpret_cast<const v4i32*>(row + c0);
-        const v4i32 hi = *reinterpret_cast<const v4i32*>(row + c1);
-        return v8i32{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    };
+    WIPA_FP8_FRAG();
     stage(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     for (int kt = 0; kt < nk; ++kt) {
         if (kt + 1 < nk) stage(kt + 1, (kt + 1) & 1);
-        const char* wb = smem + (kt & 1) * XSTAGE + (wn * 64 + frow) * ROWB;
-        const char* ab = smem + (kt & 1) * XSTAGE + XW_TILE + (wm * (16 * MT) + frow) * ROWB;
+        const char* wb = smem + (kt & 1) * G::STAGE + (wn * 64 + frow) * ROWB;
+        const char* ab = smem + (kt & 1) * G::STAGE + G::W_TILE + (wm * (16 * MT) + frow) * ROWB;
         v8i32 fw[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) fw[i] = frag(wb + i * 16 * ROWB);
@@ -1816,130 +1626,80 @@ __global__ __launch_bounds__(512) void gemm_fp8_384_kernel(GemmParams p) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
-    // dequantisation: acc[i][j][e] is C[m = m0 + wm*192 + 16 j + frow][n = n0 + wn*64 + 16 i + 4 fq + e]
-    {
-        f32x4 ws[4];
+    WIPA_DEQUANT_FP8(MT, m0 + wm * (16 * MT), n0 + wn * 64)
+    WIPA_STORE_TILE(OutT, MT, GELU_IN_EPILOGUE, false, m0 + wm * (16 * MT), n0 + wn * 64)
+}
+
+template <typename OutT, bool ACT>
+__global__ __launch_bounds__(512) void gemm_fp8_384_kernel(GemmParams p) {
+    typedef X384<4> G;
+    constexpr int MT = G::MT;
+    extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 buffers][W tile | A tile]
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 2, wn = wave & 3;
+    const TileId tile = tile_id(p);
+    const int m0 = tile.m * G::BM, n0 = tile.n * G::BN;
+    WIPA_TILE_STAGER(G);
+    f32x4 acc[4][MT];  // [n tile i][m tile j]
+    WIPA_ZERO_ACC(4, MT);
+    const auto [frow, fsw, fq] = frag_lane(lane);
+    const int nk = p.K / ROWB;  // one byte per element
+    WIPA_FP8_FRAG();
+    stage(0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int kt = 0; kt < nk; ++kt) {
+        if (kt + 1 < nk) stage(kt + 1, (kt + 1) & 1);
+        const char* wb = smem + (kt & 1) * G::STAGE + (wn * 64 + frow) * ROWB;
+        const char* ab = smem + (kt & 1) * G::STAGE + G::W_TILE + (wm * (16 * MT) + frow) * ROWB;
+        v8i32 fw[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int n = n0 + wn * 64 + 16 * i + 4 * fq;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ws[i][e] = p.w_scale[min(n + e, p.N - 1)];
-        }
+        for (int i = 0; i < 4; ++i) fw[i] = frag(wb + i * 16 * ROWB);
 #pragma unroll
         for (int j = 0; j < MT; ++j) {
-            const float as = p.a_scale[min(m0 + wm * (16 * MT) + 16 * j + frow, p.M - 1)];
+            const v8i32 fx = frag(ab + j * 16 * ROWB);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i][j] *= ws[i] * as;
+            for (int i = 0; i < 4; ++i)
+                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw[i], fx, acc[i][j], 0, 0, 0, 0, 0, 0);
         }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
     }
-    int64_t coff_dev = p.c_offset;
-    if (p.c_offset_dev) coff_dev += *p.c_offset_dev;
-    // the dispatcher sends only stage_ok outputs here (and an activation only with a plain column bias and no column scale)
-    if constexpr (ACT) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int n = n0 + wn * 64 + 16 * i + 4 * fq;
-            float b4[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) b4[e] = (p.bias && n + e < p.N) ? p.bias[n + e] : 0.f;
-#pragma unroll
-            for (int j = 0; j < MT; ++j) {
-                const f32x2 g0 = gelu_erf2(f32x2{acc[i][j][0] + b4[0], acc[i][j][1] + b4[1]});
-                const f32x2 g1 = gelu_erf2(f32x2{acc[i][j][2] + b4[2], acc[i][j][3] + b4[3]});
-                acc[i][j] = f32x4{g0.x, g0.y, g1.x, g1.y};
-                __builtin_amdgcn_sched_barrier(0);  // one tile at a time (see gemm_nt384_body)
-            }
-        }
-        p.bias = nullptr;
-    }
-    epilogue_staged<OutT, MT, 0, MT, false, !ACT>(p, acc, smem + wave * 4096, m0 + wm * (16 * MT), n0 + wn * 64, coff_dev, lane);
+    WIPA_DEQUANT_FP8(MT, m0 + wm * (16 * MT), n0 + wn * 64)
+    WIPA_STORE_TILE(OutT, MT, ACT ? GELU_FIRST : GELU_NONE, true, m0 + wm * (16 * MT), n0 + wn * 64)
 }
 
-template <typename T, typename OutT>
-int launch384(GemmParams p, hipStream_t s) {
-    typedef X384<4> X;
-    p.tiles_m = (p.M + XBM - 1) / XBM;
-    p.tiles_n = (p.N + X::BN - 1) / X::BN;
-    const dim3 grid(p.tiles_m * p.tiles_n);
+// Launch of an LDS-DMA tile kernel: one 512-thread workgroup per G::BM x G::BN tile, all of G's LDS.
+typedef void (*TileKernel)(GemmParams);
+template <typename G>
+int launch_tile(TileKernel kernel, GemmParams p, hipStream_t s) {
+    p.tiles_m = (p.M + G::BM - 1) / G::BM;
+    p.tiles_n = (p.N + G::BN - 1) / G::BN;
+    hipLaunchKernelGGL(kernel, dim3(p.tiles_m * p.tiles_n), dim3(512), G::SMEM, s, p);
+    WIPA_LAUNCH_CHECK();
+    return WIPA_OK;
+}
+
+template <typename T, typename OutT, bool ACT, bool SPLIT, int WN>
+constexpr TileKernel nt384() {
+    if constexpr (WN == 4) return gemm_nt384_kernel<T, OutT, ACT, SPLIT>;
+    else return gemm_nt384n_kernel<T, OutT, ACT, SPLIT>;
+}
+template <typename T, typename OutT, int WN>  // WN = 4: 384 x 256, WN = 2: 384 x 128
+int launch384(const GemmParams& p, hipStream_t s) {
     const bool act = p.act == 1 && p.stage_ok;
     if constexpr (sizeof(T) == 4) {
-        if (p.f32_split) {
-            if (act) hipLaunchKernelGGL((gemm_nt384_kernel<T, OutT, true, true>), grid, dim3(512), X::SMEM, s, p);
-            else hipLaunchKernelGGL((gemm_nt384_kernel<T, OutT, false, true>), grid, dim3(512), X::SMEM, s, p);
-            WIPA_LAUNCH_CHECK();
-            return WIPA_OK;
-        }
+        if (p.f32_split) return launch_tile<X384<WN>>(act ? nt384<T, OutT, true, true, WN>() : nt384<T, OutT, false, true, WN>(), p, s);
     }
-    if (act)
-        hipLaunchKernelGGL((gemm_nt384_kernel<T, OutT, true, false>), grid, dim3(512), X::SMEM, s, p);
-    else
-        hipLaunchKernelGGL((gemm_nt384_kernel<T, OutT, false, false>), grid, dim3(512), X::SMEM, s, p);
-    WIPA_LAUNCH_CHECK();
-    return WIPA_OK;
+    return launch_tile<X384<WN>>(act ? nt384<T, OutT, true, false, WN>() : nt384<T, OutT, false, false, WN>(), p, s);
 }
 
 template <typename T, typename OutT>
-int launch384n(GemmParams p, hipStream_t s) {
-    typedef X384<2> X;
-    p.tiles_m = (p.M + XBM - 1) / XBM;
-    p.tiles_n = (p.N + X::BN - 1) / X::BN;
-    const dim3 grid(p.tiles_m * p.tiles_n);
-    const bool act = p.act == 1 && p.stage_ok;
-    if constexpr (sizeof(T) == 4) {
-        if (p.f32_split) {
-            if (act) hipLaunchKernelGGL((gemm_nt384n_kernel<T, OutT, true, true>), grid, dim3(512), X::SMEM, s, p);
-            else hipLaunchKernelGGL((gemm_nt384n_kernel<T, OutT, false, true>), grid, dim3(512), X::SMEM, s, p);
-            WIPA_LAUNCH_CHECK();
-            return WIPA_OK;
-        }
-    }
-    if (act)
-        hipLaunchKernelGGL((gemm_nt384n_kernel<T, OutT, true, false>), grid, dim3(512), X::SMEM, s, p);
-    else
-        hipLaunchKernelGGL((gemm_nt384n_kernel<T, OutT, false, false>), grid, dim3(512), X::SMEM, s, p);
-    WIPA_LAUNCH_CHECK();
-    return WIPA_OK;
-}
-
-template <typename OutT>
-int launch256p(GemmParams p, hipStream_t s) {
-    p.tiles_m = (p.M + LBM - 1) / LBM;
-    p.tiles_n = (p.N + LBN - 1) / LBN;
-    hipLaunchKernelGGL((gemm_nt256p_kernel<OutT>), dim3(p.tiles_m * p.tiles_n), dim3(512), LSMEM, s, p);
-    WIPA_LAUNCH_CHECK();
-    return WIPA_OK;
-}
-
-template <typename T, typename OutT>
-int launch256(GemmParams p, hipStream_t s) {
-    p.tiles_m = (p.M + LBM - 1) / LBM;
-    p.tiles_n = (p.N + LBN - 1) / LBN;
-    if (sizeof(T) == 4 && p.f32_split)
-        hipLaunchKernelGGL((gemm_nt256_kernel<T, OutT, sizeof(T) == 4>), dim3(p.tiles_m * p.tiles_n), dim3(512), LSMEM, s, p);
-    else
-        hipLaunchKernelGGL((gemm_nt256_kernel<T, OutT, false>), dim3(p.tiles_m * p.tiles_n), dim3(512), LSMEM, s, p);
-    WIPA_LAUNCH_CHECK();
-    return WIPA_OK;
-}
-
-template <typename OutT>
-int launch_fp8_256(GemmParams p, hipStream_t s) {
-    p.tiles_m = (p.M + LBM - 1) / LBM;
-    p.tiles_n = (p.N + LBN - 1) / LBN;
-    hipLaunchKernelGGL((gemm_fp8_256_kernel<OutT>), dim3(p.tiles_m * p.tiles_n), dim3(512), LSMEM, s, p);
-    WIPA_LAUNCH_CHECK();
-    return WIPA_OK;
-}
-
-template <typename OutT>
-int launch_fp8_384(GemmParams p, hipStream_t s) {
-    typedef X384<4> X;
-    p.tiles_m = (p.M + XBM - 1) / XBM;
-    p.tiles_n = (p.N + X::BN - 1) / X::BN;
-    if (p.act == 1) hipLaunchKernelGGL((gemm_fp8_384_kernel<OutT, true>), dim3(p.tiles_m * p.tiles_n), dim3(512), X::SMEM, s, p);
-    else hipLaunchKernelGGL((gemm_fp8_384_kernel<OutT, false>), dim3(p.tiles_m * p.tiles_n), dim3(512), X::SMEM, s, p);
-    WIPA_LAUNCH_CHECK();
-    return WIPA_OK;
+int launch256(const GemmParams& p, hipStream_t s) {
+    const bool split = sizeof(T) == 4 && p.f32_split;
+    return launch_tile<L256>(split ? gemm_nt256_kernel<T, OutT, sizeof(T) == 4> : gemm_nt256_kernel<T, OutT, false>, p, s);
 }
 
 constexpr int SMEM_BYTES = 4 * TILE_BYTES;  // 64 KiB
@@ -1949,98 +1709,79 @@ int init_attrs() {
     static std::once_flag once;
     static hipError_t err = hipSuccess;
     std::call_once(once, [] {
-        const void* fns[7] = {reinterpret_cast<const void*>(&gemm_nt_kernel<__bf16, __bf16>),
-                              reinterpret_cast<const void*>(&gemm_nt_kernel<__bf16, float>),
-                              reinterpret_cast<const void*>(&gemm_nt_kernel<float, __bf16>),
-                              reinterpret_cast<const void*>(&gemm_nt_kernel<float, float>),
-                              reinterpret_cast<const void*>(&gemm_nt_kernel<float, float, true, true>),
-                              reinterpret_cast<const void*>(&gemm_nt_kernel<float, float, true, false>),
-                              reinterpret_cast<const void*>(&gemm_nt_kernel<float, float, false, true>)};
-        for (const void* f : fns) {
-            const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-            if (e != hipSuccess) err = e;
-        }
-        const void* phased[2] = {reinterpret_cast<const void*>(&gemm_nt256p_kernel<__bf16>),
-                                 reinterpret_cast<const void*>(&gemm_nt256p_kernel<float>)};
-        for (const void* f : phased) {
-            const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LSMEM);
-            if (e != hipSuccess) err = e;
-        }
-        const void* big[6] = {reinterpret_cast<const void*>(&gemm_nt256_kernel<__bf16, __bf16, false>),
-                              reinterpret_cast<const void*>(&gemm_nt256_kernel<__bf16, float, false>),
-                              reinterpret_cast<const void*>(&gemm_nt256_kernel<float, __bf16, false>),
-                              reinterpret_cast<const void*>(&gemm_nt256_kernel<float, float, false>),
-                              reinterpret_cast<const void*>(&gemm_nt256_kernel<float, __bf16, true>),
-                              reinterpret_cast<const void*>(&gemm_nt256_kernel<float, float, true>)};
-        for (const void* f : big) {
-            const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LSMEM);
-            if (e != hipSuccess) err = e;
-        }
-        const void* wide[20] = {reinterpret_cast<const void*>(&gemm_nt384_kernel<__bf16, __bf16, false, false>),
-                                reinterpret_cast<const void*>(&gemm_nt384_kernel<__bf16, float, false, false>),
-                                reinterpret_cast<const void*>(&gemm_nt384_kernel<float, __bf16, false, false>),
-                                reinterpret_cast<const void*>(&gemm_nt384_kernel<float, float, false, false>),
-                                reinterpret_cast<const void*>(&gemm_nt384_kernel<__bf16, __bf16, true, false>),
-                                reinterpret_cast<const void*>(&gemm_nt384_kernel<__bf16, float, true, false>),
-                                reinterpret_cast<const void*>(&gemm_nt384_kernel<float, __bf16, true, false>),
-                                reinterpret_cast<const void*>(&gemm_nt384_kernel<float, float, true, false>),
-                                reinterpret_cast<const void*>(&gemm_nt384_kernel<float, __bf16, false, true>),
-                                reinterpret_cast<const void*>(&gemm_nt384_kernel<float, float, false, true>),
-                                reinterpret_cast<const void*>(&gemm_nt384_kernel<float, __bf16, true, true>),
-                                reinterpret_cast<const void*>(&gemm_nt384_kernel<float, float, true, true>),
-                                reinterpret_cast<const void*>(&gemm_nt384n_kernel<float, __bf16, false, false>),
-                                reinterpret_cast<const void*>(&gemm_nt384n_kernel<float, float, false, false>),
-                                reinterpret_cast<const void*>(&gemm_nt384n_kernel<float, __bf16, true, false>),
-                                reinterpret_cast<const void*>(&gemm_nt384n_kernel<float, float, true, false>),
-                                reinterpret_cast<const void*>(&gemm_nt384n_kernel<float, __bf16, false, true>),
-                                reinterpret_cast<const void*>(&gemm_nt384n_kernel<float, float, false, true>),
-                                reinterpret_cast<const void*>(&gemm_nt384n_kernel<float, __bf16, true, true>),
-                                reinterpret_cast<const void*>(&gemm_nt384n_kernel<float, float, true, true>)};
-        for (int i = 0; i < 20; ++i) {
-            const hipError_t e = hipFuncSetAttribute(wide[i], hipFuncAttributeMaxDynamicSharedMemorySize, i < 12 ? X384<4>::SMEM : X384<2>::SMEM);
-            if (e != hipSuccess) err = e;
-        }
-        const void* f8k[2] = {reinterpret_cast<const void*>(&gemm_fp8_256_kernel<__bf16>),
-                              reinterpret_cast<const void*>(&gemm_fp8_256_kernel<float>)};
-        for (const void* f : f8k) {
-            const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LSMEM);
-            if (e != hipSuccess) err = e;
-        }
-        const void* f8w[4] = {reinterpret_cast<const void*>(&gemm_fp8_384_kernel<__bf16, false>),
-                              reinterpret_cast<const void*>(&gemm_fp8_384_kernel<float, false>),
-                              reinterpret_cast<const void*>(&gemm_fp8_384_kernel<__bf16, true>),
-                              reinterpret_cast<const void*>(&gemm_fp8_384_kernel<float, true>)};
-        for (const void* f : f8w) {
-            const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, X384<4>::SMEM);
-            if (e != hipSuccess) err = e;
-        }
-        const void* lnk[9] = {reinterpret_cast<const void*>(&gemm_skinny_ln_kernel<__bf16, __bf16, 1>),
-                              reinterpret_cast<const void*>(&gemm_skinny_ln_kernel<__bf16, __bf16, 2>),
-                              reinterpret_cast<const void*>(&gemm_skinny_ln_kernel<__bf16, __bf16, 4>),
-                              reinterpret_cast<const void*>(&gemm_skinny_ln_kernel<__bf16, float, 1>),
-                              reinterpret_cast<const void*>(&gemm_skinny_ln_kernel<__bf16, float, 2>),
-                              reinterpret_cast<const void*>(&gemm_skinny_ln_kernel<__bf16, float, 4>),
-                              reinterpret_cast<const void*>(&gemm_skinny_ln_kernel<float, float, 1>),
-                              reinterpret_cast<const void*>(&gemm_skinny_ln_kernel<float, float, 2>),
-                              reinterpret_cast<const void*>(&gemm_skinny_ln_kernel<float, float, 4>)};
-        for (const void* f : lnk) {
-            const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-            if (e != hipSuccess) err = e;
-        }
-        const void* widek[] = {reinterpret_cast<const void*>(&gemm_wide_persistent_kernel<float, 12>),
-                               reinterpret_cast<const void*>(&gemm_wide_persistent_kernel<float, 16>),
-                               reinterpret_cast<const void*>(&gemm_wide_persistent_kernel<float, 24>),
-                               reinterpret_cast<const void*>(&gemm_wide_persistent_kernel<float, 32>),
-                               reinterpret_cast<const void*>(&gemm_wide_persistent_kernel<__bf16, 12>),
-                               reinterpret_cast<const void*>(&gemm_wide_persistent_kernel<__bf16, 16>),
-                               reinterpret_cast<const void*>(&gemm_wide_persistent_kernel<__bf16, 24>),
-                               reinterpret_cast<const void*>(&gemm_wide_persistent_kernel<__bf16, 32>),
-                               reinterpret_cast<const void*>(&gemm_wide_persistent_kernel<float, 12, true>),
-                               reinterpret_cast<const void*>(&gemm_wide_persistent_kernel<float, 16, true>),
-                               reinterpret_cast<const void*>(&gemm_wide_persistent_kernel<float, 24, true>),
-                               reinterpret_cast<const void*>(&gemm_wide_persistent_kernel<float, 32, true>)};
-        for (const void* f : widek) {
-            const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * (1024 + 8) * 2);
+        constexpr int X4 = X384<4>::SMEM, X2 = X384<2>::SMEM, LN = 144 * 1024, WIDE = 64 * (1024 + 8) * 2;
+#define WIPA_K(lds, ...) {reinterpret_cast<const void*>(&__VA_ARGS__), lds}
+        const struct {
+            const void* fn;
+            int lds;
+        } table[] = {
+            WIPA_K(SMEM_BYTES, gemm_nt_kernel<__bf16, __bf16>),
+            WIPA_K(SMEM_BYTES, gemm_nt_kernel<__bf16, float>),
+            WIPA_K(SMEM_BYTES, gemm_nt_kernel<float, __bf16>),
+            WIPA_K(SMEM_BYTES, gemm_nt_kernel<float, float>),
+            WIPA_K(SMEM_BYTES, gemm_nt_kernel<float, float, true, true>),
+            WIPA_K(SMEM_BYTES, gemm_nt_kernel<float, float, true, false>),
+            WIPA_K(SMEM_BYTES, gemm_nt_kernel<float, float, false, true>),
+            WIPA_K(LSMEM, gemm_nt256p_kernel<__bf16>),
+            WIPA_K(LSMEM, gemm_nt256p_kernel<float>),
+            WIPA_K(LSMEM, gemm_nt256_kernel<__bf16, __bf16, false>),
+            WIPA_K(LSMEM, gemm_nt256_kernel<__bf16, float, false>),
+            WIPA_K(LSMEM, gemm_nt256_kernel<float, __bf16, false>),
+            WIPA_K(LSMEM, gemm_nt256_kernel<float, float, false>),
+            WIPA_K(LSMEM, gemm_nt256_kernel<float, __bf16, true>),
+            WIPA_K(LSMEM, gemm_nt256_kernel<float, float, true>),
+            WIPA_K(X4, gemm_nt384_kernel<__bf16, __bf16, false, false>),
+            WIPA_K(X4, gemm_nt384_kernel<__bf16, float, false, false>),
+            WIPA_K(X4, gemm_nt384_kernel<float, __bf16, false, false>),
+            WIPA_K(X4, gemm_nt384_kernel<float, float, false, false>),
+            WIPA_K(X4, gemm_nt384_kernel<__bf16, __bf16, true, false>),
+            WIPA_K(X4, gemm_nt384_kernel<__bf16, float, true, false>),
+            WIPA_K(X4, gemm_nt384_kernel<float, __bf16, true, false>),
+            WIPA_K(X4, gemm_nt384_kernel<float, float, true, false>),
+            WIPA_K(X4, gemm_nt384_kernel<float, __bf16, false, true>),
+            WIPA_K(X4, gemm_nt384_kernel<float, float, false, true>),
+            WIPA_K(X4, gemm_nt384_kernel<float, __bf16, true, true>),
+            WIPA_K(X4, gemm_nt384_kernel<float, float, true, true>),
+            WIPA_K(X2, gemm_nt384n_kernel<float, __bf16, false, false>),
+            WIPA_K(X2, gemm_nt384n_kernel<float, float, false, false>),
+            WIPA_K(X2, gemm_nt384n_kernel<float, __bf16, true, false>),
+            WIPA_K(X2, gemm_nt384n_kernel<float, float, true, false>),
+            WIPA_K(X2, gemm_nt384n_kernel<float, __bf16, false, true>),
+            WIPA_K(X2, gemm_nt384n_kernel<float, float, false, true>),
+            WIPA_K(X2, gemm_nt384n_kernel<float, __bf16, true, true>),
+            WIPA_K(X2, gemm_nt384n_kernel<float, float, true, true>),
+            WIPA_K(LSMEM, gemm_fp8_256_kernel<__bf16>),
+            WIPA_K(LSMEM, gemm_fp8_256_kernel<float>),
+            WIPA_K(X4, gemm_fp8_384_kernel<__bf16, false>),
+            WIPA_K(X4, gemm_fp8_384_kernel<float, false>),
+            WIPA_K(X4, gemm_fp8_384_kernel<__bf16, true>),
+            WIPA_K(X4, gemm_fp8_384_kernel<float, true>),
+            WIPA_K(LN, gemm_skinny_ln_kernel<__bf16, __bf16, 1>),
+            WIPA_K(LN, gemm_skinny_ln_kernel<__bf16, __bf16, 2>),
+            WIPA_K(LN, gemm_skinny_ln_kernel<__bf16, __bf16, 4>),
+            WIPA_K(LN, gemm_skinny_ln_kernel<__bf16, float, 1>),
+            WIPA_K(LN, gemm_skinny_ln_kernel<__bf16, float, 2>),
+            WIPA_K(LN, gemm_skinny_ln_kernel<__bf16, float, 4>),
+            WIPA_K(LN, gemm_skinny_ln_kernel<float, float, 1>),
+            WIPA_K(LN, gemm_skinny_ln_kernel<float, float, 2>),
+            WIPA_K(LN, gemm_skinny_ln_kernel<float, float, 4>),
+            WIPA_K(WIDE, gemm_wide_persistent_kernel<float, 12>),
+            WIPA_K(WIDE, gemm_wide_persistent_kernel<float, 16>),
+            WIPA_K(WIDE, gemm_wide_persistent_kernel<float, 24>),
+            WIPA_K(WIDE, gemm_wide_persistent_kernel<float, 32>),
+            WIPA_K(WIDE, gemm_wide_persistent_kernel<__bf16, 12>),
+            WIPA_K(WIDE, gemm_wide_persistent_kernel<__bf16, 16>),
+            WIPA_K(WIDE, gemm_wide_persistent_kernel<__bf16, 24>),
+            WIPA_K(WIDE, gemm_wide_persistent_kernel<__bf16, 32>),
+            WIPA_K(WIDE, gemm_wide_persistent_kernel<float, 12, true>),
+            WIPA_K(WIDE, gemm_wide_persistent_kernel<float, 16, true>),
+            WIPA_K(WIDE, gemm_wide_persistent_kernel<float, 24, true>),
+            WIPA_K(WIDE, gemm_wide_persistent_kernel<float, 32, true>),
+        };
+#undef WIPA_K
+        static_assert(sizeof(table) / sizeof(table[0]) == 62, "every kernel with dynamic LDS above the default limit");
+        for (const auto& k : table) {
+            const hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds);
             if (e != hipSuccess) err = e;
         }
     });
@@ -2083,6 +1824,59 @@ extern "C" int wipa_gemm_dispatch_counts(int64_t* out, int n, int reset) {
     return WIPA_OK;
 }
 
+// wipa_gemm_desc -> GemmParams: operands, shape, output remaps (absent row / column groups become one group), 128 x 128 tile
+// counts (the larger tiles set their own in launch_tile), and whether the output mapping allows 4-element stores (vec_ok) and
+// the staged epilogue's 16-byte row-major stores (stage_ok; no_stage: WIPA_GEMM_NO_STAGE).  a_esz / w_esz: bytes per element
+// of A / W.  The scales, the LayerNorm prologue and the K-major flags are set by the paths that accept them.
+static GemmParams params_from_desc(const wipa_gemm_desc* d, int64_t a_esz, int64_t w_esz, bool no_stage) {
+    GemmParams p;
+    // f32 inputs in the tile kernels: exact f32 products on the f32 MFMA unless the caller opted into three bf16 MFMA
+    // terms per product (desc.f32_split: 2x the rate, ~5e-6 relative error).  The weight-streaming kernel stays exact.
+    p.f32_split = (d->in_dtype == WIPA_F32 && d->f32_split) ? 1 : 0;
+    p.A = (const char*)d->A;
+    p.W = (const char*)d->W;
+    p.C = (char*)d->C;
+    p.bias = d->bias;
+    p.residual = (const char*)d->residual;
+    p.pos = d->pos;
+    p.c_offset_dev = d->c_offset_dev;
+    p.lda_b = d->lda * a_esz;
+    p.ldw_b = d->ldw * w_esz;
+    p.ldc = d->ldc;
+    p.ldpos = d->ldpos;
+    p.M = d->M;
+    p.N = d->N;
+    p.K = d->K;
+    p.rg_in = d->rg_in > 0 ? d->rg_in : d->M;
+    p.rg_valid = d->rg_in > 0 ? d->rg_valid : d->M;
+    p.rg_stride = d->rg_in > 0 ? d->rg_stride : 0;
+    p.cg_in = d->cg_in > 0 ? d->cg_in : d->N;
+    p.cg_stride = d->cg_in > 0 ? d->cg_stride : 0;
+    p.c_offset = d->c_offset;
+    p.zero_invalid = d->zero_invalid_rows;
+    p.bias_along_m = d->bias_along_m;
+    p.act = d->act;
+    p.col_scale_n = d->col_scale_n;
+    p.col_scale = d->col_scale;
+    p.tiles_m = (d->M + BM - 1) / BM;
+    p.tiles_n = (d->N + BN - 1) / BN;
+    p.k_slices = d->k_slices > 1 ? d->k_slices : 1;
+    p.slab_stride = d->slab_stride;
+    const bool aligned = (((uintptr_t)d->C) % 16 == 0) && (!d->residual || ((uintptr_t)d->residual) % 16 == 0);
+    p.vec_ok = (p.ldc % 4 == 0) && (p.rg_stride % 4 == 0) && (p.cg_stride % 4 == 0) && (p.cg_in % 4 == 0) && (p.c_offset % 4 == 0) &&
+               aligned;  // 4 consecutive outputs per store
+    const int64_t epc = 16 / (int64_t)wipa_dtype_size(d->out_dtype);  // elements per 16-byte row-major store
+    p.stage_ok = !no_stage && (p.ldc % epc == 0) && (p.rg_stride % epc == 0) && (p.cg_stride % epc == 0) && (p.cg_in % epc == 0) &&
+                 (p.c_offset % epc == 0) && (p.col_scale_n % epc == 0) && !d->c_offset_dev && aligned;
+    return p;
+}
+
+// how well a grid of bm x bn tiles fills the 256 CUs: tiles / (rounds x 256)
+static double grid_fill(const wipa_gemm_desc* d, int bm, int bn) {
+    const int64_t tiles = (int64_t)((d->M + bm - 1) / bm) * ((d->N + bn - 1) / bn);
+    return (double)tiles / (double)(((tiles + 255) / 256) * 256);
+}
+
 // fp8 activations x fp8 weights (wipa_gemm_desc.in_dtype = WIPA_FP8_E4M3): the block-scaled MFMA tile kernel
 static int gemm_fp8(const wipa_gemm_desc* d, wipa_stream_t stream) {
     WIPA_REQUIRE(d->A && d->a_scale && d->w_scale && (d->w_dtype == 0 || d->w_dtype == WIPA_FP8_E4M3),
@@ -2091,26 +1885,9 @@ static int gemm_fp8(const wipa_gemm_desc* d, wipa_stream_t stream) {
                  "wipa_gemm: fp8 operands: K=%d must be a multiple of 128 and rows 16-byte aligned", d->K);
     WIPA_REQUIRE(!d->ln_x && !d->a_trans && !d->w_trans && d->k_slices <= 1, "wipa_gemm: fp8 operands: no LayerNorm prologue, K-major operands or k_slices");
     WIPA_REQUIRE(d->lda < (1 << 22) && d->ldw < (1 << 22), "wipa_gemm: fp8 operands: row pitch too large for 32-bit tile offsets");
-    GemmParams p;
-    p.A = (const char*)d->A; p.W = (const char*)d->W; p.C = (char*)d->C;
-    p.bias = d->bias; p.residual = (const char*)d->residual; p.pos = d->pos; p.c_offset_dev = d->c_offset_dev;
-    p.lda_b = d->lda; p.ldw_b = d->ldw; p.w_scale = d->w_scale; p.a_scale = d->a_scale;
-    p.ldc = d->ldc; p.ldpos = d->ldpos; p.M = d->M; p.N = d->N; p.K = d->K;
-    p.rg_in = d->rg_in > 0 ? d->rg_in : d->M;
-    p.rg_valid = d->rg_in > 0 ? d->rg_valid : d->M;
-    p.rg_stride = d->rg_in > 0 ? d->rg_stride : 0;
-    p.cg_in = d->cg_in > 0 ? d->cg_in : d->N;
-    p.cg_stride = d->cg_in > 0 ? d->cg_stride : 0;
-    p.c_offset = d->c_offset; p.zero_invalid = d->zero_invalid_rows; p.bias_along_m = d->bias_along_m; p.act = d->act;
-    p.col_scale_n = d->col_scale_n; p.col_scale = d->col_scale;
-    p.k_slices = 1; p.slab_stride = 0;
-    const int64_t osz = (int64_t)wipa_dtype_size(d->out_dtype);
-    p.vec_ok = (p.ldc % 4 == 0) && (p.rg_stride % 4 == 0) && (p.cg_stride % 4 == 0) && (p.cg_in % 4 == 0) && (p.c_offset % 4 == 0) &&
-               (((uintptr_t)d->C) % 16 == 0) && (!d->residual || ((uintptr_t)d->residual) % 16 == 0);
-    const int64_t epc = 16 / osz;
-    p.stage_ok = (p.ldc % epc == 0) && (p.rg_stride % epc == 0) && (p.cg_stride % epc == 0) && (p.cg_in % epc == 0) && (p.c_offset % epc == 0) &&
-                 (p.col_scale_n % epc == 0) && !d->c_offset_dev && (((uintptr_t)d->C) % 16 == 0) &&
-                 (!d->residual || ((uintptr_t)d->residual) % 16 == 0);
+    GemmParams p = params_from_desc(d, 1, 1, false);
+    p.w_scale = d->w_scale;
+    p.a_scale = d->a_scale;
     const int rc = init_attrs();
     if (rc != WIPA_OK) return rc;
     count_dispatch(WIPA_GEMM_TILE_FP8);
@@ -2123,14 +1900,16 @@ static int gemm_fp8(const wipa_gemm_desc* d, wipa_stream_t stream) {
     const bool act384_ok = d->act == 0 || (!d->bias_along_m && d->col_scale_n == 0);
     bool use384 = false;
     if (p.stage_ok && act384_ok && force_f8 != 256 && d->M >= 2 * XBM) {
-        auto fill = [](int64_t tiles) { const int64_t rounds = (tiles + 255) / 256; return (double)tiles / (double)(rounds * 256); };
-        const double e256 = fill((int64_t)((d->M + LBM - 1) / LBM) * ((d->N + LBN - 1) / LBN));
-        const double e384 = fill((int64_t)((d->M + XBM - 1) / XBM) * ((d->N + LBN - 1) / LBN));
-        use384 = force_f8 == 384 || (e384 >= 0.95 * e256 && d->K >= 2048);
+        use384 = force_f8 == 384 || (grid_fill(d, XBM, LBN) >= 0.95 * grid_fill(d, LBM, LBN) && d->K >= 2048);
     }
     if (use384) count_dispatch(WIPA_GEMM_TILE_FP8_384);
-    if (use384) return d->out_dtype == WIPA_BF16 ? launch_fp8_384<__bf16>(p, (hipStream_t)stream) : launch_fp8_384<float>(p, (hipStream_t)stream);
-    return d->out_dtype == WIPA_BF16 ? launch_fp8_256<__bf16>(p, (hipStream_t)stream) : launch_fp8_256<float>(p, (hipStream_t)stream);
+    const bool bf16_out = d->out_dtype == WIPA_BF16;
+    if (use384) {
+        const TileKernel k = p.act == 1 ? (bf16_out ? gemm_fp8_384_kernel<__bf16, true> : gemm_fp8_384_kernel<float, true>)
+                                        : (bf16_out ? gemm_fp8_384_kernel<__bf16, false> : gemm_fp8_384_kernel<float, false>);
+        return launch_tile<X384<4>>(k, p, (hipStream_t)stream);
+    }
+    return launch_tile<L256>(bf16_out ? gemm_fp8_256_kernel<__bf16> : gemm_fp8_256_kernel<float>, p, (hipStream_t)stream);
 }
 
 extern "C" int wipa_gemm(const wipa_gemm_desc* d, wipa_stream_t stream) {
@@ -2153,60 +1932,15 @@ extern "C" int wipa_gemm(const wipa_gemm_desc* d, wipa_stream_t stream) {
     WIPA_REQUIRE(d->w_dtype == WIPA_FP8_E4M3 || (d->K * esz) % ROWB == 0, "wipa_gemm: K=%d must be a multiple of %d elements", d->K, (int)(ROWB / esz));
     WIPA_REQUIRE((d->lda * esz) % 16 == 0 && (d->ldw * esz) % 16 == 0, "wipa_gemm: lda/ldw rows must be 16-byte aligned");
     WIPA_REQUIRE(((uintptr_t)d->A % 16) == 0 && ((uintptr_t)d->W % 16) == 0, "wipa_gemm: A/W must be 16-byte aligned");
-    GemmParams p;
-    p.A = (const char*)d->A;
-    p.W = (const char*)d->W;
-    p.C = (char*)d->C;
-    p.bias = d->bias;
-    p.residual = (const char*)d->residual;
-    p.pos = d->pos;
-    p.c_offset_dev = d->c_offset_dev;
-    p.lda_b = d->lda * esz;
-    p.ldw_b = d->w_dtype == WIPA_FP8_E4M3 ? d->ldw : d->ldw * esz;
+    static const int no_stage = [] { const char* e = getenv("WIPA_GEMM_NO_STAGE"); return e ? atoi(e) : 0; }();
+    GemmParams p = params_from_desc(d, esz, d->w_dtype == WIPA_FP8_E4M3 ? 1 : esz, no_stage != 0);
     p.w_scale = d->w_scale;
-    p.ldc = d->ldc;
-    p.ldpos = d->ldpos;
-    p.M = d->M;
-    p.N = d->N;
-    p.K = d->K;
-    p.rg_in = d->rg_in > 0 ? d->rg_in : d->M;
-    p.rg_valid = d->rg_in > 0 ? d->rg_valid : d->M;
-    p.rg_stride = d->rg_in > 0 ? d->rg_stride : 0;
-    p.cg_in = d->cg_in > 0 ? d->cg_in : d->N;
-    p.cg_stride = d->cg_in > 0 ? d->cg_stride : 0;
-    p.c_offset = d->c_offset;
-    p.zero_invalid = d->zero_invalid_rows;
-    p.bias_along_m = d->bias_along_m;
-    p.act = d->act;
-    p.col_scale_n = d->col_scale_n;
-    p.col_scale = d->col_scale;
-    p.tiles_m = (d->M + BM - 1) / BM;
-    p.tiles_n = (d->N + BN - 1) / BN;
-    p.k_slices = d->k_slices > 1 ? d->k_slices : 1;
-    p.slab_stride = d->slab_stride;
     if (p.k_slices > 1) {
         WIPA_REQUIRE(!d->residual && !d->pos && d->act == 0 && d->col_scale_n == 0,
                      "wipa_gemm: k_slices writes partial sums: no residual/pos/act/col_scale");
         WIPA_REQUIRE(p.k_slices <= 16 && d->slab_stride % 4 == 0, "wipa_gemm: bad k_slices / slab_stride");
     }
-    const int64_t osz = (int64_t)wipa_dtype_size(d->out_dtype);
-    const int64_t valign = 16 / osz == 4 ? 4 : 4;  // 4 consecutive outputs per store
-    p.vec_ok = (p.ldc % valign == 0) && (p.rg_stride % valign == 0) && (p.cg_stride % valign == 0) &&
-               (p.cg_in % 4 == 0) && (p.c_offset % valign == 0) && (((uintptr_t)d->C) % 16 == 0) &&
-               (!d->residual || ((uintptr_t)d->residual) % 16 == 0);
-    {
-        const int64_t epc = 16 / osz;  // elements per 16-byte row-major store
-        static const int no_stage = [] { const char* e = getenv("WIPA_GEMM_NO_STAGE"); return e ? atoi(e) : 0; }();
-        p.stage_ok = !no_stage && (p.ldc % epc == 0) && (p.rg_stride % epc == 0) && (p.cg_stride % epc == 0) &&
-                     (p.cg_in % epc == 0) && (p.c_offset % epc == 0) && (p.col_scale_n % epc == 0) && !d->c_offset_dev && (((uintptr_t)d->C) % 16 == 0) &&
-                     (!d->residual || ((uintptr_t)d->residual) % 16 == 0);
-    }
     hipStream_t s = (hipStream_t)stream;
-    {
-        // f32 inputs in the tile kernels: exact f32 products on the f32 MFMA unless the caller opted into three bf16 MFMA
-        // terms per product (desc.f32_split: 2x the rate, ~5e-6 relative error).  The weight-streaming kernel stays exact.
-        p.f32_split = (d->in_dtype == WIPA_F32 && d->f32_split) ? 1 : 0;
-    }
     {
         const int rc = init_attrs();
         if (rc != WIPA_OK) return rc;
@@ -2271,28 +2005,25 @@ extern "C" int wipa_gemm(const wipa_gemm_desc* d, wipa_stream_t stream) {
     const bool act384_ok = d->act == 0 || (p.stage_ok && !d->bias_along_m && d->col_scale_n == 0);
     bool use384 = force_tile == 384 && act384_ok, narrow = false;
     if (big && force_tile == 0 && act384_ok && d->M >= 2 * XBM) {
-        auto fill = [](int64_t t) { return (double)t / (double)(((t + 255) / 256) * 256); };
-        const int64_t tm384 = (d->M + XBM - 1) / XBM;
-        const double e256 = fill((int64_t)((d->M + LBM - 1) / LBM) * ((d->N + LBN - 1) / LBN));
-        const double e384 = fill(tm384 * ((d->N + LBN - 1) / LBN));
+        const double e256 = grid_fill(d, LBM, LBN), e384 = grid_fill(d, XBM, LBN);
         use384 = e384 >= 0.95 * e256;
         // 384 x 128 tiles when the wide grids leave a large part of the last round empty (48 000 x 768: 375 or 564 tiles, 0.73
         // either way, against 750 narrow ones, 0.98).  Float32 only: it runs at the f32 MFMA's pace whatever the tile (1077 ->
         // 845 us per GEMM); bf16 pays for the extra staged bytes per FLOP and measured no gain even at a fill ratio of 1.33
         // (whisper-small, 32 clips: 12.99 ms of GEMMs per pass with narrow tiles, 12.81 ms with wide ones).
-        const double e384n = fill(tm384 * ((d->N + 127) / 128));
+        const double e384n = grid_fill(d, XBM, 128);
         if (d->in_dtype == WIPA_F32 && e384n >= 1.10 * (e384 > e256 ? e384 : e256)) use384 = narrow = true;
     }
     if (big && force_tile == 2568 && d->in_dtype == WIPA_BF16 && d->K % 128 == 0) {  // phase-interleaved 256 x 256 (A/B runs)
         count_dispatch(WIPA_GEMM_TILE256P);
-        return d->out_dtype == WIPA_BF16 ? launch256p<__bf16>(p, s) : launch256p<float>(p, s);
+        return launch_tile<L256>(d->out_dtype == WIPA_BF16 ? gemm_nt256p_kernel<__bf16> : gemm_nt256p_kernel<float>, p, s);
     }
     if (big && use384) {
         count_dispatch(narrow ? WIPA_GEMM_TILE384N : WIPA_GEMM_TILE384);
-        if (narrow) return d->out_dtype == WIPA_BF16 ? launch384n<float, __bf16>(p, s) : launch384n<float, float>(p, s);
+        if (narrow) return d->out_dtype == WIPA_BF16 ? launch384<float, __bf16, 2>(p, s) : launch384<float, float, 2>(p, s);
         if (d->in_dtype == WIPA_BF16)
-            return d->out_dtype == WIPA_BF16 ? launch384<__bf16, __bf16>(p, s) : launch384<__bf16, float>(p, s);
-        return d->out_dtype == WIPA_BF16 ? launch384<float, __bf16>(p, s) : launch384<float, float>(p, s);
+            return d->out_dtype == WIPA_BF16 ? launch384<__bf16, __bf16, 4>(p, s) : launch384<__bf16, float, 4>(p, s);
+        return d->out_dtype == WIPA_BF16 ? launch384<float, __bf16, 4>(p, s) : launch384<float, float, 4>(p, s);
     }
     if (big) {
         count_dispatch(WIPA_GEMM_TILE256);
@@ -2325,16 +2056,15 @@ extern "C" int wipa_logits_greedy(const void* x, int64_t ldx, const void* w, int
     WIPA_REQUIRE((ldx * 2) % 16 == 0 && (ldw * 2) % 16 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)w % 16) == 0 &&
                      (!logits || (((uintptr_t)logits % 16) == 0 && ldl % 4 == 0 && ldl >= V)),
                  "wipa_logits_greedy: rows must be 16-byte aligned");
-    GemmParams p;
     static float dummy_c[4];
-    p.A = (const char*)x; p.W = (const char*)w; p.C = (char*)(logits ? logits : dummy_c);
-    p.bias = nullptr; p.residual = nullptr; p.pos = nullptr; p.c_offset_dev = nullptr;
-    p.lda_b = ldx * 2; p.ldw_b = ldw * 2; p.ldc = logits ? ldl : 0; p.ldpos = 0;
-    p.M = B; p.N = V; p.K = d;
-    p.rg_in = B; p.rg_valid = B; p.rg_stride = 0; p.cg_in = V; p.cg_stride = 0; p.c_offset = 0;
-    p.zero_invalid = 0; p.bias_along_m = 0; p.act = 0; p.col_scale_n = 0; p.col_scale = 1.f;
-    p.tiles_m = 1; p.tiles_n = 1; p.k_slices = 1; p.slab_stride = 0;
-    p.vec_ok = 1; p.stage_ok = 0;
+    wipa_gemm_desc g = {};
+    g.A = x; g.W = w; g.C = logits ? logits : dummy_c;
+    g.lda = ldx; g.ldw = ldw; g.ldc = logits ? ldl : 0;
+    g.M = B; g.N = V; g.K = d;
+    g.in_dtype = WIPA_BF16; g.out_dtype = WIPA_F32; g.col_scale = 1.f;
+    GemmParams p = params_from_desc(&g, 2, 2, true);
+    p.tiles_m = 1; p.tiles_n = 1;
+    p.vec_ok = 1;  // checked above (dummy_c is never stored to)
     p.g_mask_first = mask_first; p.g_mask_always = mask_always; p.g_pos = pos_dev; p.g_n_init = n_init; p.g_part = partials;
     p.g_store = logits ? 1 : 0;
     const int rc = init_attrs();
