@@ -9,12 +9,10 @@
 // (call sites scripts/train_whisper_ipa.py:223,232; scripts/transcribe_single.py:54-55).
 #include <cstring>
 
+#include "attn_stream.h"
 #include "wipa_common.h"
 
 namespace {
-
-constexpr float NEG_BIG = -1.0e30f;
-constexpr float NEG_TEST = -1.0e29f;
 
 // =============================================================================
 // generic attention, f32 math
@@ -134,17 +132,7 @@ __global__ __launch_bounds__(256) void attn_generic_kernel(AttnParams p) {
         m = m_new;
     }
     // merge the 16 key lanes of this query (consecutive lanes of one wave)
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) {
-        const float m_o = __shfl_xor(m, o, 64);
-        const float l_o = __shfl_xor(l, o, 64);
-        const float m_n = fmaxf(m, m_o);
-        const float a = __expf(m - m_n), bsc = __expf(m_o - m_n);
-        l = l * a + l_o * bsc;
-#pragma unroll
-        for (int d = 0; d < 64; ++d) acc[d] = acc[d] * a + __shfl_xor(acc[d], o, 64) * bsc;
-        m = m_n;
-    }
+    WIPA_LANE_MERGE(1, 16, 64, m, l, acc);
     if (qi < p.Tq) {
         const float inv = 1.f / l;
         if (p.lse && kl == 0) p.lse[((int64_t)b * gridDim.y + h) * p.Tq + qi] = m + __logf(l);
@@ -310,70 +298,23 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(AttnParams p) {
     float acc[EPL];
 #pragma unroll
     for (int e = 0; e < EPL; ++e) acc[e] = 0.f;
-    // software pipeline: the loads of key group i+1 are in flight while group i is reduced
-    auto load_group = [&](int t0, Vec16<T>(&kv_)[U], Vec16<T>(&vv_)[U]) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int t = min(t0 + u * G + g, Tk - 1);
-            if constexpr (NT) {  // cross-attention: 3.5 GB per step read exactly once -> non-temporal (nt) loads
-                typedef decltype(kv_[u].v) VT;
-                kv_[u].v = __builtin_nontemporal_load(reinterpret_cast<const VT*>(Kb + (int64_t)t * k_rs));
-                vv_[u].v = __builtin_nontemporal_load(reinterpret_cast<const VT*>(Vb + (int64_t)t * v_rs));
-            } else {
-                kv_[u] = *reinterpret_cast<const Vec16<T>*>(Kb + (int64_t)t * k_rs);
-                vv_[u] = *reinterpret_cast<const Vec16<T>*>(Vb + (int64_t)t * v_rs);
-            }
-        }
-    };
-    auto consume_group = [&](int t0, const Vec16<T>(&kvec)[U], const Vec16<T>(&vvec)[U]) {
-        float s[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            float a = 0.f;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) a = fmaf(qf[e], kvec[u].get(e), a);
-#pragma unroll
-            for (int o = 1; o < LPK; o <<= 1) a += __shfl_xor(a, o, 64);
-            s[u] = (t0 + u * G + g < Tk) ? a : NEG_BIG;
-        }
-        float m_new = m;
-#pragma unroll
-        for (int u = 0; u < U; ++u) m_new = fmaxf(m_new, s[u]);
-        const float alpha = __expf(m - m_new);
-        l *= alpha;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) acc[e] *= alpha;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const float pr = (s[u] <= NEG_TEST) ? 0.f : __expf(s[u] - m_new);
-            l += pr;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) acc[e] = fmaf(pr, vvec[u].get(e), acc[e]);
-        }
-        m = m_new;
-    };
     // One register set (U K-rows + U V-rows in flight per lane), latency hidden by the other waves of the CU.
     // A register double-buffer measured the same 5.4 TB/s stand-alone but needs 135 VGPRs; the lean form keeps
     // the kernel small enough to share a SIMD with the 2 x 212-VGPR waves of the encoder GEMM of another
     // in-flight pass (see bench.py --pipeline), where it can use the HBM bandwidth the GEMM leaves idle.
     constexpr int STEP = WPH * G * U;
-    for (int t0 = kw * G * U; t0 < Tk; t0 += STEP) {
+    auto key_group = [&](int t0) {  // a lambda on purpose: the same text straight in the loop compiles to other code
         Vec16<T> ka[U], va[U];
-        load_group(t0, ka, va);
-        consume_group(t0, ka, va);
-    }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {  // cross-attention (NT): 3.5 GB per step read exactly once -> non-temporal (nt) loads
+            ka[u] = load_row_clamped<NT>(Kb, t0 + u * G + g, Tk - 1, k_rs);
+            va[u] = load_row_clamped<NT>(Vb, t0 + u * G + g, Tk - 1, v_rs);
+        }
+        WIPA_STREAM_STEP(U, qf, ka, va, t0, m, l, acc);
+    };
+    for (int t0 = kw * G * U; t0 < Tk; t0 += STEP) key_group(t0);
     // merge the G key groups of this wave (lanes with equal c)
-#pragma unroll
-    for (int o = LPK; o < 64; o <<= 1) {
-        const float m_o = __shfl_xor(m, o, 64);
-        const float l_o = __shfl_xor(l, o, 64);
-        const float m_n = fmaxf(m, m_o);
-        const float a = __expf(m - m_n), bsc = __expf(m_o - m_n);
-        l = l * a + l_o * bsc;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) acc[e] = acc[e] * a + __shfl_xor(acc[e], o, 64) * bsc;
-        m = m_n;
-    }
+    WIPA_LANE_MERGE(LPK, 64, EPL, m, l, acc);
     if (WPH == 1) {
         if (lane < LPK) {
             const float inv = 1.f / l;
@@ -383,26 +324,9 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(AttnParams p) {
         }
         return;
     }
-    if (lane < LPK) {
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) s_acc[wave][c * EPL + e] = acc[e];
-        if (lane == 0) {
-            s_m[wave] = m;
-            s_l[wave] = l;
-        }
-    }
+    WIPA_WAVE_MERGE_STORE(s_acc, s_m, s_l, m, l, acc);
     __syncthreads();
-    if (tid < 64) {
-        const float mm = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
-        float num = 0.f, den = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const float sc = __expf(s_m[w] - mm);
-            num += s_acc[w][tid] * sc;
-            den += s_l[w] * sc;
-        }
-        reinterpret_cast<T*>(p.out)[b * p.o_bs + h * p.o_hs + tid] = from_f32<T>(num / den);
-    }
+    if (tid < 64) WIPA_WAVE_MERGE_OUT(s_acc, s_m, s_l, tid, reinterpret_cast<T*>(p.out)[b * p.o_bs + h * p.o_hs + tid]);
 }
 
 // Prompt prefill: the NQ prompt positions of a clip attend to the SAME cached cross K/V, so one pass over the cache serves
@@ -442,76 +366,23 @@ __global__ __launch_bounds__(256) void decode_attn_multi_kernel(AttnParams p) {
     constexpr int STEP = 4 * G * U;
     for (int t0 = wave * G * U; t0 < Tk; t0 += STEP) {
         Vec16<T> ka[U], va[U];
-        typedef decltype(ka[0].v) VT;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int key = min(t0 + u * G + g, Tk - 1);
-            ka[u].v = __builtin_nontemporal_load(reinterpret_cast<const VT*>(Kb + (int64_t)key * k_rs));
-            va[u].v = __builtin_nontemporal_load(reinterpret_cast<const VT*>(Vb + (int64_t)key * v_rs));
+            ka[u] = load_row_clamped(Kb, t0 + u * G + g, Tk - 1, k_rs);
+            va[u] = load_row_clamped(Vb, t0 + u * G + g, Tk - 1, v_rs);
         }
 #pragma unroll
-        for (int t = 0; t < NQ; ++t) {
-            float s[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                float a = 0.f;
-#pragma unroll
-                for (int e = 0; e < EPL; ++e) a = fmaf(qf[t][e], ka[u].get(e), a);
-#pragma unroll
-                for (int o = 1; o < LPK; o <<= 1) a += __shfl_xor(a, o, 64);
-                s[u] = (t0 + u * G + g < Tk) ? a : NEG_BIG;
-            }
-            float m_new = m[t];
-#pragma unroll
-            for (int u = 0; u < U; ++u) m_new = fmaxf(m_new, s[u]);
-            const float alpha = __expf(m[t] - m_new);
-            l[t] *= alpha;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) acc[t][e] *= alpha;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const float pr = (s[u] <= NEG_TEST) ? 0.f : __expf(s[u] - m_new);
-                l[t] += pr;
-#pragma unroll
-                for (int e = 0; e < EPL; ++e) acc[t][e] = fmaf(pr, va[u].get(e), acc[t][e]);
-            }
-            m[t] = m_new;
-        }
+        for (int t = 0; t < NQ; ++t) WIPA_STREAM_STEP(U, qf[t], ka, va, t0, m[t], l[t], acc[t]);
     }
 #pragma unroll
     for (int t = 0; t < NQ; ++t) {
-#pragma unroll
-        for (int o = LPK; o < 64; o <<= 1) {
-            const float m_o = __shfl_xor(m[t], o, 64);
-            const float l_o = __shfl_xor(l[t], o, 64);
-            const float m_n = fmaxf(m[t], m_o);
-            const float a = __expf(m[t] - m_n), bsc = __expf(m_o - m_n);
-            l[t] = l[t] * a + l_o * bsc;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) acc[t][e] = acc[t][e] * a + __shfl_xor(acc[t][e], o, 64) * bsc;
-            m[t] = m_n;
-        }
-        if (lane < LPK) {
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) s_acc[t][wave][c * EPL + e] = acc[t][e];
-            if (lane == 0) {
-                s_m[t][wave] = m[t];
-                s_l[t][wave] = l[t];
-            }
-        }
+        WIPA_LANE_MERGE(LPK, 64, EPL, m[t], l[t], acc[t]);
+        WIPA_WAVE_MERGE_STORE(s_acc[t], s_m[t], s_l[t], m[t], l[t], acc[t]);
     }
     __syncthreads();
     if (tid < 64 * NQ) {
         const int t = tid >> 6, dd = tid & 63;
-        const float mm = fmaxf(fmaxf(s_m[t][0], s_m[t][1]), fmaxf(s_m[t][2], s_m[t][3]));
-        float num = 0.f, den = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const float sc = __expf(s_m[t][w] - mm);
-            num += s_acc[t][w][dd] * sc;
-            den += s_l[t][w] * sc;
-        }
-        reinterpret_cast<T*>(p.out)[b * p.o_bs + (int64_t)t * p.o_rs + h * p.o_hs + dd] = from_f32<T>(num / den);
+        WIPA_WAVE_MERGE_OUT(s_acc[t], s_m[t], s_l[t], dd, reinterpret_cast<T*>(p.out)[b * p.o_bs + (int64_t)t * p.o_rs + h * p.o_hs + dd]);
     }
 }
 
@@ -521,6 +392,55 @@ __global__ __launch_bounds__(256) void decode_attn_multi_kernel(AttnParams p) {
 constexpr int FA_ROWB = 128;                // bytes per LDS row (64 bf16)
 constexpr int FA_TILE = 64 * FA_ROWB;       // 8 KiB
 constexpr float LOG2E = 1.4426950408889634f;
+
+// The online softmax of one 64-key tile, one text for the three flash kernels (a macro over their locals: as a __forceinline__
+// function over references it compiled to different code in all three).  In: S[2], the raw scores S^T of tile kt in the 32x32
+// accumulator layout -- element i of S[u] in lane half hh is key 64 kt + 32u + 8(i>>2) + 4hh + (i&3), the lane's query is its
+// column.  Out: S holds p = exp2(S*log2e - m); O[2] is rescaled when the running max moved; m (log2 domain) and l are updated,
+// l being the lane half's share of the row sum until WIPA_FLASH_SOFTMAX_FINISH adds the two halves.
+//   * The ragged last tile is masked behind a scalar BRANCH, which the empty asm keeps one: if-converted, the 32 compares and
+//     selects ran on every tile and cost as much VALU time as the softmax itself.
+//   * Every tile holds at least one real key, so m_new is finite; a masked score gives exp2(-1e30) = 0 without a test.
+//   * p as one FMA + v_exp, two scores per VALU slot (v_pk_fma_f32 / v_pk_add_f32); only the exponentials stay scalar.
+//   * The rescale is wave-uniform (__any): the running max rarely moves after the first tiles.
+#define WIPA_FLASH_SOFTMAX_TILE()                                                                  \
+    do {                                                                                           \
+        if (kt * 64 + 64 > T) {                                                                    \
+            asm volatile("" ::: "memory");                                                         \
+            _Pragma("unroll") for (int u = 0; u < 2; ++u)                                          \
+                _Pragma("unroll") for (int i = 0; i < 16; ++i) {                                   \
+                    const int key = kt * 64 + 32 * u + (i & 3) + 8 * (i >> 2) + 4 * hh;            \
+                    if (key >= T) S[u][i] = NEG_BIG;                                               \
+                }                                                                                  \
+        }                                                                                          \
+        float mx = NEG_BIG;                                                                        \
+        _Pragma("unroll") for (int u = 0; u < 2; ++u)                                              \
+            _Pragma("unroll") for (int i = 0; i < 16; ++i) mx = fmaxf(mx, S[u][i]);                \
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));                                                    \
+        const float m_new = fmaxf(m, mx * LOG2E);                                                  \
+        f32x2 psum2 = {0.f, 0.f};                                                                  \
+        const f32x2 l2e = {LOG2E, LOG2E}, mneg = {-m_new, -m_new};                                 \
+        _Pragma("unroll") for (int u = 0; u < 2; ++u)                                              \
+            _Pragma("unroll") for (int i = 0; i < 16; i += 2) {                                    \
+                const f32x2 x = __builtin_elementwise_fma(f32x2{S[u][i], S[u][i + 1]}, l2e, mneg); \
+                const f32x2 pv = {__builtin_amdgcn_exp2f(x.x), __builtin_amdgcn_exp2f(x.y)};       \
+                S[u][i] = pv.x;                                                                    \
+                S[u][i + 1] = pv.y;                                                                \
+                psum2 += pv;                                                                       \
+            }                                                                                      \
+        const float psum = psum2.x + psum2.y;                                                      \
+        if (__any(m_new > m)) {                                                                    \
+            const float alpha = __builtin_amdgcn_exp2f(m - m_new);                                 \
+            l *= alpha;                                                                            \
+            _Pragma("unroll") for (int i = 0; i < 16; ++i) {                                       \
+                O[0][i] *= alpha;                                                                  \
+                O[1][i] *= alpha;                                                                  \
+            }                                                                                      \
+            m = m_new;                                                                             \
+        }                                                                                          \
+        l += psum;                                                                                 \
+    } while (0)
+#define WIPA_FLASH_SOFTMAX_FINISH() l += __shfl_xor(l, 32, 64)
 
 // blockDim.x / 64 = 4 or 8 waves: 128 or 256 queries share every K / V^T tile (8 waves halve the L2->LDS fill per FLOP).
 __global__ __launch_bounds__(512) void flash_enc_bf16_kernel(const __bf16* __restrict__ qk, int64_t ldqk,
@@ -599,51 +519,7 @@ __global__ __launch_bounds__(512) void flash_enc_bf16_kernel(const __bf16* __res
                 S[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[s], S[u], 0, 0, 0);
             }
         }
-        // row max on the raw scores (ragged last tile masked), then p = exp2(S*log2e - m) as one FMA + v_exp
-        const bool ragged = (kt * 64 + 64 > T);
-        if (ragged) {  // last tile only.  The empty asm keeps this a scalar BRANCH: if-converted, the 32 compares and
-                       // selects ran on every tile and cost as much VALU time as the softmax itself.
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int key = kt * 64 + 32 * u + (i & 3) + 8 * (i >> 2) + 4 * hh;
-                    if (key >= T) S[u][i] = NEG_BIG;
-                }
-        }
-        float mx = NEG_BIG;
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) mx = fmaxf(mx, S[u][i]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m, mx * LOG2E);  // every tile holds at least one real key, so m_new is finite
-        // two scores per VALU slot (v_pk_fma_f32 / v_pk_add_f32); only the exponentials stay scalar
-        f32x2 psum2 = {0.f, 0.f};
-        const f32x2 l2e = {LOG2E, LOG2E}, mneg = {-m_new, -m_new};
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int i = 0; i < 16; i += 2) {
-                const f32x2 x = __builtin_elementwise_fma(f32x2{S[u][i], S[u][i + 1]}, l2e, mneg);  // masked: exp2(-1e30) = 0
-                const f32x2 pv = {__builtin_amdgcn_exp2f(x.x), __builtin_amdgcn_exp2f(x.y)};
-                S[u][i] = pv.x;
-                S[u][i + 1] = pv.y;
-                psum2 += pv;
-            }
-        const float psum = psum2.x + psum2.y;
-        if (__any(m_new > m)) {  // wave-uniform: the running max rarely moves after the first tiles
-            const float alpha = __builtin_amdgcn_exp2f(m - m_new);
-            l *= alpha;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                O[0][i] *= alpha;
-                O[1][i] *= alpha;
-            }
-            m = m_new;
-        }
-        l += psum;
+        WIPA_FLASH_SOFTMAX_TILE();
         // O^T += V^T * P^T : P^T comes straight from the S accumulators (k order of the
         // 32x32 C layout: element j of half hh is key 16s' + 8(j>>2) + 4hh + (j&3))
 #pragma unroll
@@ -669,7 +545,7 @@ __global__ __launch_bounds__(512) void flash_enc_bf16_kernel(const __bf16* __res
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
-    l += __shfl_xor(l, 32, 64);
+    WIPA_FLASH_SOFTMAX_FINISH();
     const int qrow = q0 + r;
     if (qrow < T) {
         const float inv = 1.f / l;
@@ -698,65 +574,97 @@ __global__ __launch_bounds__(512) void flash_enc_bf16_kernel(const __bf16* __res
 constexpr int FF_LD = 68;                  // floats per LDS row: 64 + 4 (conflict-free ds_read_b128 down a column)
 constexpr int FF_TILE = 64 * FF_LD;        // floats per operand tile
 
+// The K half of the staging: this thread's 16 consecutive k (segment kseg) of one key, in rk, to the key's LDS row.
+// Exact kernel: even and odd k separated, even k -> [0, 32), odd k -> [32, 64) of the row.  Split kernel: as they come.
+__device__ __forceinline__ void stage_k_parity(float* krow, int kseg, const f32x4 (&rk)[4]) {
+    float* kt = krow + 8 * kseg;
+    *reinterpret_cast<f32x4*>(kt) = f32x4{rk[0][0], rk[0][2], rk[1][0], rk[1][2]};
+    *reinterpret_cast<f32x4*>(kt + 4) = f32x4{rk[2][0], rk[2][2], rk[3][0], rk[3][2]};
+    *reinterpret_cast<f32x4*>(kt + 32) = f32x4{rk[0][1], rk[0][3], rk[1][1], rk[1][3]};
+    *reinterpret_cast<f32x4*>(kt + 36) = f32x4{rk[2][1], rk[2][3], rk[3][1], rk[3][3]};
+}
+__device__ __forceinline__ void stage_k_plain(float* krow, int kseg, const f32x4 (&rk)[4]) {
+    float* kt = krow + 16 * kseg;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) *reinterpret_cast<f32x4*>(kt + 4 * c) = rk[c];
+}
+
+// The scaffold of the two f32 kernels, as text over the kernel's locals (q, k, v, out, their row strides and T are the kernel's
+// arguments).  A kernel supplies its Q fragments, the K half of the staging (STAGE_K: one of the two functions above) and the
+// two product blocks, which stay in the kernel as plain text between the TILE macros.
+#define WIPA_FLASH_F32_INDICES()                                                                                 \
+    __shared__ __attribute__((aligned(16))) float smem[4 * FF_TILE]; /* [buf][K tile | V^T tile], 69 632 B */    \
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;                                               \
+    const int r = lane & 31, hh = lane >> 5;                                                                     \
+    const int h = blockIdx.y, b = blockIdx.z;                                                                    \
+    const int q0 = blockIdx.x * 128 + wave * 32;                                                                 \
+    const int nkt = (T + 63) / 64
+
+// staging roles.  K: key row tid>>2, 16 consecutive k (segment tid&3).  V: key tid&63, 16 consecutive d (tid>>6); V arrives
+// [key][d] and is transposed into the V^T tile.  Then the accumulators and the first tile.
+#define WIPA_FLASH_F32_STAGING(STAGE_K)                                                                          \
+    const int krow = tid >> 2, kseg = tid & 3;                                                                   \
+    const int vkey = tid & 63, vseg = tid >> 6;                                                                  \
+    const float* kg = k + (int64_t)b * T * ldk + h * 64 + 16 * kseg;                                             \
+    const float* vg = v + (int64_t)b * T * ldv + h * 64 + 16 * vseg;                                             \
+    f32x4 rk[4], rv[4];                                                                                          \
+    auto gload = [&](int kt) {                                                                                   \
+        const float* kp = kg + (int64_t)min(kt * 64 + krow, T - 1) * ldk;                                        \
+        const float* vp = vg + (int64_t)min(kt * 64 + vkey, T - 1) * ldv;                                        \
+        _Pragma("unroll") for (int c = 0; c < 4; ++c) {                                                          \
+            rk[c] = *reinterpret_cast<const f32x4*>(kp + 4 * c);                                                 \
+            rv[c] = *reinterpret_cast<const f32x4*>(vp + 4 * c);                                                 \
+        }                                                                                                        \
+    };                                                                                                           \
+    auto swrite = [&](int buf) {                                                                                 \
+        STAGE_K(smem + buf * 2 * FF_TILE + krow * FF_LD, kseg, rk);                                              \
+        float* vt = smem + buf * 2 * FF_TILE + FF_TILE + (16 * vseg) * FF_LD + vkey; /* V^T[d][key] */           \
+        _Pragma("unroll") for (int c = 0; c < 4; ++c)                                                            \
+            _Pragma("unroll") for (int e = 0; e < 4; ++e) vt[(4 * c + e) * FF_LD] = rv[c][e];                    \
+    };                                                                                                           \
+    f32x16 O[2];                                                                                                 \
+    _Pragma("unroll") for (int i = 0; i < 16; ++i) O[0][i] = O[1][i] = 0.f;                                      \
+    float m = NEG_BIG, l = 0.f; /* m in the log2 domain */                                                       \
+    gload(0);                                                                                                    \
+    swrite(0);                                                                                                   \
+    __syncthreads()
+
+// inside for (kt): the next tile's global loads fly over this tile's products and are written to the other buffer behind them
+#define WIPA_FLASH_F32_TILE_BEGIN()                                                                              \
+    if (kt + 1 < nkt) gload(kt + 1);                                                                             \
+    const float* kbuf = smem + (kt & 1) * 2 * FF_TILE;                                                           \
+    const float* vbuf = kbuf + FF_TILE;                                                                          \
+    f32x16 S[2]
+#define WIPA_FLASH_F32_TILE_END()                                                                                \
+    if (kt + 1 < nkt) swrite((kt + 1) & 1);                                                                      \
+    __syncthreads()
+
+#define WIPA_FLASH_F32_TAIL()                                                                                    \
+    WIPA_FLASH_SOFTMAX_FINISH();                                                                                 \
+    const int qrow = q0 + r;                                                                                     \
+    if (qrow < T) {                                                                                              \
+        const float inv = 1.f / l;                                                                               \
+        float* op = out + ((int64_t)b * T + qrow) * ldo + h * 64 + 4 * hh;                                       \
+        _Pragma("unroll") for (int dt = 0; dt < 2; ++dt)                                                         \
+            _Pragma("unroll") for (int g4 = 0; g4 < 4; ++g4)                                                     \
+                *reinterpret_cast<f32x4*>(op + 32 * dt + 8 * g4) =                                               \
+                    f32x4{O[dt][4 * g4] * inv, O[dt][4 * g4 + 1] * inv, O[dt][4 * g4 + 2] * inv, O[dt][4 * g4 + 3] * inv}; \
+    }
+
 __global__ __launch_bounds__(256, 2) void flash_enc_f32_kernel(const float* __restrict__ q, int64_t ldq,
                                                                const float* __restrict__ k, int64_t ldk,
                                                                const float* __restrict__ v, int64_t ldv,
                                                                float* __restrict__ out, int64_t ldo, int T) {
-    __shared__ __attribute__((aligned(16))) float smem[4 * FF_TILE];  // [buf][K tile | V^T tile], 69 632 B
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, hh = lane >> 5;
-    const int h = blockIdx.y, b = blockIdx.z;
-    const int q0 = blockIdx.x * 128 + wave * 32;
-    const int nkt = (T + 63) / 64;
-
+    WIPA_FLASH_F32_INDICES();
     float qf[32];
     {
         const float* qp = q + ((int64_t)b * T + min(q0 + r, T - 1)) * ldq + h * 64 + hh;
 #pragma unroll
         for (int s = 0; s < 32; ++s) qf[s] = qp[2 * s];
     }
-    // staging roles.  K: key row tid>>2, 16 consecutive k (segment tid&3).  V: key tid&63, 16 consecutive d (tid>>6).
-    const int krow = tid >> 2, kseg = tid & 3;
-    const int vkey = tid & 63, vseg = tid >> 6;
-    const float* kg = k + (int64_t)b * T * ldk + h * 64 + 16 * kseg;
-    const float* vg = v + (int64_t)b * T * ldv + h * 64 + 16 * vseg;
-    f32x4 rk[4], rv[4];
-    auto gload = [&](int kt) {
-        const float* kp = kg + (int64_t)min(kt * 64 + krow, T - 1) * ldk;
-        const float* vp = vg + (int64_t)min(kt * 64 + vkey, T - 1) * ldv;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            rk[c] = *reinterpret_cast<const f32x4*>(kp + 4 * c);
-            rv[c] = *reinterpret_cast<const f32x4*>(vp + 4 * c);
-        }
-    };
-    auto swrite = [&](int buf) {
-        float* kt = smem + buf * 2 * FF_TILE + krow * FF_LD + 8 * kseg;
-        // even k -> [0, 32), odd k -> [32, 64) of the key row
-        *reinterpret_cast<f32x4*>(kt) = f32x4{rk[0][0], rk[0][2], rk[1][0], rk[1][2]};
-        *reinterpret_cast<f32x4*>(kt + 4) = f32x4{rk[2][0], rk[2][2], rk[3][0], rk[3][2]};
-        *reinterpret_cast<f32x4*>(kt + 32) = f32x4{rk[0][1], rk[0][3], rk[1][1], rk[1][3]};
-        *reinterpret_cast<f32x4*>(kt + 36) = f32x4{rk[2][1], rk[2][3], rk[3][1], rk[3][3]};
-        float* vt = smem + buf * 2 * FF_TILE + FF_TILE + (16 * vseg) * FF_LD + vkey;  // V^T[d][key]
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) vt[(4 * c + e) * FF_LD] = rv[c][e];
-    };
-
-    f32x16 O[2];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) O[0][i] = O[1][i] = 0.f;
-    float m = NEG_BIG, l = 0.f;  // m in the log2 domain
-
-    gload(0);
-    swrite(0);
-    __syncthreads();
+    WIPA_FLASH_F32_STAGING(stage_k_parity);
     for (int kt = 0; kt < nkt; ++kt) {
-        if (kt + 1 < nkt) gload(kt + 1);
-        const float* kbuf = smem + (kt & 1) * 2 * FF_TILE;
-        const float* vbuf = kbuf + FF_TILE;
-        f32x16 S[2];
+        WIPA_FLASH_F32_TILE_BEGIN();
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
 #pragma unroll
@@ -769,46 +677,7 @@ __global__ __launch_bounds__(256, 2) void flash_enc_f32_kernel(const float* __re
                 for (int e = 0; e < 4; ++e) S[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[e], qf[4 * c + e], S[u], 0, 0, 0);
             }
         }
-        if (kt * 64 + 64 > T) {  // ragged last tile: a scalar branch (see the bf16 kernel)
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int key = kt * 64 + 32 * u + (i & 3) + 8 * (i >> 2) + 4 * hh;
-                    if (key >= T) S[u][i] = NEG_BIG;
-                }
-        }
-        float mx = NEG_BIG;
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) mx = fmaxf(mx, S[u][i]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m, mx * LOG2E);
-        f32x2 psum2 = {0.f, 0.f};
-        const f32x2 l2e = {LOG2E, LOG2E}, mneg = {-m_new, -m_new};
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int i = 0; i < 16; i += 2) {
-                const f32x2 x = __builtin_elementwise_fma(f32x2{S[u][i], S[u][i + 1]}, l2e, mneg);
-                const f32x2 pv = {__builtin_amdgcn_exp2f(x.x), __builtin_amdgcn_exp2f(x.y)};
-                S[u][i] = pv.x;
-                S[u][i + 1] = pv.y;
-                psum2 += pv;
-            }
-        if (__any(m_new > m)) {
-            const float alpha = __builtin_amdgcn_exp2f(m - m_new);
-            l *= alpha;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                O[0][i] *= alpha;
-                O[1][i] *= alpha;
-            }
-            m = m_new;
-        }
-        l += psum2.x + psum2.y;
+        WIPA_FLASH_SOFTMAX_TILE();
         // O^T[d][q] += V^T[d][key] P^T[key][q]; step s of accumulator element s: key 32u + 8(s>>2) + 4hh + (s&3)
 #pragma unroll
         for (int u = 0; u < 2; ++u)
@@ -823,21 +692,9 @@ __global__ __launch_bounds__(256, 2) void flash_enc_f32_kernel(const float* __re
                         O[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(vf[e], S[u][4 * g + e], O[dt], 0, 0, 0);
                 }
             }
-        if (kt + 1 < nkt) swrite((kt + 1) & 1);
-        __syncthreads();
+        WIPA_FLASH_F32_TILE_END();
     }
-    l += __shfl_xor(l, 32, 64);
-    const int qrow = q0 + r;
-    if (qrow < T) {
-        const float inv = 1.f / l;
-        float* op = out + ((int64_t)b * T + qrow) * ldo + h * 64 + 4 * hh;
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4)
-                *reinterpret_cast<f32x4*>(op + 32 * dt + 8 * g4) =
-                    f32x4{O[dt][4 * g4] * inv, O[dt][4 * g4 + 1] * inv, O[dt][4 * g4 + 2] * inv, O[dt][4 * g4 + 3] * inv};
-    }
+    WIPA_FLASH_F32_TAIL();
 }
 
 // K5 in f32, fast form: every product on the bf16 MFMA (32x32x16) with the f32 operands split in registers.  The scores
@@ -849,13 +706,7 @@ __global__ __launch_bounds__(256, 2) void flash_enc_f32s_kernel(const float* __r
                                                                 const float* __restrict__ k, int64_t ldk,
                                                                 const float* __restrict__ v, int64_t ldv,
                                                                 float* __restrict__ out, int64_t ldo, int T) {
-    __shared__ __attribute__((aligned(16))) float smem[4 * FF_TILE];  // [buf][K tile | V^T tile]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, hh = lane >> 5;
-    const int h = blockIdx.y, b = blockIdx.z;
-    const int q0 = blockIdx.x * 128 + wave * 32;
-    const int nkt = (T + 63) / 64;
-
+    WIPA_FLASH_F32_INDICES();
     // Q fragments (B operand): lane (r, hh) holds Q[q0+r][16s + 8hh + 0..7], split once
     bf16x8 qh[4], qm[4], ql[4];
     {
@@ -864,44 +715,9 @@ __global__ __launch_bounds__(256, 2) void flash_enc_f32s_kernel(const float* __r
         for (int s = 0; s < 4; ++s)
             split_bf16x3(*reinterpret_cast<const f32x4*>(qp + 16 * s), *reinterpret_cast<const f32x4*>(qp + 16 * s + 4), qh[s], qm[s], ql[s]);
     }
-    const int krow = tid >> 2, kseg = tid & 3;
-    const int vkey = tid & 63, vseg = tid >> 6;
-    const float* kg = k + (int64_t)b * T * ldk + h * 64 + 16 * kseg;
-    const float* vg = v + (int64_t)b * T * ldv + h * 64 + 16 * vseg;
-    f32x4 rk[4], rv[4];
-    auto gload = [&](int kt) {
-        const float* kp = kg + (int64_t)min(kt * 64 + krow, T - 1) * ldk;
-        const float* vp = vg + (int64_t)min(kt * 64 + vkey, T - 1) * ldv;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            rk[c] = *reinterpret_cast<const f32x4*>(kp + 4 * c);
-            rv[c] = *reinterpret_cast<const f32x4*>(vp + 4 * c);
-        }
-    };
-    auto swrite = [&](int buf) {
-        float* kt = smem + buf * 2 * FF_TILE + krow * FF_LD + 16 * kseg;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) *reinterpret_cast<f32x4*>(kt + 4 * c) = rk[c];
-        float* vt = smem + buf * 2 * FF_TILE + FF_TILE + (16 * vseg) * FF_LD + vkey;  // V^T[d][key]
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) vt[(4 * c + e) * FF_LD] = rv[c][e];
-    };
-
-    f32x16 O[2];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) O[0][i] = O[1][i] = 0.f;
-    float m = NEG_BIG, l = 0.f;  // m in the log2 domain
-
-    gload(0);
-    swrite(0);
-    __syncthreads();
+    WIPA_FLASH_F32_STAGING(stage_k_plain);
     for (int kt = 0; kt < nkt; ++kt) {
-        if (kt + 1 < nkt) gload(kt + 1);
-        const float* kbuf = smem + (kt & 1) * 2 * FF_TILE;
-        const float* vbuf = kbuf + FF_TILE;
-        f32x16 S[2];
+        WIPA_FLASH_F32_TILE_BEGIN();
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
 #pragma unroll
@@ -919,46 +735,7 @@ __global__ __launch_bounds__(256, 2) void flash_enc_f32s_kernel(const float* __r
                 S[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh, qh[s], S[u], 0, 0, 0);
             }
         }
-        if (kt * 64 + 64 > T) {  // ragged last tile: a scalar branch
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int key = kt * 64 + 32 * u + (i & 3) + 8 * (i >> 2) + 4 * hh;
-                    if (key >= T) S[u][i] = NEG_BIG;
-                }
-        }
-        float mx = NEG_BIG;
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) mx = fmaxf(mx, S[u][i]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m, mx * LOG2E);
-        f32x2 psum2 = {0.f, 0.f};
-        const f32x2 l2e = {LOG2E, LOG2E}, mneg = {-m_new, -m_new};
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int i = 0; i < 16; i += 2) {
-                const f32x2 x = __builtin_elementwise_fma(f32x2{S[u][i], S[u][i + 1]}, l2e, mneg);
-                const f32x2 pv = {__builtin_amdgcn_exp2f(x.x), __builtin_amdgcn_exp2f(x.y)};
-                S[u][i] = pv.x;
-                S[u][i + 1] = pv.y;
-                psum2 += pv;
-            }
-        if (__any(m_new > m)) {
-            const float alpha = __builtin_amdgcn_exp2f(m - m_new);
-            l *= alpha;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                O[0][i] *= alpha;
-                O[1][i] *= alpha;
-            }
-            m = m_new;
-        }
-        l += psum2.x + psum2.y;
+        WIPA_FLASH_SOFTMAX_TILE();
         // O^T += V^T P^T; MFMA k slot j of half hh is key 16 sp + 8 (j>>2) + 4 hh + (j&3) of the 32-key block u
 #pragma unroll
         for (int u = 0; u < 2; ++u)
@@ -977,34 +754,29 @@ __global__ __launch_bounds__(256, 2) void flash_enc_f32s_kernel(const float* __r
                     O[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, ph, O[dt], 0, 0, 0);
                 }
             }
-        if (kt + 1 < nkt) swrite((kt + 1) & 1);
-        __syncthreads();
+        WIPA_FLASH_F32_TILE_END();
     }
-    l += __shfl_xor(l, 32, 64);
-    const int qrow = q0 + r;
-    if (qrow < T) {
-        const float inv = 1.f / l;
-        float* op = out + ((int64_t)b * T + qrow) * ldo + h * 64 + 4 * hh;
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4)
-                *reinterpret_cast<f32x4*>(op + 32 * dt + 8 * g4) =
-                    f32x4{O[dt][4 * g4] * inv, O[dt][4 * g4 + 1] * inv, O[dt][4 * g4 + 2] * inv, O[dt][4 * g4 + 3] * inv};
-    }
+    WIPA_FLASH_F32_TAIL();
 }
+
+#undef WIPA_FLASH_F32_INDICES
+#undef WIPA_FLASH_F32_STAGING
+#undef WIPA_FLASH_F32_TILE_BEGIN
+#undef WIPA_FLASH_F32_TILE_END
+#undef WIPA_FLASH_F32_TAIL
+#undef WIPA_FLASH_SOFTMAX_TILE
+#undef WIPA_FLASH_SOFTMAX_FINISH
 
 }  // namespace
 
-extern "C" int wipa_attention(const wipa_attn_desc* d, wipa_stream_t stream) {
-    WIPA_REQUIRE(d && d->q && d->k && d->v && d->out, "wipa_attention: null pointer");
-    WIPA_REQUIRE(d->B > 0 && d->H > 0 && d->Tq > 0, "wipa_attention: bad shape");
-    WIPA_REQUIRE(d->dtype == WIPA_F32 || d->dtype == WIPA_BF16, "wipa_attention: bad dtype %d", d->dtype);
+// 16-byte row loads: every stride of q, k and v keeps the alignment of the base pointers
+static bool attn_strides_aligned(const wipa_attn_desc* d) {
     const int64_t al = d->dtype == WIPA_BF16 ? 8 : 4;
-    WIPA_REQUIRE(d->q_rs % al == 0 && d->k_rs % al == 0 && d->v_rs % al == 0 && d->q_hs % al == 0 && d->k_hs % al == 0 &&
-                     d->v_hs % al == 0 && d->q_bs % al == 0 && d->k_bs % al == 0 && d->v_bs % al == 0,
-                 "wipa_attention: strides must keep 16-byte alignment");
-    AttnParams p;
+    return d->q_rs % al == 0 && d->k_rs % al == 0 && d->v_rs % al == 0 && d->q_hs % al == 0 && d->k_hs % al == 0 && d->v_hs % al == 0 &&
+           d->q_bs % al == 0 && d->k_bs % al == 0 && d->v_bs % al == 0;
+}
+
+static void fill_attn_params(const wipa_attn_desc* d, AttnParams& p) {
     p.q = (const char*)d->q;
     p.k = (const char*)d->k;
     p.v = (const char*)d->v;
@@ -1019,6 +791,16 @@ extern "C" int wipa_attention(const wipa_attn_desc* d, wipa_stream_t stream) {
     p.Tq = d->Tq;
     p.Tk = d->Tk;
     p.causal = d->causal;
+    p.H = d->H;
+}
+
+extern "C" int wipa_attention(const wipa_attn_desc* d, wipa_stream_t stream) {
+    WIPA_REQUIRE(d && d->q && d->k && d->v && d->out, "wipa_attention: null pointer");
+    WIPA_REQUIRE(d->B > 0 && d->H > 0 && d->Tq > 0, "wipa_attention: bad shape");
+    WIPA_REQUIRE(d->dtype == WIPA_F32 || d->dtype == WIPA_BF16, "wipa_attention: bad dtype %d", d->dtype);
+    WIPA_REQUIRE(attn_strides_aligned(d), "wipa_attention: strides must keep 16-byte alignment");
+    AttnParams p;
+    fill_attn_params(d, p);
     dim3 grid((d->Tq + 15) / 16, d->H, d->B);
     // float32 with whole 16-query fragments and no device-side offsets (teacher-forced decoder, fine-tune step): f32 MFMA kernel;
     // the few-row prefill and everything bf16 stay on the VALU kernel.  WIPA_ATTN_FWD=valu keeps it for A/B runs.
@@ -1069,33 +851,11 @@ extern "C" int wipa_flash_attn_enc_f32(const float* q, int64_t ldq, const float*
     return WIPA_OK;
 }
 
-static int fill_attn_params(const wipa_attn_desc* d, AttnParams& p) {
-    p.q = (const char*)d->q;
-    p.k = (const char*)d->k;
-    p.v = (const char*)d->v;
-    p.out = (char*)d->out;
-    p.tk_dev = d->tk_dev;
-    p.q_row_dev = d->q_row_dev;
-    p.lse = d->lse;
-    p.q_bs = d->q_bs; p.q_rs = d->q_rs; p.q_hs = d->q_hs;
-    p.k_bs = d->k_bs; p.k_rs = d->k_rs; p.k_hs = d->k_hs;
-    p.v_bs = d->v_bs; p.v_rs = d->v_rs; p.v_hs = d->v_hs;
-    p.o_bs = d->o_bs; p.o_rs = d->o_rs; p.o_hs = d->o_hs;
-    p.Tq = d->Tq;
-    p.Tk = d->Tk;
-    p.causal = d->causal;
-    p.H = d->H;
-    return WIPA_OK;
-}
-
 extern "C" int wipa_decode_attn(const wipa_attn_desc* d, wipa_stream_t stream) {
     WIPA_REQUIRE(d && d->q && d->k && d->v && d->out, "wipa_decode_attn: null pointer");
     WIPA_REQUIRE(d->B > 0 && d->H > 0 && d->Tq == 1, "wipa_decode_attn: one query row per (b,h) (Tq=%d)", d->Tq);
     WIPA_REQUIRE(d->dtype == WIPA_F32 || d->dtype == WIPA_BF16, "wipa_decode_attn: bad dtype %d", d->dtype);
-    const int64_t al = d->dtype == WIPA_BF16 ? 8 : 4;
-    WIPA_REQUIRE(d->q_rs % al == 0 && d->k_rs % al == 0 && d->v_rs % al == 0 && d->q_hs % al == 0 && d->k_hs % al == 0 &&
-                     d->v_hs % al == 0 && d->q_bs % al == 0 && d->k_bs % al == 0 && d->v_bs % al == 0,
-                 "wipa_decode_attn: strides must keep 16-byte alignment");
+    WIPA_REQUIRE(attn_strides_aligned(d), "wipa_decode_attn: strides must keep 16-byte alignment");
     AttnParams p;
     fill_attn_params(d, p);
     // short caches (the growing self-attention cache, <= n_text_ctx keys): default-policy loads, and four waves per head
@@ -1125,29 +885,8 @@ extern "C" int wipa_decode_attn(const wipa_attn_desc* d, wipa_stream_t stream) {
     return WIPA_OK;
 }
 
-extern "C" int wipa_decode_cross_attn(const void* q, const void* kv, void* out, int B, int H, int Tk, int dtype,
-                                      wipa_stream_t stream) {
-    WIPA_REQUIRE(q && kv && out, "wipa_decode_cross_attn: null pointer");
-    WIPA_REQUIRE(B > 0 && H > 0 && Tk > 0, "wipa_decode_cross_attn: bad shape");
-    WIPA_REQUIRE(dtype == WIPA_F32 || dtype == WIPA_BF16, "wipa_decode_cross_attn: bad dtype %d", dtype);
-    wipa_attn_desc d;
-    memset(&d, 0, sizeof(d));
-    const size_t e = wipa_dtype_size(dtype);
-    d.q = q; d.k = kv; d.v = (const char*)kv + (size_t)H * Tk * 64 * e; d.out = out;
-    d.q_bs = (int64_t)H * 64; d.q_rs = (int64_t)H * 64; d.q_hs = 64;
-    d.k_bs = (int64_t)2 * H * Tk * 64; d.k_rs = 64; d.k_hs = (int64_t)Tk * 64;
-    d.v_bs = d.k_bs; d.v_rs = 64; d.v_hs = d.k_hs;
-    d.o_bs = (int64_t)H * 64; d.o_rs = (int64_t)H * 64; d.o_hs = 64;
-    d.B = B; d.H = H; d.Tq = 1; d.Tk = Tk; d.causal = 0; d.dtype = dtype;
-    return wipa_decode_attn(&d, stream);
-}
-
-extern "C" int wipa_decode_cross_attn_multi(const void* q, const void* kv, void* out, int B, int H, int Tk, int n_q, int dtype,
-                                            wipa_stream_t stream) {
-    WIPA_REQUIRE(q && kv && out, "wipa_decode_cross_attn_multi: null pointer");
-    WIPA_REQUIRE(B > 0 && H > 0 && Tk > 0 && n_q >= 1 && n_q <= 4, "wipa_decode_cross_attn_multi: bad shape (n_q=%d)", n_q);
-    WIPA_REQUIRE(dtype == WIPA_F32 || dtype == WIPA_BF16, "wipa_decode_cross_attn_multi: bad dtype %d", dtype);
-    if (n_q == 1) return wipa_decode_cross_attn(q, kv, out, B, H, Tk, dtype, stream);
+// q [B][n_q][H*64] against the cached cross K/V of a clip, kv [B][2H][Tk][64] (K heads then V heads); out like q
+static wipa_attn_desc cross_attn_desc(const void* q, const void* kv, void* out, int B, int H, int Tk, int n_q, int dtype) {
     wipa_attn_desc d;
     memset(&d, 0, sizeof(d));
     const size_t e = wipa_dtype_size(dtype);
@@ -1157,6 +896,25 @@ extern "C" int wipa_decode_cross_attn_multi(const void* q, const void* kv, void*
     d.v_bs = d.k_bs; d.v_rs = 64; d.v_hs = d.k_hs;
     d.o_bs = d.q_bs; d.o_rs = d.q_rs; d.o_hs = 64;
     d.B = B; d.H = H; d.Tq = n_q; d.Tk = Tk; d.causal = 0; d.dtype = dtype;
+    return d;
+}
+
+extern "C" int wipa_decode_cross_attn(const void* q, const void* kv, void* out, int B, int H, int Tk, int dtype,
+                                      wipa_stream_t stream) {
+    WIPA_REQUIRE(q && kv && out, "wipa_decode_cross_attn: null pointer");
+    WIPA_REQUIRE(B > 0 && H > 0 && Tk > 0, "wipa_decode_cross_attn: bad shape");
+    WIPA_REQUIRE(dtype == WIPA_F32 || dtype == WIPA_BF16, "wipa_decode_cross_attn: bad dtype %d", dtype);
+    const wipa_attn_desc d = cross_attn_desc(q, kv, out, B, H, Tk, 1, dtype);
+    return wipa_decode_attn(&d, stream);
+}
+
+extern "C" int wipa_decode_cross_attn_multi(const void* q, const void* kv, void* out, int B, int H, int Tk, int n_q, int dtype,
+                                            wipa_stream_t stream) {
+    WIPA_REQUIRE(q && kv && out, "wipa_decode_cross_attn_multi: null pointer");
+    WIPA_REQUIRE(B > 0 && H > 0 && Tk > 0 && n_q >= 1 && n_q <= 4, "wipa_decode_cross_attn_multi: bad shape (n_q=%d)", n_q);
+    WIPA_REQUIRE(dtype == WIPA_F32 || dtype == WIPA_BF16, "wipa_decode_cross_attn_multi: bad dtype %d", dtype);
+    if (n_q == 1) return wipa_decode_cross_attn(q, kv, out, B, H, Tk, dtype, stream);
+    const wipa_attn_desc d = cross_attn_desc(q, kv, out, B, H, Tk, n_q, dtype);
     AttnParams p;
     fill_attn_params(&d, p);
     const dim3 grid(H, B);

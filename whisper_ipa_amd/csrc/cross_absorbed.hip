@@ -30,11 +30,11 @@
 #include <mutex>
 #include <type_traits>
 
+#include "attn_stream.h"
 #include "wipa_common.h"
 
 namespace {
 
-constexpr float NEG_BIG = -1.0e30f;
 constexpr int FT = 32;  // frames per tile
 // xa residency budgets per pass in 10^6 bytes (wipa_cross_absorbed_resident_groups): -1 = every group on the default policy
 constexpr long long XA_RESIDENT_MB_SHARED = 16;  // <= 2 frame splits: several passes in flight share the Infinity Cache
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(512, 1) void cross_absorbed_kernel(AbsParams p) {
         for (int ft = 0; ft < 2; ++ft)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float e = (s[ft][r] <= -1.0e29f) ? 0.f : __expf(s[ft][r] - m_new);
+                const float e = (s[ft][r] <= NEG_TEST) ? 0.f : __expf(s[ft][r] - m_new);
                 pr[4 * ft + r] = e;
                 ls += e;
             }
@@ -477,7 +477,7 @@ __global__ __launch_bounds__(64 * NW_, 1) void cross_absorbed_v2_kernel(AbsParam
             bf16x4v pf;  // A operand of P x group (16x16x16): row = head l15, k = frames 4g .. 4g + 3 -- the lane's own values
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float e = (s[r] <= -1.0e29f) ? 0.f : __expf(s[r] - m_ref);
+                const float e = (s[r] <= NEG_TEST) ? 0.f : __expf(s[r] - m_ref);
                 pf[r] = (__bf16)e;
                 ls += e;
             }
@@ -973,6 +973,31 @@ int launch_attn(const AbsParams& p_in, int B, hipStream_t s) {
     return WIPA_OK;
 }
 
+// The scratch of a call carved up -- Qp [B][16][d] bf16, then part_m and part_l [B][S][16] and part_o [B][S][16][d] f32 -- and the
+// streaming kernel's parameters filled from it.  S is the call's split count (wipa_cross_absorbed_splits).
+AbsParams abs_params(void* scratch, int B, int d, int Tk, int S, int H, const void* xa) {
+    char* sc = (char*)scratch;
+    AbsParams p = {};
+    p.qp = (const __bf16*)sc; p.xa = (const __bf16*)xa;
+    p.part_m = (float*)(sc + (size_t)B * 16 * d * 2);
+    p.part_l = p.part_m + (size_t)B * S * 16;
+    p.part_o = p.part_l + (size_t)B * S * 16;
+    p.Tk = Tk; p.n_splits = S; p.H = H;
+    const int tiles = (Tk + FT - 1) / FT;
+    p.tiles_per_split = (tiles + S - 1) / S;
+    return p;
+}
+
+// The one ladder over the supported widths: f(std::integral_constant<int, D>()) with the call's d as the compile-time D.
+template <typename F>
+int for_width(int d, F f) {
+    if (d == 384) return f(std::integral_constant<int, 384>());
+    if (d == 512) return f(std::integral_constant<int, 512>());
+    if (d == 768) return f(std::integral_constant<int, 768>());
+    if (d == 1024) return f(std::integral_constant<int, 1024>());
+    return WIPA_ERR_ARG;
+}
+
 }  // namespace
 
 // Frame splits per clip: a clip's result must not depend on the batch it rides in (the partition of the frames fixes the order of
@@ -1039,23 +1064,20 @@ extern "C" int wipa_cross_absorbed_init(int d) {
     std::lock_guard<std::mutex> lk(mu);
     if (done[wi]) return WIPA_OK;
     hipError_t e = hipSuccess;
-#define ABS_ATTR(D)                                                                                                                        \
-    {                                                                                                                                      \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_absorbed_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize,      \
-                                AbsCfg<D>::SMEM);                                                                                          \
-        if (e == hipSuccess && D <= 768)                                                                                                   \
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_absorbed_v2_kernel<(D <= 768 ? D : 768), 3>),                     \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, AbsCfg2<(D <= 768 ? D : 768), 3>::SMEM);                   \
-        if (e == hipSuccess)                                                                                                               \
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_absorbed_v2_kernel<D, 2>),                                        \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, AbsCfg2<D, 2>::SMEM);                                      \
-    }
-    if (d == 384) ABS_ATTR(384)
-    else if (d == 512) ABS_ATTR(512)
-    else if (d == 768) ABS_ATTR(768)
-    else if (d == 1024) ABS_ATTR(1024)
-    else return WIPA_ERR_ARG;
-#undef ABS_ATTR
+    for_width(d, [&](auto width) {
+        constexpr int D = decltype(width)::value;
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_absorbed_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                AbsCfg<D>::SMEM);
+        if constexpr (D <= 768) {
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_absorbed_v2_kernel<D, 3>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, AbsCfg2<D, 3>::SMEM);
+        }
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_absorbed_v2_kernel<D, 2>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, AbsCfg2<D, 2>::SMEM);
+        return WIPA_OK;
+    });
     WIPA_CHECK_HIP(e);
     done[wi] = true;
     return WIPA_OK;
@@ -1072,20 +1094,8 @@ extern "C" int wipa_cross_absorbed_stream(const void* xa, void* scratch, size_t 
     const int rc0 = wipa_cross_absorbed_init(d);
     if (rc0 != WIPA_OK) return rc0;
     const int S = wipa_cross_absorbed_splits(n_splits, Tk);
-    char* sc = (char*)scratch;
-    AbsParams p = {};
-    p.qp = (const __bf16*)sc; p.xa = (const __bf16*)xa;
-    p.part_m = (float*)(sc + (size_t)B * 16 * d * 2);
-    p.part_l = p.part_m + (size_t)B * S * 16;
-    p.part_o = p.part_l + (size_t)B * S * 16;
-    p.Tk = Tk; p.n_splits = S; p.H = H;
-    const int tiles = (Tk + FT - 1) / FT;
-    p.tiles_per_split = (tiles + S - 1) / S;
-    int rc;
-    if (d == 384) rc = launch_attn<384>(p, B, (hipStream_t)stream);
-    else if (d == 512) rc = launch_attn<512>(p, B, (hipStream_t)stream);
-    else if (d == 768) rc = launch_attn<768>(p, B, (hipStream_t)stream);
-    else rc = launch_attn<1024>(p, B, (hipStream_t)stream);
+    const AbsParams p = abs_params(scratch, B, d, Tk, S, H, xa);
+    const int rc = for_width(d, [&](auto width) { return launch_attn<decltype(width)::value>(p, B, (hipStream_t)stream); });
     if (rc != WIPA_OK) return rc;
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;
@@ -1109,35 +1119,22 @@ extern "C" int wipa_cross_absorbed_attention(const void* q, int64_t q_row_stride
         if (rc0 != WIPA_OK) return rc0;
     }
     const int S = wipa_cross_absorbed_splits(n_splits, Tk);
-    char* sc = (char*)scratch;
-    __bf16* qp = (__bf16*)sc;
-    float* part_m = (float*)(sc + (size_t)B * 16 * d * 2);
-    float* part_l = part_m + (size_t)B * S * 16;
-    float* part_o = part_l + (size_t)B * S * 16;
-    AbsParams p = {};
-    p.qp = qp; p.xa = (const __bf16*)xa; p.part_m = part_m; p.part_l = part_l; p.part_o = part_o;
-    p.Tk = Tk; p.n_splits = S; p.H = H;
-    const int tiles = (Tk + FT - 1) / FT;
-    p.tiles_per_split = (tiles + S - 1) / S;
+    const AbsParams p = abs_params(scratch, B, d, Tk, S, H, xa);
     const dim3 gq(16, (B + 15) / 16, 4), gm(H, (B + WIPA_MERGE_CL - 1) / WIPA_MERGE_CL);
-    int rc = WIPA_OK;
     const char* st_env = getenv("WIPA_ABS_STAGES");  // debugging: bit 0 absorb-q, bit 1 stream, bit 2 merge (default all)
     const int stages = st_env ? atoi(st_env) : 7;
-#define ABS_RUN(D)                                                                                                                         \
-    do {                                                                                                                                   \
-        if (stages & 1)                                                                                                                    \
-            hipLaunchKernelGGL((cross_absorb_q_kernel<D>), gq, dim3(64), 0, s, (const __bf16*)q, q_row_stride, (const __bf16*)wkT, qp, B, H, k_scale); \
-        if (stages & 2) rc = launch_attn<D>(p, B, s);                                                                                      \
-        if (rc == WIPA_OK && (stages & 4)) {                                                                                               \
-            hipLaunchKernelGGL((cross_merge_proj_kernel<D>), gm, dim3(64 * MergeCfg<D>::NWM), 0, s, part_m, part_l, part_o, S,            \
-                               (const __bf16*)wv, bv, (__bf16*)out, out_row_stride, B);                                                    \
-        }                                                                                                                                  \
-    } while (0)
-    if (d == 384) ABS_RUN(384);
-    else if (d == 512) ABS_RUN(512);
-    else if (d == 768) ABS_RUN(768);
-    else ABS_RUN(1024);
-#undef ABS_RUN
+    const int rc = for_width(d, [&](auto width) {
+        constexpr int D = decltype(width)::value;
+        int rc = WIPA_OK;
+        if (stages & 1)
+            hipLaunchKernelGGL((cross_absorb_q_kernel<D>), gq, dim3(64), 0, s, (const __bf16*)q, q_row_stride, (const __bf16*)wkT,
+                               const_cast<__bf16*>(p.qp), B, H, k_scale);
+        if (stages & 2) rc = launch_attn<D>(p, B, s);
+        if (rc == WIPA_OK && (stages & 4))
+            hipLaunchKernelGGL((cross_merge_proj_kernel<D>), gm, dim3(64 * MergeCfg<D>::NWM), 0, s, p.part_m, p.part_l, p.part_o, S,
+                               (const __bf16*)wv, bv, (__bf16*)out, out_row_stride, B);
+        return rc;
+    });
     if (rc != WIPA_OK) return rc;
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;
@@ -1182,43 +1179,29 @@ static int absorbed_block(const wipa_cross_block_desc* c, const void* wkT, const
     WIPA_REQUIRE(scratch_bytes >= wipa_cross_absorbed_scratch_bytes(B, d, Tk), "wipa_decode_cross_absorbed_block: scratch too small");
     hipStream_t s = (hipStream_t)stream;
     const int S = wipa_cross_absorbed_splits(c->cross_splits, Tk);
-    char* sc = (char*)scratch;
-    __bf16* qp = (__bf16*)sc;
-    float* part_m = (float*)(sc + (size_t)B * 16 * d * 2);
-    float* part_l = part_m + (size_t)B * S * 16;
-    float* part_o = part_l + (size_t)B * S * 16;
+    const AbsParams p = abs_params(scratch, B, d, Tk, S, H, c->kv);
     AbsPrologueParams q = {};
     q.x_in = c->x_in; q.x_out = c->x_out; q.slabs = c->slabs; q.ln_w = c->ln_w; q.ln_b = c->ln_b;
-    q.wq = (const __bf16*)c->wq; q.bq = c->bq; q.wkT = (const __bf16*)wkT; q.qp = qp;
+    q.wq = (const __bf16*)c->wq; q.bq = c->bq; q.wkT = (const __bf16*)wkT; q.qp = const_cast<__bf16*>(p.qp);
     q.slab_stride = c->slab_stride; q.n_slabs = c->n_slabs; q.B = B; q.H = H;
     q.eps = c->eps; q.q_scale = c->qk_scale; q.k_scale = c->qk_scale;
-    AbsParams p = {};
-    p.qp = qp; p.xa = (const __bf16*)c->kv; p.part_m = part_m; p.part_l = part_l; p.part_o = part_o;
-    p.Tk = Tk; p.n_splits = S; p.H = H;
-    const int tiles = (Tk + FT - 1) / FT;
-    p.tiles_per_split = (tiles + S - 1) / S;
     // clips per prologue workgroup: 8 (default since round 4: H x B / 8 = 96 workgroups at 64 clips; a lone decode step 1.304 vs
     // 1.338 ms, the pipelined pass unchanged) or 16 (WIPA_ABS_PROLOGUE_CLIPS=16: every MFMA row a clip, 48 workgroups)
     static const int cg = [] { const char* e = getenv("WIPA_ABS_PROLOGUE_CLIPS"); return e ? atoi(e) : 8; }();
     const dim3 gp(H, cg == 8 ? (B + 7) / 8 : (B + 15) / 16), gm(H, (B + WIPA_MERGE_CL - 1) / WIPA_MERGE_CL);
-    int rc = WIPA_OK;
-#define ABS_BLOCK(D)                                                                                                                       \
-    do {                                                                                                                                   \
-        if (cg == 8) hipLaunchKernelGGL((cross_absorb_prologue_kernel<D, 8>), gp, dim3(512), 0, s, q);                                     \
-        else hipLaunchKernelGGL((cross_absorb_prologue_kernel<D, 16>), gp, dim3(512), 0, s, q);                                            \
-        rc = launch_attn<D>(p, B, s);                                                                                                      \
-        if (rc == WIPA_OK && wo)                                                                                                           \
-            hipLaunchKernelGGL((cross_merge_proj_kernel<D, true>), gm, dim3(64 * MergeCfg<D>::NWM), 0, s, part_m, part_l, part_o,  \
-                               S, (const __bf16*)wv, bv, (__bf16*)nullptr, (int64_t)d, B, (const __bf16*)wo, bo, slabs_out, slab_stride);  \
-        else if (rc == WIPA_OK)                                                                                                            \
-            hipLaunchKernelGGL((cross_merge_proj_kernel<D>), gm, dim3(64 * MergeCfg<D>::NWM), 0, s, part_m, part_l, part_o, S,             \
-                               (const __bf16*)wv, bv, (__bf16*)c->out, (int64_t)d, B);                                                     \
-    } while (0)
-    if (d == 384) ABS_BLOCK(384);
-    else if (d == 512) ABS_BLOCK(512);
-    else if (d == 768) ABS_BLOCK(768);
-    else ABS_BLOCK(1024);
-#undef ABS_BLOCK
+    const int rc = for_width(d, [&](auto width) {
+        constexpr int D = decltype(width)::value;
+        if (cg == 8) hipLaunchKernelGGL((cross_absorb_prologue_kernel<D, 8>), gp, dim3(512), 0, s, q);
+        else hipLaunchKernelGGL((cross_absorb_prologue_kernel<D, 16>), gp, dim3(512), 0, s, q);
+        const int rc = launch_attn<D>(p, B, s);
+        if (rc == WIPA_OK && wo)
+            hipLaunchKernelGGL((cross_merge_proj_kernel<D, true>), gm, dim3(64 * MergeCfg<D>::NWM), 0, s, p.part_m, p.part_l, p.part_o, S,
+                               (const __bf16*)wv, bv, (__bf16*)nullptr, (int64_t)d, B, (const __bf16*)wo, bo, slabs_out, slab_stride);
+        else if (rc == WIPA_OK)
+            hipLaunchKernelGGL((cross_merge_proj_kernel<D>), gm, dim3(64 * MergeCfg<D>::NWM), 0, s, p.part_m, p.part_l, p.part_o, S,
+                               (const __bf16*)wv, bv, (__bf16*)c->out, (int64_t)d, B);
+        return rc;
+    });
     if (rc != WIPA_OK) return rc;
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;

@@ -20,12 +20,11 @@
 #include <cstdlib>
 #include <mutex>
 
+#include "attn_stream.h"
 #include "wipa_common.h"
 
 namespace {
 
-constexpr float NEG_BIG = -1.0e30f;
-constexpr float NEG_TEST = -1.0e29f;
 constexpr int RG = 16;  // token rows per self-block workgroup (one MFMA row tile)
 
 struct SelfBlockParams {
@@ -264,17 +263,7 @@ __global__ __launch_bounds__(256) void decode_self_block_kernel(SelfBlockParams 
             }
             m = m_new;
         }
-#pragma unroll
-        for (int o = LPK; o < 16; o <<= 1) {  // merge the key groups of this row
-            const float m_o = __shfl_xor(m, o, 64);
-            const float l_o = __shfl_xor(l, o, 64);
-            const float m_n = fmaxf(m, m_o);
-            const float a = __expf(m - m_n), bsc = __expf(m_o - m_n);
-            l = l * a + l_o * bsc;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) acc[e] = acc[e] * a + __shfl_xor(acc[e], o, 64) * bsc;
-            m = m_n;
-        }
+        WIPA_LANE_MERGE(LPK, 16, EPL, m, l, acc);  // merge the key groups of this row
         if (g == 0) {
             const float inv = 1.f / l;
             T* op = reinterpret_cast<T*>(o_s + r * PITCH_O) + c * EPL;
@@ -368,7 +357,6 @@ __global__ __launch_bounds__(256, 6) void decode_cross_block_kernel(CrossBlockPa
     const int64_t head = (int64_t)Tk * 64;
     const T* Kb = reinterpret_cast<const T*>(p.kv) + ((int64_t)b * 2 * p.H + h) * head + c * EPL;
     const T* Vb = Kb + (int64_t)p.H * head;
-    typedef decltype(wcur[0].v) VT;
 
     constexpr int PRE = 3;  // key rows of the first group requested ahead (all U would spill at 80 registers)
     Vec16<T> kpre[PRE];
@@ -404,8 +392,7 @@ __global__ __launch_bounds__(256, 6) void decode_cross_block_kernel(CrossBlockPa
         if (lane == 0) s_red[wave] = sum;
         __syncthreads();
 #pragma unroll
-        for (int u = 0; u < PRE; ++u)
-            kpre[u].v = __builtin_nontemporal_load(reinterpret_cast<const VT*>(Kb + (int64_t)min(wave * G * U + u * G + g, Tk - 1) * 64));
+        for (int u = 0; u < PRE; ++u) kpre[u] = load_row_clamped(Kb, wave * G * U + u * G + g, Tk - 1, 64);
         const float mean = ((s_red[0] + s_red[1]) + (s_red[2] + s_red[3])) / (float)d;
         float sq = 0.f;
 #pragma unroll
@@ -464,7 +451,7 @@ __global__ __launch_bounds__(256, 6) void decode_cross_block_kernel(CrossBlockPa
     }
     __syncthreads();
 
-    // ---- 3. streaming cross-attention (the arithmetic of decode_attn_kernel<T, 4>: 4 waves split the keys)
+    // ---- 3. streaming cross-attention (the step and merges of decode_attn_kernel<T, 4>: 4 waves split the keys)
     float qf[EPL];
 #pragma unroll
     for (int e = 0; e < EPL; ++e) qf[e] = q_s[c * EPL + e];
@@ -475,33 +462,8 @@ __global__ __launch_bounds__(256, 6) void decode_cross_block_kernel(CrossBlockPa
     auto key_group = [&](Vec16<T> (&ka)[U], int t0) {
         Vec16<T> va[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u)
-            va[u].v = __builtin_nontemporal_load(reinterpret_cast<const VT*>(Vb + (int64_t)min(t0 + u * G + g, Tk - 1) * 64));
-        float s[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            float a = 0.f;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) a = fmaf(qf[e], ka[u].get(e), a);
-#pragma unroll
-            for (int o = 1; o < LPK; o <<= 1) a += __shfl_xor(a, o, 64);
-            s[u] = (t0 + u * G + g < Tk) ? a : NEG_BIG;
-        }
-        float m_new = m;
-#pragma unroll
-        for (int u = 0; u < U; ++u) m_new = fmaxf(m_new, s[u]);
-        const float alpha = __expf(m - m_new);
-        l *= alpha;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) acc[e] *= alpha;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const float pr = (s[u] <= NEG_TEST) ? 0.f : __expf(s[u] - m_new);
-            l += pr;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) acc[e] = fmaf(pr, va[u].get(e), acc[e]);
-        }
-        m = m_new;
+        for (int u = 0; u < U; ++u) va[u] = load_row_clamped(Vb, t0 + u * G + g, Tk - 1, 64);
+        WIPA_STREAM_STEP(U, qf, ka, va, t0, m, l, acc);
     };
     if (wave * G * U < Tk) {
         const int t0 = wave * G * U;
@@ -509,48 +471,20 @@ __global__ __launch_bounds__(256, 6) void decode_cross_block_kernel(CrossBlockPa
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (u < PRE) ka[u] = kpre[u];
-            else ka[u].v = __builtin_nontemporal_load(reinterpret_cast<const VT*>(Kb + (int64_t)min(t0 + u * G + g, Tk - 1) * 64));
+            else ka[u] = load_row_clamped(Kb, t0 + u * G + g, Tk - 1, 64);
         }
         key_group(ka, t0);
     }
     for (int t0 = wave * G * U + STEP; t0 < Tk; t0 += STEP) {
         Vec16<T> ka[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u)
-            ka[u].v = __builtin_nontemporal_load(reinterpret_cast<const VT*>(Kb + (int64_t)min(t0 + u * G + g, Tk - 1) * 64));
+        for (int u = 0; u < U; ++u) ka[u] = load_row_clamped(Kb, t0 + u * G + g, Tk - 1, 64);
         key_group(ka, t0);
     }
-#pragma unroll
-    for (int o = LPK; o < 64; o <<= 1) {
-        const float m_o = __shfl_xor(m, o, 64);
-        const float l_o = __shfl_xor(l, o, 64);
-        const float m_n = fmaxf(m, m_o);
-        const float a = __expf(m - m_n), bsc = __expf(m_o - m_n);
-        l = l * a + l_o * bsc;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) acc[e] = acc[e] * a + __shfl_xor(acc[e], o, 64) * bsc;
-        m = m_n;
-    }
-    if (lane < LPK) {
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) s_acc[wave][c * EPL + e] = acc[e];
-        if (lane == 0) {
-            s_m[wave] = m;
-            s_l[wave] = l;
-        }
-    }
+    WIPA_LANE_MERGE(LPK, 64, EPL, m, l, acc);
+    WIPA_WAVE_MERGE_STORE(s_acc, s_m, s_l, m, l, acc);
     __syncthreads();
-    if (tid < 64) {
-        const float mm = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
-        float num = 0.f, den = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const float sc = __expf(s_m[w] - mm);
-            num += s_acc[w][tid] * sc;
-            den += s_l[w] * sc;
-        }
-        reinterpret_cast<T*>(p.out)[(int64_t)b * d + h * 64 + tid] = from_f32<T>(num / den);
-    }
+    if (tid < 64) WIPA_WAVE_MERGE_OUT(s_acc, s_m, s_l, tid, reinterpret_cast<T*>(p.out)[(int64_t)b * d + h * 64 + tid]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -703,40 +637,13 @@ __global__ __launch_bounds__(256, 3) void decode_cross_block_pre_kernel(CrossBlo
     float m = NEG_BIG, l = 0.f, acc[EPL];
 #pragma unroll
     for (int e = 0; e < EPL; ++e) acc[e] = 0.f;
-    auto key_group = [&](const Vec16<T> (&ka)[U], const Vec16<T> (&va)[U], int t0) {
-        float s[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            float a = 0.f;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) a = fmaf(qf[e], ka[u].get(e), a);
-#pragma unroll
-            for (int o = 1; o < LPK; o <<= 1) a += __shfl_xor(a, o, 64);
-            s[u] = (t0 + u * G + g < Tk) ? a : NEG_BIG;
-        }
-        float m_new = m;
-#pragma unroll
-        for (int u = 0; u < U; ++u) m_new = fmaxf(m_new, s[u]);
-        const float alpha = __expf(m - m_new);
-        l *= alpha;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) acc[e] *= alpha;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const float pr = (s[u] <= NEG_TEST) ? 0.f : __expf(s[u] - m_new);
-            l += pr;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) acc[e] = fmaf(pr, va[u].get(e), acc[e]);
-        }
-        m = m_new;
-    };
+    // (a lambda on purpose: the step expanded straight at its two call sites compiles to other code)
+    auto key_group = [&](const Vec16<T> (&ka)[U], const Vec16<T> (&va)[U], int t0) { WIPA_STREAM_STEP(U, qf, ka, va, t0, m, l, acc); };
     auto load_step = [&](Vec16<T> (&ka)[U], Vec16<T> (&va)[U], int t0) {
 #pragma unroll
-        for (int u = 0; u < U; ++u)
-            ka[u].v = __builtin_nontemporal_load(reinterpret_cast<const VT*>(Kb + (int64_t)min(t0 + u * G + g, Tk - 1) * 64));
+        for (int u = 0; u < U; ++u) ka[u] = load_row_clamped(Kb, t0 + u * G + g, Tk - 1, 64);
 #pragma unroll
-        for (int u = 0; u < U; ++u)
-            va[u].v = __builtin_nontemporal_load(reinterpret_cast<const VT*>(Vb + (int64_t)min(t0 + u * G + g, Tk - 1) * 64));
+        for (int u = 0; u < U; ++u) va[u] = load_row_clamped(Vb, t0 + u * G + g, Tk - 1, 64);
     };
     const int t_first = wave * G * U;
     Vec16<T> kn[U], vn[U];
@@ -769,37 +676,10 @@ __global__ __launch_bounds__(256, 3) void decode_cross_block_pre_kernel(CrossBlo
         if (t0 + STEP < Tk) load_step(kn, vn, t0 + STEP);
         key_group(ka, va, t0);
     }
-#pragma unroll
-    for (int o = LPK; o < 64; o <<= 1) {
-        const float m_o = __shfl_xor(m, o, 64);
-        const float l_o = __shfl_xor(l, o, 64);
-        const float m_n = fmaxf(m, m_o);
-        const float a = __expf(m - m_n), bsc = __expf(m_o - m_n);
-        l = l * a + l_o * bsc;
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) acc[e] = acc[e] * a + __shfl_xor(acc[e], o, 64) * bsc;
-        m = m_n;
-    }
-    if (lane < LPK) {
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) s_acc[wave][c * EPL + e] = acc[e];
-        if (lane == 0) {
-            s_m[wave] = m;
-            s_l[wave] = l;
-        }
-    }
+    WIPA_LANE_MERGE(LPK, 64, EPL, m, l, acc);
+    WIPA_WAVE_MERGE_STORE(s_acc, s_m, s_l, m, l, acc);
     __syncthreads();
-    if (tid < 64) {
-        const float mm = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
-        float num = 0.f, den = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const float sc = __expf(s_m[w] - mm);
-            num += s_acc[w][tid] * sc;
-            den += s_l[w] * sc;
-        }
-        reinterpret_cast<T*>(p.out)[(int64_t)b * d + h * 64 + tid] = from_f32<T>(num / den);
-    }
+    if (tid < 64) WIPA_WAVE_MERGE_OUT(s_acc, s_m, s_l, tid, reinterpret_cast<T*>(p.out)[(int64_t)b * d + h * 64 + tid]);
 }
 
 #undef XBAR
