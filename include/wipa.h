@@ -48,6 +48,36 @@ int wipa_stream_create(wipa_stream_t* out);
 int wipa_stream_create_cu_limited(int n_cus, wipa_stream_t* out);
 int wipa_stream_destroy(wipa_stream_t s);
 
+/* ------------------------------------------------------------------ K0 audio ingest
+ * replaces the host side of load_audio -> pad_or_trim at scripts/ipa_data_loader.py:44,80, scripts/transcribe_single.py:43-44,
+ * scripts/evaluate_model.py:63: raw interleaved PCM (the bytes of a WAV data chunk, as read) -> mono f32 at 16 kHz, zero-padded or
+ * cut to 30 s, one launch for a batch whose clips may differ in rate, sample format and channel count.
+ *   x[i]  = mean over the channels (f32, channel order) of the samples of frame i, scaled (u - 128) / 128 | / 32768 | / 2147483648;
+ *   y[m]  = sum_{k=-K..K} T[p][k+K] * x[q+k],  q = (m S) div D,  p = (m S) mod D,  x = 0 outside [0, n_frames),  for m < n_out;
+ *   y[m]  = 0 for n_out <= m < 480000 (every element of audio_out [batch, 480000] f32 is written).
+ * S / D = rate / 16000 in lowest terms; T = the clip's table, D x (2K+1) f32 at tables + table_offset: the Hann-windowed sinc
+ * cutoff sinc(cutoff dt) (0.5 + 0.5 cos(pi clip(dt / half, -1, 1))), dt = p / D - k, cutoff = min(1, D / S), half = 16 / cutoff,
+ * K = ceil(half) (whisper_ipa_amd.audio.resample_table builds it); rate = 16000 is S = D = 1, K = 0, T = [1], bit-exact.
+ * n_frames: the frames present at byte_offset -- a caller need not upload more than ceil(480000 S / D) + K + 1 of a long clip;
+ * n_out = min(480000, ceil(frames of the whole clip * D / S)).  byte_offset is a multiple of the sample size.
+ * Supported: 4000 <= rate <= 192000 Hz, 1..8 channels.  pcm (pcm_bytes long), descs, tables (tables_floats long) and audio_out are
+ * device pointers; descs_host is the same descriptor array in HOST memory: every clip is checked against the limits and the two
+ * buffer sizes before the launch, and a clip outside them is an error (WIPA_ERR_ARG, wipa_last_error names the clip). */
+enum { WIPA_PCM_U8 = 1, WIPA_PCM_S16 = 2, WIPA_PCM_S32 = 4 }; /* = bytes per sample */
+#define WIPA_RESAMPLE_TILE 512 /* consecutive outputs per workgroup */
+typedef struct wipa_pcm_clip {
+    int64_t byte_offset;  /* of the clip's first frame, from pcm */
+    int64_t table_offset; /* of the clip's table, in floats from tables */
+    int32_t n_frames;     /* frames uploaded */
+    int32_t n_out;        /* outputs before the zero tail */
+    int32_t n_channels;
+    int32_t format;       /* WIPA_PCM_* */
+    int32_t rate;         /* source rate, Hz */
+    int32_t S, D, K;
+} wipa_pcm_clip;
+int wipa_resample_pad(const void* pcm, size_t pcm_bytes, const wipa_pcm_clip* descs, const wipa_pcm_clip* descs_host, int batch,
+                      const float* tables, size_t tables_floats, float* audio_out, wipa_stream_t s);
+
 /* ------------------------------------------------------------------ K1 log-mel
  * replaces mlx_whisper.audio.log_mel_spectrogram (+ pad_or_trim) at
  * scripts/ipa_data_loader.py:80-82, scripts/transcribe_single.py:44-45,

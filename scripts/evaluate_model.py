@@ -33,7 +33,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from evaluate_ipa import evaluate_batch  # noqa: E402
 from whisper_ipa_amd import parallel  # noqa: E402
-from whisper_ipa_amd.audio import load_audio, pad_or_trim  # noqa: E402
+from whisper_ipa_amd.audio import PcmBatch, load_audio, pad_or_trim, read_pcm  # noqa: E402
 from whisper_ipa_amd.decoding import DecodingOptions  # noqa: E402
 from whisper_ipa_amd.load_models import load_model, overlay_decoder_weights  # noqa: E402
 from whisper_ipa_amd.pipeline import transcribe_batches  # noqa: E402
@@ -54,30 +54,40 @@ def load_checkpoint_model(checkpoint_path: str, base_model: str = "mlx-community
     return model
 
 
-def load_clips(audio_paths: List[str]):
-    """host side of reference :184-189 for a list of clips: (audio [n_ok, 480000] f32 or None, positions of the readable clips);
-    a clip that cannot be read is reported and yields "" (:202-204)."""
+INGEST_MODES = ("device", "host")
+
+
+def load_clips(audio_paths: List[str], ingest: str = "device"):
+    """host side of reference :184-189 for a list of clips: (batch or None, positions of the readable clips); a clip that cannot
+    be read is reported and yields "" (:202-204).  ``ingest="device"``: the batch is a ``PcmBatch`` -- the files' PCM bytes packed
+    for one copy; conversion, resampling and the 30 s pad run on the GPU (whisper_ipa_amd.audio.load_audio_batch).
+    ``ingest="host"``: audio [n_ok, 480000] f32 from ``pad_or_trim(load_audio(path))`` in numpy, as before."""
+    if ingest not in INGEST_MODES:
+        raise ValueError(f"ingest must be one of {INGEST_MODES}, got {ingest!r}")
     clips, slots = [], []
     for i, path in enumerate(audio_paths):
         try:
-            clips.append(np.asarray(pad_or_trim(load_audio(path)), dtype=np.float32))
+            clips.append(read_pcm(path) if ingest == "device" else np.asarray(pad_or_trim(load_audio(path)), dtype=np.float32))
             slots.append(i)
         except Exception as e:
             print(f"\nError transcribing {path}: {e}")
-    return (torch.from_numpy(np.stack(clips)) if clips else None), slots
+    if not clips:
+        return None, slots
+    return (PcmBatch(clips) if ingest == "device" else torch.from_numpy(np.stack(clips))), slots
 
 
 def transcribe_clips(model, audio_paths: List[str], options: DecodingOptions, batch_size: int = 64,
-                     passes_in_flight: int = 4, progress=None) -> List[str]:
+                     passes_in_flight: int = 4, progress=None, ingest: str = "device") -> List[str]:
     """reference :181-212 for the whole list: ``batch_size`` clips per batch, ``passes_in_flight`` batches in flight on one GPU
-    (whisper_ipa_amd.pipeline.transcribe_batches: log-mel -> encoder -> greedy decode per batch on its own stream set, the
-    files of the next batches read on a helper thread meanwhile).  One text per path, "" where the file could not be read."""
+    (whisper_ipa_amd.pipeline.transcribe_batches: (ingest ->) log-mel -> encoder -> greedy decode per batch on its own stream
+    set, the files of the next batches read on a helper thread meanwhile).  One text per path, "" where the file could not be
+    read.  ``ingest``: where the samples are converted and resampled (``load_clips``); 16 kHz files give the same bits either way."""
     texts = [""] * len(audio_paths)
     metas = []  # (first clip of the batch, positions of its readable clips), in submission order
 
     def batches():
         for b in range(0, len(audio_paths), batch_size):
-            audio, slots = load_clips(audio_paths[b:b + batch_size])
+            audio, slots = load_clips(audio_paths[b:b + batch_size], ingest)
             if audio is None:
                 continue
             metas.append((b, slots))
@@ -100,7 +110,7 @@ def transcribe_batch(model, audio_paths: List[str], n_mels: int, options: Decodi
 
 def evaluate_model(model_path: str, test_data_path: str, num_samples: Optional[int] = None, model_name: str = "Model",
                    is_checkpoint: bool = False, n_mels: int = 80, base_model: str = "mlx-community/whisper-small-mlx",
-                   batch_size: int = 64, passes_in_flight: int = 4) -> Dict:
+                   batch_size: int = 64, passes_in_flight: int = 4, ingest: str = "device") -> Dict:
     rank, world_size = parallel.world()
     say = print if rank == 0 else (lambda *a, **k: None)
     say("=" * 70)
@@ -130,7 +140,7 @@ def evaluate_model(model_path: str, test_data_path: str, num_samples: Optional[i
     mine = test_data[lo:hi]
     say("\nTranscribing test samples...")
     local_hyp = transcribe_clips(model, [s["audio_path"] for s in mine], options, batch_size=batch_size,
-                                 passes_in_flight=passes_in_flight,
+                                 passes_in_flight=passes_in_flight, ingest=ingest,
                                  progress=lambda n: say(f"  {n}/{len(mine)} clips on rank 0", flush=True))
     hypotheses = local_hyp
     if world_size > 1:
@@ -201,6 +211,9 @@ def main(argv=None) -> Dict:
     ap.add_argument("--batch-size", type=int, default=64, help="clips decoded together per GPU")
     ap.add_argument("--passes-in-flight", type=int, default=4,
                     help="batches kept in flight on one GPU (whisper_ipa_amd.pipeline.transcribe_batches); 1 = one batch at a time")
+    ap.add_argument("--ingest", choices=INGEST_MODES, default="device",
+                    help="where the files' samples are converted, resampled to 16 kHz and padded: on the GPU (default) or in numpy "
+                         "on the host (16 kHz files give the same bits either way)")
     ap.add_argument("--results-json", type=str, default=None, help="also write both result dicts here (rank 0)")
     ap.add_argument("--allow-byte-fallback", action="store_true",
                     help="run without the Whisper vocabulary (WIPA_TIKTOKEN unset): hypotheses render ids >= 256 as <|idN|>; "
@@ -222,10 +235,10 @@ def main(argv=None) -> Dict:
     if not args.skip_base:
         base_results = evaluate_model(args.base_model, args.test_data, num_samples, model_name="Base Whisper Model",
                                       is_checkpoint=False, n_mels=args.n_mels, base_model=args.base_model, batch_size=args.batch_size,
-                                      passes_in_flight=args.passes_in_flight)
+                                      passes_in_flight=args.passes_in_flight, ingest=args.ingest)
     trained_results = evaluate_model(args.checkpoint, args.test_data, num_samples, model_name="Trained Checkpoint",
                                      is_checkpoint=True, n_mels=args.n_mels, base_model=args.base_model, batch_size=args.batch_size,
-                                      passes_in_flight=args.passes_in_flight)
+                                     passes_in_flight=args.passes_in_flight, ingest=args.ingest)
     if rank == 0:
         if base_results:
             compare_models(base_results, trained_results)

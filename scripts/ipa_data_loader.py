@@ -15,12 +15,11 @@ import sys
 from pathlib import Path
 from typing import Dict, List, Optional
 
-import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from whisper_ipa_amd.audio import N_SAMPLES, load_audio, log_mel_spectrogram, pad_or_trim  # noqa: E402
+from whisper_ipa_amd.audio import load_audio, load_audio_batch, log_mel_spectrogram  # noqa: E402
 
 
 class IPADataset:
@@ -79,10 +78,10 @@ class IPADataset:
         need = [True] * len(indices) if audio_for is None else [bool(f) for f in audio_for]
         assert len(need) == len(indices)
         entries = [self.data[i] for i in indices]
-        samples = [self[i] for i, f in zip(indices, need) if f]
+        paths = [os.path.join(self.audio_root, e["audio_path"]) if self.audio_root else e["audio_path"] for e, f in zip(entries, need) if f]
         mel = None
-        if samples:
-            audio = np.stack([pad_or_trim(s["audio"], N_SAMPLES) for s in samples])
+        if paths:
+            audio = load_audio_batch(paths)  # load_audio + pad_or_trim (:44,80) of the flagged clips: one copy, one launch
             mel = log_mel_spectrogram(audio, n_mels=self.n_mels)  # [n_flagged, 3000, n_mels] on the GPU, one launch
         texts = [e["ipa_transcription"] for e in entries]
         tokens = self.tokenize_batch(texts)

@@ -1,6 +1,6 @@
 """Inference entry point with the behaviour of the reference's scripts/transcribe_single.py:
 base model -> fp32 -> overlay the fine-tuned ``decoder.*`` tensors of ``<checkpoint>/model.safetensors``
-(reference :10-39), then load_audio -> pad_or_trim -> log_mel_spectrogram -> model.encoder -> greedy
+(reference :10-39), then load_audio -> pad_or_trim (one GPU launch: load_audio_batch) -> log_mel_spectrogram -> model.encoder -> greedy
 ``decode(language="en", without_timestamps=True)`` -> ``result[0].text.strip()`` (reference :41-56).
 
 The reference hard-codes its three paths (:10,59-60) and fetches the base model by hub name; here
@@ -18,7 +18,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from whisper_ipa_amd.audio import load_audio, log_mel_spectrogram, pad_or_trim  # noqa: E402
+from whisper_ipa_amd.audio import load_audio_batch, log_mel_spectrogram  # noqa: E402
 from whisper_ipa_amd.decoding import DecodingOptions, decode  # noqa: E402
 from whisper_ipa_amd.load_models import load_model, overlay_decoder_weights  # noqa: E402
 
@@ -40,8 +40,8 @@ def load_checkpoint_model(checkpoint_path: str, base_model: str = "mlx-community
 
 def transcribe_file(model, audio_path: str) -> str:
     print(f"Transcribing {audio_path}...")
-    audio = pad_or_trim(load_audio(audio_path))
-    mel = log_mel_spectrogram(audio, n_mels=model.dims.n_mels)[None].to(torch.float32)
+    audio = load_audio_batch([audio_path])  # load_audio -> pad_or_trim (reference :43-44) on the GPU: [1, 480000]
+    mel = log_mel_spectrogram(audio, n_mels=model.dims.n_mels).to(torch.float32)
     options = DecodingOptions(language="en", without_timestamps=True)  # IPA is decoded "as English"
     audio_features = model.encoder(mel)
     result = decode(model, audio_features, options)

@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libwipa.so")
 
 WIPA_F32, WIPA_BF16, WIPA_FP8_E4M3 = 0, 1, 2
 GREEDY_PARTS = 2048  # WIPA_GREEDY_PARTS
+RESAMPLE_TILE = 512  # WIPA_RESAMPLE_TILE
 ENC_GLOBAL, ENC_PER_LAYER = 7, 14
 DEC_GLOBAL, DEC_PER_LAYER, DEC_FP8_PER_LAYER = 4, 20, 6
 GEMM_DISPATCH = ("tile128", "tile256", "tile384", "tile384n", "tile256p", "skinny", "skinny_fp8", "skinny_ln", "kmajor", "split_k",
@@ -77,6 +78,12 @@ class AttnDesc(C.Structure):
     ]
 
 
+class PcmClipDesc(C.Structure):
+    """wipa_pcm_clip"""
+    _fields_ = [("byte_offset", c_int64), ("table_offset", c_int64)] + [(n, C.c_int32) for n in (
+        "n_frames", "n_out", "n_channels", "format", "rate", "S", "D", "K")]
+
+
 class ModelCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "n_mels", "n_audio_ctx", "n_audio_state", "n_audio_head", "n_audio_layer",
@@ -99,6 +106,7 @@ SIGNATURES = {
     "wipa_stream_create": (c_int, [C.POINTER(c_void_p)]),
     "wipa_stream_create_cu_limited": (c_int, [c_int, C.POINTER(c_void_p)]),
     "wipa_stream_destroy": (c_int, [c_void_p]),
+    "wipa_resample_pad": (c_int, [c_void_p, c_size_t, c_void_p, _P(PcmClipDesc), c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     "wipa_logmel_tables_bytes": (c_size_t, [c_int]),
     "wipa_logmel_init": (c_int, [c_void_p, c_int, c_void_p]),
     "wipa_logmel_workspace_bytes": (c_size_t, [c_int, c_int]),

@@ -4,11 +4,20 @@
 
 ``log_mel_spectrogram`` runs on the GPU (K1, csrc/logmel.hip).  ``load_audio`` reads WAV
 files directly: the reference shells out to ffmpeg, which this image does not have.
+
+``load_audio_batch`` is ``pad_or_trim(load_audio(file))`` for a batch of files on the GPU (K0, csrc/resample.hip): the host only
+reads the PCM bytes (``read_pcm``) and packs them (``PcmBatch``); sample conversion, channel mix-down, resampling to 16 kHz and the
+30 s pad / cut are one copy and one launch.  ``load_audio`` / ``_resample`` stay as the host path and as the kernel's reference.
 """
 from __future__ import annotations
 
+import ctypes as C
+import math
+import os
 import wave
-from typing import Union
+from collections import OrderedDict
+from dataclasses import dataclass
+from typing import Iterable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -48,6 +57,12 @@ def load_audio(file: str, sr: int = SAMPLE_RATE) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def _sinc_window(dt: np.ndarray, cutoff: float, half: float) -> np.ndarray:
+    """weight of a tap ``dt`` input samples away from the output position: the low-pass sinc at ``cutoff`` (of the input Nyquist)
+    under a Hann window of half-width ``half`` -- the one spelling ``_resample`` and ``resample_table`` share"""
+    return cutoff * np.sinc(cutoff * dt) * (0.5 + 0.5 * np.cos(np.pi * np.clip(dt / half, -1.0, 1.0)))
+
+
 def _resample(a: np.ndarray, src: int, dst: int, zero_crossings: int = 16) -> np.ndarray:
     """Windowed-sinc (Hann, ``zero_crossings`` lobes each side) resampling, evaluated per OUTPUT sample -- the polyphase
     form: output m sits at input position m*src/dst and sums the 2*zero_crossings/cutoff input samples around it, so the work
@@ -69,7 +84,7 @@ def _resample(a: np.ndarray, src: int, dst: int, zero_crossings: int = 16) -> np
         base = np.floor(pos).astype(np.int64)
         idx = base[:, None] + k[None, :]
         dt = pos[:, None] - idx                # distance of every tap from the output position, in input samples
-        w = cutoff * np.sinc(cutoff * dt) * (0.5 + 0.5 * np.cos(np.pi * np.clip(dt / half, -1.0, 1.0)))
+        w = _sinc_window(dt, cutoff, half)
         ok = (idx >= 0) & (idx < n_in)
         y[m] = (w * np.where(ok, x[np.clip(idx, 0, n_in - 1)], 0.0)).sum(axis=1)
     return y.astype(np.float32)
@@ -95,6 +110,198 @@ def pad_or_trim(array: ArrayLike, length: int = N_SAMPLES, axis: int = -1) -> Ar
         widths[axis] = (0, length - n)
         array = np.pad(array, widths)
     return array
+
+
+# ---- device-side ingest (K0, csrc/resample.hip): raw PCM -> [B, 480000] f32 at 16 kHz on the GPU ---------------------------------
+
+MIN_RATE, MAX_RATE = 4000, 192000     # source rates wipa_resample_pad accepts
+RESAMPLE_TILE = _lib.RESAMPLE_TILE    # consecutive outputs per workgroup (WIPA_RESAMPLE_TILE)
+TABLE_CACHE_ENTRIES = 8               # resampling tables kept per process (44 099 Hz -> 16 kHz is 5.8 MB; common rates are KBs)
+
+
+def _resample_geometry(src: int, dst: int = SAMPLE_RATE, zero_crossings: int = 16) -> Tuple[int, int, int]:
+    """(S, D, K): src / dst in lowest terms and the filter half-width in input samples, as ``_resample`` takes it"""
+    src, dst = int(src), int(dst)
+    if src <= 0 or dst <= 0:
+        raise ValueError(f"sample rates must be positive, got {src} -> {dst}")
+    g = math.gcd(src, dst)
+    if src == dst:
+        return 1, 1, 0
+    half = zero_crossings / min(1.0, dst / src)
+    return src // g, dst // g, int(np.ceil(half))
+
+
+def resample_table(src: int, dst: int = SAMPLE_RATE) -> Tuple[int, int, int, np.ndarray]:
+    """``_resample`` as an exact polyphase table.  Output m sits at input position m S / D (S / D = src / dst in lowest terms):
+    with q = (m S) div D and p = (m S) mod D,  y[m] = sum_{k=-K..K} T[p][k + K] x[q + k]  (x = 0 outside the clip).
+    Returns (S, D, K, T [D, 2K+1]) with T in float64, as ``_resample`` evaluates it; the device copy is T rounded once to f32.
+    src == dst is (1, 1, 0, [[1.0]]).  Host only."""
+    S, D, K = _resample_geometry(src, dst)
+    if K == 0:
+        return S, D, K, np.ones((1, 1), dtype=np.float64)
+    cutoff = min(1.0, dst / src)
+    half = 16 / cutoff
+    dt = np.arange(D, dtype=np.float64)[:, None] / D - np.arange(-K, K + 1, dtype=np.float64)[None, :]
+    return S, D, K, _sinc_window(dt, cutoff, half)
+
+
+def pcm_frame_cap(rate: int, sr: int = SAMPLE_RATE) -> int:
+    """frames of a clip at ``rate`` Hz that the 30 s output window can touch: the last output sits at input position
+    479 999 S / D and reaches K frames further"""
+    S, D, K = _resample_geometry(rate, sr)
+    return -(-N_SAMPLES * S // D) + K + 1
+
+
+@dataclass
+class PcmClip:
+    """The PCM of one file as stored: ``data`` holds ``n_frames`` interleaved frames of ``n_channels`` samples of ``width`` bytes
+    (1: unsigned, 2 / 4: signed little-endian) at ``rate`` Hz.  ``total_frames``: frames of the whole clip when ``data`` is only
+    its head (None: ``n_frames``) -- it sets where the resampled clip ends."""
+    data: bytes
+    n_frames: int
+    n_channels: int
+    width: int
+    rate: int
+    total_frames: Optional[int] = None
+
+
+def _check_pcm_format(n_channels: int, width: int, rate: int) -> None:
+    if width not in (1, 2, 4):
+        raise ValueError(f"unsupported WAV sample width {width}")
+    if not 1 <= n_channels <= 8:
+        raise ValueError(f"unsupported channel count {n_channels} (1..8)")
+    if not MIN_RATE <= rate <= MAX_RATE:
+        raise ValueError(f"unsupported sample rate {rate} Hz ({MIN_RATE}..{MAX_RATE} Hz)")
+
+
+def read_pcm(file: str, sr: int = SAMPLE_RATE) -> PcmClip:
+    """The header and the raw frames of a PCM WAV file, unconverted; no more frames than the 30 s window can touch
+    (``pcm_frame_cap``).  Host only."""
+    with wave.open(file, "rb") as w:
+        n_ch, width, rate, n = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
+        _check_pcm_format(n_ch, width, rate)
+        cap = pcm_frame_cap(rate, sr)
+        raw = w.readframes(min(n, cap))
+    got = len(raw) // (n_ch * width)
+    return PcmClip(raw, got, n_ch, width, rate, total_frames=n if (n > cap and got == cap) else got)
+
+
+class PcmBatch:
+    """Clips packed for ONE host-to-device copy: ``buffer`` (uint8, pinned when a GPU is present) = the ``wipa_pcm_clip``
+    descriptors, then every clip's bytes (16-byte aligned, cut to ``pcm_frame_cap`` frames).  ``rates`` lists the distinct source
+    rates in order of first appearance; their tables are expected back to back (each start rounded up to 4 floats) in that
+    order -- ``table_offsets`` -- which is how ``load_audio_batch`` lays them out.  Host only: no GPU work happens here."""
+
+    ALIGN = 16
+
+    def __init__(self, clips: Iterable[Union[str, "os.PathLike", PcmClip]], sr: int = SAMPLE_RATE, pin: Optional[bool] = None):
+        if sr != SAMPLE_RATE:
+            raise ValueError(f"the device path resamples to {SAMPLE_RATE} Hz")
+        clips = [c if isinstance(c, PcmClip) else read_pcm(os.fspath(c), sr) for c in clips]
+        if not clips:
+            raise ValueError("PcmBatch needs at least one clip")
+        self.B = len(clips)
+        self.descs = (_lib.PcmClipDesc * self.B)()
+        self.rates: List[int] = []
+        self.table_offsets: List[int] = []
+        self.table_floats = 0
+        off = -(-C.sizeof(self.descs) // 256) * 256
+        for d, c in zip(self.descs, clips):
+            _check_pcm_format(c.n_channels, c.width, c.rate)
+            frame = c.n_channels * c.width
+            if c.n_frames < 0 or len(c.data) < c.n_frames * frame:
+                raise ValueError(f"PcmClip holds {len(c.data)} bytes, fewer than its {c.n_frames} frames of {frame}")
+            S, D, K = _resample_geometry(c.rate, sr)
+            if c.rate not in self.rates:
+                self.rates.append(c.rate)
+                self.table_offsets.append(self.table_floats)
+                self.table_floats += -(-D * (2 * K + 1) // 4) * 4
+            total = c.n_frames if c.total_frames is None else max(int(c.total_frames), c.n_frames)
+            d.byte_offset, d.table_offset = off, self.table_offsets[self.rates.index(c.rate)]
+            d.n_frames = min(c.n_frames, pcm_frame_cap(c.rate, sr))
+            d.n_out = min(N_SAMPLES, -(-total * D // S))
+            d.n_channels, d.format, d.rate, d.S, d.D, d.K = c.n_channels, c.width, c.rate, S, D, K
+            off += -(-d.n_frames * frame // self.ALIGN) * self.ALIGN
+        self.nbytes = max(off, self.ALIGN)
+        pin = torch.cuda.is_available() if pin is None else pin
+        self.buffer = torch.empty(self.nbytes, dtype=torch.uint8, pin_memory=bool(pin))
+        view = self.buffer.numpy()
+        view[: C.sizeof(self.descs)] = np.frombuffer(self.descs, dtype=np.uint8)
+        for d, c in zip(self.descs, clips):
+            n = d.n_frames * c.n_channels * c.width
+            view[d.byte_offset: d.byte_offset + n] = np.frombuffer(c.data, dtype=np.uint8, count=n)
+
+    def __len__(self) -> int:
+        return self.B
+
+
+_resample_tables: "OrderedDict" = OrderedDict()   # (device index, src, dst) -> device table; small LRU
+_table_sets: "OrderedDict" = OrderedDict()        # (device index, rates) -> (concatenated tables, the single tables it was built from)
+
+
+def _device_table(dev: torch.device, src: int, dst: int = SAMPLE_RATE) -> torch.Tensor:
+    """the table of one rate on the device, built on the host once per (device, src, dst) and kept in an LRU"""
+    key = (dev.index, int(src), int(dst))
+    t = _resample_tables.get(key)
+    if t is not None:
+        _resample_tables.move_to_end(key)
+        return t
+    T = resample_table(src, dst)[3]
+    t = torch.from_numpy(T.astype(np.float32).reshape(-1)).to(dev)
+    torch.cuda.current_stream().synchronize()  # once per rate: other library streams read it without ordering against this one
+    _resample_tables[key] = t
+    if len(_resample_tables) > TABLE_CACHE_ENTRIES:
+        torch.cuda.synchronize(dev)  # a launch on another stream may still read what is dropped
+        old, _ = _resample_tables.popitem(last=False)
+        for k in [k for k in _table_sets if k[0] == old[0] and old[1] in k[1]]:
+            del _table_sets[k]
+    return t
+
+
+def _tables_for(dev: torch.device, batch: PcmBatch) -> torch.Tensor:
+    """the batch's tables as one buffer laid out as its descriptors say (``PcmBatch.table_offsets``)"""
+    if len(batch.rates) == 1:
+        return _device_table(dev, batch.rates[0])
+    key = (dev.index, tuple(batch.rates))
+    hit = _table_sets.get(key)
+    if hit is not None:
+        _table_sets.move_to_end(key)
+        return hit
+    buf = torch.zeros(batch.table_floats, dtype=torch.float32, device=dev)
+    for rate, off in zip(batch.rates, batch.table_offsets):
+        t = _device_table(dev, rate)
+        buf[off: off + t.numel()].copy_(t)
+    torch.cuda.current_stream().synchronize()
+    _table_sets[key] = buf
+    if len(_table_sets) > TABLE_CACHE_ENTRIES:
+        torch.cuda.synchronize(dev)
+        _table_sets.popitem(last=False)
+    return buf
+
+
+def _ingest(batch: PcmBatch, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, tuple]:
+    """copy + launch on the current library stream; returns (audio, what must stay alive until the launch has run)"""
+    L = _lib.lib()
+    dev = device()
+    with on_stream() as s:
+        tables = _tables_for(dev, batch)
+        pcm = torch.empty(batch.nbytes, dtype=torch.uint8, device=dev)
+        pcm.copy_(batch.buffer, non_blocking=True)  # descriptors and samples: one copy
+        if out is None:
+            out = torch.empty(batch.B, N_SAMPLES, dtype=torch.float32, device=dev)
+        assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (batch.B, N_SAMPLES) and out.is_contiguous()
+        _lib.check(L.wipa_resample_pad(ptr(pcm), batch.nbytes, ptr(pcm), batch.descs, batch.B, ptr(tables), tables.numel(), ptr(out),
+                                       sptr(s)), "wipa_resample_pad")
+    return out, (batch, pcm, tables)
+
+
+def load_audio_batch(clips: Union[PcmBatch, Sequence[Union[str, PcmClip]]], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``pad_or_trim(load_audio(file))`` for a batch, on the GPU: files (PCM WAV), ``PcmClip``s or a ``PcmBatch`` ->
+    audio [B, 480000] f32 on the device.  One host-to-device copy and one launch (csrc/resample.hip) on the current library
+    stream; 16 kHz input is bit-identical to the host path, other rates agree to f32 rounding of the same filter.
+    ``out``: an existing [B, 480000] f32 device tensor to write into (every element is written)."""
+    batch = clips if isinstance(clips, PcmBatch) else PcmBatch(clips)
+    return _ingest(batch, out)[0]
 
 
 _tables = {}

@@ -238,12 +238,19 @@ class TranscribePipeline:
             self._splits_before = None
 
     # ---- one pass
-    def _features(self, batch) -> torch.Tensor:
-        """audio [B, samples] (padded / cut to 30 s) | mel [B, 3000, n_mels] | features [B, 1500, d] -> features, enqueued on the
-        current library stream"""
+    def _features(self, batch, keep: Optional[list] = None) -> torch.Tensor:
+        """raw PCM (``audio.PcmBatch``) | audio [B, samples] (padded / cut to 30 s) | mel [B, 3000, n_mels] | features [B, 1500, d]
+        -> features, enqueued on the current library stream.  ``keep`` receives what the enqueued work still reads."""
         m, d = self.model, self.model.dims
         if isinstance(batch, dict):
-            batch = batch.get("audio_features", batch.get("mel_features", batch.get("audio")))
+            batch = batch["pcm"] if "pcm" in batch else batch.get("audio_features", batch.get("mel_features", batch.get("audio")))
+        if isinstance(batch, A.PcmBatch):
+            # device-side ingest on the pass's own stream: one copy of the packed bytes, one launch, then log-mel.  The pinned
+            # staging buffer, the device copy and the tables belong to this pass until it is collected: the caller may drop the
+            # batch as soon as it has handed it over, and the copy and the launch run later, unordered against any other stream
+            batch, held = A._ingest(batch)  # audio [B, 480000] f32 on the device: the audio branch below takes it from here
+            if keep is not None:
+                keep.extend(held)
         t = torch.as_tensor(batch)
         if t.dim() == 3 and tuple(t.shape[-2:]) == (d.n_audio_ctx, d.n_audio_state):
             feats = t.to(device=m.device, non_blocking=True)
@@ -285,7 +292,8 @@ class TranscribePipeline:
         with use_stream(slot) as s:
             if cur != s:
                 s.wait_stream(cur)  # the batch may have been produced on the caller's stream
-            parts = [self._features(b) for b, _ in group]  # log-mel + encoder per batch, as without groups
+            held: list = []
+            parts = [self._features(b, held) for b, _ in group]  # (ingest +) log-mel + encoder per batch, as without groups
             sizes = tuple(int(f.shape[0]) for f in parts)
             feats = parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)  # the group's rows decode as one chain
             del parts
@@ -296,7 +304,7 @@ class TranscribePipeline:
             st = _state_for(m, B, pk)
             m_always = _mask(m, self.always)
             m_first = _mask(m, list(self.always) + list(self.first))
-            keep = [feats, m_always, m_first]
+            keep = [feats, m_always, m_first] + held
             cfg, tab, blob, nb = C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel()
             _lib.check(L.wipa_decoder_set_audio(cfg, tab, ptr(feats), blob, nb, B, sptr(s)), "wipa_decoder_set_audio")
             lang_tok = lang_logits = None
@@ -419,8 +427,10 @@ def transcribe_batches(model, batches: Iterable, options: Optional[DecodingOptio
     """Transcribe a sequence of batches with ``passes_in_flight`` of them in flight; yields one ``PassResult`` per batch, in
     input order (``.results``: the reference's DecodingResult list; ``.texts``; ``.tokens``).
 
-    ``batches``: an iterable of audio [B, samples] (f32, host or device; padded / cut to 30 s), mel [B, 3000, n_mels] or encoder
-    features [B, 1500, d] -- or dicts carrying one of ``audio_features`` / ``mel_features`` / ``audio`` (IPADataset.get_batch).
+    ``batches``: an iterable of ``audio.PcmBatch`` (raw PCM of the files: converted, resampled and padded on the device, on the
+    pass's own stream), audio [B, samples] (f32, host or device; padded / cut to 30 s), mel [B, 3000, n_mels] or encoder
+    features [B, 1500, d] -- or dicts carrying one of ``pcm`` / ``audio_features`` / ``mel_features`` / ``audio``
+    (IPADataset.get_batch).
     It is consumed lazily, one batch per free slot.  ``prefetch`` > 0 iterates it on a helper thread that many batches ahead
     (for iterables that only do HOST work -- reading and resampling audio files; anything that enqueues GPU work should stay on
     the calling thread).
