@@ -423,6 +423,28 @@ int wipa_embed_layernorm(const int32_t* tokens, int64_t ld_tok, int B, const int
                          const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b,
                          void* y, int y_dtype, int D, float eps, wipa_stream_t s);
 
+/* ------------------------------------------------------------------ K14 PER / PFER edit distances
+ * replaces the dynamic programs behind phone_error_rate (scripts/evaluate_ipa.py:80-105: editdistance.eval on the two phone lists)
+ * and PFERCalculator.phone_feature_error_rate (:139-213: the O(m n) Python loop with a feature comparison per cell), as
+ * evaluate_batch (:346-378) runs them for every (reference, hypothesis) pair: n_pairs pairs in one launch, one wave per pair
+ * (csrc/score.hip).  Phones are ids into a per-call vocabulary of n_phones entries.
+ *   ref_ids / hyp_ids: the pairs' sequences back to back; pair p is ref_ids[ref_off[p] .. ref_off[p+1]) against hyp_ids[hyp_off[p] ..
+ *   hyp_off[p+1]); ref_off / hyp_off int32 [n_pairs + 1];  order int32 [n_pairs]: a permutation of the pairs, the order in which
+ *   the workgroups take them (the caller sorts by length product, longest first);
+ *   feat_codes uint64 [n_phones]: 24 articulatory features at 2 bits each (bits 2f, 2f+1: 0 for 0, 1 for +1, 2 for -1), or NULL;
+ *   per_dist[p]  = Levenshtein distance with unit costs (substitution: the ids differ);
+ *   pfer24[p]    = the same recurrence with insertion = deletion = 24 and substitution = the number of features that differ
+ *                  (24 x the reference's feature-weighted distance, exactly); 24 * per_dist[p] when feat_codes is NULL.
+ * All of the above are device pointers.  ref_off_host / hyp_off_host are the two offset arrays in HOST memory: they are checked
+ * before the launch -- first offset 0, non-decreasing, no sequence longer than WIPA_SCORE_MAX_LEN -- and a violation is an error
+ * (WIPA_ERR_ARG, wipa_last_error names the pair) with nothing launched.  The ids are the caller's to keep inside [0, n_phones).
+ * n_pairs = 0 succeeds without a launch. */
+#define WIPA_SCORE_MAX_LEN 1024 /* phones per sequence */
+int wipa_edit_distance_batch(const int32_t* ref_ids, const int32_t* ref_off, const int32_t* hyp_ids, const int32_t* hyp_off,
+                             const int32_t* order, int n_pairs, const uint64_t* feat_codes, int n_phones,
+                             const int32_t* ref_off_host, const int32_t* hyp_off_host,
+                             int32_t* per_dist, int32_t* pfer24, wipa_stream_t s);
+
 /* ------------------------------------------------------------------ host-side text plumbing (no GPU work)
  * Byte-level BPE of mlx_whisper.tokenizer (tiktoken's CoreBPE) and the token-batch builder of
  * IPADataset._tokenize_ipa_batch (scripts/ipa_data_loader.py:102-131, 146-152).  HOST pointers throughout.

@@ -3,8 +3,11 @@
 ``PFERCalculatorCosine`` (:216-287), ``phone_feature_error_rate[_cosine]`` (:300-343), ``evaluate_batch`` (:346-378)
 -> {'per','pfer','per_std','pfer_std','num_samples','per_scores','pfer_scores'}.
 
-Host-side string work (O(len^2) DP), not GPU work.  The reference takes the 24 articulatory features and its primary
-segmentation from ``panphon.FeatureTable``; panphon is not in this image.  The feature source is therefore pluggable:
+The string work (Unicode segmentation, feature lookup) is the host's.  The O(len^2) dynamic programs run either on the host, as
+the reference's do, or -- ``evaluate_batch(..., scoring="device")`` -- for the whole batch in one launch on the GPU
+(whisper_ipa_amd.scoring, csrc/score.hip: the same recurrences in exact integers).  The reference takes the 24 articulatory
+features and its primary segmentation from ``panphon.FeatureTable``; panphon is not in this image.  The feature source is
+therefore pluggable:
 
 * ``panphon`` when it imports;
 * else a panphon-format feature CSV named by ``WIPA_PANPHON_CSV`` (panphon's ``data/ipa_all.csv``: header
@@ -240,17 +243,107 @@ def phone_feature_error_rate_cosine(reference: str, hypothesis: str) -> float:
     return get_pfer_calculator_cosine().phone_feature_error_rate(reference, hypothesis)
 
 
-def evaluate_batch(references: List[str], hypotheses: List[str]) -> Dict:
+SCORING_MODES = ("host", "device")
+_warned_unencodable = False
+
+
+def pair_lookup_counts(ref: List[str], hyp: List[str], phones) -> Dict[str, int]:
+    """How often the host DP looks each phone of ``phones`` up while it scores one pair: ``feature_distance`` fetches both phones'
+    features in every cell whose two phone STRINGS differ, so a phone with c_r occurrences among the m reference phones and c_h
+    among the n hypothesis phones is fetched c_r (n - c_h) + c_h (m - c_r) times.  Phones never fetched are left out."""
+    out = {}
+    m, n = len(ref), len(hyp)
+    for p in phones.intersection(ref).union(phones.intersection(hyp)):
+        c_r, c_h = ref.count(p), hyp.count(p)
+        k = c_r * (n - c_h) + c_h * (m - c_r)
+        if k:
+            out[p] = k
+    return out
+
+
+def _evaluate_batch_device(references: List[str], hypotheses: List[str]) -> Optional[Dict]:
+    """``evaluate_batch`` with every DP cell on the GPU; None when a phone's features cannot be encoded (the caller then scores on
+    the host).  Tokenisation, the empty-reference rule (reference :94-96) and the feature lookup -- once per distinct phone -- stay
+    here; per = per_dist / len(ref) * 100 is the host's expression on the same integers, pfer = pfer24 / 24 / len(ref) * 100."""
+    global _warned_unencodable
+    try:
+        import whisper_ipa_amd  # noqa: F401
+    except ImportError:
+        sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from whisper_ipa_amd import scoring  # before the first torch.cuda call: the package asks for its hardware queues at import
+    import torch
+
+    if not torch.cuda.is_available():
+        raise RuntimeError('evaluate_batch(scoring="device") needs a GPU; scoring="host" runs the same metrics in Python')
+    have_features = _get_feature_table() is not None
+    calc = get_pfer_calculator() if have_features else None
+    counters = [calc.unknown_phones, getattr(calc.ft, "base_fallbacks", {})] if calc is not None else [{}, {}]
+    for c in counters:
+        c.clear()
+    n = len(references)
+    per_scores, pfer_scores = [0.0] * n, [0.0] * n
+    slots, refs, hyps = [], [], []
+    for k, (r, h) in enumerate(zip(references, hypotheses)):
+        ref, hyp = tokenize_ipa(r), tokenize_ipa(h)
+        if not ref:
+            per_scores[k] = pfer_scores[k] = 0.0 if not hyp else 100.0
+        else:
+            slots.append(k)
+            refs.append(ref)
+            hyps.append(hyp)
+    try:
+        handle = scoring.score_launch(refs, hyps, calc.get_phone_features if have_features else None)
+    except ValueError as e:  # encode_features: a table whose values are not -1 / 0 / +1
+        if not _warned_unencodable:
+            _warned_unencodable = True
+            print(f"NOTE: the feature table cannot be scored on the device ({e}); scoring on the host", file=sys.stderr, flush=True)
+        return None
+    # the one-per-distinct-phone lookups above have marked the phones the table does not know / knows by their base character
+    flagged = [set(c) for c in counters]
+    for c in counters:
+        c.clear()
+    per_dist, pfer24 = scoring.score_collect(handle)
+    fallback_pairs = 0
+    for k, ref, hyp, d_per, d_pf in zip(slots, refs, hyps, per_dist.tolist(), pfer24.tolist()):
+        if d_per < 0:  # a side longer than the kernel takes: the host functions, which also count their own lookups
+            fallback_pairs += 1
+            per_scores[k] = phone_error_rate(references[k], hypotheses[k])
+            pfer_scores[k] = phone_feature_error_rate(references[k], hypotheses[k]) if have_features else per_scores[k]
+            continue
+        per_scores[k] = d_per / len(ref) * 100.0
+        pfer_scores[k] = d_pf / 24.0 / len(ref) * 100.0 if have_features else per_scores[k]
+        for c, phones in zip(counters, flagged):
+            if phones:
+                for p, times in pair_lookup_counts(ref, hyp, phones).items():
+                    c[p] = c.get(p, 0) + times
+    empty = not per_scores
+    return {"per": 0.0 if empty else float(np.mean(per_scores)), "pfer": 0.0 if empty else float(np.mean(pfer_scores)),
+            "per_std": 0.0 if empty else float(np.std(per_scores)), "pfer_std": 0.0 if empty else float(np.std(pfer_scores)),
+            "num_samples": n, "per_scores": per_scores, "pfer_scores": pfer_scores, "pfer_is_per_fallback": not have_features,
+            "pfer_unknown_phones": dict(counters[0]) if calc is not None else {},
+            "pfer_base_fallback_phones": dict(counters[1]) if calc is not None else {},
+            "device_fallback_pairs": fallback_pairs}  # pairs beyond the kernel's length cap, scored by the host functions
+
+
+def evaluate_batch(references: List[str], hypotheses: List[str], scoring: str = "host") -> Dict:
     """reference :346-378: the RAW strings are scored (no normalisation here), per-sample scores are returned.
     Without a feature source the ``pfer`` slot carries PER and ``pfer_is_per_fallback`` is True (stderr says so once):
-    best-checkpoint selection then ranks by PER."""
+    best-checkpoint selection then ranks by PER.
+    ``scoring="device"``: the edit distances of all pairs in one GPU launch (``_evaluate_batch_device``) -- the same keys and
+    meanings, PER bit-equal, PFER equal to float64 rounding, plus ``device_fallback_pairs``; RuntimeError without a GPU."""
     global _warned
     assert len(references) == len(hypotheses), "Reference and hypothesis lists must have same length"
+    if scoring not in SCORING_MODES:
+        raise ValueError(f"scoring must be one of {SCORING_MODES}, got {scoring!r}")
     have_features = _get_feature_table() is not None
     if not have_features and not _warned:
         _warned = True
         print("WARNING: no articulatory feature table (panphon / WIPA_PANPHON_CSV): PFER is NOT computed, the 'pfer' values below "
               "are PER and best-checkpoint selection ranks by PER", file=sys.stderr, flush=True)
+    if scoring == "device":
+        results = _evaluate_batch_device(references, hypotheses)
+        if results is not None:
+            return results
     per_scores, pfer_scores = [], []
     calc = get_pfer_calculator() if have_features else None
     if calc is not None:

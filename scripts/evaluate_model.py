@@ -10,6 +10,8 @@ Differences that the hardware asks for:
     (tests/test_gpu_model.py::test_full_size_bench_workload_properties, ::test_transcribe_batches_*);
   * under ``torchrun`` every rank takes a contiguous slice of the test list with a full weight
     replica and no collective on the data path; the hypotheses are gathered once at the end;
+  * PER / PFER of the whole list are scored in one GPU launch (``--scoring device``, whisper_ipa_amd.scoring; ``host`` keeps the
+    reference's Python loops): the same integers, so the same PER and, to float64 rounding, the same PFER;
   * the base model is a local directory (no hub access) and the base-model leg uses the same
     mel -> encoder -> decode(language="en", without_timestamps=True) path as the checkpoint leg
     (the reference's base leg goes through mlx_whisper.transcribe, which wraps the same calls for
@@ -31,7 +33,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from evaluate_ipa import evaluate_batch  # noqa: E402
+from evaluate_ipa import SCORING_MODES, evaluate_batch  # noqa: E402
 from whisper_ipa_amd import parallel  # noqa: E402
 from whisper_ipa_amd.audio import PcmBatch, load_audio, pad_or_trim, read_pcm  # noqa: E402
 from whisper_ipa_amd.decoding import DecodingOptions  # noqa: E402
@@ -110,7 +112,7 @@ def transcribe_batch(model, audio_paths: List[str], n_mels: int, options: Decodi
 
 def evaluate_model(model_path: str, test_data_path: str, num_samples: Optional[int] = None, model_name: str = "Model",
                    is_checkpoint: bool = False, n_mels: int = 80, base_model: str = "mlx-community/whisper-small-mlx",
-                   batch_size: int = 64, passes_in_flight: int = 4, ingest: str = "device") -> Dict:
+                   batch_size: int = 64, passes_in_flight: int = 4, ingest: str = "device", scoring: str = "device") -> Dict:
     rank, world_size = parallel.world()
     say = print if rank == 0 else (lambda *a, **k: None)
     say("=" * 70)
@@ -151,7 +153,8 @@ def evaluate_model(model_path: str, test_data_path: str, num_samples: Optional[i
         hypotheses = [h for part in parts for h in part]
     references = [s["ipa_transcription"] for s in test_data]
 
-    results = evaluate_batch(references, hypotheses)  # per-sample scores included (reference evaluate_ipa.py:370-378)
+    # per-sample scores included (reference evaluate_ipa.py:370-378); scoring="device": every pair's edit distances in one launch
+    results = evaluate_batch(references, hypotheses, scoring=scoring)
     for i in range(min(3, len(references))):
         say(f"\nSample {i + 1}:")
         say(f"  Reference:  {references[i]}")
@@ -214,6 +217,9 @@ def main(argv=None) -> Dict:
     ap.add_argument("--ingest", choices=INGEST_MODES, default="device",
                     help="where the files' samples are converted, resampled to 16 kHz and padded: on the GPU (default) or in numpy "
                          "on the host (16 kHz files give the same bits either way)")
+    ap.add_argument("--scoring", choices=SCORING_MODES[::-1], default="device",
+                    help="where the PER / PFER edit distances are computed: all pairs in one launch on the GPU (default) or pair by "
+                         "pair in Python on the host (PER is equal either way, PFER to float64 rounding)")
     ap.add_argument("--results-json", type=str, default=None, help="also write both result dicts here (rank 0)")
     ap.add_argument("--allow-byte-fallback", action="store_true",
                     help="run without the Whisper vocabulary (WIPA_TIKTOKEN unset): hypotheses render ids >= 256 as <|idN|>; "
@@ -235,10 +241,10 @@ def main(argv=None) -> Dict:
     if not args.skip_base:
         base_results = evaluate_model(args.base_model, args.test_data, num_samples, model_name="Base Whisper Model",
                                       is_checkpoint=False, n_mels=args.n_mels, base_model=args.base_model, batch_size=args.batch_size,
-                                      passes_in_flight=args.passes_in_flight, ingest=args.ingest)
+                                      passes_in_flight=args.passes_in_flight, ingest=args.ingest, scoring=args.scoring)
     trained_results = evaluate_model(args.checkpoint, args.test_data, num_samples, model_name="Trained Checkpoint",
                                      is_checkpoint=True, n_mels=args.n_mels, base_model=args.base_model, batch_size=args.batch_size,
-                                     passes_in_flight=args.passes_in_flight, ingest=args.ingest)
+                                     passes_in_flight=args.passes_in_flight, ingest=args.ingest, scoring=args.scoring)
     if rank == 0:
         if base_results:
             compare_models(base_results, trained_results)

@@ -181,13 +181,16 @@ def train_step(trainer: DecoderTrainer, batch: Dict, tokenizer):
 VALIDATE_PASSES_IN_FLIGHT = 4  # validation batches in flight on one GPU (whisper_ipa_amd.pipeline.transcribe_batches)
 
 
-def validate(model, dataset, tokenizer, num_samples: int = 100) -> Dict:
+def validate(model, dataset, tokenizer, num_samples: int = 100, scoring: str = "host") -> Dict:
     """reference :314-407: batched greedy decode (language=None -> detection, fp16=False), PER / PFER.
 
     Data parallel: COLLECTIVE -- every rank calls it.  The validation batches (4 clips each, the reference's size) are dealt
     round-robin to the ranks, each rank decodes its share with its own weight replica, the (reference, hypothesis) pairs are
     gathered once and every rank scores the whole list in the reference's sample order, so all ranks return the same
-    metrics.  (Round 2 validated on rank 0 alone while the other ranks idled in the next step's all-reduce.)"""
+    metrics.  (Round 2 validated on rank 0 alone while the other ranks idled in the next step's all-reduce.)
+    ``scoring`` goes to ``evaluate_batch``: "device" computes the edit distances of the whole list in one GPU launch on every rank
+    (exact integers, so the ranks still agree bit for bit); "host", the default of this function, is the Python loop.  The
+    command line's ``--scoring`` defaults to "device"."""
     rank, world = parallel.world()
     main = rank == 0
     if main:
@@ -239,7 +242,7 @@ def validate(model, dataset, tokenizer, num_samples: int = 100) -> Dict:
         print("\nSample Predictions:")
         for k in range(min(3, len(mine[0][1]))):
             print(f"  Ref:  [{mine[0][1][k]}]\n  Pred: [{mine[0][2][k]}]\n" + "-" * 30)
-    metrics = evaluate_batch(references, hypotheses)
+    metrics = evaluate_batch(references, hypotheses, scoring=scoring)
     model.train()
     if main:
         print(f"Validation Results:\n  PER:  {metrics['per']:.2f}%\n  PFER: {metrics['pfer']:.2f}%")
@@ -285,7 +288,7 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
           batch_size: int = 4, learning_rate: float = 1e-5, validate_every: int = 100, save_every: int = 500,
           test_run: bool = False, audio_root: str = "", seed: Optional[int] = None, exact_f32: bool = False,
           allow_byte_fallback: bool = False, cache_encoder_features: bool = True, feature_cache_clips: Optional[int] = None,
-          clip_scope: str = "reference"):
+          clip_scope: str = "reference", scoring: str = "device"):
     rank, world = _init_distributed()
     try:
         parallel.require_even_shards(batch_size, world)  # every rank gets clips; no mismatched collectives
@@ -300,7 +303,7 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
                      "num_steps": num_steps, "batch_size": batch_size, "learning_rate": learning_rate,
                      "validate_every": validate_every, "save_every": save_every, "test_run": test_run,
                      "world_size": world, "f32_products": "exact" if exact_f32 else "split",
-                     "cache_encoder_features": bool(cache_encoder_features), "clip_scope": clip_scope}
+                     "cache_encoder_features": bool(cache_encoder_features), "clip_scope": clip_scope, "scoring": scoring}
         save_training_config(output_dir, args_dict, get_hardware_info())
     logger = TrainingLogger(output_dir) if main else None
     print(f"Loading model: {model_name}")
@@ -372,7 +375,7 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
                       f"Samples/sec: {batch_size / step_time:.1f}")
                 logger.log_train_step(step, loss_value, learning_rate, step_time, batch_size, time.time() - start_time)
             if step % validate_every == 0:
-                metrics = validate(model, test_dataset, tokenizer, num_samples=min(100, len(test_dataset)))  # collective
+                metrics = validate(model, test_dataset, tokenizer, num_samples=min(100, len(test_dataset)), scoring=scoring)  # collective
             if main and step % validate_every == 0:
                 if logger.log_validation(step, metrics, time.time() - start_time):
                     best = output_dir / "best-checkpoint"
@@ -399,7 +402,7 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
 
     if main:
         print("\n" + "=" * 70 + "\nTraining complete! Running final validation...\n" + "=" * 70)
-    metrics = validate(model, test_dataset, tokenizer, num_samples=min(500, len(test_dataset)))  # collective
+    metrics = validate(model, test_dataset, tokenizer, num_samples=min(500, len(test_dataset)), scoring=scoring)  # collective
     if main:
         logger.log_validation(num_steps, metrics, time.time() - start_time)
         if latest_loss is not None:
@@ -436,6 +439,9 @@ def main():
     p.add_argument("--batch-size", type=int, default=12, help="Batch size (global, split over the GPUs)")
     p.add_argument("--lr", type=float, default=1e-5, help="Learning rate")
     p.add_argument("--validate-every", type=int, default=1000, help="Validate every N steps")
+    p.add_argument("--scoring", choices=["device", "host"], default="device",
+                   help="where validation computes the PER / PFER edit distances: the whole validation list in one GPU launch (default) "
+                        "or pair by pair in Python on the host; PER is equal either way, PFER to float64 rounding")
     p.add_argument("--save-every", type=int, default=1000, help="Save checkpoint every N steps")
     p.add_argument("--test-run", action="store_true", help="Test run with only 100 samples")
     p.add_argument("--audio-root", type=str, default="", help="prefix for the relative audio_path entries of the JSON")
@@ -462,7 +468,7 @@ def main():
           num_steps=a.steps, batch_size=a.batch_size, learning_rate=a.lr, validate_every=a.validate_every,
           save_every=a.save_every, test_run=a.test_run, audio_root=a.audio_root, exact_f32=a.exact_f32,
           allow_byte_fallback=a.allow_byte_fallback, cache_encoder_features=not a.no_cache_encoder_features,
-          feature_cache_clips=a.feature_cache_clips, clip_scope=a.clip_scope)
+          feature_cache_clips=a.feature_cache_clips, clip_scope=a.clip_scope, scoring=a.scoring)
 
 
 if __name__ == "__main__":

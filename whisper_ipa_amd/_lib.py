@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(_HERE, "libwipa.so")
 WIPA_F32, WIPA_BF16, WIPA_FP8_E4M3 = 0, 1, 2
 GREEDY_PARTS = 2048  # WIPA_GREEDY_PARTS
 RESAMPLE_TILE = 512  # WIPA_RESAMPLE_TILE
+SCORE_MAX_LEN = 1024  # WIPA_SCORE_MAX_LEN
 ENC_GLOBAL, ENC_PER_LAYER = 7, 14
 DEC_GLOBAL, DEC_PER_LAYER, DEC_FP8_PER_LAYER = 4, 20, 6
 GEMM_DISPATCH = ("tile128", "tile256", "tile384", "tile384n", "tile256p", "skinny", "skinny_fp8", "skinny_ln", "kmajor", "split_k",
@@ -157,6 +158,8 @@ SIGNATURES = {
                                                 c_int, c_int, c_float, c_void_p]),
     "wipa_embed_layernorm": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
+    "wipa_edit_distance_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, _P(C.c_int32),
+                                         _P(C.c_int32), c_void_p, c_void_p, c_void_p]),
     "wipa_bpe_create": (c_void_p, [c_void_p, c_void_p, c_void_p, c_int]),
     "wipa_bpe_free": (None, [c_void_p]),
     "wipa_bpe_encode_piece": (c_int, [c_void_p, C.c_char_p, c_int, c_void_p, c_int]),
