@@ -417,6 +417,34 @@ int wipa_greedy_step_embed_partials(const float* partials, int n_parts, int B, i
                                     int32_t* not_done, const void* tok_emb, int emb_dtype, const float* emb_scale, const float* pos_emb,
                                     int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y, int y_dtype, int D, float eps,
                                     wipa_stream_t s);
+/* Timestamp rules in the greedy update: ApplyTimestampRules of openai-whisper's decoding.py, which mlx_whisper.transcribe applies
+ * on every step (scripts/evaluate_model.py:112-119 of the reference; transformers' WhisperTimeStampLogitsProcessor is the same
+ * algorithm; mlx_whisper's port is [UPSTREAM-UNVERIFIED]).  With tb = timestamp_begin, nt = no_timestamps, seq = tokens[b][n_init .. p]:
+ *   1. l = logits + (p + 1 == n_init ? mask_first : mask_always); l[nt] = -inf
+ *   2. last = len(seq) >= 1 and seq[-1] >= tb; pen = len(seq) < 2 or seq[-2] >= tb;
+ *      last and pen: l[tb:] = -inf;  last and not pen: l[:eot] = -inf
+ *   3. t = the last token >= tb of seq IN ORDER (not the maximum), if any; t_last = t if last and not pen else t + 1; l[tb:t_last] = -inf
+ *   4. p + 1 == n_init: l[:tb] = -inf and, if max_initial_timestamp_index >= 0, l[tb + index + 1:] = -inf
+ *   5. logsumexp(l[tb:]) > max(l[:tb]) (false when no timestamp is left): l[:tb] = -inf
+ *   6. next = argmax(l), lowest index on ties; sum_logprobs += l[next] - logsumexp(l) over the row after 5, unless the previous
+ *      token was eot; EOT latch and not_done as wipa_greedy_step.
+ * The kernel reads the row's own history; there is no per-row mask in memory.  V <= 65536, 16-byte aligned rows and masks,
+ * eot < timestamp_begin < V. */
+typedef struct wipa_decode_rules {
+    int32_t timestamp_begin;             /* first timestamp token <|0.00|> */
+    int32_t no_timestamps;               /* <|notimestamps|>: never sampled under the rules */
+    int32_t max_initial_timestamp_index; /* round(max_initial_timestamp / 0.02); < 0: no cap */
+} wipa_decode_rules;
+/* wipa_greedy_step with the rules (no embedding): the rule arithmetic alone, on any rows */
+int wipa_timestamp_step(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
+                        int32_t* tokens, int64_t ld_tok, const int32_t* pos_dev, int n_init, int eot, const wipa_decode_rules* rules,
+                        float* sum_logprobs, int32_t* not_done, wipa_stream_t s);
+/* wipa_greedy_step_embed with the rules: the tail of a decode step under wipa_decoder_run_rules */
+int wipa_timestamp_step_embed(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
+                              int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init,
+                              int eot, const wipa_decode_rules* rules, float* sum_logprobs, int32_t* not_done, const void* tok_emb,
+                              int emb_dtype, const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w,
+                              const float* ln_b, void* y, int y_dtype, int D, float eps, wipa_stream_t s);
 /* The same row routine alone, for the token ALREADY at position p = *pos_dev: x[b] = tok_emb[tokens[b][p]] + pos_emb[p],
  * y[b] = LayerNorm(x[b]).  wipa_decoder_run launches it once before its first step. */
 int wipa_embed_layernorm(const int32_t* tokens, int64_t ld_tok, int B, const int32_t* pos_dev, const void* tok_emb, int emb_dtype,
@@ -582,6 +610,18 @@ int wipa_decoder_run(const wipa_model_cfg* cfg, const void* const* weights, void
  * prompt through the decoder in one forward).  Continue with wipa_decoder_run for the remaining steps. */
 int wipa_decoder_prefill(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
                          int eot, const float* mask_first, const float* mask_always, int use_graph, wipa_stream_t s);
+/* wipa_decoder_run / wipa_decoder_prefill with the timestamp rules (wipa_decode_rules above) in every greedy update: the step's
+ * tail is wipa_timestamp_step_embed, the prompt pass ends with wipa_timestamp_step (rule 4 acts on the first sampled token).
+ * rules == NULL enqueues exactly what the plain entry points enqueue.  The rules are part of the step graph's and the prefill
+ * graph's key.  With rules every step writes its logits and the row-scan tail reads them (the per-wave partials of
+ * wipa_logits_greedy cannot carry rules that depend on the row's history).  A configuration whose step does not end in the fused
+ * tail (WIPA_DECODE_TAIL=0, WIPA_DECODE_FUSED=1) is refused with WIPA_ERR_ARG: it is never decoded without the rules. */
+int wipa_decoder_run_rules(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int n_init,
+                           int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
+                           const wipa_decode_rules* rules, wipa_stream_t s);
+int wipa_decoder_prefill_rules(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
+                               int eot, const float* mask_first, const float* mask_always, int use_graph,
+                               const wipa_decode_rules* rules, wipa_stream_t s);
 /* drop the cached step graphs that reference this state blob (call before freeing it). */
 int wipa_decoder_release(void* state);
 

@@ -12,10 +12,14 @@ Differences that the hardware asks for:
     replica and no collective on the data path; the hypotheses are gathered once at the end;
   * PER / PFER of the whole list are scored in one GPU launch (``--scoring device``, whisper_ipa_amd.scoring; ``host`` keeps the
     reference's Python loops): the same integers, so the same PER and, to float64 rounding, the same PFER;
-  * the base model is a local directory (no hub access) and the base-model leg uses the same
-    mel -> encoder -> decode(language="en", without_timestamps=True) path as the checkpoint leg
-    (the reference's base leg goes through mlx_whisper.transcribe, which wraps the same calls for
-    a clip of at most 30 s).
+  * the base model is a local directory (no hub access).  The reference's base leg goes through
+    ``mlx_whisper.transcribe(audio_path, path_or_hf_repo=..., language=..., word_timestamps=False)`` (:112-119), which is NOT the
+    checkpoint leg's ``decode(language="en", without_timestamps=True)``: it decodes with timestamps on (a three-token prompt),
+    applies the timestamp rules on every step, cuts segments, skips silent windows and walks files longer than 30 s window by
+    window.  ``--base-decode transcribe`` sends the base leg through ``whisper_ipa_amd.transcribe``, which does all of that
+    (greedy only, without conditioning on previous text; see that module for what it refuses); ``--base-decode decode``, the
+    default, keeps the base leg on the checkpoint leg's path as before, which gives a different token stream than the
+    reference's base leg.
 All compute runs in libwipa.so on the GPU.
 """
 from __future__ import annotations
@@ -104,6 +108,32 @@ def transcribe_clips(model, audio_paths: List[str], options: DecodingOptions, ba
     return texts
 
 
+BASE_DECODE_MODES = ("decode", "transcribe")
+
+
+def transcribe_files(model, audio_paths: List[str], batch_size: int = 64, progress=None) -> List[str]:
+    """reference :112-119 for the whole list: ``mlx_whisper.transcribe(path, language="en", word_timestamps=False)["text"]`` per
+    file through whisper_ipa_amd.transcribe, ``batch_size`` files per call (their windows decode as one batch per round).  One
+    text per path, "" where the file could not be read."""
+    from whisper_ipa_amd import transcribe
+
+    texts = [""] * len(audio_paths)
+    for b in range(0, len(audio_paths), batch_size):
+        clips, slots = [], []
+        for i, path in enumerate(audio_paths[b:b + batch_size]):
+            try:
+                clips.append(np.asarray(load_audio(path), dtype=np.float32))
+                slots.append(b + i)
+            except Exception as e:
+                print(f"\nError transcribing {path}: {e}")
+        if clips:
+            for i, r in zip(slots, transcribe(model, clips, language="en", word_timestamps=False)):
+                texts[i] = r["text"].strip()
+        if progress is not None:
+            progress(min(b + batch_size, len(audio_paths)))
+    return texts
+
+
 def transcribe_batch(model, audio_paths: List[str], n_mels: int, options: DecodingOptions) -> List[str]:
     """ONE batch with nothing else in flight (round 4's entry point, kept for callers that hold a single batch)"""
     assert n_mels == model.dims.n_mels
@@ -112,7 +142,8 @@ def transcribe_batch(model, audio_paths: List[str], n_mels: int, options: Decodi
 
 def evaluate_model(model_path: str, test_data_path: str, num_samples: Optional[int] = None, model_name: str = "Model",
                    is_checkpoint: bool = False, n_mels: int = 80, base_model: str = "mlx-community/whisper-small-mlx",
-                   batch_size: int = 64, passes_in_flight: int = 4, ingest: str = "device", scoring: str = "device") -> Dict:
+                   batch_size: int = 64, passes_in_flight: int = 4, ingest: str = "device", scoring: str = "device",
+                   base_decode: str = "decode") -> Dict:
     rank, world_size = parallel.world()
     say = print if rank == 0 else (lambda *a, **k: None)
     say("=" * 70)
@@ -141,9 +172,13 @@ def evaluate_model(model_path: str, test_data_path: str, num_samples: Optional[i
     lo, hi = parallel.shard_bounds(len(test_data), world_size, rank)
     mine = test_data[lo:hi]
     say("\nTranscribing test samples...")
-    local_hyp = transcribe_clips(model, [s["audio_path"] for s in mine], options, batch_size=batch_size,
-                                 passes_in_flight=passes_in_flight, ingest=ingest,
-                                 progress=lambda n: say(f"  {n}/{len(mine)} clips on rank 0", flush=True))
+    if base_decode == "transcribe" and not is_checkpoint:
+        local_hyp = transcribe_files(model, [s["audio_path"] for s in mine], batch_size=batch_size,
+                                     progress=lambda n: say(f"  {n}/{len(mine)} clips on rank 0", flush=True))
+    else:
+        local_hyp = transcribe_clips(model, [s["audio_path"] for s in mine], options, batch_size=batch_size,
+                                     passes_in_flight=passes_in_flight, ingest=ingest,
+                                     progress=lambda n: say(f"  {n}/{len(mine)} clips on rank 0", flush=True))
     hypotheses = local_hyp
     if world_size > 1:
         import torch.distributed as dist
@@ -220,6 +255,10 @@ def main(argv=None) -> Dict:
     ap.add_argument("--scoring", choices=SCORING_MODES[::-1], default="device",
                     help="where the PER / PFER edit distances are computed: all pairs in one launch on the GPU (default) or pair by "
                          "pair in Python on the host (PER is equal either way, PFER to float64 rounding)")
+    ap.add_argument("--base-decode", choices=BASE_DECODE_MODES, default="decode",
+                    help="the base-model leg: 'decode' = the checkpoint leg's decode(without_timestamps=True) (default, as before); "
+                         "'transcribe' = whisper_ipa_amd.transcribe, the call the reference makes for it (timestamps on, timestamp "
+                         "rules, segments, no-speech skip, 30 s windows)")
     ap.add_argument("--results-json", type=str, default=None, help="also write both result dicts here (rank 0)")
     ap.add_argument("--allow-byte-fallback", action="store_true",
                     help="run without the Whisper vocabulary (WIPA_TIKTOKEN unset): hypotheses render ids >= 256 as <|idN|>; "
@@ -241,7 +280,8 @@ def main(argv=None) -> Dict:
     if not args.skip_base:
         base_results = evaluate_model(args.base_model, args.test_data, num_samples, model_name="Base Whisper Model",
                                       is_checkpoint=False, n_mels=args.n_mels, base_model=args.base_model, batch_size=args.batch_size,
-                                      passes_in_flight=args.passes_in_flight, ingest=args.ingest, scoring=args.scoring)
+                                      passes_in_flight=args.passes_in_flight, ingest=args.ingest, scoring=args.scoring,
+                                      base_decode=args.base_decode)
     trained_results = evaluate_model(args.checkpoint, args.test_data, num_samples, model_name="Trained Checkpoint",
                                      is_checkpoint=True, n_mels=args.n_mels, base_model=args.base_model, batch_size=args.batch_size,
                                      passes_in_flight=args.passes_in_flight, ingest=args.ingest, scoring=args.scoring)

@@ -15,6 +15,7 @@ from . import audio, decoding, pipeline, scoring, tokenizer, whisper  # noqa: F4
 from .audio import load_audio, load_audio_batch, log_mel_spectrogram, pad_or_trim  # noqa: F401
 from .decoding import DecodingOptions, DecodingResult, decode  # noqa: F401
 from .pipeline import PassResult, TranscribePipeline, transcribe_batches  # noqa: F401
+from .transcribe import transcribe  # noqa: F401  (the function: ``whisper_ipa_amd.transcribe(model, audio)``, as mlx_whisper.transcribe)
 from .scoring import encode_features, score_collect, score_launch, score_pairs  # noqa: F401
 from .whisper import ModelDimensions, Whisper  # noqa: F401
 

@@ -92,6 +92,11 @@ class ModelCfg(C.Structure):
         "enc_act_fp8", "dec_cross_absorbed", "dec_cross_splits")]
 
 
+class DecodeRules(C.Structure):
+    """wipa_decode_rules"""
+    _fields_ = [(n, C.c_int32) for n in ("timestamp_begin", "no_timestamps", "max_initial_timestamp_index")]
+
+
 class DecLayout(C.Structure):
     _fields_ = [(n, c_int64) for n in (
         "total_bytes", "tokens", "ld_tok", "pos", "not_done", "sum_logprobs", "logits", "ld_logits",
@@ -149,6 +154,11 @@ SIGNATURES = {
     "wipa_greedy_step_embed": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                        c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
+    "wipa_timestamp_step": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int,
+                                    _P(DecodeRules), c_void_p, c_void_p, c_void_p]),
+    "wipa_timestamp_step_embed": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                          c_int, c_int, _P(DecodeRules), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "wipa_logits_greedy_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "wipa_logits_greedy_partials_bytes": (c_size_t, [c_int]),
     "wipa_logits_greedy": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
@@ -176,6 +186,10 @@ SIGNATURES = {
                                  c_int, c_void_p]),
     "wipa_decoder_prefill": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                      c_void_p]),
+    "wipa_decoder_run_rules": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                       c_int, _P(DecodeRules), c_void_p]),
+    "wipa_decoder_prefill_rules": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                           _P(DecodeRules), c_void_p]),
     "wipa_decode_cross_attn_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "wipa_decoder_release": (c_int, [c_void_p]),
     "wipa_decoder_logits_workspace_bytes": (c_size_t, [_P(ModelCfg), c_int, c_int]),

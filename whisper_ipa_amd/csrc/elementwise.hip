@@ -558,6 +558,204 @@ __global__ __launch_bounds__(GS_THREADS) void greedy_tail_kernel(TailParams q) {
     }
 }
 
+// ------------------------------------------------------------------ timestamp rules in the step's tail
+// ApplyTimestampRules of openai-whisper's decoding.py (the algorithm of transformers' WhisperTimeStampLogitsProcessor; mlx_whisper's
+// port of it is [UPSTREAM-UNVERIFIED]) on the row the tail already holds in registers.  The rules depend on the row's OWN history
+// tokens[b][n_init .. p] (seq) and on a comparison of probability masses, so they cannot be a static vocabulary mask:
+//   nt column -inf;  last = seq[-1] >= tb, pen = len(seq) < 2 or seq[-2] >= tb:  last and pen -> no timestamp, last and not pen ->
+//   no text below eot;  t = the LAST timestamp of seq in order (a forced history need not be monotone): timestamps below t (below
+//   t + 1 unless last and not pen) -inf;  first sampled position: text -inf and timestamps capped at tb + max_initial;  then, over
+//   the row as it stands, logsumexp(timestamps) > max(text) -> text -inf.
+// Every rule kills a column RANGE, so the filtered row is: text columns (< tb) alive from text_lo on, bar nt; timestamp columns alive
+// in [ts_lo, ts_hi].  Two reductions, text side and timestamp side, each (max, lowest column) then a sum of exponentials in the
+// fixed order of greedy_tail_kernel (per thread ascending, wave tree, waves in order); the mass comparison and the log-probability
+// of the winner come from those four numbers.  Like greedy_tail_kernel, every thread computes `next` from values all of them hold.
+struct RulesDev {
+    int tb, nt, max_init;  // timestamp_begin, <|notimestamps|>, max_initial_timestamp_index (< 0: no cap)
+};
+
+struct RowPick {
+    int next;        // the arg-max of the filtered row (lowest column on ties)
+    float logprob;   // log_softmax of the filtered row at next (thread 0 of the workgroup only)
+};
+
+__device__ __forceinline__ RowPick rules_row_pick(const float* __restrict__ row, const float* __restrict__ mask, int V, const int32_t* __restrict__ tk,
+                                                  int p, int n_init, int eot, RulesDev r, float* s_v, int* s_i, float* s_sum) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nq = V >> 2;
+    // the row's loads go out first; the history scan below hides under them
+    f32x4 vals[GS_MAXQ];
+#pragma unroll
+    for (int j = 0; j < GS_MAXQ; ++j) {
+        const int qi = tid + j * GS_THREADS;
+        if (qi < nq) {
+            vals[j] = *reinterpret_cast<const f32x4*>(row + 4 * qi) + *reinterpret_cast<const f32x4*>(mask + 4 * qi);
+        } else {
+            vals[j] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        }
+    }
+    const int ti = 4 * nq + tid;  // the (V mod 4) trailing elements: timestamp columns for every Whisper vocabulary, but not assumed
+    const bool has_tail = tid < 4 && ti < V;
+    float tailv = has_tail ? row[ti] + mask[ti] : -INFINITY;
+    // history: seq = tk[n_init .. p].  Every WAVE scans all of it (at most n_ctx - n_init tokens, 7 per lane) and reduces with
+    // shuffles: no LDS, no barrier, and every thread ends with the same t_idx
+    const int len = p + 1 - n_init;
+    int t_idx = -1;  // index in seq of its last timestamp token
+    for (int i = lane; i < len; i += 64) t_idx = tk[n_init + i] >= r.tb ? i : t_idx;  // ascending per lane: the last match stays
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) t_idx = max(t_idx, __shfl_xor(t_idx, o, 64));
+    const bool first = len == 0;
+    const bool last = t_idx >= 0 && t_idx == len - 1;
+    const bool pen = len < 2 || tk[p - 1] >= r.tb;
+    int text_lo = 0, ts_lo = r.tb, ts_hi = V - 1;
+    if (last && pen) ts_lo = V;         // a closed pair: text next
+    if (last && !pen) text_lo = eot;    // a single timestamp: EOT or a timestamp next
+    if (t_idx >= 0) ts_lo = max(ts_lo, tk[n_init + t_idx] + ((last && !pen) ? 0 : 1));
+    if (first) {
+        text_lo = r.tb;
+        if (r.max_init >= 0) ts_hi = min(ts_hi, r.tb + r.max_init);
+    }
+    auto alive = [&](int c) { return c < r.tb ? (c >= text_lo && c != r.nt) : (c >= ts_lo && c <= ts_hi); };
+    MaxIdx mt{-INFINITY, 0x7fffffff}, ms{-INFINITY, 0x7fffffff};  // text side, timestamp side
+    if (has_tail) {
+        if (!alive(ti)) tailv = -INFINITY;
+        if (ti < r.tb) mt = MaxIdx{tailv, ti};
+        else ms = MaxIdx{tailv, ti};
+    }
+#pragma unroll
+    for (int j = 0; j < GS_MAXQ; ++j) {
+        const int qi = tid + j * GS_THREADS;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c = 4 * qi + e;
+            if (qi < nq) {
+                if (!alive(c)) vals[j][e] = -INFINITY;
+                if (c < r.tb) mt = better(mt, MaxIdx{vals[j][e], c});
+                else ms = better(ms, MaxIdx{vals[j][e], c});
+            }
+        }
+    }
+    mt = wave_argmax(mt);
+    ms = wave_argmax(ms);
+    constexpr int NW = GS_THREADS / 64;
+    if (lane == 0) {
+        s_v[wave] = mt.v; s_i[wave] = mt.i;
+        s_v[NW + wave] = ms.v; s_i[NW + wave] = ms.i;
+    }
+    __syncthreads();
+    MaxIdx bt{s_v[0], s_i[0]}, bs{s_v[NW], s_i[NW]};
+#pragma unroll
+    for (int w = 1; w < NW; ++w) {
+        bt = better(bt, MaxIdx{s_v[w], s_i[w]});
+        bs = better(bs, MaxIdx{s_v[NW + w], s_i[NW + w]});
+    }
+    // sums of exponentials against each side's own max; a side with nothing alive has max -inf: base 0 keeps exp(-inf - base) = 0
+    const float base_t = bt.v == -INFINITY ? 0.f : bt.v, base_s = bs.v == -INFINITY ? 0.f : bs.v;
+    float se_t = 0.f, se_s = 0.f;
+    if (has_tail) {
+        if (ti < r.tb) se_t += __expf(tailv - base_t);
+        else se_s += __expf(tailv - base_s);
+    }
+#pragma unroll
+    for (int j = 0; j < GS_MAXQ; ++j) {
+        const int qi = tid + j * GS_THREADS;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const bool text = 4 * qi + e < r.tb;  // padding quads hold -inf: exp gives 0 on either side
+            const float ex = __expf(vals[j][e] - (text ? base_t : base_s));
+            se_t += text ? ex : 0.f;
+            se_s += text ? 0.f : ex;
+        }
+    }
+    se_t = wave_reduce_sum(se_t);
+    se_s = wave_reduce_sum(se_s);
+    if (lane == 0) {
+        s_sum[wave] = se_t;
+        s_sum[NW + wave] = se_s;
+    }
+    __syncthreads();
+    float tot_t = 0.f, tot_s = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        tot_t += s_sum[w];
+        tot_s += s_sum[NW + w];
+    }
+    // timestamp mass against the best text token: the common normaliser cancels; false when no timestamp is alive
+    const float ts_mass = bs.v == -INFINITY ? -INFINITY : bs.v + logf(tot_s);
+    RowPick out;
+    if (ts_mass > bt.v) {  // text -inf: the row is its timestamp side
+        out.next = bs.i;
+        out.logprob = -logf(tot_s);
+    } else {
+        const MaxIdx bm = better(bt, bs);
+        out.next = bm.i;
+        out.logprob = -logf(tot_t * __expf(base_t - bm.v) + (bs.v == -INFINITY ? 0.f : tot_s * __expf(base_s - bm.v)));
+    }
+    return out;
+}
+
+// wipa_timestamp_step: wipa_greedy_step with the rules, no embedding
+__global__ __launch_bounds__(GS_THREADS) void timestamp_step_kernel(const float* __restrict__ logits, int64_t ldl, int V,
+                                                                    const float* __restrict__ mask_first, const float* __restrict__ mask_always,
+                                                                    int32_t* __restrict__ tokens, int64_t ld_tok, const int32_t* __restrict__ pos_dev,
+                                                                    int n_init, int eot, RulesDev r, float* __restrict__ sum_logprobs,
+                                                                    int32_t* __restrict__ not_done) {
+    __shared__ float s_v[2 * GS_THREADS / 64];
+    __shared__ int s_i[2 * GS_THREADS / 64];
+    __shared__ float s_sum[2 * GS_THREADS / 64];
+    const int b = blockIdx.x;
+    const int p = *pos_dev;
+    if (p + 1 < n_init) return;  // prompt token already in place
+    int32_t* tk = tokens + (int64_t)b * ld_tok;
+    const RowPick pick = rules_row_pick(logits + (int64_t)b * ldl, (p + 1 == n_init) ? mask_first : mask_always, V, tk, p, n_init, eot, r, s_v,
+                                        s_i, s_sum);
+    if (threadIdx.x == 0) {
+        const int prev = tk[p];
+        const int next = (prev == eot) ? eot : pick.next;
+        if (prev != eot) sum_logprobs[b] += pick.logprob;
+        tk[p + 1] = next;
+        if (next != eot) atomicAdd(not_done, 1);
+    }
+}
+
+// greedy_tail_kernel's row-scan branch with the rules: the same prompt walk, EOT latch, next embedding + LayerNorm (so the next
+// step's input row has the bits the plain tail would give for the same token) and position advance
+template <typename TO>
+__global__ __launch_bounds__(GS_THREADS) void timestamp_tail_kernel(TailParams q, RulesDev r) {
+    __shared__ float s_v[2 * GS_THREADS / 64];
+    __shared__ int s_i[2 * GS_THREADS / 64];
+    __shared__ float s_sum[2 * GS_THREADS / 64];
+    __shared__ float s_red[4];
+    const int b = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int p = *(volatile const int32_t*)q.pos;  // one load per thread, as in greedy_tail_kernel
+    int32_t* tk = q.tokens + (int64_t)b * q.ld_tok;
+    int next;
+    if (p + 1 < q.n_init) {
+        next = tk[p + 1];
+    } else {
+        const RowPick pick = rules_row_pick(q.logits + (int64_t)b * q.ldl, (p + 1 == q.n_init) ? q.mask_first : q.mask_always, q.V, tk, p, q.n_init,
+                                            q.eot, r, s_v, s_i, s_sum);
+        const int prev = tk[p];
+        next = (prev == q.eot) ? q.eot : pick.next;
+        if (tid == 0) {
+            if (prev != q.eot) q.sum_logprobs[b] += pick.logprob;
+            tk[p + 1] = next;
+            if (next != q.eot) atomicAdd(q.not_done, 1);
+        }
+    }
+    row_embed_layernorm<TO>(tid, next, min(p + 1, q.n_ctx - 1), q.emb, q.emb_dtype, q.emb_scale, q.pos_emb, q.x + (int64_t)b * q.D, q.ln_w,
+                            q.ln_b, (TO*)q.y + (int64_t)b * q.D, q.D, q.eps, s_red);
+    if (tid == 0) {  // position advance by the last workgroup to arrive (see greedy_tail_kernel)
+        const int arrived = atomicAdd(q.done_counter, 1);
+        if (arrived == (int)gridDim.x - 1) {
+            *q.done_counter = 0;
+            *q.pos = p + 1;
+            *q.posd = (int64_t)(p + 1) * q.D;
+        }
+    }
+}
+
 __global__ void add_i32_kernel(int32_t* p, int32_t v) { *p += v; }
 
 // ------------------------------------------------------------------ masked cross entropy
@@ -810,6 +1008,61 @@ extern "C" int wipa_greedy_step_embed_partials(const float* partials, int n_part
     if (y_dtype == WIPA_F32) hipLaunchKernelGGL((greedy_tail_kernel<float>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, q);
     else if (y_dtype == WIPA_BF16) hipLaunchKernelGGL((greedy_tail_kernel<__bf16>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, q);
     else WIPA_REQUIRE(false, "wipa_greedy_step_embed_partials: bad dtype %d", y_dtype);
+    WIPA_LAUNCH_CHECK();
+    return WIPA_OK;
+}
+
+static int rules_check(const char* who, const wipa_decode_rules* rules, const float* logits, int V, int64_t ldl, const float* mask_first,
+                       const float* mask_always, int eot, RulesDev* out) {
+    WIPA_REQUIRE(rules, "%s: null rules", who);
+    WIPA_REQUIRE(rules->timestamp_begin > 0 && rules->timestamp_begin < V && eot < rules->timestamp_begin && rules->no_timestamps >= 0 &&
+                     rules->no_timestamps < rules->timestamp_begin,
+                 "%s: need eot < timestamp_begin < V and no_timestamps below timestamp_begin (eot=%d timestamp_begin=%d no_timestamps=%d V=%d)", who,
+                 eot, rules->timestamp_begin, rules->no_timestamps, V);
+    // the rules live in the register-resident row scan only
+    WIPA_REQUIRE(V <= 4 * GS_MAXQ * GS_THREADS && ldl % 4 == 0 && ((uintptr_t)logits % 16) == 0 && ((uintptr_t)mask_first % 16) == 0 &&
+                     ((uintptr_t)mask_always % 16) == 0, "%s: vocabulary of %d / unaligned logits or masks", who, V);
+    out->tb = rules->timestamp_begin;
+    out->nt = rules->no_timestamps;
+    out->max_init = rules->max_initial_timestamp_index;
+    return WIPA_OK;
+}
+
+extern "C" int wipa_timestamp_step(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
+                                   int32_t* tokens, int64_t ld_tok, const int32_t* pos_dev, int n_init, int eot,
+                                   const wipa_decode_rules* rules, float* sum_logprobs, int32_t* not_done, wipa_stream_t stream) {
+    WIPA_REQUIRE(logits && mask_first && mask_always && tokens && pos_dev && sum_logprobs && not_done && B > 0 && n_init >= 1,
+                 "wipa_timestamp_step: bad arguments");
+    RulesDev r;
+    const int rc = rules_check("wipa_timestamp_step", rules, logits, V, ldl, mask_first, mask_always, eot, &r);
+    if (rc != WIPA_OK) return rc;
+    hipLaunchKernelGGL(timestamp_step_kernel, dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, logits, ldl, V, mask_first, mask_always, tokens,
+                       ld_tok, pos_dev, n_init, eot, r, sum_logprobs, not_done);
+    WIPA_LAUNCH_CHECK();
+    return WIPA_OK;
+}
+
+extern "C" int wipa_timestamp_step_embed(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
+                                         int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter,
+                                         int n_init, int eot, const wipa_decode_rules* rules, float* sum_logprobs, int32_t* not_done,
+                                         const void* tok_emb, int emb_dtype, const float* emb_scale, const float* pos_emb, int n_ctx, float* x,
+                                         const float* ln_w, const float* ln_b, void* y, int y_dtype, int D, float eps, wipa_stream_t stream) {
+    WIPA_REQUIRE(logits && mask_first && mask_always && tokens && pos_dev && posd_dev && done_counter && sum_logprobs && not_done &&
+                     tok_emb && pos_emb && x && ln_w && ln_b && y && B > 0 && n_ctx > 0 && n_init >= 1, "wipa_timestamp_step_embed: bad arguments");
+    int rc = tail_params_check("wipa_timestamp_step_embed", logits, V, ldl, mask_first, mask_always, D, emb_dtype, emb_scale);
+    if (rc != WIPA_OK) return rc;
+    RulesDev r;
+    rc = rules_check("wipa_timestamp_step_embed", rules, logits, V, ldl, mask_first, mask_always, eot, &r);
+    if (rc != WIPA_OK) return rc;
+    TailParams q = {};
+    q.logits = logits; q.ldl = ldl; q.V = V; q.mask_first = mask_first; q.mask_always = mask_always;
+    q.tokens = tokens; q.ld_tok = ld_tok; q.pos = pos_dev; q.posd = posd_dev; q.done_counter = done_counter;
+    q.n_init = n_init; q.eot = eot; q.n_ctx = n_ctx; q.sum_logprobs = sum_logprobs; q.not_done = not_done;
+    q.emb = tok_emb; q.emb_dtype = emb_dtype; q.emb_scale = emb_scale; q.pos_emb = pos_emb;
+    q.x = x; q.ln_w = ln_w; q.ln_b = ln_b; q.y = y; q.D = D; q.eps = eps;
+    if (y_dtype == WIPA_F32) hipLaunchKernelGGL((timestamp_tail_kernel<float>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, q, r);
+    else if (y_dtype == WIPA_BF16) hipLaunchKernelGGL((timestamp_tail_kernel<__bf16>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, q, r);
+    else WIPA_REQUIRE(false, "wipa_timestamp_step_embed: bad dtype %d", y_dtype);
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;
 }

@@ -169,8 +169,32 @@ def _use_prefill(n_init: int, total_steps: int) -> bool:
     return n_init >= 2 and total_steps >= n_init and os.environ.get("WIPA_NO_PREFILL") != "1"
 
 
+def timestamp_rules(tok: Tokenizer, max_initial_timestamp: Optional[float] = 1.0) -> "_lib.DecodeRules":
+    """ApplyTimestampRules' parameters for ``tok`` as the wipa_decode_rules the step's tail takes (include/wipa.h):
+    max_initial_timestamp_index = round(max_initial_timestamp / 0.02), 50 for the default of 1.0 s; None -> -1, no cap."""
+    index = -1 if max_initial_timestamp is None else int(round(float(max_initial_timestamp) / 0.02))
+    return _lib.DecodeRules(int(tok.timestamp_begin), int(tok.no_timestamps), index)
+
+
+def _dec_run(L, pk, st, B, n_init, eot, m_first, m_always, n, use_graph, rules, s):
+    """wipa_decoder_run, or wipa_decoder_run_rules when the greedy update carries the timestamp rules"""
+    args = (C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, n_init, eot, ptr(m_first), ptr(m_always), n, int(use_graph))
+    if rules is None:
+        _lib.check(L.wipa_decoder_run(*args, sptr(s)), "wipa_decoder_run")
+    else:
+        _lib.check(L.wipa_decoder_run_rules(*args, C.byref(rules), sptr(s)), "wipa_decoder_run_rules")
+
+
+def _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s):
+    args = (C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, n_init, eot, ptr(m_first), ptr(m_always), int(use_graph))
+    if rules is None:
+        _lib.check(L.wipa_decoder_prefill(*args, sptr(s)), "wipa_decoder_prefill")
+    else:
+        _lib.check(L.wipa_decoder_prefill_rules(*args, C.byref(rules), sptr(s)), "wipa_decoder_prefill_rules")
+
+
 def greedy_launch(model, audio_features: torch.Tensor, initial_tokens: Sequence[int], suppress_always: Sequence[int],
-                  suppress_first: Sequence[int], eot: int, max_new_tokens: int, use_graph: bool = True) -> GreedyHandle:
+                  suppress_first: Sequence[int], eot: int, max_new_tokens: int, use_graph: bool = True, rules=None) -> GreedyHandle:
     """Enqueue cross-KV projection + a FIXED number of decoder steps on the current library
     stream and return without synchronising (EOT rows are latched on the device, so running
     past the end of a row is harmless).  Pair with greedy_collect()."""
@@ -191,12 +215,10 @@ def greedy_launch(model, audio_features: torch.Tensor, initial_tokens: Sequence[
         _lib.check(L.wipa_decoder_begin(C.byref(pk["cfg"]), ptr(st.blob), st.blob.numel(), B, init, n_init, sptr(s)), "wipa_decoder_begin")
         rest = total
         if _use_prefill(n_init, total):  # the prompt positions and the first new token in one batched pass
-            _lib.check(L.wipa_decoder_prefill(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, n_init, eot, ptr(m_first),
-                                              ptr(m_always), int(use_graph), sptr(s)), "wipa_decoder_prefill")
+            _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s)
             rest = total - n_init
-        _lib.check(L.wipa_decoder_run(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, n_init, eot, ptr(m_first),
-                                      ptr(m_always), rest, int(use_graph), sptr(s)), "wipa_decoder_run")
-    return GreedyHandle(st, s, n_init, total, (feats, m_always, m_first))
+        _dec_run(L, pk, st, B, n_init, eot, m_first, m_always, rest, use_graph, rules, s)
+    return GreedyHandle(st, s, n_init, total, (feats, m_always, m_first, rules))
 
 
 def greedy_collect(h: GreedyHandle) -> GreedyTokens:
@@ -210,9 +232,10 @@ def greedy_collect(h: GreedyHandle) -> GreedyTokens:
 
 def greedy_decode_tokens(model, audio_features: torch.Tensor, initial_tokens: Sequence[int], suppress_always: Sequence[int],
                          suppress_first: Sequence[int], eot: int, max_new_tokens: Optional[int] = None,
-                         stop_on_eot: bool = True, use_graph: bool = True, check_every: int = 8) -> GreedyTokens:
+                         stop_on_eot: bool = True, use_graph: bool = True, check_every: int = 8, rules=None) -> GreedyTokens:
     """DecodingTask._main_loop for temperature 0, n_group 1 (see module docstring).
-    ``audio_features`` [B, 1500, d] in the model dtype."""
+    ``audio_features`` [B, 1500, d] in the model dtype.  ``rules`` (``timestamp_rules``): ApplyTimestampRules in every greedy
+    update, on the device; ``initial_tokens`` is then the prompt without <|notimestamps|>."""
     L = _lib.lib()
     B = audio_features.shape[0]
     n_init = len(initial_tokens)
@@ -232,15 +255,13 @@ def greedy_decode_tokens(model, audio_features: torch.Tensor, initial_tokens: Se
                    "wipa_decoder_set_audio")
         _lib.check(L.wipa_decoder_begin(C.byref(pk["cfg"]), ptr(st.blob), st.blob.numel(), B, init, n_init, sptr(s)), "wipa_decoder_begin")
         if _use_prefill(n_init, total):
-            _lib.check(L.wipa_decoder_prefill(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, n_init, eot, ptr(m_first),
-                                              ptr(m_always), int(use_graph), sptr(s)), "wipa_decoder_prefill")
+            _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s)
             done_steps = n_init
         while done_steps < total:
             n = min(check_every if stop_on_eot else total, total - done_steps)
             if done_steps == 0:
                 n = min(total, n + n_init - 1)
-            _lib.check(L.wipa_decoder_run(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, n_init, eot, ptr(m_first),
-                                          ptr(m_always), n, int(use_graph), sptr(s)), "wipa_decoder_run")
+            _dec_run(L, pk, st, B, n_init, eot, m_first, m_always, n, use_graph, rules, s)
             done_steps += n
             if stop_on_eot and done_steps >= n_init:
                 last = st.tokens[:, done_steps].cpu()  # synchronises the library stream
@@ -261,7 +282,7 @@ def greedy_decode_tokens(model, audio_features: torch.Tensor, initial_tokens: Se
 
 
 def forced_decode_logits(model, audio_features: torch.Tensor, tokens: np.ndarray, n_init: int, suppress_always: Sequence[int],
-                         suppress_first: Sequence[int], eot: int, use_graph: bool = True):
+                         suppress_first: Sequence[int], eot: int, use_graph: bool = True, rules=None):
     """The KV-cached decode-step path (prompt prefill + replayed step graph -- the kernels greedy_decode_tokens runs) driven
     along a GIVEN token history: after every step the greedy choice is read and then overwritten with ``tokens[:, p + 1]``.
     ``tokens`` [B, n_init + n_steps] int (host).  Returns (step logits [B, n_steps, V] f32 on the device, unfiltered, and the
@@ -288,32 +309,49 @@ def forced_decode_logits(model, audio_features: torch.Tensor, tokens: np.ndarray
         _lib.check(L.wipa_decoder_set_audio(C.byref(pk["cfg"]), pk["dec_tab"], ptr(feats), ptr(st.blob), st.blob.numel(), B, sptr(s)),
                    "wipa_decoder_set_audio")
         _lib.check(L.wipa_decoder_begin(C.byref(pk["cfg"]), ptr(st.blob), st.blob.numel(), B, init, n_init, sptr(s)), "wipa_decoder_begin")
-        _lib.check(L.wipa_decoder_prefill(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, n_init, eot, ptr(m_first),
-                                          ptr(m_always), int(use_graph), sptr(s)), "wipa_decoder_prefill")
+        _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s)
         for i in range(n_steps):
             p = n_init + i  # the token position the last step has just filled
             trace[:, i].copy_(st.logits)
             chosen[:, i].copy_(st.tokens[:, p])
             st.tokens[:, p].copy_(forced[:, p])
             if i + 1 < n_steps:
-                _lib.check(L.wipa_decoder_run(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, n_init, eot, ptr(m_first),
-                                              ptr(m_always), 1, int(use_graph), sptr(s)), "wipa_decoder_run")
+                _dec_run(L, pk, st, B, n_init, eot, m_first, m_always, 1, use_graph, rules, s)
         out_chosen = chosen.cpu().numpy().astype(np.int64)
     return trace, out_chosen
 
 
-def detect_language(model, audio_features: torch.Tensor, tokenizer: Tokenizer):
+def _sot_pass(model, audio_features: torch.Tensor, tokenizer: Tokenizer) -> GreedyTokens:
+    """one decoder step on the prompt [sot], every logit but the language tokens masked in the greedy update; ``last_logits``
+    are the UNFILTERED logits of that position"""
+    lang = set(tokenizer.all_language_tokens)
+    not_lang = [i for i in range(model.dims.n_vocab) if i not in lang]
+    # with n_init = 1 the greedy kernel applies mask_first at position 0
+    return greedy_decode_tokens(model, audio_features, [tokenizer.sot], not_lang, [], eot=-1, max_new_tokens=1, stop_on_eot=False)
+
+
+def _no_speech_from(last_logits: torch.Tensor, tokenizer: Tokenizer) -> np.ndarray:
+    with on_stream():
+        return torch.softmax(last_logits.float(), dim=-1)[:, tokenizer.no_speech].cpu().numpy().astype(np.float64)
+
+
+def detect_language(model, audio_features: torch.Tensor, tokenizer: Tokenizer, with_no_speech: bool = False):
     """Whisper.detect_language (train_whisper_ipa.py:339 via language=None): one decoder pass on
-    [sot]; every logit but the language tokens masked; argmax.  Returns (language token ids [B], probs)."""
-    B = audio_features.shape[0]
+    [sot]; every logit but the language tokens masked; argmax.  Returns (language token ids [B], probs); with
+    ``with_no_speech`` also the no-speech probabilities of the same pass (``no_speech_probs``)."""
     lang = list(tokenizer.all_language_tokens)
-    not_lang = [i for i in range(model.dims.n_vocab) if i not in set(lang)]
-    # one step on the prompt [sot]: with n_init = 1 the greedy kernel applies mask_first at position 0
-    res = greedy_decode_tokens(model, audio_features, [tokenizer.sot], not_lang, [], eot=-1, max_new_tokens=1,
-                               stop_on_eot=False)
-    logits = res.last_logits[:, lang].float()
-    probs = torch.softmax(logits, dim=-1).cpu().numpy()
+    res = _sot_pass(model, audio_features, tokenizer)
+    with on_stream():
+        probs = torch.softmax(res.last_logits[:, lang].float(), dim=-1).cpu().numpy()
+    if with_no_speech:
+        return res.tokens[:, 1], probs, _no_speech_from(res.last_logits, tokenizer)
     return res.tokens[:, 1], probs
+
+
+def no_speech_probs(model, audio_features: torch.Tensor, tokenizer: Tokenizer) -> np.ndarray:
+    """DecodingResult.no_speech_prob of upstream's DecodingTask: softmax of the unfiltered logits after the prompt's first token
+    [sot] at <|nospeech|>, per row -- the decoder pass detect_language makes."""
+    return _no_speech_from(_sot_pass(model, audio_features, tokenizer).last_logits, tokenizer)
 
 
 def _suppress_lists(options: DecodingOptions, tok: Tokenizer):
@@ -328,15 +366,20 @@ def _suppress_lists(options: DecodingOptions, tok: Tokenizer):
     return sorted(set(suppress)), first
 
 
+def _refuse_unsupported(options: DecodingOptions) -> None:
+    if options.beam_size or (options.best_of or 1) > 1 or options.temperature != 0.0:
+        raise NotImplementedError("temperature above 0, best_of and beam_size are not implemented: the reference only ever runs greedy "
+                                  "decode (SURVEY.md section 0)")
+    if not options.without_timestamps and (options.prompt is not None or options.prefix is not None):
+        raise NotImplementedError("prompt / prefix conditioning is not implemented on the timestamp path")
+
+
 def decode(model, mel: torch.Tensor, options: DecodingOptions = DecodingOptions(), **kwargs):
     """mlx_whisper.decoding.decode: accepts a mel [B,3000,n_mels] / [3000,n_mels] or encoded
     features [B,1500,d] / [1500,d]; returns a DecodingResult or a list of them."""
     if kwargs:
         options = DecodingOptions(**{**options.__dict__, **kwargs})
-    if options.beam_size or (options.best_of or 1) > 1 or options.temperature != 0.0:
-        raise NotImplementedError("the reference only ever runs greedy decode (SURVEY.md section 0)")
-    if not options.without_timestamps:
-        raise NotImplementedError("timestamp rules are not on the reference's path (without_timestamps=True everywhere)")
+    _refuse_unsupported(options)
     single = mel.dim() == 2
     if single:
         mel = mel[None]
@@ -353,15 +396,26 @@ def decode(model, mel: torch.Tensor, options: DecodingOptions = DecodingOptions(
     B = feats.shape[0]
     tok = get_tokenizer(model.is_multilingual, num_languages=model.num_languages, language=options.language or "en",
                         task=options.task)
-    initial = list(tok.sot_sequence_including_notimestamps)
+    # without_timestamps=False: mlx_whisper.transcribe's decode (the reference's scripts/evaluate_model.py:112-119): the prompt is
+    # the three-token sot_sequence and ApplyTimestampRules runs in every greedy update
+    timed = not options.without_timestamps
+    rules = timestamp_rules(tok, options.max_initial_timestamp) if timed else None
+    initial = list(tok.sot_sequence) if timed else list(tok.sot_sequence_including_notimestamps)
     languages = [options.language or "en"] * B
     lang_probs = [None] * B
+    no_speech = [float("nan")] * B  # filled on the timestamp path only: the without_timestamps=True path stays as it was
     if options.language is None:
         # NOTE: one language per batch row in the reference; rows may differ, so decode per detected group
-        lang_tokens, probs = detect_language(model, feats, tok)
+        if timed:
+            lang_tokens, probs, nsp = detect_language(model, feats, tok, with_no_speech=True)
+            no_speech = [float(v) for v in nsp]
+        else:
+            lang_tokens, probs = detect_language(model, feats, tok)
         from .tokenizer import LANGUAGES
         languages = [LANGUAGES[int(t) - tok.sot - 1] for t in lang_tokens]
         lang_probs = [dict(zip(LANGUAGES[: tok.num_languages], p.tolist())) for p in probs]
+    elif timed:
+        no_speech = [float(v) for v in no_speech_probs(model, feats, tok)]
     always, first = _suppress_lists(options, tok)
     sample_len = options.sample_len or d.n_text_ctx // 2
     results: List[Optional[DecodingResult]] = [None] * B
@@ -370,14 +424,14 @@ def decode(model, mel: torch.Tensor, options: DecodingOptions = DecodingOptions(
         init = list(initial)
         init[1] = tok.to_language_token(lang)
         sub = feats[rows] if len(rows) != B else feats
-        g = greedy_decode_tokens(model, sub, init, always, first, tok.eot, max_new_tokens=sample_len)
+        g = greedy_decode_tokens(model, sub, init, always, first, tok.eot, max_new_tokens=sample_len, rules=rules)
         for j, i in enumerate(rows):
             row = g.tokens[j, len(init):].tolist()
             if tok.eot in row:
                 row = row[: row.index(tok.eot)]
-            text = tok.decode(row).strip()
+            text = tok.decode([t for t in row if t < tok.timestamp_begin]).strip()  # tokens keeps the timestamps, text does not
             comp = len(text.encode("utf-8")) / max(len(zlib.compress(text.encode("utf-8"))), 1) if text else float("nan")
             results[i] = DecodingResult(audio_features=feats[i], language=lang, language_probs=lang_probs[i], tokens=row,
                                         text=text, avg_logprob=float(g.sum_logprobs[j]) / (len(row) + 1),
-                                        temperature=options.temperature, compression_ratio=comp)
+                                        temperature=options.temperature, compression_ratio=comp, no_speech_prob=no_speech[i])
     return results[0] if single else results

@@ -52,7 +52,8 @@ import torch
 
 from . import _lib
 from . import audio as A
-from .decoding import (DecodingOptions, DecodingResult, _mask, _packed_for, _state_for, _suppress_lists, _use_prefill)
+from .decoding import (DecodingOptions, DecodingResult, _dec_prefill, _dec_run, _mask, _packed_for, _refuse_unsupported, _state_for,
+                       _suppress_lists, _use_prefill, timestamp_rules)
 import os
 
 from .runtime import OWN_STREAM_COUNT, hw_queues, ptr, sptr, use_stream
@@ -78,10 +79,12 @@ class PassResult:
     _tok: object = None
     _eot: int = 0
     _temperature: float = 0.0
+    no_speech_probs: Optional[np.ndarray] = None   # [B], the timestamp path only (options.without_timestamps=False)
     _results: Optional[List[DecodingResult]] = field(default=None, repr=False)
 
     def rows(self) -> List[List[int]]:
-        """new tokens of every clip, cut at the first EOT (DecodingTask.run: tokens[sample_begin : first eot])"""
+        """new tokens of every clip, cut at the first EOT (DecodingTask.run: tokens[sample_begin : first eot]); on the timestamp
+        path the timestamp tokens stay in"""
         out = []
         for r in self.tokens[:, self.n_init:]:
             r = r.tolist()
@@ -92,13 +95,15 @@ class PassResult:
     def results(self) -> List[DecodingResult]:
         if self._results is None:
             res = []
+            tb = self._tok.timestamp_begin
             for i, row in enumerate(self.rows()):
-                text = self._tok.decode(row).strip()
+                text = self._tok.decode([t for t in row if t < tb]).strip()
                 comp = len(text.encode("utf-8")) / max(len(zlib.compress(text.encode("utf-8"))), 1) if text else float("nan")
                 res.append(DecodingResult(audio_features=self.audio_features[i], language=self.languages[i],
                                           language_probs=self.language_probs[i], tokens=row, text=text,
                                           avg_logprob=float(self.sum_logprobs[i]) / (len(row) + 1), temperature=self._temperature,
-                                          compression_ratio=comp))
+                                          compression_ratio=comp,
+                                          no_speech_prob=float("nan") if self.no_speech_probs is None else float(self.no_speech_probs[i])))
             self._results = res
         return self._results
 
@@ -132,6 +137,7 @@ class _Pass:
     stop_at: Optional[int] = None     # steps after which a probe saw every row at EOT
     lang_tok: Optional[torch.Tensor] = None
     lang_logits: Optional[torch.Tensor] = None
+    no_speech: Optional[torch.Tensor] = None   # [B] softmax of the [sot] pass's logits at <|nospeech|> (timestamp path)
     keep: tuple = ()
     sizes: tuple = ()      # clips of every batch of the decode group, in input order (sum = B)
     indices: tuple = ()    # their positions in the input sequence
@@ -177,10 +183,7 @@ class TranscribePipeline:
                  max_new_tokens: Optional[int] = None, stop_on_eot: bool = True, check_every: int = 8,
                  cross_splits: Optional[int] = None, use_graph: bool = True, decode_group: int = 1):
         options = options or DecodingOptions(language="en", without_timestamps=True)
-        if options.beam_size or (options.best_of or 1) > 1 or options.temperature != 0.0:
-            raise NotImplementedError("the reference only ever runs greedy decode (SURVEY.md section 0)")
-        if not options.without_timestamps:
-            raise NotImplementedError("timestamp rules are not on the reference's path (without_timestamps=True everywhere)")
+        _refuse_unsupported(options)
         if passes_in_flight < 1:
             raise _lib.WipaError(f"passes_in_flight must be >= 1, got {passes_in_flight}")
         if decode_group < 1:
@@ -192,7 +195,11 @@ class TranscribePipeline:
         d = model.dims
         self.tok = get_tokenizer(model.is_multilingual, num_languages=model.num_languages, language=options.language or "en",
                                  task=options.task)
-        self.initial = list(self.tok.sot_sequence_including_notimestamps)
+        # without_timestamps=False (mlx_whisper.transcribe's decode): the three-token prompt, ApplyTimestampRules in every greedy
+        # update on the device (wipa_decoder_run_rules) and the no-speech probability of a [sot] pass.  Same schedule, same probes.
+        self.timed = not options.without_timestamps
+        self.rules = timestamp_rules(self.tok, options.max_initial_timestamp) if self.timed else None
+        self.initial = list(self.tok.sot_sequence) if self.timed else list(self.tok.sot_sequence_including_notimestamps)
         self.always, self.first = _suppress_lists(options, self.tok)
         n_new = max_new_tokens if max_new_tokens is not None else (options.sample_len or d.n_text_ctx // 2)
         self.max_new = min(int(n_new), d.n_text_ctx - len(self.initial))
@@ -269,8 +276,7 @@ class TranscribePipeline:
     def _run(self, p: _Pass, n: int) -> None:
         L = _lib.lib()
         st = p.state
-        _lib.check(L.wipa_decoder_run(C.byref(p.pk["cfg"]), p.pk["dec_tab"], ptr(st.blob), st.blob.numel(), p.B, p.n_init, p.eot,
-                                      ptr(p.masks[1]), ptr(p.masks[0]), n, int(self.use_graph), sptr(p.stream)), "wipa_decoder_run")
+        _dec_run(L, p.pk, st, p.B, p.n_init, p.eot, p.masks[1], p.masks[0], n, self.use_graph, self.rules, p.stream)
         p.enqueued += n
 
     def _enqueue_chunks(self, p: _Pass) -> None:
@@ -307,7 +313,15 @@ class TranscribePipeline:
             keep = [feats, m_always, m_first] + held
             cfg, tab, blob, nb = C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel()
             _lib.check(L.wipa_decoder_set_audio(cfg, tab, ptr(feats), blob, nb, B, sptr(s)), "wipa_decoder_set_audio")
-            lang_tok = lang_logits = None
+            lang_tok = lang_logits = no_speech = None
+            if self.lang_ids is None and self.timed:
+                # the timestamp path reports no_speech_prob: one decoder step on [sot] (the pass language detection makes), softmax
+                # of its unfiltered logits at <|nospeech|>; the token it samples is overwritten by the prompt below
+                sot = (C.c_int32 * 1)(int(self.tok.sot))
+                _lib.check(L.wipa_decoder_begin(cfg, blob, nb, B, sot, 1, sptr(s)), "wipa_decoder_begin")
+                _lib.check(L.wipa_decoder_run(cfg, tab, blob, nb, B, 1, -1, ptr(m_always), ptr(m_always), 1, int(self.use_graph), sptr(s)),
+                           "wipa_decoder_run")
+                no_speech = torch.softmax(st.logits.float(), dim=-1)[:, int(self.tok.no_speech)].clone()
             if self.lang_ids is not None:
                 # Whisper.detect_language (train_whisper_ipa.py:339 via language=None): one decoder pass on [sot], every logit but
                 # the language tokens masked, argmax -- as decoding.detect_language, but the winners stay on the device and go
@@ -320,15 +334,16 @@ class TranscribePipeline:
                            "wipa_decoder_run")
                 lang_tok = st.tokens[:, 1].clone()
                 lang_logits = st.logits[:, self.lang_ids].float().clone()
+                if self.timed:  # the same pass gives the no-speech probability
+                    no_speech = torch.softmax(st.logits.float(), dim=-1)[:, int(self.tok.no_speech)].clone()
             init = (C.c_int32 * n_init)(*[int(t) for t in self.initial])
             _lib.check(L.wipa_decoder_begin(cfg, blob, nb, B, init, n_init, sptr(s)), "wipa_decoder_begin")
             if lang_tok is not None:
                 st.tokens[:, 1].copy_(lang_tok)
             p = _Pass(group[0][1], slot, s, st, pk, B, n_init, total, 0, (m_always, m_first), feats, int(self.tok.eot),
-                      lang_tok=lang_tok, lang_logits=lang_logits, keep=tuple(keep), sizes=sizes, indices=tuple(i for _, i in group))
+                      lang_tok=lang_tok, lang_logits=lang_logits, no_speech=no_speech, keep=tuple(keep), sizes=sizes, indices=tuple(i for _, i in group))
             if _use_prefill(n_init, total):  # the prompt positions and the first new token in one batched pass
-                _lib.check(L.wipa_decoder_prefill(cfg, tab, blob, nb, B, n_init, p.eot, ptr(m_first), ptr(m_always), int(self.use_graph),
-                                                  sptr(s)), "wipa_decoder_prefill")
+                _dec_prefill(L, pk, st, B, n_init, p.eot, m_first, m_always, self.use_graph, self.rules, s)
                 p.enqueued = n_init
             if not self.stop_on_eot:
                 if p.enqueued < total:
@@ -364,6 +379,7 @@ class TranscribePipeline:
             slp = p.state.sum_logprobs.cpu().numpy().copy()
             lang_tok = p.lang_tok.cpu().numpy() if p.lang_tok is not None else None
             lang_logits = p.lang_logits.cpu() if p.lang_logits is not None else None
+            no_speech = p.no_speech.cpu().numpy().astype(np.float64) if p.no_speech is not None else None
         p.stream.synchronize()
         languages_all = [self.options.language or "en"] * p.B
         probs_all: List[Optional[dict]] = [None] * p.B
@@ -383,7 +399,8 @@ class TranscribePipeline:
                     n_steps = int(np.argmax(all_eot)) + 1
                     t = t[:, : p.n_init + n_steps]
             out.append(PassResult(t, p.n_init, n_steps, slp[r0:r0 + size], languages_all[r0:r0 + size], probs_all[r0:r0 + size],
-                                  p.feats[r0:r0 + size], index=index, _tok=self.tok, _eot=p.eot, _temperature=self.options.temperature))
+                                  p.feats[r0:r0 + size], index=index, _tok=self.tok, _eot=p.eot, _temperature=self.options.temperature,
+                                  no_speech_probs=None if no_speech is None else no_speech[r0:r0 + size]))
             r0 += size
         return out
 

@@ -220,6 +220,23 @@ class Tokenizer:
             out.append(buf.decode("utf-8", errors="replace"))
         return "".join(out)
 
+    def decode_with_timestamps(self, token_ids: Sequence[int]) -> str:
+        """mlx_whisper.tokenizer.Tokenizer.decode_with_timestamps: the text with every timestamp token rendered as
+        <|12.34|> (0.02 s per token above timestamp_begin)."""
+        out, run = [], []
+        for t in token_ids:
+            t = int(t)
+            if t >= self.timestamp_begin:
+                if run:
+                    out.append(self.decode(run))
+                    run = []
+                out.append(f"<|{(t - self.timestamp_begin) * 0.02:.2f}|>")
+            else:
+                run.append(t)
+        if run:
+            out.append(self.decode(run))
+        return "".join(out)
+
     @property
     def non_speech_tokens(self) -> Tuple[int, ...]:
         """mlx_whisper.tokenizer.Tokenizer.non_speech_tokens: derived from the vocabulary when it

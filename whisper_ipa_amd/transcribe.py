@@ -1,0 +1,202 @@
+"""``transcribe(model, audio, ...)``: mlx_whisper.transcribe as the reference's base-model leg calls it
+(scripts/evaluate_model.py:112-119: ``mlx_whisper.transcribe(audio_path, path_or_hf_repo=..., language=..., word_timestamps=False)``)
+-- decode with timestamps on, cut the result into segments at consecutive timestamp pairs, skip silent windows, and walk files
+longer than 30 s window by window.  The window loop is openai-whisper's transcribe.py (mlx_whisper 0.4.3 ports it;
+[UPSTREAM-UNVERIFIED] where the port cannot be inspected): ``seek`` advances in mel frames, to the last closed timestamp pair
+unless the window ends in a single timestamp.
+
+What differs from upstream, on purpose:
+  * the next windows of ALL files still in progress go through log-mel, encoder and decode as one batch per round (rows of one
+    batch belong to different files at different seeks); upstream transcribes one file at a time;
+  * each window's log-mel is computed from the window's own samples (``pad_or_trim`` + the existing kernel), so the 8 dB floor
+    under the maximum is per window; upstream computes one log-mel of the whole file.  A single-window file is unaffected;
+  * only temperature 0 runs.  Where ``compression_ratio_threshold`` / ``logprob_threshold`` would have made upstream retry at a
+    higher temperature, the window's segments carry ``needs_fallback=True`` and one warning is printed per call.
+"""
+from __future__ import annotations
+
+import warnings
+from typing import Callable, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+
+from .audio import HOP_LENGTH, N_FRAMES, N_SAMPLES, SAMPLE_RATE
+
+FRAMES_PER_SECOND = SAMPLE_RATE // HOP_LENGTH  # 100 mel frames per second
+INPUT_STRIDE = 2                               # mel frames per encoder output position (N_FRAMES // n_audio_ctx)
+TIME_PRECISION = INPUT_STRIDE * HOP_LENGTH / SAMPLE_RATE  # 0.02 s per timestamp token
+
+SEGMENT_KEYS = ("id", "seek", "start", "end", "text", "tokens", "temperature", "avg_logprob", "compression_ratio", "no_speech_prob")
+
+
+def split_segments(tokens: Sequence[int], tb: int, time_offset: float, segment_size: int) -> Tuple[List[dict], int]:
+    """One decoded window -> (segments, seek advance in mel frames).  ``tokens``: the window's sampled ids up to EOT, timestamps
+    included; ``tb``: timestamp_begin; ``segment_size``: the window's content in mel frames (<= 3000).  Each segment is
+    {"start", "end", "tokens"}.  Segments are cut at consecutive timestamp pairs; if the window ends in a single timestamp the
+    tail after the last pair is a segment too and the whole window is consumed, otherwise ``seek`` moves to the last pair and the
+    tail is decoded again with the next window.  Without any pair the window is one segment: up to its last timestamp if that is
+    not <|0.00|>, else spanning the window."""
+    tokens = [int(t) for t in tokens]
+    is_ts = [t >= tb for t in tokens]
+    single_timestamp_ending = is_ts[-2:] == [False, True]
+    consecutive = [i + 1 for i in range(len(tokens) - 1) if is_ts[i] and is_ts[i + 1]]
+    segments: List[dict] = []
+    if consecutive:
+        slices = list(consecutive)
+        if single_timestamp_ending:
+            slices.append(len(tokens))
+        last = 0
+        for cur in slices:
+            sl = tokens[last:cur]
+            segments.append({"start": time_offset + (sl[0] - tb) * TIME_PRECISION, "end": time_offset + (sl[-1] - tb) * TIME_PRECISION,
+                             "tokens": sl})
+            last = cur
+        if single_timestamp_ending:
+            return segments, segment_size
+        return segments, (tokens[last - 1] - tb) * INPUT_STRIDE
+    duration = segment_size * HOP_LENGTH / SAMPLE_RATE
+    stamps = [t for t in tokens if t >= tb]
+    if stamps and stamps[-1] != tb:
+        duration = (stamps[-1] - tb) * TIME_PRECISION
+    segments.append({"start": time_offset, "end": time_offset + duration, "tokens": tokens})
+    return segments, segment_size
+
+
+def _refuse(condition_on_previous_text, initial_prompt, word_timestamps, clip_timestamps, hallucination_silence_threshold, temperature,
+            decode_options) -> None:
+    if condition_on_previous_text:
+        raise NotImplementedError("condition_on_previous_text=True (prompt conditioning) is not implemented")
+    if initial_prompt is not None:
+        raise NotImplementedError("initial_prompt (prompt conditioning) is not implemented")
+    if word_timestamps:
+        raise NotImplementedError("word_timestamps=True is not implemented")
+    if clip_timestamps not in (None, "0", [0], (0,)):
+        raise NotImplementedError("clip_timestamps is not implemented")
+    if hallucination_silence_threshold is not None:
+        raise NotImplementedError("hallucination_silence_threshold is not implemented")
+    temps = (temperature,) if isinstance(temperature, (int, float)) else tuple(temperature)
+    if not temps or float(temps[0]) != 0.0:
+        raise NotImplementedError("temperature must be 0.0 or a tuple that starts with 0.0: only temperature 0 is run")
+    for k in ("beam_size", "best_of", "prompt", "prefix"):
+        if decode_options.get(k) is not None:
+            raise NotImplementedError(f"{k} is not implemented")
+
+
+def _model_decoder(model, decode_options: dict) -> Callable:
+    """the default ``decode_fn``: windows [n, 480000] f32 + per-row languages (None: detect) -> DecodingResults, through the
+    package's log-mel, encoder and ``decode(without_timestamps=False)``; rows are grouped by language"""
+    import torch
+
+    from . import audio as A
+    from .decoding import DecodingOptions, decode
+
+    def run(windows: np.ndarray, languages: List[Optional[str]]):
+        out = [None] * len(languages)
+        dev_audio = torch.from_numpy(np.ascontiguousarray(windows)).to(model.device)
+        mel = A.log_mel_spectrogram(dev_audio, n_mels=model.dims.n_mels)
+        for lang in sorted(set(languages), key=lambda l: (l is not None, l or "")):
+            rows = [i for i, l in enumerate(languages) if l == lang]
+            opts = DecodingOptions(**{**decode_options, "language": lang, "without_timestamps": False, "temperature": 0.0})
+            res = decode(model, mel[rows] if len(rows) != len(languages) else mel, opts)
+            for i, r in zip(rows, res):
+                out[i] = r
+        return out
+
+    return run
+
+
+def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Union[float, Tuple[float, ...]] = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
+               compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
+               no_speech_threshold: Optional[float] = 0.6, condition_on_previous_text: bool = False,
+               initial_prompt: Optional[str] = None, word_timestamps: bool = False, clip_timestamps=None,
+               hallucination_silence_threshold: Optional[float] = None, language: Optional[str] = None, decode_fn: Optional[Callable] = None,
+               tokenizer=None, **decode_options):
+    """``audio``: a path, a 16 kHz mono float array, or a list of them.  Returns {"text", "segments", "language"} (a list of
+    them for a list) with mlx_whisper's segment keys (``SEGMENT_KEYS``; plus ``needs_fallback`` where upstream would have
+    retried).  ``condition_on_previous_text`` defaults to False here: True is refused, like every option this path does not
+    serve.  ``decode_fn(windows [n, 480000] f32, languages [n])`` -> objects with tokens / avg_logprob / no_speech_prob /
+    compression_ratio / temperature / language replaces the model's decode (tests; ``tokenizer`` is then required when
+    ``model`` is None)."""
+    _refuse(condition_on_previous_text, initial_prompt, word_timestamps, clip_timestamps, hallucination_silence_threshold, temperature,
+            decode_options)
+    single = not isinstance(audio, (list, tuple))
+    items = [audio] if single else list(audio)
+    clips = []
+    for a in items:
+        if isinstance(a, str):
+            from .audio import load_audio
+
+            a = load_audio(a)
+        a = np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype=np.float32)
+        if a.ndim != 1:
+            raise ValueError(f"transcribe: audio is a path or a mono sample array, got shape {a.shape}")
+        clips.append(a)
+    if tokenizer is None:
+        from .tokenizer import get_tokenizer
+
+        tokenizer = get_tokenizer(model.is_multilingual, num_languages=model.num_languages, language=language or "en", task="transcribe")
+    tok, tb = tokenizer, int(tokenizer.timestamp_begin)
+    decode_fn = decode_fn or _model_decoder(model, decode_options)
+
+    n = len(clips)
+    content_frames = [len(a) // HOP_LENGTH for a in clips]
+    seek = [0] * n
+    languages: List[Optional[str]] = [language] * n
+    all_segments: List[List[dict]] = [[] for _ in range(n)]
+    all_tokens: List[List[int]] = [[] for _ in range(n)]
+    warned = False
+    while True:
+        live = [i for i in range(n) if seek[i] < content_frames[i]]
+        if not live:
+            break
+        # one batch per round: the next window of every file still in progress
+        sizes = [min(N_FRAMES, content_frames[i] - seek[i]) for i in live]
+        windows = np.zeros((len(live), N_SAMPLES), dtype=np.float32)
+        for r, (i, size) in enumerate(zip(live, sizes)):
+            s0 = seek[i] * HOP_LENGTH
+            chunk = clips[i][s0:s0 + size * HOP_LENGTH]
+            windows[r, :len(chunk)] = chunk  # pad_or_trim of the window's own samples
+        results = decode_fn(windows, [languages[i] for i in live])
+        for i, size, res in zip(live, sizes, results):
+            if languages[i] is None:
+                languages[i] = res.language  # detected on the file's first window, kept for the rest
+            time_offset = seek[i] * HOP_LENGTH / SAMPLE_RATE
+            tokens = [int(t) for t in res.tokens]
+            if no_speech_threshold is not None:
+                skip = res.no_speech_prob > no_speech_threshold
+                if logprob_threshold is not None and res.avg_logprob > logprob_threshold:
+                    skip = False  # a confident transcript overrides the no-speech probability
+                if skip:
+                    seek[i] += size
+                    continue
+            needs_fallback = False
+            if compression_ratio_threshold is not None and res.compression_ratio > compression_ratio_threshold:
+                needs_fallback = True  # too repetitive
+            if logprob_threshold is not None and res.avg_logprob < logprob_threshold:
+                needs_fallback = True  # average log-probability too low
+            if no_speech_threshold is not None and res.no_speech_prob > no_speech_threshold and logprob_threshold is not None \
+                    and res.avg_logprob < logprob_threshold:
+                needs_fallback = False  # silence
+            if needs_fallback and not warned:
+                warnings.warn("whisper_ipa_amd.transcribe: a window failed compression_ratio_threshold / logprob_threshold; upstream would "
+                              "retry at a higher temperature, this path runs temperature 0 only (segments carry needs_fallback=True)",
+                              RuntimeWarning, stacklevel=2)
+                warned = True
+            at = seek[i]
+            segs, advance = split_segments(tokens, tb, time_offset, size)
+            seek[i] += advance
+            for sg in segs:
+                text = tok.decode([t for t in sg["tokens"] if t < tok.eot])
+                if sg["start"] == sg["end"] or text.strip() == "":
+                    text, sg["tokens"] = "", []
+                seg = {"id": len(all_segments[i]), "seek": at, "start": sg["start"], "end": sg["end"], "text": text, "tokens": sg["tokens"],
+                       "temperature": res.temperature, "avg_logprob": res.avg_logprob, "compression_ratio": res.compression_ratio,
+                       "no_speech_prob": res.no_speech_prob}
+                if needs_fallback:
+                    seg["needs_fallback"] = True
+                all_segments[i].append(seg)
+                all_tokens[i].extend(sg["tokens"])
+            if advance <= 0:  # a pair at <|0.00|> only: never stand still
+                seek[i] += size
+    out = [{"text": tok.decode([t for t in all_tokens[i] if t < tb]), "segments": all_segments[i], "language": languages[i]} for i in range(n)]
+    return out[0] if single else out
