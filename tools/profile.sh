@@ -16,6 +16,10 @@
 #   xa-sweep     headline line over xa residency budgets (WIPA_XA_RESIDENT_MB), 4 passes and 1 pass in flight
 #   xa-ab        headline A/B, alternating: every group default policy (-1) against the default budget (PARENT=<dir>: + the parent's build)
 #   xa-trace     kernel traces at -1 and at the default budget: lone durations of the streaming kernel and the skinny GEMMs by grid
+#   abs-trace    kernel trace of `bench.py --gpus 1 --steps 6 --warmup 2`, by kernel and grid (TAG=before|after names the file)
+#   abs-ab       the streaming kernel's loop variants (WIPA_ABS_LOOP): lone streaming / merge launches at 0 and 1, alternating in one process;
+#                the headline line of PARENT=<built checkout of the commit before> against this tree, alternating, five runs each;
+#                `--dump-outputs` of both compared with cmp
 #   final        the tree's final check: pytest -m gpu, smoke(), the default bench line
 # RAW rocprofv3 output stays on the GPU box (/tmp/wipa_prof/$ROUND: a traced bench run is > 64 MiB, more than gpurun copies back);
 # every mode ends by running tools/summaries.py THERE, so what comes back under gpurun_out/$ROUND/ is the summaries (named as they
@@ -153,6 +157,31 @@ xa-sweep|xa-ab)
     else for MB in -1 0 16 32 48 64 96; do xa_line "MB=$MB rep$r" $MB | tee -a $F || exit 1; done; fi
   done
   if [ $MODE = xa-sweep ]; then for r in 1 2 3; do for MB in -1 0 48 148; do xa_line "MB=$MB rep$r" $MB --pipeline 1 | tee -a $F || exit 1; done; done; fi ;;
+abs-trace)
+  TAG=${TAG:-after}
+  timeout -k 10 420 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/abs_kt_$TAG -o bench -- python3 $ROOT/bench.py --gpus 1 --steps 6 --warmup 2 > $OUT/abs_kt_$TAG.log 2>&1 || exit 1
+  python3 $ROOT/tools/trace_by_grid.py "$(find $OUT/abs_kt_$TAG -name '*kernel_trace.csv' | head -1)" "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --gpus 1 --steps 6 --warmup 2   (MI355X, $TAG; all passes incl. warm-up; the tracer runs the passes in flight one after another)" > $KEEP/abs_loop_$TAG.txt || exit 1
+  head -6 $KEEP/abs_loop_$TAG.txt ;;
+abs-ab)
+  cd $ROOT
+  [ -n "$PARENT" ] || { echo "abs-ab needs PARENT=<built checkout of the commit before>"; exit 2; }
+  F=$KEEP/abs_loop_ab.txt; : > $F
+  echo "# lone launches: python3 tools/cross_absorbed_bench.py 64 ab" >> $F
+  timeout -k 10 200 python3 tools/cross_absorbed_bench.py 64 ab >> $F 2> $OUT/abs_lone.err || exit 1
+  echo "# headline: python3 bench.py --gpus 1 --steps 20 --warmup 5, the parent's build and this tree alternating" >> $F
+  abs_line() {  # label dir [VAR=value]
+    (cd $2 && env $3 timeout -k 10 200 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/abs_tmp.json 2> $OUT/abs_tmp.err) || return 1
+    python3 -c "import json; d = json.loads(open('$OUT/abs_tmp.json').read().strip().splitlines()[-1]); print('$1', 'ms_per_step', d['ms_per_step'], 'passes_identical', d['passes_identical'], 'tokens_checksum', d['tokens_checksum'])"
+  }
+  for r in 1 2 3 4 5; do
+    abs_line "parent rep$r" $PARENT | tee -a $F || exit 1
+    abs_line "new rep$r" $ROOT | tee -a $F || exit 1
+  done
+  abs_line "new WIPA_ABS_LOOP=0" $ROOT WIPA_ABS_LOOP=0 | tee -a $F || exit 1
+  echo "# --dump-outputs of the parent's build against this tree (cmp)" >> $F
+  (cd $PARENT && timeout -k 10 200 python3 bench.py --gpus 1 --steps 4 --warmup 1 --dump-outputs $OUT/abs_dump_parent > /dev/null 2>&1) || exit 1
+  timeout -k 10 200 python3 bench.py --gpus 1 --steps 4 --warmup 1 --dump-outputs $OUT/abs_dump_new > /dev/null 2>&1 || exit 1
+  for f in $(ls $OUT/abs_dump_parent); do if cmp -s $OUT/abs_dump_parent/$f $OUT/abs_dump_new/$f; then echo "$f EQUAL"; else echo "$f DIFFERENT"; fi; done | tee -a $F ;;
 xa-trace)
   # lone durations of the streaming kernel (grids 2x64 and 4x64) and of the skinny GEMMs next to it, every group default policy
   # against the default budget: a kernel trace of its own per setting (no counters, no other tracing domain)
@@ -161,6 +190,6 @@ xa-trace)
     else WIPA_XA_RESIDENT_MB=$MB timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/xa_kt_$MB -o bench -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-finetune --no-other-configs --steps 6 > $OUT/xa_kt_$MB.log 2>&1; fi || exit 1
   done
   python3 $ROOT/tools/xa_trace_summary.py "all-default=$(find $OUT/xa_kt_-1 -name '*kernel_trace.csv' | head -1)" "budget=$(find $OUT/xa_kt_dflt -name '*kernel_trace.csv' | head -1)" | tee $KEEP/xa_residency_trace.txt ;;
-*) echo "usage: bash tools/profile.sh bench|gemm|cross|train-size|gaps|chain-probe|chain-pad|gemm-probe|group-sweep|xa-probe|xa-sweep|xa-ab|xa-trace|final   (ROUND=r05 SPLITS=2)"; exit 2 ;;
+*) echo "usage: bash tools/profile.sh bench|gemm|cross|train-size|gaps|chain-probe|chain-pad|gemm-probe|group-sweep|xa-probe|xa-sweep|xa-ab|xa-trace|abs-trace|abs-ab|final   (ROUND=r05 SPLITS=2)"; exit 2 ;;
 esac
 echo "== done $MODE"

@@ -19,10 +19,11 @@
 //                            16-frame groups of xa in two private LDS slots filled by LDS-DMA (no barrier in the loop), computes
 //                            S^T[16 frames, 16 heads] over all channels against the absorbed queries held in registers, a
 //                            softmax against a fixed per-head reference, and O'[16 heads, d] += P group with the SAME group read
-//                            column-wise by ds_read_b64_tr_b16; the three waves' (m, l, O') merge through LDS at the end
+//                            column-wise by ds_read_b64_tr_b16 (the reads of the next column block in flight behind the current
+//                            block's MFMAs, counted waits); the three waves' (m, l, O') merge through LDS at the end
 //   cross_absorbed_kernel    (d = 1024, and WIPA_ABS_KERNEL=1 for A/B runs) the first form: 32-frame tiles shared by 4 waves
 //                            that split the CHANNELS, partial scores exchanged through LDS in a fixed order, online softmax
-//   cross_merge_proj_kernel  merges the splits (fixed order), out_h = (O'_h / l_h) Wv_h^T + bv_h -> [B, d] bf16
+//   cross_merge_proj_kernel  merges the splits (fixed order; built per split count), out_h = (O'_h / l_h) Wv_h^T + bv_h -> [B, d] bf16
 //
 // Rounding points differ from the cached-K/V path (K and V are never rounded to bf16 here; Qp and O' are): the results
 // are equal up to bf16 noise, and closer to the f32 arithmetic.  bf16 models with <= 16 heads and d in {384, 512, 768, 1024}.
@@ -32,6 +33,15 @@
 
 #include "attn_stream.h"
 #include "wipa_common.h"
+
+// WIPA_ABS_LOOP=0 selects the streaming kernel's loop and the merge launch as they were before the pipelined P x group phase (A/B
+// runs, the bit-equality test); default 1; 2 = the pipelined loop with the general merge launch, 3 = the loop before with the merge
+// launch built for the split count (the parts apart).  Read per call like the other step variants: the decode step's graph key carries it.
+int wipa_cross_absorbed_loop_variant() {
+    const char* e = getenv("WIPA_ABS_LOOP");
+    const int v = e ? atoi(e) : 1;
+    return (v >= 0 && v <= 3) ? v : 1;
+}
 
 namespace {
 
@@ -319,7 +329,61 @@ struct AbsCfg2 {
                  : "v"(A[0]), "v"(A[1]), "v"(A[2]), "v"(A[3]), "v"(A[4]), "v"(A[5]), "v"(A[6]), "v"(A[7])                           \
                  : "memory")
 
-template <int D, int NW_>
+// The pipelined P x group phase (PIPE): the transposed reads of column block k + 1 are in flight while block k's MFMAs issue.
+// LDS operations return in order, so a counted wait retires exactly the older block.  The rule above still holds -- a register a
+// read writes is valid only once its wait has run inside a statement that names it: WIPA_TR8_ISSUE only starts the reads of a
+// block (Y), WIPA_TR8_NEXT starts the next block's reads (Y) and waits until at most those eight are outstanding, which retires
+// the block before (X, read-write operands: the MFMAs take X from THIS statement, not from the one that issued its reads), and
+// WIPA_TR8_LAST retires the last block.  Nothing but VALU work sits between a block's issue and its wait; any LDS or scalar load
+// the compiler might put there only makes the counted wait stricter.
+#define WIPA_TR8_ISSUE(Y, A, IMM)                                                                                                    \
+    asm volatile("ds_read_b64_tr_b16 %0, %8 offset:" #IMM "\n\tds_read_b64_tr_b16 %1, %9 offset:" #IMM                              \
+                 "\n\tds_read_b64_tr_b16 %2, %10 offset:" #IMM "\n\tds_read_b64_tr_b16 %3, %11 offset:" #IMM                          \
+                 "\n\tds_read_b64_tr_b16 %4, %12 offset:" #IMM "\n\tds_read_b64_tr_b16 %5, %13 offset:" #IMM                          \
+                 "\n\tds_read_b64_tr_b16 %6, %14 offset:" #IMM "\n\tds_read_b64_tr_b16 %7, %15 offset:" #IMM                          \
+                 : "=&v"(Y[0]), "=&v"(Y[1]), "=&v"(Y[2]), "=&v"(Y[3]), "=&v"(Y[4]), "=&v"(Y[5]), "=&v"(Y[6]), "=&v"(Y[7])           \
+                 : "v"(A[0]), "v"(A[1]), "v"(A[2]), "v"(A[3]), "v"(A[4]), "v"(A[5]), "v"(A[6]), "v"(A[7])                           \
+                 : "memory")
+#define WIPA_TR8_NEXT(Y, X, A, IMM)                                                                                                  \
+    asm volatile("ds_read_b64_tr_b16 %0, %16 offset:" #IMM "\n\tds_read_b64_tr_b16 %1, %17 offset:" #IMM                            \
+                 "\n\tds_read_b64_tr_b16 %2, %18 offset:" #IMM "\n\tds_read_b64_tr_b16 %3, %19 offset:" #IMM                          \
+                 "\n\tds_read_b64_tr_b16 %4, %20 offset:" #IMM "\n\tds_read_b64_tr_b16 %5, %21 offset:" #IMM                          \
+                 "\n\tds_read_b64_tr_b16 %6, %22 offset:" #IMM "\n\tds_read_b64_tr_b16 %7, %23 offset:" #IMM "\n\ts_waitcnt lgkmcnt(8)" \
+                 : "=&v"(Y[0]), "=&v"(Y[1]), "=&v"(Y[2]), "=&v"(Y[3]), "=&v"(Y[4]), "=&v"(Y[5]), "=&v"(Y[6]), "=&v"(Y[7]),          \
+                   "+v"(X[0]), "+v"(X[1]), "+v"(X[2]), "+v"(X[3]), "+v"(X[4]), "+v"(X[5]), "+v"(X[6]), "+v"(X[7])                   \
+                 : "v"(A[0]), "v"(A[1]), "v"(A[2]), "v"(A[3]), "v"(A[4]), "v"(A[5]), "v"(A[6]), "v"(A[7])                           \
+                 : "memory")
+#define WIPA_TR8_LAST(X)                                                                                                             \
+    asm volatile("s_waitcnt lgkmcnt(0)"                                                                                              \
+                 : "+v"(X[0]), "+v"(X[1]), "+v"(X[2]), "+v"(X[3]), "+v"(X[4]), "+v"(X[5]), "+v"(X[6]), "+v"(X[7])                   \
+                 :                                                                                                                   \
+                 : "memory")
+
+// The value of lane ^ 16 / lane ^ 32 combined with the lane's own through the REGISTER FILE (v_permlane16_swap / v_permlane32_swap)
+// instead of __shfl_xor's ds_bpermute, a round trip through the LDS crossbar in the same queue as the operand reads.  Swapping a
+// register with a copy of itself leaves (own, other) in the even rows / the lower half and (other, own) in the odd rows / the upper
+// half of the result pair; max and + of two floats do not depend on the operand order, bit for bit, so the pair is combined as it is.
+__device__ __forceinline__ float max_xor16(float v) {
+    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+__device__ __forceinline__ float max_xor32(float v) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+__device__ __forceinline__ float sum_xor16(float v) {
+    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+__device__ __forceinline__ float sum_xor32(float v) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+
+// PIPE = false is the loop as it was before the pipelined phase (WIPA_ABS_LOOP=0: A/B runs and the bit-equality test): six drained
+// read blocks per group, __shfl_xor exchanges.  Both forms read the same bytes and do the
+// same arithmetic in the same order: same bits.
+template <int D, int NW_, bool PIPE>
 __global__ __launch_bounds__(64 * NW_, 1) void cross_absorbed_v2_kernel(AbsParams p) {
     typedef AbsCfg2<D, NW_> X;
     constexpr int NWV = X::NWV, GF = X::GF, ROWB = X::ROWB, SLOT = X::SLOT;
@@ -442,8 +506,13 @@ __global__ __launch_bounds__(64 * NW_, 1) void cross_absorbed_v2_kernel(AbsParam
             if (f0 + 4 * g + r >= p.Tk) s[r] = NEG_BIG;
             mx = fmaxf(mx, s[r]);
         }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        if constexpr (PIPE) {
+            mx = max_xor16(mx);
+            mx = max_xor32(mx);
+        } else {
+            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        }
         return s;
     };
     // Softmax against a FIXED per-head reference m_ref (the maximum over the wave's first group) instead of a running maximum:
@@ -473,6 +542,14 @@ __global__ __launch_bounds__(64 * NW_, 1) void cross_absorbed_v2_kernel(AbsParam
                 drifted = true;
                 break;
             }
+            unsigned tas[8];  // transposed-read addresses of this slot
+#pragma unroll
+            for (int cc = 0; cc < 8; ++cc) tas[cc] = ta[cc] + slot * SLOT;
+            v2i32 xe[8], xo[8];  // (PIPE) the read blocks in flight: even blocks land in xe, odd ones in xo
+            if constexpr (PIPE) {
+                WIPA_TR8_ISSUE(xe, tas, 0);  // block 0 flies while the probabilities are computed:
+                __builtin_amdgcn_sched_barrier(0);  // left alone, the scheduler sinks the statement below the exponentials
+            }
             float ls = 0.f;
             bf16x4v pf;  // A operand of P x group (16x16x16): row = head l15, k = frames 4g .. 4g + 3 -- the lane's own values
 #pragma unroll
@@ -481,14 +558,40 @@ __global__ __launch_bounds__(64 * NW_, 1) void cross_absorbed_v2_kernel(AbsParam
                 pf[r] = (__bf16)e;
                 ls += e;
             }
-            ls += __shfl_xor(ls, 16, 64);
-            ls += __shfl_xor(ls, 32, 64);
-            l_run += ls;
+            if constexpr (!PIPE) {
+                ls += __shfl_xor(ls, 16, 64);
+                ls += __shfl_xor(ls, 32, 64);
+                l_run += ls;
+            }
             // ---- O'[head][channel] += P x group: ONE transposed read per column tile (rows = frames 4g + q, 16 channels)
-            {
-                unsigned tas[8];
-#pragma unroll
-                for (int cc = 0; cc < 8; ++cc) tas[cc] = ta[cc] + slot * SLOT;
+            if constexpr (PIPE) {
+                // block BLK's MFMAs issue behind the statement that started block BLK + 1's reads (into the other register set) and
+                // retired its own: same reads, same MFMA order per accumulator as below
+                constexpr int NB = CT / 8;
+                __builtin_amdgcn_sched_barrier(0);  // block 0's wait stays behind the exponentials
+#define WIPA_PV_STEP(BLK, CUR, NXT, IMM_NEXT)                                                                                       \
+    if constexpr (NB > BLK) {                                                                                                       \
+        if constexpr (NB > BLK + 1) WIPA_TR8_NEXT(NXT, CUR, tas, IMM_NEXT);                                                         \
+        else {                                                                                                                      \
+            __builtin_amdgcn_sched_barrier(0); /* or the MFMAs of the block before sink below the full wait */                      \
+            WIPA_TR8_LAST(CUR);                                                                                                     \
+        }                                                                                                                           \
+        _Pragma("unroll") for (int cc = 0; cc < 8; ++cc) acc[8 * BLK + cc] =                                                       \
+            __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(pf, __builtin_bit_cast(bf16x4v, CUR[cc]), acc[8 * BLK + cc], 0, 0, 0);       \
+    }
+                WIPA_PV_STEP(0, xe, xo, 256)
+                WIPA_PV_STEP(1, xo, xe, 512)
+                WIPA_PV_STEP(2, xe, xo, 768)
+                WIPA_PV_STEP(3, xo, xe, 1024)
+                WIPA_PV_STEP(4, xe, xo, 1280)
+                WIPA_PV_STEP(5, xo, xe, 1536)
+                WIPA_PV_STEP(6, xe, xo, 1792)
+                WIPA_PV_STEP(7, xo, xe, 2048)
+#undef WIPA_PV_STEP
+                ls = sum_xor16(ls);  // the sum's exchanges ride among the MFMAs
+                ls = sum_xor32(ls);
+                l_run += ls;
+            } else {
 #define WIPA_PV_BLK(BLK, IMM)                                                                                                       \
     if constexpr (CT / 8 > BLK) {                                                                                                   \
         v2i32 x[8];                                                                                                                 \
@@ -555,11 +658,14 @@ __global__ __launch_bounds__(64 * NW_, 1) void cross_absorbed_v2_kernel(AbsParam
             mv[v] = sm[v * 16 + hd];
             M = fmaxf(M, mv[v]);
         }
+        float wgt[NWV];  // the waves' weights of this head, once per head (the same values as inside the column loop: same bits)
+#pragma unroll
+        for (int v = 0; v < NWV; ++v) wgt[v] = __expf(mv[v] - M);
         for (int c4 = tid; 4 * c4 < D; c4 += NWV * 64) {
             f32x4 o = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int v = 0; v < NWV; ++v)  // fixed order
-                o += __expf(mv[v] - M) * *reinterpret_cast<const f32x4*>(so + (v * 16 + hd) * RS + 4 * c4);
+                o += wgt[v] * *reinterpret_cast<const f32x4*>(so + (v * 16 + hd) * RS + 4 * c4);
             *reinterpret_cast<f32x4*>(po + hd * D + 4 * c4) = o;
         }
     }
@@ -574,6 +680,9 @@ __global__ __launch_bounds__(64 * NW_, 1) void cross_absorbed_v2_kernel(AbsParam
     }
 }
 #undef WIPA_TR8
+#undef WIPA_TR8_ISSUE
+#undef WIPA_TR8_NEXT
+#undef WIPA_TR8_LAST
 
 // Qp[b][h][c] = scale * sum_j q[b][h*64 + j] WkT[c][h*64 + j]     (WkT = Wk^T, [d_in][d_out]: 16-byte loads along j)
 // one WAVE per (head 0..15, 16 clips, channel quarter): 192 short independent chains instead of 48 workgroups; heads >= H are
@@ -650,7 +759,11 @@ struct MergeCfg {
 // MFMA (48 column tiles over the waves, the fragments requested with the first loads of the kernel): slab_h[clip][0..d) in f32,
 // one slab per head at slabs_out + h * slab_stride (head 0 carries the out-projection bias).  The next LayerNorm sums x + the H
 // slabs in head order (deterministic; add_slabs_layernorm takes up to 16).  One launch instead of two per layer.
-template <int D, bool OUTP = false>
+// NS: the split count the instantiation is built for.  NS = 4 is the general form (any n_splits <= 4: splits past n_splits are
+// clamped duplicates that carry weight 0), the only one before the specialisation; NS = 1 .. 3 serve n_splits == NS and request and
+// multiply the real splits only, in the same fixed order.  The terms they drop are exact zeros times finite partials, added to sums
+// that started at +0: the results are the same bits, with half the partial loads per lane at two splits.
+template <int D, bool OUTP = false, int NS = 4>
 __global__ __launch_bounds__(64 * MergeCfg<D>::NWM) void cross_merge_proj_kernel(
     const float* __restrict__ part_m, const float* __restrict__ part_l, const float* __restrict__ part_o, int n_splits,
     const __bf16* __restrict__ wv, const float* __restrict__ bv, __bf16* __restrict__ out, int64_t o_rs, int B,
@@ -689,20 +802,20 @@ __global__ __launch_bounds__(64 * MergeCfg<D>::NWM) void cross_merge_proj_kernel
         }
     }
     // ... the split statistics of this lane's clip ...
-    float pm[4], pl[4];
+    float pm[NS], pl[NS];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        const int sc = min(s, n_splits - 1);
+    for (int s = 0; s < NS; ++s) {
+        const int sc = NS == 4 ? min(s, n_splits - 1) : s;
         pm[s] = part_m[((int64_t)bc * n_splits + sc) * 16 + h];
         pl[s] = part_l[((int64_t)bc * n_splits + sc) * 16 + h];
     }
     // ... and the 8-channel pieces of the partial rows its A fragments are made of
-    f32x4 po[KS][4][2];
+    f32x4 po[KS][NS][2];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int sc = min(s, n_splits - 1);
+        for (int s = 0; s < NS; ++s) {
+            const int sc = NS == 4 ? min(s, n_splits - 1) : s;
             const float* pr = part_o + (((int64_t)bc * n_splits + sc) * 16 + h) * D + w * KQ + 32 * ks + 8 * g;
             po[ks][s][0] = *reinterpret_cast<const f32x4*>(pr);
             po[ks][s][1] = *reinterpret_cast<const f32x4*>(pr + 4);
@@ -710,30 +823,33 @@ __global__ __launch_bounds__(64 * MergeCfg<D>::NWM) void cross_merge_proj_kernel
     __builtin_amdgcn_sched_barrier(0);
     // split weights exp(m_s - M) / L: every lane computes them for itself (no shared array, no single-thread section: see the
     // determinism test)
-    float ws[4];
+    float ws[NS];
     {
         float M = NEG_BIG;
 #pragma unroll
-        for (int s = 0; s < 4; ++s)
-            if (s < n_splits) M = fmaxf(M, pm[s]);
+        for (int s = 0; s < NS; ++s)
+            if (NS < 4 || s < n_splits) M = fmaxf(M, pm[s]);
         float Lsum = 0.f;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            ws[s] = s < n_splits ? __expf(pm[s] - M) : 0.f;
-            Lsum += ws[s] * pl[s];
+        for (int s = 0; s < NS; ++s) {
+            ws[s] = (NS < 4 || s < n_splits) ? __expf(pm[s] - M) : 0.f;
+            // a fused multiply-add, spelled out: the general form compiles `Lsum += ws * pl` to one, but with two splits the compiler
+            // pairs the products into a packed multiply and adds them rounded -- another last bit of Lsum in a few rows per launch
+            Lsum = __builtin_fmaf(ws[s], pl[s], Lsum);
         }
         const float inv = 1.0f / Lsum;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) ws[s] *= inv;
+        for (int s = 0; s < NS; ++s) ws[s] *= inv;
     }
     f32x4 acc[4] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
         f32x4 lo = {0.f, 0.f, 0.f, 0.f}, hi = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {  // fixed order; splits past n_splits carry weight 0
-            lo += ws[s] * po[ks][s][0];
-            hi += ws[s] * po[ks][s][1];
+        for (int s = 0; s < NS; ++s) {  // fixed order; (NS = 4) splits past n_splits carry weight 0
+            const f32x4 w4 = {ws[s], ws[s], ws[s], ws[s]};  // fused as well, whatever the instantiation
+            lo = __builtin_elementwise_fma(w4, po[ks][s][0], lo);
+            hi = __builtin_elementwise_fma(w4, po[ks][s][1], hi);
         }
         bf16x8 a;
 #pragma unroll
@@ -952,10 +1068,23 @@ __global__ __launch_bounds__(512) void cross_absorb_prologue_kernel(AbsPrologueP
     }
 }
 
-// WIPA_ABS_KERNEL=1 keeps the channel-split kernel (A/B runs); default: the independent-wave kernel
+// The merge launch: the instantiation built for the call's split count (WIPA_ABS_LOOP=0: always the general NS = 4 form)
+template <int D, bool OUTP, typename... Args>
+void launch_merge(int lv, int S, dim3 grid, hipStream_t s, Args... args) {
+    constexpr int T = 64 * MergeCfg<D>::NWM;
+    const int ns = (lv == 1 || lv == 3) ? S : 4;
+    if (ns == 1) hipLaunchKernelGGL((cross_merge_proj_kernel<D, OUTP, 1>), grid, dim3(T), 0, s, args...);
+    else if (ns == 2) hipLaunchKernelGGL((cross_merge_proj_kernel<D, OUTP, 2>), grid, dim3(T), 0, s, args...);
+    else if (ns == 3) hipLaunchKernelGGL((cross_merge_proj_kernel<D, OUTP, 3>), grid, dim3(T), 0, s, args...);
+    else hipLaunchKernelGGL((cross_merge_proj_kernel<D, OUTP, 4>), grid, dim3(T), 0, s, args...);
+}
+
+// WIPA_ABS_KERNEL=1 keeps the channel-split kernel (A/B runs); default: the independent-wave kernel.  WIPA_ABS_LOOP=0 keeps that
+// kernel's loop as it was before the pipelined P x group phase (and the general merge launch): both variables are read per call.
 template <int D>
-int launch_attn(const AbsParams& p_in, int B, hipStream_t s) {
+int launch_attn(int lv, const AbsParams& p_in, int B, hipStream_t s) {
     const char* e = getenv("WIPA_ABS_KERNEL");
+    const bool pipe = lv == 1 || lv == 2;
     AbsParams p = p_in;
     p.resident_groups = wipa_cross_absorbed_resident_groups(B, D, p.Tk, p.n_splits);  // every entry point launches through here
     // d = 1024: 64 column tiles are all 256 accumulation registers and a 16-frame group is 32 KiB, so the independent-wave form fits
@@ -963,12 +1092,15 @@ int launch_attn(const AbsParams& p_in, int B, hipStream_t s) {
     // launch, 845 vs 821 ms per pass); WIPA_ABS_KERNEL=2 selects it for A/B runs
     if ((e && atoi(e) == 1) || (D > 768 && !(e && atoi(e) == 2)))
         hipLaunchKernelGGL((cross_absorbed_kernel<D>), dim3(p.n_splits, B), dim3(64 * AbsCfg<D>::NW), AbsCfg<D>::SMEM, s, p);
-    else if constexpr (D > 768)
-        hipLaunchKernelGGL((cross_absorbed_v2_kernel<D, 2>), dim3(p.n_splits, B), dim3(128), (AbsCfg2<D, 2>::SMEM), s, p);
-    else {
+    else if constexpr (D > 768) {
+        if (pipe) hipLaunchKernelGGL((cross_absorbed_v2_kernel<D, 2, true>), dim3(p.n_splits, B), dim3(128), (AbsCfg2<D, 2>::SMEM), s, p);
+        else hipLaunchKernelGGL((cross_absorbed_v2_kernel<D, 2, false>), dim3(p.n_splits, B), dim3(128), (AbsCfg2<D, 2>::SMEM), s, p);
+    } else {
         static const int waves = [] { const char* w = getenv("WIPA_ABS_WAVES"); return w ? atoi(w) : 3; }();  // A/B: 2 leaves 64 KiB of LDS and two SIMDs to other kernels
-        if (waves == 2) hipLaunchKernelGGL((cross_absorbed_v2_kernel<D, 2>), dim3(p.n_splits, B), dim3(128), (AbsCfg2<D, 2>::SMEM), s, p);
-        else hipLaunchKernelGGL((cross_absorbed_v2_kernel<D, 3>), dim3(p.n_splits, B), dim3(192), (AbsCfg2<D, 3>::SMEM), s, p);
+        if (waves == 2 && pipe) hipLaunchKernelGGL((cross_absorbed_v2_kernel<D, 2, true>), dim3(p.n_splits, B), dim3(128), (AbsCfg2<D, 2>::SMEM), s, p);
+        else if (waves == 2) hipLaunchKernelGGL((cross_absorbed_v2_kernel<D, 2, false>), dim3(p.n_splits, B), dim3(128), (AbsCfg2<D, 2>::SMEM), s, p);
+        else if (pipe) hipLaunchKernelGGL((cross_absorbed_v2_kernel<D, 3, true>), dim3(p.n_splits, B), dim3(192), (AbsCfg2<D, 3>::SMEM), s, p);
+        else hipLaunchKernelGGL((cross_absorbed_v2_kernel<D, 3, false>), dim3(p.n_splits, B), dim3(192), (AbsCfg2<D, 3>::SMEM), s, p);
     }
     return WIPA_OK;
 }
@@ -1070,11 +1202,17 @@ extern "C" int wipa_cross_absorbed_init(int d) {
                                 AbsCfg<D>::SMEM);
         if constexpr (D <= 768) {
             if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_absorbed_v2_kernel<D, 3>),
+                e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_absorbed_v2_kernel<D, 3, true>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, AbsCfg2<D, 3>::SMEM);
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_absorbed_v2_kernel<D, 3, false>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, AbsCfg2<D, 3>::SMEM);
         }
         if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_absorbed_v2_kernel<D, 2>),
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_absorbed_v2_kernel<D, 2, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, AbsCfg2<D, 2>::SMEM);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_absorbed_v2_kernel<D, 2, false>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, AbsCfg2<D, 2>::SMEM);
         return WIPA_OK;
     });
@@ -1095,7 +1233,7 @@ extern "C" int wipa_cross_absorbed_stream(const void* xa, void* scratch, size_t 
     if (rc0 != WIPA_OK) return rc0;
     const int S = wipa_cross_absorbed_splits(n_splits, Tk);
     const AbsParams p = abs_params(scratch, B, d, Tk, S, H, xa);
-    const int rc = for_width(d, [&](auto width) { return launch_attn<decltype(width)::value>(p, B, (hipStream_t)stream); });
+    const int rc = for_width(d, [&](auto width) { return launch_attn<decltype(width)::value>(wipa_cross_absorbed_loop_variant(), p, B, (hipStream_t)stream); });
     if (rc != WIPA_OK) return rc;
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;
@@ -1121,6 +1259,7 @@ extern "C" int wipa_cross_absorbed_attention(const void* q, int64_t q_row_stride
     const int S = wipa_cross_absorbed_splits(n_splits, Tk);
     const AbsParams p = abs_params(scratch, B, d, Tk, S, H, xa);
     const dim3 gq(16, (B + 15) / 16, 4), gm(H, (B + WIPA_MERGE_CL - 1) / WIPA_MERGE_CL);
+    const int lv = wipa_cross_absorbed_loop_variant();  // once per call: the streaming and the merge launch take the same variant
     const char* st_env = getenv("WIPA_ABS_STAGES");  // debugging: bit 0 absorb-q, bit 1 stream, bit 2 merge (default all)
     const int stages = st_env ? atoi(st_env) : 7;
     const int rc = for_width(d, [&](auto width) {
@@ -1129,10 +1268,10 @@ extern "C" int wipa_cross_absorbed_attention(const void* q, int64_t q_row_stride
         if (stages & 1)
             hipLaunchKernelGGL((cross_absorb_q_kernel<D>), gq, dim3(64), 0, s, (const __bf16*)q, q_row_stride, (const __bf16*)wkT,
                                const_cast<__bf16*>(p.qp), B, H, k_scale);
-        if (stages & 2) rc = launch_attn<D>(p, B, s);
+        if (stages & 2) rc = launch_attn<D>(lv, p, B, s);
         if (rc == WIPA_OK && (stages & 4))
-            hipLaunchKernelGGL((cross_merge_proj_kernel<D>), gm, dim3(64 * MergeCfg<D>::NWM), 0, s, p.part_m, p.part_l, p.part_o, S,
-                               (const __bf16*)wv, bv, (__bf16*)out, out_row_stride, B);
+            launch_merge<D, false>(lv, S, gm, s, (const float*)p.part_m, (const float*)p.part_l, (const float*)p.part_o, S, (const __bf16*)wv, bv,
+                                   (__bf16*)out, out_row_stride, B, (const __bf16*)nullptr, (const float*)nullptr, (float*)nullptr, (int64_t)0);
         return rc;
     });
     if (rc != WIPA_OK) return rc;
@@ -1187,19 +1326,20 @@ static int absorbed_block(const wipa_cross_block_desc* c, const void* wkT, const
     q.eps = c->eps; q.q_scale = c->qk_scale; q.k_scale = c->qk_scale;
     // clips per prologue workgroup: 8 (default since round 4: H x B / 8 = 96 workgroups at 64 clips; a lone decode step 1.304 vs
     // 1.338 ms, the pipelined pass unchanged) or 16 (WIPA_ABS_PROLOGUE_CLIPS=16: every MFMA row a clip, 48 workgroups)
+    const int lv = wipa_cross_absorbed_loop_variant();  // once per call: the streaming and the merge launch take the same variant
     static const int cg = [] { const char* e = getenv("WIPA_ABS_PROLOGUE_CLIPS"); return e ? atoi(e) : 8; }();
     const dim3 gp(H, cg == 8 ? (B + 7) / 8 : (B + 15) / 16), gm(H, (B + WIPA_MERGE_CL - 1) / WIPA_MERGE_CL);
     const int rc = for_width(d, [&](auto width) {
         constexpr int D = decltype(width)::value;
         if (cg == 8) hipLaunchKernelGGL((cross_absorb_prologue_kernel<D, 8>), gp, dim3(512), 0, s, q);
         else hipLaunchKernelGGL((cross_absorb_prologue_kernel<D, 16>), gp, dim3(512), 0, s, q);
-        const int rc = launch_attn<D>(p, B, s);
+        const int rc = launch_attn<D>(lv, p, B, s);
         if (rc == WIPA_OK && wo)
-            hipLaunchKernelGGL((cross_merge_proj_kernel<D, true>), gm, dim3(64 * MergeCfg<D>::NWM), 0, s, p.part_m, p.part_l, p.part_o, S,
-                               (const __bf16*)wv, bv, (__bf16*)nullptr, (int64_t)d, B, (const __bf16*)wo, bo, slabs_out, slab_stride);
+            launch_merge<D, true>(lv, S, gm, s, (const float*)p.part_m, (const float*)p.part_l, (const float*)p.part_o, S, (const __bf16*)wv, bv,
+                                  (__bf16*)nullptr, (int64_t)d, B, (const __bf16*)wo, bo, slabs_out, slab_stride);
         else if (rc == WIPA_OK)
-            hipLaunchKernelGGL((cross_merge_proj_kernel<D>), gm, dim3(64 * MergeCfg<D>::NWM), 0, s, p.part_m, p.part_l, p.part_o, S,
-                               (const __bf16*)wv, bv, (__bf16*)c->out, (int64_t)d, B);
+            launch_merge<D, false>(lv, S, gm, s, (const float*)p.part_m, (const float*)p.part_l, (const float*)p.part_o, S, (const __bf16*)wv, bv,
+                                   (__bf16*)c->out, (int64_t)d, B, (const __bf16*)nullptr, (const float*)nullptr, (float*)nullptr, (int64_t)0);
         return rc;
     });
     if (rc != WIPA_OK) return rc;

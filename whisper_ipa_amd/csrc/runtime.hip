@@ -1020,7 +1020,7 @@ extern "C" int wipa_decoder_run_rules(const wipa_model_cfg* cfg, const void* con
     WIPA_REQUIRE(s != nullptr, "wipa_decoder_run: graph capture needs a non-default stream");
     // (the streaming launch's resident_groups argument is baked into the captured step too, but needs no term here: it is a function
     // of B, the width, the frame count and dec_cross_splits -- all in the key -- and of a budget that is constant per process)
-    const int variant = cfg->dtype * 2 + t_f32_split + 4 * decode_mode(cfg, B) + 16 * cfg->dec_w_dtype + 64 * cfg->dec_cross_absorbed * (absorbed_block_fused() ? 2 : 1) + 256 * (int)tail_fused() + 512 * (int)absorbed_merge_out() + 1024 * cfg->dec_cross_splits + 8192 * (int)lean_ok;
+    const int variant = cfg->dtype * 2 + t_f32_split + 4 * decode_mode(cfg, B) + 16 * cfg->dec_w_dtype + 64 * cfg->dec_cross_absorbed * (absorbed_block_fused() ? 2 : 1) + 256 * (int)tail_fused() + 512 * (int)absorbed_merge_out() + 1024 * cfg->dec_cross_splits + 8192 * (int)lean_ok + 16384 * (cfg->dec_cross_absorbed ? wipa_cross_absorbed_loop_variant() : 0);
     auto step_graph = [&](bool lean, hipGraphExec_t* out) -> int {  // kind 0: the full step, 2: the lean one
         hipGraphExec_t exec = nullptr;
         const GraphKey key(state, (const void*)w, (const void*)mask_first, (const void*)mask_always, B, n_init, eot, variant, cfg->weights_generation,
@@ -1091,7 +1091,7 @@ extern "C" int wipa_decoder_prefill_rules(const wipa_model_cfg* cfg, const void*
     WIPA_CHECK_HIP(hipMemsetAsync(done_counter_of(st, L), 0, sizeof(int32_t), s));  // as wipa_decoder_run: the tail's counter starts at zero
     if (!use_graph || s == nullptr || !graphs_allowed()) return enqueue();
     hipGraphExec_t exec = nullptr;
-    const GraphKey key(state, (const void*)w, (const void*)mask_first, (const void*)mask_always, B, n_init, eot, cfg->dtype * 2 + t_f32_split + 4 * decode_mode(cfg, B) + 16 * cfg->dec_w_dtype + 64 * cfg->dec_cross_absorbed * (absorbed_block_fused() ? 2 : 1) + 256 * (int)tail_fused() + 512 * (int)absorbed_merge_out() + 1024 * cfg->dec_cross_splits + 8192 * (int)(!use_fused_step(cfg, B) && logits_fused(cfg, B)), cfg->weights_generation, 1,
+    const GraphKey key(state, (const void*)w, (const void*)mask_first, (const void*)mask_always, B, n_init, eot, cfg->dtype * 2 + t_f32_split + 4 * decode_mode(cfg, B) + 16 * cfg->dec_w_dtype + 64 * cfg->dec_cross_absorbed * (absorbed_block_fused() ? 2 : 1) + 256 * (int)tail_fused() + 512 * (int)absorbed_merge_out() + 1024 * cfg->dec_cross_splits + 8192 * (int)(!use_fused_step(cfg, B) && logits_fused(cfg, B)) + 16384 * (cfg->dec_cross_absorbed ? wipa_cross_absorbed_loop_variant() : 0), cfg->weights_generation, 1,
                        rules ? rules->timestamp_begin : 0, rules ? rules->no_timestamps : 0, rules ? rules->max_initial_timestamp_index : 0);
     {
         std::lock_guard<std::mutex> lk(g_graph_mu);

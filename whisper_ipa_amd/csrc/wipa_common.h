@@ -18,6 +18,8 @@ void wipa_set_error(const char* fmt, ...);
 // one-time kernel attribute setup (dynamic LDS limits); must first run OUTSIDE a stream capture
 int wipa_decode_fused_init();
 int wipa_gemm_init();
+// the absorbed cross-attention's loop variant of this call (WIPA_ABS_LOOP, cross_absorbed.hip): a term of the decode graph key
+int wipa_cross_absorbed_loop_variant();
 
 #define WIPA_CHECK_HIP(expr)                                                        \
     do {                                                                            \
