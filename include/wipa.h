@@ -445,6 +445,41 @@ int wipa_timestamp_step_embed(const float* logits, int64_t ldl, int B, int V, co
                               int eot, const wipa_decode_rules* rules, float* sum_logprobs, int32_t* not_done, const void* tok_emb,
                               int emb_dtype, const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w,
                               const float* ln_b, void* y, int y_dtype, int D, float eps, wipa_stream_t s);
+/* Temperature sampling in the greedy update (upstream's GreedyDecoder.update with temperature > 0).  On the filtered row l -- the row
+ * the greedy tails reduce: logits + mask, after rules 1-5 above when rules are given, rule 5 evaluated on the untempered row --
+ *   next ~ Categorical(softmax(l / T)),   sum_logprobs += l[next] - logsumexp(l)   (the UNTEMPERED log-softmax at the drawn column);
+ * EOT latch, not_done, prompt walk, next embedding + LayerNorm and position advance as in the greedy tails.
+ * The draw is Gumbel-max: next = argmax_c (l[c] * (1 / T) + g_c) over the alive columns, lowest column on ties, with
+ *   g_c = -log(-log(u_c)),  u_c = ((word >> 9) + 0.5) * 2^-23  (exact in f32; g in (-2.8, 16.7); logf for both logarithms),
+ * and the bits from Philox4x32-10: key = (seed_lo, seed_hi), counter = (c >> 2, p | attempt << 16, stream_lo[b], stream_hi[b]),
+ * word c & 3 of the output for column c; p = *pos_dev, the position whose logits these are, read on the device.  A row's noise
+ * depends on (seed, stream[b], attempt, p, c) only -- never on B or on the row's index -- so a row draws the same tokens in
+ * whichever batch it is decoded.  A row with no alive column keeps the greedy answer.
+ *
+ * The SAMPLING RECORD is one caller-owned DEVICE buffer of wipa_sample_record_bytes(B) bytes, 4-byte aligned:
+ *   offset  0  uint32 seed_lo          offset  8  uint32 attempt (< 65536)
+ *   offset  4  uint32 seed_hi          offset 12  float  1 / temperature
+ *   offset 16 + 8 * b  uint32 stream_lo[b], uint32 stream_hi[b]          for every row b < B
+ * The kernels read it when they RUN: the caller may rewrite it between calls (stream-ordered) and a captured step graph that
+ * holds its address serves every seed, attempt, temperature and stream assignment.  wipa_sample_record_fill writes the HOST
+ * image of a record (streams: [B][2] uint32, NULL: (b, 0)); the caller copies it to the device.  It returns WIPA_ERR_ARG for a
+ * temperature that is not above 0 or an attempt outside 0..65535; every entry point below returns WIPA_ERR_ARG for a NULL record
+ * where one is required.  V <= 65536 and positions below 65536. */
+size_t wipa_sample_record_bytes(int B);
+int wipa_sample_record_fill(void* host_record, size_t record_bytes, uint64_t seed, int attempt, float temperature,
+                            const uint32_t* streams, int B);
+/* the draw alone on any rows (no embedding), like wipa_timestamp_step; rules may be NULL (the plain filtered row); sample: required */
+int wipa_sample_step(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
+                     int32_t* tokens, int64_t ld_tok, const int32_t* pos_dev, int n_init, int eot, const wipa_decode_rules* rules,
+                     const void* sample, float* sum_logprobs, int32_t* not_done, wipa_stream_t s);
+/* wipa_timestamp_step_embed / wipa_greedy_step_embed (rules == NULL) with the draw: the tail of a sampling decode step */
+int wipa_sample_step_embed(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
+                           int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init,
+                           int eot, const wipa_decode_rules* rules, const void* sample, float* sum_logprobs, int32_t* not_done,
+                           const void* tok_emb, int emb_dtype, const float* emb_scale, const float* pos_emb, int n_ctx, float* x,
+                           const float* ln_w, const float* ln_b, void* y, int y_dtype, int D, float eps, wipa_stream_t s);
+/* a measurement aid: out[c] = g_c of row `row` of the record at position p, for c < V */
+int wipa_sample_noise(const void* sample, int row, int p, int V, float* out, wipa_stream_t s);
 /* The same row routine alone, for the token ALREADY at position p = *pos_dev: x[b] = tok_emb[tokens[b][p]] + pos_emb[p],
  * y[b] = LayerNorm(x[b]).  wipa_decoder_run launches it once before its first step. */
 int wipa_embed_layernorm(const int32_t* tokens, int64_t ld_tok, int B, const int32_t* pos_dev, const void* tok_emb, int emb_dtype,
@@ -622,6 +657,17 @@ int wipa_decoder_run_rules(const wipa_model_cfg* cfg, const void* const* weights
 int wipa_decoder_prefill_rules(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
                                int eot, const float* mask_first, const float* mask_always, int use_graph,
                                const wipa_decode_rules* rules, wipa_stream_t s);
+/* wipa_decoder_run_rules / wipa_decoder_prefill_rules at a temperature above 0: `sample` is the device sampling record
+ * (wipa_sample_record_bytes above), rules may be NULL.  The step's tail is wipa_sample_step_embed, the prompt pass ends with
+ * wipa_sample_step; sampling steps write their logits and use the row-scan tail, like steps with rules.  sample == NULL enqueues
+ * exactly what wipa_decoder_run[_rules] / wipa_decoder_prefill[_rules] enqueue.  The graph key holds the record's ADDRESS, not its
+ * contents: rewriting seed, attempt, temperature or streams replays the same graph.  wipa_dec_layout does not change. */
+int wipa_decoder_run_sample(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int n_init,
+                            int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
+                            const wipa_decode_rules* rules, const void* sample, wipa_stream_t s);
+int wipa_decoder_prefill_sample(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
+                                int eot, const float* mask_first, const float* mask_always, int use_graph,
+                                const wipa_decode_rules* rules, const void* sample, wipa_stream_t s);
 /* drop the cached step graphs that reference this state blob (call before freeing it). */
 int wipa_decoder_release(void* state);
 

@@ -111,10 +111,11 @@ def transcribe_clips(model, audio_paths: List[str], options: DecodingOptions, ba
 BASE_DECODE_MODES = ("decode", "transcribe")
 
 
-def transcribe_files(model, audio_paths: List[str], batch_size: int = 64, progress=None) -> List[str]:
+def transcribe_files(model, audio_paths: List[str], batch_size: int = 64, progress=None, seed: Optional[int] = None) -> List[str]:
     """reference :112-119 for the whole list: ``mlx_whisper.transcribe(path, language="en", word_timestamps=False)["text"]`` per
     file through whisper_ipa_amd.transcribe, ``batch_size`` files per call (their windows decode as one batch per round).  One
-    text per path, "" where the file could not be read."""
+    text per path, "" where the file could not be read.  ``seed``: run mlx_whisper.transcribe's temperature schedule on the windows
+    that fail its thresholds (None: temperature 0 only, such windows are flagged)."""
     from whisper_ipa_amd import transcribe
 
     texts = [""] * len(audio_paths)
@@ -127,7 +128,7 @@ def transcribe_files(model, audio_paths: List[str], batch_size: int = 64, progre
             except Exception as e:
                 print(f"\nError transcribing {path}: {e}")
         if clips:
-            for i, r in zip(slots, transcribe(model, clips, language="en", word_timestamps=False)):
+            for i, r in zip(slots, transcribe(model, clips, language="en", word_timestamps=False, seed=seed)):
                 texts[i] = r["text"].strip()
         if progress is not None:
             progress(min(b + batch_size, len(audio_paths)))
@@ -143,7 +144,7 @@ def transcribe_batch(model, audio_paths: List[str], n_mels: int, options: Decodi
 def evaluate_model(model_path: str, test_data_path: str, num_samples: Optional[int] = None, model_name: str = "Model",
                    is_checkpoint: bool = False, n_mels: int = 80, base_model: str = "mlx-community/whisper-small-mlx",
                    batch_size: int = 64, passes_in_flight: int = 4, ingest: str = "device", scoring: str = "device",
-                   base_decode: str = "decode") -> Dict:
+                   base_decode: str = "decode", seed: Optional[int] = None) -> Dict:
     rank, world_size = parallel.world()
     say = print if rank == 0 else (lambda *a, **k: None)
     say("=" * 70)
@@ -173,7 +174,7 @@ def evaluate_model(model_path: str, test_data_path: str, num_samples: Optional[i
     mine = test_data[lo:hi]
     say("\nTranscribing test samples...")
     if base_decode == "transcribe" and not is_checkpoint:
-        local_hyp = transcribe_files(model, [s["audio_path"] for s in mine], batch_size=batch_size,
+        local_hyp = transcribe_files(model, [s["audio_path"] for s in mine], batch_size=batch_size, seed=seed,
                                      progress=lambda n: say(f"  {n}/{len(mine)} clips on rank 0", flush=True))
     else:
         local_hyp = transcribe_clips(model, [s["audio_path"] for s in mine], options, batch_size=batch_size,
@@ -259,6 +260,10 @@ def main(argv=None) -> Dict:
                     help="the base-model leg: 'decode' = the checkpoint leg's decode(without_timestamps=True) (default, as before); "
                          "'transcribe' = whisper_ipa_amd.transcribe, the call the reference makes for it (timestamps on, timestamp "
                          "rules, segments, no-speech skip, 30 s windows)")
+    ap.add_argument("--seed", type=int, default=None,
+                    help="with --base-decode transcribe: re-decode the windows that fail the compression-ratio / log-probability "
+                         "thresholds at 0.2, 0.4, ... 1.0 as mlx_whisper.transcribe does, sampling reproducibly from this seed "
+                         "(default: temperature 0 only)")
     ap.add_argument("--results-json", type=str, default=None, help="also write both result dicts here (rank 0)")
     ap.add_argument("--allow-byte-fallback", action="store_true",
                     help="run without the Whisper vocabulary (WIPA_TIKTOKEN unset): hypotheses render ids >= 256 as <|idN|>; "
@@ -281,7 +286,7 @@ def main(argv=None) -> Dict:
         base_results = evaluate_model(args.base_model, args.test_data, num_samples, model_name="Base Whisper Model",
                                       is_checkpoint=False, n_mels=args.n_mels, base_model=args.base_model, batch_size=args.batch_size,
                                       passes_in_flight=args.passes_in_flight, ingest=args.ingest, scoring=args.scoring,
-                                      base_decode=args.base_decode)
+                                      base_decode=args.base_decode, seed=args.seed)
     trained_results = evaluate_model(args.checkpoint, args.test_data, num_samples, model_name="Trained Checkpoint",
                                      is_checkpoint=True, n_mels=args.n_mels, base_model=args.base_model, batch_size=args.batch_size,
                                      passes_in_flight=args.passes_in_flight, ingest=args.ingest, scoring=args.scoring)

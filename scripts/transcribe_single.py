@@ -38,11 +38,12 @@ def load_checkpoint_model(checkpoint_path: str, base_model: str = "mlx-community
     return model
 
 
-def transcribe_file(model, audio_path: str) -> str:
+def transcribe_file(model, audio_path: str, temperature: float = 0.0, seed=None) -> str:
     print(f"Transcribing {audio_path}...")
     audio = load_audio_batch([audio_path])  # load_audio -> pad_or_trim (reference :43-44) on the GPU: [1, 480000]
     mel = log_mel_spectrogram(audio, n_mels=model.dims.n_mels).to(torch.float32)
-    options = DecodingOptions(language="en", without_timestamps=True)  # IPA is decoded "as English"
+    # IPA is decoded "as English"; a temperature above 0 samples, reproducibly, from ``seed``
+    options = DecodingOptions(language="en", without_timestamps=True, temperature=temperature, seed=seed)
     audio_features = model.encoder(mel)
     result = decode(model, audio_features, options)
     return result[0].text.strip()
@@ -54,6 +55,8 @@ def main(argv=None):
     ap.add_argument("--audio", default="4.wav")
     ap.add_argument("--base-model", default="mlx-community/whisper-large-v3-mlx",
                     help="local directory with config.json + weights.safetensors (hub names cannot resolve offline)")
+    ap.add_argument("--temperature", type=float, default=0.0, help="above 0: sample instead of taking the arg-max (needs --seed)")
+    ap.add_argument("--seed", type=int, default=None, help="seed of the sampling draw: the same seed gives the same transcript")
     ap.add_argument("--allow-byte-fallback", action="store_true",
                     help="run without the Whisper vocabulary (WIPA_TIKTOKEN unset): ids >= 256 print as <|idN|>; synthetic weights only")
     args = ap.parse_args(argv)
@@ -61,7 +64,9 @@ def main(argv=None):
 
     require_real_vocabulary(get_tokenizer(True), args.allow_byte_fallback, "transcribing with a trained checkpoint")
     model = load_checkpoint_model(args.checkpoint, args.base_model)
-    text = transcribe_file(model, args.audio)
+    if args.temperature != 0.0 and args.seed is None:
+        ap.error("--temperature above 0 needs --seed")
+    text = transcribe_file(model, args.audio, temperature=args.temperature, seed=args.seed)
     print("\n" + "=" * 50)
     print(f"Audio: {args.audio}")
     print(f"Prediction: {text}")

@@ -159,6 +159,14 @@ SIGNATURES = {
     "wipa_timestamp_step_embed": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                           c_int, c_int, _P(DecodeRules), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
+    "wipa_sample_record_bytes": (c_size_t, [c_int]),
+    "wipa_sample_record_fill": (c_int, [c_void_p, c_size_t, C.c_uint64, c_int, c_float, c_void_p, c_int]),
+    "wipa_sample_step": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int,
+                                 _P(DecodeRules), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "wipa_sample_step_embed": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                       c_int, c_int, _P(DecodeRules), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
+    "wipa_sample_noise": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "wipa_logits_greedy_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "wipa_logits_greedy_partials_bytes": (c_size_t, [c_int]),
     "wipa_logits_greedy": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
@@ -190,6 +198,10 @@ SIGNATURES = {
                                        c_int, _P(DecodeRules), c_void_p]),
     "wipa_decoder_prefill_rules": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                            _P(DecodeRules), c_void_p]),
+    "wipa_decoder_run_sample": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                        c_int, _P(DecodeRules), c_void_p, c_void_p]),
+    "wipa_decoder_prefill_sample": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                            _P(DecodeRules), c_void_p, c_void_p]),
     "wipa_decode_cross_attn_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "wipa_decoder_release": (c_int, [c_void_p]),
     "wipa_decoder_logits_workspace_bytes": (c_size_t, [_P(ModelCfg), c_int, c_int]),

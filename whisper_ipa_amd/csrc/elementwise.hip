@@ -1,7 +1,10 @@
 // K3 LayerNorm, K8 embedding, K13 greedy step, K9 masked cross-entropy, small utilities.
 // All HBM-bound row kernels: one wave (LayerNorm) or one workgroup (vocab reductions) per
 // row, 8/16-byte vector loads, wave64 shuffle reductions, f32 math.
+#include <string.h>
+
 #include "wipa_common.h"
+#include "philox.h"
 
 namespace {
 
@@ -579,8 +582,18 @@ struct RowPick {
     float logprob;   // log_softmax of the filtered row at next (thread 0 of the workgroup only)
 };
 
-__device__ __forceinline__ RowPick rules_row_pick(const float* __restrict__ row, const float* __restrict__ mask, int V, const int32_t* __restrict__ tk,
-                                                  int p, int n_init, int eot, RulesDev r, float* s_v, int* s_i, float* s_sum) {
+// SAMPLE (temperature above 0): on the SAME filtered row l, next = argmax_c (l[c] / T + g_c) over the alive columns, lowest column on
+// ties -- the Gumbel-max form of Categorical(softmax(l / T)): a third (max, lowest column) reduction, no prefix sum, the same result
+// in any reduction order.  g_c comes from Philox4x32-10 (philox.h) with key (seed_lo, seed_hi) and counter (c >> 2, p | attempt << 16,
+// stream_lo[b], stream_hi[b]); word c & 3 belongs to column c, so one call serves one f32x4 quad of the row, and a quad with nothing
+// alive draws nothing.  Rule 5 and the log-probability stay on the UNTEMPERED row: logprob = l[next] - logsumexp(l), with the
+// log-sum-exp of the greedy branch (same sums, same order), so it is a fixed function of the row's logits.
+// RULES = false: the plain filtered row (r.tb = V: every column is on the text side, no history scan).
+// rec: the caller's sampling record (wipa.h: wipa_sample_record_bytes): u32 seed_lo, seed_hi, attempt, f32 1/T, then [lo, hi] per row.
+template <bool RULES, bool SAMPLE>
+__device__ __forceinline__ RowPick row_pick(const float* __restrict__ row, const float* __restrict__ mask, int V, const int32_t* __restrict__ tk,
+                                            int p, int n_init, int eot, RulesDev r, float* s_v, int* s_i, float* s_sum,
+                                            const uint32_t* __restrict__ rec, int b) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nq = V >> 2;
     // the row's loads go out first; the history scan below hides under them
@@ -599,21 +612,23 @@ __device__ __forceinline__ RowPick rules_row_pick(const float* __restrict__ row,
     float tailv = has_tail ? row[ti] + mask[ti] : -INFINITY;
     // history: seq = tk[n_init .. p].  Every WAVE scans all of it (at most n_ctx - n_init tokens, 7 per lane) and reduces with
     // shuffles: no LDS, no barrier, and every thread ends with the same t_idx
-    const int len = p + 1 - n_init;
-    int t_idx = -1;  // index in seq of its last timestamp token
-    for (int i = lane; i < len; i += 64) t_idx = tk[n_init + i] >= r.tb ? i : t_idx;  // ascending per lane: the last match stays
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) t_idx = max(t_idx, __shfl_xor(t_idx, o, 64));
-    const bool first = len == 0;
-    const bool last = t_idx >= 0 && t_idx == len - 1;
-    const bool pen = len < 2 || tk[p - 1] >= r.tb;
     int text_lo = 0, ts_lo = r.tb, ts_hi = V - 1;
-    if (last && pen) ts_lo = V;         // a closed pair: text next
-    if (last && !pen) text_lo = eot;    // a single timestamp: EOT or a timestamp next
-    if (t_idx >= 0) ts_lo = max(ts_lo, tk[n_init + t_idx] + ((last && !pen) ? 0 : 1));
-    if (first) {
-        text_lo = r.tb;
-        if (r.max_init >= 0) ts_hi = min(ts_hi, r.tb + r.max_init);
+    if constexpr (RULES) {
+        const int len = p + 1 - n_init;
+        int t_idx = -1;  // index in seq of its last timestamp token
+        for (int i = lane; i < len; i += 64) t_idx = tk[n_init + i] >= r.tb ? i : t_idx;  // ascending per lane: the last match stays
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) t_idx = max(t_idx, __shfl_xor(t_idx, o, 64));
+        const bool first = len == 0;
+        const bool last = t_idx >= 0 && t_idx == len - 1;
+        const bool pen = len < 2 || tk[p - 1] >= r.tb;
+        if (last && pen) ts_lo = V;         // a closed pair: text next
+        if (last && !pen) text_lo = eot;    // a single timestamp: EOT or a timestamp next
+        if (t_idx >= 0) ts_lo = max(ts_lo, tk[n_init + t_idx] + ((last && !pen) ? 0 : 1));
+        if (first) {
+            text_lo = r.tb;
+            if (r.max_init >= 0) ts_hi = min(ts_hi, r.tb + r.max_init);
+        }
     }
     auto alive = [&](int c) { return c < r.tb ? (c >= text_lo && c != r.nt) : (c >= ts_lo && c <= ts_hi); };
     MaxIdx mt{-INFINITY, 0x7fffffff}, ms{-INFINITY, 0x7fffffff};  // text side, timestamp side
@@ -683,15 +698,62 @@ __device__ __forceinline__ RowPick rules_row_pick(const float* __restrict__ row,
     // timestamp mass against the best text token: the common normaliser cancels; false when no timestamp is alive
     const float ts_mass = bs.v == -INFINITY ? -INFINITY : bs.v + logf(tot_s);
     RowPick out;
+    float top_v;  // l at the arg-max: logsumexp(l) = top_v - out.logprob
     if (ts_mass > bt.v) {  // text -inf: the row is its timestamp side
         out.next = bs.i;
         out.logprob = -logf(tot_s);
+        top_v = bs.v;
     } else {
         const MaxIdx bm = better(bt, bs);
         out.next = bm.i;
         out.logprob = -logf(tot_t * __expf(base_t - bm.v) + (bs.v == -INFINITY ? 0.f : tot_s * __expf(base_s - bm.v)));
+        top_v = bm.v;
+    }
+    if constexpr (SAMPLE) {
+        const int dead_below = ts_mass > bt.v ? r.tb : 0;  // rule 5 killed the text side
+        const float inv_t = __uint_as_float(rec[3]);
+        const uint32_t k0 = rec[0], k1 = rec[1], c1 = (uint32_t)p | (rec[2] << 16), c2 = rec[4 + 2 * b], c3 = rec[5 + 2 * b];
+        MaxIdx mk{-INFINITY, 0x7fffffff};
+        if (has_tail && ti >= dead_below && tailv > -INFINITY) {
+            const Philox4 x = philox4x32_10((uint32_t)nq, c1, c2, c3, k0, k1);
+            const uint32_t word = tid == 0 ? x.w[0] : tid == 1 ? x.w[1] : tid == 2 ? x.w[2] : x.w[3];  // has_tail: tid < 4
+            mk = MaxIdx{fmaf(tailv, inv_t, gumbel_from_word(word)), ti};
+        }
+#pragma unroll
+        for (int j = 0; j < GS_MAXQ; ++j) {
+            const int qi = tid + j * GS_THREADS;
+            bool any = false;  // padding quads and dead columns hold -inf
+#pragma unroll
+            for (int e = 0; e < 4; ++e) any = any || (4 * qi + e >= dead_below && vals[j][e] > -INFINITY);
+            if (any) {
+                const Philox4 x = philox4x32_10((uint32_t)qi, c1, c2, c3, k0, k1);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (4 * qi + e >= dead_below && vals[j][e] > -INFINITY)
+                        mk = better(mk, MaxIdx{fmaf(vals[j][e], inv_t, gumbel_from_word(x.w[e])), 4 * qi + e});
+            }
+        }
+        mk = wave_argmax(mk);
+        // s_v / s_i were last read before the barrier above the sums: every thread is past it
+        if (lane == 0) {
+            s_v[wave] = mk.v;
+            s_i[wave] = mk.i;
+        }
+        __syncthreads();
+        MaxIdx bk{s_v[0], s_i[0]};
+#pragma unroll
+        for (int w = 1; w < NW; ++w) bk = better(bk, MaxIdx{s_v[w], s_i[w]});
+        if (bk.i != 0x7fffffff) {  // a row with nothing alive keeps the greedy answer
+            out.logprob = ((row[bk.i] + mask[bk.i]) - top_v) + out.logprob;
+            out.next = bk.i;
+        }
     }
     return out;
+}
+
+__device__ __forceinline__ RowPick rules_row_pick(const float* __restrict__ row, const float* __restrict__ mask, int V, const int32_t* __restrict__ tk,
+                                                  int p, int n_init, int eot, RulesDev r, float* s_v, int* s_i, float* s_sum) {
+    return row_pick<true, false>(row, mask, V, tk, p, n_init, eot, r, s_v, s_i, s_sum, nullptr, 0);
 }
 
 // wipa_timestamp_step: wipa_greedy_step with the rules, no embedding
@@ -754,6 +816,78 @@ __global__ __launch_bounds__(GS_THREADS) void timestamp_tail_kernel(TailParams q
             *q.posd = (int64_t)(p + 1) * q.D;
         }
     }
+}
+
+// wipa_sample_step: timestamp_step_kernel with the draw (RULES = false: wipa_greedy_step with the draw)
+template <bool RULES>
+__global__ __launch_bounds__(GS_THREADS) void sample_step_kernel(const float* __restrict__ logits, int64_t ldl, int V,
+                                                                 const float* __restrict__ mask_first, const float* __restrict__ mask_always,
+                                                                 int32_t* __restrict__ tokens, int64_t ld_tok, const int32_t* __restrict__ pos_dev,
+                                                                 int n_init, int eot, RulesDev r, const uint32_t* __restrict__ rec,
+                                                                 float* __restrict__ sum_logprobs, int32_t* __restrict__ not_done) {
+    __shared__ float s_v[2 * GS_THREADS / 64];
+    __shared__ int s_i[2 * GS_THREADS / 64];
+    __shared__ float s_sum[2 * GS_THREADS / 64];
+    const int b = blockIdx.x;
+    const int p = *pos_dev;
+    if (p + 1 < n_init) return;  // prompt token already in place
+    int32_t* tk = tokens + (int64_t)b * ld_tok;
+    const RowPick pick = row_pick<RULES, true>(logits + (int64_t)b * ldl, (p + 1 == n_init) ? mask_first : mask_always, V, tk, p, n_init, eot, r,
+                                               s_v, s_i, s_sum, rec, b);
+    if (threadIdx.x == 0) {
+        const int prev = tk[p];
+        const int next = (prev == eot) ? eot : pick.next;
+        if (prev != eot) sum_logprobs[b] += pick.logprob;
+        tk[p + 1] = next;
+        if (next != eot) atomicAdd(not_done, 1);
+    }
+}
+
+// timestamp_tail_kernel with the draw: the tail of a decode step at a temperature above 0, with and without rules
+template <typename TO, bool RULES>
+__global__ __launch_bounds__(GS_THREADS) void sample_tail_kernel(TailParams q, RulesDev r, const uint32_t* __restrict__ rec) {
+    __shared__ float s_v[2 * GS_THREADS / 64];
+    __shared__ int s_i[2 * GS_THREADS / 64];
+    __shared__ float s_sum[2 * GS_THREADS / 64];
+    __shared__ float s_red[4];
+    const int b = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int p = *(volatile const int32_t*)q.pos;  // one load per thread, as in greedy_tail_kernel: the draw's counter reads it live
+    int32_t* tk = q.tokens + (int64_t)b * q.ld_tok;
+    int next;
+    if (p + 1 < q.n_init) {
+        next = tk[p + 1];
+    } else {
+        const RowPick pick = row_pick<RULES, true>(q.logits + (int64_t)b * q.ldl, (p + 1 == q.n_init) ? q.mask_first : q.mask_always, q.V, tk, p,
+                                                   q.n_init, q.eot, r, s_v, s_i, s_sum, rec, b);
+        const int prev = tk[p];
+        next = (prev == q.eot) ? q.eot : pick.next;
+        if (tid == 0) {
+            if (prev != q.eot) q.sum_logprobs[b] += pick.logprob;
+            tk[p + 1] = next;
+            if (next != q.eot) atomicAdd(q.not_done, 1);
+        }
+    }
+    row_embed_layernorm<TO>(tid, next, min(p + 1, q.n_ctx - 1), q.emb, q.emb_dtype, q.emb_scale, q.pos_emb, q.x + (int64_t)b * q.D, q.ln_w,
+                            q.ln_b, (TO*)q.y + (int64_t)b * q.D, q.D, q.eps, s_red);
+    if (tid == 0) {  // position advance by the last workgroup to arrive (see greedy_tail_kernel)
+        const int arrived = atomicAdd(q.done_counter, 1);
+        if (arrived == (int)gridDim.x - 1) {
+            *q.done_counter = 0;
+            *q.pos = p + 1;
+            *q.posd = (int64_t)(p + 1) * q.D;
+        }
+    }
+}
+
+// wipa_sample_noise: g_c of one (row, position), c < V -- the numbers the sampling tails add, for measurement
+__global__ __launch_bounds__(256) void sample_noise_kernel(const uint32_t* __restrict__ rec, int row, int p, int V, float* __restrict__ out) {
+    const int qi = blockIdx.x * 256 + threadIdx.x;
+    if (4 * qi >= V) return;
+    const Philox4 x = philox4x32_10((uint32_t)qi, (uint32_t)p | (rec[2] << 16), rec[4 + 2 * row], rec[5 + 2 * row], rec[0], rec[1]);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (4 * qi + e < V) out[4 * qi + e] = gumbel_from_word(x.w[e]);
 }
 
 __global__ void add_i32_kernel(int32_t* p, int32_t v) { *p += v; }
@@ -1063,6 +1197,100 @@ extern "C" int wipa_timestamp_step_embed(const float* logits, int64_t ldl, int B
     if (y_dtype == WIPA_F32) hipLaunchKernelGGL((timestamp_tail_kernel<float>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, q, r);
     else if (y_dtype == WIPA_BF16) hipLaunchKernelGGL((timestamp_tail_kernel<__bf16>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, q, r);
     else WIPA_REQUIRE(false, "wipa_timestamp_step_embed: bad dtype %d", y_dtype);
+    WIPA_LAUNCH_CHECK();
+    return WIPA_OK;
+}
+
+// ------------------------------------------------------------------ temperature sampling
+// the sampling record: 16 bytes of header (u32 seed_lo, seed_hi, attempt; f32 1 / temperature) and one (lo, hi) u32 pair per row
+extern "C" size_t wipa_sample_record_bytes(int B) { return B > 0 ? 16 + (size_t)B * 8 : 0; }
+
+extern "C" int wipa_sample_record_fill(void* host_record, size_t record_bytes, uint64_t seed, int attempt, float temperature,
+                                       const uint32_t* streams, int B) {
+    WIPA_REQUIRE(host_record && B > 0 && record_bytes >= wipa_sample_record_bytes(B), "wipa_sample_record_fill: null record / %zu bytes for %d rows",
+                 record_bytes, B);
+    WIPA_REQUIRE(temperature > 0.f && temperature < INFINITY, "wipa_sample_record_fill: temperature %g (sampling needs a temperature above 0)",
+                 (double)temperature);
+    WIPA_REQUIRE(attempt >= 0 && attempt < 65536, "wipa_sample_record_fill: attempt %d outside 0..65535", attempt);
+    uint32_t* r = (uint32_t*)host_record;
+    const float inv_t = 1.0f / temperature;
+    r[0] = (uint32_t)seed;
+    r[1] = (uint32_t)(seed >> 32);
+    r[2] = (uint32_t)attempt;
+    memcpy(r + 3, &inv_t, 4);
+    for (int b = 0; b < B; ++b) {
+        r[4 + 2 * b] = streams ? streams[2 * b] : (uint32_t)b;
+        r[5 + 2 * b] = streams ? streams[2 * b + 1] : 0u;
+    }
+    return WIPA_OK;
+}
+
+// rules may be NULL: the plain filtered row, every column on the text side
+static int sample_check(const char* who, const wipa_decode_rules* rules, const void* sample, const float* logits, int V, int64_t ldl,
+                        const float* mask_first, const float* mask_always, int eot, int n_ctx, RulesDev* out) {
+    WIPA_REQUIRE(sample && ((uintptr_t)sample % 4) == 0, "%s: null / unaligned sampling record", who);
+    WIPA_REQUIRE(n_ctx <= 65536, "%s: positions above 65535 do not fit the draw's counter", who);
+    if (rules) return rules_check(who, rules, logits, V, ldl, mask_first, mask_always, eot, out);
+    WIPA_REQUIRE(V > 0 && V <= 4 * GS_MAXQ * GS_THREADS && ldl % 4 == 0 && ((uintptr_t)logits % 16) == 0 && ((uintptr_t)mask_first % 16) == 0 &&
+                     ((uintptr_t)mask_always % 16) == 0, "%s: vocabulary of %d / unaligned logits or masks", who, V);
+    out->tb = V;
+    out->nt = -1;
+    out->max_init = -1;
+    return WIPA_OK;
+}
+
+extern "C" int wipa_sample_step(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
+                                int32_t* tokens, int64_t ld_tok, const int32_t* pos_dev, int n_init, int eot, const wipa_decode_rules* rules,
+                                const void* sample, float* sum_logprobs, int32_t* not_done, wipa_stream_t stream) {
+    WIPA_REQUIRE(logits && mask_first && mask_always && tokens && pos_dev && sum_logprobs && not_done && B > 0 && n_init >= 1,
+                 "wipa_sample_step: bad arguments");
+    RulesDev r;
+    const int rc = sample_check("wipa_sample_step", rules, sample, logits, V, ldl, mask_first, mask_always, eot, 0, &r);
+    if (rc != WIPA_OK) return rc;
+    if (rules)
+        hipLaunchKernelGGL((sample_step_kernel<true>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, logits, ldl, V, mask_first, mask_always,
+                           tokens, ld_tok, pos_dev, n_init, eot, r, (const uint32_t*)sample, sum_logprobs, not_done);
+    else
+        hipLaunchKernelGGL((sample_step_kernel<false>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, logits, ldl, V, mask_first, mask_always,
+                           tokens, ld_tok, pos_dev, n_init, eot, r, (const uint32_t*)sample, sum_logprobs, not_done);
+    WIPA_LAUNCH_CHECK();
+    return WIPA_OK;
+}
+
+extern "C" int wipa_sample_step_embed(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
+                                      int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter,
+                                      int n_init, int eot, const wipa_decode_rules* rules, const void* sample, float* sum_logprobs,
+                                      int32_t* not_done, const void* tok_emb, int emb_dtype, const float* emb_scale, const float* pos_emb,
+                                      int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y, int y_dtype, int D, float eps,
+                                      wipa_stream_t stream) {
+    WIPA_REQUIRE(logits && mask_first && mask_always && tokens && pos_dev && posd_dev && done_counter && sum_logprobs && not_done &&
+                     tok_emb && pos_emb && x && ln_w && ln_b && y && B > 0 && n_ctx > 0 && n_init >= 1, "wipa_sample_step_embed: bad arguments");
+    int rc = tail_params_check("wipa_sample_step_embed", logits, V, ldl, mask_first, mask_always, D, emb_dtype, emb_scale);
+    if (rc != WIPA_OK) return rc;
+    RulesDev r;
+    rc = sample_check("wipa_sample_step_embed", rules, sample, logits, V, ldl, mask_first, mask_always, eot, n_ctx, &r);
+    if (rc != WIPA_OK) return rc;
+    TailParams q = {};
+    q.logits = logits; q.ldl = ldl; q.V = V; q.mask_first = mask_first; q.mask_always = mask_always;
+    q.tokens = tokens; q.ld_tok = ld_tok; q.pos = pos_dev; q.posd = posd_dev; q.done_counter = done_counter;
+    q.n_init = n_init; q.eot = eot; q.n_ctx = n_ctx; q.sum_logprobs = sum_logprobs; q.not_done = not_done;
+    q.emb = tok_emb; q.emb_dtype = emb_dtype; q.emb_scale = emb_scale; q.pos_emb = pos_emb;
+    q.x = x; q.ln_w = ln_w; q.ln_b = ln_b; q.y = y; q.D = D; q.eps = eps;
+    const uint32_t* rec = (const uint32_t*)sample;
+    const dim3 grid(B), block(GS_THREADS);
+    hipStream_t s = (hipStream_t)stream;
+    if (y_dtype == WIPA_F32 && rules) hipLaunchKernelGGL((sample_tail_kernel<float, true>), grid, block, 0, s, q, r, rec);
+    else if (y_dtype == WIPA_F32) hipLaunchKernelGGL((sample_tail_kernel<float, false>), grid, block, 0, s, q, r, rec);
+    else if (y_dtype == WIPA_BF16 && rules) hipLaunchKernelGGL((sample_tail_kernel<__bf16, true>), grid, block, 0, s, q, r, rec);
+    else if (y_dtype == WIPA_BF16) hipLaunchKernelGGL((sample_tail_kernel<__bf16, false>), grid, block, 0, s, q, r, rec);
+    else WIPA_REQUIRE(false, "wipa_sample_step_embed: bad dtype %d", y_dtype);
+    WIPA_LAUNCH_CHECK();
+    return WIPA_OK;
+}
+
+extern "C" int wipa_sample_noise(const void* sample, int row, int p, int V, float* out, wipa_stream_t stream) {
+    WIPA_REQUIRE(sample && ((uintptr_t)sample % 4) == 0 && out && row >= 0 && p >= 0 && p < 65536 && V > 0, "wipa_sample_noise: bad arguments");
+    hipLaunchKernelGGL(sample_noise_kernel, dim3(((V + 3) / 4 + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)sample, row, p, V, out);
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;
 }

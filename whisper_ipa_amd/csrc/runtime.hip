@@ -411,10 +411,13 @@ thread_local bool t_lean_logits = false;
 // the step ends in wipa_timestamp_step_embed on the written logits: the per-wave partials cannot carry rules that depend on the
 // row's own history, so logits_fused() is off and no step of the call is lean.
 thread_local const wipa_decode_rules* t_rules = nullptr;
+// The sampling record of the call in progress (wipa_decoder_run_sample / _prefill_sample; NULL: temperature 0).  A sampling step
+// ends in wipa_sample_step_embed on the written logits, like a step with rules: the draw needs every alive column of the row.
+thread_local const void* t_sample = nullptr;
 bool logits_fused(const wipa_model_cfg* cfg, int B) {
     const char* e = getenv("WIPA_LOGITS_FUSED");  // read per call like the other step variants: part of the graph key
     const bool on = !(e && atoi(e) == 0);
-    return on && !t_rules && tail_fused() && cfg->dec_w_dtype == 0 && wipa_logits_greedy_supported(B, cfg->n_vocab, cfg->n_text_state, cfg->dtype);
+    return on && !t_rules && !t_sample && tail_fused() && cfg->dec_w_dtype == 0 && wipa_logits_greedy_supported(B, cfg->n_vocab, cfg->n_text_state, cfg->dtype);
 }
 int32_t* done_counter_of(char* st, const wipa_dec_layout& L) { return (int32_t*)(st + L.pos + 64); }  // zeroed with pos by wipa_decoder_begin
 
@@ -578,6 +581,13 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
     if (tail) {
         // greedy update + embedding of the chosen token + first LayerNorm of the NEXT position + position advance: one launch
         const void* const* lw0 = w + WIPA_DEC_GLOBAL;
+        if (t_sample) {
+            RT_CALL(wipa_sample_step_embed(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, posd,
+                                           done_counter_of(st, L), n_init, eot, t_rules, t_sample, (float*)(st + L.sum_logprobs),
+                                           (int32_t*)(st + L.not_done), w[0], emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], nctx, x_first,
+                                           (const float*)lw0[0], (const float*)lw0[1], ln, dt, d, 1e-5f, stream));
+            return WIPA_OK;
+        }
         if (t_rules) {
             RT_CALL(wipa_timestamp_step_embed(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, posd,
                                               done_counter_of(st, L), n_init, eot, t_rules, (float*)(st + L.sum_logprobs),
@@ -591,7 +601,7 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
                                        (const float*)lw0[1], ln, dt, d, 1e-5f, stream));
         return WIPA_OK;
     }
-    WIPA_REQUIRE(!t_rules, "decode step: the timestamp rules need the fused tail (WIPA_DECODE_TAIL=0 is set)");
+    WIPA_REQUIRE(!t_rules && !t_sample, "decode step: the timestamp rules and sampling need the fused tail (WIPA_DECODE_TAIL=0 is set)");
     RT_CALL(wipa_greedy_step(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, n_init,
                              eot, (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), stream));
     hipLaunchKernelGGL(advance_pos_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pos, posd, d);
@@ -606,7 +616,7 @@ int enqueue_step_fused(const wipa_model_cfg* cfg, const void* const* w, char* st
     const int dt = cfg->dtype;
     const size_t e = wipa_dtype_size(dt);
     const int d = cfg->n_text_state, H = cfg->n_text_head, nctx = cfg->n_text_ctx, Ta = cfg->n_audio_ctx;
-    WIPA_REQUIRE(!t_rules, "decode step: the timestamp rules need the fused tail (WIPA_DECODE_FUSED=1 is set)");
+    WIPA_REQUIRE(!t_rules && !t_sample, "decode step: the timestamp rules and sampling need the fused tail (WIPA_DECODE_FUSED=1 is set)");
     const DecScratch S = dec_scratch(cfg, B);
     char* sc = st + L.scratch;
     float* xa = (float*)(sc + S.x);
@@ -800,7 +810,10 @@ int enqueue_prefill(const wipa_model_cfg* cfg, const void* const* w, char* st, c
     RT_CALL(gemm(ln + (size_t)(P - 1) * d * e, (int64_t)P * d, w[0], d, logits, L.ld_logits, B, cfg->n_vocab, d, dt, WIPA_F32, nullptr, 0,
                  nullptr, stream));
     hipLaunchKernelGGL(set_pos_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pos, posd, P - 1, d);
-    if (t_rules)  // the first sampled token: rule 4 (timestamps only, capped at max_initial_timestamp_index)
+    if (t_sample)  // the first sampled token is a draw too (with rule 4 under rules)
+        RT_CALL(wipa_sample_step(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, n_init, eot, t_rules, t_sample,
+                                 (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), stream));
+    else if (t_rules)  // the first sampled token: rule 4 (timestamps only, capped at max_initial_timestamp_index)
         RT_CALL(wipa_timestamp_step(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, n_init, eot, t_rules,
                                     (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), stream));
     else
@@ -863,12 +876,22 @@ int state_fits(const char* who, const wipa_dec_layout& L, size_t state_bytes) {
 // The key carries cfg->weights_generation: the host address of a weight table can be reused by a NEW table after the old
 // one was freed, so the address alone does not identify the device pointers baked into a captured graph.
 // The timestamp rules are baked into the captured tail's arguments: three more terms (timestamp_begin = 0: no rules).
-typedef std::tuple<const void*, const void*, const void*, const void*, int, int, int, int, int, int, int, int, int> GraphKey;  // ..., generation, kind: 0 step, 1 prefill, 2 lean step (no logit stores), rules
+// The sampling record enters with its ADDRESS (NULL: temperature 0): seed, attempt, temperature and streams are read from it by
+// the replayed tail, so a new seed or temperature replays the same graph.
+typedef std::tuple<const void*, const void*, const void*, const void*, int, int, int, int, int, int, int, int, int, const void*> GraphKey;  // ..., generation, kind: 0 step, 1 prefill, 2 lean step (no logit stores), rules, sampling record
 // the rules of a call, for its scope: set on entry, cleared on every way out
 struct RulesScope {
-    explicit RulesScope(const wipa_decode_rules* r) { t_rules = r; }
-    ~RulesScope() { t_rules = nullptr; }
+    explicit RulesScope(const wipa_decode_rules* r, const void* sample = nullptr) { t_rules = r; t_sample = sample; }
+    ~RulesScope() { t_rules = nullptr; t_sample = nullptr; }
 };
+// sampling lives in the fused step tail, like the rules: refused before anything is enqueued where the step cannot carry it
+int sample_servable(const char* who, const wipa_model_cfg* cfg, int B, const void* sample) {
+    if (!sample) return WIPA_OK;
+    WIPA_REQUIRE(tail_fused() && !use_fused_step(cfg, B),
+                 "%s: sampling lives in the fused step tail; WIPA_DECODE_TAIL=0 / WIPA_DECODE_FUSED=1 cannot serve it", who);
+    WIPA_REQUIRE(cfg->n_vocab <= 65536 && cfg->n_text_ctx <= 65536, "%s: need n_vocab and n_text_ctx <= 65536 (n_vocab=%d)", who, cfg->n_vocab);
+    return WIPA_OK;
+}
 // a configuration whose steps cannot carry the rules is refused before anything is enqueued: never decoded without them
 int rules_servable(const char* who, const wipa_model_cfg* cfg, int B, int eot, const wipa_decode_rules* r) {
     if (!r) return WIPA_OK;
@@ -985,11 +1008,18 @@ extern "C" int wipa_decoder_run(const wipa_model_cfg* cfg, const void* const* w,
 extern "C" int wipa_decoder_run_rules(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
                                       int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
                                       const wipa_decode_rules* rules, wipa_stream_t stream) {
+    return wipa_decoder_run_sample(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, n_steps, use_graph, rules, nullptr, stream);
+}
+
+extern "C" int wipa_decoder_run_sample(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
+                                       int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
+                                       const wipa_decode_rules* rules, const void* sample, wipa_stream_t stream) {
     RT_CALL(cfg_check(cfg));
     SplitScope split_scope(cfg);
     WIPA_REQUIRE(w && state && mask_first && mask_always && B > 0 && n_steps >= 0, "wipa_decoder_run: bad arguments");
     RT_CALL(rules_servable("wipa_decoder_run_rules", cfg, B, eot, rules));
-    RulesScope rules_scope(rules);
+    RT_CALL(sample_servable("wipa_decoder_run_sample", cfg, B, sample));
+    RulesScope rules_scope(rules, sample);
     W8Scope w8_scope(cfg, w);
     const wipa_dec_layout L = dec_layout(cfg, B);
     RT_CALL(state_fits("wipa_decoder_run", L, state_bytes));
@@ -1025,7 +1055,7 @@ extern "C" int wipa_decoder_run_rules(const wipa_model_cfg* cfg, const void* con
         hipGraphExec_t exec = nullptr;
         const GraphKey key(state, (const void*)w, (const void*)mask_first, (const void*)mask_always, B, n_init, eot, variant, cfg->weights_generation,
                            lean ? 2 : 0, rules ? rules->timestamp_begin : 0, rules ? rules->no_timestamps : 0,
-                           rules ? rules->max_initial_timestamp_index : 0);
+                           rules ? rules->max_initial_timestamp_index : 0, sample);
         {
             std::lock_guard<std::mutex> lk(g_graph_mu);
             auto it = g_graphs.find(key);
@@ -1069,11 +1099,18 @@ extern "C" int wipa_decoder_prefill(const wipa_model_cfg* cfg, const void* const
 extern "C" int wipa_decoder_prefill_rules(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
                                           int n_init, int eot, const float* mask_first, const float* mask_always, int use_graph,
                                           const wipa_decode_rules* rules, wipa_stream_t stream) {
+    return wipa_decoder_prefill_sample(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, use_graph, rules, nullptr, stream);
+}
+
+extern "C" int wipa_decoder_prefill_sample(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
+                                           int n_init, int eot, const float* mask_first, const float* mask_always, int use_graph,
+                                           const wipa_decode_rules* rules, const void* sample, wipa_stream_t stream) {
     RT_CALL(cfg_check(cfg));
     SplitScope split_scope(cfg);
     WIPA_REQUIRE(w && state && mask_first && mask_always && B > 0, "wipa_decoder_prefill: bad arguments");
     RT_CALL(rules_servable("wipa_decoder_prefill_rules", cfg, B, eot, rules));
-    RulesScope rules_scope(rules);
+    RT_CALL(sample_servable("wipa_decoder_prefill_sample", cfg, B, sample));
+    RulesScope rules_scope(rules, sample);
     WIPA_REQUIRE(n_init >= 1 && n_init <= MAX_PROMPT, "wipa_decoder_prefill: 1..%d prompt tokens (got %d)", MAX_PROMPT, n_init);
     W8Scope w8_scope(cfg, w);
     const wipa_dec_layout L = dec_layout(cfg, B);
@@ -1092,7 +1129,7 @@ extern "C" int wipa_decoder_prefill_rules(const wipa_model_cfg* cfg, const void*
     if (!use_graph || s == nullptr || !graphs_allowed()) return enqueue();
     hipGraphExec_t exec = nullptr;
     const GraphKey key(state, (const void*)w, (const void*)mask_first, (const void*)mask_always, B, n_init, eot, cfg->dtype * 2 + t_f32_split + 4 * decode_mode(cfg, B) + 16 * cfg->dec_w_dtype + 64 * cfg->dec_cross_absorbed * (absorbed_block_fused() ? 2 : 1) + 256 * (int)tail_fused() + 512 * (int)absorbed_merge_out() + 1024 * cfg->dec_cross_splits + 8192 * (int)(!use_fused_step(cfg, B) && logits_fused(cfg, B)) + 16384 * (cfg->dec_cross_absorbed ? wipa_cross_absorbed_loop_variant() : 0), cfg->weights_generation, 1,
-                       rules ? rules->timestamp_begin : 0, rules ? rules->no_timestamps : 0, rules ? rules->max_initial_timestamp_index : 0);
+                       rules ? rules->timestamp_begin : 0, rules ? rules->no_timestamps : 0, rules ? rules->max_initial_timestamp_index : 0, sample);
     {
         std::lock_guard<std::mutex> lk(g_graph_mu);
         auto it = g_graphs.find(key);

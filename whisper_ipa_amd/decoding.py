@@ -1,4 +1,4 @@
-"""KV-cached greedy decoding with the surface of ``mlx_whisper.decoding`` used by the
+"""KV-cached greedy and temperature-sampling decoding with the surface of ``mlx_whisper.decoding`` used by the
 reference: ``DecodingOptions``, ``DecodingResult``, ``decode(model, mel_or_features, options)``
 (scripts/transcribe_single.py:49-56; scripts/train_whisper_ipa.py:338-362;
 scripts/evaluate_model.py:170-201).
@@ -6,6 +6,11 @@ scripts/evaluate_model.py:170-201).
 The whole loop runs on the GPU: one decoder step is captured into a hipGraph by
 csrc/runtime.hip and replayed; token ids, EOT latches and log-prob sums stay in device
 memory; the host only looks at the last token column every few steps to stop early.
+
+``temperature > 0`` (upstream's GreedyDecoder.update with a Categorical draw) runs when ``DecodingOptions.seed`` is given: the draw
+is a Gumbel-max over counter-based Philox noise in the step's tail (csrc/elementwise.hip: row_pick<.., SAMPLE>), a pure function of
+(seed, the row's stream, attempt, position, column) -- reproducible, and independent of the batch a row is decoded in.  Seed,
+attempt, 1 / T and the streams live in a small device record the replayed step graph reads; nothing of them is baked into it.
 """
 from __future__ import annotations
 
@@ -41,6 +46,9 @@ class DecodingOptions:
     without_timestamps: bool = False
     max_initial_timestamp: Optional[float] = 1.0
     fp16: bool = True
+    seed: Optional[int] = None          # temperature > 0 needs one: sampling is opt-in and reproducible
+    sample_streams: Optional[Sequence] = None  # per-row (lo, hi) Philox streams; default (row, 0)
+    sample_attempt: int = 0             # which retry of the row this is (transcribe's fallback schedule index)
 
 
 @dataclass
@@ -97,6 +105,23 @@ class DecoderState:
     def logits(self) -> torch.Tensor:
         lay = self.layout
         return self._view(lay.logits, self.B * lay.ld_logits * 4, torch.float32).view(self.B, lay.ld_logits)[:, : self.model.dims.n_vocab]
+
+    def sample_record(self, sample: "Sampling") -> torch.Tensor:
+        """the device sampling record of this state (include/wipa.h), rewritten in stream order with ``sample``'s values.  ONE buffer
+        per state: the step graph is keyed on its address, so a new seed / temperature / attempt replays the captured graph."""
+        L = _lib.lib()
+        nbytes = int(L.wipa_sample_record_bytes(self.B))
+        streams = sample.streams if sample.streams is not None else [(b, 0) for b in range(self.B)]
+        if len(streams) != self.B:
+            raise ValueError(f"sample_streams: {len(streams)} streams for {self.B} rows")
+        flat = (C.c_uint32 * (2 * self.B))(*[int(v) & 0xFFFFFFFF for pair in streams for v in pair])
+        host = np.zeros(nbytes, dtype=np.uint8)
+        _lib.check(L.wipa_sample_record_fill(host.ctypes.data, nbytes, int(sample.seed) & 0xFFFFFFFFFFFFFFFF, int(sample.attempt),
+                                             float(sample.temperature), flat, self.B), "wipa_sample_record_fill")
+        if getattr(self, "_sample_rec", None) is None:
+            self._sample_rec = torch.empty(nbytes, dtype=torch.uint8, device=self.blob.device)
+        self._sample_rec.copy_(torch.from_numpy(host))  # on the caller's library stream: after every step already enqueued
+        return self._sample_rec
 
     def release(self):
         _lib.lib().wipa_decoder_release(ptr(self.blob))
@@ -156,6 +181,15 @@ def _mask(model, ids: Sequence[int]) -> torch.Tensor:
 
 
 @dataclass
+class Sampling:
+    """what a sampling decode needs besides the logits (DecodingOptions.seed / temperature / sample_streams / sample_attempt)"""
+    seed: int
+    temperature: float
+    streams: Optional[Sequence] = None  # per-row (lo, hi); None: (row, 0)
+    attempt: int = 0
+
+
+@dataclass
 class GreedyHandle:
     state: "DecoderState"
     stream: torch.cuda.Stream
@@ -176,18 +210,25 @@ def timestamp_rules(tok: Tokenizer, max_initial_timestamp: Optional[float] = 1.0
     return _lib.DecodeRules(int(tok.timestamp_begin), int(tok.no_timestamps), index)
 
 
-def _dec_run(L, pk, st, B, n_init, eot, m_first, m_always, n, use_graph, rules, s):
-    """wipa_decoder_run, or wipa_decoder_run_rules when the greedy update carries the timestamp rules"""
+def _dec_run(L, pk, st, B, n_init, eot, m_first, m_always, n, use_graph, rules, s, sample_rec=None):
+    """wipa_decoder_run, or wipa_decoder_run_rules when the greedy update carries the timestamp rules; wipa_decoder_run_sample
+    (rules or not) when ``sample_rec``, the state's device sampling record, is given"""
     args = (C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, n_init, eot, ptr(m_first), ptr(m_always), n, int(use_graph))
-    if rules is None:
+    if sample_rec is not None:
+        _lib.check(L.wipa_decoder_run_sample(*args, C.byref(rules) if rules is not None else None, ptr(sample_rec), sptr(s)),
+                   "wipa_decoder_run_sample")
+    elif rules is None:
         _lib.check(L.wipa_decoder_run(*args, sptr(s)), "wipa_decoder_run")
     else:
         _lib.check(L.wipa_decoder_run_rules(*args, C.byref(rules), sptr(s)), "wipa_decoder_run_rules")
 
 
-def _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s):
+def _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s, sample_rec=None):
     args = (C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, n_init, eot, ptr(m_first), ptr(m_always), int(use_graph))
-    if rules is None:
+    if sample_rec is not None:
+        _lib.check(L.wipa_decoder_prefill_sample(*args, C.byref(rules) if rules is not None else None, ptr(sample_rec), sptr(s)),
+                   "wipa_decoder_prefill_sample")
+    elif rules is None:
         _lib.check(L.wipa_decoder_prefill(*args, sptr(s)), "wipa_decoder_prefill")
     else:
         _lib.check(L.wipa_decoder_prefill_rules(*args, C.byref(rules), sptr(s)), "wipa_decoder_prefill_rules")
@@ -232,8 +273,9 @@ def greedy_collect(h: GreedyHandle) -> GreedyTokens:
 
 def greedy_decode_tokens(model, audio_features: torch.Tensor, initial_tokens: Sequence[int], suppress_always: Sequence[int],
                          suppress_first: Sequence[int], eot: int, max_new_tokens: Optional[int] = None,
-                         stop_on_eot: bool = True, use_graph: bool = True, check_every: int = 8, rules=None) -> GreedyTokens:
-    """DecodingTask._main_loop for temperature 0, n_group 1 (see module docstring).
+                         stop_on_eot: bool = True, use_graph: bool = True, check_every: int = 8, rules=None,
+                         sample: Optional[Sampling] = None) -> GreedyTokens:
+    """DecodingTask._main_loop for n_group 1 (see module docstring): temperature 0, or a Categorical draw per step with ``sample``.
     ``audio_features`` [B, 1500, d] in the model dtype.  ``rules`` (``timestamp_rules``): ApplyTimestampRules in every greedy
     update, on the device; ``initial_tokens`` is then the prompt without <|notimestamps|>."""
     L = _lib.lib()
@@ -254,14 +296,15 @@ def greedy_decode_tokens(model, audio_features: torch.Tensor, initial_tokens: Se
         _lib.check(L.wipa_decoder_set_audio(C.byref(pk["cfg"]), pk["dec_tab"], ptr(feats), ptr(st.blob), st.blob.numel(), B, sptr(s)),
                    "wipa_decoder_set_audio")
         _lib.check(L.wipa_decoder_begin(C.byref(pk["cfg"]), ptr(st.blob), st.blob.numel(), B, init, n_init, sptr(s)), "wipa_decoder_begin")
+        rec = st.sample_record(sample) if sample is not None else None
         if _use_prefill(n_init, total):
-            _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s)
+            _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s, rec)
             done_steps = n_init
         while done_steps < total:
             n = min(check_every if stop_on_eot else total, total - done_steps)
             if done_steps == 0:
                 n = min(total, n + n_init - 1)
-            _dec_run(L, pk, st, B, n_init, eot, m_first, m_always, n, use_graph, rules, s)
+            _dec_run(L, pk, st, B, n_init, eot, m_first, m_always, n, use_graph, rules, s, rec)
             done_steps += n
             if stop_on_eot and done_steps >= n_init:
                 last = st.tokens[:, done_steps].cpu()  # synchronises the library stream
@@ -367,9 +410,14 @@ def _suppress_lists(options: DecodingOptions, tok: Tokenizer):
 
 
 def _refuse_unsupported(options: DecodingOptions) -> None:
-    if options.beam_size or (options.best_of or 1) > 1 or options.temperature != 0.0:
-        raise NotImplementedError("temperature above 0, best_of and beam_size are not implemented: the reference only ever runs greedy "
-                                  "decode (SURVEY.md section 0)")
+    if options.beam_size or (options.best_of or 1) > 1:
+        raise NotImplementedError("best_of and beam_size are not implemented: the reference only ever runs greedy decode and "
+                                  "mlx_whisper.transcribe's temperature schedule (SURVEY.md section 0)")
+    if options.temperature != 0.0 and options.seed is None:
+        raise NotImplementedError("temperature above 0 needs DecodingOptions.seed: sampling is opt-in and reproducible by construction "
+                                  "(temperature without a seed is not implemented)")
+    if options.temperature < 0.0:
+        raise ValueError(f"temperature must be >= 0, got {options.temperature}")
     if not options.without_timestamps and (options.prompt is not None or options.prefix is not None):
         raise NotImplementedError("prompt / prefix conditioning is not implemented on the timestamp path")
 
@@ -418,13 +466,22 @@ def decode(model, mel: torch.Tensor, options: DecodingOptions = DecodingOptions(
         no_speech = [float(v) for v in no_speech_probs(model, feats, tok)]
     always, first = _suppress_lists(options, tok)
     sample_len = options.sample_len or d.n_text_ctx // 2
+    # temperature 0 with a seed is the greedy path, bit for bit; above 0 every row draws from its own stream, whichever language
+    # group it lands in
+    streams = None
+    if options.temperature != 0.0:
+        streams = [(int(a), int(b)) for a, b in options.sample_streams] if options.sample_streams is not None else [(i, 0) for i in range(B)]
+        if len(streams) != B:
+            raise ValueError(f"sample_streams: {len(streams)} streams for {B} rows")
     results: List[Optional[DecodingResult]] = [None] * B
     for lang in sorted(set(languages)):
         rows = [i for i, l in enumerate(languages) if l == lang]
         init = list(initial)
         init[1] = tok.to_language_token(lang)
         sub = feats[rows] if len(rows) != B else feats
-        g = greedy_decode_tokens(model, sub, init, always, first, tok.eot, max_new_tokens=sample_len, rules=rules)
+        sample = None if streams is None else Sampling(int(options.seed), float(options.temperature), [streams[i] for i in rows],
+                                                       int(options.sample_attempt))
+        g = greedy_decode_tokens(model, sub, init, always, first, tok.eot, max_new_tokens=sample_len, rules=rules, sample=sample)
         for j, i in enumerate(rows):
             row = g.tokens[j, len(init):].tolist()
             if tok.eot in row:

@@ -184,6 +184,9 @@ class TranscribePipeline:
                  cross_splits: Optional[int] = None, use_graph: bool = True, decode_group: int = 1):
         options = options or DecodingOptions(language="en", without_timestamps=True)
         _refuse_unsupported(options)
+        if options.temperature != 0.0:
+            raise NotImplementedError("temperature above 0 is not implemented in transcribe_batches: several passes in flight stay greedy-only "
+                                      "(decode() samples when a seed is given)")
         if passes_in_flight < 1:
             raise _lib.WipaError(f"passes_in_flight must be >= 1, got {passes_in_flight}")
         if decode_group < 1:

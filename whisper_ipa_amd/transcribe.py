@@ -10,8 +10,13 @@ What differs from upstream, on purpose:
     batch belong to different files at different seeks); upstream transcribes one file at a time;
   * each window's log-mel is computed from the window's own samples (``pad_or_trim`` + the existing kernel), so the 8 dB floor
     under the maximum is per window; upstream computes one log-mel of the whole file.  A single-window file is unaffected;
-  * only temperature 0 runs.  Where ``compression_ratio_threshold`` / ``logprob_threshold`` would have made upstream retry at a
-    higher temperature, the window's segments carry ``needs_fallback=True`` and one warning is printed per call.
+  * the temperature fallback is keyed on ``seed``.  With ``seed=None`` only temperature 0 runs: where
+    ``compression_ratio_threshold`` / ``logprob_threshold`` would have made upstream retry at a higher temperature, the window's
+    segments carry ``needs_fallback=True`` and one warning is printed per call.  With a seed the failing windows of a round are
+    decoded again, as ONE sub-batch per temperature of the schedule, from the encoder features the first decode left (no second
+    log-mel, no second encoder pass), until they pass or the schedule ends (the last attempt is kept, as upstream does).  The draw
+    is a function of (seed, (seek, file index), index in the schedule, position, column): a window samples the same tokens
+    whichever rows it is retried with.  Upstream draws from a global generator instead; ``best_of`` is not implemented.
 """
 from __future__ import annotations
 
@@ -102,7 +107,35 @@ def _model_decoder(model, decode_options: dict) -> Callable:
                 out[i] = r
         return out
 
+    def retry(results, languages: List[str], *, temperature: float, attempt: int, streams, seed: int):
+        """the default ``fallback_fn``: the rows' encoder features (``DecodingResult.audio_features``) decoded again at
+        ``temperature``, each row on its own stream"""
+        out = [None] * len(results)
+        feats = torch.stack([r.audio_features for r in results])
+        for lang in sorted(set(languages)):
+            rows = [i for i, l in enumerate(languages) if l == lang]
+            opts = DecodingOptions(**{**decode_options, "language": lang, "without_timestamps": False, "temperature": float(temperature),
+                                      "seed": int(seed), "sample_streams": [streams[i] for i in rows], "sample_attempt": int(attempt)})
+            res = decode(model, feats[rows] if len(rows) != len(languages) else feats, opts)
+            for i, r in zip(rows, res):
+                out[i] = r
+        return out
+
+    run.retry = retry
     return run
+
+
+def _needs_fallback(res, compression_ratio_threshold, logprob_threshold, no_speech_threshold) -> bool:
+    """upstream's decode_with_fallback predicate on one decoded window"""
+    needs_fallback = False
+    if compression_ratio_threshold is not None and res.compression_ratio > compression_ratio_threshold:
+        needs_fallback = True  # too repetitive
+    if logprob_threshold is not None and res.avg_logprob < logprob_threshold:
+        needs_fallback = True  # average log-probability too low
+    if no_speech_threshold is not None and res.no_speech_prob > no_speech_threshold and logprob_threshold is not None \
+            and res.avg_logprob < logprob_threshold:
+        needs_fallback = False  # silence
+    return needs_fallback
 
 
 def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Union[float, Tuple[float, ...]] = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
@@ -110,13 +143,17 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
                no_speech_threshold: Optional[float] = 0.6, condition_on_previous_text: bool = False,
                initial_prompt: Optional[str] = None, word_timestamps: bool = False, clip_timestamps=None,
                hallucination_silence_threshold: Optional[float] = None, language: Optional[str] = None, decode_fn: Optional[Callable] = None,
-               tokenizer=None, **decode_options):
+               tokenizer=None, seed: Optional[int] = None, fallback_fn: Optional[Callable] = None, **decode_options):
     """``audio``: a path, a 16 kHz mono float array, or a list of them.  Returns {"text", "segments", "language"} (a list of
     them for a list) with mlx_whisper's segment keys (``SEGMENT_KEYS``; plus ``needs_fallback`` where upstream would have
     retried).  ``condition_on_previous_text`` defaults to False here: True is refused, like every option this path does not
     serve.  ``decode_fn(windows [n, 480000] f32, languages [n])`` -> objects with tokens / avg_logprob / no_speech_prob /
     compression_ratio / temperature / language replaces the model's decode (tests; ``tokenizer`` is then required when
-    ``model`` is None)."""
+    ``model`` is None).  ``seed``: run the temperature schedule (module docstring); segments then carry the temperature that
+    produced them, and neither ``needs_fallback`` nor the warning appears where a retry ran.  ``fallback_fn(results, languages,
+    temperature=, attempt=, streams=, seed=)`` -> new results for those rows replaces the model's retry; with a custom ``decode_fn``
+    and no ``fallback_fn`` a seed changes nothing.  ``streams[j]`` = (seek in mel frames, file index), ``attempt`` = index in the
+    schedule."""
     _refuse(condition_on_previous_text, initial_prompt, word_timestamps, clip_timestamps, hallucination_silence_threshold, temperature,
             decode_options)
     single = not isinstance(audio, (list, tuple))
@@ -136,7 +173,12 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
 
         tokenizer = get_tokenizer(model.is_multilingual, num_languages=model.num_languages, language=language or "en", task="transcribe")
     tok, tb = tokenizer, int(tokenizer.timestamp_begin)
-    decode_fn = decode_fn or _model_decoder(model, decode_options)
+    temps = (float(temperature),) if isinstance(temperature, (int, float)) else tuple(float(t) for t in temperature)
+    if decode_fn is None:
+        decode_fn = _model_decoder(model, decode_options)
+        fallback_fn = fallback_fn or decode_fn.retry
+    if seed is None:
+        fallback_fn = None  # as ever: the flag and the warning
 
     n = len(clips)
     content_frames = [len(a) // HOP_LENGTH for a in clips]
@@ -156,8 +198,22 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
             s0 = seek[i] * HOP_LENGTH
             chunk = clips[i][s0:s0 + size * HOP_LENGTH]
             windows[r, :len(chunk)] = chunk  # pad_or_trim of the window's own samples
-        results = decode_fn(windows, [languages[i] for i in live])
-        for i, size, res in zip(live, sizes, results):
+        results = list(decode_fn(windows, [languages[i] for i in live]))
+        retried = set()  # rows of this round that went through the schedule
+        if fallback_fn is not None:
+            thresholds = (compression_ratio_threshold, logprob_threshold, no_speech_threshold)
+            failing = [r for r in range(len(live)) if _needs_fallback(results[r], *thresholds)]
+            for attempt in range(1, len(temps)):
+                if not failing:
+                    break
+                # the failing rows of the round as ONE sub-batch; the language is the file's, or what this window's first decode detected
+                again = fallback_fn([results[r] for r in failing], [languages[live[r]] or results[r].language for r in failing],
+                                    temperature=temps[attempt], attempt=attempt, streams=[(seek[live[r]], live[r]) for r in failing], seed=seed)
+                for r, res in zip(failing, again):
+                    results[r] = res
+                retried.update(failing)
+                failing = [r for r in failing if _needs_fallback(results[r], *thresholds)]
+        for row, (i, size, res) in enumerate(zip(live, sizes, results)):
             if languages[i] is None:
                 languages[i] = res.language  # detected on the file's first window, kept for the rest
             time_offset = seek[i] * HOP_LENGTH / SAMPLE_RATE
@@ -169,14 +225,7 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
                 if skip:
                     seek[i] += size
                     continue
-            needs_fallback = False
-            if compression_ratio_threshold is not None and res.compression_ratio > compression_ratio_threshold:
-                needs_fallback = True  # too repetitive
-            if logprob_threshold is not None and res.avg_logprob < logprob_threshold:
-                needs_fallback = True  # average log-probability too low
-            if no_speech_threshold is not None and res.no_speech_prob > no_speech_threshold and logprob_threshold is not None \
-                    and res.avg_logprob < logprob_threshold:
-                needs_fallback = False  # silence
+            needs_fallback = row not in retried and _needs_fallback(res, compression_ratio_threshold, logprob_threshold, no_speech_threshold)
             if needs_fallback and not warned:
                 warnings.warn("whisper_ipa_amd.transcribe: a window failed compression_ratio_threshold / logprob_threshold; upstream would "
                               "retry at a higher temperature, this path runs temperature 0 only (segments carry needs_fallback=True)",
