@@ -508,6 +508,45 @@ int wipa_edit_distance_batch(const int32_t* ref_ids, const int32_t* ref_off, con
                              const int32_t* ref_off_host, const int32_t* hyp_off_host,
                              int32_t* per_dist, int32_t* pfer24, wipa_stream_t s);
 
+/* ------------------------------------------------------------------ K15 word-timestamp alignment (csrc/align.hip)
+ * The numeric core of openai-whisper timing.py find_alignment, which mlx_whisper ports ([UPSTREAM-UNVERIFIED]: restated from
+ * memory, pinned to the local transformers copy of the same chain): per alignment head softmax over a window's own frames,
+ * z-score over the token axis (population std, no epsilon), width-7 median filter with reflect padding, mean over heads; then
+ * dynamic time warping of the negated matrix.  All sizes per clip live in device memory; nothing of clip b depends on the
+ * rest of the batch. */
+#define WIPA_ALIGN_MAX_TOKENS 448  /* token rows per clip (n_text_ctx) */
+#define WIPA_ALIGN_MAX_FRAMES 1500 /* encoder frames per clip (n_audio_ctx) */
+#define WIPA_ALIGN_MAX_HEADS 32    /* alignment heads of one decoder layer */
+/* One decoder layer's alignment heads, ADDED into out [B, T, ld_out] f32 (the caller zeroes it before the first layer):
+ *   q [B, T, d] and keys k[b * k_bs + h * k_hs + frame * 64 + c] (elements), both of `dtype` and both carrying the 64^-0.25 scale, as
+ *   wipa_decoder_logits leaves them in its workspace; heads_host: n_heads head indices of this layer (HOST), summed in this order;
+ *   n_tokens / n_frames int32 [B] (device): clip b uses rows [0, n_tokens[b]) and frames [0, n_frames[b]) only, other cells of out
+ *   are not touched; n_frames[b] <= 3 skips the median filter, as upstream does.
+ *   divisor != 0: the cell is divided by it after the LAST head of this call (the mean over all heads of all layers).
+ * Everything after the q.k products (f32 FMA chains, exact for f32 and bf16 operands) runs in f32.  No float atomics: one
+ * thread owns an output cell for all heads of a call.  scratch: wipa_align_weights_scratch_bytes(B, T, n_heads, n_audio_ctx). */
+size_t wipa_align_weights_scratch_bytes(int B, int T, int n_heads, int n_audio_ctx);
+int wipa_align_weights(const void* q, const void* k, int64_t k_bs, int64_t k_hs, int dtype, int B, int T, int d, int n_audio_ctx,
+                       const int32_t* heads_host, int n_heads, const int32_t* n_tokens, const int32_t* n_frames, void* scratch,
+                       size_t scratch_bytes, float* out, int64_t ld_out, float divisor, wipa_stream_t s);
+/* probs[m] for the rows m = row0 .. row0 + rows - 1 of a [B * T] grid (m = b T + t): softmax over columns [0, eot) of logits row
+ * m - row0, taken at tokens[m + 1]; 0 where t + 1 >= n_tokens[b] or that token is not below eot. */
+int wipa_token_probs(const float* logits, int64_t ldl, int row0, int rows, const int32_t* tokens, const int32_t* n_tokens, int B, int T,
+                     int eot, float* probs, wipa_stream_t s);
+/* Batched DTW, one wave per clip.  Clip b aligns rows [first_row, first_row + n_rows[b]) and columns [0, n_cols[b]) of
+ * matrix[b * batch_stride + row * ld + col]; the kernel negates the matrix itself.  cost is f32 [N+1, M+1], +inf except
+ * cost[0][0] = 0; cost[i][j] = -x[i-1][j-1] + c with (c, t) = (c0, 0) if c0 < c1 and c0 < c2, else (c1, 1) if c1 < c0 and c1 < c2,
+ * else (c2, 2), for c0 = cost[i-1][j-1], c1 = cost[i-1][j], c2 = cost[i][j-1]: one f32 add per cell, so cost, trace and path are
+ * those of the float32 restatement bit for bit, ties included.  The path (text_idx / time_idx [B, ld_path] int32, ascending)
+ * has path_len[b] <= N + M - 1 entries; n_rows[b] = 0 writes length 0.  n_rows_host / n_cols_host are the HOST copies: they
+ * are checked before the launch (0 <= N <= WIPA_ALIGN_MAX_TOKENS, 1 <= M <= WIPA_ALIGN_MAX_FRAMES where N > 0, rows inside
+ * rows_avail, N + M <= ld_path); a violation is WIPA_ERR_ARG with nothing launched.  scratch holds the 2-bit trace codes:
+ * wipa_dtw_scratch_bytes(B, largest n_rows). */
+size_t wipa_dtw_scratch_bytes(int B, int max_rows);
+int wipa_dtw_batch(const float* matrix, int64_t batch_stride, int64_t ld, int first_row, int rows_avail, const int32_t* n_rows,
+                   const int32_t* n_cols, const int32_t* n_rows_host, const int32_t* n_cols_host, int B, void* scratch,
+                   size_t scratch_bytes, int32_t* text_idx, int32_t* time_idx, int64_t ld_path, int32_t* path_len, wipa_stream_t s);
+
 /* ------------------------------------------------------------------ host-side text plumbing (no GPU work)
  * Byte-level BPE of mlx_whisper.tokenizer (tiktoken's CoreBPE) and the token-batch builder of
  * IPADataset._tokenize_ipa_batch (scripts/ipa_data_loader.py:102-131, 146-152).  HOST pointers throughout.
@@ -677,6 +716,26 @@ size_t wipa_decoder_logits_workspace_bytes(const wipa_model_cfg* cfg, int B, int
 int wipa_decoder_logits(const wipa_model_cfg* cfg, const void* const* weights, const int32_t* tokens, const void* features,
                         float* logits, int64_t ld_logits, void* workspace, size_t workspace_bytes, int B, int T,
                         wipa_stream_t s);
+
+/* find_alignment's device part on the same teacher-forced pass (one layer body shared with wipa_decoder_logits):
+ *   tokens [B, T] int32 (rows padded past n_tokens[b] with any valid id), features [B, n_audio_ctx, d];
+ *   heads_host: n_heads (layer, head) pairs (HOST int32 [2 n_heads]); after the cross-attention projections of every layer that
+ *   has some, wipa_align_weights adds them -- in list order within a layer, layers in stream order -- and the last such call
+ *   divides by n_heads;  n_tokens / n_frames int32 [B] on the device, *_host their host copies (checked before any launch);
+ *   matrix f32 [B, T, n_audio_ctx] receives the head mean (rows / frames outside a clip's range are 0);
+ *   the DTW (wipa_dtw_batch) then runs on rows [first_row, first_row + n_rows[b]) and frames [0, n_frames[b]) into text_idx /
+ *   time_idx [B, ld_path], path_len [B]: n_rows[b] = n_tokens[b] - first_row - 1 is upstream's matrix[len(sot_sequence) : -1],
+ *   0 leaves the clip without a path (n_rows device, n_rows_host its host copy);
+ *   token_probs f32 [B, T]: wipa_token_probs of the final logits, which are projected in blocks of logits_rows rows
+ *   (0 = as many as fit 1 GiB of f32 logits) and never exist as a whole.
+ * fp8 decoder weight tables are refused, as by wipa_decoder_logits. */
+size_t wipa_decoder_align_workspace_bytes(const wipa_model_cfg* cfg, int B, int T, int n_heads, int logits_rows);
+int wipa_decoder_align(const wipa_model_cfg* cfg, const void* const* weights, const int32_t* tokens, const void* features,
+                       const int32_t* heads_host, int n_heads, const int32_t* n_tokens, const int32_t* n_frames,
+                       const int32_t* n_rows, const int32_t* n_tokens_host, const int32_t* n_frames_host, const int32_t* n_rows_host,
+                       int first_row, int eot, float* matrix,
+                       int32_t* text_idx, int32_t* time_idx, int64_t ld_path, int32_t* path_len, float* token_probs, int logits_rows,
+                       void* workspace, size_t workspace_bytes, int B, int T, wipa_stream_t s);
 
 /* ------------------------------------------------------------------ K9 masked CE
  * compute_loss of train_whisper_ipa.py:207-263 on teacher-forced logits.

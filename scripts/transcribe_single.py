@@ -57,6 +57,8 @@ def main(argv=None):
                     help="local directory with config.json + weights.safetensors (hub names cannot resolve offline)")
     ap.add_argument("--temperature", type=float, default=0.0, help="above 0: sample instead of taking the arg-max (needs --seed)")
     ap.add_argument("--seed", type=int, default=None, help="seed of the sampling draw: the same seed gives the same transcript")
+    ap.add_argument("--word-timestamps", action="store_true",
+                    help="transcribe through whisper_ipa_amd.transcribe(word_timestamps=True) and also print one line per word (start, end, probability)")
     ap.add_argument("--allow-byte-fallback", action="store_true",
                     help="run without the Whisper vocabulary (WIPA_TIKTOKEN unset): ids >= 256 print as <|idN|>; synthetic weights only")
     args = ap.parse_args(argv)
@@ -66,11 +68,24 @@ def main(argv=None):
     model = load_checkpoint_model(args.checkpoint, args.base_model)
     if args.temperature != 0.0 and args.seed is None:
         ap.error("--temperature above 0 needs --seed")
-    text = transcribe_file(model, args.audio, temperature=args.temperature, seed=args.seed)
+    words = []
+    if args.word_timestamps:  # one decode: the prediction is the transcript the words belong to
+        if args.temperature != 0.0:
+            ap.error("--word-timestamps goes through transcribe(), whose schedule starts at temperature 0: drop --temperature")
+        from whisper_ipa_amd import transcribe
+
+        print(f"Transcribing {args.audio}...")
+        out = transcribe(model, args.audio, language="en", word_timestamps=True, seed=args.seed)
+        text = out["text"].strip()
+        words = [w for seg in out["segments"] for w in seg.get("words", [])]
+    else:
+        text = transcribe_file(model, args.audio, temperature=args.temperature, seed=args.seed)
     print("\n" + "=" * 50)
     print(f"Audio: {args.audio}")
     print(f"Prediction: {text}")
     print("=" * 50)
+    for w in words:
+        print(f"[{w['start']:7.2f} -> {w['end']:7.2f}] p={w['probability']:.3f} {w['word']}")
     return text
 
 

@@ -178,6 +178,17 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "wipa_edit_distance_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, _P(C.c_int32),
                                          _P(C.c_int32), c_void_p, c_void_p, c_void_p]),
+    "wipa_align_weights_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "wipa_align_weights": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, _P(C.c_int32), c_int, c_void_p,
+                                   c_void_p, c_void_p, c_size_t, c_void_p, c_int64, c_float, c_void_p]),
+    "wipa_token_probs": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "wipa_dtw_scratch_bytes": (c_size_t, [c_int, c_int]),
+    "wipa_dtw_batch": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, _P(C.c_int32), _P(C.c_int32), c_int, c_void_p,
+                               c_size_t, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "wipa_decoder_align_workspace_bytes": (c_size_t, [_P(ModelCfg), c_int, c_int, c_int, c_int]),
+    "wipa_decoder_align": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_void_p, _P(C.c_int32), c_int, c_void_p, c_void_p, c_void_p,
+                                   _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64,
+                                   c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     "wipa_bpe_create": (c_void_p, [c_void_p, c_void_p, c_void_p, c_int]),
     "wipa_bpe_free": (None, [c_void_p]),
     "wipa_bpe_encode_piece": (c_int, [c_void_p, C.c_char_p, c_int, c_void_p, c_int]),

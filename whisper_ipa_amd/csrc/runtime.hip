@@ -1188,25 +1188,18 @@ TfWs tf_ws(const wipa_model_cfg* c, int B, int T) {
 }
 }  // namespace
 
-extern "C" size_t wipa_decoder_logits_workspace_bytes(const wipa_model_cfg* cfg, int B, int T) {
-    if (!cfg || B <= 0 || T <= 0) return 0;
-    return tf_ws(cfg, B, T).total;
-}
-
-extern "C" int wipa_decoder_logits(const wipa_model_cfg* cfg, const void* const* w, const int32_t* tokens, const void* features,
-                                   float* logits, int64_t ld_logits, void* workspace, size_t workspace_bytes, int B, int T,
-                                   wipa_stream_t stream) {
-    RT_CALL(cfg_check(cfg));
-    SplitScope split_scope(cfg);
-    WIPA_REQUIRE(w && tokens && features && logits && workspace && B > 0 && T > 0, "wipa_decoder_logits: bad arguments");
-    WIPA_REQUIRE(T <= cfg->n_text_ctx, "wipa_decoder_logits: T=%d exceeds n_text_ctx=%d", T, cfg->n_text_ctx);
-    WIPA_REQUIRE(cfg->dec_w_dtype == 0, "wipa_decoder_logits: the teacher-forced decoder runs on a bf16 / f32 weight table (fp8 tables serve the decode step)");
-    const TfWs L = tf_ws(cfg, B, T);
-    WIPA_REQUIRE(workspace_bytes >= L.total, "wipa_decoder_logits: workspace too small (%zu < %zu)", workspace_bytes, L.total);
+namespace {
+// what wipa_decoder_align does between a layer's cross-attention projections and its cross-attention
+struct TfHook {
+    virtual int after_cross_projections(int layer, const void* q, const void* ckv, int64_t k_bs, int64_t k_hs) const = 0;
+    virtual ~TfHook() {}
+};
+// embedding + every decoder layer of the teacher-forced pass; leaves the residual stream in ws.x (f32 [B*T, d])
+int tf_layers(const wipa_model_cfg* cfg, const void* const* w, const int32_t* tokens, const void* features, char* ws, const TfWs& L, int B,
+              int T, const TfHook* hook, wipa_stream_t stream) {
     const int dt = cfg->dtype;
     const size_t e = wipa_dtype_size(dt);
     const int d = cfg->n_text_state, H = cfg->n_text_head, Ta = cfg->n_audio_ctx, M = B * T;
-    char* ws = (char*)workspace;
     float* x = (float*)(ws + L.x);
     void* ln = ws + L.ln;
     char* qkv = ws + L.qkv;
@@ -1251,6 +1244,7 @@ extern "C" int wipa_decoder_logits(const wipa_model_cfg* cfg, const void* const*
             g.cg_in = 64; g.cg_stride = (int64_t)Ta * 64;
             RT_CALL(gemm(features, d, lw[10], d, ckv, 64, B * Ta, 2 * d, d, dt, dt, (const float*)lw[11], 0, nullptr, stream, &g));
         }
+        if (hook) RT_CALL(hook->after_cross_projections(l, q, ckv, (int64_t)2 * H * Ta * 64, (int64_t)Ta * 64));
         {
             wipa_attn_desc a;
             memset(&a, 0, sizeof(a));
@@ -1267,7 +1261,138 @@ extern "C" int wipa_decoder_logits(const wipa_model_cfg* cfg, const void* const*
         RT_CALL(gemm(ln, d, lw[16], d, hb, 4 * d, M, 4 * d, d, dt, dt, (const float*)lw[17], 1, nullptr, stream));
         RT_CALL(gemm(hb, 4 * d, lw[18], 4 * d, x, d, M, d, 4 * d, dt, WIPA_F32, (const float*)lw[19], 0, x, stream));
     }
+    return WIPA_OK;
+}
+}  // namespace
+
+extern "C" size_t wipa_decoder_logits_workspace_bytes(const wipa_model_cfg* cfg, int B, int T) {
+    if (!cfg || B <= 0 || T <= 0) return 0;
+    return tf_ws(cfg, B, T).total;
+}
+
+extern "C" int wipa_decoder_logits(const wipa_model_cfg* cfg, const void* const* w, const int32_t* tokens, const void* features,
+                                   float* logits, int64_t ld_logits, void* workspace, size_t workspace_bytes, int B, int T,
+                                   wipa_stream_t stream) {
+    RT_CALL(cfg_check(cfg));
+    SplitScope split_scope(cfg);
+    WIPA_REQUIRE(w && tokens && features && logits && workspace && B > 0 && T > 0, "wipa_decoder_logits: bad arguments");
+    WIPA_REQUIRE(T <= cfg->n_text_ctx, "wipa_decoder_logits: T=%d exceeds n_text_ctx=%d", T, cfg->n_text_ctx);
+    WIPA_REQUIRE(cfg->dec_w_dtype == 0, "wipa_decoder_logits: the teacher-forced decoder runs on a bf16 / f32 weight table (fp8 tables serve the decode step)");
+    const TfWs L = tf_ws(cfg, B, T);
+    WIPA_REQUIRE(workspace_bytes >= L.total, "wipa_decoder_logits: workspace too small (%zu < %zu)", workspace_bytes, L.total);
+    RT_CALL(tf_layers(cfg, w, tokens, features, (char*)workspace, L, B, T, nullptr, stream));
+    const int dt = cfg->dtype, d = cfg->n_text_state, M = B * T;
+    float* x = (float*)((char*)workspace + L.x);
+    void* ln = (char*)workspace + L.ln;
     RT_CALL(wipa_layernorm(x, WIPA_F32, d, ln, dt, d, (const float*)w[2], (const float*)w[3], M, d, 1e-5f, stream));
     RT_CALL(gemm(ln, d, w[0], d, logits, ld_logits, M, cfg->n_vocab, d, dt, WIPA_F32, nullptr, 0, nullptr, stream));
+    return WIPA_OK;
+}
+
+// ------------------------------------------------------------------ word-timestamp alignment on the teacher-forced pass
+namespace {
+constexpr size_t ALIGN_LOGITS_BYTES = (size_t)1 << 30;  // the most f32 logits that exist at once
+struct AlignWs {
+    TfWs tf;
+    size_t stats, stats_bytes, logits, trace, trace_bytes, total;
+    int block_rows;
+};
+AlignWs align_ws(const wipa_model_cfg* c, int B, int T, int n_heads, int logits_rows) {
+    AlignWs a;
+    a.tf = tf_ws(c, B, T);
+    size_t o = a.tf.total;
+    const int per_layer = std::min(std::max(n_heads, 1), (int)c->n_text_head);  // a layer holds each of its heads once
+    a.stats_bytes = wipa_align_weights_scratch_bytes(B, T, per_layer, c->n_audio_ctx);
+    a.stats = o; o += align256(a.stats_bytes);
+    const size_t row_bytes = (size_t)round_up(c->n_vocab, 8) * 4;  // the row stride Whisper.logits uses
+    size_t rows = std::max<size_t>(1, ALIGN_LOGITS_BYTES / row_bytes);
+    if (logits_rows > 0) rows = std::min<size_t>(rows, (size_t)logits_rows);
+    a.block_rows = (int)std::min<size_t>(rows, (size_t)B * T);
+    a.logits = o; o += align256((size_t)a.block_rows * row_bytes);
+    a.trace_bytes = wipa_dtw_scratch_bytes(B, T);
+    a.trace = o; o += align256(a.trace_bytes);
+    a.total = o;
+    return a;
+}
+struct AlignHook : TfHook {
+    const wipa_model_cfg* cfg;
+    std::vector<std::vector<int32_t>> by_layer;  // head indices in list order
+    int last_layer = -1, n_heads = 0, B = 0, T = 0;
+    const int32_t *n_tokens = nullptr, *n_frames = nullptr;
+    void* stats = nullptr;
+    size_t stats_bytes = 0;
+    float* matrix = nullptr;
+    wipa_stream_t stream = nullptr;
+    int after_cross_projections(int layer, const void* q, const void* ckv, int64_t k_bs, int64_t k_hs) const override {
+        const std::vector<int32_t>& hs = by_layer[layer];
+        if (hs.empty()) return WIPA_OK;
+        return wipa_align_weights(q, ckv, k_bs, k_hs, cfg->dtype, B, T, cfg->n_text_state, cfg->n_audio_ctx, hs.data(), (int)hs.size(), n_tokens,
+                                  n_frames, stats, stats_bytes, matrix, cfg->n_audio_ctx, layer == last_layer ? (float)n_heads : 0.f, stream);
+    }
+};
+}  // namespace
+
+extern "C" size_t wipa_decoder_align_workspace_bytes(const wipa_model_cfg* cfg, int B, int T, int n_heads, int logits_rows) {
+    if (!cfg || B <= 0 || T <= 0 || n_heads <= 0 || logits_rows < 0) return 0;
+    return align_ws(cfg, B, T, n_heads, logits_rows).total;
+}
+
+extern "C" int wipa_decoder_align(const wipa_model_cfg* cfg, const void* const* w, const int32_t* tokens, const void* features,
+                                  const int32_t* heads_host, int n_heads, const int32_t* n_tokens, const int32_t* n_frames,
+                                  const int32_t* n_rows, const int32_t* n_tokens_host, const int32_t* n_frames_host, const int32_t* n_rows_host,
+                                  int first_row, int eot, float* matrix, int32_t* text_idx, int32_t* time_idx, int64_t ld_path, int32_t* path_len,
+                                  float* token_probs, int logits_rows, void* workspace, size_t workspace_bytes, int B, int T,
+                                  wipa_stream_t stream) {
+    RT_CALL(cfg_check(cfg));
+    SplitScope split_scope(cfg);
+    WIPA_REQUIRE(w && tokens && features && heads_host && n_tokens && n_frames && n_rows && n_tokens_host && n_frames_host && n_rows_host &&
+                     matrix && text_idx && time_idx && path_len && token_probs && workspace && B > 0 && T > 0,
+                 "wipa_decoder_align: bad arguments");
+    WIPA_REQUIRE(T <= cfg->n_text_ctx && T <= WIPA_ALIGN_MAX_TOKENS, "wipa_decoder_align: T=%d exceeds n_text_ctx=%d", T, cfg->n_text_ctx);
+    WIPA_REQUIRE(cfg->dec_w_dtype == 0, "wipa_decoder_align: the teacher-forced decoder runs on a bf16 / f32 weight table (fp8 tables serve the decode step)");
+    WIPA_REQUIRE(n_heads >= 1 && n_heads <= cfg->n_text_layer * cfg->n_text_head && cfg->n_text_head <= WIPA_ALIGN_MAX_HEADS,
+                 "wipa_decoder_align: %d alignment heads (1..%d)", n_heads, cfg->n_text_layer * cfg->n_text_head);
+    WIPA_REQUIRE(logits_rows >= 0 && eot >= 1 && eot <= cfg->n_vocab && first_row >= 0, "wipa_decoder_align: logits_rows=%d eot=%d first_row=%d",
+                 logits_rows, eot, first_row);
+    for (int b = 0; b < B; ++b) {
+        WIPA_REQUIRE(n_tokens_host[b] >= 1 && n_tokens_host[b] <= T, "wipa_decoder_align: clip %d: %d tokens (1..%d)", b, n_tokens_host[b], T);
+        WIPA_REQUIRE(n_frames_host[b] >= 1 && n_frames_host[b] <= cfg->n_audio_ctx, "wipa_decoder_align: clip %d: %d frames (1..%d)", b,
+                     n_frames_host[b], cfg->n_audio_ctx);
+        WIPA_REQUIRE(n_rows_host[b] >= 0 && first_row + n_rows_host[b] <= n_tokens_host[b], "wipa_decoder_align: clip %d: rows [%d, %d + %d) of %d tokens",
+                     b, first_row, first_row, n_rows_host[b], n_tokens_host[b]);
+    }
+    AlignHook hook;
+    hook.cfg = cfg;
+    hook.by_layer.resize(cfg->n_text_layer);
+    for (int i = 0; i < n_heads; ++i) {
+        const int l = heads_host[2 * i], h = heads_host[2 * i + 1];
+        WIPA_REQUIRE(l >= 0 && l < cfg->n_text_layer && h >= 0 && h < cfg->n_text_head, "wipa_decoder_align: alignment head (%d, %d) of %d x %d", l, h,
+                     cfg->n_text_layer, cfg->n_text_head);
+        std::vector<int32_t>& hs = hook.by_layer[l];
+        WIPA_REQUIRE(std::find(hs.begin(), hs.end(), h) == hs.end(), "wipa_decoder_align: alignment head (%d, %d) listed twice", l, h);
+        hs.push_back(h);
+        hook.last_layer = std::max(hook.last_layer, l);
+    }
+    const AlignWs L = align_ws(cfg, B, T, n_heads, logits_rows);
+    WIPA_REQUIRE(workspace_bytes >= L.total, "wipa_decoder_align: workspace too small (%zu < %zu)", workspace_bytes, L.total);
+    char* ws = (char*)workspace;
+    const int dt = cfg->dtype, d = cfg->n_text_state, Ta = cfg->n_audio_ctx, M = B * T, V = cfg->n_vocab, ldl = round_up(V, 8);
+    hook.n_heads = n_heads; hook.B = B; hook.T = T;
+    hook.n_tokens = n_tokens; hook.n_frames = n_frames;
+    hook.stats = ws + L.stats; hook.stats_bytes = L.stats_bytes;
+    hook.matrix = matrix; hook.stream = stream;
+    WIPA_CHECK_HIP(hipMemsetAsync(matrix, 0, (size_t)M * Ta * sizeof(float), (hipStream_t)stream));
+    RT_CALL(tf_layers(cfg, w, tokens, features, ws, L.tf, B, T, &hook, stream));
+    RT_CALL(wipa_dtw_batch(matrix, (int64_t)T * Ta, Ta, first_row, T, n_rows, n_frames, n_rows_host, n_frames_host, B, ws + L.trace, L.trace_bytes,
+                           text_idx, time_idx, ld_path, path_len, stream));
+    float* x = (float*)(ws + L.tf.x);
+    char* ln = ws + L.tf.ln;
+    float* lg = (float*)(ws + L.logits);
+    RT_CALL(wipa_layernorm(x, WIPA_F32, d, ln, dt, d, (const float*)w[2], (const float*)w[3], M, d, 1e-5f, stream));
+    for (int r0 = 0; r0 < M; r0 += L.block_rows) {
+        const int rows = std::min(L.block_rows, M - r0);
+        RT_CALL(gemm(ln + (size_t)r0 * d * wipa_dtype_size(dt), d, w[0], d, lg, ldl, rows, V, d, dt, WIPA_F32, nullptr, 0, nullptr, stream));
+        RT_CALL(wipa_token_probs(lg, ldl, r0, rows, tokens, n_tokens, B, T, eot, token_probs, stream));
+    }
     return WIPA_OK;
 }

@@ -237,6 +237,52 @@ class Tokenizer:
             out.append(self.decode(run))
         return "".join(out)
 
+    # ---- words (openai-whisper tokenizer.py split_to_word_tokens, which mlx_whisper ports; [UPSTREAM-UNVERIFIED])
+    def split_to_word_tokens(self, tokens: Sequence[int]) -> Tuple[List[str], List[List[int]]]:
+        """(words, their token lists).  Languages written without spaces are cut at every complete Unicode character, the others
+        at spaces and punctuation."""
+        if self.language in {"zh", "ja", "th", "lo", "my", "yue"}:
+            return self.split_tokens_on_unicode(tokens)
+        return self.split_tokens_on_spaces(tokens)
+
+    def split_tokens_on_unicode(self, tokens: Sequence[int]) -> Tuple[List[str], List[List[int]]]:
+        """Tokens are accumulated until they decode without U+FFFD -- a character of a byte-level BPE may straddle tokens, as
+        most IPA symbols do -- or until the U+FFFD is genuinely part of the text (the full decoding has one at the same
+        place)."""
+        decoded_full = self.decode_with_timestamps(tokens)
+        replacement_char = "�"
+        words: List[str] = []
+        word_tokens: List[List[int]] = []
+        current: List[int] = []
+        unicode_offset = 0
+        for token in tokens:
+            current.append(int(token))
+            decoded = self.decode_with_timestamps(current)
+            if replacement_char not in decoded or decoded_full[unicode_offset + decoded.index(replacement_char)] == replacement_char:
+                words.append(decoded)
+                word_tokens.append(current)
+                current = []
+                unicode_offset += len(decoded)
+        return words, word_tokens
+
+    def split_tokens_on_spaces(self, tokens: Sequence[int]) -> Tuple[List[str], List[List[int]]]:
+        import string
+
+        subwords, subword_tokens_list = self.split_tokens_on_unicode(tokens)
+        words: List[str] = []
+        word_tokens: List[List[int]] = []
+        for subword, subword_tokens in zip(subwords, subword_tokens_list):
+            special = subword_tokens[0] >= self.eot
+            with_space = subword.startswith(" ")
+            punctuation = subword.strip() in string.punctuation
+            if special or with_space or punctuation or len(words) == 0:
+                words.append(subword)
+                word_tokens.append(subword_tokens)
+            else:
+                words[-1] = words[-1] + subword
+                word_tokens[-1].extend(subword_tokens)
+        return words, word_tokens
+
     @property
     def non_speech_tokens(self) -> Tuple[int, ...]:
         """mlx_whisper.tokenizer.Tokenizer.non_speech_tokens: derived from the vocabulary when it

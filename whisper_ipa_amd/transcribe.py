@@ -16,7 +16,12 @@ What differs from upstream, on purpose:
     decoded again, as ONE sub-batch per temperature of the schedule, from the encoder features the first decode left (no second
     log-mel, no second encoder pass), until they pass or the schedule ends (the last attempt is kept, as upstream does).  The draw
     is a function of (seed, (seek, file index), index in the schedule, position, column): a window samples the same tokens
-    whichever rows it is retried with.  Upstream draws from a global generator instead; ``best_of`` is not implemented.
+    whichever rows it is retried with.  Upstream draws from a global generator instead; ``best_of`` is not implemented;
+  * ``word_timestamps=True``: after a round's decode and fallback, the windows that were not skipped go through ONE
+    ``timing.find_alignment`` call from the encoder features their decode left (no second log-mel, no second encoder pass), and
+    every segment gains ``"words"``.  Upstream's word-duration heuristics, its snapping of segment bounds to the words and of
+    ``seek`` to the last word are left out (timing.py says why), so segments and seeks are those of ``word_timestamps=False``.
+    An fp8-quantised model is refused before anything is decoded.
 """
 from __future__ import annotations
 
@@ -68,13 +73,13 @@ def split_segments(tokens: Sequence[int], tb: int, time_offset: float, segment_s
 
 
 def _refuse(condition_on_previous_text, initial_prompt, word_timestamps, clip_timestamps, hallucination_silence_threshold, temperature,
-            decode_options) -> None:
+            decode_options, can_align: bool = False) -> None:
     if condition_on_previous_text:
         raise NotImplementedError("condition_on_previous_text=True (prompt conditioning) is not implemented")
     if initial_prompt is not None:
         raise NotImplementedError("initial_prompt (prompt conditioning) is not implemented")
-    if word_timestamps:
-        raise NotImplementedError("word_timestamps=True is not implemented")
+    if word_timestamps and not can_align:
+        raise NotImplementedError("word_timestamps=True is not implemented without a model: a custom decode_fn needs an align_fn")
     if clip_timestamps not in (None, "0", [0], (0,)):
         raise NotImplementedError("clip_timestamps is not implemented")
     if hallucination_silence_threshold is not None:
@@ -125,6 +130,43 @@ def _model_decoder(model, decode_options: dict) -> Callable:
     return run
 
 
+def _add_words(model, tok, to_align, prepend_punctuations, append_punctuations, align_fn) -> None:
+    """one alignment call for the round's windows; every segment of ``to_align`` gains "words".  As upstream, the words are
+    found and dealt on the tokens every segment was decoded with; a segment that was emptied (zero length, blank text) then
+    keeps no words"""
+    from . import timing
+
+    results = [t[0] for t in to_align]
+    kept = [t[1] for t in to_align]
+    segs = [[{"tokens": toks} for toks in t[5]] for t in to_align]  # stand-ins that still hold their tokens
+    sizes = [t[2] for t in to_align]
+    offsets = [t[3] for t in to_align]
+    langs = [t[4] for t in to_align]
+    if align_fn is not None:
+        timing.add_word_timestamps(segs, None, tok, None, sizes, offsets, prepend_punctuations, append_punctuations,
+                                   align_fn=lambda text_tokens, _features, num_frames: align_fn(results, text_tokens, num_frames, langs))
+        _keep_words(kept, segs)
+        return
+    import torch
+
+    from .tokenizer import get_tokenizer
+
+    # the sot_sequence names the language: windows are aligned per language, each group in one call
+    for lang in sorted(set(langs), key=lambda l: l or ""):
+        rows = [j for j, l in enumerate(langs) if l == lang]
+        ltok = get_tokenizer(model.is_multilingual, num_languages=model.num_languages, language=lang or "en", task="transcribe")
+        feats = torch.stack([results[j].audio_features for j in rows])
+        timing.add_word_timestamps([segs[j] for j in rows], model, ltok, feats, [sizes[j] for j in rows], [offsets[j] for j in rows],
+                                   prepend_punctuations, append_punctuations)
+    _keep_words(kept, segs)
+
+
+def _keep_words(kept, segs) -> None:
+    for window, stand_ins in zip(kept, segs):
+        for seg, stand_in in zip(window, stand_ins):
+            seg["words"] = stand_in["words"] if seg["tokens"] or not stand_in["tokens"] else []
+
+
 def _needs_fallback(res, compression_ratio_threshold, logprob_threshold, no_speech_threshold) -> bool:
     """upstream's decode_with_fallback predicate on one decoded window"""
     needs_fallback = False
@@ -143,7 +185,9 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
                no_speech_threshold: Optional[float] = 0.6, condition_on_previous_text: bool = False,
                initial_prompt: Optional[str] = None, word_timestamps: bool = False, clip_timestamps=None,
                hallucination_silence_threshold: Optional[float] = None, language: Optional[str] = None, decode_fn: Optional[Callable] = None,
-               tokenizer=None, seed: Optional[int] = None, fallback_fn: Optional[Callable] = None, **decode_options):
+               tokenizer=None, seed: Optional[int] = None, fallback_fn: Optional[Callable] = None,
+               prepend_punctuations: str = "\"'“¿([{-", append_punctuations: str = "\"'.。,，!！?？:：”)]}、",
+               align_fn: Optional[Callable] = None, **decode_options):
     """``audio``: a path, a 16 kHz mono float array, or a list of them.  Returns {"text", "segments", "language"} (a list of
     them for a list) with mlx_whisper's segment keys (``SEGMENT_KEYS``; plus ``needs_fallback`` where upstream would have
     retried).  ``condition_on_previous_text`` defaults to False here: True is refused, like every option this path does not
@@ -153,9 +197,15 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
     produced them, and neither ``needs_fallback`` nor the warning appears where a retry ran.  ``fallback_fn(results, languages,
     temperature=, attempt=, streams=, seed=)`` -> new results for those rows replaces the model's retry; with a custom ``decode_fn``
     and no ``fallback_fn`` a seed changes nothing.  ``streams[j]`` = (seek in mel frames, file index), ``attempt`` = index in the
-    schedule."""
+    schedule.  ``word_timestamps=True``: every segment gains ``"words"``: [{"word", "start", "end", "probability"}]
+    (timing.py); ``align_fn(results, text_tokens, num_frames, languages)`` -> one list of WordTiming per window replaces the
+    model's alignment (``results``: the windows' decode results, ``text_tokens[j]`` the ids below EOT of window j's segments,
+    ``num_frames[j]`` its content in mel frames); it is required with a custom ``decode_fn``."""
     _refuse(condition_on_previous_text, initial_prompt, word_timestamps, clip_timestamps, hallucination_silence_threshold, temperature,
-            decode_options)
+            decode_options, can_align=align_fn is not None or (model is not None and decode_fn is None))
+    if word_timestamps and align_fn is None and getattr(model, "_fp8", None):
+        raise NotImplementedError("word_timestamps=True is not implemented for an fp8-quantised model: the alignment runs the "
+                                  "teacher-forced decoder on bf16 / f32 weights")
     single = not isinstance(audio, (list, tuple))
     items = [audio] if single else list(audio)
     clips = []
@@ -199,6 +249,7 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
             chunk = clips[i][s0:s0 + size * HOP_LENGTH]
             windows[r, :len(chunk)] = chunk  # pad_or_trim of the window's own samples
         results = list(decode_fn(windows, [languages[i] for i in live]))
+        to_align = []  # (result, the window's segments, content frames, time offset, language, the segments' decoded tokens): rows not skipped
         retried = set()  # rows of this round that went through the schedule
         if fallback_fn is not None:
             thresholds = (compression_ratio_threshold, logprob_threshold, no_speech_threshold)
@@ -234,6 +285,8 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
             at = seek[i]
             segs, advance = split_segments(tokens, tb, time_offset, size)
             seek[i] += advance
+            first_new = len(all_segments[i])
+            decoded_tokens = [list(sg["tokens"]) for sg in segs]  # the alignment sees what was decoded, emptied segments included
             for sg in segs:
                 text = tok.decode([t for t in sg["tokens"] if t < tok.eot])
                 if sg["start"] == sg["end"] or text.strip() == "":
@@ -245,7 +298,11 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
                     seg["needs_fallback"] = True
                 all_segments[i].append(seg)
                 all_tokens[i].extend(sg["tokens"])
+            if word_timestamps:
+                to_align.append((res, all_segments[i][first_new:], size, time_offset, languages[i], decoded_tokens))
             if advance <= 0:  # a pair at <|0.00|> only: never stand still
                 seek[i] += size
+        if word_timestamps and to_align:
+            _add_words(model, tok, to_align, prepend_punctuations, append_punctuations, align_fn)
     out = [{"text": tok.decode([t for t in all_tokens[i] if t < tb]), "segments": all_segments[i], "language": languages[i]} for i in range(n)]
     return out[0] if single else out

@@ -11,8 +11,9 @@ from __future__ import annotations
 import ctypes as C
 import math
 from dataclasses import dataclass, asdict
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -190,6 +191,48 @@ class Whisper:
     @property
     def num_languages(self) -> int:
         return self.dims.n_vocab - 51765 - int(self.is_multilingual)
+
+    @property
+    def alignment_heads(self) -> List[Tuple[int, int]]:
+        """the (layer, head) pairs whose cross-attention carries word timing (timing.find_alignment), in the order their
+        weights are summed; by default every head of the last half of the decoder layers, as upstream's Whisper.__init__"""
+        heads = getattr(self, "_alignment_heads", None)
+        if heads is None:
+            d = self.dims
+            heads = [(l, h) for l in range(d.n_text_layer // 2, d.n_text_layer) for h in range(d.n_text_head)]
+        return list(heads)
+
+    def set_alignment_heads(self, heads) -> None:
+        """``heads``: (layer, head) pairs; a boolean mask [n_text_layer, n_text_head]; or upstream's dump of that mask (base85 of
+        the gzipped bool bytes, the ``_ALIGNMENT_HEADS`` strings of the official checkpoints).  None restores the default."""
+        d = self.dims
+        if heads is None:
+            self._alignment_heads = None
+            return
+        if isinstance(heads, (bytes, str)):
+            import base64
+            import gzip
+
+            raw = gzip.decompress(base64.b85decode(heads))
+            mask = np.frombuffer(raw, dtype=bool)
+            if mask.size != d.n_text_layer * d.n_text_head:
+                raise ValueError(f"set_alignment_heads: the dump holds {mask.size} flags, the model has {d.n_text_layer} x {d.n_text_head} heads")
+            heads = mask.reshape(d.n_text_layer, d.n_text_head)
+        arr = np.asarray(heads.detach().cpu().numpy() if hasattr(heads, "detach") else heads)
+        if arr.dtype == bool:
+            if arr.shape != (d.n_text_layer, d.n_text_head):
+                raise ValueError(f"set_alignment_heads: mask of shape {arr.shape}, the model has {d.n_text_layer} x {d.n_text_head} heads")
+            pairs = [(int(l), int(h)) for l, h in zip(*np.nonzero(arr))]
+        else:
+            pairs = [(int(l), int(h)) for l, h in arr.reshape(-1, 2)]
+        if not pairs:
+            raise ValueError("set_alignment_heads: no head selected")
+        for l, h in pairs:
+            if not (0 <= l < d.n_text_layer and 0 <= h < d.n_text_head):
+                raise ValueError(f"set_alignment_heads: head ({l}, {h}) of a {d.n_text_layer} x {d.n_text_head} decoder")
+        if len(set(pairs)) != len(pairs):
+            raise ValueError("set_alignment_heads: a head is listed twice")
+        self._alignment_heads = pairs
 
     def train(self, mode: bool = True):
         self.training = mode
