@@ -486,6 +486,37 @@ int wipa_embed_layernorm(const int32_t* tokens, int64_t ld_tok, int B, const int
                          const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b,
                          void* y, int y_dtype, int D, float eps, wipa_stream_t s);
 
+/* Ragged prompts (prompt conditioning: wipa_decoder_begin_ragged / wipa_decoder_run_ragged below).  The rows of a batch carry prompts
+ * of different lengths RIGHT-ALIGNED to one common width P: row b's own tokens sit in columns [start[b], P) of tokens[b], columns below
+ * start[b] are padding (token 0, never looked at), generation starts at column P for every row, and ONE position counter serves the
+ * batch.  starts_dev: int32 [B] on the device, required by every *_ragged entry point.  Per row then:
+ *   - the position-embedding index of column c is max(c - start[b], 0);
+ *   - the Philox counter's position word of a draw is the row's own position p - start[b] (a row draws the same tokens in whichever
+ *     batch, i.e. under whichever P, it is decoded);
+ *   - the self-attention of column p reads keys start[b] .. p (wipa_decode_attn_ragged; a padding query reads its own key only).
+ * These are separate instantiations of the step's kernels: the entry points without starts launch what they always launched.
+ * wipa_embed_layernorm_ragged is wipa_embed_layernorm, wipa_step_embed_ragged is the step's tail -- wipa_sample_step_embed with a
+ * sampling record, else wipa_timestamp_step_embed with rules, else wipa_greedy_step_embed -- and wipa_decode_attn_ragged is
+ * wipa_decode_attn in its four-wave form for the self-attention cache (q_row_dev and tk_dev required). */
+int wipa_embed_layernorm_ragged(const int32_t* tokens, int64_t ld_tok, int B, const int32_t* pos_dev, const int32_t* starts_dev,
+                                const void* tok_emb, int emb_dtype, const float* emb_scale, const float* pos_emb, int n_ctx, float* x,
+                                const float* ln_w, const float* ln_b, void* y, int y_dtype, int D, float eps, wipa_stream_t s);
+int wipa_step_embed_ragged(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
+                           int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init,
+                           int eot, const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, float* sum_logprobs,
+                           int32_t* not_done, const void* tok_emb, int emb_dtype, const float* emb_scale, const float* pos_emb, int n_ctx,
+                           float* x, const float* ln_w, const float* ln_b, void* y, int y_dtype, int D, float eps, wipa_stream_t s);
+int wipa_decode_attn_ragged(const wipa_attn_desc* d, const int32_t* starts_dev, wipa_stream_t s);
+/* The same three sites for a whole prompt at once (wipa_decoder_prefill_ragged): wipa_embed_tokens for columns 0 .. T-1 (f32 / bf16
+ * embedding), wipa_attention for the causal self-attention with Tq == Tk (always the f32-math VALU kernel: the f32 MFMA form declines
+ * device-side offsets; a padding query sees the row's first own key), and wipa_sample_step with the row's own position in the counter. */
+int wipa_embed_tokens_ragged(const int32_t* tokens, int64_t ld_tok, int B, int T, const int32_t* starts_dev, const void* tok_emb,
+                             int emb_dtype, const float* pos_emb, float* x, int D, wipa_stream_t s);
+int wipa_attention_ragged(const wipa_attn_desc* d, const int32_t* starts_dev, wipa_stream_t s);
+int wipa_sample_step_ragged(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
+                            int32_t* tokens, int64_t ld_tok, const int32_t* pos_dev, int n_init, int eot, const wipa_decode_rules* rules,
+                            const void* sample, const int32_t* starts_dev, float* sum_logprobs, int32_t* not_done, wipa_stream_t s);
+
 /* ------------------------------------------------------------------ K14 PER / PFER edit distances
  * replaces the dynamic programs behind phone_error_rate (scripts/evaluate_ipa.py:80-105: editdistance.eval on the two phone lists)
  * and PFERCalculator.phone_feature_error_rate (:139-213: the O(m n) Python loop with a feature comparison per cell), as
@@ -707,6 +738,42 @@ int wipa_decoder_run_sample(const wipa_model_cfg* cfg, const void* const* weight
 int wipa_decoder_prefill_sample(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
                                 int eot, const float* mask_first, const float* mask_always, int use_graph,
                                 const wipa_decode_rules* rules, const void* sample, wipa_stream_t s);
+/* Per-row prompts (mlx_whisper.transcribe's condition_on_previous_text / initial_prompt, DecodingOptions.prompt / prefix: each row's
+ * initial tokens are [sot_prev] + history + sot_sequence + prefix, 1..n_text_ctx of them), in the layout described at
+ * wipa_embed_layernorm_ragged above.
+ * wipa_decoder_begin_ragged: wipa_decoder_begin for rows that differ.  tokens_host int32 [B, P] (HOST): row b's own tokens in columns
+ *   [starts_host[b], P), 0 below; starts_host int32 [B] (HOST); both are copied in stream order (tokens into the blob, starts into the
+ *   caller-owned DEVICE array starts_dev int32 [B], which the later calls take).  pos = 0, counters and log-prob sums cleared.
+ *   Refused (WIPA_ERR_ARG, nothing enqueued): P outside 1..n_text_ctx, a start outside 0..P-1 (every row holds at least one token), a
+ *   token outside the vocabulary, fp8 decoder tables.
+ * wipa_decoder_run_ragged: wipa_decoder_run_sample (rules and sample may be NULL) with n_init = P and the rows' starts.  The prompt is
+ *   walked one column per step ("p + 1 < n_init: the given token is taken"); column P is the first generated one for every row.
+ *   starts_dev == NULL enqueues exactly what wipa_decoder_run_sample enqueues.  With starts every step writes its logits and ends
+ *   in the row-scan tail (as with rules); the address of starts_dev is part of the step graph's key.  Refused: a configuration whose
+ *   step is not the unfused one with the fused tail (WIPA_DECODE_TAIL=0, WIPA_DECODE_FUSED=1), fp8 decoder tables, P outside
+ *   1..n_text_ctx, n_steps > n_text_ctx - 1 (the position lives on the device and a call may include the P - 1 steps of the prompt
+ *   walk, so this is the bound that holds at every position; the caller keeps P + new tokens <= n_text_ctx). */
+/* wipa_decoder_prefill_ragged: the first P steps (columns 0 .. P-1 and the first generated token) as ONE batched pass, right after
+ *   wipa_decoder_begin_ragged; continue with wipa_decoder_run_ragged.  The state it leaves is what stepping the prompt leaves, up to
+ *   the rounding of the batched kernels: the pass is the teacher-forced layer body (GEMMs over B * P rows, wipa_attention for both
+ *   attentions) writing K / V of every column into the blob's self-attention cache; cross K / V come from the blob's cache, or with
+ *   absorbed projections are projected per layer from the blob's copy of the encoder output into the workspace.  Logits exist for two
+ *   columns per clip: column P - 1 goes to state.logits and feeds the first greedy / rules / sampling update, and column sot_col (the
+ *   rows' <|startoftranscript|>, the same column for every row; -1: none) goes to f32 [B, ld_logits] at OFFSET 0 of the workspace
+ *   (upstream's logits[:, sot_index], for no_speech_prob).  workspace: caller-owned, wipa_decoder_prompt_workspace_bytes(cfg, B, P)
+ *   bytes, 256-byte aligned; the blob layout does not change.  Captured into a graph like wipa_decoder_prefill: P, sot_col and the
+ *   addresses of starts_dev and of the workspace are part of its key.  Refused: what wipa_decoder_run_ragged refuses, a workspace
+ *   that is too small, P + 1 > n_text_ctx, sot_col outside -1 .. P-1. */
+size_t wipa_decoder_prompt_workspace_bytes(const wipa_model_cfg* cfg, int B, int P);
+int wipa_decoder_prefill_ragged(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int P,
+                                int sot_col, int eot, const float* mask_first, const float* mask_always, int use_graph,
+                                const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, void* workspace,
+                                size_t workspace_bytes, wipa_stream_t s);
+int wipa_decoder_begin_ragged(const wipa_model_cfg* cfg, void* state, size_t state_bytes, int B, const int32_t* tokens_host,
+                              const int32_t* starts_host, int P, int32_t* starts_dev, wipa_stream_t s);
+int wipa_decoder_run_ragged(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int n_init,
+                            int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
+                            const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, wipa_stream_t s);
 /* drop the cached step graphs that reference this state blob (call before freeing it). */
 int wipa_decoder_release(void* state);
 

@@ -17,7 +17,8 @@ Differences that the hardware asks for:
     checkpoint leg's ``decode(language="en", without_timestamps=True)``: it decodes with timestamps on (a three-token prompt),
     applies the timestamp rules on every step, cuts segments, skips silent windows and walks files longer than 30 s window by
     window.  ``--base-decode transcribe`` sends the base leg through ``whisper_ipa_amd.transcribe``, which does all of that
-    (greedy only, without conditioning on previous text; see that module for what it refuses); ``--base-decode decode``, the
+    (without conditioning on previous text unless ``--condition-on-previous-text`` asks for upstream's default, ``--initial-prompt``
+    for a prompt before every file's first window; see that module for what it refuses); ``--base-decode decode``, the
     default, keeps the base leg on the checkpoint leg's path as before, which gives a different token stream than the
     reference's base leg.
 All compute runs in libwipa.so on the GPU.
@@ -111,11 +112,13 @@ def transcribe_clips(model, audio_paths: List[str], options: DecodingOptions, ba
 BASE_DECODE_MODES = ("decode", "transcribe")
 
 
-def transcribe_files(model, audio_paths: List[str], batch_size: int = 64, progress=None, seed: Optional[int] = None) -> List[str]:
+def transcribe_files(model, audio_paths: List[str], batch_size: int = 64, progress=None, seed: Optional[int] = None,
+                     condition_on_previous_text: bool = False, initial_prompt: Optional[str] = None) -> List[str]:
     """reference :112-119 for the whole list: ``mlx_whisper.transcribe(path, language="en", word_timestamps=False)["text"]`` per
     file through whisper_ipa_amd.transcribe, ``batch_size`` files per call (their windows decode as one batch per round).  One
     text per path, "" where the file could not be read.  ``seed``: run mlx_whisper.transcribe's temperature schedule on the windows
-    that fail its thresholds (None: temperature 0 only, such windows are flagged)."""
+    that fail its thresholds (None: temperature 0 only, such windows are flagged).  ``condition_on_previous_text`` / ``initial_prompt``:
+    mlx_whisper.transcribe's options of those names (upstream defaults to conditioning on; here it is opt-in)."""
     from whisper_ipa_amd import transcribe
 
     texts = [""] * len(audio_paths)
@@ -128,7 +131,8 @@ def transcribe_files(model, audio_paths: List[str], batch_size: int = 64, progre
             except Exception as e:
                 print(f"\nError transcribing {path}: {e}")
         if clips:
-            for i, r in zip(slots, transcribe(model, clips, language="en", word_timestamps=False, seed=seed)):
+            for i, r in zip(slots, transcribe(model, clips, language="en", word_timestamps=False, seed=seed,
+                                              condition_on_previous_text=condition_on_previous_text, initial_prompt=initial_prompt)):
                 texts[i] = r["text"].strip()
         if progress is not None:
             progress(min(b + batch_size, len(audio_paths)))
@@ -144,7 +148,8 @@ def transcribe_batch(model, audio_paths: List[str], n_mels: int, options: Decodi
 def evaluate_model(model_path: str, test_data_path: str, num_samples: Optional[int] = None, model_name: str = "Model",
                    is_checkpoint: bool = False, n_mels: int = 80, base_model: str = "mlx-community/whisper-small-mlx",
                    batch_size: int = 64, passes_in_flight: int = 4, ingest: str = "device", scoring: str = "device",
-                   base_decode: str = "decode", seed: Optional[int] = None) -> Dict:
+                   base_decode: str = "decode", seed: Optional[int] = None, condition_on_previous_text: bool = False,
+                   initial_prompt: Optional[str] = None) -> Dict:
     rank, world_size = parallel.world()
     say = print if rank == 0 else (lambda *a, **k: None)
     say("=" * 70)
@@ -175,6 +180,7 @@ def evaluate_model(model_path: str, test_data_path: str, num_samples: Optional[i
     say("\nTranscribing test samples...")
     if base_decode == "transcribe" and not is_checkpoint:
         local_hyp = transcribe_files(model, [s["audio_path"] for s in mine], batch_size=batch_size, seed=seed,
+                                     condition_on_previous_text=condition_on_previous_text, initial_prompt=initial_prompt,
                                      progress=lambda n: say(f"  {n}/{len(mine)} clips on rank 0", flush=True))
     else:
         local_hyp = transcribe_clips(model, [s["audio_path"] for s in mine], options, batch_size=batch_size,
@@ -264,6 +270,11 @@ def main(argv=None) -> Dict:
                     help="with --base-decode transcribe: re-decode the windows that fail the compression-ratio / log-probability "
                          "thresholds at 0.2, 0.4, ... 1.0 as mlx_whisper.transcribe does, sampling reproducibly from this seed "
                          "(default: temperature 0 only)")
+    ap.add_argument("--condition-on-previous-text", action="store_true",
+                    help="with --base-decode transcribe: decode every window after a file's first with the file's previous tokens as "
+                         "its prompt, as mlx_whisper.transcribe does by default (default here: off)")
+    ap.add_argument("--initial-prompt", type=str, default=None,
+                    help="with --base-decode transcribe: mlx_whisper.transcribe's initial_prompt, the prompt of every file's first window")
     ap.add_argument("--results-json", type=str, default=None, help="also write both result dicts here (rank 0)")
     ap.add_argument("--allow-byte-fallback", action="store_true",
                     help="run without the Whisper vocabulary (WIPA_TIKTOKEN unset): hypotheses render ids >= 256 as <|idN|>; "
@@ -286,7 +297,8 @@ def main(argv=None) -> Dict:
         base_results = evaluate_model(args.base_model, args.test_data, num_samples, model_name="Base Whisper Model",
                                       is_checkpoint=False, n_mels=args.n_mels, base_model=args.base_model, batch_size=args.batch_size,
                                       passes_in_flight=args.passes_in_flight, ingest=args.ingest, scoring=args.scoring,
-                                      base_decode=args.base_decode, seed=args.seed)
+                                      base_decode=args.base_decode, seed=args.seed,
+                                      condition_on_previous_text=args.condition_on_previous_text, initial_prompt=args.initial_prompt)
     trained_results = evaluate_model(args.checkpoint, args.test_data, num_samples, model_name="Trained Checkpoint",
                                      is_checkpoint=True, n_mels=args.n_mels, base_model=args.base_model, batch_size=args.batch_size,
                                      passes_in_flight=args.passes_in_flight, ingest=args.ingest, scoring=args.scoring)

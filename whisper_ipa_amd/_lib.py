@@ -213,6 +213,22 @@ SIGNATURES = {
                                         c_int, _P(DecodeRules), c_void_p, c_void_p]),
     "wipa_decoder_prefill_sample": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                             _P(DecodeRules), c_void_p, c_void_p]),
+    "wipa_embed_layernorm_ragged": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
+    "wipa_step_embed_ragged": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                       c_int, c_int, _P(DecodeRules), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                       c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
+    "wipa_decode_attn_ragged": (c_int, [_P(AttnDesc), c_void_p, c_void_p]),
+    "wipa_embed_tokens_ragged": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "wipa_attention_ragged": (c_int, [_P(AttnDesc), c_void_p, c_void_p]),
+    "wipa_sample_step_ragged": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int,
+                                        _P(DecodeRules), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "wipa_decoder_prompt_workspace_bytes": (c_size_t, [_P(ModelCfg), c_int, c_int]),
+    "wipa_decoder_prefill_ragged": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                            _P(DecodeRules), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wipa_decoder_begin_ragged": (c_int, [_P(ModelCfg), c_void_p, c_size_t, c_int, _P(C.c_int32), _P(C.c_int32), c_int, c_void_p, c_void_p]),
+    "wipa_decoder_run_ragged": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                        c_int, _P(DecodeRules), c_void_p, c_void_p, c_void_p]),
     "wipa_decode_cross_attn_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "wipa_decoder_release": (c_int, [c_void_p]),
     "wipa_decoder_logits_workspace_bytes": (c_size_t, [_P(ModelCfg), c_int, c_int]),

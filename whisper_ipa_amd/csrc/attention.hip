@@ -29,17 +29,31 @@ struct AttnParams {
     int Tq, Tk, causal, H;
 };
 
+// Ragged prompts (left-padded rows; wipa_decode_attn_ragged, wipa_attention_ragged): row b's first visible key.  The RAGGED instantiations
+// take it; the others keep AttnParams' layout and their code.
+template <bool RAGGED>
+struct AttnArgs : AttnParams {};
+template <>
+struct AttnArgs<true> : AttnParams {
+    const int32_t* k_start;  // int32 [B], device
+};
+
 constexpr int GA_LD = 68;  // padded f32 row (64 + 4): conflict-free ds_read_b128 across 16 keys
 
-template <typename T>
-__global__ __launch_bounds__(256) void attn_generic_kernel(AttnParams p) {
+// RAGGED (causal self-attention over left-padded prompt rows, Tq == Tk): query i of row b sees keys k_start[b] .. i.  As in
+// decode_attn_kernel the row's K / V base moves up by k_start[b] rows and Tk shrinks by as much, so a live query walks its keys in the
+// tiles it would walk in a batch of its own; a padding query (i < k_start[b]) sees the row's first own key: finite, and nobody reads it.
+template <typename T, bool RAGGED = false>
+__global__ __launch_bounds__(256) void attn_generic_kernel(AttnArgs<RAGGED> p) {
     __shared__ __attribute__((aligned(16))) float Ks[64 * GA_LD];
     __shared__ __attribute__((aligned(16))) float Vs[64 * GA_LD];
     constexpr int EPL = Vec16<T>::EPL;
     const int tid = threadIdx.x;
     const int ql = tid >> 4, kl = tid & 15;
     const int h = blockIdx.y, b = blockIdx.z;
-    const int Tk = p.Tk + (p.tk_dev ? *p.tk_dev : 0);
+    int k_first = 0;  // a constant 0 without RAGGED
+    if constexpr (RAGGED) k_first = p.k_start[b];
+    const int Tk = p.Tk + (p.tk_dev ? *p.tk_dev : 0) - k_first;
     const int qi = blockIdx.x * 16 + ql;
     const int qc = min(qi, p.Tq - 1);
     const int q_row0 = p.q_row_dev ? *p.q_row_dev : 0;
@@ -55,14 +69,20 @@ __global__ __launch_bounds__(256) void attn_generic_kernel(AttnParams p) {
 #pragma unroll
     for (int d = 0; d < 64; ++d) acc[d] = 0.f;
     float m = NEG_BIG, l = 0.f;
-    const int kmax = p.causal ? (qc + (Tk - p.Tq)) : (Tk - 1);  // last visible key of this query
+    int kmax = p.causal ? (qc + (Tk - p.Tq)) : (Tk - 1);  // last visible key of this query
+    if constexpr (RAGGED) kmax = max(kmax, 0);
     // staging role: key row srow, 16-element segment sseg
     const int srow = tid >> 2, sseg = (tid & 3) * 16;
     const T* kb = reinterpret_cast<const T*>(p.k) + b * p.k_bs + h * p.k_hs;
     const T* vb = reinterpret_cast<const T*>(p.v) + b * p.v_bs + h * p.v_hs;
+    if constexpr (RAGGED) {
+        kb += (int64_t)k_first * p.k_rs;
+        vb += (int64_t)k_first * p.v_rs;
+    }
     // causal: no query of this block sees keys beyond the block's last query
     const int q_last = min(blockIdx.x * 16 + 15, p.Tq - 1);
-    const int k_end = p.causal ? min(Tk, q_last + (Tk - p.Tq) + 1) : Tk;
+    int k_end = p.causal ? min(Tk, q_last + (Tk - p.Tq) + 1) : Tk;
+    if constexpr (RAGGED) k_end = max(k_end, 1);
     for (int k0 = 0; k0 < k_end; k0 += 64) {
         __syncthreads();
         {
@@ -269,8 +289,13 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_mfma_kernel(AttnParams p) {
 // which the next step reads again.  Round 4: the self-attention of a decode step takes WPH = 4 with NT off once the cache can
 // exceed 32 keys -- a wave of the one-wave form walks 32 keys per dependent round trip (7 of them at 224 keys: 6.6 us at 32
 // keys, 9.9 us at 64, growing), four waves take 128 per round trip.
-template <typename T, int WPH, bool NT = (WPH == 4)>
-__global__ __launch_bounds__(256) void decode_attn_kernel(AttnParams p) {
+// RAGGED (left-padded prompt rows, wipa_decode_attn_ragged): row b sees the keys k_start[b] .. Tk - 1 only.  The row's K / V base
+// pointers move up by k_start[b] rows and Tk shrinks by as much -- no mask: the row walks exactly the keys, in exactly the lane and
+// wave partition, it would walk if it were decoded alone with an unpadded prompt, and the clamped loads never touch a padding row.
+// A query at a padding column (below k_start[b]) sees its own key only.  A separate instantiation: the kernels of calls without
+// prompts keep their arguments and their code.
+template <typename T, int WPH, bool NT = (WPH == 4), bool RAGGED = false>
+__global__ __launch_bounds__(256) void decode_attn_kernel(AttnArgs<RAGGED> p) {
     constexpr int EPL = Vec16<T>::EPL;  // elements per 16-byte load
     constexpr int LPK = 64 / EPL;       // lanes per key row (64 dims)
     constexpr int G = 64 / LPK;         // keys per wave instruction
@@ -282,8 +307,11 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(AttnParams p) {
     if (WPH == 1 && h >= p.H) return;  // no workgroup barrier on this path
     const int kw = WPH == 4 ? wave : 0;
     const int g = lane / LPK, c = lane % LPK;
-    const int Tk = p.Tk + (p.tk_dev ? *p.tk_dev : 0);
+    const int Tk_all = p.Tk + (p.tk_dev ? *p.tk_dev : 0);
     const int q_row0 = p.q_row_dev ? *p.q_row_dev : 0;
+    int k_first = 0;  // a constant 0 without RAGGED
+    if constexpr (RAGGED) k_first = min(p.k_start[b], q_row0);
+    const int Tk = Tk_all - k_first;
     float qf[EPL];
     {
         const T* qp = reinterpret_cast<const T*>(p.q) + b * p.q_bs + (int64_t)q_row0 * p.q_rs + h * p.q_hs + c * EPL;
@@ -293,6 +321,10 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(AttnParams p) {
     }
     const T* Kb = reinterpret_cast<const T*>(p.k) + b * p.k_bs + h * p.k_hs + c * EPL;
     const T* Vb = reinterpret_cast<const T*>(p.v) + b * p.v_bs + h * p.v_hs + c * EPL;
+    if constexpr (RAGGED) {
+        Kb += (int64_t)k_first * p.k_rs;
+        Vb += (int64_t)k_first * p.v_rs;
+    }
     const int64_t k_rs = p.k_rs, v_rs = p.v_rs;
     float m = NEG_BIG, l = 0.f;
     float acc[EPL];
@@ -799,7 +831,7 @@ extern "C" int wipa_attention(const wipa_attn_desc* d, wipa_stream_t stream) {
     WIPA_REQUIRE(d->B > 0 && d->H > 0 && d->Tq > 0, "wipa_attention: bad shape");
     WIPA_REQUIRE(d->dtype == WIPA_F32 || d->dtype == WIPA_BF16, "wipa_attention: bad dtype %d", d->dtype);
     WIPA_REQUIRE(attn_strides_aligned(d), "wipa_attention: strides must keep 16-byte alignment");
-    AttnParams p;
+    AttnArgs<false> p;
     fill_attn_params(d, p);
     dim3 grid((d->Tq + 15) / 16, d->H, d->B);
     // float32 with whole 16-query fragments and no device-side offsets (teacher-forced decoder, fine-tune step): f32 MFMA kernel;
@@ -815,6 +847,27 @@ extern "C" int wipa_attention(const wipa_attn_desc* d, wipa_stream_t stream) {
         hipLaunchKernelGGL((attn_generic_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, p);
     else
         hipLaunchKernelGGL((attn_generic_kernel<__bf16>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    WIPA_LAUNCH_CHECK();
+    return WIPA_OK;
+}
+
+// the causal self-attention of a ragged prompt pass: always the f32-math VALU kernel (the f32 MFMA form declines device-side offsets,
+// and the rows' starts are one)
+extern "C" int wipa_attention_ragged(const wipa_attn_desc* d, const int32_t* starts_dev, wipa_stream_t stream) {
+    WIPA_REQUIRE(d && d->q && d->k && d->v && d->out && starts_dev, "wipa_attention_ragged: null pointer (starts_dev is required)");
+    WIPA_REQUIRE(d->B > 0 && d->H > 0 && d->Tq > 0, "wipa_attention_ragged: bad shape");
+    WIPA_REQUIRE(d->dtype == WIPA_F32 || d->dtype == WIPA_BF16, "wipa_attention_ragged: bad dtype %d", d->dtype);
+    WIPA_REQUIRE(attn_strides_aligned(d), "wipa_attention_ragged: strides must keep 16-byte alignment");
+    WIPA_REQUIRE(d->causal && d->Tq == d->Tk && !d->tk_dev && !d->q_row_dev && !d->lse,
+                 "wipa_attention_ragged: causal self-attention with Tq == Tk (Tq=%d Tk=%d), no device-side offsets, no lse", d->Tq, d->Tk);
+    AttnArgs<true> p;
+    fill_attn_params(d, p);
+    p.k_start = starts_dev;
+    dim3 grid((d->Tq + 15) / 16, d->H, d->B);
+    if (d->dtype == WIPA_F32)
+        hipLaunchKernelGGL((attn_generic_kernel<float, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL((attn_generic_kernel<__bf16, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;
 }
@@ -856,7 +909,7 @@ extern "C" int wipa_decode_attn(const wipa_attn_desc* d, wipa_stream_t stream) {
     WIPA_REQUIRE(d->B > 0 && d->H > 0 && d->Tq == 1, "wipa_decode_attn: one query row per (b,h) (Tq=%d)", d->Tq);
     WIPA_REQUIRE(d->dtype == WIPA_F32 || d->dtype == WIPA_BF16, "wipa_decode_attn: bad dtype %d", d->dtype);
     WIPA_REQUIRE(attn_strides_aligned(d), "wipa_decode_attn: strides must keep 16-byte alignment");
-    AttnParams p;
+    AttnArgs<false> p;
     fill_attn_params(d, p);
     // short caches (the growing self-attention cache, <= n_text_ctx keys): default-policy loads, and four waves per head
     // (WIPA_SELF_ATTN_WAVES=1: the one-wave-per-head form of rounds 1-3); long ones (cached cross K / V): 4 waves, nt loads
@@ -881,6 +934,25 @@ extern "C" int wipa_decode_attn(const wipa_attn_desc* d, wipa_stream_t stream) {
         else
             hipLaunchKernelGGL((decode_attn_kernel<__bf16, 4>), grid, dim3(256), 0, (hipStream_t)stream, p);
     }
+    WIPA_LAUNCH_CHECK();
+    return WIPA_OK;
+}
+
+// wipa_decode_attn for the growing self-attention cache of rows with left-padded prompts: row b sees keys starts_dev[b] .. Tk - 1
+extern "C" int wipa_decode_attn_ragged(const wipa_attn_desc* d, const int32_t* starts_dev, wipa_stream_t stream) {
+    WIPA_REQUIRE(d && d->q && d->k && d->v && d->out && starts_dev, "wipa_decode_attn_ragged: null pointer (starts_dev is required)");
+    WIPA_REQUIRE(d->B > 0 && d->H > 0 && d->Tq == 1, "wipa_decode_attn_ragged: one query row per (b,h) (Tq=%d)", d->Tq);
+    WIPA_REQUIRE(d->dtype == WIPA_F32 || d->dtype == WIPA_BF16, "wipa_decode_attn_ragged: bad dtype %d", d->dtype);
+    WIPA_REQUIRE(attn_strides_aligned(d), "wipa_decode_attn_ragged: strides must keep 16-byte alignment");
+    WIPA_REQUIRE(d->q_row_dev && d->tk_dev, "wipa_decode_attn_ragged: the query row and the key count come from the device (q_row_dev, tk_dev)");
+    AttnArgs<true> p;
+    fill_attn_params(d, p);
+    p.k_start = starts_dev;
+    dim3 grid(d->H, d->B);  // the four-wave, default-policy form the self-attention cache takes in wipa_decode_attn
+    if (d->dtype == WIPA_F32)
+        hipLaunchKernelGGL((decode_attn_kernel<float, 4, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL((decode_attn_kernel<__bf16, 4, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;
 }

@@ -153,16 +153,21 @@ __global__ __launch_bounds__(256) void add_slabs_layernorm_kernel(float* __restr
 }
 
 // ------------------------------------------------------------------ embedding
-template <typename TE>
+// RAGGED (left-padded prompt rows, wipa_embed_tokens_ragged): the token of column p takes the position row p - start[b] (padding
+// columns, below start[b], row 0); a separate instantiation, `start` is not looked at otherwise
+template <typename TE, bool RAGGED = false>
 __global__ __launch_bounds__(256) void embed_kernel(const int32_t* __restrict__ tokens, int64_t ld_tok, int T, int t_start,
                                                     const int32_t* __restrict__ pos_dev, const TE* __restrict__ emb,
-                                                    const float* __restrict__ pos_emb, float* __restrict__ x, int D) {
+                                                    const float* __restrict__ pos_emb, float* __restrict__ x, int D,
+                                                    const int32_t* __restrict__ start) {
     const int row = blockIdx.x;  // b*T + t
     const int b = row / T, t = row - b * T;
     const int p = t_start + (pos_dev ? *pos_dev : 0) + t;
     const int tok = tokens[(int64_t)b * ld_tok + p];
     const TE* e = emb + (int64_t)tok * D;
-    const float* pe = pos_emb + (int64_t)p * D;
+    int pp = p;
+    if constexpr (RAGGED) pp = max(p - start[b], 0);
+    const float* pe = pos_emb + (int64_t)pp * D;
     float* xr = x + (int64_t)row * D;
     for (int c = threadIdx.x * 4; c < D; c += 1024) {
         const f32x4 a = ld4<TE>(e + c);
@@ -433,18 +438,30 @@ struct TailParams {
     const float* part; int n_part;  // wipa_logits_greedy's partials [B][3][n_part] instead of the logits (part != nullptr)
 };
 
-template <typename TO>
-__global__ __launch_bounds__(256) void embed_layernorm_kernel(TailParams q) {
+// Ragged prompts (left-padded rows, one shared column counter): row b's own tokens start at column start[b] (int32 [B], device), so
+// its position-embedding index and its sampling counter are column - start[b].  A SEPARATE instantiation of every tail
+// (template <..., bool RAGGED>): the kernels of calls without prompts keep their arguments and their code.
+template <bool RAGGED>
+struct TailArgs : TailParams {};
+template <>
+struct TailArgs<true> : TailParams {
+    const int32_t* start;
+};
+
+template <typename TO, bool RAGGED = false>
+__global__ __launch_bounds__(256) void embed_layernorm_kernel(TailArgs<RAGGED> q) {
     __shared__ float s_red[4];
     const int b = blockIdx.x;
     const int p = *q.pos;
     const int tok = q.tokens[(int64_t)b * q.ld_tok + p];
-    row_embed_layernorm<TO>(threadIdx.x, tok, min(p, q.n_ctx - 1), q.emb, q.emb_dtype, q.emb_scale, q.pos_emb, q.x + (int64_t)b * q.D, q.ln_w,
+    int pp = min(p, q.n_ctx - 1);
+    if constexpr (RAGGED) pp = max(pp - q.start[b], 0);  // padding columns, below start[b], take row 0
+    row_embed_layernorm<TO>(threadIdx.x, tok, pp, q.emb, q.emb_dtype, q.emb_scale, q.pos_emb, q.x + (int64_t)b * q.D, q.ln_w,
                             q.ln_b, (TO*)q.y + (int64_t)b * q.D, q.D, q.eps, s_red);
 }
 
-template <typename TO>
-__global__ __launch_bounds__(GS_THREADS) void greedy_tail_kernel(TailParams q) {
+template <typename TO, bool RAGGED = false>
+__global__ __launch_bounds__(GS_THREADS) void greedy_tail_kernel(TailArgs<RAGGED> q) {
     __shared__ float s_v[GS_THREADS / 64];
     __shared__ int s_i[GS_THREADS / 64];
     __shared__ float s_sum[GS_THREADS / 64];
@@ -545,7 +562,9 @@ __global__ __launch_bounds__(GS_THREADS) void greedy_tail_kernel(TailParams q) {
         }
     }
     // the next step's input row: embedding of the chosen token at position p + 1, then the first block's LayerNorm
-    row_embed_layernorm<TO>(tid, next, min(p + 1, q.n_ctx - 1), q.emb, q.emb_dtype, q.emb_scale, q.pos_emb, q.x + (int64_t)b * q.D, q.ln_w,
+    int pp = min(p + 1, q.n_ctx - 1);  // the position-embedding row of the next column
+    if constexpr (RAGGED) pp = max(pp - q.start[b], 0);
+    row_embed_layernorm<TO>(tid, next, pp, q.emb, q.emb_dtype, q.emb_scale, q.pos_emb, q.x + (int64_t)b * q.D, q.ln_w,
                             q.ln_b, (TO*)q.y + (int64_t)b * q.D, q.D, q.eps, s_red);
     // position advance by the LAST workgroup: every thread of every workgroup read *pos at its start and has used it before
     // its workgroup's barrier above, i.e. before its counter increment -- no workgroup can still see the old position late.
@@ -590,10 +609,12 @@ struct RowPick {
 // log-sum-exp of the greedy branch (same sums, same order), so it is a fixed function of the row's logits.
 // RULES = false: the plain filtered row (r.tb = V: every column is on the text side, no history scan).
 // rec: the caller's sampling record (wipa.h: wipa_sample_record_bytes): u32 seed_lo, seed_hi, attempt, f32 1/T, then [lo, hi] per row.
+// p_own: the position word of the counter -- p, or with ragged prompts the row's OWN position p - start[b] (a draw must not depend on
+// the prompt width the row's neighbours set).
 template <bool RULES, bool SAMPLE>
 __device__ __forceinline__ RowPick row_pick(const float* __restrict__ row, const float* __restrict__ mask, int V, const int32_t* __restrict__ tk,
                                             int p, int n_init, int eot, RulesDev r, float* s_v, int* s_i, float* s_sum,
-                                            const uint32_t* __restrict__ rec, int b) {
+                                            const uint32_t* __restrict__ rec, int b, int p_own) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nq = V >> 2;
     // the row's loads go out first; the history scan below hides under them
@@ -712,7 +733,7 @@ __device__ __forceinline__ RowPick row_pick(const float* __restrict__ row, const
     if constexpr (SAMPLE) {
         const int dead_below = ts_mass > bt.v ? r.tb : 0;  // rule 5 killed the text side
         const float inv_t = __uint_as_float(rec[3]);
-        const uint32_t k0 = rec[0], k1 = rec[1], c1 = (uint32_t)p | (rec[2] << 16), c2 = rec[4 + 2 * b], c3 = rec[5 + 2 * b];
+        const uint32_t k0 = rec[0], k1 = rec[1], c1 = (uint32_t)p_own | (rec[2] << 16), c2 = rec[4 + 2 * b], c3 = rec[5 + 2 * b];
         MaxIdx mk{-INFINITY, 0x7fffffff};
         if (has_tail && ti >= dead_below && tailv > -INFINITY) {
             const Philox4 x = philox4x32_10((uint32_t)nq, c1, c2, c3, k0, k1);
@@ -753,7 +774,7 @@ __device__ __forceinline__ RowPick row_pick(const float* __restrict__ row, const
 
 __device__ __forceinline__ RowPick rules_row_pick(const float* __restrict__ row, const float* __restrict__ mask, int V, const int32_t* __restrict__ tk,
                                                   int p, int n_init, int eot, RulesDev r, float* s_v, int* s_i, float* s_sum) {
-    return row_pick<true, false>(row, mask, V, tk, p, n_init, eot, r, s_v, s_i, s_sum, nullptr, 0);
+    return row_pick<true, false>(row, mask, V, tk, p, n_init, eot, r, s_v, s_i, s_sum, nullptr, 0, p);
 }
 
 // wipa_timestamp_step: wipa_greedy_step with the rules, no embedding
@@ -782,8 +803,8 @@ __global__ __launch_bounds__(GS_THREADS) void timestamp_step_kernel(const float*
 
 // greedy_tail_kernel's row-scan branch with the rules: the same prompt walk, EOT latch, next embedding + LayerNorm (so the next
 // step's input row has the bits the plain tail would give for the same token) and position advance
-template <typename TO>
-__global__ __launch_bounds__(GS_THREADS) void timestamp_tail_kernel(TailParams q, RulesDev r) {
+template <typename TO, bool RAGGED = false>
+__global__ __launch_bounds__(GS_THREADS) void timestamp_tail_kernel(TailArgs<RAGGED> q, RulesDev r) {
     __shared__ float s_v[2 * GS_THREADS / 64];
     __shared__ int s_i[2 * GS_THREADS / 64];
     __shared__ float s_sum[2 * GS_THREADS / 64];
@@ -806,7 +827,9 @@ __global__ __launch_bounds__(GS_THREADS) void timestamp_tail_kernel(TailParams q
             if (next != q.eot) atomicAdd(q.not_done, 1);
         }
     }
-    row_embed_layernorm<TO>(tid, next, min(p + 1, q.n_ctx - 1), q.emb, q.emb_dtype, q.emb_scale, q.pos_emb, q.x + (int64_t)b * q.D, q.ln_w,
+    int pp = min(p + 1, q.n_ctx - 1);  // the position-embedding row of the next column
+    if constexpr (RAGGED) pp = max(pp - q.start[b], 0);
+    row_embed_layernorm<TO>(tid, next, pp, q.emb, q.emb_dtype, q.emb_scale, q.pos_emb, q.x + (int64_t)b * q.D, q.ln_w,
                             q.ln_b, (TO*)q.y + (int64_t)b * q.D, q.D, q.eps, s_red);
     if (tid == 0) {  // position advance by the last workgroup to arrive (see greedy_tail_kernel)
         const int arrived = atomicAdd(q.done_counter, 1);
@@ -819,12 +842,13 @@ __global__ __launch_bounds__(GS_THREADS) void timestamp_tail_kernel(TailParams q
 }
 
 // wipa_sample_step: timestamp_step_kernel with the draw (RULES = false: wipa_greedy_step with the draw)
-template <bool RULES>
+template <bool RULES, bool RAGGED = false>
 __global__ __launch_bounds__(GS_THREADS) void sample_step_kernel(const float* __restrict__ logits, int64_t ldl, int V,
                                                                  const float* __restrict__ mask_first, const float* __restrict__ mask_always,
                                                                  int32_t* __restrict__ tokens, int64_t ld_tok, const int32_t* __restrict__ pos_dev,
                                                                  int n_init, int eot, RulesDev r, const uint32_t* __restrict__ rec,
-                                                                 float* __restrict__ sum_logprobs, int32_t* __restrict__ not_done) {
+                                                                 float* __restrict__ sum_logprobs, int32_t* __restrict__ not_done,
+                                                                 const int32_t* __restrict__ start) {
     __shared__ float s_v[2 * GS_THREADS / 64];
     __shared__ int s_i[2 * GS_THREADS / 64];
     __shared__ float s_sum[2 * GS_THREADS / 64];
@@ -832,8 +856,10 @@ __global__ __launch_bounds__(GS_THREADS) void sample_step_kernel(const float* __
     const int p = *pos_dev;
     if (p + 1 < n_init) return;  // prompt token already in place
     int32_t* tk = tokens + (int64_t)b * ld_tok;
+    int p_own = p;  // the position word of the draw's counter: the row's own position (RAGGED: start is not looked at otherwise)
+    if constexpr (RAGGED) p_own = max(p - start[b], 0);
     const RowPick pick = row_pick<RULES, true>(logits + (int64_t)b * ldl, (p + 1 == n_init) ? mask_first : mask_always, V, tk, p, n_init, eot, r,
-                                               s_v, s_i, s_sum, rec, b);
+                                               s_v, s_i, s_sum, rec, b, p_own);
     if (threadIdx.x == 0) {
         const int prev = tk[p];
         const int next = (prev == eot) ? eot : pick.next;
@@ -844,8 +870,8 @@ __global__ __launch_bounds__(GS_THREADS) void sample_step_kernel(const float* __
 }
 
 // timestamp_tail_kernel with the draw: the tail of a decode step at a temperature above 0, with and without rules
-template <typename TO, bool RULES>
-__global__ __launch_bounds__(GS_THREADS) void sample_tail_kernel(TailParams q, RulesDev r, const uint32_t* __restrict__ rec) {
+template <typename TO, bool RULES, bool RAGGED = false>
+__global__ __launch_bounds__(GS_THREADS) void sample_tail_kernel(TailArgs<RAGGED> q, RulesDev r, const uint32_t* __restrict__ rec) {
     __shared__ float s_v[2 * GS_THREADS / 64];
     __shared__ int s_i[2 * GS_THREADS / 64];
     __shared__ float s_sum[2 * GS_THREADS / 64];
@@ -858,8 +884,10 @@ __global__ __launch_bounds__(GS_THREADS) void sample_tail_kernel(TailParams q, R
     if (p + 1 < q.n_init) {
         next = tk[p + 1];
     } else {
+        int p_own = p;  // the position word of the draw's counter: the row's own position
+        if constexpr (RAGGED) p_own = max(p - q.start[b], 0);
         const RowPick pick = row_pick<RULES, true>(q.logits + (int64_t)b * q.ldl, (p + 1 == q.n_init) ? q.mask_first : q.mask_always, q.V, tk, p,
-                                                   q.n_init, q.eot, r, s_v, s_i, s_sum, rec, b);
+                                                   q.n_init, q.eot, r, s_v, s_i, s_sum, rec, b, p_own);
         const int prev = tk[p];
         next = (prev == q.eot) ? q.eot : pick.next;
         if (tid == 0) {
@@ -868,7 +896,9 @@ __global__ __launch_bounds__(GS_THREADS) void sample_tail_kernel(TailParams q, R
             if (next != q.eot) atomicAdd(q.not_done, 1);
         }
     }
-    row_embed_layernorm<TO>(tid, next, min(p + 1, q.n_ctx - 1), q.emb, q.emb_dtype, q.emb_scale, q.pos_emb, q.x + (int64_t)b * q.D, q.ln_w,
+    int pp = min(p + 1, q.n_ctx - 1);  // the position-embedding row of the next column
+    if constexpr (RAGGED) pp = max(pp - q.start[b], 0);
+    row_embed_layernorm<TO>(tid, next, pp, q.emb, q.emb_dtype, q.emb_scale, q.pos_emb, q.x + (int64_t)b * q.D, q.ln_w,
                             q.ln_b, (TO*)q.y + (int64_t)b * q.D, q.D, q.eps, s_red);
     if (tid == 0) {  // position advance by the last workgroup to arrive (see greedy_tail_kernel)
         const int arrived = atomicAdd(q.done_counter, 1);
@@ -1045,15 +1075,31 @@ extern "C" int wipa_embed_tokens(const int32_t* tokens, int64_t ld_tok, int B, i
     hipStream_t s = (hipStream_t)stream;
     if (emb_dtype == WIPA_F32)
         hipLaunchKernelGGL((embed_kernel<float>), dim3(B * T), dim3(256), 0, s, tokens, ld_tok, T, t_start, pos_dev,
-                           (const float*)tok_emb, pos_emb, x, D);
+                           (const float*)tok_emb, pos_emb, x, D, (const int32_t*)nullptr);
     else if (emb_dtype == WIPA_BF16)
         hipLaunchKernelGGL((embed_kernel<__bf16>), dim3(B * T), dim3(256), 0, s, tokens, ld_tok, T, t_start, pos_dev,
-                           (const __bf16*)tok_emb, pos_emb, x, D);
+                           (const __bf16*)tok_emb, pos_emb, x, D, (const int32_t*)nullptr);
     else if (emb_dtype == WIPA_FP8_E4M3)
         hipLaunchKernelGGL(embed_fp8_kernel, dim3(B * T), dim3(256), 0, s, tokens, ld_tok, T, t_start, pos_dev,
                            (const unsigned char*)tok_emb, emb_scale, pos_emb, x, D);
     else
         WIPA_REQUIRE(false, "wipa_embed_tokens: bad dtype %d", emb_dtype);
+    WIPA_LAUNCH_CHECK();
+    return WIPA_OK;
+}
+
+extern "C" int wipa_embed_tokens_ragged(const int32_t* tokens, int64_t ld_tok, int B, int T, const int32_t* starts_dev, const void* tok_emb,
+                                        int emb_dtype, const float* pos_emb, float* x, int D, wipa_stream_t stream) {
+    WIPA_REQUIRE(tokens && starts_dev && tok_emb && pos_emb && x, "wipa_embed_tokens_ragged: null pointer (starts_dev is required)");
+    WIPA_REQUIRE(emb_dtype == WIPA_F32 || emb_dtype == WIPA_BF16, "wipa_embed_tokens_ragged: f32 or bf16 embedding (got %d)", emb_dtype);
+    WIPA_REQUIRE(D % 4 == 0 && B > 0 && T > 0, "wipa_embed_tokens_ragged: D must be a multiple of 4, B and T positive");
+    hipStream_t s = (hipStream_t)stream;
+    if (emb_dtype == WIPA_F32)
+        hipLaunchKernelGGL((embed_kernel<float, true>), dim3(B * T), dim3(256), 0, s, tokens, ld_tok, T, 0, (const int32_t*)nullptr,
+                           (const float*)tok_emb, pos_emb, x, D, starts_dev);
+    else
+        hipLaunchKernelGGL((embed_kernel<__bf16, true>), dim3(B * T), dim3(256), 0, s, tokens, ld_tok, T, 0, (const int32_t*)nullptr,
+                           (const __bf16*)tok_emb, pos_emb, x, D, starts_dev);
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;
 }
@@ -1091,7 +1137,7 @@ extern "C" int wipa_embed_layernorm(const int32_t* tokens, int64_t ld_tok, int B
     WIPA_REQUIRE(tokens && pos_dev && tok_emb && pos_emb && x && ln_w && ln_b && y && B > 0 && n_ctx > 0, "wipa_embed_layernorm: bad arguments");
     const int rc = tail_params_check("wipa_embed_layernorm", nullptr, 0, 0, nullptr, nullptr, D, emb_dtype, emb_scale);
     if (rc != WIPA_OK) return rc;
-    TailParams q = {};
+    TailArgs<false> q = {};
     q.tokens = const_cast<int32_t*>(tokens); q.ld_tok = ld_tok; q.pos = const_cast<int32_t*>(pos_dev); q.n_ctx = n_ctx;
     q.emb = tok_emb; q.emb_dtype = emb_dtype; q.emb_scale = emb_scale; q.pos_emb = pos_emb;
     q.x = x; q.ln_w = ln_w; q.ln_b = ln_b; q.y = y; q.D = D; q.eps = eps;
@@ -1111,7 +1157,7 @@ extern "C" int wipa_greedy_step_embed(const float* logits, int64_t ldl, int B, i
                      tok_emb && pos_emb && x && ln_w && ln_b && y && B > 0 && n_ctx > 0, "wipa_greedy_step_embed: bad arguments");
     const int rc = tail_params_check("wipa_greedy_step_embed", logits, V, ldl, mask_first, mask_always, D, emb_dtype, emb_scale);
     if (rc != WIPA_OK) return rc;
-    TailParams q = {};
+    TailArgs<false> q = {};
     q.logits = logits; q.ldl = ldl; q.V = V; q.mask_first = mask_first; q.mask_always = mask_always;
     q.tokens = tokens; q.ld_tok = ld_tok; q.pos = pos_dev; q.posd = posd_dev; q.done_counter = done_counter;
     q.n_init = n_init; q.eot = eot; q.n_ctx = n_ctx; q.sum_logprobs = sum_logprobs; q.not_done = not_done;
@@ -1133,7 +1179,7 @@ extern "C" int wipa_greedy_step_embed_partials(const float* partials, int n_part
                      ln_w && ln_b && y && B > 0 && n_ctx > 0, "wipa_greedy_step_embed_partials: bad arguments");
     const int rc = tail_params_check("wipa_greedy_step_embed_partials", nullptr, 0, 0, nullptr, nullptr, D, emb_dtype, emb_scale);
     if (rc != WIPA_OK) return rc;
-    TailParams q = {};
+    TailArgs<false> q = {};
     q.part = partials; q.n_part = n_parts;
     q.tokens = tokens; q.ld_tok = ld_tok; q.pos = pos_dev; q.posd = posd_dev; q.done_counter = done_counter;
     q.n_init = n_init; q.eot = eot; q.n_ctx = n_ctx; q.sum_logprobs = sum_logprobs; q.not_done = not_done;
@@ -1188,7 +1234,7 @@ extern "C" int wipa_timestamp_step_embed(const float* logits, int64_t ldl, int B
     RulesDev r;
     rc = rules_check("wipa_timestamp_step_embed", rules, logits, V, ldl, mask_first, mask_always, eot, &r);
     if (rc != WIPA_OK) return rc;
-    TailParams q = {};
+    TailArgs<false> q = {};
     q.logits = logits; q.ldl = ldl; q.V = V; q.mask_first = mask_first; q.mask_always = mask_always;
     q.tokens = tokens; q.ld_tok = ld_tok; q.pos = pos_dev; q.posd = posd_dev; q.done_counter = done_counter;
     q.n_init = n_init; q.eot = eot; q.n_ctx = n_ctx; q.sum_logprobs = sum_logprobs; q.not_done = not_done;
@@ -1249,10 +1295,29 @@ extern "C" int wipa_sample_step(const float* logits, int64_t ldl, int B, int V, 
     if (rc != WIPA_OK) return rc;
     if (rules)
         hipLaunchKernelGGL((sample_step_kernel<true>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, logits, ldl, V, mask_first, mask_always,
-                           tokens, ld_tok, pos_dev, n_init, eot, r, (const uint32_t*)sample, sum_logprobs, not_done);
+                           tokens, ld_tok, pos_dev, n_init, eot, r, (const uint32_t*)sample, sum_logprobs, not_done, (const int32_t*)nullptr);
     else
         hipLaunchKernelGGL((sample_step_kernel<false>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, logits, ldl, V, mask_first, mask_always,
-                           tokens, ld_tok, pos_dev, n_init, eot, r, (const uint32_t*)sample, sum_logprobs, not_done);
+                           tokens, ld_tok, pos_dev, n_init, eot, r, (const uint32_t*)sample, sum_logprobs, not_done, (const int32_t*)nullptr);
+    WIPA_LAUNCH_CHECK();
+    return WIPA_OK;
+}
+
+// wipa_sample_step for left-padded prompt rows: the draw's counter takes the row's own position *pos_dev - starts_dev[b]
+extern "C" int wipa_sample_step_ragged(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
+                                       int32_t* tokens, int64_t ld_tok, const int32_t* pos_dev, int n_init, int eot, const wipa_decode_rules* rules,
+                                       const void* sample, const int32_t* starts_dev, float* sum_logprobs, int32_t* not_done, wipa_stream_t stream) {
+    WIPA_REQUIRE(logits && mask_first && mask_always && tokens && pos_dev && starts_dev && sum_logprobs && not_done && B > 0 && n_init >= 1,
+                 "wipa_sample_step_ragged: bad arguments (starts_dev is required)");
+    RulesDev r;
+    const int rc = sample_check("wipa_sample_step_ragged", rules, sample, logits, V, ldl, mask_first, mask_always, eot, 0, &r);
+    if (rc != WIPA_OK) return rc;
+    if (rules)
+        hipLaunchKernelGGL((sample_step_kernel<true, true>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, logits, ldl, V, mask_first,
+                           mask_always, tokens, ld_tok, pos_dev, n_init, eot, r, (const uint32_t*)sample, sum_logprobs, not_done, starts_dev);
+    else
+        hipLaunchKernelGGL((sample_step_kernel<false, true>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, logits, ldl, V, mask_first,
+                           mask_always, tokens, ld_tok, pos_dev, n_init, eot, r, (const uint32_t*)sample, sum_logprobs, not_done, starts_dev);
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;
 }
@@ -1270,7 +1335,7 @@ extern "C" int wipa_sample_step_embed(const float* logits, int64_t ldl, int B, i
     RulesDev r;
     rc = sample_check("wipa_sample_step_embed", rules, sample, logits, V, ldl, mask_first, mask_always, eot, n_ctx, &r);
     if (rc != WIPA_OK) return rc;
-    TailParams q = {};
+    TailArgs<false> q = {};
     q.logits = logits; q.ldl = ldl; q.V = V; q.mask_first = mask_first; q.mask_always = mask_always;
     q.tokens = tokens; q.ld_tok = ld_tok; q.pos = pos_dev; q.posd = posd_dev; q.done_counter = done_counter;
     q.n_init = n_init; q.eot = eot; q.n_ctx = n_ctx; q.sum_logprobs = sum_logprobs; q.not_done = not_done;
@@ -1284,6 +1349,70 @@ extern "C" int wipa_sample_step_embed(const float* logits, int64_t ldl, int B, i
     else if (y_dtype == WIPA_BF16 && rules) hipLaunchKernelGGL((sample_tail_kernel<__bf16, true>), grid, block, 0, s, q, r, rec);
     else if (y_dtype == WIPA_BF16) hipLaunchKernelGGL((sample_tail_kernel<__bf16, false>), grid, block, 0, s, q, r, rec);
     else WIPA_REQUIRE(false, "wipa_sample_step_embed: bad dtype %d", y_dtype);
+    WIPA_LAUNCH_CHECK();
+    return WIPA_OK;
+}
+
+// ------------------------------------------------------------------ ragged prompts: the RAGGED instantiations of the tails
+extern "C" int wipa_embed_layernorm_ragged(const int32_t* tokens, int64_t ld_tok, int B, const int32_t* pos_dev, const int32_t* starts_dev,
+                                           const void* tok_emb, int emb_dtype, const float* emb_scale, const float* pos_emb, int n_ctx, float* x,
+                                           const float* ln_w, const float* ln_b, void* y, int y_dtype, int D, float eps, wipa_stream_t stream) {
+    WIPA_REQUIRE(tokens && pos_dev && starts_dev && tok_emb && pos_emb && x && ln_w && ln_b && y && B > 0 && n_ctx > 0,
+                 "wipa_embed_layernorm_ragged: bad arguments (starts_dev is required)");
+    const int rc = tail_params_check("wipa_embed_layernorm_ragged", nullptr, 0, 0, nullptr, nullptr, D, emb_dtype, emb_scale);
+    if (rc != WIPA_OK) return rc;
+    TailArgs<true> q = {};
+    q.tokens = const_cast<int32_t*>(tokens); q.ld_tok = ld_tok; q.pos = const_cast<int32_t*>(pos_dev); q.n_ctx = n_ctx;
+    q.emb = tok_emb; q.emb_dtype = emb_dtype; q.emb_scale = emb_scale; q.pos_emb = pos_emb;
+    q.x = x; q.ln_w = ln_w; q.ln_b = ln_b; q.y = y; q.D = D; q.eps = eps;
+    q.start = starts_dev;
+    if (y_dtype == WIPA_F32) hipLaunchKernelGGL((embed_layernorm_kernel<float, true>), dim3(B), dim3(256), 0, (hipStream_t)stream, q);
+    else if (y_dtype == WIPA_BF16) hipLaunchKernelGGL((embed_layernorm_kernel<__bf16, true>), dim3(B), dim3(256), 0, (hipStream_t)stream, q);
+    else WIPA_REQUIRE(false, "wipa_embed_layernorm_ragged: bad dtype %d", y_dtype);
+    WIPA_LAUNCH_CHECK();
+    return WIPA_OK;
+}
+
+extern "C" int wipa_step_embed_ragged(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
+                                      int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter,
+                                      int n_init, int eot, const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev,
+                                      float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype, const float* emb_scale,
+                                      const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y, int y_dtype,
+                                      int D, float eps, wipa_stream_t stream) {
+    WIPA_REQUIRE(logits && mask_first && mask_always && tokens && pos_dev && posd_dev && done_counter && starts_dev && sum_logprobs && not_done &&
+                     tok_emb && pos_emb && x && ln_w && ln_b && y && B > 0 && n_ctx > 0 && n_init >= 1,
+                 "wipa_step_embed_ragged: bad arguments (starts_dev is required)");
+    WIPA_REQUIRE(y_dtype == WIPA_F32 || y_dtype == WIPA_BF16, "wipa_step_embed_ragged: bad dtype %d", y_dtype);
+    int rc = tail_params_check("wipa_step_embed_ragged", logits, V, ldl, mask_first, mask_always, D, emb_dtype, emb_scale);
+    if (rc != WIPA_OK) return rc;
+    RulesDev r = {V, -1, -1};
+    if (sample) rc = sample_check("wipa_step_embed_ragged", rules, sample, logits, V, ldl, mask_first, mask_always, eot, n_ctx, &r);
+    else if (rules) rc = rules_check("wipa_step_embed_ragged", rules, logits, V, ldl, mask_first, mask_always, eot, &r);
+    if (rc != WIPA_OK) return rc;
+    TailArgs<true> q = {};
+    q.logits = logits; q.ldl = ldl; q.V = V; q.mask_first = mask_first; q.mask_always = mask_always;
+    q.tokens = tokens; q.ld_tok = ld_tok; q.pos = pos_dev; q.posd = posd_dev; q.done_counter = done_counter;
+    q.n_init = n_init; q.eot = eot; q.n_ctx = n_ctx; q.sum_logprobs = sum_logprobs; q.not_done = not_done;
+    q.emb = tok_emb; q.emb_dtype = emb_dtype; q.emb_scale = emb_scale; q.pos_emb = pos_emb;
+    q.x = x; q.ln_w = ln_w; q.ln_b = ln_b; q.y = y; q.D = D; q.eps = eps;
+    q.start = starts_dev;
+    const uint32_t* rec = (const uint32_t*)sample;
+    const dim3 grid(B), block(GS_THREADS);
+    hipStream_t s = (hipStream_t)stream;
+    const bool f32 = y_dtype == WIPA_F32;
+    if (sample && rules) {
+        if (f32) hipLaunchKernelGGL((sample_tail_kernel<float, true, true>), grid, block, 0, s, q, r, rec);
+        else hipLaunchKernelGGL((sample_tail_kernel<__bf16, true, true>), grid, block, 0, s, q, r, rec);
+    } else if (sample) {
+        if (f32) hipLaunchKernelGGL((sample_tail_kernel<float, false, true>), grid, block, 0, s, q, r, rec);
+        else hipLaunchKernelGGL((sample_tail_kernel<__bf16, false, true>), grid, block, 0, s, q, r, rec);
+    } else if (rules) {
+        if (f32) hipLaunchKernelGGL((timestamp_tail_kernel<float, true>), grid, block, 0, s, q, r);
+        else hipLaunchKernelGGL((timestamp_tail_kernel<__bf16, true>), grid, block, 0, s, q, r);
+    } else {
+        if (f32) hipLaunchKernelGGL((greedy_tail_kernel<float, true>), grid, block, 0, s, q);
+        else hipLaunchKernelGGL((greedy_tail_kernel<__bf16, true>), grid, block, 0, s, q);
+    }
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;
 }

@@ -371,13 +371,12 @@ __global__ void advance_pos_kernel(int32_t* pos, int64_t* posd, int d) {
     *posd = (int64_t)p * d;
 }
 
-__global__ void fill_tokens_kernel(int32_t* tokens, int64_t ld_tok, int B, int n_init, int i0, int i1, int i2, int i3,
-                                   const int32_t* extra) {
-    // rows get the prompt; prompts longer than 4 come through `extra` (device copy)
+__global__ void fill_tokens_kernel(int32_t* tokens, int64_t ld_tok, int B, int n_init, int i0, int i1, int i2, int i3) {
+    // every row gets the same prompt of up to four tokens; per-row prompts of any length come through wipa_decoder_begin_ragged
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const int first4[4] = {i0, i1, i2, i3};
-    for (int t = 0; t < n_init; ++t) tokens[(int64_t)b * ld_tok + t] = (t < 4 || !extra) ? first4[t & 3] : extra[t];
+    for (int t = 0; t < n_init; ++t) tokens[(int64_t)b * ld_tok + t] = first4[t & 3];
 }
 
 // one decoder step (all layers + logits + greedy update + position advance)
@@ -414,10 +413,14 @@ thread_local const wipa_decode_rules* t_rules = nullptr;
 // The sampling record of the call in progress (wipa_decoder_run_sample / _prefill_sample; NULL: temperature 0).  A sampling step
 // ends in wipa_sample_step_embed on the written logits, like a step with rules: the draw needs every alive column of the row.
 thread_local const void* t_sample = nullptr;
+// Ragged prompts (wipa_decoder_run_ragged): the device array int32 [B] of the rows' first own column (NULL: every row starts at
+// column 0, today's step).  With it the step's self-attention, its tail and its head are the RAGGED instantiations, and the tail
+// is the row scan on written logits, like a step with rules (the per-wave partials path stays what it is).
+thread_local const int32_t* t_starts = nullptr;
 bool logits_fused(const wipa_model_cfg* cfg, int B) {
     const char* e = getenv("WIPA_LOGITS_FUSED");  // read per call like the other step variants: part of the graph key
     const bool on = !(e && atoi(e) == 0);
-    return on && !t_rules && !t_sample && tail_fused() && cfg->dec_w_dtype == 0 && wipa_logits_greedy_supported(B, cfg->n_vocab, cfg->n_text_state, cfg->dtype);
+    return on && !t_rules && !t_sample && !t_starts && tail_fused() && cfg->dec_w_dtype == 0 && wipa_logits_greedy_supported(B, cfg->n_vocab, cfg->n_text_state, cfg->dtype);
 }
 int32_t* done_counter_of(char* st, const wipa_dec_layout& L) { return (int32_t*)(st + L.pos + 64); }  // zeroed with pos by wipa_decoder_begin
 
@@ -426,6 +429,10 @@ int enqueue_step_head(const wipa_model_cfg* cfg, const void* const* w, char* st,
     const DecScratch S = dec_scratch(cfg, B);
     char* sc = st + L.scratch;
     const void* const* lw0 = w + WIPA_DEC_GLOBAL;
+    if (t_starts)
+        return wipa_embed_layernorm_ragged((const int32_t*)(st + L.tokens), L.ld_tok, B, (const int32_t*)(st + L.pos), t_starts, w[0], emb_dtype(cfg),
+                                           emb_scale(cfg, w), (const float*)w[1], cfg->n_text_ctx, (float*)(sc + S.x), (const float*)lw0[0],
+                                           (const float*)lw0[1], sc + S.ln, cfg->dtype, cfg->n_text_state, 1e-5f, stream);
     return wipa_embed_layernorm((const int32_t*)(st + L.tokens), L.ld_tok, B, (const int32_t*)(st + L.pos), w[0], emb_dtype(cfg), emb_scale(cfg, w),
                                 (const float*)w[1], cfg->n_text_ctx, (float*)(sc + S.x), (const float*)lw0[0], (const float*)lw0[1], sc + S.ln,
                                 cfg->dtype, cfg->n_text_state, 1e-5f, stream);
@@ -501,7 +508,8 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
             a.v_bs = a.q_bs; a.v_rs = d; a.v_hs = 64;
             a.o_bs = d; a.o_rs = d; a.o_hs = 64;
             a.B = B; a.H = H; a.Tq = 1; a.Tk = 1; a.causal = 0; a.dtype = dt;
-            RT_CALL(wipa_decode_attn(&a, stream));
+            if (t_starts) RT_CALL(wipa_decode_attn_ragged(&a, t_starts, stream));  // row b sees keys starts[b] .. pos
+            else RT_CALL(wipa_decode_attn(&a, stream));
         }
         RT_CALL(residual_gemm(ao, d, lw[4], lw[5]));
         if (cross_fused) {
@@ -581,6 +589,13 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
     if (tail) {
         // greedy update + embedding of the chosen token + first LayerNorm of the NEXT position + position advance: one launch
         const void* const* lw0 = w + WIPA_DEC_GLOBAL;
+        if (t_starts) {  // the RAGGED tails: position embedding and sampling counter at the row's own position
+            RT_CALL(wipa_step_embed_ragged(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, posd,
+                                           done_counter_of(st, L), n_init, eot, t_rules, t_sample, t_starts, (float*)(st + L.sum_logprobs),
+                                           (int32_t*)(st + L.not_done), w[0], emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], nctx, x_first,
+                                           (const float*)lw0[0], (const float*)lw0[1], ln, dt, d, 1e-5f, stream));
+            return WIPA_OK;
+        }
         if (t_sample) {
             RT_CALL(wipa_sample_step_embed(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, posd,
                                            done_counter_of(st, L), n_init, eot, t_rules, t_sample, (float*)(st + L.sum_logprobs),
@@ -601,7 +616,7 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
                                        (const float*)lw0[1], ln, dt, d, 1e-5f, stream));
         return WIPA_OK;
     }
-    WIPA_REQUIRE(!t_rules && !t_sample, "decode step: the timestamp rules and sampling need the fused tail (WIPA_DECODE_TAIL=0 is set)");
+    WIPA_REQUIRE(!t_rules && !t_sample && !t_starts, "decode step: the timestamp rules, sampling and ragged prompts need the fused tail (WIPA_DECODE_TAIL=0 is set)");
     RT_CALL(wipa_greedy_step(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, n_init,
                              eot, (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), stream));
     hipLaunchKernelGGL(advance_pos_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pos, posd, d);
@@ -616,7 +631,7 @@ int enqueue_step_fused(const wipa_model_cfg* cfg, const void* const* w, char* st
     const int dt = cfg->dtype;
     const size_t e = wipa_dtype_size(dt);
     const int d = cfg->n_text_state, H = cfg->n_text_head, nctx = cfg->n_text_ctx, Ta = cfg->n_audio_ctx;
-    WIPA_REQUIRE(!t_rules && !t_sample, "decode step: the timestamp rules and sampling need the fused tail (WIPA_DECODE_FUSED=1 is set)");
+    WIPA_REQUIRE(!t_rules && !t_sample && !t_starts, "decode step: the timestamp rules, sampling and ragged prompts need the fused tail (WIPA_DECODE_FUSED=1 is set)");
     const DecScratch S = dec_scratch(cfg, B);
     char* sc = st + L.scratch;
     float* xa = (float*)(sc + S.x);
@@ -878,11 +893,15 @@ int state_fits(const char* who, const wipa_dec_layout& L, size_t state_bytes) {
 // The timestamp rules are baked into the captured tail's arguments: three more terms (timestamp_begin = 0: no rules).
 // The sampling record enters with its ADDRESS (NULL: temperature 0): seed, attempt, temperature and streams are read from it by
 // the replayed tail, so a new seed or temperature replays the same graph.
-typedef std::tuple<const void*, const void*, const void*, const void*, int, int, int, int, int, int, int, int, int, const void*> GraphKey;  // ..., generation, kind: 0 step, 1 prefill, 2 lean step (no logit stores), rules, sampling record
+// The starts array of a ragged call enters with its ADDRESS too (NULL: no prompts): the replayed kernels read the rows' starts from it.
+// The ragged prompt pass (kind 3 + 16 * (sot_col + 1)) bakes its workspace in as well: the last term (NULL otherwise).
+typedef std::tuple<const void*, const void*, const void*, const void*, int, int, int, int, int, int, int, int, int, const void*, const void*, const void*> GraphKey;  // ..., generation, kind: 0 step, 1 prefill, 2 lean step (no logit stores), rules, sampling record, starts, workspace
 // the rules of a call, for its scope: set on entry, cleared on every way out
 struct RulesScope {
-    explicit RulesScope(const wipa_decode_rules* r, const void* sample = nullptr) { t_rules = r; t_sample = sample; }
-    ~RulesScope() { t_rules = nullptr; t_sample = nullptr; }
+    explicit RulesScope(const wipa_decode_rules* r, const void* sample = nullptr, const int32_t* starts = nullptr) {
+        t_rules = r; t_sample = sample; t_starts = starts;
+    }
+    ~RulesScope() { t_rules = nullptr; t_sample = nullptr; t_starts = nullptr; }
 };
 // sampling lives in the fused step tail, like the rules: refused before anything is enqueued where the step cannot carry it
 int sample_servable(const char* who, const wipa_model_cfg* cfg, int B, const void* sample) {
@@ -890,6 +909,16 @@ int sample_servable(const char* who, const wipa_model_cfg* cfg, int B, const voi
     WIPA_REQUIRE(tail_fused() && !use_fused_step(cfg, B),
                  "%s: sampling lives in the fused step tail; WIPA_DECODE_TAIL=0 / WIPA_DECODE_FUSED=1 cannot serve it", who);
     WIPA_REQUIRE(cfg->n_vocab <= 65536 && cfg->n_text_ctx <= 65536, "%s: need n_vocab and n_text_ctx <= 65536 (n_vocab=%d)", who, cfg->n_vocab);
+    return WIPA_OK;
+}
+// ragged prompts live in the RAGGED instantiations of the unfused step's self-attention and tail: refused before anything is enqueued
+// where the step is another one, and on fp8 decoder tables (as wipa_decoder_logits refuses them)
+int starts_servable(const char* who, const wipa_model_cfg* cfg, int B, int n_init, const int32_t* starts_dev) {
+    if (!starts_dev) return WIPA_OK;
+    WIPA_REQUIRE(tail_fused() && !use_fused_step(cfg, B),
+                 "%s: starts_dev (ragged prompts) needs the unfused step with the fused tail; WIPA_DECODE_TAIL=0 / WIPA_DECODE_FUSED=1 cannot serve it", who);
+    WIPA_REQUIRE(cfg->dec_w_dtype == 0, "%s: starts_dev (ragged prompts) is not served on fp8 decoder tables (cfg.dec_w_dtype)", who);
+    WIPA_REQUIRE(n_init >= 1 && n_init <= cfg->n_text_ctx, "%s: prompt width P=%d outside 1..n_text_ctx=%d", who, n_init, cfg->n_text_ctx);
     return WIPA_OK;
 }
 // a configuration whose steps cannot carry the rules is refused before anything is enqueued: never decoded without them
@@ -994,8 +1023,39 @@ extern "C" int wipa_decoder_begin(const wipa_model_cfg* cfg, void* state, size_t
     int t4[4] = {0, 0, 0, 0};
     for (int i = 0; i < n_init; ++i) t4[i] = initial_tokens_host[i];
     hipLaunchKernelGGL(fill_tokens_kernel, dim3((B + 63) / 64), dim3(64), 0, s, (int32_t*)(st + L.tokens), L.ld_tok, B, n_init,
-                       t4[0], t4[1], t4[2], t4[3], (const int32_t*)nullptr);
+                       t4[0], t4[1], t4[2], t4[3]);
     WIPA_LAUNCH_CHECK();
+    return WIPA_OK;
+}
+
+extern "C" int wipa_decoder_begin_ragged(const wipa_model_cfg* cfg, void* state, size_t state_bytes, int B, const int32_t* tokens_host,
+                                         const int32_t* starts_host, int P, int32_t* starts_dev, wipa_stream_t stream) {
+    RT_CALL(cfg_check(cfg));
+    SplitScope split_scope(cfg);
+    WIPA_REQUIRE(state && tokens_host && starts_host && starts_dev && B > 0, "wipa_decoder_begin_ragged: null pointer / bad batch");
+    WIPA_REQUIRE(P >= 1 && P <= cfg->n_text_ctx, "wipa_decoder_begin_ragged: prompt width P=%d outside 1..n_text_ctx=%d", P, cfg->n_text_ctx);
+    WIPA_REQUIRE(cfg->dec_w_dtype == 0, "wipa_decoder_begin_ragged: ragged prompts are not served on fp8 decoder tables (cfg.dec_w_dtype)");
+    for (int b = 0; b < B; ++b)
+        WIPA_REQUIRE(starts_host[b] >= 0 && P - starts_host[b] >= 1, "wipa_decoder_begin_ragged: start[%d]=%d outside 0..P-1 (P=%d): a row holds 1..P tokens",
+                     b, starts_host[b], P);
+    for (int b = 0; b < B; ++b)
+        for (int t = 0; t < P; ++t)
+            WIPA_REQUIRE(tokens_host[(size_t)b * P + t] >= 0 && tokens_host[(size_t)b * P + t] < cfg->n_vocab,
+                         "wipa_decoder_begin_ragged: tokens[%d][%d]=%d outside the vocabulary of %d", b, t, tokens_host[(size_t)b * P + t], cfg->n_vocab);
+    const wipa_dec_layout L = dec_layout(cfg, B);
+    RT_CALL(state_fits("wipa_decoder_begin_ragged", L, state_bytes));
+    hipStream_t s = (hipStream_t)stream;
+    char* st = (char*)state;
+    const DecScratch S = dec_scratch(cfg, B);
+    RT_CALL(wipa_decode_fused_init());  // kernel attributes are set here, outside the stream capture of the step
+    RT_CALL(wipa_gemm_init());
+    WIPA_CHECK_HIP(hipMemsetAsync(st + L.tokens, 0, (size_t)B * L.ld_tok * 4, s));  // padding columns hold token 0
+    WIPA_CHECK_HIP(hipMemsetAsync(st + L.pos, 0, 512, s));  // pos and not_done
+    WIPA_CHECK_HIP(hipMemsetAsync(st + L.sum_logprobs, 0, (size_t)B * 4, s));
+    WIPA_CHECK_HIP(hipMemsetAsync(st + L.scratch + S.posd, 0, 8, s));
+    // the rows as the caller packed them (row b's own tokens in columns [start[b], P)), and the starts the step's kernels read
+    WIPA_CHECK_HIP(hipMemcpy2DAsync(st + L.tokens, (size_t)L.ld_tok * 4, tokens_host, (size_t)P * 4, (size_t)P * 4, (size_t)B, hipMemcpyHostToDevice, s));
+    WIPA_CHECK_HIP(hipMemcpyAsync(starts_dev, starts_host, (size_t)B * 4, hipMemcpyHostToDevice, s));
     return WIPA_OK;
 }
 
@@ -1014,12 +1074,24 @@ extern "C" int wipa_decoder_run_rules(const wipa_model_cfg* cfg, const void* con
 extern "C" int wipa_decoder_run_sample(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
                                        int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
                                        const wipa_decode_rules* rules, const void* sample, wipa_stream_t stream) {
+    return wipa_decoder_run_ragged(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, n_steps, use_graph, rules, sample, nullptr,
+                                   stream);
+}
+
+extern "C" int wipa_decoder_run_ragged(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
+                                       int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
+                                       const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, wipa_stream_t stream) {
     RT_CALL(cfg_check(cfg));
     SplitScope split_scope(cfg);
     WIPA_REQUIRE(w && state && mask_first && mask_always && B > 0 && n_steps >= 0, "wipa_decoder_run: bad arguments");
     RT_CALL(rules_servable("wipa_decoder_run_rules", cfg, B, eot, rules));
     RT_CALL(sample_servable("wipa_decoder_run_sample", cfg, B, sample));
-    RulesScope rules_scope(rules, sample);
+    RT_CALL(starts_servable("wipa_decoder_run_ragged", cfg, B, n_init, starts_dev));
+    // the position lives on the device: a call may carry the prompt walk (P - 1 steps) besides the new tokens, so what can be refused
+    // here is a step count that no position admits
+    WIPA_REQUIRE(!starts_dev || n_steps <= cfg->n_text_ctx - 1, "wipa_decoder_run_ragged: n_steps=%d with P=%d runs past n_text_ctx=%d", n_steps,
+                 n_init, cfg->n_text_ctx);
+    RulesScope rules_scope(rules, sample, starts_dev);
     W8Scope w8_scope(cfg, w);
     const wipa_dec_layout L = dec_layout(cfg, B);
     RT_CALL(state_fits("wipa_decoder_run", L, state_bytes));
@@ -1055,7 +1127,7 @@ extern "C" int wipa_decoder_run_sample(const wipa_model_cfg* cfg, const void* co
         hipGraphExec_t exec = nullptr;
         const GraphKey key(state, (const void*)w, (const void*)mask_first, (const void*)mask_always, B, n_init, eot, variant, cfg->weights_generation,
                            lean ? 2 : 0, rules ? rules->timestamp_begin : 0, rules ? rules->no_timestamps : 0,
-                           rules ? rules->max_initial_timestamp_index : 0, sample);
+                           rules ? rules->max_initial_timestamp_index : 0, sample, (const void*)starts_dev, (const void*)nullptr);
         {
             std::lock_guard<std::mutex> lk(g_graph_mu);
             auto it = g_graphs.find(key);
@@ -1129,7 +1201,197 @@ extern "C" int wipa_decoder_prefill_sample(const wipa_model_cfg* cfg, const void
     if (!use_graph || s == nullptr || !graphs_allowed()) return enqueue();
     hipGraphExec_t exec = nullptr;
     const GraphKey key(state, (const void*)w, (const void*)mask_first, (const void*)mask_always, B, n_init, eot, cfg->dtype * 2 + t_f32_split + 4 * decode_mode(cfg, B) + 16 * cfg->dec_w_dtype + 64 * cfg->dec_cross_absorbed * (absorbed_block_fused() ? 2 : 1) + 256 * (int)tail_fused() + 512 * (int)absorbed_merge_out() + 1024 * cfg->dec_cross_splits + 8192 * (int)(!use_fused_step(cfg, B) && logits_fused(cfg, B)) + 16384 * (cfg->dec_cross_absorbed ? wipa_cross_absorbed_loop_variant() : 0), cfg->weights_generation, 1,
-                       rules ? rules->timestamp_begin : 0, rules ? rules->no_timestamps : 0, rules ? rules->max_initial_timestamp_index : 0, sample);
+                       rules ? rules->timestamp_begin : 0, rules ? rules->no_timestamps : 0, rules ? rules->max_initial_timestamp_index : 0, sample, (const void*)nullptr, (const void*)nullptr);
+    {
+        std::lock_guard<std::mutex> lk(g_graph_mu);
+        auto it = g_graphs.find(key);
+        if (it != g_graphs.end()) exec = it->second;
+    }
+    if (!exec) {
+        hipGraph_t graph = nullptr;
+        WIPA_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
+        const int rc = enqueue();
+        const hipError_t ee = hipStreamEndCapture(s, &graph);
+        if (rc != WIPA_OK) {
+            if (graph) hipGraphDestroy(graph);
+            return rc;
+        }
+        WIPA_CHECK_HIP(ee);
+        WIPA_CHECK_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+        WIPA_CHECK_HIP(hipGraphDestroy(graph));
+        std::lock_guard<std::mutex> lk(g_graph_mu);
+        g_graphs[key] = exec;
+    }
+    WIPA_CHECK_HIP(hipGraphLaunch(exec, s));
+    return WIPA_OK;
+}
+
+// ------------------------------------------------------------------ ragged prompt pass
+// The whole prompt of every row (up to n_text_ctx columns, rows left-padded to the common width P) in ONE batched pass: the existing
+// prefill is sized for four rows per clip and runs one absorbed cross-attention launch per prompt position, neither of which scales
+// to P = 227.  This pass is the teacher-forced layer body (tf_layers: batched GEMMs over B * P rows, wipa_attention for both
+// attentions) with the differences a decode state needs: the q|k|v GEMM scatters into the blob's self-K/V cache at columns 0 .. P-1
+// (as enqueue_prefill does), embedding and self-attention take the rows' starts, the cross K/V come from the blob (cached form) or
+// are projected per layer from the blob's copy of the encoder output (absorbed form), and logits exist for two columns per clip only.
+namespace {
+struct PromptWs {
+    size_t sot_logits, x, ln, q, ao, h, ckv, total;
+};
+PromptWs prompt_ws(const wipa_model_cfg* c, int B, int P) {
+    const size_t e = wipa_dtype_size(c->dtype), d = c->n_text_state, M = (size_t)B * P;
+    PromptWs w;
+    size_t o = 0;
+    w.sot_logits = o; o += align256((size_t)B * round_up(c->n_vocab, 8) * 4);  // first: the caller reads it at offset 0
+    w.x = o;   o += align256(M * d * 4);
+    w.ln = o;  o += align256(M * d * e);
+    w.q = o;   o += align256(M * d * e);
+    w.ao = o;  o += align256(M * d * e);
+    w.h = o;   o += align256(M * 4 * d * e);
+    w.ckv = o; o += c->dec_cross_absorbed ? align256((size_t)B * 2 * c->n_text_head * c->n_audio_ctx * 64 * e) : 0;
+    w.total = o;
+    return w;
+}
+
+int enqueue_prefill_ragged(const wipa_model_cfg* cfg, const void* const* w, char* st, const wipa_dec_layout& L, int B, int P, int sot_col,
+                           int eot, const float* mask_first, const float* mask_always, const int32_t* starts, char* ws, const PromptWs& W,
+                           wipa_stream_t stream) {
+    const int dt = cfg->dtype;
+    const size_t e = wipa_dtype_size(dt);
+    const int d = cfg->n_text_state, H = cfg->n_text_head, nctx = cfg->n_text_ctx, Ta = cfg->n_audio_ctx, M = B * P;
+    const DecScratch S = dec_scratch(cfg, B);
+    float* x = (float*)(ws + W.x);
+    char* ln = ws + W.ln;
+    void* q = ws + W.q;
+    void* ao = ws + W.ao;
+    void* hb = ws + W.h;
+    int64_t* posd = (int64_t*)(st + L.scratch + S.posd);
+    int32_t* tokens = (int32_t*)(st + L.tokens);
+    int32_t* pos = (int32_t*)(st + L.pos);
+    RT_CALL(wipa_embed_tokens_ragged(tokens, L.ld_tok, B, P, starts, w[0], dt, (const float*)w[1], x, d, stream));
+    for (int l = 0; l < cfg->n_text_layer; ++l) {
+        const void* const* lw = w + WIPA_DEC_GLOBAL + WIPA_DEC_PER_LAYER * l;
+        char* skv = st + L.self_kv + (size_t)l * 3 * B * nctx * d * e;  // [3][B][nctx][d]
+        RT_CALL(wipa_layernorm(x, WIPA_F32, d, ln, dt, d, (const float*)lw[0], (const float*)lw[1], M, d, 1e-5f, stream));
+        {
+            // q|k|v of columns 0..P-1 -> slot[n / d][b][t][n % d] of the blob's cache
+            wipa_gemm_desc g;
+            memset(&g, 0, sizeof(g));
+            g.col_scale_n = 2 * d; g.col_scale = QK_SCALE;
+            g.rg_in = P; g.rg_valid = P; g.rg_stride = (int64_t)nctx * d;
+            g.cg_in = d; g.cg_stride = (int64_t)B * nctx * d;
+            RT_CALL(gemm(ln, d, lw[2], d, skv, d, M, 3 * d, d, dt, dt, (const float*)lw[3], 0, nullptr, stream, &g));
+        }
+        {
+            wipa_attn_desc a;
+            memset(&a, 0, sizeof(a));
+            const size_t slot = (size_t)B * nctx * d * e;
+            a.q = skv; a.k = skv + slot; a.v = skv + 2 * slot; a.out = ao;
+            a.q_bs = (int64_t)nctx * d; a.q_rs = d; a.q_hs = 64;
+            a.k_bs = a.q_bs; a.k_rs = d; a.k_hs = 64;
+            a.v_bs = a.q_bs; a.v_rs = d; a.v_hs = 64;
+            a.o_bs = (int64_t)P * d; a.o_rs = d; a.o_hs = 64;
+            a.B = B; a.H = H; a.Tq = P; a.Tk = P; a.causal = 1; a.dtype = dt;
+            RT_CALL(wipa_attention_ragged(&a, starts, stream));  // row b: column i sees columns starts[b] .. i
+        }
+        RT_CALL(gemm(ao, d, lw[4], d, x, d, M, d, d, dt, WIPA_F32, (const float*)lw[5], 0, x, stream));
+        RT_CALL(wipa_layernorm(x, WIPA_F32, d, ln, dt, d, (const float*)lw[6], (const float*)lw[7], M, d, 1e-5f, stream));
+        {
+            wipa_gemm_desc g;
+            memset(&g, 0, sizeof(g));
+            g.col_scale_n = d; g.col_scale = QK_SCALE;
+            RT_CALL(gemm(ln, d, lw[8], d, q, d, M, d, d, dt, dt, (const float*)lw[9], 0, nullptr, stream, &g));
+        }
+        const char* ckv = st + L.cross_kv + (size_t)l * B * 2 * H * Ta * 64 * e;  // the cached form's K / V of this layer
+        if (cfg->dec_cross_absorbed) {
+            // absorbed form: the blob holds the encoder output itself; this layer's K / V are projected from it into the workspace
+            wipa_gemm_desc g;
+            memset(&g, 0, sizeof(g));
+            g.col_scale_n = d; g.col_scale = QK_SCALE;
+            g.rg_in = Ta; g.rg_valid = Ta; g.rg_stride = (int64_t)2 * H * Ta * 64;
+            g.cg_in = 64; g.cg_stride = (int64_t)Ta * 64;
+            RT_CALL(gemm(st + L.cross_kv, d, lw[10], d, ws + W.ckv, 64, B * Ta, 2 * d, d, dt, dt, (const float*)lw[11], 0, nullptr, stream, &g));
+            ckv = ws + W.ckv;
+        }
+        {
+            wipa_attn_desc a;
+            memset(&a, 0, sizeof(a));
+            a.q = q; a.k = ckv; a.v = ckv + (size_t)H * Ta * 64 * e; a.out = ao;
+            a.q_bs = (int64_t)P * d; a.q_rs = d; a.q_hs = 64;
+            a.k_bs = (int64_t)2 * H * Ta * 64; a.k_rs = 64; a.k_hs = (int64_t)Ta * 64;
+            a.v_bs = a.k_bs; a.v_rs = 64; a.v_hs = a.k_hs;
+            a.o_bs = (int64_t)P * d; a.o_rs = d; a.o_hs = 64;
+            a.B = B; a.H = H; a.Tq = P; a.Tk = Ta; a.causal = 0; a.dtype = dt;
+            RT_CALL(wipa_attention(&a, stream));
+        }
+        RT_CALL(gemm(ao, d, lw[12], d, x, d, M, d, d, dt, WIPA_F32, (const float*)lw[13], 0, x, stream));
+        RT_CALL(wipa_layernorm(x, WIPA_F32, d, ln, dt, d, (const float*)lw[14], (const float*)lw[15], M, d, 1e-5f, stream));
+        RT_CALL(gemm(ln, d, lw[16], d, hb, 4 * d, M, 4 * d, d, dt, dt, (const float*)lw[17], 1, nullptr, stream));
+        RT_CALL(gemm(hb, 4 * d, lw[18], 4 * d, x, d, M, d, 4 * d, dt, WIPA_F32, (const float*)lw[19], 0, x, stream));
+    }
+    RT_CALL(wipa_layernorm(x, WIPA_F32, d, ln, dt, d, (const float*)w[2], (const float*)w[3], M, d, 1e-5f, stream));
+    // logits of two columns per clip: the last prompt column (rows (b, P-1) of ln, row stride P * d) into the state, and the
+    // <|startoftranscript|> column into the workspace (upstream's logits[:, sot_index], for no_speech_prob)
+    float* logits = (float*)(st + L.logits);
+    RT_CALL(gemm(ln + (size_t)(P - 1) * d * e, (int64_t)P * d, w[0], d, logits, L.ld_logits, B, cfg->n_vocab, d, dt, WIPA_F32, nullptr, 0,
+                 nullptr, stream));
+    if (sot_col >= 0)
+        RT_CALL(gemm(ln + (size_t)sot_col * d * e, (int64_t)P * d, w[0], d, ws + W.sot_logits, L.ld_logits, B, cfg->n_vocab, d, dt, WIPA_F32,
+                     nullptr, 0, nullptr, stream));
+    hipLaunchKernelGGL(set_pos_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pos, posd, P - 1, d);
+    if (t_sample)
+        RT_CALL(wipa_sample_step_ragged(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, P, eot, t_rules, t_sample,
+                                        starts, (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), stream));
+    else if (t_rules)
+        RT_CALL(wipa_timestamp_step(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, P, eot, t_rules,
+                                    (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), stream));
+    else
+        RT_CALL(wipa_greedy_step(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, P, eot,
+                                 (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), stream));
+    hipLaunchKernelGGL(advance_pos_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pos, posd, d);
+    WIPA_LAUNCH_CHECK();
+    return WIPA_OK;
+}
+}  // namespace
+
+extern "C" size_t wipa_decoder_prompt_workspace_bytes(const wipa_model_cfg* cfg, int B, int P) {
+    if (!cfg || B <= 0 || P <= 0) return 0;
+    return prompt_ws(cfg, B, P).total;
+}
+
+extern "C" int wipa_decoder_prefill_ragged(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int P,
+                                           int sot_col, int eot, const float* mask_first, const float* mask_always, int use_graph,
+                                           const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, void* workspace,
+                                           size_t workspace_bytes, wipa_stream_t stream) {
+    RT_CALL(cfg_check(cfg));
+    SplitScope split_scope(cfg);
+    WIPA_REQUIRE(w && state && mask_first && mask_always && B > 0, "wipa_decoder_prefill_ragged: bad arguments");
+    WIPA_REQUIRE(starts_dev && workspace, "wipa_decoder_prefill_ragged: starts_dev and workspace are required");
+    WIPA_REQUIRE(cfg->dec_w_dtype == 0, "wipa_decoder_prefill_ragged: the prompt pass runs on a bf16 / f32 weight table (cfg.dec_w_dtype: fp8 tables "
+                                        "serve the decode step)");
+    RT_CALL(rules_servable("wipa_decoder_prefill_ragged", cfg, B, eot, rules));
+    RT_CALL(sample_servable("wipa_decoder_prefill_ragged", cfg, B, sample));
+    RT_CALL(starts_servable("wipa_decoder_prefill_ragged", cfg, B, P, starts_dev));
+    WIPA_REQUIRE(P + 1 <= cfg->n_text_ctx, "wipa_decoder_prefill_ragged: P=%d leaves no column to generate in n_text_ctx=%d", P, cfg->n_text_ctx);
+    WIPA_REQUIRE(sot_col >= -1 && sot_col < P, "wipa_decoder_prefill_ragged: sot_col=%d outside -1..P-1 (P=%d)", sot_col, P);
+    const PromptWs W = prompt_ws(cfg, B, P);
+    WIPA_REQUIRE(workspace_bytes >= W.total, "wipa_decoder_prefill_ragged: workspace too small (%zu < %zu: wipa_decoder_prompt_workspace_bytes)",
+                 workspace_bytes, W.total);
+    RulesScope rules_scope(rules, sample, starts_dev);
+    const wipa_dec_layout L = dec_layout(cfg, B);
+    RT_CALL(state_fits("wipa_decoder_prefill_ragged", L, state_bytes));
+    char* st = (char*)state;
+    hipStream_t s = (hipStream_t)stream;
+    RT_CALL(init_before_capture(cfg));
+    WIPA_CHECK_HIP(hipMemsetAsync(done_counter_of(st, L), 0, sizeof(int32_t), s));
+    auto enqueue = [&]() -> int {
+        return enqueue_prefill_ragged(cfg, w, st, L, B, P, sot_col, eot, mask_first, mask_always, starts_dev, (char*)workspace, W, stream);
+    };
+    if (!use_graph || s == nullptr || !graphs_allowed()) return enqueue();
+    hipGraphExec_t exec = nullptr;
+    const GraphKey key(state, (const void*)w, (const void*)mask_first, (const void*)mask_always, B, P, eot,
+                       cfg->dtype * 2 + t_f32_split + 64 * cfg->dec_cross_absorbed, cfg->weights_generation, 3 + 16 * (sot_col + 1),
+                       rules ? rules->timestamp_begin : 0, rules ? rules->no_timestamps : 0, rules ? rules->max_initial_timestamp_index : 0, sample,
+                       (const void*)starts_dev, (const void*)workspace);
     {
         std::lock_guard<std::mutex> lk(g_graph_mu);
         auto it = g_graphs.find(key);

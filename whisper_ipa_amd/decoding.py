@@ -11,6 +11,16 @@ memory; the host only looks at the last token column every few steps to stop ear
 is a Gumbel-max over counter-based Philox noise in the step's tail (csrc/elementwise.hip: row_pick<.., SAMPLE>), a pure function of
 (seed, the row's stream, attempt, position, column) -- reproducible, and independent of the batch a row is decoded in.  Seed,
 attempt, 1 / T and the streams live in a small device record the replayed step graph reads; nothing of them is baked into it.
+
+Prompt conditioning (``DecodingOptions.prompt`` / ``prefix`` / ``prompts``; ``transcribe(condition_on_previous_text=True)``): every row's
+initial tokens are ``[sot_prev] + history + sot_sequence + prefix`` (upstream's ``_get_initial_tokens``), so the rows of one batch differ
+in length.  They are packed RIGHT-ALIGNED to one prompt width P (``pack_prompts``): row b's tokens sit in columns [P - n_b, P), the
+columns before them are padding, one position counter serves the batch and generation starts at column P for every row; the device
+kernels take the rows' first columns (``starts``) and give every row its own position embeddings, its own attention window and its
+own sampling counter (include/wipa.h: wipa_decoder_begin_ragged / wipa_decoder_run_ragged).  P is the longest row rounded up to a
+multiple of 16 where that leaves room to generate.  ONE documented deviation from upstream: ``sample_len`` is clamped to
+``n_text_ctx - P`` for the whole batch, so a row with a short prompt decoded next to one with the full 223-token history can generate
+448 - 227 = 221 tokens, not 224.  Without any prompt or prefix ``decode`` makes exactly the library calls it made before.
 """
 from __future__ import annotations
 
@@ -18,7 +28,7 @@ import os
 
 import ctypes as C
 import zlib
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import List, Optional, Sequence, Union
 
 import numpy as np
@@ -46,6 +56,7 @@ class DecodingOptions:
     without_timestamps: bool = False
     max_initial_timestamp: Optional[float] = 1.0
     fp16: bool = True
+    prompts: Optional[Sequence[Optional[Sequence[int]]]] = None  # one prompt (token ids, or None) PER ROW: what transcribe's conditioning uses
     seed: Optional[int] = None          # temperature > 0 needs one: sampling is opt-in and reproducible
     sample_streams: Optional[Sequence] = None  # per-row (lo, hi) Philox streams; default (row, 0)
     sample_attempt: int = 0             # which retry of the row this is (transcribe's fallback schedule index)
@@ -70,6 +81,9 @@ class GreedyTokens:
     n_steps: int              # generated positions
     sum_logprobs: np.ndarray  # [B]
     last_logits: Optional[torch.Tensor] = None  # [B, V] f32 logits of the last executed step (device)
+    n_init: Optional[int] = None               # ragged prompts: the common prompt width P (tokens[:, P:] is what was generated)
+    starts: Optional[np.ndarray] = None        # ragged prompts: [B] first own column of every row
+    sot_logits: Optional[torch.Tensor] = None  # ragged prompts: [B, V] f32 logits at the rows' <|startoftranscript|> column (device copy)
 
 
 class DecoderState:
@@ -122,6 +136,25 @@ class DecoderState:
             self._sample_rec = torch.empty(nbytes, dtype=torch.uint8, device=self.blob.device)
         self._sample_rec.copy_(torch.from_numpy(host))  # on the caller's library stream: after every step already enqueued
         return self._sample_rec
+
+    @property
+    def starts(self) -> torch.Tensor:
+        """the device array int32 [B] of the rows' first own columns (ragged prompts).  ONE buffer per state: the step graph is keyed
+        on its address, so every ragged decode of this state replays the same captured step."""
+        if getattr(self, "_starts", None) is None:
+            self._starts = torch.zeros(self.B, dtype=torch.int32, device=self.blob.device)
+        return self._starts
+
+    def prompt_workspace(self, pk, P: int) -> torch.Tensor:
+        """the caller-owned workspace of wipa_decoder_prefill_ragged for a prompt width of P; kept, and re-made only to grow (its
+        address is part of the prompt pass's graph key)"""
+        need = int(_lib.lib().wipa_decoder_prompt_workspace_bytes(C.byref(pk["cfg"]), self.B, P))
+        ws = getattr(self, "_prompt_ws", None)
+        if ws is None or ws.numel() < need:
+            stream().synchronize()  # nothing enqueued may still read the old one
+            with on_stream():
+                self._prompt_ws = ws = torch.empty(need, dtype=torch.uint8, device=self.blob.device)
+        return ws
 
     def release(self):
         _lib.lib().wipa_decoder_release(ptr(self.blob))
@@ -210,11 +243,15 @@ def timestamp_rules(tok: Tokenizer, max_initial_timestamp: Optional[float] = 1.0
     return _lib.DecodeRules(int(tok.timestamp_begin), int(tok.no_timestamps), index)
 
 
-def _dec_run(L, pk, st, B, n_init, eot, m_first, m_always, n, use_graph, rules, s, sample_rec=None):
+def _dec_run(L, pk, st, B, n_init, eot, m_first, m_always, n, use_graph, rules, s, sample_rec=None, starts=None):
     """wipa_decoder_run, or wipa_decoder_run_rules when the greedy update carries the timestamp rules; wipa_decoder_run_sample
-    (rules or not) when ``sample_rec``, the state's device sampling record, is given"""
+    (rules or not) when ``sample_rec``, the state's device sampling record, is given; wipa_decoder_run_ragged when ``starts``, the
+    state's device array of first columns, is given (``n_init`` is then the prompt width P)"""
     args = (C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, n_init, eot, ptr(m_first), ptr(m_always), n, int(use_graph))
-    if sample_rec is not None:
+    if starts is not None:
+        _lib.check(L.wipa_decoder_run_ragged(*args, C.byref(rules) if rules is not None else None,
+                                             ptr(sample_rec) if sample_rec is not None else None, ptr(starts), sptr(s)), "wipa_decoder_run_ragged")
+    elif sample_rec is not None:
         _lib.check(L.wipa_decoder_run_sample(*args, C.byref(rules) if rules is not None else None, ptr(sample_rec), sptr(s)),
                    "wipa_decoder_run_sample")
     elif rules is None:
@@ -324,6 +361,159 @@ def greedy_decode_tokens(model, audio_features: torch.Tensor, initial_tokens: Se
     return GreedyTokens(toks, n_steps, slp, last_logits)
 
 
+# ---------------------------------------------------------------- prompt conditioning: per-row prompts
+PROMPT_WIDTH_MULTIPLE = 16  # P is rounded up to it: at most n_text_ctx / 16 captured step graphs per state (P is in the graph key)
+
+
+def _token_ids(tok: Tokenizer, text_or_ids) -> List[int]:
+    """upstream: a string becomes ``encode(" " + s.strip())``, a list of ids is taken as it is"""
+    if isinstance(text_or_ids, str):
+        return [int(t) for t in tok.encode(" " + text_or_ids.strip())]
+    return [int(t) for t in text_or_ids]
+
+
+def initial_tokens(tok: Tokenizer, sot_sequence: Sequence[int], prompt, prefix, n_ctx: int, sample_len: int) -> List[int]:
+    """DecodingTask._get_initial_tokens of upstream, literally: ``sot_sequence + prefix[-(n_ctx // 2 - sample_len):]`` (a bound of
+    0 keeps everything: ``[-0:]``), and with a non-empty prompt ``[sot_prev] + prompt[-(n_ctx // 2 - 1):]`` in front of it."""
+    tokens = [int(t) for t in sot_sequence]
+    if prefix is not None and len(prefix):
+        prefix_tokens = _token_ids(tok, prefix)
+        max_prefix_len = n_ctx // 2 - sample_len
+        prefix_tokens = prefix_tokens[-max_prefix_len:]
+        tokens = tokens + prefix_tokens
+    if prompt is not None and len(prompt):
+        prompt_tokens = _token_ids(tok, prompt)
+        tokens = [int(tok.sot_prev)] + prompt_tokens[-(n_ctx // 2 - 1):] + tokens
+    return tokens
+
+
+def resolve_prompts(options: DecodingOptions, B: int) -> Optional[List]:
+    """the prompt of every row (string, ids or None) from ``options.prompt`` (one for all rows) or ``options.prompts`` (one per
+    row); None when no row has one.  Giving both is a ValueError."""
+    if options.prompt is not None and options.prompts is not None:
+        raise ValueError("DecodingOptions: give prompt (one for all rows) or prompts (one per row), not both")
+    if options.prompts is not None:
+        rows = list(options.prompts)
+        if len(rows) != B:
+            raise ValueError(f"DecodingOptions.prompts: {len(rows)} prompts for {B} rows")
+    else:
+        rows = [options.prompt] * B
+    rows = [r if (r is not None and len(r)) else None for r in rows]
+    return rows if any(r is not None for r in rows) else None
+
+
+def pack_prompts(rows: Optional[Sequence[Sequence[int]]], n_ctx: int, sample_len: int, pad_to: Optional[int] = None):
+    """Per-row initial tokens -> ``(tokens [B, P] int32, starts [B] int32, P)``: row b right-aligned in columns [P - n_b, P), token 0
+    before them.  P = the longest row rounded up to a multiple of 16, unless that would leave fewer than ``min(sample_len, n_ctx -
+    longest)`` columns to generate in: then P = longest.  ``pad_to``: this P instead (a row decoded alone at the width of a batch).
+    ``rows`` None (no row has a prompt or a prefix): None -- there is no ragged path to take."""
+    if rows is None:
+        return None
+    rows = [[int(t) for t in r] for r in rows]
+    if not rows or any(len(r) < 1 for r in rows):
+        raise ValueError("pack_prompts: every row holds at least one initial token")
+    longest = max(len(r) for r in rows)
+    if longest > n_ctx:
+        raise ValueError(f"pack_prompts: {longest} initial tokens exceed n_text_ctx = {n_ctx}")
+    if pad_to is not None:
+        P = int(pad_to)
+        if P < longest or P > n_ctx:
+            raise ValueError(f"pack_prompts: pad_to = {P} outside {longest}..{n_ctx}")
+    else:
+        P = -(-longest // PROMPT_WIDTH_MULTIPLE) * PROMPT_WIDTH_MULTIPLE
+        if n_ctx - P < min(sample_len, n_ctx - longest):
+            P = longest
+    tokens = np.zeros((len(rows), P), dtype=np.int32)
+    starts = np.zeros(len(rows), dtype=np.int32)
+    for b, r in enumerate(rows):
+        starts[b] = P - len(r)
+        tokens[b, P - len(r):] = r
+    return tokens, starts, P
+
+
+def ragged_decode_tokens(model, audio_features: torch.Tensor, rows: Sequence[Sequence[int]], suppress_always: Sequence[int],
+                         suppress_first: Sequence[int], eot: int, max_new_tokens: Optional[int] = None, stop_on_eot: bool = True,
+                         use_graph: bool = True, check_every: int = 8, rules=None, sample: Optional[Sampling] = None,
+                         pad_to: Optional[int] = None, sot_back: Optional[int] = None) -> GreedyTokens:
+    """``greedy_decode_tokens`` for rows with their OWN initial tokens (``rows[b]``: [sot_prev] + history + sot_sequence + prefix), packed
+    by ``pack_prompts``.  ``tokens`` of the result are [B, P + n_steps] with the padding in front; ``n_init`` = P.  The prompt goes through
+    one batched pass (wipa_decoder_prefill_ragged); with WIPA_NO_PREFILL=1 it is walked column by column by the replayed decode step,
+    which is what the batched pass is tested against.  ``sot_back``: the rows' <|startoftranscript|> sits ``sot_back`` columns before P
+    (len(sot_sequence) + len(prefix)); the unfiltered logits of that column come back as ``sot_logits`` (upstream's
+    ``logits[:, sot_index]`` for no_speech_prob).  ``max_new_tokens`` is clamped to n_text_ctx - P."""
+    L = _lib.lib()
+    B = audio_features.shape[0]
+    n_ctx = model.dims.n_text_ctx
+    if getattr(model, "_fp8", None):
+        raise NotImplementedError("prompt conditioning is not implemented for an fp8-quantised model: the ragged decode step runs on "
+                                  "bf16 / f32 decoder tables")
+    if len(rows) != B:
+        raise ValueError(f"ragged_decode_tokens: {len(rows)} rows of initial tokens for {B} clips")
+    if max_new_tokens is None:
+        max_new_tokens = n_ctx // 2
+    tokens_h, starts_h, P = pack_prompts(rows, n_ctx, max_new_tokens, pad_to)
+    max_new_tokens = min(max_new_tokens, n_ctx - P)
+    if max_new_tokens < 1:
+        raise ValueError(f"ragged_decode_tokens: a prompt width of {P} leaves no room to generate in n_text_ctx = {n_ctx}")
+    if sot_back is not None and not 1 <= sot_back <= P - int(starts_h.max()):
+        raise ValueError(f"ragged_decode_tokens: sot_back = {sot_back} outside the shortest row")
+    pk = _packed_for(model, B, max_new_tokens)
+    st = _state_for(model, B, pk)
+    m_always = _mask(model, suppress_always)
+    m_first = _mask(model, list(suppress_always) + list(suppress_first))
+    tokens_h = np.ascontiguousarray(tokens_h, dtype=np.int32)
+    starts_h = np.ascontiguousarray(starts_h, dtype=np.int32)
+    i32p = C.POINTER(C.c_int32)
+    total = (P - 1) + max_new_tokens
+    done_steps = 0
+    sot_logits = None
+    with on_stream() as s:
+        feats = audio_features.to(device=model.device, dtype=model.dtype).contiguous()
+        _lib.check(L.wipa_decoder_set_audio(C.byref(pk["cfg"]), pk["dec_tab"], ptr(feats), ptr(st.blob), st.blob.numel(), B, sptr(s)),
+                   "wipa_decoder_set_audio")
+        starts = st.starts
+        _lib.check(L.wipa_decoder_begin_ragged(C.byref(pk["cfg"]), ptr(st.blob), st.blob.numel(), B, tokens_h.ctypes.data_as(i32p),
+                                               starts_h.ctypes.data_as(i32p), P, ptr(starts), sptr(s)), "wipa_decoder_begin_ragged")
+        rec = st.sample_record(sample) if sample is not None else None
+        if P >= 2 and os.environ.get("WIPA_NO_PREFILL") != "1":  # the whole prompt and the first new token in one batched pass
+            ws = st.prompt_workspace(pk, P)
+            _lib.check(L.wipa_decoder_prefill_ragged(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, P,
+                                                     P - sot_back if sot_back is not None else -1, eot, ptr(m_first), ptr(m_always),
+                                                     int(use_graph), C.byref(rules) if rules is not None else None,
+                                                     ptr(rec) if rec is not None else None, ptr(starts), ptr(ws), ws.numel(), sptr(s)),
+                       "wipa_decoder_prefill_ragged")
+            if sot_back is not None:  # the pass leaves the <|startoftranscript|> column's logits at the head of its workspace
+                ld = st.layout.ld_logits
+                sot_logits = ws[: B * ld * 4].view(torch.float32).view(B, ld)[:, : model.dims.n_vocab].clone()
+            done_steps = P
+        elif sot_back is not None:  # the steps up to the <|startoftranscript|> column: its logits are those of the call's last step
+            n = P - sot_back + 1
+            _dec_run(L, pk, st, B, P, eot, m_first, m_always, n, use_graph, rules, s, rec, starts)
+            sot_logits = st.logits.clone()
+            done_steps = n
+        while done_steps < total:
+            n = min(check_every if stop_on_eot else total, total - done_steps)
+            if done_steps < P - 1:  # the rest of the prompt walk rides with the first generated columns
+                n = min(total - done_steps, n + (P - 1 - done_steps))
+            _dec_run(L, pk, st, B, P, eot, m_first, m_always, n, use_graph, rules, s, rec, starts)
+            done_steps += n
+            if stop_on_eot and done_steps >= P:
+                last = st.tokens[:, done_steps].cpu()  # synchronises the library stream
+                if bool((last == eot).all()):
+                    break
+        toks = st.tokens[:, : done_steps + 1].cpu().numpy().astype(np.int64)  # synchronises: the host arrays of begin are consumed
+        slp = st.sum_logprobs.cpu().numpy().copy()
+        last_logits = st.logits
+    n_steps = done_steps - (P - 1)
+    if stop_on_eot:
+        body = toks[:, P:]
+        all_eot = (body == eot).all(axis=0)
+        if all_eot.any():
+            n_steps = int(np.argmax(all_eot)) + 1
+            toks = toks[:, : P + n_steps]
+    return GreedyTokens(toks, n_steps, slp, last_logits, n_init=P, starts=starts_h.copy(), sot_logits=sot_logits)
+
+
 def forced_decode_logits(model, audio_features: torch.Tensor, tokens: np.ndarray, n_init: int, suppress_always: Sequence[int],
                          suppress_first: Sequence[int], eot: int, use_graph: bool = True, rules=None):
     """The KV-cached decode-step path (prompt prefill + replayed step graph -- the kernels greedy_decode_tokens runs) driven
@@ -420,6 +610,8 @@ def _refuse_unsupported(options: DecodingOptions) -> None:
         raise ValueError(f"temperature must be >= 0, got {options.temperature}")
     if not options.without_timestamps and (options.prompt is not None or options.prefix is not None):
         raise NotImplementedError("prompt / prefix conditioning is not implemented on the timestamp path")
+    if getattr(options, "prompts", None) is not None:
+        raise NotImplementedError("prompts (per-row prompt conditioning) is served by decode() only")
 
 
 def decode(model, mel: torch.Tensor, options: DecodingOptions = DecodingOptions(), **kwargs):
@@ -427,7 +619,14 @@ def decode(model, mel: torch.Tensor, options: DecodingOptions = DecodingOptions(
     features [B,1500,d] / [1500,d]; returns a DecodingResult or a list of them."""
     if kwargs:
         options = DecodingOptions(**{**options.__dict__, **kwargs})
-    _refuse_unsupported(options)
+    # decode() serves prompts itself: they are resolved first and the refusals see the options without them
+    n_rows = 1 if mel.dim() == 2 else mel.shape[0]
+    prompts = resolve_prompts(options, n_rows)
+    prefix = options.prefix if (options.prefix is not None and len(options.prefix)) else None
+    _refuse_unsupported(replace(options, prompt=None, prefix=None, prompts=None))
+    if (prompts is not None or prefix is not None) and getattr(model, "_fp8", None):
+        raise NotImplementedError("prompt / prefix conditioning is not implemented for an fp8-quantised model: the ragged decode step "
+                                  "runs on bf16 / f32 decoder tables")
     single = mel.dim() == 2
     if single:
         mel = mel[None]
@@ -462,7 +661,7 @@ def decode(model, mel: torch.Tensor, options: DecodingOptions = DecodingOptions(
         from .tokenizer import LANGUAGES
         languages = [LANGUAGES[int(t) - tok.sot - 1] for t in lang_tokens]
         lang_probs = [dict(zip(LANGUAGES[: tok.num_languages], p.tolist())) for p in probs]
-    elif timed:
+    elif timed and prompts is None and prefix is None:
         no_speech = [float(v) for v in no_speech_probs(model, feats, tok)]
     always, first = _suppress_lists(options, tok)
     sample_len = options.sample_len or d.n_text_ctx // 2
@@ -481,9 +680,21 @@ def decode(model, mel: torch.Tensor, options: DecodingOptions = DecodingOptions(
         sub = feats[rows] if len(rows) != B else feats
         sample = None if streams is None else Sampling(int(options.seed), float(options.temperature), [streams[i] for i in rows],
                                                        int(options.sample_attempt))
-        g = greedy_decode_tokens(model, sub, init, always, first, tok.eot, max_new_tokens=sample_len, rules=rules, sample=sample)
+        if prompts is None and prefix is None:  # no row has a prompt: the path without prompts, call for call
+            g = greedy_decode_tokens(model, sub, init, always, first, tok.eot, max_new_tokens=sample_len, rules=rules, sample=sample)
+            n_init = len(init)
+        else:
+            own = [initial_tokens(tok, init, prompts[i] if prompts is not None else None, prefix, d.n_text_ctx, sample_len) for i in rows]
+            sot_back = len(initial_tokens(tok, init, None, prefix, d.n_text_ctx, sample_len))  # sot_sequence + prefix: the same for every row
+            g = ragged_decode_tokens(model, sub, own, always, first, tok.eot, max_new_tokens=sample_len, rules=rules, sample=sample,
+                                     sot_back=sot_back if timed else None)
+            n_init = g.n_init
+            if timed:  # upstream's logits[:, sot_index] of the prompted pass
+                nsp = _no_speech_from(g.sot_logits, tok)
+                for j, i in enumerate(rows):
+                    no_speech[i] = float(nsp[j])
         for j, i in enumerate(rows):
-            row = g.tokens[j, len(init):].tolist()
+            row = g.tokens[j, n_init:].tolist()
             if tok.eot in row:
                 row = row[: row.index(tok.eot)]
             text = tok.decode([t for t in row if t < tok.timestamp_begin]).strip()  # tokens keeps the timestamps, text does not

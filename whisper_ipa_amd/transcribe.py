@@ -21,10 +21,17 @@ What differs from upstream, on purpose:
     ``timing.find_alignment`` call from the encoder features their decode left (no second log-mel, no second encoder pass), and
     every segment gains ``"words"``.  Upstream's word-duration heuristics, its snapping of segment bounds to the words and of
     ``seek`` to the last word are left out (timing.py says why), so segments and seeks are those of ``word_timestamps=False``.
-    An fp8-quantised model is refused before anything is decoded.
+    An fp8-quantised model is refused before anything is decoded;
+  * ``condition_on_previous_text`` defaults to False.  With True -- or with an ``initial_prompt`` -- every file keeps upstream's
+    bookkeeping (``all_tokens``, ``prompt_reset_since``; a window decoded above temperature 0.5 resets the prompt, a skipped window
+    changes nothing) and the rows of a round carry their OWN prompts, of different lengths, through ``decode(prompts=...)``: the
+    ragged decode of decoding.py.  One deviation comes with batching (decoding.py's docstring): ``sample_len`` is clamped to
+    ``n_text_ctx`` minus the round's common prompt width, so a window next to one with a full 223-token history generates at most
+    221 tokens, not 224.
 """
 from __future__ import annotations
 
+import inspect
 import warnings
 from typing import Callable, List, Optional, Sequence, Tuple, Union
 
@@ -74,10 +81,6 @@ def split_segments(tokens: Sequence[int], tb: int, time_offset: float, segment_s
 
 def _refuse(condition_on_previous_text, initial_prompt, word_timestamps, clip_timestamps, hallucination_silence_threshold, temperature,
             decode_options, can_align: bool = False) -> None:
-    if condition_on_previous_text:
-        raise NotImplementedError("condition_on_previous_text=True (prompt conditioning) is not implemented")
-    if initial_prompt is not None:
-        raise NotImplementedError("initial_prompt (prompt conditioning) is not implemented")
     if word_timestamps and not can_align:
         raise NotImplementedError("word_timestamps=True is not implemented without a model: a custom decode_fn needs an align_fn")
     if clip_timestamps not in (None, "0", [0], (0,)):
@@ -92,6 +95,29 @@ def _refuse(condition_on_previous_text, initial_prompt, word_timestamps, clip_ti
             raise NotImplementedError(f"{k} is not implemented")
 
 
+def _takes_prompts(fn: Callable) -> bool:
+    try:
+        params = inspect.signature(fn).parameters
+    except (TypeError, ValueError):
+        return False
+    return "prompts" in params or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values())
+
+
+def _refuse_conditioning(condition_on_previous_text, initial_prompt, model, decode_fn, fallback_fn) -> None:
+    """prompt conditioning needs decoders that take the rows' prompts: a custom one without a ``prompts`` parameter is refused (the
+    pattern of ``align_fn`` for word timestamps), and so is an fp8-quantised model"""
+    if not condition_on_previous_text and initial_prompt is None:
+        return
+    name = "condition_on_previous_text=True" if condition_on_previous_text else "initial_prompt"
+    for what, fn in (("decode_fn", decode_fn), ("fallback_fn", fallback_fn)):
+        if fn is not None and not _takes_prompts(fn):
+            raise NotImplementedError(f"{name} is not implemented for a custom {what} without a prompts= parameter: every round's rows "
+                                      f"carry their own prompts ({what}(..., prompts=[...]))")
+    if decode_fn is None and getattr(model, "_fp8", None):
+        raise NotImplementedError(f"{name} is not implemented for an fp8-quantised model: the ragged decode step runs on bf16 / f32 "
+                                  "decoder tables")
+
+
 def _model_decoder(model, decode_options: dict) -> Callable:
     """the default ``decode_fn``: windows [n, 480000] f32 + per-row languages (None: detect) -> DecodingResults, through the
     package's log-mel, encoder and ``decode(without_timestamps=False)``; rows are grouped by language"""
@@ -100,27 +126,35 @@ def _model_decoder(model, decode_options: dict) -> Callable:
     from . import audio as A
     from .decoding import DecodingOptions, decode
 
-    def run(windows: np.ndarray, languages: List[Optional[str]]):
+    def with_prompts(opts: dict, prompts, rows) -> dict:
+        """the rows' own prompts (token ids; an empty one is no prompt), when the caller conditions on previous text"""
+        if prompts is not None and any(len(prompts[i]) for i in rows):
+            opts["prompts"] = [list(prompts[i]) for i in rows]
+        return opts
+
+    def run(windows: np.ndarray, languages: List[Optional[str]], prompts=None):
         out = [None] * len(languages)
         dev_audio = torch.from_numpy(np.ascontiguousarray(windows)).to(model.device)
         mel = A.log_mel_spectrogram(dev_audio, n_mels=model.dims.n_mels)
         for lang in sorted(set(languages), key=lambda l: (l is not None, l or "")):
             rows = [i for i, l in enumerate(languages) if l == lang]
-            opts = DecodingOptions(**{**decode_options, "language": lang, "without_timestamps": False, "temperature": 0.0})
+            opts = DecodingOptions(**with_prompts({**decode_options, "language": lang, "without_timestamps": False, "temperature": 0.0},
+                                                  prompts, rows))
             res = decode(model, mel[rows] if len(rows) != len(languages) else mel, opts)
             for i, r in zip(rows, res):
                 out[i] = r
         return out
 
-    def retry(results, languages: List[str], *, temperature: float, attempt: int, streams, seed: int):
+    def retry(results, languages: List[str], *, temperature: float, attempt: int, streams, seed: int, prompts=None):
         """the default ``fallback_fn``: the rows' encoder features (``DecodingResult.audio_features``) decoded again at
-        ``temperature``, each row on its own stream"""
+        ``temperature``, each row on its own stream and with the prompt it was first decoded with"""
         out = [None] * len(results)
         feats = torch.stack([r.audio_features for r in results])
         for lang in sorted(set(languages)):
             rows = [i for i, l in enumerate(languages) if l == lang]
-            opts = DecodingOptions(**{**decode_options, "language": lang, "without_timestamps": False, "temperature": float(temperature),
-                                      "seed": int(seed), "sample_streams": [streams[i] for i in rows], "sample_attempt": int(attempt)})
+            opts = DecodingOptions(**with_prompts({**decode_options, "language": lang, "without_timestamps": False,
+                                                   "temperature": float(temperature), "seed": int(seed),
+                                                   "sample_streams": [streams[i] for i in rows], "sample_attempt": int(attempt)}, prompts, rows))
             res = decode(model, feats[rows] if len(rows) != len(languages) else feats, opts)
             for i, r in zip(rows, res):
                 out[i] = r
@@ -190,8 +224,12 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
                align_fn: Optional[Callable] = None, **decode_options):
     """``audio``: a path, a 16 kHz mono float array, or a list of them.  Returns {"text", "segments", "language"} (a list of
     them for a list) with mlx_whisper's segment keys (``SEGMENT_KEYS``; plus ``needs_fallback`` where upstream would have
-    retried).  ``condition_on_previous_text`` defaults to False here: True is refused, like every option this path does not
-    serve.  ``decode_fn(windows [n, 480000] f32, languages [n])`` -> objects with tokens / avg_logprob / no_speech_prob /
+    retried).  ``condition_on_previous_text`` defaults to False here.  With True every window after a file's first is decoded with
+    the file's previous tokens (timestamps included) as its prompt, ``<|startofprev|> ... <|startoftranscript|> ...``, until a window
+    decoded above temperature 0.5 resets it; ``initial_prompt`` is the prompt of the first window (of every window until such a reset
+    with conditioning on) and is left out of the returned ``text``.  ``decode_fn`` is then called as ``decode_fn(windows, languages,
+    prompts=[ids per row])`` and ``fallback_fn`` gets ``prompts=`` too; a custom one without that parameter is refused.
+    ``decode_fn(windows [n, 480000] f32, languages [n])`` -> objects with tokens / avg_logprob / no_speech_prob /
     compression_ratio / temperature / language replaces the model's decode (tests; ``tokenizer`` is then required when
     ``model`` is None).  ``seed``: run the temperature schedule (module docstring); segments then carry the temperature that
     produced them, and neither ``needs_fallback`` nor the warning appears where a retry ran.  ``fallback_fn(results, languages,
@@ -203,6 +241,8 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
     ``num_frames[j]`` its content in mel frames); it is required with a custom ``decode_fn``."""
     _refuse(condition_on_previous_text, initial_prompt, word_timestamps, clip_timestamps, hallucination_silence_threshold, temperature,
             decode_options, can_align=align_fn is not None or (model is not None and decode_fn is None))
+    _refuse_conditioning(condition_on_previous_text, initial_prompt, model, decode_fn, fallback_fn)
+    conditioning = bool(condition_on_previous_text) or initial_prompt is not None
     if word_timestamps and align_fn is None and getattr(model, "_fp8", None):
         raise NotImplementedError("word_timestamps=True is not implemented for an fp8-quantised model: the alignment runs the "
                                   "teacher-forced decoder on bf16 / f32 weights")
@@ -235,7 +275,11 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
     seek = [0] * n
     languages: List[Optional[str]] = [language] * n
     all_segments: List[List[dict]] = [[] for _ in range(n)]
-    all_tokens: List[List[int]] = [[] for _ in range(n)]
+    # upstream's prompt bookkeeping, per file: all_tokens starts with the initial prompt, the next window's prompt is what came after
+    # prompt_reset_since
+    initial_ids = [int(t) for t in tok.encode(" " + initial_prompt.strip())] if initial_prompt is not None else []
+    all_tokens: List[List[int]] = [list(initial_ids) for _ in range(n)]
+    prompt_reset_since = [0] * n
     warned = False
     while True:
         live = [i for i in range(n) if seek[i] < content_frames[i]]
@@ -248,7 +292,11 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
             s0 = seek[i] * HOP_LENGTH
             chunk = clips[i][s0:s0 + size * HOP_LENGTH]
             windows[r, :len(chunk)] = chunk  # pad_or_trim of the window's own samples
-        results = list(decode_fn(windows, [languages[i] for i in live]))
+        prompts = [list(all_tokens[i][prompt_reset_since[i]:]) for i in live] if conditioning else None
+        if conditioning:
+            results = list(decode_fn(windows, [languages[i] for i in live], prompts=prompts))
+        else:
+            results = list(decode_fn(windows, [languages[i] for i in live]))
         to_align = []  # (result, the window's segments, content frames, time offset, language, the segments' decoded tokens): rows not skipped
         retried = set()  # rows of this round that went through the schedule
         if fallback_fn is not None:
@@ -258,8 +306,10 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
                 if not failing:
                     break
                 # the failing rows of the round as ONE sub-batch; the language is the file's, or what this window's first decode detected
+                more = {"prompts": [prompts[r] for r in failing]} if conditioning else {}  # the retry keeps the window's prompt
                 again = fallback_fn([results[r] for r in failing], [languages[live[r]] or results[r].language for r in failing],
-                                    temperature=temps[attempt], attempt=attempt, streams=[(seek[live[r]], live[r]) for r in failing], seed=seed)
+                                    temperature=temps[attempt], attempt=attempt, streams=[(seek[live[r]], live[r]) for r in failing], seed=seed,
+                                    **more)
                 for r, res in zip(failing, again):
                     results[r] = res
                 retried.update(failing)
@@ -300,9 +350,11 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
                 all_tokens[i].extend(sg["tokens"])
             if word_timestamps:
                 to_align.append((res, all_segments[i][first_new:], size, time_offset, languages[i], decoded_tokens))
+            if not condition_on_previous_text or res.temperature > 0.5:
+                prompt_reset_since[i] = len(all_tokens[i])  # do not feed the prompt tokens if a high temperature was used
             if advance <= 0:  # a pair at <|0.00|> only: never stand still
                 seek[i] += size
         if word_timestamps and to_align:
             _add_words(model, tok, to_align, prepend_punctuations, append_punctuations, align_fn)
-    out = [{"text": tok.decode([t for t in all_tokens[i] if t < tb]), "segments": all_segments[i], "language": languages[i]} for i in range(n)]
+    out = [{"text": tok.decode([t for t in all_tokens[i][len(initial_ids):] if t < tb]), "segments": all_segments[i], "language": languages[i]} for i in range(n)]
     return out[0] if single else out
