@@ -223,6 +223,80 @@ __device__ __forceinline__ MaxIdx wave_argmax(MaxIdx m) {
 }
 
 constexpr int GS_THREADS = 1024;
+constexpr int GS_WAVES = GS_THREADS / 64;
+
+// Block reductions of a GS_THREADS workgroup (lane, wave: of the calling thread): the wave tree, lane 0's LDS write, ONE barrier, then
+// every thread folds the waves IN ORDER -- the order that makes the fused and the unfused step agree bit for bit.  s_v / s_i / s_sum:
+// GS_WAVES slots of LDS each.  The fold hands the value back as a float and the column by reference: kept in a MaxIdx it compiles to
+// the same compares with their operands swapped.
+__device__ __forceinline__ float fold_waves_argmax(const float* s_v, const int* s_i, int& idx) {
+    MaxIdx bm{s_v[0], s_i[0]};
+#pragma unroll
+    for (int w = 1; w < GS_WAVES; ++w) bm = better(bm, MaxIdx{s_v[w], s_i[w]});
+    idx = bm.i;
+    return bm.v;
+}
+__device__ __forceinline__ MaxIdx block_argmax(MaxIdx m, int lane, int wave, float* s_v, int* s_i) {
+    m = wave_argmax(m);
+    if (lane == 0) {
+        s_v[wave] = m.v;
+        s_i[wave] = m.i;
+    }
+    __syncthreads();
+    m.v = fold_waves_argmax(s_v, s_i, m.i);
+    return m;
+}
+__device__ __forceinline__ float block_sum(float v, int lane, int wave, float* s_sum) {
+    v = wave_reduce_sum(v);
+    if (lane == 0) s_sum[wave] = v;
+    __syncthreads();
+    float tot = 0.f;
+#pragma unroll
+    for (int w = 0; w < GS_WAVES; ++w) tot += s_sum[w];
+    return tot;
+}
+
+// the prompt walk: the column after p holds a prompt token already, the step picks nothing; and the mask of a column that is picked
+__device__ __forceinline__ bool in_prompt(int p, int n_init) { return p + 1 < n_init; }
+__device__ __forceinline__ const float* step_mask(int p, int n_init, const float* mask_first, const float* mask_always) {
+    return (p + 1 == n_init) ? mask_first : mask_always;
+}
+
+// The commit of a picked token.  at: the row's column p (at[0] the previous token, at[1] the new one).  The EOT latch (a row whose
+// previous token is eot takes eot again and adds no log-probability), the log-probability sum, the token store and the count of rows
+// still running.  Two forms.  commit_by_thread0 (the step kernels): thread 0 does all of it.  commit (the tails): EVERY thread
+// computes `next` from values all of them hold -- no single-thread section that hands a value to the workgroup through LDS: the
+// pattern whose merge-kernel instance misbehaved, DESIGN.md section 8 -- and thread 0 alone writes.  logprob: log_softmax of the
+// filtered row at `pick`.
+__device__ __forceinline__ void commit_by_thread0(int32_t* at, int eot, int pick, float logprob, float* sum_logprob, int32_t* not_done) {
+    if (threadIdx.x == 0) {
+        const int prev = at[0];
+        int next = pick;
+        if (prev == eot) {
+            next = eot;
+        } else {
+            *sum_logprob += logprob;
+        }
+        at[1] = next;
+        if (next != eot) atomicAdd(not_done, 1);
+    }
+}
+__device__ __forceinline__ int commit(int32_t* at, int eot, int pick, float logprob, float* sum_logprob, int32_t* not_done) {
+    const int prev = at[0];
+    const int next = (prev == eot) ? eot : pick;
+    if (threadIdx.x == 0) {
+        if (prev != eot) *sum_logprob += logprob;
+        at[1] = next;
+        if (next != eot) atomicAdd(not_done, 1);
+    }
+    return next;
+}
+
+// the plain filtered row's arg-max (lowest column on ties) and sum of exponentials against it: log_softmax at the arg-max = -log(tot)
+struct RowScan {
+    MaxIdx top;
+    float tot;
+};
 
 __global__ __launch_bounds__(GS_THREADS) void greedy_step_kernel(const float* __restrict__ logits, int64_t ldl, int V,
                                                                  const float* __restrict__ mask_first,
@@ -231,13 +305,13 @@ __global__ __launch_bounds__(GS_THREADS) void greedy_step_kernel(const float* __
                                                                  const int32_t* __restrict__ pos_dev, int n_init, int eot,
                                                                  float* __restrict__ sum_logprobs,
                                                                  int32_t* __restrict__ not_done) {
-    __shared__ float s_v[GS_THREADS / 64];
-    __shared__ int s_i[GS_THREADS / 64];
-    __shared__ float s_sum[GS_THREADS / 64];
+    __shared__ float s_v[GS_WAVES];
+    __shared__ int s_i[GS_WAVES];
+    __shared__ float s_sum[GS_WAVES];
     const int b = blockIdx.x;
     const int p = *pos_dev;
-    if (p + 1 < n_init) return;  // prompt token already in place
-    const float* mask = (p + 1 == n_init) ? mask_first : mask_always;
+    if (in_prompt(p, n_init)) return;
+    const float* mask = step_mask(p, n_init, mask_first, mask_always);
     const float* row = logits + (int64_t)b * ldl;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     MaxIdx m{-INFINITY, 0x7fffffff};
@@ -245,55 +319,19 @@ __global__ __launch_bounds__(GS_THREADS) void greedy_step_kernel(const float* __
         const float v = row[i] + mask[i];
         m = better(m, MaxIdx{v, i});
     }
-    m = wave_argmax(m);
-    if (lane == 0) {
-        s_v[wave] = m.v;
-        s_i[wave] = m.i;
-    }
-    __syncthreads();
-    MaxIdx bm{s_v[0], s_i[0]};
-#pragma unroll
-    for (int w = 1; w < GS_THREADS / 64; ++w) bm = better(bm, MaxIdx{s_v[w], s_i[w]});
+    const MaxIdx bm = block_argmax(m, lane, wave, s_v, s_i);
     float se = 0.f;
     for (int i = tid; i < V; i += GS_THREADS) se += __expf(row[i] + mask[i] - bm.v);
-    se = wave_reduce_sum(se);
-    if (lane == 0) s_sum[wave] = se;
-    __syncthreads();
-    if (tid == 0) {
-        float tot = 0.f;
-#pragma unroll
-        for (int w = 0; w < GS_THREADS / 64; ++w) tot += s_sum[w];
-        const int prev = tokens[(int64_t)b * ld_tok + p];
-        int next = bm.i;
-        if (prev == eot) {
-            next = eot;
-        } else {
-            sum_logprobs[b] += -logf(tot);  // log_softmax at the argmax = -(log sum exp(x - max))
-        }
-        tokens[(int64_t)b * ld_tok + p + 1] = next;
-        if (next != eot) atomicAdd(not_done, 1);
-    }
+    const float tot = block_sum(se, lane, wave, s_sum);
+    commit_by_thread0(tokens + ((int64_t)b * ld_tok + p), eot, bm.i, -logf(tot), sum_logprobs + b, not_done);
 }
 
-// Register-resident variant for V <= 65536 (every Whisper vocabulary): the filtered row is fetched ONCE with 16-byte loads
+// Register-resident scan for V <= 65536 (every Whisper vocabulary): the filtered row is fetched ONCE with 16-byte loads
 // that are all in flight together (13 per thread for V = 51 865), the arg-max and the sum of exponentials both run out of
 // registers.  The two-pass scalar kernel above took 30 us per step on 64 rows (latency-bound: 2 x 51 dependent loads).
 constexpr int GS_MAXQ = 16;
-__global__ __launch_bounds__(GS_THREADS) void greedy_step_reg_kernel(const float* __restrict__ logits, int64_t ldl, int V,
-                                                                     const float* __restrict__ mask_first,
-                                                                     const float* __restrict__ mask_always,
-                                                                     int32_t* __restrict__ tokens, int64_t ld_tok,
-                                                                     const int32_t* __restrict__ pos_dev, int n_init, int eot,
-                                                                     float* __restrict__ sum_logprobs,
-                                                                     int32_t* __restrict__ not_done) {
-    __shared__ float s_v[GS_THREADS / 64];
-    __shared__ int s_i[GS_THREADS / 64];
-    __shared__ float s_sum[GS_THREADS / 64];
-    const int b = blockIdx.x;
-    const int p = *pos_dev;
-    if (p + 1 < n_init) return;  // prompt token already in place
-    const float* mask = (p + 1 == n_init) ? mask_first : mask_always;
-    const float* row = logits + (int64_t)b * ldl;
+__device__ __forceinline__ RowScan row_scan_reg(const float* __restrict__ row, const float* __restrict__ mask, int V, float* s_v, int* s_i,
+                                                float* s_sum) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nq = V >> 2;
     f32x4 vals[GS_MAXQ];
@@ -316,37 +354,31 @@ __global__ __launch_bounds__(GS_THREADS) void greedy_step_reg_kernel(const float
 #pragma unroll
         for (int e = 0; e < 4; ++e) m = better(m, MaxIdx{vals[j][e], qi < nq ? 4 * qi + e : 0x7fffffff});
     }
-    m = wave_argmax(m);
-    if (lane == 0) {
-        s_v[wave] = m.v;
-        s_i[wave] = m.i;
-    }
-    __syncthreads();
-    MaxIdx bm{s_v[0], s_i[0]};
-#pragma unroll
-    for (int w = 1; w < GS_THREADS / 64; ++w) bm = better(bm, MaxIdx{s_v[w], s_i[w]});
+    const MaxIdx bm = block_argmax(m, lane, wave, s_v, s_i);
     float se = __expf(tailv - bm.v);
 #pragma unroll
     for (int j = 0; j < GS_MAXQ; ++j)
 #pragma unroll
         for (int e = 0; e < 4; ++e) se += __expf(vals[j][e] - bm.v);
-    se = wave_reduce_sum(se);
-    if (lane == 0) s_sum[wave] = se;
-    __syncthreads();
-    if (tid == 0) {
-        float tot = 0.f;
-#pragma unroll
-        for (int w = 0; w < GS_THREADS / 64; ++w) tot += s_sum[w];
-        const int prev = tokens[(int64_t)b * ld_tok + p];
-        int next = bm.i;
-        if (prev == eot) {
-            next = eot;
-        } else {
-            sum_logprobs[b] += -logf(tot);
-        }
-        tokens[(int64_t)b * ld_tok + p + 1] = next;
-        if (next != eot) atomicAdd(not_done, 1);
-    }
+    return RowScan{bm, block_sum(se, lane, wave, s_sum)};
+}
+
+__global__ __launch_bounds__(GS_THREADS) void greedy_step_reg_kernel(const float* __restrict__ logits, int64_t ldl, int V,
+                                                                     const float* __restrict__ mask_first,
+                                                                     const float* __restrict__ mask_always,
+                                                                     int32_t* __restrict__ tokens, int64_t ld_tok,
+                                                                     const int32_t* __restrict__ pos_dev, int n_init, int eot,
+                                                                     float* __restrict__ sum_logprobs,
+                                                                     int32_t* __restrict__ not_done) {
+    __shared__ float s_v[GS_WAVES];
+    __shared__ int s_i[GS_WAVES];
+    __shared__ float s_sum[GS_WAVES];
+    const int b = blockIdx.x;
+    const int p = *pos_dev;
+    if (in_prompt(p, n_init)) return;
+    const float* mask = step_mask(p, n_init, mask_first, mask_always);
+    const RowScan sc = row_scan_reg(logits + (int64_t)b * ldl, mask, V, s_v, s_i, s_sum);
+    commit_by_thread0(tokens + ((int64_t)b * ld_tok + p), eot, sc.top.i, -logf(sc.tot), sum_logprobs + b, not_done);
 }
 
 // ------------------------------------------------------------------ decode-step tail / head (round 4)
@@ -448,34 +480,61 @@ struct TailArgs<true> : TailParams {
     const int32_t* start;
 };
 
+// the row's position-embedding index at column `col`: clamped to the table, and with ragged prompts counted from the row's own start
+template <bool RAGGED>
+__device__ __forceinline__ int pos_row(const TailArgs<RAGGED>& q, int b, int col) {
+    int pp = min(col, q.n_ctx - 1);
+    if constexpr (RAGGED) pp = max(pp - q.start[b], 0);  // padding columns, below start[b], take row 0
+    return pp;
+}
+
 template <typename TO, bool RAGGED = false>
 __global__ __launch_bounds__(256) void embed_layernorm_kernel(TailArgs<RAGGED> q) {
     __shared__ float s_red[4];
     const int b = blockIdx.x;
     const int p = *q.pos;
     const int tok = q.tokens[(int64_t)b * q.ld_tok + p];
-    int pp = min(p, q.n_ctx - 1);
-    if constexpr (RAGGED) pp = max(pp - q.start[b], 0);  // padding columns, below start[b], take row 0
-    row_embed_layernorm<TO>(threadIdx.x, tok, pp, q.emb, q.emb_dtype, q.emb_scale, q.pos_emb, q.x + (int64_t)b * q.D, q.ln_w,
+    row_embed_layernorm<TO>(threadIdx.x, tok, pos_row(q, b, p), q.emb, q.emb_dtype, q.emb_scale, q.pos_emb, q.x + (int64_t)b * q.D, q.ln_w,
                             q.ln_b, (TO*)q.y + (int64_t)b * q.D, q.D, q.eps, s_red);
+}
+
+// The tails' read of the position.  volatile: ONE load per thread at the kernel's start, never re-materialised by the compiler after
+// a barrier -- the last workgroup to arrive overwrites *pos while slower workgroups are still between their barriers and their exit
+// (the sampling tails' draw counter reads this value live, too)
+__device__ __forceinline__ int tail_pos(const int32_t* pos) { return *(volatile const int32_t*)pos; }
+
+// What every tail does after `next` is known (every thread of the workgroup calls it with the same p and next): the next step's
+// input row -- the embedding of the chosen token at position p + 1, then the first block's LayerNorm -- and the position advance by
+// the LAST workgroup to arrive.  Every thread of every workgroup read *pos at its start (tail_pos) and has used it before the row
+// routine's barriers, i.e. before its workgroup's counter increment -- no workgroup can still see the old position late.
+// Needs *done_counter == 0 at launch and one launch in flight per state blob: wipa_decoder_run / _prefill zero the counter
+// at the start of every call (a launch that died mid-grid must not leave later calls without a position advance)
+template <typename TO, bool RAGGED>
+__device__ __forceinline__ void tail_finish(const TailArgs<RAGGED>& q, int p, int next, float* s_red) {
+    const int b = blockIdx.x;
+    row_embed_layernorm<TO>(threadIdx.x, next, pos_row(q, b, p + 1), q.emb, q.emb_dtype, q.emb_scale, q.pos_emb, q.x + (int64_t)b * q.D,
+                            q.ln_w, q.ln_b, (TO*)q.y + (int64_t)b * q.D, q.D, q.eps, s_red);
+    if (threadIdx.x == 0) {
+        const int arrived = atomicAdd(q.done_counter, 1);  // counts arrivals only: what the step wrote reaches the next launch at the kernel boundary
+        if (arrived == (int)gridDim.x - 1) {
+            *q.done_counter = 0;
+            *q.pos = p + 1;
+            *q.posd = (int64_t)(p + 1) * q.D;
+        }
+    }
 }
 
 template <typename TO, bool RAGGED = false>
 __global__ __launch_bounds__(GS_THREADS) void greedy_tail_kernel(TailArgs<RAGGED> q) {
-    __shared__ float s_v[GS_THREADS / 64];
-    __shared__ int s_i[GS_THREADS / 64];
-    __shared__ float s_sum[GS_THREADS / 64];
+    __shared__ float s_v[GS_WAVES];
+    __shared__ int s_i[GS_WAVES];
+    __shared__ float s_sum[GS_WAVES];
     __shared__ float s_red[4];
     const int b = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // volatile: ONE load per thread at the kernel's start, never re-materialised by the compiler after the barrier below -- the
-    // last workgroup to arrive overwrites *q.pos while slower workgroups are still between their barrier and their exit
-    const int p = *(volatile const int32_t*)q.pos;
-    const int V = q.V;
-    // `next` is computed by EVERY thread from values all of them hold (no single-thread section that hands a value to the
-    // workgroup through LDS: the pattern whose merge-kernel instance misbehaved); thread 0 alone writes
+    const int p = tail_pos(q.pos);
     int next;
-    if (p + 1 < q.n_init) {  // prompt walk: the token is already in place (uniform branch: p is the same for every thread)
+    if (in_prompt(p, q.n_init)) {  // the token is already in place (uniform branch: p is the same for every thread)
         next = q.tokens[(int64_t)b * q.ld_tok + p + 1];
     } else if (q.part) {
         // the logits GEMM left one (max, sum exp, arg-max) per wave of its grid for this row: merge them -- (value, lowest column)
@@ -485,99 +544,17 @@ __global__ __launch_bounds__(GS_THREADS) void greedy_tail_kernel(TailArgs<RAGGED
         const int* pi = reinterpret_cast<const int*>(pm + 2 * q.n_part);
         MaxIdx m{-INFINITY, 0x7fffffff};
         for (int i = tid; i < q.n_part; i += GS_THREADS) m = better(m, MaxIdx{pm[i], pi[i]});
-        m = wave_argmax(m);
-        if (lane == 0) {
-            s_v[wave] = m.v;
-            s_i[wave] = m.i;
-        }
-        __syncthreads();
-        MaxIdx bm{s_v[0], s_i[0]};
-#pragma unroll
-        for (int w = 1; w < GS_THREADS / 64; ++w) bm = better(bm, MaxIdx{s_v[w], s_i[w]});
+        const MaxIdx bm = block_argmax(m, lane, wave, s_v, s_i);
         float se = 0.f;
         for (int i = tid; i < q.n_part; i += GS_THREADS) se += ps[i] * __expf(pm[i] - bm.v);
-        se = wave_reduce_sum(se);
-        if (lane == 0) s_sum[wave] = se;
-        __syncthreads();
-        const int prev = q.tokens[(int64_t)b * q.ld_tok + p];
-        next = (prev == q.eot) ? q.eot : bm.i;
-        if (tid == 0) {
-            float tot = 0.f;
-#pragma unroll
-            for (int w = 0; w < GS_THREADS / 64; ++w) tot += s_sum[w];
-            if (prev != q.eot) q.sum_logprobs[b] += -logf(tot);
-            q.tokens[(int64_t)b * q.ld_tok + p + 1] = next;
-            if (next != q.eot) atomicAdd(q.not_done, 1);
-        }
+        const float tot = block_sum(se, lane, wave, s_sum);
+        next = commit(q.tokens + ((int64_t)b * q.ld_tok + p), q.eot, bm.i, -logf(tot), q.sum_logprobs + b, q.not_done);
     } else {
-        const float* mask = (p + 1 == q.n_init) ? q.mask_first : q.mask_always;
-        const float* row = q.logits + (int64_t)b * q.ldl;
-        const int nq = V >> 2;
-        f32x4 vals[GS_MAXQ];
-#pragma unroll
-        for (int j = 0; j < GS_MAXQ; ++j) {
-            const int qi = tid + j * GS_THREADS;
-            if (qi < nq) {
-                vals[j] = *reinterpret_cast<const f32x4*>(row + 4 * qi) + *reinterpret_cast<const f32x4*>(mask + 4 * qi);
-            } else {
-                vals[j] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-            }
-        }
-        const int ti = 4 * nq + tid;  // the (V mod 4) trailing elements
-        const bool has_tail = tid < 4 && ti < V;
-        const float tailv = has_tail ? row[ti] + mask[ti] : -INFINITY;
-        MaxIdx m{tailv, has_tail ? ti : 0x7fffffff};
-#pragma unroll
-        for (int j = 0; j < GS_MAXQ; ++j) {
-            const int qi = tid + j * GS_THREADS;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) m = better(m, MaxIdx{vals[j][e], qi < nq ? 4 * qi + e : 0x7fffffff});
-        }
-        m = wave_argmax(m);
-        if (lane == 0) {
-            s_v[wave] = m.v;
-            s_i[wave] = m.i;
-        }
-        __syncthreads();
-        MaxIdx bm{s_v[0], s_i[0]};
-#pragma unroll
-        for (int w = 1; w < GS_THREADS / 64; ++w) bm = better(bm, MaxIdx{s_v[w], s_i[w]});
-        float se = __expf(tailv - bm.v);
-#pragma unroll
-        for (int j = 0; j < GS_MAXQ; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) se += __expf(vals[j][e] - bm.v);
-        se = wave_reduce_sum(se);
-        if (lane == 0) s_sum[wave] = se;
-        __syncthreads();
-        const int prev = q.tokens[(int64_t)b * q.ld_tok + p];
-        next = (prev == q.eot) ? q.eot : bm.i;
-        if (tid == 0) {
-            float tot = 0.f;
-#pragma unroll
-            for (int w = 0; w < GS_THREADS / 64; ++w) tot += s_sum[w];
-            if (prev != q.eot) q.sum_logprobs[b] += -logf(tot);
-            q.tokens[(int64_t)b * q.ld_tok + p + 1] = next;
-            if (next != q.eot) atomicAdd(q.not_done, 1);
-        }
+        const float* mask = step_mask(p, q.n_init, q.mask_first, q.mask_always);
+        const RowScan sc = row_scan_reg(q.logits + (int64_t)b * q.ldl, mask, q.V, s_v, s_i, s_sum);
+        next = commit(q.tokens + ((int64_t)b * q.ld_tok + p), q.eot, sc.top.i, -logf(sc.tot), q.sum_logprobs + b, q.not_done);
     }
-    // the next step's input row: embedding of the chosen token at position p + 1, then the first block's LayerNorm
-    int pp = min(p + 1, q.n_ctx - 1);  // the position-embedding row of the next column
-    if constexpr (RAGGED) pp = max(pp - q.start[b], 0);
-    row_embed_layernorm<TO>(tid, next, pp, q.emb, q.emb_dtype, q.emb_scale, q.pos_emb, q.x + (int64_t)b * q.D, q.ln_w,
-                            q.ln_b, (TO*)q.y + (int64_t)b * q.D, q.D, q.eps, s_red);
-    // position advance by the LAST workgroup: every thread of every workgroup read *pos at its start and has used it before
-    // its workgroup's barrier above, i.e. before its counter increment -- no workgroup can still see the old position late.
-    // Needs *done_counter == 0 at launch and one launch in flight per state blob: wipa_decoder_run / _prefill zero the counter
-    // at the start of every call (a launch that died mid-grid must not leave later calls without a position advance)
-    if (tid == 0) {
-        const int arrived = atomicAdd(q.done_counter, 1);  // counts arrivals only: what the step wrote reaches the next launch at the kernel boundary
-        if (arrived == (int)gridDim.x - 1) {
-            *q.done_counter = 0;
-            *q.pos = p + 1;
-            *q.posd = (int64_t)(p + 1) * q.D;
-        }
-    }
+    tail_finish<TO>(q, p, next, s_red);
 }
 
 // ------------------------------------------------------------------ timestamp rules in the step's tail
@@ -671,9 +648,11 @@ __device__ __forceinline__ RowPick row_pick(const float* __restrict__ row, const
             }
         }
     }
+    // block_argmax / block_sum written out, two sides around ONE barrier each (and once more for the draw's keys below): routed through
+    // the helpers the sampling kernels compiled to 350 - 400 bytes of scratch instead of 100 - 136, so this text stays as it is
     mt = wave_argmax(mt);
     ms = wave_argmax(ms);
-    constexpr int NW = GS_THREADS / 64;
+    constexpr int NW = GS_WAVES;
     if (lane == 0) {
         s_v[wave] = mt.v; s_i[wave] = mt.i;
         s_v[NW + wave] = ms.v; s_i[NW + wave] = ms.i;
@@ -772,9 +751,45 @@ __device__ __forceinline__ RowPick row_pick(const float* __restrict__ row, const
     return out;
 }
 
-__device__ __forceinline__ RowPick rules_row_pick(const float* __restrict__ row, const float* __restrict__ mask, int V, const int32_t* __restrict__ tk,
-                                                  int p, int n_init, int eot, RulesDev r, float* s_v, int* s_i, float* s_sum) {
-    return row_pick<true, false>(row, mask, V, tk, p, n_init, eot, r, s_v, s_i, s_sum, nullptr, 0, p);
+// The step kernels with rules and / or the draw (no embedding): greedy_step_reg_kernel's walk test and thread-0 commit around row_pick.
+// start: RAGGED && SAMPLE only -- the position word of the draw's counter is the row's own position (not looked at otherwise)
+template <bool RULES, bool SAMPLE, bool RAGGED>
+__device__ __forceinline__ void pick_step(const float* __restrict__ logits, int64_t ldl, int V, const float* __restrict__ mask_first,
+                                          const float* __restrict__ mask_always, int32_t* __restrict__ tokens, int64_t ld_tok,
+                                          const int32_t* __restrict__ pos_dev, int n_init, int eot, RulesDev r, const uint32_t* __restrict__ rec,
+                                          float* __restrict__ sum_logprobs, int32_t* __restrict__ not_done, const int32_t* __restrict__ start,
+                                          float* s_v, int* s_i, float* s_sum) {
+    const int b = blockIdx.x;
+    const int p = *pos_dev;
+    if (in_prompt(p, n_init)) return;
+    int32_t* tk = tokens + (int64_t)b * ld_tok;
+    int p_own = p;
+    if constexpr (SAMPLE && RAGGED) p_own = max(p - start[b], 0);
+    const RowPick pick = row_pick<RULES, SAMPLE>(logits + (int64_t)b * ldl, step_mask(p, n_init, mask_first, mask_always), V, tk, p, n_init, eot, r,
+                                                 s_v, s_i, s_sum, rec, b, p_own);
+    commit_by_thread0(tk + p, eot, pick.next, pick.logprob, sum_logprobs + b, not_done);
+}
+
+// The tails with rules and / or the draw: greedy_tail_kernel with row_pick in the place of the plain row scan -- the same prompt walk,
+// EOT latch, next embedding + LayerNorm (so the next step's input row has the bits the plain tail would give for the same token) and
+// position advance
+template <typename TO, bool RULES, bool SAMPLE, bool RAGGED>
+__device__ __forceinline__ void pick_tail(const TailArgs<RAGGED>& q, RulesDev r, const uint32_t* __restrict__ rec, float* s_v, int* s_i,
+                                          float* s_sum, float* s_red) {
+    const int b = blockIdx.x;
+    const int p = tail_pos(q.pos);
+    int32_t* tk = q.tokens + (int64_t)b * q.ld_tok;
+    int next;
+    if (in_prompt(p, q.n_init)) {
+        next = tk[p + 1];
+    } else {
+        int p_own = p;  // the position word of the draw's counter: the row's own position
+        if constexpr (SAMPLE && RAGGED) p_own = max(p - q.start[b], 0);
+        const RowPick pick = row_pick<RULES, SAMPLE>(q.logits + (int64_t)b * q.ldl, step_mask(p, q.n_init, q.mask_first, q.mask_always), q.V, tk, p,
+                                                     q.n_init, q.eot, r, s_v, s_i, s_sum, rec, b, p_own);
+        next = commit(tk + p, q.eot, pick.next, pick.logprob, q.sum_logprobs + b, q.not_done);
+    }
+    tail_finish<TO>(q, p, next, s_red);
 }
 
 // wipa_timestamp_step: wipa_greedy_step with the rules, no embedding
@@ -783,62 +798,21 @@ __global__ __launch_bounds__(GS_THREADS) void timestamp_step_kernel(const float*
                                                                     int32_t* __restrict__ tokens, int64_t ld_tok, const int32_t* __restrict__ pos_dev,
                                                                     int n_init, int eot, RulesDev r, float* __restrict__ sum_logprobs,
                                                                     int32_t* __restrict__ not_done) {
-    __shared__ float s_v[2 * GS_THREADS / 64];
-    __shared__ int s_i[2 * GS_THREADS / 64];
-    __shared__ float s_sum[2 * GS_THREADS / 64];
-    const int b = blockIdx.x;
-    const int p = *pos_dev;
-    if (p + 1 < n_init) return;  // prompt token already in place
-    int32_t* tk = tokens + (int64_t)b * ld_tok;
-    const RowPick pick = rules_row_pick(logits + (int64_t)b * ldl, (p + 1 == n_init) ? mask_first : mask_always, V, tk, p, n_init, eot, r, s_v,
-                                        s_i, s_sum);
-    if (threadIdx.x == 0) {
-        const int prev = tk[p];
-        const int next = (prev == eot) ? eot : pick.next;
-        if (prev != eot) sum_logprobs[b] += pick.logprob;
-        tk[p + 1] = next;
-        if (next != eot) atomicAdd(not_done, 1);
-    }
+    __shared__ float s_v[2 * GS_WAVES];
+    __shared__ int s_i[2 * GS_WAVES];
+    __shared__ float s_sum[2 * GS_WAVES];
+    pick_step<true, false, false>(logits, ldl, V, mask_first, mask_always, tokens, ld_tok, pos_dev, n_init, eot, r, nullptr, sum_logprobs, not_done,
+                                  nullptr, s_v, s_i, s_sum);
 }
 
-// greedy_tail_kernel's row-scan branch with the rules: the same prompt walk, EOT latch, next embedding + LayerNorm (so the next
-// step's input row has the bits the plain tail would give for the same token) and position advance
+// wipa_timestamp_step_embed: the step's tail with the rules
 template <typename TO, bool RAGGED = false>
 __global__ __launch_bounds__(GS_THREADS) void timestamp_tail_kernel(TailArgs<RAGGED> q, RulesDev r) {
-    __shared__ float s_v[2 * GS_THREADS / 64];
-    __shared__ int s_i[2 * GS_THREADS / 64];
-    __shared__ float s_sum[2 * GS_THREADS / 64];
+    __shared__ float s_v[2 * GS_WAVES];
+    __shared__ int s_i[2 * GS_WAVES];
+    __shared__ float s_sum[2 * GS_WAVES];
     __shared__ float s_red[4];
-    const int b = blockIdx.x;
-    const int tid = threadIdx.x;
-    const int p = *(volatile const int32_t*)q.pos;  // one load per thread, as in greedy_tail_kernel
-    int32_t* tk = q.tokens + (int64_t)b * q.ld_tok;
-    int next;
-    if (p + 1 < q.n_init) {
-        next = tk[p + 1];
-    } else {
-        const RowPick pick = rules_row_pick(q.logits + (int64_t)b * q.ldl, (p + 1 == q.n_init) ? q.mask_first : q.mask_always, q.V, tk, p, q.n_init,
-                                            q.eot, r, s_v, s_i, s_sum);
-        const int prev = tk[p];
-        next = (prev == q.eot) ? q.eot : pick.next;
-        if (tid == 0) {
-            if (prev != q.eot) q.sum_logprobs[b] += pick.logprob;
-            tk[p + 1] = next;
-            if (next != q.eot) atomicAdd(q.not_done, 1);
-        }
-    }
-    int pp = min(p + 1, q.n_ctx - 1);  // the position-embedding row of the next column
-    if constexpr (RAGGED) pp = max(pp - q.start[b], 0);
-    row_embed_layernorm<TO>(tid, next, pp, q.emb, q.emb_dtype, q.emb_scale, q.pos_emb, q.x + (int64_t)b * q.D, q.ln_w,
-                            q.ln_b, (TO*)q.y + (int64_t)b * q.D, q.D, q.eps, s_red);
-    if (tid == 0) {  // position advance by the last workgroup to arrive (see greedy_tail_kernel)
-        const int arrived = atomicAdd(q.done_counter, 1);
-        if (arrived == (int)gridDim.x - 1) {
-            *q.done_counter = 0;
-            *q.pos = p + 1;
-            *q.posd = (int64_t)(p + 1) * q.D;
-        }
-    }
+    pick_tail<TO, true, false>(q, r, nullptr, s_v, s_i, s_sum, s_red);
 }
 
 // wipa_sample_step: timestamp_step_kernel with the draw (RULES = false: wipa_greedy_step with the draw)
@@ -849,65 +823,21 @@ __global__ __launch_bounds__(GS_THREADS) void sample_step_kernel(const float* __
                                                                  int n_init, int eot, RulesDev r, const uint32_t* __restrict__ rec,
                                                                  float* __restrict__ sum_logprobs, int32_t* __restrict__ not_done,
                                                                  const int32_t* __restrict__ start) {
-    __shared__ float s_v[2 * GS_THREADS / 64];
-    __shared__ int s_i[2 * GS_THREADS / 64];
-    __shared__ float s_sum[2 * GS_THREADS / 64];
-    const int b = blockIdx.x;
-    const int p = *pos_dev;
-    if (p + 1 < n_init) return;  // prompt token already in place
-    int32_t* tk = tokens + (int64_t)b * ld_tok;
-    int p_own = p;  // the position word of the draw's counter: the row's own position (RAGGED: start is not looked at otherwise)
-    if constexpr (RAGGED) p_own = max(p - start[b], 0);
-    const RowPick pick = row_pick<RULES, true>(logits + (int64_t)b * ldl, (p + 1 == n_init) ? mask_first : mask_always, V, tk, p, n_init, eot, r,
-                                               s_v, s_i, s_sum, rec, b, p_own);
-    if (threadIdx.x == 0) {
-        const int prev = tk[p];
-        const int next = (prev == eot) ? eot : pick.next;
-        if (prev != eot) sum_logprobs[b] += pick.logprob;
-        tk[p + 1] = next;
-        if (next != eot) atomicAdd(not_done, 1);
-    }
+    __shared__ float s_v[2 * GS_WAVES];
+    __shared__ int s_i[2 * GS_WAVES];
+    __shared__ float s_sum[2 * GS_WAVES];
+    pick_step<RULES, true, RAGGED>(logits, ldl, V, mask_first, mask_always, tokens, ld_tok, pos_dev, n_init, eot, r, rec, sum_logprobs, not_done, start,
+                                   s_v, s_i, s_sum);
 }
 
-// timestamp_tail_kernel with the draw: the tail of a decode step at a temperature above 0, with and without rules
+// wipa_sample_step_embed: the tail of a decode step at a temperature above 0, with and without rules
 template <typename TO, bool RULES, bool RAGGED = false>
 __global__ __launch_bounds__(GS_THREADS) void sample_tail_kernel(TailArgs<RAGGED> q, RulesDev r, const uint32_t* __restrict__ rec) {
-    __shared__ float s_v[2 * GS_THREADS / 64];
-    __shared__ int s_i[2 * GS_THREADS / 64];
-    __shared__ float s_sum[2 * GS_THREADS / 64];
+    __shared__ float s_v[2 * GS_WAVES];
+    __shared__ int s_i[2 * GS_WAVES];
+    __shared__ float s_sum[2 * GS_WAVES];
     __shared__ float s_red[4];
-    const int b = blockIdx.x;
-    const int tid = threadIdx.x;
-    const int p = *(volatile const int32_t*)q.pos;  // one load per thread, as in greedy_tail_kernel: the draw's counter reads it live
-    int32_t* tk = q.tokens + (int64_t)b * q.ld_tok;
-    int next;
-    if (p + 1 < q.n_init) {
-        next = tk[p + 1];
-    } else {
-        int p_own = p;  // the position word of the draw's counter: the row's own position
-        if constexpr (RAGGED) p_own = max(p - q.start[b], 0);
-        const RowPick pick = row_pick<RULES, true>(q.logits + (int64_t)b * q.ldl, (p + 1 == q.n_init) ? q.mask_first : q.mask_always, q.V, tk, p,
-                                                   q.n_init, q.eot, r, s_v, s_i, s_sum, rec, b, p_own);
-        const int prev = tk[p];
-        next = (prev == q.eot) ? q.eot : pick.next;
-        if (tid == 0) {
-            if (prev != q.eot) q.sum_logprobs[b] += pick.logprob;
-            tk[p + 1] = next;
-            if (next != q.eot) atomicAdd(q.not_done, 1);
-        }
-    }
-    int pp = min(p + 1, q.n_ctx - 1);  // the position-embedding row of the next column
-    if constexpr (RAGGED) pp = max(pp - q.start[b], 0);
-    row_embed_layernorm<TO>(tid, next, pp, q.emb, q.emb_dtype, q.emb_scale, q.pos_emb, q.x + (int64_t)b * q.D, q.ln_w,
-                            q.ln_b, (TO*)q.y + (int64_t)b * q.D, q.D, q.eps, s_red);
-    if (tid == 0) {  // position advance by the last workgroup to arrive (see greedy_tail_kernel)
-        const int arrived = atomicAdd(q.done_counter, 1);
-        if (arrived == (int)gridDim.x - 1) {
-            *q.done_counter = 0;
-            *q.pos = p + 1;
-            *q.posd = (int64_t)(p + 1) * q.D;
-        }
-    }
+    pick_tail<TO, RULES, true>(q, r, rec, s_v, s_i, s_sum, s_red);
 }
 
 // wipa_sample_noise: g_c of one (row, position), c < V -- the numbers the sampling tails add, for measurement
@@ -1104,90 +1034,23 @@ extern "C" int wipa_embed_tokens_ragged(const int32_t* tokens, int64_t ld_tok, i
     return WIPA_OK;
 }
 
+// the register-resident row scan (row_scan_reg, row_pick) can serve this row layout: 16 quads per thread, 16-byte loads
+static bool reg_scan_ok(const float* logits, int V, int64_t ldl, const float* mask_first, const float* mask_always) {
+    return V <= 4 * GS_MAXQ * GS_THREADS && ldl % 4 == 0 && ((uintptr_t)logits % 16) == 0 && ((uintptr_t)mask_first % 16) == 0 &&
+           ((uintptr_t)mask_always % 16) == 0;
+}
+
 extern "C" int wipa_greedy_step(const float* logits, int64_t ldl, int B, int V, const float* mask_first,
                                 const float* mask_always, int32_t* tokens, int64_t ld_tok, const int32_t* pos_dev,
                                 int n_init, int eot, float* sum_logprobs, int32_t* not_done, wipa_stream_t stream) {
     WIPA_REQUIRE(logits && mask_first && mask_always && tokens && pos_dev && sum_logprobs && not_done,
                  "wipa_greedy_step: null pointer");
-    const bool reg_ok = V <= 4 * GS_MAXQ * GS_THREADS && ldl % 4 == 0 && ((uintptr_t)logits % 16) == 0 &&
-                        ((uintptr_t)mask_first % 16) == 0 && ((uintptr_t)mask_always % 16) == 0;
-    if (reg_ok)
+    if (reg_scan_ok(logits, V, ldl, mask_first, mask_always))
         hipLaunchKernelGGL(greedy_step_reg_kernel, dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, logits, ldl, V, mask_first,
                            mask_always, tokens, ld_tok, pos_dev, n_init, eot, sum_logprobs, not_done);
     else
         hipLaunchKernelGGL(greedy_step_kernel, dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, logits, ldl, V, mask_first,
                            mask_always, tokens, ld_tok, pos_dev, n_init, eot, sum_logprobs, not_done);
-    WIPA_LAUNCH_CHECK();
-    return WIPA_OK;
-}
-
-static int tail_params_check(const char* who, const float* logits, int V, int64_t ldl, const float* mask_first, const float* mask_always,
-                             int D, int emb_dtype, const float* emb_scale) {
-    WIPA_REQUIRE(D % 4 == 0 && D > 0 && D <= 2048, "%s: D=%d must be a multiple of 4 and <= 2048", who, D);
-    WIPA_REQUIRE(emb_dtype == WIPA_F32 || emb_dtype == WIPA_BF16 || (emb_dtype == WIPA_FP8_E4M3 && emb_scale), "%s: bad embedding dtype %d", who, emb_dtype);
-    if (logits)
-        WIPA_REQUIRE(V <= 4 * GS_MAXQ * GS_THREADS && ldl % 4 == 0 && ((uintptr_t)logits % 16) == 0 && ((uintptr_t)mask_first % 16) == 0 &&
-                         ((uintptr_t)mask_always % 16) == 0, "%s: vocabulary of %d / unaligned logits or masks", who, V);
-    return WIPA_OK;
-}
-
-extern "C" int wipa_embed_layernorm(const int32_t* tokens, int64_t ld_tok, int B, const int32_t* pos_dev, const void* tok_emb,
-                                    int emb_dtype, const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w,
-                                    const float* ln_b, void* y, int y_dtype, int D, float eps, wipa_stream_t stream) {
-    WIPA_REQUIRE(tokens && pos_dev && tok_emb && pos_emb && x && ln_w && ln_b && y && B > 0 && n_ctx > 0, "wipa_embed_layernorm: bad arguments");
-    const int rc = tail_params_check("wipa_embed_layernorm", nullptr, 0, 0, nullptr, nullptr, D, emb_dtype, emb_scale);
-    if (rc != WIPA_OK) return rc;
-    TailArgs<false> q = {};
-    q.tokens = const_cast<int32_t*>(tokens); q.ld_tok = ld_tok; q.pos = const_cast<int32_t*>(pos_dev); q.n_ctx = n_ctx;
-    q.emb = tok_emb; q.emb_dtype = emb_dtype; q.emb_scale = emb_scale; q.pos_emb = pos_emb;
-    q.x = x; q.ln_w = ln_w; q.ln_b = ln_b; q.y = y; q.D = D; q.eps = eps;
-    if (y_dtype == WIPA_F32) hipLaunchKernelGGL((embed_layernorm_kernel<float>), dim3(B), dim3(256), 0, (hipStream_t)stream, q);
-    else if (y_dtype == WIPA_BF16) hipLaunchKernelGGL((embed_layernorm_kernel<__bf16>), dim3(B), dim3(256), 0, (hipStream_t)stream, q);
-    else WIPA_REQUIRE(false, "wipa_embed_layernorm: bad dtype %d", y_dtype);
-    WIPA_LAUNCH_CHECK();
-    return WIPA_OK;
-}
-
-extern "C" int wipa_greedy_step_embed(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
-                                      int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter,
-                                      int n_init, int eot, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
-                                      const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w,
-                                      const float* ln_b, void* y, int y_dtype, int D, float eps, wipa_stream_t stream) {
-    WIPA_REQUIRE(logits && mask_first && mask_always && tokens && pos_dev && posd_dev && done_counter && sum_logprobs && not_done &&
-                     tok_emb && pos_emb && x && ln_w && ln_b && y && B > 0 && n_ctx > 0, "wipa_greedy_step_embed: bad arguments");
-    const int rc = tail_params_check("wipa_greedy_step_embed", logits, V, ldl, mask_first, mask_always, D, emb_dtype, emb_scale);
-    if (rc != WIPA_OK) return rc;
-    TailArgs<false> q = {};
-    q.logits = logits; q.ldl = ldl; q.V = V; q.mask_first = mask_first; q.mask_always = mask_always;
-    q.tokens = tokens; q.ld_tok = ld_tok; q.pos = pos_dev; q.posd = posd_dev; q.done_counter = done_counter;
-    q.n_init = n_init; q.eot = eot; q.n_ctx = n_ctx; q.sum_logprobs = sum_logprobs; q.not_done = not_done;
-    q.emb = tok_emb; q.emb_dtype = emb_dtype; q.emb_scale = emb_scale; q.pos_emb = pos_emb;
-    q.x = x; q.ln_w = ln_w; q.ln_b = ln_b; q.y = y; q.D = D; q.eps = eps;
-    if (y_dtype == WIPA_F32) hipLaunchKernelGGL((greedy_tail_kernel<float>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, q);
-    else if (y_dtype == WIPA_BF16) hipLaunchKernelGGL((greedy_tail_kernel<__bf16>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, q);
-    else WIPA_REQUIRE(false, "wipa_greedy_step_embed: bad dtype %d", y_dtype);
-    WIPA_LAUNCH_CHECK();
-    return WIPA_OK;
-}
-
-extern "C" int wipa_greedy_step_embed_partials(const float* partials, int n_parts, int B, int32_t* tokens, int64_t ld_tok, int32_t* pos_dev,
-                                               int64_t* posd_dev, int32_t* done_counter, int n_init, int eot, float* sum_logprobs,
-                                               int32_t* not_done, const void* tok_emb, int emb_dtype, const float* emb_scale,
-                                               const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y,
-                                               int y_dtype, int D, float eps, wipa_stream_t stream) {
-    WIPA_REQUIRE(partials && n_parts > 0 && tokens && pos_dev && posd_dev && done_counter && sum_logprobs && not_done && tok_emb && pos_emb && x &&
-                     ln_w && ln_b && y && B > 0 && n_ctx > 0, "wipa_greedy_step_embed_partials: bad arguments");
-    const int rc = tail_params_check("wipa_greedy_step_embed_partials", nullptr, 0, 0, nullptr, nullptr, D, emb_dtype, emb_scale);
-    if (rc != WIPA_OK) return rc;
-    TailArgs<false> q = {};
-    q.part = partials; q.n_part = n_parts;
-    q.tokens = tokens; q.ld_tok = ld_tok; q.pos = pos_dev; q.posd = posd_dev; q.done_counter = done_counter;
-    q.n_init = n_init; q.eot = eot; q.n_ctx = n_ctx; q.sum_logprobs = sum_logprobs; q.not_done = not_done;
-    q.emb = tok_emb; q.emb_dtype = emb_dtype; q.emb_scale = emb_scale; q.pos_emb = pos_emb;
-    q.x = x; q.ln_w = ln_w; q.ln_b = ln_b; q.y = y; q.D = D; q.eps = eps;
-    if (y_dtype == WIPA_F32) hipLaunchKernelGGL((greedy_tail_kernel<float>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, q);
-    else if (y_dtype == WIPA_BF16) hipLaunchKernelGGL((greedy_tail_kernel<__bf16>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, q);
-    else WIPA_REQUIRE(false, "wipa_greedy_step_embed_partials: bad dtype %d", y_dtype);
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;
 }
@@ -1200,11 +1063,23 @@ static int rules_check(const char* who, const wipa_decode_rules* rules, const fl
                  "%s: need eot < timestamp_begin < V and no_timestamps below timestamp_begin (eot=%d timestamp_begin=%d no_timestamps=%d V=%d)", who,
                  eot, rules->timestamp_begin, rules->no_timestamps, V);
     // the rules live in the register-resident row scan only
-    WIPA_REQUIRE(V <= 4 * GS_MAXQ * GS_THREADS && ldl % 4 == 0 && ((uintptr_t)logits % 16) == 0 && ((uintptr_t)mask_first % 16) == 0 &&
-                     ((uintptr_t)mask_always % 16) == 0, "%s: vocabulary of %d / unaligned logits or masks", who, V);
+    WIPA_REQUIRE(reg_scan_ok(logits, V, ldl, mask_first, mask_always), "%s: vocabulary of %d / unaligned logits or masks", who, V);
     out->tb = rules->timestamp_begin;
     out->nt = rules->no_timestamps;
     out->max_init = rules->max_initial_timestamp_index;
+    return WIPA_OK;
+}
+
+// rules may be NULL: the plain filtered row, every column on the text side
+static int sample_check(const char* who, const wipa_decode_rules* rules, const void* sample, const float* logits, int V, int64_t ldl,
+                        const float* mask_first, const float* mask_always, int eot, int n_ctx, RulesDev* out) {
+    WIPA_REQUIRE(sample && ((uintptr_t)sample % 4) == 0, "%s: null / unaligned sampling record", who);
+    WIPA_REQUIRE(n_ctx <= 65536, "%s: positions above 65535 do not fit the draw's counter", who);
+    if (rules) return rules_check(who, rules, logits, V, ldl, mask_first, mask_always, eot, out);
+    WIPA_REQUIRE(V > 0 && reg_scan_ok(logits, V, ldl, mask_first, mask_always), "%s: vocabulary of %d / unaligned logits or masks", who, V);
+    out->tb = V;
+    out->nt = -1;
+    out->max_init = -1;
     return WIPA_OK;
 }
 
@@ -1218,31 +1093,6 @@ extern "C" int wipa_timestamp_step(const float* logits, int64_t ldl, int B, int 
     if (rc != WIPA_OK) return rc;
     hipLaunchKernelGGL(timestamp_step_kernel, dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, logits, ldl, V, mask_first, mask_always, tokens,
                        ld_tok, pos_dev, n_init, eot, r, sum_logprobs, not_done);
-    WIPA_LAUNCH_CHECK();
-    return WIPA_OK;
-}
-
-extern "C" int wipa_timestamp_step_embed(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
-                                         int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter,
-                                         int n_init, int eot, const wipa_decode_rules* rules, float* sum_logprobs, int32_t* not_done,
-                                         const void* tok_emb, int emb_dtype, const float* emb_scale, const float* pos_emb, int n_ctx, float* x,
-                                         const float* ln_w, const float* ln_b, void* y, int y_dtype, int D, float eps, wipa_stream_t stream) {
-    WIPA_REQUIRE(logits && mask_first && mask_always && tokens && pos_dev && posd_dev && done_counter && sum_logprobs && not_done &&
-                     tok_emb && pos_emb && x && ln_w && ln_b && y && B > 0 && n_ctx > 0 && n_init >= 1, "wipa_timestamp_step_embed: bad arguments");
-    int rc = tail_params_check("wipa_timestamp_step_embed", logits, V, ldl, mask_first, mask_always, D, emb_dtype, emb_scale);
-    if (rc != WIPA_OK) return rc;
-    RulesDev r;
-    rc = rules_check("wipa_timestamp_step_embed", rules, logits, V, ldl, mask_first, mask_always, eot, &r);
-    if (rc != WIPA_OK) return rc;
-    TailArgs<false> q = {};
-    q.logits = logits; q.ldl = ldl; q.V = V; q.mask_first = mask_first; q.mask_always = mask_always;
-    q.tokens = tokens; q.ld_tok = ld_tok; q.pos = pos_dev; q.posd = posd_dev; q.done_counter = done_counter;
-    q.n_init = n_init; q.eot = eot; q.n_ctx = n_ctx; q.sum_logprobs = sum_logprobs; q.not_done = not_done;
-    q.emb = tok_emb; q.emb_dtype = emb_dtype; q.emb_scale = emb_scale; q.pos_emb = pos_emb;
-    q.x = x; q.ln_w = ln_w; q.ln_b = ln_b; q.y = y; q.D = D; q.eps = eps;
-    if (y_dtype == WIPA_F32) hipLaunchKernelGGL((timestamp_tail_kernel<float>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, q, r);
-    else if (y_dtype == WIPA_BF16) hipLaunchKernelGGL((timestamp_tail_kernel<__bf16>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, q, r);
-    else WIPA_REQUIRE(false, "wipa_timestamp_step_embed: bad dtype %d", y_dtype);
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;
 }
@@ -1271,17 +1121,26 @@ extern "C" int wipa_sample_record_fill(void* host_record, size_t record_bytes, u
     return WIPA_OK;
 }
 
-// rules may be NULL: the plain filtered row, every column on the text side
-static int sample_check(const char* who, const wipa_decode_rules* rules, const void* sample, const float* logits, int V, int64_t ldl,
-                        const float* mask_first, const float* mask_always, int eot, int n_ctx, RulesDev* out) {
-    WIPA_REQUIRE(sample && ((uintptr_t)sample % 4) == 0, "%s: null / unaligned sampling record", who);
-    WIPA_REQUIRE(n_ctx <= 65536, "%s: positions above 65535 do not fit the draw's counter", who);
-    if (rules) return rules_check(who, rules, logits, V, ldl, mask_first, mask_always, eot, out);
-    WIPA_REQUIRE(V > 0 && V <= 4 * GS_MAXQ * GS_THREADS && ldl % 4 == 0 && ((uintptr_t)logits % 16) == 0 && ((uintptr_t)mask_first % 16) == 0 &&
-                     ((uintptr_t)mask_always % 16) == 0, "%s: vocabulary of %d / unaligned logits or masks", who, V);
-    out->tb = V;
-    out->nt = -1;
-    out->max_init = -1;
+// wipa_sample_step and, with starts_dev (left-padded prompt rows: the draw's counter takes the row's own position *pos_dev - starts_dev[b]),
+// wipa_sample_step_ragged
+static int sample_step(const char* who, const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
+                       int32_t* tokens, int64_t ld_tok, const int32_t* pos_dev, int n_init, int eot, const wipa_decode_rules* rules,
+                       const void* sample, const int32_t* starts_dev, float* sum_logprobs, int32_t* not_done, wipa_stream_t stream) {
+    RulesDev r;
+    const int rc = sample_check(who, rules, sample, logits, V, ldl, mask_first, mask_always, eot, 0, &r);
+    if (rc != WIPA_OK) return rc;
+#define SAMPLE_STEP(RULES, RAGGED)                                                                                                         \
+    hipLaunchKernelGGL((sample_step_kernel<RULES, RAGGED>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, logits, ldl, V, mask_first, \
+                       mask_always, tokens, ld_tok, pos_dev, n_init, eot, r, (const uint32_t*)sample, sum_logprobs, not_done, starts_dev)
+    if (starts_dev) {
+        if (rules) SAMPLE_STEP(true, true);
+        else SAMPLE_STEP(false, true);
+    } else {
+        if (rules) SAMPLE_STEP(true, false);
+        else SAMPLE_STEP(false, false);
+    }
+#undef SAMPLE_STEP
+    WIPA_LAUNCH_CHECK();
     return WIPA_OK;
 }
 
@@ -1290,36 +1149,141 @@ extern "C" int wipa_sample_step(const float* logits, int64_t ldl, int B, int V, 
                                 const void* sample, float* sum_logprobs, int32_t* not_done, wipa_stream_t stream) {
     WIPA_REQUIRE(logits && mask_first && mask_always && tokens && pos_dev && sum_logprobs && not_done && B > 0 && n_init >= 1,
                  "wipa_sample_step: bad arguments");
-    RulesDev r;
-    const int rc = sample_check("wipa_sample_step", rules, sample, logits, V, ldl, mask_first, mask_always, eot, 0, &r);
-    if (rc != WIPA_OK) return rc;
-    if (rules)
-        hipLaunchKernelGGL((sample_step_kernel<true>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, logits, ldl, V, mask_first, mask_always,
-                           tokens, ld_tok, pos_dev, n_init, eot, r, (const uint32_t*)sample, sum_logprobs, not_done, (const int32_t*)nullptr);
-    else
-        hipLaunchKernelGGL((sample_step_kernel<false>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, logits, ldl, V, mask_first, mask_always,
-                           tokens, ld_tok, pos_dev, n_init, eot, r, (const uint32_t*)sample, sum_logprobs, not_done, (const int32_t*)nullptr);
-    WIPA_LAUNCH_CHECK();
-    return WIPA_OK;
+    return sample_step("wipa_sample_step", logits, ldl, B, V, mask_first, mask_always, tokens, ld_tok, pos_dev, n_init, eot, rules, sample, nullptr,
+                       sum_logprobs, not_done, stream);
 }
 
-// wipa_sample_step for left-padded prompt rows: the draw's counter takes the row's own position *pos_dev - starts_dev[b]
 extern "C" int wipa_sample_step_ragged(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
                                        int32_t* tokens, int64_t ld_tok, const int32_t* pos_dev, int n_init, int eot, const wipa_decode_rules* rules,
                                        const void* sample, const int32_t* starts_dev, float* sum_logprobs, int32_t* not_done, wipa_stream_t stream) {
     WIPA_REQUIRE(logits && mask_first && mask_always && tokens && pos_dev && starts_dev && sum_logprobs && not_done && B > 0 && n_init >= 1,
                  "wipa_sample_step_ragged: bad arguments (starts_dev is required)");
-    RulesDev r;
-    const int rc = sample_check("wipa_sample_step_ragged", rules, sample, logits, V, ldl, mask_first, mask_always, eot, 0, &r);
+    return sample_step("wipa_sample_step_ragged", logits, ldl, B, V, mask_first, mask_always, tokens, ld_tok, pos_dev, n_init, eot, rules, sample,
+                       starts_dev, sum_logprobs, not_done, stream);
+}
+
+// ------------------------------------------------------------------ the step's tail and head: one fill, one check, one launcher
+// the logits group stays unset for the head and the partials tail, the step-state group for the head
+static TailParams tail_params(const float* logits, int64_t ldl, int V, const float* mask_first, const float* mask_always, int32_t* tokens,
+                              int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init, int eot, float* sum_logprobs,
+                              int32_t* not_done, const void* tok_emb, int emb_dtype, const float* emb_scale, const float* pos_emb, int n_ctx,
+                              float* x, const float* ln_w, const float* ln_b, void* y, int D, float eps) {
+    TailParams q = {};
+    q.logits = logits; q.ldl = ldl; q.V = V; q.mask_first = mask_first; q.mask_always = mask_always;
+    q.tokens = tokens; q.ld_tok = ld_tok; q.pos = pos_dev; q.posd = posd_dev; q.done_counter = done_counter;
+    q.n_init = n_init; q.eot = eot; q.n_ctx = n_ctx; q.sum_logprobs = sum_logprobs; q.not_done = not_done;
+    q.emb = tok_emb; q.emb_dtype = emb_dtype; q.emb_scale = emb_scale; q.pos_emb = pos_emb;
+    q.x = x; q.ln_w = ln_w; q.ln_b = ln_b; q.y = y; q.D = D; q.eps = eps;
+    return q;
+}
+
+enum TailKind { TAIL_HEAD, TAIL_STEP };  // embed_layernorm_kernel alone | a step's last launch
+
+template <typename TO, bool RAGGED>
+static void launch_tail_as(TailKind kind, const TailParams& tp, int B, bool rules, RulesDev r, const uint32_t* rec, const int32_t* starts,
+                           hipStream_t s) {
+    TailArgs<RAGGED> q = {};
+    static_cast<TailParams&>(q) = tp;
+    if constexpr (RAGGED) q.start = starts;
+    const dim3 grid(B), block(GS_THREADS);
+    if (kind == TAIL_HEAD) hipLaunchKernelGGL((embed_layernorm_kernel<TO, RAGGED>), grid, dim3(256), 0, s, q);
+    else if (rec && rules) hipLaunchKernelGGL((sample_tail_kernel<TO, true, RAGGED>), grid, block, 0, s, q, r, rec);
+    else if (rec) hipLaunchKernelGGL((sample_tail_kernel<TO, false, RAGGED>), grid, block, 0, s, q, r, rec);
+    else if (rules) hipLaunchKernelGGL((timestamp_tail_kernel<TO, RAGGED>), grid, block, 0, s, q, r);
+    else hipLaunchKernelGGL((greedy_tail_kernel<TO, RAGGED>), grid, block, 0, s, q);
+}
+
+// The checks every tail / head entry point shares, then the launch of the instantiation that (y_dtype, rules, sample, starts_dev) name.
+// The callers have checked their own pointers; rules, sample and starts_dev may each be NULL.
+static int launch_tail(const char* who, TailKind kind, const TailParams& tp, int B, int y_dtype, const wipa_decode_rules* rules, const void* sample,
+                       const int32_t* starts_dev, wipa_stream_t stream) {
+    WIPA_REQUIRE(tp.D % 4 == 0 && tp.D > 0 && tp.D <= 2048, "%s: D=%d must be a multiple of 4 and <= 2048", who, tp.D);
+    WIPA_REQUIRE(tp.emb_dtype == WIPA_F32 || tp.emb_dtype == WIPA_BF16 || (tp.emb_dtype == WIPA_FP8_E4M3 && tp.emb_scale),
+                 "%s: bad embedding dtype %d", who, tp.emb_dtype);
+    if (tp.logits)
+        WIPA_REQUIRE(reg_scan_ok(tp.logits, tp.V, tp.ldl, tp.mask_first, tp.mask_always), "%s: vocabulary of %d / unaligned logits or masks", who,
+                     tp.V);
+    RulesDev r = {tp.V, -1, -1};
+    int rc = WIPA_OK;
+    if (sample) rc = sample_check(who, rules, sample, tp.logits, tp.V, tp.ldl, tp.mask_first, tp.mask_always, tp.eot, tp.n_ctx, &r);
+    else if (rules) rc = rules_check(who, rules, tp.logits, tp.V, tp.ldl, tp.mask_first, tp.mask_always, tp.eot, &r);
     if (rc != WIPA_OK) return rc;
-    if (rules)
-        hipLaunchKernelGGL((sample_step_kernel<true, true>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, logits, ldl, V, mask_first,
-                           mask_always, tokens, ld_tok, pos_dev, n_init, eot, r, (const uint32_t*)sample, sum_logprobs, not_done, starts_dev);
-    else
-        hipLaunchKernelGGL((sample_step_kernel<false, true>), dim3(B), dim3(GS_THREADS), 0, (hipStream_t)stream, logits, ldl, V, mask_first,
-                           mask_always, tokens, ld_tok, pos_dev, n_init, eot, r, (const uint32_t*)sample, sum_logprobs, not_done, starts_dev);
+    WIPA_REQUIRE(y_dtype == WIPA_F32 || y_dtype == WIPA_BF16, "%s: bad dtype %d", who, y_dtype);
+    const uint32_t* rec = (const uint32_t*)sample;
+    hipStream_t s = (hipStream_t)stream;
+    const bool f32 = y_dtype == WIPA_F32;
+    if (starts_dev) {
+        if (f32) launch_tail_as<float, true>(kind, tp, B, rules != nullptr, r, rec, starts_dev, s);
+        else launch_tail_as<__bf16, true>(kind, tp, B, rules != nullptr, r, rec, starts_dev, s);
+    } else {
+        if (f32) launch_tail_as<float, false>(kind, tp, B, rules != nullptr, r, rec, nullptr, s);
+        else launch_tail_as<__bf16, false>(kind, tp, B, rules != nullptr, r, rec, nullptr, s);
+    }
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;
+}
+
+// wipa_embed_layernorm and, with starts_dev, wipa_embed_layernorm_ragged
+static int embed_layernorm(const char* who, const int32_t* tokens, int64_t ld_tok, int B, const int32_t* pos_dev, const int32_t* starts_dev,
+                           const void* tok_emb, int emb_dtype, const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w,
+                           const float* ln_b, void* y, int y_dtype, int D, float eps, wipa_stream_t stream) {
+    const TailParams tp = tail_params(nullptr, 0, 0, nullptr, nullptr, const_cast<int32_t*>(tokens), ld_tok, const_cast<int32_t*>(pos_dev), nullptr,
+                                      nullptr, 0, 0, nullptr, nullptr, tok_emb, emb_dtype, emb_scale, pos_emb, n_ctx, x, ln_w, ln_b, y, D, eps);
+    return launch_tail(who, TAIL_HEAD, tp, B, y_dtype, nullptr, nullptr, starts_dev, stream);
+}
+
+extern "C" int wipa_embed_layernorm(const int32_t* tokens, int64_t ld_tok, int B, const int32_t* pos_dev, const void* tok_emb,
+                                    int emb_dtype, const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w,
+                                    const float* ln_b, void* y, int y_dtype, int D, float eps, wipa_stream_t stream) {
+    WIPA_REQUIRE(tokens && pos_dev && tok_emb && pos_emb && x && ln_w && ln_b && y && B > 0 && n_ctx > 0, "wipa_embed_layernorm: bad arguments");
+    return embed_layernorm("wipa_embed_layernorm", tokens, ld_tok, B, pos_dev, nullptr, tok_emb, emb_dtype, emb_scale, pos_emb, n_ctx, x, ln_w, ln_b,
+                           y, y_dtype, D, eps, stream);
+}
+
+extern "C" int wipa_embed_layernorm_ragged(const int32_t* tokens, int64_t ld_tok, int B, const int32_t* pos_dev, const int32_t* starts_dev,
+                                           const void* tok_emb, int emb_dtype, const float* emb_scale, const float* pos_emb, int n_ctx, float* x,
+                                           const float* ln_w, const float* ln_b, void* y, int y_dtype, int D, float eps, wipa_stream_t stream) {
+    WIPA_REQUIRE(tokens && pos_dev && starts_dev && tok_emb && pos_emb && x && ln_w && ln_b && y && B > 0 && n_ctx > 0,
+                 "wipa_embed_layernorm_ragged: bad arguments (starts_dev is required)");
+    return embed_layernorm("wipa_embed_layernorm_ragged", tokens, ld_tok, B, pos_dev, starts_dev, tok_emb, emb_dtype, emb_scale, pos_emb, n_ctx, x,
+                           ln_w, ln_b, y, y_dtype, D, eps, stream);
+}
+
+// The step's last launch on written logits (declared in wipa_common.h for the runtime; not exported): rules, sample and starts_dev
+// may each be NULL, and name the exported entry point whose checks and error prefix apply
+int wipa_step_tail(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always, int32_t* tokens,
+                   int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init, int eot, const wipa_decode_rules* rules,
+                   const void* sample, const int32_t* starts_dev, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
+                   const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y, int y_dtype,
+                   int D, float eps, wipa_stream_t stream) {
+    const char* who = starts_dev ? "wipa_step_embed_ragged" : sample ? "wipa_sample_step_embed" : rules ? "wipa_timestamp_step_embed"
+                                                                                                   : "wipa_greedy_step_embed";
+    const bool plain = !rules && !sample && !starts_dev;  // wipa_greedy_step_embed alone takes n_init below 1
+    WIPA_REQUIRE(logits && mask_first && mask_always && tokens && pos_dev && posd_dev && done_counter && sum_logprobs && not_done && tok_emb &&
+                     pos_emb && x && ln_w && ln_b && y && B > 0 && n_ctx > 0 && (plain || n_init >= 1),
+                 "%s: bad arguments%s", who, starts_dev ? " (starts_dev is required)" : "");
+    const TailParams tp = tail_params(logits, ldl, V, mask_first, mask_always, tokens, ld_tok, pos_dev, posd_dev, done_counter, n_init, eot,
+                                      sum_logprobs, not_done, tok_emb, emb_dtype, emb_scale, pos_emb, n_ctx, x, ln_w, ln_b, y, D, eps);
+    return launch_tail(who, TAIL_STEP, tp, B, y_dtype, rules, sample, starts_dev, stream);
+}
+
+extern "C" int wipa_greedy_step_embed(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
+                                      int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter,
+                                      int n_init, int eot, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
+                                      const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w,
+                                      const float* ln_b, void* y, int y_dtype, int D, float eps, wipa_stream_t stream) {
+    return wipa_step_tail(logits, ldl, B, V, mask_first, mask_always, tokens, ld_tok, pos_dev, posd_dev, done_counter, n_init, eot, nullptr, nullptr,
+                          nullptr, sum_logprobs, not_done, tok_emb, emb_dtype, emb_scale, pos_emb, n_ctx, x, ln_w, ln_b, y, y_dtype, D, eps, stream);
+}
+
+extern "C" int wipa_timestamp_step_embed(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
+                                         int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter,
+                                         int n_init, int eot, const wipa_decode_rules* rules, float* sum_logprobs, int32_t* not_done,
+                                         const void* tok_emb, int emb_dtype, const float* emb_scale, const float* pos_emb, int n_ctx, float* x,
+                                         const float* ln_w, const float* ln_b, void* y, int y_dtype, int D, float eps, wipa_stream_t stream) {
+    WIPA_REQUIRE(rules, "wipa_timestamp_step_embed: null rules");
+    return wipa_step_tail(logits, ldl, B, V, mask_first, mask_always, tokens, ld_tok, pos_dev, posd_dev, done_counter, n_init, eot, rules, nullptr,
+                          nullptr, sum_logprobs, not_done, tok_emb, emb_dtype, emb_scale, pos_emb, n_ctx, x, ln_w, ln_b, y, y_dtype, D, eps, stream);
 }
 
 extern "C" int wipa_sample_step_embed(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
@@ -1328,93 +1292,35 @@ extern "C" int wipa_sample_step_embed(const float* logits, int64_t ldl, int B, i
                                       int32_t* not_done, const void* tok_emb, int emb_dtype, const float* emb_scale, const float* pos_emb,
                                       int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y, int y_dtype, int D, float eps,
                                       wipa_stream_t stream) {
-    WIPA_REQUIRE(logits && mask_first && mask_always && tokens && pos_dev && posd_dev && done_counter && sum_logprobs && not_done &&
-                     tok_emb && pos_emb && x && ln_w && ln_b && y && B > 0 && n_ctx > 0 && n_init >= 1, "wipa_sample_step_embed: bad arguments");
-    int rc = tail_params_check("wipa_sample_step_embed", logits, V, ldl, mask_first, mask_always, D, emb_dtype, emb_scale);
-    if (rc != WIPA_OK) return rc;
-    RulesDev r;
-    rc = sample_check("wipa_sample_step_embed", rules, sample, logits, V, ldl, mask_first, mask_always, eot, n_ctx, &r);
-    if (rc != WIPA_OK) return rc;
-    TailArgs<false> q = {};
-    q.logits = logits; q.ldl = ldl; q.V = V; q.mask_first = mask_first; q.mask_always = mask_always;
-    q.tokens = tokens; q.ld_tok = ld_tok; q.pos = pos_dev; q.posd = posd_dev; q.done_counter = done_counter;
-    q.n_init = n_init; q.eot = eot; q.n_ctx = n_ctx; q.sum_logprobs = sum_logprobs; q.not_done = not_done;
-    q.emb = tok_emb; q.emb_dtype = emb_dtype; q.emb_scale = emb_scale; q.pos_emb = pos_emb;
-    q.x = x; q.ln_w = ln_w; q.ln_b = ln_b; q.y = y; q.D = D; q.eps = eps;
-    const uint32_t* rec = (const uint32_t*)sample;
-    const dim3 grid(B), block(GS_THREADS);
-    hipStream_t s = (hipStream_t)stream;
-    if (y_dtype == WIPA_F32 && rules) hipLaunchKernelGGL((sample_tail_kernel<float, true>), grid, block, 0, s, q, r, rec);
-    else if (y_dtype == WIPA_F32) hipLaunchKernelGGL((sample_tail_kernel<float, false>), grid, block, 0, s, q, r, rec);
-    else if (y_dtype == WIPA_BF16 && rules) hipLaunchKernelGGL((sample_tail_kernel<__bf16, true>), grid, block, 0, s, q, r, rec);
-    else if (y_dtype == WIPA_BF16) hipLaunchKernelGGL((sample_tail_kernel<__bf16, false>), grid, block, 0, s, q, r, rec);
-    else WIPA_REQUIRE(false, "wipa_sample_step_embed: bad dtype %d", y_dtype);
-    WIPA_LAUNCH_CHECK();
-    return WIPA_OK;
+    WIPA_REQUIRE(sample, "wipa_sample_step_embed: null / unaligned sampling record");
+    return wipa_step_tail(logits, ldl, B, V, mask_first, mask_always, tokens, ld_tok, pos_dev, posd_dev, done_counter, n_init, eot, rules, sample,
+                          nullptr, sum_logprobs, not_done, tok_emb, emb_dtype, emb_scale, pos_emb, n_ctx, x, ln_w, ln_b, y, y_dtype, D, eps, stream);
 }
 
-// ------------------------------------------------------------------ ragged prompts: the RAGGED instantiations of the tails
-extern "C" int wipa_embed_layernorm_ragged(const int32_t* tokens, int64_t ld_tok, int B, const int32_t* pos_dev, const int32_t* starts_dev,
-                                           const void* tok_emb, int emb_dtype, const float* emb_scale, const float* pos_emb, int n_ctx, float* x,
-                                           const float* ln_w, const float* ln_b, void* y, int y_dtype, int D, float eps, wipa_stream_t stream) {
-    WIPA_REQUIRE(tokens && pos_dev && starts_dev && tok_emb && pos_emb && x && ln_w && ln_b && y && B > 0 && n_ctx > 0,
-                 "wipa_embed_layernorm_ragged: bad arguments (starts_dev is required)");
-    const int rc = tail_params_check("wipa_embed_layernorm_ragged", nullptr, 0, 0, nullptr, nullptr, D, emb_dtype, emb_scale);
-    if (rc != WIPA_OK) return rc;
-    TailArgs<true> q = {};
-    q.tokens = const_cast<int32_t*>(tokens); q.ld_tok = ld_tok; q.pos = const_cast<int32_t*>(pos_dev); q.n_ctx = n_ctx;
-    q.emb = tok_emb; q.emb_dtype = emb_dtype; q.emb_scale = emb_scale; q.pos_emb = pos_emb;
-    q.x = x; q.ln_w = ln_w; q.ln_b = ln_b; q.y = y; q.D = D; q.eps = eps;
-    q.start = starts_dev;
-    if (y_dtype == WIPA_F32) hipLaunchKernelGGL((embed_layernorm_kernel<float, true>), dim3(B), dim3(256), 0, (hipStream_t)stream, q);
-    else if (y_dtype == WIPA_BF16) hipLaunchKernelGGL((embed_layernorm_kernel<__bf16, true>), dim3(B), dim3(256), 0, (hipStream_t)stream, q);
-    else WIPA_REQUIRE(false, "wipa_embed_layernorm_ragged: bad dtype %d", y_dtype);
-    WIPA_LAUNCH_CHECK();
-    return WIPA_OK;
-}
-
+// the RAGGED instantiations of the tails (left-padded prompt rows)
 extern "C" int wipa_step_embed_ragged(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
                                       int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter,
                                       int n_init, int eot, const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev,
                                       float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype, const float* emb_scale,
                                       const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y, int y_dtype,
                                       int D, float eps, wipa_stream_t stream) {
-    WIPA_REQUIRE(logits && mask_first && mask_always && tokens && pos_dev && posd_dev && done_counter && starts_dev && sum_logprobs && not_done &&
-                     tok_emb && pos_emb && x && ln_w && ln_b && y && B > 0 && n_ctx > 0 && n_init >= 1,
-                 "wipa_step_embed_ragged: bad arguments (starts_dev is required)");
-    WIPA_REQUIRE(y_dtype == WIPA_F32 || y_dtype == WIPA_BF16, "wipa_step_embed_ragged: bad dtype %d", y_dtype);
-    int rc = tail_params_check("wipa_step_embed_ragged", logits, V, ldl, mask_first, mask_always, D, emb_dtype, emb_scale);
-    if (rc != WIPA_OK) return rc;
-    RulesDev r = {V, -1, -1};
-    if (sample) rc = sample_check("wipa_step_embed_ragged", rules, sample, logits, V, ldl, mask_first, mask_always, eot, n_ctx, &r);
-    else if (rules) rc = rules_check("wipa_step_embed_ragged", rules, logits, V, ldl, mask_first, mask_always, eot, &r);
-    if (rc != WIPA_OK) return rc;
-    TailArgs<true> q = {};
-    q.logits = logits; q.ldl = ldl; q.V = V; q.mask_first = mask_first; q.mask_always = mask_always;
-    q.tokens = tokens; q.ld_tok = ld_tok; q.pos = pos_dev; q.posd = posd_dev; q.done_counter = done_counter;
-    q.n_init = n_init; q.eot = eot; q.n_ctx = n_ctx; q.sum_logprobs = sum_logprobs; q.not_done = not_done;
-    q.emb = tok_emb; q.emb_dtype = emb_dtype; q.emb_scale = emb_scale; q.pos_emb = pos_emb;
-    q.x = x; q.ln_w = ln_w; q.ln_b = ln_b; q.y = y; q.D = D; q.eps = eps;
-    q.start = starts_dev;
-    const uint32_t* rec = (const uint32_t*)sample;
-    const dim3 grid(B), block(GS_THREADS);
-    hipStream_t s = (hipStream_t)stream;
-    const bool f32 = y_dtype == WIPA_F32;
-    if (sample && rules) {
-        if (f32) hipLaunchKernelGGL((sample_tail_kernel<float, true, true>), grid, block, 0, s, q, r, rec);
-        else hipLaunchKernelGGL((sample_tail_kernel<__bf16, true, true>), grid, block, 0, s, q, r, rec);
-    } else if (sample) {
-        if (f32) hipLaunchKernelGGL((sample_tail_kernel<float, false, true>), grid, block, 0, s, q, r, rec);
-        else hipLaunchKernelGGL((sample_tail_kernel<__bf16, false, true>), grid, block, 0, s, q, r, rec);
-    } else if (rules) {
-        if (f32) hipLaunchKernelGGL((timestamp_tail_kernel<float, true>), grid, block, 0, s, q, r);
-        else hipLaunchKernelGGL((timestamp_tail_kernel<__bf16, true>), grid, block, 0, s, q, r);
-    } else {
-        if (f32) hipLaunchKernelGGL((greedy_tail_kernel<float, true>), grid, block, 0, s, q);
-        else hipLaunchKernelGGL((greedy_tail_kernel<__bf16, true>), grid, block, 0, s, q);
-    }
-    WIPA_LAUNCH_CHECK();
-    return WIPA_OK;
+    WIPA_REQUIRE(starts_dev, "wipa_step_embed_ragged: bad arguments (starts_dev is required)");
+    return wipa_step_tail(logits, ldl, B, V, mask_first, mask_always, tokens, ld_tok, pos_dev, posd_dev, done_counter, n_init, eot, rules, sample,
+                          starts_dev, sum_logprobs, not_done, tok_emb, emb_dtype, emb_scale, pos_emb, n_ctx, x, ln_w, ln_b, y, y_dtype, D, eps, stream);
+}
+
+// the tail on wipa_logits_greedy's per-wave partials: no logits, so no rules, no draw and no ragged rows
+extern "C" int wipa_greedy_step_embed_partials(const float* partials, int n_parts, int B, int32_t* tokens, int64_t ld_tok, int32_t* pos_dev,
+                                               int64_t* posd_dev, int32_t* done_counter, int n_init, int eot, float* sum_logprobs,
+                                               int32_t* not_done, const void* tok_emb, int emb_dtype, const float* emb_scale,
+                                               const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y,
+                                               int y_dtype, int D, float eps, wipa_stream_t stream) {
+    WIPA_REQUIRE(partials && n_parts > 0 && tokens && pos_dev && posd_dev && done_counter && sum_logprobs && not_done && tok_emb && pos_emb && x &&
+                     ln_w && ln_b && y && B > 0 && n_ctx > 0, "wipa_greedy_step_embed_partials: bad arguments");
+    TailParams tp = tail_params(nullptr, 0, 0, nullptr, nullptr, tokens, ld_tok, pos_dev, posd_dev, done_counter, n_init, eot, sum_logprobs, not_done,
+                                tok_emb, emb_dtype, emb_scale, pos_emb, n_ctx, x, ln_w, ln_b, y, D, eps);
+    tp.part = partials; tp.n_part = n_parts;
+    return launch_tail("wipa_greedy_step_embed_partials", TAIL_STEP, tp, B, y_dtype, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int wipa_sample_noise(const void* sample, int row, int p, int V, float* out, wipa_stream_t stream) {

@@ -588,32 +588,13 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
     RT_CALL(gemm(ln, d, w[0], d, logits, L.ld_logits, B, cfg->n_vocab, d, dt, WIPA_F32, nullptr, 0, nullptr, stream));
     if (tail) {
         // greedy update + embedding of the chosen token + first LayerNorm of the NEXT position + position advance: one launch
+        // (with t_rules the timestamp rules, with t_sample the draw, with t_starts the RAGGED tails: position embedding and sampling
+        // counter at the row's own position)
         const void* const* lw0 = w + WIPA_DEC_GLOBAL;
-        if (t_starts) {  // the RAGGED tails: position embedding and sampling counter at the row's own position
-            RT_CALL(wipa_step_embed_ragged(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, posd,
-                                           done_counter_of(st, L), n_init, eot, t_rules, t_sample, t_starts, (float*)(st + L.sum_logprobs),
-                                           (int32_t*)(st + L.not_done), w[0], emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], nctx, x_first,
-                                           (const float*)lw0[0], (const float*)lw0[1], ln, dt, d, 1e-5f, stream));
-            return WIPA_OK;
-        }
-        if (t_sample) {
-            RT_CALL(wipa_sample_step_embed(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, posd,
-                                           done_counter_of(st, L), n_init, eot, t_rules, t_sample, (float*)(st + L.sum_logprobs),
-                                           (int32_t*)(st + L.not_done), w[0], emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], nctx, x_first,
-                                           (const float*)lw0[0], (const float*)lw0[1], ln, dt, d, 1e-5f, stream));
-            return WIPA_OK;
-        }
-        if (t_rules) {
-            RT_CALL(wipa_timestamp_step_embed(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, posd,
-                                              done_counter_of(st, L), n_init, eot, t_rules, (float*)(st + L.sum_logprobs),
-                                              (int32_t*)(st + L.not_done), w[0], emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], nctx, x_first,
-                                              (const float*)lw0[0], (const float*)lw0[1], ln, dt, d, 1e-5f, stream));
-            return WIPA_OK;
-        }
-        RT_CALL(wipa_greedy_step_embed(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, posd,
-                                       done_counter_of(st, L), n_init, eot, (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), w[0],
-                                       emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], nctx, x_first, (const float*)lw0[0],
-                                       (const float*)lw0[1], ln, dt, d, 1e-5f, stream));
+        RT_CALL(wipa_step_tail(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, posd, done_counter_of(st, L),
+                               n_init, eot, t_rules, t_sample, t_starts, (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), w[0],
+                               emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], nctx, x_first, (const float*)lw0[0], (const float*)lw0[1], ln,
+                               dt, d, 1e-5f, stream));
         return WIPA_OK;
     }
     WIPA_REQUIRE(!t_rules && !t_sample && !t_starts, "decode step: the timestamp rules, sampling and ragged prompts need the fused tail (WIPA_DECODE_TAIL=0 is set)");
@@ -935,6 +916,54 @@ int rules_servable(const char* who, const wipa_model_cfg* cfg, int B, int eot, c
 std::mutex g_graph_mu;
 std::map<GraphKey, hipGraphExec_t> g_graphs;
 
+// the variant word of a step or prefill key: every switch that changes what enqueue_decode_step / enqueue_prefill enqueue for (cfg, B).
+// (The streaming launch's resident_groups argument is baked into the captured step too, but needs no term here: it is a function
+// of B, the width, the frame count and dec_cross_splits -- all in the key -- and of a budget that is constant per process.)
+// Read inside the call's RulesScope: logits_fused() looks at the rules, the sampling record and the starts of the call.
+bool lean_steps(const wipa_model_cfg* cfg, int B) { return !use_fused_step(cfg, B) && logits_fused(cfg, B); }
+int step_variant(const wipa_model_cfg* cfg, int B) {
+    return cfg->dtype * 2 + t_f32_split + 4 * decode_mode(cfg, B) + 16 * cfg->dec_w_dtype +
+           64 * cfg->dec_cross_absorbed * (absorbed_block_fused() ? 2 : 1) + 256 * (int)tail_fused() + 512 * (int)absorbed_merge_out() +
+           1024 * cfg->dec_cross_splits + 8192 * (int)lean_steps(cfg, B) +
+           16384 * (cfg->dec_cross_absorbed ? wipa_cross_absorbed_loop_variant() : 0);
+}
+// a key from the arguments of a decode call; the three rule terms are 0 without rules
+GraphKey graph_key(const wipa_model_cfg* cfg, const void* const* w, const void* state, const float* mask_first, const float* mask_always, int B,
+                   int n_init, int eot, int variant, int kind, const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev,
+                   const void* workspace) {
+    return GraphKey(state, (const void*)w, (const void*)mask_first, (const void*)mask_always, B, n_init, eot, variant, cfg->weights_generation, kind,
+                    rules ? rules->timestamp_begin : 0, rules ? rules->no_timestamps : 0, rules ? rules->max_initial_timestamp_index : 0, sample,
+                    (const void*)starts_dev, workspace);
+}
+// The executable graph cached under `key`.  When there is none, `enqueue` is captured on s (relaxed mode, nothing but kernel launches
+// between begin and end), instantiated and inserted; an enqueue that fails ends the capture, destroys the graph and hands its code back.
+template <typename Enqueue>
+int cached_graph(const GraphKey& key, hipStream_t s, Enqueue&& enqueue, hipGraphExec_t* out) {
+    hipGraphExec_t exec = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_graph_mu);
+        auto it = g_graphs.find(key);
+        if (it != g_graphs.end()) exec = it->second;
+    }
+    if (!exec) {
+        hipGraph_t graph = nullptr;
+        WIPA_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
+        const int rc = enqueue();
+        const hipError_t ee = hipStreamEndCapture(s, &graph);
+        if (rc != WIPA_OK) {
+            if (graph) hipGraphDestroy(graph);
+            return rc;
+        }
+        WIPA_CHECK_HIP(ee);
+        WIPA_CHECK_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+        WIPA_CHECK_HIP(hipGraphDestroy(graph));
+        std::lock_guard<std::mutex> lk(g_graph_mu);
+        g_graphs[key] = exec;
+    }
+    *out = exec;
+    return WIPA_OK;
+}
+
 }  // namespace
 
 extern "C" int wipa_profile_begin(wipa_stream_t stream) {
@@ -1107,7 +1136,7 @@ extern "C" int wipa_decoder_run_ragged(const wipa_model_cfg* cfg, const void* co
     if (step_needs_head(cfg, B)) RT_CALL(enqueue_step_head(cfg, w, st, L, B, stream));
     // every step of the call but the LAST is "lean" when the logits projection carries the greedy partials: its logits are not
     // written (state.logits holds those of the last step of a call, which is what callers read)
-    const bool lean_ok = !use_fused_step(cfg, B) && logits_fused(cfg, B);
+    const bool lean_ok = lean_steps(cfg, B);
     struct LeanScope {
         explicit LeanScope(bool v) { t_lean_logits = v; }
         ~LeanScope() { t_lean_logits = false; }
@@ -1120,40 +1149,13 @@ extern "C" int wipa_decoder_run_ragged(const wipa_model_cfg* cfg, const void* co
         return WIPA_OK;
     }
     WIPA_REQUIRE(s != nullptr, "wipa_decoder_run: graph capture needs a non-default stream");
-    // (the streaming launch's resident_groups argument is baked into the captured step too, but needs no term here: it is a function
-    // of B, the width, the frame count and dec_cross_splits -- all in the key -- and of a budget that is constant per process)
-    const int variant = cfg->dtype * 2 + t_f32_split + 4 * decode_mode(cfg, B) + 16 * cfg->dec_w_dtype + 64 * cfg->dec_cross_absorbed * (absorbed_block_fused() ? 2 : 1) + 256 * (int)tail_fused() + 512 * (int)absorbed_merge_out() + 1024 * cfg->dec_cross_splits + 8192 * (int)lean_ok + 16384 * (cfg->dec_cross_absorbed ? wipa_cross_absorbed_loop_variant() : 0);
+    const int variant = step_variant(cfg, B);
     auto step_graph = [&](bool lean, hipGraphExec_t* out) -> int {  // kind 0: the full step, 2: the lean one
-        hipGraphExec_t exec = nullptr;
-        const GraphKey key(state, (const void*)w, (const void*)mask_first, (const void*)mask_always, B, n_init, eot, variant, cfg->weights_generation,
-                           lean ? 2 : 0, rules ? rules->timestamp_begin : 0, rules ? rules->no_timestamps : 0,
-                           rules ? rules->max_initial_timestamp_index : 0, sample, (const void*)starts_dev, (const void*)nullptr);
-        {
-            std::lock_guard<std::mutex> lk(g_graph_mu);
-            auto it = g_graphs.find(key);
-            if (it != g_graphs.end()) exec = it->second;
-        }
-        if (!exec) {
-            hipGraph_t graph = nullptr;
-            WIPA_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
-            int rc;
-            {
-                LeanScope scope(lean);
-                rc = enqueue_decode_step(cfg, w, st, L, B, n_init, eot, mask_first, mask_always, stream);
-            }
-            const hipError_t ee = hipStreamEndCapture(s, &graph);
-            if (rc != WIPA_OK) {
-                if (graph) hipGraphDestroy(graph);
-                return rc;
-            }
-            WIPA_CHECK_HIP(ee);
-            WIPA_CHECK_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-            WIPA_CHECK_HIP(hipGraphDestroy(graph));
-            std::lock_guard<std::mutex> lk(g_graph_mu);
-            g_graphs[key] = exec;
-        }
-        *out = exec;
-        return WIPA_OK;
+        const GraphKey key = graph_key(cfg, w, state, mask_first, mask_always, B, n_init, eot, variant, lean ? 2 : 0, rules, sample, starts_dev, nullptr);
+        return cached_graph(key, s, [&]() -> int {
+            LeanScope scope(lean);
+            return enqueue_decode_step(cfg, w, st, L, B, n_init, eot, mask_first, mask_always, stream);
+        }, out);
     };
     hipGraphExec_t full = nullptr, lean = nullptr;
     RT_CALL(step_graph(false, &full));
@@ -1200,28 +1202,8 @@ extern "C" int wipa_decoder_prefill_sample(const wipa_model_cfg* cfg, const void
     WIPA_CHECK_HIP(hipMemsetAsync(done_counter_of(st, L), 0, sizeof(int32_t), s));  // as wipa_decoder_run: the tail's counter starts at zero
     if (!use_graph || s == nullptr || !graphs_allowed()) return enqueue();
     hipGraphExec_t exec = nullptr;
-    const GraphKey key(state, (const void*)w, (const void*)mask_first, (const void*)mask_always, B, n_init, eot, cfg->dtype * 2 + t_f32_split + 4 * decode_mode(cfg, B) + 16 * cfg->dec_w_dtype + 64 * cfg->dec_cross_absorbed * (absorbed_block_fused() ? 2 : 1) + 256 * (int)tail_fused() + 512 * (int)absorbed_merge_out() + 1024 * cfg->dec_cross_splits + 8192 * (int)(!use_fused_step(cfg, B) && logits_fused(cfg, B)) + 16384 * (cfg->dec_cross_absorbed ? wipa_cross_absorbed_loop_variant() : 0), cfg->weights_generation, 1,
-                       rules ? rules->timestamp_begin : 0, rules ? rules->no_timestamps : 0, rules ? rules->max_initial_timestamp_index : 0, sample, (const void*)nullptr, (const void*)nullptr);
-    {
-        std::lock_guard<std::mutex> lk(g_graph_mu);
-        auto it = g_graphs.find(key);
-        if (it != g_graphs.end()) exec = it->second;
-    }
-    if (!exec) {
-        hipGraph_t graph = nullptr;
-        WIPA_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
-        const int rc = enqueue();
-        const hipError_t ee = hipStreamEndCapture(s, &graph);
-        if (rc != WIPA_OK) {
-            if (graph) hipGraphDestroy(graph);
-            return rc;
-        }
-        WIPA_CHECK_HIP(ee);
-        WIPA_CHECK_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-        WIPA_CHECK_HIP(hipGraphDestroy(graph));
-        std::lock_guard<std::mutex> lk(g_graph_mu);
-        g_graphs[key] = exec;
-    }
+    RT_CALL(cached_graph(graph_key(cfg, w, state, mask_first, mask_always, B, n_init, eot, step_variant(cfg, B), 1, rules, sample, nullptr, nullptr), s,
+                         enqueue, &exec));
     WIPA_CHECK_HIP(hipGraphLaunch(exec, s));
     return WIPA_OK;
 }
@@ -1388,30 +1370,9 @@ extern "C" int wipa_decoder_prefill_ragged(const wipa_model_cfg* cfg, const void
     };
     if (!use_graph || s == nullptr || !graphs_allowed()) return enqueue();
     hipGraphExec_t exec = nullptr;
-    const GraphKey key(state, (const void*)w, (const void*)mask_first, (const void*)mask_always, B, P, eot,
-                       cfg->dtype * 2 + t_f32_split + 64 * cfg->dec_cross_absorbed, cfg->weights_generation, 3 + 16 * (sot_col + 1),
-                       rules ? rules->timestamp_begin : 0, rules ? rules->no_timestamps : 0, rules ? rules->max_initial_timestamp_index : 0, sample,
-                       (const void*)starts_dev, (const void*)workspace);
-    {
-        std::lock_guard<std::mutex> lk(g_graph_mu);
-        auto it = g_graphs.find(key);
-        if (it != g_graphs.end()) exec = it->second;
-    }
-    if (!exec) {
-        hipGraph_t graph = nullptr;
-        WIPA_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
-        const int rc = enqueue();
-        const hipError_t ee = hipStreamEndCapture(s, &graph);
-        if (rc != WIPA_OK) {
-            if (graph) hipGraphDestroy(graph);
-            return rc;
-        }
-        WIPA_CHECK_HIP(ee);
-        WIPA_CHECK_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-        WIPA_CHECK_HIP(hipGraphDestroy(graph));
-        std::lock_guard<std::mutex> lk(g_graph_mu);
-        g_graphs[key] = exec;
-    }
+    // the prompt pass has its own, shorter variant word
+    RT_CALL(cached_graph(graph_key(cfg, w, state, mask_first, mask_always, B, P, eot, cfg->dtype * 2 + t_f32_split + 64 * cfg->dec_cross_absorbed,
+                                   3 + 16 * (sot_col + 1), rules, sample, starts_dev, workspace), s, enqueue, &exec));
     WIPA_CHECK_HIP(hipGraphLaunch(exec, s));
     return WIPA_OK;
 }

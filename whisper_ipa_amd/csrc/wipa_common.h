@@ -20,6 +20,13 @@ int wipa_decode_fused_init();
 int wipa_gemm_init();
 // the absorbed cross-attention's loop variant of this call (WIPA_ABS_LOOP, cross_absorbed.hip): a term of the decode graph key
 int wipa_cross_absorbed_loop_variant();
+// the decode step's last launch on written logits (elementwise.hip): wipa_greedy_step_embed / wipa_timestamp_step_embed /
+// wipa_sample_step_embed / wipa_step_embed_ragged behind one argument list -- rules, sample and starts_dev may each be NULL
+int wipa_step_tail(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always, int32_t* tokens,
+                   int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init, int eot, const wipa_decode_rules* rules,
+                   const void* sample, const int32_t* starts_dev, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
+                   const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y, int y_dtype,
+                   int D, float eps, wipa_stream_t stream);
 
 #define WIPA_CHECK_HIP(expr)                                                        \
     do {                                                                            \
