@@ -273,6 +273,12 @@ int wipa_decode_cross_attn(const void* q, const void* kv, void* out, int B, int 
 int wipa_decode_cross_attn_multi(const void* q, const void* kv, void* out, int B, int H, int Tk, int n_q, int dtype,
                                  wipa_stream_t s);
 
+/* candidate groups: q / out as above for B rows, kv holds B / n_group clips and row b reads the cache of clip b / n_group -- the
+ * arithmetic of wipa_decode_cross_attn (n_q = 1) / wipa_decode_cross_attn_multi on the same bytes, in separate instantiations of their
+ * kernels.  n_group >= 1 and B % n_group == 0; n_group = 1 launches exactly what the ungrouped entry points launch. */
+int wipa_decode_cross_attn_grouped(const void* q, const void* kv, void* out, int B, int H, int Tk, int n_q, int n_group, int dtype,
+                                   wipa_stream_t s);
+
 /* ------------------------------------------------------------------ fused decode-step blocks (K11 / K12)
  * One decode step of mlx_whisper's ResidualAttentionBlock with a KV cache (DecodingTask._main_loop,
  * transcribe_single.py:55) in 5 launches per layer instead of 11: see csrc/decode_fused.hip.
@@ -321,6 +327,9 @@ typedef struct wipa_cross_block_desc {
     float eps, qk_scale;
     int32_t cross_splits; /* wipa_decode_cross_absorbed_block[_out] only: frame splits per clip of the streaming launch, 1..4; 0 = the
                            * default (4).  wipa_decode_cross_block ignores it. */
+    int32_t n_group;      /* candidate groups (wipa_model_cfg.dec_n_group): G > 1: the B rows are B / G clips x G candidates, kv holds
+                           * B / G clips and row b reads clip b / G (a separate instantiation of the kernels that read kv; B % G == 0).
+                           * 0 / 1: one clip per row, the launches and kernels of a descriptor without the field. */
 } wipa_cross_block_desc;
 int wipa_decode_cross_block(const wipa_cross_block_desc* d, wipa_stream_t s);
 
@@ -355,6 +364,12 @@ int wipa_cross_absorbed_init(int d);
 int wipa_cross_absorbed_attention(const void* q, int64_t q_row_stride, const void* wkT, const void* xa, const void* wv, const float* bv,
                                   void* out, int64_t out_row_stride, void* scratch, size_t scratch_bytes, int B, int H, int d, int Tk,
                                   float k_scale, int n_splits, wipa_stream_t s);
+/* candidate groups: B query rows, xa [B / n_group, Tk, d]; the streaming launch reads row b's frames at clip b / n_group (a separate
+ * instantiation; the query prologue, the partials and the merge are per row and unchanged) and the residency rule counts the
+ * B / n_group distinct clips.  n_group = 1 is wipa_cross_absorbed_attention. */
+int wipa_cross_absorbed_attention_grouped(const void* q, int64_t q_row_stride, const void* wkT, const void* xa, const void* wv,
+                                          const float* bv, void* out, int64_t out_row_stride, void* scratch, size_t scratch_bytes, int B,
+                                          int H, int d, int Tk, float k_scale, int n_splits, int n_group, wipa_stream_t s);
 /* The absorbed cross block of ONE decode step in three launches (the decode loop's form; wipa_cross_absorbed_attention with a
  * given query serves the prompt prefill and the tests): [split-K slab sum + residual + cross_attn_ln + cross query + absorbed query]
  * -> streaming kernel -> [merge + value projection].  The descriptor is wipa_decode_cross_block's with c->kv = the encoder output
@@ -480,6 +495,18 @@ int wipa_sample_step_embed(const float* logits, int64_t ldl, int B, int V, const
                            const float* ln_w, const float* ln_b, void* y, int y_dtype, int D, float eps, wipa_stream_t s);
 /* a measurement aid: out[c] = g_c of row `row` of the record at position p, for c < V */
 int wipa_sample_noise(const void* sample, int row, int p, int V, float* out, wipa_stream_t s);
+/* Best-of-N ranking on the device: MaximumLikelihoodRanker.rank of upstream's decoding.py over candidate groups, one wave per clip.
+ * tokens int32 [B, ld_tok], B = clips x n_group, rows c G .. c G + G - 1 the candidates of clip c; the generated columns are
+ * [sample_begin, sample_begin + n).  Per candidate: length = generated tokens before the first eot, n when there is none (upstream's
+ * t[sample_begin : first eot]); score = (double)sum_logprobs[b] / penalty[length] (IEEE division; penalty: DEVICE f64 [n + 1], built
+ * by the host exactly as upstream computes it: length, or ((5 + length) / 6) ** length_penalty).  ONE deviation: length 0 scores
+ * -inf where upstream divides by zero (reachable with suppress_blank=False only).  Per clip the winner is the FIRST maximum (the
+ * lowest candidate on ties, np.argmax).  Outputs: winner int32 [clips], length int32 [B], best_tokens int32 [clips, ld_out] = the
+ * winner's columns [0, sample_begin + n) (ld_out >= sample_begin + n), best_sum f32 [clips] = the winner's sum_logprobs.
+ * 1 <= n_group <= 64, B % n_group == 0, n >= 1. */
+int wipa_rank_groups(const int32_t* tokens, int64_t ld_tok, int B, int n_group, int sample_begin, int n, int eot, const float* sum_logprobs,
+                     const double* penalty, int32_t* winner, int32_t* length, int32_t* best_tokens, int64_t ld_out, float* best_sum,
+                     wipa_stream_t s);
 /* The same row routine alone, for the token ALREADY at position p = *pos_dev: x[b] = tok_emb[tokens[b][p]] + pos_emb[p],
  * y[b] = LayerNorm(x[b]).  wipa_decoder_run launches it once before its first step. */
 int wipa_embed_layernorm(const int32_t* tokens, int64_t ld_tok, int B, const int32_t* pos_dev, const void* tok_emb, int emb_dtype,
@@ -629,6 +656,15 @@ typedef struct wipa_model_cfg {
                                * Part of the step graph's and the prefill graph's key: wipa_decoder_prefill and wipa_decoder_run
                                * use the SAME count, so a prompt pass followed by steps rounds as the steps alone do
                                * (tests/test_gpu_model.py::test_prompt_prefill_equals_stepwise_prompt_absorbed). */
+    int32_t dec_n_group; /* candidate groups (best-of-N sampling: upstream's n_group = best_of).  0 / 1: one clip per decode row -- every
+                          * entry point enqueues exactly what it enqueued before the field existed.  G > 1: B in every wipa_decoder_* call
+                          * counts ROWS = clips x G, rows c G .. c G + G - 1 are the candidates of clip c and share its audio:
+                          * wipa_decoder_layout sizes cross_kv for B / G clips (everything else for B rows), wipa_decoder_set_audio takes
+                          * the features of B / G clips and copies / projects them once per clip, and every launch that reads the
+                          * per-clip audio reads clip b / G for row b (grouped instantiations; a grouped row does the arithmetic of an
+                          * ungrouped row on the same bytes).  B % G != 0 is WIPA_ERR_ARG with nothing enqueued.  Part of the step graph's
+                          * and the prompt-pass graphs' keys.  Served where a sampling decode is served (plain, rules, ragged prompts,
+                          * f32 / bf16, cached / absorbed); the fully fused step (WIPA_DECODE_FUSED=1) is refused as sampling refuses it. */
 } wipa_model_cfg;
 
 /* Encoder weight table (const void* [WIPA_ENC_GLOBAL + WIPA_ENC_PER_LAYER * n_layer]):
@@ -687,7 +723,7 @@ typedef struct wipa_dec_layout {
     int64_t logits;       /* f32 [B, ld_logits]: logits of the last step of the last wipa_decoder_run / wipa_decoder_prefill call
                            * (earlier steps of a call may not write them: wipa_logits_greedy) */
     int64_t ld_logits;
-    int64_t cross_kv;     /* T [n_layer][B][2H][n_audio_ctx][64] */
+    int64_t cross_kv;     /* T [n_layer][B][2H][n_audio_ctx][64] (B / dec_n_group clips with candidate groups) */
     int64_t self_kv;      /* T [n_layer][3][B][n_text_ctx][d]  (slot 0 q staging, 1 K, 2 V) */
     int64_t scratch;
 } wipa_dec_layout;

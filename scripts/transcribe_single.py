@@ -38,12 +38,12 @@ def load_checkpoint_model(checkpoint_path: str, base_model: str = "mlx-community
     return model
 
 
-def transcribe_file(model, audio_path: str, temperature: float = 0.0, seed=None) -> str:
+def transcribe_file(model, audio_path: str, temperature: float = 0.0, seed=None, best_of=None) -> str:
     print(f"Transcribing {audio_path}...")
     audio = load_audio_batch([audio_path])  # load_audio -> pad_or_trim (reference :43-44) on the GPU: [1, 480000]
     mel = log_mel_spectrogram(audio, n_mels=model.dims.n_mels).to(torch.float32)
-    # IPA is decoded "as English"; a temperature above 0 samples, reproducibly, from ``seed``
-    options = DecodingOptions(language="en", without_timestamps=True, temperature=temperature, seed=seed)
+    # IPA is decoded "as English"; a temperature above 0 samples, reproducibly, from ``seed``; ``best_of`` candidates, the best one kept
+    options = DecodingOptions(language="en", without_timestamps=True, temperature=temperature, seed=seed, best_of=best_of)
     audio_features = model.encoder(mel)
     result = decode(model, audio_features, options)
     return result[0].text.strip()
@@ -57,6 +57,8 @@ def main(argv=None):
                     help="local directory with config.json + weights.safetensors (hub names cannot resolve offline)")
     ap.add_argument("--temperature", type=float, default=0.0, help="above 0: sample instead of taking the arg-max (needs --seed)")
     ap.add_argument("--seed", type=int, default=None, help="seed of the sampling draw: the same seed gives the same transcript")
+    ap.add_argument("--best-of", type=int, default=None,
+                    help="with --temperature above 0: draw this many candidates and keep the one with the highest length-normalised log-probability")
     ap.add_argument("--word-timestamps", action="store_true",
                     help="transcribe through whisper_ipa_amd.transcribe(word_timestamps=True) and also print one line per word (start, end, probability)")
     ap.add_argument("--allow-byte-fallback", action="store_true",
@@ -68,6 +70,8 @@ def main(argv=None):
     model = load_checkpoint_model(args.checkpoint, args.base_model)
     if args.temperature != 0.0 and args.seed is None:
         ap.error("--temperature above 0 needs --seed")
+    if args.best_of is not None and args.temperature == 0.0 and not args.word_timestamps:
+        ap.error("--best-of needs --temperature above 0 (best_of with greedy sampling is not compatible)")
     words = []
     if args.word_timestamps:  # one decode: the prediction is the transcript the words belong to
         if args.temperature != 0.0:
@@ -75,11 +79,12 @@ def main(argv=None):
         from whisper_ipa_amd import transcribe
 
         print(f"Transcribing {args.audio}...")
-        out = transcribe(model, args.audio, language="en", word_timestamps=True, seed=args.seed)
+        out = transcribe(model, args.audio, language="en", word_timestamps=True, seed=args.seed,
+                         **({"best_of": args.best_of} if args.best_of is not None else {}))
         text = out["text"].strip()
         words = [w for seg in out["segments"] for w in seg.get("words", [])]
     else:
-        text = transcribe_file(model, args.audio, temperature=args.temperature, seed=args.seed)
+        text = transcribe_file(model, args.audio, temperature=args.temperature, seed=args.seed, best_of=args.best_of)
     print("\n" + "=" * 50)
     print(f"Audio: {args.audio}")
     print(f"Prediction: {text}")

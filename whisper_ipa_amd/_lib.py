@@ -62,7 +62,7 @@ class CrossBlockDesc(C.Structure):
         ("wq", c_void_p), ("bq", c_void_p), ("kv", c_void_p), ("out", c_void_p),
         ("slab_stride", c_int64),
         ("n_slabs", C.c_int32), ("B", C.c_int32), ("d", C.c_int32), ("H", C.c_int32), ("Tk", C.c_int32), ("dtype", C.c_int32),
-        ("eps", c_float), ("qk_scale", c_float), ("cross_splits", C.c_int32),
+        ("eps", c_float), ("qk_scale", c_float), ("cross_splits", C.c_int32), ("n_group", C.c_int32),
     ]
 
 
@@ -89,7 +89,7 @@ class ModelCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "n_mels", "n_audio_ctx", "n_audio_state", "n_audio_head", "n_audio_layer",
         "n_vocab", "n_text_ctx", "n_text_state", "n_text_head", "n_text_layer", "dtype", "f32_split", "dec_w_dtype", "weights_generation",
-        "enc_act_fp8", "dec_cross_absorbed", "dec_cross_splits")]
+        "enc_act_fp8", "dec_cross_absorbed", "dec_cross_splits", "dec_n_group")]
 
 
 class DecodeRules(C.Structure):
@@ -230,6 +230,11 @@ SIGNATURES = {
     "wipa_decoder_run_ragged": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                         c_int, _P(DecodeRules), c_void_p, c_void_p, c_void_p]),
     "wipa_decode_cross_attn_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "wipa_decode_cross_attn_grouped": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "wipa_cross_absorbed_attention_grouped": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                                      c_size_t, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p]),
+    "wipa_rank_groups": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_int64, c_void_p, c_void_p]),
     "wipa_decoder_release": (c_int, [c_void_p]),
     "wipa_decoder_logits_workspace_bytes": (c_size_t, [_P(ModelCfg), c_int, c_int]),
     "wipa_decoder_logits": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_size_t,

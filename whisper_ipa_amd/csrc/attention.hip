@@ -31,11 +31,18 @@ struct AttnParams {
 
 // Ragged prompts (left-padded rows; wipa_decode_attn_ragged, wipa_attention_ragged): row b's first visible key.  The RAGGED instantiations
 // take it; the others keep AttnParams' layout and their code.
-template <bool RAGGED>
+// Candidate groups (best-of-N sampling; wipa_decode_cross_attn_grouped): the B rows are B / n_group clips x n_group candidates and K / V
+// hold one entry per CLIP: row b reads clip b / n_group.  The GROUPED instantiations take the count; the others keep their arguments
+// and their code.
+template <bool RAGGED, bool GROUPED = false>
 struct AttnArgs : AttnParams {};
 template <>
 struct AttnArgs<true> : AttnParams {
     const int32_t* k_start;  // int32 [B], device
+};
+template <>
+struct AttnArgs<false, true> : AttnParams {
+    int n_group;
 };
 
 constexpr int GA_LD = 68;  // padded f32 row (64 + 4): conflict-free ds_read_b128 across 16 keys
@@ -294,8 +301,9 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_mfma_kernel(AttnParams p) {
 // wave partition, it would walk if it were decoded alone with an unpadded prompt, and the clamped loads never touch a padding row.
 // A query at a padding column (below k_start[b]) sees its own key only.  A separate instantiation: the kernels of calls without
 // prompts keep their arguments and their code.
-template <typename T, int WPH, bool NT = (WPH == 4), bool RAGGED = false>
-__global__ __launch_bounds__(256) void decode_attn_kernel(AttnArgs<RAGGED> p) {
+// GROUPED (candidate groups): K / V of row b are those of clip b / n_group; nothing else differs.
+template <typename T, int WPH, bool NT = (WPH == 4), bool RAGGED = false, bool GROUPED = false>
+__global__ __launch_bounds__(256) void decode_attn_kernel(AttnArgs<RAGGED, GROUPED> p) {
     constexpr int EPL = Vec16<T>::EPL;  // elements per 16-byte load
     constexpr int LPK = 64 / EPL;       // lanes per key row (64 dims)
     constexpr int G = 64 / LPK;         // keys per wave instruction
@@ -319,8 +327,10 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(AttnArgs<RAGGED> p) {
 #pragma unroll
         for (int e = 0; e < EPL; ++e) qf[e] = qv.get(e);
     }
-    const T* Kb = reinterpret_cast<const T*>(p.k) + b * p.k_bs + h * p.k_hs + c * EPL;
-    const T* Vb = reinterpret_cast<const T*>(p.v) + b * p.v_bs + h * p.v_hs + c * EPL;
+    int kvb = b;  // the cache entry the row reads: its own, or its clip's
+    if constexpr (GROUPED) kvb = b / p.n_group;
+    const T* Kb = reinterpret_cast<const T*>(p.k) + kvb * p.k_bs + h * p.k_hs + c * EPL;
+    const T* Vb = reinterpret_cast<const T*>(p.v) + kvb * p.v_bs + h * p.v_hs + c * EPL;
     if constexpr (RAGGED) {
         Kb += (int64_t)k_first * p.k_rs;
         Vb += (int64_t)k_first * p.v_rs;
@@ -364,8 +374,8 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(AttnArgs<RAGGED> p) {
 // Prompt prefill: the NQ prompt positions of a clip attend to the SAME cached cross K/V, so one pass over the cache serves
 // all of them (the per-position decode step would stream the 3.5 GB cache NQ times).  Same decomposition and the same
 // per-query arithmetic order as decode_attn_kernel<T, 4>: 4 waves split the keys, LDS merge; q / out rows are (b, t).
-template <typename T, int NQ>
-__global__ __launch_bounds__(256) void decode_attn_multi_kernel(AttnParams p) {
+template <typename T, int NQ, bool GROUPED = false>
+__global__ __launch_bounds__(256) void decode_attn_multi_kernel(AttnArgs<false, GROUPED> p) {
     constexpr int EPL = Vec16<T>::EPL;
     constexpr int LPK = 64 / EPL;
     constexpr int G = 64 / LPK;
@@ -384,8 +394,10 @@ __global__ __launch_bounds__(256) void decode_attn_multi_kernel(AttnParams p) {
 #pragma unroll
         for (int e = 0; e < EPL; ++e) qf[t][e] = qv.get(e);
     }
-    const T* Kb = reinterpret_cast<const T*>(p.k) + b * p.k_bs + h * p.k_hs + c * EPL;
-    const T* Vb = reinterpret_cast<const T*>(p.v) + b * p.v_bs + h * p.v_hs + c * EPL;
+    int kvb = b;
+    if constexpr (GROUPED) kvb = b / p.n_group;
+    const T* Kb = reinterpret_cast<const T*>(p.k) + kvb * p.k_bs + h * p.k_hs + c * EPL;
+    const T* Vb = reinterpret_cast<const T*>(p.v) + kvb * p.v_bs + h * p.v_hs + c * EPL;
     const int64_t k_rs = p.k_rs, v_rs = p.v_rs;
     float m[NQ], l[NQ], acc[NQ][EPL];
 #pragma unroll
@@ -826,7 +838,12 @@ static void fill_attn_params(const wipa_attn_desc* d, AttnParams& p) {
     p.H = d->H;
 }
 
-extern "C" int wipa_attention(const wipa_attn_desc* d, wipa_stream_t stream) {
+extern "C" int wipa_attention(const wipa_attn_desc* d, wipa_stream_t stream) { return wipa_attention_as(d, d ? d->Tq : 0, stream); }
+
+// wipa_attention with the kernel chosen as for path_tq query rows per batch entry.  The grouped prompt pass hands the G x P query rows
+// of a clip's candidates to one batch entry (non-causal cross-attention: every query row's arithmetic is its own, whatever rows sit
+// next to it) and must stay on the kernel its P rows alone would take.
+int wipa_attention_as(const wipa_attn_desc* d, int path_tq, wipa_stream_t stream) {
     WIPA_REQUIRE(d && d->q && d->k && d->v && d->out, "wipa_attention: null pointer");
     WIPA_REQUIRE(d->B > 0 && d->H > 0 && d->Tq > 0, "wipa_attention: bad shape");
     WIPA_REQUIRE(d->dtype == WIPA_F32 || d->dtype == WIPA_BF16, "wipa_attention: bad dtype %d", d->dtype);
@@ -837,7 +854,7 @@ extern "C" int wipa_attention(const wipa_attn_desc* d, wipa_stream_t stream) {
     // float32 with whole 16-query fragments and no device-side offsets (teacher-forced decoder, fine-tune step): f32 MFMA kernel;
     // the few-row prefill and everything bf16 stay on the VALU kernel.  WIPA_ATTN_FWD=valu keeps it for A/B runs.
     static const bool valu = [] { const char* e = getenv("WIPA_ATTN_FWD"); return e && !strcmp(e, "valu"); }();
-    if (d->dtype == WIPA_F32 && !valu && d->Tq >= 16 && !d->tk_dev && !d->q_row_dev && d->o_rs % 4 == 0 && d->o_hs % 4 == 0 &&
+    if (d->dtype == WIPA_F32 && !valu && path_tq >= 16 && !d->tk_dev && !d->q_row_dev && d->o_rs % 4 == 0 && d->o_hs % 4 == 0 &&
         d->o_bs % 4 == 0) {
         hipLaunchKernelGGL(attn_fwd_f32_mfma_kernel, dim3((d->Tq + 63) / 64, d->H, d->B), dim3(256), 0, (hipStream_t)stream, p);
         WIPA_LAUNCH_CHECK();
@@ -987,7 +1004,7 @@ extern "C" int wipa_decode_cross_attn_multi(const void* q, const void* kv, void*
     WIPA_REQUIRE(dtype == WIPA_F32 || dtype == WIPA_BF16, "wipa_decode_cross_attn_multi: bad dtype %d", dtype);
     if (n_q == 1) return wipa_decode_cross_attn(q, kv, out, B, H, Tk, dtype, stream);
     const wipa_attn_desc d = cross_attn_desc(q, kv, out, B, H, Tk, n_q, dtype);
-    AttnParams p;
+    AttnArgs<false> p;
     fill_attn_params(&d, p);
     const dim3 grid(H, B);
     hipStream_t s = (hipStream_t)stream;
@@ -1002,3 +1019,47 @@ extern "C" int wipa_decode_cross_attn_multi(const void* q, const void* kv, void*
     return WIPA_OK;
 }
 
+
+// Candidate groups: the cached cross-attention of B = clips x n_group rows against the K / V of B / n_group clips -- the long-cache form
+// of wipa_decode_attn (four waves, nt loads) for one query row, decode_attn_multi_kernel for 2..4, in their GROUPED instantiations.
+extern "C" int wipa_decode_cross_attn_grouped(const void* q, const void* kv, void* out, int B, int H, int Tk, int n_q, int n_group, int dtype,
+                                              wipa_stream_t stream) {
+    WIPA_REQUIRE(q && kv && out, "wipa_decode_cross_attn_grouped: null pointer");
+    WIPA_REQUIRE(B > 0 && H > 0 && Tk > 0 && n_q >= 1 && n_q <= 4, "wipa_decode_cross_attn_grouped: bad shape (n_q=%d)", n_q);
+    WIPA_REQUIRE(n_group >= 1 && B % n_group == 0, "wipa_decode_cross_attn_grouped: %d rows are no multiple of n_group=%d", B, n_group);
+    WIPA_REQUIRE(dtype == WIPA_F32 || dtype == WIPA_BF16, "wipa_decode_cross_attn_grouped: bad dtype %d", dtype);
+    if (n_group == 1) return wipa_decode_cross_attn_multi(q, kv, out, B, H, Tk, n_q, dtype, stream);
+    const wipa_attn_desc d = cross_attn_desc(q, kv, out, B, H, Tk, n_q, dtype);
+    WIPA_REQUIRE(attn_strides_aligned(&d), "wipa_decode_cross_attn_grouped: strides must keep 16-byte alignment");
+    AttnArgs<false, true> p;
+    fill_attn_params(&d, p);
+    p.n_group = n_group;
+    const dim3 grid(H, B);
+    hipStream_t s = (hipStream_t)stream;
+    if (n_q == 1) {
+        // the forms wipa_decode_attn chooses between for Tk keys without device-side offsets: up to 512 keys the default-policy
+        // loads of a short cache (four waves, or one per head with WIPA_SELF_ATTN_WAVES=1), above that four waves and nt loads
+        static const int self_waves = [] { const char* e = getenv("WIPA_SELF_ATTN_WAVES"); return e ? atoi(e) : 4; }();
+        if (Tk <= 512 && self_waves == 4) {
+            if (dtype == WIPA_F32) hipLaunchKernelGGL((decode_attn_kernel<float, 4, false, false, true>), grid, dim3(256), 0, s, p);
+            else hipLaunchKernelGGL((decode_attn_kernel<__bf16, 4, false, false, true>), grid, dim3(256), 0, s, p);
+        } else if (Tk <= 512) {
+            const dim3 grid1((H + 3) / 4, B);
+            if (dtype == WIPA_F32) hipLaunchKernelGGL((decode_attn_kernel<float, 1, false, false, true>), grid1, dim3(256), 0, s, p);
+            else hipLaunchKernelGGL((decode_attn_kernel<__bf16, 1, false, false, true>), grid1, dim3(256), 0, s, p);
+        } else if (dtype == WIPA_F32)
+            hipLaunchKernelGGL((decode_attn_kernel<float, 4, true, false, true>), grid, dim3(256), 0, s, p);
+        else
+            hipLaunchKernelGGL((decode_attn_kernel<__bf16, 4, true, false, true>), grid, dim3(256), 0, s, p);
+    } else {
+#define WIPA_MULTI_G(T, NQ) hipLaunchKernelGGL((decode_attn_multi_kernel<T, NQ, true>), grid, dim3(256), 0, s, p)
+        if (dtype == WIPA_F32) {
+            if (n_q == 2) WIPA_MULTI_G(float, 2); else if (n_q == 3) WIPA_MULTI_G(float, 3); else WIPA_MULTI_G(float, 4);
+        } else {
+            if (n_q == 2) WIPA_MULTI_G(__bf16, 2); else if (n_q == 3) WIPA_MULTI_G(__bf16, 3); else WIPA_MULTI_G(__bf16, 4);
+        }
+#undef WIPA_MULTI_G
+    }
+    WIPA_LAUNCH_CHECK();
+    return WIPA_OK;
+}

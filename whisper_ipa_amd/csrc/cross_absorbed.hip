@@ -62,6 +62,16 @@ struct AbsParams {
     int resident_groups;  // the first 16-frame groups of every split that load with the default cache policy; the rest stream nt
 };
 
+// Candidate groups (best-of-N sampling): the B rows are B / n_group clips x n_group candidates and xa holds one entry per CLIP; the
+// streaming kernels read row b's frames at clip b / n_group.  The GROUPED instantiations take the count; the others keep AbsParams'
+// layout and their code.  Qp and the partials are per row either way.
+template <bool GROUPED>
+struct AbsArgs : AbsParams {};
+template <>
+struct AbsArgs<true> : AbsParams {
+    int n_group;
+};
+
 // cache policy of an LDS-DMA transfer of xa (the instruction's aux field: an immediate, so a policy is an instantiation)
 constexpr int POLICY_DEFAULT = 0, POLICY_NT = 2;
 
@@ -82,8 +92,8 @@ struct AbsCfg {
     static constexpr int SMEM = NBUF * TILE + SX;
 };
 
-template <int D>
-__global__ __launch_bounds__(512, 1) void cross_absorbed_kernel(AbsParams p) {
+template <int D, bool GROUPED = false>
+__global__ __launch_bounds__(512, 1) void cross_absorbed_kernel(AbsArgs<GROUPED> p) {
     typedef AbsCfg<D> X;
     constexpr int NW = X::NW, ROWB = X::ROWB, TILE = X::TILE, NBUF = X::NBUF;
     constexpr int NDMA = TILE / 1024 / NW;    // LDS-DMA transfers per wave and tile (1 KiB each)
@@ -99,7 +109,9 @@ __global__ __launch_bounds__(512, 1) void cross_absorbed_kernel(AbsParams p) {
     const int tile0 = split * p.tiles_per_split;
     const int n_tiles_total = (p.Tk + FT - 1) / FT;
     const int nt = max(0, min(p.tiles_per_split, n_tiles_total - tile0));
-    const __bf16* xb = p.xa + (int64_t)b * p.Tk * D;
+    int xclip = b;  // the clip whose frames the row streams: its own, or its group's
+    if constexpr (GROUPED) xclip = b / p.n_group;
+    const __bf16* xb = p.xa + (int64_t)xclip * p.Tk * D;
 
     // Qp fragments of this wave's channels: B operand of the score product, lane (head = l15, k-group g)
     bf16x8 qf[KS];
@@ -383,8 +395,8 @@ __device__ __forceinline__ float sum_xor32(float v) {
 // PIPE = false is the loop as it was before the pipelined phase (WIPA_ABS_LOOP=0: A/B runs and the bit-equality test): six drained
 // read blocks per group, __shfl_xor exchanges.  Both forms read the same bytes and do the
 // same arithmetic in the same order: same bits.
-template <int D, int NW_, bool PIPE>
-__global__ __launch_bounds__(64 * NW_, 1) void cross_absorbed_v2_kernel(AbsParams p) {
+template <int D, int NW_, bool PIPE, bool GROUPED = false>
+__global__ __launch_bounds__(64 * NW_, 1) void cross_absorbed_v2_kernel(AbsArgs<GROUPED> p) {
     typedef AbsCfg2<D, NW_> X;
     constexpr int NWV = X::NWV, GF = X::GF, ROWB = X::ROWB, SLOT = X::SLOT;
     constexpr int NDMA = SLOT / 1024;  // LDS-DMA transfers per group (24 for d = 768)
@@ -401,7 +413,9 @@ __global__ __launch_bounds__(64 * NW_, 1) void cross_absorbed_v2_kernel(AbsParam
     const int g0 = split * gps;
     const int ng = max(0, min(gps, groups_total - g0));            // groups of this split
     const int my_n = ng > wave ? (ng - wave + NWV - 1) / NWV : 0;  // this wave takes groups wave, wave + 3, ...
-    const __bf16* xb = p.xa + (int64_t)b * p.Tk * D;
+    int xclip = b;  // the clip whose frames the row streams: its own, or its group's
+    if constexpr (GROUPED) xclip = b / p.n_group;
+    const __bf16* xb = p.xa + (int64_t)xclip * p.Tk * D;
     char* my = smem + wave * (2 * SLOT);
 
     bf16x8 qf[KS];  // absorbed queries, all k-steps: B operand of the scores, lane (head l15, k-group g)
@@ -1081,28 +1095,40 @@ void launch_merge(int lv, int S, dim3 grid, hipStream_t s, Args... args) {
 
 // WIPA_ABS_KERNEL=1 keeps the channel-split kernel (A/B runs); default: the independent-wave kernel.  WIPA_ABS_LOOP=0 keeps that
 // kernel's loop as it was before the pipelined P x group phase (and the general merge launch): both variables are read per call.
-template <int D>
-int launch_attn(int lv, const AbsParams& p_in, int B, hipStream_t s) {
+template <int D, bool GROUPED>
+int launch_attn_as(int lv, const AbsArgs<GROUPED>& p, int B, hipStream_t s) {
     const char* e = getenv("WIPA_ABS_KERNEL");
     const bool pipe = lv == 1 || lv == 2;
-    AbsParams p = p_in;
-    p.resident_groups = wipa_cross_absorbed_resident_groups(B, D, p.Tk, p.n_splits);  // every entry point launches through here
     // d = 1024: 64 column tiles are all 256 accumulation registers and a 16-frame group is 32 KiB, so the independent-wave form fits
     // with TWO waves only -- measured slower than the channel-split form there (whisper-medium, 256 clips: 191.5 vs 171.7 us per
     // launch, 845 vs 821 ms per pass); WIPA_ABS_KERNEL=2 selects it for A/B runs
     if ((e && atoi(e) == 1) || (D > 768 && !(e && atoi(e) == 2)))
-        hipLaunchKernelGGL((cross_absorbed_kernel<D>), dim3(p.n_splits, B), dim3(64 * AbsCfg<D>::NW), AbsCfg<D>::SMEM, s, p);
+        hipLaunchKernelGGL((cross_absorbed_kernel<D, GROUPED>), dim3(p.n_splits, B), dim3(64 * AbsCfg<D>::NW), AbsCfg<D>::SMEM, s, p);
     else if constexpr (D > 768) {
-        if (pipe) hipLaunchKernelGGL((cross_absorbed_v2_kernel<D, 2, true>), dim3(p.n_splits, B), dim3(128), (AbsCfg2<D, 2>::SMEM), s, p);
-        else hipLaunchKernelGGL((cross_absorbed_v2_kernel<D, 2, false>), dim3(p.n_splits, B), dim3(128), (AbsCfg2<D, 2>::SMEM), s, p);
+        if (pipe) hipLaunchKernelGGL((cross_absorbed_v2_kernel<D, 2, true, GROUPED>), dim3(p.n_splits, B), dim3(128), (AbsCfg2<D, 2>::SMEM), s, p);
+        else hipLaunchKernelGGL((cross_absorbed_v2_kernel<D, 2, false, GROUPED>), dim3(p.n_splits, B), dim3(128), (AbsCfg2<D, 2>::SMEM), s, p);
     } else {
         static const int waves = [] { const char* w = getenv("WIPA_ABS_WAVES"); return w ? atoi(w) : 3; }();  // A/B: 2 leaves 64 KiB of LDS and two SIMDs to other kernels
-        if (waves == 2 && pipe) hipLaunchKernelGGL((cross_absorbed_v2_kernel<D, 2, true>), dim3(p.n_splits, B), dim3(128), (AbsCfg2<D, 2>::SMEM), s, p);
-        else if (waves == 2) hipLaunchKernelGGL((cross_absorbed_v2_kernel<D, 2, false>), dim3(p.n_splits, B), dim3(128), (AbsCfg2<D, 2>::SMEM), s, p);
-        else if (pipe) hipLaunchKernelGGL((cross_absorbed_v2_kernel<D, 3, true>), dim3(p.n_splits, B), dim3(192), (AbsCfg2<D, 3>::SMEM), s, p);
-        else hipLaunchKernelGGL((cross_absorbed_v2_kernel<D, 3, false>), dim3(p.n_splits, B), dim3(192), (AbsCfg2<D, 3>::SMEM), s, p);
+        if (waves == 2 && pipe) hipLaunchKernelGGL((cross_absorbed_v2_kernel<D, 2, true, GROUPED>), dim3(p.n_splits, B), dim3(128), (AbsCfg2<D, 2>::SMEM), s, p);
+        else if (waves == 2) hipLaunchKernelGGL((cross_absorbed_v2_kernel<D, 2, false, GROUPED>), dim3(p.n_splits, B), dim3(128), (AbsCfg2<D, 2>::SMEM), s, p);
+        else if (pipe) hipLaunchKernelGGL((cross_absorbed_v2_kernel<D, 3, true, GROUPED>), dim3(p.n_splits, B), dim3(192), (AbsCfg2<D, 3>::SMEM), s, p);
+        else hipLaunchKernelGGL((cross_absorbed_v2_kernel<D, 3, false, GROUPED>), dim3(p.n_splits, B), dim3(192), (AbsCfg2<D, 3>::SMEM), s, p);
     }
     return WIPA_OK;
+}
+// every entry point launches through here.  n_group > 1 (candidate groups): the GROUPED instantiations, and the residency rule counts
+// the B / n_group DISTINCT clips -- the bytes that compete for the Infinity Cache -- not the rows that read them.
+template <int D>
+int launch_attn(int lv, const AbsParams& p_in, int B, hipStream_t s, int n_group = 1) {
+    if (n_group > 1) {
+        AbsArgs<true> p{p_in};
+        p.n_group = n_group;
+        p.resident_groups = wipa_cross_absorbed_resident_groups(B / n_group, D, p.Tk, p.n_splits);
+        return launch_attn_as<D, true>(lv, p, B, s);
+    }
+    AbsArgs<false> p{p_in};
+    p.resident_groups = wipa_cross_absorbed_resident_groups(B, D, p.Tk, p.n_splits);
+    return launch_attn_as<D, false>(lv, p, B, s);
 }
 
 // The scratch of a call carved up -- Qp [B][16][d] bf16, then part_m and part_l [B][S][16] and part_o [B][S][16][d] f32 -- and the
@@ -1214,6 +1240,24 @@ extern "C" int wipa_cross_absorbed_init(int d) {
         if (e == hipSuccess)
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_absorbed_v2_kernel<D, 2, false>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, AbsCfg2<D, 2>::SMEM);
+        // ... and of the candidate-group instantiations
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_absorbed_kernel<D, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    AbsCfg<D>::SMEM);
+        if constexpr (D <= 768) {
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_absorbed_v2_kernel<D, 3, true, true>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, AbsCfg2<D, 3>::SMEM);
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_absorbed_v2_kernel<D, 3, false, true>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, AbsCfg2<D, 3>::SMEM);
+        }
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_absorbed_v2_kernel<D, 2, true, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, AbsCfg2<D, 2>::SMEM);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_absorbed_v2_kernel<D, 2, false, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, AbsCfg2<D, 2>::SMEM);
         return WIPA_OK;
     });
     WIPA_CHECK_HIP(e);
@@ -1242,7 +1286,16 @@ extern "C" int wipa_cross_absorbed_stream(const void* xa, void* scratch, size_t 
 extern "C" int wipa_cross_absorbed_attention(const void* q, int64_t q_row_stride, const void* wkT, const void* xa, const void* wv,
                                              const float* bv, void* out, int64_t out_row_stride, void* scratch, size_t scratch_bytes,
                                              int B, int H, int d, int Tk, float k_scale, int n_splits, wipa_stream_t stream) {
+    return wipa_cross_absorbed_attention_grouped(q, q_row_stride, wkT, xa, wv, bv, out, out_row_stride, scratch, scratch_bytes, B, H, d, Tk,
+                                                 k_scale, n_splits, 1, stream);
+}
+
+extern "C" int wipa_cross_absorbed_attention_grouped(const void* q, int64_t q_row_stride, const void* wkT, const void* xa, const void* wv,
+                                                     const float* bv, void* out, int64_t out_row_stride, void* scratch,
+                                                     size_t scratch_bytes, int B, int H, int d, int Tk, float k_scale, int n_splits,
+                                                     int n_group, wipa_stream_t stream) {
     WIPA_REQUIRE(q && wkT && xa && wv && bv && out && scratch, "wipa_cross_absorbed_attention: null pointer");
+    WIPA_REQUIRE(n_group >= 1 && B % n_group == 0, "wipa_cross_absorbed_attention: %d rows are no multiple of n_group=%d", B, n_group);
     WIPA_REQUIRE(n_splits >= 0 && n_splits <= 4, "wipa_cross_absorbed_attention: n_splits %d (0 = default, 1..4)", n_splits);
     WIPA_REQUIRE(B > 0 && B <= 65535 && H >= 1 && H <= 16 && d == H * 64 && (d == 384 || d == 512 || d == 768 || d == 1024) && Tk >= 1,
                  "wipa_cross_absorbed_attention: bf16, <= 16 heads of 64, d in {384, 512, 768, 1024} (got H=%d d=%d)", H, d);
@@ -1268,7 +1321,7 @@ extern "C" int wipa_cross_absorbed_attention(const void* q, int64_t q_row_stride
         if (stages & 1)
             hipLaunchKernelGGL((cross_absorb_q_kernel<D>), gq, dim3(64), 0, s, (const __bf16*)q, q_row_stride, (const __bf16*)wkT,
                                const_cast<__bf16*>(p.qp), B, H, k_scale);
-        if (stages & 2) rc = launch_attn<D>(lv, p, B, s);
+        if (stages & 2) rc = launch_attn<D>(lv, p, B, s, n_group);
         if (rc == WIPA_OK && (stages & 4))
             launch_merge<D, false>(lv, S, gm, s, (const float*)p.part_m, (const float*)p.part_l, (const float*)p.part_o, S, (const __bf16*)wv, bv,
                                    (__bf16*)out, out_row_stride, B, (const __bf16*)nullptr, (const float*)nullptr, (float*)nullptr, (int64_t)0);
@@ -1310,9 +1363,9 @@ static int absorbed_block(const wipa_cross_block_desc* c, const void* wkT, const
     const int B = c->B, H = c->H, d = c->d, Tk = c->Tk;
     WIPA_REQUIRE(c->dtype == WIPA_BF16 && B > 0 && B <= 65535 * 16 && H >= 1 && H <= 16 && d == H * 64 &&
                      (d == 384 || d == 512 || d == 768 || d == 1024) && Tk >= 1 && c->n_slabs >= 0 && c->n_slabs <= 4 && !c->bias_o &&
-                     c->cross_splits >= 0 && c->cross_splits <= 4,
+                     c->cross_splits >= 0 && c->cross_splits <= 4 && c->n_group >= 0 && (c->n_group <= 1 || B % c->n_group == 0),
                  "wipa_decode_cross_absorbed_block: bf16, <= 16 heads of 64, d in {384, 512, 768, 1024}, <= 4 slabs, no separate bias, "
-                 "cross_splits 0..4");
+                 "cross_splits 0..4, rows a multiple of n_group");
     WIPA_REQUIRE(c->n_slabs == 0 || c->slabs, "wipa_decode_cross_absorbed_block: slabs missing");
     WIPA_REQUIRE((int64_t)Tk * d * 2 < ((int64_t)1 << 31), "wipa_decode_cross_absorbed_block: clip too long for 32-bit tile offsets");
     WIPA_REQUIRE(scratch_bytes >= wipa_cross_absorbed_scratch_bytes(B, d, Tk), "wipa_decode_cross_absorbed_block: scratch too small");
@@ -1333,7 +1386,7 @@ static int absorbed_block(const wipa_cross_block_desc* c, const void* wkT, const
         constexpr int D = decltype(width)::value;
         if (cg == 8) hipLaunchKernelGGL((cross_absorb_prologue_kernel<D, 8>), gp, dim3(512), 0, s, q);
         else hipLaunchKernelGGL((cross_absorb_prologue_kernel<D, 16>), gp, dim3(512), 0, s, q);
-        const int rc = launch_attn<D>(lv, p, B, s);
+        const int rc = launch_attn<D>(lv, p, B, s, c->n_group > 1 ? c->n_group : 1);  // c->kv holds B / n_group clips
         if (rc == WIPA_OK && wo)
             launch_merge<D, true>(lv, S, gm, s, (const float*)p.part_m, (const float*)p.part_l, (const float*)p.part_o, S, (const __bf16*)wv, bv,
                                   (__bf16*)nullptr, (int64_t)d, B, (const __bf16*)wo, bo, slabs_out, slab_stride);

@@ -322,10 +322,19 @@ struct CrossBlockParams {
     float eps, qk_scale;
 };
 
+// Candidate groups (wipa_cross_block_desc.n_group > 1): kv holds B / n_group clips and row b streams the K / V of clip b / n_group.
+// The GROUPED instantiations take the count; the others keep CrossBlockParams' layout and their code.
+template <bool GROUPED>
+struct CrossBlockArgs : CrossBlockParams {};
+template <>
+struct CrossBlockArgs<true> : CrossBlockParams {
+    int n_group;
+};
+
 constexpr int MAX_SLABS_X = 20;  // heads of whisper-large
 
-template <typename T>
-__global__ __launch_bounds__(256, 6) void decode_cross_block_kernel(CrossBlockParams p) {
+template <typename T, bool GROUPED = false>
+__global__ __launch_bounds__(256, 6) void decode_cross_block_kernel(CrossBlockArgs<GROUPED> p) {
     constexpr int EPL = Vec16<T>::EPL;
     constexpr int LPK = 64 / EPL;
     constexpr int G = 64 / LPK;
@@ -355,7 +364,9 @@ __global__ __launch_bounds__(256, 6) void decode_cross_block_kernel(CrossBlockPa
     const int g = lane / LPK, c = lane % LPK;
     const int Tk = p.Tk;
     const int64_t head = (int64_t)Tk * 64;
-    const T* Kb = reinterpret_cast<const T*>(p.kv) + ((int64_t)b * 2 * p.H + h) * head + c * EPL;
+    int kvb = b;  // the cache entry the row reads: its own, or its clip's
+    if constexpr (GROUPED) kvb = b / p.n_group;
+    const T* Kb = reinterpret_cast<const T*>(p.kv) + ((int64_t)kvb * 2 * p.H + h) * head + c * EPL;
     const T* Vb = Kb + (int64_t)p.H * head;
 
     constexpr int PRE = 3;  // key rows of the first group requested ahead (all U would spill at 80 registers)
@@ -506,8 +517,8 @@ __global__ __launch_bounds__(256, 6) void decode_cross_block_kernel(CrossBlockPa
 // bf16, d <= 768 (24 weight chunks per thread); other shapes and larger grids keep decode_cross_block_kernel.
 typedef __attribute__((address_space(3))) void* lds_ptr_x;
 
-template <int U>
-__global__ __launch_bounds__(256, 3) void decode_cross_block_pre_kernel(CrossBlockParams p) {
+template <int U, bool GROUPED = false>
+__global__ __launch_bounds__(256, 3) void decode_cross_block_pre_kernel(CrossBlockArgs<GROUPED> p) {
     typedef __bf16 T;
     constexpr int EPL = 8, LPK = 8, G = 8;
     constexpr int NQ = 24;            // 16-byte chunks of a query-weight row per thread (d <= 768)
@@ -552,7 +563,9 @@ __global__ __launch_bounds__(256, 3) void decode_cross_block_pre_kernel(CrossBlo
     const int g = lane / LPK, c = lane % LPK;
     const int Tk = p.Tk;
     const int64_t head = (int64_t)Tk * 64;
-    const T* Kh = reinterpret_cast<const T*>(p.kv) + ((int64_t)b * 2 * p.H + h) * head;
+    int kvb = b;
+    if constexpr (GROUPED) kvb = b / p.n_group;
+    const T* Kh = reinterpret_cast<const T*>(p.kv) + ((int64_t)kvb * 2 * p.H + h) * head;
     const T* Vh = Kh + (int64_t)p.H * head;
     {
         const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc((void*)Kh, 0, 0x7fffffff, 0x00020000);
@@ -749,6 +762,8 @@ extern "C" int wipa_decode_cross_block(const wipa_cross_block_desc* d, wipa_stre
     WIPA_REQUIRE(((uintptr_t)d->x_in % 16) == 0 && ((uintptr_t)d->x_out % 16) == 0 && ((uintptr_t)d->slabs % 16) == 0 &&
                      ((uintptr_t)d->wq % 16) == 0 && ((uintptr_t)d->kv % 16) == 0 && d->slab_stride % 4 == 0,
                  "wipa_decode_cross_block: operands must be 16-byte aligned");
+    WIPA_REQUIRE(d->n_group >= 0 && (d->n_group <= 1 || d->B % d->n_group == 0), "wipa_decode_cross_block: %d rows are no multiple of n_group=%d",
+                 d->B, d->n_group);
     CrossBlockParams p;
     p.x_in = d->x_in; p.x_out = d->x_out; p.slabs = d->slabs; p.bias_o = d->bias_o; p.ln_w = d->ln_w; p.ln_b = d->ln_b;
     p.wq = (const char*)d->wq; p.bq = d->bq; p.kv = (const char*)d->kv; p.out = (char*)d->out;
@@ -763,13 +778,25 @@ extern "C" int wipa_decode_cross_block(const wipa_cross_block_desc* d, wipa_stre
     const char* pre_env = getenv("WIPA_CROSS_PRE");  // read per call (enqueue / capture time): tests flip it within a process
     int pre = pre_env ? atoi(pre_env) : -1;
     if (pre < 0) pre = (d->H * d->B <= 3 * 256) ? 4 : 0;
-    if (d->dtype == WIPA_BF16 && d->d <= 768 && d->d % 8 == 0 && d->Tk >= 8 && d->n_slabs >= 1 && d->n_slabs <= 4 && !d->bias_o && (pre == 4 || pre == 6)) {
-        if (pre == 4) hipLaunchKernelGGL(decode_cross_block_pre_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, p);
-        else hipLaunchKernelGGL(decode_cross_block_pre_kernel<6>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    const bool staged = d->dtype == WIPA_BF16 && d->d <= 768 && d->d % 8 == 0 && d->Tk >= 8 && d->n_slabs >= 1 && d->n_slabs <= 4 && !d->bias_o && (pre == 4 || pre == 6);
+    if (d->n_group > 1) {  // candidate groups: the same choice of kernel, in the instantiations that read clip b / n_group
+        CrossBlockArgs<true> pg{p};
+        pg.n_group = d->n_group;
+        if (staged && pre == 4) hipLaunchKernelGGL((decode_cross_block_pre_kernel<4, true>), grid, dim3(256), 0, (hipStream_t)stream, pg);
+        else if (staged) hipLaunchKernelGGL((decode_cross_block_pre_kernel<6, true>), grid, dim3(256), 0, (hipStream_t)stream, pg);
+        else if (d->dtype == WIPA_BF16) hipLaunchKernelGGL((decode_cross_block_kernel<__bf16, true>), grid, dim3(256), 0, (hipStream_t)stream, pg);
+        else hipLaunchKernelGGL((decode_cross_block_kernel<float, true>), grid, dim3(256), 0, (hipStream_t)stream, pg);
+        WIPA_LAUNCH_CHECK();
+        return WIPA_OK;
+    }
+    const CrossBlockArgs<false> pu{p};
+    if (staged) {
+        if (pre == 4) hipLaunchKernelGGL(decode_cross_block_pre_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, pu);
+        else hipLaunchKernelGGL(decode_cross_block_pre_kernel<6>, grid, dim3(256), 0, (hipStream_t)stream, pu);
     } else if (d->dtype == WIPA_BF16)
-        hipLaunchKernelGGL(decode_cross_block_kernel<__bf16>, grid, dim3(256), 0, (hipStream_t)stream, p);
+        hipLaunchKernelGGL(decode_cross_block_kernel<__bf16>, grid, dim3(256), 0, (hipStream_t)stream, pu);
     else
-        hipLaunchKernelGGL(decode_cross_block_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, p);
+        hipLaunchKernelGGL(decode_cross_block_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, pu);
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;
 }

@@ -88,6 +88,7 @@ int cfg_check(const wipa_model_cfg* c) {
                  "{384, 512, 768, 1024}", c->dec_cross_absorbed);
     WIPA_REQUIRE(c->dec_cross_splits >= 0 && c->dec_cross_splits <= 4 && (c->dec_cross_splits == 0 || c->dec_cross_absorbed == 1),
                  "cfg.dec_cross_splits %d: 0 (default) or 1..4 frame splits, with dec_cross_absorbed = 1 only", c->dec_cross_splits);
+    WIPA_REQUIRE(c->dec_n_group >= 0 && c->dec_n_group <= 64, "cfg.dec_n_group %d: 0 / 1 (one clip per row) or 2..64 candidates per clip", c->dec_n_group);
     WIPA_REQUIRE(c->enc_act_fp8 == 0 || (c->enc_act_fp8 == 1 && c->dtype == WIPA_BF16 && c->n_audio_state % 128 == 0),
                  "cfg.enc_act_fp8 %d: fp8 encoder activations need a bf16 model whose width is a multiple of 128", c->enc_act_fp8);
     return WIPA_OK;
@@ -311,6 +312,10 @@ extern "C" int wipa_encoder_forward(const wipa_model_cfg* cfg, const void* const
 namespace {
 
 constexpr int MAX_SLABS = 4;
+// Candidate groups (cfg.dec_n_group = G > 1; best-of-N sampling): the B rows of a decode call are B / G clips x G candidates, and what
+// is per CLIP -- the cross_kv region and every read of it -- is sized and indexed by clip: row b reads clip b / G.
+inline int group_of(const wipa_model_cfg* c) { return c->dec_n_group > 1 ? c->dec_n_group : 1; }
+inline int clips_of(const wipa_model_cfg* c, int B) { return B / group_of(c); }
 struct DecScratch {
     size_t x, x2, ln, q, ao, h, slabs, posd, absorbed, greedy_part, total;
 };
@@ -357,8 +362,9 @@ wipa_dec_layout dec_layout(const wipa_model_cfg* c, int B) {
     L.ld_logits = round_up(c->n_vocab, 8);
     L.logits = o; o += align256((size_t)B * L.ld_logits * 4);
     // cached cross K / V of every layer -- or, with absorbed projections, ONE copy of the encoder output [B, n_audio_ctx, d]
-    L.cross_kv = o; o += align256(c->dec_cross_absorbed ? (size_t)B * c->n_audio_ctx * d * e
-                                                        : (size_t)c->n_text_layer * B * 2 * H * c->n_audio_ctx * 64 * e);
+    const size_t Bc = clips_of(c, B);  // the audio is held once per clip
+    L.cross_kv = o; o += align256(c->dec_cross_absorbed ? Bc * c->n_audio_ctx * d * e
+                                                        : (size_t)c->n_text_layer * Bc * 2 * H * c->n_audio_ctx * 64 * e);
     L.self_kv = o; o += align256((size_t)c->n_text_layer * 3 * B * c->n_text_ctx * d * e);
     L.scratch = o; o += dec_scratch(c, B).total;
     L.total_bytes = o;
@@ -450,6 +456,7 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
     float* x_other = (float*)(sc + S.x2);
     const bool absorbed = cfg->dec_cross_absorbed != 0;
     const bool cross_fused = !absorbed && decode_mode(cfg, B) == 2;
+    const int G = group_of(cfg), Bc = clips_of(cfg, B);
     void* ln = sc + S.ln;
     void* q = sc + S.q;
     void* ao = sc + S.ao;
@@ -484,7 +491,7 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
     for (int l = 0; l < cfg->n_text_layer; ++l) {
         const void* const* lw = w + WIPA_DEC_GLOBAL + WIPA_DEC_PER_LAYER * l;
         char* skv = st + L.self_kv + (size_t)l * 3 * B * nctx * d * e;  // [3][B][nctx][d]
-        char* ckv = st + L.cross_kv + (size_t)l * B * 2 * H * Ta * 64 * e;
+        char* ckv = st + L.cross_kv + (size_t)l * Bc * 2 * H * Ta * 64 * e;
         bool cross_out_done = false;
         if (!(tail && l == 0)) RT_CALL(ln_step(lw[0], lw[1]));
         {
@@ -521,6 +528,7 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
             c.ln_w = (const float*)lw[6]; c.ln_b = (const float*)lw[7]; c.wq = lw[8]; c.bq = (const float*)lw[9];
             c.kv = ckv; c.out = ao; c.slab_stride = slab_stride;
             c.n_slabs = pend; c.B = B; c.d = d; c.H = H; c.Tk = Ta; c.dtype = dt; c.eps = 1e-5f; c.qk_scale = QK_SCALE;
+            c.n_group = cfg->dec_n_group;
             RT_CALL(wipa_decode_cross_block(&c, stream));
             pend = 0;
             std::swap(x, x_other);
@@ -535,6 +543,7 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
             c.kv = st + L.cross_kv; c.out = ao; c.slab_stride = slab_stride;
             c.n_slabs = pend; c.B = B; c.d = d; c.H = H; c.Tk = Ta; c.dtype = dt; c.eps = 1e-5f; c.qk_scale = QK_SCALE;
             c.cross_splits = cfg->dec_cross_splits;
+            c.n_group = cfg->dec_n_group;
             if (absorbed_merge_out()) {
                 // ... and the cross-attention OUT projection rides in the third launch: one slab per head, summed by the mlp LayerNorm
                 RT_CALL(wipa_decode_cross_absorbed_block_out(&c, wkT, (const char*)lw[10] + (size_t)d * d * e, (const float*)lw[11] + d,
@@ -560,9 +569,12 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
             if (absorbed) {
                 // scores and values from ONE pass over the encoder output: Wk absorbed into the query, Wv into the output
                 const void* wkT = w[WIPA_DEC_GLOBAL + WIPA_DEC_PER_LAYER * cfg->n_text_layer + WIPA_DEC_ABSORBED_PER_LAYER * l];
-                RT_CALL(wipa_cross_absorbed_attention(q, d, wkT, st + L.cross_kv, (const char*)lw[10] + (size_t)d * d * e,
-                                                      (const float*)lw[11] + d, ao, d, sc + S.absorbed, S.greedy_part - S.absorbed, B, H, d, Ta,
-                                                      QK_SCALE, cfg->dec_cross_splits, stream));
+                // (G = 1 is wipa_cross_absorbed_attention)
+                RT_CALL(wipa_cross_absorbed_attention_grouped(q, d, wkT, st + L.cross_kv, (const char*)lw[10] + (size_t)d * d * e,
+                                                              (const float*)lw[11] + d, ao, d, sc + S.absorbed, S.greedy_part - S.absorbed, B, H,
+                                                              d, Ta, QK_SCALE, cfg->dec_cross_splits, G, stream));
+            } else if (G > 1) {
+                RT_CALL(wipa_decode_cross_attn_grouped(q, ckv, ao, B, H, Ta, 1, G, dt, stream));
             } else {
                 RT_CALL(wipa_decode_cross_attn(q, ckv, ao, B, H, Ta, dt, stream));
             }
@@ -714,6 +726,7 @@ int enqueue_prefill(const wipa_model_cfg* cfg, const void* const* w, char* st, c
     const size_t e = wipa_dtype_size(dt);
     const int d = cfg->n_text_state, H = cfg->n_text_head, nctx = cfg->n_text_ctx, Ta = cfg->n_audio_ctx;
     const int P = n_init, M = B * P;
+    const int G = group_of(cfg), Bc = clips_of(cfg, B);
     const DecScratch S = dec_scratch(cfg, B);
     char* sc = st + L.scratch;
     float* x = (float*)(sc + S.x);
@@ -746,7 +759,7 @@ int enqueue_prefill(const wipa_model_cfg* cfg, const void* const* w, char* st, c
     for (int l = 0; l < cfg->n_text_layer; ++l) {
         const void* const* lw = w + WIPA_DEC_GLOBAL + WIPA_DEC_PER_LAYER * l;
         char* skv = st + L.self_kv + (size_t)l * 3 * B * nctx * d * e;  // [3][B][nctx][d]
-        char* ckv = st + L.cross_kv + (size_t)l * B * 2 * H * Ta * 64 * e;
+        char* ckv = st + L.cross_kv + (size_t)l * Bc * 2 * H * Ta * 64 * e;
         RT_CALL(ln_step(lw[0], lw[1]));
         {
             // q|k|v of positions 0..P-1 -> slot[n / d][b][t][n % d]
@@ -783,10 +796,12 @@ int enqueue_prefill(const wipa_model_cfg* cfg, const void* const* w, char* st, c
             // one absorbed pass per prompt position: rows (b, t) of q / ao with row stride P * d
             const void* wkT = w[WIPA_DEC_GLOBAL + WIPA_DEC_PER_LAYER * cfg->n_text_layer + WIPA_DEC_ABSORBED_PER_LAYER * l];
             for (int t = 0; t < P; ++t)
-                RT_CALL(wipa_cross_absorbed_attention((const char*)q + (size_t)t * d * e, (int64_t)P * d, wkT, st + L.cross_kv,
-                                                      (const char*)lw[10] + (size_t)d * d * e, (const float*)lw[11] + d,
-                                                      (char*)ao + (size_t)t * d * e, (int64_t)P * d, sc + S.absorbed, S.greedy_part - S.absorbed, B,
-                                                      H, d, Ta, QK_SCALE, cfg->dec_cross_splits, stream));
+                RT_CALL(wipa_cross_absorbed_attention_grouped((const char*)q + (size_t)t * d * e, (int64_t)P * d, wkT, st + L.cross_kv,
+                                                              (const char*)lw[10] + (size_t)d * d * e, (const float*)lw[11] + d,
+                                                              (char*)ao + (size_t)t * d * e, (int64_t)P * d, sc + S.absorbed,
+                                                              S.greedy_part - S.absorbed, B, H, d, Ta, QK_SCALE, cfg->dec_cross_splits, G, stream));
+        } else if (G > 1) {  // candidate groups: the prompt rows of every candidate against the K / V of its clip
+            RT_CALL(wipa_decode_cross_attn_grouped(q, ckv, ao, B, H, Ta, P, G, dt, stream));
         } else {
             RT_CALL(wipa_decode_cross_attn_multi(q, ckv, ao, B, H, Ta, P, dt, stream));
         }
@@ -892,6 +907,16 @@ int sample_servable(const char* who, const wipa_model_cfg* cfg, int B, const voi
     WIPA_REQUIRE(cfg->n_vocab <= 65536 && cfg->n_text_ctx <= 65536, "%s: need n_vocab and n_text_ctx <= 65536 (n_vocab=%d)", who, cfg->n_vocab);
     return WIPA_OK;
 }
+// candidate groups are served where a sampling decode is served (what sampling refuses is refused in sampling's words), on rows that
+// divide into whole groups; refused before anything is enqueued
+int group_servable(const char* who, const wipa_model_cfg* cfg, int B) {
+    const int G = group_of(cfg);
+    WIPA_REQUIRE(B % G == 0, "%s: B=%d rows are no multiple of cfg.dec_n_group=%d (rows = clips x candidates)", who, B, G);
+    if (G == 1) return WIPA_OK;
+    WIPA_REQUIRE(tail_fused() && !use_fused_step(cfg, B),
+                 "%s: sampling lives in the fused step tail; WIPA_DECODE_TAIL=0 / WIPA_DECODE_FUSED=1 cannot serve it", who);
+    return WIPA_OK;
+}
 // ragged prompts live in the RAGGED instantiations of the unfused step's self-attention and tail: refused before anything is enqueued
 // where the step is another one, and on fp8 decoder tables (as wipa_decoder_logits refuses them)
 int starts_servable(const char* who, const wipa_model_cfg* cfg, int B, int n_init, const int32_t* starts_dev) {
@@ -925,7 +950,7 @@ int step_variant(const wipa_model_cfg* cfg, int B) {
     return cfg->dtype * 2 + t_f32_split + 4 * decode_mode(cfg, B) + 16 * cfg->dec_w_dtype +
            64 * cfg->dec_cross_absorbed * (absorbed_block_fused() ? 2 : 1) + 256 * (int)tail_fused() + 512 * (int)absorbed_merge_out() +
            1024 * cfg->dec_cross_splits + 8192 * (int)lean_steps(cfg, B) +
-           16384 * (cfg->dec_cross_absorbed ? wipa_cross_absorbed_loop_variant() : 0);
+           16384 * (cfg->dec_cross_absorbed ? wipa_cross_absorbed_loop_variant() : 0) + 65536 * (group_of(cfg) > 1 ? group_of(cfg) : 0);
 }
 // a key from the arguments of a decode call; the three rule terms are 0 without rules
 GraphKey graph_key(const wipa_model_cfg* cfg, const void* const* w, const void* state, const float* mask_first, const float* mask_always, int B,
@@ -999,6 +1024,7 @@ extern "C" int wipa_decoder_layout(const wipa_model_cfg* cfg, int B, wipa_dec_la
     RT_CALL(cfg_check(cfg));
     SplitScope split_scope(cfg);
     WIPA_REQUIRE(out && B > 0, "wipa_decoder_layout: bad arguments");
+    WIPA_REQUIRE(B % group_of(cfg) == 0, "wipa_decoder_layout: B=%d rows are no multiple of cfg.dec_n_group=%d", B, cfg->dec_n_group);
     *out = dec_layout(cfg, B);
     return WIPA_OK;
 }
@@ -1008,6 +1034,8 @@ extern "C" int wipa_decoder_set_audio(const wipa_model_cfg* cfg, const void* con
     RT_CALL(cfg_check(cfg));
     SplitScope split_scope(cfg);
     WIPA_REQUIRE(w && features && state && B > 0, "wipa_decoder_set_audio: null pointer / bad batch");
+    WIPA_REQUIRE(B % group_of(cfg) == 0, "wipa_decoder_set_audio: B=%d rows are no multiple of cfg.dec_n_group=%d", B, cfg->dec_n_group);
+    const int Bc = clips_of(cfg, B);  // features hold B / dec_n_group clips: copied / projected once per clip
     const wipa_dec_layout L = dec_layout(cfg, B);
     RT_CALL(state_fits("wipa_decoder_set_audio", L, state_bytes));
     const int dt = cfg->dtype;
@@ -1016,18 +1044,18 @@ extern "C" int wipa_decoder_set_audio(const wipa_model_cfg* cfg, const void* con
     WIPA_REQUIRE(cfg->n_audio_state == d, "encoder/decoder widths differ");
     if (cfg->dec_cross_absorbed) {
         // no key / value projection and no cache: the decode steps stream the encoder output itself (csrc/cross_absorbed.hip)
-        WIPA_CHECK_HIP(hipMemcpyAsync((char*)state + L.cross_kv, features, (size_t)B * Ta * d * e, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        WIPA_CHECK_HIP(hipMemcpyAsync((char*)state + L.cross_kv, features, (size_t)Bc * Ta * d * e, hipMemcpyDeviceToDevice, (hipStream_t)stream));
         return WIPA_OK;
     }
     for (int l = 0; l < cfg->n_text_layer; ++l) {
         const void* const* lw = w + WIPA_DEC_GLOBAL + WIPA_DEC_PER_LAYER * l;
-        char* ckv = (char*)state + L.cross_kv + (size_t)l * B * 2 * H * Ta * 64 * e;
+        char* ckv = (char*)state + L.cross_kv + (size_t)l * Bc * 2 * H * Ta * 64 * e;
         wipa_gemm_desc g;
         memset(&g, 0, sizeof(g));
         g.col_scale_n = d; g.col_scale = QK_SCALE;  // the key half; values stay unscaled
         g.rg_in = Ta; g.rg_valid = Ta; g.rg_stride = (int64_t)2 * H * Ta * 64;
         g.cg_in = 64; g.cg_stride = (int64_t)Ta * 64;
-        PROF(PROF_GEMM, gemm(features, d, lw[10], d, ckv, 64, B * Ta, 2 * d, d, dt, dt, (const float*)lw[11], 0, nullptr, stream, &g));
+        PROF(PROF_GEMM, gemm(features, d, lw[10], d, ckv, 64, Bc * Ta, 2 * d, d, dt, dt, (const float*)lw[11], 0, nullptr, stream, &g));
     }
     return WIPA_OK;
 }
@@ -1038,6 +1066,7 @@ extern "C" int wipa_decoder_begin(const wipa_model_cfg* cfg, void* state, size_t
     SplitScope split_scope(cfg);
     WIPA_REQUIRE(state && initial_tokens_host && n_init >= 1 && n_init <= 4 && B > 0,
                  "wipa_decoder_begin: need 1..4 prompt tokens (got %d)", n_init);
+    WIPA_REQUIRE(B % group_of(cfg) == 0, "wipa_decoder_begin: B=%d rows are no multiple of cfg.dec_n_group=%d", B, cfg->dec_n_group);
     const wipa_dec_layout L = dec_layout(cfg, B);
     RT_CALL(state_fits("wipa_decoder_begin", L, state_bytes));
     hipStream_t s = (hipStream_t)stream;
@@ -1064,6 +1093,7 @@ extern "C" int wipa_decoder_begin_ragged(const wipa_model_cfg* cfg, void* state,
     WIPA_REQUIRE(state && tokens_host && starts_host && starts_dev && B > 0, "wipa_decoder_begin_ragged: null pointer / bad batch");
     WIPA_REQUIRE(P >= 1 && P <= cfg->n_text_ctx, "wipa_decoder_begin_ragged: prompt width P=%d outside 1..n_text_ctx=%d", P, cfg->n_text_ctx);
     WIPA_REQUIRE(cfg->dec_w_dtype == 0, "wipa_decoder_begin_ragged: ragged prompts are not served on fp8 decoder tables (cfg.dec_w_dtype)");
+    WIPA_REQUIRE(B % group_of(cfg) == 0, "wipa_decoder_begin_ragged: B=%d rows are no multiple of cfg.dec_n_group=%d", B, cfg->dec_n_group);
     for (int b = 0; b < B; ++b)
         WIPA_REQUIRE(starts_host[b] >= 0 && P - starts_host[b] >= 1, "wipa_decoder_begin_ragged: start[%d]=%d outside 0..P-1 (P=%d): a row holds 1..P tokens",
                      b, starts_host[b], P);
@@ -1116,6 +1146,7 @@ extern "C" int wipa_decoder_run_ragged(const wipa_model_cfg* cfg, const void* co
     RT_CALL(rules_servable("wipa_decoder_run_rules", cfg, B, eot, rules));
     RT_CALL(sample_servable("wipa_decoder_run_sample", cfg, B, sample));
     RT_CALL(starts_servable("wipa_decoder_run_ragged", cfg, B, n_init, starts_dev));
+    RT_CALL(group_servable("wipa_decoder_run", cfg, B));
     // the position lives on the device: a call may carry the prompt walk (P - 1 steps) besides the new tokens, so what can be refused
     // here is a step count that no position admits
     WIPA_REQUIRE(!starts_dev || n_steps <= cfg->n_text_ctx - 1, "wipa_decoder_run_ragged: n_steps=%d with P=%d runs past n_text_ctx=%d", n_steps,
@@ -1184,6 +1215,7 @@ extern "C" int wipa_decoder_prefill_sample(const wipa_model_cfg* cfg, const void
     WIPA_REQUIRE(w && state && mask_first && mask_always && B > 0, "wipa_decoder_prefill: bad arguments");
     RT_CALL(rules_servable("wipa_decoder_prefill_rules", cfg, B, eot, rules));
     RT_CALL(sample_servable("wipa_decoder_prefill_sample", cfg, B, sample));
+    RT_CALL(group_servable("wipa_decoder_prefill", cfg, B));
     RulesScope rules_scope(rules, sample);
     WIPA_REQUIRE(n_init >= 1 && n_init <= MAX_PROMPT, "wipa_decoder_prefill: 1..%d prompt tokens (got %d)", MAX_PROMPT, n_init);
     W8Scope w8_scope(cfg, w);
@@ -1229,7 +1261,7 @@ PromptWs prompt_ws(const wipa_model_cfg* c, int B, int P) {
     w.q = o;   o += align256(M * d * e);
     w.ao = o;  o += align256(M * d * e);
     w.h = o;   o += align256(M * 4 * d * e);
-    w.ckv = o; o += c->dec_cross_absorbed ? align256((size_t)B * 2 * c->n_text_head * c->n_audio_ctx * 64 * e) : 0;
+    w.ckv = o; o += c->dec_cross_absorbed ? align256((size_t)clips_of(c, B) * 2 * c->n_text_head * c->n_audio_ctx * 64 * e) : 0;  // per clip
     w.total = o;
     return w;
 }
@@ -1240,6 +1272,7 @@ int enqueue_prefill_ragged(const wipa_model_cfg* cfg, const void* const* w, char
     const int dt = cfg->dtype;
     const size_t e = wipa_dtype_size(dt);
     const int d = cfg->n_text_state, H = cfg->n_text_head, nctx = cfg->n_text_ctx, Ta = cfg->n_audio_ctx, M = B * P;
+    const int G = group_of(cfg), Bc = clips_of(cfg, B);
     const DecScratch S = dec_scratch(cfg, B);
     float* x = (float*)(ws + W.x);
     char* ln = ws + W.ln;
@@ -1283,7 +1316,7 @@ int enqueue_prefill_ragged(const wipa_model_cfg* cfg, const void* const* w, char
             g.col_scale_n = d; g.col_scale = QK_SCALE;
             RT_CALL(gemm(ln, d, lw[8], d, q, d, M, d, d, dt, dt, (const float*)lw[9], 0, nullptr, stream, &g));
         }
-        const char* ckv = st + L.cross_kv + (size_t)l * B * 2 * H * Ta * 64 * e;  // the cached form's K / V of this layer
+        const char* ckv = st + L.cross_kv + (size_t)l * Bc * 2 * H * Ta * 64 * e;  // the cached form's K / V of this layer (per clip)
         if (cfg->dec_cross_absorbed) {
             // absorbed form: the blob holds the encoder output itself; this layer's K / V are projected from it into the workspace
             wipa_gemm_desc g;
@@ -1291,7 +1324,7 @@ int enqueue_prefill_ragged(const wipa_model_cfg* cfg, const void* const* w, char
             g.col_scale_n = d; g.col_scale = QK_SCALE;
             g.rg_in = Ta; g.rg_valid = Ta; g.rg_stride = (int64_t)2 * H * Ta * 64;
             g.cg_in = 64; g.cg_stride = (int64_t)Ta * 64;
-            RT_CALL(gemm(st + L.cross_kv, d, lw[10], d, ws + W.ckv, 64, B * Ta, 2 * d, d, dt, dt, (const float*)lw[11], 0, nullptr, stream, &g));
+            RT_CALL(gemm(st + L.cross_kv, d, lw[10], d, ws + W.ckv, 64, Bc * Ta, 2 * d, d, dt, dt, (const float*)lw[11], 0, nullptr, stream, &g));
             ckv = ws + W.ckv;
         }
         {
@@ -1303,7 +1336,15 @@ int enqueue_prefill_ragged(const wipa_model_cfg* cfg, const void* const* w, char
             a.v_bs = a.k_bs; a.v_rs = 64; a.v_hs = a.k_hs;
             a.o_bs = (int64_t)P * d; a.o_rs = d; a.o_hs = 64;
             a.B = B; a.H = H; a.Tq = P; a.Tk = Ta; a.causal = 0; a.dtype = dt;
-            RT_CALL(wipa_attention(&a, stream));
+            if (G > 1) {
+                // candidate groups: the G x P query rows of a clip's candidates are contiguous -- one batch entry per CLIP holds them
+                // all against the clip's K / V, on the kernel P rows take (every query row's arithmetic is its own)
+                a.B = Bc; a.Tq = G * P;
+                a.q_bs = (int64_t)G * P * d; a.o_bs = a.q_bs;
+                RT_CALL(wipa_attention_as(&a, P, stream));
+            } else {
+                RT_CALL(wipa_attention(&a, stream));
+            }
         }
         RT_CALL(gemm(ao, d, lw[12], d, x, d, M, d, d, dt, WIPA_F32, (const float*)lw[13], 0, x, stream));
         RT_CALL(wipa_layernorm(x, WIPA_F32, d, ln, dt, d, (const float*)lw[14], (const float*)lw[15], M, d, 1e-5f, stream));
@@ -1353,6 +1394,7 @@ extern "C" int wipa_decoder_prefill_ragged(const wipa_model_cfg* cfg, const void
     RT_CALL(rules_servable("wipa_decoder_prefill_ragged", cfg, B, eot, rules));
     RT_CALL(sample_servable("wipa_decoder_prefill_ragged", cfg, B, sample));
     RT_CALL(starts_servable("wipa_decoder_prefill_ragged", cfg, B, P, starts_dev));
+    RT_CALL(group_servable("wipa_decoder_prefill_ragged", cfg, B));
     WIPA_REQUIRE(P + 1 <= cfg->n_text_ctx, "wipa_decoder_prefill_ragged: P=%d leaves no column to generate in n_text_ctx=%d", P, cfg->n_text_ctx);
     WIPA_REQUIRE(sot_col >= -1 && sot_col < P, "wipa_decoder_prefill_ragged: sot_col=%d outside -1..P-1 (P=%d)", sot_col, P);
     const PromptWs W = prompt_ws(cfg, B, P);
@@ -1371,7 +1413,7 @@ extern "C" int wipa_decoder_prefill_ragged(const wipa_model_cfg* cfg, const void
     if (!use_graph || s == nullptr || !graphs_allowed()) return enqueue();
     hipGraphExec_t exec = nullptr;
     // the prompt pass has its own, shorter variant word
-    RT_CALL(cached_graph(graph_key(cfg, w, state, mask_first, mask_always, B, P, eot, cfg->dtype * 2 + t_f32_split + 64 * cfg->dec_cross_absorbed,
+    RT_CALL(cached_graph(graph_key(cfg, w, state, mask_first, mask_always, B, P, eot, cfg->dtype * 2 + t_f32_split + 64 * cfg->dec_cross_absorbed + 256 * (group_of(cfg) > 1 ? group_of(cfg) : 0),
                                    3 + 16 * (sot_col + 1), rules, sample, starts_dev, workspace), s, enqueue, &exec));
     WIPA_CHECK_HIP(hipGraphLaunch(exec, s));
     return WIPA_OK;

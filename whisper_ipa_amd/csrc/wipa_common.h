@@ -20,6 +20,8 @@ int wipa_decode_fused_init();
 int wipa_gemm_init();
 // the absorbed cross-attention's loop variant of this call (WIPA_ABS_LOOP, cross_absorbed.hip): a term of the decode graph key
 int wipa_cross_absorbed_loop_variant();
+// wipa_attention with the kernel chosen as for path_tq query rows per batch entry (attention.hip; the grouped prompt pass)
+int wipa_attention_as(const wipa_attn_desc* d, int path_tq, wipa_stream_t stream);
 // the decode step's last launch on written logits (elementwise.hip): wipa_greedy_step_embed / wipa_timestamp_step_embed /
 // wipa_sample_step_embed / wipa_step_embed_ragged behind one argument list -- rules, sample and starts_dev may each be NULL
 int wipa_step_tail(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always, int32_t* tokens,

@@ -21,6 +21,13 @@ own sampling counter (include/wipa.h: wipa_decoder_begin_ragged / wipa_decoder_r
 multiple of 16 where that leaves room to generate.  ONE documented deviation from upstream: ``sample_len`` is clamped to
 ``n_text_ctx - P`` for the whole batch, so a row with a short prompt decoded next to one with the full 223-token history can generate
 448 - 227 = 221 tokens, not 224.  Without any prompt or prefix ``decode`` makes exactly the library calls it made before.
+
+Best-of-N (``DecodingOptions.best_of`` at a temperature above 0; upstream's ``n_group = best_of`` with MaximumLikelihoodRanker): every
+clip is decoded as a GROUP of N candidate rows that share the clip's audio -- the decode state holds it once per clip
+(``wipa_model_cfg.dec_n_group``) and the features are never replicated.  Candidate k of a row with stream (lo, hi) draws from stream
+(lo, hi + (k << 24)), so candidate 0 is the row's draw without ``best_of`` and a window's candidates do not depend on its neighbours.
+``wipa_rank_groups`` picks, on the device, the candidate with the highest ``sum_logprobs / penalty(length)`` (first maximum) and the
+host reads the winners only.  ONE deviation from upstream: a candidate of length 0 scores -inf where upstream divides by zero.
 """
 from __future__ import annotations
 
@@ -84,6 +91,8 @@ class GreedyTokens:
     n_init: Optional[int] = None               # ragged prompts: the common prompt width P (tokens[:, P:] is what was generated)
     starts: Optional[np.ndarray] = None        # ragged prompts: [B] first own column of every row
     sot_logits: Optional[torch.Tensor] = None  # ragged prompts: [B, V] f32 logits at the rows' <|startoftranscript|> column (device copy)
+    winner: Optional[np.ndarray] = None        # ranked candidate groups: [clips] the winning candidate of every clip
+    lengths: Optional[np.ndarray] = None       # ranked candidate groups: [clips, G] generated tokens before the first EOT, per candidate
 
 
 class DecoderState:
@@ -186,7 +195,7 @@ def _state_for(model, B: int, pk=None) -> DecoderState:
     whisper-small), so e.g. quantize_weights() after a first decode must not find the old blob."""
     pk = pk or model.packed()
     states = model.__dict__.setdefault("_dec_states", {})
-    sid = (stream_id(), int(pk["cfg"].dec_cross_absorbed))  # one blob per library stream and cross-attention form
+    sid = (stream_id(), int(pk["cfg"].dec_cross_absorbed), int(pk["cfg"].dec_n_group))  # one blob per library stream, cross-attention form and group size
     st = states.get(sid)
     if st is not None and (st.B != B or st.blob.device != model.device or st.layout_key != _layout_of(pk, B)):
         stream().synchronize()
@@ -196,6 +205,57 @@ def _state_for(model, B: int, pk=None) -> DecoderState:
         st = DecoderState(model, B, pk)
         states[sid] = st
     return st
+
+
+# ---------------------------------------------------------------- best-of-N: candidate groups
+STREAM_HI_CANDIDATE_SHIFT = 24  # candidate k of a row with stream (lo, hi) draws from (lo, hi + (k << 24))
+
+
+def candidate_streams(streams: Sequence, n_group: int) -> List[tuple]:
+    """per-clip (lo, hi) streams -> per-row streams of clips x n_group candidates, clip-major.  Candidate 0 keeps the clip's stream."""
+    out = []
+    for lo, hi in streams:
+        lo, hi = int(lo), int(hi)
+        if n_group > 1 and not 0 <= hi < (1 << STREAM_HI_CANDIDATE_SHIFT):
+            raise ValueError(f"sample_streams: hi = {hi} must be below 2**{STREAM_HI_CANDIDATE_SHIFT} with best_of > 1 (the candidate index "
+                             "lives in the bits above)")
+        out.extend((lo, hi + (k << STREAM_HI_CANDIDATE_SHIFT)) for k in range(n_group))
+    return out
+
+
+def length_penalty_table(n: int, length_penalty: Optional[float]) -> np.ndarray:
+    """penalty[length] for length 0..n exactly as upstream's MaximumLikelihoodRanker computes it, in Python floats: ``length`` when
+    ``length_penalty`` is None, else ``((5 + length) / 6) ** length_penalty`` (Google NMT)."""
+    if length_penalty is None:
+        return np.array([float(length) for length in range(n + 1)], dtype=np.float64)
+    return np.array([((5 + length) / 6) ** length_penalty for length in range(n + 1)], dtype=np.float64)
+
+
+def _grouped(pk: dict, n_group: int) -> dict:
+    """``pk`` with cfg.dec_n_group = n_group: the same tables behind a copy of the cfg as it is NOW (cross_splits and the weights'
+    generation may change between decodes); n_group 1 is ``pk`` itself"""
+    if n_group <= 1:
+        return pk
+    cfg = _lib.ModelCfg.from_buffer_copy(pk["cfg"])
+    cfg.dec_n_group = int(n_group)
+    return {**pk, "cfg": cfg}
+
+
+def _rank_groups(st: "DecoderState", n_group: int, sample_begin: int, n: int, eot: int, length_penalty: Optional[float], s):
+    """wipa_rank_groups on the state's rows -> host (winner tokens [clips, sample_begin + n] int64, winner sums [clips], winner [clips],
+    lengths [clips, G]): clips x columns come back, not rows x columns"""
+    clips = st.B // n_group
+    dev = st.blob.device
+    pen = torch.from_numpy(length_penalty_table(n, length_penalty)).to(dev)
+    winner = torch.empty(clips, dtype=torch.int32, device=dev)
+    length = torch.empty(st.B, dtype=torch.int32, device=dev)
+    width = sample_begin + n
+    best = torch.empty(clips, width, dtype=torch.int32, device=dev)
+    best_sum = torch.empty(clips, dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().wipa_rank_groups(ptr(st.tokens), st.layout.ld_tok, st.B, n_group, sample_begin, n, eot, ptr(st.sum_logprobs), ptr(pen),
+                                           ptr(winner), ptr(length), ptr(best), width, ptr(best_sum), sptr(s)), "wipa_rank_groups")
+    return (best.cpu().numpy().astype(np.int64), best_sum.cpu().numpy().copy(), winner.cpu().numpy().astype(np.int64),
+            length.cpu().numpy().astype(np.int64).reshape(clips, n_group))
 
 
 def _mask(model, ids: Sequence[int]) -> torch.Tensor:
@@ -311,17 +371,28 @@ def greedy_collect(h: GreedyHandle) -> GreedyTokens:
 def greedy_decode_tokens(model, audio_features: torch.Tensor, initial_tokens: Sequence[int], suppress_always: Sequence[int],
                          suppress_first: Sequence[int], eot: int, max_new_tokens: Optional[int] = None,
                          stop_on_eot: bool = True, use_graph: bool = True, check_every: int = 8, rules=None,
-                         sample: Optional[Sampling] = None) -> GreedyTokens:
-    """DecodingTask._main_loop for n_group 1 (see module docstring): temperature 0, or a Categorical draw per step with ``sample``.
+                         sample: Optional[Sampling] = None, n_group: int = 1, rank: bool = False,
+                         length_penalty: Optional[float] = None) -> GreedyTokens:
+    """DecodingTask._main_loop (see module docstring): temperature 0, or a Categorical draw per step with ``sample``.
     ``audio_features`` [B, 1500, d] in the model dtype.  ``rules`` (``timestamp_rules``): ApplyTimestampRules in every greedy
-    update, on the device; ``initial_tokens`` is then the prompt without <|notimestamps|>."""
+    update, on the device; ``initial_tokens`` is then the prompt without <|notimestamps|>.
+    ``n_group`` > 1 (upstream's n_group = best_of): every clip is decoded as ``n_group`` candidate rows, clip-major, that share the
+    clip's features in the decode state; ``sample.streams`` are per CLIP and candidate k draws from ``candidate_streams``' stream k.
+    The result holds all clips x n_group rows -- or, with ``rank``, the winners of wipa_rank_groups only (one row per clip, plus
+    ``winner`` and ``lengths``), read back as clips x columns."""
     L = _lib.lib()
-    B = audio_features.shape[0]
+    clips = audio_features.shape[0]
+    B = clips * n_group
+    if n_group > 1:
+        if sample is None:
+            raise ValueError("n_group > 1 needs a sampling decode (sample=...): greedy candidates would all be the same row")
+        sample = replace(sample, streams=candidate_streams(sample.streams if sample.streams is not None else [(c, 0) for c in range(clips)],
+                                                           n_group))
     n_init = len(initial_tokens)
     if max_new_tokens is None:
         max_new_tokens = model.dims.n_text_ctx // 2
     max_new_tokens = min(max_new_tokens, model.dims.n_text_ctx - n_init)
-    pk = _packed_for(model, B, max_new_tokens)
+    pk = _grouped(_packed_for(model, B, max_new_tokens), n_group)
     st = _state_for(model, B, pk)
     m_always = _mask(model, suppress_always)
     m_first = _mask(model, list(suppress_always) + list(suppress_first))
@@ -347,8 +418,12 @@ def greedy_decode_tokens(model, audio_features: torch.Tensor, initial_tokens: Se
                 last = st.tokens[:, done_steps].cpu()  # synchronises the library stream
                 if bool((last == eot).all()):
                     break
-        toks = st.tokens[:, : done_steps + 1].cpu().numpy().astype(np.int64)
-        slp = st.sum_logprobs.cpu().numpy().copy()
+        winner = lengths = None
+        if rank and n_group > 1:  # the winners only come back: clips x columns
+            toks, slp, winner, lengths = _rank_groups(st, n_group, n_init, done_steps - (n_init - 1), eot, length_penalty, s)
+        else:
+            toks = st.tokens[:, : done_steps + 1].cpu().numpy().astype(np.int64)
+            slp = st.sum_logprobs.cpu().numpy().copy()
         last_logits = st.logits
     n_steps = done_steps - (n_init - 1)
     if stop_on_eot:
@@ -358,7 +433,7 @@ def greedy_decode_tokens(model, audio_features: torch.Tensor, initial_tokens: Se
         if all_eot.any():
             n_steps = int(np.argmax(all_eot)) + 1
             toks = toks[:, : n_init + n_steps]
-    return GreedyTokens(toks, n_steps, slp, last_logits)
+    return GreedyTokens(toks, n_steps, slp, last_logits, winner=winner, lengths=lengths)
 
 
 # ---------------------------------------------------------------- prompt conditioning: per-row prompts
@@ -434,21 +509,30 @@ def pack_prompts(rows: Optional[Sequence[Sequence[int]]], n_ctx: int, sample_len
 def ragged_decode_tokens(model, audio_features: torch.Tensor, rows: Sequence[Sequence[int]], suppress_always: Sequence[int],
                          suppress_first: Sequence[int], eot: int, max_new_tokens: Optional[int] = None, stop_on_eot: bool = True,
                          use_graph: bool = True, check_every: int = 8, rules=None, sample: Optional[Sampling] = None,
-                         pad_to: Optional[int] = None, sot_back: Optional[int] = None) -> GreedyTokens:
+                         pad_to: Optional[int] = None, sot_back: Optional[int] = None, n_group: int = 1, rank: bool = False,
+                         length_penalty: Optional[float] = None) -> GreedyTokens:
     """``greedy_decode_tokens`` for rows with their OWN initial tokens (``rows[b]``: [sot_prev] + history + sot_sequence + prefix), packed
     by ``pack_prompts``.  ``tokens`` of the result are [B, P + n_steps] with the padding in front; ``n_init`` = P.  The prompt goes through
     one batched pass (wipa_decoder_prefill_ragged); with WIPA_NO_PREFILL=1 it is walked column by column by the replayed decode step,
     which is what the batched pass is tested against.  ``sot_back``: the rows' <|startoftranscript|> sits ``sot_back`` columns before P
     (len(sot_sequence) + len(prefix)); the unfiltered logits of that column come back as ``sot_logits`` (upstream's
-    ``logits[:, sot_index]`` for no_speech_prob).  ``max_new_tokens`` is clamped to n_text_ctx - P."""
+    ``logits[:, sot_index]`` for no_speech_prob).  ``max_new_tokens`` is clamped to n_text_ctx - P.
+    ``n_group`` / ``rank`` / ``length_penalty``: candidate groups as in ``greedy_decode_tokens``: ``rows`` and ``sample.streams`` are per
+    clip, every candidate of a clip starts from the clip's own initial tokens, ``sot_logits`` and ``starts`` stay per clip."""
     L = _lib.lib()
-    B = audio_features.shape[0]
+    clips = audio_features.shape[0]
+    B = clips * n_group
     n_ctx = model.dims.n_text_ctx
     if getattr(model, "_fp8", None):
         raise NotImplementedError("prompt conditioning is not implemented for an fp8-quantised model: the ragged decode step runs on "
                                   "bf16 / f32 decoder tables")
-    if len(rows) != B:
-        raise ValueError(f"ragged_decode_tokens: {len(rows)} rows of initial tokens for {B} clips")
+    if len(rows) != clips:
+        raise ValueError(f"ragged_decode_tokens: {len(rows)} rows of initial tokens for {clips} clips")
+    if n_group > 1:
+        if sample is None:
+            raise ValueError("n_group > 1 needs a sampling decode (sample=...): greedy candidates would all be the same row")
+        sample = replace(sample, streams=candidate_streams(sample.streams if sample.streams is not None else [(c, 0) for c in range(clips)],
+                                                           n_group))
     if max_new_tokens is None:
         max_new_tokens = n_ctx // 2
     tokens_h, starts_h, P = pack_prompts(rows, n_ctx, max_new_tokens, pad_to)
@@ -457,10 +541,13 @@ def ragged_decode_tokens(model, audio_features: torch.Tensor, rows: Sequence[Seq
         raise ValueError(f"ragged_decode_tokens: a prompt width of {P} leaves no room to generate in n_text_ctx = {n_ctx}")
     if sot_back is not None and not 1 <= sot_back <= P - int(starts_h.max()):
         raise ValueError(f"ragged_decode_tokens: sot_back = {sot_back} outside the shortest row")
-    pk = _packed_for(model, B, max_new_tokens)
+    pk = _grouped(_packed_for(model, B, max_new_tokens), n_group)
     st = _state_for(model, B, pk)
     m_always = _mask(model, suppress_always)
     m_first = _mask(model, list(suppress_always) + list(suppress_first))
+    clip_starts_h = starts_h
+    if n_group > 1:  # every candidate starts from its clip's initial tokens; the features are not replicated
+        tokens_h, starts_h = np.repeat(tokens_h, n_group, axis=0), np.repeat(starts_h, n_group)
     tokens_h = np.ascontiguousarray(tokens_h, dtype=np.int32)
     starts_h = np.ascontiguousarray(starts_h, dtype=np.int32)
     i32p = C.POINTER(C.c_int32)
@@ -501,9 +588,15 @@ def ragged_decode_tokens(model, audio_features: torch.Tensor, rows: Sequence[Seq
                 last = st.tokens[:, done_steps].cpu()  # synchronises the library stream
                 if bool((last == eot).all()):
                     break
-        toks = st.tokens[:, : done_steps + 1].cpu().numpy().astype(np.int64)  # synchronises: the host arrays of begin are consumed
-        slp = st.sum_logprobs.cpu().numpy().copy()
+        winner = lengths = None
+        if rank and n_group > 1:  # the winners only come back: clips x columns
+            toks, slp, winner, lengths = _rank_groups(st, n_group, P, done_steps - (P - 1), eot, length_penalty, s)
+        else:
+            toks = st.tokens[:, : done_steps + 1].cpu().numpy().astype(np.int64)  # synchronises: the host arrays of begin are consumed
+            slp = st.sum_logprobs.cpu().numpy().copy()
         last_logits = st.logits
+        if sot_logits is not None and n_group > 1:
+            sot_logits = sot_logits[::n_group]  # the candidates of a clip share their prompt: one row per clip
     n_steps = done_steps - (P - 1)
     if stop_on_eot:
         body = toks[:, P:]
@@ -511,7 +604,9 @@ def ragged_decode_tokens(model, audio_features: torch.Tensor, rows: Sequence[Seq
         if all_eot.any():
             n_steps = int(np.argmax(all_eot)) + 1
             toks = toks[:, : P + n_steps]
-    return GreedyTokens(toks, n_steps, slp, last_logits, n_init=P, starts=starts_h.copy(), sot_logits=sot_logits)
+    ranked = rank and n_group > 1
+    return GreedyTokens(toks, n_steps, slp, last_logits, n_init=P, starts=(clip_starts_h if ranked else starts_h).copy(), sot_logits=sot_logits,
+                        winner=winner, lengths=lengths)
 
 
 def forced_decode_logits(model, audio_features: torch.Tensor, tokens: np.ndarray, n_init: int, suppress_always: Sequence[int],
@@ -599,10 +694,43 @@ def _suppress_lists(options: DecodingOptions, tok: Tokenizer):
     return sorted(set(suppress)), first
 
 
+def best_of_group(options: DecodingOptions) -> int:
+    """upstream's DecodingTask._verify_options for the sampling options, and the candidates per clip they ask for (n_group = best_of or
+    1).  ``best_of`` needs a temperature above 0 (upstream's ValueError) and, like every sampling decode here, a seed; with it
+    ``length_penalty`` lies in 0..1 (upstream's ValueError) and ``patience``, which belongs to the beams, is refused.  A decode without
+    ``best_of`` is checked as it always was: both options are ignored there, and beams stay refused (``_refuse_unsupported``)."""
+    if options.beam_size is not None and options.best_of is not None:
+        raise ValueError("beam_size and best_of can't be given together")
+    if options.temperature == 0 and options.best_of is not None:
+        raise ValueError("best_of with greedy sampling (T=0) is not compatible")
+    if options.best_of is None:
+        return 1
+    if options.length_penalty is not None and not (0 <= options.length_penalty <= 1):
+        raise ValueError("length_penalty (alpha) should be a value between 0 and 1")
+    if options.patience is not None:
+        raise NotImplementedError("patience is not implemented: it belongs to beam search (beam_size), which is not implemented")
+    n = int(options.best_of)
+    if n < 1 or n != options.best_of:
+        raise ValueError(f"best_of must be a positive integer, got {options.best_of!r}")
+    if n > 64:
+        raise ValueError(f"best_of = {n}: at most 64 candidates per clip (wipa_rank_groups ranks a group in one wave)")
+    if options.seed is None:
+        raise NotImplementedError("best_of needs DecodingOptions.seed: sampling is opt-in and reproducible by construction "
+                                  "(temperature without a seed is not implemented)")
+    if n > 1 and options.sample_streams is not None:
+        candidate_streams(options.sample_streams, n)  # hi >= 2**24 is a ValueError
+    return n
+
+
+MAX_DECODE_ROWS = 65535  # rows of one decode state: the step's kernels put the row on a 16-bit grid axis
+
+
 def _refuse_unsupported(options: DecodingOptions) -> None:
+    """what a path that decodes one row per clip does not serve.  ``decode()`` serves best_of itself (``best_of_group``) and shows this
+    function the options without it, as it does with the prompts."""
     if options.beam_size or (options.best_of or 1) > 1:
-        raise NotImplementedError("best_of and beam_size are not implemented: the reference only ever runs greedy decode and "
-                                  "mlx_whisper.transcribe's temperature schedule (SURVEY.md section 0)")
+        raise NotImplementedError("beam_size is not implemented (the reference's decoder has no beam search either) and best_of is "
+                                  "served by decode() only, at a temperature above 0 with a seed")
     if options.temperature != 0.0 and options.seed is None:
         raise NotImplementedError("temperature above 0 needs DecodingOptions.seed: sampling is opt-in and reproducible by construction "
                                   "(temperature without a seed is not implemented)")
@@ -623,7 +751,8 @@ def decode(model, mel: torch.Tensor, options: DecodingOptions = DecodingOptions(
     n_rows = 1 if mel.dim() == 2 else mel.shape[0]
     prompts = resolve_prompts(options, n_rows)
     prefix = options.prefix if (options.prefix is not None and len(options.prefix)) else None
-    _refuse_unsupported(replace(options, prompt=None, prefix=None, prompts=None))
+    n_group = best_of_group(options)  # decode() serves best_of itself too: candidate groups that share one encoder output
+    _refuse_unsupported(replace(options, prompt=None, prefix=None, prompts=None, best_of=None))
     if (prompts is not None or prefix is not None) and getattr(model, "_fp8", None):
         raise NotImplementedError("prompt / prefix conditioning is not implemented for an fp8-quantised model: the ragged decode step "
                                   "runs on bf16 / f32 decoder tables")
@@ -673,33 +802,38 @@ def decode(model, mel: torch.Tensor, options: DecodingOptions = DecodingOptions(
         if len(streams) != B:
             raise ValueError(f"sample_streams: {len(streams)} streams for {B} rows")
     results: List[Optional[DecodingResult]] = [None] * B
+    # best_of: a clip's candidates ride in ONE state and share its audio there; the ranker leaves one row per clip
+    group_kw = dict(n_group=n_group, rank=True, length_penalty=options.length_penalty) if n_group > 1 else {}
+    per_call = max(1, MAX_DECODE_ROWS // n_group)  # more rows than a state holds: chunks of whole groups
     for lang in sorted(set(languages)):
-        rows = [i for i, l in enumerate(languages) if l == lang]
+        lang_rows = [i for i, l in enumerate(languages) if l == lang]
         init = list(initial)
         init[1] = tok.to_language_token(lang)
-        sub = feats[rows] if len(rows) != B else feats
-        sample = None if streams is None else Sampling(int(options.seed), float(options.temperature), [streams[i] for i in rows],
-                                                       int(options.sample_attempt))
-        if prompts is None and prefix is None:  # no row has a prompt: the path without prompts, call for call
-            g = greedy_decode_tokens(model, sub, init, always, first, tok.eot, max_new_tokens=sample_len, rules=rules, sample=sample)
-            n_init = len(init)
-        else:
-            own = [initial_tokens(tok, init, prompts[i] if prompts is not None else None, prefix, d.n_text_ctx, sample_len) for i in rows]
-            sot_back = len(initial_tokens(tok, init, None, prefix, d.n_text_ctx, sample_len))  # sot_sequence + prefix: the same for every row
-            g = ragged_decode_tokens(model, sub, own, always, first, tok.eot, max_new_tokens=sample_len, rules=rules, sample=sample,
-                                     sot_back=sot_back if timed else None)
-            n_init = g.n_init
-            if timed:  # upstream's logits[:, sot_index] of the prompted pass
-                nsp = _no_speech_from(g.sot_logits, tok)
-                for j, i in enumerate(rows):
-                    no_speech[i] = float(nsp[j])
-        for j, i in enumerate(rows):
-            row = g.tokens[j, n_init:].tolist()
-            if tok.eot in row:
-                row = row[: row.index(tok.eot)]
-            text = tok.decode([t for t in row if t < tok.timestamp_begin]).strip()  # tokens keeps the timestamps, text does not
-            comp = len(text.encode("utf-8")) / max(len(zlib.compress(text.encode("utf-8"))), 1) if text else float("nan")
-            results[i] = DecodingResult(audio_features=feats[i], language=lang, language_probs=lang_probs[i], tokens=row,
-                                        text=text, avg_logprob=float(g.sum_logprobs[j]) / (len(row) + 1),
-                                        temperature=options.temperature, compression_ratio=comp, no_speech_prob=no_speech[i])
+        for rows in ([lang_rows] if n_group == 1 else [lang_rows[c:c + per_call] for c in range(0, len(lang_rows), per_call)]):
+            sub = feats[rows] if len(rows) != B else feats
+            sample = None if streams is None else Sampling(int(options.seed), float(options.temperature), [streams[i] for i in rows],
+                                                           int(options.sample_attempt))
+            if prompts is None and prefix is None:  # no row has a prompt: the path without prompts, call for call
+                g = greedy_decode_tokens(model, sub, init, always, first, tok.eot, max_new_tokens=sample_len, rules=rules, sample=sample,
+                                         **group_kw)
+                n_init = len(init)
+            else:
+                own = [initial_tokens(tok, init, prompts[i] if prompts is not None else None, prefix, d.n_text_ctx, sample_len) for i in rows]
+                sot_back = len(initial_tokens(tok, init, None, prefix, d.n_text_ctx, sample_len))  # sot_sequence + prefix: the same for every row
+                g = ragged_decode_tokens(model, sub, own, always, first, tok.eot, max_new_tokens=sample_len, rules=rules, sample=sample,
+                                         sot_back=sot_back if timed else None, **group_kw)
+                n_init = g.n_init
+                if timed:  # upstream's logits[:, sot_index] of the prompted pass
+                    nsp = _no_speech_from(g.sot_logits, tok)
+                    for j, i in enumerate(rows):
+                        no_speech[i] = float(nsp[j])
+            for j, i in enumerate(rows):  # with best_of row j of g is clip j's winner
+                row = g.tokens[j, n_init:].tolist()
+                if tok.eot in row:
+                    row = row[: row.index(tok.eot)]
+                text = tok.decode([t for t in row if t < tok.timestamp_begin]).strip()  # tokens keeps the timestamps, text does not
+                comp = len(text.encode("utf-8")) / max(len(zlib.compress(text.encode("utf-8"))), 1) if text else float("nan")
+                results[i] = DecodingResult(audio_features=feats[i], language=lang, language_probs=lang_probs[i], tokens=row,
+                                            text=text, avg_logprob=float(g.sum_logprobs[j]) / (len(row) + 1),
+                                            temperature=options.temperature, compression_ratio=comp, no_speech_prob=no_speech[i])
     return results[0] if single else results

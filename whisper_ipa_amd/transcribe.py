@@ -16,7 +16,11 @@ What differs from upstream, on purpose:
     decoded again, as ONE sub-batch per temperature of the schedule, from the encoder features the first decode left (no second
     log-mel, no second encoder pass), until they pass or the schedule ends (the last attempt is kept, as upstream does).  The draw
     is a function of (seed, (seek, file index), index in the schedule, position, column): a window samples the same tokens
-    whichever rows it is retried with.  Upstream draws from a global generator instead; ``best_of`` is not implemented;
+    whichever rows it is retried with.  Upstream draws from a global generator instead.  ``best_of=N`` (with a seed) is dropped at
+    temperature 0, as upstream's decode_with_fallback drops it, and passed to every retry: the window is then decoded as N candidates
+    that share its encoder output, candidate k on stream (seek, file index + (k << 24)), and the retry's result is the candidate
+    with the highest length-normalised log-probability (decoding.py).  A custom ``fallback_fn`` receives ``best_of=N``; a custom
+    ``decode_fn`` without a ``fallback_fn`` cannot serve it and is refused;
   * ``word_timestamps=True``: after a round's decode and fallback, the windows that were not skipped go through ONE
     ``timing.find_alignment`` call from the encoder features their decode left (no second log-mel, no second encoder pass), and
     every segment gains ``"words"``.  Upstream's word-duration heuristics, its snapping of segment bounds to the words and of
@@ -80,7 +84,7 @@ def split_segments(tokens: Sequence[int], tb: int, time_offset: float, segment_s
 
 
 def _refuse(condition_on_previous_text, initial_prompt, word_timestamps, clip_timestamps, hallucination_silence_threshold, temperature,
-            decode_options, can_align: bool = False) -> None:
+            decode_options, can_align: bool = False, can_retry: bool = True) -> None:
     if word_timestamps and not can_align:
         raise NotImplementedError("word_timestamps=True is not implemented without a model: a custom decode_fn needs an align_fn")
     if clip_timestamps not in (None, "0", [0], (0,)):
@@ -90,9 +94,12 @@ def _refuse(condition_on_previous_text, initial_prompt, word_timestamps, clip_ti
     temps = (temperature,) if isinstance(temperature, (int, float)) else tuple(temperature)
     if not temps or float(temps[0]) != 0.0:
         raise NotImplementedError("temperature must be 0.0 or a tuple that starts with 0.0: only temperature 0 is run")
-    for k in ("beam_size", "best_of", "prompt", "prefix"):
+    for k in ("beam_size", "prompt", "prefix"):
         if decode_options.get(k) is not None:
             raise NotImplementedError(f"{k} is not implemented")
+    if decode_options.get("best_of") is not None and not can_retry:
+        raise NotImplementedError("best_of is not implemented for a custom decode_fn without a fallback_fn: the candidates are drawn by "
+                                  "the retries (fallback_fn(..., best_of=N))")
 
 
 def _takes_prompts(fn: Callable) -> bool:
@@ -145,16 +152,18 @@ def _model_decoder(model, decode_options: dict) -> Callable:
                 out[i] = r
         return out
 
-    def retry(results, languages: List[str], *, temperature: float, attempt: int, streams, seed: int, prompts=None):
+    def retry(results, languages: List[str], *, temperature: float, attempt: int, streams, seed: int, prompts=None, best_of=None):
         """the default ``fallback_fn``: the rows' encoder features (``DecodingResult.audio_features``) decoded again at
-        ``temperature``, each row on its own stream and with the prompt it was first decoded with"""
+        ``temperature``, each row on its own stream and with the prompt it was first decoded with; ``best_of``: as that many
+        candidates per row, of which decode() keeps the best"""
         out = [None] * len(results)
         feats = torch.stack([r.audio_features for r in results])
         for lang in sorted(set(languages)):
             rows = [i for i, l in enumerate(languages) if l == lang]
             opts = DecodingOptions(**with_prompts({**decode_options, "language": lang, "without_timestamps": False,
                                                    "temperature": float(temperature), "seed": int(seed),
-                                                   "sample_streams": [streams[i] for i in rows], "sample_attempt": int(attempt)}, prompts, rows))
+                                                   "sample_streams": [streams[i] for i in rows], "sample_attempt": int(attempt),
+                                                   **({"best_of": int(best_of)} if best_of is not None else {})}, prompts, rows))
             res = decode(model, feats[rows] if len(rows) != len(languages) else feats, opts)
             for i, r in zip(rows, res):
                 out[i] = r
@@ -235,12 +244,13 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
     produced them, and neither ``needs_fallback`` nor the warning appears where a retry ran.  ``fallback_fn(results, languages,
     temperature=, attempt=, streams=, seed=)`` -> new results for those rows replaces the model's retry; with a custom ``decode_fn``
     and no ``fallback_fn`` a seed changes nothing.  ``streams[j]`` = (seek in mel frames, file index), ``attempt`` = index in the
-    schedule.  ``word_timestamps=True``: every segment gains ``"words"``: [{"word", "start", "end", "probability"}]
+    schedule.  ``best_of=N``: every retry decodes N candidates per window and keeps the best (``fallback_fn`` then gets ``best_of=N``).  ``word_timestamps=True``: every segment gains ``"words"``: [{"word", "start", "end", "probability"}]
     (timing.py); ``align_fn(results, text_tokens, num_frames, languages)`` -> one list of WordTiming per window replaces the
     model's alignment (``results``: the windows' decode results, ``text_tokens[j]`` the ids below EOT of window j's segments,
     ``num_frames[j]`` its content in mel frames); it is required with a custom ``decode_fn``."""
     _refuse(condition_on_previous_text, initial_prompt, word_timestamps, clip_timestamps, hallucination_silence_threshold, temperature,
-            decode_options, can_align=align_fn is not None or (model is not None and decode_fn is None))
+            decode_options, can_align=align_fn is not None or (model is not None and decode_fn is None),
+            can_retry=decode_fn is None or fallback_fn is not None)
     _refuse_conditioning(condition_on_previous_text, initial_prompt, model, decode_fn, fallback_fn)
     conditioning = bool(condition_on_previous_text) or initial_prompt is not None
     if word_timestamps and align_fn is None and getattr(model, "_fp8", None):
@@ -264,6 +274,8 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
         tokenizer = get_tokenizer(model.is_multilingual, num_languages=model.num_languages, language=language or "en", task="transcribe")
     tok, tb = tokenizer, int(tokenizer.timestamp_begin)
     temps = (float(temperature),) if isinstance(temperature, (int, float)) else tuple(float(t) for t in temperature)
+    # upstream's decode_with_fallback: best_of belongs to the temperatures above 0 -- the first decode never sees it, every retry does
+    best_of = decode_options.pop("best_of", None)
     if decode_fn is None:
         decode_fn = _model_decoder(model, decode_options)
         fallback_fn = fallback_fn or decode_fn.retry
@@ -307,6 +319,8 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
                     break
                 # the failing rows of the round as ONE sub-batch; the language is the file's, or what this window's first decode detected
                 more = {"prompts": [prompts[r] for r in failing]} if conditioning else {}  # the retry keeps the window's prompt
+                if best_of is not None:
+                    more["best_of"] = best_of
                 again = fallback_fn([results[r] for r in failing], [languages[live[r]] or results[r].language for r in failing],
                                     temperature=temps[attempt], attempt=attempt, streams=[(seek[live[r]], live[r]) for r in failing], seed=seed,
                                     **more)
