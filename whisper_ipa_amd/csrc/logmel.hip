@@ -472,6 +472,7 @@ extern "C" int wipa_logmel(const float* audio, int batch, int n_mels, const void
                            void* workspace, size_t workspace_bytes, wipa_stream_t stream) {
     WIPA_REQUIRE(audio && tables && mel && workspace, "wipa_logmel: null pointer");
     WIPA_REQUIRE(batch > 0, "wipa_logmel: batch must be positive");
+    WIPA_REQUIRE(mel_dtype == WIPA_F32 || mel_dtype == WIPA_BF16, "wipa_logmel: bad mel dtype %d", mel_dtype);  // before any launch
     const WsLayout W = ws_layout(batch, n_mels);
     WIPA_REQUIRE(workspace_bytes >= W.total, "wipa_logmel: workspace too small (%zu < %zu)", workspace_bytes, W.total);
     const TableLayout L = table_layout(n_mels);
@@ -486,7 +487,6 @@ extern "C" int wipa_logmel(const float* audio, int batch, int n_mels, const void
     const int per_clip = WIPA_N_FRAMES * n_mels;
     const int per_out = (WIPA_N_FRAMES + 2) * n_mels;
     if (use_fused(n_mels)) {
-        WIPA_REQUIRE(mel_dtype == WIPA_F32 || mel_dtype == WIPA_BF16, "wipa_logmel: bad mel dtype %d", mel_dtype);
         WIPA_CHECK_HIP(hipMemsetAsync(gmax, 0, batch * sizeof(unsigned), s));
         const int rc = mel_dtype == WIPA_F32 ? launch_fused_jt<float>(audio, batch, n_mels, tb, L, (float*)mel, gmax, s)
                                              : launch_fused_jt<__bf16>(audio, batch, n_mels, tb, L, (__bf16*)mel, gmax, s);
@@ -522,11 +522,9 @@ extern "C" int wipa_logmel(const float* audio, int batch, int n_mels, const void
     if (mel_dtype == WIPA_F32)
         hipLaunchKernelGGL((mel_norm_kernel<float>), dim3((per_out + 255) / 256, batch), dim3(256), 0, s, logmel, gmax,
                            n_mels, (float*)mel);
-    else if (mel_dtype == WIPA_BF16)
+    else
         hipLaunchKernelGGL((mel_norm_kernel<__bf16>), dim3((per_out + 255) / 256, batch), dim3(256), 0, s, logmel, gmax,
                            n_mels, (__bf16*)mel);
-    else
-        WIPA_REQUIRE(false, "wipa_logmel: bad mel dtype %d", mel_dtype);
     WIPA_LAUNCH_CHECK();
     // 4 zero tail rows: the conv1 GEMM's halo / K-padding over-read of the last clip
     const size_t esz = wipa_dtype_size(mel_dtype);
