@@ -246,16 +246,20 @@ def test_zero_starts_reproduce_the_plain_entry_points(refs, monkeypatch, with_ru
 
 
 class _Spy:
-    """libwipa behind a counter: every call of an entry point is recorded by name"""
+    """libwipa behind a recorder: every call of an entry point is recorded by name (``calls``) and with every plain-int argument
+    (``records``: (name, ints) -- sizes, batch, prompt width, eot, step count, use_graph, and the addresses ``ptr()`` hands over)"""
 
     def __init__(self, real):
-        self._real, self.calls = real, []
+        self._real, self.calls, self.records, self.run_steps = real, [], [], []
 
     def __getattr__(self, name):
         fn = getattr(self._real, name)
 
         def counted(*a):
             self.calls.append(name)
+            self.records.append((name, tuple(v for v in a if type(v) is int)))
+            if name.startswith("wipa_decoder_run"):
+                self.run_steps.append(a[9])  # n_steps: the tenth argument of all four run entry points
             return fn(*a)
 
         return counted
@@ -279,6 +283,7 @@ def test_decode_without_prompts_makes_the_calls_it_made(refs, monkeypatch):
     b = wipa.decode(m, feats, opts, prompts=[None, None])
     monkeypatch.setattr(_lib, "_lib", real)
     assert spy_a.calls == spy_b.calls and not any("ragged" in c for c in spy_b.calls), (spy_a.calls, spy_b.calls)
+    assert spy_a.records == spy_b.records, (spy_a.records, spy_b.records)  # ... with the same integer arguments, step counts included
     assert [r.tokens for r in a] == [r.tokens for r in b]
     # and a prompt takes the ragged entry points
     spy_c = _Spy(real)
@@ -287,6 +292,43 @@ def test_decode_without_prompts_makes_the_calls_it_made(refs, monkeypatch):
     monkeypatch.setattr(_lib, "_lib", real)
     assert "wipa_decoder_begin_ragged" in spy_c.calls and "wipa_decoder_run_ragged" in spy_c.calls and "wipa_decoder_begin" not in spy_c.calls
     assert all(np.isfinite(r.no_speech_prob) for r in c)
+
+
+@pytest.mark.parametrize("prefill", [True, False])
+def test_decode_loop_step_schedule(refs, monkeypatch, prefill):
+    """The n_steps of every wipa_decoder_run* call of one decode, for both public loops: eot = -1 (no row ever ends), 12 new tokens,
+    the default check_every of 8, no rules.  With the batched prompt pass exactly one prefill call precedes the run calls; with
+    WIPA_NO_PREFILL=1 there is none and the prompt walk (P - 1 steps) rides with the first generated columns -- after the steps up to
+    the <|startoftranscript|> column when ``sot_back`` asks for that column's logits."""
+    from whisper_ipa_amd import _lib
+    from whisper_ipa_amd.decoding import greedy_decode_tokens, ragged_decode_tokens
+
+    W, xa, _ = refs["lively"]
+    always, first = R.suppress_lists(SP)
+    m = _model(MICRO, W, torch.float32)
+    feats = xa.cuda()
+    if not prefill:
+        monkeypatch.setenv("WIPA_NO_PREFILL", "1")
+    rows = [list(ROWS[1][-5:]), list(PR.SOT_SEQUENCE)]
+    assert [len(r) for r in rows] == [5, 3] and len(PR.SOT_SEQUENCE) == 3
+    kw = dict(max_new_tokens=12)
+    cases = [("wipa_decoder_prefill", lambda: greedy_decode_tokens(m, feats, PR.SOT_SEQUENCE, always, first, -1, **kw), [8, 3], [10, 4]),
+             ("wipa_decoder_prefill_ragged", lambda: ragged_decode_tokens(m, feats, rows, always, first, -1, pad_to=6, **kw), [8, 3], [13, 4]),
+             ("wipa_decoder_prefill_ragged", lambda: ragged_decode_tokens(m, feats, rows, always, first, -1, pad_to=6, sot_back=3, **kw),
+              [8, 3], [4, 9, 4])]
+    real = _lib.lib()
+    for prefill_name, run, with_pass, stepped in cases:
+        spy = _Spy(real)
+        monkeypatch.setattr(_lib, "_lib", spy)
+        g = run()
+        monkeypatch.setattr(_lib, "_lib", real)
+        assert g.n_steps == 12
+        print(prefill_name, spy.run_steps)
+        assert spy.run_steps == (with_pass if prefill else stepped), (prefill_name, spy.run_steps)
+        passes = [c for c in spy.calls if c.startswith("wipa_decoder_prefill")]
+        assert passes == ([prefill_name] if prefill else []), passes
+        if prefill:
+            assert spy.calls.index(prefill_name) < min(i for i, c in enumerate(spy.calls) if c.startswith("wipa_decoder_run"))
 
 
 # ---------------------------------------------------------------- 6. refusals that need a live state

@@ -407,36 +407,43 @@ bool tail_fused() {
     const char* e = getenv("WIPA_DECODE_TAIL");
     return !(e && atoi(e) == 0);
 }
+// What one decode call asks of its steps.  The entry point fills it from its arguments and hands it down by const reference to
+// everything that enqueues a step or keys a graph: nothing about a call is ambient.
+struct StepCtx {
+    // the timestamp rules (wipa_decoder_run_rules / _prefill_rules; NULL: the plain greedy update).  With rules the step ends in
+    // wipa_timestamp_step_embed on the written logits: the per-wave partials cannot carry rules that depend on the row's own history,
+    // so logits_fused() is off and no step of the call is lean.
+    const wipa_decode_rules* rules;
+    // the sampling record (wipa_decoder_run_sample / _prefill_sample; NULL: temperature 0).  A sampling step ends in
+    // wipa_sample_step_embed on the written logits, like a step with rules: the draw needs every alive column of the row.
+    const void* sample;
+    // ragged prompts (wipa_decoder_run_ragged): the device array int32 [B] of the rows' first own column (NULL: every row starts at
+    // column 0).  With it the step's self-attention, its tail and its head are the RAGGED instantiations, and the tail is the row
+    // scan on written logits, like a step with rules (the per-wave partials path stays what it is).
+    const int32_t* starts;
+    int n_init, eot;  // prompt columns (the prompt width P of a ragged call) and the end-of-text id
+    const float *mask_first, *mask_always;
+    // a step whose logits nobody reads (every step of a wipa_decoder_run call but the last) does not write them at all
+    bool lean;
+};
 // The logits projection with the greedy partials in its epilogue + a tail that merges them (round 4; WIPA_LOGITS_FUSED=0 restores
 // the plain GEMM + the row-scanning tail): bf16 models without fp8 decoder tables, <= 64 rows, tail-fused steps.  Measured on
 // whisper-small, 64 clips: the logits' 64-byte stores were 8 of the GEMM's 32 us, the tail's read-back of the 13 MB another ~10.
-// A step whose logits nobody reads (every step of a wipa_decoder_run call but the last) does not write them at all: t_lean_logits.
-thread_local bool t_lean_logits = false;
-// The timestamp rules of the call in progress (wipa_decoder_run_rules / _prefill_rules; NULL: the plain greedy update).  With rules
-// the step ends in wipa_timestamp_step_embed on the written logits: the per-wave partials cannot carry rules that depend on the
-// row's own history, so logits_fused() is off and no step of the call is lean.
-thread_local const wipa_decode_rules* t_rules = nullptr;
-// The sampling record of the call in progress (wipa_decoder_run_sample / _prefill_sample; NULL: temperature 0).  A sampling step
-// ends in wipa_sample_step_embed on the written logits, like a step with rules: the draw needs every alive column of the row.
-thread_local const void* t_sample = nullptr;
-// Ragged prompts (wipa_decoder_run_ragged): the device array int32 [B] of the rows' first own column (NULL: every row starts at
-// column 0, today's step).  With it the step's self-attention, its tail and its head are the RAGGED instantiations, and the tail
-// is the row scan on written logits, like a step with rules (the per-wave partials path stays what it is).
-thread_local const int32_t* t_starts = nullptr;
-bool logits_fused(const wipa_model_cfg* cfg, int B) {
+bool logits_fused(const wipa_model_cfg* cfg, int B, const StepCtx& c) {
     const char* e = getenv("WIPA_LOGITS_FUSED");  // read per call like the other step variants: part of the graph key
     const bool on = !(e && atoi(e) == 0);
-    return on && !t_rules && !t_sample && !t_starts && tail_fused() && cfg->dec_w_dtype == 0 && wipa_logits_greedy_supported(B, cfg->n_vocab, cfg->n_text_state, cfg->dtype);
+    return on && !c.rules && !c.sample && !c.starts && tail_fused() && cfg->dec_w_dtype == 0 && wipa_logits_greedy_supported(B, cfg->n_vocab, cfg->n_text_state, cfg->dtype);
 }
 int32_t* done_counter_of(char* st, const wipa_dec_layout& L) { return (int32_t*)(st + L.pos + 64); }  // zeroed with pos by wipa_decoder_begin
 
 // x = embedding of the token at the current position, ln = first block's LayerNorm of it: what a tail-fused step expects to find
-int enqueue_step_head(const wipa_model_cfg* cfg, const void* const* w, char* st, const wipa_dec_layout& L, int B, wipa_stream_t stream) {
+int enqueue_step_head(const wipa_model_cfg* cfg, const void* const* w, char* st, const wipa_dec_layout& L, int B, const StepCtx& ctx,
+                      wipa_stream_t stream) {
     const DecScratch S = dec_scratch(cfg, B);
     char* sc = st + L.scratch;
     const void* const* lw0 = w + WIPA_DEC_GLOBAL;
-    if (t_starts)
-        return wipa_embed_layernorm_ragged((const int32_t*)(st + L.tokens), L.ld_tok, B, (const int32_t*)(st + L.pos), t_starts, w[0], emb_dtype(cfg),
+    if (ctx.starts)
+        return wipa_embed_layernorm_ragged((const int32_t*)(st + L.tokens), L.ld_tok, B, (const int32_t*)(st + L.pos), ctx.starts, w[0], emb_dtype(cfg),
                                            emb_scale(cfg, w), (const float*)w[1], cfg->n_text_ctx, (float*)(sc + S.x), (const float*)lw0[0],
                                            (const float*)lw0[1], sc + S.ln, cfg->dtype, cfg->n_text_state, 1e-5f, stream);
     return wipa_embed_layernorm((const int32_t*)(st + L.tokens), L.ld_tok, B, (const int32_t*)(st + L.pos), w[0], emb_dtype(cfg), emb_scale(cfg, w),
@@ -444,15 +451,44 @@ int enqueue_step_head(const wipa_model_cfg* cfg, const void* const* w, char* st,
                                 cfg->dtype, cfg->n_text_state, 1e-5f, stream);
 }
 
-int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, const wipa_dec_layout& L, int B, int n_init,
-                 int eot, const float* mask_first, const float* mask_always, wipa_stream_t stream) {
+// The f32 residual stream of a decode step and of the four-row prompt pass.  Residual GEMMs (out, cross.out, mlp2) are split along K
+// over workgroups; each slice writes a partial slab and the NEXT LayerNorm kernel adds the slabs to x in a fixed order first
+// (deterministic split-K, no atomics).  `pend` = slabs waiting to be folded into x.
+struct SlabStream {
+    float* x;
+    float* slabs;
+    void* ln;
+    int rows, d, dt;
+    int split_rows_max;  // split-K lives in the weight-streaming kernel: up to this many rows
+    int stream_weights;
+    wipa_stream_t stream;
+    int64_t slab_stride = (int64_t)rows * d;
+    int pend = 0;
+    int ln_step(const void* lw_w, const void* lw_b) {
+        const int rc = wipa_add_slabs_layernorm(x, d, slabs, pend, slab_stride, ln, dt, d, (const float*)lw_w, (const float*)lw_b,
+                                                rows, d, 1e-5f, stream);
+        pend = 0;
+        return rc;
+    }
+    int residual_gemm(const void* A, int K, const void* W, const void* bias) {
+        wipa_gemm_desc g;
+        memset(&g, 0, sizeof(g));
+        g.stream_weights = stream_weights;
+        g.k_slices = rows <= split_rows_max ? k_slices_for(K, dt) : 1;
+        g.slab_stride = slab_stride;
+        pend = g.k_slices;
+        return gemm(A, K, W, K, slabs, d, rows, d, K, dt, WIPA_F32, (const float*)bias, 0, nullptr, stream, &g);
+    }
+};
+
+int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, const wipa_dec_layout& L, int B, const StepCtx& ctx,
+                 wipa_stream_t stream) {
     const int dt = cfg->dtype;
     const bool tail = tail_fused();
     const size_t e = wipa_dtype_size(dt);
     const int d = cfg->n_text_state, H = cfg->n_text_head, nctx = cfg->n_text_ctx, Ta = cfg->n_audio_ctx;
     const DecScratch S = dec_scratch(cfg, B);
     char* sc = st + L.scratch;
-    float* x = (float*)(sc + S.x);
     float* x_other = (float*)(sc + S.x2);
     const bool absorbed = cfg->dec_cross_absorbed != 0;
     const bool cross_fused = !absorbed && decode_mode(cfg, B) == 2;
@@ -464,36 +500,19 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
     int64_t* posd = (int64_t*)(sc + S.posd);
     int32_t* tokens = (int32_t*)(st + L.tokens);
     int32_t* pos = (int32_t*)(st + L.pos);
-    // Residual GEMMs (out, cross.out, mlp2) are split along K over workgroups; each slice writes a
-    // partial slab and the NEXT LayerNorm kernel adds the slabs to x in a fixed order first
-    // (deterministic split-K, no atomics).  `pend` = slabs waiting to be folded into x.
     float* slabs = (float*)(sc + S.slabs);
-    const int64_t slab_stride = (int64_t)B * d;
-    int pend = 0;
-    auto ln_step = [&](const void* lw_w, const void* lw_b) -> int {
-        const int rc = wipa_add_slabs_layernorm(x, d, slabs, pend, slab_stride, ln, dt, d, (const float*)lw_w, (const float*)lw_b,
-                                                B, d, 1e-5f, stream);
-        pend = 0;
-        return rc;
-    };
-    auto residual_gemm = [&](const void* A, int K, const void* W, const void* bias) -> int {
-        wipa_gemm_desc g;
-        memset(&g, 0, sizeof(g));
-        g.k_slices = B <= 256 ? k_slices_for(K, dt) : 1;  // split-K lives in the weight-streaming (M <= 256) kernel
-        g.slab_stride = slab_stride;
-        pend = g.k_slices;
-        return gemm(A, K, W, K, slabs, d, B, d, K, dt, WIPA_F32, (const float*)bias, 0, nullptr, stream, &g);
-    };
+    SlabStream r{(float*)(sc + S.x), slabs, ln, B, d, dt, 256, 0, stream};  // r.x moves to x_other and back with every fused cross block
+    const int64_t slab_stride = r.slab_stride;
     // tail-fused steps find x (this position's embedding) and ln (the first block's LayerNorm of it) in place: written by the
     // previous step's last launch, or by enqueue_step_head before the first step of a wipa_decoder_run call
-    float* const x_first = x;
-    if (!tail) RT_CALL(wipa_embed_tokens(tokens, L.ld_tok, B, 1, 0, pos, w[0], emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], x, d, stream));
+    float* const x_first = r.x;
+    if (!tail) RT_CALL(wipa_embed_tokens(tokens, L.ld_tok, B, 1, 0, pos, w[0], emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], r.x, d, stream));
     for (int l = 0; l < cfg->n_text_layer; ++l) {
         const void* const* lw = w + WIPA_DEC_GLOBAL + WIPA_DEC_PER_LAYER * l;
         char* skv = st + L.self_kv + (size_t)l * 3 * B * nctx * d * e;  // [3][B][nctx][d]
         char* ckv = st + L.cross_kv + (size_t)l * Bc * 2 * H * Ta * 64 * e;
         bool cross_out_done = false;
-        if (!(tail && l == 0)) RT_CALL(ln_step(lw[0], lw[1]));
+        if (!(tail && l == 0)) RT_CALL(r.ln_step(lw[0], lw[1]));
         {
             // q|k|v of this position -> slot[n / d][b][pos][n % d]
             wipa_gemm_desc g;
@@ -515,33 +534,33 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
             a.v_bs = a.q_bs; a.v_rs = d; a.v_hs = 64;
             a.o_bs = d; a.o_rs = d; a.o_hs = 64;
             a.B = B; a.H = H; a.Tq = 1; a.Tk = 1; a.causal = 0; a.dtype = dt;
-            if (t_starts) RT_CALL(wipa_decode_attn_ragged(&a, t_starts, stream));  // row b sees keys starts[b] .. pos
+            if (ctx.starts) RT_CALL(wipa_decode_attn_ragged(&a, ctx.starts, stream));  // row b sees keys starts[b] .. pos
             else RT_CALL(wipa_decode_attn(&a, stream));
         }
-        RT_CALL(residual_gemm(ao, d, lw[4], lw[5]));
+        RT_CALL(r.residual_gemm(ao, d, lw[4], lw[5]));
         if (cross_fused) {
             // one launch for [slab sum + residual + cross_attn_ln + cross query + cross-attention]; the residual row moves to
             // the other buffer (H workgroups read the row that one of them writes)
             wipa_cross_block_desc c;
             memset(&c, 0, sizeof(c));
-            c.x_in = x; c.x_out = x_other; c.slabs = slabs; c.bias_o = nullptr;  // slab 0 carries the out-projection bias
+            c.x_in = r.x; c.x_out = x_other; c.slabs = slabs; c.bias_o = nullptr;  // slab 0 carries the out-projection bias
             c.ln_w = (const float*)lw[6]; c.ln_b = (const float*)lw[7]; c.wq = lw[8]; c.bq = (const float*)lw[9];
             c.kv = ckv; c.out = ao; c.slab_stride = slab_stride;
-            c.n_slabs = pend; c.B = B; c.d = d; c.H = H; c.Tk = Ta; c.dtype = dt; c.eps = 1e-5f; c.qk_scale = QK_SCALE;
+            c.n_slabs = r.pend; c.B = B; c.d = d; c.H = H; c.Tk = Ta; c.dtype = dt; c.eps = 1e-5f; c.qk_scale = QK_SCALE;
             c.n_group = cfg->dec_n_group;
             RT_CALL(wipa_decode_cross_block(&c, stream));
-            pend = 0;
-            std::swap(x, x_other);
-        } else if (absorbed && absorbed_block_fused() && pend <= 4) {
+            r.pend = 0;
+            std::swap(r.x, x_other);
+        } else if (absorbed && absorbed_block_fused() && r.pend <= 4) {
             // three launches: [slab sum + residual + cross_attn_ln + cross query + absorbed query] -> stream over the encoder output
             // -> [merge + value projection]; the residual row moves to the other buffer like in the fused cross block
             const void* wkT = w[WIPA_DEC_GLOBAL + WIPA_DEC_PER_LAYER * cfg->n_text_layer + WIPA_DEC_ABSORBED_PER_LAYER * l];
             wipa_cross_block_desc c;
             memset(&c, 0, sizeof(c));
-            c.x_in = x; c.x_out = x_other; c.slabs = slabs; c.bias_o = nullptr;
+            c.x_in = r.x; c.x_out = x_other; c.slabs = slabs; c.bias_o = nullptr;
             c.ln_w = (const float*)lw[6]; c.ln_b = (const float*)lw[7]; c.wq = lw[8]; c.bq = (const float*)lw[9];
             c.kv = st + L.cross_kv; c.out = ao; c.slab_stride = slab_stride;
-            c.n_slabs = pend; c.B = B; c.d = d; c.H = H; c.Tk = Ta; c.dtype = dt; c.eps = 1e-5f; c.qk_scale = QK_SCALE;
+            c.n_slabs = r.pend; c.B = B; c.d = d; c.H = H; c.Tk = Ta; c.dtype = dt; c.eps = 1e-5f; c.qk_scale = QK_SCALE;
             c.cross_splits = cfg->dec_cross_splits;
             c.n_group = cfg->dec_n_group;
             if (absorbed_merge_out()) {
@@ -549,17 +568,17 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
                 RT_CALL(wipa_decode_cross_absorbed_block_out(&c, wkT, (const char*)lw[10] + (size_t)d * d * e, (const float*)lw[11] + d,
                                                              lw[12], (const float*)lw[13], slabs, slab_stride, sc + S.absorbed,
                                                              S.greedy_part - S.absorbed, stream));
-                pend = H;
-                std::swap(x, x_other);
+                r.pend = H;
+                std::swap(r.x, x_other);
                 cross_out_done = true;
             } else {
                 RT_CALL(wipa_decode_cross_absorbed_block(&c, wkT, (const char*)lw[10] + (size_t)d * d * e, (const float*)lw[11] + d,
                                                          sc + S.absorbed, S.greedy_part - S.absorbed, stream));
-                pend = 0;
-                std::swap(x, x_other);
+                r.pend = 0;
+                std::swap(r.x, x_other);
             }
         } else {
-            RT_CALL(ln_step(lw[6], lw[7]));
+            RT_CALL(r.ln_step(lw[6], lw[7]));
             {
                 wipa_gemm_desc g;
                 memset(&g, 0, sizeof(g));
@@ -579,19 +598,19 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
                 RT_CALL(wipa_decode_cross_attn(q, ckv, ao, B, H, Ta, dt, stream));
             }
         }
-        if (!cross_out_done) RT_CALL(residual_gemm(ao, d, lw[12], lw[13]));
-        RT_CALL(ln_step(lw[14], lw[15]));
+        if (!cross_out_done) RT_CALL(r.residual_gemm(ao, d, lw[12], lw[13]));
+        RT_CALL(r.ln_step(lw[14], lw[15]));
         RT_CALL(gemm(ln, d, lw[16], d, hb, 4 * d, B, 4 * d, d, dt, dt, (const float*)lw[17], 1, nullptr, stream));
-        RT_CALL(residual_gemm(hb, 4 * d, lw[18], lw[19]));
+        RT_CALL(r.residual_gemm(hb, 4 * d, lw[18], lw[19]));
     }
-    RT_CALL(ln_step(w[2], w[3]));
+    RT_CALL(r.ln_step(w[2], w[3]));
     float* logits = (float*)(st + L.logits);
-    if (logits_fused(cfg, B)) {
+    if (logits_fused(cfg, B, ctx)) {
         const void* const* lw0 = w + WIPA_DEC_GLOBAL;
         float* part = (float*)(sc + S.greedy_part);
-        RT_CALL(wipa_logits_greedy(ln, d, w[0], d, t_lean_logits ? nullptr : logits, L.ld_logits, B, cfg->n_vocab, d, mask_first, mask_always, pos,
-                                   n_init, part, wipa_logits_greedy_partials_bytes(B), stream));
-        RT_CALL(wipa_greedy_step_embed_partials(part, WIPA_GREEDY_PARTS, B, tokens, L.ld_tok, pos, posd, done_counter_of(st, L), n_init, eot,
+        RT_CALL(wipa_logits_greedy(ln, d, w[0], d, ctx.lean ? nullptr : logits, L.ld_logits, B, cfg->n_vocab, d, ctx.mask_first, ctx.mask_always, pos,
+                                   ctx.n_init, part, wipa_logits_greedy_partials_bytes(B), stream));
+        RT_CALL(wipa_greedy_step_embed_partials(part, WIPA_GREEDY_PARTS, B, tokens, L.ld_tok, pos, posd, done_counter_of(st, L), ctx.n_init, ctx.eot,
                                                 (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), w[0], emb_dtype(cfg), emb_scale(cfg, w),
                                                 (const float*)w[1], nctx, x_first, (const float*)lw0[0], (const float*)lw0[1], ln, dt, d, 1e-5f,
                                                 stream));
@@ -600,18 +619,18 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
     RT_CALL(gemm(ln, d, w[0], d, logits, L.ld_logits, B, cfg->n_vocab, d, dt, WIPA_F32, nullptr, 0, nullptr, stream));
     if (tail) {
         // greedy update + embedding of the chosen token + first LayerNorm of the NEXT position + position advance: one launch
-        // (with t_rules the timestamp rules, with t_sample the draw, with t_starts the RAGGED tails: position embedding and sampling
+        // (with ctx.rules the timestamp rules, with ctx.sample the draw, with ctx.starts the RAGGED tails: position embedding and sampling
         // counter at the row's own position)
         const void* const* lw0 = w + WIPA_DEC_GLOBAL;
-        RT_CALL(wipa_step_tail(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, posd, done_counter_of(st, L),
-                               n_init, eot, t_rules, t_sample, t_starts, (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), w[0],
+        RT_CALL(wipa_step_tail(logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos, posd,
+                               done_counter_of(st, L), ctx.n_init, ctx.eot, ctx.rules, ctx.sample, ctx.starts, (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), w[0],
                                emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], nctx, x_first, (const float*)lw0[0], (const float*)lw0[1], ln,
                                dt, d, 1e-5f, stream));
         return WIPA_OK;
     }
-    WIPA_REQUIRE(!t_rules && !t_sample && !t_starts, "decode step: the timestamp rules, sampling and ragged prompts need the fused tail (WIPA_DECODE_TAIL=0 is set)");
-    RT_CALL(wipa_greedy_step(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, n_init,
-                             eot, (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), stream));
+    WIPA_REQUIRE(!ctx.rules && !ctx.sample && !ctx.starts, "decode step: the timestamp rules, sampling and ragged prompts need the fused tail (WIPA_DECODE_TAIL=0 is set)");
+    RT_CALL(wipa_greedy_step(logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos, ctx.n_init,
+                             ctx.eot, (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), stream));
     hipLaunchKernelGGL(advance_pos_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pos, posd, d);
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;
@@ -619,12 +638,12 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
 
 // One decoder step with the fused blocks of decode_fused.hip: embed + 5 launches per layer + final LayerNorm + logits +
 // greedy update + position advance (65 launches for whisper-small instead of 137).  Same state transitions as enqueue_step.
-int enqueue_step_fused(const wipa_model_cfg* cfg, const void* const* w, char* st, const wipa_dec_layout& L, int B, int n_init,
-                       int eot, const float* mask_first, const float* mask_always, wipa_stream_t stream) {
+int enqueue_step_fused(const wipa_model_cfg* cfg, const void* const* w, char* st, const wipa_dec_layout& L, int B, const StepCtx& ctx,
+                       wipa_stream_t stream) {
     const int dt = cfg->dtype;
     const size_t e = wipa_dtype_size(dt);
     const int d = cfg->n_text_state, H = cfg->n_text_head, nctx = cfg->n_text_ctx, Ta = cfg->n_audio_ctx;
-    WIPA_REQUIRE(!t_rules && !t_sample && !t_starts, "decode step: the timestamp rules, sampling and ragged prompts need the fused tail (WIPA_DECODE_FUSED=1 is set)");
+    WIPA_REQUIRE(!ctx.rules && !ctx.sample && !ctx.starts, "decode step: the timestamp rules, sampling and ragged prompts need the fused tail (WIPA_DECODE_FUSED=1 is set)");
     const DecScratch S = dec_scratch(cfg, B);
     char* sc = st + L.scratch;
     float* xa = (float*)(sc + S.x);
@@ -677,8 +696,8 @@ int enqueue_step_fused(const wipa_model_cfg* cfg, const void* const* w, char* st
     RT_CALL(wipa_add_slabs_layernorm(cur, d, nullptr, 0, 0, ln, dt, d, (const float*)w[2], (const float*)w[3], B, d, 1e-5f, stream));
     float* logits = (float*)(st + L.logits);
     RT_CALL(gemm(ln, d, w[0], d, logits, L.ld_logits, B, cfg->n_vocab, d, dt, WIPA_F32, nullptr, 0, nullptr, stream));
-    RT_CALL(wipa_greedy_step(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, n_init,
-                             eot, (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), stream));
+    RT_CALL(wipa_greedy_step(logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos, ctx.n_init,
+                             ctx.eot, (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), stream));
     hipLaunchKernelGGL(advance_pos_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pos, posd, d);
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;
@@ -705,10 +724,10 @@ bool use_fused_step(const wipa_model_cfg* cfg, int B) { return !cfg->dec_cross_a
 // whether the steps of this configuration end with the fused tail (and therefore need enqueue_step_head before the first one)
 bool step_needs_head(const wipa_model_cfg* cfg, int B) { return !use_fused_step(cfg, B) && tail_fused(); }
 
-int enqueue_decode_step(const wipa_model_cfg* cfg, const void* const* w, char* st, const wipa_dec_layout& L, int B, int n_init,
-                        int eot, const float* mask_first, const float* mask_always, wipa_stream_t stream) {
-    if (use_fused_step(cfg, B)) return enqueue_step_fused(cfg, w, st, L, B, n_init, eot, mask_first, mask_always, stream);
-    return enqueue_step(cfg, w, st, L, B, n_init, eot, mask_first, mask_always, stream);
+int enqueue_decode_step(const wipa_model_cfg* cfg, const void* const* w, char* st, const wipa_dec_layout& L, int B, const StepCtx& ctx,
+                        wipa_stream_t stream) {
+    if (use_fused_step(cfg, B)) return enqueue_step_fused(cfg, w, st, L, B, ctx, stream);
+    return enqueue_step(cfg, w, st, L, B, ctx, stream);
 }
 
 __global__ void set_pos_kernel(int32_t* pos, int64_t* posd, int value, int d) {
@@ -716,56 +735,65 @@ __global__ void set_pos_kernel(int32_t* pos, int64_t* posd, int value, int d) {
     *posd = (int64_t)value * d;
 }
 
+// The first new token after a batched prompt pass over P = ctx.n_init columns, from the last column's logits in the state: the
+// position is set to P - 1, the update writes token P (a draw with a sampling record -- at the row's own position with starts --,
+// rule 4 under rules: timestamps only, capped at max_initial_timestamp_index), the position advances.
+int enqueue_first_token(const wipa_model_cfg* cfg, char* st, const wipa_dec_layout& L, int B, const StepCtx& ctx, wipa_stream_t stream) {
+    const int P = ctx.n_init, d = cfg->n_text_state;
+    float* logits = (float*)(st + L.logits);
+    int64_t* posd = (int64_t*)(st + L.scratch + dec_scratch(cfg, B).posd);
+    int32_t* tokens = (int32_t*)(st + L.tokens);
+    int32_t* pos = (int32_t*)(st + L.pos);
+    float* sums = (float*)(st + L.sum_logprobs);
+    int32_t* not_done = (int32_t*)(st + L.not_done);
+    hipLaunchKernelGGL(set_pos_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pos, posd, P - 1, d);
+    if (ctx.sample && ctx.starts)
+        RT_CALL(wipa_sample_step_ragged(logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos, P, ctx.eot,
+                                        ctx.rules, ctx.sample, ctx.starts, sums, not_done, stream));
+    else if (ctx.sample)
+        RT_CALL(wipa_sample_step(logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos, P, ctx.eot, ctx.rules,
+                                 ctx.sample, sums, not_done, stream));
+    else if (ctx.rules)
+        RT_CALL(wipa_timestamp_step(logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos, P, ctx.eot, ctx.rules,
+                                    sums, not_done, stream));
+    else
+        RT_CALL(wipa_greedy_step(logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos, P, ctx.eot, sums,
+                                 not_done, stream));
+    hipLaunchKernelGGL(advance_pos_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pos, posd, d);
+    WIPA_LAUNCH_CHECK();
+    return WIPA_OK;
+}
+
 // The first n_init decoder steps as ONE batched pass over the prompt (rows (b, t), t < n_init): mlx_whisper runs the
 // prompt through the decoder in one forward too.  Self-K/V of positions 0..n_init-1 land in the cache, the cross K/V are
 // streamed once for all prompt positions (decode_attn_multi_kernel), logits are computed for the last position only, and
 // the greedy update writes token n_init.  Afterwards the state equals that after n_init calls of enqueue_step.
-int enqueue_prefill(const wipa_model_cfg* cfg, const void* const* w, char* st, const wipa_dec_layout& L, int B, int n_init,
-                    int eot, const float* mask_first, const float* mask_always, wipa_stream_t stream) {
+int enqueue_prefill(const wipa_model_cfg* cfg, const void* const* w, char* st, const wipa_dec_layout& L, int B, const StepCtx& ctx,
+                    wipa_stream_t stream) {
     const int dt = cfg->dtype;
     const size_t e = wipa_dtype_size(dt);
     const int d = cfg->n_text_state, H = cfg->n_text_head, nctx = cfg->n_text_ctx, Ta = cfg->n_audio_ctx;
-    const int P = n_init, M = B * P;
+    const int P = ctx.n_init, M = B * P;
     const int G = group_of(cfg), Bc = clips_of(cfg, B);
     const DecScratch S = dec_scratch(cfg, B);
     char* sc = st + L.scratch;
-    float* x = (float*)(sc + S.x);
     char* ln = sc + S.ln;
     void* q = sc + S.q;
     void* ao = sc + S.ao;
     void* hb = sc + S.h;
-    int64_t* posd = (int64_t*)(sc + S.posd);
-    int32_t* tokens = (int32_t*)(st + L.tokens);
-    int32_t* pos = (int32_t*)(st + L.pos);
-    float* slabs = (float*)(sc + S.slabs);
-    const int64_t slab_stride = (int64_t)M * d;
-    int pend = 0;
-    auto ln_step = [&](const void* lw_w, const void* lw_b) -> int {
-        const int rc = wipa_add_slabs_layernorm(x, d, slabs, pend, slab_stride, ln, dt, d, (const float*)lw_w, (const float*)lw_b,
-                                                M, d, 1e-5f, stream);
-        pend = 0;
-        return rc;
-    };
-    auto residual_gemm = [&](const void* A, int K, const void* W, const void* bias) -> int {
-        wipa_gemm_desc g;
-        memset(&g, 0, sizeof(g));
-        g.stream_weights = 1;
-        g.k_slices = M <= 1024 ? k_slices_for(K, dt) : 1;
-        g.slab_stride = slab_stride;
-        pend = g.k_slices;
-        return gemm(A, K, W, K, slabs, d, M, d, K, dt, WIPA_F32, (const float*)bias, 0, nullptr, stream, &g);
-    };
-    RT_CALL(wipa_embed_tokens(tokens, L.ld_tok, B, P, 0, nullptr, w[0], emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], x, d, stream));
+    SlabStream r{(float*)(sc + S.x), (float*)(sc + S.slabs), ln, M, d, dt, 1024, 1, stream};
+    RT_CALL(wipa_embed_tokens((const int32_t*)(st + L.tokens), L.ld_tok, B, P, 0, nullptr, w[0], emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1],
+                              r.x, d, stream));
     for (int l = 0; l < cfg->n_text_layer; ++l) {
         const void* const* lw = w + WIPA_DEC_GLOBAL + WIPA_DEC_PER_LAYER * l;
         char* skv = st + L.self_kv + (size_t)l * 3 * B * nctx * d * e;  // [3][B][nctx][d]
         char* ckv = st + L.cross_kv + (size_t)l * Bc * 2 * H * Ta * 64 * e;
-        RT_CALL(ln_step(lw[0], lw[1]));
+        RT_CALL(r.ln_step(lw[0], lw[1]));
         {
             // q|k|v of positions 0..P-1 -> slot[n / d][b][t][n % d]
             wipa_gemm_desc g;
             memset(&g, 0, sizeof(g));
-        g.stream_weights = 1;
+            g.stream_weights = 1;
             g.col_scale_n = 2 * d; g.col_scale = QK_SCALE;
             g.rg_in = P; g.rg_valid = P; g.rg_stride = (int64_t)nctx * d;
             g.cg_in = d; g.cg_stride = (int64_t)B * nctx * d;
@@ -783,12 +811,12 @@ int enqueue_prefill(const wipa_model_cfg* cfg, const void* const* w, char* st, c
             a.B = B; a.H = H; a.Tq = P; a.Tk = P; a.causal = 1; a.dtype = dt;
             RT_CALL(wipa_attention(&a, stream));
         }
-        RT_CALL(residual_gemm(ao, d, lw[4], lw[5]));
-        RT_CALL(ln_step(lw[6], lw[7]));
+        RT_CALL(r.residual_gemm(ao, d, lw[4], lw[5]));
+        RT_CALL(r.ln_step(lw[6], lw[7]));
         {
             wipa_gemm_desc g;
             memset(&g, 0, sizeof(g));
-        g.stream_weights = 1;
+            g.stream_weights = 1;
             g.col_scale_n = d; g.col_scale = QK_SCALE;
             RT_CALL(gemm(ln, d, lw[8], d, q, d, M, d, d, dt, dt, (const float*)lw[9], 0, nullptr, stream, &g));
         }
@@ -805,34 +833,21 @@ int enqueue_prefill(const wipa_model_cfg* cfg, const void* const* w, char* st, c
         } else {
             RT_CALL(wipa_decode_cross_attn_multi(q, ckv, ao, B, H, Ta, P, dt, stream));
         }
-        RT_CALL(residual_gemm(ao, d, lw[12], lw[13]));
-        RT_CALL(ln_step(lw[14], lw[15]));
+        RT_CALL(r.residual_gemm(ao, d, lw[12], lw[13]));
+        RT_CALL(r.ln_step(lw[14], lw[15]));
         {
             wipa_gemm_desc g;
             memset(&g, 0, sizeof(g));
             g.stream_weights = 1;
             RT_CALL(gemm(ln, d, lw[16], d, hb, 4 * d, M, 4 * d, d, dt, dt, (const float*)lw[17], 1, nullptr, stream, &g));
         }
-        RT_CALL(residual_gemm(hb, 4 * d, lw[18], lw[19]));
+        RT_CALL(r.residual_gemm(hb, 4 * d, lw[18], lw[19]));
     }
-    RT_CALL(ln_step(w[2], w[3]));
-    float* logits = (float*)(st + L.logits);
+    RT_CALL(r.ln_step(w[2], w[3]));
     // logits of the LAST prompt position only: rows (b, P-1) of ln, i.e. row stride P*d
-    RT_CALL(gemm(ln + (size_t)(P - 1) * d * e, (int64_t)P * d, w[0], d, logits, L.ld_logits, B, cfg->n_vocab, d, dt, WIPA_F32, nullptr, 0,
+    RT_CALL(gemm(ln + (size_t)(P - 1) * d * e, (int64_t)P * d, w[0], d, st + L.logits, L.ld_logits, B, cfg->n_vocab, d, dt, WIPA_F32, nullptr, 0,
                  nullptr, stream));
-    hipLaunchKernelGGL(set_pos_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pos, posd, P - 1, d);
-    if (t_sample)  // the first sampled token is a draw too (with rule 4 under rules)
-        RT_CALL(wipa_sample_step(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, n_init, eot, t_rules, t_sample,
-                                 (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), stream));
-    else if (t_rules)  // the first sampled token: rule 4 (timestamps only, capped at max_initial_timestamp_index)
-        RT_CALL(wipa_timestamp_step(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, n_init, eot, t_rules,
-                                    (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), stream));
-    else
-        RT_CALL(wipa_greedy_step(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, n_init,
-                                 eot, (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), stream));
-    hipLaunchKernelGGL(advance_pos_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pos, posd, d);
-    WIPA_LAUNCH_CHECK();
-    return WIPA_OK;
+    return enqueue_first_token(cfg, st, L, B, ctx, stream);
 }
 
 // Hardware-counter collection (rocprofv3 --pmc sets ROCPROF_COUNTER_COLLECTION) serialises every dispatch and intercepts the
@@ -892,13 +907,6 @@ int state_fits(const char* who, const wipa_dec_layout& L, size_t state_bytes) {
 // The starts array of a ragged call enters with its ADDRESS too (NULL: no prompts): the replayed kernels read the rows' starts from it.
 // The ragged prompt pass (kind 3 + 16 * (sot_col + 1)) bakes its workspace in as well: the last term (NULL otherwise).
 typedef std::tuple<const void*, const void*, const void*, const void*, int, int, int, int, int, int, int, int, int, const void*, const void*, const void*> GraphKey;  // ..., generation, kind: 0 step, 1 prefill, 2 lean step (no logit stores), rules, sampling record, starts, workspace
-// the rules of a call, for its scope: set on entry, cleared on every way out
-struct RulesScope {
-    explicit RulesScope(const wipa_decode_rules* r, const void* sample = nullptr, const int32_t* starts = nullptr) {
-        t_rules = r; t_sample = sample; t_starts = starts;
-    }
-    ~RulesScope() { t_rules = nullptr; t_sample = nullptr; t_starts = nullptr; }
-};
 // sampling lives in the fused step tail, like the rules: refused before anything is enqueued where the step cannot carry it
 int sample_servable(const char* who, const wipa_model_cfg* cfg, int B, const void* sample) {
     if (!sample) return WIPA_OK;
@@ -944,21 +952,20 @@ std::map<GraphKey, hipGraphExec_t> g_graphs;
 // the variant word of a step or prefill key: every switch that changes what enqueue_decode_step / enqueue_prefill enqueue for (cfg, B).
 // (The streaming launch's resident_groups argument is baked into the captured step too, but needs no term here: it is a function
 // of B, the width, the frame count and dec_cross_splits -- all in the key -- and of a budget that is constant per process.)
-// Read inside the call's RulesScope: logits_fused() looks at the rules, the sampling record and the starts of the call.
-bool lean_steps(const wipa_model_cfg* cfg, int B) { return !use_fused_step(cfg, B) && logits_fused(cfg, B); }
-int step_variant(const wipa_model_cfg* cfg, int B) {
+// The call's context decides with the switches: logits_fused() looks at its rules, its sampling record and its starts.
+bool lean_steps(const wipa_model_cfg* cfg, int B, const StepCtx& c) { return !use_fused_step(cfg, B) && logits_fused(cfg, B, c); }
+int step_variant(const wipa_model_cfg* cfg, int B, const StepCtx& c) {
     return cfg->dtype * 2 + t_f32_split + 4 * decode_mode(cfg, B) + 16 * cfg->dec_w_dtype +
            64 * cfg->dec_cross_absorbed * (absorbed_block_fused() ? 2 : 1) + 256 * (int)tail_fused() + 512 * (int)absorbed_merge_out() +
-           1024 * cfg->dec_cross_splits + 8192 * (int)lean_steps(cfg, B) +
+           1024 * cfg->dec_cross_splits + 8192 * (int)lean_steps(cfg, B, c) +
            16384 * (cfg->dec_cross_absorbed ? wipa_cross_absorbed_loop_variant() : 0) + 65536 * (group_of(cfg) > 1 ? group_of(cfg) : 0);
 }
-// a key from the arguments of a decode call; the three rule terms are 0 without rules
-GraphKey graph_key(const wipa_model_cfg* cfg, const void* const* w, const void* state, const float* mask_first, const float* mask_always, int B,
-                   int n_init, int eot, int variant, int kind, const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev,
+// a key from the context of a decode call; the three rule terms are 0 without rules
+GraphKey graph_key(const wipa_model_cfg* cfg, const void* const* w, const void* state, int B, const StepCtx& c, int variant, int kind,
                    const void* workspace) {
-    return GraphKey(state, (const void*)w, (const void*)mask_first, (const void*)mask_always, B, n_init, eot, variant, cfg->weights_generation, kind,
-                    rules ? rules->timestamp_begin : 0, rules ? rules->no_timestamps : 0, rules ? rules->max_initial_timestamp_index : 0, sample,
-                    (const void*)starts_dev, workspace);
+    return GraphKey(state, (const void*)w, (const void*)c.mask_first, (const void*)c.mask_always, B, c.n_init, c.eot, variant,
+                    cfg->weights_generation, kind, c.rules ? c.rules->timestamp_begin : 0, c.rules ? c.rules->no_timestamps : 0,
+                    c.rules ? c.rules->max_initial_timestamp_index : 0, c.sample, (const void*)c.starts, workspace);
 }
 // The executable graph cached under `key`.  When there is none, `enqueue` is captured on s (relaxed mode, nothing but kernel launches
 // between begin and end), instantiated and inserted; an enqueue that fails ends the capture, destroys the graph and hands its code back.
@@ -986,6 +993,39 @@ int cached_graph(const GraphKey& key, hipStream_t s, Enqueue&& enqueue, hipGraph
         g_graphs[key] = exec;
     }
     *out = exec;
+    return WIPA_OK;
+}
+// A prompt pass: replayed from the graph cached under `key`, or enqueued as it is -- without use_graph, where graphs are off, and
+// quietly on the default stream, which cannot be captured.
+template <typename Enqueue>
+int replay_or_enqueue(bool use_graph, hipStream_t s, const GraphKey& key, Enqueue&& enqueue) {
+    if (!use_graph || s == nullptr || !graphs_allowed()) return enqueue();
+    hipGraphExec_t exec = nullptr;
+    RT_CALL(cached_graph(key, s, enqueue, &exec));
+    WIPA_CHECK_HIP(hipGraphLaunch(exec, s));
+    return WIPA_OK;
+}
+
+// The names an entry point's refusals carry: its own, and those of the forwarding entry points whose argument a check is about.
+struct EntryNames {
+    const char *own, *rules, *sample, *starts;
+};
+// What wipa_decoder_run_ragged, wipa_decoder_prefill_sample and wipa_decoder_prefill_ragged do between their argument checks and
+// their first launch, in this order: what the steps cannot serve is refused, then the entry point's `own_checks`, then a state blob
+// too small for the layout (*L); every kernel attribute is set outside any capture; a call that will enqueue steps (n_steps > 0)
+// starts the greedy tail's arrival counter at zero (4 bytes, outside the step graph).
+template <typename OwnChecks>
+int decode_prologue(const EntryNames& who, const wipa_model_cfg* cfg, int B, const StepCtx& c, char* st, size_t state_bytes, int n_steps,
+                    hipStream_t s, wipa_dec_layout* L, OwnChecks&& own_checks) {
+    RT_CALL(rules_servable(who.rules, cfg, B, c.eot, c.rules));
+    RT_CALL(sample_servable(who.sample, cfg, B, c.sample));
+    RT_CALL(starts_servable(who.starts, cfg, B, c.n_init, c.starts));
+    RT_CALL(group_servable(who.own, cfg, B));
+    RT_CALL(own_checks());
+    *L = dec_layout(cfg, B);
+    RT_CALL(state_fits(who.own, *L, state_bytes));
+    RT_CALL(init_before_capture(cfg));
+    if (n_steps > 0) WIPA_CHECK_HIP(hipMemsetAsync(done_counter_of(st, *L), 0, sizeof(int32_t), s));
     return WIPA_OK;
 }
 
@@ -1143,55 +1183,43 @@ extern "C" int wipa_decoder_run_ragged(const wipa_model_cfg* cfg, const void* co
     RT_CALL(cfg_check(cfg));
     SplitScope split_scope(cfg);
     WIPA_REQUIRE(w && state && mask_first && mask_always && B > 0 && n_steps >= 0, "wipa_decoder_run: bad arguments");
-    RT_CALL(rules_servable("wipa_decoder_run_rules", cfg, B, eot, rules));
-    RT_CALL(sample_servable("wipa_decoder_run_sample", cfg, B, sample));
-    RT_CALL(starts_servable("wipa_decoder_run_ragged", cfg, B, n_init, starts_dev));
-    RT_CALL(group_servable("wipa_decoder_run", cfg, B));
-    // the position lives on the device: a call may carry the prompt walk (P - 1 steps) besides the new tokens, so what can be refused
-    // here is a step count that no position admits
-    WIPA_REQUIRE(!starts_dev || n_steps <= cfg->n_text_ctx - 1, "wipa_decoder_run_ragged: n_steps=%d with P=%d runs past n_text_ctx=%d", n_steps,
-                 n_init, cfg->n_text_ctx);
-    RulesScope rules_scope(rules, sample, starts_dev);
-    W8Scope w8_scope(cfg, w);
-    const wipa_dec_layout L = dec_layout(cfg, B);
-    RT_CALL(state_fits("wipa_decoder_run", L, state_bytes));
+    // every step of the call but the LAST is "lean" when the logits projection carries the greedy partials: its logits are not
+    // written (state.logits holds those of the last step of a call, which is what callers read)
+    const StepCtx full{rules, sample, starts_dev, n_init, eot, mask_first, mask_always, false};
+    StepCtx lean = full;
+    lean.lean = true;
+    static const EntryNames who = {"wipa_decoder_run", "wipa_decoder_run_rules", "wipa_decoder_run_sample", "wipa_decoder_run_ragged"};
     char* st = (char*)state;
     hipStream_t s = (hipStream_t)stream;
-    RT_CALL(init_before_capture(cfg));
+    wipa_dec_layout L;
+    RT_CALL(decode_prologue(who, cfg, B, full, st, state_bytes, n_steps, s, &L, [&]() -> int {
+        // the position lives on the device: a call may carry the prompt walk (P - 1 steps) besides the new tokens, so what can be
+        // refused here is a step count that no position admits
+        WIPA_REQUIRE(!starts_dev || n_steps <= cfg->n_text_ctx - 1, "wipa_decoder_run_ragged: n_steps=%d with P=%d runs past n_text_ctx=%d", n_steps,
+                     n_init, cfg->n_text_ctx);
+        return WIPA_OK;
+    }));
     if (n_steps == 0) return WIPA_OK;
-    // the greedy tail's arrival counter starts every call at zero (4 bytes, outside the step graph)
-    WIPA_CHECK_HIP(hipMemsetAsync(done_counter_of(st, L), 0, sizeof(int32_t), s));
+    W8Scope w8_scope(cfg, w);
     // the first step's input rows (embedding + first LayerNorm of the token at the current position): every later step gets
     // them from the previous step's last launch.  Outside the graph: once per call, whatever wrote the token (the greedy
     // update, the prompt, a forced history)
-    if (step_needs_head(cfg, B)) RT_CALL(enqueue_step_head(cfg, w, st, L, B, stream));
-    // every step of the call but the LAST is "lean" when the logits projection carries the greedy partials: its logits are not
-    // written (state.logits holds those of the last step of a call, which is what callers read)
-    const bool lean_ok = lean_steps(cfg, B);
-    struct LeanScope {
-        explicit LeanScope(bool v) { t_lean_logits = v; }
-        ~LeanScope() { t_lean_logits = false; }
-    };
+    if (step_needs_head(cfg, B)) RT_CALL(enqueue_step_head(cfg, w, st, L, B, full, stream));
+    const bool lean_ok = lean_steps(cfg, B, full);
     if (!use_graph || !graphs_allowed()) {
-        for (int i = 0; i < n_steps; ++i) {
-            LeanScope lean(lean_ok && i + 1 < n_steps);
-            RT_CALL(enqueue_decode_step(cfg, w, st, L, B, n_init, eot, mask_first, mask_always, stream));
-        }
+        for (int i = 0; i < n_steps; ++i) RT_CALL(enqueue_decode_step(cfg, w, st, L, B, (lean_ok && i + 1 < n_steps) ? lean : full, stream));
         return WIPA_OK;
     }
     WIPA_REQUIRE(s != nullptr, "wipa_decoder_run: graph capture needs a non-default stream");
-    const int variant = step_variant(cfg, B);
-    auto step_graph = [&](bool lean, hipGraphExec_t* out) -> int {  // kind 0: the full step, 2: the lean one
-        const GraphKey key = graph_key(cfg, w, state, mask_first, mask_always, B, n_init, eot, variant, lean ? 2 : 0, rules, sample, starts_dev, nullptr);
-        return cached_graph(key, s, [&]() -> int {
-            LeanScope scope(lean);
-            return enqueue_decode_step(cfg, w, st, L, B, n_init, eot, mask_first, mask_always, stream);
-        }, out);
+    const int variant = step_variant(cfg, B, full);
+    auto step_graph = [&](const StepCtx& c, hipGraphExec_t* out) -> int {  // kind 0: the full step, 2: the lean one
+        return cached_graph(graph_key(cfg, w, state, B, c, variant, c.lean ? 2 : 0, nullptr), s,
+                            [&]() -> int { return enqueue_decode_step(cfg, w, st, L, B, c, stream); }, out);
     };
-    hipGraphExec_t full = nullptr, lean = nullptr;
-    RT_CALL(step_graph(false, &full));
-    if (lean_ok && n_steps > 1) RT_CALL(step_graph(true, &lean));
-    for (int i = 0; i < n_steps; ++i) WIPA_CHECK_HIP(hipGraphLaunch((lean && i + 1 < n_steps) ? lean : full, s));
+    hipGraphExec_t full_exec = nullptr, lean_exec = nullptr;
+    RT_CALL(step_graph(full, &full_exec));
+    if (lean_ok && n_steps > 1) RT_CALL(step_graph(lean, &lean_exec));
+    for (int i = 0; i < n_steps; ++i) WIPA_CHECK_HIP(hipGraphLaunch((lean_exec && i + 1 < n_steps) ? lean_exec : full_exec, s));
     return WIPA_OK;
 }
 
@@ -1213,40 +1241,33 @@ extern "C" int wipa_decoder_prefill_sample(const wipa_model_cfg* cfg, const void
     RT_CALL(cfg_check(cfg));
     SplitScope split_scope(cfg);
     WIPA_REQUIRE(w && state && mask_first && mask_always && B > 0, "wipa_decoder_prefill: bad arguments");
-    RT_CALL(rules_servable("wipa_decoder_prefill_rules", cfg, B, eot, rules));
-    RT_CALL(sample_servable("wipa_decoder_prefill_sample", cfg, B, sample));
-    RT_CALL(group_servable("wipa_decoder_prefill", cfg, B));
-    RulesScope rules_scope(rules, sample);
-    WIPA_REQUIRE(n_init >= 1 && n_init <= MAX_PROMPT, "wipa_decoder_prefill: 1..%d prompt tokens (got %d)", MAX_PROMPT, n_init);
-    W8Scope w8_scope(cfg, w);
-    const wipa_dec_layout L = dec_layout(cfg, B);
-    RT_CALL(state_fits("wipa_decoder_prefill", L, state_bytes));
+    const StepCtx ctx{rules, sample, nullptr, n_init, eot, mask_first, mask_always, false};
+    static const EntryNames who = {"wipa_decoder_prefill", "wipa_decoder_prefill_rules", "wipa_decoder_prefill_sample", "wipa_decoder_prefill"};
     char* st = (char*)state;
-    auto enqueue = [&]() -> int {
-        if (n_init == 1) {  // a bare [sot] prompt: one ordinary step at position 0 (with its head when the step is tail-fused)
-            if (step_needs_head(cfg, B)) RT_CALL(enqueue_step_head(cfg, w, st, L, B, stream));
-            return enqueue_decode_step(cfg, w, st, L, B, n_init, eot, mask_first, mask_always, stream);
-        }
-        return enqueue_prefill(cfg, w, st, L, B, n_init, eot, mask_first, mask_always, stream);
-    };
     hipStream_t s = (hipStream_t)stream;
-    RT_CALL(init_before_capture(cfg));
-    WIPA_CHECK_HIP(hipMemsetAsync(done_counter_of(st, L), 0, sizeof(int32_t), s));  // as wipa_decoder_run: the tail's counter starts at zero
-    if (!use_graph || s == nullptr || !graphs_allowed()) return enqueue();
-    hipGraphExec_t exec = nullptr;
-    RT_CALL(cached_graph(graph_key(cfg, w, state, mask_first, mask_always, B, n_init, eot, step_variant(cfg, B), 1, rules, sample, nullptr, nullptr), s,
-                         enqueue, &exec));
-    WIPA_CHECK_HIP(hipGraphLaunch(exec, s));
-    return WIPA_OK;
+    wipa_dec_layout L;
+    RT_CALL(decode_prologue(who, cfg, B, ctx, st, state_bytes, 1, s, &L, [&]() -> int {
+        WIPA_REQUIRE(n_init >= 1 && n_init <= MAX_PROMPT, "wipa_decoder_prefill: 1..%d prompt tokens (got %d)", MAX_PROMPT, n_init);
+        return WIPA_OK;
+    }));
+    W8Scope w8_scope(cfg, w);
+    return replay_or_enqueue(use_graph, s, graph_key(cfg, w, state, B, ctx, step_variant(cfg, B, ctx), 1, nullptr), [&]() -> int {
+        if (n_init == 1) {  // a bare [sot] prompt: one ordinary step at position 0 (with its head when the step is tail-fused)
+            if (step_needs_head(cfg, B)) RT_CALL(enqueue_step_head(cfg, w, st, L, B, ctx, stream));
+            return enqueue_decode_step(cfg, w, st, L, B, ctx, stream);
+        }
+        return enqueue_prefill(cfg, w, st, L, B, ctx, stream);
+    });
 }
 
 // ------------------------------------------------------------------ ragged prompt pass
 // The whole prompt of every row (up to n_text_ctx columns, rows left-padded to the common width P) in ONE batched pass: the existing
 // prefill is sized for four rows per clip and runs one absorbed cross-attention launch per prompt position, neither of which scales
-// to P = 227.  This pass is the teacher-forced layer body (tf_layers: batched GEMMs over B * P rows, wipa_attention for both
-// attentions) with the differences a decode state needs: the q|k|v GEMM scatters into the blob's self-K/V cache at columns 0 .. P-1
-// (as enqueue_prefill does), embedding and self-attention take the rows' starts, the cross K/V come from the blob (cached form) or
-// are projected per layer from the blob's copy of the encoder output (absorbed form), and logits exist for two columns per clip only.
+// to P = 227.  This pass and the teacher-forced one (tf_layers) are ONE layer walk, batched_layers: batched GEMMs over B * P rows,
+// wipa_attention for both attentions.  Here it runs with what a decode state needs: the q|k|v GEMM scatters into the blob's self-K/V
+// cache at columns 0 .. P-1 (as enqueue_prefill does), embedding and self-attention take the rows' starts, the cross K/V come from the
+// blob (cached form) or are projected per layer from the blob's copy of the encoder output (absorbed form), and logits exist for two
+// columns per clip only.
 namespace {
 struct PromptWs {
     size_t sot_logits, x, ln, q, ao, h, ckv, total;
@@ -1266,47 +1287,70 @@ PromptWs prompt_ws(const wipa_model_cfg* c, int B, int P) {
     return w;
 }
 
-int enqueue_prefill_ragged(const wipa_model_cfg* cfg, const void* const* w, char* st, const wipa_dec_layout& L, int B, int P, int sot_col,
-                           int eot, const float* mask_first, const float* mask_always, const int32_t* starts, char* ws, const PromptWs& W,
-                           wipa_stream_t stream) {
+// what wipa_decoder_align does between a layer's cross-attention projections and its cross-attention
+struct TfHook {
+    virtual int after_cross_projections(int layer, const void* q, const void* ckv, int64_t k_bs, int64_t k_hs) const = 0;
+    virtual ~TfHook() {}
+};
+
+// The batched decoder-layer walk over B * T rows (T columns per row): embedding, then per layer LayerNorm, q|k|v GEMM, causal
+// self-attention, out GEMM with residual, LayerNorm, query GEMM, cross K / V projection, cross-attention, out GEMM, LayerNorm and the
+// two MLP GEMMs.  Leaves the residual stream in x.  Its callers, the teacher-forced pass (tf_layers) and the ragged prompt pass
+// (enqueue_prefill_ragged), differ in the five numbered places.
+struct BatchedWalk {
+    int B, T;
+    const int32_t* tokens;  // [B, ld_tok]
+    int64_t ld_tok;
+    float* x;               // workspace: x f32 [B * T, d]; ln, q, ao [B * T, d] and hb [B * T, 4 d] in the model dtype
+    char* ln;
+    void *q, *ao, *hb;
+    char* qkv;              // 1. q|k|v land in packed rows [B * T, 3 d] of the workspace, or (NULL) are scattered into the blob's
+    char* self_kv;          //    self-K/V cache [layer][3][B][nctx][d] at columns 0 .. T-1, as enqueue_prefill does
+    const int32_t* starts;  // 2. NULL, or the rows' first own columns: embedding and self-attention are the `starts`-aware ones
+    const void* features;   // 3. the cross K / V are projected per layer from features [clips, n_audio_ctx, d] into ckv_ws, or (NULL)
+    char* ckv_ws;           //    read from the blob's cached K / V, [layer][clips][2][H][n_audio_ctx][64]
+    const char* ckv_cache;
+    int n_group;            // 4. candidate groups: rows = clips x n_group; the cross-attention takes a clip's candidates together
+    const TfHook* hook;     // 5. NULL, or what runs between the cross projections and the cross-attention
+};
+int batched_layers(const wipa_model_cfg* cfg, const void* const* w, const BatchedWalk& k, wipa_stream_t stream) {
     const int dt = cfg->dtype;
     const size_t e = wipa_dtype_size(dt);
-    const int d = cfg->n_text_state, H = cfg->n_text_head, nctx = cfg->n_text_ctx, Ta = cfg->n_audio_ctx, M = B * P;
-    const int G = group_of(cfg), Bc = clips_of(cfg, B);
-    const DecScratch S = dec_scratch(cfg, B);
-    float* x = (float*)(ws + W.x);
-    char* ln = ws + W.ln;
-    void* q = ws + W.q;
-    void* ao = ws + W.ao;
-    void* hb = ws + W.h;
-    int64_t* posd = (int64_t*)(st + L.scratch + S.posd);
-    int32_t* tokens = (int32_t*)(st + L.tokens);
-    int32_t* pos = (int32_t*)(st + L.pos);
-    RT_CALL(wipa_embed_tokens_ragged(tokens, L.ld_tok, B, P, starts, w[0], dt, (const float*)w[1], x, d, stream));
+    const int d = cfg->n_text_state, H = cfg->n_text_head, nctx = cfg->n_text_ctx, Ta = cfg->n_audio_ctx;
+    const int B = k.B, T = k.T, M = B * T, G = k.n_group, Bc = B / G;
+    float* x = k.x;
+    char* ln = k.ln;
+    void *q = k.q, *ao = k.ao, *hb = k.hb;
+    if (k.starts) RT_CALL(wipa_embed_tokens_ragged(k.tokens, k.ld_tok, B, T, k.starts, w[0], dt, (const float*)w[1], x, d, stream));
+    else RT_CALL(wipa_embed_tokens(k.tokens, k.ld_tok, B, T, 0, nullptr, w[0], dt, nullptr, (const float*)w[1], x, d, stream));
     for (int l = 0; l < cfg->n_text_layer; ++l) {
         const void* const* lw = w + WIPA_DEC_GLOBAL + WIPA_DEC_PER_LAYER * l;
-        char* skv = st + L.self_kv + (size_t)l * 3 * B * nctx * d * e;  // [3][B][nctx][d]
+        // q, k and v of a row lie `part` bytes apart: side by side in a packed row, or a cache slot [B][nctx][d] apart
+        char* qkv = k.qkv ? k.qkv : k.self_kv + (size_t)l * 3 * B * nctx * d * e;
+        const size_t part = k.qkv ? (size_t)d * e : (size_t)B * nctx * d * e;
+        const int64_t qkv_rs = k.qkv ? 3 * d : d, qkv_bs = k.qkv ? (int64_t)T * 3 * d : (int64_t)nctx * d;
         RT_CALL(wipa_layernorm(x, WIPA_F32, d, ln, dt, d, (const float*)lw[0], (const float*)lw[1], M, d, 1e-5f, stream));
         {
-            // q|k|v of columns 0..P-1 -> slot[n / d][b][t][n % d] of the blob's cache
             wipa_gemm_desc g;
             memset(&g, 0, sizeof(g));
             g.col_scale_n = 2 * d; g.col_scale = QK_SCALE;
-            g.rg_in = P; g.rg_valid = P; g.rg_stride = (int64_t)nctx * d;
-            g.cg_in = d; g.cg_stride = (int64_t)B * nctx * d;
-            RT_CALL(gemm(ln, d, lw[2], d, skv, d, M, 3 * d, d, dt, dt, (const float*)lw[3], 0, nullptr, stream, &g));
+            if (!k.qkv) {  // columns 0..T-1 -> slot[n / d][b][t][n % d] of the blob's cache
+                g.rg_in = T; g.rg_valid = T; g.rg_stride = (int64_t)nctx * d;
+                g.cg_in = d; g.cg_stride = (int64_t)B * nctx * d;
+            }
+            RT_CALL(gemm(ln, d, lw[2], d, qkv, qkv_rs, M, 3 * d, d, dt, dt, (const float*)lw[3], 0, nullptr, stream, &g));
         }
         {
             wipa_attn_desc a;
             memset(&a, 0, sizeof(a));
-            const size_t slot = (size_t)B * nctx * d * e;
-            a.q = skv; a.k = skv + slot; a.v = skv + 2 * slot; a.out = ao;
-            a.q_bs = (int64_t)nctx * d; a.q_rs = d; a.q_hs = 64;
-            a.k_bs = a.q_bs; a.k_rs = d; a.k_hs = 64;
-            a.v_bs = a.q_bs; a.v_rs = d; a.v_hs = 64;
-            a.o_bs = (int64_t)P * d; a.o_rs = d; a.o_hs = 64;
-            a.B = B; a.H = H; a.Tq = P; a.Tk = P; a.causal = 1; a.dtype = dt;
-            RT_CALL(wipa_attention_ragged(&a, starts, stream));  // row b: column i sees columns starts[b] .. i
+            a.q = qkv; a.k = qkv + part; a.v = qkv + 2 * part; a.out = ao;
+            a.q_bs = qkv_bs; a.q_rs = qkv_rs; a.q_hs = 64;
+            a.k_bs = a.q_bs; a.k_rs = qkv_rs; a.k_hs = 64;
+            a.v_bs = a.q_bs; a.v_rs = qkv_rs; a.v_hs = 64;
+            a.o_bs = (int64_t)T * d; a.o_rs = d; a.o_hs = 64;
+            a.B = B; a.H = H; a.Tq = T; a.Tk = T; a.causal = 1; a.dtype = dt;
+            if (k.starts) RT_CALL(wipa_attention_ragged(&a, k.starts, stream));  // row b: column i sees columns starts[b] .. i
+            else RT_CALL(wipa_attention(&a, stream));
         }
         RT_CALL(gemm(ao, d, lw[4], d, x, d, M, d, d, dt, WIPA_F32, (const float*)lw[5], 0, x, stream));
         RT_CALL(wipa_layernorm(x, WIPA_F32, d, ln, dt, d, (const float*)lw[6], (const float*)lw[7], M, d, 1e-5f, stream));
@@ -1316,32 +1360,34 @@ int enqueue_prefill_ragged(const wipa_model_cfg* cfg, const void* const* w, char
             g.col_scale_n = d; g.col_scale = QK_SCALE;
             RT_CALL(gemm(ln, d, lw[8], d, q, d, M, d, d, dt, dt, (const float*)lw[9], 0, nullptr, stream, &g));
         }
-        const char* ckv = st + L.cross_kv + (size_t)l * Bc * 2 * H * Ta * 64 * e;  // the cached form's K / V of this layer (per clip)
-        if (cfg->dec_cross_absorbed) {
-            // absorbed form: the blob holds the encoder output itself; this layer's K / V are projected from it into the workspace
+        const int64_t ckv_bs = (int64_t)2 * H * Ta * 64, ckv_hs = (int64_t)Ta * 64;
+        const char* ckv = k.ckv_ws;
+        if (k.features) {
             wipa_gemm_desc g;
             memset(&g, 0, sizeof(g));
-            g.col_scale_n = d; g.col_scale = QK_SCALE;
-            g.rg_in = Ta; g.rg_valid = Ta; g.rg_stride = (int64_t)2 * H * Ta * 64;
-            g.cg_in = 64; g.cg_stride = (int64_t)Ta * 64;
-            RT_CALL(gemm(st + L.cross_kv, d, lw[10], d, ws + W.ckv, 64, Bc * Ta, 2 * d, d, dt, dt, (const float*)lw[11], 0, nullptr, stream, &g));
-            ckv = ws + W.ckv;
+            g.col_scale_n = d; g.col_scale = QK_SCALE;  // the key half; values stay unscaled
+            g.rg_in = Ta; g.rg_valid = Ta; g.rg_stride = ckv_bs;
+            g.cg_in = 64; g.cg_stride = ckv_hs;
+            RT_CALL(gemm(k.features, d, lw[10], d, k.ckv_ws, 64, Bc * Ta, 2 * d, d, dt, dt, (const float*)lw[11], 0, nullptr, stream, &g));
+        } else {
+            ckv = k.ckv_cache + (size_t)l * Bc * ckv_bs * e;
         }
+        if (k.hook) RT_CALL(k.hook->after_cross_projections(l, q, ckv, ckv_bs, ckv_hs));
         {
             wipa_attn_desc a;
             memset(&a, 0, sizeof(a));
             a.q = q; a.k = ckv; a.v = ckv + (size_t)H * Ta * 64 * e; a.out = ao;
-            a.q_bs = (int64_t)P * d; a.q_rs = d; a.q_hs = 64;
-            a.k_bs = (int64_t)2 * H * Ta * 64; a.k_rs = 64; a.k_hs = (int64_t)Ta * 64;
+            a.q_bs = (int64_t)T * d; a.q_rs = d; a.q_hs = 64;
+            a.k_bs = ckv_bs; a.k_rs = 64; a.k_hs = ckv_hs;
             a.v_bs = a.k_bs; a.v_rs = 64; a.v_hs = a.k_hs;
-            a.o_bs = (int64_t)P * d; a.o_rs = d; a.o_hs = 64;
-            a.B = B; a.H = H; a.Tq = P; a.Tk = Ta; a.causal = 0; a.dtype = dt;
+            a.o_bs = (int64_t)T * d; a.o_rs = d; a.o_hs = 64;
+            a.B = B; a.H = H; a.Tq = T; a.Tk = Ta; a.causal = 0; a.dtype = dt;
             if (G > 1) {
-                // candidate groups: the G x P query rows of a clip's candidates are contiguous -- one batch entry per CLIP holds them
-                // all against the clip's K / V, on the kernel P rows take (every query row's arithmetic is its own)
-                a.B = Bc; a.Tq = G * P;
-                a.q_bs = (int64_t)G * P * d; a.o_bs = a.q_bs;
-                RT_CALL(wipa_attention_as(&a, P, stream));
+                // candidate groups: the G x T query rows of a clip's candidates are contiguous -- one batch entry per CLIP holds them
+                // all against the clip's K / V, on the kernel T rows take (every query row's arithmetic is its own)
+                a.B = Bc; a.Tq = G * T;
+                a.q_bs = (int64_t)G * T * d; a.o_bs = a.q_bs;
+                RT_CALL(wipa_attention_as(&a, T, stream));
             } else {
                 RT_CALL(wipa_attention(&a, stream));
             }
@@ -1351,28 +1397,34 @@ int enqueue_prefill_ragged(const wipa_model_cfg* cfg, const void* const* w, char
         RT_CALL(gemm(ln, d, lw[16], d, hb, 4 * d, M, 4 * d, d, dt, dt, (const float*)lw[17], 1, nullptr, stream));
         RT_CALL(gemm(hb, 4 * d, lw[18], 4 * d, x, d, M, d, 4 * d, dt, WIPA_F32, (const float*)lw[19], 0, x, stream));
     }
-    RT_CALL(wipa_layernorm(x, WIPA_F32, d, ln, dt, d, (const float*)w[2], (const float*)w[3], M, d, 1e-5f, stream));
+    return WIPA_OK;
+}
+
+int enqueue_prefill_ragged(const wipa_model_cfg* cfg, const void* const* w, char* st, const wipa_dec_layout& L, int B, int sot_col,
+                           const StepCtx& ctx, char* ws, const PromptWs& W, wipa_stream_t stream) {
+    const int dt = cfg->dtype;
+    const size_t e = wipa_dtype_size(dt);
+    const int d = cfg->n_text_state, P = ctx.n_init, M = B * P;
+    BatchedWalk k = {};
+    k.B = B; k.T = P;
+    k.tokens = (const int32_t*)(st + L.tokens); k.ld_tok = L.ld_tok;
+    k.x = (float*)(ws + W.x); k.ln = ws + W.ln; k.q = ws + W.q; k.ao = ws + W.ao; k.hb = ws + W.h;
+    k.self_kv = st + L.self_kv;
+    k.starts = ctx.starts;
+    // absorbed form: the blob holds the encoder output itself (per clip); every layer's K / V are projected from it into the workspace
+    if (cfg->dec_cross_absorbed) { k.features = st + L.cross_kv; k.ckv_ws = ws + W.ckv; }
+    else k.ckv_cache = st + L.cross_kv;
+    k.n_group = group_of(cfg);
+    RT_CALL(batched_layers(cfg, w, k, stream));
+    RT_CALL(wipa_layernorm(k.x, WIPA_F32, d, k.ln, dt, d, (const float*)w[2], (const float*)w[3], M, d, 1e-5f, stream));
     // logits of two columns per clip: the last prompt column (rows (b, P-1) of ln, row stride P * d) into the state, and the
     // <|startoftranscript|> column into the workspace (upstream's logits[:, sot_index], for no_speech_prob)
-    float* logits = (float*)(st + L.logits);
-    RT_CALL(gemm(ln + (size_t)(P - 1) * d * e, (int64_t)P * d, w[0], d, logits, L.ld_logits, B, cfg->n_vocab, d, dt, WIPA_F32, nullptr, 0,
+    RT_CALL(gemm(k.ln + (size_t)(P - 1) * d * e, (int64_t)P * d, w[0], d, st + L.logits, L.ld_logits, B, cfg->n_vocab, d, dt, WIPA_F32, nullptr, 0,
                  nullptr, stream));
     if (sot_col >= 0)
-        RT_CALL(gemm(ln + (size_t)sot_col * d * e, (int64_t)P * d, w[0], d, ws + W.sot_logits, L.ld_logits, B, cfg->n_vocab, d, dt, WIPA_F32,
+        RT_CALL(gemm(k.ln + (size_t)sot_col * d * e, (int64_t)P * d, w[0], d, ws + W.sot_logits, L.ld_logits, B, cfg->n_vocab, d, dt, WIPA_F32,
                      nullptr, 0, nullptr, stream));
-    hipLaunchKernelGGL(set_pos_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pos, posd, P - 1, d);
-    if (t_sample)
-        RT_CALL(wipa_sample_step_ragged(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, P, eot, t_rules, t_sample,
-                                        starts, (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), stream));
-    else if (t_rules)
-        RT_CALL(wipa_timestamp_step(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, P, eot, t_rules,
-                                    (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), stream));
-    else
-        RT_CALL(wipa_greedy_step(logits, L.ld_logits, B, cfg->n_vocab, mask_first, mask_always, tokens, L.ld_tok, pos, P, eot,
-                                 (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), stream));
-    hipLaunchKernelGGL(advance_pos_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pos, posd, d);
-    WIPA_LAUNCH_CHECK();
-    return WIPA_OK;
+    return enqueue_first_token(cfg, st, L, B, ctx, stream);
 }
 }  // namespace
 
@@ -1391,32 +1443,25 @@ extern "C" int wipa_decoder_prefill_ragged(const wipa_model_cfg* cfg, const void
     WIPA_REQUIRE(starts_dev && workspace, "wipa_decoder_prefill_ragged: starts_dev and workspace are required");
     WIPA_REQUIRE(cfg->dec_w_dtype == 0, "wipa_decoder_prefill_ragged: the prompt pass runs on a bf16 / f32 weight table (cfg.dec_w_dtype: fp8 tables "
                                         "serve the decode step)");
-    RT_CALL(rules_servable("wipa_decoder_prefill_ragged", cfg, B, eot, rules));
-    RT_CALL(sample_servable("wipa_decoder_prefill_ragged", cfg, B, sample));
-    RT_CALL(starts_servable("wipa_decoder_prefill_ragged", cfg, B, P, starts_dev));
-    RT_CALL(group_servable("wipa_decoder_prefill_ragged", cfg, B));
-    WIPA_REQUIRE(P + 1 <= cfg->n_text_ctx, "wipa_decoder_prefill_ragged: P=%d leaves no column to generate in n_text_ctx=%d", P, cfg->n_text_ctx);
-    WIPA_REQUIRE(sot_col >= -1 && sot_col < P, "wipa_decoder_prefill_ragged: sot_col=%d outside -1..P-1 (P=%d)", sot_col, P);
-    const PromptWs W = prompt_ws(cfg, B, P);
-    WIPA_REQUIRE(workspace_bytes >= W.total, "wipa_decoder_prefill_ragged: workspace too small (%zu < %zu: wipa_decoder_prompt_workspace_bytes)",
-                 workspace_bytes, W.total);
-    RulesScope rules_scope(rules, sample, starts_dev);
-    const wipa_dec_layout L = dec_layout(cfg, B);
-    RT_CALL(state_fits("wipa_decoder_prefill_ragged", L, state_bytes));
+    const StepCtx ctx{rules, sample, starts_dev, P, eot, mask_first, mask_always, false};
+    static const EntryNames who = {"wipa_decoder_prefill_ragged", "wipa_decoder_prefill_ragged", "wipa_decoder_prefill_ragged",
+                                   "wipa_decoder_prefill_ragged"};
     char* st = (char*)state;
     hipStream_t s = (hipStream_t)stream;
-    RT_CALL(init_before_capture(cfg));
-    WIPA_CHECK_HIP(hipMemsetAsync(done_counter_of(st, L), 0, sizeof(int32_t), s));
-    auto enqueue = [&]() -> int {
-        return enqueue_prefill_ragged(cfg, w, st, L, B, P, sot_col, eot, mask_first, mask_always, starts_dev, (char*)workspace, W, stream);
-    };
-    if (!use_graph || s == nullptr || !graphs_allowed()) return enqueue();
-    hipGraphExec_t exec = nullptr;
+    wipa_dec_layout L;
+    const PromptWs W = prompt_ws(cfg, B, P);  // offsets only: nothing is touched before the checks
+    RT_CALL(decode_prologue(who, cfg, B, ctx, st, state_bytes, 1, s, &L, [&]() -> int {
+        WIPA_REQUIRE(P + 1 <= cfg->n_text_ctx, "wipa_decoder_prefill_ragged: P=%d leaves no column to generate in n_text_ctx=%d", P, cfg->n_text_ctx);
+        WIPA_REQUIRE(sot_col >= -1 && sot_col < P, "wipa_decoder_prefill_ragged: sot_col=%d outside -1..P-1 (P=%d)", sot_col, P);
+        WIPA_REQUIRE(workspace_bytes >= W.total, "wipa_decoder_prefill_ragged: workspace too small (%zu < %zu: wipa_decoder_prompt_workspace_bytes)",
+                     workspace_bytes, W.total);
+        return WIPA_OK;
+    }));
     // the prompt pass has its own, shorter variant word
-    RT_CALL(cached_graph(graph_key(cfg, w, state, mask_first, mask_always, B, P, eot, cfg->dtype * 2 + t_f32_split + 64 * cfg->dec_cross_absorbed + 256 * (group_of(cfg) > 1 ? group_of(cfg) : 0),
-                                   3 + 16 * (sot_col + 1), rules, sample, starts_dev, workspace), s, enqueue, &exec));
-    WIPA_CHECK_HIP(hipGraphLaunch(exec, s));
-    return WIPA_OK;
+    const int variant = cfg->dtype * 2 + t_f32_split + 64 * cfg->dec_cross_absorbed + 256 * (group_of(cfg) > 1 ? group_of(cfg) : 0);
+    return replay_or_enqueue(use_graph, s, graph_key(cfg, w, state, B, ctx, variant, 3 + 16 * (sot_col + 1), workspace), [&]() -> int {
+        return enqueue_prefill_ragged(cfg, w, st, L, B, sot_col, ctx, (char*)workspace, W, stream);
+    });
 }
 
 extern "C" int wipa_decoder_release(void* state) {
@@ -1454,79 +1499,18 @@ TfWs tf_ws(const wipa_model_cfg* c, int B, int T) {
 }  // namespace
 
 namespace {
-// what wipa_decoder_align does between a layer's cross-attention projections and its cross-attention
-struct TfHook {
-    virtual int after_cross_projections(int layer, const void* q, const void* ckv, int64_t k_bs, int64_t k_hs) const = 0;
-    virtual ~TfHook() {}
-};
 // embedding + every decoder layer of the teacher-forced pass; leaves the residual stream in ws.x (f32 [B*T, d])
 int tf_layers(const wipa_model_cfg* cfg, const void* const* w, const int32_t* tokens, const void* features, char* ws, const TfWs& L, int B,
               int T, const TfHook* hook, wipa_stream_t stream) {
-    const int dt = cfg->dtype;
-    const size_t e = wipa_dtype_size(dt);
-    const int d = cfg->n_text_state, H = cfg->n_text_head, Ta = cfg->n_audio_ctx, M = B * T;
-    float* x = (float*)(ws + L.x);
-    void* ln = ws + L.ln;
-    char* qkv = ws + L.qkv;
-    void* q = ws + L.q;
-    void* ao = ws + L.ao;
-    void* hb = ws + L.h;
-    char* ckv = ws + L.ckv;
-    RT_CALL(wipa_embed_tokens(tokens, T, B, T, 0, nullptr, w[0], dt, nullptr, (const float*)w[1], x, d, stream));
-    for (int l = 0; l < cfg->n_text_layer; ++l) {
-        const void* const* lw = w + WIPA_DEC_GLOBAL + WIPA_DEC_PER_LAYER * l;
-        RT_CALL(wipa_layernorm(x, WIPA_F32, d, ln, dt, d, (const float*)lw[0], (const float*)lw[1], M, d, 1e-5f, stream));
-        {
-            wipa_gemm_desc g;
-            memset(&g, 0, sizeof(g));
-            g.col_scale_n = 2 * d; g.col_scale = QK_SCALE;
-            RT_CALL(gemm(ln, d, lw[2], d, qkv, 3 * d, M, 3 * d, d, dt, dt, (const float*)lw[3], 0, nullptr, stream, &g));
-        }
-        {
-            wipa_attn_desc a;
-            memset(&a, 0, sizeof(a));
-            a.q = qkv; a.k = qkv + (size_t)d * e; a.v = qkv + 2 * (size_t)d * e; a.out = ao;
-            a.q_bs = (int64_t)T * 3 * d; a.q_rs = 3 * d; a.q_hs = 64;
-            a.k_bs = a.q_bs; a.k_rs = 3 * d; a.k_hs = 64;
-            a.v_bs = a.q_bs; a.v_rs = 3 * d; a.v_hs = 64;
-            a.o_bs = (int64_t)T * d; a.o_rs = d; a.o_hs = 64;
-            a.B = B; a.H = H; a.Tq = T; a.Tk = T; a.causal = 1; a.dtype = dt;
-            RT_CALL(wipa_attention(&a, stream));
-        }
-        RT_CALL(gemm(ao, d, lw[4], d, x, d, M, d, d, dt, WIPA_F32, (const float*)lw[5], 0, x, stream));
-        RT_CALL(wipa_layernorm(x, WIPA_F32, d, ln, dt, d, (const float*)lw[6], (const float*)lw[7], M, d, 1e-5f, stream));
-        {
-            wipa_gemm_desc g;
-            memset(&g, 0, sizeof(g));
-            g.col_scale_n = d; g.col_scale = QK_SCALE;
-            RT_CALL(gemm(ln, d, lw[8], d, q, d, M, d, d, dt, dt, (const float*)lw[9], 0, nullptr, stream, &g));
-        }
-        {
-            wipa_gemm_desc g;
-            memset(&g, 0, sizeof(g));
-            g.col_scale_n = d; g.col_scale = QK_SCALE;
-            g.rg_in = Ta; g.rg_valid = Ta; g.rg_stride = (int64_t)2 * H * Ta * 64;
-            g.cg_in = 64; g.cg_stride = (int64_t)Ta * 64;
-            RT_CALL(gemm(features, d, lw[10], d, ckv, 64, B * Ta, 2 * d, d, dt, dt, (const float*)lw[11], 0, nullptr, stream, &g));
-        }
-        if (hook) RT_CALL(hook->after_cross_projections(l, q, ckv, (int64_t)2 * H * Ta * 64, (int64_t)Ta * 64));
-        {
-            wipa_attn_desc a;
-            memset(&a, 0, sizeof(a));
-            a.q = q; a.k = ckv; a.v = ckv + (size_t)H * Ta * 64 * e; a.out = ao;
-            a.q_bs = (int64_t)T * d; a.q_rs = d; a.q_hs = 64;
-            a.k_bs = (int64_t)2 * H * Ta * 64; a.k_rs = 64; a.k_hs = (int64_t)Ta * 64;
-            a.v_bs = a.k_bs; a.v_rs = 64; a.v_hs = a.k_hs;
-            a.o_bs = (int64_t)T * d; a.o_rs = d; a.o_hs = 64;
-            a.B = B; a.H = H; a.Tq = T; a.Tk = Ta; a.causal = 0; a.dtype = dt;
-            RT_CALL(wipa_attention(&a, stream));
-        }
-        RT_CALL(gemm(ao, d, lw[12], d, x, d, M, d, d, dt, WIPA_F32, (const float*)lw[13], 0, x, stream));
-        RT_CALL(wipa_layernorm(x, WIPA_F32, d, ln, dt, d, (const float*)lw[14], (const float*)lw[15], M, d, 1e-5f, stream));
-        RT_CALL(gemm(ln, d, lw[16], d, hb, 4 * d, M, 4 * d, d, dt, dt, (const float*)lw[17], 1, nullptr, stream));
-        RT_CALL(gemm(hb, 4 * d, lw[18], 4 * d, x, d, M, d, 4 * d, dt, WIPA_F32, (const float*)lw[19], 0, x, stream));
-    }
-    return WIPA_OK;
+    BatchedWalk k = {};
+    k.B = B; k.T = T;
+    k.tokens = tokens; k.ld_tok = T;
+    k.x = (float*)(ws + L.x); k.ln = ws + L.ln; k.q = ws + L.q; k.ao = ws + L.ao; k.hb = ws + L.h;
+    k.qkv = ws + L.qkv;
+    k.features = features; k.ckv_ws = ws + L.ckv;  // one clip per row
+    k.n_group = 1;
+    k.hook = hook;
+    return batched_layers(cfg, w, k, stream);
 }
 }  // namespace
 

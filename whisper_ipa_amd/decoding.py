@@ -331,6 +331,28 @@ def _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules,
         _lib.check(L.wipa_decoder_prefill_rules(*args, C.byref(rules), sptr(s)), "wipa_decoder_prefill_rules")
 
 
+def _begin_with(initial_tokens: Sequence[int]):
+    """how a decode without per-row prompts begins: wipa_decoder_begin with one prompt of 1..4 tokens for every row (no ``starts``)"""
+    n_init = len(initial_tokens)
+    init = (C.c_int32 * n_init)(*[int(t) for t in initial_tokens])
+
+    def begin(L, pk, st, B, s):
+        _lib.check(L.wipa_decoder_begin(C.byref(pk["cfg"]), ptr(st.blob), st.blob.numel(), B, init, n_init, sptr(s)), "wipa_decoder_begin")
+        return None
+
+    return begin
+
+
+def _open(model, L, pk, st, audio_features: torch.Tensor, B: int, s, begin):
+    """the opening of every decode, on the library stream ``s``: the features in the model's dtype into the state
+    (wipa_decoder_set_audio), then ``begin``.  Returns (the features, which must outlive the enqueued work, and what ``begin`` returns:
+    the state's device array of first columns, or None)"""
+    feats = audio_features.to(device=model.device, dtype=model.dtype).contiguous()
+    _lib.check(L.wipa_decoder_set_audio(C.byref(pk["cfg"]), pk["dec_tab"], ptr(feats), ptr(st.blob), st.blob.numel(), B, sptr(s)),
+               "wipa_decoder_set_audio")
+    return feats, begin(L, pk, st, B, s)
+
+
 def greedy_launch(model, audio_features: torch.Tensor, initial_tokens: Sequence[int], suppress_always: Sequence[int],
                   suppress_first: Sequence[int], eot: int, max_new_tokens: int, use_graph: bool = True, rules=None) -> GreedyHandle:
     """Enqueue cross-KV projection + a FIXED number of decoder steps on the current library
@@ -343,14 +365,11 @@ def greedy_launch(model, audio_features: torch.Tensor, initial_tokens: Sequence[
     pk = _packed_for(model, B, max_new_tokens)
     m_always = _mask(model, suppress_always)
     m_first = _mask(model, list(suppress_always) + list(suppress_first))
-    init = (C.c_int32 * n_init)(*[int(t) for t in initial_tokens])
+    begin = _begin_with(initial_tokens)
     total = (n_init - 1) + max_new_tokens
     with on_stream() as s:
         st = _state_for(model, B, pk)
-        feats = audio_features.to(device=model.device, dtype=model.dtype).contiguous()
-        _lib.check(L.wipa_decoder_set_audio(C.byref(pk["cfg"]), pk["dec_tab"], ptr(feats), ptr(st.blob), st.blob.numel(), B, sptr(s)),
-                   "wipa_decoder_set_audio")
-        _lib.check(L.wipa_decoder_begin(C.byref(pk["cfg"]), ptr(st.blob), st.blob.numel(), B, init, n_init, sptr(s)), "wipa_decoder_begin")
+        feats, _ = _open(model, L, pk, st, audio_features, B, s, begin)
         rest = total
         if _use_prefill(n_init, total):  # the prompt positions and the first new token in one batched pass
             _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s)
@@ -368,6 +387,72 @@ def greedy_collect(h: GreedyHandle) -> GreedyTokens:
     return GreedyTokens(toks, h.steps - (h.n_init - 1), slp, h.state.logits)
 
 
+def _for_candidates(sample: Optional[Sampling], clips: int, n_group: int) -> Optional[Sampling]:
+    """``sample`` for clips x n_group candidate rows: its per-CLIP streams become per-row ones (``candidate_streams``)"""
+    if n_group <= 1:
+        return sample
+    if sample is None:
+        raise ValueError("n_group > 1 needs a sampling decode (sample=...): greedy candidates would all be the same row")
+    return replace(sample, streams=candidate_streams(sample.streams if sample.streams is not None else [(c, 0) for c in range(clips)], n_group))
+
+
+def _decode_loop(model, audio_features: torch.Tensor, P: int, max_new_tokens: int, begin, run_prompt, suppress_always, suppress_first,
+                 eot: int, stop_on_eot: bool, use_graph: bool, check_every: int, rules, sample: Optional[Sampling], n_group: int, rank: bool,
+                 length_penalty: Optional[float], sot_back: Optional[int] = None) -> GreedyTokens:
+    """The decode loop of ``greedy_decode_tokens`` and ``ragged_decode_tokens``, for a prompt of ``P`` columns and ``max_new_tokens``
+    already clamped to n_text_ctx - P.  The caller supplies how to begin -- ``begin(L, pk, st, B, s)`` returns the state's device array
+    of first columns, or None -- and how the batched prompt pass is run: ``run_prompt(L, pk, st, B, m_first, m_always, rec, starts, s)``
+    returns the logits of the <|startoftranscript|> column, or None.  ``sample`` is per ROW here (``_for_candidates``)."""
+    L = _lib.lib()
+    B = audio_features.shape[0] * n_group
+    pk = _grouped(_packed_for(model, B, max_new_tokens), n_group)
+    st = _state_for(model, B, pk)
+    m_always = _mask(model, suppress_always)
+    m_first = _mask(model, list(suppress_always) + list(suppress_first))
+    total = (P - 1) + max_new_tokens
+    done_steps = 0
+    sot_logits = None
+    with on_stream() as s:
+        feats, starts = _open(model, L, pk, st, audio_features, B, s, begin)
+        rec = st.sample_record(sample) if sample is not None else None
+        if _use_prefill(P, total):  # the whole prompt and the first new token in one batched pass
+            sot_logits = run_prompt(L, pk, st, B, m_first, m_always, rec, starts, s)
+            done_steps = P
+        elif sot_back is not None:  # the steps up to the <|startoftranscript|> column: its logits are those of the call's last step
+            n = P - sot_back + 1
+            _dec_run(L, pk, st, B, P, eot, m_first, m_always, n, use_graph, rules, s, rec, starts)
+            sot_logits = st.logits.clone()
+            done_steps = n
+        while done_steps < total:
+            n = min(check_every if stop_on_eot else total, total - done_steps)
+            if done_steps < P - 1:  # the rest of the prompt walk rides with the first generated columns
+                n = min(total - done_steps, n + (P - 1 - done_steps))
+            _dec_run(L, pk, st, B, P, eot, m_first, m_always, n, use_graph, rules, s, rec, starts)
+            done_steps += n
+            if stop_on_eot and done_steps >= P:
+                last = st.tokens[:, done_steps].cpu()  # synchronises the library stream
+                if bool((last == eot).all()):
+                    break
+        winner = lengths = None
+        if rank and n_group > 1:  # the winners only come back: clips x columns
+            toks, slp, winner, lengths = _rank_groups(st, n_group, P, done_steps - (P - 1), eot, length_penalty, s)
+        else:
+            toks = st.tokens[:, : done_steps + 1].cpu().numpy().astype(np.int64)  # synchronises: the host arrays of begin are consumed
+            slp = st.sum_logprobs.cpu().numpy().copy()
+        last_logits = st.logits
+        if sot_logits is not None and n_group > 1:
+            sot_logits = sot_logits[::n_group]  # the candidates of a clip share their prompt: one row per clip
+    n_steps = done_steps - (P - 1)
+    if stop_on_eot:
+        # the reference stops at the first step after which every row ends in EOT
+        body = toks[:, P:]
+        all_eot = (body == eot).all(axis=0)
+        if all_eot.any():
+            n_steps = int(np.argmax(all_eot)) + 1
+            toks = toks[:, : P + n_steps]
+    return GreedyTokens(toks, n_steps, slp, last_logits, sot_logits=sot_logits, winner=winner, lengths=lengths)
+
+
 def greedy_decode_tokens(model, audio_features: torch.Tensor, initial_tokens: Sequence[int], suppress_always: Sequence[int],
                          suppress_first: Sequence[int], eot: int, max_new_tokens: Optional[int] = None,
                          stop_on_eot: bool = True, use_graph: bool = True, check_every: int = 8, rules=None,
@@ -380,60 +465,17 @@ def greedy_decode_tokens(model, audio_features: torch.Tensor, initial_tokens: Se
     clip's features in the decode state; ``sample.streams`` are per CLIP and candidate k draws from ``candidate_streams``' stream k.
     The result holds all clips x n_group rows -- or, with ``rank``, the winners of wipa_rank_groups only (one row per clip, plus
     ``winner`` and ``lengths``), read back as clips x columns."""
-    L = _lib.lib()
-    clips = audio_features.shape[0]
-    B = clips * n_group
-    if n_group > 1:
-        if sample is None:
-            raise ValueError("n_group > 1 needs a sampling decode (sample=...): greedy candidates would all be the same row")
-        sample = replace(sample, streams=candidate_streams(sample.streams if sample.streams is not None else [(c, 0) for c in range(clips)],
-                                                           n_group))
+    sample = _for_candidates(sample, audio_features.shape[0], n_group)
     n_init = len(initial_tokens)
     if max_new_tokens is None:
         max_new_tokens = model.dims.n_text_ctx // 2
     max_new_tokens = min(max_new_tokens, model.dims.n_text_ctx - n_init)
-    pk = _grouped(_packed_for(model, B, max_new_tokens), n_group)
-    st = _state_for(model, B, pk)
-    m_always = _mask(model, suppress_always)
-    m_first = _mask(model, list(suppress_always) + list(suppress_first))
-    init = (C.c_int32 * n_init)(*[int(t) for t in initial_tokens])
-    total = (n_init - 1) + max_new_tokens
-    done_steps = 0
-    with on_stream() as s:
-        feats = audio_features.to(device=model.device, dtype=model.dtype).contiguous()
-        _lib.check(L.wipa_decoder_set_audio(C.byref(pk["cfg"]), pk["dec_tab"], ptr(feats), ptr(st.blob), st.blob.numel(), B, sptr(s)),
-                   "wipa_decoder_set_audio")
-        _lib.check(L.wipa_decoder_begin(C.byref(pk["cfg"]), ptr(st.blob), st.blob.numel(), B, init, n_init, sptr(s)), "wipa_decoder_begin")
-        rec = st.sample_record(sample) if sample is not None else None
-        if _use_prefill(n_init, total):
-            _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s, rec)
-            done_steps = n_init
-        while done_steps < total:
-            n = min(check_every if stop_on_eot else total, total - done_steps)
-            if done_steps == 0:
-                n = min(total, n + n_init - 1)
-            _dec_run(L, pk, st, B, n_init, eot, m_first, m_always, n, use_graph, rules, s, rec)
-            done_steps += n
-            if stop_on_eot and done_steps >= n_init:
-                last = st.tokens[:, done_steps].cpu()  # synchronises the library stream
-                if bool((last == eot).all()):
-                    break
-        winner = lengths = None
-        if rank and n_group > 1:  # the winners only come back: clips x columns
-            toks, slp, winner, lengths = _rank_groups(st, n_group, n_init, done_steps - (n_init - 1), eot, length_penalty, s)
-        else:
-            toks = st.tokens[:, : done_steps + 1].cpu().numpy().astype(np.int64)
-            slp = st.sum_logprobs.cpu().numpy().copy()
-        last_logits = st.logits
-    n_steps = done_steps - (n_init - 1)
-    if stop_on_eot:
-        # the reference stops at the first step after which every row ends in EOT
-        body = toks[:, n_init:]
-        all_eot = (body == eot).all(axis=0)
-        if all_eot.any():
-            n_steps = int(np.argmax(all_eot)) + 1
-            toks = toks[:, : n_init + n_steps]
-    return GreedyTokens(toks, n_steps, slp, last_logits, winner=winner, lengths=lengths)
+
+    def run_prompt(L, pk, st, B, m_first, m_always, rec, starts, s):
+        _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s, rec)
+
+    return _decode_loop(model, audio_features, n_init, max_new_tokens, _begin_with(initial_tokens), run_prompt, suppress_always, suppress_first,
+                        eot, stop_on_eot, use_graph, check_every, rules, sample, n_group, rank, length_penalty)
 
 
 # ---------------------------------------------------------------- prompt conditioning: per-row prompts
@@ -519,20 +561,14 @@ def ragged_decode_tokens(model, audio_features: torch.Tensor, rows: Sequence[Seq
     ``logits[:, sot_index]`` for no_speech_prob).  ``max_new_tokens`` is clamped to n_text_ctx - P.
     ``n_group`` / ``rank`` / ``length_penalty``: candidate groups as in ``greedy_decode_tokens``: ``rows`` and ``sample.streams`` are per
     clip, every candidate of a clip starts from the clip's own initial tokens, ``sot_logits`` and ``starts`` stay per clip."""
-    L = _lib.lib()
     clips = audio_features.shape[0]
-    B = clips * n_group
     n_ctx = model.dims.n_text_ctx
     if getattr(model, "_fp8", None):
         raise NotImplementedError("prompt conditioning is not implemented for an fp8-quantised model: the ragged decode step runs on "
                                   "bf16 / f32 decoder tables")
     if len(rows) != clips:
         raise ValueError(f"ragged_decode_tokens: {len(rows)} rows of initial tokens for {clips} clips")
-    if n_group > 1:
-        if sample is None:
-            raise ValueError("n_group > 1 needs a sampling decode (sample=...): greedy candidates would all be the same row")
-        sample = replace(sample, streams=candidate_streams(sample.streams if sample.streams is not None else [(c, 0) for c in range(clips)],
-                                                           n_group))
+    sample = _for_candidates(sample, clips, n_group)
     if max_new_tokens is None:
         max_new_tokens = n_ctx // 2
     tokens_h, starts_h, P = pack_prompts(rows, n_ctx, max_new_tokens, pad_to)
@@ -541,72 +577,35 @@ def ragged_decode_tokens(model, audio_features: torch.Tensor, rows: Sequence[Seq
         raise ValueError(f"ragged_decode_tokens: a prompt width of {P} leaves no room to generate in n_text_ctx = {n_ctx}")
     if sot_back is not None and not 1 <= sot_back <= P - int(starts_h.max()):
         raise ValueError(f"ragged_decode_tokens: sot_back = {sot_back} outside the shortest row")
-    pk = _grouped(_packed_for(model, B, max_new_tokens), n_group)
-    st = _state_for(model, B, pk)
-    m_always = _mask(model, suppress_always)
-    m_first = _mask(model, list(suppress_always) + list(suppress_first))
     clip_starts_h = starts_h
     if n_group > 1:  # every candidate starts from its clip's initial tokens; the features are not replicated
         tokens_h, starts_h = np.repeat(tokens_h, n_group, axis=0), np.repeat(starts_h, n_group)
     tokens_h = np.ascontiguousarray(tokens_h, dtype=np.int32)
     starts_h = np.ascontiguousarray(starts_h, dtype=np.int32)
     i32p = C.POINTER(C.c_int32)
-    total = (P - 1) + max_new_tokens
-    done_steps = 0
-    sot_logits = None
-    with on_stream() as s:
-        feats = audio_features.to(device=model.device, dtype=model.dtype).contiguous()
-        _lib.check(L.wipa_decoder_set_audio(C.byref(pk["cfg"]), pk["dec_tab"], ptr(feats), ptr(st.blob), st.blob.numel(), B, sptr(s)),
-                   "wipa_decoder_set_audio")
+
+    def begin(L, pk, st, B, s):
         starts = st.starts
         _lib.check(L.wipa_decoder_begin_ragged(C.byref(pk["cfg"]), ptr(st.blob), st.blob.numel(), B, tokens_h.ctypes.data_as(i32p),
                                                starts_h.ctypes.data_as(i32p), P, ptr(starts), sptr(s)), "wipa_decoder_begin_ragged")
-        rec = st.sample_record(sample) if sample is not None else None
-        if P >= 2 and os.environ.get("WIPA_NO_PREFILL") != "1":  # the whole prompt and the first new token in one batched pass
-            ws = st.prompt_workspace(pk, P)
-            _lib.check(L.wipa_decoder_prefill_ragged(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, P,
-                                                     P - sot_back if sot_back is not None else -1, eot, ptr(m_first), ptr(m_always),
-                                                     int(use_graph), C.byref(rules) if rules is not None else None,
-                                                     ptr(rec) if rec is not None else None, ptr(starts), ptr(ws), ws.numel(), sptr(s)),
-                       "wipa_decoder_prefill_ragged")
-            if sot_back is not None:  # the pass leaves the <|startoftranscript|> column's logits at the head of its workspace
-                ld = st.layout.ld_logits
-                sot_logits = ws[: B * ld * 4].view(torch.float32).view(B, ld)[:, : model.dims.n_vocab].clone()
-            done_steps = P
-        elif sot_back is not None:  # the steps up to the <|startoftranscript|> column: its logits are those of the call's last step
-            n = P - sot_back + 1
-            _dec_run(L, pk, st, B, P, eot, m_first, m_always, n, use_graph, rules, s, rec, starts)
-            sot_logits = st.logits.clone()
-            done_steps = n
-        while done_steps < total:
-            n = min(check_every if stop_on_eot else total, total - done_steps)
-            if done_steps < P - 1:  # the rest of the prompt walk rides with the first generated columns
-                n = min(total - done_steps, n + (P - 1 - done_steps))
-            _dec_run(L, pk, st, B, P, eot, m_first, m_always, n, use_graph, rules, s, rec, starts)
-            done_steps += n
-            if stop_on_eot and done_steps >= P:
-                last = st.tokens[:, done_steps].cpu()  # synchronises the library stream
-                if bool((last == eot).all()):
-                    break
-        winner = lengths = None
-        if rank and n_group > 1:  # the winners only come back: clips x columns
-            toks, slp, winner, lengths = _rank_groups(st, n_group, P, done_steps - (P - 1), eot, length_penalty, s)
-        else:
-            toks = st.tokens[:, : done_steps + 1].cpu().numpy().astype(np.int64)  # synchronises: the host arrays of begin are consumed
-            slp = st.sum_logprobs.cpu().numpy().copy()
-        last_logits = st.logits
-        if sot_logits is not None and n_group > 1:
-            sot_logits = sot_logits[::n_group]  # the candidates of a clip share their prompt: one row per clip
-    n_steps = done_steps - (P - 1)
-    if stop_on_eot:
-        body = toks[:, P:]
-        all_eot = (body == eot).all(axis=0)
-        if all_eot.any():
-            n_steps = int(np.argmax(all_eot)) + 1
-            toks = toks[:, : P + n_steps]
-    ranked = rank and n_group > 1
-    return GreedyTokens(toks, n_steps, slp, last_logits, n_init=P, starts=(clip_starts_h if ranked else starts_h).copy(), sot_logits=sot_logits,
-                        winner=winner, lengths=lengths)
+        return starts
+
+    def run_prompt(L, pk, st, B, m_first, m_always, rec, starts, s):
+        ws = st.prompt_workspace(pk, P)
+        _lib.check(L.wipa_decoder_prefill_ragged(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, P,
+                                                 P - sot_back if sot_back is not None else -1, eot, ptr(m_first), ptr(m_always),
+                                                 int(use_graph), C.byref(rules) if rules is not None else None,
+                                                 ptr(rec) if rec is not None else None, ptr(starts), ptr(ws), ws.numel(), sptr(s)),
+                   "wipa_decoder_prefill_ragged")
+        if sot_back is None:
+            return None
+        ld = st.layout.ld_logits  # the pass leaves the <|startoftranscript|> column's logits at the head of its workspace
+        return ws[: B * ld * 4].view(torch.float32).view(B, ld)[:, : model.dims.n_vocab].clone()
+
+    g = _decode_loop(model, audio_features, P, max_new_tokens, begin, run_prompt, suppress_always, suppress_first, eot, stop_on_eot, use_graph,
+                     check_every, rules, sample, n_group, rank, length_penalty, sot_back)
+    g.n_init, g.starts = P, (clip_starts_h if rank and n_group > 1 else starts_h).copy()
+    return g
 
 
 def forced_decode_logits(model, audio_features: torch.Tensor, tokens: np.ndarray, n_init: int, suppress_always: Sequence[int],
@@ -626,17 +625,13 @@ def forced_decode_logits(model, audio_features: torch.Tensor, tokens: np.ndarray
     st = _state_for(model, B, pk)
     m_always = _mask(model, suppress_always)
     m_first = _mask(model, list(suppress_always) + list(suppress_first))
-    init = (C.c_int32 * n_init)(*[int(t) for t in tokens[0, :n_init]])
     assert (tokens[:, :n_init] == tokens[0, :n_init]).all(), "one prompt for all rows"
     V = model.dims.n_vocab
     with on_stream() as s:
         forced = torch.from_numpy(tokens.astype(np.int32)).to(model.device)
         trace = torch.empty(B, n_steps, V, dtype=torch.float32, device=model.device)
         chosen = torch.empty(B, n_steps, dtype=torch.int32, device=model.device)
-        feats = audio_features.to(device=model.device, dtype=model.dtype).contiguous()
-        _lib.check(L.wipa_decoder_set_audio(C.byref(pk["cfg"]), pk["dec_tab"], ptr(feats), ptr(st.blob), st.blob.numel(), B, sptr(s)),
-                   "wipa_decoder_set_audio")
-        _lib.check(L.wipa_decoder_begin(C.byref(pk["cfg"]), ptr(st.blob), st.blob.numel(), B, init, n_init, sptr(s)), "wipa_decoder_begin")
+        feats, _ = _open(model, L, pk, st, audio_features, B, s, _begin_with(tokens[0, :n_init]))
         _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s)
         for i in range(n_steps):
             p = n_init + i  # the token position the last step has just filled
