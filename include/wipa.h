@@ -883,7 +883,8 @@ int wipa_masked_ce_bwd(float* logits, int64_t ldl, const int32_t* tokens, int64_
 int wipa_embed_bwd(const int32_t* tokens_flat, const float* dx, int B, int T, int D, float* d_tok_emb, float* d_pos_emb,
                    wipa_stream_t s);
 /* Backward of wipa_attention (f32): d is the forward descriptor (q,k,v pre-scaled); out / d_out share the
- * o_* strides; dq,dk,dv share the q/k/v strides; dvec f32 [B,H,Tq] scratch. dq and dk are multiplied by qk_scale. */
+ * o_* strides; dq,dk,dv share the q/k/v strides; dvec f32 [B,H,Tq] scratch. dq and dk are multiplied by qk_scale.
+ * Every batch, row and head stride must be a multiple of 4 floats (16-byte rows), or the call is refused. */
 int wipa_attention_bwd(const wipa_attn_desc* d, const float* out, const float* d_out, const float* lse, float* dq, float* dk,
                        float* dv, float* dvec, float qk_scale, wipa_stream_t s);
 /* Flat multi-tensor optimiser step: per-tensor g *= min(1, max_norm/(|g|+1e-6)), then mlx-style AdamW

@@ -408,7 +408,8 @@ extern "C" int wipa_attention_bwd(const wipa_attn_desc* d, const float* out, con
     WIPA_REQUIRE(d->dtype == WIPA_F32, "wipa_attention_bwd: f32 only");
     WIPA_REQUIRE(d->B > 0 && d->H > 0 && d->Tq > 0 && d->Tk > 0, "wipa_attention_bwd: bad shape");
     WIPA_REQUIRE(d->q_rs % 4 == 0 && d->k_rs % 4 == 0 && d->v_rs % 4 == 0 && d->o_rs % 4 == 0 && d->q_hs % 4 == 0 &&
-                     d->k_hs % 4 == 0 && d->v_hs % 4 == 0 && d->o_hs % 4 == 0,
+                     d->k_hs % 4 == 0 && d->v_hs % 4 == 0 && d->o_hs % 4 == 0 && d->q_bs % 4 == 0 && d->k_bs % 4 == 0 &&
+                     d->v_bs % 4 == 0 && d->o_bs % 4 == 0,
                  "wipa_attention_bwd: strides must keep 16-byte alignment");
     AttnBwdParams p;
     p.q = (const float*)d->q; p.k = (const float*)d->k; p.v = (const float*)d->v;
