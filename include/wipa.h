@@ -810,6 +810,45 @@ int wipa_decoder_begin_ragged(const wipa_model_cfg* cfg, void* state, size_t sta
 int wipa_decoder_run_ragged(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int n_init,
                             int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
                             const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, wipa_stream_t s);
+/* Continuous batching: the B rows of a state are SLOTS.  A clip is admitted into a slot at the column the state
+ * stands at, decodes there with its own position embeddings, attention window, sampling counter AND prompt end, and when it has
+ * finished the next clip takes the slot while the other rows go on.  starts_dev is int32 [2][B] on the device, caller-owned: starts_dev[b]
+ * is the first own column of slot b's clip, starts_dev[B + b] the number of tokens it may generate (all zero: every slot is finished).
+ * Per row, with own = start[b] + n_init, the step at column p (which fills column p + 1):
+ *   p + 1 < own: the row is idle or in its prompt -- the token of column p + 1 is taken as it stands, nothing is written, nothing is
+ *   counted, sum_logprobs[b] is untouched;  p + 1 == own: the pick under mask_first;  own < p + 1 < own + limit: the pick under mask_always;
+ *   p + 1 >= own + limit: column p + 1 takes eot, without a log-probability, and the EOT latch holds the row from there on.
+ * The latch is the token of column p: a slot leaves it when an admission writes initial tokens over the finished row's last column.
+ * Served: both cross-attention forms, bf16 / f32 decoder tables, one row per clip, 1..4 initial tokens.  Refused by name
+ * (WIPA_ERR_ARG, nothing enqueued): fp8 tables, candidate groups, timestamp rules, a step without the fused tail.
+ * wipa_decoder_admit_rows: in stream order, for row i of n_rows: features_host[i] (a DEVICE pointer to the clip's encoder output
+ *   [n_audio_ctx, d] in cfg.dtype; the array of pointers is on the host) is copied into slot slots_host[i] of the blob's audio copy
+ *   (absorbed form), or projected into the slot's K / V of every layer as wipa_decoder_set_audio projects it (cached form: n_text_layer
+ *   GEMMs of n_audio_ctx rows per admission; wipa_decoder_begin must have run on this process before, as for every decode); the
+ *   n_init tokens initial_tokens_host[i][0 .. n_init) go to columns [c, c + n_init) of the slot, c being the state's position: the column
+ *   the next step reads (the finished row's last token, which the caller has copied out, is overwritten; every run call re-embeds column
+ *   c before its first step); starts_dev[slot] = c, starts_dev[B + slot] = limits_host[i]; sum_logprobs[slot] = 0; with a sampling record
+ *   (sample, the record the run calls take) the slot's Philox stream becomes streams_host[i] = (lo, hi).  An admission whose initial
+ *   tokens would not leave one column to generate in the table (c + n_init >= n_text_ctx) is not carried out: shift first.
+ * wipa_decoder_shift_columns: for every row, the token columns [shift, pos] move to [0, pos - shift], and so do the self-attention K / V
+ *   rows of every layer; pos and every start drop by shift.  A row whose start lies below shift (finished, or never admitted) ends with
+ *   start 0 and limit 0.  Source and destination overlap: no scratch buffer, an ORDER -- one workgroup owns a (layer, K | V, row) strip
+ *   and walks it in ascending chunks, all loads of a chunk before a barrier and all its stores after it; the destination lies below the
+ *   source, so no store reaches bytes a later chunk still has to load.  Plain vector loads and stores.  Position embedding, attention
+ *   window and sampling counter are relative to the row's start, and the attention kernel walks a row's keys from its start in the
+ *   same partition wherever that start lies, so a shift changes no bit of what a row computes.  Refused: shift outside
+ *   1..n_text_ctx-1; a shift above the position is not carried out.
+ * wipa_decoder_run_continuous: wipa_decoder_run_ragged with the CONTINUOUS tails and rules == NULL.  The step graph's key is that of
+ *   wipa_decoder_run_ragged plus the variant; the replayed kernels read starts_dev, so admissions and shifts replay the same graph. */
+int wipa_decoder_admit_rows(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int n_rows,
+                            const int32_t* slots_host,
+                            const void* const* features_host, const int32_t* initial_tokens_host, int n_init, const int32_t* limits_host,
+                            int32_t* starts_dev, void* sample, const uint32_t* streams_host, wipa_stream_t s);
+int wipa_decoder_shift_columns(const wipa_model_cfg* cfg, void* state, size_t state_bytes, int B, int32_t* starts_dev, int shift,
+                               wipa_stream_t s);
+int wipa_decoder_run_continuous(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int n_init,
+                                int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
+                                const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, wipa_stream_t s);
 /* drop the cached step graphs that reference this state blob (call before freeing it). */
 int wipa_decoder_release(void* state);
 

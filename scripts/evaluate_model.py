@@ -109,6 +109,34 @@ def transcribe_clips(model, audio_paths: List[str], options: DecodingOptions, ba
     return texts
 
 
+DECODE_MODES = ("lockstep", "continuous")
+
+
+def transcribe_clips_continuous(model, audio_paths: List[str], options: DecodingOptions, slots: int = 64, progress=None,
+                                ingest: str = "device") -> List[str]:
+    """``transcribe_clips`` through whisper_ipa_amd.decode_continuous: the clips' log-mels, ``slots`` files at a time, then ONE
+    continuous decode of all of them -- ``slots`` rows, and a row whose clip has reached EOT takes the next pending clip (the encoder runs
+    in chunks of ``slots`` clips ahead of need).  One text per path, "" where the file could not be read."""
+    from whisper_ipa_amd import decode_continuous
+    from whisper_ipa_amd.audio import load_audio_batch, log_mel_spectrogram
+
+    texts = [""] * len(audio_paths)
+    mels, where = [], []
+    for b in range(0, len(audio_paths), slots):
+        audio, ok = load_clips(audio_paths[b:b + slots], ingest)
+        if audio is None:
+            continue
+        audio = load_audio_batch(audio) if ingest == "device" else audio.to(model.device)
+        mels.append(log_mel_spectrogram(audio, n_mels=model.dims.n_mels))
+        where += [b + i for i in ok]
+        if progress is not None:
+            progress(min(b + slots, len(audio_paths)))
+    if mels:
+        for i, r in zip(where, decode_continuous(model, torch.cat(mels), options, slots=slots)):
+            texts[i] = r.text.strip()
+    return texts
+
+
 BASE_DECODE_MODES = ("decode", "transcribe")
 
 
@@ -149,7 +177,9 @@ def evaluate_model(model_path: str, test_data_path: str, num_samples: Optional[i
                    is_checkpoint: bool = False, n_mels: int = 80, base_model: str = "mlx-community/whisper-small-mlx",
                    batch_size: int = 64, passes_in_flight: int = 4, ingest: str = "device", scoring: str = "device",
                    base_decode: str = "decode", seed: Optional[int] = None, condition_on_previous_text: bool = False,
-                   initial_prompt: Optional[str] = None) -> Dict:
+                   initial_prompt: Optional[str] = None, decode: str = "lockstep") -> Dict:
+    if decode not in DECODE_MODES:
+        raise ValueError(f"decode must be one of {DECODE_MODES}, got {decode!r}")
     rank, world_size = parallel.world()
     say = print if rank == 0 else (lambda *a, **k: None)
     say("=" * 70)
@@ -182,6 +212,9 @@ def evaluate_model(model_path: str, test_data_path: str, num_samples: Optional[i
         local_hyp = transcribe_files(model, [s["audio_path"] for s in mine], batch_size=batch_size, seed=seed,
                                      condition_on_previous_text=condition_on_previous_text, initial_prompt=initial_prompt,
                                      progress=lambda n: say(f"  {n}/{len(mine)} clips on rank 0", flush=True))
+    elif decode == "continuous":
+        local_hyp = transcribe_clips_continuous(model, [s["audio_path"] for s in mine], options, slots=batch_size, ingest=ingest,
+                                                progress=lambda n: say(f"  {n}/{len(mine)} clips read on rank 0", flush=True))
     else:
         local_hyp = transcribe_clips(model, [s["audio_path"] for s in mine], options, batch_size=batch_size,
                                      passes_in_flight=passes_in_flight, ingest=ingest,
@@ -266,6 +299,10 @@ def main(argv=None) -> Dict:
                     help="the base-model leg: 'decode' = the checkpoint leg's decode(without_timestamps=True) (default, as before); "
                          "'transcribe' = whisper_ipa_amd.transcribe, the call the reference makes for it (timestamps on, timestamp "
                          "rules, segments, no-speech skip, 30 s windows)")
+    ap.add_argument("--decode", choices=DECODE_MODES, default="lockstep",
+                    help="how decode(without_timestamps=True) walks the clips: 'lockstep' = batches of --batch-size, each run until its "
+                         "last row ends (default, as before); 'continuous' = whisper_ipa_amd.decode_continuous: --batch-size rows, and a "
+                         "row whose clip has ended takes the next clip (--passes-in-flight does not apply)")
     ap.add_argument("--seed", type=int, default=None,
                     help="with --base-decode transcribe: re-decode the windows that fail the compression-ratio / log-probability "
                          "thresholds at 0.2, 0.4, ... 1.0 as mlx_whisper.transcribe does, sampling reproducibly from this seed "
@@ -298,10 +335,11 @@ def main(argv=None) -> Dict:
                                       is_checkpoint=False, n_mels=args.n_mels, base_model=args.base_model, batch_size=args.batch_size,
                                       passes_in_flight=args.passes_in_flight, ingest=args.ingest, scoring=args.scoring,
                                       base_decode=args.base_decode, seed=args.seed,
-                                      condition_on_previous_text=args.condition_on_previous_text, initial_prompt=args.initial_prompt)
+                                      condition_on_previous_text=args.condition_on_previous_text, initial_prompt=args.initial_prompt,
+                                      decode=args.decode)
     trained_results = evaluate_model(args.checkpoint, args.test_data, num_samples, model_name="Trained Checkpoint",
                                      is_checkpoint=True, n_mels=args.n_mels, base_model=args.base_model, batch_size=args.batch_size,
-                                     passes_in_flight=args.passes_in_flight, ingest=args.ingest, scoring=args.scoring)
+                                     passes_in_flight=args.passes_in_flight, ingest=args.ingest, scoring=args.scoring, decode=args.decode)
     if rank == 0:
         if base_results:
             compare_models(base_results, trained_results)

@@ -11,8 +11,9 @@ from . import runtime as _runtime
 
 _runtime.request_hw_queues()  # GPU_MAX_HW_QUEUES=8 unless the user set it; must precede the first HIP call (see runtime.py)
 
-from . import audio, decoding, pipeline, scoring, timing, tokenizer, whisper  # noqa: F401,E402
+from . import audio, continuous, decoding, pipeline, scoring, timing, tokenizer, whisper  # noqa: F401,E402
 from .audio import load_audio, load_audio_batch, log_mel_spectrogram, pad_or_trim  # noqa: F401
+from .continuous import decode_continuous  # noqa: F401
 from .decoding import DecodingOptions, DecodingResult, decode  # noqa: F401
 from .pipeline import PassResult, TranscribePipeline, transcribe_batches  # noqa: F401
 from .transcribe import transcribe  # noqa: F401  (the function: ``whisper_ipa_amd.transcribe(model, audio)``, as mlx_whisper.transcribe)

@@ -840,6 +840,79 @@ __global__ __launch_bounds__(GS_THREADS) void sample_tail_kernel(TailArgs<RAGGED
     pick_tail<TO, RULES, true>(q, r, rec, s_v, s_i, s_sum, s_red);
 }
 
+// ------------------------------------------------------------------ continuous batching: the CONTINUOUS tails
+// The RAGGED tails with a prompt end PER ROW (wipa_decoder_run_continuous): the rows of a state are slots, and a slot's clip was admitted
+// at its own column.  q.start is int32 [2][B]: start[b] is the row's first own column, start[B + b] the number of tokens it may generate.
+// With own = start[b] + n_init (the row's first generated column), the step at column p
+//   p + 1 <  own          the row is idle or in its prompt: the token of column p + 1 is taken as it stands, nothing is written, nothing
+//                         is counted in not_done, sum_logprobs[b] is not touched;
+//   p + 1 == own          the pick under mask_first;  own < p + 1 < own + limit: the pick under mask_always;
+//   p + 1 >= own + limit  the row has generated what it may: column p + 1 takes eot without a log-probability, and the EOT latch of
+//                         `commit` holds it from there on.
+// The latch is read from the token of column p, so a slot leaves it when wipa_decoder_admit_rows writes the next clip's initial tokens
+// over the finished row's last column: nothing is kept per row but the tokens, the two arrays and the log-probability sum.
+// Position embedding (pos_row), the next step's input row and the position advance are the RAGGED ones (tail_finish<TO, true>); the draw's
+// counter takes the row's own position p - start[b], as in the RAGGED sampling tail.  New kernels beside the RAGGED instantiations: those
+// keep their code.  A step at the last column of the table (p + 1 >= n_ctx) does nothing at all, position advance included.
+struct ContinuousRow {
+    int own, limit;
+};
+__device__ __forceinline__ ContinuousRow continuous_row(const TailArgs<true>& q, int b) {
+    return ContinuousRow{q.start[b] + q.n_init, q.start[(int)gridDim.x + b]};
+}
+
+template <typename TO>
+__global__ __launch_bounds__(GS_THREADS) void greedy_tail_continuous_kernel(TailArgs<true> q) {
+    __shared__ float s_v[GS_WAVES];
+    __shared__ int s_i[GS_WAVES];
+    __shared__ float s_sum[GS_WAVES];
+    __shared__ float s_red[4];
+    const int b = blockIdx.x;
+    const int p = tail_pos(q.pos);
+    if (p + 1 >= q.n_ctx) return;  // uniform over the grid: no token column, no K / V row and no position row lies past the table
+    const ContinuousRow r = continuous_row(q, b);
+    int32_t* tk = q.tokens + (int64_t)b * q.ld_tok;
+    int next;
+    if (p + 1 < r.own) {  // uniform over the workgroup: one row per workgroup
+        next = tk[p + 1];
+    } else if (p + 1 >= r.own + r.limit) {
+        next = q.eot;
+        if (threadIdx.x == 0) tk[p + 1] = next;
+    } else {
+        const float* mask = (p + 1 == r.own) ? q.mask_first : q.mask_always;
+        const RowScan sc = row_scan_reg(q.logits + (int64_t)b * q.ldl, mask, q.V, s_v, s_i, s_sum);
+        next = commit(tk + p, q.eot, sc.top.i, -logf(sc.tot), q.sum_logprobs + b, q.not_done);
+    }
+    tail_finish<TO>(q, p, next, s_red);
+}
+
+template <typename TO>
+__global__ __launch_bounds__(GS_THREADS) void sample_tail_continuous_kernel(TailArgs<true> q, const uint32_t* __restrict__ rec) {
+    __shared__ float s_v[2 * GS_WAVES];
+    __shared__ int s_i[2 * GS_WAVES];
+    __shared__ float s_sum[2 * GS_WAVES];
+    __shared__ float s_red[4];
+    const int b = blockIdx.x;
+    const int p = tail_pos(q.pos);
+    if (p + 1 >= q.n_ctx) return;
+    const ContinuousRow r = continuous_row(q, b);
+    int32_t* tk = q.tokens + (int64_t)b * q.ld_tok;
+    int next;
+    if (p + 1 < r.own) {
+        next = tk[p + 1];
+    } else if (p + 1 >= r.own + r.limit) {
+        next = q.eot;
+        if (threadIdx.x == 0) tk[p + 1] = next;
+    } else {
+        const float* mask = (p + 1 == r.own) ? q.mask_first : q.mask_always;
+        const RulesDev none = {q.V, -1, -1};  // no rules: every column is on the text side
+        const RowPick pick = row_pick<false, true>(q.logits + (int64_t)b * q.ldl, mask, q.V, tk, p, q.n_init, q.eot, none, s_v, s_i, s_sum, rec, b,
+                                                   max(p - q.start[b], 0));
+        next = commit(tk + p, q.eot, pick.next, pick.logprob, q.sum_logprobs + b, q.not_done);
+    }
+    tail_finish<TO>(q, p, next, s_red);
+}
+
 // wipa_sample_noise: g_c of one (row, position), c < V -- the numbers the sampling tails add, for measurement
 __global__ __launch_bounds__(256) void sample_noise_kernel(const uint32_t* __restrict__ rec, int row, int p, int V, float* __restrict__ out) {
     const int qi = blockIdx.x * 256 + threadIdx.x;
@@ -1307,6 +1380,43 @@ extern "C" int wipa_step_embed_ragged(const float* logits, int64_t ldl, int B, i
     WIPA_REQUIRE(starts_dev, "wipa_step_embed_ragged: bad arguments (starts_dev is required)");
     return wipa_step_tail(logits, ldl, B, V, mask_first, mask_always, tokens, ld_tok, pos_dev, posd_dev, done_counter, n_init, eot, rules, sample,
                           starts_dev, sum_logprobs, not_done, tok_emb, emb_dtype, emb_scale, pos_emb, n_ctx, x, ln_w, ln_b, y, y_dtype, D, eps, stream);
+}
+
+// the CONTINUOUS tails (declared in wipa_common.h for wipa_decoder_run_continuous; not exported): the checks of wipa_step_tail without
+// rules; starts_dev is int32 [2][B], the rows' first own columns and then the tokens each may generate
+int wipa_step_tail_continuous(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always, int32_t* tokens,
+                              int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init, int eot, const void* sample,
+                              const int32_t* starts_dev, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
+                              const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y,
+                              int y_dtype, int D, float eps, wipa_stream_t stream) {
+    const char* who = "wipa_decoder_run_continuous";
+    WIPA_REQUIRE(logits && mask_first && mask_always && tokens && pos_dev && posd_dev && done_counter && sum_logprobs && not_done && tok_emb &&
+                     pos_emb && x && ln_w && ln_b && y && starts_dev && B > 0 && n_ctx > 0 && n_init >= 1 && ld_tok >= n_ctx,
+                 "%s: bad arguments of the step's tail (starts_dev is required)", who);
+    const TailParams tp = tail_params(logits, ldl, V, mask_first, mask_always, tokens, ld_tok, pos_dev, posd_dev, done_counter, n_init, eot,
+                                      sum_logprobs, not_done, tok_emb, emb_dtype, emb_scale, pos_emb, n_ctx, x, ln_w, ln_b, y, D, eps);
+    WIPA_REQUIRE(tp.D % 4 == 0 && tp.D > 0 && tp.D <= 2048, "%s: D=%d must be a multiple of 4 and <= 2048", who, tp.D);
+    WIPA_REQUIRE(tp.emb_dtype == WIPA_F32 || tp.emb_dtype == WIPA_BF16, "%s: bad embedding dtype %d", who, tp.emb_dtype);
+    WIPA_REQUIRE(reg_scan_ok(tp.logits, tp.V, tp.ldl, tp.mask_first, tp.mask_always), "%s: vocabulary of %d / unaligned logits or masks", who, tp.V);
+    WIPA_REQUIRE(y_dtype == WIPA_F32 || y_dtype == WIPA_BF16, "%s: bad dtype %d", who, y_dtype);
+    if (sample) {
+        RulesDev r = {tp.V, -1, -1};
+        const int rc = sample_check(who, nullptr, sample, tp.logits, tp.V, tp.ldl, tp.mask_first, tp.mask_always, tp.eot, tp.n_ctx, &r);
+        if (rc != WIPA_OK) return rc;
+    }
+    TailArgs<true> q = {};
+    static_cast<TailParams&>(q) = tp;
+    q.start = starts_dev;
+    const dim3 grid(B), block(GS_THREADS);
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t* rec = (const uint32_t*)sample;
+    const bool f32 = y_dtype == WIPA_F32;
+    if (rec && f32) hipLaunchKernelGGL((sample_tail_continuous_kernel<float>), grid, block, 0, s, q, rec);
+    else if (rec) hipLaunchKernelGGL((sample_tail_continuous_kernel<__bf16>), grid, block, 0, s, q, rec);
+    else if (f32) hipLaunchKernelGGL((greedy_tail_continuous_kernel<float>), grid, block, 0, s, q);
+    else hipLaunchKernelGGL((greedy_tail_continuous_kernel<__bf16>), grid, block, 0, s, q);
+    WIPA_LAUNCH_CHECK();
+    return WIPA_OK;
 }
 
 // the tail on wipa_logits_greedy's per-wave partials: no logits, so no rules, no draw and no ragged rows

@@ -425,6 +425,9 @@ struct StepCtx {
     const float *mask_first, *mask_always;
     // a step whose logits nobody reads (every step of a wipa_decoder_run call but the last) does not write them at all
     bool lean;
+    // continuous batching (wipa_decoder_run_continuous): `starts` is int32 [2][B] -- first own columns, then the tokens each row may
+    // generate -- and the step ends in the CONTINUOUS tail (a prompt end per row); everything before the tail is the ragged step
+    bool continuous;
 };
 // The logits projection with the greedy partials in its epilogue + a tail that merges them (round 4; WIPA_LOGITS_FUSED=0 restores
 // the plain GEMM + the row-scanning tail): bf16 models without fp8 decoder tables, <= 64 rows, tail-fused steps.  Measured on
@@ -622,6 +625,11 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
         // (with ctx.rules the timestamp rules, with ctx.sample the draw, with ctx.starts the RAGGED tails: position embedding and sampling
         // counter at the row's own position)
         const void* const* lw0 = w + WIPA_DEC_GLOBAL;
+        if (ctx.continuous)
+            return wipa_step_tail_continuous(logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos, posd,
+                                             done_counter_of(st, L), ctx.n_init, ctx.eot, ctx.sample, ctx.starts, (float*)(st + L.sum_logprobs),
+                                             (int32_t*)(st + L.not_done), w[0], emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], nctx, x_first,
+                                             (const float*)lw0[0], (const float*)lw0[1], ln, dt, d, 1e-5f, stream);
         RT_CALL(wipa_step_tail(logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos, posd,
                                done_counter_of(st, L), ctx.n_init, ctx.eot, ctx.rules, ctx.sample, ctx.starts, (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), w[0],
                                emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], nctx, x_first, (const float*)lw0[0], (const float*)lw0[1], ln,
@@ -958,7 +966,8 @@ int step_variant(const wipa_model_cfg* cfg, int B, const StepCtx& c) {
     return cfg->dtype * 2 + t_f32_split + 4 * decode_mode(cfg, B) + 16 * cfg->dec_w_dtype +
            64 * cfg->dec_cross_absorbed * (absorbed_block_fused() ? 2 : 1) + 256 * (int)tail_fused() + 512 * (int)absorbed_merge_out() +
            1024 * cfg->dec_cross_splits + 8192 * (int)lean_steps(cfg, B, c) +
-           16384 * (cfg->dec_cross_absorbed ? wipa_cross_absorbed_loop_variant() : 0) + 65536 * (group_of(cfg) > 1 ? group_of(cfg) : 0);
+           16384 * (cfg->dec_cross_absorbed ? wipa_cross_absorbed_loop_variant() : 0) + 65536 * (group_of(cfg) > 1 ? group_of(cfg) : 0) +
+           (1 << 28) * (int)c.continuous;
 }
 // a key from the context of a decode call; the three rule terms are 0 without rules
 GraphKey graph_key(const wipa_model_cfg* cfg, const void* const* w, const void* state, int B, const StepCtx& c, int variant, int kind,
@@ -1177,18 +1186,22 @@ extern "C" int wipa_decoder_run_sample(const wipa_model_cfg* cfg, const void* co
                                    stream);
 }
 
-extern "C" int wipa_decoder_run_ragged(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
-                                       int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
-                                       const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, wipa_stream_t stream) {
+// wipa_decoder_run_ragged and, with `continuous`, wipa_decoder_run_continuous: the same call but for the tail the steps end in
+static int decoder_run(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init, int eot,
+                       const float* mask_first, const float* mask_always, int n_steps, int use_graph, const wipa_decode_rules* rules,
+                       const void* sample, const int32_t* starts_dev, bool continuous, wipa_stream_t stream) {
     RT_CALL(cfg_check(cfg));
     SplitScope split_scope(cfg);
     WIPA_REQUIRE(w && state && mask_first && mask_always && B > 0 && n_steps >= 0, "wipa_decoder_run: bad arguments");
     // every step of the call but the LAST is "lean" when the logits projection carries the greedy partials: its logits are not
     // written (state.logits holds those of the last step of a call, which is what callers read)
-    const StepCtx full{rules, sample, starts_dev, n_init, eot, mask_first, mask_always, false};
+    const StepCtx full{rules, sample, starts_dev, n_init, eot, mask_first, mask_always, false, continuous};
     StepCtx lean = full;
     lean.lean = true;
-    static const EntryNames who = {"wipa_decoder_run", "wipa_decoder_run_rules", "wipa_decoder_run_sample", "wipa_decoder_run_ragged"};
+    static const EntryNames who_ragged = {"wipa_decoder_run", "wipa_decoder_run_rules", "wipa_decoder_run_sample", "wipa_decoder_run_ragged"};
+    static const EntryNames who_continuous = {"wipa_decoder_run_continuous", "wipa_decoder_run_continuous", "wipa_decoder_run_continuous",
+                                              "wipa_decoder_run_continuous"};
+    const EntryNames& who = continuous ? who_continuous : who_ragged;
     char* st = (char*)state;
     hipStream_t s = (hipStream_t)stream;
     wipa_dec_layout L;
@@ -1220,6 +1233,191 @@ extern "C" int wipa_decoder_run_ragged(const wipa_model_cfg* cfg, const void* co
     RT_CALL(step_graph(full, &full_exec));
     if (lean_ok && n_steps > 1) RT_CALL(step_graph(lean, &lean_exec));
     for (int i = 0; i < n_steps; ++i) WIPA_CHECK_HIP(hipGraphLaunch((lean_exec && i + 1 < n_steps) ? lean_exec : full_exec, s));
+    return WIPA_OK;
+}
+
+extern "C" int wipa_decoder_run_ragged(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
+                                       int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
+                                       const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, wipa_stream_t stream) {
+    return decoder_run(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, n_steps, use_graph, rules, sample, starts_dev, false,
+                       stream);
+}
+
+// ------------------------------------------------------------------ continuous batching: slots, admission, column shift
+namespace {
+
+// what a continuous decode serves, in the words of its entry points: bf16 / f32 decoder tables, one row per clip
+int continuous_servable(const char* who, const wipa_model_cfg* cfg, int B, const int32_t* starts_dev) {
+    WIPA_REQUIRE(starts_dev, "%s: starts_dev (int32 [2][B]: first own columns, then token limits) is required", who);
+    WIPA_REQUIRE(cfg->dec_w_dtype == 0, "%s: fp8 decoder tables are not served (cfg.dec_w_dtype)", who);
+    WIPA_REQUIRE(group_of(cfg) == 1, "%s: candidate groups are not served (cfg.dec_n_group=%d)", who, cfg->dec_n_group);
+    WIPA_REQUIRE(B > 0, "%s: bad batch", who);
+    return WIPA_OK;
+}
+
+// one admitted clip: its initial tokens into columns [*pos, *pos + n_init) of the slot's row, the slot's start, limit and log-probability
+// sum, and (with a sampling record) the Philox stream of its draws.  One thread; a column range that does not fit the table is not written.
+__global__ void admit_row_kernel(int32_t* tokens, int64_t ld_tok, const int32_t* pos, int n_ctx, int slot, int B, int n_init, int t0, int t1,
+                                 int t2, int t3, int limit, int32_t* starts, float* sum_logprobs, uint32_t* rec, uint32_t stream_lo,
+                                 uint32_t stream_hi) {
+    const int c = *pos;
+    if (c < 0 || c + n_init >= n_ctx) return;
+    const int first4[4] = {t0, t1, t2, t3};
+    for (int t = 0; t < n_init; ++t) tokens[(int64_t)slot * ld_tok + c + t] = first4[t];
+    starts[slot] = c;
+    starts[B + slot] = limit;
+    sum_logprobs[slot] = 0.f;
+    if (rec) {
+        rec[4 + 2 * slot] = stream_lo;
+        rec[5 + 2 * slot] = stream_hi;
+    }
+}
+
+// wipa_decoder_shift_columns, part 1: the bytes [shift * row_bytes, (*pos + 1) * row_bytes) of every strip move down by shift * row_bytes.
+// Source and destination overlap; the ORDER makes it safe, no scratch: ONE workgroup owns a strip and walks it in ascending chunks of
+// 256 x 16 bytes, every thread loads its 16 bytes of the chunk, the workgroup meets at a barrier, then every thread stores.  The
+// destination lies below the source (shift > 0), so a chunk's stores end below the first byte of the next chunk's loads, and within a
+// chunk every load precedes every store.  strip s of the grid starts at base + s * strip_bytes; row_bytes is a multiple of 16.
+__global__ __launch_bounds__(256) void shift_rows_kernel(char* base, int64_t strip_bytes, int64_t row_bytes, const int32_t* pos, int n_ctx, int shift) {
+    const int p = *pos;
+    if (shift <= 0 || shift > p || p >= n_ctx) return;  // uniform; nothing is read or written outside the strip's n_ctx rows
+    char* strip = base + (int64_t)blockIdx.x * strip_bytes;
+    const int64_t n = (int64_t)(p + 1 - shift) * row_bytes, off = (int64_t)shift * row_bytes;
+    for (int64_t c0 = 0; c0 < n; c0 += 256 * 16) {  // uniform trip count: the barrier is reached by all
+        const int64_t i = c0 + (int64_t)threadIdx.x * 16;
+        uint4 v = {0u, 0u, 0u, 0u};
+        if (i < n) v = *reinterpret_cast<const uint4*>(strip + off + i);
+        __syncthreads();
+        if (i < n) *reinterpret_cast<uint4*>(strip + i) = v;
+        __syncthreads();  // the next chunk's loads stay behind this chunk's stores (they touch disjoint bytes; kept for a plain proof)
+    }
+}
+// part 2, the token columns (4-byte elements: a shift need not keep 16-byte alignment): one workgroup per row, the same order
+__global__ __launch_bounds__(256) void shift_tokens_kernel(int32_t* tokens, int64_t ld_tok, const int32_t* pos, int n_ctx, int shift) {
+    const int p = *pos;
+    if (shift <= 0 || shift > p || p >= n_ctx) return;
+    int32_t* row = tokens + (int64_t)blockIdx.x * ld_tok;
+    const int n = p + 1 - shift;
+    for (int c0 = 0; c0 < n; c0 += 256) {
+        const int i = c0 + (int)threadIdx.x;
+        int32_t v = 0;
+        if (i < n) v = row[shift + i];
+        __syncthreads();
+        if (i < n) row[i] = v;
+        __syncthreads();
+    }
+}
+// part 3, after both: the position and the rows' starts.  A row whose start lies below the shift has left the table's window -- it was
+// finished, or never admitted: start 0, limit 0 (it takes eot at every column).
+__global__ void shift_finish_kernel(int32_t* pos, int64_t* posd, int d, int32_t* starts, int B, int n_ctx, int shift) {
+    const int p = *pos;
+    if (shift <= 0 || shift > p || p >= n_ctx) return;
+    for (int b = threadIdx.x; b < B; b += blockDim.x) {
+        const int s0 = starts[b];
+        starts[b] = max(s0 - shift, 0);
+        if (s0 < shift) starts[B + b] = 0;
+    }
+    if (threadIdx.x == 0) {
+        *pos = p - shift;
+        *posd = (int64_t)(p - shift) * d;
+    }
+}
+
+}  // namespace
+
+extern "C" int wipa_decoder_run_continuous(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
+                                           int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
+                                           const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, wipa_stream_t stream) {
+    RT_CALL(cfg_check(cfg));
+    WIPA_REQUIRE(!rules, "wipa_decoder_run_continuous: the timestamp rules are not served (they scan the row from a common column n_init; "
+                 "rules must be NULL)");
+    RT_CALL(continuous_servable("wipa_decoder_run_continuous", cfg, B, starts_dev));
+    WIPA_REQUIRE(n_init >= 1 && n_init <= 4, "wipa_decoder_run_continuous: 1..4 initial tokens per clip (got %d)", n_init);
+    return decoder_run(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, n_steps, use_graph, nullptr, sample, starts_dev, true,
+                       stream);
+}
+
+extern "C" int wipa_decoder_admit_rows(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_rows,
+                                       const int32_t* slots_host,
+                                       const void* const* features_host, const int32_t* initial_tokens_host, int n_init,
+                                       const int32_t* limits_host, int32_t* starts_dev, void* sample, const uint32_t* streams_host,
+                                       wipa_stream_t stream) {
+    RT_CALL(cfg_check(cfg));
+    SplitScope split_scope(cfg);
+    const char* who = "wipa_decoder_admit_rows";
+    RT_CALL(continuous_servable(who, cfg, B, starts_dev));
+    WIPA_REQUIRE(w && state && n_rows >= 0 && (n_rows == 0 || (slots_host && features_host && initial_tokens_host && limits_host)),
+                 "%s: null pointer / bad row count", who);
+    WIPA_REQUIRE(n_init >= 1 && n_init <= 4, "%s: 1..4 initial tokens per clip (got %d)", who, n_init);
+    WIPA_REQUIRE(!sample || (streams_host && ((uintptr_t)sample % 4) == 0), "%s: a sampling record needs streams_host (uint32 [n_rows][2])", who);
+    for (int i = 0; i < n_rows; ++i) {
+        WIPA_REQUIRE(slots_host[i] >= 0 && slots_host[i] < B, "%s: slot[%d]=%d outside 0..%d", who, i, slots_host[i], B - 1);
+        for (int j = 0; j < i; ++j) WIPA_REQUIRE(slots_host[j] != slots_host[i], "%s: slot %d is listed twice", who, slots_host[i]);
+        WIPA_REQUIRE(features_host[i], "%s: features[%d] is null", who, i);
+        WIPA_REQUIRE(limits_host[i] >= 0 && limits_host[i] <= cfg->n_text_ctx, "%s: limit[%d]=%d outside 0..n_text_ctx", who, i, limits_host[i]);
+        for (int t = 0; t < n_init; ++t)
+            WIPA_REQUIRE(initial_tokens_host[i * n_init + t] >= 0 && initial_tokens_host[i * n_init + t] < cfg->n_vocab,
+                         "%s: initial token [%d][%d]=%d outside the vocabulary of %d", who, i, t, initial_tokens_host[i * n_init + t], cfg->n_vocab);
+    }
+    const wipa_dec_layout L = dec_layout(cfg, B);
+    RT_CALL(state_fits(who, L, state_bytes));
+    hipStream_t s = (hipStream_t)stream;
+    char* st = (char*)state;
+    const int dt = cfg->dtype;
+    const size_t e = wipa_dtype_size(dt);
+    const int d = cfg->n_text_state, H = cfg->n_text_head, Ta = cfg->n_audio_ctx;
+    WIPA_REQUIRE(cfg->n_audio_state == d, "encoder/decoder widths differ");
+    const size_t clip_bytes = (size_t)Ta * d * e;
+    for (int i = 0; i < n_rows; ++i) {
+        const int slot = slots_host[i];
+        if (cfg->dec_cross_absorbed) {  // the steps stream the encoder output itself: an admission is a copy
+            WIPA_CHECK_HIP(hipMemcpyAsync(st + L.cross_kv + (size_t)slot * clip_bytes, features_host[i], clip_bytes, hipMemcpyDeviceToDevice, s));
+        } else {  // the cached form: wipa_decoder_set_audio's projection for this clip alone, into the slot's K / V of every layer
+            for (int l = 0; l < cfg->n_text_layer; ++l) {
+                const void* const* lw = w + WIPA_DEC_GLOBAL + WIPA_DEC_PER_LAYER * l;
+                char* ckv = st + L.cross_kv + ((size_t)l * B + slot) * 2 * H * Ta * 64 * e;
+                wipa_gemm_desc g;
+                memset(&g, 0, sizeof(g));
+                g.col_scale_n = d; g.col_scale = QK_SCALE;  // the key half; values stay unscaled
+                g.rg_in = Ta; g.rg_valid = Ta; g.rg_stride = (int64_t)2 * H * Ta * 64;
+                g.cg_in = 64; g.cg_stride = (int64_t)Ta * 64;
+                RT_CALL(gemm(features_host[i], d, lw[10], d, ckv, 64, Ta, 2 * d, d, dt, dt, (const float*)lw[11], 0, nullptr, stream, &g));
+            }
+        }
+        int t4[4] = {0, 0, 0, 0};
+        for (int t = 0; t < n_init; ++t) t4[t] = initial_tokens_host[i * n_init + t];
+        hipLaunchKernelGGL(admit_row_kernel, dim3(1), dim3(1), 0, s, (int32_t*)(st + L.tokens), L.ld_tok, (const int32_t*)(st + L.pos),
+                           cfg->n_text_ctx, slot, B, n_init, t4[0], t4[1], t4[2], t4[3], limits_host[i], starts_dev, (float*)(st + L.sum_logprobs),
+                           (uint32_t*)sample, sample ? streams_host[2 * i] : 0u, sample ? streams_host[2 * i + 1] : 0u);
+        WIPA_LAUNCH_CHECK();
+    }
+    return WIPA_OK;
+}
+
+extern "C" int wipa_decoder_shift_columns(const wipa_model_cfg* cfg, void* state, size_t state_bytes, int B, int32_t* starts_dev, int shift,
+                                          wipa_stream_t stream) {
+    RT_CALL(cfg_check(cfg));
+    SplitScope split_scope(cfg);
+    const char* who = "wipa_decoder_shift_columns";
+    RT_CALL(continuous_servable(who, cfg, B, starts_dev));
+    WIPA_REQUIRE(state && shift >= 1 && shift < cfg->n_text_ctx, "%s: shift=%d outside 1..n_text_ctx-1", who, shift);
+    const wipa_dec_layout L = dec_layout(cfg, B);
+    RT_CALL(state_fits(who, L, state_bytes));
+    hipStream_t s = (hipStream_t)stream;
+    char* st = (char*)state;
+    const size_t e = wipa_dtype_size(cfg->dtype);
+    const int d = cfg->n_text_state, nctx = cfg->n_text_ctx;
+    const int64_t row_bytes = (int64_t)d * e, strip_bytes = (int64_t)nctx * row_bytes, slot = (int64_t)B * strip_bytes;
+    WIPA_REQUIRE(row_bytes % 16 == 0, "%s: a K / V row of %lld bytes is no multiple of 16", who, (long long)row_bytes);
+    const int32_t* pos = (const int32_t*)(st + L.pos);
+    for (int l = 0; l < cfg->n_text_layer; ++l) {
+        char* skv = st + L.self_kv + (size_t)l * 3 * slot;  // [3][B][nctx][d]: the query slot holds nothing a later step reads
+        hipLaunchKernelGGL(shift_rows_kernel, dim3(2 * B), dim3(256), 0, s, skv + slot, strip_bytes, row_bytes, pos, nctx, shift);  // K then V: 2 B strips
+    }
+    hipLaunchKernelGGL(shift_tokens_kernel, dim3(B), dim3(256), 0, s, (int32_t*)(st + L.tokens), L.ld_tok, pos, nctx, shift);
+    hipLaunchKernelGGL(shift_finish_kernel, dim3(1), dim3(256), 0, s, (int32_t*)(st + L.pos), (int64_t*)(st + L.scratch + dec_scratch(cfg, B).posd), d,
+                       starts_dev, B, nctx, shift);
+    WIPA_LAUNCH_CHECK();
     return WIPA_OK;
 }
 
