@@ -820,7 +820,8 @@ int wipa_decoder_run_ragged(const wipa_model_cfg* cfg, const void* const* weight
  *   p + 1 >= own + limit: column p + 1 takes eot, without a log-probability, and the EOT latch holds the row from there on.
  * The latch is the token of column p: a slot leaves it when an admission writes initial tokens over the finished row's last column.
  * Served: both cross-attention forms, bf16 / f32 decoder tables, one row per clip, 1..4 initial tokens.  Refused by name
- * (WIPA_ERR_ARG, nothing enqueued): fp8 tables, candidate groups, timestamp rules, a step without the fused tail.
+ * (WIPA_ERR_ARG, nothing enqueued): fp8 tables, candidate groups, a step without the fused tail; wipa_decoder_run_continuous also refuses
+ * timestamp rules, which wipa_decoder_run_continuous_rules serves.
  * wipa_decoder_admit_rows: in stream order, for row i of n_rows: features_host[i] (a DEVICE pointer to the clip's encoder output
  *   [n_audio_ctx, d] in cfg.dtype; the array of pointers is on the host) is copied into slot slots_host[i] of the blob's audio copy
  *   (absorbed form), or projected into the slot's K / V of every layer as wipa_decoder_set_audio projects it (cached form: n_text_layer
@@ -839,7 +840,20 @@ int wipa_decoder_run_ragged(const wipa_model_cfg* cfg, const void* const* weight
  *   same partition wherever that start lies, so a shift changes no bit of what a row computes.  Refused: shift outside
  *   1..n_text_ctx-1; a shift above the position is not carried out.
  * wipa_decoder_run_continuous: wipa_decoder_run_ragged with the CONTINUOUS tails and rules == NULL.  The step graph's key is that of
- *   wipa_decoder_run_ragged plus the variant; the replayed kernels read starts_dev, so admissions and shifts replay the same graph. */
+ *   wipa_decoder_run_ragged plus the variant; the replayed kernels read starts_dev, so admissions and shifts replay the same graph.
+ *   It refuses rules: the call with rules is the next one.
+ * wipa_decoder_run_continuous_rules: wipa_decoder_run_continuous with the timestamp rules; rules is required (NULL is refused by name).
+ *   The four cases per row stay.  The pick applies the rules to the row's OWN sequence, the tokens of columns own .. p: its length is
+ *   p + 1 - own, the pick at p + 1 == own is the first one (mask_first; text dead, timestamps capped by max_initial_timestamp_index), and
+ *   no token below own is looked at -- those are the slot's previous clip, which usually ended in timestamps, or the prompt.  A shift
+ *   moves the starts and the tokens together, so a pick cannot see it.  With a sampling record the draw's counter takes the row's own
+ *   position p - start[b], as in wipa_decoder_run_continuous.
+ *   no_speech_dev (float [B] on the device, caller-owned, may be NULL): at the step whose column is a row's first own one (p == start[b],
+ *   limit > 0: the row's <|startoftranscript|>, upstream's logits[:, sot_index]) the tail writes softmax(logits row)[no_speech_token] of
+ *   the UNFILTERED row to no_speech_dev[b], with a plain store; the value stays until the slot's next admission reaches that step.
+ *   The step graph's key is that of wipa_decoder_run_continuous plus the variant, the address of no_speech_dev and no_speech_token.  On
+ *   bf16 the logits projection writes the logits, as for wipa_decoder_run_rules.  Refused by name (WIPA_ERR_ARG, nothing enqueued):
+ *   rules == NULL, fp8 tables, candidate groups, a step without the fused tail, no_speech_token outside the vocabulary. */
 int wipa_decoder_admit_rows(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int n_rows,
                             const int32_t* slots_host,
                             const void* const* features_host, const int32_t* initial_tokens_host, int n_init, const int32_t* limits_host,
@@ -849,6 +863,10 @@ int wipa_decoder_shift_columns(const wipa_model_cfg* cfg, void* state, size_t st
 int wipa_decoder_run_continuous(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int n_init,
                                 int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
                                 const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, wipa_stream_t s);
+int wipa_decoder_run_continuous_rules(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B,
+                                      int n_init, int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
+                                      const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, float* no_speech_dev,
+                                      int no_speech_token, wipa_stream_t s);
 /* drop the cached step graphs that reference this state blob (call before freeing it). */
 int wipa_decoder_release(void* state);
 

@@ -141,18 +141,23 @@ BASE_DECODE_MODES = ("decode", "transcribe")
 
 
 def transcribe_files(model, audio_paths: List[str], batch_size: int = 64, progress=None, seed: Optional[int] = None,
-                     condition_on_previous_text: bool = False, initial_prompt: Optional[str] = None) -> List[str]:
+                     condition_on_previous_text: bool = False, initial_prompt: Optional[str] = None, schedule: str = "rounds") -> List[str]:
     """reference :112-119 for the whole list: ``mlx_whisper.transcribe(path, language="en", word_timestamps=False)["text"]`` per
     file through whisper_ipa_amd.transcribe, ``batch_size`` files per call (their windows decode as one batch per round).  One
     text per path, "" where the file could not be read.  ``seed``: run mlx_whisper.transcribe's temperature schedule on the windows
     that fail its thresholds (None: temperature 0 only, such windows are flagged).  ``condition_on_previous_text`` / ``initial_prompt``:
-    mlx_whisper.transcribe's options of those names (upstream defaults to conditioning on; here it is opt-in)."""
+    mlx_whisper.transcribe's options of those names (upstream defaults to conditioning on; here it is opt-in).
+    ``schedule="continuous"``: transcribe(schedule="continuous", slots=batch_size) -- the windows go through ``batch_size`` rows of one
+    decode state with refill, 8 x ``batch_size`` files per call (what bounds a call is the host memory of its samples, not its rows);
+    it serves temperature 0 without conditioning and refuses the rest by name."""
     from whisper_ipa_amd import transcribe
 
     texts = [""] * len(audio_paths)
-    for b in range(0, len(audio_paths), batch_size):
+    more = {"schedule": "continuous", "slots": batch_size} if schedule == "continuous" else {}
+    per_call = 8 * batch_size if schedule == "continuous" else batch_size
+    for b in range(0, len(audio_paths), per_call):
         clips, slots = [], []
-        for i, path in enumerate(audio_paths[b:b + batch_size]):
+        for i, path in enumerate(audio_paths[b:b + per_call]):
             try:
                 clips.append(np.asarray(load_audio(path), dtype=np.float32))
                 slots.append(b + i)
@@ -160,10 +165,10 @@ def transcribe_files(model, audio_paths: List[str], batch_size: int = 64, progre
                 print(f"\nError transcribing {path}: {e}")
         if clips:
             for i, r in zip(slots, transcribe(model, clips, language="en", word_timestamps=False, seed=seed,
-                                              condition_on_previous_text=condition_on_previous_text, initial_prompt=initial_prompt)):
+                                              condition_on_previous_text=condition_on_previous_text, initial_prompt=initial_prompt, **more)):
                 texts[i] = r["text"].strip()
         if progress is not None:
-            progress(min(b + batch_size, len(audio_paths)))
+            progress(min(b + per_call, len(audio_paths)))
     return texts
 
 
@@ -211,6 +216,7 @@ def evaluate_model(model_path: str, test_data_path: str, num_samples: Optional[i
     if base_decode == "transcribe" and not is_checkpoint:
         local_hyp = transcribe_files(model, [s["audio_path"] for s in mine], batch_size=batch_size, seed=seed,
                                      condition_on_previous_text=condition_on_previous_text, initial_prompt=initial_prompt,
+                                     schedule="continuous" if decode == "continuous" else "rounds",
                                      progress=lambda n: say(f"  {n}/{len(mine)} clips on rank 0", flush=True))
     elif decode == "continuous":
         local_hyp = transcribe_clips_continuous(model, [s["audio_path"] for s in mine], options, slots=batch_size, ingest=ingest,
@@ -302,7 +308,8 @@ def main(argv=None) -> Dict:
     ap.add_argument("--decode", choices=DECODE_MODES, default="lockstep",
                     help="how decode(without_timestamps=True) walks the clips: 'lockstep' = batches of --batch-size, each run until its "
                          "last row ends (default, as before); 'continuous' = whisper_ipa_amd.decode_continuous: --batch-size rows, and a "
-                         "row whose clip has ended takes the next clip (--passes-in-flight does not apply)")
+                         "row whose clip has ended takes the next clip (--passes-in-flight does not apply); with --base-decode "
+                         "transcribe the base leg runs transcribe(schedule='continuous', slots=--batch-size)")
     ap.add_argument("--seed", type=int, default=None,
                     help="with --base-decode transcribe: re-decode the windows that fail the compression-ratio / log-probability "
                          "thresholds at 0.2, 0.4, ... 1.0 as mlx_whisper.transcribe does, sampling reproducibly from this seed "

@@ -231,6 +231,8 @@ SIGNATURES = {
                                         c_int, _P(DecodeRules), c_void_p, c_void_p, c_void_p]),
     "wipa_decoder_run_continuous": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                             c_int, _P(DecodeRules), c_void_p, c_void_p, c_void_p]),
+    "wipa_decoder_run_continuous_rules": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                                  c_int, _P(DecodeRules), c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "wipa_decoder_admit_rows": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, _P(C.c_int32), _P(c_void_p), _P(C.c_int32), c_int,
                                         _P(C.c_int32), c_void_p, c_void_p, _P(C.c_uint32), c_void_p]),
     "wipa_decoder_shift_columns": (c_int, [_P(ModelCfg), c_void_p, c_size_t, c_int, c_void_p, c_int, c_void_p]),

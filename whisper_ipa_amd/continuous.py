@@ -11,6 +11,12 @@ counter nears the end of the table, all columns move down by the smallest start 
 
 The scheduler (``run_schedule``) is plain Python against a small stepper interface, so it is tested without a GPU; ``DeviceStepper`` is
 the stepper on the library.
+
+With ``without_timestamps=False`` the steps end in the CONTINUOUS tails with the timestamp rules (wipa_decoder_run_continuous_rules;
+DESIGN.md section 14): the rules run on every row's own sequence, from its own first column, and the tail leaves the row's no-speech
+probability at its <|startoftranscript|> column.  ``run_stream`` is the scheduler for clips that are not all known when the run starts
+-- the windows of files, of which ``transcribe(schedule="continuous")`` keeps one per file in flight (``stream_windows``); a check is
+one device-to-host copy (``DeviceStepper.snapshot``).
 """
 from __future__ import annotations
 
@@ -24,7 +30,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .decoding import (DecoderState, DecodingOptions, DecodingResult, Sampling, _mask, _suppress_lists, detect_language)
+from .decoding import (DecoderState, DecodingOptions, DecodingResult, Sampling, _mask, _suppress_lists, detect_language, timestamp_rules)
 from .runtime import on_stream, ptr, sptr, stream_id
 from .tokenizer import get_tokenizer
 
@@ -36,6 +42,8 @@ class ScheduleStats:
     shifts: List[int] = field(default_factory=list)  # the shift amounts, in order
     admissions: List[Tuple[int, int, int]] = field(default_factory=list)  # (slot, clip, column) in admission order
     retired: List[int] = field(default_factory=list)                      # clips in the order they were retired
+    groups: List[int] = field(default_factory=list)                       # run_stream: the sizes of the admitted groups, in order
+    live_rows: List[int] = field(default_factory=list)                    # run_stream: the live rows of every interval of check_every steps
 
 
 def default_column_limit(n_ctx: int, n_init: int, check_every: int) -> int:
@@ -115,6 +123,86 @@ def run_schedule(stepper, n_clips: int, slots: int, n_init: int, limits: Sequenc
     return stats
 
 
+def run_stream(stepper, source, slots: int, n_init: int, eot: int, n_ctx: int, check_every: int = 8,
+               column_limit: Optional[int] = None) -> ScheduleStats:
+    """``run_schedule`` for clips that are not all known when the run starts (the windows of files: a file's next window exists once its
+    previous one has retired).  The clips come from ``source`` and their results go back to it:
+
+      source.pending() -> [(clip, limit)]   the clips that are ready now, each returned once, in the order they take slots; asked at the
+                                            start and after every check (a retirement may have made more ready).  ``clip`` is any
+                                            hashable value; it may generate ``limit`` tokens
+      source.retired(clip, tokens, sum_logprob, no_speech)   the clip's generated tokens before its first ``eot`` (a list), its
+                                            log-probability sum and its no-speech probability, as host values, at the check that retires it
+
+      stepper.admit(triples)    [(slot, clip, limit)]: ONE call per check for all clips that start at the current column (a group)
+      stepper.run(n), stepper.shift(shift)   as for ``run_schedule``
+      stepper.snapshot() -> (tokens [slots, >= column + 1], sums [slots], no_speech [slots])   host arrays from ONE device-to-host copy
+                                            (this is where the host waits); everything a check retires is read from them
+
+    Clips beyond the free slots wait in a queue, in the order ``pending`` gave them.  The run ends when nothing is live and nothing is
+    pending."""
+    if slots < 1 or check_every < 1:
+        raise ValueError(f"decode_continuous: slots = {slots} and check_every = {check_every} must be positive")
+    if column_limit is None:
+        column_limit = default_column_limit(n_ctx, n_init, check_every)
+    if not column_limit + n_init < n_ctx:
+        raise ValueError(f"decode_continuous: column_limit = {column_limit} above {n_ctx - 1 - n_init} (n_text_ctx - 1 - n_init)")
+    stats = ScheduleStats()
+    queue: deque = deque()
+    live: Dict[int, Tuple[object, int, int]] = {}  # slot -> (clip, start, limit)
+    pos = 0
+
+    def admit_pending():
+        queue.extend(source.pending())
+        triples = []
+        for slot in range(slots):
+            if not queue:
+                break
+            if slot not in live:
+                clip, limit = queue.popleft()
+                limit = int(limit)
+                # the bound of run_schedule, per clip: after a shift the oldest live row starts at column 0 and the next interval must fit
+                need = n_init + limit + 2 * check_every - 1
+                if limit < 1 or need > column_limit:
+                    raise ValueError(f"decode_continuous: a clip's limit of {limit} tokens is outside 1 .. {column_limit - n_init - 2 * check_every + 1} "
+                                     f"(column_limit - n_init - 2 * check_every + 1)")
+                live[slot] = (clip, pos, limit)
+                triples.append((slot, clip, limit))
+                stats.admissions.append((slot, clip, pos))
+        if triples:
+            stepper.admit(triples)
+            stats.groups.append(len(triples))
+
+    admit_pending()
+    while live:
+        if pos + check_every > column_limit:
+            shift = min(start for _, start, _ in live.values())
+            assert shift > 0, "decode_continuous: a live row spans the whole column window (the shift would be 0)"
+            stepper.shift(shift)
+            stats.shifts.append(shift)
+            pos -= shift
+            live = {slot: (clip, start - shift, limit) for slot, (clip, start, limit) in live.items()}
+            assert pos + check_every <= column_limit
+        stats.live_rows.append(len(live))
+        stepper.run(check_every)
+        stats.steps += check_every
+        pos += check_every
+        tokens, sums, no_speech = stepper.snapshot()
+        for slot in sorted(live):
+            clip, start, limit = live[slot]
+            own = start + n_init
+            generated = pos - own + 1  # columns own .. pos
+            if generated >= 1 and (int(tokens[slot][pos]) == eot or generated >= limit):
+                row = [int(t) for t in tokens[slot][own:own + min(generated, limit)]]
+                if eot in row:
+                    row = row[: row.index(eot)]
+                source.retired(clip, row, float(sums[slot]), float(no_speech[slot]))
+                stats.retired.append(clip)
+                del live[slot]
+        admit_pending()
+    return stats
+
+
 def lockstep_steps(limits: Sequence[int], slots: int) -> int:
     """the generating steps a lockstep decode of the same clips takes: batches of ``slots`` in input order, each run to its longest row"""
     limits = [int(n) for n in limits]
@@ -137,7 +225,10 @@ class DeviceStepper:
     """``run_schedule``'s stepper on wipa_decoder_*: one decode state of ``slots`` rows, owned by the model per library stream."""
 
     def __init__(self, model, slots: int, features, initial, n_init: int, limits: Sequence[int], eot: int,
-                 suppress_always: Sequence[int], suppress_first: Sequence[int], sample: Optional[Sampling], s, use_graph: bool = True):
+                 suppress_always: Sequence[int], suppress_first: Sequence[int], sample: Optional[Sampling], s, use_graph: bool = True,
+                 rules: Optional["_lib.DecodeRules"] = None, no_speech_token: Optional[int] = None):
+        """``rules``: the timestamp rules (wipa_decoder_run_continuous_rules; None: wipa_decoder_run_continuous).  With them and
+        ``no_speech_token`` the step's tail leaves every row's no-speech probability in ``self.no_speech``"""
         self.L = _lib.lib()
         self.model, self.B, self.s, self.eot, self.use_graph = model, int(slots), s, int(eot), use_graph
         self.features = features  # clip -> device tensor [n_audio_ctx, d] in the model's dtype, contiguous
@@ -160,12 +251,20 @@ class DeviceStepper:
         if getattr(st, "_cont_starts", None) is None:  # ONE buffer per state: its address is part of the step graph's key
             st._cont_starts = torch.zeros(2 * self.B, dtype=torch.int32, device=model.device)
         self.starts = st._cont_starts
+        self.rules = rules
+        self.no_speech = None
+        if rules is not None and no_speech_token is not None:
+            if getattr(st, "_cont_no_speech", None) is None:  # ONE buffer per state, like the starts
+                st._cont_no_speech = torch.zeros(self.B, dtype=torch.float32, device=model.device)
+            self.no_speech = st._cont_no_speech
+        self.no_speech_token = int(no_speech_token) if no_speech_token is not None else 0
         self.m_always = _mask(model, suppress_always)
         self.m_first = _mask(model, list(suppress_always) + list(suppress_first))
         n = len(self.limits)
         self.width = max(self.limits, default=1)
         self.out_tokens = torch.full((max(n, 1), self.width), self.eot, dtype=torch.int32, device=model.device)
         self.out_sums = torch.zeros(max(n, 1), dtype=torch.float32, device=model.device)
+        self.out_no_speech = torch.full((max(n, 1),), float("nan"), dtype=torch.float32, device=model.device)
         self.pos = 0
         self._keep = []  # what enqueued work reads
         self._begin()
@@ -176,11 +275,16 @@ class DeviceStepper:
         _lib.check(L.wipa_decoder_begin(C.byref(pk["cfg"]), ptr(st.blob), st.blob.numel(), self.B, init, self.n_init, sptr(self.s)),
                    "wipa_decoder_begin")
         self.starts.zero_()
+        if self.no_speech is not None:
+            self.no_speech.fill_(float("nan"))
         self.rec = None
         if self.sample is not None:  # seed, attempt and temperature; the streams are written per admission
             self.rec = st.sample_record(Sampling(self.sample.seed, self.sample.temperature, None, self.sample.attempt))
 
     def admit(self, pairs):
+        """pairs [(slot, clip)] of ``run_schedule`` (the clip's limit is ``limits[clip]``), or triples [(slot, clip, limit)] of ``run_stream``"""
+        limits = [int(t[2]) if len(t) > 2 else self.limits[t[1]] for t in pairs]
+        pairs = [(t[0], t[1]) for t in pairs]
         n = len(pairs)
         slots = (C.c_int32 * n)(*[slot for slot, _ in pairs])
         feats = [self.features(clip) for _, clip in pairs]
@@ -189,7 +293,7 @@ class DeviceStepper:
         rows = [[int(t) for t in self.initial(clip)] for _, clip in pairs]
         assert all(len(r) == self.n_init for r in rows)
         init = (C.c_int32 * (n * self.n_init))(*[t for r in rows for t in r])
-        lim = (C.c_int32 * n)(*[self.limits[clip] for _, clip in pairs])
+        lim = (C.c_int32 * n)(*limits)
         streams = None
         if self.sample is not None:
             own = self.sample.streams
@@ -202,6 +306,14 @@ class DeviceStepper:
 
     def run(self, n: int):
         pk, st = self.pk, self.st
+        if self.rules is not None:
+            _lib.check(self.L.wipa_decoder_run_continuous_rules(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), self.B, self.n_init,
+                                                                self.eot, ptr(self.m_first), ptr(self.m_always), n, int(self.use_graph),
+                                                                C.byref(self.rules), ptr(self.rec) if self.rec is not None else None,
+                                                                ptr(self.starts), ptr(self.no_speech) if self.no_speech is not None else None,
+                                                                self.no_speech_token, sptr(self.s)), "wipa_decoder_run_continuous_rules")
+            self.pos += n
+            return
         _lib.check(self.L.wipa_decoder_run_continuous(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), self.B, self.n_init,
                                                       self.eot, ptr(self.m_first), ptr(self.m_always), n, int(self.use_graph), None,
                                                       ptr(self.rec) if self.rec is not None else None, ptr(self.starts), sptr(self.s)),
@@ -214,6 +326,16 @@ class DeviceStepper:
     def retire(self, slot: int, clip: int, first_column: int, n_columns: int):
         self.out_tokens[clip, :n_columns].copy_(self.st.tokens[slot, first_column:first_column + n_columns])
         self.out_sums[clip].copy_(self.st.sum_logprobs[slot])
+        if self.no_speech is not None:
+            self.out_no_speech[clip].copy_(self.no_speech[slot])
+
+    def snapshot(self):
+        """``run_stream``'s check: (tokens [slots, column + 1], sums [slots], no_speech [slots]) on the host from ONE device-to-host copy
+        (the three are packed into one int32 buffer on the device first); synchronises the library stream"""
+        B, n = self.B, self.pos + 1
+        nsp = self.no_speech if self.no_speech is not None else torch.full((B,), float("nan"), dtype=torch.float32, device=self.model.device)
+        host = torch.cat([self.st.tokens[:, :n].reshape(-1), self.st.sum_logprobs.view(torch.int32), nsp.view(torch.int32)]).cpu().numpy()
+        return host[: B * n].reshape(B, n), host[B * n: B * n + B].view(np.float32), host[B * n + B:].view(np.float32)
 
     def shift(self, shift: int):
         pk, st = self.pk, self.st
@@ -236,9 +358,10 @@ def _layout_key(pk, B: int) -> tuple:
 
 
 # ---------------------------------------------------------------- the public entry point
-def refuse_unserved(model, options: DecodingOptions) -> None:
-    """what ``decode_continuous`` does not serve, each refused by the option's name"""
-    if not options.without_timestamps:
+def refuse_unserved(model, options: DecodingOptions, timestamps: bool = False) -> None:
+    """what a continuous decode does not serve, each refused by the option's name.  ``timestamps``: the caller serves
+    ``without_timestamps=False`` (``decode_continuous`` does, on wipa_decoder_run_continuous_rules)"""
+    if not options.without_timestamps and not timestamps:
         raise NotImplementedError("decode_continuous: without_timestamps=False is not implemented (the timestamp rules scan a row from a "
                                   "common first column); pass without_timestamps=True")
     for name in ("prompt", "prefix", "prompts"):
@@ -302,6 +425,66 @@ class _Features:
         return self.chunks[k][clip - k * self.chunk]
 
 
+class _GroupStepper(DeviceStepper):
+    """``run_stream``'s stepper for ``transcribe(schedule="continuous")``: an admitted group's windows go through ONE log-mel call, ONE
+    encoder call and ONE detect_language call (the windows of files whose language is still unknown), then ONE admission"""
+
+    def __init__(self, model, slots: int, source, options: DecodingOptions, tok, base, always, first, rules, s):
+        self.source, self.options, self.tok, self.base = source, options, tok, list(base)
+        self._feat: Dict[object, torch.Tensor] = {}
+        self._init: Dict[object, List[int]] = {}
+        super().__init__(model, slots, self._feat.pop, self._init.pop, len(base), [], tok.eot, always, first, None, s, rules=rules,
+                         no_speech_token=tok.no_speech)
+
+    def admit(self, triples):
+        from . import audio as A
+        from .tokenizer import LANGUAGES
+
+        clips = [clip for _, clip, _ in triples]
+        windows, languages = self.source.group(clips)
+        model = self.model
+        dev_audio = torch.from_numpy(np.ascontiguousarray(windows)).to(model.device)
+        feats = model.embed_audio(A.log_mel_spectrogram(dev_audio, n_mels=model.dims.n_mels))
+        if self.options.fp16 and model.dtype == torch.float32:  # DecodingOptions.fp16: as decode() rounds the features
+            feats = feats.to(torch.float16).to(torch.float32)
+        feats = feats.to(device=model.device, dtype=model.dtype).contiguous()
+        unknown = [j for j, lang in enumerate(languages) if lang is None]
+        if unknown:
+            lang_tokens, _ = detect_language(model, feats[unknown] if len(unknown) != len(clips) else feats, self.tok)
+            found = [LANGUAGES[int(t) - self.tok.sot - 1] for t in lang_tokens]
+            self.source.detected([clips[j] for j in unknown], found)
+            for j, lang in zip(unknown, found):
+                languages[j] = lang
+        for j, clip in enumerate(clips):
+            row = list(self.base)
+            row[1] = self.tok.to_language_token(languages[j])
+            self._feat[clip], self._init[clip] = feats[j], row
+        super().admit(triples)
+
+    def snapshot(self):
+        out = super().snapshot()
+        self._keep.clear()  # the stream has been waited for: every admission's copy of its features is done
+        return out
+
+
+def stream_windows(model, source, decode_options: dict, slots: int, check_every: int = 8,
+                   column_limit: Optional[int] = None) -> ScheduleStats:
+    """The model's continuous decoder for ``transcribe(schedule="continuous")``: ``run_stream`` over ``source`` (transcribe._WindowSource:
+    ``pending`` / ``retired`` of ``run_stream``, plus ``group(clips)`` -> (samples [n, 480000], languages) and ``detected(clips, languages)``)
+    on ``slots`` rows, with timestamps, at temperature 0"""
+    options = DecodingOptions(**{**decode_options, "without_timestamps": False, "temperature": 0.0})
+    refuse_unserved(model, options, timestamps=True)
+    tok = get_tokenizer(model.is_multilingual, num_languages=model.num_languages, language=options.language or "en", task=options.task)
+    always, first = _suppress_lists(options, tok)
+    rules = timestamp_rules(tok, options.max_initial_timestamp)
+    base = list(tok.sot_sequence)
+    with on_stream() as s:
+        stepper = _GroupStepper(model, slots, source, options, tok, base, always, first, rules, s)
+        stats = run_stream(stepper, source, slots, len(base), tok.eot, model.dims.n_text_ctx, check_every, column_limit)
+        stepper._keep.clear()
+    return stats
+
+
 def decode_continuous(model, mels_or_features: torch.Tensor, options: DecodingOptions = DecodingOptions(without_timestamps=True),
                       slots: int = 64, sample_lens: Optional[Sequence[int]] = None, check_every: int = 8,
                       column_limit: Optional[int] = None, stats_out: Optional[list] = None) -> List[DecodingResult]:
@@ -309,8 +492,10 @@ def decode_continuous(model, mels_or_features: torch.Tensor, options: DecodingOp
     results in input order.  ``sample_lens``: the tokens clip i may generate (default ``options.sample_len`` or n_text_ctx // 2 for
     every clip).  Served: greedy, and ``temperature > 0`` with ``seed`` -- clip i draws from ``options.sample_streams[i]`` or from
     stream (i, 0), whichever slot it lands in and whenever it is admitted.  ``language=None`` detects the language (and fills
-    ``no_speech_prob``) per encoded chunk of ``slots`` clips.  ``stats_out``: a list that receives the run's ``ScheduleStats``."""
-    refuse_unserved(model, options)
+    ``no_speech_prob``) per encoded chunk of ``slots`` clips.  ``stats_out``: a list that receives the run's ``ScheduleStats``.
+    ``without_timestamps=False``: the initial tokens are ``sot_sequence``, the timestamp rules of ``decode()`` run on every row's own
+    sequence, and ``no_speech_prob`` is what the step's tail left at the row's <|startoftranscript|> column."""
+    refuse_unserved(model, options, timestamps=True)
     x = mels_or_features
     if x.dim() != 3:
         raise ValueError("decode_continuous: mels [N, 3000, n_mels] or features [N, n_audio_ctx, d]")
@@ -326,7 +511,9 @@ def decode_continuous(model, mels_or_features: torch.Tensor, options: DecodingOp
             stats_out.append(ScheduleStats())
         return []
     always, first = _suppress_lists(options, tok)
-    base = list(tok.sot_sequence_including_notimestamps)
+    timed = not options.without_timestamps
+    rules = timestamp_rules(tok, options.max_initial_timestamp) if timed else None
+    base = list(tok.sot_sequence) if timed else list(tok.sot_sequence_including_notimestamps)
     sample = None
     if options.temperature != 0.0:
         streams = [(int(a), int(b)) for a, b in options.sample_streams] if options.sample_streams is not None else [(i, 0) for i in range(N)]
@@ -343,8 +530,10 @@ def decode_continuous(model, mels_or_features: torch.Tensor, options: DecodingOp
         return row
 
     with on_stream() as s:
-        stepper = DeviceStepper(model, slots, feats, initial, len(base), limits, tok.eot, always, first, sample, s)
+        stepper = DeviceStepper(model, slots, feats, initial, len(base), limits, tok.eot, always, first, sample, s, rules=rules,
+                                no_speech_token=tok.no_speech if timed else None)
         stats = run_schedule(stepper, N, slots, len(base), limits, tok.eot, d.n_text_ctx, check_every, column_limit)
+        tail_no_speech = stepper.out_no_speech.cpu().numpy() if timed else None
         toks, sums = stepper.results()
     if stats_out is not None:
         stats_out.append(stats)
@@ -363,5 +552,5 @@ def decode_continuous(model, mels_or_features: torch.Tensor, options: DecodingOp
         # the features the caller gave; those encoded here are dropped chunk by chunk once their clips are admitted
         results.append(DecodingResult(audio_features=x[i] if feats.encoded else None, language=lang, language_probs=feats.lang_probs.get(i), tokens=row, text=text,
                                       avg_logprob=float(sums[i]) / (len(row) + 1), temperature=options.temperature, compression_ratio=comp,
-                                      no_speech_prob=feats.no_speech.get(i, float("nan"))))
+                                      no_speech_prob=float(tail_no_speech[i]) if timed else feats.no_speech.get(i, float("nan"))))
     return results

@@ -913,6 +913,76 @@ __global__ __launch_bounds__(GS_THREADS) void sample_tail_continuous_kernel(Tail
     tail_finish<TO>(q, p, next, s_red);
 }
 
+// The CONTINUOUS tails with the timestamp rules (wipa_decoder_run_continuous_rules).  The four cases above stay; the pick is
+// row_pick<true, SAMPLE> on the row's OWN sequence tk[own .. p]: row_pick's n_init argument is nothing but the first column of the sequence
+// it scans, so `own` in its place states the rule -- len = p + 1 - own, the pick is "first" (text dead, timestamps capped) when p + 1 == own,
+// and no token below own is looked at: those belong to the slot's previous clip, which usually ended in timestamps, or to the prompt.  A
+// column shift moves start and the tokens together, so own moves with the sequence and the pick cannot see it.
+// The no-speech probability: at the step whose column is the row's <|startoftranscript|> (p == start[b], limit > 0) the logits row is
+// upstream's logits[:, sot_index]; softmax(row)[no_speech_token] of the UNFILTERED row goes to no_speech[b] -- row_scan_reg's loads and
+// reduction order without the mask, a plain store by thread 0.  With n_init == 1 the same step also picks: the scan's LDS slots are free
+// again once every thread has left block_sum's barrier, and row_pick writes s_sum only behind a barrier of its own.
+__device__ __forceinline__ void row_no_speech(const float* __restrict__ row, int V, int token, float* __restrict__ out, float* s_v, int* s_i,
+                                              float* s_sum) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nq = V >> 2;
+    f32x4 vals[GS_MAXQ];
+#pragma unroll
+    for (int j = 0; j < GS_MAXQ; ++j) {
+        const int qi = tid + j * GS_THREADS;
+        vals[j] = qi < nq ? *reinterpret_cast<const f32x4*>(row + 4 * qi) : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    }
+    const int ti = 4 * nq + tid;  // the (V mod 4) trailing elements
+    const bool has_tail = tid < 4 && ti < V;
+    const float tailv = has_tail ? row[ti] : -INFINITY;
+    MaxIdx m{tailv, has_tail ? ti : 0x7fffffff};
+#pragma unroll
+    for (int j = 0; j < GS_MAXQ; ++j) {
+        const int qi = tid + j * GS_THREADS;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) m = better(m, MaxIdx{vals[j][e], qi < nq ? 4 * qi + e : 0x7fffffff});
+    }
+    const MaxIdx bm = block_argmax(m, lane, wave, s_v, s_i);
+    float se = __expf(tailv - bm.v);
+#pragma unroll
+    for (int j = 0; j < GS_MAXQ; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) se += __expf(vals[j][e] - bm.v);
+    const float tot = block_sum(se, lane, wave, s_sum);
+    if (tid == 0) *out = __expf(row[token] - bm.v) / tot;
+}
+
+template <typename TO, bool SAMPLE>
+__global__ __launch_bounds__(GS_THREADS) void rules_tail_continuous_kernel(TailArgs<true> q, RulesDev rules, const uint32_t* __restrict__ rec,
+                                                                           float* __restrict__ no_speech, int no_speech_token) {
+    __shared__ float s_v[2 * GS_WAVES];
+    __shared__ int s_i[2 * GS_WAVES];
+    __shared__ float s_sum[2 * GS_WAVES];
+    __shared__ float s_red[4];
+    const int b = blockIdx.x;
+    const int p = tail_pos(q.pos);
+    if (p + 1 >= q.n_ctx) return;
+    const ContinuousRow r = continuous_row(q, b);
+    int32_t* tk = q.tokens + (int64_t)b * q.ld_tok;
+    const float* row = q.logits + (int64_t)b * q.ldl;
+    if (no_speech && r.limit > 0 && p + q.n_init == r.own) {  // p == start[b]; uniform over the workgroup
+        row_no_speech(row, q.V, no_speech_token, no_speech + b, s_v, s_i, s_sum);
+        __syncthreads();
+    }
+    int next;
+    if (p + 1 < r.own) {
+        next = tk[p + 1];
+    } else if (p + 1 >= r.own + r.limit) {
+        next = q.eot;
+        if (threadIdx.x == 0) tk[p + 1] = next;
+    } else {
+        const float* mask = (p + 1 == r.own) ? q.mask_first : q.mask_always;
+        const RowPick pick = row_pick<true, SAMPLE>(row, mask, q.V, tk, p, r.own, q.eot, rules, s_v, s_i, s_sum, rec, b, max(p - q.start[b], 0));
+        next = commit(tk + p, q.eot, pick.next, pick.logprob, q.sum_logprobs + b, q.not_done);
+    }
+    tail_finish<TO>(q, p, next, s_red);
+}
+
 // wipa_sample_noise: g_c of one (row, position), c < V -- the numbers the sampling tails add, for measurement
 __global__ __launch_bounds__(256) void sample_noise_kernel(const uint32_t* __restrict__ rec, int row, int p, int V, float* __restrict__ out) {
     const int qi = blockIdx.x * 256 + threadIdx.x;
@@ -1382,14 +1452,15 @@ extern "C" int wipa_step_embed_ragged(const float* logits, int64_t ldl, int B, i
                           starts_dev, sum_logprobs, not_done, tok_emb, emb_dtype, emb_scale, pos_emb, n_ctx, x, ln_w, ln_b, y, y_dtype, D, eps, stream);
 }
 
-// the CONTINUOUS tails (declared in wipa_common.h for wipa_decoder_run_continuous; not exported): the checks of wipa_step_tail without
-// rules; starts_dev is int32 [2][B], the rows' first own columns and then the tokens each may generate
-int wipa_step_tail_continuous(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always, int32_t* tokens,
-                              int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init, int eot, const void* sample,
-                              const int32_t* starts_dev, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
-                              const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y,
-                              int y_dtype, int D, float eps, wipa_stream_t stream) {
-    const char* who = "wipa_decoder_run_continuous";
+// the CONTINUOUS tails (declared in wipa_common.h for wipa_decoder_run_continuous / _rules; not exported): the checks of wipa_step_tail;
+// starts_dev is int32 [2][B], the rows' first own columns and then the tokens each may generate.  With rules the tails are the
+// rules_tail_continuous kernels, and no_speech_dev (float [B], may be NULL) receives softmax(row)[no_speech_token] at a row's first column.
+static int step_tail_continuous(const char* who, const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
+                                int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init, int eot,
+                                const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, float* no_speech_dev,
+                                int no_speech_token, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
+                                const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y,
+                                int y_dtype, int D, float eps, wipa_stream_t stream) {
     WIPA_REQUIRE(logits && mask_first && mask_always && tokens && pos_dev && posd_dev && done_counter && sum_logprobs && not_done && tok_emb &&
                      pos_emb && x && ln_w && ln_b && y && starts_dev && B > 0 && n_ctx > 0 && n_init >= 1 && ld_tok >= n_ctx,
                  "%s: bad arguments of the step's tail (starts_dev is required)", who);
@@ -1399,11 +1470,13 @@ int wipa_step_tail_continuous(const float* logits, int64_t ldl, int B, int V, co
     WIPA_REQUIRE(tp.emb_dtype == WIPA_F32 || tp.emb_dtype == WIPA_BF16, "%s: bad embedding dtype %d", who, tp.emb_dtype);
     WIPA_REQUIRE(reg_scan_ok(tp.logits, tp.V, tp.ldl, tp.mask_first, tp.mask_always), "%s: vocabulary of %d / unaligned logits or masks", who, tp.V);
     WIPA_REQUIRE(y_dtype == WIPA_F32 || y_dtype == WIPA_BF16, "%s: bad dtype %d", who, y_dtype);
-    if (sample) {
-        RulesDev r = {tp.V, -1, -1};
-        const int rc = sample_check(who, nullptr, sample, tp.logits, tp.V, tp.ldl, tp.mask_first, tp.mask_always, tp.eot, tp.n_ctx, &r);
-        if (rc != WIPA_OK) return rc;
-    }
+    RulesDev r = {tp.V, -1, -1};
+    int rc = WIPA_OK;
+    if (sample) rc = sample_check(who, rules, sample, tp.logits, tp.V, tp.ldl, tp.mask_first, tp.mask_always, tp.eot, tp.n_ctx, &r);
+    else if (rules) rc = rules_check(who, rules, tp.logits, tp.V, tp.ldl, tp.mask_first, tp.mask_always, tp.eot, &r);
+    if (rc != WIPA_OK) return rc;
+    WIPA_REQUIRE(!no_speech_dev || (rules && no_speech_token >= 0 && no_speech_token < V), "%s: no_speech_token=%d outside the vocabulary of %d", who,
+                 no_speech_token, V);
     TailArgs<true> q = {};
     static_cast<TailParams&>(q) = tp;
     q.start = starts_dev;
@@ -1411,12 +1484,40 @@ int wipa_step_tail_continuous(const float* logits, int64_t ldl, int B, int V, co
     hipStream_t s = (hipStream_t)stream;
     const uint32_t* rec = (const uint32_t*)sample;
     const bool f32 = y_dtype == WIPA_F32;
-    if (rec && f32) hipLaunchKernelGGL((sample_tail_continuous_kernel<float>), grid, block, 0, s, q, rec);
+    if (rules) {
+        if (rec && f32) hipLaunchKernelGGL((rules_tail_continuous_kernel<float, true>), grid, block, 0, s, q, r, rec, no_speech_dev, no_speech_token);
+        else if (rec) hipLaunchKernelGGL((rules_tail_continuous_kernel<__bf16, true>), grid, block, 0, s, q, r, rec, no_speech_dev, no_speech_token);
+        else if (f32) hipLaunchKernelGGL((rules_tail_continuous_kernel<float, false>), grid, block, 0, s, q, r, rec, no_speech_dev, no_speech_token);
+        else hipLaunchKernelGGL((rules_tail_continuous_kernel<__bf16, false>), grid, block, 0, s, q, r, rec, no_speech_dev, no_speech_token);
+    } else if (rec && f32) hipLaunchKernelGGL((sample_tail_continuous_kernel<float>), grid, block, 0, s, q, rec);
     else if (rec) hipLaunchKernelGGL((sample_tail_continuous_kernel<__bf16>), grid, block, 0, s, q, rec);
     else if (f32) hipLaunchKernelGGL((greedy_tail_continuous_kernel<float>), grid, block, 0, s, q);
     else hipLaunchKernelGGL((greedy_tail_continuous_kernel<__bf16>), grid, block, 0, s, q);
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;
+}
+
+int wipa_step_tail_continuous(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always, int32_t* tokens,
+                              int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init, int eot, const void* sample,
+                              const int32_t* starts_dev, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
+                              const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y,
+                              int y_dtype, int D, float eps, wipa_stream_t stream) {
+    return step_tail_continuous("wipa_decoder_run_continuous", logits, ldl, B, V, mask_first, mask_always, tokens, ld_tok, pos_dev, posd_dev,
+                                done_counter, n_init, eot, nullptr, sample, starts_dev, nullptr, 0, sum_logprobs, not_done, tok_emb, emb_dtype, emb_scale,
+                                pos_emb, n_ctx, x, ln_w, ln_b, y, y_dtype, D, eps, stream);
+}
+
+int wipa_step_tail_continuous_rules(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
+                                    int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init, int eot,
+                                    const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, float* no_speech_dev,
+                                    int no_speech_token, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
+                                    const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y,
+                                    int y_dtype, int D, float eps, wipa_stream_t stream) {
+    const char* who = "wipa_decoder_run_continuous_rules";
+    WIPA_REQUIRE(rules, "%s: rules is required (without rules the call is wipa_decoder_run_continuous)", who);
+    return step_tail_continuous(who, logits, ldl, B, V, mask_first, mask_always, tokens, ld_tok, pos_dev, posd_dev, done_counter, n_init, eot, rules,
+                                sample, starts_dev, no_speech_dev, no_speech_token, sum_logprobs, not_done, tok_emb, emb_dtype, emb_scale, pos_emb,
+                                n_ctx, x, ln_w, ln_b, y, y_dtype, D, eps, stream);
 }
 
 // the tail on wipa_logits_greedy's per-wave partials: no logits, so no rules, no draw and no ragged rows

@@ -31,12 +31,21 @@ What differs from upstream, on purpose:
     changes nothing) and the rows of a round carry their OWN prompts, of different lengths, through ``decode(prompts=...)``: the
     ragged decode of decoding.py.  One deviation comes with batching (decoding.py's docstring): ``sample_len`` is clamped to
     ``n_text_ctx`` minus the round's common prompt width, so a window next to one with a full 223-token history generates at most
-    221 tokens, not 224.
+    221 tokens, not 224;
+  * ``schedule="continuous"`` (the default is ``"rounds"``, everything above): the windows go through ``min(slots, files)`` rows of ONE
+    decode state with refill (continuous.py) instead of one lockstep batch per round.  A file is a stream of
+    windows with at most one in flight; files take places in input order and wait beyond ``slots``; the windows that become ready at
+    the same check share one log-mel, one encoder, one language-detection and one admission call.  The per-window bookkeeping
+    (``_Books.window``) is the rounds schedule's.  Temperature 0 only: ``seed``, ``word_timestamps``, conditioning, ``best_of``, a
+    custom ``decode_fn`` and fp8 models are refused by name.
 """
 from __future__ import annotations
 
 import inspect
 import warnings
+import zlib
+from collections import deque
+from dataclasses import dataclass, field
 from typing import Callable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -223,6 +232,196 @@ def _needs_fallback(res, compression_ratio_threshold, logprob_threshold, no_spee
     return needs_fallback
 
 
+def _window_samples(clip: np.ndarray, seek: int, size: int) -> np.ndarray:
+    """pad_or_trim of the window's own samples: ``size`` content frames from mel frame ``seek`` on, zero-padded to 30 s"""
+    out = np.zeros(N_SAMPLES, dtype=np.float32)
+    s0 = seek * HOP_LENGTH
+    chunk = clip[s0:s0 + size * HOP_LENGTH]
+    out[:len(chunk)] = chunk
+    return out
+
+
+# ---------------------------------------------------------------- schedule="continuous"
+def _refuse_continuous(model, seed, word_timestamps, condition_on_previous_text, initial_prompt, best_of, decode_fn) -> None:
+    """what ``schedule="continuous"`` does not serve, each refused by the option's name before anything is decoded"""
+    def no(name, why):
+        raise NotImplementedError(f"transcribe(schedule='continuous'): {name} is not implemented ({why}); use schedule='rounds'")
+
+    if seed is not None:
+        no("seed", "the retries need a temperature per row, which the sampling record of a decode state does not hold")
+    if word_timestamps:
+        no("word_timestamps", "the alignment runs on a round's windows")
+    if condition_on_previous_text:
+        no("condition_on_previous_text", "the continuous step takes the same number of initial tokens for every row")
+    if initial_prompt is not None:
+        no("initial_prompt", "the continuous step takes the same number of initial tokens for every row")
+    if best_of is not None:
+        no("best_of", "candidate groups are drawn by the retries")
+    if decode_fn is not None:
+        no("decode_fn", "a custom decoder decodes whole batches; the continuous schedule's seam is stream_fn")
+    if getattr(model, "_fp8", None):
+        no("an fp8-quantised model", "the continuous step runs on bf16 / f32 decoder tables")
+
+
+@dataclass
+class StreamStats:
+    """what a ``schedule="continuous"`` run did"""
+    schedule: object = None                                   # what the stream returned: the run's continuous.ScheduleStats
+    rows: int = 0                                             # rows of the decode state: min(slots, files)
+    waited: List[int] = field(default_factory=list)           # the files that queued for a slot, in the order they got one
+    groups: List[List[Tuple[int, int]]] = field(default_factory=list)     # per admitted group: its windows (file, seek)
+    detected: List[List[Tuple[int, int]]] = field(default_factory=list)   # per detect_language call: the windows it looked at
+
+
+@dataclass
+class _WindowResult:
+    tokens: List[int]
+    avg_logprob: float
+    no_speech_prob: float
+    compression_ratio: float
+    temperature: float
+    language: Optional[str]
+
+
+class _WindowSource:
+    """``continuous.run_stream``'s source over the files of one ``transcribe`` call.  A file is a stream of windows with at most one in
+    flight: its next window, the clip ``(file, seek)``, exists once the previous one has retired and ``books`` knows the seek.  Files
+    take a place in input order, at most ``slots`` of them at a time, and keep it until their last window has retired; the others wait."""
+
+    def __init__(self, clips, content_frames, books: _Books, slots: int, limit: int, stats: StreamStats):
+        self.clips, self.content_frames, self.books, self.limit, self.stats = clips, content_frames, books, int(limit), stats
+        self.slots = int(slots)
+        self.waiting = deque(i for i in range(len(clips)) if content_frames[i] > 0)
+        self.active: List[int] = []    # files that hold a place, in the order they got it
+        self.ready: List[int] = []     # active files whose next window has not been handed out
+        self.size = {}                 # (file, seek) -> content frames of the window in flight
+        self.first = True
+
+    def pending(self):
+        while self.waiting and len(self.active) < self.slots:
+            i = self.waiting.popleft()
+            self.active.append(i)
+            self.ready.append(i)
+            if not self.first:
+                self.stats.waited.append(i)
+        self.first = False
+        out = []
+        for i in self.ready:
+            clip = (i, self.books.seek[i])
+            self.size[clip] = min(N_FRAMES, self.content_frames[i] - self.books.seek[i])
+            out.append((clip, self.limit))
+        self.ready = []
+        return out
+
+    def group(self, clips):
+        """the windows of one admitted group: (samples [n, 480000] f32, the files' languages, None where still unknown)"""
+        self.stats.groups.append([tuple(c) for c in clips])
+        windows = np.stack([_window_samples(self.clips[i], at, self.size[(i, at)]) for i, at in clips])
+        return windows, [self.books.languages[i] for i, _ in clips]
+
+    def detected(self, clips, languages):
+        """the one detect_language call of a group told the languages of these windows' files"""
+        self.stats.detected.append([tuple(c) for c in clips])
+        for (i, _), lang in zip(clips, languages):
+            self.books.languages[i] = lang
+
+    def retired(self, clip, tokens, sum_logprob, no_speech):
+        i, at = clip
+        assert at == self.books.seek[i], "a file has one window in flight"
+        tok = self.books.tok
+        tokens = [int(t) for t in tokens]
+        text = tok.decode([t for t in tokens if t < self.books.tb]).strip()
+        comp = len(text.encode("utf-8")) / max(len(zlib.compress(text.encode("utf-8"))), 1) if text else float("nan")
+        res = _WindowResult(tokens, float(sum_logprob) / (len(tokens) + 1), float(no_speech), comp, 0.0, self.books.languages[i])
+        self.books.window(i, self.size.pop(clip), res, False)
+        if self.books.seek[i] < self.content_frames[i]:
+            self.ready.append(i)
+        else:
+            self.active.remove(i)
+
+
+def _transcribe_continuous(model, clips, content_frames, books: _Books, language, decode_options, stream_fn, slots: int,
+                           check_every: int) -> StreamStats:
+    """``transcribe(schedule="continuous")``: every window of every file through min(slots, files) rows of one decode state.  The windows
+    that become ready at the same check form one group: one log-mel call from the windows' own samples, one encoder call, one
+    detect_language call for the windows of files whose language is still unknown, one admission."""
+    if slots < 1 or check_every < 1:
+        raise ValueError(f"transcribe: slots = {slots} and check_every = {check_every} must be positive")
+    stats = StreamStats(rows=max(min(int(slots), len(clips)), 1))
+    n_text_ctx = model.dims.n_text_ctx if model is not None else 448
+    limit = decode_options.get("sample_len") or n_text_ctx // 2
+    source = _WindowSource(clips, content_frames, books, stats.rows, limit, stats)
+    if stream_fn is None:
+        from .continuous import stream_windows
+
+        def stream_fn(source, slots, check_every):
+            return stream_windows(model, source, {**decode_options, "language": language}, slots=slots, check_every=check_every)
+
+    stats.schedule = stream_fn(source, slots=stats.rows, check_every=check_every)
+    return stats
+
+
+class _Books:
+    """The per-file state of a ``transcribe`` call and the bookkeeping of ONE decoded window, which both schedules share: the no-speech
+    skip, ``split_segments``, the seek advance, the segment dicts, ``needs_fallback`` and upstream's prompt bookkeeping."""
+
+    def __init__(self, tok, n: int, language, initial_ids, thresholds, condition_on_previous_text: bool):
+        self.tok, self.tb = tok, int(tok.timestamp_begin)
+        self.compression_ratio_threshold, self.logprob_threshold, self.no_speech_threshold = thresholds
+        self.condition_on_previous_text = condition_on_previous_text
+        self.seek = [0] * n
+        self.languages: List[Optional[str]] = [language] * n
+        self.all_segments: List[List[dict]] = [[] for _ in range(n)]
+        # upstream's prompt bookkeeping, per file: all_tokens starts with the initial prompt, the next window's prompt is what came after
+        # prompt_reset_since
+        self.all_tokens: List[List[int]] = [list(initial_ids) for _ in range(n)]
+        self.prompt_reset_since = [0] * n
+        self.warned = False
+
+    def window(self, i: int, size: int, res, retried: bool):
+        """file i's window of ``size`` content frames at ``seek[i]`` was decoded to ``res``.  Returns None for a skipped window, else
+        (the window's new segments, its time offset, the segments' decoded tokens) -- what the word alignment needs"""
+        tok = self.tok
+        if self.languages[i] is None:
+            self.languages[i] = res.language  # detected on the file's first window, kept for the rest
+        time_offset = self.seek[i] * HOP_LENGTH / SAMPLE_RATE
+        tokens = [int(t) for t in res.tokens]
+        if self.no_speech_threshold is not None:
+            skip = res.no_speech_prob > self.no_speech_threshold
+            if self.logprob_threshold is not None and res.avg_logprob > self.logprob_threshold:
+                skip = False  # a confident transcript overrides the no-speech probability
+            if skip:
+                self.seek[i] += size
+                return None
+        needs_fallback = not retried and _needs_fallback(res, self.compression_ratio_threshold, self.logprob_threshold, self.no_speech_threshold)
+        if needs_fallback and not self.warned:
+            warnings.warn("whisper_ipa_amd.transcribe: a window failed compression_ratio_threshold / logprob_threshold; upstream would "
+                          "retry at a higher temperature, this path runs temperature 0 only (segments carry needs_fallback=True)",
+                          RuntimeWarning, stacklevel=3)
+            self.warned = True
+        at = self.seek[i]
+        segs, advance = split_segments(tokens, self.tb, time_offset, size)
+        self.seek[i] += advance
+        first_new = len(self.all_segments[i])
+        decoded_tokens = [list(sg["tokens"]) for sg in segs]  # the alignment sees what was decoded, emptied segments included
+        for sg in segs:
+            text = tok.decode([t for t in sg["tokens"] if t < tok.eot])
+            if sg["start"] == sg["end"] or text.strip() == "":
+                text, sg["tokens"] = "", []
+            seg = {"id": len(self.all_segments[i]), "seek": at, "start": sg["start"], "end": sg["end"], "text": text, "tokens": sg["tokens"],
+                   "temperature": res.temperature, "avg_logprob": res.avg_logprob, "compression_ratio": res.compression_ratio,
+                   "no_speech_prob": res.no_speech_prob}
+            if needs_fallback:
+                seg["needs_fallback"] = True
+            self.all_segments[i].append(seg)
+            self.all_tokens[i].extend(sg["tokens"])
+        if not self.condition_on_previous_text or res.temperature > 0.5:
+            self.prompt_reset_since[i] = len(self.all_tokens[i])  # do not feed the prompt tokens if a high temperature was used
+        if advance <= 0:  # a pair at <|0.00|> only: never stand still
+            self.seek[i] += size
+        return self.all_segments[i][first_new:], time_offset, decoded_tokens
+
+
 def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Union[float, Tuple[float, ...]] = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
                compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
                no_speech_threshold: Optional[float] = 0.6, condition_on_previous_text: bool = False,
@@ -230,7 +429,8 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
                hallucination_silence_threshold: Optional[float] = None, language: Optional[str] = None, decode_fn: Optional[Callable] = None,
                tokenizer=None, seed: Optional[int] = None, fallback_fn: Optional[Callable] = None,
                prepend_punctuations: str = "\"'“¿([{-", append_punctuations: str = "\"'.。,，!！?？:：”)]}、",
-               align_fn: Optional[Callable] = None, **decode_options):
+               align_fn: Optional[Callable] = None, schedule: str = "rounds", slots: int = 64, check_every: int = 8,
+               stream_fn: Optional[Callable] = None, stats_out: Optional[list] = None, **decode_options):
     """``audio``: a path, a 16 kHz mono float array, or a list of them.  Returns {"text", "segments", "language"} (a list of
     them for a list) with mlx_whisper's segment keys (``SEGMENT_KEYS``; plus ``needs_fallback`` where upstream would have
     retried).  ``condition_on_previous_text`` defaults to False here.  With True every window after a file's first is decoded with
@@ -247,7 +447,12 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
     schedule.  ``best_of=N``: every retry decodes N candidates per window and keeps the best (``fallback_fn`` then gets ``best_of=N``).  ``word_timestamps=True``: every segment gains ``"words"``: [{"word", "start", "end", "probability"}]
     (timing.py); ``align_fn(results, text_tokens, num_frames, languages)`` -> one list of WordTiming per window replaces the
     model's alignment (``results``: the windows' decode results, ``text_tokens[j]`` the ids below EOT of window j's segments,
-    ``num_frames[j]`` its content in mel frames); it is required with a custom ``decode_fn``."""
+    ``num_frames[j]`` its content in mel frames); it is required with a custom ``decode_fn``.
+    ``schedule="continuous"``: the windows go through ``slots`` rows of ONE decode state with refill instead of one lockstep batch per
+    round (``_transcribe_continuous``); the host looks at the rows every ``check_every`` steps.  Temperature 0 only; ``seed``,
+    ``word_timestamps``, ``condition_on_previous_text`` / ``initial_prompt``, ``best_of``, a custom ``decode_fn`` and fp8 models are
+    refused.  ``stream_fn(source, slots=, check_every=)`` replaces the model's continuous decoder (tests); ``stats_out``: a list that
+    receives the run's ``StreamStats``."""
     _refuse(condition_on_previous_text, initial_prompt, word_timestamps, clip_timestamps, hallucination_silence_threshold, temperature,
             decode_options, can_align=align_fn is not None or (model is not None and decode_fn is None),
             can_retry=decode_fn is None or fallback_fn is not None)
@@ -276,7 +481,11 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
     temps = (float(temperature),) if isinstance(temperature, (int, float)) else tuple(float(t) for t in temperature)
     # upstream's decode_with_fallback: best_of belongs to the temperatures above 0 -- the first decode never sees it, every retry does
     best_of = decode_options.pop("best_of", None)
-    if decode_fn is None:
+    if schedule not in ("rounds", "continuous"):
+        raise ValueError(f"transcribe: schedule is 'rounds' or 'continuous', got {schedule!r}")
+    if schedule == "continuous":
+        _refuse_continuous(model, seed, word_timestamps, condition_on_previous_text, initial_prompt, best_of, decode_fn)
+    elif decode_fn is None:
         decode_fn = _model_decoder(model, decode_options)
         fallback_fn = fallback_fn or decode_fn.retry
     if seed is None:
@@ -284,16 +493,16 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
 
     n = len(clips)
     content_frames = [len(a) // HOP_LENGTH for a in clips]
-    seek = [0] * n
-    languages: List[Optional[str]] = [language] * n
-    all_segments: List[List[dict]] = [[] for _ in range(n)]
-    # upstream's prompt bookkeeping, per file: all_tokens starts with the initial prompt, the next window's prompt is what came after
-    # prompt_reset_since
     initial_ids = [int(t) for t in tok.encode(" " + initial_prompt.strip())] if initial_prompt is not None else []
-    all_tokens: List[List[int]] = [list(initial_ids) for _ in range(n)]
-    prompt_reset_since = [0] * n
-    warned = False
-    while True:
+    books = _Books(tok, n, language, initial_ids, (compression_ratio_threshold, logprob_threshold, no_speech_threshold),
+                   bool(condition_on_previous_text))
+    seek, languages, all_segments, all_tokens, prompt_reset_since = (books.seek, books.languages, books.all_segments, books.all_tokens,
+                                                                     books.prompt_reset_since)
+    if schedule == "continuous":
+        stats = _transcribe_continuous(model, clips, content_frames, books, language, decode_options, stream_fn, slots, check_every)
+        if stats_out is not None:
+            stats_out.append(stats)
+    while schedule == "rounds":
         live = [i for i in range(n) if seek[i] < content_frames[i]]
         if not live:
             break
@@ -301,9 +510,7 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
         sizes = [min(N_FRAMES, content_frames[i] - seek[i]) for i in live]
         windows = np.zeros((len(live), N_SAMPLES), dtype=np.float32)
         for r, (i, size) in enumerate(zip(live, sizes)):
-            s0 = seek[i] * HOP_LENGTH
-            chunk = clips[i][s0:s0 + size * HOP_LENGTH]
-            windows[r, :len(chunk)] = chunk  # pad_or_trim of the window's own samples
+            windows[r] = _window_samples(clips[i], seek[i], size)
         prompts = [list(all_tokens[i][prompt_reset_since[i]:]) for i in live] if conditioning else None
         if conditioning:
             results = list(decode_fn(windows, [languages[i] for i in live], prompts=prompts))
@@ -329,45 +536,10 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
                 retried.update(failing)
                 failing = [r for r in failing if _needs_fallback(results[r], *thresholds)]
         for row, (i, size, res) in enumerate(zip(live, sizes, results)):
-            if languages[i] is None:
-                languages[i] = res.language  # detected on the file's first window, kept for the rest
-            time_offset = seek[i] * HOP_LENGTH / SAMPLE_RATE
-            tokens = [int(t) for t in res.tokens]
-            if no_speech_threshold is not None:
-                skip = res.no_speech_prob > no_speech_threshold
-                if logprob_threshold is not None and res.avg_logprob > logprob_threshold:
-                    skip = False  # a confident transcript overrides the no-speech probability
-                if skip:
-                    seek[i] += size
-                    continue
-            needs_fallback = row not in retried and _needs_fallback(res, compression_ratio_threshold, logprob_threshold, no_speech_threshold)
-            if needs_fallback and not warned:
-                warnings.warn("whisper_ipa_amd.transcribe: a window failed compression_ratio_threshold / logprob_threshold; upstream would "
-                              "retry at a higher temperature, this path runs temperature 0 only (segments carry needs_fallback=True)",
-                              RuntimeWarning, stacklevel=2)
-                warned = True
-            at = seek[i]
-            segs, advance = split_segments(tokens, tb, time_offset, size)
-            seek[i] += advance
-            first_new = len(all_segments[i])
-            decoded_tokens = [list(sg["tokens"]) for sg in segs]  # the alignment sees what was decoded, emptied segments included
-            for sg in segs:
-                text = tok.decode([t for t in sg["tokens"] if t < tok.eot])
-                if sg["start"] == sg["end"] or text.strip() == "":
-                    text, sg["tokens"] = "", []
-                seg = {"id": len(all_segments[i]), "seek": at, "start": sg["start"], "end": sg["end"], "text": text, "tokens": sg["tokens"],
-                       "temperature": res.temperature, "avg_logprob": res.avg_logprob, "compression_ratio": res.compression_ratio,
-                       "no_speech_prob": res.no_speech_prob}
-                if needs_fallback:
-                    seg["needs_fallback"] = True
-                all_segments[i].append(seg)
-                all_tokens[i].extend(sg["tokens"])
-            if word_timestamps:
-                to_align.append((res, all_segments[i][first_new:], size, time_offset, languages[i], decoded_tokens))
-            if not condition_on_previous_text or res.temperature > 0.5:
-                prompt_reset_since[i] = len(all_tokens[i])  # do not feed the prompt tokens if a high temperature was used
-            if advance <= 0:  # a pair at <|0.00|> only: never stand still
-                seek[i] += size
+            booked = books.window(i, size, res, row in retried)
+            if booked is not None and word_timestamps:
+                new_segments, time_offset, decoded_tokens = booked
+                to_align.append((res, new_segments, size, time_offset, languages[i], decoded_tokens))
         if word_timestamps and to_align:
             _add_words(model, tok, to_align, prepend_punctuations, append_punctuations, align_fn)
     out = [{"text": tok.decode([t for t in all_tokens[i][len(initial_ids):] if t < tb]), "segments": all_segments[i], "language": languages[i]} for i in range(n)]
