@@ -483,6 +483,29 @@ int wipa_timestamp_step_embed(const float* logits, int64_t ldl, int B, int V, co
 size_t wipa_sample_record_bytes(int B);
 int wipa_sample_record_fill(void* host_record, size_t record_bytes, uint64_t seed, int attempt, float temperature,
                             const uint32_t* streams, int B);
+/* The SAMPLING RECORD WITH A ROW PART: a second form, for a decode whose rows differ in temperature and attempt (continuous batching
+ * with the temperature fallback: wipa_decoder_run_continuous_rows).  One caller-owned DEVICE buffer of wipa_sample_rows_bytes(B)
+ * = 16 + 16 * B bytes, 16-byte aligned:
+ *   offset  0  uint32 seed_lo          offset  8  uint32 B (the rows the buffer holds)
+ *   offset  4  uint32 seed_hi          offset 12  uint32 0
+ *   offset 16 + 16 * b  uint32 stream_lo[b], uint32 stream_hi[b], uint32 attempt[b] (< 65536), float 1 / temperature[b]   for b < B
+ * 1 / temperature[b] == 0 marks a GREEDY row: its pick is the arg-max of the filtered row and nothing is drawn.  A sampled row's bits
+ * are those of the record above: key = (seed_lo, seed_hi), counter = (c >> 2, p_own | attempt[b] << 16, stream_lo[b], stream_hi[b]), so a
+ * row at temperature T and attempt a draws exactly the tokens the single-temperature tails draw for it.  The kernels read the record
+ * when they RUN: admissions rewrite row entries in stream order and one captured step graph serves every assignment.
+ * wipa_sample_rows_fill writes the HOST image: the header, and every row greedy on stream (b, 0) at attempt 0; the caller copies it to
+ *   the device.
+ * wipa_sample_rows_fill_row writes ONE row's entry into the host image, with the checks and the 1 / temperature of wipa_sample_rows_set.
+ * wipa_sample_rows_set writes, in stream order, the entries of rows slots_host[i], i < n_rows: streams_host[i] = (lo, hi) (uint32
+ *   [n_rows][2]), attempts_host[i], 1 / temperatures_host[i] (0 for temperature 0).  The values travel as kernel arguments (the host
+ *   arrays may be freed when the call returns), as those of wipa_decoder_admit_rows do.  WIPA_ERR_ARG, with a message naming the
+ *   argument and nothing enqueued: a temperature that is negative or not finite, an attempt outside 0..65535, a slot outside 0..B-1. */
+size_t wipa_sample_rows_bytes(int B);
+int wipa_sample_rows_fill(void* host_image, size_t bytes, uint64_t seed, int B);
+int wipa_sample_rows_fill_row(void* host_image, size_t bytes, int B, int slot, uint32_t stream_lo, uint32_t stream_hi, int attempt,
+                              float temperature);
+int wipa_sample_rows_set(void* rows_dev, int B, int n_rows, const int32_t* slots_host, const uint32_t* streams_host,
+                         const int32_t* attempts_host, const float* temperatures_host, wipa_stream_t s);
 /* the draw alone on any rows (no embedding), like wipa_timestamp_step; rules may be NULL (the plain filtered row); sample: required */
 int wipa_sample_step(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
                      int32_t* tokens, int64_t ld_tok, const int32_t* pos_dev, int n_init, int eot, const wipa_decode_rules* rules,
@@ -853,7 +876,17 @@ int wipa_decoder_run_ragged(const wipa_model_cfg* cfg, const void* const* weight
  *   the UNFILTERED row to no_speech_dev[b], with a plain store; the value stays until the slot's next admission reaches that step.
  *   The step graph's key is that of wipa_decoder_run_continuous plus the variant, the address of no_speech_dev and no_speech_token.  On
  *   bf16 the logits projection writes the logits, as for wipa_decoder_run_rules.  Refused by name (WIPA_ERR_ARG, nothing enqueued):
- *   rules == NULL, fp8 tables, candidate groups, a step without the fused tail, no_speech_token outside the vocabulary. */
+ *   rules == NULL, fp8 tables, candidate groups, a step without the fused tail, no_speech_token outside the vocabulary.
+ * wipa_decoder_run_continuous_rows: wipa_decoder_run_continuous_rules (rules given) or wipa_decoder_run_continuous (rules == NULL) with a
+ *   TEMPERATURE PER ROW: sample_rows is the sampling record with a row part (wipa_sample_rows_bytes above; required), and the steps end
+ *   in the rows_tail_continuous kernels.  The four cases per row, the rules on the row's own sequence, the no-speech store and the
+ *   counter's own position p - start[b] stay; a row whose 1 / temperature is 0 takes the greedy pick, every other row the draw at its own
+ *   temperature, attempt and stream -- a retried window beside first attempts and beside retries at other temperatures, in ONE launch.
+ *   wipa_decoder_admit_rows is called with sample == NULL, and wipa_sample_rows_set for the same slots.  The step graph's key is that
+ *   of the call without the record plus the variant and the record's address.  On bf16 the logits projection writes the logits.
+ *   Without rules a greedy row's pick is row_pick's arg-max (the same token as wipa_decoder_run_continuous; its log-probability sums
+ *   the exponentials in the rules tails' order).  no_speech_dev needs rules.  Refused by name (WIPA_ERR_ARG, nothing enqueued):
+ *   sample_rows == NULL or unaligned, fp8 tables, candidate groups, a step without the fused tail, and what the two calls above refuse. */
 int wipa_decoder_admit_rows(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int n_rows,
                             const int32_t* slots_host,
                             const void* const* features_host, const int32_t* initial_tokens_host, int n_init, const int32_t* limits_host,
@@ -867,6 +900,10 @@ int wipa_decoder_run_continuous_rules(const wipa_model_cfg* cfg, const void* con
                                       int n_init, int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
                                       const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, float* no_speech_dev,
                                       int no_speech_token, wipa_stream_t s);
+int wipa_decoder_run_continuous_rows(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B,
+                                     int n_init, int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
+                                     const wipa_decode_rules* rules, const void* sample_rows, const int32_t* starts_dev, float* no_speech_dev,
+                                     int no_speech_token, wipa_stream_t s);
 /* drop the cached step graphs that reference this state blob (call before freeing it). */
 int wipa_decoder_release(void* state);
 

@@ -149,7 +149,8 @@ def transcribe_files(model, audio_paths: List[str], batch_size: int = 64, progre
     mlx_whisper.transcribe's options of those names (upstream defaults to conditioning on; here it is opt-in).
     ``schedule="continuous"``: transcribe(schedule="continuous", slots=batch_size) -- the windows go through ``batch_size`` rows of one
     decode state with refill, 8 x ``batch_size`` files per call (what bounds a call is the host memory of its samples, not its rows);
-    it serves temperature 0 without conditioning and refuses the rest by name."""
+    it serves ``seed`` (a retried window is admitted again with a temperature of its own) without conditioning and refuses the rest by
+    name."""
     from whisper_ipa_amd import transcribe
 
     texts = [""] * len(audio_paths)

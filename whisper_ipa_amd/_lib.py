@@ -233,6 +233,12 @@ SIGNATURES = {
                                             c_int, _P(DecodeRules), c_void_p, c_void_p, c_void_p]),
     "wipa_decoder_run_continuous_rules": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                                   c_int, _P(DecodeRules), c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "wipa_decoder_run_continuous_rows": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                                 c_int, _P(DecodeRules), c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "wipa_sample_rows_bytes": (c_size_t, [c_int]),
+    "wipa_sample_rows_fill": (c_int, [c_void_p, c_size_t, C.c_uint64, c_int]),
+    "wipa_sample_rows_fill_row": (c_int, [c_void_p, c_size_t, c_int, c_int, C.c_uint32, C.c_uint32, c_int, c_float]),
+    "wipa_sample_rows_set": (c_int, [c_void_p, c_int, c_int, _P(C.c_int32), _P(C.c_uint32), _P(C.c_int32), _P(c_float), c_void_p]),
     "wipa_decoder_admit_rows": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, _P(C.c_int32), _P(c_void_p), _P(C.c_int32), c_int,
                                         _P(C.c_int32), c_void_p, c_void_p, _P(C.c_uint32), c_void_p]),
     "wipa_decoder_shift_columns": (c_int, [_P(ModelCfg), c_void_p, c_size_t, c_int, c_void_p, c_int, c_void_p]),

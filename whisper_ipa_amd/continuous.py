@@ -17,6 +17,12 @@ DESIGN.md section 14): the rules run on every row's own sequence, from its own f
 probability at its <|startoftranscript|> column.  ``run_stream`` is the scheduler for clips that are not all known when the run starts
 -- the windows of files, of which ``transcribe(schedule="continuous")`` keeps one per file in flight (``stream_windows``); a check is
 one device-to-host copy (``DeviceStepper.snapshot``).
+
+A TEMPERATURE PER ROW: ``decode_continuous(temperatures=, attempts=)`` and ``transcribe(schedule="continuous",
+seed=S)`` keep the state's sampling record with a row part (wipa_sample_rows_set: stream, attempt and 1 / temperature per slot, 0 for a
+greedy row) and end the steps in the tails that read it (wipa_decoder_run_continuous_rows), so a window retried at a higher temperature
+sits beside greedy first attempts and beside retries of other windows at other temperatures.  ``run_stream``'s source may hand a clip
+out again, with its draw; ``_GroupStepper`` admits it from the encoder features its first admission left.
 """
 from __future__ import annotations
 
@@ -130,11 +136,15 @@ def run_stream(stepper, source, slots: int, n_init: int, eot: int, n_ctx: int, c
 
       source.pending() -> [(clip, limit)]   the clips that are ready now, each returned once, in the order they take slots; asked at the
                                             start and after every check (a retirement may have made more ready).  ``clip`` is any
-                                            hashable value; it may generate ``limit`` tokens
+                                            hashable value; it may generate ``limit`` tokens.  An entry may be (clip, limit, draw) with
+                                            ``draw`` = None (greedy) or (temperature, attempt, stream): the row's own temperature, its
+                                            index in the fallback schedule and its Philox stream (lo, hi).  A source may hand a clip out
+                                            AGAIN after it has retired (a retry): it is admitted at the check that retired it
       source.retired(clip, tokens, sum_logprob, no_speech)   the clip's generated tokens before its first ``eot`` (a list), its
                                             log-probability sum and its no-speech probability, as host values, at the check that retires it
 
-      stepper.admit(triples)    [(slot, clip, limit)]: ONE call per check for all clips that start at the current column (a group)
+      stepper.admit(triples)    [(slot, clip, limit)]: ONE call per check for all clips that start at the current column (a group); an
+                                entry whose source gave a draw is (slot, clip, limit, draw)
       stepper.run(n), stepper.shift(shift)   as for ``run_schedule``
       stepper.snapshot() -> (tokens [slots, >= column + 1], sums [slots], no_speech [slots])   host arrays from ONE device-to-host copy
                                             (this is where the host waits); everything a check retires is read from them
@@ -159,7 +169,7 @@ def run_stream(stepper, source, slots: int, n_init: int, eot: int, n_ctx: int, c
             if not queue:
                 break
             if slot not in live:
-                clip, limit = queue.popleft()
+                clip, limit, *draw = queue.popleft()
                 limit = int(limit)
                 # the bound of run_schedule, per clip: after a shift the oldest live row starts at column 0 and the next interval must fit
                 need = n_init + limit + 2 * check_every - 1
@@ -167,7 +177,7 @@ def run_stream(stepper, source, slots: int, n_init: int, eot: int, n_ctx: int, c
                     raise ValueError(f"decode_continuous: a clip's limit of {limit} tokens is outside 1 .. {column_limit - n_init - 2 * check_every + 1} "
                                      f"(column_limit - n_init - 2 * check_every + 1)")
                 live[slot] = (clip, pos, limit)
-                triples.append((slot, clip, limit))
+                triples.append((slot, clip, limit, *draw))
                 stats.admissions.append((slot, clip, pos))
         if triples:
             stepper.admit(triples)
@@ -226,9 +236,13 @@ class DeviceStepper:
 
     def __init__(self, model, slots: int, features, initial, n_init: int, limits: Sequence[int], eot: int,
                  suppress_always: Sequence[int], suppress_first: Sequence[int], sample: Optional[Sampling], s, use_graph: bool = True,
-                 rules: Optional["_lib.DecodeRules"] = None, no_speech_token: Optional[int] = None):
+                 rules: Optional["_lib.DecodeRules"] = None, no_speech_token: Optional[int] = None, row_seed: Optional[int] = None,
+                 draws=None):
         """``rules``: the timestamp rules (wipa_decoder_run_continuous_rules; None: wipa_decoder_run_continuous).  With them and
-        ``no_speech_token`` the step's tail leaves every row's no-speech probability in ``self.no_speech``"""
+        ``no_speech_token`` the step's tail leaves every row's no-speech probability in ``self.no_speech``.
+        ``row_seed``: a TEMPERATURE PER ROW (wipa_decoder_run_continuous_rows; ``sample`` is then None): the state's sampling record
+        with a row part is filled with this seed, and every admission writes the admitted clips' entries -- ``draws(clip)`` or the
+        fourth element of an admitted tuple, (temperature, attempt, (stream_lo, stream_hi)); None is a greedy row"""
         self.L = _lib.lib()
         self.model, self.B, self.s, self.eot, self.use_graph = model, int(slots), s, int(eot), use_graph
         self.features = features  # clip -> device tensor [n_audio_ctx, d] in the model's dtype, contiguous
@@ -237,6 +251,9 @@ class DeviceStepper:
             raise ValueError("decode_continuous: every clip takes the same number (1..4) of initial tokens")
         self.limits = [int(n) for n in limits]
         self.sample = sample
+        if row_seed is not None and sample is not None:
+            raise ValueError("decode_continuous: a temperature per row takes the place of the single-temperature sampling record")
+        self.row_seed, self.draws = row_seed, draws
         self.pk = pk = model.packed(absorbed=model.use_absorbed())  # the absorbed form where it applies, else the cached one
         states = model.__dict__.setdefault("_continuous_states", {})
         key = (stream_id(), self.B, int(pk["cfg"].dec_cross_absorbed))
@@ -257,6 +274,12 @@ class DeviceStepper:
             if getattr(st, "_cont_no_speech", None) is None:  # ONE buffer per state, like the starts
                 st._cont_no_speech = torch.zeros(self.B, dtype=torch.float32, device=model.device)
             self.no_speech = st._cont_no_speech
+        self.rows = None
+        if row_seed is not None:  # ONE buffer per state, like the starts: its address is part of the step graph's key
+            nbytes = int(self.L.wipa_sample_rows_bytes(self.B))
+            if getattr(st, "_cont_rows", None) is None:
+                st._cont_rows = torch.zeros(nbytes, dtype=torch.uint8, device=model.device)
+            self.rows = st._cont_rows
         self.no_speech_token = int(no_speech_token) if no_speech_token is not None else 0
         self.m_always = _mask(model, suppress_always)
         self.m_first = _mask(model, list(suppress_always) + list(suppress_first))
@@ -277,13 +300,19 @@ class DeviceStepper:
         self.starts.zero_()
         if self.no_speech is not None:
             self.no_speech.fill_(float("nan"))
+        if self.rows is not None:  # the header, and every row greedy until a clip is admitted
+            host = np.zeros(self.rows.numel(), dtype=np.uint8)
+            _lib.check(L.wipa_sample_rows_fill(host.ctypes.data, host.size, int(self.row_seed) & 0xFFFFFFFFFFFFFFFF, self.B), "wipa_sample_rows_fill")
+            self.rows.copy_(torch.from_numpy(host))  # on the caller's library stream
         self.rec = None
         if self.sample is not None:  # seed, attempt and temperature; the streams are written per admission
             self.rec = st.sample_record(Sampling(self.sample.seed, self.sample.temperature, None, self.sample.attempt))
 
     def admit(self, pairs):
-        """pairs [(slot, clip)] of ``run_schedule`` (the clip's limit is ``limits[clip]``), or triples [(slot, clip, limit)] of ``run_stream``"""
+        """pairs [(slot, clip)] of ``run_schedule`` (the clip's limit is ``limits[clip]``), or triples [(slot, clip, limit)] of ``run_stream``,
+        which may carry a fourth element: the clip's draw (temperature, attempt, stream) or None"""
         limits = [int(t[2]) if len(t) > 2 else self.limits[t[1]] for t in pairs]
+        given = [t[3] if len(t) > 3 else (self.draws(t[1]) if self.draws is not None else None) for t in pairs]
         pairs = [(t[0], t[1]) for t in pairs]
         n = len(pairs)
         slots = (C.c_int32 * n)(*[slot for slot, _ in pairs])
@@ -303,9 +332,25 @@ class DeviceStepper:
         _lib.check(self.L.wipa_decoder_admit_rows(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), self.B, n, slots, fptr, init,
                                                   self.n_init, lim, ptr(self.starts), ptr(self.rec) if self.rec is not None else None, streams,
                                                   sptr(self.s)), "wipa_decoder_admit_rows")
+        if self.rows is not None:  # the admitted slots' entries of the row record, in stream order behind the admission
+            draws = [d if d is not None else (0.0, 0, (slot, 0)) for d, (slot, _) in zip(given, pairs)]
+            flat = (C.c_uint32 * (2 * n))(*[int(v) & 0xFFFFFFFF for _, _, stream in draws for v in stream])
+            attempts = (C.c_int32 * n)(*[int(a) for _, a, _ in draws])
+            temps = (C.c_float * n)(*[float(t) for t, _, _ in draws])
+            _lib.check(self.L.wipa_sample_rows_set(ptr(self.rows), self.B, n, slots, flat, attempts, temps, sptr(self.s)), "wipa_sample_rows_set")
+        elif any(d is not None for d in given):
+            raise ValueError("decode_continuous: a clip came with a draw, but the stepper was not built for a temperature per row (row_seed)")
 
     def run(self, n: int):
         pk, st = self.pk, self.st
+        if self.rows is not None:
+            _lib.check(self.L.wipa_decoder_run_continuous_rows(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), self.B, self.n_init,
+                                                               self.eot, ptr(self.m_first), ptr(self.m_always), n, int(self.use_graph),
+                                                               C.byref(self.rules) if self.rules is not None else None, ptr(self.rows),
+                                                               ptr(self.starts), ptr(self.no_speech) if self.no_speech is not None else None,
+                                                               self.no_speech_token, sptr(self.s)), "wipa_decoder_run_continuous_rows")
+            self.pos += n
+            return
         if self.rules is not None:
             _lib.check(self.L.wipa_decoder_run_continuous_rules(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), self.B, self.n_init,
                                                                 self.eot, ptr(self.m_first), ptr(self.m_always), n, int(self.use_graph),
@@ -427,20 +472,33 @@ class _Features:
 
 class _GroupStepper(DeviceStepper):
     """``run_stream``'s stepper for ``transcribe(schedule="continuous")``: an admitted group's windows go through ONE log-mel call, ONE
-    encoder call and ONE detect_language call (the windows of files whose language is still unknown), then ONE admission"""
+    encoder call and ONE detect_language call (the windows of files whose language is still unknown), then ONE admission.
+    ``seed``: the temperature fallback (a temperature per row).  A window's encoder features and initial tokens are HELD from its first
+    admission until the source says the window is booked (``release``; the source calls it through its ``on_booked`` attribute): a
+    window the source hands out again -- a retry -- is admitted from them, with no second log-mel, encoder or language detection, and
+    ``source.group`` is asked for fresh windows only.  A file has one window in flight, so at most one feature tensor per active file."""
 
-    def __init__(self, model, slots: int, source, options: DecodingOptions, tok, base, always, first, rules, s):
+    def __init__(self, model, slots: int, source, options: DecodingOptions, tok, base, always, first, rules, s, seed: Optional[int] = None):
         self.source, self.options, self.tok, self.base = source, options, tok, list(base)
-        self._feat: Dict[object, torch.Tensor] = {}
-        self._init: Dict[object, List[int]] = {}
-        super().__init__(model, slots, self._feat.pop, self._init.pop, len(base), [], tok.eot, always, first, None, s, rules=rules,
-                         no_speech_token=tok.no_speech)
+        self._held: Dict[object, Tuple[torch.Tensor, List[int]]] = {}
+        source.on_booked = self.release
+        super().__init__(model, slots, lambda clip: self._held[clip][0], lambda clip: self._held[clip][1], len(base), [], tok.eot, always, first,
+                         None, s, rules=rules, no_speech_token=tok.no_speech, row_seed=seed)
+
+    def release(self, clip):
+        """the window is booked: nothing will ask for its features again"""
+        self._held.pop(clip, None)
 
     def admit(self, triples):
+        fresh = [t[1] for t in triples if t[1] not in self._held]
+        if fresh:
+            self._encode(fresh)
+        super().admit(triples)
+
+    def _encode(self, clips):
         from . import audio as A
         from .tokenizer import LANGUAGES
 
-        clips = [clip for _, clip, _ in triples]
         windows, languages = self.source.group(clips)
         model = self.model
         dev_audio = torch.from_numpy(np.ascontiguousarray(windows)).to(model.device)
@@ -458,8 +516,7 @@ class _GroupStepper(DeviceStepper):
         for j, clip in enumerate(clips):
             row = list(self.base)
             row[1] = self.tok.to_language_token(languages[j])
-            self._feat[clip], self._init[clip] = feats[j], row
-        super().admit(triples)
+            self._held[clip] = (feats[j], row)
 
     def snapshot(self):
         out = super().snapshot()
@@ -468,10 +525,11 @@ class _GroupStepper(DeviceStepper):
 
 
 def stream_windows(model, source, decode_options: dict, slots: int, check_every: int = 8,
-                   column_limit: Optional[int] = None) -> ScheduleStats:
+                   column_limit: Optional[int] = None, seed: Optional[int] = None) -> ScheduleStats:
     """The model's continuous decoder for ``transcribe(schedule="continuous")``: ``run_stream`` over ``source`` (transcribe._WindowSource:
     ``pending`` / ``retired`` of ``run_stream``, plus ``group(clips)`` -> (samples [n, 480000], languages) and ``detected(clips, languages)``)
-    on ``slots`` rows, with timestamps, at temperature 0"""
+    on ``slots`` rows, with timestamps.  Without ``seed`` every row is at temperature 0; with it the source's entries carry their draws
+    (a retried window's temperature, attempt and stream) and the steps end in the tails with a temperature per row"""
     options = DecodingOptions(**{**decode_options, "without_timestamps": False, "temperature": 0.0})
     refuse_unserved(model, options, timestamps=True)
     tok = get_tokenizer(model.is_multilingual, num_languages=model.num_languages, language=options.language or "en", task=options.task)
@@ -479,7 +537,7 @@ def stream_windows(model, source, decode_options: dict, slots: int, check_every:
     rules = timestamp_rules(tok, options.max_initial_timestamp)
     base = list(tok.sot_sequence)
     with on_stream() as s:
-        stepper = _GroupStepper(model, slots, source, options, tok, base, always, first, rules, s)
+        stepper = _GroupStepper(model, slots, source, options, tok, base, always, first, rules, s, seed=seed)
         stats = run_stream(stepper, source, slots, len(base), tok.eot, model.dims.n_text_ctx, check_every, column_limit)
         stepper._keep.clear()
     return stats
@@ -487,15 +545,34 @@ def stream_windows(model, source, decode_options: dict, slots: int, check_every:
 
 def decode_continuous(model, mels_or_features: torch.Tensor, options: DecodingOptions = DecodingOptions(without_timestamps=True),
                       slots: int = 64, sample_lens: Optional[Sequence[int]] = None, check_every: int = 8,
-                      column_limit: Optional[int] = None, stats_out: Optional[list] = None) -> List[DecodingResult]:
+                      column_limit: Optional[int] = None, stats_out: Optional[list] = None, temperatures: Optional[Sequence[float]] = None,
+                      attempts: Optional[Sequence[int]] = None) -> List[DecodingResult]:
     """``decode`` for a stream of clips through ``slots`` rows with refill: mels [N, 3000, n_mels] or encoded features [N, 1500, d];
     results in input order.  ``sample_lens``: the tokens clip i may generate (default ``options.sample_len`` or n_text_ctx // 2 for
     every clip).  Served: greedy, and ``temperature > 0`` with ``seed`` -- clip i draws from ``options.sample_streams[i]`` or from
     stream (i, 0), whichever slot it lands in and whenever it is admitted.  ``language=None`` detects the language (and fills
     ``no_speech_prob``) per encoded chunk of ``slots`` clips.  ``stats_out``: a list that receives the run's ``ScheduleStats``.
     ``without_timestamps=False``: the initial tokens are ``sot_sequence``, the timestamp rules of ``decode()`` run on every row's own
-    sequence, and ``no_speech_prob`` is what the step's tail left at the row's <|startoftranscript|> column."""
+    sequence, and ``no_speech_prob`` is what the step's tail left at the row's <|startoftranscript|> column.
+    ``temperatures``: a temperature >= 0 PER CLIP (0: a greedy clip), with ``attempts`` (default 0 for every clip) the clip's index in a
+    fallback schedule; needs ``options.seed`` and ``options.temperature == 0``.  Clip i draws what ``decode`` draws for it at that
+    temperature and attempt on its stream; the steps end in the tails with a temperature per row (wipa_decoder_run_continuous_rows)."""
     refuse_unserved(model, options, timestamps=True)
+    if temperatures is None and attempts is not None:
+        raise ValueError("decode_continuous: attempts comes with temperatures (a temperature and an attempt per clip)")
+    if temperatures is not None:
+        if options.seed is None:
+            raise NotImplementedError("decode_continuous: temperatures needs DecodingOptions.seed (sampling is opt-in and reproducible)")
+        if options.temperature != 0.0:
+            raise ValueError("decode_continuous: temperatures (a temperature per clip) cannot be combined with options.temperature != 0")
+        temperatures = [float(t) for t in temperatures]
+        attempts = [int(a) for a in attempts] if attempts is not None else [0] * len(temperatures)
+        if len(temperatures) != mels_or_features.shape[0] or len(attempts) != len(temperatures):
+            raise ValueError(f"decode_continuous: {len(temperatures)} temperatures and {len(attempts)} attempts for {mels_or_features.shape[0]} clips")
+        if any(not (t >= 0.0 and t < float("inf")) for t in temperatures):
+            raise ValueError(f"decode_continuous: temperatures must be >= 0 and finite, got {temperatures}")
+        if any(not 0 <= a < 65536 for a in attempts):
+            raise ValueError(f"decode_continuous: attempts outside 0..65535: {attempts}")
     x = mels_or_features
     if x.dim() != 3:
         raise ValueError("decode_continuous: mels [N, 3000, n_mels] or features [N, n_audio_ctx, d]")
@@ -520,6 +597,15 @@ def decode_continuous(model, mels_or_features: torch.Tensor, options: DecodingOp
         if len(streams) != N:
             raise ValueError(f"sample_streams: {len(streams)} streams for {N} clips")
         sample = Sampling(int(options.seed), float(options.temperature), streams, int(options.sample_attempt))
+    draws = None
+    if temperatures is not None and N:
+        row_streams = [(int(a), int(b)) for a, b in options.sample_streams] if options.sample_streams is not None else [(i, 0) for i in range(N)]
+        if len(row_streams) != N:
+            raise ValueError(f"sample_streams: {len(row_streams)} streams for {N} clips")
+
+        def draws(clip: int):
+            return temperatures[clip], attempts[clip], row_streams[clip]
+
     feats = _Features(model, x, slots, options, tok)
 
     def initial(clip: int) -> List[int]:  # with language=None the chunk's detection has run when the clip is admitted
@@ -531,7 +617,8 @@ def decode_continuous(model, mels_or_features: torch.Tensor, options: DecodingOp
 
     with on_stream() as s:
         stepper = DeviceStepper(model, slots, feats, initial, len(base), limits, tok.eot, always, first, sample, s, rules=rules,
-                                no_speech_token=tok.no_speech if timed else None)
+                                no_speech_token=tok.no_speech if timed else None, row_seed=int(options.seed) if draws is not None else None,
+                                draws=draws)
         stats = run_schedule(stepper, N, slots, len(base), limits, tok.eot, d.n_text_ctx, check_every, column_limit)
         tail_no_speech = stepper.out_no_speech.cpu().numpy() if timed else None
         toks, sums = stepper.results()
@@ -551,6 +638,7 @@ def decode_continuous(model, mels_or_features: torch.Tensor, options: DecodingOp
             lang = LANGUAGES[feats.lang_token[i] - tok.sot - 1]
         # the features the caller gave; those encoded here are dropped chunk by chunk once their clips are admitted
         results.append(DecodingResult(audio_features=x[i] if feats.encoded else None, language=lang, language_probs=feats.lang_probs.get(i), tokens=row, text=text,
-                                      avg_logprob=float(sums[i]) / (len(row) + 1), temperature=options.temperature, compression_ratio=comp,
+                                      avg_logprob=float(sums[i]) / (len(row) + 1),
+                                      temperature=temperatures[i] if temperatures is not None else options.temperature, compression_ratio=comp,
                                       no_speech_prob=float(tail_no_speech[i]) if timed else feats.no_speech.get(i, float("nan"))))
     return results

@@ -588,7 +588,12 @@ struct RowPick {
 // rec: the caller's sampling record (wipa.h: wipa_sample_record_bytes): u32 seed_lo, seed_hi, attempt, f32 1/T, then [lo, hi] per row.
 // p_own: the position word of the counter -- p, or with ragged prompts the row's OWN position p - start[b] (a draw must not depend on
 // the prompt width the row's neighbours set).
-template <bool RULES, bool SAMPLE>
+// ROWS (SAMPLE only): rec is the record with a ROW PART (wipa.h: wipa_sample_rows_bytes) -- u32 seed_lo, seed_hi, B, 0, then per row
+// [stream_lo, stream_hi, attempt, f32 1/T].  The key and the counter are built from the same words, so a row at (T, attempt) draws what
+// the single-temperature record draws for it.  A row whose 1/T is 0 is a GREEDY row: the draw block is skipped and the row keeps the
+// greedy answer computed above it.  That branch holds a __syncthreads(); it is uniform because ONE workgroup owns ONE row (b is
+// blockIdx.x in every caller), so every thread of the workgroup reads the same 1/T.  ROWS = false compiles to what it was.
+template <bool RULES, bool SAMPLE, bool ROWS = false>
 __device__ __forceinline__ RowPick row_pick(const float* __restrict__ row, const float* __restrict__ mask, int V, const int32_t* __restrict__ tk,
                                             int p, int n_init, int eot, RulesDev r, float* s_v, int* s_i, float* s_sum,
                                             const uint32_t* __restrict__ rec, int b, int p_own) {
@@ -711,8 +716,12 @@ __device__ __forceinline__ RowPick row_pick(const float* __restrict__ row, const
     }
     if constexpr (SAMPLE) {
         const int dead_below = ts_mass > bt.v ? r.tb : 0;  // rule 5 killed the text side
-        const float inv_t = __uint_as_float(rec[3]);
-        const uint32_t k0 = rec[0], k1 = rec[1], c1 = (uint32_t)p_own | (rec[2] << 16), c2 = rec[4 + 2 * b], c3 = rec[5 + 2 * b];
+        const float inv_t = __uint_as_float(ROWS ? rec[7 + 4 * b] : rec[3]);
+        const uint32_t k0 = rec[0], k1 = rec[1], c1 = (uint32_t)p_own | ((ROWS ? rec[6 + 4 * b] : rec[2]) << 16),
+                       c2 = ROWS ? rec[4 + 4 * b] : rec[4 + 2 * b], c3 = ROWS ? rec[5 + 4 * b] : rec[5 + 2 * b];
+        if constexpr (ROWS) {
+            if (inv_t == 0.f) return out;  // a greedy row; uniform over the workgroup (one row per workgroup): the barrier below is reached by all or none
+        }
         MaxIdx mk{-INFINITY, 0x7fffffff};
         if (has_tail && ti >= dead_below && tailv > -INFINITY) {
             const Philox4 x = philox4x32_10((uint32_t)nq, c1, c2, c3, k0, k1);
@@ -981,6 +990,57 @@ __global__ __launch_bounds__(GS_THREADS) void rules_tail_continuous_kernel(TailA
         next = commit(tk + p, q.eot, pick.next, pick.logprob, q.sum_logprobs + b, q.not_done);
     }
     tail_finish<TO>(q, p, next, s_red);
+}
+
+// The CONTINUOUS tails with a TEMPERATURE PER ROW (wipa_decoder_run_continuous_rows): rules_tail_continuous_kernel<TO, true> (RULES) and
+// sample_tail_continuous_kernel (no rules) with the row's 1/T, attempt and stream read from the row's entry of the record with a row part
+// (row_pick<RULES, true, true>).  The four cases, the no-speech store at p == start[b], `commit` and `tail_finish` are those kernels'.  A
+// greedy row (1/T == 0) leaves row_pick with the greedy answer before the draw: the branch is uniform over the workgroup because one
+// workgroup owns one row, so a retried window sits beside greedy first attempts and beside retries at other temperatures in ONE launch.
+template <typename TO, bool RULES>
+__global__ __launch_bounds__(GS_THREADS) void rows_tail_continuous_kernel(TailArgs<true> q, RulesDev rules, const uint32_t* __restrict__ rec,
+                                                                          float* __restrict__ no_speech, int no_speech_token) {
+    __shared__ float s_v[2 * GS_WAVES];
+    __shared__ int s_i[2 * GS_WAVES];
+    __shared__ float s_sum[2 * GS_WAVES];
+    __shared__ float s_red[4];
+    const int b = blockIdx.x;
+    const int p = tail_pos(q.pos);
+    if (p + 1 >= q.n_ctx) return;
+    const ContinuousRow r = continuous_row(q, b);
+    int32_t* tk = q.tokens + (int64_t)b * q.ld_tok;
+    const float* row = q.logits + (int64_t)b * q.ldl;
+    if constexpr (RULES) {
+        if (no_speech && r.limit > 0 && p + q.n_init == r.own) {  // p == start[b]; uniform over the workgroup
+            row_no_speech(row, q.V, no_speech_token, no_speech + b, s_v, s_i, s_sum);
+            __syncthreads();
+        }
+    }
+    int next;
+    if (p + 1 < r.own) {
+        next = tk[p + 1];
+    } else if (p + 1 >= r.own + r.limit) {
+        next = q.eot;
+        if (threadIdx.x == 0) tk[p + 1] = next;
+    } else {
+        const float* mask = (p + 1 == r.own) ? q.mask_first : q.mask_always;
+        // RULES: the row's own sequence tk[own .. p]; without rules row_pick does not look at its n_init argument
+        const RowPick pick = row_pick<RULES, true, true>(row, mask, q.V, tk, p, RULES ? r.own : q.n_init, q.eot, rules, s_v, s_i, s_sum, rec, b,
+                                                         max(p - q.start[b], 0));
+        next = commit(tk + p, q.eot, pick.next, pick.logprob, q.sum_logprobs + b, q.not_done);
+    }
+    tail_finish<TO>(q, p, next, s_red);
+}
+
+// wipa_sample_rows_set: one row's entry of the record with a row part.  One thread; a slot outside the record's rows (its header holds
+// B) is not written.
+__global__ void sample_rows_set_kernel(uint32_t* rec, int slot, uint32_t stream_lo, uint32_t stream_hi, uint32_t attempt, float inv_t) {
+    if (slot < 0 || (uint32_t)slot >= rec[2]) return;
+    uint32_t* e = rec + 4 + 4 * slot;
+    e[0] = stream_lo;
+    e[1] = stream_hi;
+    e[2] = attempt;
+    e[3] = __float_as_uint(inv_t);
 }
 
 // wipa_sample_noise: g_c of one (row, position), c < V -- the numbers the sampling tails add, for measurement
@@ -1264,6 +1324,71 @@ extern "C" int wipa_sample_record_fill(void* host_record, size_t record_bytes, u
     return WIPA_OK;
 }
 
+// the sampling record with a ROW PART: 16 bytes of header (u32 seed_lo, seed_hi, B, 0) and 16 bytes per row (u32 stream_lo, stream_hi,
+// attempt; f32 1 / temperature, 0 for a greedy row)
+extern "C" size_t wipa_sample_rows_bytes(int B) { return B > 0 ? 16 + (size_t)B * 16 : 0; }
+
+extern "C" int wipa_sample_rows_fill(void* host_image, size_t bytes, uint64_t seed, int B) {
+    WIPA_REQUIRE(host_image && B > 0 && bytes >= wipa_sample_rows_bytes(B), "wipa_sample_rows_fill: null image / %zu bytes for %d rows", bytes, B);
+    uint32_t* r = (uint32_t*)host_image;
+    r[0] = (uint32_t)seed;
+    r[1] = (uint32_t)(seed >> 32);
+    r[2] = (uint32_t)B;
+    r[3] = 0u;
+    for (int b = 0; b < B; ++b) {  // every row greedy, on stream (b, 0), attempt 0
+        r[4 + 4 * b] = (uint32_t)b;
+        r[5 + 4 * b] = 0u;
+        r[6 + 4 * b] = 0u;
+        r[7 + 4 * b] = 0u;  // 1 / T = 0.0f
+    }
+    return WIPA_OK;
+}
+
+// what one row entry may hold, refused by the argument's name; *inv_t: 1 / temperature, 0 for temperature 0 (a greedy row)
+static int sample_rows_entry(const char* who, int B, int i, int slot, int attempt, float temperature, float* inv_t) {
+    WIPA_REQUIRE(slot >= 0 && slot < B, "%s: slot[%d]=%d outside 0..%d", who, i, slot, B - 1);
+    WIPA_REQUIRE(attempt >= 0 && attempt < 65536, "%s: attempt[%d]=%d outside 0..65535", who, i, attempt);
+    WIPA_REQUIRE(temperature >= 0.f && temperature < INFINITY, "%s: temperature[%d]=%g is negative or not finite (0 is a greedy row)", who, i,
+                 (double)temperature);
+    *inv_t = temperature > 0.f ? 1.0f / temperature : 0.f;
+    return WIPA_OK;
+}
+
+extern "C" int wipa_sample_rows_fill_row(void* host_image, size_t bytes, int B, int slot, uint32_t stream_lo, uint32_t stream_hi, int attempt,
+                                         float temperature) {
+    WIPA_REQUIRE(host_image && B > 0 && bytes >= wipa_sample_rows_bytes(B), "wipa_sample_rows_fill_row: null image / %zu bytes for %d rows", bytes, B);
+    float inv_t;
+    const int rc = sample_rows_entry("wipa_sample_rows_fill_row", B, 0, slot, attempt, temperature, &inv_t);
+    if (rc != WIPA_OK) return rc;
+    uint32_t* e = (uint32_t*)host_image + 4 + 4 * slot;
+    e[0] = stream_lo;
+    e[1] = stream_hi;
+    e[2] = (uint32_t)attempt;
+    memcpy(e + 3, &inv_t, 4);
+    return WIPA_OK;
+}
+
+extern "C" int wipa_sample_rows_set(void* rows_dev, int B, int n_rows, const int32_t* slots_host, const uint32_t* streams_host,
+                                    const int32_t* attempts_host, const float* temperatures_host, wipa_stream_t stream) {
+    const char* who = "wipa_sample_rows_set";
+    WIPA_REQUIRE(rows_dev && ((uintptr_t)rows_dev % 16) == 0, "%s: null / unaligned record (rows_dev: 16-byte aligned)", who);
+    WIPA_REQUIRE(B > 0 && n_rows >= 0 && (n_rows == 0 || (slots_host && streams_host && attempts_host && temperatures_host)),
+                 "%s: null pointer / bad row count", who);
+    float inv_t = 0.f;  // every entry is checked before the first launch
+    for (int i = 0; i < n_rows; ++i) {
+        const int rc = sample_rows_entry(who, B, i, slots_host[i], attempts_host[i], temperatures_host[i], &inv_t);
+        if (rc != WIPA_OK) return rc;
+    }
+    // the values travel as kernel arguments, like those of wipa_decoder_admit_rows: the host arrays are free when the call returns
+    for (int i = 0; i < n_rows; ++i) {
+        sample_rows_entry(who, B, i, slots_host[i], attempts_host[i], temperatures_host[i], &inv_t);
+        hipLaunchKernelGGL(sample_rows_set_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (uint32_t*)rows_dev, slots_host[i], streams_host[2 * i],
+                           streams_host[2 * i + 1], (uint32_t)attempts_host[i], inv_t);
+        WIPA_LAUNCH_CHECK();
+    }
+    return WIPA_OK;
+}
+
 // wipa_sample_step and, with starts_dev (left-padded prompt rows: the draw's counter takes the row's own position *pos_dev - starts_dev[b]),
 // wipa_sample_step_ragged
 static int sample_step(const char* who, const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
@@ -1457,8 +1582,8 @@ extern "C" int wipa_step_embed_ragged(const float* logits, int64_t ldl, int B, i
 // rules_tail_continuous kernels, and no_speech_dev (float [B], may be NULL) receives softmax(row)[no_speech_token] at a row's first column.
 static int step_tail_continuous(const char* who, const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
                                 int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init, int eot,
-                                const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, float* no_speech_dev,
-                                int no_speech_token, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
+                                const wipa_decode_rules* rules, const void* sample, const void* sample_rows, const int32_t* starts_dev,
+                                float* no_speech_dev, int no_speech_token, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
                                 const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y,
                                 int y_dtype, int D, float eps, wipa_stream_t stream) {
     WIPA_REQUIRE(logits && mask_first && mask_always && tokens && pos_dev && posd_dev && done_counter && sum_logprobs && not_done && tok_emb &&
@@ -1472,7 +1597,9 @@ static int step_tail_continuous(const char* who, const float* logits, int64_t ld
     WIPA_REQUIRE(y_dtype == WIPA_F32 || y_dtype == WIPA_BF16, "%s: bad dtype %d", who, y_dtype);
     RulesDev r = {tp.V, -1, -1};
     int rc = WIPA_OK;
-    if (sample) rc = sample_check(who, rules, sample, tp.logits, tp.V, tp.ldl, tp.mask_first, tp.mask_always, tp.eot, tp.n_ctx, &r);
+    WIPA_REQUIRE(!sample_rows || (!sample && ((uintptr_t)sample_rows % 16) == 0), "%s: sample_rows is 16-byte aligned and takes the place of sample", who);
+    if (sample || sample_rows)
+        rc = sample_check(who, rules, sample ? sample : sample_rows, tp.logits, tp.V, tp.ldl, tp.mask_first, tp.mask_always, tp.eot, tp.n_ctx, &r);
     else if (rules) rc = rules_check(who, rules, tp.logits, tp.V, tp.ldl, tp.mask_first, tp.mask_always, tp.eot, &r);
     if (rc != WIPA_OK) return rc;
     WIPA_REQUIRE(!no_speech_dev || (rules && no_speech_token >= 0 && no_speech_token < V), "%s: no_speech_token=%d outside the vocabulary of %d", who,
@@ -1484,7 +1611,13 @@ static int step_tail_continuous(const char* who, const float* logits, int64_t ld
     hipStream_t s = (hipStream_t)stream;
     const uint32_t* rec = (const uint32_t*)sample;
     const bool f32 = y_dtype == WIPA_F32;
-    if (rules) {
+    if (sample_rows) {  // a temperature per row: wipa_decoder_run_continuous_rows
+        const uint32_t* rows = (const uint32_t*)sample_rows;
+        if (rules && f32) hipLaunchKernelGGL((rows_tail_continuous_kernel<float, true>), grid, block, 0, s, q, r, rows, no_speech_dev, no_speech_token);
+        else if (rules) hipLaunchKernelGGL((rows_tail_continuous_kernel<__bf16, true>), grid, block, 0, s, q, r, rows, no_speech_dev, no_speech_token);
+        else if (f32) hipLaunchKernelGGL((rows_tail_continuous_kernel<float, false>), grid, block, 0, s, q, r, rows, nullptr, 0);
+        else hipLaunchKernelGGL((rows_tail_continuous_kernel<__bf16, false>), grid, block, 0, s, q, r, rows, nullptr, 0);
+    } else if (rules) {
         if (rec && f32) hipLaunchKernelGGL((rules_tail_continuous_kernel<float, true>), grid, block, 0, s, q, r, rec, no_speech_dev, no_speech_token);
         else if (rec) hipLaunchKernelGGL((rules_tail_continuous_kernel<__bf16, true>), grid, block, 0, s, q, r, rec, no_speech_dev, no_speech_token);
         else if (f32) hipLaunchKernelGGL((rules_tail_continuous_kernel<float, false>), grid, block, 0, s, q, r, rec, no_speech_dev, no_speech_token);
@@ -1503,7 +1636,7 @@ int wipa_step_tail_continuous(const float* logits, int64_t ldl, int B, int V, co
                               const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y,
                               int y_dtype, int D, float eps, wipa_stream_t stream) {
     return step_tail_continuous("wipa_decoder_run_continuous", logits, ldl, B, V, mask_first, mask_always, tokens, ld_tok, pos_dev, posd_dev,
-                                done_counter, n_init, eot, nullptr, sample, starts_dev, nullptr, 0, sum_logprobs, not_done, tok_emb, emb_dtype, emb_scale,
+                                done_counter, n_init, eot, nullptr, sample, nullptr, starts_dev, nullptr, 0, sum_logprobs, not_done, tok_emb, emb_dtype, emb_scale,
                                 pos_emb, n_ctx, x, ln_w, ln_b, y, y_dtype, D, eps, stream);
 }
 
@@ -1516,8 +1649,22 @@ int wipa_step_tail_continuous_rules(const float* logits, int64_t ldl, int B, int
     const char* who = "wipa_decoder_run_continuous_rules";
     WIPA_REQUIRE(rules, "%s: rules is required (without rules the call is wipa_decoder_run_continuous)", who);
     return step_tail_continuous(who, logits, ldl, B, V, mask_first, mask_always, tokens, ld_tok, pos_dev, posd_dev, done_counter, n_init, eot, rules,
-                                sample, starts_dev, no_speech_dev, no_speech_token, sum_logprobs, not_done, tok_emb, emb_dtype, emb_scale, pos_emb,
-                                n_ctx, x, ln_w, ln_b, y, y_dtype, D, eps, stream);
+                                sample, nullptr, starts_dev, no_speech_dev, no_speech_token, sum_logprobs, not_done, tok_emb, emb_dtype, emb_scale,
+                                pos_emb, n_ctx, x, ln_w, ln_b, y, y_dtype, D, eps, stream);
+}
+
+// wipa_decoder_run_continuous_rows: the CONTINUOUS tails with a temperature per row; rules may be NULL, sample_rows is required
+int wipa_step_tail_continuous_rows(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
+                                   int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init, int eot,
+                                   const wipa_decode_rules* rules, const void* sample_rows, const int32_t* starts_dev, float* no_speech_dev,
+                                   int no_speech_token, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
+                                   const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y,
+                                   int y_dtype, int D, float eps, wipa_stream_t stream) {
+    const char* who = "wipa_decoder_run_continuous_rows";
+    WIPA_REQUIRE(sample_rows, "%s: sample_rows (the sampling record with a row part) is required", who);
+    return step_tail_continuous(who, logits, ldl, B, V, mask_first, mask_always, tokens, ld_tok, pos_dev, posd_dev, done_counter, n_init, eot, rules,
+                                nullptr, sample_rows, starts_dev, rules ? no_speech_dev : nullptr, no_speech_token, sum_logprobs, not_done, tok_emb,
+                                emb_dtype, emb_scale, pos_emb, n_ctx, x, ln_w, ln_b, y, y_dtype, D, eps, stream);
 }
 
 // the tail on wipa_logits_greedy's per-wave partials: no logits, so no rules, no draw and no ragged rows

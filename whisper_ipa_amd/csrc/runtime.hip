@@ -432,6 +432,9 @@ struct StepCtx {
     // own column (NULL: not wanted), and the vocabulary column it is read at
     float* no_speech;
     int no_speech_token;
+    // wipa_decoder_run_continuous_rows (continuous with a temperature per row): the sampling record with a row part (wipa_sample_rows_bytes;
+    // NULL otherwise).  It takes the place of `sample`, which is NULL then, and the step ends in the rows_tail_continuous kernels.
+    const void* sample_rows;
 };
 // The logits projection with the greedy partials in its epilogue + a tail that merges them (round 4; WIPA_LOGITS_FUSED=0 restores
 // the plain GEMM + the row-scanning tail): bf16 models without fp8 decoder tables, <= 64 rows, tail-fused steps.  Measured on
@@ -629,6 +632,12 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
         // (with ctx.rules the timestamp rules, with ctx.sample the draw, with ctx.starts the RAGGED tails: position embedding and sampling
         // counter at the row's own position)
         const void* const* lw0 = w + WIPA_DEC_GLOBAL;
+        if (ctx.continuous && ctx.sample_rows)
+            return wipa_step_tail_continuous_rows(logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos, posd,
+                                                  done_counter_of(st, L), ctx.n_init, ctx.eot, ctx.rules, ctx.sample_rows, ctx.starts, ctx.no_speech,
+                                                  ctx.no_speech_token, (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), w[0],
+                                                  emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], nctx, x_first, (const float*)lw0[0],
+                                                  (const float*)lw0[1], ln, dt, d, 1e-5f, stream);
         if (ctx.continuous && ctx.rules)
             return wipa_step_tail_continuous_rules(logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos, posd,
                                                    done_counter_of(st, L), ctx.n_init, ctx.eot, ctx.rules, ctx.sample, ctx.starts, ctx.no_speech,
@@ -925,6 +934,7 @@ int state_fits(const char* who, const wipa_dec_layout& L, size_t state_bytes) {
 // The starts array of a ragged call enters with its ADDRESS too (NULL: no prompts): the replayed kernels read the rows' starts from it.
 // The ragged prompt pass (kind 3 + 16 * (sot_col + 1)) bakes its workspace in as well (NULL otherwise).
 // A continuous step with rules bakes in the no-speech array's address and its vocabulary column: the last two terms (NULL and 0 otherwise).
+// A continuous step with a temperature per row has its own variant bit, and its record's address stands in the sampling record's term.
 typedef std::tuple<const void*, const void*, const void*, const void*, int, int, int, int, int, int, int, int, int, const void*, const void*, const void*, const void*, int> GraphKey;  // ..., generation, kind: 0 step, 1 prefill, 2 lean step (no logit stores), rules, sampling record, starts, workspace, no-speech array, no-speech column
 // sampling lives in the fused step tail, like the rules: refused before anything is enqueued where the step cannot carry it
 int sample_servable(const char* who, const wipa_model_cfg* cfg, int B, const void* sample) {
@@ -978,14 +988,14 @@ int step_variant(const wipa_model_cfg* cfg, int B, const StepCtx& c) {
            64 * cfg->dec_cross_absorbed * (absorbed_block_fused() ? 2 : 1) + 256 * (int)tail_fused() + 512 * (int)absorbed_merge_out() +
            1024 * cfg->dec_cross_splits + 8192 * (int)lean_steps(cfg, B, c) +
            16384 * (cfg->dec_cross_absorbed ? wipa_cross_absorbed_loop_variant() : 0) + 65536 * (group_of(cfg) > 1 ? group_of(cfg) : 0) +
-           (1 << 28) * (int)c.continuous + (1 << 29) * (int)(c.continuous && c.rules);
+           (1 << 28) * (int)c.continuous + (1 << 29) * (int)(c.continuous && c.rules) + (1 << 30) * (int)(c.continuous && c.sample_rows);
 }
 // a key from the context of a decode call; the three rule terms are 0 without rules
 GraphKey graph_key(const wipa_model_cfg* cfg, const void* const* w, const void* state, int B, const StepCtx& c, int variant, int kind,
                    const void* workspace) {
     return GraphKey(state, (const void*)w, (const void*)c.mask_first, (const void*)c.mask_always, B, c.n_init, c.eot, variant,
                     cfg->weights_generation, kind, c.rules ? c.rules->timestamp_begin : 0, c.rules ? c.rules->no_timestamps : 0,
-                    c.rules ? c.rules->max_initial_timestamp_index : 0, c.sample, (const void*)c.starts, workspace,
+                    c.rules ? c.rules->max_initial_timestamp_index : 0, c.sample ? c.sample : c.sample_rows, (const void*)c.starts, workspace,
                     (const void*)c.no_speech, c.no_speech ? c.no_speech_token : 0);
 }
 // The executable graph cached under `key`.  When there is none, `enqueue` is captured on s (relaxed mode, nothing but kernel launches
@@ -1198,18 +1208,18 @@ extern "C" int wipa_decoder_run_sample(const wipa_model_cfg* cfg, const void* co
                                    stream);
 }
 
-// wipa_decoder_run_ragged and, with `continuous`, wipa_decoder_run_continuous (rules NULL) / wipa_decoder_run_continuous_rules: the same call
-// but for the tail the steps end in
+// wipa_decoder_run_ragged and, with `continuous`, wipa_decoder_run_continuous (rules NULL) / wipa_decoder_run_continuous_rules /
+// wipa_decoder_run_continuous_rows (sample_rows): the same call but for the tail the steps end in
 static int decoder_run(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init, int eot,
                        const float* mask_first, const float* mask_always, int n_steps, int use_graph, const wipa_decode_rules* rules,
                        const void* sample, const int32_t* starts_dev, bool continuous, float* no_speech_dev, int no_speech_token,
-                       wipa_stream_t stream) {
+                       const void* sample_rows, wipa_stream_t stream) {
     RT_CALL(cfg_check(cfg));
     SplitScope split_scope(cfg);
     WIPA_REQUIRE(w && state && mask_first && mask_always && B > 0 && n_steps >= 0, "wipa_decoder_run: bad arguments");
     // every step of the call but the LAST is "lean" when the logits projection carries the greedy partials: its logits are not
     // written (state.logits holds those of the last step of a call, which is what callers read)
-    const StepCtx full{rules, sample, starts_dev, n_init, eot, mask_first, mask_always, false, continuous, no_speech_dev, no_speech_token};
+    const StepCtx full{rules, sample, starts_dev, n_init, eot, mask_first, mask_always, false, continuous, no_speech_dev, no_speech_token, sample_rows};
     StepCtx lean = full;
     lean.lean = true;
     static const EntryNames who_ragged = {"wipa_decoder_run", "wipa_decoder_run_rules", "wipa_decoder_run_sample", "wipa_decoder_run_ragged"};
@@ -1217,7 +1227,9 @@ static int decoder_run(const wipa_model_cfg* cfg, const void* const* w, void* st
                                               "wipa_decoder_run_continuous"};
     static const EntryNames who_continuous_rules = {"wipa_decoder_run_continuous_rules", "wipa_decoder_run_continuous_rules",
                                                     "wipa_decoder_run_continuous_rules", "wipa_decoder_run_continuous_rules"};
-    const EntryNames& who = continuous ? (rules ? who_continuous_rules : who_continuous) : who_ragged;
+    static const EntryNames who_continuous_rows = {"wipa_decoder_run_continuous_rows", "wipa_decoder_run_continuous_rows",
+                                                   "wipa_decoder_run_continuous_rows", "wipa_decoder_run_continuous_rows"};
+    const EntryNames& who = !continuous ? who_ragged : sample_rows ? who_continuous_rows : rules ? who_continuous_rules : who_continuous;
     char* st = (char*)state;
     hipStream_t s = (hipStream_t)stream;
     wipa_dec_layout L;
@@ -1256,7 +1268,7 @@ extern "C" int wipa_decoder_run_ragged(const wipa_model_cfg* cfg, const void* co
                                        int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
                                        const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, wipa_stream_t stream) {
     return decoder_run(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, n_steps, use_graph, rules, sample, starts_dev, false,
-                       nullptr, 0, stream);
+                       nullptr, 0, nullptr, stream);
 }
 
 // ------------------------------------------------------------------ continuous batching: slots, admission, column shift
@@ -1350,7 +1362,7 @@ extern "C" int wipa_decoder_run_continuous(const wipa_model_cfg* cfg, const void
     RT_CALL(continuous_servable("wipa_decoder_run_continuous", cfg, B, starts_dev));
     WIPA_REQUIRE(n_init >= 1 && n_init <= 4, "wipa_decoder_run_continuous: 1..4 initial tokens per clip (got %d)", n_init);
     return decoder_run(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, n_steps, use_graph, nullptr, sample, starts_dev, true,
-                       nullptr, 0, stream);
+                       nullptr, 0, nullptr, stream);
 }
 
 extern "C" int wipa_decoder_run_continuous_rules(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
@@ -1366,7 +1378,27 @@ extern "C" int wipa_decoder_run_continuous_rules(const wipa_model_cfg* cfg, cons
     WIPA_REQUIRE(!no_speech_dev || (no_speech_token >= 0 && no_speech_token < cfg->n_vocab), "%s: no_speech_token=%d outside the vocabulary of %d",
                  who, no_speech_token, cfg->n_vocab);
     return decoder_run(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, n_steps, use_graph, rules, sample, starts_dev, true,
-                       no_speech_dev, no_speech_token, stream);
+                       no_speech_dev, no_speech_token, nullptr, stream);
+}
+
+// wipa_decoder_run_continuous_rules (rules) / wipa_decoder_run_continuous (rules == NULL) with a temperature per row: the steps end in the
+// rows_tail_continuous kernels, which read every row's 1 / temperature, attempt and stream from sample_rows when they run
+extern "C" int wipa_decoder_run_continuous_rows(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
+                                                int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
+                                                const wipa_decode_rules* rules, const void* sample_rows, const int32_t* starts_dev,
+                                                float* no_speech_dev, int no_speech_token, wipa_stream_t stream) {
+    RT_CALL(cfg_check(cfg));
+    const char* who = "wipa_decoder_run_continuous_rows";
+    WIPA_REQUIRE(sample_rows && ((uintptr_t)sample_rows % 16) == 0,
+                 "%s: sample_rows is required (the sampling record with a row part, wipa_sample_rows_bytes, 16-byte aligned; without it the call "
+                 "is wipa_decoder_run_continuous / _rules)", who);
+    RT_CALL(continuous_servable(who, cfg, B, starts_dev));
+    RT_CALL(sample_servable(who, cfg, B, sample_rows));
+    WIPA_REQUIRE(n_init >= 1 && n_init <= 4, "%s: 1..4 initial tokens per clip (got %d)", who, n_init);
+    WIPA_REQUIRE(!no_speech_dev || (rules && no_speech_token >= 0 && no_speech_token < cfg->n_vocab),
+                 "%s: no_speech_token=%d outside the vocabulary of %d (no_speech_dev needs rules)", who, no_speech_token, cfg->n_vocab);
+    return decoder_run(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, n_steps, use_graph, rules, nullptr, starts_dev, true,
+                       rules ? no_speech_dev : nullptr, no_speech_token, sample_rows, stream);
 }
 
 extern "C" int wipa_decoder_admit_rows(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_rows,

@@ -36,8 +36,15 @@ What differs from upstream, on purpose:
     decode state with refill (continuous.py) instead of one lockstep batch per round.  A file is a stream of
     windows with at most one in flight; files take places in input order and wait beyond ``slots``; the windows that become ready at
     the same check share one log-mel, one encoder, one language-detection and one admission call.  The per-window bookkeeping
-    (``_Books.window``) is the rounds schedule's.  Temperature 0 only: ``seed``, ``word_timestamps``, conditioning, ``best_of``, a
-    custom ``decode_fn`` and fp8 models are refused by name.
+    (``_Books.window``) is the rounds schedule's.  With ``seed`` the temperature fallback runs on this schedule too: a window that
+    fails the thresholds is not booked, its file keeps its place, and the SAME window becomes pending again at the next temperature
+    of the schedule, with the stream (seek, file index), the attempt index and the seed of the rounds schedule's retry -- so both
+    schedules draw the same tokens.  It is admitted at the check that retired the failed attempt, from the encoder features its first
+    admission left (no second log-mel, encoder or language detection), into a row that sits beside greedy first attempts and beside
+    retries of other windows at other temperatures: the decode state's sampling record holds a temperature per row
+    (wipa_decoder_run_continuous_rows).  The window is booked when it passes or the schedule ends (the last attempt is kept).
+    ``word_timestamps``, conditioning, ``best_of``, a custom ``decode_fn`` and fp8 models are refused by name, and so is ``seed`` with a
+    custom ``stream_fn`` that does not declare ``stream_fn.retries = True``.
 """
 from __future__ import annotations
 
@@ -242,13 +249,14 @@ def _window_samples(clip: np.ndarray, seek: int, size: int) -> np.ndarray:
 
 
 # ---------------------------------------------------------------- schedule="continuous"
-def _refuse_continuous(model, seed, word_timestamps, condition_on_previous_text, initial_prompt, best_of, decode_fn) -> None:
+def _refuse_continuous(model, seed, word_timestamps, condition_on_previous_text, initial_prompt, best_of, decode_fn, stream_fn=None) -> None:
     """what ``schedule="continuous"`` does not serve, each refused by the option's name before anything is decoded"""
     def no(name, why):
         raise NotImplementedError(f"transcribe(schedule='continuous'): {name} is not implemented ({why}); use schedule='rounds'")
 
-    if seed is not None:
-        no("seed", "the retries need a temperature per row, which the sampling record of a decode state does not hold")
+    if seed is not None and stream_fn is not None and not getattr(stream_fn, "retries", False):
+        no("seed", "the retries hand a window out again with a temperature, an attempt and a stream of its own; a custom stream_fn that "
+                   "serves them declares stream_fn.retries = True, as a custom decode_fn brings a fallback_fn")
     if word_timestamps:
         no("word_timestamps", "the alignment runs on a round's windows")
     if condition_on_previous_text:
@@ -269,8 +277,9 @@ class StreamStats:
     schedule: object = None                                   # what the stream returned: the run's continuous.ScheduleStats
     rows: int = 0                                             # rows of the decode state: min(slots, files)
     waited: List[int] = field(default_factory=list)           # the files that queued for a slot, in the order they got one
-    groups: List[List[Tuple[int, int]]] = field(default_factory=list)     # per admitted group: its windows (file, seek)
+    groups: List[List[Tuple[int, int]]] = field(default_factory=list)     # per admitted group: its FRESH windows (file, seek)
     detected: List[List[Tuple[int, int]]] = field(default_factory=list)   # per detect_language call: the windows it looked at
+    retries: List[Tuple[int, int, int]] = field(default_factory=list)     # (file, seek, attempt) of every retry, in the order they became pending
 
 
 @dataclass
@@ -286,10 +295,16 @@ class _WindowResult:
 class _WindowSource:
     """``continuous.run_stream``'s source over the files of one ``transcribe`` call.  A file is a stream of windows with at most one in
     flight: its next window, the clip ``(file, seek)``, exists once the previous one has retired and ``books`` knows the seek.  Files
-    take a place in input order, at most ``slots`` of them at a time, and keep it until their last window has retired; the others wait."""
+    take a place in input order, at most ``slots`` of them at a time, and keep it until their last window has retired; the others wait.
+    ``temps`` and ``seed``: the temperature fallback.  ``pending`` then returns (clip, limit, draw) -- draw None for a window's first
+    attempt, (temps[attempt], attempt, (seek, file)) for a retry -- and a window that fails the thresholds with temperatures left is not
+    booked: the same clip becomes pending again.  ``on_booked(clip)``, when the stream sets it, hears of every window that is booked."""
 
-    def __init__(self, clips, content_frames, books: _Books, slots: int, limit: int, stats: StreamStats):
+    def __init__(self, clips, content_frames, books: _Books, slots: int, limit: int, stats: StreamStats, temps=(0.0,), seed=None):
         self.clips, self.content_frames, self.books, self.limit, self.stats = clips, content_frames, books, int(limit), stats
+        self.temps, self.seed = tuple(float(t) for t in temps), seed
+        self.attempt = {}              # file -> index in temps of its window in flight
+        self.on_booked = None
         self.slots = int(slots)
         self.waiting = deque(i for i in range(len(clips)) if content_frames[i] > 0)
         self.active: List[int] = []    # files that hold a place, in the order they got it
@@ -309,7 +324,11 @@ class _WindowSource:
         for i in self.ready:
             clip = (i, self.books.seek[i])
             self.size[clip] = min(N_FRAMES, self.content_frames[i] - self.books.seek[i])
-            out.append((clip, self.limit))
+            attempt = self.attempt.setdefault(i, 0)
+            if self.seed is None:
+                out.append((clip, self.limit))
+            else:  # the rounds schedule's retry: stream (seek, file index), the index in the schedule
+                out.append((clip, self.limit, (self.temps[attempt], attempt, (clip[1], i)) if attempt else None))
         self.ready = []
         return out
 
@@ -332,8 +351,19 @@ class _WindowSource:
         tokens = [int(t) for t in tokens]
         text = tok.decode([t for t in tokens if t < self.books.tb]).strip()
         comp = len(text.encode("utf-8")) / max(len(zlib.compress(text.encode("utf-8"))), 1) if text else float("nan")
-        res = _WindowResult(tokens, float(sum_logprob) / (len(tokens) + 1), float(no_speech), comp, 0.0, self.books.languages[i])
-        self.books.window(i, self.size.pop(clip), res, False)
+        attempt = self.attempt.get(i, 0)
+        res = _WindowResult(tokens, float(sum_logprob) / (len(tokens) + 1), float(no_speech), comp, self.temps[attempt], self.books.languages[i])
+        books = self.books
+        if self.seed is not None and attempt + 1 < len(self.temps) and _needs_fallback(
+                res, books.compression_ratio_threshold, books.logprob_threshold, books.no_speech_threshold):
+            self.attempt[i] = attempt + 1  # not booked: the file keeps its place and the same window is pending again
+            self.stats.retries.append((i, at, attempt + 1))
+            self.ready.append(i)
+            return
+        self.attempt[i] = 0
+        self.books.window(i, self.size.pop(clip), res, attempt > 0)  # upstream's "the last attempt is kept"
+        if self.on_booked is not None:
+            self.on_booked(clip)
         if self.books.seek[i] < self.content_frames[i]:
             self.ready.append(i)
         else:
@@ -341,7 +371,7 @@ class _WindowSource:
 
 
 def _transcribe_continuous(model, clips, content_frames, books: _Books, language, decode_options, stream_fn, slots: int,
-                           check_every: int) -> StreamStats:
+                           check_every: int, temps=(0.0,), seed=None) -> StreamStats:
     """``transcribe(schedule="continuous")``: every window of every file through min(slots, files) rows of one decode state.  The windows
     that become ready at the same check form one group: one log-mel call from the windows' own samples, one encoder call, one
     detect_language call for the windows of files whose language is still unknown, one admission."""
@@ -350,12 +380,12 @@ def _transcribe_continuous(model, clips, content_frames, books: _Books, language
     stats = StreamStats(rows=max(min(int(slots), len(clips)), 1))
     n_text_ctx = model.dims.n_text_ctx if model is not None else 448
     limit = decode_options.get("sample_len") or n_text_ctx // 2
-    source = _WindowSource(clips, content_frames, books, stats.rows, limit, stats)
+    source = _WindowSource(clips, content_frames, books, stats.rows, limit, stats, temps, seed)
     if stream_fn is None:
         from .continuous import stream_windows
 
         def stream_fn(source, slots, check_every):
-            return stream_windows(model, source, {**decode_options, "language": language}, slots=slots, check_every=check_every)
+            return stream_windows(model, source, {**decode_options, "language": language}, slots=slots, check_every=check_every, seed=seed)
 
     stats.schedule = stream_fn(source, slots=stats.rows, check_every=check_every)
     return stats
@@ -449,10 +479,12 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
     model's alignment (``results``: the windows' decode results, ``text_tokens[j]`` the ids below EOT of window j's segments,
     ``num_frames[j]`` its content in mel frames); it is required with a custom ``decode_fn``.
     ``schedule="continuous"``: the windows go through ``slots`` rows of ONE decode state with refill instead of one lockstep batch per
-    round (``_transcribe_continuous``); the host looks at the rows every ``check_every`` steps.  Temperature 0 only; ``seed``,
-    ``word_timestamps``, ``condition_on_previous_text`` / ``initial_prompt``, ``best_of``, a custom ``decode_fn`` and fp8 models are
-    refused.  ``stream_fn(source, slots=, check_every=)`` replaces the model's continuous decoder (tests); ``stats_out``: a list that
-    receives the run's ``StreamStats``."""
+    round (``_transcribe_continuous``); the host looks at the rows every ``check_every`` steps.  ``seed`` runs the temperature schedule
+    there too (a retried window is pending again with its own temperature; module docstring).  ``word_timestamps``,
+    ``condition_on_previous_text`` / ``initial_prompt``, ``best_of``, a custom ``decode_fn`` and fp8 models are refused.
+    ``stream_fn(source, slots=, check_every=)`` replaces the model's continuous decoder (tests); with a seed it must declare
+    ``stream_fn.retries = True`` and take ``source.pending()`` entries of (clip, limit, draw).  ``stats_out``: a list that receives the
+    run's ``StreamStats``."""
     _refuse(condition_on_previous_text, initial_prompt, word_timestamps, clip_timestamps, hallucination_silence_threshold, temperature,
             decode_options, can_align=align_fn is not None or (model is not None and decode_fn is None),
             can_retry=decode_fn is None or fallback_fn is not None)
@@ -484,7 +516,7 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
     if schedule not in ("rounds", "continuous"):
         raise ValueError(f"transcribe: schedule is 'rounds' or 'continuous', got {schedule!r}")
     if schedule == "continuous":
-        _refuse_continuous(model, seed, word_timestamps, condition_on_previous_text, initial_prompt, best_of, decode_fn)
+        _refuse_continuous(model, seed, word_timestamps, condition_on_previous_text, initial_prompt, best_of, decode_fn, stream_fn)
     elif decode_fn is None:
         decode_fn = _model_decoder(model, decode_options)
         fallback_fn = fallback_fn or decode_fn.retry
@@ -499,7 +531,7 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
     seek, languages, all_segments, all_tokens, prompt_reset_since = (books.seek, books.languages, books.all_segments, books.all_tokens,
                                                                      books.prompt_reset_since)
     if schedule == "continuous":
-        stats = _transcribe_continuous(model, clips, content_frames, books, language, decode_options, stream_fn, slots, check_every)
+        stats = _transcribe_continuous(model, clips, content_frames, books, language, decode_options, stream_fn, slots, check_every, temps, seed)
         if stats_out is not None:
             stats_out.append(stats)
     while schedule == "rounds":
