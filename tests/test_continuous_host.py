@@ -173,6 +173,93 @@ def test_step_counts_and_the_bound_from_the_lengths():
     assert lockstep_steps([], 4) == 0 and continuous_steps_bound([], 4, N_INIT, 8) == 0
 
 
+class BothStepper:
+    """a scripted stepper that serves both schedulers: slots x n_ctx token table, n_init = 3; clip i's k-th generated token is
+    100 * (i + 1) + k, and it says EOT after ``lengths[i]`` tokens or at its limit.  ``admit`` takes ``run_schedule``'s pairs (the limit is
+    ``limits[clip]``) and ``run_stream``'s triples; ``last_tokens`` / ``retire`` and ``snapshot`` read the same table."""
+
+    N_INIT = 3
+
+    def __init__(self, slots, lengths, limits, n_ctx):
+        self.slots, self.lengths, self.limits, self.n_ctx = slots, lengths, limits, n_ctx
+        self.tokens = np.full((slots, n_ctx), EOT, dtype=np.int64)
+        self.start, self.clip, self.limit = [0] * slots, [None] * slots, [0] * slots
+        self.pos = 0
+        self.rows = {}
+
+    def admit(self, entries):
+        for slot, clip, *limit in entries:
+            assert self.pos + self.N_INIT < self.n_ctx
+            self.clip[slot], self.start[slot], self.limit[slot] = clip, self.pos, limit[0] if limit else self.limits[clip]
+            self.tokens[slot, self.pos:self.pos + self.N_INIT] = [1, 2, 3]
+
+    def run(self, n):
+        for _ in range(n):
+            p = self.pos
+            assert p + 1 < self.n_ctx, "a step past the table"
+            for slot, clip in enumerate(self.clip):
+                own = self.start[slot] + self.N_INIT
+                if clip is None or p + 1 < own:
+                    continue
+                k = p + 1 - own
+                done = self.tokens[slot, p] == EOT or k >= self.limit[slot] or k >= self.lengths[clip]
+                self.tokens[slot, p + 1] = EOT if done else 100 * (clip + 1) + k
+            self.pos += 1
+
+    def shift(self, shift):
+        assert 0 < shift <= self.pos
+        n = self.pos + 1 - shift
+        self.tokens[:, :n] = self.tokens[:, shift:shift + n].copy()
+        self.pos -= shift
+        self.start = [max(s - shift, 0) for s in self.start]
+
+    def last_tokens(self):
+        return self.tokens[:, self.pos].copy()
+
+    def retire(self, slot, clip, first_column, n_columns):
+        assert self.clip[slot] == clip and first_column == self.start[slot] + self.N_INIT
+        self.rows[clip] = _text(self.tokens[slot, first_column:first_column + n_columns].tolist())
+
+    def snapshot(self):
+        return self.tokens[:, : self.pos + 1].copy(), np.zeros(self.slots, dtype=np.float32), np.zeros(self.slots, dtype=np.float32)
+
+
+def test_both_schedulers_make_the_same_schedule():
+    """the same 9 clips through 3 slots of a 48-column table, check_every = 4, n_init = 3: ``run_schedule`` and ``run_stream`` (a source
+    whose first ``pending()`` gives every clip) take the same steps, shift by the same amounts, admit the same clips into the same slots at
+    the same columns, retire them in the same order and hand out the same token rows.  Clips 1, 5 and 8 never say EOT: they end at their
+    limits."""
+    from whisper_ipa_amd.continuous import run_schedule, run_stream
+
+    n_ctx, slots, check_every = 48, 3, 4
+    limits = [12, 25, 16, 18, 9, 22, 15, 19, 20]
+    lengths = [10, 99, 16, 17, 2, 99, 14, 18, 99]  # text tokens before EOT; 99: none within the limit
+    a = BothStepper(slots, lengths, limits, n_ctx)
+    sa = run_schedule(a, len(limits), slots, BothStepper.N_INIT, limits, EOT, n_ctx, check_every)
+
+    class Source:
+        def __init__(self):
+            self.clips, self.rows = [(i, n) for i, n in enumerate(limits)], {}
+
+        def pending(self):
+            out, self.clips = self.clips, []
+            return out
+
+        def retired(self, clip, tokens, sum_logprob, no_speech):
+            assert clip not in self.rows
+            self.rows[clip] = list(tokens)
+
+    b, src = BothStepper(slots, lengths, limits, n_ctx), Source()
+    sb = run_stream(b, src, slots, BothStepper.N_INIT, EOT, n_ctx, check_every)
+    assert len(sa.shifts) >= 2 and all(x > 0 for x in sa.shifts)
+    assert (sa.steps, sa.shifts, sa.admissions, sa.retired) == (sb.steps, sb.shifts, sb.admissions, sb.retired)
+    assert sorted(sa.retired) == list(range(9)) and sa.retired != sorted(sa.retired)
+    want = {i: [100 * (i + 1) + k for k in range(min(lengths[i], limits[i]))] for i in range(9)}
+    assert a.rows == want and src.rows == want
+    assert [len(want[i]) == limits[i] for i in range(9)].count(True) >= 1  # a clip that ended by its limit
+    assert (a.tokens == b.tokens).all()
+
+
 def test_refusals_name_the_option():
     from whisper_ipa_amd.continuous import refuse_unserved
     from whisper_ipa_amd.decoding import DecodingOptions

@@ -27,7 +27,6 @@ out again, with its draw; ``_GroupStepper`` admits it from the encoder features 
 from __future__ import annotations
 
 import ctypes as C
-import zlib
 from collections import deque
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -36,7 +35,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .decoding import (DecoderState, DecodingOptions, DecodingResult, Sampling, _mask, _suppress_lists, detect_language, timestamp_rules)
+from .decoding import (DecoderState, DecodingOptions, DecodingResult, Sampling, _mask, _suppress_lists, compression_ratio, detect_language,
+                       timestamp_rules)
 from .runtime import on_stream, ptr, sptr, stream_id
 from .tokenizer import get_tokenizer
 
@@ -49,7 +49,7 @@ class ScheduleStats:
     admissions: List[Tuple[int, int, int]] = field(default_factory=list)  # (slot, clip, column) in admission order
     retired: List[int] = field(default_factory=list)                      # clips in the order they were retired
     groups: List[int] = field(default_factory=list)                       # run_stream: the sizes of the admitted groups, in order
-    live_rows: List[int] = field(default_factory=list)                    # run_stream: the live rows of every interval of check_every steps
+    live_rows: List[int] = field(default_factory=list)                    # the live rows of every interval of check_every steps
 
 
 def default_column_limit(n_ctx: int, n_init: int, check_every: int) -> int:
@@ -70,7 +70,8 @@ def run_schedule(stepper, n_clips: int, slots: int, n_init: int, limits: Sequenc
       stepper.shift(shift)              move every column down by ``shift``
 
     Clip i may generate ``limits[i]`` tokens.  A row is finished when its last token is ``eot`` or it has generated its limit; clips are
-    admitted in input order into the lowest free slot.  The column counter is mirrored here (it advances by one per step)."""
+    admitted in input order into the lowest free slot.  The column counter is mirrored on the host (it advances by one per step); the loop
+    is ``_run_slots``, which ``run_stream`` shares."""
     if slots < 1 or check_every < 1:
         raise ValueError(f"decode_continuous: slots = {slots} and check_every = {check_every} must be positive")
     if len(limits) != n_clips:
@@ -86,47 +87,10 @@ def run_schedule(stepper, n_clips: int, slots: int, n_init: int, limits: Sequenc
     if not (column_limit + n_init < n_ctx and column_limit >= need):
         raise ValueError(f"decode_continuous: column_limit = {column_limit} outside {need} .. {n_ctx - 1 - n_init} (n_init + longest sample_len + "
                          f"2 * check_every - 1 .. n_text_ctx - 1 - n_init)")
-    stats = ScheduleStats()
-    queue = deque(range(n_clips))
-    live: Dict[int, Tuple[int, int]] = {}  # slot -> (clip, start)
-    pos = 0
-
-    def admit_pending():
-        pairs = []
-        for slot in range(slots):
-            if not queue:
-                break
-            if slot not in live:
-                clip = queue.popleft()
-                live[slot] = (clip, pos)
-                pairs.append((slot, clip))
-                stats.admissions.append((slot, clip, pos))
-        if pairs:
-            stepper.admit(pairs)
-
-    admit_pending()
-    while live:
-        if pos + check_every > column_limit:  # the next interval would pass the limit
-            shift = min(start for _, start in live.values())
-            assert shift > 0, "decode_continuous: a live row spans the whole column window (the shift would be 0)"
-            stepper.shift(shift)
-            stats.shifts.append(shift)
-            pos -= shift
-            live = {slot: (clip, start - shift) for slot, (clip, start) in live.items()}
-            assert pos + check_every <= column_limit
-        stepper.run(check_every)
-        stats.steps += check_every
-        pos += check_every
-        last = stepper.last_tokens()
-        for slot in sorted(live):
-            clip, start = live[slot]
-            generated = pos - (start + n_init) + 1  # columns start + n_init .. pos
-            if generated >= 1 and (int(last[slot]) == eot or generated >= int(limits[clip])):
-                stepper.retire(slot, clip, start + n_init, min(generated, int(limits[clip])))
-                stats.retired.append(clip)
-                del live[slot]
-        admit_pending()
-    return stats
+    batches = iter([[(clip, limits[clip]) for clip in range(n_clips)]])  # every clip is pending from the start, none later
+    return _run_slots(stepper, ScheduleStats(), slots, n_init, eot, check_every, column_limit, lambda: next(batches, []),
+                      lambda group: stepper.admit([(slot, clip) for slot, clip, _ in group]),
+                      lambda pos: (stepper.last_tokens(), stepper.retire))
 
 
 def run_stream(stepper, source, slots: int, n_init: int, eot: int, n_ctx: int, check_every: int = 8,
@@ -158,34 +122,61 @@ def run_stream(stepper, source, slots: int, n_init: int, eot: int, n_ctx: int, c
     if not column_limit + n_init < n_ctx:
         raise ValueError(f"decode_continuous: column_limit = {column_limit} above {n_ctx - 1 - n_init} (n_text_ctx - 1 - n_init)")
     stats = ScheduleStats()
+
+    def admit(group):
+        for _, _, limit, *_ in group:
+            # the bound of run_schedule, per clip: after a shift the oldest live row starts at column 0 and the next interval must fit
+            need = n_init + limit + 2 * check_every - 1
+            if limit < 1 or need > column_limit:
+                raise ValueError(f"decode_continuous: a clip's limit of {limit} tokens is outside 1 .. {column_limit - n_init - 2 * check_every + 1} "
+                                 f"(column_limit - n_init - 2 * check_every + 1)")
+        stepper.admit(group)
+        stats.groups.append(len(group))
+
+    def check(pos):
+        tokens, sums, no_speech = stepper.snapshot()
+
+        def retire(slot, clip, own, n_columns):
+            row = [int(t) for t in tokens[slot][own:own + n_columns]]
+            if eot in row:
+                row = row[: row.index(eot)]
+            source.retired(clip, row, float(sums[slot]), float(no_speech[slot]))
+
+        return [row[pos] for row in tokens], retire
+
+    return _run_slots(stepper, stats, slots, n_init, eot, check_every, column_limit, source.pending, admit, check)
+
+
+def _run_slots(stepper, stats: ScheduleStats, slots: int, n_init: int, eot: int, check_every: int, column_limit: int, pending, admit,
+               check) -> ScheduleStats:
+    """The loop of ``run_schedule`` and ``run_stream``: the column mirror, the shift rule, admission into the lowest free slot, the
+    finished test and the stats.  What the two protocols differ in comes as three callables:
+
+      pending() -> [(clip, limit, *draw)]   the clips that join the queue now; asked at the start and after every check
+      admit(group)                          group [(slot, clip, limit, *draw)]: the clips that start at the current column, one call
+      check(pos) -> (last, retire)          after an interval: ``last[slot]`` is the token a slot holds at column ``pos`` (this is where the
+                                            host waits), ``retire(slot, clip, first_column, n_columns)`` takes a finished clip's columns out"""
     queue: deque = deque()
     live: Dict[int, Tuple[object, int, int]] = {}  # slot -> (clip, start, limit)
     pos = 0
 
     def admit_pending():
-        queue.extend(source.pending())
-        triples = []
+        queue.extend(pending())
+        group = []
         for slot in range(slots):
             if not queue:
                 break
             if slot not in live:
                 clip, limit, *draw = queue.popleft()
-                limit = int(limit)
-                # the bound of run_schedule, per clip: after a shift the oldest live row starts at column 0 and the next interval must fit
-                need = n_init + limit + 2 * check_every - 1
-                if limit < 1 or need > column_limit:
-                    raise ValueError(f"decode_continuous: a clip's limit of {limit} tokens is outside 1 .. {column_limit - n_init - 2 * check_every + 1} "
-                                     f"(column_limit - n_init - 2 * check_every + 1)")
-                live[slot] = (clip, pos, limit)
-                triples.append((slot, clip, limit, *draw))
+                live[slot] = (clip, pos, int(limit))
+                group.append((slot, clip, int(limit), *draw))
                 stats.admissions.append((slot, clip, pos))
-        if triples:
-            stepper.admit(triples)
-            stats.groups.append(len(triples))
+        if group:
+            admit(group)
 
     admit_pending()
     while live:
-        if pos + check_every > column_limit:
+        if pos + check_every > column_limit:  # the next interval would pass the limit
             shift = min(start for _, start, _ in live.values())
             assert shift > 0, "decode_continuous: a live row spans the whole column window (the shift would be 0)"
             stepper.shift(shift)
@@ -197,16 +188,13 @@ def run_stream(stepper, source, slots: int, n_init: int, eot: int, n_ctx: int, c
         stepper.run(check_every)
         stats.steps += check_every
         pos += check_every
-        tokens, sums, no_speech = stepper.snapshot()
+        last, retire = check(pos)
         for slot in sorted(live):
             clip, start, limit = live[slot]
             own = start + n_init
             generated = pos - own + 1  # columns own .. pos
-            if generated >= 1 and (int(tokens[slot][pos]) == eot or generated >= limit):
-                row = [int(t) for t in tokens[slot][own:own + min(generated, limit)]]
-                if eot in row:
-                    row = row[: row.index(eot)]
-                source.retired(clip, row, float(sums[slot]), float(no_speech[slot]))
+            if generated >= 1 and (int(last[slot]) == eot or generated >= limit):
+                retire(slot, clip, own, min(generated, limit))
                 stats.retired.append(clip)
                 del live[slot]
         admit_pending()
@@ -343,26 +331,17 @@ class DeviceStepper:
 
     def run(self, n: int):
         pk, st = self.pk, self.st
+        common = (C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), self.B, self.n_init, self.eot, ptr(self.m_first),
+                  ptr(self.m_always), n, int(self.use_graph), C.byref(self.rules) if self.rules is not None else None)
+        rec = ptr(self.rec) if self.rec is not None else None
+        no_speech = (ptr(self.no_speech) if self.no_speech is not None else None, self.no_speech_token)
         if self.rows is not None:
-            _lib.check(self.L.wipa_decoder_run_continuous_rows(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), self.B, self.n_init,
-                                                               self.eot, ptr(self.m_first), ptr(self.m_always), n, int(self.use_graph),
-                                                               C.byref(self.rules) if self.rules is not None else None, ptr(self.rows),
-                                                               ptr(self.starts), ptr(self.no_speech) if self.no_speech is not None else None,
-                                                               self.no_speech_token, sptr(self.s)), "wipa_decoder_run_continuous_rows")
-            self.pos += n
-            return
-        if self.rules is not None:
-            _lib.check(self.L.wipa_decoder_run_continuous_rules(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), self.B, self.n_init,
-                                                                self.eot, ptr(self.m_first), ptr(self.m_always), n, int(self.use_graph),
-                                                                C.byref(self.rules), ptr(self.rec) if self.rec is not None else None,
-                                                                ptr(self.starts), ptr(self.no_speech) if self.no_speech is not None else None,
-                                                                self.no_speech_token, sptr(self.s)), "wipa_decoder_run_continuous_rules")
-            self.pos += n
-            return
-        _lib.check(self.L.wipa_decoder_run_continuous(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), self.B, self.n_init,
-                                                      self.eot, ptr(self.m_first), ptr(self.m_always), n, int(self.use_graph), None,
-                                                      ptr(self.rec) if self.rec is not None else None, ptr(self.starts), sptr(self.s)),
-                   "wipa_decoder_run_continuous")
+            name, args = "wipa_decoder_run_continuous_rows", (ptr(self.rows), ptr(self.starts), *no_speech)
+        elif self.rules is not None:
+            name, args = "wipa_decoder_run_continuous_rules", (rec, ptr(self.starts), *no_speech)
+        else:
+            name, args = "wipa_decoder_run_continuous", (rec, ptr(self.starts))
+        _lib.check(getattr(self.L, name)(*common, *args, sptr(self.s)), name)
         self.pos += n
 
     def last_tokens(self) -> np.ndarray:
@@ -632,7 +611,7 @@ def decode_continuous(model, mels_or_features: torch.Tensor, options: DecodingOp
         if tok.eot in row:
             row = row[: row.index(tok.eot)]
         text = tok.decode([t for t in row if t < tok.timestamp_begin]).strip()
-        comp = len(text.encode("utf-8")) / max(len(zlib.compress(text.encode("utf-8"))), 1) if text else float("nan")
+        comp = compression_ratio(text)
         lang = options.language or "en"
         if options.language is None:
             lang = LANGUAGES[feats.lang_token[i] - tok.sot - 1]

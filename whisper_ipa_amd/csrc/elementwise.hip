@@ -1577,15 +1577,30 @@ extern "C" int wipa_step_embed_ragged(const float* logits, int64_t ldl, int B, i
                           starts_dev, sum_logprobs, not_done, tok_emb, emb_dtype, emb_scale, pos_emb, n_ctx, x, ln_w, ln_b, y, y_dtype, D, eps, stream);
 }
 
-// the CONTINUOUS tails (declared in wipa_common.h for wipa_decoder_run_continuous / _rules; not exported): the checks of wipa_step_tail;
-// starts_dev is int32 [2][B], the rows' first own columns and then the tokens each may generate.  With rules the tails are the
-// rules_tail_continuous kernels, and no_speech_dev (float [B], may be NULL) receives softmax(row)[no_speech_token] at a row's first column.
-static int step_tail_continuous(const char* who, const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
-                                int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init, int eot,
-                                const wipa_decode_rules* rules, const void* sample, const void* sample_rows, const int32_t* starts_dev,
-                                float* no_speech_dev, int no_speech_token, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
-                                const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y,
-                                int y_dtype, int D, float eps, wipa_stream_t stream) {
+template <typename TO>
+static void launch_tail_continuous_as(const TailArgs<true>& q, int B, bool rules, RulesDev r, const uint32_t* rec, const uint32_t* rows,
+                                      float* no_speech_dev, int no_speech_token, hipStream_t s) {
+    const dim3 grid(B), block(GS_THREADS);
+    if (rows && rules) hipLaunchKernelGGL((rows_tail_continuous_kernel<TO, true>), grid, block, 0, s, q, r, rows, no_speech_dev, no_speech_token);
+    else if (rows) hipLaunchKernelGGL((rows_tail_continuous_kernel<TO, false>), grid, block, 0, s, q, r, rows, nullptr, 0);
+    else if (rules && rec) hipLaunchKernelGGL((rules_tail_continuous_kernel<TO, true>), grid, block, 0, s, q, r, rec, no_speech_dev, no_speech_token);
+    else if (rules) hipLaunchKernelGGL((rules_tail_continuous_kernel<TO, false>), grid, block, 0, s, q, r, rec, no_speech_dev, no_speech_token);
+    else if (rec) hipLaunchKernelGGL((sample_tail_continuous_kernel<TO>), grid, block, 0, s, q, rec);
+    else hipLaunchKernelGGL((greedy_tail_continuous_kernel<TO>), grid, block, 0, s, q);
+}
+
+// The CONTINUOUS tails (declared in wipa_common.h for the runtime; not exported): the checks of wipa_step_tail; starts_dev is int32 [2][B],
+// the rows' first own columns and then the tokens each may generate.  rules, sample, sample_rows and no_speech_dev may each be NULL;
+// rules and sample_rows name the exported entry point whose error prefix applies.  With rules the tails are the rules_tail_continuous
+// kernels, and no_speech_dev (float [B]) receives softmax(row)[no_speech_token] at a row's first column; sample_rows (the sampling record
+// with a row part) takes the place of sample and selects the rows_tail_continuous kernels: a temperature per row.
+int wipa_step_tail_continuous(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always, int32_t* tokens,
+                              int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init, int eot,
+                              const wipa_decode_rules* rules, const void* sample, const void* sample_rows, const int32_t* starts_dev,
+                              float* no_speech_dev, int no_speech_token, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
+                              const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y,
+                              int y_dtype, int D, float eps, wipa_stream_t stream) {
+    const char* who = sample_rows ? "wipa_decoder_run_continuous_rows" : rules ? "wipa_decoder_run_continuous_rules" : "wipa_decoder_run_continuous";
     WIPA_REQUIRE(logits && mask_first && mask_always && tokens && pos_dev && posd_dev && done_counter && sum_logprobs && not_done && tok_emb &&
                      pos_emb && x && ln_w && ln_b && y && starts_dev && B > 0 && n_ctx > 0 && n_init >= 1 && ld_tok >= n_ctx,
                  "%s: bad arguments of the step's tail (starts_dev is required)", who);
@@ -1607,64 +1622,15 @@ static int step_tail_continuous(const char* who, const float* logits, int64_t ld
     TailArgs<true> q = {};
     static_cast<TailParams&>(q) = tp;
     q.start = starts_dev;
-    const dim3 grid(B), block(GS_THREADS);
     hipStream_t s = (hipStream_t)stream;
-    const uint32_t* rec = (const uint32_t*)sample;
-    const bool f32 = y_dtype == WIPA_F32;
-    if (sample_rows) {  // a temperature per row: wipa_decoder_run_continuous_rows
-        const uint32_t* rows = (const uint32_t*)sample_rows;
-        if (rules && f32) hipLaunchKernelGGL((rows_tail_continuous_kernel<float, true>), grid, block, 0, s, q, r, rows, no_speech_dev, no_speech_token);
-        else if (rules) hipLaunchKernelGGL((rows_tail_continuous_kernel<__bf16, true>), grid, block, 0, s, q, r, rows, no_speech_dev, no_speech_token);
-        else if (f32) hipLaunchKernelGGL((rows_tail_continuous_kernel<float, false>), grid, block, 0, s, q, r, rows, nullptr, 0);
-        else hipLaunchKernelGGL((rows_tail_continuous_kernel<__bf16, false>), grid, block, 0, s, q, r, rows, nullptr, 0);
-    } else if (rules) {
-        if (rec && f32) hipLaunchKernelGGL((rules_tail_continuous_kernel<float, true>), grid, block, 0, s, q, r, rec, no_speech_dev, no_speech_token);
-        else if (rec) hipLaunchKernelGGL((rules_tail_continuous_kernel<__bf16, true>), grid, block, 0, s, q, r, rec, no_speech_dev, no_speech_token);
-        else if (f32) hipLaunchKernelGGL((rules_tail_continuous_kernel<float, false>), grid, block, 0, s, q, r, rec, no_speech_dev, no_speech_token);
-        else hipLaunchKernelGGL((rules_tail_continuous_kernel<__bf16, false>), grid, block, 0, s, q, r, rec, no_speech_dev, no_speech_token);
-    } else if (rec && f32) hipLaunchKernelGGL((sample_tail_continuous_kernel<float>), grid, block, 0, s, q, rec);
-    else if (rec) hipLaunchKernelGGL((sample_tail_continuous_kernel<__bf16>), grid, block, 0, s, q, rec);
-    else if (f32) hipLaunchKernelGGL((greedy_tail_continuous_kernel<float>), grid, block, 0, s, q);
-    else hipLaunchKernelGGL((greedy_tail_continuous_kernel<__bf16>), grid, block, 0, s, q);
+    if (y_dtype == WIPA_F32)
+        launch_tail_continuous_as<float>(q, B, rules != nullptr, r, (const uint32_t*)sample, (const uint32_t*)sample_rows, no_speech_dev,
+                                         no_speech_token, s);
+    else
+        launch_tail_continuous_as<__bf16>(q, B, rules != nullptr, r, (const uint32_t*)sample, (const uint32_t*)sample_rows, no_speech_dev,
+                                          no_speech_token, s);
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;
-}
-
-int wipa_step_tail_continuous(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always, int32_t* tokens,
-                              int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init, int eot, const void* sample,
-                              const int32_t* starts_dev, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
-                              const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y,
-                              int y_dtype, int D, float eps, wipa_stream_t stream) {
-    return step_tail_continuous("wipa_decoder_run_continuous", logits, ldl, B, V, mask_first, mask_always, tokens, ld_tok, pos_dev, posd_dev,
-                                done_counter, n_init, eot, nullptr, sample, nullptr, starts_dev, nullptr, 0, sum_logprobs, not_done, tok_emb, emb_dtype, emb_scale,
-                                pos_emb, n_ctx, x, ln_w, ln_b, y, y_dtype, D, eps, stream);
-}
-
-int wipa_step_tail_continuous_rules(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
-                                    int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init, int eot,
-                                    const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, float* no_speech_dev,
-                                    int no_speech_token, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
-                                    const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y,
-                                    int y_dtype, int D, float eps, wipa_stream_t stream) {
-    const char* who = "wipa_decoder_run_continuous_rules";
-    WIPA_REQUIRE(rules, "%s: rules is required (without rules the call is wipa_decoder_run_continuous)", who);
-    return step_tail_continuous(who, logits, ldl, B, V, mask_first, mask_always, tokens, ld_tok, pos_dev, posd_dev, done_counter, n_init, eot, rules,
-                                sample, nullptr, starts_dev, no_speech_dev, no_speech_token, sum_logprobs, not_done, tok_emb, emb_dtype, emb_scale,
-                                pos_emb, n_ctx, x, ln_w, ln_b, y, y_dtype, D, eps, stream);
-}
-
-// wipa_decoder_run_continuous_rows: the CONTINUOUS tails with a temperature per row; rules may be NULL, sample_rows is required
-int wipa_step_tail_continuous_rows(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
-                                   int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init, int eot,
-                                   const wipa_decode_rules* rules, const void* sample_rows, const int32_t* starts_dev, float* no_speech_dev,
-                                   int no_speech_token, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
-                                   const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y,
-                                   int y_dtype, int D, float eps, wipa_stream_t stream) {
-    const char* who = "wipa_decoder_run_continuous_rows";
-    WIPA_REQUIRE(sample_rows, "%s: sample_rows (the sampling record with a row part) is required", who);
-    return step_tail_continuous(who, logits, ldl, B, V, mask_first, mask_always, tokens, ld_tok, pos_dev, posd_dev, done_counter, n_init, eot, rules,
-                                nullptr, sample_rows, starts_dev, rules ? no_speech_dev : nullptr, no_speech_token, sum_logprobs, not_done, tok_emb,
-                                emb_dtype, emb_scale, pos_emb, n_ctx, x, ln_w, ln_b, y, y_dtype, D, eps, stream);
 }
 
 // the tail on wipa_logits_greedy's per-wave partials: no logits, so no rules, no draw and no ragged rows

@@ -632,23 +632,12 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
         // (with ctx.rules the timestamp rules, with ctx.sample the draw, with ctx.starts the RAGGED tails: position embedding and sampling
         // counter at the row's own position)
         const void* const* lw0 = w + WIPA_DEC_GLOBAL;
-        if (ctx.continuous && ctx.sample_rows)
-            return wipa_step_tail_continuous_rows(logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos, posd,
-                                                  done_counter_of(st, L), ctx.n_init, ctx.eot, ctx.rules, ctx.sample_rows, ctx.starts, ctx.no_speech,
-                                                  ctx.no_speech_token, (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), w[0],
-                                                  emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], nctx, x_first, (const float*)lw0[0],
-                                                  (const float*)lw0[1], ln, dt, d, 1e-5f, stream);
-        if (ctx.continuous && ctx.rules)
-            return wipa_step_tail_continuous_rules(logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos, posd,
-                                                   done_counter_of(st, L), ctx.n_init, ctx.eot, ctx.rules, ctx.sample, ctx.starts, ctx.no_speech,
-                                                   ctx.no_speech_token, (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), w[0],
-                                                   emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], nctx, x_first, (const float*)lw0[0],
-                                                   (const float*)lw0[1], ln, dt, d, 1e-5f, stream);
         if (ctx.continuous)
             return wipa_step_tail_continuous(logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos, posd,
-                                             done_counter_of(st, L), ctx.n_init, ctx.eot, ctx.sample, ctx.starts, (float*)(st + L.sum_logprobs),
-                                             (int32_t*)(st + L.not_done), w[0], emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], nctx, x_first,
-                                             (const float*)lw0[0], (const float*)lw0[1], ln, dt, d, 1e-5f, stream);
+                                             done_counter_of(st, L), ctx.n_init, ctx.eot, ctx.rules, ctx.sample, ctx.sample_rows, ctx.starts,
+                                             ctx.no_speech, ctx.no_speech_token, (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), w[0],
+                                             emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], nctx, x_first, (const float*)lw0[0],
+                                             (const float*)lw0[1], ln, dt, d, 1e-5f, stream);
         RT_CALL(wipa_step_tail(logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos, posd,
                                done_counter_of(st, L), ctx.n_init, ctx.eot, ctx.rules, ctx.sample, ctx.starts, (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), w[0],
                                emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], nctx, x_first, (const float*)lw0[0], (const float*)lw0[1], ln,
@@ -1041,6 +1030,7 @@ int replay_or_enqueue(bool use_graph, hipStream_t s, const GraphKey& key, Enqueu
 struct EntryNames {
     const char *own, *rules, *sample, *starts;
 };
+EntryNames entry_names(const char* own) { return EntryNames{own, own, own, own}; }  // an entry point that nothing forwards to
 // What wipa_decoder_run_ragged, wipa_decoder_prefill_sample and wipa_decoder_prefill_ragged do between their argument checks and
 // their first launch, in this order: what the steps cannot serve is refused, then the entry point's `own_checks`, then a state blob
 // too small for the layout (*L); every kernel attribute is set outside any capture; a call that will enqueue steps (n_steps > 0)
@@ -1057,6 +1047,30 @@ int decode_prologue(const EntryNames& who, const wipa_model_cfg* cfg, int B, con
     RT_CALL(state_fits(who.own, *L, state_bytes));
     RT_CALL(init_before_capture(cfg));
     if (n_steps > 0) WIPA_CHECK_HIP(hipMemsetAsync(done_counter_of(st, *L), 0, sizeof(int32_t), s));
+    return WIPA_OK;
+}
+
+// One layer's cached cross K / V of `n_clips` clips (lw: the layer's weights): features x [Wk | Wv] with the key half scaled, written to
+// ckv as [clip][K | V][H][Ta][64].  wipa_decoder_set_audio projects all clips of a call, wipa_decoder_admit_rows one clip into its slot.
+int cross_kv_gemm(const wipa_model_cfg* cfg, const void* const* lw, const void* features, void* ckv, int n_clips, wipa_stream_t stream) {
+    const int d = cfg->n_text_state, H = cfg->n_text_head, Ta = cfg->n_audio_ctx, dt = cfg->dtype;
+    wipa_gemm_desc g;
+    memset(&g, 0, sizeof(g));
+    g.col_scale_n = d; g.col_scale = QK_SCALE;  // the key half; values stay unscaled
+    g.rg_in = Ta; g.rg_valid = Ta; g.rg_stride = (int64_t)2 * H * Ta * 64;
+    g.cg_in = 64; g.cg_stride = (int64_t)Ta * 64;
+    return gemm(features, d, lw[10], d, ckv, 64, n_clips * Ta, 2 * d, d, dt, dt, (const float*)lw[11], 0, nullptr, stream, &g);
+}
+
+// What wipa_decoder_begin and wipa_decoder_begin_ragged reset before they write their tokens: every token column (padding columns hold
+// token 0), the position, the per-row results and the step's position offset
+int begin_reset(const wipa_model_cfg* cfg, char* st, const wipa_dec_layout& L, int B, hipStream_t s) {
+    RT_CALL(wipa_decode_fused_init());  // kernel attributes are set here, outside the stream capture of the step
+    RT_CALL(wipa_gemm_init());
+    WIPA_CHECK_HIP(hipMemsetAsync(st + L.tokens, 0, (size_t)B * L.ld_tok * 4, s));
+    WIPA_CHECK_HIP(hipMemsetAsync(st + L.pos, 0, 512, s));  // pos and not_done
+    WIPA_CHECK_HIP(hipMemsetAsync(st + L.sum_logprobs, 0, (size_t)B * 4, s));
+    WIPA_CHECK_HIP(hipMemsetAsync(st + L.scratch + dec_scratch(cfg, B).posd, 0, 8, s));
     return WIPA_OK;
 }
 
@@ -1109,8 +1123,7 @@ extern "C" int wipa_decoder_set_audio(const wipa_model_cfg* cfg, const void* con
     const int Bc = clips_of(cfg, B);  // features hold B / dec_n_group clips: copied / projected once per clip
     const wipa_dec_layout L = dec_layout(cfg, B);
     RT_CALL(state_fits("wipa_decoder_set_audio", L, state_bytes));
-    const int dt = cfg->dtype;
-    const size_t e = wipa_dtype_size(dt);
+    const size_t e = wipa_dtype_size(cfg->dtype);
     const int d = cfg->n_text_state, H = cfg->n_text_head, Ta = cfg->n_audio_ctx;
     WIPA_REQUIRE(cfg->n_audio_state == d, "encoder/decoder widths differ");
     if (cfg->dec_cross_absorbed) {
@@ -1120,13 +1133,7 @@ extern "C" int wipa_decoder_set_audio(const wipa_model_cfg* cfg, const void* con
     }
     for (int l = 0; l < cfg->n_text_layer; ++l) {
         const void* const* lw = w + WIPA_DEC_GLOBAL + WIPA_DEC_PER_LAYER * l;
-        char* ckv = (char*)state + L.cross_kv + (size_t)l * Bc * 2 * H * Ta * 64 * e;
-        wipa_gemm_desc g;
-        memset(&g, 0, sizeof(g));
-        g.col_scale_n = d; g.col_scale = QK_SCALE;  // the key half; values stay unscaled
-        g.rg_in = Ta; g.rg_valid = Ta; g.rg_stride = (int64_t)2 * H * Ta * 64;
-        g.cg_in = 64; g.cg_stride = (int64_t)Ta * 64;
-        PROF(PROF_GEMM, gemm(features, d, lw[10], d, ckv, 64, Bc * Ta, 2 * d, d, dt, dt, (const float*)lw[11], 0, nullptr, stream, &g));
+        PROF(PROF_GEMM, cross_kv_gemm(cfg, lw, features, (char*)state + L.cross_kv + (size_t)l * Bc * 2 * H * Ta * 64 * e, Bc, stream));
     }
     return WIPA_OK;
 }
@@ -1142,13 +1149,7 @@ extern "C" int wipa_decoder_begin(const wipa_model_cfg* cfg, void* state, size_t
     RT_CALL(state_fits("wipa_decoder_begin", L, state_bytes));
     hipStream_t s = (hipStream_t)stream;
     char* st = (char*)state;
-    const DecScratch S = dec_scratch(cfg, B);
-    RT_CALL(wipa_decode_fused_init());  // kernel attributes are set here, outside the stream capture of the step
-    RT_CALL(wipa_gemm_init());
-    WIPA_CHECK_HIP(hipMemsetAsync(st + L.tokens, 0, (size_t)B * L.ld_tok * 4, s));
-    WIPA_CHECK_HIP(hipMemsetAsync(st + L.pos, 0, 512, s));  // pos and not_done
-    WIPA_CHECK_HIP(hipMemsetAsync(st + L.sum_logprobs, 0, (size_t)B * 4, s));
-    WIPA_CHECK_HIP(hipMemsetAsync(st + L.scratch + S.posd, 0, 8, s));
+    RT_CALL(begin_reset(cfg, st, L, B, s));
     int t4[4] = {0, 0, 0, 0};
     for (int i = 0; i < n_init; ++i) t4[i] = initial_tokens_host[i];
     hipLaunchKernelGGL(fill_tokens_kernel, dim3((B + 63) / 64), dim3(64), 0, s, (int32_t*)(st + L.tokens), L.ld_tok, B, n_init,
@@ -1176,13 +1177,7 @@ extern "C" int wipa_decoder_begin_ragged(const wipa_model_cfg* cfg, void* state,
     RT_CALL(state_fits("wipa_decoder_begin_ragged", L, state_bytes));
     hipStream_t s = (hipStream_t)stream;
     char* st = (char*)state;
-    const DecScratch S = dec_scratch(cfg, B);
-    RT_CALL(wipa_decode_fused_init());  // kernel attributes are set here, outside the stream capture of the step
-    RT_CALL(wipa_gemm_init());
-    WIPA_CHECK_HIP(hipMemsetAsync(st + L.tokens, 0, (size_t)B * L.ld_tok * 4, s));  // padding columns hold token 0
-    WIPA_CHECK_HIP(hipMemsetAsync(st + L.pos, 0, 512, s));  // pos and not_done
-    WIPA_CHECK_HIP(hipMemsetAsync(st + L.sum_logprobs, 0, (size_t)B * 4, s));
-    WIPA_CHECK_HIP(hipMemsetAsync(st + L.scratch + S.posd, 0, 8, s));
+    RT_CALL(begin_reset(cfg, st, L, B, s));
     // the rows as the caller packed them (row b's own tokens in columns [start[b], P)), and the starts the step's kernels read
     WIPA_CHECK_HIP(hipMemcpy2DAsync(st + L.tokens, (size_t)L.ld_tok * 4, tokens_host, (size_t)P * 4, (size_t)P * 4, (size_t)B, hipMemcpyHostToDevice, s));
     WIPA_CHECK_HIP(hipMemcpyAsync(starts_dev, starts_host, (size_t)B * 4, hipMemcpyHostToDevice, s));
@@ -1208,36 +1203,25 @@ extern "C" int wipa_decoder_run_sample(const wipa_model_cfg* cfg, const void* co
                                    stream);
 }
 
-// wipa_decoder_run_ragged and, with `continuous`, wipa_decoder_run_continuous (rules NULL) / wipa_decoder_run_continuous_rules /
-// wipa_decoder_run_continuous_rows (sample_rows): the same call but for the tail the steps end in
-static int decoder_run(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init, int eot,
-                       const float* mask_first, const float* mask_always, int n_steps, int use_graph, const wipa_decode_rules* rules,
-                       const void* sample, const int32_t* starts_dev, bool continuous, float* no_speech_dev, int no_speech_token,
-                       const void* sample_rows, wipa_stream_t stream) {
+// wipa_decoder_run_ragged and, with full.continuous, the continuous entry points: the same call but for the tail the steps end in.
+// `full` is the call's context as its last step sees it (lean = false); `who` names the entry point in the refusals.
+static int decoder_run(const EntryNames& who, const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
+                       const StepCtx& full, int n_steps, int use_graph, wipa_stream_t stream) {
     RT_CALL(cfg_check(cfg));
     SplitScope split_scope(cfg);
-    WIPA_REQUIRE(w && state && mask_first && mask_always && B > 0 && n_steps >= 0, "wipa_decoder_run: bad arguments");
+    WIPA_REQUIRE(w && state && full.mask_first && full.mask_always && B > 0 && n_steps >= 0, "wipa_decoder_run: bad arguments");
     // every step of the call but the LAST is "lean" when the logits projection carries the greedy partials: its logits are not
     // written (state.logits holds those of the last step of a call, which is what callers read)
-    const StepCtx full{rules, sample, starts_dev, n_init, eot, mask_first, mask_always, false, continuous, no_speech_dev, no_speech_token, sample_rows};
     StepCtx lean = full;
     lean.lean = true;
-    static const EntryNames who_ragged = {"wipa_decoder_run", "wipa_decoder_run_rules", "wipa_decoder_run_sample", "wipa_decoder_run_ragged"};
-    static const EntryNames who_continuous = {"wipa_decoder_run_continuous", "wipa_decoder_run_continuous", "wipa_decoder_run_continuous",
-                                              "wipa_decoder_run_continuous"};
-    static const EntryNames who_continuous_rules = {"wipa_decoder_run_continuous_rules", "wipa_decoder_run_continuous_rules",
-                                                    "wipa_decoder_run_continuous_rules", "wipa_decoder_run_continuous_rules"};
-    static const EntryNames who_continuous_rows = {"wipa_decoder_run_continuous_rows", "wipa_decoder_run_continuous_rows",
-                                                   "wipa_decoder_run_continuous_rows", "wipa_decoder_run_continuous_rows"};
-    const EntryNames& who = !continuous ? who_ragged : sample_rows ? who_continuous_rows : rules ? who_continuous_rules : who_continuous;
     char* st = (char*)state;
     hipStream_t s = (hipStream_t)stream;
     wipa_dec_layout L;
     RT_CALL(decode_prologue(who, cfg, B, full, st, state_bytes, n_steps, s, &L, [&]() -> int {
         // the position lives on the device: a call may carry the prompt walk (P - 1 steps) besides the new tokens, so what can be
         // refused here is a step count that no position admits
-        WIPA_REQUIRE(!starts_dev || n_steps <= cfg->n_text_ctx - 1, "wipa_decoder_run_ragged: n_steps=%d with P=%d runs past n_text_ctx=%d", n_steps,
-                     n_init, cfg->n_text_ctx);
+        WIPA_REQUIRE(!full.starts || n_steps <= cfg->n_text_ctx - 1, "wipa_decoder_run_ragged: n_steps=%d with P=%d runs past n_text_ctx=%d", n_steps,
+                     full.n_init, cfg->n_text_ctx);
         return WIPA_OK;
     }));
     if (n_steps == 0) return WIPA_OK;
@@ -1267,8 +1251,9 @@ static int decoder_run(const wipa_model_cfg* cfg, const void* const* w, void* st
 extern "C" int wipa_decoder_run_ragged(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
                                        int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
                                        const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, wipa_stream_t stream) {
-    return decoder_run(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, n_steps, use_graph, rules, sample, starts_dev, false,
-                       nullptr, 0, nullptr, stream);
+    static const EntryNames who = {"wipa_decoder_run", "wipa_decoder_run_rules", "wipa_decoder_run_sample", "wipa_decoder_run_ragged"};
+    const StepCtx full{rules, sample, starts_dev, n_init, eot, mask_first, mask_always, false, false, nullptr, 0, nullptr};
+    return decoder_run(who, cfg, w, state, state_bytes, B, full, n_steps, use_graph, stream);
 }
 
 // ------------------------------------------------------------------ continuous batching: slots, admission, column shift
@@ -1353,16 +1338,27 @@ __global__ void shift_finish_kernel(int32_t* pos, int64_t* posd, int d, int32_t*
 
 }  // namespace
 
+// What the three continuous entry points share once each has refused what is its own to refuse: what a continuous decode serves, the
+// n_init range and the no-speech column, then the run.  c: the call's context (continuous; no_speech NULL where the entry point has none).
+static int decoder_run_continuous(const char* who, const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
+                                  const StepCtx& c, int n_steps, int use_graph, wipa_stream_t stream) {
+    RT_CALL(continuous_servable(who, cfg, B, c.starts));
+    RT_CALL(sample_servable(who, cfg, B, c.sample_rows));
+    WIPA_REQUIRE(c.n_init >= 1 && c.n_init <= 4, "%s: 1..4 initial tokens per clip (got %d)", who, c.n_init);
+    WIPA_REQUIRE(!c.no_speech || (c.rules && c.no_speech_token >= 0 && c.no_speech_token < cfg->n_vocab),
+                 "%s: no_speech_token=%d outside the vocabulary of %d%s", who, c.no_speech_token, cfg->n_vocab,
+                 c.sample_rows ? " (no_speech_dev needs rules)" : "");
+    return decoder_run(entry_names(who), cfg, w, state, state_bytes, B, c, n_steps, use_graph, stream);
+}
+
 extern "C" int wipa_decoder_run_continuous(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
                                            int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
                                            const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, wipa_stream_t stream) {
     RT_CALL(cfg_check(cfg));
     WIPA_REQUIRE(!rules, "wipa_decoder_run_continuous: the timestamp rules are not served (they scan the row from a common column n_init; "
                  "rules must be NULL)");
-    RT_CALL(continuous_servable("wipa_decoder_run_continuous", cfg, B, starts_dev));
-    WIPA_REQUIRE(n_init >= 1 && n_init <= 4, "wipa_decoder_run_continuous: 1..4 initial tokens per clip (got %d)", n_init);
-    return decoder_run(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, n_steps, use_graph, nullptr, sample, starts_dev, true,
-                       nullptr, 0, nullptr, stream);
+    const StepCtx c{nullptr, sample, starts_dev, n_init, eot, mask_first, mask_always, false, true, nullptr, 0, nullptr};
+    return decoder_run_continuous("wipa_decoder_run_continuous", cfg, w, state, state_bytes, B, c, n_steps, use_graph, stream);
 }
 
 extern "C" int wipa_decoder_run_continuous_rules(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
@@ -1373,12 +1369,8 @@ extern "C" int wipa_decoder_run_continuous_rules(const wipa_model_cfg* cfg, cons
     const char* who = "wipa_decoder_run_continuous_rules";
     WIPA_REQUIRE(rules, "%s: rules is required (the timestamp rules on every row's own sequence; without rules the call is "
                  "wipa_decoder_run_continuous)", who);
-    RT_CALL(continuous_servable(who, cfg, B, starts_dev));
-    WIPA_REQUIRE(n_init >= 1 && n_init <= 4, "%s: 1..4 initial tokens per clip (got %d)", who, n_init);
-    WIPA_REQUIRE(!no_speech_dev || (no_speech_token >= 0 && no_speech_token < cfg->n_vocab), "%s: no_speech_token=%d outside the vocabulary of %d",
-                 who, no_speech_token, cfg->n_vocab);
-    return decoder_run(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, n_steps, use_graph, rules, sample, starts_dev, true,
-                       no_speech_dev, no_speech_token, nullptr, stream);
+    const StepCtx c{rules, sample, starts_dev, n_init, eot, mask_first, mask_always, false, true, no_speech_dev, no_speech_token, nullptr};
+    return decoder_run_continuous(who, cfg, w, state, state_bytes, B, c, n_steps, use_graph, stream);
 }
 
 // wipa_decoder_run_continuous_rules (rules) / wipa_decoder_run_continuous (rules == NULL) with a temperature per row: the steps end in the
@@ -1392,13 +1384,8 @@ extern "C" int wipa_decoder_run_continuous_rows(const wipa_model_cfg* cfg, const
     WIPA_REQUIRE(sample_rows && ((uintptr_t)sample_rows % 16) == 0,
                  "%s: sample_rows is required (the sampling record with a row part, wipa_sample_rows_bytes, 16-byte aligned; without it the call "
                  "is wipa_decoder_run_continuous / _rules)", who);
-    RT_CALL(continuous_servable(who, cfg, B, starts_dev));
-    RT_CALL(sample_servable(who, cfg, B, sample_rows));
-    WIPA_REQUIRE(n_init >= 1 && n_init <= 4, "%s: 1..4 initial tokens per clip (got %d)", who, n_init);
-    WIPA_REQUIRE(!no_speech_dev || (rules && no_speech_token >= 0 && no_speech_token < cfg->n_vocab),
-                 "%s: no_speech_token=%d outside the vocabulary of %d (no_speech_dev needs rules)", who, no_speech_token, cfg->n_vocab);
-    return decoder_run(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, n_steps, use_graph, rules, nullptr, starts_dev, true,
-                       rules ? no_speech_dev : nullptr, no_speech_token, sample_rows, stream);
+    const StepCtx c{rules, nullptr, starts_dev, n_init, eot, mask_first, mask_always, false, true, no_speech_dev, no_speech_token, sample_rows};
+    return decoder_run_continuous(who, cfg, w, state, state_bytes, B, c, n_steps, use_graph, stream);
 }
 
 extern "C" int wipa_decoder_admit_rows(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_rows,
@@ -1427,8 +1414,7 @@ extern "C" int wipa_decoder_admit_rows(const wipa_model_cfg* cfg, const void* co
     RT_CALL(state_fits(who, L, state_bytes));
     hipStream_t s = (hipStream_t)stream;
     char* st = (char*)state;
-    const int dt = cfg->dtype;
-    const size_t e = wipa_dtype_size(dt);
+    const size_t e = wipa_dtype_size(cfg->dtype);
     const int d = cfg->n_text_state, H = cfg->n_text_head, Ta = cfg->n_audio_ctx;
     WIPA_REQUIRE(cfg->n_audio_state == d, "encoder/decoder widths differ");
     const size_t clip_bytes = (size_t)Ta * d * e;
@@ -1439,13 +1425,7 @@ extern "C" int wipa_decoder_admit_rows(const wipa_model_cfg* cfg, const void* co
         } else {  // the cached form: wipa_decoder_set_audio's projection for this clip alone, into the slot's K / V of every layer
             for (int l = 0; l < cfg->n_text_layer; ++l) {
                 const void* const* lw = w + WIPA_DEC_GLOBAL + WIPA_DEC_PER_LAYER * l;
-                char* ckv = st + L.cross_kv + ((size_t)l * B + slot) * 2 * H * Ta * 64 * e;
-                wipa_gemm_desc g;
-                memset(&g, 0, sizeof(g));
-                g.col_scale_n = d; g.col_scale = QK_SCALE;  // the key half; values stay unscaled
-                g.rg_in = Ta; g.rg_valid = Ta; g.rg_stride = (int64_t)2 * H * Ta * 64;
-                g.cg_in = 64; g.cg_stride = (int64_t)Ta * 64;
-                RT_CALL(gemm(features_host[i], d, lw[10], d, ckv, 64, Ta, 2 * d, d, dt, dt, (const float*)lw[11], 0, nullptr, stream, &g));
+                RT_CALL(cross_kv_gemm(cfg, lw, features_host[i], st + L.cross_kv + ((size_t)l * B + slot) * 2 * H * Ta * 64 * e, 1, stream));
             }
         }
         int t4[4] = {0, 0, 0, 0};
@@ -1706,8 +1686,7 @@ extern "C" int wipa_decoder_prefill_ragged(const wipa_model_cfg* cfg, const void
     WIPA_REQUIRE(cfg->dec_w_dtype == 0, "wipa_decoder_prefill_ragged: the prompt pass runs on a bf16 / f32 weight table (cfg.dec_w_dtype: fp8 tables "
                                         "serve the decode step)");
     const StepCtx ctx{rules, sample, starts_dev, P, eot, mask_first, mask_always, false};
-    static const EntryNames who = {"wipa_decoder_prefill_ragged", "wipa_decoder_prefill_ragged", "wipa_decoder_prefill_ragged",
-                                   "wipa_decoder_prefill_ragged"};
+    const EntryNames who = entry_names("wipa_decoder_prefill_ragged");
     char* st = (char*)state;
     hipStream_t s = (hipStream_t)stream;
     wipa_dec_layout L;

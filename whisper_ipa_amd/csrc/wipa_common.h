@@ -29,28 +29,16 @@ int wipa_step_tail(const float* logits, int64_t ldl, int B, int V, const float* 
                    const void* sample, const int32_t* starts_dev, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
                    const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y, int y_dtype,
                    int D, float eps, wipa_stream_t stream);
-// the same launch for wipa_decoder_run_continuous: the CONTINUOUS tails (a prompt end per row; starts_dev int32 [2][B]), no rules
+// the same launch for wipa_decoder_run_continuous / _rules / _rows: the CONTINUOUS tails (a prompt end per row; starts_dev int32 [2][B]).
+// rules, sample, sample_rows and no_speech_dev may each be NULL: with rules the pick runs on the row's own sequence and no_speech_dev
+// (float [B]) receives softmax(logits row)[no_speech_token] at the step of a row's first own column; sample_rows (the sampling record with
+// a row part) takes the place of sample and gives every row its own temperature
 int wipa_step_tail_continuous(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always, int32_t* tokens,
-                              int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init, int eot, const void* sample,
-                              const int32_t* starts_dev, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
+                              int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init, int eot,
+                              const wipa_decode_rules* rules, const void* sample, const void* sample_rows, const int32_t* starts_dev,
+                              float* no_speech_dev, int no_speech_token, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
                               const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y,
                               int y_dtype, int D, float eps, wipa_stream_t stream);
-// and for wipa_decoder_run_continuous_rules: the CONTINUOUS tails with the timestamp rules on the row's own sequence; no_speech_dev
-// (float [B], may be NULL) receives softmax(logits row)[no_speech_token] at the step of a row's first own column
-int wipa_step_tail_continuous_rules(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
-                                    int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init, int eot,
-                                    const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, float* no_speech_dev,
-                                    int no_speech_token, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
-                                    const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y,
-                                    int y_dtype, int D, float eps, wipa_stream_t stream);
-// and for wipa_decoder_run_continuous_rows: the CONTINUOUS tails with a temperature per row (sample_rows: the sampling record with a row
-// part, required); rules may be NULL, and no_speech_dev is looked at with rules only
-int wipa_step_tail_continuous_rows(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
-                                   int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init, int eot,
-                                   const wipa_decode_rules* rules, const void* sample_rows, const int32_t* starts_dev, float* no_speech_dev,
-                                   int no_speech_token, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
-                                   const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y,
-                                   int y_dtype, int D, float eps, wipa_stream_t stream);
 
 #define WIPA_CHECK_HIP(expr)                                                        \
     do {                                                                            \

@@ -82,6 +82,12 @@ class DecodingResult:
     compression_ratio: float = float("nan")
 
 
+def compression_ratio(text: str) -> float:
+    """the text's UTF-8 bytes over their zlib-compressed bytes (the fallback's repetition test); nan for an empty text"""
+    raw = text.encode("utf-8")
+    return len(raw) / max(len(zlib.compress(raw)), 1) if text else float("nan")
+
+
 @dataclass
 class GreedyTokens:
     tokens: np.ndarray        # [B, n_init + n_steps] int64 (EOT-latched)
@@ -827,7 +833,7 @@ def decode(model, mel: torch.Tensor, options: DecodingOptions = DecodingOptions(
                 if tok.eot in row:
                     row = row[: row.index(tok.eot)]
                 text = tok.decode([t for t in row if t < tok.timestamp_begin]).strip()  # tokens keeps the timestamps, text does not
-                comp = len(text.encode("utf-8")) / max(len(zlib.compress(text.encode("utf-8"))), 1) if text else float("nan")
+                comp = compression_ratio(text)
                 results[i] = DecodingResult(audio_features=feats[i], language=lang, language_probs=lang_probs[i], tokens=row,
                                             text=text, avg_logprob=float(g.sum_logprobs[j]) / (len(row) + 1),
                                             temperature=options.temperature, compression_ratio=comp, no_speech_prob=no_speech[i])

@@ -42,7 +42,6 @@ import ctypes as C
 import queue
 import threading
 import warnings
-import zlib
 from collections import deque
 from dataclasses import dataclass, field
 from typing import Deque, Iterable, Iterator, List, Optional, Sequence
@@ -52,7 +51,7 @@ import torch
 
 from . import _lib
 from . import audio as A
-from .decoding import (DecodingOptions, DecodingResult, _dec_prefill, _dec_run, _mask, _packed_for, _refuse_unsupported, _state_for,
+from .decoding import (DecodingOptions, DecodingResult, compression_ratio, _dec_prefill, _dec_run, _mask, _packed_for, _refuse_unsupported, _state_for,
                        _suppress_lists, _use_prefill, timestamp_rules)
 import os
 
@@ -98,7 +97,7 @@ class PassResult:
             tb = self._tok.timestamp_begin
             for i, row in enumerate(self.rows()):
                 text = self._tok.decode([t for t in row if t < tb]).strip()
-                comp = len(text.encode("utf-8")) / max(len(zlib.compress(text.encode("utf-8"))), 1) if text else float("nan")
+                comp = compression_ratio(text)
                 res.append(DecodingResult(audio_features=self.audio_features[i], language=self.languages[i],
                                           language_probs=self.language_probs[i], tokens=row, text=text,
                                           avg_logprob=float(self.sum_logprobs[i]) / (len(row) + 1), temperature=self._temperature,

@@ -50,7 +50,6 @@ from __future__ import annotations
 
 import inspect
 import warnings
-import zlib
 from collections import deque
 from dataclasses import dataclass, field
 from typing import Callable, List, Optional, Sequence, Tuple, Union
@@ -347,10 +346,12 @@ class _WindowSource:
     def retired(self, clip, tokens, sum_logprob, no_speech):
         i, at = clip
         assert at == self.books.seek[i], "a file has one window in flight"
+        from .decoding import compression_ratio
+
         tok = self.books.tok
         tokens = [int(t) for t in tokens]
         text = tok.decode([t for t in tokens if t < self.books.tb]).strip()
-        comp = len(text.encode("utf-8")) / max(len(zlib.compress(text.encode("utf-8"))), 1) if text else float("nan")
+        comp = compression_ratio(text)
         attempt = self.attempt.get(i, 0)
         res = _WindowResult(tokens, float(sum_logprob) / (len(tokens) + 1), float(no_speech), comp, self.temps[attempt], self.books.languages[i])
         books = self.books
