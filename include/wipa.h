@@ -904,6 +904,42 @@ int wipa_decoder_run_continuous_rows(const wipa_model_cfg* cfg, const void* cons
                                      int n_init, int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
                                      const wipa_decode_rules* rules, const void* sample_rows, const int32_t* starts_dev, float* no_speech_dev,
                                      int no_speech_token, wipa_stream_t s);
+
+/* Continuous batching with a PROMPT PER ROW.  A clip is still admitted at the state's column c; its prompt of L
+ * columns ([sot_prev] + history; L = 0: none) stands IN FRONT of that column, at [c - L, c), and its n_init initial tokens at
+ * [c, c + n_init), where they stand without a prompt.  The prompted calls take starts_dev as int32 [3][B]: row 0 the window start c - L
+ * (what the RAGGED attention, the position rows and the tails' next-input row read), row 1 the token limit, row 2 the prompt columns L.
+ * wipa_decoder_shift_columns serves such an array as it is: it moves rows 0 and 1 and does not look past them, and the K / V of
+ * prompt columns move with the rest.  The caller keeps the position at or above the widest prompt it will admit:
+ * wipa_decoder_seek: puts the position of an IDLE state (after wipa_decoder_begin, no live row) at `column`, and with it the offset
+ *   the step's q|k|v GEMM scatters at.  Refused (WIPA_ERR_ARG) unless 0 <= column < n_text_ctx - 1.
+ * wipa_decoder_admit_prompted_workspace_bytes: the DEVICE workspace an admission of n_rows rows with prompt width W takes.
+ * wipa_decoder_admit_rows_prompted: wipa_decoder_admit_rows (sampling streams included) for rows with prompts.  prompt_lens_host[i] is
+ *   L_i, prompt_tokens_host int32 [n_rows][W] holds row i's prompt RIGHT-ALIGNED (columns W - L_i .. W-1; what lies in front is not
+ *   looked at), W >= max L_i.  Tokens and the three starts entries are written on the device from the position read there; an admission
+ *   with c - W < 0, or without a column left to generate (c + n_init >= n_text_ctx), is not carried out at all.  With W > 0 ONE batched
+ *   layer walk over the packed rows [n_rows * W] (local starts W - L_i, cross K / V projected from the admitted clips' features into
+ *   the workspace) follows, each layer's q|k|v GEMM followed by a scatter of the prompt columns' K and V rows into
+ *   [layer][K | V][slot_i][c - L_i, c) of the self-attention cache; the last layer stops behind its q|k|v GEMM and no logits are
+ *   computed (the step at column c produces the sot-column logits itself).  Host arrays may be freed when the call returns.
+ *   Refused by name (WIPA_ERR_ARG, nothing enqueued): what wipa_decoder_admit_rows refuses, W or an L_i outside
+ *   0 .. n_text_ctx - n_init - 1, L_i > W, a prompt token outside the vocabulary, a workspace that is too small.
+ * wipa_decoder_run_continuous_prompted: the three continuous run calls in ONE, for a [3][B] starts_dev (required): rules, sample,
+ *   sample_rows and no_speech_dev may each be NULL (sample and sample_rows exclude each other; no_speech_dev needs rules).  The steps
+ *   end in the PROMPTED tails: own = start + L + n_init, the no-speech store at column start + L, the rules on tk[own .. p], the
+ *   draw's counter p - start (the row's position in its own unpadded sequence).  Head and attention are the RAGGED kernels as they
+ *   are.  The step graph's key is that of the unprompted call plus a variant bit. */
+int wipa_decoder_seek(const wipa_model_cfg* cfg, void* state, size_t state_bytes, int B, int column, wipa_stream_t s);
+size_t wipa_decoder_admit_prompted_workspace_bytes(const wipa_model_cfg* cfg, int n_rows, int W);
+int wipa_decoder_admit_rows_prompted(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int n_rows,
+                                     const int32_t* slots_host, const void* const* features_host, const int32_t* initial_tokens_host,
+                                     int n_init, const int32_t* limits_host, const int32_t* prompt_lens_host,
+                                     const int32_t* prompt_tokens_host, int W, int32_t* starts_dev, void* sample,
+                                     const uint32_t* streams_host, void* workspace, size_t workspace_bytes, wipa_stream_t s);
+int wipa_decoder_run_continuous_prompted(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B,
+                                         int n_init, int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
+                                         const wipa_decode_rules* rules, const void* sample, const void* sample_rows,
+                                         const int32_t* starts_dev, float* no_speech_dev, int no_speech_token, wipa_stream_t s);
 /* drop the cached step graphs that reference this state blob (call before freeing it). */
 int wipa_decoder_release(void* state);
 

@@ -149,8 +149,9 @@ def transcribe_files(model, audio_paths: List[str], batch_size: int = 64, progre
     mlx_whisper.transcribe's options of those names (upstream defaults to conditioning on; here it is opt-in).
     ``schedule="continuous"``: transcribe(schedule="continuous", slots=batch_size) -- the windows go through ``batch_size`` rows of one
     decode state with refill, 8 x ``batch_size`` files per call (what bounds a call is the host memory of its samples, not its rows);
-    it serves ``seed`` (a retried window is admitted again with a temperature of its own) without conditioning and refuses the rest by
-    name."""
+    it serves ``seed`` (a retried window is admitted again with a temperature of its own) and ``condition_on_previous_text`` /
+    ``initial_prompt`` (a window is admitted with its file's prompt in front of its admission column; with the default sample_len the
+    prompt keeps the last 196 history tokens, not upstream's 223 -- transcribe's ``prompt_budget``), and refuses the rest by name."""
     from whisper_ipa_amd import transcribe
 
     texts = [""] * len(audio_paths)
@@ -317,7 +318,7 @@ def main(argv=None) -> Dict:
                          "(default: temperature 0 only)")
     ap.add_argument("--condition-on-previous-text", action="store_true",
                     help="with --base-decode transcribe: decode every window after a file's first with the file's previous tokens as "
-                         "its prompt, as mlx_whisper.transcribe does by default (default here: off)")
+                         "its prompt, as mlx_whisper.transcribe does by default (default here: off); served by --decode continuous too")
     ap.add_argument("--initial-prompt", type=str, default=None,
                     help="with --base-decode transcribe: mlx_whisper.transcribe's initial_prompt, the prompt of every file's first window")
     ap.add_argument("--results-json", type=str, default=None, help="also write both result dicts here (rank 0)")

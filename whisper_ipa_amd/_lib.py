@@ -242,6 +242,13 @@ SIGNATURES = {
     "wipa_decoder_admit_rows": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, _P(C.c_int32), _P(c_void_p), _P(C.c_int32), c_int,
                                         _P(C.c_int32), c_void_p, c_void_p, _P(C.c_uint32), c_void_p]),
     "wipa_decoder_shift_columns": (c_int, [_P(ModelCfg), c_void_p, c_size_t, c_int, c_void_p, c_int, c_void_p]),
+    "wipa_decoder_seek": (c_int, [_P(ModelCfg), c_void_p, c_size_t, c_int, c_int, c_void_p]),
+    "wipa_decoder_admit_prompted_workspace_bytes": (c_size_t, [_P(ModelCfg), c_int, c_int]),
+    "wipa_decoder_admit_rows_prompted": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, _P(C.c_int32), _P(c_void_p),
+                                                 _P(C.c_int32), c_int, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), c_int, c_void_p, c_void_p,
+                                                 _P(C.c_uint32), c_void_p, c_size_t, c_void_p]),
+    "wipa_decoder_run_continuous_prompted": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p,
+                                                     c_int, c_int, _P(DecodeRules), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "wipa_decode_cross_attn_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "wipa_decode_cross_attn_grouped": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "wipa_cross_absorbed_attention_grouped": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,

@@ -23,6 +23,12 @@ seed=S)`` keep the state's sampling record with a row part (wipa_sample_rows_set
 greedy row) and end the steps in the tails that read it (wipa_decoder_run_continuous_rows), so a window retried at a higher temperature
 sits beside greedy first attempts and beside retries of other windows at other temperatures.  ``run_stream``'s source may hand a clip
 out again, with its draw; ``_GroupStepper`` admits it from the encoder features its first admission left.
+
+A PROMPT PER ROW: ``decode_continuous(prompts=)`` and ``transcribe(schedule="continuous",
+condition_on_previous_text=True)``.  A clip is still admitted at the column the state stands at; its prompt ([sot_prev] + history)
+stands IN FRONT of that column and goes through one batched pass over the admitted rows only (wipa_decoder_admit_rows_prompted), and
+the steps end in the PROMPTED tails (wipa_decoder_run_continuous_prompted).  So that a prompt always has room, a prompted run opens its
+state at column ``prompt_room`` (wipa_decoder_seek) and the loop never shifts below it.
 """
 from __future__ import annotations
 
@@ -59,7 +65,7 @@ def default_column_limit(n_ctx: int, n_init: int, check_every: int) -> int:
 
 
 def run_schedule(stepper, n_clips: int, slots: int, n_init: int, limits: Sequence[int], eot: int, n_ctx: int, check_every: int = 8,
-                 column_limit: Optional[int] = None) -> ScheduleStats:
+                 column_limit: Optional[int] = None, prompt_lens: Optional[Sequence[int]] = None, prompt_room: int = 0) -> ScheduleStats:
     """Decode clips 0 .. n_clips-1 through ``slots`` rows of ``stepper``:
 
       stepper.admit(pairs)              pairs [(slot, clip)]: the clips start at the current column of their slots
@@ -71,7 +77,9 @@ def run_schedule(stepper, n_clips: int, slots: int, n_init: int, limits: Sequenc
 
     Clip i may generate ``limits[i]`` tokens.  A row is finished when its last token is ``eot`` or it has generated its limit; clips are
     admitted in input order into the lowest free slot.  The column counter is mirrored on the host (it advances by one per step); the loop
-    is ``_run_slots``, which ``run_stream`` shares."""
+    is ``_run_slots``, which ``run_stream`` shares.
+    ``prompt_lens`` / ``prompt_room``: clip i carries ``prompt_lens[i]`` prompt columns IN FRONT of its admission column, and the run keeps
+    the column counter at or above ``prompt_room`` (the stepper opens its state there); 0 is the loop without prompts, call for call."""
     if slots < 1 or check_every < 1:
         raise ValueError(f"decode_continuous: slots = {slots} and check_every = {check_every} must be positive")
     if len(limits) != n_clips:
@@ -83,18 +91,25 @@ def run_schedule(stepper, n_clips: int, slots: int, n_init: int, limits: Sequenc
     longest = max([int(n) for n in limits], default=0)
     # a live row spans at most n_init + limit columns plus the steps up to the check that retires it; after a shift the oldest live row
     # starts at column 0 and the next interval must still fit
-    need = n_init + longest + 2 * check_every - 1
+    need = prompt_room + n_init + longest + 2 * check_every - 1
     if not (column_limit + n_init < n_ctx and column_limit >= need):
-        raise ValueError(f"decode_continuous: column_limit = {column_limit} outside {need} .. {n_ctx - 1 - n_init} (n_init + longest sample_len + "
+        room = "prompt_room + " if prompt_room else ""
+        raise ValueError(f"decode_continuous: column_limit = {column_limit} outside {need} .. {n_ctx - 1 - n_init} ({room}n_init + longest sample_len + "
                          f"2 * check_every - 1 .. n_text_ctx - 1 - n_init)")
-    batches = iter([[(clip, limits[clip]) for clip in range(n_clips)]])  # every clip is pending from the start, none later
+    if prompt_lens is None:
+        entries = [(clip, limits[clip]) for clip in range(n_clips)]
+    else:
+        if len(prompt_lens) != n_clips:
+            raise ValueError(f"decode_continuous: {len(prompt_lens)} prompts for {n_clips} clips")
+        entries = [(clip, limits[clip], None, range(int(prompt_lens[clip]))) for clip in range(n_clips)]  # the loop wants a prompt's length only
+    batches = iter([entries])  # every clip is pending from the start, none later
     return _run_slots(stepper, ScheduleStats(), slots, n_init, eot, check_every, column_limit, lambda: next(batches, []),
-                      lambda group: stepper.admit([(slot, clip) for slot, clip, _ in group]),
-                      lambda pos: (stepper.last_tokens(), stepper.retire))
+                      lambda group: stepper.admit([(slot, clip) for slot, clip, *_ in group]),
+                      lambda pos: (stepper.last_tokens(), stepper.retire), prompt_room=prompt_room)
 
 
 def run_stream(stepper, source, slots: int, n_init: int, eot: int, n_ctx: int, check_every: int = 8,
-               column_limit: Optional[int] = None) -> ScheduleStats:
+               column_limit: Optional[int] = None, prompt_room: int = 0) -> ScheduleStats:
     """``run_schedule`` for clips that are not all known when the run starts (the windows of files: a file's next window exists once its
     previous one has retired).  The clips come from ``source`` and their results go back to it:
 
@@ -103,12 +118,15 @@ def run_stream(stepper, source, slots: int, n_init: int, eot: int, n_ctx: int, c
                                             hashable value; it may generate ``limit`` tokens.  An entry may be (clip, limit, draw) with
                                             ``draw`` = None (greedy) or (temperature, attempt, stream): the row's own temperature, its
                                             index in the fallback schedule and its Philox stream (lo, hi).  A source may hand a clip out
-                                            AGAIN after it has retired (a retry): it is admitted at the check that retired it
+                                            AGAIN after it has retired (a retry): it is admitted at the check that retired it.
+                                            With ``prompt_room`` > 0 an entry may be (clip, limit, draw, prompt): ``prompt`` is the clip's
+                                            prompt columns ([sot_prev] + history; empty or None: no prompt), which stand in front of
+                                            its admission column; the run keeps the column counter at or above ``prompt_room``
       source.retired(clip, tokens, sum_logprob, no_speech)   the clip's generated tokens before its first ``eot`` (a list), its
                                             log-probability sum and its no-speech probability, as host values, at the check that retires it
 
       stepper.admit(triples)    [(slot, clip, limit)]: ONE call per check for all clips that start at the current column (a group); an
-                                entry whose source gave a draw is (slot, clip, limit, draw)
+                                entry whose source gave a draw is (slot, clip, limit, draw), one with a prompt (slot, clip, limit, draw, prompt)
       stepper.run(n), stepper.shift(shift)   as for ``run_schedule``
       stepper.snapshot() -> (tokens [slots, >= column + 1], sums [slots], no_speech [slots])   host arrays from ONE device-to-host copy
                                             (this is where the host waits); everything a check retires is read from them
@@ -125,11 +143,13 @@ def run_stream(stepper, source, slots: int, n_init: int, eot: int, n_ctx: int, c
 
     def admit(group):
         for _, _, limit, *_ in group:
-            # the bound of run_schedule, per clip: after a shift the oldest live row starts at column 0 and the next interval must fit
-            need = n_init + limit + 2 * check_every - 1
+            # the bound of run_schedule, per clip: after a shift the oldest live row's sot sequence starts at column prompt_room at the
+            # latest and the next interval must fit
+            need = prompt_room + n_init + limit + 2 * check_every - 1
             if limit < 1 or need > column_limit:
-                raise ValueError(f"decode_continuous: a clip's limit of {limit} tokens is outside 1 .. {column_limit - n_init - 2 * check_every + 1} "
-                                 f"(column_limit - n_init - 2 * check_every + 1)")
+                raise ValueError(f"decode_continuous: a clip's limit of {limit} tokens is outside 1 .. "
+                                 f"{column_limit - prompt_room - n_init - 2 * check_every + 1} (column_limit"
+                                 f"{' - prompt_room' if prompt_room else ''} - n_init - 2 * check_every + 1)")
         stepper.admit(group)
         stats.groups.append(len(group))
 
@@ -144,21 +164,27 @@ def run_stream(stepper, source, slots: int, n_init: int, eot: int, n_ctx: int, c
 
         return [row[pos] for row in tokens], retire
 
-    return _run_slots(stepper, stats, slots, n_init, eot, check_every, column_limit, source.pending, admit, check)
+    return _run_slots(stepper, stats, slots, n_init, eot, check_every, column_limit, source.pending, admit, check, prompt_room=prompt_room)
 
 
 def _run_slots(stepper, stats: ScheduleStats, slots: int, n_init: int, eot: int, check_every: int, column_limit: int, pending, admit,
-               check) -> ScheduleStats:
+               check, prompt_room: int = 0) -> ScheduleStats:
     """The loop of ``run_schedule`` and ``run_stream``: the column mirror, the shift rule, admission into the lowest free slot, the
     finished test and the stats.  What the two protocols differ in comes as three callables:
 
       pending() -> [(clip, limit, *draw)]   the clips that join the queue now; asked at the start and after every check
       admit(group)                          group [(slot, clip, limit, *draw)]: the clips that start at the current column, one call
       check(pos) -> (last, retire)          after an interval: ``last[slot]`` is the token a slot holds at column ``pos`` (this is where the
-                                            host waits), ``retire(slot, clip, first_column, n_columns)`` takes a finished clip's columns out"""
+                                            host waits), ``retire(slot, clip, first_column, n_columns)`` takes a finished clip's columns out
+
+    ``prompt_room`` = R > 0 (prompts in front of the admission column): the counter starts at R and no shift takes it below R, so a prompt
+    of up to R columns always has room; an entry's fourth element is its prompt, and its row's window starts L = len(prompt) columns
+    below its admission column.  R = 0 is the loop without prompts, call for call."""
     queue: deque = deque()
-    live: Dict[int, Tuple[object, int, int]] = {}  # slot -> (clip, start, limit)
-    pos = 0
+    live: Dict[int, Tuple[object, int, int, int]] = {}  # slot -> (clip, window start, limit, prompt columns)
+    pos = int(prompt_room)
+    if pos < 0:
+        raise ValueError(f"decode_continuous: prompt_room = {prompt_room} must not be negative")
 
     def admit_pending():
         queue.extend(pending())
@@ -167,9 +193,12 @@ def _run_slots(stepper, stats: ScheduleStats, slots: int, n_init: int, eot: int,
             if not queue:
                 break
             if slot not in live:
-                clip, limit, *draw = queue.popleft()
-                live[slot] = (clip, pos, int(limit))
-                group.append((slot, clip, int(limit), *draw))
+                clip, limit, *rest = queue.popleft()
+                n_prompt = len(rest[1]) if len(rest) > 1 and rest[1] is not None else 0
+                if n_prompt > prompt_room:
+                    raise ValueError(f"decode_continuous: a prompt of {n_prompt} columns does not fit prompt_room = {prompt_room}")
+                live[slot] = (clip, pos - n_prompt, int(limit), n_prompt)
+                group.append((slot, clip, int(limit), *rest))
                 stats.admissions.append((slot, clip, pos))
         if group:
             admit(group)
@@ -177,12 +206,12 @@ def _run_slots(stepper, stats: ScheduleStats, slots: int, n_init: int, eot: int,
     admit_pending()
     while live:
         if pos + check_every > column_limit:  # the next interval would pass the limit
-            shift = min(start for _, start, _ in live.values())
+            shift = min(min(start for _, start, _, _ in live.values()), pos - prompt_room)  # never below the prompt room
             assert shift > 0, "decode_continuous: a live row spans the whole column window (the shift would be 0)"
             stepper.shift(shift)
             stats.shifts.append(shift)
             pos -= shift
-            live = {slot: (clip, start - shift, limit) for slot, (clip, start, limit) in live.items()}
+            live = {slot: (clip, start - shift, limit, n_prompt) for slot, (clip, start, limit, n_prompt) in live.items()}
             assert pos + check_every <= column_limit
         stats.live_rows.append(len(live))
         stepper.run(check_every)
@@ -190,8 +219,8 @@ def _run_slots(stepper, stats: ScheduleStats, slots: int, n_init: int, eot: int,
         pos += check_every
         last, retire = check(pos)
         for slot in sorted(live):
-            clip, start, limit = live[slot]
-            own = start + n_init
+            clip, start, limit, n_prompt = live[slot]
+            own = start + n_prompt + n_init
             generated = pos - own + 1  # columns own .. pos
             if generated >= 1 and (int(last[slot]) == eot or generated >= limit):
                 retire(slot, clip, own, min(generated, limit))
@@ -225,12 +254,16 @@ class DeviceStepper:
     def __init__(self, model, slots: int, features, initial, n_init: int, limits: Sequence[int], eot: int,
                  suppress_always: Sequence[int], suppress_first: Sequence[int], sample: Optional[Sampling], s, use_graph: bool = True,
                  rules: Optional["_lib.DecodeRules"] = None, no_speech_token: Optional[int] = None, row_seed: Optional[int] = None,
-                 draws=None):
+                 draws=None, prompts=None, prompt_room: Optional[int] = None):
         """``rules``: the timestamp rules (wipa_decoder_run_continuous_rules; None: wipa_decoder_run_continuous).  With them and
         ``no_speech_token`` the step's tail leaves every row's no-speech probability in ``self.no_speech``.
         ``row_seed``: a TEMPERATURE PER ROW (wipa_decoder_run_continuous_rows; ``sample`` is then None): the state's sampling record
         with a row part is filled with this seed, and every admission writes the admitted clips' entries -- ``draws(clip)`` or the
-        fourth element of an admitted tuple, (temperature, attempt, (stream_lo, stream_hi)); None is a greedy row"""
+        fourth element of an admitted tuple, (temperature, attempt, (stream_lo, stream_hi)); None is a greedy row.
+        ``prompt_room`` (None: no prompts, the calls and the [2][B] starts buffer of the unprompted stepper): a PROMPTED stepper -- the
+        state is opened at that column (wipa_decoder_seek), admissions go through wipa_decoder_admit_rows_prompted with the clips' prompt
+        columns (``prompts(clip)`` or the fifth element of an admitted tuple: [sot_prev] + history, empty for none), the steps through
+        wipa_decoder_run_continuous_prompted, on a [3][B] starts buffer of its own"""
         self.L = _lib.lib()
         self.model, self.B, self.s, self.eot, self.use_graph = model, int(slots), s, int(eot), use_graph
         self.features = features  # clip -> device tensor [n_audio_ctx, d] in the model's dtype, contiguous
@@ -242,6 +275,9 @@ class DeviceStepper:
         if row_seed is not None and sample is not None:
             raise ValueError("decode_continuous: a temperature per row takes the place of the single-temperature sampling record")
         self.row_seed, self.draws = row_seed, draws
+        self.prompts, self.prompt_room = prompts, (int(prompt_room) if prompt_room is not None else None)
+        if self.prompt_room is not None and not 0 <= self.prompt_room < model.dims.n_text_ctx - 1:
+            raise ValueError(f"decode_continuous: prompt_room = {prompt_room} outside 0 .. n_text_ctx - 2")
         self.pk = pk = model.packed(absorbed=model.use_absorbed())  # the absorbed form where it applies, else the cached one
         states = model.__dict__.setdefault("_continuous_states", {})
         key = (stream_id(), self.B, int(pk["cfg"].dec_cross_absorbed))
@@ -256,6 +292,10 @@ class DeviceStepper:
         if getattr(st, "_cont_starts", None) is None:  # ONE buffer per state: its address is part of the step graph's key
             st._cont_starts = torch.zeros(2 * self.B, dtype=torch.int32, device=model.device)
         self.starts = st._cont_starts
+        if self.prompt_room is not None:  # a buffer of its own: the unprompted stepper's stays [2][B]
+            if getattr(st, "_cont_starts_prompted", None) is None:
+                st._cont_starts_prompted = torch.zeros(3 * self.B, dtype=torch.int32, device=model.device)
+            self.starts = st._cont_starts_prompted
         self.rules = rules
         self.no_speech = None
         if rules is not None and no_speech_token is not None:
@@ -286,6 +326,10 @@ class DeviceStepper:
         _lib.check(L.wipa_decoder_begin(C.byref(pk["cfg"]), ptr(st.blob), st.blob.numel(), self.B, init, self.n_init, sptr(self.s)),
                    "wipa_decoder_begin")
         self.starts.zero_()
+        if self.prompt_room is not None:  # open the prompt room: the idle state's position, once
+            _lib.check(L.wipa_decoder_seek(C.byref(pk["cfg"]), ptr(st.blob), st.blob.numel(), self.B, self.prompt_room, sptr(self.s)),
+                       "wipa_decoder_seek")
+            self.pos = self.prompt_room
         if self.no_speech is not None:
             self.no_speech.fill_(float("nan"))
         if self.rows is not None:  # the header, and every row greedy until a clip is admitted
@@ -298,9 +342,10 @@ class DeviceStepper:
 
     def admit(self, pairs):
         """pairs [(slot, clip)] of ``run_schedule`` (the clip's limit is ``limits[clip]``), or triples [(slot, clip, limit)] of ``run_stream``,
-        which may carry a fourth element: the clip's draw (temperature, attempt, stream) or None"""
+        which may carry a fourth element: the clip's draw (temperature, attempt, stream) or None, and a fifth: its prompt columns"""
         limits = [int(t[2]) if len(t) > 2 else self.limits[t[1]] for t in pairs]
         given = [t[3] if len(t) > 3 else (self.draws(t[1]) if self.draws is not None else None) for t in pairs]
+        prompt_rows = [list(t[4] or []) if len(t) > 4 else (list(self.prompts(t[1]) or []) if self.prompts is not None else []) for t in pairs]
         pairs = [(t[0], t[1]) for t in pairs]
         n = len(pairs)
         slots = (C.c_int32 * n)(*[slot for slot, _ in pairs])
@@ -317,9 +362,23 @@ class DeviceStepper:
             flat = [int(v) & 0xFFFFFFFF for _, clip in pairs for v in (own[clip] if own is not None else (clip, 0))]
             streams = (C.c_uint32 * (2 * n))(*flat)
         pk, st = self.pk, self.st
-        _lib.check(self.L.wipa_decoder_admit_rows(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), self.B, n, slots, fptr, init,
-                                                  self.n_init, lim, ptr(self.starts), ptr(self.rec) if self.rec is not None else None, streams,
-                                                  sptr(self.s)), "wipa_decoder_admit_rows")
+        if self.prompt_room is not None:
+            W = max(len(r) for r in prompt_rows)
+            lens = (C.c_int32 * n)(*[len(r) for r in prompt_rows])
+            flat = (C.c_int32 * max(n * W, 1))(*[int(t) for r in prompt_rows for t in [0] * (W - len(r)) + r])  # right-aligned
+            nbytes = int(self.L.wipa_decoder_admit_prompted_workspace_bytes(C.byref(pk["cfg"]), n, W))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.model.device)
+            self._keep.append(ws)
+            _lib.check(self.L.wipa_decoder_admit_rows_prompted(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), self.B, n, slots,
+                                                               fptr, init, self.n_init, lim, lens, flat, W, ptr(self.starts),
+                                                               ptr(self.rec) if self.rec is not None else None, streams, ptr(ws), nbytes,
+                                                               sptr(self.s)), "wipa_decoder_admit_rows_prompted")
+        else:
+            if any(prompt_rows):
+                raise ValueError("decode_continuous: a clip came with a prompt, but the stepper was not built for prompts (prompt_room)")
+            _lib.check(self.L.wipa_decoder_admit_rows(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), self.B, n, slots, fptr,
+                                                      init, self.n_init, lim, ptr(self.starts), ptr(self.rec) if self.rec is not None else None,
+                                                      streams, sptr(self.s)), "wipa_decoder_admit_rows")
         if self.rows is not None:  # the admitted slots' entries of the row record, in stream order behind the admission
             draws = [d if d is not None else (0.0, 0, (slot, 0)) for d, (slot, _) in zip(given, pairs)]
             flat = (C.c_uint32 * (2 * n))(*[int(v) & 0xFFFFFFFF for _, _, stream in draws for v in stream])
@@ -335,7 +394,9 @@ class DeviceStepper:
                   ptr(self.m_always), n, int(self.use_graph), C.byref(self.rules) if self.rules is not None else None)
         rec = ptr(self.rec) if self.rec is not None else None
         no_speech = (ptr(self.no_speech) if self.no_speech is not None else None, self.no_speech_token)
-        if self.rows is not None:
+        if self.prompt_room is not None:
+            name, args = "wipa_decoder_run_continuous_prompted", (rec, ptr(self.rows) if self.rows is not None else None, ptr(self.starts), *no_speech)
+        elif self.rows is not None:
             name, args = "wipa_decoder_run_continuous_rows", (ptr(self.rows), ptr(self.starts), *no_speech)
         elif self.rules is not None:
             name, args = "wipa_decoder_run_continuous_rules", (rec, ptr(self.starts), *no_speech)
@@ -345,7 +406,10 @@ class DeviceStepper:
         self.pos += n
 
     def last_tokens(self) -> np.ndarray:
-        return self.st.tokens[:, self.pos].cpu().numpy()  # synchronises the library stream
+        last = self.st.tokens[:, self.pos].cpu().numpy()  # synchronises the library stream
+        if self.prompt_room is not None:
+            self._keep.clear()  # every admission's prompt pass is done: its workspace is not held to the end of the run
+        return last
 
     def retire(self, slot: int, clip: int, first_column: int, n_columns: int):
         self.out_tokens[clip, :n_columns].copy_(self.st.tokens[slot, first_column:first_column + n_columns])
@@ -457,12 +521,13 @@ class _GroupStepper(DeviceStepper):
     window the source hands out again -- a retry -- is admitted from them, with no second log-mel, encoder or language detection, and
     ``source.group`` is asked for fresh windows only.  A file has one window in flight, so at most one feature tensor per active file."""
 
-    def __init__(self, model, slots: int, source, options: DecodingOptions, tok, base, always, first, rules, s, seed: Optional[int] = None):
+    def __init__(self, model, slots: int, source, options: DecodingOptions, tok, base, always, first, rules, s, seed: Optional[int] = None,
+                 prompt_room: Optional[int] = None):
         self.source, self.options, self.tok, self.base = source, options, tok, list(base)
         self._held: Dict[object, Tuple[torch.Tensor, List[int]]] = {}
         source.on_booked = self.release
         super().__init__(model, slots, lambda clip: self._held[clip][0], lambda clip: self._held[clip][1], len(base), [], tok.eot, always, first,
-                         None, s, rules=rules, no_speech_token=tok.no_speech, row_seed=seed)
+                         None, s, rules=rules, no_speech_token=tok.no_speech, row_seed=seed, prompt_room=prompt_room)
 
     def release(self, clip):
         """the window is booked: nothing will ask for its features again"""
@@ -504,11 +569,13 @@ class _GroupStepper(DeviceStepper):
 
 
 def stream_windows(model, source, decode_options: dict, slots: int, check_every: int = 8,
-                   column_limit: Optional[int] = None, seed: Optional[int] = None) -> ScheduleStats:
+                   column_limit: Optional[int] = None, seed: Optional[int] = None, prompt_room: Optional[int] = None) -> ScheduleStats:
     """The model's continuous decoder for ``transcribe(schedule="continuous")``: ``run_stream`` over ``source`` (transcribe._WindowSource:
     ``pending`` / ``retired`` of ``run_stream``, plus ``group(clips)`` -> (samples [n, 480000], languages) and ``detected(clips, languages)``)
     on ``slots`` rows, with timestamps.  Without ``seed`` every row is at temperature 0; with it the source's entries carry their draws
-    (a retried window's temperature, attempt and stream) and the steps end in the tails with a temperature per row"""
+    (a retried window's temperature, attempt and stream) and the steps end in the tails with a temperature per row.  ``prompt_room``
+    (None: no prompts): the source's entries carry their prompt columns as a fourth element, which stand in front of a window's admission
+    column; the state is opened at that column and never shifted below it"""
     options = DecodingOptions(**{**decode_options, "without_timestamps": False, "temperature": 0.0})
     refuse_unserved(model, options, timestamps=True)
     tok = get_tokenizer(model.is_multilingual, num_languages=model.num_languages, language=options.language or "en", task=options.task)
@@ -516,8 +583,9 @@ def stream_windows(model, source, decode_options: dict, slots: int, check_every:
     rules = timestamp_rules(tok, options.max_initial_timestamp)
     base = list(tok.sot_sequence)
     with on_stream() as s:
-        stepper = _GroupStepper(model, slots, source, options, tok, base, always, first, rules, s, seed=seed)
-        stats = run_stream(stepper, source, slots, len(base), tok.eot, model.dims.n_text_ctx, check_every, column_limit)
+        stepper = _GroupStepper(model, slots, source, options, tok, base, always, first, rules, s, seed=seed, prompt_room=prompt_room)
+        stats = run_stream(stepper, source, slots, len(base), tok.eot, model.dims.n_text_ctx, check_every, column_limit,
+                           prompt_room=int(prompt_room) if prompt_room is not None else 0)
         stepper._keep.clear()
     return stats
 
@@ -525,7 +593,8 @@ def stream_windows(model, source, decode_options: dict, slots: int, check_every:
 def decode_continuous(model, mels_or_features: torch.Tensor, options: DecodingOptions = DecodingOptions(without_timestamps=True),
                       slots: int = 64, sample_lens: Optional[Sequence[int]] = None, check_every: int = 8,
                       column_limit: Optional[int] = None, stats_out: Optional[list] = None, temperatures: Optional[Sequence[float]] = None,
-                      attempts: Optional[Sequence[int]] = None) -> List[DecodingResult]:
+                      attempts: Optional[Sequence[int]] = None, prompts: Optional[Sequence[Sequence[int]]] = None,
+                      prompt_room: Optional[int] = None) -> List[DecodingResult]:
     """``decode`` for a stream of clips through ``slots`` rows with refill: mels [N, 3000, n_mels] or encoded features [N, 1500, d];
     results in input order.  ``sample_lens``: the tokens clip i may generate (default ``options.sample_len`` or n_text_ctx // 2 for
     every clip).  Served: greedy, and ``temperature > 0`` with ``seed`` -- clip i draws from ``options.sample_streams[i]`` or from
@@ -535,7 +604,25 @@ def decode_continuous(model, mels_or_features: torch.Tensor, options: DecodingOp
     sequence, and ``no_speech_prob`` is what the step's tail left at the row's <|startoftranscript|> column.
     ``temperatures``: a temperature >= 0 PER CLIP (0: a greedy clip), with ``attempts`` (default 0 for every clip) the clip's index in a
     fallback schedule; needs ``options.seed`` and ``options.temperature == 0``.  Clip i draws what ``decode`` draws for it at that
-    temperature and attempt on its stream; the steps end in the tails with a temperature per row (wipa_decoder_run_continuous_rows)."""
+    temperature and attempt on its stream; the steps end in the tails with a temperature per row (wipa_decoder_run_continuous_rows).
+    ``prompts``: the previous-text token ids PER CLIP, without ``sot_prev`` ([]: no prompt) -- clip i is decoded as ``decode`` decodes a row
+    whose initial tokens are ``[sot_prev] + prompts[i] + sot_sequence`` (the last ``n_text_ctx // 2 - 1`` ids of a longer history, as
+    there): its prompt stands in front of its admission column and goes through one batched pass when the clip is admitted (DESIGN.md
+    section 16).  ``prompt_room`` (default: the longest prompt + 1) is the column the state is opened at and never shifted below; every
+    prompt with its ``sot_prev`` must fit it.  The room comes out of the column window: ``prompt_room + n_init + the longest sample_len +
+    2 * check_every - 1`` must not exceed ``column_limit`` (default ``n_text_ctx - 1 - check_every`` = 439), or ``ValueError`` names
+    ``column_limit``.  So a full 223-token history (room 224) leaves 197 tokens to generate at ``check_every`` 8, not the default
+    ``sample_len`` of 224: pass ``sample_lens`` / ``options.sample_len`` of at most 197, or shorter histories (196 tokens fit beside 224;
+    ``transcribe``'s ``prompt_budget`` makes that cut).  Works with ``temperatures=`` / ``attempts=``; refused with ``best_of`` and on
+    an fp8-quantised model."""
+    if prompts is not None:
+        if options.best_of is not None and options.best_of > 1:
+            raise NotImplementedError("decode_continuous: prompts with best_of is not implemented (candidate groups are served by decode())")
+        if getattr(model, "_fp8", None):
+            raise NotImplementedError("decode_continuous: prompts on an fp8-quantised model is not implemented (the prompt pass and the "
+                                      "continuous step run on bf16 / f32 decoder tables)")
+    elif prompt_room is not None:
+        raise ValueError("decode_continuous: prompt_room comes with prompts")
     refuse_unserved(model, options, timestamps=True)
     if temperatures is None and attempts is not None:
         raise ValueError("decode_continuous: attempts comes with temperatures (a temperature and an attempt per clip)")
@@ -585,6 +672,18 @@ def decode_continuous(model, mels_or_features: torch.Tensor, options: DecodingOp
         def draws(clip: int):
             return temperatures[clip], attempts[clip], row_streams[clip]
 
+    prompt_rows = None
+    if prompts is not None:
+        if len(prompts) != N:
+            raise ValueError(f"decode_continuous: {len(prompts)} prompts for {N} clips")
+        # upstream's _get_initial_tokens, as decode(prompts=) builds a row: [sot_prev] + the last n_text_ctx // 2 - 1 tokens of the history
+        keep = d.n_text_ctx // 2 - 1
+        prompt_rows = [([int(tok.sot_prev)] + [int(t) for t in list(ids)[-keep:]]) if len(ids) else [] for ids in prompts]
+        longest = max(len(r) for r in prompt_rows)
+        room = longest if prompt_room is None else int(prompt_room)
+        if not longest <= room <= d.n_text_ctx - len(base) - 1:
+            raise ValueError(f"decode_continuous: prompt_room = {room} outside {longest} .. {d.n_text_ctx - len(base) - 1} (the longest prompt + 1 "
+                             f".. n_text_ctx - n_init - 1)")
     feats = _Features(model, x, slots, options, tok)
 
     def initial(clip: int) -> List[int]:  # with language=None the chunk's detection has run when the clip is admitted
@@ -597,8 +696,13 @@ def decode_continuous(model, mels_or_features: torch.Tensor, options: DecodingOp
     with on_stream() as s:
         stepper = DeviceStepper(model, slots, feats, initial, len(base), limits, tok.eot, always, first, sample, s, rules=rules,
                                 no_speech_token=tok.no_speech if timed else None, row_seed=int(options.seed) if draws is not None else None,
-                                draws=draws)
-        stats = run_schedule(stepper, N, slots, len(base), limits, tok.eot, d.n_text_ctx, check_every, column_limit)
+                                draws=draws, prompts=(lambda clip: prompt_rows[clip]) if prompt_rows is not None else None,
+                                prompt_room=room if prompt_rows is not None else None)
+        if prompt_rows is None:
+            stats = run_schedule(stepper, N, slots, len(base), limits, tok.eot, d.n_text_ctx, check_every, column_limit)
+        else:
+            stats = run_schedule(stepper, N, slots, len(base), limits, tok.eot, d.n_text_ctx, check_every, column_limit,
+                                 prompt_lens=[len(r) for r in prompt_rows], prompt_room=room)
         tail_no_speech = stepper.out_no_speech.cpu().numpy() if timed else None
         toks, sums = stepper.results()
     if stats_out is not None:

@@ -1032,6 +1032,56 @@ __global__ __launch_bounds__(GS_THREADS) void rows_tail_continuous_kernel(TailAr
     tail_finish<TO>(q, p, next, s_red);
 }
 
+// The PROMPTED tails (wipa_decoder_run_continuous_prompted): the CONTINUOUS tails for rows that carry a PROMPT in front of their
+// admission column.  q.start is int32 [3][B]: start[b] is the row's window start (its first prompt column: what the RAGGED attention,
+// the position rows and tail_finish read, as they read it in every continuous step), start[B + b] the tokens it may generate and
+// start[2 B + b] its prompt columns L (0: no prompt).  The row's sot sequence stands at [start + L, start + L + n_init), so
+//   own = start + L + n_init;   the no-speech store fires at p == start + L, i.e. p + n_init == own;   the rules scan tk[own .. p];
+//   the draw's counter stays p - start[b], the row's position in its own unpadded sequence [sot_prev] + history + sot sequence + ...
+// Everything else is the CONTINUOUS tails' four cases, on the same device functions (row_scan_reg / row_pick, row_no_speech, commit,
+// tail_finish).  ONE body for the six (rules, draw) cases, as NEW kernels: the CONTINUOUS kernels above keep their symbols and their code.
+enum TailDraw { DRAW_NONE = 0, DRAW_RECORD = 1, DRAW_ROWS = 2 };  // greedy | the single-temperature record | a temperature per row
+
+template <typename TO, bool RULES, int DRAW>
+__global__ __launch_bounds__(GS_THREADS) void tail_prompted_kernel(TailArgs<true> q, RulesDev rules, const uint32_t* __restrict__ rec,
+                                                                   float* __restrict__ no_speech, int no_speech_token) {
+    __shared__ float s_v[2 * GS_WAVES];
+    __shared__ int s_i[2 * GS_WAVES];
+    __shared__ float s_sum[2 * GS_WAVES];
+    __shared__ float s_red[4];
+    const int b = blockIdx.x, B = (int)gridDim.x;
+    const int p = tail_pos(q.pos);
+    if (p + 1 >= q.n_ctx) return;  // uniform over the grid, as in the CONTINUOUS tails
+    const int start = q.start[b], limit = q.start[B + b], own = start + q.start[2 * B + b] + q.n_init;
+    int32_t* tk = q.tokens + (int64_t)b * q.ld_tok;
+    const float* row = q.logits + (int64_t)b * q.ldl;
+    if constexpr (RULES) {
+        if (no_speech && limit > 0 && p + q.n_init == own) {  // p is the row's <|startoftranscript|> column; uniform over the workgroup
+            row_no_speech(row, q.V, no_speech_token, no_speech + b, s_v, s_i, s_sum);
+            __syncthreads();
+        }
+    }
+    int next;
+    if (p + 1 < own) {  // idle, in its prompt or in its sot sequence: the token is taken as it stands
+        next = tk[p + 1];
+    } else if (p + 1 >= own + limit) {
+        next = q.eot;
+        if (threadIdx.x == 0) tk[p + 1] = next;
+    } else {
+        const float* mask = (p + 1 == own) ? q.mask_first : q.mask_always;
+        if constexpr (!RULES && DRAW == DRAW_NONE) {
+            const RowScan sc = row_scan_reg(row, mask, q.V, s_v, s_i, s_sum);
+            next = commit(tk + p, q.eot, sc.top.i, -logf(sc.tot), q.sum_logprobs + b, q.not_done);
+        } else {
+            // RULES: the row's own sequence tk[own .. p]; without rules row_pick does not look at its n_init argument
+            const RowPick pick = row_pick<RULES, DRAW != DRAW_NONE, DRAW == DRAW_ROWS>(row, mask, q.V, tk, p, RULES ? own : q.n_init, q.eot, rules, s_v,
+                                                                                        s_i, s_sum, rec, b, max(p - start, 0));
+            next = commit(tk + p, q.eot, pick.next, pick.logprob, q.sum_logprobs + b, q.not_done);
+        }
+    }
+    tail_finish<TO>(q, p, next, s_red);
+}
+
 // wipa_sample_rows_set: one row's entry of the record with a row part.  One thread; a slot outside the record's rows (its header holds
 // B) is not written.
 __global__ void sample_rows_set_kernel(uint32_t* rec, int slot, uint32_t stream_lo, uint32_t stream_hi, uint32_t attempt, float inv_t) {
@@ -1589,18 +1639,35 @@ static void launch_tail_continuous_as(const TailArgs<true>& q, int B, bool rules
     else hipLaunchKernelGGL((greedy_tail_continuous_kernel<TO>), grid, block, 0, s, q);
 }
 
+// the PROMPTED tails: the same selection among the instantiations of tail_prompted_kernel (starts_dev is int32 [3][B])
+template <typename TO>
+static void launch_tail_prompted_as(const TailArgs<true>& q, int B, bool rules, RulesDev r, const uint32_t* rec, const uint32_t* rows,
+                                    float* no_speech_dev, int no_speech_token, hipStream_t s) {
+    const dim3 grid(B), block(GS_THREADS);
+#define TAIL_PROMPTED(RULES, DRAW, REC, NSP, NSP_TOKEN) \
+    hipLaunchKernelGGL((tail_prompted_kernel<TO, RULES, DRAW>), grid, block, 0, s, q, r, REC, NSP, NSP_TOKEN)
+    if (rows && rules) TAIL_PROMPTED(true, DRAW_ROWS, rows, no_speech_dev, no_speech_token);
+    else if (rows) TAIL_PROMPTED(false, DRAW_ROWS, rows, nullptr, 0);
+    else if (rules && rec) TAIL_PROMPTED(true, DRAW_RECORD, rec, no_speech_dev, no_speech_token);
+    else if (rules) TAIL_PROMPTED(true, DRAW_NONE, rec, no_speech_dev, no_speech_token);
+    else if (rec) TAIL_PROMPTED(false, DRAW_RECORD, rec, nullptr, 0);
+    else TAIL_PROMPTED(false, DRAW_NONE, rec, nullptr, 0);
+#undef TAIL_PROMPTED
+}
+
 // The CONTINUOUS tails (declared in wipa_common.h for the runtime; not exported): the checks of wipa_step_tail; starts_dev is int32 [2][B],
 // the rows' first own columns and then the tokens each may generate.  rules, sample, sample_rows and no_speech_dev may each be NULL;
-// rules and sample_rows name the exported entry point whose error prefix applies.  With rules the tails are the rules_tail_continuous
+// rules and sample_rows name the exported entry point whose error prefix applies (prompted: wipa_decoder_run_continuous_prompted, whose
+// starts_dev is int32 [3][B] with the rows' prompt columns last, and whose tails are the PROMPTED ones).  With rules the tails are the rules_tail_continuous
 // kernels, and no_speech_dev (float [B]) receives softmax(row)[no_speech_token] at a row's first column; sample_rows (the sampling record
 // with a row part) takes the place of sample and selects the rows_tail_continuous kernels: a temperature per row.
 int wipa_step_tail_continuous(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always, int32_t* tokens,
                               int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init, int eot,
                               const wipa_decode_rules* rules, const void* sample, const void* sample_rows, const int32_t* starts_dev,
-                              float* no_speech_dev, int no_speech_token, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
-                              const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y,
-                              int y_dtype, int D, float eps, wipa_stream_t stream) {
-    const char* who = sample_rows ? "wipa_decoder_run_continuous_rows" : rules ? "wipa_decoder_run_continuous_rules" : "wipa_decoder_run_continuous";
+                              int prompted, float* no_speech_dev, int no_speech_token, float* sum_logprobs, int32_t* not_done, const void* tok_emb,
+                              int emb_dtype, const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b,
+                              void* y, int y_dtype, int D, float eps, wipa_stream_t stream) {
+    const char* who = prompted ? "wipa_decoder_run_continuous_prompted" : sample_rows ? "wipa_decoder_run_continuous_rows" : rules ? "wipa_decoder_run_continuous_rules" : "wipa_decoder_run_continuous";
     WIPA_REQUIRE(logits && mask_first && mask_always && tokens && pos_dev && posd_dev && done_counter && sum_logprobs && not_done && tok_emb &&
                      pos_emb && x && ln_w && ln_b && y && starts_dev && B > 0 && n_ctx > 0 && n_init >= 1 && ld_tok >= n_ctx,
                  "%s: bad arguments of the step's tail (starts_dev is required)", who);
@@ -1623,7 +1690,14 @@ int wipa_step_tail_continuous(const float* logits, int64_t ldl, int B, int V, co
     static_cast<TailParams&>(q) = tp;
     q.start = starts_dev;
     hipStream_t s = (hipStream_t)stream;
-    if (y_dtype == WIPA_F32)
+    if (prompted) {
+        if (y_dtype == WIPA_F32)
+            launch_tail_prompted_as<float>(q, B, rules != nullptr, r, (const uint32_t*)sample, (const uint32_t*)sample_rows, no_speech_dev,
+                                           no_speech_token, s);
+        else
+            launch_tail_prompted_as<__bf16>(q, B, rules != nullptr, r, (const uint32_t*)sample, (const uint32_t*)sample_rows, no_speech_dev,
+                                            no_speech_token, s);
+    } else if (y_dtype == WIPA_F32)
         launch_tail_continuous_as<float>(q, B, rules != nullptr, r, (const uint32_t*)sample, (const uint32_t*)sample_rows, no_speech_dev,
                                          no_speech_token, s);
     else

@@ -435,6 +435,9 @@ struct StepCtx {
     // wipa_decoder_run_continuous_rows (continuous with a temperature per row): the sampling record with a row part (wipa_sample_rows_bytes;
     // NULL otherwise).  It takes the place of `sample`, which is NULL then, and the step ends in the rows_tail_continuous kernels.
     const void* sample_rows;
+    // wipa_decoder_run_continuous_prompted: `starts` is int32 [3][B] -- window starts, token limits, prompt columns -- and the step ends
+    // in the PROMPTED tails (the sot sequence stands behind the row's prompt); everything before the tail is the continuous step
+    bool prompted;
 };
 // The logits projection with the greedy partials in its epilogue + a tail that merges them (round 4; WIPA_LOGITS_FUSED=0 restores
 // the plain GEMM + the row-scanning tail): bf16 models without fp8 decoder tables, <= 64 rows, tail-fused steps.  Measured on
@@ -635,7 +638,7 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
         if (ctx.continuous)
             return wipa_step_tail_continuous(logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos, posd,
                                              done_counter_of(st, L), ctx.n_init, ctx.eot, ctx.rules, ctx.sample, ctx.sample_rows, ctx.starts,
-                                             ctx.no_speech, ctx.no_speech_token, (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), w[0],
+                                             (int)ctx.prompted, ctx.no_speech, ctx.no_speech_token, (float*)(st + L.sum_logprobs), (int32_t*)(st + L.not_done), w[0],
                                              emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], nctx, x_first, (const float*)lw0[0],
                                              (const float*)lw0[1], ln, dt, d, 1e-5f, stream);
         RT_CALL(wipa_step_tail(logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos, posd,
@@ -924,6 +927,8 @@ int state_fits(const char* who, const wipa_dec_layout& L, size_t state_bytes) {
 // The ragged prompt pass (kind 3 + 16 * (sot_col + 1)) bakes its workspace in as well (NULL otherwise).
 // A continuous step with rules bakes in the no-speech array's address and its vocabulary column: the last two terms (NULL and 0 otherwise).
 // A continuous step with a temperature per row has its own variant bit, and its record's address stands in the sampling record's term.
+// A PROMPTED continuous step is the continuous key plus a variant bit of its own (candidate groups, which share that range of the word,
+// are not served by a continuous call).
 typedef std::tuple<const void*, const void*, const void*, const void*, int, int, int, int, int, int, int, int, int, const void*, const void*, const void*, const void*, int> GraphKey;  // ..., generation, kind: 0 step, 1 prefill, 2 lean step (no logit stores), rules, sampling record, starts, workspace, no-speech array, no-speech column
 // sampling lives in the fused step tail, like the rules: refused before anything is enqueued where the step cannot carry it
 int sample_servable(const char* who, const wipa_model_cfg* cfg, int B, const void* sample) {
@@ -977,7 +982,7 @@ int step_variant(const wipa_model_cfg* cfg, int B, const StepCtx& c) {
            64 * cfg->dec_cross_absorbed * (absorbed_block_fused() ? 2 : 1) + 256 * (int)tail_fused() + 512 * (int)absorbed_merge_out() +
            1024 * cfg->dec_cross_splits + 8192 * (int)lean_steps(cfg, B, c) +
            16384 * (cfg->dec_cross_absorbed ? wipa_cross_absorbed_loop_variant() : 0) + 65536 * (group_of(cfg) > 1 ? group_of(cfg) : 0) +
-           (1 << 28) * (int)c.continuous + (1 << 29) * (int)(c.continuous && c.rules) + (1 << 30) * (int)(c.continuous && c.sample_rows);
+           (1 << 27) * (int)(c.continuous && c.prompted) + (1 << 28) * (int)c.continuous + (1 << 29) * (int)(c.continuous && c.rules) + (1 << 30) * (int)(c.continuous && c.sample_rows);
 }
 // a key from the context of a decode call; the three rule terms are 0 without rules
 GraphKey graph_key(const wipa_model_cfg* cfg, const void* const* w, const void* state, int B, const StepCtx& c, int variant, int kind,
@@ -1336,6 +1341,100 @@ __global__ void shift_finish_kernel(int32_t* pos, int64_t* posd, int d, int32_t*
     }
 }
 
+// what wipa_decoder_admit_rows and wipa_decoder_admit_rows_prompted refuse alike, before anything is enqueued
+int admit_checks(const char* who, const wipa_model_cfg* cfg, const void* const* w, const void* state, int B, int n_rows, const int32_t* slots_host,
+                 const void* const* features_host, const int32_t* initial_tokens_host, int n_init, const int32_t* limits_host,
+                 const int32_t* starts_dev, const void* sample, const uint32_t* streams_host) {
+    RT_CALL(continuous_servable(who, cfg, B, starts_dev));
+    WIPA_REQUIRE(w && state && n_rows >= 0 && (n_rows == 0 || (slots_host && features_host && initial_tokens_host && limits_host)),
+                 "%s: null pointer / bad row count", who);
+    WIPA_REQUIRE(n_init >= 1 && n_init <= 4, "%s: 1..4 initial tokens per clip (got %d)", who, n_init);
+    WIPA_REQUIRE(!sample || (streams_host && ((uintptr_t)sample % 4) == 0), "%s: a sampling record needs streams_host (uint32 [n_rows][2])", who);
+    for (int i = 0; i < n_rows; ++i) {
+        WIPA_REQUIRE(slots_host[i] >= 0 && slots_host[i] < B, "%s: slot[%d]=%d outside 0..%d", who, i, slots_host[i], B - 1);
+        for (int j = 0; j < i; ++j) WIPA_REQUIRE(slots_host[j] != slots_host[i], "%s: slot %d is listed twice", who, slots_host[i]);
+        WIPA_REQUIRE(features_host[i], "%s: features[%d] is null", who, i);
+        WIPA_REQUIRE(limits_host[i] >= 0 && limits_host[i] <= cfg->n_text_ctx, "%s: limit[%d]=%d outside 0..n_text_ctx", who, i, limits_host[i]);
+        for (int t = 0; t < n_init; ++t)
+            WIPA_REQUIRE(initial_tokens_host[i * n_init + t] >= 0 && initial_tokens_host[i * n_init + t] < cfg->n_vocab,
+                         "%s: initial token [%d][%d]=%d outside the vocabulary of %d", who, i, t, initial_tokens_host[i * n_init + t], cfg->n_vocab);
+    }
+    WIPA_REQUIRE(cfg->n_audio_state == cfg->n_text_state, "encoder/decoder widths differ");
+    return WIPA_OK;
+}
+
+// one admitted clip's cross-attention input into its slot of the blob
+int admit_cross(const wipa_model_cfg* cfg, const void* const* w, char* st, const wipa_dec_layout& L, int B, int slot, const void* features,
+                wipa_stream_t stream) {
+    const size_t e = wipa_dtype_size(cfg->dtype);
+    const int d = cfg->n_text_state, H = cfg->n_text_head, Ta = cfg->n_audio_ctx;
+    const size_t clip_bytes = (size_t)Ta * d * e;
+    if (cfg->dec_cross_absorbed) {  // the steps stream the encoder output itself: an admission is a copy
+        WIPA_CHECK_HIP(hipMemcpyAsync(st + L.cross_kv + (size_t)slot * clip_bytes, features, clip_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return WIPA_OK;
+    }
+    // the cached form: wipa_decoder_set_audio's projection for this clip alone, into the slot's K / V of every layer
+    for (int l = 0; l < cfg->n_text_layer; ++l) {
+        const void* const* lw = w + WIPA_DEC_GLOBAL + WIPA_DEC_PER_LAYER * l;
+        RT_CALL(cross_kv_gemm(cfg, lw, features, st + L.cross_kv + ((size_t)l * B + slot) * 2 * H * Ta * 64 * e, 1, stream));
+    }
+    return WIPA_OK;
+}
+
+// wipa_decoder_seek: the position of an idle state, and the element offset (column * d) the q|k|v GEMM of a step scatters at
+__global__ void seek_kernel(int32_t* pos, int64_t* posd, int d, int column) {
+    *pos = column;
+    *posd = (int64_t)column * d;
+}
+
+// wipa_decoder_admit_rows_prompted.  meta is int32 [n_rows][ADMIT_META]: slot, prompt columns L, limit, the four initial tokens, the
+// Philox stream (lo, hi); ptok int32 [n_rows][W] holds the prompts right-aligned.  With c = *pos, row i's prompt goes to columns
+// [c - L, c) of its slot, its initial tokens to [c, c + n_init), and starts[slot], starts[B + slot], starts[2 B + slot] take c - L, the
+// limit and L.  One workgroup per admitted row.  An admission without room -- c - W < 0, or no column left to generate -- is not carried
+// out: the same test stands in scatter_prompt_kv_kernel, so a row is admitted with its K / V or not at all.
+constexpr int ADMIT_META = 12;
+__device__ __forceinline__ bool admission_fits(int c, int W, int n_init, int n_ctx) { return c - W >= 0 && c + n_init < n_ctx; }
+
+__global__ __launch_bounds__(256) void admit_rows_prompted_kernel(int32_t* tokens, int64_t ld_tok, const int32_t* pos, int n_ctx, int B, int n_init,
+                                                                  int W, const int32_t* __restrict__ meta, const int32_t* __restrict__ ptok,
+                                                                  int32_t* starts, float* sum_logprobs, uint32_t* rec) {
+    const int c = *pos;
+    if (!admission_fits(c, W, n_init, n_ctx)) return;
+    const int32_t* m = meta + (int64_t)blockIdx.x * ADMIT_META;
+    const int slot = m[0], L = m[1];
+    int32_t* tk = tokens + (int64_t)slot * ld_tok;
+    for (int j = threadIdx.x; j < L; j += blockDim.x) tk[c - L + j] = ptok[(int64_t)blockIdx.x * W + (W - L) + j];
+    if (threadIdx.x == 0) {
+        for (int t = 0; t < n_init; ++t) tk[c + t] = m[3 + t];
+        starts[slot] = c - L;
+        starts[B + slot] = m[2];
+        starts[2 * B + slot] = L;
+        sum_logprobs[slot] = 0.f;
+        if (rec) {
+            rec[4 + 2 * slot] = (uint32_t)m[7];
+            rec[5 + 2 * slot] = (uint32_t)m[8];
+        }
+    }
+}
+
+// The prompt pass left a layer's q|k|v in packed rows [n_rows * W][3 d]; the K and V rows j >= W - L_i of row i go to columns
+// [c - L_i, c) of the slot's K and V strips of that layer, skv [3][B][n_ctx][d] (c = *pos).  Workgroup (i, K | V) owns one strip;
+// 16-byte plain loads and stores, row_bytes = d * element size is a multiple of 16.
+__global__ __launch_bounds__(256) void scatter_prompt_kv_kernel(const char* __restrict__ qkv, char* __restrict__ skv, const int32_t* __restrict__ meta,
+                                                                const int32_t* pos, int n_ctx, int n_init, int W, int B, int64_t row_bytes) {
+    const int c = *pos;
+    if (!admission_fits(c, W, n_init, n_ctx)) return;
+    const int i = blockIdx.x, part = 1 + (int)blockIdx.y;  // 1: K, 2: V
+    const int slot = meta[(int64_t)i * ADMIT_META], L = meta[(int64_t)i * ADMIT_META + 1];
+    const char* src = qkv + ((int64_t)i * W + (W - L)) * 3 * row_bytes + part * row_bytes;
+    char* dst = skv + (((int64_t)part * B + slot) * n_ctx + (c - L)) * row_bytes;
+    const int per_row = (int)(row_bytes / 16), total = L * per_row;
+    for (int idx = threadIdx.x; idx < total; idx += 256) {
+        const int r = idx / per_row, o = idx - r * per_row;
+        *reinterpret_cast<uint4*>(dst + (int64_t)r * row_bytes + o * 16) = *reinterpret_cast<const uint4*>(src + (int64_t)r * 3 * row_bytes + o * 16);
+    }
+}
+
 }  // namespace
 
 // What the three continuous entry points share once each has refused what is its own to refuse: what a continuous decode serves, the
@@ -1396,38 +1495,15 @@ extern "C" int wipa_decoder_admit_rows(const wipa_model_cfg* cfg, const void* co
     RT_CALL(cfg_check(cfg));
     SplitScope split_scope(cfg);
     const char* who = "wipa_decoder_admit_rows";
-    RT_CALL(continuous_servable(who, cfg, B, starts_dev));
-    WIPA_REQUIRE(w && state && n_rows >= 0 && (n_rows == 0 || (slots_host && features_host && initial_tokens_host && limits_host)),
-                 "%s: null pointer / bad row count", who);
-    WIPA_REQUIRE(n_init >= 1 && n_init <= 4, "%s: 1..4 initial tokens per clip (got %d)", who, n_init);
-    WIPA_REQUIRE(!sample || (streams_host && ((uintptr_t)sample % 4) == 0), "%s: a sampling record needs streams_host (uint32 [n_rows][2])", who);
-    for (int i = 0; i < n_rows; ++i) {
-        WIPA_REQUIRE(slots_host[i] >= 0 && slots_host[i] < B, "%s: slot[%d]=%d outside 0..%d", who, i, slots_host[i], B - 1);
-        for (int j = 0; j < i; ++j) WIPA_REQUIRE(slots_host[j] != slots_host[i], "%s: slot %d is listed twice", who, slots_host[i]);
-        WIPA_REQUIRE(features_host[i], "%s: features[%d] is null", who, i);
-        WIPA_REQUIRE(limits_host[i] >= 0 && limits_host[i] <= cfg->n_text_ctx, "%s: limit[%d]=%d outside 0..n_text_ctx", who, i, limits_host[i]);
-        for (int t = 0; t < n_init; ++t)
-            WIPA_REQUIRE(initial_tokens_host[i * n_init + t] >= 0 && initial_tokens_host[i * n_init + t] < cfg->n_vocab,
-                         "%s: initial token [%d][%d]=%d outside the vocabulary of %d", who, i, t, initial_tokens_host[i * n_init + t], cfg->n_vocab);
-    }
+    RT_CALL(admit_checks(who, cfg, w, state, B, n_rows, slots_host, features_host, initial_tokens_host, n_init, limits_host, starts_dev, sample,
+                         streams_host));
     const wipa_dec_layout L = dec_layout(cfg, B);
     RT_CALL(state_fits(who, L, state_bytes));
     hipStream_t s = (hipStream_t)stream;
     char* st = (char*)state;
-    const size_t e = wipa_dtype_size(cfg->dtype);
-    const int d = cfg->n_text_state, H = cfg->n_text_head, Ta = cfg->n_audio_ctx;
-    WIPA_REQUIRE(cfg->n_audio_state == d, "encoder/decoder widths differ");
-    const size_t clip_bytes = (size_t)Ta * d * e;
     for (int i = 0; i < n_rows; ++i) {
         const int slot = slots_host[i];
-        if (cfg->dec_cross_absorbed) {  // the steps stream the encoder output itself: an admission is a copy
-            WIPA_CHECK_HIP(hipMemcpyAsync(st + L.cross_kv + (size_t)slot * clip_bytes, features_host[i], clip_bytes, hipMemcpyDeviceToDevice, s));
-        } else {  // the cached form: wipa_decoder_set_audio's projection for this clip alone, into the slot's K / V of every layer
-            for (int l = 0; l < cfg->n_text_layer; ++l) {
-                const void* const* lw = w + WIPA_DEC_GLOBAL + WIPA_DEC_PER_LAYER * l;
-                RT_CALL(cross_kv_gemm(cfg, lw, features_host[i], st + L.cross_kv + ((size_t)l * B + slot) * 2 * H * Ta * 64 * e, 1, stream));
-            }
-        }
+        RT_CALL(admit_cross(cfg, w, st, L, B, slot, features_host[i], stream));
         int t4[4] = {0, 0, 0, 0};
         for (int t = 0; t < n_init; ++t) t4[t] = initial_tokens_host[i * n_init + t];
         hipLaunchKernelGGL(admit_row_kernel, dim3(1), dim3(1), 0, s, (int32_t*)(st + L.tokens), L.ld_tok, (const int32_t*)(st + L.pos),
@@ -1535,10 +1611,16 @@ struct TfHook {
     virtual ~TfHook() {}
 };
 
+// what wipa_decoder_admit_rows_prompted does behind a layer's q|k|v GEMM (qkv: where the layer's q|k|v went)
+struct QkvHook {
+    virtual int after_qkv(int layer, const char* qkv) const = 0;
+    virtual ~QkvHook() {}
+};
+
 // The batched decoder-layer walk over B * T rows (T columns per row): embedding, then per layer LayerNorm, q|k|v GEMM, causal
 // self-attention, out GEMM with residual, LayerNorm, query GEMM, cross K / V projection, cross-attention, out GEMM, LayerNorm and the
 // two MLP GEMMs.  Leaves the residual stream in x.  Its callers, the teacher-forced pass (tf_layers) and the ragged prompt pass
-// (enqueue_prefill_ragged), differ in the five numbered places.
+// (enqueue_prefill_ragged), differ in the first five numbered places; the prompt pass of an admission (wipa_decoder_admit_rows_prompted) adds the sixth.
 struct BatchedWalk {
     int B, T;
     const int32_t* tokens;  // [B, ld_tok]
@@ -1554,6 +1636,8 @@ struct BatchedWalk {
     const char* ckv_cache;
     int n_group;            // 4. candidate groups: rows = clips x n_group; the cross-attention takes a clip's candidates together
     const TfHook* hook;     // 5. NULL, or what runs between the cross projections and the cross-attention
+    const QkvHook* qkv_hook;  // 6. NULL, or what runs behind a layer's q|k|v GEMM; with kv_only the walk is wanted for the K / V of its
+    bool kv_only;             //    columns alone, and the last layer stops there (nothing reads what lies behind)
 };
 int batched_layers(const wipa_model_cfg* cfg, const void* const* w, const BatchedWalk& k, wipa_stream_t stream) {
     const int dt = cfg->dtype;
@@ -1582,6 +1666,8 @@ int batched_layers(const wipa_model_cfg* cfg, const void* const* w, const Batche
             }
             RT_CALL(gemm(ln, d, lw[2], d, qkv, qkv_rs, M, 3 * d, d, dt, dt, (const float*)lw[3], 0, nullptr, stream, &g));
         }
+        if (k.qkv_hook) RT_CALL(k.qkv_hook->after_qkv(l, qkv));
+        if (k.kv_only && l + 1 == cfg->n_text_layer) break;
         {
             wipa_attn_desc a;
             memset(&a, 0, sizeof(a));
@@ -1703,6 +1789,160 @@ extern "C" int wipa_decoder_prefill_ragged(const wipa_model_cfg* cfg, const void
     return replay_or_enqueue(use_graph, s, graph_key(cfg, w, state, B, ctx, variant, 3 + 16 * (sot_col + 1), workspace), [&]() -> int {
         return enqueue_prefill_ragged(cfg, w, st, L, B, sot_col, ctx, (char*)workspace, W, stream);
     });
+}
+
+// ------------------------------------------------------------------ continuous batching with a prompt per row
+namespace {
+struct AdmitWs {
+    size_t meta, tokens, starts, feat, x, ln, qkv, q, ao, h, ckv, total;
+};
+AdmitWs admit_ws(const wipa_model_cfg* c, int n_rows, int W) {
+    const size_t e = wipa_dtype_size(c->dtype), d = c->n_text_state, M = (size_t)n_rows * W;
+    AdmitWs w;
+    size_t o = 0;
+    w.meta = o;   o += align256((size_t)n_rows * ADMIT_META * 4);
+    w.tokens = o; o += align256(M * 4);
+    w.starts = o; o += align256((size_t)n_rows * 4);
+    w.feat = w.x = w.ln = w.qkv = w.q = w.ao = w.h = w.ckv = o;
+    if (W > 0) {  // the prompt pass
+        w.feat = o; o += align256((size_t)n_rows * c->n_audio_ctx * d * e);
+        w.x = o;    o += align256(M * d * 4);
+        w.ln = o;   o += align256(M * d * e);
+        w.qkv = o;  o += align256(M * 3 * d * e);
+        w.q = o;    o += align256(M * d * e);
+        w.ao = o;   o += align256(M * d * e);
+        w.h = o;    o += align256(M * 4 * d * e);
+        w.ckv = o;  o += align256((size_t)n_rows * 2 * c->n_text_head * c->n_audio_ctx * 64 * e);
+    }
+    w.total = o;
+    return w;
+}
+struct ScatterHook : QkvHook {
+    const wipa_model_cfg* cfg;
+    char* self_kv;
+    const int32_t *meta, *pos;
+    int n_rows, W, B, n_init;
+    hipStream_t s;
+    int after_qkv(int layer, const char* qkv) const override {
+        const int64_t row_bytes = (int64_t)cfg->n_text_state * wipa_dtype_size(cfg->dtype);
+        char* skv = self_kv + (size_t)layer * 3 * B * cfg->n_text_ctx * row_bytes;
+        hipLaunchKernelGGL(scatter_prompt_kv_kernel, dim3(n_rows, 2), dim3(256), 0, s, qkv, skv, meta, pos, cfg->n_text_ctx, n_init, W, B, row_bytes);
+        WIPA_LAUNCH_CHECK();
+        return WIPA_OK;
+    }
+};
+}  // namespace
+
+extern "C" int wipa_decoder_seek(const wipa_model_cfg* cfg, void* state, size_t state_bytes, int B, int column, wipa_stream_t stream) {
+    RT_CALL(cfg_check(cfg));
+    SplitScope split_scope(cfg);
+    const char* who = "wipa_decoder_seek";
+    WIPA_REQUIRE(state && B > 0, "%s: null pointer / bad batch", who);
+    WIPA_REQUIRE(column >= 0 && column < cfg->n_text_ctx - 1, "%s: column=%d outside 0..n_text_ctx-2", who, column);
+    const wipa_dec_layout L = dec_layout(cfg, B);
+    RT_CALL(state_fits(who, L, state_bytes));
+    char* st = (char*)state;
+    hipLaunchKernelGGL(seek_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int32_t*)(st + L.pos), (int64_t*)(st + L.scratch + dec_scratch(cfg, B).posd),
+                       cfg->n_text_state, column);
+    WIPA_LAUNCH_CHECK();
+    return WIPA_OK;
+}
+
+extern "C" size_t wipa_decoder_admit_prompted_workspace_bytes(const wipa_model_cfg* cfg, int n_rows, int W) {
+    if (!cfg || n_rows <= 0 || W < 0) return 0;
+    return admit_ws(cfg, n_rows, W).total;
+}
+
+extern "C" int wipa_decoder_admit_rows_prompted(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_rows,
+                                                const int32_t* slots_host, const void* const* features_host,
+                                                const int32_t* initial_tokens_host, int n_init, const int32_t* limits_host,
+                                                const int32_t* prompt_lens_host, const int32_t* prompt_tokens_host, int W, int32_t* starts_dev,
+                                                void* sample, const uint32_t* streams_host, void* workspace, size_t workspace_bytes,
+                                                wipa_stream_t stream) {
+    RT_CALL(cfg_check(cfg));
+    SplitScope split_scope(cfg);
+    const char* who = "wipa_decoder_admit_rows_prompted";
+    WIPA_REQUIRE(starts_dev, "%s: starts_dev (int32 [3][B]: window starts, token limits, prompt columns) is required", who);
+    RT_CALL(admit_checks(who, cfg, w, state, B, n_rows, slots_host, features_host, initial_tokens_host, n_init, limits_host, starts_dev, sample,
+                         streams_host));
+    const int L_max = cfg->n_text_ctx - n_init - 1;
+    WIPA_REQUIRE(W >= 0 && W <= L_max && (n_rows == 0 || prompt_lens_host) && (W == 0 || n_rows == 0 || prompt_tokens_host),
+                 "%s: prompt width W=%d outside 0..%d (n_text_ctx - n_init - 1), or null prompt arrays", who, W, L_max);
+    for (int i = 0; i < n_rows; ++i) {
+        const int Li = prompt_lens_host[i];
+        WIPA_REQUIRE(Li >= 0 && Li <= L_max, "%s: prompt length L[%d]=%d outside 0..%d (n_text_ctx - n_init - 1)", who, i, Li, L_max);
+        WIPA_REQUIRE(Li <= W, "%s: prompt length L[%d]=%d exceeds the width W=%d of the prompt array", who, i, Li, W);
+        for (int j = W - Li; j < W; ++j)
+            WIPA_REQUIRE(prompt_tokens_host[(size_t)i * W + j] >= 0 && prompt_tokens_host[(size_t)i * W + j] < cfg->n_vocab,
+                         "%s: prompt token [%d][%d]=%d outside the vocabulary of %d", who, i, j, prompt_tokens_host[(size_t)i * W + j], cfg->n_vocab);
+    }
+    if (n_rows == 0) return WIPA_OK;
+    const AdmitWs A = admit_ws(cfg, n_rows, W);
+    WIPA_REQUIRE(workspace && workspace_bytes >= A.total, "%s: workspace too small (%zu < %zu: wipa_decoder_admit_prompted_workspace_bytes)", who,
+                 workspace ? workspace_bytes : (size_t)0, A.total);
+    const size_t e = wipa_dtype_size(cfg->dtype);
+    const int d = cfg->n_text_state, Ta = cfg->n_audio_ctx;
+    WIPA_REQUIRE(((size_t)d * e) % 16 == 0, "%s: a K / V row of %zu bytes is no multiple of 16", who, (size_t)d * e);
+    const wipa_dec_layout L = dec_layout(cfg, B);
+    RT_CALL(state_fits(who, L, state_bytes));
+    hipStream_t s = (hipStream_t)stream;
+    char* st = (char*)state;
+    char* ws = (char*)workspace;
+    // meta, the right-aligned prompts (padding columns hold token 0) and the local starts W - L_i: one host image, one copy.  The image is
+    // pageable memory, which the copy has left when the call returns (as wipa_decoder_begin_ragged's arrays)
+    std::vector<int32_t> image((A.feat - A.meta) / 4, 0);
+    for (int i = 0; i < n_rows; ++i) {
+        int32_t* m = image.data() + (size_t)i * ADMIT_META;
+        m[0] = slots_host[i]; m[1] = prompt_lens_host[i]; m[2] = limits_host[i];
+        for (int t = 0; t < n_init; ++t) m[3 + t] = initial_tokens_host[i * n_init + t];
+        m[7] = sample ? (int32_t)streams_host[2 * i] : 0;
+        m[8] = sample ? (int32_t)streams_host[2 * i + 1] : 0;
+        for (int j = W - prompt_lens_host[i]; j < W; ++j) image[A.tokens / 4 + (size_t)i * W + j] = prompt_tokens_host[(size_t)i * W + j];
+        image[A.starts / 4 + i] = W - prompt_lens_host[i];
+    }
+    WIPA_CHECK_HIP(hipMemcpyAsync(ws + A.meta, image.data(), image.size() * 4, hipMemcpyHostToDevice, s));
+    const int32_t* meta = (const int32_t*)(ws + A.meta);
+    const int32_t* pos = (const int32_t*)(st + L.pos);
+    for (int i = 0; i < n_rows; ++i) RT_CALL(admit_cross(cfg, w, st, L, B, slots_host[i], features_host[i], stream));
+    hipLaunchKernelGGL(admit_rows_prompted_kernel, dim3(n_rows), dim3(256), 0, s, (int32_t*)(st + L.tokens), L.ld_tok, pos, cfg->n_text_ctx, B, n_init,
+                       W, meta, (const int32_t*)(ws + A.tokens), starts_dev, (float*)(st + L.sum_logprobs), (uint32_t*)sample);
+    WIPA_LAUNCH_CHECK();
+    if (W == 0) return WIPA_OK;
+    // the prompt pass: ONE batched walk over the admitted rows only, packed [n_rows * W], local starts W - L_i; it is wanted for the K / V
+    // of the prompt columns alone, which ScatterHook moves into the slots' self-attention cache behind every layer's q|k|v GEMM
+    const size_t clip_bytes = (size_t)Ta * d * e;
+    for (int i = 0; i < n_rows; ++i)
+        WIPA_CHECK_HIP(hipMemcpyAsync(ws + A.feat + (size_t)i * clip_bytes, features_host[i], clip_bytes, hipMemcpyDeviceToDevice, s));
+    ScatterHook hook;
+    hook.cfg = cfg; hook.self_kv = st + L.self_kv; hook.meta = meta; hook.pos = pos;
+    hook.n_rows = n_rows; hook.W = W; hook.B = B; hook.n_init = n_init; hook.s = s;
+    BatchedWalk k = {};
+    k.B = n_rows; k.T = W;
+    k.tokens = (const int32_t*)(ws + A.tokens); k.ld_tok = W;
+    k.x = (float*)(ws + A.x); k.ln = ws + A.ln; k.q = ws + A.q; k.ao = ws + A.ao; k.hb = ws + A.h;
+    k.qkv = ws + A.qkv;
+    k.starts = (const int32_t*)(ws + A.starts);
+    k.features = ws + A.feat; k.ckv_ws = ws + A.ckv;  // projected per layer from the admitted clips' features, in both cross forms
+    k.n_group = 1;
+    k.qkv_hook = &hook; k.kv_only = true;
+    return batched_layers(cfg, w, k, stream);
+}
+
+// ONE entry point for the PROMPTED steps: rules, sample, sample_rows and no_speech_dev may each be NULL (sample and sample_rows exclude
+// each other); starts_dev is int32 [3][B].  The call of wipa_decoder_run_continuous / _rules / _rows but for the tails the steps end in.
+extern "C" int wipa_decoder_run_continuous_prompted(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
+                                                    int n_init, int eot, const float* mask_first, const float* mask_always, int n_steps,
+                                                    int use_graph, const wipa_decode_rules* rules, const void* sample, const void* sample_rows,
+                                                    const int32_t* starts_dev, float* no_speech_dev, int no_speech_token, wipa_stream_t stream) {
+    RT_CALL(cfg_check(cfg));
+    const char* who = "wipa_decoder_run_continuous_prompted";
+    WIPA_REQUIRE(starts_dev, "%s: starts_dev (int32 [3][B]: window starts, token limits, prompt columns) is required", who);
+    WIPA_REQUIRE(!sample_rows || (!sample && ((uintptr_t)sample_rows % 16) == 0),
+                 "%s: sample_rows (16-byte aligned) takes the place of sample: pass one of them", who);
+    WIPA_REQUIRE(!no_speech_dev || rules, "%s: no_speech_dev needs rules", who);
+    StepCtx c{rules, sample, starts_dev, n_init, eot, mask_first, mask_always, false, true, no_speech_dev, no_speech_token, sample_rows};
+    c.prompted = true;
+    return decoder_run_continuous(who, cfg, w, state, state_bytes, B, c, n_steps, use_graph, stream);
 }
 
 extern "C" int wipa_decoder_release(void* state) {

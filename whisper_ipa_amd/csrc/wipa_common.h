@@ -36,9 +36,9 @@ int wipa_step_tail(const float* logits, int64_t ldl, int B, int V, const float* 
 int wipa_step_tail_continuous(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always, int32_t* tokens,
                               int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init, int eot,
                               const wipa_decode_rules* rules, const void* sample, const void* sample_rows, const int32_t* starts_dev,
-                              float* no_speech_dev, int no_speech_token, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
-                              const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y,
-                              int y_dtype, int D, float eps, wipa_stream_t stream);
+                              int prompted, float* no_speech_dev, int no_speech_token, float* sum_logprobs, int32_t* not_done, const void* tok_emb,
+                              int emb_dtype, const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b,
+                              void* y, int y_dtype, int D, float eps, wipa_stream_t stream);
 
 #define WIPA_CHECK_HIP(expr)                                                        \
     do {                                                                            \

@@ -43,8 +43,12 @@ What differs from upstream, on purpose:
     admission left (no second log-mel, encoder or language detection), into a row that sits beside greedy first attempts and beside
     retries of other windows at other temperatures: the decode state's sampling record holds a temperature per row
     (wipa_decoder_run_continuous_rows).  The window is booked when it passes or the schedule ends (the last attempt is kept).
-    ``word_timestamps``, conditioning, ``best_of``, a custom ``decode_fn`` and fp8 models are refused by name, and so is ``seed`` with a
-    custom ``stream_fn`` that does not declare ``stream_fn.retries = True``.
+    Conditioning (``condition_on_previous_text`` / ``initial_prompt``) runs on this schedule too: a file's next window exists once its
+    previous one is booked, so ``_WindowSource.pending`` hands it out with the prompt the rounds loop would build, and the prompt stands
+    in front of the window's admission column (continuous.py).  ``prompt_budget`` bounds the history kept.
+    ``word_timestamps``, ``best_of``, a custom ``decode_fn`` and fp8 models are refused by name, and so are ``seed`` with a custom
+    ``stream_fn`` that does not declare ``stream_fn.retries = True`` and conditioning with one that does not declare
+    ``stream_fn.prompts = True``.
 """
 from __future__ import annotations
 
@@ -247,6 +251,11 @@ def _window_samples(clip: np.ndarray, seek: int, size: int) -> np.ndarray:
     return out
 
 
+def _last_tokens(history: Sequence[int], budget: int) -> List[int]:
+    """the last ``budget`` tokens of a history (``history[-0:]`` would be all of it)"""
+    return [int(t) for t in history[-budget:]] if budget > 0 else []
+
+
 # ---------------------------------------------------------------- schedule="continuous"
 def _refuse_continuous(model, seed, word_timestamps, condition_on_previous_text, initial_prompt, best_of, decode_fn, stream_fn=None) -> None:
     """what ``schedule="continuous"`` does not serve, each refused by the option's name before anything is decoded"""
@@ -258,10 +267,15 @@ def _refuse_continuous(model, seed, word_timestamps, condition_on_previous_text,
                    "serves them declares stream_fn.retries = True, as a custom decode_fn brings a fallback_fn")
     if word_timestamps:
         no("word_timestamps", "the alignment runs on a round's windows")
-    if condition_on_previous_text:
-        no("condition_on_previous_text", "the continuous step takes the same number of initial tokens for every row")
-    if initial_prompt is not None:
-        no("initial_prompt", "the continuous step takes the same number of initial tokens for every row")
+    # prompts: the model's own stream serves them (a prompt per row in front of its admission column); a custom stream_fn that does
+    # declares stream_fn.prompts = True and takes source.pending() entries of (clip, limit, draw, prompt) -- the pattern of `retries`
+    if stream_fn is not None and not getattr(stream_fn, "prompts", False):
+        if condition_on_previous_text:
+            no("condition_on_previous_text", "every window is handed out with its file's prompt; a custom stream_fn that serves prompts "
+                                             "declares stream_fn.prompts = True")
+        if initial_prompt is not None:
+            no("initial_prompt", "every window is handed out with its file's prompt; a custom stream_fn that serves prompts declares "
+                                 "stream_fn.prompts = True")
     if best_of is not None:
         no("best_of", "candidate groups are drawn by the retries")
     if decode_fn is not None:
@@ -279,6 +293,8 @@ class StreamStats:
     groups: List[List[Tuple[int, int]]] = field(default_factory=list)     # per admitted group: its FRESH windows (file, seek)
     detected: List[List[Tuple[int, int]]] = field(default_factory=list)   # per detect_language call: the windows it looked at
     retries: List[Tuple[int, int, int]] = field(default_factory=list)     # (file, seek, attempt) of every retry, in the order they became pending
+    prompt_budget: Optional[int] = None                       # conditioning: the history tokens a window's prompt keeps, counted from the end
+    prompts: List[Tuple[int, int, int, int]] = field(default_factory=list)  # conditioning: (file, seek, history tokens, of which kept) per hand-out
 
 
 @dataclass
@@ -297,10 +313,16 @@ class _WindowSource:
     take a place in input order, at most ``slots`` of them at a time, and keep it until their last window has retired; the others wait.
     ``temps`` and ``seed``: the temperature fallback.  ``pending`` then returns (clip, limit, draw) -- draw None for a window's first
     attempt, (temps[attempt], attempt, (seek, file)) for a retry -- and a window that fails the thresholds with temperatures left is not
-    booked: the same clip becomes pending again.  ``on_booked(clip)``, when the stream sets it, hears of every window that is booked."""
+    booked: the same clip becomes pending again.  ``on_booked(clip)``, when the stream sets it, hears of every window that is booked.
+    ``prompt_budget`` (None: no conditioning): ``pending`` returns (clip, limit, draw, prompt) with the window's prompt columns --
+    ``[sot_prev]`` + the last ``prompt_budget`` tokens of the file's ``all_tokens[prompt_reset_since:]``, what the rounds loop hands to
+    ``decode(prompts=)``; empty without history.  A file has one window in flight and a failed attempt books nothing, so a retry is
+    handed out with the prompt of its first attempt."""
 
-    def __init__(self, clips, content_frames, books: _Books, slots: int, limit: int, stats: StreamStats, temps=(0.0,), seed=None):
+    def __init__(self, clips, content_frames, books: _Books, slots: int, limit: int, stats: StreamStats, temps=(0.0,), seed=None,
+                 prompt_budget: Optional[int] = None):
         self.clips, self.content_frames, self.books, self.limit, self.stats = clips, content_frames, books, int(limit), stats
+        self.prompt_budget = prompt_budget
         self.temps, self.seed = tuple(float(t) for t in temps), seed
         self.attempt = {}              # file -> index in temps of its window in flight
         self.on_booked = None
@@ -324,10 +346,17 @@ class _WindowSource:
             clip = (i, self.books.seek[i])
             self.size[clip] = min(N_FRAMES, self.content_frames[i] - self.books.seek[i])
             attempt = self.attempt.setdefault(i, 0)
-            if self.seed is None:
+            # the rounds schedule's retry: stream (seek, file index), the index in the schedule
+            draw = (self.temps[attempt], attempt, (clip[1], i)) if self.seed is not None and attempt else None
+            if self.prompt_budget is not None:
+                history = self.books.all_tokens[i][self.books.prompt_reset_since[i]:]
+                kept = _last_tokens(history, self.prompt_budget)
+                self.stats.prompts.append((i, clip[1], len(history), len(kept)))
+                out.append((clip, self.limit, draw, ([int(self.books.tok.sot_prev)] + kept) if kept else []))
+            elif self.seed is None:
                 out.append((clip, self.limit))
-            else:  # the rounds schedule's retry: stream (seek, file index), the index in the schedule
-                out.append((clip, self.limit, (self.temps[attempt], attempt, (clip[1], i)) if attempt else None))
+            else:
+                out.append((clip, self.limit, draw))
         self.ready = []
         return out
 
@@ -371,8 +400,19 @@ class _WindowSource:
             self.active.remove(i)
 
 
+def continuous_prompt_budget(n_text_ctx: int, n_init: int, sample_len: int, check_every: int) -> int:
+    """the most history tokens a window's prompt can keep on the continuous schedule: upstream's ``n_ctx // 2 - 1``, and what the column
+    window leaves in front of a row that generates ``sample_len`` tokens -- a live row spans ``prompt_room + n_init + sample_len +
+    2 * check_every - 1`` columns with ``prompt_room`` = budget + 1 (the ``sot_prev``), at most the default column limit.  With the
+    defaults (448, 3, 224, 8) that is 196 tokens against upstream's 223; a ``sample_len`` of 197 or less restores 223."""
+    from .continuous import default_column_limit
+
+    return max(min(n_text_ctx // 2 - 1, default_column_limit(n_text_ctx, n_init, check_every) - n_init - int(sample_len) - 2 * check_every), 0)
+
+
 def _transcribe_continuous(model, clips, content_frames, books: _Books, language, decode_options, stream_fn, slots: int,
-                           check_every: int, temps=(0.0,), seed=None) -> StreamStats:
+                           check_every: int, temps=(0.0,), seed=None, conditioning: bool = False,
+                           prompt_budget: Optional[int] = None) -> StreamStats:
     """``transcribe(schedule="continuous")``: every window of every file through min(slots, files) rows of one decode state.  The windows
     that become ready at the same check form one group: one log-mel call from the windows' own samples, one encoder call, one
     detect_language call for the windows of files whose language is still unknown, one admission."""
@@ -381,14 +421,23 @@ def _transcribe_continuous(model, clips, content_frames, books: _Books, language
     stats = StreamStats(rows=max(min(int(slots), len(clips)), 1))
     n_text_ctx = model.dims.n_text_ctx if model is not None else 448
     limit = decode_options.get("sample_len") or n_text_ctx // 2
-    source = _WindowSource(clips, content_frames, books, stats.rows, limit, stats, temps, seed)
+    budget = None
+    if conditioning:
+        largest = continuous_prompt_budget(n_text_ctx, len(books.tok.sot_sequence), limit, check_every)
+        budget = largest if prompt_budget is None else int(prompt_budget)
+        if not 0 <= budget <= largest:
+            raise ValueError(f"transcribe(schedule='continuous'): prompt_budget = {budget} outside 0 .. {largest} (n_text_ctx // 2 - 1, and what "
+                             f"the column window leaves in front of sample_len = {limit} tokens at check_every = {check_every})")
+        stats.prompt_budget = budget
+    source = _WindowSource(clips, content_frames, books, stats.rows, limit, stats, temps, seed, prompt_budget=budget)
+    more = {"prompt_room": budget + 1} if conditioning else {}  # the sot_prev in front of the history
     if stream_fn is None:
         from .continuous import stream_windows
 
-        def stream_fn(source, slots, check_every):
-            return stream_windows(model, source, {**decode_options, "language": language}, slots=slots, check_every=check_every, seed=seed)
+        def stream_fn(source, slots, check_every, **kw):
+            return stream_windows(model, source, {**decode_options, "language": language}, slots=slots, check_every=check_every, seed=seed, **kw)
 
-    stats.schedule = stream_fn(source, slots=stats.rows, check_every=check_every)
+    stats.schedule = stream_fn(source, slots=stats.rows, check_every=check_every, **more)
     return stats
 
 
@@ -461,7 +510,8 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
                tokenizer=None, seed: Optional[int] = None, fallback_fn: Optional[Callable] = None,
                prepend_punctuations: str = "\"'“¿([{-", append_punctuations: str = "\"'.。,，!！?？:：”)]}、",
                align_fn: Optional[Callable] = None, schedule: str = "rounds", slots: int = 64, check_every: int = 8,
-               stream_fn: Optional[Callable] = None, stats_out: Optional[list] = None, **decode_options):
+               stream_fn: Optional[Callable] = None, stats_out: Optional[list] = None, prompt_budget: Optional[int] = None,
+               **decode_options):
     """``audio``: a path, a 16 kHz mono float array, or a list of them.  Returns {"text", "segments", "language"} (a list of
     them for a list) with mlx_whisper's segment keys (``SEGMENT_KEYS``; plus ``needs_fallback`` where upstream would have
     retried).  ``condition_on_previous_text`` defaults to False here.  With True every window after a file's first is decoded with
@@ -481,16 +531,28 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
     ``num_frames[j]`` its content in mel frames); it is required with a custom ``decode_fn``.
     ``schedule="continuous"``: the windows go through ``slots`` rows of ONE decode state with refill instead of one lockstep batch per
     round (``_transcribe_continuous``); the host looks at the rows every ``check_every`` steps.  ``seed`` runs the temperature schedule
-    there too (a retried window is pending again with its own temperature; module docstring).  ``word_timestamps``,
-    ``condition_on_previous_text`` / ``initial_prompt``, ``best_of``, a custom ``decode_fn`` and fp8 models are refused.
+    there too (a retried window is pending again with its own temperature; module docstring).  ``condition_on_previous_text`` /
+    ``initial_prompt`` are served there as on the rounds schedule: a window is handed out with its file's prompt, which stands in front
+    of the window's admission column and goes through one batched pass at the admission.  ``word_timestamps``,
+    ``best_of``, a custom ``decode_fn`` and fp8 models are refused.
     ``stream_fn(source, slots=, check_every=)`` replaces the model's continuous decoder (tests); with a seed it must declare
-    ``stream_fn.retries = True`` and take ``source.pending()`` entries of (clip, limit, draw).  ``stats_out``: a list that receives the
-    run's ``StreamStats``."""
+    ``stream_fn.retries = True`` and take ``source.pending()`` entries of (clip, limit, draw); with conditioning it must declare
+    ``stream_fn.prompts = True``, take entries of (clip, limit, draw, prompt) and a ``prompt_room=`` keyword.  ``stats_out``: a list
+    that receives the run's ``StreamStats``.
+    ``prompt_budget`` (both schedules, with conditioning): the history tokens a window's prompt keeps, counted as the last ones.  None
+    on ``rounds`` is upstream's ``n_text_ctx // 2 - 1`` = 223.  None on ``continuous`` is the largest budget that fits the column window,
+    ``min(n_text_ctx // 2 - 1, column_limit - n_init - sample_len - 2 * check_every)``: with the defaults that is 196 tokens against
+    upstream's 223 at ``sample_len`` 224 (``continuous_prompt_budget``); a smaller ``sample_len`` restores 223.  So with the defaults
+    the two schedules condition a window that has more than 196 tokens of history on different prompts; an explicit ``prompt_budget``
+    of at most 196 gives both the same."""
     _refuse(condition_on_previous_text, initial_prompt, word_timestamps, clip_timestamps, hallucination_silence_threshold, temperature,
             decode_options, can_align=align_fn is not None or (model is not None and decode_fn is None),
             can_retry=decode_fn is None or fallback_fn is not None)
     _refuse_conditioning(condition_on_previous_text, initial_prompt, model, decode_fn, fallback_fn)
     conditioning = bool(condition_on_previous_text) or initial_prompt is not None
+    if prompt_budget is not None and (int(prompt_budget) < 0 or not conditioning):
+        raise ValueError(f"transcribe: prompt_budget = {prompt_budget} must not be negative and comes with condition_on_previous_text=True or "
+                         "an initial_prompt")
     if word_timestamps and align_fn is None and getattr(model, "_fp8", None):
         raise NotImplementedError("word_timestamps=True is not implemented for an fp8-quantised model: the alignment runs the "
                                   "teacher-forced decoder on bf16 / f32 weights")
@@ -532,7 +594,8 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
     seek, languages, all_segments, all_tokens, prompt_reset_since = (books.seek, books.languages, books.all_segments, books.all_tokens,
                                                                      books.prompt_reset_since)
     if schedule == "continuous":
-        stats = _transcribe_continuous(model, clips, content_frames, books, language, decode_options, stream_fn, slots, check_every, temps, seed)
+        stats = _transcribe_continuous(model, clips, content_frames, books, language, decode_options, stream_fn, slots, check_every, temps, seed,
+                                       conditioning=conditioning, prompt_budget=prompt_budget)
         if stats_out is not None:
             stats_out.append(stats)
     while schedule == "rounds":
@@ -545,6 +608,8 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
         for r, (i, size) in enumerate(zip(live, sizes)):
             windows[r] = _window_samples(clips[i], seek[i], size)
         prompts = [list(all_tokens[i][prompt_reset_since[i]:]) for i in live] if conditioning else None
+        if conditioning and prompt_budget is not None:  # None: decode() keeps upstream's last n_text_ctx // 2 - 1
+            prompts = [_last_tokens(p, int(prompt_budget)) for p in prompts]
         if conditioning:
             results = list(decode_fn(windows, [languages[i] for i in live], prompts=prompts))
         else:
