@@ -557,6 +557,12 @@ int wipa_step_embed_ragged(const float* logits, int64_t ldl, int B, int V, const
                            int32_t* not_done, const void* tok_emb, int emb_dtype, const float* emb_scale, const float* pos_emb, int n_ctx,
                            float* x, const float* ln_w, const float* ln_b, void* y, int y_dtype, int D, float eps, wipa_stream_t s);
 int wipa_decode_attn_ragged(const wipa_attn_desc* d, const int32_t* starts_dev, wipa_stream_t s);
+/* wipa_decode_attn for the self-attention cache of beams (see wipa_beam_bytes below): the B rows are clips x n_group beams and key t of
+ * row b is read from physical row b - b % n_group + anc[b][t] (anc uint8, row stride anc_ld, device).  With the identity table it is
+ * wipa_decode_attn bit for bit; with any table it equals wipa_decode_attn on a cache gathered accordingly.  At most 512 keys.  Like
+ * wipa_decode_attn_ragged it always takes the four-wave form: under WIPA_SELF_ATTN_WAVES=1, where wipa_decode_attn takes one wave per
+ * head, the two agree to rounding only. */
+int wipa_decode_attn_beam(const wipa_attn_desc* d, const uint8_t* anc, int64_t anc_ld, int n_group, wipa_stream_t s);
 /* The same three sites for a whole prompt at once (wipa_decoder_prefill_ragged): wipa_embed_tokens for columns 0 .. T-1 (f32 / bf16
  * embedding), wipa_attention for the causal self-attention with Tq == Tk (always the f32-math VALU kernel: the f32 MFMA form declines
  * device-side offsets; a padding query sees the row's first own key), and wipa_sample_step with the row's own position in the counter. */
@@ -797,6 +803,53 @@ int wipa_decoder_run_sample(const wipa_model_cfg* cfg, const void* const* weight
 int wipa_decoder_prefill_sample(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
                                 int eot, const float* mask_first, const float* mask_always, int use_graph,
                                 const wipa_decode_rules* rules, const void* sample, wipa_stream_t s);
+/* Beam search (upstream's BeamSearchDecoder + MaximumLikelihoodRanker; DecodingOptions.beam_size / patience / length_penalty).  The B rows
+ * of a call are B / n_group clips x n_group beams, clip-major, with cfg.dec_n_group = n_group = beam_size (1..16; 1 is one row per clip).
+ * Per step and clip, every beam offers the n_group + 1 best columns of its FILTERED row (the row the greedy / rules tails reduce;
+ * logprob = l[c] - logsumexp(l), lowest column on ties); the candidates are walked in descending sum_logprobs[row] + logprob (one f32
+ * add; ties: lower beam, then lower rank): a candidate ending in eot joins the clip's finished store while that holds fewer than
+ * max_candidates = round(beam_size * patience) sequences, any other becomes the next beam until n_group are saved.  On the first
+ * generated step only beam 0 offers (the beams of a clip are one sequence there).  Live beams never hold eot: there is no EOT latch.
+ * A clip is complete when its store holds max_candidates sequences; it keeps stepping and its store no longer changes.  Where
+ * max_candidates < n_group (patience below 1) the completing step itself fills the store up to n_group with that step's new beams + eot,
+ * in descending sum_logprobs, as upstream's finalize would right there: the store's row needs columns up to *pos_dev + 2 < ld_tok.
+ * The self-attention cache is NOT permuted: new K / V go to row b's own physical row and the ancestor table says where a beam's
+ * history lies (wipa_decode_attn_beam).
+ * The caller-owned device buffer `beam` of wipa_beam_bytes(B, n_group, max_candidates, ld_tok) bytes, 16-byte aligned, every part
+ * rounded up to 256 bytes, cap = max(n_group, max_candidates), clips = B / n_group:
+ *   anc        uint8 [B][ld_tok]              group-local physical row that holds column t of row b's history (row stride ld_tok)
+ *   candidates {f32 logprob, i32 column} [B][n_group + 1]   the rows' offers of the current step, sorted
+ *   src        int32 [B]                      the row (group-local) every beam of the last step descends from
+ *   finished   int32 [clips][cap][ld_tok]     the store's sequences from column 0, eot behind the last token
+ *   scores     f32   [clips][cap]             their sum_logprobs
+ *   lengths    int32 [clips][cap]             their generated tokens before eot
+ *   counts     int32 [clips]                  sequences in the store
+ *   counters   int32 [64]                     [0] clips of the running step whose store is not full, [1] arrived workgroups
+ * wipa_beam_begin clears the counts and the counters and writes the identity table (after wipa_decoder_begin, before the prompt pass).
+ * wipa_beam_step is the selection alone on any rows (no embedding, no position advance), like wipa_sample_step: tokens column
+ * *pos_dev + 1, the gathered token rows and table, sum_logprobs, the store, and *not_done = the clips whose store is not full after
+ * this step.  rules may be NULL.  wipa_decoder_prefill_beam / wipa_decoder_run_beam are wipa_decoder_prefill_sample / _run_sample with
+ * beams: beam == NULL enqueues exactly what those enqueue; with beam, sample must be NULL.  The step graph is keyed on the buffer's
+ * address and on max_candidates.  Refused (WIPA_ERR_ARG, nothing enqueued): fp8 decoder tables, WIPA_DECODE_TAIL=0,
+ * WIPA_DECODE_FUSED=1, B % n_group != 0, n_group outside 1..16, max_candidates outside 1..64, a buffer below wipa_beam_bytes.
+ * wipa_beam_finalize (after the last step; n = generated columns): a clip with fewer than n_group finished sequences is filled with its
+ * live beams + eot in descending sum_logprobs; then wipa_rank_groups' arithmetic over the store -- (double)sum / penalty[length],
+ * penalty f64 [n + 1], first maximum -- and per clip the winner's columns [0, sample_begin + length) followed by eot up to column
+ * sample_begin + n, its sum_logprobs and its length. */
+size_t wipa_beam_bytes(int B, int n_group, int max_candidates, int64_t ld_tok);
+int wipa_beam_begin(void* beam, size_t beam_bytes, int B, int n_group, int max_candidates, int64_t ld_tok, wipa_stream_t s);
+int wipa_beam_step(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always, int32_t* tokens,
+                   int64_t ld_tok, int32_t* pos_dev, int n_init, int eot, const wipa_decode_rules* rules, void* beam, int n_group,
+                   int max_candidates, float* sum_logprobs, int32_t* not_done, wipa_stream_t s);
+int wipa_beam_finalize(void* beam, const int32_t* tokens, int64_t ld_tok, int B, int n_group, int max_candidates, int sample_begin, int n,
+                       int eot, const float* sum_logprobs, const double* penalty, int32_t* best_tokens, int64_t ld_out, float* best_sum,
+                       int32_t* best_len, wipa_stream_t s);
+int wipa_decoder_run_beam(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int n_init, int eot,
+                          const float* mask_first, const float* mask_always, int n_steps, int use_graph, const wipa_decode_rules* rules,
+                          void* beam, size_t beam_bytes, int max_candidates, wipa_stream_t s);
+int wipa_decoder_prefill_beam(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init, int eot,
+                              const float* mask_first, const float* mask_always, int use_graph, const wipa_decode_rules* rules,
+                              const void* sample, void* beam, size_t beam_bytes, int max_candidates, wipa_stream_t s);
 /* Per-row prompts (mlx_whisper.transcribe's condition_on_previous_text / initial_prompt, DecodingOptions.prompt / prefix: each row's
  * initial tokens are [sot_prev] + history + sot_sequence + prefix, 1..n_text_ctx of them), in the layout described at
  * wipa_embed_layernorm_ragged above.

@@ -141,7 +141,8 @@ BASE_DECODE_MODES = ("decode", "transcribe")
 
 
 def transcribe_files(model, audio_paths: List[str], batch_size: int = 64, progress=None, seed: Optional[int] = None,
-                     condition_on_previous_text: bool = False, initial_prompt: Optional[str] = None, schedule: str = "rounds") -> List[str]:
+                     condition_on_previous_text: bool = False, initial_prompt: Optional[str] = None, schedule: str = "rounds",
+                     beams: Optional[dict] = None) -> List[str]:
     """reference :112-119 for the whole list: ``mlx_whisper.transcribe(path, language="en", word_timestamps=False)["text"]`` per
     file through whisper_ipa_amd.transcribe, ``batch_size`` files per call (their windows decode as one batch per round).  One
     text per path, "" where the file could not be read.  ``seed``: run mlx_whisper.transcribe's temperature schedule on the windows
@@ -151,7 +152,9 @@ def transcribe_files(model, audio_paths: List[str], batch_size: int = 64, progre
     decode state with refill, 8 x ``batch_size`` files per call (what bounds a call is the host memory of its samples, not its rows);
     it serves ``seed`` (a retried window is admitted again with a temperature of its own) and ``condition_on_previous_text`` /
     ``initial_prompt`` (a window is admitted with its file's prompt in front of its admission column; with the default sample_len the
-    prompt keeps the last 196 history tokens, not upstream's 223 -- transcribe's ``prompt_budget``), and refuses the rest by name."""
+    prompt keeps the last 196 history tokens, not upstream's 223 -- transcribe's ``prompt_budget``), and refuses the rest by name.
+    ``beams``: ``beam_size`` / ``patience`` / ``length_penalty`` for transcribe (rounds schedule: every window's temperature-0 decode is a
+    beam search)."""
     from whisper_ipa_amd import transcribe
 
     texts = [""] * len(audio_paths)
@@ -167,7 +170,8 @@ def transcribe_files(model, audio_paths: List[str], batch_size: int = 64, progre
                 print(f"\nError transcribing {path}: {e}")
         if clips:
             for i, r in zip(slots, transcribe(model, clips, language="en", word_timestamps=False, seed=seed,
-                                              condition_on_previous_text=condition_on_previous_text, initial_prompt=initial_prompt, **more)):
+                                              condition_on_previous_text=condition_on_previous_text, initial_prompt=initial_prompt, **more,
+                                              **(beams or {}))):
                 texts[i] = r["text"].strip()
         if progress is not None:
             progress(min(b + per_call, len(audio_paths)))
@@ -184,7 +188,7 @@ def evaluate_model(model_path: str, test_data_path: str, num_samples: Optional[i
                    is_checkpoint: bool = False, n_mels: int = 80, base_model: str = "mlx-community/whisper-small-mlx",
                    batch_size: int = 64, passes_in_flight: int = 4, ingest: str = "device", scoring: str = "device",
                    base_decode: str = "decode", seed: Optional[int] = None, condition_on_previous_text: bool = False,
-                   initial_prompt: Optional[str] = None, decode: str = "lockstep") -> Dict:
+                   initial_prompt: Optional[str] = None, decode: str = "lockstep", beams: Optional[dict] = None) -> Dict:
     if decode not in DECODE_MODES:
         raise ValueError(f"decode must be one of {DECODE_MODES}, got {decode!r}")
     rank, world_size = parallel.world()
@@ -218,7 +222,7 @@ def evaluate_model(model_path: str, test_data_path: str, num_samples: Optional[i
     if base_decode == "transcribe" and not is_checkpoint:
         local_hyp = transcribe_files(model, [s["audio_path"] for s in mine], batch_size=batch_size, seed=seed,
                                      condition_on_previous_text=condition_on_previous_text, initial_prompt=initial_prompt,
-                                     schedule="continuous" if decode == "continuous" else "rounds",
+                                     schedule="continuous" if decode == "continuous" else "rounds", beams=beams,
                                      progress=lambda n: say(f"  {n}/{len(mine)} clips on rank 0", flush=True))
     elif decode == "continuous":
         local_hyp = transcribe_clips_continuous(model, [s["audio_path"] for s in mine], options, slots=batch_size, ingest=ingest,
@@ -321,6 +325,11 @@ def main(argv=None) -> Dict:
                          "its prompt, as mlx_whisper.transcribe does by default (default here: off); served by --decode continuous too")
     ap.add_argument("--initial-prompt", type=str, default=None,
                     help="with --base-decode transcribe: mlx_whisper.transcribe's initial_prompt, the prompt of every file's first window")
+    ap.add_argument("--beam-size", type=int, default=None,
+                    help="with --base-decode transcribe: beam search with this many beams for every window's temperature-0 decode")
+    ap.add_argument("--patience", type=float, default=None, help="with --beam-size: the finished store holds round(beam_size * patience) sequences")
+    ap.add_argument("--length-penalty", type=float, default=None,
+                    help="with --beam-size (or best-of retries): rank by sum_logprobs / ((5 + length) / 6) ** this instead of by length")
     ap.add_argument("--results-json", type=str, default=None, help="also write both result dicts here (rank 0)")
     ap.add_argument("--allow-byte-fallback", action="store_true",
                     help="run without the Whisper vocabulary (WIPA_TIKTOKEN unset): hypotheses render ids >= 256 as <|idN|>; "
@@ -339,13 +348,16 @@ def main(argv=None) -> Dict:
     rank, _ = parallel.world()
     num_samples = None if args.num_samples == 0 else args.num_samples
     base_results = None
+    beams = {k: v for k, v in (("beam_size", args.beam_size), ("patience", args.patience), ("length_penalty", args.length_penalty)) if v is not None}
+    if beams and args.base_decode != "transcribe":
+        ap.error("--beam-size / --patience / --length-penalty go with --base-decode transcribe")
     if not args.skip_base:
         base_results = evaluate_model(args.base_model, args.test_data, num_samples, model_name="Base Whisper Model",
                                       is_checkpoint=False, n_mels=args.n_mels, base_model=args.base_model, batch_size=args.batch_size,
                                       passes_in_flight=args.passes_in_flight, ingest=args.ingest, scoring=args.scoring,
                                       base_decode=args.base_decode, seed=args.seed,
                                       condition_on_previous_text=args.condition_on_previous_text, initial_prompt=args.initial_prompt,
-                                      decode=args.decode)
+                                      decode=args.decode, beams=beams)
     trained_results = evaluate_model(args.checkpoint, args.test_data, num_samples, model_name="Trained Checkpoint",
                                      is_checkpoint=True, n_mels=args.n_mels, base_model=args.base_model, batch_size=args.batch_size,
                                      passes_in_flight=args.passes_in_flight, ingest=args.ingest, scoring=args.scoring, decode=args.decode)

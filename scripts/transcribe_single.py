@@ -38,12 +38,15 @@ def load_checkpoint_model(checkpoint_path: str, base_model: str = "mlx-community
     return model
 
 
-def transcribe_file(model, audio_path: str, temperature: float = 0.0, seed=None, best_of=None) -> str:
+def transcribe_file(model, audio_path: str, temperature: float = 0.0, seed=None, best_of=None, beam_size=None, patience=None,
+                    length_penalty=None) -> str:
     print(f"Transcribing {audio_path}...")
     audio = load_audio_batch([audio_path])  # load_audio -> pad_or_trim (reference :43-44) on the GPU: [1, 480000]
     mel = log_mel_spectrogram(audio, n_mels=model.dims.n_mels).to(torch.float32)
     # IPA is decoded "as English"; a temperature above 0 samples, reproducibly, from ``seed``; ``best_of`` candidates, the best one kept
-    options = DecodingOptions(language="en", without_timestamps=True, temperature=temperature, seed=seed, best_of=best_of)
+    # ``beam_size`` (temperature 0): beam search, with ``patience`` and ``length_penalty`` as upstream's DecodingOptions take them
+    options = DecodingOptions(language="en", without_timestamps=True, temperature=temperature, seed=seed, best_of=best_of, beam_size=beam_size,
+                              patience=patience, length_penalty=length_penalty)
     audio_features = model.encoder(mel)
     result = decode(model, audio_features, options)
     return result[0].text.strip()
@@ -59,6 +62,10 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=None, help="seed of the sampling draw: the same seed gives the same transcript")
     ap.add_argument("--best-of", type=int, default=None,
                     help="with --temperature above 0: draw this many candidates and keep the one with the highest length-normalised log-probability")
+    ap.add_argument("--beam-size", type=int, default=None, help="at temperature 0: beam search with this many beams (1..16)")
+    ap.add_argument("--patience", type=float, default=None, help="with --beam-size: the finished store holds round(beam_size * patience) sequences")
+    ap.add_argument("--length-penalty", type=float, default=None,
+                    help="with --beam-size or --best-of: rank by sum_logprobs / ((5 + length) / 6) ** this instead of by length")
     ap.add_argument("--word-timestamps", action="store_true",
                     help="transcribe through whisper_ipa_amd.transcribe(word_timestamps=True) and also print one line per word (start, end, probability)")
     ap.add_argument("--allow-byte-fallback", action="store_true",
@@ -72,6 +79,8 @@ def main(argv=None):
         ap.error("--temperature above 0 needs --seed")
     if args.best_of is not None and args.temperature == 0.0 and not args.word_timestamps:
         ap.error("--best-of needs --temperature above 0 (best_of with greedy sampling is not compatible)")
+    if args.beam_size is not None and (args.temperature != 0.0 or args.word_timestamps):
+        ap.error("--beam-size runs at temperature 0 and without --word-timestamps")
     words = []
     if args.word_timestamps:  # one decode: the prediction is the transcript the words belong to
         if args.temperature != 0.0:
@@ -84,7 +93,8 @@ def main(argv=None):
         text = out["text"].strip()
         words = [w for seg in out["segments"] for w in seg.get("words", [])]
     else:
-        text = transcribe_file(model, args.audio, temperature=args.temperature, seed=args.seed, best_of=args.best_of)
+        text = transcribe_file(model, args.audio, temperature=args.temperature, seed=args.seed, best_of=args.best_of, beam_size=args.beam_size,
+                               patience=args.patience, length_penalty=args.length_penalty)
     print("\n" + "=" * 50)
     print(f"Audio: {args.audio}")
     print(f"Prediction: {text}")

@@ -219,6 +219,17 @@ SIGNATURES = {
                                        c_int, c_int, _P(DecodeRules), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                        c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "wipa_decode_attn_ragged": (c_int, [_P(AttnDesc), c_void_p, c_void_p]),
+    "wipa_decode_attn_beam": (c_int, [_P(AttnDesc), c_void_p, c_int64, c_int, c_void_p]),
+    "wipa_beam_bytes": (c_size_t, [c_int, c_int, c_int, c_int64]),
+    "wipa_beam_begin": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int64, c_void_p]),
+    "wipa_beam_step": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, _P(DecodeRules),
+                               c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "wipa_beam_finalize": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64,
+                                   c_void_p, c_void_p, c_void_p]),
+    "wipa_decoder_run_beam": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                                      _P(DecodeRules), c_void_p, c_size_t, c_int, c_void_p]),
+    "wipa_decoder_prefill_beam": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                          _P(DecodeRules), c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "wipa_embed_tokens_ragged": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "wipa_attention_ragged": (c_int, [_P(AttnDesc), c_void_p, c_void_p]),
     "wipa_sample_step_ragged": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int,

@@ -34,7 +34,10 @@ struct AttnParams {
 // Candidate groups (best-of-N sampling; wipa_decode_cross_attn_grouped): the B rows are B / n_group clips x n_group candidates and K / V
 // hold one entry per CLIP: row b reads clip b / n_group.  The GROUPED instantiations take the count; the others keep their arguments
 // and their code.
-template <bool RAGGED, bool GROUPED = false>
+// Beams (wipa_decode_attn_beam): the B rows are B / n_group clips x n_group beams, and a beam's history is spread over the physical cache
+// rows of its clip: key t of row b lies in physical row b - b % n_group + anc[b][t].  The BEAM instantiations take the table; the others keep
+// their arguments and their code.
+template <bool RAGGED, bool GROUPED = false, bool BEAM = false>
 struct AttnArgs : AttnParams {};
 template <>
 struct AttnArgs<true> : AttnParams {
@@ -42,6 +45,12 @@ struct AttnArgs<true> : AttnParams {
 };
 template <>
 struct AttnArgs<false, true> : AttnParams {
+    int n_group;
+};
+template <>
+struct AttnArgs<false, false, true> : AttnParams {
+    const uint8_t* anc;  // uint8 [B][anc_ld], device: the group-local physical row that holds column t of row b's history
+    int64_t anc_ld;
     int n_group;
 };
 
@@ -302,8 +311,11 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_mfma_kernel(AttnParams p) {
 // A query at a padding column (below k_start[b]) sees its own key only.  A separate instantiation: the kernels of calls without
 // prompts keep their arguments and their code.
 // GROUPED (candidate groups): K / V of row b are those of clip b / n_group; nothing else differs.
-template <typename T, int WPH, bool NT = (WPH == 4), bool RAGGED = false, bool GROUPED = false>
-__global__ __launch_bounds__(256) void decode_attn_kernel(AttnArgs<RAGGED, GROUPED> p) {
+// BEAM (beams over an ancestor table, wipa_decode_attn_beam): key t of row b is loaded from physical row b - b % n_group + anc[b][t] --
+// one byte per key ahead of the row's load, the same clamped index for both.  The key partition over lanes and waves, the clamp and the
+// streaming softmax are the text below, so a BEAM row does the arithmetic of a plain row on a physically gathered cache.
+template <typename T, int WPH, bool NT = (WPH == 4), bool RAGGED = false, bool GROUPED = false, bool BEAM = false>
+__global__ __launch_bounds__(256) void decode_attn_kernel(AttnArgs<RAGGED, GROUPED, BEAM> p) {
     constexpr int EPL = Vec16<T>::EPL;  // elements per 16-byte load
     constexpr int LPK = 64 / EPL;       // lanes per key row (64 dims)
     constexpr int G = 64 / LPK;         // keys per wave instruction
@@ -336,6 +348,13 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(AttnArgs<RAGGED, GROUP
         Vb += (int64_t)k_first * p.v_rs;
     }
     const int64_t k_rs = p.k_rs, v_rs = p.v_rs;
+    const uint8_t* anc_row = nullptr;  // BEAM only: Kb / Vb then point at the first physical row of the row's clip
+    if constexpr (BEAM) {
+        const int64_t back = (int64_t)(b % p.n_group);
+        Kb -= back * p.k_bs;
+        Vb -= back * p.v_bs;
+        anc_row = p.anc + (int64_t)b * p.anc_ld;
+    }
     float m = NEG_BIG, l = 0.f;
     float acc[EPL];
 #pragma unroll
@@ -349,8 +368,15 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(AttnArgs<RAGGED, GROUP
         Vec16<T> ka[U], va[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {  // cross-attention (NT): 3.5 GB per step read exactly once -> non-temporal (nt) loads
-            ka[u] = load_row_clamped<NT>(Kb, t0 + u * G + g, Tk - 1, k_rs);
-            va[u] = load_row_clamped<NT>(Vb, t0 + u * G + g, Tk - 1, v_rs);
+            if constexpr (BEAM) {
+                const int t = min(t0 + u * G + g, Tk - 1);  // load_row_clamped's clamp, taken first: the table is read at the same index
+                const int64_t phys = min((int)anc_row[t], p.n_group - 1);  // a table entry never leaves the clip's rows
+                ka[u] = load_row_clamped<NT>(Kb + phys * p.k_bs, t, Tk - 1, k_rs);
+                va[u] = load_row_clamped<NT>(Vb + phys * p.v_bs, t, Tk - 1, v_rs);
+            } else {
+                ka[u] = load_row_clamped<NT>(Kb, t0 + u * G + g, Tk - 1, k_rs);
+                va[u] = load_row_clamped<NT>(Vb, t0 + u * G + g, Tk - 1, v_rs);
+            }
         }
         WIPA_STREAM_STEP(U, qf, ka, va, t0, m, l, acc);
     };
@@ -970,6 +996,31 @@ extern "C" int wipa_decode_attn_ragged(const wipa_attn_desc* d, const int32_t* s
         hipLaunchKernelGGL((decode_attn_kernel<float, 4, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
     else
         hipLaunchKernelGGL((decode_attn_kernel<__bf16, 4, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    WIPA_LAUNCH_CHECK();
+    return WIPA_OK;
+}
+
+// wipa_decode_attn for the self-attention cache of beams: row b's key t lies in physical row b - b % n_group + anc[b][t]
+extern "C" int wipa_decode_attn_beam(const wipa_attn_desc* d, const uint8_t* anc, int64_t anc_ld, int n_group, wipa_stream_t stream) {
+    WIPA_REQUIRE(d && d->q && d->k && d->v && d->out && anc, "wipa_decode_attn_beam: null pointer (anc is required)");
+    WIPA_REQUIRE(d->B > 0 && d->H > 0 && d->Tq == 1, "wipa_decode_attn_beam: one query row per (b,h) (Tq=%d)", d->Tq);
+    WIPA_REQUIRE(d->dtype == WIPA_F32 || d->dtype == WIPA_BF16, "wipa_decode_attn_beam: bad dtype %d", d->dtype);
+    WIPA_REQUIRE(attn_strides_aligned(d), "wipa_decode_attn_beam: strides must keep 16-byte alignment");
+    WIPA_REQUIRE(n_group >= 1 && n_group <= 16 && d->B % n_group == 0, "wipa_decode_attn_beam: n_group=%d outside 1..16 or not dividing B=%d", n_group,
+                 d->B);
+    const int max_keys = d->Tk + (d->tk_dev ? 448 : 0);
+    WIPA_REQUIRE(max_keys <= 512 && anc_ld >= (d->tk_dev ? 1 : d->Tk), "wipa_decode_attn_beam: Tk=%d keys (a short, growing cache of at most 512) / anc_ld=%lld",
+                 d->Tk, (long long)anc_ld);
+    AttnArgs<false, false, true> p;
+    fill_attn_params(d, p);
+    p.anc = anc;
+    p.anc_ld = anc_ld;
+    p.n_group = n_group;
+    dim3 grid(d->H, d->B);  // the four-wave, default-policy form the self-attention cache takes in wipa_decode_attn
+    if (d->dtype == WIPA_F32)
+        hipLaunchKernelGGL((decode_attn_kernel<float, 4, false, false, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL((decode_attn_kernel<__bf16, 4, false, false, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;
 }

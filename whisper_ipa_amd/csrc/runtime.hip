@@ -438,6 +438,11 @@ struct StepCtx {
     // wipa_decoder_run_continuous_prompted: `starts` is int32 [3][B] -- window starts, token limits, prompt columns -- and the step ends
     // in the PROMPTED tails (the sot sequence stands behind the row's prompt); everything before the tail is the continuous step
     bool prompted;
+    // beams (wipa_decoder_run_beam / _prefill_beam): the caller's beam buffer (wipa_beam_bytes; NULL: no beams) and the size of a clip's
+    // finished store.  The rows are clips x cfg.dec_n_group beams; the self-attention reads the cache through the buffer's ancestor
+    // table and the step ends in the beam tail (csrc/beam.hip) on the written logits.
+    void* beam = nullptr;
+    int beam_max_candidates = 0;
 };
 // The logits projection with the greedy partials in its epilogue + a tail that merges them (round 4; WIPA_LOGITS_FUSED=0 restores
 // the plain GEMM + the row-scanning tail): bf16 models without fp8 decoder tables, <= 64 rows, tail-fused steps.  Measured on
@@ -445,7 +450,7 @@ struct StepCtx {
 bool logits_fused(const wipa_model_cfg* cfg, int B, const StepCtx& c) {
     const char* e = getenv("WIPA_LOGITS_FUSED");  // read per call like the other step variants: part of the graph key
     const bool on = !(e && atoi(e) == 0);
-    return on && !c.rules && !c.sample && !c.starts && tail_fused() && cfg->dec_w_dtype == 0 && wipa_logits_greedy_supported(B, cfg->n_vocab, cfg->n_text_state, cfg->dtype);
+    return on && !c.rules && !c.sample && !c.starts && !c.beam && tail_fused() && cfg->dec_w_dtype == 0 && wipa_logits_greedy_supported(B, cfg->n_vocab, cfg->n_text_state, cfg->dtype);
 }
 int32_t* done_counter_of(char* st, const wipa_dec_layout& L) { return (int32_t*)(st + L.pos + 64); }  // zeroed with pos by wipa_decoder_begin
 
@@ -548,6 +553,7 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
             a.o_bs = d; a.o_rs = d; a.o_hs = 64;
             a.B = B; a.H = H; a.Tq = 1; a.Tk = 1; a.causal = 0; a.dtype = dt;
             if (ctx.starts) RT_CALL(wipa_decode_attn_ragged(&a, ctx.starts, stream));  // row b sees keys starts[b] .. pos
+            else if (ctx.beam) RT_CALL(wipa_decode_attn_beam(&a, (const uint8_t*)ctx.beam, L.ld_tok, G, stream));  // the table heads the buffer
             else RT_CALL(wipa_decode_attn(&a, stream));
         }
         RT_CALL(r.residual_gemm(ao, d, lw[4], lw[5]));
@@ -635,6 +641,11 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
         // (with ctx.rules the timestamp rules, with ctx.sample the draw, with ctx.starts the RAGGED tails: position embedding and sampling
         // counter at the row's own position)
         const void* const* lw0 = w + WIPA_DEC_GLOBAL;
+        if (ctx.beam)  // top G + 1 per row, then per clip: selection, gather, finished store, the next input rows, the position advance
+            return wipa_beam_tail("wipa_decoder_run_beam", logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos,
+                                  posd, ctx.n_init, ctx.eot, ctx.rules, ctx.beam, G, ctx.beam_max_candidates, (float*)(st + L.sum_logprobs),
+                                  (int32_t*)(st + L.not_done), w[0], emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], nctx, x_first,
+                                  (const float*)lw0[0], (const float*)lw0[1], ln, dt, d, 1e-5f, stream);
         if (ctx.continuous)
             return wipa_step_tail_continuous(logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos, posd,
                                              done_counter_of(st, L), ctx.n_init, ctx.eot, ctx.rules, ctx.sample, ctx.sample_rows, ctx.starts,
@@ -766,7 +777,10 @@ int enqueue_first_token(const wipa_model_cfg* cfg, char* st, const wipa_dec_layo
     float* sums = (float*)(st + L.sum_logprobs);
     int32_t* not_done = (int32_t*)(st + L.not_done);
     hipLaunchKernelGGL(set_pos_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pos, posd, P - 1, d);
-    if (ctx.sample && ctx.starts)
+    if (ctx.beam)
+        RT_CALL(wipa_beam_step(logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos, P, ctx.eot, ctx.rules,
+                               ctx.beam, group_of(cfg), ctx.beam_max_candidates, sums, not_done, stream));
+    else if (ctx.sample && ctx.starts)
         RT_CALL(wipa_sample_step_ragged(logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos, P, ctx.eot,
                                         ctx.rules, ctx.sample, ctx.starts, sums, not_done, stream));
     else if (ctx.sample)
@@ -929,7 +943,8 @@ int state_fits(const char* who, const wipa_dec_layout& L, size_t state_bytes) {
 // A continuous step with a temperature per row has its own variant bit, and its record's address stands in the sampling record's term.
 // A PROMPTED continuous step is the continuous key plus a variant bit of its own (candidate groups, which share that range of the word,
 // are not served by a continuous call).
-typedef std::tuple<const void*, const void*, const void*, const void*, int, int, int, int, int, int, int, int, int, const void*, const void*, const void*, const void*, int> GraphKey;  // ..., generation, kind: 0 step, 1 prefill, 2 lean step (no logit stores), rules, sampling record, starts, workspace, no-speech array, no-speech column
+// A BEAM step bakes in the beam buffer's address and max_candidates: the last two terms, of their own (NULL and 0 without beams).
+typedef std::tuple<const void*, const void*, const void*, const void*, int, int, int, int, int, int, int, int, int, const void*, const void*, const void*, const void*, int, const void*, int> GraphKey;  // ..., generation, kind: 0 step, 1 prefill, 2 lean step (no logit stores), rules, sampling record, starts, workspace, no-speech array, no-speech column
 // sampling lives in the fused step tail, like the rules: refused before anything is enqueued where the step cannot carry it
 int sample_servable(const char* who, const wipa_model_cfg* cfg, int B, const void* sample) {
     if (!sample) return WIPA_OK;
@@ -990,7 +1005,7 @@ GraphKey graph_key(const wipa_model_cfg* cfg, const void* const* w, const void* 
     return GraphKey(state, (const void*)w, (const void*)c.mask_first, (const void*)c.mask_always, B, c.n_init, c.eot, variant,
                     cfg->weights_generation, kind, c.rules ? c.rules->timestamp_begin : 0, c.rules ? c.rules->no_timestamps : 0,
                     c.rules ? c.rules->max_initial_timestamp_index : 0, c.sample ? c.sample : c.sample_rows, (const void*)c.starts, workspace,
-                    (const void*)c.no_speech, c.no_speech ? c.no_speech_token : 0);
+                    (const void*)c.no_speech, c.no_speech ? c.no_speech_token : 0, (const void*)c.beam, c.beam ? c.beam_max_candidates : 0);
 }
 // The executable graph cached under `key`.  When there is none, `enqueue` is captured on s (relaxed mode, nothing but kernel launches
 // between begin and end), instantiated and inserted; an enqueue that fails ends the capture, destroys the graph and hands its code back.
@@ -1556,10 +1571,52 @@ extern "C" int wipa_decoder_prefill_rules(const wipa_model_cfg* cfg, const void*
 extern "C" int wipa_decoder_prefill_sample(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
                                            int n_init, int eot, const float* mask_first, const float* mask_always, int use_graph,
                                            const wipa_decode_rules* rules, const void* sample, wipa_stream_t stream) {
+    return wipa_decoder_prefill_beam(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, use_graph, rules, sample, nullptr, 0, 0,
+                                     stream);
+}
+
+namespace {
+// what a beam call serves, in the words of its entry point; refused before anything is enqueued
+int beam_servable(const char* who, const wipa_model_cfg* cfg, int B, const void* sample, const void* beam, size_t beam_bytes, int max_candidates) {
+    if (!beam) return WIPA_OK;
+    const int G = group_of(cfg);
+    WIPA_REQUIRE(!sample, "%s: beam and sample cannot be given together (beams run at temperature 0)", who);
+    WIPA_REQUIRE(cfg->dec_w_dtype == 0, "%s: beam is not served on fp8 decoder tables (cfg.dec_w_dtype)", who);
+    WIPA_REQUIRE(tail_fused() && !use_fused_step(cfg, B), "%s: beam needs the unfused step with the fused tail; WIPA_DECODE_TAIL=0 / WIPA_DECODE_FUSED=1 cannot serve it", who);
+    WIPA_REQUIRE(G >= 1 && G <= 16, "%s: cfg.dec_n_group=%d (n_group) outside 1..16", who, G);
+    WIPA_REQUIRE(B % G == 0, "%s: B=%d rows are no multiple of cfg.dec_n_group=%d (n_group)", who, B, G);
+    WIPA_REQUIRE(max_candidates >= 1 && max_candidates <= 64, "%s: max_candidates=%d outside 1..64", who, max_candidates);
+    WIPA_REQUIRE(cfg->n_vocab <= 65536, "%s: need n_vocab <= 65536 (n_vocab=%d)", who, cfg->n_vocab);
+    const size_t need = wipa_beam_bytes(B, G, max_candidates, dec_layout(cfg, B).ld_tok);
+    WIPA_REQUIRE(beam_bytes >= need, "%s: the beam buffer holds %zu bytes, this shape needs %zu (wipa_beam_bytes)", who, beam_bytes, need);
+    return WIPA_OK;
+}
+}  // namespace
+
+extern "C" int wipa_decoder_run_beam(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init, int eot,
+                                     const float* mask_first, const float* mask_always, int n_steps, int use_graph, const wipa_decode_rules* rules,
+                                     void* beam, size_t beam_bytes, int max_candidates, wipa_stream_t stream) {
+    if (!beam) return wipa_decoder_run_sample(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, n_steps, use_graph, rules, nullptr, stream);
+    RT_CALL(cfg_check(cfg));
+    RT_CALL(beam_servable("wipa_decoder_run_beam", cfg, B, nullptr, beam, beam_bytes, max_candidates));
+    static const EntryNames who = entry_names("wipa_decoder_run_beam");
+    StepCtx full{rules, nullptr, nullptr, n_init, eot, mask_first, mask_always, false, false, nullptr, 0, nullptr};
+    full.beam = beam;
+    full.beam_max_candidates = max_candidates;
+    return decoder_run(who, cfg, w, state, state_bytes, B, full, n_steps, use_graph, stream);
+}
+
+extern "C" int wipa_decoder_prefill_beam(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
+                                         int eot, const float* mask_first, const float* mask_always, int use_graph,
+                                         const wipa_decode_rules* rules, const void* sample, void* beam, size_t beam_bytes, int max_candidates,
+                                         wipa_stream_t stream) {
     RT_CALL(cfg_check(cfg));
     SplitScope split_scope(cfg);
     WIPA_REQUIRE(w && state && mask_first && mask_always && B > 0, "wipa_decoder_prefill: bad arguments");
-    const StepCtx ctx{rules, sample, nullptr, n_init, eot, mask_first, mask_always, false};
+    RT_CALL(beam_servable("wipa_decoder_prefill_beam", cfg, B, sample, beam, beam_bytes, max_candidates));
+    StepCtx ctx{rules, sample, nullptr, n_init, eot, mask_first, mask_always, false};
+    ctx.beam = beam;
+    ctx.beam_max_candidates = beam ? max_candidates : 0;
     static const EntryNames who = {"wipa_decoder_prefill", "wipa_decoder_prefill_rules", "wipa_decoder_prefill_sample", "wipa_decoder_prefill"};
     char* st = (char*)state;
     hipStream_t s = (hipStream_t)stream;

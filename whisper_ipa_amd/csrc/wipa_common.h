@@ -40,6 +40,14 @@ int wipa_step_tail_continuous(const float* logits, int64_t ldl, int B, int V, co
                               int emb_dtype, const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b,
                               void* y, int y_dtype, int D, float eps, wipa_stream_t stream);
 
+// the beam tail on written logits (beam.hip): beam_topk + beam_select.  tok_emb == NULL: the selection alone (wipa_beam_step); else a decode
+// step's last two launches, with the next step's input rows and the position advance
+int wipa_beam_tail(const char* who, const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
+                   int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int n_init, int eot, const wipa_decode_rules* rules,
+                   void* beam, int n_group, int max_candidates, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
+                   const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y, int y_dtype,
+                   int D, float eps, wipa_stream_t stream);
+
 #define WIPA_CHECK_HIP(expr)                                                        \
     do {                                                                            \
         hipError_t _e = (expr);                                                     \

@@ -28,6 +28,13 @@ clip is decoded as a GROUP of N candidate rows that share the clip's audio -- th
 (lo, hi + (k << 24)), so candidate 0 is the row's draw without ``best_of`` and a window's candidates do not depend on its neighbours.
 ``wipa_rank_groups`` picks, on the device, the candidate with the highest ``sum_logprobs / penalty(length)`` (first maximum) and the
 host reads the winners only.  ONE deviation from upstream: a candidate of length 0 scores -inf where upstream divides by zero.
+
+Beam search (``DecodingOptions.beam_size`` / ``patience`` / ``length_penalty`` at temperature 0; upstream's BeamSearchDecoder with
+MaximumLikelihoodRanker): every clip is decoded as a group of ``beam_size`` rows that share its audio, like best-of.  The step's tail
+(csrc/beam.hip) takes every row's ``beam_size + 1`` best continuations, keeps per clip the best ``beam_size`` that do not end and moves the
+ones that do into the clip's finished store (``round(beam_size * patience)`` sequences); the self-attention cache is never permuted --
+a beam reads its history through an ancestor table (csrc/attention.hip, decode_attn_kernel<.., BEAM>).  ``wipa_beam_finalize`` ranks on
+the device and the host reads one row per clip.  Not served with beams: prompts / prefixes, a temperature above 0, fp8 decoder tables.
 """
 from __future__ import annotations
 
@@ -129,6 +136,21 @@ class DecoderState:
     @property
     def sum_logprobs(self) -> torch.Tensor:
         return self._view(self.layout.sum_logprobs, self.B * 4, torch.float32)
+
+    @property
+    def not_done(self) -> torch.Tensor:
+        return self._view(self.layout.not_done, 4, torch.int32)
+
+    def beam_buffer(self, n_group: int, max_candidates: int) -> torch.Tensor:
+        """the caller-owned beam buffer of this state (include/wipa.h: wipa_beam_bytes).  Kept, and re-made only to grow: the step graph
+        is keyed on its address."""
+        need = int(_lib.lib().wipa_beam_bytes(self.B, n_group, max_candidates, self.layout.ld_tok))
+        buf = getattr(self, "_beam_buf", None)
+        if buf is None or buf.numel() < need:
+            stream().synchronize()  # nothing enqueued may still read the old one
+            with on_stream():
+                self._beam_buf = buf = torch.empty(need, dtype=torch.uint8, device=self.blob.device)
+        return buf
 
     @property
     def logits(self) -> torch.Tensor:
@@ -264,6 +286,29 @@ def _rank_groups(st: "DecoderState", n_group: int, sample_begin: int, n: int, eo
             length.cpu().numpy().astype(np.int64).reshape(clips, n_group))
 
 
+@dataclass(frozen=True)
+class Beams:
+    """what a beam decode needs besides n_group = beam_size: the size of a clip's finished store, round(beam_size * patience)"""
+    max_candidates: int
+
+
+def _beam_finalize(st: "DecoderState", buf: torch.Tensor, n_group: int, beams: Beams, sample_begin: int, n: int, eot: int,
+                   length_penalty: Optional[float], s):
+    """wipa_beam_finalize on the state's rows -> host (winner tokens [clips, sample_begin + n + 1] int64, eot behind the winner's last
+    token; winner sums [clips]; winner lengths [clips]): clips x columns come back"""
+    clips = st.B // n_group
+    dev = st.blob.device
+    pen = torch.from_numpy(length_penalty_table(n, length_penalty)).to(dev)
+    width = sample_begin + n + 1
+    best = torch.empty(clips, width, dtype=torch.int32, device=dev)
+    best_sum = torch.empty(clips, dtype=torch.float32, device=dev)
+    best_len = torch.empty(clips, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().wipa_beam_finalize(ptr(buf), ptr(st.tokens), st.layout.ld_tok, st.B, n_group, beams.max_candidates, sample_begin, n, eot,
+                                             ptr(st.sum_logprobs), ptr(pen), ptr(best), width, ptr(best_sum), ptr(best_len), sptr(s)),
+               "wipa_beam_finalize")
+    return best.cpu().numpy().astype(np.int64), best_sum.cpu().numpy().copy(), best_len.cpu().numpy().astype(np.int64)
+
+
 def _mask(model, ids: Sequence[int]) -> torch.Tensor:
     cache = model.__dict__.setdefault("_mask_cache", {})
     key = tuple(sorted(set(int(i) for i in ids)))
@@ -309,12 +354,15 @@ def timestamp_rules(tok: Tokenizer, max_initial_timestamp: Optional[float] = 1.0
     return _lib.DecodeRules(int(tok.timestamp_begin), int(tok.no_timestamps), index)
 
 
-def _dec_run(L, pk, st, B, n_init, eot, m_first, m_always, n, use_graph, rules, s, sample_rec=None, starts=None):
+def _dec_run(L, pk, st, B, n_init, eot, m_first, m_always, n, use_graph, rules, s, sample_rec=None, starts=None, beam=None):
     """wipa_decoder_run, or wipa_decoder_run_rules when the greedy update carries the timestamp rules; wipa_decoder_run_sample
     (rules or not) when ``sample_rec``, the state's device sampling record, is given; wipa_decoder_run_ragged when ``starts``, the
     state's device array of first columns, is given (``n_init`` is then the prompt width P)"""
     args = (C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, n_init, eot, ptr(m_first), ptr(m_always), n, int(use_graph))
-    if starts is not None:
+    if beam is not None:  # (the state's beam buffer, max_candidates): wipa_decoder_run_beam
+        _lib.check(L.wipa_decoder_run_beam(*args, C.byref(rules) if rules is not None else None, ptr(beam[0]), beam[0].numel(), beam[1], sptr(s)),
+                   "wipa_decoder_run_beam")
+    elif starts is not None:
         _lib.check(L.wipa_decoder_run_ragged(*args, C.byref(rules) if rules is not None else None,
                                              ptr(sample_rec) if sample_rec is not None else None, ptr(starts), sptr(s)), "wipa_decoder_run_ragged")
     elif sample_rec is not None:
@@ -326,9 +374,12 @@ def _dec_run(L, pk, st, B, n_init, eot, m_first, m_always, n, use_graph, rules, 
         _lib.check(L.wipa_decoder_run_rules(*args, C.byref(rules), sptr(s)), "wipa_decoder_run_rules")
 
 
-def _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s, sample_rec=None):
+def _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s, sample_rec=None, beam=None):
     args = (C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, n_init, eot, ptr(m_first), ptr(m_always), int(use_graph))
-    if sample_rec is not None:
+    if beam is not None:
+        _lib.check(L.wipa_decoder_prefill_beam(*args, C.byref(rules) if rules is not None else None, None, ptr(beam[0]), beam[0].numel(), beam[1],
+                                               sptr(s)), "wipa_decoder_prefill_beam")
+    elif sample_rec is not None:
         _lib.check(L.wipa_decoder_prefill_sample(*args, C.byref(rules) if rules is not None else None, ptr(sample_rec), sptr(s)),
                    "wipa_decoder_prefill_sample")
     elif rules is None:
@@ -404,11 +455,14 @@ def _for_candidates(sample: Optional[Sampling], clips: int, n_group: int) -> Opt
 
 def _decode_loop(model, audio_features: torch.Tensor, P: int, max_new_tokens: int, begin, run_prompt, suppress_always, suppress_first,
                  eot: int, stop_on_eot: bool, use_graph: bool, check_every: int, rules, sample: Optional[Sampling], n_group: int, rank: bool,
-                 length_penalty: Optional[float], sot_back: Optional[int] = None) -> GreedyTokens:
+                 length_penalty: Optional[float], sot_back: Optional[int] = None, beams: Optional[Beams] = None) -> GreedyTokens:
     """The decode loop of ``greedy_decode_tokens`` and ``ragged_decode_tokens``, for a prompt of ``P`` columns and ``max_new_tokens``
     already clamped to n_text_ctx - P.  The caller supplies how to begin -- ``begin(L, pk, st, B, s)`` returns the state's device array
     of first columns, or None -- and how the batched prompt pass is run: ``run_prompt(L, pk, st, B, m_first, m_always, rec, starts, s)``
-    returns the logits of the <|startoftranscript|> column, or None.  ``sample`` is per ROW here (``_for_candidates``)."""
+    returns the logits of the <|startoftranscript|> column, or None.  ``sample`` is per ROW here (``_for_candidates``).
+    ``beams``: the rows are clips x ``n_group`` BEAMS -- the state's beam buffer is begun behind the tokens, prompt pass and steps are the
+    beam entry points (``run_prompt`` takes the buffer as ``beam=``), the loop stops when no clip is still collecting (the state's
+    ``not_done``) and the winners of wipa_beam_finalize come back."""
     L = _lib.lib()
     B = audio_features.shape[0] * n_group
     pk = _grouped(_packed_for(model, B, max_new_tokens), n_group)
@@ -421,8 +475,13 @@ def _decode_loop(model, audio_features: torch.Tensor, P: int, max_new_tokens: in
     with on_stream() as s:
         feats, starts = _open(model, L, pk, st, audio_features, B, s, begin)
         rec = st.sample_record(sample) if sample is not None else None
+        beam = None
+        if beams is not None:
+            buf = st.beam_buffer(n_group, beams.max_candidates)
+            _lib.check(L.wipa_beam_begin(ptr(buf), buf.numel(), B, n_group, beams.max_candidates, st.layout.ld_tok, sptr(s)), "wipa_beam_begin")
+            beam = (buf, beams.max_candidates)
         if _use_prefill(P, total):  # the whole prompt and the first new token in one batched pass
-            sot_logits = run_prompt(L, pk, st, B, m_first, m_always, rec, starts, s)
+            sot_logits = run_prompt(L, pk, st, B, m_first, m_always, rec, starts, s, **({"beam": beam} if beam is not None else {}))
             done_steps = P
         elif sot_back is not None:  # the steps up to the <|startoftranscript|> column: its logits are those of the call's last step
             n = P - sot_back + 1
@@ -433,14 +492,21 @@ def _decode_loop(model, audio_features: torch.Tensor, P: int, max_new_tokens: in
             n = min(check_every if stop_on_eot else total, total - done_steps)
             if done_steps < P - 1:  # the rest of the prompt walk rides with the first generated columns
                 n = min(total - done_steps, n + (P - 1 - done_steps))
-            _dec_run(L, pk, st, B, P, eot, m_first, m_always, n, use_graph, rules, s, rec, starts)
+            _dec_run(L, pk, st, B, P, eot, m_first, m_always, n, use_graph, rules, s, rec, starts, beam)
             done_steps += n
             if stop_on_eot and done_steps >= P:
+                if beam is not None:  # live beams never hold EOT: the step's tail counts the clips whose finished store is not full
+                    if int(st.not_done.cpu()) == 0:  # synchronises the library stream
+                        break
+                    continue
                 last = st.tokens[:, done_steps].cpu()  # synchronises the library stream
                 if bool((last == eot).all()):
                     break
         winner = lengths = None
-        if rank and n_group > 1:  # the winners only come back: clips x columns
+        if beam is not None:  # fill-up and ranking on the device; the winners come back: clips x columns
+            toks, slp, best_len = _beam_finalize(st, beam[0], n_group, beams, P, done_steps - (P - 1), eot, length_penalty, s)
+            lengths = best_len.reshape(-1, 1)
+        elif rank and n_group > 1:  # the winners only come back: clips x columns
             toks, slp, winner, lengths = _rank_groups(st, n_group, P, done_steps - (P - 1), eot, length_penalty, s)
         else:
             toks = st.tokens[:, : done_steps + 1].cpu().numpy().astype(np.int64)  # synchronises: the host arrays of begin are consumed
@@ -463,25 +529,30 @@ def greedy_decode_tokens(model, audio_features: torch.Tensor, initial_tokens: Se
                          suppress_first: Sequence[int], eot: int, max_new_tokens: Optional[int] = None,
                          stop_on_eot: bool = True, use_graph: bool = True, check_every: int = 8, rules=None,
                          sample: Optional[Sampling] = None, n_group: int = 1, rank: bool = False,
-                         length_penalty: Optional[float] = None) -> GreedyTokens:
+                         length_penalty: Optional[float] = None, beams: Optional[Beams] = None) -> GreedyTokens:
     """DecodingTask._main_loop (see module docstring): temperature 0, or a Categorical draw per step with ``sample``.
     ``audio_features`` [B, 1500, d] in the model dtype.  ``rules`` (``timestamp_rules``): ApplyTimestampRules in every greedy
     update, on the device; ``initial_tokens`` is then the prompt without <|notimestamps|>.
     ``n_group`` > 1 (upstream's n_group = best_of): every clip is decoded as ``n_group`` candidate rows, clip-major, that share the
     clip's features in the decode state; ``sample.streams`` are per CLIP and candidate k draws from ``candidate_streams``' stream k.
     The result holds all clips x n_group rows -- or, with ``rank``, the winners of wipa_rank_groups only (one row per clip, plus
-    ``winner`` and ``lengths``), read back as clips x columns."""
-    sample = _for_candidates(sample, audio_features.shape[0], n_group)
+    ``winner`` and ``lengths``), read back as clips x columns.
+    ``beams``: the ``n_group`` rows of a clip are BEAMS at temperature 0 (``sample`` must be None; ``n_group`` 1 is a beam of one).  The
+    result holds one row per clip, the winner of wipa_beam_finalize with eot behind its last token, and ``lengths`` [clips, 1]."""
+    if beams is not None and sample is not None:
+        raise ValueError("beams run at temperature 0: sample must be None")
+    if beams is None:
+        sample = _for_candidates(sample, audio_features.shape[0], n_group)
     n_init = len(initial_tokens)
     if max_new_tokens is None:
         max_new_tokens = model.dims.n_text_ctx // 2
     max_new_tokens = min(max_new_tokens, model.dims.n_text_ctx - n_init)
 
-    def run_prompt(L, pk, st, B, m_first, m_always, rec, starts, s):
-        _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s, rec)
+    def run_prompt(L, pk, st, B, m_first, m_always, rec, starts, s, beam=None):
+        _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s, rec, beam)
 
     return _decode_loop(model, audio_features, n_init, max_new_tokens, _begin_with(initial_tokens), run_prompt, suppress_always, suppress_first,
-                        eot, stop_on_eot, use_graph, check_every, rules, sample, n_group, rank, length_penalty)
+                        eot, stop_on_eot, use_graph, check_every, rules, sample, n_group, rank, length_penalty, beams=beams)
 
 
 # ---------------------------------------------------------------- prompt conditioning: per-row prompts
@@ -723,6 +794,37 @@ def best_of_group(options: DecodingOptions) -> int:
     return n
 
 
+def beam_group(options: DecodingOptions, model) -> Optional[tuple]:
+    """upstream's DecodingTask._verify_options for the beam options and what they ask for: None without ``beam_size``, else
+    ``(beam_size, max_candidates)`` with ``max_candidates = round(beam_size * patience)`` (``patience`` None is 1.0).  ``beam_size`` is an
+    int in 1..16 (1: the beam path with one row per clip), ``patience`` is above 0 with 1 <= max_candidates <= 64, ``length_penalty`` lies
+    in 0..1 (upstream's ValueError).  Refused by name: a model that is not a loaded Whisper on bf16 / f32 decoder tables, a temperature
+    above 0 (upstream drops the beams there; ``transcribe`` does that itself), prompts and prefixes."""
+    if options.beam_size is None:
+        return None
+    n = options.beam_size
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= 16:
+        raise ValueError(f"beam_size must be an integer between 1 and 16, got {n!r}")
+    n = int(n)
+    if options.patience is not None and not options.patience > 0:
+        raise ValueError("patience should be a positive number")
+    max_candidates = round(n * (1.0 if options.patience is None else float(options.patience)))
+    if not 1 <= max_candidates <= 64:
+        raise ValueError(f"round(beam_size * patience) = {max_candidates} must lie between 1 and 64")
+    if options.length_penalty is not None and not (0 <= options.length_penalty <= 1):
+        raise ValueError("length_penalty (alpha) should be a value between 0 and 1")
+    if model is None or not hasattr(model, "packed") or not hasattr(model, "dims"):
+        raise NotImplementedError("beam_size is served by decode() on a loaded Whisper model only (bf16 / f32 decoder tables)")
+    if getattr(model, "_fp8", None):
+        raise NotImplementedError("beam_size is not implemented for an fp8-quantised model: the beam step runs on bf16 / f32 decoder tables")
+    if options.temperature != 0.0:
+        raise NotImplementedError("beam_size at a temperature above 0 is not implemented: beams run at temperature 0 (upstream's fallback "
+                                  "drops beam_size above 0; transcribe() does the same)")
+    if (options.prompt is not None and len(options.prompt)) or (options.prefix is not None and len(options.prefix)) or options.prompts is not None:
+        raise NotImplementedError("beam_size with prompt / prefix / prompts is not implemented: beams run on rows without prompts")
+    return n, int(max_candidates)
+
+
 MAX_DECODE_ROWS = 65535  # rows of one decode state: the step's kernels put the row on a 16-bit grid axis
 
 
@@ -753,7 +855,10 @@ def decode(model, mel: torch.Tensor, options: DecodingOptions = DecodingOptions(
     prompts = resolve_prompts(options, n_rows)
     prefix = options.prefix if (options.prefix is not None and len(options.prefix)) else None
     n_group = best_of_group(options)  # decode() serves best_of itself too: candidate groups that share one encoder output
-    _refuse_unsupported(replace(options, prompt=None, prefix=None, prompts=None, best_of=None))
+    beam = beam_group(options, model)  # ... and beams, before it touches the features: groups of beam_size rows
+    if beam is not None:
+        n_group = beam[0]
+    _refuse_unsupported(replace(options, prompt=None, prefix=None, prompts=None, best_of=None, beam_size=None))
     if (prompts is not None or prefix is not None) and getattr(model, "_fp8", None):
         raise NotImplementedError("prompt / prefix conditioning is not implemented for an fp8-quantised model: the ragged decode step "
                                   "runs on bf16 / f32 decoder tables")
@@ -805,12 +910,14 @@ def decode(model, mel: torch.Tensor, options: DecodingOptions = DecodingOptions(
     results: List[Optional[DecodingResult]] = [None] * B
     # best_of: a clip's candidates ride in ONE state and share its audio there; the ranker leaves one row per clip
     group_kw = dict(n_group=n_group, rank=True, length_penalty=options.length_penalty) if n_group > 1 else {}
+    if beam is not None:  # the beams of a clip ride in one state too; wipa_beam_finalize leaves one row per clip
+        group_kw = dict(n_group=n_group, length_penalty=options.length_penalty, beams=Beams(beam[1]))
     per_call = max(1, MAX_DECODE_ROWS // n_group)  # more rows than a state holds: chunks of whole groups
     for lang in sorted(set(languages)):
         lang_rows = [i for i, l in enumerate(languages) if l == lang]
         init = list(initial)
         init[1] = tok.to_language_token(lang)
-        for rows in ([lang_rows] if n_group == 1 else [lang_rows[c:c + per_call] for c in range(0, len(lang_rows), per_call)]):
+        for rows in ([lang_rows] if n_group == 1 and beam is None else [lang_rows[c:c + per_call] for c in range(0, len(lang_rows), per_call)]):
             sub = feats[rows] if len(rows) != B else feats
             sample = None if streams is None else Sampling(int(options.seed), float(options.temperature), [streams[i] for i in rows],
                                                            int(options.sample_attempt))

@@ -103,7 +103,7 @@ def split_segments(tokens: Sequence[int], tb: int, time_offset: float, segment_s
 
 
 def _refuse(condition_on_previous_text, initial_prompt, word_timestamps, clip_timestamps, hallucination_silence_threshold, temperature,
-            decode_options, can_align: bool = False, can_retry: bool = True) -> None:
+            decode_options, can_align: bool = False, can_retry: bool = True, can_beam: bool = False) -> None:
     if word_timestamps and not can_align:
         raise NotImplementedError("word_timestamps=True is not implemented without a model: a custom decode_fn needs an align_fn")
     if clip_timestamps not in (None, "0", [0], (0,)):
@@ -113,9 +113,19 @@ def _refuse(condition_on_previous_text, initial_prompt, word_timestamps, clip_ti
     temps = (temperature,) if isinstance(temperature, (int, float)) else tuple(temperature)
     if not temps or float(temps[0]) != 0.0:
         raise NotImplementedError("temperature must be 0.0 or a tuple that starts with 0.0: only temperature 0 is run")
-    for k in ("beam_size", "prompt", "prefix"):
+    for k in ("prompt", "prefix"):
         if decode_options.get(k) is not None:
             raise NotImplementedError(f"{k} is not implemented")
+    if decode_options.get("beam_size") is not None:
+        # beams are a capability of the decoder: the package's own has it, a custom decode_fn says so with a ``beams`` attribute
+        if not can_beam:
+            raise NotImplementedError("beam_size is not implemented for a custom decode_fn without a beams attribute: the temperature-0 "
+                                      "decode of every window runs the beams (decode_fn.beams = True)")
+        if condition_on_previous_text or initial_prompt is not None:
+            raise NotImplementedError("beam_size with condition_on_previous_text=True / initial_prompt is not implemented: beams run on "
+                                      "rows without prompts")
+        if word_timestamps:
+            raise NotImplementedError("beam_size with word_timestamps=True is not implemented")
     if decode_options.get("best_of") is not None and not can_retry:
         raise NotImplementedError("best_of is not implemented for a custom decode_fn without a fallback_fn: the candidates are drawn by "
                                   "the retries (fallback_fn(..., best_of=N))")
@@ -177,9 +187,11 @@ def _model_decoder(model, decode_options: dict) -> Callable:
         candidates per row, of which decode() keeps the best"""
         out = [None] * len(results)
         feats = torch.stack([r.audio_features for r in results])
+        # upstream's decode_with_fallback: above temperature 0 the beams are dropped (beam_size, patience), best_of takes their place
+        sampling_options = {k: v for k, v in decode_options.items() if k not in ("beam_size", "patience")}
         for lang in sorted(set(languages)):
             rows = [i for i, l in enumerate(languages) if l == lang]
-            opts = DecodingOptions(**with_prompts({**decode_options, "language": lang, "without_timestamps": False,
+            opts = DecodingOptions(**with_prompts({**sampling_options, "language": lang, "without_timestamps": False,
                                                    "temperature": float(temperature), "seed": int(seed),
                                                    "sample_streams": [streams[i] for i in rows], "sample_attempt": int(attempt),
                                                    **({"best_of": int(best_of)} if best_of is not None else {})}, prompts, rows))
@@ -525,7 +537,11 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
     produced them, and neither ``needs_fallback`` nor the warning appears where a retry ran.  ``fallback_fn(results, languages,
     temperature=, attempt=, streams=, seed=)`` -> new results for those rows replaces the model's retry; with a custom ``decode_fn``
     and no ``fallback_fn`` a seed changes nothing.  ``streams[j]`` = (seek in mel frames, file index), ``attempt`` = index in the
-    schedule.  ``best_of=N``: every retry decodes N candidates per window and keeps the best (``fallback_fn`` then gets ``best_of=N``).  ``word_timestamps=True``: every segment gains ``"words"``: [{"word", "start", "end", "probability"}]
+    schedule.  ``beam_size=N`` (with ``patience=``, ``length_penalty=``; rounds schedule): the temperature-0 decode of every window is a
+    beam search (decoding.py); the retries above 0 drop ``beam_size`` / ``patience``, as upstream's ``decode_with_fallback`` does, and go on
+    as without beams, with ``best_of`` if given.  A custom ``decode_fn`` serves beams when it has a true ``beams`` attribute.  Refused by
+    name with beams: ``schedule="continuous"``, ``condition_on_previous_text`` / ``initial_prompt``, ``word_timestamps``.
+    ``best_of=N``: every retry decodes N candidates per window and keeps the best (``fallback_fn`` then gets ``best_of=N``).  ``word_timestamps=True``: every segment gains ``"words"``: [{"word", "start", "end", "probability"}]
     (timing.py); ``align_fn(results, text_tokens, num_frames, languages)`` -> one list of WordTiming per window replaces the
     model's alignment (``results``: the windows' decode results, ``text_tokens[j]`` the ids below EOT of window j's segments,
     ``num_frames[j]`` its content in mel frames); it is required with a custom ``decode_fn``.
@@ -547,7 +563,8 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
     of at most 196 gives both the same."""
     _refuse(condition_on_previous_text, initial_prompt, word_timestamps, clip_timestamps, hallucination_silence_threshold, temperature,
             decode_options, can_align=align_fn is not None or (model is not None and decode_fn is None),
-            can_retry=decode_fn is None or fallback_fn is not None)
+            can_retry=decode_fn is None or fallback_fn is not None,
+            can_beam=(decode_fn is None and model is not None) or bool(getattr(decode_fn, "beams", False)))
     _refuse_conditioning(condition_on_previous_text, initial_prompt, model, decode_fn, fallback_fn)
     conditioning = bool(condition_on_previous_text) or initial_prompt is not None
     if prompt_budget is not None and (int(prompt_budget) < 0 or not conditioning):
@@ -578,6 +595,9 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
     best_of = decode_options.pop("best_of", None)
     if schedule not in ("rounds", "continuous"):
         raise ValueError(f"transcribe: schedule is 'rounds' or 'continuous', got {schedule!r}")
+    if schedule == "continuous" and decode_options.get("beam_size") is not None:
+        raise NotImplementedError("transcribe(schedule='continuous'): beam_size is not implemented (the slots of the continuous schedule "
+                                  "are single rows); use schedule='rounds'")
     if schedule == "continuous":
         _refuse_continuous(model, seed, word_timestamps, condition_on_previous_text, initial_prompt, best_of, decode_fn, stream_fn)
     elif decode_fn is None:
