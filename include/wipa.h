@@ -95,6 +95,21 @@ int wipa_logmel(const float* audio, int batch, int n_mels, const void* tables, v
                 void* workspace, size_t workspace_bytes, wipa_stream_t s);
 /* [B,3000,n_mels] f32 (any producer) -> padded mel [B*3002 + 4, n_mels] T for the encoder. */
 int wipa_mel_pad_cast(const float* mel, int batch, int n_mels, void* mel_padded, int dtype, wipa_stream_t s);
+/* Short audio context (wipa_model_cfg.n_audio_ctx = T < 1500): the encoder consumes the first n_frames = 2T frames in the layout
+ *   [B*(n_frames + 2) + 4, n_mels] T: frame t of clip b at row b*(n_frames + 2) + t + 1, rows b*(n_frames + 2) and
+ *   b*(n_frames + 2) + n_frames + 1 and the 4 tail rows zero.
+ * The 3002-row layout cannot be read in place: its row n_frames + 1 is the real frame n_frames, where conv1 at frame n_frames - 1
+ * must see its zero padding.  The front end is unchanged -- 30 s of audio, the clamp at the clip's maximum - 8 taken over all 3000
+ * frames -- so rows 1..n_frames carry the bits wipa_logmel writes there.  1 <= n_frames <= 3000; n_frames = 3000 is the layout above.
+ * wipa_logmel_frames: wipa_logmel into the workspace (wipa_logmel_frames_workspace_bytes), then one copy of the rows.
+ * wipa_mel_pad_cast_frames: mel f32, frame t of clip b at mel + b*clip_stride + t*n_mels (clip_stride in elements, >= n_frames *
+ * n_mels: 3000 * n_mels takes the first n_frames of a full mel without a copy). */
+#define WIPA_MEL_ROWS_FRAMES(B, n_frames) ((int64_t)(B) * ((n_frames) + 2) + 4)
+size_t wipa_logmel_frames_workspace_bytes(int batch, int n_mels, int n_frames);
+int wipa_logmel_frames(const float* audio, int batch, int n_mels, const void* tables, void* mel, int mel_dtype, int n_frames,
+                       void* workspace, size_t workspace_bytes, wipa_stream_t s);
+int wipa_mel_pad_cast_frames(const float* mel, int64_t clip_stride, int batch, int n_mels, int n_frames, void* mel_padded, int dtype,
+                             wipa_stream_t s);
 
 /* ------------------------------------------------------------------ K4 GEMM
  * C = epilogue(A * W^T): every nn.Linear / Conv1d of mlx_whisper.whisper
@@ -657,6 +672,10 @@ int wipa_build_token_batch(const int32_t* ids, const int32_t* row_lens, int n_ro
 typedef struct wipa_model_cfg {
     int32_t n_mels, n_audio_ctx, n_audio_state, n_audio_head, n_audio_layer;
     int32_t n_vocab, n_text_ctx, n_text_state, n_text_head, n_text_layer;
+    /* n_audio_ctx = T, 1..1500: the audio positions the model RUNS on (whisper.cpp's --audio-ctx).  The encoder reads a padded mel
+     * of 2T frames (WIPA_MEL_ROWS_FRAMES(B, 2T) rows; 3002 per clip at T = 1500), adds the first T rows of its positional table and
+     * writes features [B, T, d]; every decoder entry point takes features [clips, T, d] and sizes its cross-attention state, its
+     * workspaces and the alignment matrix for T.  Outside 1..1500: WIPA_ERR_ARG (size queries return 0). */
     int32_t dtype; /* WIPA_F32 or WIPA_BF16: matrices, activations, KV caches */
     int32_t f32_split; /* dtype == WIPA_F32 only: 1 lets the encoder / teacher-forced GEMMs and the encoder flash attention
                         * use split-bf16 products (see wipa_gemm_desc.f32_split); 0 = exact f32 products (default) */

@@ -40,16 +40,20 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from evaluate_ipa import SCORING_MODES, evaluate_batch  # noqa: E402
 from whisper_ipa_amd import parallel  # noqa: E402
-from whisper_ipa_amd.audio import PcmBatch, load_audio, pad_or_trim, read_pcm  # noqa: E402
+from whisper_ipa_amd.audio import PcmBatch, count_longer_than_audio_ctx, load_audio, pad_or_trim, read_pcm  # noqa: E402
 from whisper_ipa_amd.decoding import DecodingOptions  # noqa: E402
-from whisper_ipa_amd.load_models import load_model, overlay_decoder_weights  # noqa: E402
+from whisper_ipa_amd.load_models import load_model, overlay_decoder_weights, resolve_audio_ctx  # noqa: E402
 from whisper_ipa_amd.pipeline import transcribe_batches  # noqa: E402
 
 
-def load_checkpoint_model(checkpoint_path: str, base_model: str = "mlx-community/whisper-small-mlx"):
-    """reference :20-79: base architecture in fp32 + the checkpoint's ``decoder.*`` tensors."""
+def load_checkpoint_model(checkpoint_path: str, base_model: str = "mlx-community/whisper-small-mlx", audio_ctx: Optional[int] = None):
+    """reference :20-79: base architecture in fp32 + the checkpoint's ``decoder.*`` tensors.  ``audio_ctx``: --audio-ctx; without
+    one the value the checkpoint's training_config.json recorded is used, and a different one is used with a warning."""
     print(f"Loading base model architecture: {base_model}")
-    model = load_model(base_model)
+    audio_ctx, warning = resolve_audio_ctx(audio_ctx, checkpoint_path)
+    if warning:
+        print(warning)
+    model = load_model(base_model, audio_ctx=audio_ctx)
     model.set_dtype(torch.float32)
     try:
         n = overlay_decoder_weights(model, checkpoint_path)
@@ -64,23 +68,34 @@ def load_checkpoint_model(checkpoint_path: str, base_model: str = "mlx-community
 INGEST_MODES = ("device", "host")
 
 
-def load_clips(audio_paths: List[str], ingest: str = "device"):
+def load_clips(audio_paths: List[str], ingest: str = "device", audio_ctx: Optional[int] = None):
     """host side of reference :184-189 for a list of clips: (batch or None, positions of the readable clips); a clip that cannot
     be read is reported and yields "" (:202-204).  ``ingest="device"``: the batch is a ``PcmBatch`` -- the files' PCM bytes packed
     for one copy; conversion, resampling and the 30 s pad run on the GPU (whisper_ipa_amd.audio.load_audio_batch).
-    ``ingest="host"``: audio [n_ok, 480000] f32 from ``pad_or_trim(load_audio(path))`` in numpy, as before."""
+    ``ingest="host"``: audio [n_ok, 480000] f32 from ``pad_or_trim(load_audio(path))`` in numpy, as before.
+    ``audio_ctx`` (the model's): the clips longer than audio_ctx * 20 ms are counted and reported on one warning line."""
     if ingest not in INGEST_MODES:
         raise ValueError(f"ingest must be one of {INGEST_MODES}, got {ingest!r}")
-    clips, slots = [], []
+    clips, slots, over = [], [], 0
     for i, path in enumerate(audio_paths):
         try:
-            clips.append(read_pcm(path) if ingest == "device" else np.asarray(pad_or_trim(load_audio(path)), dtype=np.float32))
+            if ingest == "device":
+                clips.append(read_pcm(path))
+            else:
+                a = load_audio(path)
+                over += count_longer_than_audio_ctx([len(a)], audio_ctx)
+                clips.append(np.asarray(pad_or_trim(a), dtype=np.float32))
             slots.append(i)
         except Exception as e:
             print(f"\nError transcribing {path}: {e}")
     if not clips:
         return None, slots
-    return (PcmBatch(clips) if ingest == "device" else torch.from_numpy(np.stack(clips))), slots
+    batch = PcmBatch(clips) if ingest == "device" else torch.from_numpy(np.stack(clips))
+    if ingest == "device":
+        over = count_longer_than_audio_ctx(batch.sample_counts(), audio_ctx)
+    if over:
+        print(f"\nWARNING: {over} of {len(clips)} clips are longer than audio_ctx {audio_ctx} ({audio_ctx * 0.02:.2f} s) and are cut")
+    return batch, slots
 
 
 def transcribe_clips(model, audio_paths: List[str], options: DecodingOptions, batch_size: int = 64,
@@ -94,7 +109,7 @@ def transcribe_clips(model, audio_paths: List[str], options: DecodingOptions, ba
 
     def batches():
         for b in range(0, len(audio_paths), batch_size):
-            audio, slots = load_clips(audio_paths[b:b + batch_size], ingest)
+            audio, slots = load_clips(audio_paths[b:b + batch_size], ingest, audio_ctx=getattr(model, "audio_ctx", None))
             if audio is None:
                 continue
             metas.append((b, slots))
@@ -123,7 +138,7 @@ def transcribe_clips_continuous(model, audio_paths: List[str], options: Decoding
     texts = [""] * len(audio_paths)
     mels, where = [], []
     for b in range(0, len(audio_paths), slots):
-        audio, ok = load_clips(audio_paths[b:b + slots], ingest)
+        audio, ok = load_clips(audio_paths[b:b + slots], ingest, audio_ctx=getattr(model, "audio_ctx", None))
         if audio is None:
             continue
         audio = load_audio_batch(audio) if ingest == "device" else audio.to(model.device)
@@ -188,7 +203,8 @@ def evaluate_model(model_path: str, test_data_path: str, num_samples: Optional[i
                    is_checkpoint: bool = False, n_mels: int = 80, base_model: str = "mlx-community/whisper-small-mlx",
                    batch_size: int = 64, passes_in_flight: int = 4, ingest: str = "device", scoring: str = "device",
                    base_decode: str = "decode", seed: Optional[int] = None, condition_on_previous_text: bool = False,
-                   initial_prompt: Optional[str] = None, decode: str = "lockstep", beams: Optional[dict] = None) -> Dict:
+                   initial_prompt: Optional[str] = None, decode: str = "lockstep", beams: Optional[dict] = None,
+                   audio_ctx: Optional[int] = None) -> Dict:
     if decode not in DECODE_MODES:
         raise ValueError(f"decode must be one of {DECODE_MODES}, got {decode!r}")
     rank, world_size = parallel.world()
@@ -207,10 +223,14 @@ def evaluate_model(model_path: str, test_data_path: str, num_samples: Optional[i
     say(f"\nModel: {model_path}")
     if is_checkpoint:
         say("\nLoading checkpoint...")
-        model = load_checkpoint_model(model_path, base_model=base_model)
+        model = load_checkpoint_model(model_path, base_model=base_model, audio_ctx=audio_ctx)
     else:
-        model = load_model(model_path)
+        model = load_model(model_path, audio_ctx=audio_ctx)
         model.set_dtype(torch.float32)
+    if model.audio_ctx is not None:
+        say(f"audio_ctx {model.audio_ctx}: the model runs on {model.audio_ctx * 0.02:.2f} s of context")
+        if base_decode == "transcribe" and not is_checkpoint:
+            raise SystemExit("--base-decode transcribe is not implemented with --audio-ctx (transcribe() assumes 30 s windows)")
     if model.dims.n_mels != n_mels:
         say(f"NOTE: --n-mels {n_mels} does not match the model ({model.dims.n_mels}); using the model's")
         n_mels = model.dims.n_mels
@@ -331,6 +351,10 @@ def main(argv=None) -> Dict:
     ap.add_argument("--length-penalty", type=float, default=None,
                     help="with --beam-size (or best-of retries): rank by sum_logprobs / ((5 + length) / 6) ** this instead of by length")
     ap.add_argument("--results-json", type=str, default=None, help="also write both result dicts here (rank 0)")
+    ap.add_argument("--audio-ctx", type=int, default=None,
+                    help="run both models on their first N audio positions of 20 ms (default: what the checkpoint's training_config.json "
+                         "records, else all 1500).  A value other than the recorded one is used with a warning; clips longer than "
+                         "N * 20 ms are cut and counted on a warning line")
     ap.add_argument("--allow-byte-fallback", action="store_true",
                     help="run without the Whisper vocabulary (WIPA_TIKTOKEN unset): hypotheses render ids >= 256 as <|idN|>; "
                          "synthetic weights only")
@@ -351,16 +375,21 @@ def main(argv=None) -> Dict:
     beams = {k: v for k, v in (("beam_size", args.beam_size), ("patience", args.patience), ("length_penalty", args.length_penalty)) if v is not None}
     if beams and args.base_decode != "transcribe":
         ap.error("--beam-size / --patience / --length-penalty go with --base-decode transcribe")
+    # both legs at ONE context: the requested one, else the one the checkpoint was trained at
+    audio_ctx, warning = resolve_audio_ctx(args.audio_ctx, args.checkpoint)
+    if warning and rank == 0:
+        print(warning)
     if not args.skip_base:
         base_results = evaluate_model(args.base_model, args.test_data, num_samples, model_name="Base Whisper Model",
                                       is_checkpoint=False, n_mels=args.n_mels, base_model=args.base_model, batch_size=args.batch_size,
                                       passes_in_flight=args.passes_in_flight, ingest=args.ingest, scoring=args.scoring,
                                       base_decode=args.base_decode, seed=args.seed,
                                       condition_on_previous_text=args.condition_on_previous_text, initial_prompt=args.initial_prompt,
-                                      decode=args.decode, beams=beams)
+                                      decode=args.decode, beams=beams, audio_ctx=audio_ctx)
     trained_results = evaluate_model(args.checkpoint, args.test_data, num_samples, model_name="Trained Checkpoint",
                                      is_checkpoint=True, n_mels=args.n_mels, base_model=args.base_model, batch_size=args.batch_size,
-                                     passes_in_flight=args.passes_in_flight, ingest=args.ingest, scoring=args.scoring, decode=args.decode)
+                                     passes_in_flight=args.passes_in_flight, ingest=args.ingest, scoring=args.scoring, decode=args.decode,
+                                     audio_ctx=audio_ctx)
     if rank == 0:
         if base_results:
             compare_models(base_results, trained_results)

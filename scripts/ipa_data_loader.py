@@ -25,7 +25,8 @@ from whisper_ipa_amd.audio import load_audio, load_audio_batch, log_mel_spectrog
 class IPADataset:
     """audio + IPA transcription pairs (reference :17-131)."""
 
-    def __init__(self, json_path: str, tokenizer, n_mels: int = 80, audio_root: str = ""):
+    def __init__(self, json_path: str, tokenizer, n_mels: int = 80, audio_root: str = "", audio_ctx: Optional[int] = None):
+        self.audio_ctx = audio_ctx  # the positions the model runs on (Whisper.audio_ctx): get_batch counts the clips it cuts
         self.json_path = Path(json_path)
         self.tokenizer = tokenizer
         self.n_mels = n_mels
@@ -80,8 +81,10 @@ class IPADataset:
         entries = [self.data[i] for i in indices]
         paths = [os.path.join(self.audio_root, e["audio_path"]) if self.audio_root else e["audio_path"] for e, f in zip(entries, need) if f]
         mel = None
+        report = {"longer_than_audio_ctx": 0}
         if paths:
-            audio = load_audio_batch(paths)  # load_audio + pad_or_trim (:44,80) of the flagged clips: one copy, one launch
+            # load_audio + pad_or_trim (:44,80) of the flagged clips: one copy, one launch
+            audio = load_audio_batch(paths, audio_ctx=self.audio_ctx, report=report)
             mel = log_mel_spectrogram(audio, n_mels=self.n_mels)  # [n_flagged, 3000, n_mels] on the GPU, one launch
         texts = [e["ipa_transcription"] for e in entries]
         tokens = self.tokenize_batch(texts)
@@ -90,15 +93,16 @@ class IPADataset:
             "tokens": tokens.to(mel.device) if mel is not None else tokens,
             "ipa_texts": texts,
             "audio_paths": [e["audio_path"] for e in entries],
+            "clips_over_audio_ctx": report["longer_than_audio_ctx"],  # of the clips read: longer than audio_ctx * 20 ms, i.e. cut
         }
 
 
 def create_data_loader(json_path: str, multilingual: bool = True, n_mels: int = 80, audio_root: str = "",
-                       allow_byte_fallback: bool = False) -> IPADataset:
+                       allow_byte_fallback: bool = False, audio_ctx: Optional[int] = None) -> IPADataset:
     from whisper_ipa_amd import tokenizer as tok
 
     print(f"Loading Whisper tokenizer (multilingual={multilingual})...")
     tokenizer = tok.require_real_vocabulary(tok.get_tokenizer(multilingual=multilingual), allow_byte_fallback,
                                             "building IPA training / evaluation batches")
     tokenizer.language = "en"  # reference :152 (does not change the frozen sot_sequence)
-    return IPADataset(json_path, tokenizer, n_mels=n_mels, audio_root=audio_root)
+    return IPADataset(json_path, tokenizer, n_mels=n_mels, audio_root=audio_root, audio_ctx=audio_ctx)

@@ -288,7 +288,7 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
           batch_size: int = 4, learning_rate: float = 1e-5, validate_every: int = 100, save_every: int = 500,
           test_run: bool = False, audio_root: str = "", seed: Optional[int] = None, exact_f32: bool = False,
           allow_byte_fallback: bool = False, cache_encoder_features: bool = True, feature_cache_clips: Optional[int] = None,
-          clip_scope: str = "reference", scoring: str = "device"):
+          clip_scope: str = "reference", scoring: str = "device", audio_ctx: Optional[int] = None):
     rank, world = _init_distributed()
     try:
         parallel.require_even_shards(batch_size, world)  # every rank gets clips; no mismatched collectives
@@ -303,14 +303,15 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
                      "num_steps": num_steps, "batch_size": batch_size, "learning_rate": learning_rate,
                      "validate_every": validate_every, "save_every": save_every, "test_run": test_run,
                      "world_size": world, "f32_products": "exact" if exact_f32 else "split",
-                     "cache_encoder_features": bool(cache_encoder_features), "clip_scope": clip_scope, "scoring": scoring}
+                     "cache_encoder_features": bool(cache_encoder_features), "clip_scope": clip_scope, "scoring": scoring,
+                     "audio_ctx": audio_ctx}  # read back by the evaluation scripts (load_models.resolve_audio_ctx)
         save_training_config(output_dir, args_dict, get_hardware_info())
     logger = TrainingLogger(output_dir) if main else None
     print(f"Loading model: {model_name}")
     t0 = time.time()
-    model = load_model(model_name)
+    model = load_model(model_name, audio_ctx=audio_ctx)
     model.set_dtype(torch.float32)
-    print(f"  ✓ Model loaded in {time.time() - t0:.1f}s")
+    print(f"  ✓ Model loaded in {time.time() - t0:.1f}s" + (f" (audio_ctx {audio_ctx}: {audio_ctx * 0.02:.2f} s of context)" if audio_ctx else ""))
     freeze_encoder(model)
     # mlx AdamW defaults (reference :513); the clip reaches what the reference's clip_grad_dict reaches (:287-303: dicts only,
     # the decoder.blocks list passes through) unless --clip-scope all
@@ -319,9 +320,9 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
     if model.dims.n_mels != n_mels:
         n_mels = model.dims.n_mels
     train_dataset = create_data_loader(train_data_path, multilingual=True, n_mels=n_mels, audio_root=audio_root,
-                                       allow_byte_fallback=allow_byte_fallback)
+                                       allow_byte_fallback=allow_byte_fallback, audio_ctx=audio_ctx)
     test_dataset = create_data_loader(test_data_path, multilingual=True, n_mels=n_mels, audio_root=audio_root,
-                                      allow_byte_fallback=allow_byte_fallback)
+                                      allow_byte_fallback=allow_byte_fallback, audio_ctx=audio_ctx)
     tokenizer = train_dataset.tokenizer
     if test_run:
         train_dataset.data = train_dataset.data[:100]
@@ -333,7 +334,7 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
         cache = trainer.enable_feature_cache(feature_cache_clips if feature_cache_clips is not None else
                                              min(len(train_dataset), trainer.feature_cache_capacity_default()))
         print(f"  ✓ Frozen-encoder feature cache: up to {cache.max_clips} clips "
-              f"({cache.max_clips * model.dims.n_audio_ctx * model.dims.n_audio_state * 4 / 2**30:.1f} GiB of HBM)")
+              f"({cache.max_clips * model.n_audio_ctx * model.dims.n_audio_state * 4 / 2**30:.1f} GiB of HBM)")
 
     print("\n" + "=" * 70 + f"\nStarting training for {num_steps} steps\n" + "=" * 70)
     model.train()
@@ -365,6 +366,9 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
                     batch["tokens"] = torch.nn.functional.pad(batch["tokens"], (0, pad), value=tokenizer.eot)
             elif local_error is not None:
                 raise local_error
+            if batch.get("clips_over_audio_ctx"):
+                print(f"WARNING: step {step}: {batch['clips_over_audio_ctx']} of the clips read are longer than audio_ctx {audio_ctx} "
+                      f"({audio_ctx * 0.02:.2f} s) and are cut")
             step_start = time.time()
             loss, _ = train_step(trainer, batch, tokenizer)
             loss_value = float(loss.item())  # device sync, like mx.eval(loss) (reference :309)
@@ -463,12 +467,15 @@ def main():
                         "all: every decoder tensor by its own norm")
     p.add_argument("--allow-byte-fallback", action="store_true",
                    help="run without the Whisper vocabulary (WIPA_TIKTOKEN unset): raw-byte text ids; synthetic weights only")
+    p.add_argument("--audio-ctx", type=int, default=None,
+                   help="run the model on its first N audio positions of 20 ms instead of all 1500 (whisper.cpp's --audio-ctx; 300 covers "
+                        "6 s clips).  Recorded in training_config.json; clips longer than N * 20 ms are cut, with a warning.  Default: none")
     a = p.parse_args()
     train(model_name=a.model, train_data_path=a.train_data, test_data_path=a.test_data, output_dir=a.output_dir,
           num_steps=a.steps, batch_size=a.batch_size, learning_rate=a.lr, validate_every=a.validate_every,
           save_every=a.save_every, test_run=a.test_run, audio_root=a.audio_root, exact_f32=a.exact_f32,
           allow_byte_fallback=a.allow_byte_fallback, cache_encoder_features=not a.no_cache_encoder_features,
-          feature_cache_clips=a.feature_cache_clips, clip_scope=a.clip_scope, scoring=a.scoring)
+          feature_cache_clips=a.feature_cache_clips, clip_scope=a.clip_scope, scoring=a.scoring, audio_ctx=a.audio_ctx)
 
 
 if __name__ == "__main__":

@@ -20,12 +20,17 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from whisper_ipa_amd.audio import load_audio_batch, log_mel_spectrogram  # noqa: E402
 from whisper_ipa_amd.decoding import DecodingOptions, decode  # noqa: E402
-from whisper_ipa_amd.load_models import load_model, overlay_decoder_weights  # noqa: E402
+from whisper_ipa_amd.load_models import load_model, overlay_decoder_weights, resolve_audio_ctx  # noqa: E402
 
 
-def load_checkpoint_model(checkpoint_path: str, base_model: str = "mlx-community/whisper-large-v3-mlx"):
+def load_checkpoint_model(checkpoint_path: str, base_model: str = "mlx-community/whisper-large-v3-mlx", audio_ctx=None):
+    """``audio_ctx``: --audio-ctx; without one the value the checkpoint's training_config.json recorded is used, and a different one
+    is used with a warning (load_models.resolve_audio_ctx)"""
     print(f"Loading base model architecture: {base_model}")
-    model = load_model(base_model)
+    audio_ctx, warning = resolve_audio_ctx(audio_ctx, checkpoint_path)
+    if warning:
+        print(warning)
+    model = load_model(base_model, audio_ctx=audio_ctx)
     model.set_dtype(torch.float32)
     if checkpoint_path:
         try:
@@ -41,7 +46,10 @@ def load_checkpoint_model(checkpoint_path: str, base_model: str = "mlx-community
 def transcribe_file(model, audio_path: str, temperature: float = 0.0, seed=None, best_of=None, beam_size=None, patience=None,
                     length_penalty=None) -> str:
     print(f"Transcribing {audio_path}...")
-    audio = load_audio_batch([audio_path])  # load_audio -> pad_or_trim (reference :43-44) on the GPU: [1, 480000]
+    report = {}
+    audio = load_audio_batch([audio_path], audio_ctx=model.audio_ctx, report=report)  # load_audio -> pad_or_trim (reference :43-44) on the GPU: [1, 480000]
+    if report["longer_than_audio_ctx"]:
+        print(f"WARNING: {audio_path} is longer than audio_ctx {model.audio_ctx} ({model.audio_ctx * 0.02:.2f} s) and is cut")
     mel = log_mel_spectrogram(audio, n_mels=model.dims.n_mels).to(torch.float32)
     # IPA is decoded "as English"; a temperature above 0 samples, reproducibly, from ``seed``; ``best_of`` candidates, the best one kept
     # ``beam_size`` (temperature 0): beam search, with ``patience`` and ``length_penalty`` as upstream's DecodingOptions take them
@@ -70,11 +78,16 @@ def main(argv=None):
                     help="transcribe through whisper_ipa_amd.transcribe(word_timestamps=True) and also print one line per word (start, end, probability)")
     ap.add_argument("--allow-byte-fallback", action="store_true",
                     help="run without the Whisper vocabulary (WIPA_TIKTOKEN unset): ids >= 256 print as <|idN|>; synthetic weights only")
+    ap.add_argument("--audio-ctx", type=int, default=None,
+                    help="run the model on its first N audio positions of 20 ms (default: what the checkpoint's training_config.json "
+                         "records, else all 1500); a clip longer than N * 20 ms is cut, with a warning")
     args = ap.parse_args(argv)
     from whisper_ipa_amd.tokenizer import get_tokenizer, require_real_vocabulary
 
     require_real_vocabulary(get_tokenizer(True), args.allow_byte_fallback, "transcribing with a trained checkpoint")
-    model = load_checkpoint_model(args.checkpoint, args.base_model)
+    model = load_checkpoint_model(args.checkpoint, args.base_model, audio_ctx=args.audio_ctx)
+    if args.word_timestamps and model.audio_ctx is not None:
+        ap.error("--word-timestamps goes through transcribe(), which is not implemented for a model with audio_ctx set")
     if args.temperature != 0.0 and args.seed is None:
         ap.error("--temperature above 0 needs --seed")
     if args.best_of is not None and args.temperature == 0.0 and not args.word_timestamps:

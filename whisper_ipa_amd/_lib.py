@@ -118,6 +118,9 @@ SIGNATURES = {
     "wipa_logmel_workspace_bytes": (c_size_t, [c_int, c_int]),
     "wipa_logmel": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "wipa_mel_pad_cast": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "wipa_logmel_frames_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "wipa_logmel_frames": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "wipa_mel_pad_cast_frames": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "wipa_gemm": (c_int, [_P(GemmDesc), c_void_p]),
     "wipa_gemm_dispatch_counts": (c_int, [_P(c_int64), c_int, c_int]),
     "wipa_layernorm": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_int,

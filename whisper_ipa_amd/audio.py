@@ -234,6 +234,10 @@ class PcmBatch:
     def __len__(self) -> int:
         return self.B
 
+    def sample_counts(self) -> List[int]:
+        """every clip's length in 16 kHz samples, capped at the 30 s window"""
+        return [int(d.n_out) for d in self.descs]
+
 
 _resample_tables: "OrderedDict" = OrderedDict()   # (device index, src, dst) -> device table; small LRU
 _table_sets: "OrderedDict" = OrderedDict()        # (device index, rates) -> (concatenated tables, the single tables it was built from)
@@ -295,12 +299,17 @@ def _ingest(batch: PcmBatch, out: Optional[torch.Tensor] = None) -> Tuple[torch.
     return out, (batch, pcm, tables)
 
 
-def load_audio_batch(clips: Union[PcmBatch, Sequence[Union[str, PcmClip]]], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def load_audio_batch(clips: Union[PcmBatch, Sequence[Union[str, PcmClip]]], out: Optional[torch.Tensor] = None,
+                     audio_ctx: Optional[int] = None, report: Optional[dict] = None) -> torch.Tensor:
     """``pad_or_trim(load_audio(file))`` for a batch, on the GPU: files (PCM WAV), ``PcmClip``s or a ``PcmBatch`` ->
     audio [B, 480000] f32 on the device.  One host-to-device copy and one launch (csrc/resample.hip) on the current library
     stream; 16 kHz input is bit-identical to the host path, other rates agree to f32 rounding of the same filter.
-    ``out``: an existing [B, 480000] f32 device tensor to write into (every element is written)."""
+    ``out``: an existing [B, 480000] f32 device tensor to write into (every element is written).
+    ``report`` (a dict): receives ``"longer_than_audio_ctx"``, the clips of the batch that exceed ``audio_ctx`` * 320 samples and are
+    therefore CUT by a model running on ``audio_ctx`` positions (``count_longer_than_audio_ctx``)."""
     batch = clips if isinstance(clips, PcmBatch) else PcmBatch(clips)
+    if report is not None:
+        report["longer_than_audio_ctx"] = count_longer_than_audio_ctx(batch.sample_counts(), audio_ctx)
     return _ingest(batch, out)[0]
 
 
@@ -321,13 +330,33 @@ def _get_tables(n_mels: int) -> torch.Tensor:
     return t
 
 
-def padded_mel_rows(batch: int) -> int:
-    return batch * PADDED_FRAMES + 4
+def padded_mel_rows(batch: int, n_frames: int = N_FRAMES) -> int:
+    return batch * (n_frames + 2) + 4
 
 
-def log_mel_padded(audio: torch.Tensor, n_mels: int = 80, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+def audio_ctx_for_seconds(seconds: float) -> int:
+    """the smallest ``audio_ctx`` (encoder positions of 20 ms = 320 samples) that covers ``seconds`` of audio: 6.0 -> 300"""
+    if not 0.0 < seconds <= CHUNK_LENGTH:
+        raise ValueError(f"audio_ctx_for_seconds: {seconds!r} s is outside (0, {CHUNK_LENGTH}]")
+    per = 2 * HOP_LENGTH
+    return max(1, -(-int(np.ceil(seconds * SAMPLE_RATE - 1e-6)) // per))
+
+
+def count_longer_than_audio_ctx(n_samples: Iterable[int], audio_ctx: Optional[int]) -> int:
+    """how many clips (by their sample counts at 16 kHz) exceed ``audio_ctx`` * 320 samples, i.e. are CUT by a model running on
+    ``audio_ctx`` positions (None: the 30 s window)"""
+    limit = N_SAMPLES if audio_ctx is None else int(audio_ctx) * 2 * HOP_LENGTH
+    return sum(1 for n in n_samples if int(n) > limit)
+
+
+def log_mel_padded(audio: torch.Tensor, n_mels: int = 80, dtype: torch.dtype = torch.float32,
+                   n_frames: Optional[int] = None) -> torch.Tensor:
     """audio [B, 480000] f32 on the GPU -> padded mel [B*3002 + 4, n_mels] in ``dtype``
-    (frame t of clip b at row b*3002 + t + 1): the layout the encoder consumes directly."""
+    (frame t of clip b at row b*3002 + t + 1): the layout the encoder consumes directly.
+    ``n_frames`` (a model with ``audio_ctx`` = N passes 2N): the first n_frames frames of the same 30 s log-mel in the layout
+    [B*(n_frames + 2) + 4, n_mels], zero halo rows at 0 and n_frames + 1 of every clip."""
+    if n_frames is not None:
+        return _log_mel_padded_frames(audio, n_mels, dtype, int(n_frames))
     L = _lib.lib()
     assert audio.is_cuda and audio.dtype == torch.float32 and audio.dim() == 2 and audio.shape[1] == N_SAMPLES
     audio = audio.contiguous()
@@ -343,6 +372,27 @@ def log_mel_padded(audio: torch.Tensor, n_mels: int = 80, dtype: torch.dtype = t
         mel = torch.empty(padded_mel_rows(B), n_mels, dtype=dtype, device=audio.device)
         _lib.check(L.wipa_logmel(ptr(audio), B, n_mels, ptr(tables), ptr(mel), dt_code(dtype), ptr(ws), ws.numel(), sptr(s)),
                    "wipa_logmel")
+    return mel
+
+
+def _log_mel_padded_frames(audio: torch.Tensor, n_mels: int, dtype: torch.dtype, n_frames: int) -> torch.Tensor:
+    L = _lib.lib()
+    assert audio.is_cuda and audio.dtype == torch.float32 and audio.dim() == 2 and audio.shape[1] == N_SAMPLES
+    if not 1 <= n_frames <= N_FRAMES:
+        raise ValueError(f"log_mel_padded: n_frames={n_frames} (1..{N_FRAMES})")
+    audio = audio.contiguous()
+    B = audio.shape[0]
+    tables = _get_tables(n_mels)
+    with on_stream() as s:
+        key = (audio.device.index, stream_id(), "frames")
+        ws = _workspaces.get(key)
+        need = L.wipa_logmel_frames_workspace_bytes(B, n_mels, n_frames)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.uint8, device=audio.device)  # one per library stream
+            _workspaces[key] = ws
+        mel = torch.empty(padded_mel_rows(B, n_frames), n_mels, dtype=dtype, device=audio.device)
+        _lib.check(L.wipa_logmel_frames(ptr(audio), B, n_mels, ptr(tables), ptr(mel), dt_code(dtype), n_frames, ptr(ws), ws.numel(),
+                                        sptr(s)), "wipa_logmel_frames")
     return mel
 
 

@@ -476,7 +476,7 @@ class _Features:
     def __init__(self, model, x: torch.Tensor, chunk: int, options: DecodingOptions, tok):
         d = model.dims
         self.model, self.x, self.chunk, self.options, self.tok = model, x, max(int(chunk), 1), options, tok
-        self.encoded = tuple(x.shape[-2:]) == (d.n_audio_ctx, d.n_audio_state)
+        self.encoded = model.is_features(x)  # by the effective N (model.audio_ctx)
         self.n = x.shape[0]
         self.chunks: Dict[int, torch.Tensor] = {}
         self.lang_token: Dict[int, int] = {}

@@ -1065,6 +1065,22 @@ __global__ __launch_bounds__(256) void mel_pad_cast_kernel(const float* __restri
     out[i] = from_f32<TO>(v);
 }
 
+// the same for the first n_frames frames of every clip (short audio context: an encoder on n_frames / 2 positions)
+template <typename TO>
+__global__ __launch_bounds__(256) void mel_pad_cast_frames_kernel(const float* __restrict__ mel, int64_t clip_stride, int n_mels,
+                                                                  int n_frames, TO* __restrict__ out, int64_t total) {
+    // out [B, n_frames + 2, n_mels]; row 0 and n_frames + 1 zero, row t+1 = mel[b][t]
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int64_t per = (int64_t)(n_frames + 2) * n_mels;
+    const int64_t b = i / per;
+    const int64_t r = i - b * per;
+    const int row = (int)(r / n_mels);
+    float v = 0.f;
+    if (row >= 1 && row <= n_frames) v = mel[b * clip_stride + (r - n_mels)];
+    out[i] = from_f32<TO>(v);
+}
+
 }  // namespace
 
 extern "C" int wipa_layernorm(const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype, int64_t ldy, const float* w,
@@ -1637,6 +1653,29 @@ extern "C" int wipa_mel_pad_cast(const float* mel, int batch, int n_mels, void* 
         hipLaunchKernelGGL((mel_pad_cast_kernel<__bf16>), grid, dim3(256), 0, s, mel, n_mels, (__bf16*)mel_padded, total);
     else
         WIPA_REQUIRE(false, "wipa_mel_pad_cast: bad dtype %d", dtype);
+    WIPA_LAUNCH_CHECK();
+    const size_t esz = wipa_dtype_size(dtype);
+    WIPA_CHECK_HIP(hipMemsetAsync((char*)mel_padded + (size_t)total * esz, 0, 4 * (size_t)n_mels * esz, s));
+    return WIPA_OK;
+}
+
+extern "C" int wipa_mel_pad_cast_frames(const float* mel, int64_t clip_stride, int batch, int n_mels, int n_frames, void* mel_padded,
+                                        int dtype, wipa_stream_t stream) {
+    WIPA_REQUIRE(mel && mel_padded, "wipa_mel_pad_cast_frames: null pointer");
+    WIPA_REQUIRE(n_frames >= 1 && n_frames <= WIPA_N_FRAMES && n_mels > 0 && clip_stride >= (int64_t)n_frames * n_mels,
+                 "wipa_mel_pad_cast_frames: n_frames=%d (1..%d), clip stride %lld", n_frames, WIPA_N_FRAMES, (long long)clip_stride);
+    const int64_t total = (int64_t)batch * (n_frames + 2) * n_mels;
+    if (total <= 0) return WIPA_OK;
+    const dim3 grid((unsigned)((total + 255) / 256));
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == WIPA_F32)
+        hipLaunchKernelGGL((mel_pad_cast_frames_kernel<float>), grid, dim3(256), 0, s, mel, clip_stride, n_mels, n_frames, (float*)mel_padded,
+                           total);
+    else if (dtype == WIPA_BF16)
+        hipLaunchKernelGGL((mel_pad_cast_frames_kernel<__bf16>), grid, dim3(256), 0, s, mel, clip_stride, n_mels, n_frames,
+                           (__bf16*)mel_padded, total);
+    else
+        WIPA_REQUIRE(false, "wipa_mel_pad_cast_frames: bad dtype %d", dtype);
     WIPA_LAUNCH_CHECK();
     const size_t esz = wipa_dtype_size(dtype);
     WIPA_CHECK_HIP(hipMemsetAsync((char*)mel_padded + (size_t)total * esz, 0, 4 * (size_t)n_mels * esz, s));

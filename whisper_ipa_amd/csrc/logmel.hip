@@ -531,3 +531,54 @@ extern "C" int wipa_logmel(const float* audio, int batch, int n_mels, const void
     WIPA_CHECK_HIP(hipMemsetAsync((char*)mel + (size_t)batch * per_out * esz, 0, 4 * (size_t)n_mels * esz, s));
     return WIPA_OK;
 }
+
+// ------------------------------------------------------------------ the first n_frames frames (short audio context)
+// An encoder on n_audio_ctx = T positions consumes n_frames = 2T frames in the layout [B][n_frames + 2][n_mels] + 4 rows: the halo
+// row n_frames + 1 must be ZERO (conv1 at frame n_frames - 1 pads there), so the 3002-row layout cannot be read in place -- its
+// row n_frames + 1 is the real frame n_frames.  The front end itself does not change (30 s of audio, clamp at the clip's
+// maximum - 8 over all 3000 frames): the full layout is written to the workspace and its rows 1..n_frames are copied.
+namespace {
+template <typename T>
+__global__ __launch_bounds__(256) void mel_frames_kernel(const T* __restrict__ full, int n_mels, int n_frames, T* __restrict__ out,
+                                                         int64_t total) {
+    // out [B, n_frames + 2, n_mels] (+ 4 rows); rows 0, n_frames + 1 and everything past the last clip zero
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int64_t per = (int64_t)(n_frames + 2) * n_mels;
+    const int64_t b = i / per;
+    const int64_t r = i - b * per;
+    const int row = (int)(r / n_mels);
+    T v = (T)0.f;
+    if (row >= 1 && row <= n_frames) v = full[b * (int64_t)(WIPA_N_FRAMES + 2) * n_mels + r];
+    out[i] = v;
+}
+}  // namespace
+
+extern "C" size_t wipa_logmel_frames_workspace_bytes(int batch, int n_mels, int n_frames) {
+    if (batch <= 0 || n_mels <= 0 || n_frames < 1 || n_frames > WIPA_N_FRAMES) return 0;
+    return ws_layout(batch, n_mels).total + ((size_t)WIPA_MEL_ROWS(batch) * n_mels * sizeof(float) + 255) / 256 * 256;
+}
+
+extern "C" int wipa_logmel_frames(const float* audio, int batch, int n_mels, const void* tables, void* mel, int mel_dtype, int n_frames,
+                                  void* workspace, size_t workspace_bytes, wipa_stream_t stream) {
+    WIPA_REQUIRE(audio && tables && mel && workspace && batch > 0, "wipa_logmel_frames: null pointer / bad batch");
+    WIPA_REQUIRE(n_frames >= 1 && n_frames <= WIPA_N_FRAMES, "wipa_logmel_frames: n_frames=%d (1..%d)", n_frames, WIPA_N_FRAMES);
+    WIPA_REQUIRE(mel_dtype == WIPA_F32 || mel_dtype == WIPA_BF16, "wipa_logmel_frames: bad mel dtype %d", mel_dtype);
+    const size_t base = ws_layout(batch, n_mels).total;
+    WIPA_REQUIRE(workspace_bytes >= wipa_logmel_frames_workspace_bytes(batch, n_mels, n_frames),
+                 "wipa_logmel_frames: workspace too small (%zu < %zu)", workspace_bytes, wipa_logmel_frames_workspace_bytes(batch, n_mels, n_frames));
+    void* full = (char*)workspace + base;
+    const int rc = wipa_logmel(audio, batch, n_mels, tables, full, mel_dtype, workspace, base, stream);
+    if (rc != WIPA_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t body = (int64_t)batch * (n_frames + 2) * n_mels;  // the 4 tail rows behind it are cleared below, as wipa_logmel does
+    const dim3 grid((unsigned)((body + 255) / 256));
+    if (mel_dtype == WIPA_F32)
+        hipLaunchKernelGGL((mel_frames_kernel<float>), grid, dim3(256), 0, s, (const float*)full, n_mels, n_frames, (float*)mel, body);
+    else
+        hipLaunchKernelGGL((mel_frames_kernel<__bf16>), grid, dim3(256), 0, s, (const __bf16*)full, n_mels, n_frames, (__bf16*)mel, body);
+    WIPA_LAUNCH_CHECK();
+    const size_t esz = wipa_dtype_size(mel_dtype);
+    WIPA_CHECK_HIP(hipMemsetAsync((char*)mel + (size_t)body * esz, 0, 4 * (size_t)n_mels * esz, s));
+    return WIPA_OK;
+}

@@ -59,12 +59,16 @@ extern "C" int wipa_stream_destroy(wipa_stream_t s) {
 namespace {
 
 constexpr float QK_SCALE = 0.35355339059327379f;  // 64 ** -0.25
-constexpr int T_ENC_PAD = 1536;                     // V^T row length (>= ceil64(1500))
-constexpr int ROWS_IN = WIPA_N_FRAMES + 2;          // 3002 padded frames per clip
+constexpr int ENC_KEY_TILE = 64;                    // keys per tile of wipa_flash_attn_enc_bf16 (its V^T rows are whole tiles)
 
 inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 inline int k_multiple(int dtype) { return dtype == WIPA_BF16 ? 64 : 32; }
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+// The encoder runs on T = cfg.n_audio_ctx positions, i.e. on the first 2T mel frames (wipa_model_cfg).  Per clip: 2T + 2 padded
+// frames (3002 at T = 1500) and a V^T row of ceil64(T) keys (1536 at T = 1500).
+inline int enc_rows_in(int T) { return 2 * T + 2; }
+inline int enc_vt_pad(int T) { return round_up(T, ENC_KEY_TILE); }
+inline bool audio_ctx_ok(const wipa_model_cfg* c) { return c->n_audio_ctx >= 1 && c->n_audio_ctx <= WIPA_N_FRAMES / 2; }
 
 #define RT_CALL(expr)                 \
     do {                              \
@@ -77,7 +81,7 @@ int cfg_check(const wipa_model_cfg* c) {
     WIPA_REQUIRE(c->dtype == WIPA_F32 || c->dtype == WIPA_BF16, "cfg.dtype %d", c->dtype);
     WIPA_REQUIRE(c->n_audio_state == c->n_audio_head * WIPA_HEAD_DIM && c->n_text_state == c->n_text_head * WIPA_HEAD_DIM,
                  "head_dim must be 64 (state %d heads %d)", c->n_audio_state, c->n_audio_head);
-    WIPA_REQUIRE(c->n_audio_ctx == WIPA_N_FRAMES / 2, "n_audio_ctx must be 1500");
+    WIPA_REQUIRE(audio_ctx_ok(c), "n_audio_ctx %d: must be 1..%d", c->n_audio_ctx, WIPA_N_FRAMES / 2);
     WIPA_REQUIRE(c->n_audio_state % 64 == 0 && c->n_text_state % 64 == 0, "state must be a multiple of 64");
     WIPA_REQUIRE(c->dec_w_dtype == 0 || (c->dec_w_dtype == WIPA_FP8_E4M3 && c->dtype == WIPA_BF16),
                  "cfg.dec_w_dtype %d: fp8 (e4m3) decoder weights need a bf16 model", c->dec_w_dtype);
@@ -192,6 +196,7 @@ struct EncWs {
 };
 EncWs enc_ws(const wipa_model_cfg* c, int B) {
     const size_t e = wipa_dtype_size(c->dtype), d = c->n_audio_state, M = (size_t)B * c->n_audio_ctx;
+    const size_t ROWS_IN = enc_rows_in(c->n_audio_ctx), T_ENC_PAD = enc_vt_pad(c->n_audio_ctx);
     EncWs w;
     size_t o = 0;
     w.c1 = o; o += align256(((size_t)B * ROWS_IN + 4) * d * e);
@@ -205,10 +210,27 @@ EncWs enc_ws(const wipa_model_cfg* c, int B) {
     return w;
 }
 
+// V [B*T][d] (row-major, bf16) -> V^T [B][d][ldvt] for wipa_flash_attn_enc_bf16; columns >= T are left as the memset wrote them.
+// grid (d / 64, ceil(T / 64), B); the tile goes through LDS so that both the reads and the writes run along rows.
+__global__ __launch_bounds__(256) void vt_from_rows_kernel(const __bf16* __restrict__ v, __bf16* __restrict__ vt, int T, int d, int64_t ldvt) {
+    __shared__ __bf16 tile[64][66];
+    const int c0 = blockIdx.x * 64, t0 = blockIdx.y * 64, b = blockIdx.z;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    for (int i = ty; i < 64; i += 4) {
+        const int t = t0 + i;
+        tile[i][tx] = t < T ? v[((int64_t)b * T + t) * d + c0 + tx] : (__bf16)0.f;
+    }
+    __syncthreads();
+    for (int i = ty; i < 64; i += 4) {
+        const int t = t0 + tx;
+        if (t < T) vt[((int64_t)b * d + c0 + i) * ldvt + t] = tile[tx][i];
+    }
+}
+
 }  // namespace
 
 extern "C" size_t wipa_encoder_workspace_bytes(const wipa_model_cfg* cfg, int B) {
-    if (!cfg || B <= 0) return 0;
+    if (!cfg || B <= 0 || !audio_ctx_ok(cfg)) return 0;
     return enc_ws(cfg, B).total;
 }
 
@@ -223,6 +245,7 @@ extern "C" int wipa_encoder_forward(const wipa_model_cfg* cfg, const void* const
     const int dt = cfg->dtype;
     const size_t e = wipa_dtype_size(dt);
     const int d = cfg->n_audio_state, H = cfg->n_audio_head, T = cfg->n_audio_ctx, M = B * T;
+    const int ROWS_IN = enc_rows_in(T), T_ENC_PAD = enc_vt_pad(T);
     char* ws = (char*)workspace;
     void* c1 = ws + L.c1;
     float* x = (float*)(ws + L.x);
@@ -234,12 +257,12 @@ extern "C" int wipa_encoder_forward(const wipa_model_cfg* cfg, const void* const
     const int K1 = round_up(3 * cfg->n_mels, k_multiple(dt));
 
     // conv1 (k3,p1) + GELU as a GEMM with overlapping rows; output row g lands at c1 row g+1,
-    // dead rows (t >= 3000) write the zero halos of conv2.
+    // dead rows (t >= 2T; 3000 at T = 1500) write the zero halos of conv2.
     WIPA_CHECK_HIP(hipMemsetAsync(c1, 0, (size_t)d * e, s));
     {
         wipa_gemm_desc g;
         memset(&g, 0, sizeof(g));
-        g.rg_in = ROWS_IN; g.rg_valid = WIPA_N_FRAMES; g.rg_stride = (int64_t)ROWS_IN * d; g.zero_invalid_rows = 1;
+        g.rg_in = ROWS_IN; g.rg_valid = 2 * T; g.rg_stride = (int64_t)ROWS_IN * d; g.zero_invalid_rows = 1;
         g.c_offset = d;
         PROF(PROF_GEMM, gemm(mel_padded, cfg->n_mels, w[0], K1, c1, d, B * ROWS_IN, d, K1, dt, dt, (const float*)w[1], 1, nullptr,
                      stream, &g));
@@ -278,10 +301,26 @@ extern "C" int wipa_encoder_forward(const wipa_model_cfg* cfg, const void* const
             // V^T per clip: swap the operand roles so the GEMM writes [d][t] directly
             wipa_gemm_desc g;
             memset(&g, 0, sizeof(g));
-            g.bias_along_m = 1; g.cg_in = T; g.cg_stride = (int64_t)d * T_ENC_PAD;
-            if (f8) PROF(PROF_GEMM, gemm_f8(l8[2], d, (const float*)l8[3], ln, d, ln_scale, vb, T_ENC_PAD, d, M, d, dt, (const float*)lw[5], 0,
-                                            nullptr, stream, &g));
-            else PROF(PROF_GEMM, gemm(lw[4], d, ln, d, vb, T_ENC_PAD, d, M, d, dt, dt, (const float*)lw[5], 0, nullptr, stream, &g));
+            g.bias_along_m = 1;
+            if (T % 4 == 0) {  // one launch: the columns (tokens) are remapped per clip
+                g.cg_in = T; g.cg_stride = (int64_t)d * T_ENC_PAD;
+                if (f8) PROF(PROF_GEMM, gemm_f8(l8[2], d, (const float*)l8[3], ln, d, ln_scale, vb, T_ENC_PAD, d, M, d, dt, (const float*)lw[5], 0,
+                                                nullptr, stream, &g));
+                else PROF(PROF_GEMM, gemm(lw[4], d, ln, d, vb, T_ENC_PAD, d, M, d, dt, dt, (const float*)lw[5], 0, nullptr, stream, &g));
+            } else {
+                // the epilogue remaps columns in groups of 4 (wipa_gemm_desc.cg_in): a clip of T % 4 != 0 tokens (short audio
+                // context only) would share a group with its neighbour.  V is projected row-major into the (idle) mlp buffer
+                // and transposed per clip by one launch.
+                if (f8) PROF(PROF_GEMM, gemm_f8(ln, d, ln_scale, l8[2], d, (const float*)l8[3], hb, d, M, d, d, dt, (const float*)lw[5], 0, nullptr,
+                                                stream));
+                else PROF(PROF_GEMM, gemm(ln, d, lw[4], d, hb, d, M, d, d, dt, dt, (const float*)lw[5], 0, nullptr, stream));
+                {
+                    ProfSpan span(PROF_OTHER);
+                    hipLaunchKernelGGL(vt_from_rows_kernel, dim3(d / 64, (T + 63) / 64, B), dim3(256), 0, s, (const __bf16*)hb, (__bf16*)vb, T, d,
+                                       (int64_t)T_ENC_PAD);
+                    WIPA_LAUNCH_CHECK();
+                }
+            }
             PROF(PROF_ATTN, wipa_flash_attn_enc_bf16(qk, 2 * d, vb, T_ENC_PAD, ao, d, B, H, T, stream));
         } else {
             PROF(PROF_GEMM, gemm(ln, d, lw[4], d, vb, d, M, d, d, dt, dt, (const float*)lw[5], 0, nullptr, stream));
@@ -1814,7 +1853,7 @@ int enqueue_prefill_ragged(const wipa_model_cfg* cfg, const void* const* w, char
 }  // namespace
 
 extern "C" size_t wipa_decoder_prompt_workspace_bytes(const wipa_model_cfg* cfg, int B, int P) {
-    if (!cfg || B <= 0 || P <= 0) return 0;
+    if (!cfg || !audio_ctx_ok(cfg) || B <= 0 || P <= 0) return 0;
     return prompt_ws(cfg, B, P).total;
 }
 
@@ -1906,7 +1945,7 @@ extern "C" int wipa_decoder_seek(const wipa_model_cfg* cfg, void* state, size_t 
 }
 
 extern "C" size_t wipa_decoder_admit_prompted_workspace_bytes(const wipa_model_cfg* cfg, int n_rows, int W) {
-    if (!cfg || n_rows <= 0 || W < 0) return 0;
+    if (!cfg || !audio_ctx_ok(cfg) || n_rows <= 0 || W < 0) return 0;
     return admit_ws(cfg, n_rows, W).total;
 }
 
@@ -2053,7 +2092,7 @@ int tf_layers(const wipa_model_cfg* cfg, const void* const* w, const int32_t* to
 }  // namespace
 
 extern "C" size_t wipa_decoder_logits_workspace_bytes(const wipa_model_cfg* cfg, int B, int T) {
-    if (!cfg || B <= 0 || T <= 0) return 0;
+    if (!cfg || !audio_ctx_ok(cfg) || B <= 0 || T <= 0) return 0;
     return tf_ws(cfg, B, T).total;
 }
 
@@ -2120,7 +2159,7 @@ struct AlignHook : TfHook {
 }  // namespace
 
 extern "C" size_t wipa_decoder_align_workspace_bytes(const wipa_model_cfg* cfg, int B, int T, int n_heads, int logits_rows) {
-    if (!cfg || B <= 0 || T <= 0 || n_heads <= 0 || logits_rows < 0) return 0;
+    if (!cfg || !audio_ctx_ok(cfg) || B <= 0 || T <= 0 || n_heads <= 0 || logits_rows < 0) return 0;
     return align_ws(cfg, B, T, n_heads, logits_rows).total;
 }
 

@@ -405,6 +405,9 @@ def _open(model, L, pk, st, audio_features: torch.Tensor, B: int, s, begin):
     (wipa_decoder_set_audio), then ``begin``.  Returns (the features, which must outlive the enqueued work, and what ``begin`` returns:
     the state's device array of first columns, or None)"""
     feats = audio_features.to(device=model.device, dtype=model.dtype).contiguous()
+    if tuple(feats.shape[-2:]) != (model.n_audio_ctx, model.dims.n_text_state):  # the state is sized for the effective N
+        raise _lib.WipaError(f"decode: audio features of shape {tuple(feats.shape)} given to a model that runs on "
+                             f"[.., {model.n_audio_ctx}, {model.dims.n_text_state}] (audio_ctx={model.audio_ctx!r})")
     _lib.check(L.wipa_decoder_set_audio(C.byref(pk["cfg"]), pk["dec_tab"], ptr(feats), ptr(st.blob), st.blob.numel(), B, sptr(s)),
                "wipa_decoder_set_audio")
     return feats, begin(L, pk, st, B, s)
@@ -866,7 +869,7 @@ def decode(model, mel: torch.Tensor, options: DecodingOptions = DecodingOptions(
     if single:
         mel = mel[None]
     d = model.dims
-    if tuple(mel.shape[-2:]) == (d.n_audio_ctx, d.n_audio_state):
+    if model.is_features(mel):  # by the effective N (model.audio_ctx); features of another length are refused
         feats = mel
     else:
         feats = model.embed_audio(mel)

@@ -86,9 +86,11 @@ def save_safetensors(path: str, flat: Dict[str, torch.Tensor]) -> None:
     save_file({k: v.detach().to("cpu").contiguous() for k, v in flat.items()}, path)
 
 
-def load_model(path_or_name: str, dtype: torch.dtype = torch.float32, sinusoid_rounding: str = "f32") -> Whisper:
+def load_model(path_or_name: str, dtype: torch.dtype = torch.float32, sinusoid_rounding: str = "f32",
+               audio_ctx: Optional[int] = None) -> Whisper:
     """Local directory -> Whisper.  Raises with a clear message for hub names (offline).
-    ``sinusoid_rounding="fp16"`` reproduces mlx_whisper's fp16-built encoder sinusoid table (Whisper.__init__)."""
+    ``sinusoid_rounding="fp16"`` reproduces mlx_whisper's fp16-built encoder sinusoid table (Whisper.__init__).
+    ``audio_ctx``: run the model on its first N audio positions (Whisper.__init__)."""
     if not os.path.isdir(path_or_name):
         raise FileNotFoundError(
             f"load_model: '{path_or_name}' is not a local directory. The reference downloads hub names "
@@ -110,9 +112,37 @@ def load_model(path_or_name: str, dtype: torch.dtype = torch.float32, sinusoid_r
             break
     if weights is None:
         raise FileNotFoundError(f"load_model: no weights.safetensors / model.safetensors in {path_or_name}")
-    model = Whisper(dims, dtype=dtype, sinusoid_rounding=sinusoid_rounding)
+    model = Whisper(dims, dtype=dtype, sinusoid_rounding=sinusoid_rounding, audio_ctx=audio_ctx)
     model.load_weights(weights)
     return model
+
+
+def trained_audio_ctx(checkpoint_dir: str):
+    """(found, audio_ctx) from the ``training_config.json`` a fine-tune run wrote beside its checkpoints
+    (scripts/train_whisper_ipa.py: ``training_args.audio_ctx``; the file lies in the run's output directory, the parent of a
+    ``checkpoint-N`` / ``best-checkpoint`` directory).  ``found`` is False when there is no such file; a file written before the key
+    existed counts as audio_ctx None, the 30 s context."""
+    for d in (checkpoint_dir, os.path.dirname(os.path.normpath(checkpoint_dir))):
+        p = os.path.join(d, "training_config.json")
+        if d and os.path.exists(p):
+            with open(p) as f:
+                v = json.load(f).get("training_args", {}).get("audio_ctx")
+            return True, (None if v is None else int(v))
+    return False, None
+
+
+def resolve_audio_ctx(requested: Optional[int], checkpoint_dir: Optional[str]):
+    """the ``audio_ctx`` an evaluation of ``checkpoint_dir`` runs at, and a one-line warning or None: the value the run recorded
+    when none is requested; the requested one otherwise -- with a warning when it is not the one the checkpoint was trained at."""
+    found, trained = trained_audio_ctx(checkpoint_dir) if checkpoint_dir else (False, None)
+    if not found:
+        return requested, None
+    if requested is None:
+        return trained, None
+    if requested != trained:
+        return requested, (f"WARNING: --audio-ctx {requested} but {checkpoint_dir} was trained at audio_ctx "
+                           f"{'none (30 s)' if trained is None else trained}: the model is evaluated at another context than it was trained at")
+    return requested, None
 
 
 def save_model(model: Whisper, path: str) -> None:

@@ -261,16 +261,19 @@ class TranscribePipeline:
             if keep is not None:
                 keep.extend(held)
         t = torch.as_tensor(batch)
-        if t.dim() == 3 and tuple(t.shape[-2:]) == (d.n_audio_ctx, d.n_audio_state):
+        if t.dim() == 3 and m.is_features(t):  # by the effective N (model.audio_ctx)
             feats = t.to(device=m.device, non_blocking=True)
         elif t.dim() == 3:
             feats = m.embed_audio(t.to(device=m.device, non_blocking=True))
         elif t.dim() == 2:
             a = A.pad_or_trim(t.to(device=m.device, dtype=torch.float32, non_blocking=True))
-            feats = m.encode_padded(A.log_mel_padded(a, d.n_mels, m.dtype), a.shape[0])
+            if m.audio_ctx is None:
+                feats = m.encode_padded(A.log_mel_padded(a, d.n_mels, m.dtype), a.shape[0])
+            else:  # the first 2N frames of the same log-mel, in their own halo layout
+                feats = m.encode_padded(A.log_mel_padded(a, d.n_mels, m.dtype, n_frames=m.n_audio_frames), a.shape[0])
         else:
             raise _lib.WipaError(f"transcribe_batches: a batch is audio [B, samples], mel [B, 3000, n_mels] or features "
-                                 f"[B, {d.n_audio_ctx}, {d.n_audio_state}]; got shape {tuple(t.shape)}")
+                                 f"[B, {m.n_audio_ctx}, {d.n_audio_state}]; got shape {tuple(t.shape)}")
         if self.options.fp16 and m.dtype == torch.float32:
             feats = feats.to(torch.float16).to(torch.float32)  # DecodingOptions.fp16, as decoding.decode
         return feats.to(m.dtype).contiguous()

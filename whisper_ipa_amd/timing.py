@@ -75,7 +75,7 @@ def align_tokens(model, tokens_rows: Sequence[Sequence[int]], n_rows: Sequence[i
         raise NotImplementedError("word timestamps run the teacher-forced decoder on bf16 / f32 weights: not implemented for an fp8-quantised model")
     L = _lib.lib()
     pk = model.packed(teacher_forced=True, absorbed=False)
-    dims = model.dims
+    dims, n_ctx = model.dims, model.n_audio_ctx  # the positions the model runs on (model.audio_ctx): n_frames is clipped to them
     B = len(tokens_rows)
     T = max(len(r) for r in tokens_rows)
     if T > dims.n_text_ctx:
@@ -85,20 +85,22 @@ def align_tokens(model, tokens_rows: Sequence[Sequence[int]], n_rows: Sequence[i
     for b, r in enumerate(tokens_rows):
         tok[b, :len(r)] = np.asarray(r, dtype=np.int32)
     n_tok = np.array([len(r) for r in tokens_rows], dtype=np.int32)
-    n_fr = np.clip(np.asarray(n_frames, dtype=np.int32), 1, dims.n_audio_ctx).astype(np.int32)
+    n_fr = np.clip(np.asarray(n_frames, dtype=np.int32), 1, n_ctx).astype(np.int32)
     n_row = np.asarray(n_rows, dtype=np.int32)
     heads_arr = np.asarray(heads, dtype=np.int32).reshape(-1)
-    ld_path = T + dims.n_audio_ctx
+    ld_path = T + n_ctx
     with on_stream() as s:
         dev = model.device
         d_tok = torch.from_numpy(tok).to(dev)
         d_sizes = torch.from_numpy(np.stack([n_tok, n_fr, n_row])).to(dev)
         feats = features.to(device=dev, dtype=model.dtype).contiguous()
-        assert feats.shape == (B, dims.n_audio_ctx, dims.n_text_state), feats.shape
+        if tuple(feats.shape) != (B, n_ctx, dims.n_text_state):
+            raise _lib.WipaError(f"align: audio features of shape {tuple(feats.shape)}, expected {(B, n_ctx, dims.n_text_state)} "
+                                 f"(audio_ctx={model.audio_ctx!r})")
         need = L.wipa_decoder_align_workspace_bytes(C.byref(pk["cfg"]), B, T, len(heads), int(logits_rows))
         # the pass buffers and up to 1 GiB of logits block: the call's own, back in torch's pool when it returns
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        matrix = torch.empty(B, T, dims.n_audio_ctx, dtype=torch.float32, device=dev)
+        matrix = torch.empty(B, T, n_ctx, dtype=torch.float32, device=dev)
         path = torch.zeros(2, B, ld_path, dtype=torch.int32, device=dev)
         path_len = torch.zeros(B, dtype=torch.int32, device=dev)
         probs = torch.zeros(B, T, dtype=torch.float32, device=dev)

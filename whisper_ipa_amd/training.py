@@ -44,12 +44,13 @@ class FrozenFeatureCache:
     Clips beyond ``max_clips`` are simply recomputed every time (spill to recompute, no eviction).  The entries are
     functions of the encoder weights: the model counts every change of an ``encoder.*`` tensor (load_weights / update /
     set_dtype / quantize_weights -> ``Whisper._enc_generation``) and the cache drops itself when the count moved, so stale
-    features cannot survive an encoder update; DecoderTrainer itself never touches encoder tensors."""
+    features cannot survive an encoder update; DecoderTrainer itself never touches encoder tensors.
+    With ``model.audio_ctx`` = N a row is N x d (five times as many clips fit at N = 300); a change of it counts as an encoder update.
+    The bit-identity across batches holds while every encoder GEMM runs in the tile kernels, i.e. for batches of more than 256 / N
+    clips: below that wipa_gemm takes the weight-streaming kernel, whose summation order differs in the last bits (N <= 256 only)."""
 
     def __init__(self, model: Whisper, max_clips: int):
-        d = model.dims
         self.model, self.max_clips = model, int(max_clips)
-        self.row_shape = (d.n_audio_ctx, d.n_audio_state)
         self.slots: Dict[int, int] = {}
         self.store: Optional[torch.Tensor] = None  # [max_clips, 1500, d] f32, allocated on first use
         self._pinned = None  # ring of [pinned int64 [2, n], event of the last upload]: host staging of the gather indices
@@ -57,15 +58,22 @@ class FrozenFeatureCache:
         self.hits = self.misses = 0
         self._enc_generation = model._enc_generation
 
+    @property
+    def row_shape(self):
+        """(N, d): N the positions the model runs on -- changing model.audio_ctx counts as an encoder change and drops the entries"""
+        return (self.model.n_audio_ctx, self.model.dims.n_audio_state)
+
     def _drop_if_encoder_changed(self) -> None:
         if self._enc_generation != self.model._enc_generation:
             self.clear()
+            if self.store is not None and tuple(self.store.shape[1:]) != self.row_shape:
+                self.store = None  # rows of another length (model.audio_ctx changed): allocated again on first use
             self._enc_generation = self.model._enc_generation
 
     @staticmethod
     def clips_that_fit(model: Whisper, fraction_of_free: float = 0.5) -> int:
         free, _ = torch.cuda.mem_get_info(model.device)
-        return int(free * fraction_of_free) // (model.dims.n_audio_ctx * model.dims.n_audio_state * 4)
+        return int(free * fraction_of_free) // (model.n_audio_ctx * model.dims.n_audio_state * 4)
 
     def clear(self) -> None:
         self.slots.clear()
@@ -367,9 +375,12 @@ class DecoderTrainer:
         m, dm, L = self.model, self.model.dims, self.L
         P = self.p
         B, T = tok_in.shape
-        d, H, V, Ta = dm.n_text_state, dm.n_text_head, dm.n_vocab, dm.n_audio_ctx
+        d, H, V, Ta = dm.n_text_state, dm.n_text_head, dm.n_vocab, self.model.n_audio_ctx
         M, Mp = B * T, _ceil(B * T, 32)
         Vp = _ceil(V, 32)
+        if tuple(audio_features.shape) != (B, Ta, d):  # Ta: the positions the model runs on (model.audio_ctx)
+            raise _lib.WipaError(f"DecoderTrainer: audio features of shape {tuple(audio_features.shape)}, expected {(B, Ta, d)} "
+                                 f"(audio_ctx={m.audio_ctx!r})")
         with on_stream() as s:
             dev = m.device
             feats = audio_features.to(device=dev, dtype=torch.float32).contiguous().view(B * Ta, d)
@@ -423,7 +434,7 @@ class DecoderTrainer:
         P, G = self.p, self.g
         saved, x_L, hf, feats, featsT, tok_in = ctx["saved"], ctx["x_L"], ctx["hf"], ctx["feats"], ctx["featsT"], ctx["tok_in"]
         B, T = ctx["B"], ctx["T"]
-        d, H, V, Ta = dm.n_text_state, dm.n_text_head, dm.n_vocab, dm.n_audio_ctx
+        d, H, V, Ta = dm.n_text_state, dm.n_text_head, dm.n_vocab, self.model.n_audio_ctx
         M, Mp = B * T, _ceil(B * T, 32)
         Vp = _ceil(V, 32)
         with on_stream() as s:

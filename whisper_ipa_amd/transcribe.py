@@ -560,7 +560,11 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
     ``min(n_text_ctx // 2 - 1, column_limit - n_init - sample_len - 2 * check_every)``: with the defaults that is 196 tokens against
     upstream's 223 at ``sample_len`` 224 (``continuous_prompt_budget``); a smaller ``sample_len`` restores 223.  So with the defaults
     the two schedules condition a window that has more than 196 tokens of history on different prompts; an explicit ``prompt_budget``
-    of at most 196 gives both the same."""
+    of at most 196 gives both the same.
+    A model with ``audio_ctx`` set is refused: the window loop, the seek arithmetic and the timestamp range assume 30 s windows."""
+    if getattr(model, "audio_ctx", None) is not None:
+        raise NotImplementedError(f"transcribe() on a model with audio_ctx={model.audio_ctx} is not implemented: its window loop, seek "
+                                  "arithmetic and timestamp range assume 30 s windows; decode() / decode_continuous() serve audio_ctx")
     _refuse(condition_on_previous_text, initial_prompt, word_timestamps, clip_timestamps, hallucination_silence_threshold, temperature,
             decode_options, can_align=align_fn is not None or (model is not None and decode_fn is None),
             can_retry=decode_fn is None or fallback_fn is not None,

@@ -118,7 +118,8 @@ class _Part:
 
 class Whisper:
     def __init__(self, dims: ModelDimensions, dtype: torch.dtype = torch.float32, f32_split: Optional[bool] = None,
-                 sinusoid_rounding: str = "f32", cross_attention: str = "auto", cross_splits: int = 0):
+                 sinusoid_rounding: str = "f32", cross_attention: str = "auto", cross_splits: int = 0,
+                 audio_ctx: Optional[int] = None):
         """``f32_split`` (float32 models only): the large GEMMs and the encoder attention take every f32 product as three
         split-bf16 MFMA terms (~5e-6 relative error per dot product) instead of on the f32 MFMA.  ON by default since round 5
         (None = on; False = exact f32 products, what the reference computes: train_whisper_ipa.py:505, transcribe_single.py:13).
@@ -149,10 +150,19 @@ class Whisper:
         GPU (bench.py's pipelined passes): the streaming kernels of two passes run side by side instead of queueing for all 256
         CUs -- measured on MI355X, whisper-small, 64 clips, 4 passes in flight: 72.3 against 75.3 ms per pass, while a lone
         decode step costs 1.35 against 1.25 ms (3: 73.5 ms / 1.26 ms; profiles/r04_stream_splits_ab.txt).  The count never
-        depends on the batch; it moves the order of the softmax merges, i.e. bf16-level rounding like any other kernel choice."""
+        depends on the batch; it moves the order of the softmax merges, i.e. bf16-level rounding like any other kernel choice.
+        ``audio_ctx`` (also an attribute that may be changed between calls): run the model on the first N of its 1500 audio
+        positions -- whisper.cpp's --audio-ctx.  It is the same Whisper with n_audio_ctx = N: the first 2N frames of the 30 s
+        log-mel (clamp maximum over the whole window included), the first N rows of the encoder's positional table, features
+        [B, N, d], and N cross-attention keys in every decoder pass.  conv1 at frame 2N - 1 and conv2 at position N - 1 see zero
+        padding where frame 2N would be, so the features are NOT the first N rows of the full-context features.  ``dims`` keeps
+        describing the weights (dims.n_audio_ctx stays 1500); ``n_audio_ctx`` is the effective N.  None (default) changes
+        nothing.  A pretrained Whisper was trained on 30 s of context: this is a setting for models fine-tuned and evaluated at
+        the same N (quality on pretrained weights is unmeasured).  Clips longer than N * 20 ms are cut."""
         if cross_splits not in (0, 1, 2, 3, 4):
             raise _lib.WipaError(f"cross_splits must be 0 (default) or 1..4, got {cross_splits!r}")
         self._cross_splits = int(cross_splits)
+        self._audio_ctx = self._checked_audio_ctx(audio_ctx, dims)
         if cross_attention not in ("auto", "absorbed", "cached"):
             raise _lib.WipaError(f"cross_attention must be 'auto', 'absorbed' or 'cached', got {cross_attention!r}")
         self.cross_attention = cross_attention
@@ -182,6 +192,53 @@ class Whisper:
             if sinusoid_rounding == "fp16":
                 pos = pos.to(torch.float16).to(torch.float32)
             self._enc_pos = pos.to(self.device)
+
+    # ---- short audio context ----------------------------------------------------------
+    @staticmethod
+    def _checked_audio_ctx(n, dims) -> Optional[int]:
+        if n is None:
+            return None
+        if isinstance(n, bool) or int(n) != n or not 1 <= int(n) <= dims.n_audio_ctx:
+            raise _lib.WipaError(f"audio_ctx must be None or an integer in 1..{dims.n_audio_ctx}, got {n!r}")
+        return int(n)
+
+    @property
+    def audio_ctx(self) -> Optional[int]:
+        return self._audio_ctx
+
+    @audio_ctx.setter
+    def audio_ctx(self, n: Optional[int]):
+        n = self._checked_audio_ctx(n, self.dims)
+        if n == self._audio_ctx:
+            return
+        self._audio_ctx = n
+        # everything sized by N dies: packed tables (their cfg), decode states and their step graphs, workspaces; cached
+        # features are functions of N as they are of the encoder weights
+        self._enc_generation += 1
+        self._invalidate()
+        self._enc_ws = {}
+        self._tf_ws = {}
+
+    @property
+    def n_audio_ctx(self) -> int:
+        """the audio positions the model runs on: ``audio_ctx``, or all of dims.n_audio_ctx"""
+        return self.dims.n_audio_ctx if self._audio_ctx is None else self._audio_ctx
+
+    @property
+    def n_audio_frames(self) -> int:
+        """the mel frames the encoder consumes: two per audio position"""
+        return 2 * self.n_audio_ctx
+
+    def is_features(self, x: torch.Tensor) -> bool:
+        """tells encoder features [.., N, d] from a mel [.., frames, n_mels] by the trailing shape; features of another length than
+        the effective N are refused by name"""
+        d, N = self.dims, self.n_audio_ctx
+        if tuple(x.shape[-2:]) == (N, d.n_audio_state):
+            return True
+        if x.shape[-1] == d.n_audio_state and x.shape[-1] != d.n_mels:
+            raise _lib.WipaError(f"audio features of {x.shape[-2]} positions given to a model that runs on {N} "
+                                 f"(audio_ctx={self._audio_ctx!r}): expected [.., {N}, {d.n_audio_state}]")
+        return False
 
     # ---- mlx.nn.Module-like surface ------------------------------------------------
     @property
@@ -363,6 +420,11 @@ class Whisper:
     # what the reference's callers get by default (scripts/transcribe_single.py:49-52 leaves sample_len unset).
     AUTO_CACHED_MAX_BATCH = 64
     AUTO_CACHED_MIN_NEW_TOKENS = 192
+    # Short audio context (audio_ctx set): the table above was measured at 1500 keys.  At 300 keys the cached form is the faster one,
+    # alone and with 4 passes in flight (whisper-small, 64 clips x 64 new tokens: 779 against 1005 us per lone step, 31.3 against 34.0 ms
+    # per pass in flight); at 750 keys absorbed still leads in flight (45.9 against 48.2 ms) although a lone cached step is shorter
+    # (profiles/audio_ctx_bench.txt).  Measured at 300 and 750 only: "auto" takes cached up to 300 and keeps absorbed above.
+    AUTO_CACHED_MAX_AUDIO_CTX = 300
 
     @property
     def cross_absorbed_eligible(self) -> bool:
@@ -374,7 +436,8 @@ class Whisper:
         """whether a decode of ``batch`` clips x ``new_tokens`` positions uses the absorbed-projection cross-attention (see
         ``cross_attention`` in __init__).  "absorbed" / "cached" force the form; "auto" takes absorbed where it applies EXCEPT
         for long outputs at a small batch (<= 64 clips with >= 192 new tokens: the measured table above), where the cached
-        K / V form is faster.  Unknown sizes (None) count as short / large.  WIPA_CROSS_ABSORB=0 turns "auto" off."""
+        K / V form is faster -- and for a model with ``audio_ctx`` <= 300, where it is faster at every measured size
+        (AUTO_CACHED_MAX_AUDIO_CTX).  Unknown sizes (None) count as short / large.  WIPA_CROSS_ABSORB=0 turns "auto" off."""
         import os
 
         eligible = self.cross_absorbed_eligible
@@ -386,7 +449,8 @@ class Whisper:
             return False
         long_small = (batch is not None and new_tokens is not None and batch <= self.AUTO_CACHED_MAX_BATCH
                       and new_tokens >= self.AUTO_CACHED_MIN_NEW_TOKENS)
-        return not long_small
+        short_ctx = self._audio_ctx is not None and self._audio_ctx <= self.AUTO_CACHED_MAX_AUDIO_CTX
+        return not (long_small or short_ctx)
 
     @property
     def cross_splits(self) -> int:
@@ -408,7 +472,7 @@ class Whisper:
     # ---- packing -------------------------------------------------------------------
     def _cfg(self, fp8: bool = False, absorbed: bool = False) -> _lib.ModelCfg:
         d = self.dims
-        return _lib.ModelCfg(d.n_mels, d.n_audio_ctx, d.n_audio_state, d.n_audio_head, d.n_audio_layer, d.n_vocab,
+        return _lib.ModelCfg(d.n_mels, self.n_audio_ctx, d.n_audio_state, d.n_audio_head, d.n_audio_layer, d.n_vocab,
                              d.n_text_ctx, d.n_text_state, d.n_text_head, d.n_text_layer, dt_code(self.dtype),
                              int(self.f32_split and self.dtype == torch.float32), _lib.WIPA_FP8_E4M3 if fp8 else 0,
                              getattr(self, "_generation", 0), int(bool(self._fp8_enc)), int(bool(absorbed) and not fp8),
@@ -530,38 +594,50 @@ class Whisper:
 
     # ---- encoder -------------------------------------------------------------------
     def encode_padded(self, mel_padded: torch.Tensor, B: int) -> torch.Tensor:
-        """padded mel [B*3002+4, n_mels] in the model dtype -> features [B, 1500, d]."""
+        """padded mel [B*(2N+2)+4, n_mels] in the model dtype (N = n_audio_ctx: [B*3002+4, n_mels] by default) -> features [B, N, d]."""
         L = _lib.lib()
         pk = self.packed()
-        assert mel_padded.dtype == self.dtype and mel_padded.shape[0] >= padded_mel_rows(B)
+        assert mel_padded.dtype == self.dtype and mel_padded.shape[0] >= padded_mel_rows(B, self.n_audio_frames)
         with on_stream() as s:
             need = L.wipa_encoder_workspace_bytes(C.byref(pk["cfg"]), B)
             ws = self._enc_ws.get(stream_id())
             if ws is None or ws.numel() < need:
                 ws = torch.empty(need, dtype=torch.uint8, device=self.device)
                 self._enc_ws[stream_id()] = ws
-            out = torch.empty(B, self.dims.n_audio_ctx, self.dims.n_audio_state, dtype=self.dtype, device=self.device)
+            out = torch.empty(B, self.n_audio_ctx, self.dims.n_audio_state, dtype=self.dtype, device=self.device)
             _lib.check(L.wipa_encoder_forward(C.byref(pk["cfg"]), pk["enc_tab"], ptr(mel_padded), ptr(out), ptr(ws), ws.numel(),
                                               B, sptr(s)), "wipa_encoder_forward")
         return out
 
     def embed_audio(self, mel: torch.Tensor) -> torch.Tensor:
-        """mel [B, 3000, n_mels] (or [3000, n_mels]) -> [B, 1500, d]  (train_whisper_ipa.py:223)."""
+        """mel [B, 3000, n_mels] (or [3000, n_mels]) -> [B, 1500, d]  (train_whisper_ipa.py:223).  With ``audio_ctx`` = N: the
+        first 2N frames of a [B, 3000, n_mels] mel, or a mel [B, 2N, n_mels], -> [B, N, d]."""
         L = _lib.lib()
         if mel.dim() == 2:
             mel = mel[None]
         B = mel.shape[0]
-        assert mel.shape[1] == N_FRAMES and mel.shape[2] == self.dims.n_mels, mel.shape
+        if self._audio_ctx is None:
+            assert mel.shape[1] == N_FRAMES and mel.shape[2] == self.dims.n_mels, mel.shape
+            with on_stream() as s:
+                mel32 = mel.to(device=self.device, dtype=torch.float32).contiguous()
+                padded = torch.empty(padded_mel_rows(B), self.dims.n_mels, dtype=self.dtype, device=self.device)
+                _lib.check(L.wipa_mel_pad_cast(ptr(mel32), B, self.dims.n_mels, ptr(padded), dt_code(self.dtype), sptr(s)),
+                           "wipa_mel_pad_cast")
+            return self.encode_padded(padded, B)
+        F = self.n_audio_frames
+        if mel.shape[1] not in (N_FRAMES, F) or mel.shape[2] != self.dims.n_mels:
+            raise _lib.WipaError(f"embed_audio: a mel of shape {tuple(mel.shape)} given to a model with audio_ctx={self._audio_ctx}: "
+                                 f"expected [B, {N_FRAMES}, {self.dims.n_mels}] or [B, {F}, {self.dims.n_mels}]")
         with on_stream() as s:
             mel32 = mel.to(device=self.device, dtype=torch.float32).contiguous()
-            padded = torch.empty(padded_mel_rows(B), self.dims.n_mels, dtype=self.dtype, device=self.device)
-            _lib.check(L.wipa_mel_pad_cast(ptr(mel32), B, self.dims.n_mels, ptr(padded), dt_code(self.dtype), sptr(s)),
-                       "wipa_mel_pad_cast")
+            padded = torch.empty(padded_mel_rows(B, F), self.dims.n_mels, dtype=self.dtype, device=self.device)
+            _lib.check(L.wipa_mel_pad_cast_frames(ptr(mel32), mel32.shape[1] * mel32.shape[2], B, self.dims.n_mels, F, ptr(padded),
+                                                  dt_code(self.dtype), sptr(s)), "wipa_mel_pad_cast_frames")
         return self.encode_padded(padded, B)
 
     # ---- teacher-forced decoder ----------------------------------------------------
     def logits(self, tokens: torch.Tensor, audio_features: torch.Tensor, differentiable: Optional[bool] = None) -> torch.Tensor:
-        """tokens [B,T] int, features [B,1500,d] -> logits [B,T,V] f32 (train_whisper_ipa.py:232).
+        """tokens [B,T] int, features [B,1500,d] ([B,N,d] with ``audio_ctx`` = N) -> logits [B,T,V] f32 (train_whisper_ipa.py:232).
 
         By default the forward-only C++ pass over the packed tables -- also in torch's (default-on) grad mode: an evaluation
         caller outside ``torch.no_grad()`` gets no saved-activation forward and no grad_fn behind its back.
@@ -588,6 +664,9 @@ class Whisper:
         with on_stream() as s:
             tok = tokens.to(device=self.device, dtype=torch.int32).contiguous()
             feats = audio_features.to(device=self.device, dtype=self.dtype).contiguous()
+            if tuple(feats.shape) != (B, self.n_audio_ctx, self.dims.n_audio_state):
+                raise _lib.WipaError(f"logits: audio features of shape {tuple(feats.shape)}, expected "
+                                     f"{(B, self.n_audio_ctx, self.dims.n_audio_state)} (audio_ctx={self._audio_ctx!r})")
             need = L.wipa_decoder_logits_workspace_bytes(C.byref(pk["cfg"]), B, T)
             tf_ws = self._tf_ws.get(stream_id())
             if tf_ws is None or tf_ws.numel() < need:
