@@ -1089,6 +1089,25 @@ int wipa_embed_bwd(const int32_t* tokens_flat, const float* dx, int B, int T, in
  * Every batch, row and head stride must be a multiple of 4 floats (16-byte rows), or the call is refused. */
 int wipa_attention_bwd(const wipa_attn_desc* d, const float* out, const float* d_out, const float* lse, float* dq, float* dk,
                        float* dv, float* dvec, float qk_scale, wipa_stream_t s);
+/* The same call with a choice of arithmetic.  f32_split = 0: wipa_attention_bwd.  1: both kernels take their five matmuls (Q K^T, dO V^T,
+ * dS K, P^T dO, dS^T Q) on the bf16 MFMA over f32 operands split in registers, with the helper and the term selection of the encoder's
+ * split forward (wipa_flash_attn_enc_f32, f32_split): three terms per operand and six products where a product forms a score or a
+ * probability gradient, two terms and three products where it consumes P / dS; exponentials, D and accumulators stay f32.  Same strides,
+ * same refusals, deterministic.  For the encoder's Tq = Tk = n_audio_ctx self-attention in the fine-tune step (no reference counterpart). */
+int wipa_attention_bwd_ex(const wipa_attn_desc* d, const float* out, const float* d_out, const float* lse, float* dq, float* dk,
+                          float* dv, float* dvec, float qk_scale, int f32_split, wipa_stream_t s);
+/* Conv stem of the AudioEncoder in the fine-tune step (csrc/conv_bwd.hip; the reference freezes the encoder, train_whisper_ipa.py:187,
+ * so these have no counterpart there).  conv1 / conv2 run as wipa_gemm calls over overlapping rows that keep the PRE-activation values.
+ * wipa_conv_stem_gelu_pos: x[b][t][:] = gelu(z[b][t][:]) + pos[t][:] for z, x [B*N, d] contiguous, pos [>= N, d]; d a multiple of 4.
+ * wipa_conv2_dx: the input gradient of conv2 (k3, s2, p1) folded back onto the 2N conv1 frames and through conv1's GELU:
+ *   taps: dz2 W2 of position t of clip b, three blocks of d floats (tap 0, 1, 2) at taps + b*taps_clip_stride + t*3*d;
+ *   z1:   conv1's pre-activation of frame s of clip b at z1 + b*z1_clip_stride + s*d;  dz1 likewise with dz1_clip_stride;
+ *   dz1[s] = gelu'(z1[s]) * (s even: tap 1 of s/2;  s odd: tap 2 of (s-1)/2, then + tap 0 of (s+1)/2 when (s+1)/2 < N).
+ *   Rows 2N .. 2N + zero_rows - 1 of every clip of dz1 are written as zero.  No atomics, a fixed order: the bits of a clip do not
+ *   depend on the batch.  Nothing outside the N*3 tap rows and the 2N z1 rows of a clip is read.  Strides in floats, multiples of 4. */
+int wipa_conv_stem_gelu_pos(const float* z, const float* pos, float* x, int B, int N, int d, wipa_stream_t s);
+int wipa_conv2_dx(const float* taps, int64_t taps_clip_stride, const float* z1, int64_t z1_clip_stride, float* dz1,
+                  int64_t dz1_clip_stride, int B, int N, int d, int zero_rows, wipa_stream_t s);
 /* Flat multi-tensor optimiser step: per-tensor g *= min(1, max_norm/(|g|+1e-6)), then mlx-style AdamW
  * (no bias correction): m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p = p (1 - lr wd) - lr m / (sqrt(v)+eps).
  * Tensors live in flat f32 buffers; a chunk table (<= 4096 elements per chunk, never crossing tensors)

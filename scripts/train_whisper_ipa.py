@@ -110,12 +110,45 @@ class TrainingLogger:
         return False
 
 
-def freeze_encoder(model) -> None:
-    print("\nFreezing encoder parameters...")
-    model.encoder.freeze()
-    print("  ✓ Encoder frozen")
+def parse_train_encoder_layers(text):
+    """``--train-encoder-layers``: "all" or a block count (range checked against the model by the trainer)"""
+    if isinstance(text, int) or text == "all":
+        return text
+    try:
+        return int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--train-encoder-layers: {text!r} is neither a number of blocks nor 'all'")
+
+
+def freeze_encoder(model, train_encoder_layers=0) -> None:
+    """reference :181-204.  With ``train_encoder_layers`` the console says what is actually frozen: the trainer decides which
+    encoder tensors it owns (DecoderTrainer(train_encoder_layers=...)); the model's freeze() flag only feeds the parameter count."""
+    from whisper_ipa_amd.training import resolve_train_encoder_layers
+
+    L = model.dims.n_audio_layer
+    resolve_train_encoder_layers(train_encoder_layers, L)  # a bad value is refused here as the trainer refuses it, by name
+    if train_encoder_layers == 0:
+        print("\nFreezing encoder parameters...")
+        model.encoder.freeze()
+        print("  ✓ Encoder frozen")
+    elif train_encoder_layers == "all":
+        print("\nTraining the whole encoder...")
+        model.encoder.unfreeze()
+        print(f"  ✓ Encoder unfrozen (trainable): conv stem, all {L} blocks, ln_post; the sinusoidal positions are no parameter")
+    else:
+        print("\nFreezing the lower encoder...")
+        model.encoder.unfreeze()
+        print(f"  ✓ Encoder: conv stem and blocks 0..{L - train_encoder_layers - 1} frozen; blocks {L - train_encoder_layers}..{L - 1} "
+              f"and ln_post unfrozen (trainable)")
     model.decoder.unfreeze()
     print("  ✓ Decoder unfrozen (trainable)")
+    if train_encoder_layers not in (0, "all"):
+        from whisper_ipa_amd.training import flat_layout
+
+        trainable = sum(flat_layout(model.dims, train_encoder_layers)["sizes"])
+        total = count_parameters(model.parameters())
+        print(f"\nTrainable parameters: {trainable:,} / {total:,} ({100 * trainable / total:.1f}%)")
+        return
     trainable, total = count_parameters(model.trainable_parameters()), count_parameters(model.parameters())
     print(f"\nTrainable parameters: {trainable:,} / {total:,} ({100 * trainable / total:.1f}%)")
 
@@ -288,7 +321,11 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
           batch_size: int = 4, learning_rate: float = 1e-5, validate_every: int = 100, save_every: int = 500,
           test_run: bool = False, audio_root: str = "", seed: Optional[int] = None, exact_f32: bool = False,
           allow_byte_fallback: bool = False, cache_encoder_features: bool = True, feature_cache_clips: Optional[int] = None,
-          clip_scope: str = "reference", scoring: str = "device", audio_ctx: Optional[int] = None):
+          clip_scope: str = "reference", scoring: str = "device", audio_ctx: Optional[int] = None, train_encoder_layers=0):
+    """``train_encoder_layers``: 0 (the reference: encoder frozen), a number K of top encoder blocks to train with ln_post, or
+    "all" (every block, ln_post and the conv stem).  No counterpart in the reference.  Runs without the feature cache."""
+    if train_encoder_layers != 0 and feature_cache_clips is not None:
+        raise SystemExit("--train-encoder-layers with --feature-cache-clips: the feature cache holds the output of a FROZEN encoder")
     rank, world = _init_distributed()
     try:
         parallel.require_even_shards(batch_size, world)  # every rank gets clips; no mismatched collectives
@@ -304,7 +341,8 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
                      "validate_every": validate_every, "save_every": save_every, "test_run": test_run,
                      "world_size": world, "f32_products": "exact" if exact_f32 else "split",
                      "cache_encoder_features": bool(cache_encoder_features), "clip_scope": clip_scope, "scoring": scoring,
-                     "audio_ctx": audio_ctx}  # read back by the evaluation scripts (load_models.resolve_audio_ctx)
+                     "audio_ctx": audio_ctx,  # read back by the evaluation scripts (load_models.resolve_audio_ctx)
+                     "train_encoder_layers": train_encoder_layers}
         save_training_config(output_dir, args_dict, get_hardware_info())
     logger = TrainingLogger(output_dir) if main else None
     print(f"Loading model: {model_name}")
@@ -312,10 +350,11 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
     model = load_model(model_name, audio_ctx=audio_ctx)
     model.set_dtype(torch.float32)
     print(f"  ✓ Model loaded in {time.time() - t0:.1f}s" + (f" (audio_ctx {audio_ctx}: {audio_ctx * 0.02:.2f} s of context)" if audio_ctx else ""))
-    freeze_encoder(model)
+    freeze_encoder(model, train_encoder_layers)
     # mlx AdamW defaults (reference :513); the clip reaches what the reference's clip_grad_dict reaches (:287-303: dicts only,
     # the decoder.blocks list passes through) unless --clip-scope all
-    trainer = DecoderTrainer(model, lr=learning_rate, f32_split=not exact_f32, clip_scope=clip_scope)
+    trainer = DecoderTrainer(model, lr=learning_rate, f32_split=not exact_f32, clip_scope=clip_scope,
+                             train_encoder_layers=train_encoder_layers)
     n_mels = 128 if "large" in model_name else 80  # reference :517
     if model.dims.n_mels != n_mels:
         n_mels = model.dims.n_mels
@@ -328,7 +367,9 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
         train_dataset.data = train_dataset.data[:100]
         num_steps = min(num_steps, 100)
     rng = np.random.default_rng(seed) if seed is not None else np.random.default_rng(int(time.time()) if world == 1 else 0)
-    if cache_encoder_features:
+    if cache_encoder_features and trainer.trains_encoder:
+        print(f"  ✓ No encoder feature cache: train_encoder_layers={train_encoder_layers!r} moves the encoder every step")
+    elif cache_encoder_features:
         # The encoder is frozen (reference :187) yet recomputed every step (:223): its output is a pure function of the clip,
         # 4.6 MB per clip for whisper-small -- the whole training list fits the 288 GB HBM.  Bit-identical to recomputing.
         cache = trainer.enable_feature_cache(feature_cache_clips if feature_cache_clips is not None else
@@ -470,12 +511,17 @@ def main():
     p.add_argument("--audio-ctx", type=int, default=None,
                    help="run the model on its first N audio positions of 20 ms instead of all 1500 (whisper.cpp's --audio-ctx; 300 covers "
                         "6 s clips).  Recorded in training_config.json; clips longer than N * 20 ms are cut, with a warning.  Default: none")
+    p.add_argument("--train-encoder-layers", type=parse_train_encoder_layers, default=0, metavar="{0..L | all}",
+                   help="also train the last K encoder blocks and ln_post (K = 1..L), or the whole encoder with its conv stem (all).  "
+                        "Default 0: the encoder is frozen, as in the reference.  Recorded in training_config.json; runs without the "
+                        "encoder feature cache and cannot be combined with --feature-cache-clips")
     a = p.parse_args()
     train(model_name=a.model, train_data_path=a.train_data, test_data_path=a.test_data, output_dir=a.output_dir,
           num_steps=a.steps, batch_size=a.batch_size, learning_rate=a.lr, validate_every=a.validate_every,
           save_every=a.save_every, test_run=a.test_run, audio_root=a.audio_root, exact_f32=a.exact_f32,
           allow_byte_fallback=a.allow_byte_fallback, cache_encoder_features=not a.no_cache_encoder_features,
-          feature_cache_clips=a.feature_cache_clips, clip_scope=a.clip_scope, scoring=a.scoring, audio_ctx=a.audio_ctx)
+          feature_cache_clips=a.feature_cache_clips, clip_scope=a.clip_scope, scoring=a.scoring, audio_ctx=a.audio_ctx,
+          train_encoder_layers=a.train_encoder_layers)
 
 
 if __name__ == "__main__":

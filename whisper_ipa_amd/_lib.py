@@ -287,6 +287,10 @@ SIGNATURES = {
     "wipa_embed_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "wipa_attention_bwd": (c_int, [_P(AttnDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
                                    c_void_p]),
+    "wipa_conv_stem_gelu_pos": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "wipa_conv2_dx": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
+    "wipa_attention_bwd_ex": (c_int, [_P(AttnDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                      c_int, c_void_p]),
     "wipa_clip_adamw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                 c_void_p, c_void_p, c_void_p, c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                 C.c_double, c_void_p]),

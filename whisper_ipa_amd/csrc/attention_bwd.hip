@@ -400,10 +400,256 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_mfma_kernel(AttnBwdParams p) 
     }
 }
 
+
+// ---- split-product forms of the two MFMA kernels (f32_split: the encoder's 1500 x 1500 self-attention in the fine-tune step).  Same
+// tiling, staging, masks and output mapping; every matmul runs on the bf16 MFMA (16x16x32) over f32 operands split in registers by
+// the helpers of flash_enc_f32s_kernel (split_bf16x3 / split_bf16x2) with its term selection: the products that FORM a score or a
+// probability gradient (Q K^T, dO V^T) take three terms per operand and the six largest cross products, smallest first; the three
+// products that consume P / dS (P^T dO, dS^T Q, dS K) take two terms per operand and three products.  Exponentials, D_i and every
+// accumulator stay f32.  A bf16 K-step holds 32 k-values: lane (frow, fq) supplies the two 16-byte chunks the f32 kernels feed in
+// steps 2m and 2m + 1 (k = 32m + 4fq + e and 32m + 16 + 4fq + e) -- both operands of a product use the same assignment, which is all
+// the contraction needs.
+__device__ __forceinline__ void mma_split3(const bf16x8& ah, const bf16x8& am, const bf16x8& al, const bf16x8& bh, const bf16x8& bm,
+                                           const bf16x8& bl, f32x4& acc) {
+    Mma<__bf16>::run(al, bh, acc);  // smallest terms first
+    Mma<__bf16>::run(am, bm, acc);
+    Mma<__bf16>::run(ah, bl, acc);
+    Mma<__bf16>::run(am, bh, acc);
+    Mma<__bf16>::run(ah, bm, acc);
+    Mma<__bf16>::run(ah, bh, acc);
+}
+__device__ __forceinline__ void mma_split2(const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl, f32x4& acc) {
+    Mma<__bf16>::run(ah, bl, acc);
+    Mma<__bf16>::run(al, bh, acc);
+    Mma<__bf16>::run(ah, bh, acc);
+}
+
+__global__ __launch_bounds__(256) void attn_bwd_dkv_split_kernel(AttnBwdParams p) {
+    __shared__ __attribute__((aligned(16))) float Qs[64 * BQ];
+    __shared__ __attribute__((aligned(16))) float Gs[64 * BQ];
+    __shared__ __attribute__((aligned(16))) float QsT[64 * BQ];
+    __shared__ __attribute__((aligned(16))) float GsT[64 * BQ];
+    __shared__ float s_lse[64], s_d[64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int frow = lane & 15, fq = lane >> 4;
+    const int h = blockIdx.y, b = blockIdx.z;
+    const int k0 = blockIdx.x * 64;
+    const int key = k0 + 16 * wave + frow;
+    const int kc = min(key, p.Tk - 1);
+    bf16x8 kh[2], km[2], kl[2], vh[2], vm[2], vl[2];  // the wave's K / V rows, split once
+    {
+        const float* kp = p.k + b * p.k_bs + (int64_t)kc * p.k_rs + h * p.k_hs + 4 * fq;
+        const float* vp = p.v + b * p.v_bs + (int64_t)kc * p.v_rs + h * p.v_hs + 4 * fq;
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            split_bf16x3(*reinterpret_cast<const f32x4*>(kp + 32 * m), *reinterpret_cast<const f32x4*>(kp + 32 * m + 16), kh[m], km[m], kl[m]);
+            split_bf16x3(*reinterpret_cast<const f32x4*>(vp + 32 * m), *reinterpret_cast<const f32x4*>(vp + 32 * m + 16), vh[m], vm[m], vl[m]);
+        }
+    }
+    f32x4 dV[4], dK[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dV[j] = dK[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int off = p.Tk - p.Tq;
+    const int q_begin = p.causal ? max(0, k0 - off) : 0;
+    const int srow = tid >> 2, sseg = (tid & 3) * 16;
+    const float* qb = p.q + b * p.q_bs + h * p.q_hs;
+    const float* gb = p.d_o + b * p.o_bs + h * p.o_hs;
+    for (int q0 = (q_begin / 64) * 64; q0 < p.Tq; q0 += 64) {
+        __syncthreads();
+        {
+            const int qi = q0 + srow;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                f32x4 a = {0.f, 0.f, 0.f, 0.f}, g = {0.f, 0.f, 0.f, 0.f};
+                if (qi < p.Tq) {
+                    a = *reinterpret_cast<const f32x4*>(qb + (int64_t)qi * p.q_rs + sseg + 4 * c);
+                    g = *reinterpret_cast<const f32x4*>(gb + (int64_t)qi * p.o_rs + sseg + 4 * c);
+                }
+                *reinterpret_cast<f32x4*>(&Qs[srow * BQ + sseg + 4 * c]) = a;
+                *reinterpret_cast<f32x4*>(&Gs[srow * BQ + sseg + 4 * c]) = g;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    QsT[(sseg + 4 * c + e) * BQ + srow] = a[e];
+                    GsT[(sseg + 4 * c + e) * BQ + srow] = g[e];
+                }
+            }
+            if (tid < 64) {
+                const int qq = q0 + tid;
+                s_lse[tid] = qq < p.Tq ? p.lse[((int64_t)b * p.H + h) * p.Tq + qq] : 0.f;
+                s_d[tid] = qq < p.Tq ? p.dvec[((int64_t)b * p.H + h) * p.Tq + qq] : 0.f;
+            }
+        }
+        __syncthreads();
+        f32x4 S[4], dP[4];  // acc[i][e] <-> q = 16i + 4fq + e, the lane's key
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            S[i] = dP[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                const float* qr = &Qs[(16 * i + frow) * BQ + 32 * m + 4 * fq];
+                const float* gr = &Gs[(16 * i + frow) * BQ + 32 * m + 4 * fq];
+                bf16x8 ah, am, al;
+                split_bf16x3(*reinterpret_cast<const f32x4*>(qr), *reinterpret_cast<const f32x4*>(qr + 16), ah, am, al);
+                mma_split3(ah, am, al, kh[m], km[m], kl[m], S[i]);
+                split_bf16x3(*reinterpret_cast<const f32x4*>(gr), *reinterpret_cast<const f32x4*>(gr + 16), ah, am, al);
+                mma_split3(ah, am, al, vh[m], vm[m], vl[m], dP[i]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int ql = 16 * i + 4 * fq + e, qi = q0 + ql;
+                const bool vis = qi < p.Tq && key < p.Tk && (!p.causal || key <= qi + off);
+                const float pr = vis ? __expf(S[i][e] - s_lse[ql]) : 0.f;
+                S[i][e] = pr;
+                dP[i][e] = pr * (dP[i][e] - s_d[ql]);
+            }
+        // dV[key][d] += sum_q P[q][key] dO[q][d];  dK[key][d] += sum_q dS[q][key] Q[q][d]   (K-step m = queries 32m .. 32m + 31)
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            bf16x8 ph, pl, sh, sl;
+            split_bf16x2(S[2 * m], S[2 * m + 1], ph, pl);
+            split_bf16x2(dP[2 * m], dP[2 * m + 1], sh, sl);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float* gt = &GsT[(16 * j + frow) * BQ + 32 * m + 4 * fq];
+                const float* qt = &QsT[(16 * j + frow) * BQ + 32 * m + 4 * fq];
+                bf16x8 bh, bl;
+                split_bf16x2(*reinterpret_cast<const f32x4*>(gt), *reinterpret_cast<const f32x4*>(gt + 16), bh, bl);
+                mma_split2(ph, pl, bh, bl, dV[j]);
+                split_bf16x2(*reinterpret_cast<const f32x4*>(qt), *reinterpret_cast<const f32x4*>(qt + 16), bh, bl);
+                mma_split2(sh, sl, bh, bl, dK[j]);
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int kj = k0 + 16 * wave + 4 * fq + r;
+        if (kj < p.Tk) {
+            float* dkp = p.dk + b * p.k_bs + (int64_t)kj * p.k_rs + h * p.k_hs + frow;
+            float* dvp = p.dv + b * p.v_bs + (int64_t)kj * p.v_rs + h * p.v_hs + frow;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                dkp[16 * j] = dK[j][r] * p.qk_scale;
+                dvp[16 * j] = dV[j][r];
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void attn_bwd_dq_split_kernel(AttnBwdParams p) {
+    __shared__ __attribute__((aligned(16))) float Ks[64 * BQ];
+    __shared__ __attribute__((aligned(16))) float Vs[64 * BQ];
+    __shared__ __attribute__((aligned(16))) float KsT[64 * BQ];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int frow = lane & 15, fq = lane >> 4;
+    const int h = blockIdx.y, b = blockIdx.z;
+    const int q0 = blockIdx.x * 64;
+    const int qi = q0 + 16 * wave + frow;
+    const int qc = min(qi, p.Tq - 1);
+    bf16x8 qh[2], qm[2], ql[2], gh[2], gm[2], gl[2];  // the wave's q / dO rows, split once
+    float dsum = 0.f;
+    {
+        const float* qp = p.q + b * p.q_bs + (int64_t)qc * p.q_rs + h * p.q_hs + 4 * fq;
+        const float* gp = p.d_o + b * p.o_bs + (int64_t)qc * p.o_rs + h * p.o_hs + 4 * fq;
+        const float* op = p.o + b * p.o_bs + (int64_t)qc * p.o_rs + h * p.o_hs + 4 * fq;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {  // D_i in f32, in the order of the exact kernel
+            const f32x4 gg = *reinterpret_cast<const f32x4*>(gp + 16 * ks);
+            const f32x4 oo = *reinterpret_cast<const f32x4*>(op + 16 * ks);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dsum = fmaf(gg[e], oo[e], dsum);
+        }
+        dsum += __shfl_xor(dsum, 16, 64);
+        dsum += __shfl_xor(dsum, 32, 64);
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            split_bf16x3(*reinterpret_cast<const f32x4*>(qp + 32 * m), *reinterpret_cast<const f32x4*>(qp + 32 * m + 16), qh[m], qm[m], ql[m]);
+            split_bf16x3(*reinterpret_cast<const f32x4*>(gp + 32 * m), *reinterpret_cast<const f32x4*>(gp + 32 * m + 16), gh[m], gm[m], gl[m]);
+        }
+    }
+    const float lse = p.lse[((int64_t)b * p.H + h) * p.Tq + qc];
+    if (fq == 0 && qi < p.Tq) p.dvec[((int64_t)b * p.H + h) * p.Tq + qi] = dsum;
+    f32x4 dQ[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dQ[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int off = p.Tk - p.Tq;
+    const int q_last = min(q0 + 63, p.Tq - 1);
+    const int k_end = p.causal ? min(p.Tk, q_last + off + 1) : p.Tk;
+    const int srow = tid >> 2, sseg = (tid & 3) * 16;
+    const float* kb = p.k + b * p.k_bs + h * p.k_hs;
+    const float* vb = p.v + b * p.v_bs + h * p.v_hs;
+    for (int k0 = 0; k0 < k_end; k0 += 64) {
+        __syncthreads();
+        {
+            const int key = k0 + srow;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                f32x4 a = {0.f, 0.f, 0.f, 0.f}, bb = {0.f, 0.f, 0.f, 0.f};
+                if (key < p.Tk) {
+                    a = *reinterpret_cast<const f32x4*>(kb + (int64_t)key * p.k_rs + sseg + 4 * c);
+                    bb = *reinterpret_cast<const f32x4*>(vb + (int64_t)key * p.v_rs + sseg + 4 * c);
+                }
+                *reinterpret_cast<f32x4*>(&Ks[srow * BQ + sseg + 4 * c]) = a;
+                *reinterpret_cast<f32x4*>(&Vs[srow * BQ + sseg + 4 * c]) = bb;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) KsT[(sseg + 4 * c + e) * BQ + srow] = a[e];
+            }
+        }
+        __syncthreads();
+        f32x4 S[4], dP[4];  // acc[i][e] <-> key = k0 + 16 i + 4 fq + e, the lane's query
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            S[i] = dP[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                const float* kr = &Ks[(16 * i + frow) * BQ + 32 * m + 4 * fq];
+                const float* vr = &Vs[(16 * i + frow) * BQ + 32 * m + 4 * fq];
+                bf16x8 ah, am, al;
+                split_bf16x3(*reinterpret_cast<const f32x4*>(kr), *reinterpret_cast<const f32x4*>(kr + 16), ah, am, al);
+                mma_split3(ah, am, al, qh[m], qm[m], ql[m], S[i]);
+                split_bf16x3(*reinterpret_cast<const f32x4*>(vr), *reinterpret_cast<const f32x4*>(vr + 16), ah, am, al);
+                mma_split3(ah, am, al, gh[m], gm[m], gl[m], dP[i]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int key = k0 + 16 * i + 4 * fq + e;
+                const bool vis = qi < p.Tq && key < p.Tk && (!p.causal || key <= qi + off);
+                dP[i][e] = vis ? __expf(S[i][e] - lse) * (dP[i][e] - dsum) : 0.f;
+            }
+        // dQ[q][d] += sum_key dS[q][key] K[key][d]   (K-step m = keys 32m .. 32m + 31 of the tile)
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            bf16x8 sh, sl;
+            split_bf16x2(dP[2 * m], dP[2 * m + 1], sh, sl);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float* kt = &KsT[(16 * j + frow) * BQ + 32 * m + 4 * fq];
+                bf16x8 bh, bl;
+                split_bf16x2(*reinterpret_cast<const f32x4*>(kt), *reinterpret_cast<const f32x4*>(kt + 16), bh, bl);
+                mma_split2(sh, sl, bh, bl, dQ[j]);
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int qq = q0 + 16 * wave + 4 * fq + r;
+        if (qq < p.Tq) {
+            float* dqp = p.dq + b * p.q_bs + (int64_t)qq * p.q_rs + h * p.q_hs + frow;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) dqp[16 * j] = dQ[j][r] * p.qk_scale;
+        }
+    }
+}
+
 }  // namespace
 
-extern "C" int wipa_attention_bwd(const wipa_attn_desc* d, const float* out, const float* d_out, const float* lse, float* dq,
-                                  float* dk, float* dv, float* dvec, float qk_scale, wipa_stream_t stream) {
+extern "C" int wipa_attention_bwd_ex(const wipa_attn_desc* d, const float* out, const float* d_out, const float* lse, float* dq,
+                                     float* dk, float* dv, float* dvec, float qk_scale, int f32_split, wipa_stream_t stream) {
     WIPA_REQUIRE(d && d->q && d->k && d->v && out && d_out && lse && dq && dk && dv && dvec, "wipa_attention_bwd: null pointer");
     WIPA_REQUIRE(d->dtype == WIPA_F32, "wipa_attention_bwd: f32 only");
     WIPA_REQUIRE(d->B > 0 && d->H > 0 && d->Tq > 0 && d->Tk > 0, "wipa_attention_bwd: bad shape");
@@ -423,7 +669,10 @@ extern "C" int wipa_attention_bwd(const wipa_attn_desc* d, const float* out, con
     hipStream_t s = (hipStream_t)stream;
     // both halves on the f32 MFMA (64 queries / 64 keys per workgroup); WIPA_ATTN_BWD=valu keeps the VALU kernels for A/B runs
     static const bool valu = [] { const char* e = getenv("WIPA_ATTN_BWD"); return e && !strcmp(e, "valu"); }();
-    if (valu) {
+    if (f32_split) {  // split-bf16 products on the bf16 MFMA (the encoder's self-attention in the fine-tune step)
+        hipLaunchKernelGGL(attn_bwd_dq_split_kernel, dim3((d->Tq + 63) / 64, d->H, d->B), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(attn_bwd_dkv_split_kernel, dim3((d->Tk + 63) / 64, d->H, d->B), dim3(256), 0, s, p);
+    } else if (valu) {
         hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3((d->Tq + 15) / 16, d->H, d->B), dim3(256), 0, s, p);
         hipLaunchKernelGGL(attn_bwd_dkv_kernel, dim3((d->Tk + 15) / 16, d->H, d->B), dim3(256), 0, s, p);
     } else {
@@ -432,4 +681,9 @@ extern "C" int wipa_attention_bwd(const wipa_attn_desc* d, const float* out, con
     }
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;
+}
+
+extern "C" int wipa_attention_bwd(const wipa_attn_desc* d, const float* out, const float* d_out, const float* lse, float* dq,
+                                  float* dk, float* dv, float* dvec, float qk_scale, wipa_stream_t stream) {
+    return wipa_attention_bwd_ex(d, out, d_out, lse, dq, dk, dv, dvec, qk_scale, 0, stream);
 }

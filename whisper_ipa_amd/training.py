@@ -9,6 +9,10 @@ hand-written backward; every arithmetic step is a libwipa kernel (GEMMs through 
 operands transposed by wipa_transpose, flash-style attention backward, LayerNorm/GELU/CE backward,
 fused clip+AdamW over one flat parameter buffer).  torch only owns the buffers.
 
+``train_encoder_layers`` (no counterpart in the reference) adds the last K encoder blocks, or the whole encoder with its conv stem, to
+what is trained: an encoder forward that keeps its activations, the gradient of the encoder output out of the decoder's backward, and
+an encoder backward that shares the decoder's block halves; the stem's backward is csrc/conv_bwd.hip plus K-major GEMMs.
+
 Data parallel (one process per GPU): the (sum CE, valid count) pair is all-reduced BEFORE the
 backward so the normalisation is global, the flat gradient buffer is all-reduced in buckets AFTER
 it, and the per-tensor clip runs on the reduced gradients -- single-process semantics are kept.
@@ -147,10 +151,92 @@ def clip_reaches(name: str, scope: str = "reference") -> bool:
     return not any(part.isdigit() for part in name.split("."))
 
 
+def resolve_train_encoder_layers(value, n_audio_layer: int) -> Tuple[int, bool]:
+    """``train_encoder_layers`` -> (index of the first trained encoder block, whether the conv stem is trained).  0 gives
+    (n_audio_layer, False): no block; K gives the last K blocks; "all" every block and the stem."""
+    if value == "all":
+        return 0, True
+    if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value <= n_audio_layer:
+        raise _lib.WipaError(f"train_encoder_layers must be 0, 1..{n_audio_layer} or 'all', got {value!r}")
+    return n_audio_layer - value, False
+
+
+def parameter_shape(dims, name: str) -> Tuple[int, ...]:
+    """shape of the tensor ``name`` (mlx_whisper's flat key names; conv weights [out, 3, in]) from the dimensions alone"""
+    enc = name.startswith("encoder.")
+    d = dims.n_audio_state if enc else dims.n_text_state
+    leaf = name.split(".", 1)[1]
+    if leaf in ("conv1.weight", "conv2.weight"):
+        return (d, 3, dims.n_mels if leaf == "conv1.weight" else d)
+    if leaf == "token_embedding.weight":
+        return (dims.n_vocab, d)
+    if leaf == "positional_embedding":
+        return (dims.n_text_ctx, d)
+    if leaf.endswith("mlp1.weight"):
+        return (4 * d, d)
+    if leaf.endswith("mlp2.weight"):
+        return (d, 4 * d)
+    if leaf.endswith("mlp1.bias"):
+        return (4 * d,)
+    return (d, d) if leaf.endswith(".weight") and "ln" not in leaf.split(".")[-2] else (d,)
+
+
+def flat_layout(dims, train_encoder_layers=0) -> Dict:
+    """Layout of the trainer's flat buffers from the dimensions alone: ``names`` / ``offsets`` / ``sizes`` -- every ``decoder.*``
+    tensor in parameter_names order, exactly as a decoder-only trainer lays them out, then the trained ``encoder.*`` tensors in
+    parameter_names order (stem, blocks, ln_post) -- and ``segments``: (label, lo, hi) of the contiguous gradient segments in the
+    order the backward finishes them (and hands them to the SegmentReducer): decoder tail, decoder blocks from the last,
+    decoder head, encoder.ln_post, encoder blocks from the last, stem."""
+    first, stem = resolve_train_encoder_layers(train_encoder_layers, dims.n_audio_layer)
+    every = parameter_names(dims)
+    names = [n for n in every if n.startswith("decoder.")]
+
+    def trained(n: str) -> bool:
+        if not n.startswith("encoder."):
+            return False
+        part = n.split(".")
+        if part[1] == "blocks":
+            return int(part[2]) >= first
+        return part[1] == "ln_post" if not stem else True
+
+    if first < dims.n_audio_layer:
+        names += [n for n in every if trained(n)]
+    sizes = [_numel(parameter_shape(dims, n)) for n in names]
+    offsets, total = {}, 0
+    for n, sz in zip(names, sizes):
+        offsets[n] = total
+        total += sz
+
+    def span(prefix: str) -> Tuple[int, int]:
+        idx = [i for i, n in enumerate(names) if n.startswith(prefix)]
+        return (offsets[names[idx[0]]], offsets[names[idx[-1]]] + sizes[idx[-1]])
+
+    Lt = dims.n_text_layer
+    dec_blocks = [span(f"decoder.blocks.{l}.") for l in range(Lt)]
+    tail = span("decoder.ln.")
+    segments = [("decoder.tail", *tail)] + [(f"decoder.blocks.{l}", *dec_blocks[l]) for l in reversed(range(Lt))]
+    segments.append(("decoder.head", 0, dec_blocks[0][0]))
+    if first < dims.n_audio_layer:
+        segments.append(("encoder.ln_post", *span("encoder.ln_post.")))
+        segments += [(f"encoder.blocks.{l}", *span(f"encoder.blocks.{l}.")) for l in reversed(range(first, dims.n_audio_layer))]
+        if stem:
+            segments.append(("encoder.stem", *span("encoder.conv")))
+    return dict(names=names, sizes=sizes, offsets=offsets, total=total, segments=segments, first_block=first, stem=stem)
+
+
 class DecoderTrainer:
     def __init__(self, model: Whisper, lr: float = 1e-5, max_grad_norm: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.01, f32_split: Optional[bool] = None, clip_scope: str = "reference"):
-        """``f32_split`` (default: the model's setting -- on unless the model was built with f32_split=False): split-bf16 products in the large GEMMs of the step.
+                 weight_decay: float = 0.01, f32_split: Optional[bool] = None, clip_scope: str = "reference",
+                 train_encoder_layers=0):
+        """``train_encoder_layers``: 0 (default) trains the decoder alone, the reference's step (its encoder is frozen,
+        train_whisper_ipa.py:187).  K in 1..n_audio_layer also trains the last K encoder blocks and ``encoder.ln_post``;
+        ``"all"`` every block, ``ln_post`` and the conv stem (``conv1.*``, ``conv2.*``).  The sinusoidal positional table of
+        the encoder is never a parameter (as in mlx_whisper).  Such a trainer steps from the mel (train_step /
+        loss_and_grads_from_mel): an encoder forward that keeps its activations, the decoder's forward and backward, then the
+        encoder's backward.  The per-tensor clip is ``clip_reaches`` by name, as it stands: under ``clip_scope="reference"``
+        ``encoder.conv*`` and ``encoder.ln_post.*`` are clipped and ``encoder.blocks.N.*`` are not (the blocks are a list, like
+        the decoder's); ``"all"`` clips each tensor.  The reference has no counterpart of any non-zero value.
+        ``f32_split`` (default: the model's setting -- on unless the model was built with f32_split=False): split-bf16 products in the large GEMMs of the step.
         ``clip_scope``: which tensors the per-tensor clip reaches.  ``"reference"`` (default) is ``clip_grad_dict`` as the
         reference wrote it (train_whisper_ipa.py:287-303): it recurses through dict values only, so the ``decoder.blocks``
         LIST is passed through (:299-300) and only ``token_embedding.weight``, ``positional_embedding`` and ``ln.*`` are
@@ -166,8 +252,16 @@ class DecoderTrainer:
         self.L = _lib.lib()
         self.f32_split = model.f32_split if f32_split is None else bool(f32_split)
         d = model.dims
-        self.names = [n for n in parameter_names(d) if n.startswith("decoder.")]
+        self.train_encoder_layers = train_encoder_layers
+        self._enc_first, self._train_stem = resolve_train_encoder_layers(train_encoder_layers, d.n_audio_layer)
+        self.trains_encoder = self._enc_first < d.n_audio_layer
+        if self.trains_encoder and d.n_audio_state != d.n_text_state:
+            raise _lib.WipaError("DecoderTrainer: train_encoder_layers needs an encoder as wide as the decoder")
+        layout = flat_layout(d, train_encoder_layers)
+        self.names = layout["names"]  # decoder tensors first, as without encoder layers, then the trained encoder tensors
+        self.segments = layout["segments"]
         P = model.flat_parameters()
+        assert all(tuple(P[n].shape) == parameter_shape(d, n) for n in self.names)
         sizes = [P[n].numel() for n in self.names]
         assert all(s % 4 == 0 for s in sizes)
         offs, total = [], 0
@@ -182,7 +276,11 @@ class DecoderTrainer:
         starts = [offs[self.names.index(f"decoder.blocks.{l}.attn.query.weight")] for l in range(d.n_text_layer)]
         tail = offs[self.names.index("decoder.ln.weight")]
         self.block_ranges = [(starts[l], starts[l + 1] if l + 1 < d.n_text_layer else tail) for l in range(d.n_text_layer)]
-        self.head_range, self.tail_range = (0, starts[0]), (tail, total)
+        dec_total = sum(s for n, s in zip(self.names, sizes) if n.startswith("decoder."))  # == total without encoder layers
+        self.head_range, self.tail_range = (0, starts[0]), (tail, dec_total)
+        seg = {label: (lo, hi) for label, lo, hi in self.segments}
+        self.enc_block_ranges = {l: seg[f"encoder.blocks.{l}"] for l in range(self._enc_first, d.n_audio_layer)}
+        self.enc_ln_post_range, self.enc_stem_range = seg.get("encoder.ln_post"), seg.get("encoder.stem")
         with on_stream():
             dev = model.device
             self.flat_p = torch.empty(total, dtype=torch.float32, device=dev)
@@ -218,17 +316,31 @@ class DecoderTrainer:
         self._leaves = None     # autograd leaves over flat_p (leaves())
         model._trainer = self   # Whisper.logits differentiates through this trainer under torch.enable_grad()
 
+    # the encoder's self-attention backward of an f32_split trainer runs the split-product kernels (wipa_attention_bwd_ex); the
+    # A/B against the exact kernels at encoder shapes is in profiles/encoder_train_bench.txt
+    ENCODER_ATTN_BWD_SPLIT = True
+
     def feature_cache_capacity_default(self) -> int:
         return FrozenFeatureCache.clips_that_fit(self.model)
 
     def enable_feature_cache(self, max_clips: Optional[int] = None) -> "FrozenFeatureCache":
         """Keep the frozen encoder's output per clip in HBM (FrozenFeatureCache); ``max_clips`` defaults to what half of the
-        free device memory holds."""
+        free device memory holds.  Refused by a trainer that trains encoder layers: the features then change with every step."""
+        self._decoder_only("enable_feature_cache")
         n = FrozenFeatureCache.clips_that_fit(self.model) if max_clips is None else int(max_clips)
         self.feature_cache = FrozenFeatureCache(self.model, max(0, n))
         return self.feature_cache
 
+    def _decoder_only(self, what: str) -> None:
+        if self.trains_encoder:
+            raise _lib.WipaError(f"DecoderTrainer.{what} is decoder-only and this trainer has train_encoder_layers="
+                                 f"{self.train_encoder_layers!r}: step from the mel (train_step / loss_and_grads_from_mel)")
+
     # ---- views into the flat buffers
+    def w(self, name: str) -> torch.Tensor:
+        """the weight ``name`` as the step reads it: the flat buffer's view of a trained tensor, the model's own tensor of a frozen one"""
+        return self.p(name) if name in self.offsets else self.model._params[name]
+
     def p(self, name: str) -> torch.Tensor:
         o = self.offsets[name]
         return self.flat_p[o:o + _numel(self.shapes[name])].view(self.shapes[name])
@@ -337,6 +449,25 @@ class DecoderTrainer:
             _lib.check(self.L.wipa_colsum(ptr(dy), dy.stride(0), M, N, ptr(db), 0, ptr(self._colsum_ws), self._colsum_ws.numel(),
                                           sptr(s)), "wipa_colsum")
 
+    def _wgrad_rows(self, dy, x, ldx, Kc, n_out, n_in, dW):
+        """dW[n_out, n_in] = sum over the Kc rows r of dy[r, :n_out]^T x[r*ldx : r*ldx + n_in]: the weight gradient of a
+        convolution run as a GEMM over OVERLAPPING rows (ldx < n_in; conv1: ldx = n_mels, conv2: ldx = 2d), both operands read
+        K-major in place -- no im2col copy.  Kc a multiple of 32; rows of dy that stand for no output (the halo rows of each
+        clip, the padding up to Kc) must be zero, x readable and finite over all Kc rows."""
+        tiles = ((n_out + 127) // 128) * ((n_in + 127) // 128)
+        slices = max(1, min(16, 512 // tiles, (Kc // 32) // 8))
+        if slices > 1:
+            need = slices * n_out * n_in
+            if self._dw_slabs is None or self._dw_slabs.numel() < need:
+                self._dw_slabs = torch.empty(need, dtype=torch.float32, device=dy.device)
+            self._gemm(dy, x, self._dw_slabs, M=n_out, N=n_in, K=Kc, lda=dy.stride(0), ldw=ldx, ldc=n_in, k_slices=slices,
+                       slab_stride=n_out * n_in, a_trans=True, w_trans=True)
+            with on_stream() as s:
+                _lib.check(self.L.wipa_sum_slabs(ptr(self._dw_slabs), slices, n_out * n_in, ptr(dW), n_out * n_in, 0, sptr(s)),
+                           "wipa_sum_slabs")
+        else:
+            self._gemm(dy, x, dW, M=n_out, N=n_in, K=Kc, lda=dy.stride(0), ldw=ldx, ldc=n_in, a_trans=True, w_trans=True)
+
     def _ln(self, x, w, b):
         return ops.layernorm(x, w, b, out_dtype=torch.float32)
 
@@ -362,9 +493,15 @@ class DecoderTrainer:
             _lib.check(self.L.wipa_attention(C.byref(a), sptr(s)), "wipa_attention")
         return out, lse, a
 
-    def _attn_bwd(self, desc, out, d_out, lse, dq, dk, dv):
+    def _attn_bwd(self, desc, out, d_out, lse, dq, dk, dv, split: bool = False):
+        """``split``: the split-product kernels (wipa_attention_bwd_ex, f32_split = 1) -- the encoder's self-attention of a trainer
+        with f32_split; the decoder's calls keep the exact kernels"""
         with on_stream() as s:
             dvec = torch.empty_like(lse)
+            if split:
+                _lib.check(self.L.wipa_attention_bwd_ex(C.byref(desc), ptr(out), ptr(d_out), ptr(lse), ptr(dq), ptr(dk), ptr(dv),
+                                                        ptr(dvec), QK_SCALE, 1, sptr(s)), "wipa_attention_bwd_ex")
+                return
             _lib.check(self.L.wipa_attention_bwd(C.byref(desc), ptr(out), ptr(d_out), ptr(lse), ptr(dq), ptr(dk), ptr(dv),
                                                  ptr(dvec), QK_SCALE, sptr(s)), "wipa_attention_bwd")
 
@@ -426,10 +563,13 @@ class DecoderTrainer:
         ctx = dict(saved=saved, x_L=x_L, hf=hf, feats=feats, featsT=featsT, tok_in=tok_in, B=B, T=T)
         return logits, ctx
 
-    def _backward(self, ctx: Dict, dlogits: torch.Tensor, group=None) -> None:
+    def _backward(self, ctx: Dict, dlogits: torch.Tensor, group=None, d_feats: Optional[torch.Tensor] = None):
         """Reverse pass from ``dlogits`` [ceil32(B*T), ceil32(V)] f32 (zero in the padding; consumed) into self.flat_g: the
         gradient of every ``decoder.*`` tensor, tied embedding included.  Under DP every finished segment of the flat
-        buffer is all-reduced (SUM) asynchronously while the earlier blocks are still in their backward."""
+        buffer is all-reduced (SUM) asynchronously while the earlier blocks are still in their backward.
+        ``d_feats`` [B*N, d] (trainers that train encoder layers): receives the gradient of the encoder output, summed over the
+        decoder layers in the order the backward visits them; the SegmentReducer is then returned with its reductions still in
+        flight, for _encoder_backward to go on with."""
         m, dm, L = self.model, self.model.dims, self.L
         P, G = self.p, self.g
         saved, x_L, hf, feats, featsT, tok_in = ctx["saved"], ctx["x_L"], ctx["hf"], ctx["feats"], ctx["featsT"], ctx["tok_in"]
@@ -462,12 +602,7 @@ class DecoderTrainer:
             for l in reversed(range(dm.n_text_layer)):
                 pre = f"decoder.blocks.{l}"
                 S = saved[l]
-                # x_next = x_c + u W2^T + b2
-                du = self._lin_bwd(dx, M, d, S["u"], None, 4 * d, P(f"{pre}.mlp2.weight"), G(f"{pre}.mlp2.weight"), G(f"{pre}.mlp2.bias"))
-                dz = torch.empty_like(du)
-                _lib.check(L.wipa_gelu_bwd(ptr(S["z"]), ptr(du), ptr(dz), dz.numel(), sptr(s)), "wipa_gelu_bwd")
-                dh3 = self._lin_bwd(dz, M, 4 * d, S["h3"], None, d, P(f"{pre}.mlp1.weight"), G(f"{pre}.mlp1.weight"), G(f"{pre}.mlp1.bias"))
-                self._ln_bwd(S["x_c"], dh3, P(f"{pre}.mlp_ln.weight"), dx, True, G(f"{pre}.mlp_ln.weight"), G(f"{pre}.mlp_ln.bias"), M, d)
+                self._mlp_bwd(pre, S, dx, M, d)
                 # x_c = x_b + c Wco^T + bco
                 dc = self._lin_bwd(dx, M, d, S["c"], None, d, P(f"{pre}.cross_attn.out.weight"), G(f"{pre}.cross_attn.out.weight"),
                                    G(f"{pre}.cross_attn.out.bias"))
@@ -475,29 +610,20 @@ class DecoderTrainer:
                 dkv = torch.empty(B * Ta, 2 * d, dtype=torch.float32, device=dev)  # d(key) | d(value), strides of the forward's kv
                 dkc, dvc = dkv[:, :d], dkv[:, d:]
                 self._attn_bwd(S["desc2"], S["c"], dc, S["lse2"], dqc, dkc, dvc)
-                # one weight-gradient GEMM for the [2d, d] pair (no input gradient: the encoder is frozen); value bias apart
-                self._lin_bwd(dkv, B * Ta, 2 * d, feats, featsT, d, self._kv_pair(self.flat_p, pre), self._kv_pair(self.flat_g, pre),
-                              None, need_dx=False)
+                if d_feats is None:
+                    # one weight-gradient GEMM for the [2d, d] pair (no input gradient: the encoder is frozen); value bias apart
+                    self._lin_bwd(dkv, B * Ta, 2 * d, feats, featsT, d, self._kv_pair(self.flat_p, pre), self._kv_pair(self.flat_g, pre),
+                                  None, need_dx=False)
+                else:  # ... and the pair's input gradient, which is the encoder output's: the last decoder layer writes it, the others add
+                    self._lin_bwd(dkv, B * Ta, 2 * d, feats, featsT, d, self._kv_pair(self.flat_p, pre), self._kv_pair(self.flat_g, pre),
+                                  None, dx=d_feats, accumulate_dx=(l != dm.n_text_layer - 1))
                 self._colsum(dvc, B * Ta, d, G(f"{pre}.cross_attn.value.bias"))
                 del dkv, dkc, dvc
                 dh2 = self._lin_bwd(dqc, M, d, S["h2"], None, d, P(f"{pre}.cross_attn.query.weight"), G(f"{pre}.cross_attn.query.weight"),
                                     G(f"{pre}.cross_attn.query.bias"))
                 self._ln_bwd(S["x_b"], dh2, P(f"{pre}.cross_attn_ln.weight"), dx, True, G(f"{pre}.cross_attn_ln.weight"),
                              G(f"{pre}.cross_attn_ln.bias"), M, d)
-                # x_b = x_a + a Wo^T + bo
-                da = self._lin_bwd(dx, M, d, S["a"], None, d, P(f"{pre}.attn.out.weight"), G(f"{pre}.attn.out.weight"), G(f"{pre}.attn.out.bias"))
-                dq = torch.empty(M, d, dtype=torch.float32, device=dev)
-                dk = torch.empty(M, d, dtype=torch.float32, device=dev)
-                dv = torch.empty(M, d, dtype=torch.float32, device=dev)
-                self._attn_bwd(S["desc1"], S["a"], da, S["lse1"], dq, dk, dv)
-                h1T = None if M % 32 == 0 else self._transpose(S["h1"], M, d, Mp)  # shared by the three projections
-                dh1 = self._lin_bwd(dq, M, d, S["h1"], h1T, d, P(f"{pre}.attn.query.weight"), G(f"{pre}.attn.query.weight"),
-                                    G(f"{pre}.attn.query.bias"))
-                self._lin_bwd(dk, M, d, S["h1"], h1T, d, P(f"{pre}.attn.key.weight"), G(f"{pre}.attn.key.weight"), None, dx=dh1,
-                              accumulate_dx=True)
-                self._lin_bwd(dv, M, d, S["h1"], h1T, d, P(f"{pre}.attn.value.weight"), G(f"{pre}.attn.value.weight"),
-                              G(f"{pre}.attn.value.bias"), dx=dh1, accumulate_dx=True)
-                self._ln_bwd(S["x_a"], dh1, P(f"{pre}.attn_ln.weight"), dx, True, G(f"{pre}.attn_ln.weight"), G(f"{pre}.attn_ln.bias"), M, d)
+                self._self_attn_bwd(pre, S, dx, B, M, Mp, d)
                 saved[l] = None
                 reduce_segment(self.block_ranges[l])
             _lib.check(L.wipa_embed_bwd(ptr(tok_in), ptr(dx), B, T, d, ptr(G("decoder.token_embedding.weight")),
@@ -505,20 +631,198 @@ class DecoderTrainer:
             if T < dm.n_text_ctx:
                 G("decoder.positional_embedding")[T:].zero_()
             reduce_segment(self.head_range)
+            if d_feats is not None:
+                return reducer
             # the time the compute stream stalls here is the all-reduce time the backward did NOT hide
             self._ar_events = None
-            if reducer.pending:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(s)
-                reducer.wait()
-                e1.record(s)
-                self._ar_events = (e0, e1)
+            self._join_reductions(reducer, s)
+        return None
+
+    def _join_reductions(self, reducer, s) -> None:
+        if reducer.pending:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(s)
+            reducer.wait()
+            e1.record(s)
+            self._ar_events = (e0, e1)
+
+    def _mlp_bwd(self, pre: str, S: Dict, dx: torch.Tensor, M: int, d: int) -> None:
+        """the MLP half of block ``pre`` (decoder or encoder), x_next = x_c + u W2^T + b2: its parameter gradients, and dx += the
+        gradient through mlp_ln"""
+        P, G = self.w, self.g
+        du = self._lin_bwd(dx, M, d, S["u"], None, 4 * d, P(f"{pre}.mlp2.weight"), G(f"{pre}.mlp2.weight"), G(f"{pre}.mlp2.bias"))
+        dz = torch.empty_like(du)
+        with on_stream() as s:
+            _lib.check(self.L.wipa_gelu_bwd(ptr(S["z"]), ptr(du), ptr(dz), dz.numel(), sptr(s)), "wipa_gelu_bwd")
+        dh3 = self._lin_bwd(dz, M, 4 * d, S["h3"], None, d, P(f"{pre}.mlp1.weight"), G(f"{pre}.mlp1.weight"), G(f"{pre}.mlp1.bias"))
+        self._ln_bwd(S["x_c"], dh3, P(f"{pre}.mlp_ln.weight"), dx, True, G(f"{pre}.mlp_ln.weight"), G(f"{pre}.mlp_ln.bias"), M, d)
+
+    def _self_attn_bwd(self, pre: str, S: Dict, dx: torch.Tensor, B: int, M: int, Mp: int, d: int, split: bool = False) -> None:
+        """the self-attention half of block ``pre`` (decoder or encoder), x_b = x_a + a Wo^T + bo: its parameter gradients, and
+        dx += the gradient through attn_ln"""
+        P, G = self.w, self.g
+        dev = dx.device
+        da = self._lin_bwd(dx, M, d, S["a"], None, d, P(f"{pre}.attn.out.weight"), G(f"{pre}.attn.out.weight"), G(f"{pre}.attn.out.bias"))
+        dq = torch.empty(M, d, dtype=torch.float32, device=dev)
+        dk = torch.empty(M, d, dtype=torch.float32, device=dev)
+        dv = torch.empty(M, d, dtype=torch.float32, device=dev)
+        self._attn_bwd(S["desc1"], S["a"], da, S["lse1"], dq, dk, dv, split)
+        h1T = None if M % 32 == 0 else self._transpose(S["h1"], M, d, Mp)  # shared by the three projections
+        dh1 = self._lin_bwd(dq, M, d, S["h1"], h1T, d, P(f"{pre}.attn.query.weight"), G(f"{pre}.attn.query.weight"),
+                            G(f"{pre}.attn.query.bias"))
+        self._lin_bwd(dk, M, d, S["h1"], h1T, d, P(f"{pre}.attn.key.weight"), G(f"{pre}.attn.key.weight"), None, dx=dh1,
+                      accumulate_dx=True)
+        self._lin_bwd(dv, M, d, S["h1"], h1T, d, P(f"{pre}.attn.value.weight"), G(f"{pre}.attn.value.weight"),
+                      G(f"{pre}.attn.value.bias"), dx=dh1, accumulate_dx=True)
+        self._ln_bwd(S["x_a"], dh1, P(f"{pre}.attn_ln.weight"), dx, True, G(f"{pre}.attn_ln.weight"), G(f"{pre}.attn_ln.bias"), M, d)
+
+    # ---- encoder: training forward (keeps activations) + backward -----------------------------
+    def _encoder_forward(self, mel: torch.Tensor):
+        """AudioEncoder.__call__ in f32 on a mel [B, 3000, n_mels] (or [B, 2N, n_mels] with ``model.audio_ctx`` = N), composed
+        from the per-kernel entry points like the decoder's _forward: conv1 and conv2 as GEMMs over overlapping rows of the
+        padded layouts wipa_encoder_forward uses (their PRE-GELU values kept), then per block LayerNorm, q, k, v, non-causal
+        wipa_attention (log-sum-exp saved), out + residual, LayerNorm, mlp1, GELU, mlp2 + residual, then ln_post.  Blocks below
+        the first trained one are not saved (their buffers go back to the allocator as the walk leaves them), and the stem's
+        only under "all".  Returns (features [B, N, d], what _encoder_backward needs)."""
+        m, dm, L = self.model, self.model.dims, self.L
+        W = self.w
+        d, H, N, n_mels = dm.n_audio_state, dm.n_audio_head, m.n_audio_ctx, dm.n_mels
+        if mel.dim() == 2:
+            mel = mel[None]
+        B, F, R = mel.shape[0], 2 * N, 2 * N + 2  # R rows per clip in the padded layouts: a zero halo row either side
+        full = 2 * dm.n_audio_ctx
+        if mel.shape[1] not in (full, F) or mel.shape[2] != n_mels:
+            raise _lib.WipaError(f"DecoderTrainer: a mel of shape {tuple(mel.shape)}, expected [B, {full}, {n_mels}]"
+                                 + (f" or [B, {F}, {n_mels}] (audio_ctx={m.audio_ctx})" if F != full else ""))
+        M, M1, M2 = B * N, B * R, B * (N + 1)
+        Kc1, Kc2 = _ceil(M1, 32), _ceil(M2, 32)  # contraction lengths of the two weight-gradient GEMMs (_stem_backward)
+        K1 = _ceil(3 * n_mels, 32)
+        with on_stream() as s:
+            dev = m.device
+            mel32 = mel.to(device=dev, dtype=torch.float32).contiguous()
+            # frame t of clip b at row b*R + t + 1; rows past B*R + 4 exist (as zeros) for the weight gradient's padded contraction
+            padded = torch.zeros(max(M1 + 4, Kc1 + 3), n_mels, dtype=torch.float32, device=dev)
+            _lib.check(L.wipa_mel_pad_cast_frames(ptr(mel32), mel32.shape[1] * n_mels, B, n_mels, F, ptr(padded), 0, sptr(s)),
+                       "wipa_mel_pad_cast_frames")
+            w1 = torch.zeros(d, K1, dtype=torch.float32, device=dev)  # K padded to whole 32-float steps with zero columns
+            w1[:, : 3 * n_mels].copy_(W("encoder.conv1.weight").reshape(d, 3 * n_mels))
+            # conv1 (k3, p1), pre-activation: GEMM row g = b*R + t reads the padded rows g..g+2 and lands at row g + 1; the two
+            # dead rows of each clip are written as zero -- gelu(0) = 0, so one GELU over the buffer leaves conv2's halos zero
+            z1 = torch.zeros(max(M1 + 4, 2 * Kc2 + 2), d, dtype=torch.float32, device=dev)
+            self._gemm(padded, w1, z1, M=M1, N=d, K=K1, lda=n_mels, ldw=K1, ldc=d, bias=W("encoder.conv1.bias"), rg_in=R, rg_valid=F,
+                       rg_stride=R * d, c_offset=d, zero_invalid_rows=True)
+            c1 = torch.empty_like(z1)
+            _lib.check(L.wipa_gelu(ptr(z1), ptr(c1), z1.numel(), sptr(s)), "wipa_gelu")
+            # conv2 (k3, s2, p1), pre-activation: row b*(N+1) + t reads c1 rows 2t..2t+2 of clip b (row N of each group is dead)
+            z2 = torch.empty(M, d, dtype=torch.float32, device=dev)
+            self._gemm(c1, W("encoder.conv2.weight").reshape(d, 3 * d), z2, M=M2, N=d, K=3 * d, lda=2 * d, ldw=3 * d, ldc=d,
+                       bias=W("encoder.conv2.bias"), rg_in=N + 1, rg_valid=N, rg_stride=N * d)
+            x = torch.empty(M, d, dtype=torch.float32, device=dev)
+            _lib.check(L.wipa_conv_stem_gelu_pos(ptr(z2), ptr(m._enc_pos), ptr(x), B, N, d, sptr(s)), "wipa_conv_stem_gelu_pos")
+            stem = dict(padded=padded, z1=z1, c1=c1, z2=z2) if self._train_stem else None
+            del padded, z1, c1, z2, w1
+            saved = {}
+            for l in range(dm.n_audio_layer):
+                pre = f"encoder.blocks.{l}"
+                S = {"x_a": x}
+                S["h1"] = self._ln(x, W(f"{pre}.attn_ln.weight"), W(f"{pre}.attn_ln.bias"))
+                S["q"] = self._lin(S["h1"], M, d, W(f"{pre}.attn.query.weight"), d, W(f"{pre}.attn.query.bias"), QK_SCALE)
+                S["k"] = self._lin(S["h1"], M, d, W(f"{pre}.attn.key.weight"), d, None, QK_SCALE)
+                S["v"] = self._lin(S["h1"], M, d, W(f"{pre}.attn.value.weight"), d, W(f"{pre}.attn.value.bias"))
+                S["a"], S["lse1"], S["desc1"] = self._attn(S["q"], S["k"], S["v"], B, H, N, N, False, N)
+                S["x_c"] = self._lin(S["a"], M, d, W(f"{pre}.attn.out.weight"), d, W(f"{pre}.attn.out.bias"), residual=x)
+                S["h3"] = self._ln(S["x_c"], W(f"{pre}.mlp_ln.weight"), W(f"{pre}.mlp_ln.bias"))
+                S["z"] = self._lin(S["h3"], M, d, W(f"{pre}.mlp1.weight"), 4 * d, W(f"{pre}.mlp1.bias"))
+                S["u"] = torch.empty_like(S["z"])
+                _lib.check(L.wipa_gelu(ptr(S["z"]), ptr(S["u"]), S["z"].numel(), sptr(s)), "wipa_gelu")
+                x = self._lin(S["u"], M, 4 * d, W(f"{pre}.mlp2.weight"), d, W(f"{pre}.mlp2.bias"), residual=S["x_c"])
+                if l >= self._enc_first:
+                    saved[l] = S
+                del S
+            feats = self._ln(x, W("encoder.ln_post.weight"), W("encoder.ln_post.bias"))
+        return feats.view(B, N, d), dict(saved=saved, x_L=x, stem=stem, B=B, N=N)
+
+    def _encoder_backward(self, ectx: Dict, d_feats: torch.Tensor, reducer) -> None:
+        """From ``d_feats`` [B*N, d], the gradient of the encoder output (consumed), into self.flat_g: ln_post, the trained
+        blocks from the last (the halves the decoder's blocks share: _mlp_bwd, _self_attn_bwd), then the stem under "all".  The
+        walk stops after the first trained block.  Every finished segment goes to ``reducer`` like the decoder's."""
+        dm = self.model.dims
+        P, G = self.w, self.g
+        saved, x_L, B, N = ectx["saved"], ectx["x_L"], ectx["B"], ectx["N"]
+        d = dm.n_audio_state
+        M, Mp = B * N, _ceil(B * N, 32)
+        with on_stream():
+            dx = torch.empty(M, d, dtype=torch.float32, device=d_feats.device)
+            self._ln_bwd(x_L, d_feats, P("encoder.ln_post.weight"), dx, False, G("encoder.ln_post.weight"), G("encoder.ln_post.bias"), M, d)
+            reducer.reduce(*self.enc_ln_post_range)
+            for l in reversed(range(self._enc_first, dm.n_audio_layer)):
+                pre = f"encoder.blocks.{l}"
+                S = saved[l]
+                self._mlp_bwd(pre, S, dx, M, d)
+                self._self_attn_bwd(pre, S, dx, B, M, Mp, d, split=self.f32_split and self.ENCODER_ATTN_BWD_SPLIT)
+                saved[l] = None
+                del S
+                reducer.reduce(*self.enc_block_ranges[l])
+            if self._train_stem:
+                self._stem_backward(ectx["stem"], dx, B, N)
+                reducer.reduce(*self.enc_stem_range)
+
+    def _stem_backward(self, stem: Dict, dx: torch.Tensor, B: int, N: int) -> torch.Tensor:
+        """conv2 and conv1 from ``dx`` [B*N, d], the gradient of the stem's output x = gelu(z2) + positional table (the table is
+        no parameter).  Weight gradients: K-major GEMMs over the overlapping-row views of the padded inputs (_wgrad_rows), the
+        dead rows of each clip carrying zero gradient; biases: wipa_colsum; conv2's input gradient: dz2 W2 as three taps per
+        position, folded onto the 2N conv1 frames and through conv1's GELU by wipa_conv2_dx.  conv1 needs no input gradient.
+        Returns dz1, the gradient of conv1's pre-activation in the rows of conv1's GEMM (frame s of clip b at row b*(2N + 2) + s)."""
+        dm, L = self.model.dims, self.L
+        P, G = self.w, self.g
+        d, n_mels = dm.n_audio_state, dm.n_mels
+        R = 2 * N + 2
+        M, M1, M2 = B * N, B * R, B * (N + 1)
+        Kc1, Kc2 = _ceil(M1, 32), _ceil(M2, 32)
+        padded, z1, c1, z2 = stem["padded"], stem["z1"], stem["c1"], stem["z2"]
+        with on_stream() as s:
+            dev = dx.device
+            dz2 = torch.empty(M, d, dtype=torch.float32, device=dev)
+            _lib.check(L.wipa_gelu_bwd(ptr(z2), ptr(dx), ptr(dz2), dz2.numel(), sptr(s)), "wipa_gelu_bwd")
+            self._colsum(dz2, M, d, G("encoder.conv2.bias"))
+            # the rows of conv2's GEMM: N + 1 per clip, the last one dead (zero), zero rows up to the padded contraction length
+            dz2p = torch.zeros(Kc2, d, dtype=torch.float32, device=dev)
+            dz2p[:M2].view(B, N + 1, d)[:, :N].copy_(dz2.view(B, N, d))
+            self._wgrad_rows(dz2p, c1, 2 * d, Kc2, d, 3 * d, G("encoder.conv2.weight").view(d, 3 * d))
+            taps = torch.empty(M2, 3 * d, dtype=torch.float32, device=dev)
+            self._mm(dz2p, P("encoder.conv2.weight").view(d, 3 * d), taps, M2, 3 * d, d, d, 3 * d, w_trans=True)
+            # the rows of conv1's GEMM: R per clip (2N frames, two dead rows written as zero by the kernel), zero rows up to Kc1
+            dz1 = torch.empty(Kc1, d, dtype=torch.float32, device=dev)
+            if Kc1 > M1:
+                dz1[M1:].zero_()
+            _lib.check(L.wipa_conv2_dx(ptr(taps), (N + 1) * 3 * d, ptr(z1[1:]), R * d, ptr(dz1), R * d, B, N, d, 2, sptr(s)),
+                       "wipa_conv2_dx")
+            self._colsum(dz1, M1, d, G("encoder.conv1.bias"))
+            self._wgrad_rows(dz1, padded, n_mels, Kc1, d, 3 * n_mels, G("encoder.conv1.weight").view(d, 3 * n_mels))
+        return dz1
+
+    def loss_and_grads_from_mel(self, mel: torch.Tensor, tokens: torch.Tensor, eot: int, group=None):
+        """The full path of a trainer that trains encoder layers: mel [B, 3000, n_mels] (or [B, 2N, n_mels] with
+        ``model.audio_ctx`` = N), tokens [B, T+1] int.  Encoder forward that keeps its activations, decoder forward and backward
+        (which also yields the gradient of the encoder output), encoder backward.  Fills every segment of self.flat_g like
+        loss_and_grads; returns (loss, sum_ce, n_valid).  With train_encoder_layers=0 it is embed_audio + loss_and_grads."""
+        if not self.trains_encoder:
+            return self.loss_and_grads(self.model.embed_audio(mel), tokens, eot, group)
+        feats, ectx = self._encoder_forward(mel)
+        self.last_features = feats  # the encoder output of this step (before the update)
+        return self._loss_and_grads(feats, tokens, eot, group, ectx)
 
     def loss_and_grads(self, audio_features: torch.Tensor, tokens: torch.Tensor, eot: int, group=None):
         """features [B, 1500, d] f32 (encoder output, no gradient), tokens [B, T+1] int.
         Fills self.flat_g (un-clipped, already divided by the global valid count and, under DP,
         all-reduced).  Returns (loss, sum_ce, n_valid) as device scalars.  The fused path of the fine-tune step: masked CE and
-        its gradient run in place on the logits (wipa_masked_ce / _bwd), nothing of size [B*T, V] is kept twice."""
+        its gradient run in place on the logits (wipa_masked_ce / _bwd), nothing of size [B*T, V] is kept twice.
+        Features carry no gradient, so only the decoder segments could be filled: a trainer that trains encoder layers
+        refuses the call (loss_and_grads_from_mel is its path)."""
+        self._decoder_only("loss_and_grads(audio_features, ...)")
+        return self._loss_and_grads(audio_features, tokens, eot, group, None)
+
+    def _loss_and_grads(self, audio_features: torch.Tensor, tokens: torch.Tensor, eot: int, group, ectx: Optional[Dict]):
         m, dm, L = self.model, self.model.dims, self.L
         B, T1 = tokens.shape
         T = T1 - 1
@@ -538,7 +842,15 @@ class DecoderTrainer:
             loss = sum_ce / torch.clamp(n_valid, min=1.0)
             _lib.check(L.wipa_masked_ce_bwd(ptr(logits), Vp, ptr(tok), T1, B, T, V, ptr(row_buf[M:]), ptr(count), sptr(s)),
                        "wipa_masked_ce_bwd")
-            self._backward(ctx, logits, group)
+            if ectx is None:
+                self._backward(ctx, logits, group)
+            else:
+                d_feats = torch.empty_like(ctx["feats"])
+                reducer = self._backward(ctx, logits, group, d_feats=d_feats)
+                del ctx, logits
+                self._encoder_backward(ectx, d_feats, reducer)
+                self._ar_events = None
+                self._join_reductions(reducer, s)
         return loss, sum_ce, n_valid
 
     # ---- torch.autograd surface: Whisper.logits differentiable w.r.t. the decoder tensors (train_whisper_ipa.py:232,284) ----
@@ -546,6 +858,7 @@ class DecoderTrainer:
         """name -> leaf tensor (requires_grad) that VIEWS the flat parameter buffer: what ``Whisper.logits`` differentiates
         against under torch.enable_grad().  ``.grad`` is filled by ``loss.backward()``; apply_update() reads self.flat_g, so a
         custom training loop copies / accumulates the leaves' gradients there (value_and_grad in scripts/train_whisper_ipa.py)."""
+        self._decoder_only("leaves")
         if self._leaves is None:
             self._leaves = {n: self.p(n).detach().requires_grad_(True) for n in self.names}
         return self._leaves
@@ -559,6 +872,7 @@ class DecoderTrainer:
         gradient as the leaves' .grad (one more copy of the decoder's size); it reduces over no process group."""
         from . import parallel
 
+        self._decoder_only("differentiable_logits")
         if parallel.world()[1] != 1:
             raise _lib.WipaError("differentiable_logits is single-process (its backward runs without the data-parallel group); "
                                  "use DecoderTrainer.train_step / loss_and_grads(group=...) under torch.distributed")
@@ -584,6 +898,10 @@ class DecoderTrainer:
                                               ptr(self.ch_len), ptr(self.ch_seg), ptr(self.seg_first), self.n_chunks, self.n_seg,
                                               ptr(self.partial), ptr(self.coef), ptr(self.norms), ptr(self.seg_clip), self.max_grad_norm, self.lr,
                                               self.b1, self.b2, self.eps, self.wd, sptr(s)), "wipa_clip_adamw")
+        if self.trains_encoder:
+            # encoder tensors moved: the packed encoder tables die with _invalidate() below, and whatever is a function of the
+            # encoder weights (a FrozenFeatureCache, cached features) watches this count
+            self.model._enc_generation += 1
         self.model._invalidate()  # fused inference tables are rebuilt lazily from the updated weights
         self.step_count += 1
 
@@ -592,6 +910,11 @@ class DecoderTrainer:
         Returns (loss as a device scalar, dict of clipped gradients).
         ``clip_keys`` (one hashable int per clip, e.g. the dataset index) with an enabled feature cache: ``mel`` holds only the
         clips ``feature_cache.missing(clip_keys)`` marks (or is None when every clip is cached); the others come from HBM."""
+        if self.trains_encoder:
+            # encoder forward that saves activations, decoder forward / backward, encoder backward (no feature cache: refused)
+            loss, _, _ = self.loss_and_grads_from_mel(mel, tokens, eot, group)
+            self.apply_update()
+            return loss, self.grads()
         if clip_keys is not None and self.feature_cache is not None:
             feats = self.feature_cache.assemble(clip_keys, mel)
         else:
@@ -599,6 +922,9 @@ class DecoderTrainer:
         loss, _, _ = self.loss_and_grads(feats, tokens, eot, group)
         self.apply_update()
         return loss, self.grads()
+
+
+FineTuneTrainer = DecoderTrainer  # the name for what it has become; the class keeps its own
 
 
 class _DecoderLogits(torch.autograd.Function):
