@@ -111,6 +111,36 @@ int wipa_logmel_frames(const float* audio, int batch, int n_mels, const void* ta
 int wipa_mel_pad_cast_frames(const float* mel, int64_t clip_stride, int batch, int n_mels, int n_frames, void* mel_padded, int dtype,
                              wipa_stream_t s);
 
+/* ------------------------------------------------------------------ SpecAugment (fine-tuning; no counterpart in the reference)
+ * Time and mel-bin masks (Park et al. 2019; transformers' apply_spec_augment / mask_time_prob / mask_feature_prob) stored into an f32
+ * mel in place.  The draw is stated in integers, so the host plan, the kernel and a numpy restatement agree bit for bit.
+ * Per clip b and axis a (0 = time, 1 = mel bins):
+ *   L = min(max(n_frames[b], 0), frames) for time (frames when n_frames is NULL), n_mels for bins;  w = min(length[a], L);
+ *   word(k) = word 0 of philox4x32_10(counter (k, a, stream_lo[b], stream_hi[b]), key (seed & 0xffffffff, seed >> 32));
+ *   x = rate_q16[a] * L;  n = min(64, max(min_masks[a], (x >> 16) + ((word(0xffffffff) >> 16) < (x & 0xffff) ? 1 : 0)));  n = 0 if L == 0;
+ *   span k in 0..n-1 covers w consecutive indices from umulhi(word(k), L - w + 1).  Spans may overlap; the mask is their union.
+ * Element (b, t, m) becomes fill when t is in a time span or m in a bin span; every other element is neither read nor written.
+ * rate_q16 = min(65536, round(prob / length * 65536)) is the caller's: the expected number of spans per position in Q16.
+ * Refused (WIPA_ERR_ARG, wipa_last_error names the setting): length < 1, min_masks outside 0..64, rate_q16 > 65536, and "too many
+ * spans": ((rate_q16 * L_max) >> 16) + 1 > 64 with L_max = frames (time) or n_mels (bins); n_mels <= 512.
+ * wipa_spec_augment_plan: HOST only, touches no GPU; streams_host uint32 [B][2] (lo, hi), n_frames_host int32 [B] or NULL;
+ *   spans_out int32 [B][2][65]: the count, then the starts (-1 in the unused places).
+ * wipa_spec_augment: element (b, t, m) at mel + b*ld_clip + t*ld_frame + m (elements), t < frames: [B, 3000, n_mels] dense, the first
+ *   2N frames of such a mel (ld_clip = 3000*n_mels, frames = 2N), or the padded layout (mel = padded + n_mels, ld_clip = (frames +
+ *   2)*n_mels): halo rows and whatever lies beyond frames are left alone.  streams_dev / n_frames_dev as above, on the device.
+ *   One launch, asynchronous; 16-byte stores when mel, ld_clip, ld_frame and n_mels allow them. */
+#define WIPA_SPEC_AUGMENT_MAX_SPANS 64
+typedef struct wipa_spec_augment_cfg {
+    int32_t length[2];    /* span length: time, bins */
+    int32_t min_masks[2]; /* lower bound of the span count */
+    uint32_t rate_q16[2]; /* spans per position, Q16 */
+    float fill;           /* the value masked elements take (transformers: 0) */
+} wipa_spec_augment_cfg;
+int wipa_spec_augment_plan(const wipa_spec_augment_cfg* cfg, const uint32_t* streams_host, const int32_t* n_frames_host, int B, int frames,
+                           int n_mels, uint64_t seed, int32_t* spans_out);
+int wipa_spec_augment(float* mel, int64_t ld_clip, int64_t ld_frame, int B, int frames, int n_mels, const wipa_spec_augment_cfg* cfg,
+                      const uint32_t* streams_dev, const int32_t* n_frames_dev, uint64_t seed, wipa_stream_t s);
+
 /* ------------------------------------------------------------------ K4 GEMM
  * C = epilogue(A * W^T): every nn.Linear / Conv1d of mlx_whisper.whisper
  * (AudioEncoder, TextDecoder, MultiHeadAttention, ResidualAttentionBlock).

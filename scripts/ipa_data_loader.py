@@ -2,7 +2,7 @@
 (``IPADataset`` :17-131, ``create_data_loader`` :134-157), on top of whisper_ipa_amd.
 
 Same JSON schema (``audio_path``, ``ipa_transcription``, ``speaker_id``, ``dataset_source``), same
-batch dict keys (``mel_features [B,3000,n_mels]``, ``tokens [B,T]``, ``ipa_texts``, ``audio_paths``),
+batch dict keys (``mel_features [B,3000,n_mels]``, ``tokens [B,T]``, ``ipa_texts``, ``audio_paths``; ``n_frames`` is an addition),
 same token framing (SOT sequence incl. <|notimestamps|> + BPE(ipa) + EOT, padded with EOT).
 Differences forced by the platform: audio is read as WAV/PCM (no ffmpeg), the log-mel of the
 whole batch is ONE GPU launch, and the returned arrays are torch tensors on the GPU.
@@ -19,7 +19,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from whisper_ipa_amd.audio import load_audio, load_audio_batch, log_mel_spectrogram  # noqa: E402
+from whisper_ipa_amd.audio import frames_of_samples, load_audio, load_audio_batch, log_mel_spectrogram  # noqa: E402
 
 
 class IPADataset:
@@ -81,7 +81,7 @@ class IPADataset:
         entries = [self.data[i] for i in indices]
         paths = [os.path.join(self.audio_root, e["audio_path"]) if self.audio_root else e["audio_path"] for e, f in zip(entries, need) if f]
         mel = None
-        report = {"longer_than_audio_ctx": 0}
+        report = {"longer_than_audio_ctx": 0, "sample_counts": []}
         if paths:
             # load_audio + pad_or_trim (:44,80) of the flagged clips: one copy, one launch
             audio = load_audio_batch(paths, audio_ctx=self.audio_ctx, report=report)
@@ -94,6 +94,9 @@ class IPADataset:
             "ipa_texts": texts,
             "audio_paths": [e["audio_path"] for e in entries],
             "clips_over_audio_ctx": report["longer_than_audio_ctx"],  # of the clips read: longer than audio_ctx * 20 ms, i.e. cut
+            # of the clips read, like mel_features: the log-mel frames that carry the clip's own samples (ceil(samples / 160), at
+            # most 3000) -- the time axis SpecAugment draws its masks over
+            "n_frames": frames_of_samples(report["sample_counts"]),
         }
 
 

@@ -35,6 +35,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from evaluate_ipa import evaluate_batch  # noqa: E402
 from ipa_data_loader import create_data_loader  # noqa: E402
 from whisper_ipa_amd import parallel  # noqa: E402
+from whisper_ipa_amd.audio import SpecAugment  # noqa: E402
 from whisper_ipa_amd.decoding import DecodingOptions  # noqa: E402
 from whisper_ipa_amd.load_models import load_model, save_safetensors  # noqa: E402
 from whisper_ipa_amd.pipeline import transcribe_batches  # noqa: E402
@@ -208,6 +209,9 @@ def value_and_grad(model, loss_fn):
 def train_step(trainer: DecoderTrainer, batch: Dict, tokenizer):
     """reference :266-311 -> (loss, clipped grads); the arithmetic is DecoderTrainer.train_step.  ``batch["clip_keys"]``
     (dataset indices) is present when the frozen-encoder feature cache is on: mel_features then covers the uncached clips only."""
+    if trainer.spec_augment is not None:  # clip_keys: the masks' streams; n_frames: each clip's own frames, their time axis
+        return trainer.train_step(batch["mel_features"], batch["tokens"], tokenizer.eot, clip_keys=batch.get("clip_keys"),
+                                  n_frames=batch.get("n_frames"))
     return trainer.train_step(batch["mel_features"], batch["tokens"], tokenizer.eot, clip_keys=batch.get("clip_keys"))
 
 
@@ -321,11 +325,18 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
           batch_size: int = 4, learning_rate: float = 1e-5, validate_every: int = 100, save_every: int = 500,
           test_run: bool = False, audio_root: str = "", seed: Optional[int] = None, exact_f32: bool = False,
           allow_byte_fallback: bool = False, cache_encoder_features: bool = True, feature_cache_clips: Optional[int] = None,
-          clip_scope: str = "reference", scoring: str = "device", audio_ctx: Optional[int] = None, train_encoder_layers=0):
-    """``train_encoder_layers``: 0 (the reference: encoder frozen), a number K of top encoder blocks to train with ln_post, or
+          clip_scope: str = "reference", scoring: str = "device", audio_ctx: Optional[int] = None, train_encoder_layers=0,
+          spec_augment: Optional[Dict] = None):
+    """``spec_augment``: None (default: no augmentation, nothing changes), or the keyword arguments of
+    ``whisper_ipa_amd.audio.SpecAugment`` (``--spec-augment``): every training step masks time and mel-bin spans of its own copy of
+    the mel, each clip over its own frames, from the stream (dataset index, step).  Runs without the feature cache.
+    ``train_encoder_layers``: 0 (the reference: encoder frozen), a number K of top encoder blocks to train with ln_post, or
     "all" (every block, ln_post and the conv stem).  No counterpart in the reference.  Runs without the feature cache."""
     if train_encoder_layers != 0 and feature_cache_clips is not None:
         raise SystemExit("--train-encoder-layers with --feature-cache-clips: the feature cache holds the output of a FROZEN encoder")
+    if spec_augment is not None and feature_cache_clips is not None:
+        raise SystemExit("--spec-augment with --feature-cache-clips: augmented features differ every time a clip returns and cannot be cached")
+    augmenter = SpecAugment(**spec_augment) if spec_augment is not None else None  # bad settings are refused here, by name
     rank, world = _init_distributed()
     try:
         parallel.require_even_shards(batch_size, world)  # every rank gets clips; no mismatched collectives
@@ -343,6 +354,8 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
                      "cache_encoder_features": bool(cache_encoder_features), "clip_scope": clip_scope, "scoring": scoring,
                      "audio_ctx": audio_ctx,  # read back by the evaluation scripts (load_models.resolve_audio_ctx)
                      "train_encoder_layers": train_encoder_layers}
+        if augmenter is not None:
+            args_dict["spec_augment"] = dict(augmenter.settings)
         save_training_config(output_dir, args_dict, get_hardware_info())
     logger = TrainingLogger(output_dir) if main else None
     print(f"Loading model: {model_name}")
@@ -354,7 +367,12 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
     # mlx AdamW defaults (reference :513); the clip reaches what the reference's clip_grad_dict reaches (:287-303: dicts only,
     # the decoder.blocks list passes through) unless --clip-scope all
     trainer = DecoderTrainer(model, lr=learning_rate, f32_split=not exact_f32, clip_scope=clip_scope,
-                             train_encoder_layers=train_encoder_layers)
+                             train_encoder_layers=train_encoder_layers, spec_augment=augmenter)
+    if augmenter is not None and main:
+        st = augmenter.settings
+        print(f"  ✓ SpecAugment: time spans of {st['mask_time_length']} frames (prob {st['mask_time_prob']}, at least "
+              f"{st['mask_time_min_masks']}) over each clip's own frames, mel-bin spans of {st['mask_feature_length']} bins (prob "
+              f"{st['mask_feature_prob']}, at least {st['mask_feature_min_masks']}); fill {st['fill']}, seed {st['seed']}")
     n_mels = 128 if "large" in model_name else 80  # reference :517
     if model.dims.n_mels != n_mels:
         n_mels = model.dims.n_mels
@@ -367,7 +385,9 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
         train_dataset.data = train_dataset.data[:100]
         num_steps = min(num_steps, 100)
     rng = np.random.default_rng(seed) if seed is not None else np.random.default_rng(int(time.time()) if world == 1 else 0)
-    if cache_encoder_features and trainer.trains_encoder:
+    if cache_encoder_features and augmenter is not None:
+        print("  ✓ No encoder feature cache: --spec-augment masks every clip anew each time it returns")
+    elif cache_encoder_features and trainer.trains_encoder:
         print(f"  ✓ No encoder feature cache: train_encoder_layers={train_encoder_layers!r} moves the encoder every step")
     elif cache_encoder_features:
         # The encoder is frozen (reference :187) yet recomputed every step (:223): its output is a pure function of the clip,
@@ -392,6 +412,8 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
                     batch["clip_keys"] = mine
                 else:
                     batch = train_dataset.get_batch(mine)
+                    if augmenter is not None:
+                        batch["clip_keys"] = mine  # the dataset indices: a clip's masks follow the clip, not its row
             except Exception as e:  # e.g. an unreadable clip on ONE rank
                 local_error = e
             # Failure must be collective: a rank that left the loop alone would leave the others waiting in the step's
@@ -515,13 +537,29 @@ def main():
                    help="also train the last K encoder blocks and ln_post (K = 1..L), or the whole encoder with its conv stem (all).  "
                         "Default 0: the encoder is frozen, as in the reference.  Recorded in training_config.json; runs without the "
                         "encoder feature cache and cannot be combined with --feature-cache-clips")
+    p.add_argument("--spec-augment", action="store_true",
+                   help="SpecAugment in the training step: time and mel-bin spans of the log-mel are masked on the GPU, each clip over "
+                        "its own frames, anew every time a clip returns.  Recorded in training_config.json; runs without the encoder "
+                        "feature cache and cannot be combined with --feature-cache-clips.  Default: off")
+    p.add_argument("--mask-time-prob", type=float, default=0.05, help="fraction of a clip's frames under time spans (before overlap)")
+    p.add_argument("--mask-time-length", type=int, default=10, help="frames per time span")
+    p.add_argument("--mask-time-min-masks", type=int, default=2, help="at least this many time spans per clip")
+    p.add_argument("--mask-feature-prob", type=float, default=0.0, help="fraction of the mel bins under bin spans (before overlap)")
+    p.add_argument("--mask-feature-length", type=int, default=10, help="bins per bin span")
+    p.add_argument("--mask-feature-min-masks", type=int, default=0, help="at least this many bin spans per clip")
+    p.add_argument("--augment-seed", type=int, default=0, help="seed of the masks (with the dataset index and the step)")
     a = p.parse_args()
+    aug = None
+    if a.spec_augment:
+        aug = dict(mask_time_prob=a.mask_time_prob, mask_time_length=a.mask_time_length, mask_time_min_masks=a.mask_time_min_masks,
+                   mask_feature_prob=a.mask_feature_prob, mask_feature_length=a.mask_feature_length,
+                   mask_feature_min_masks=a.mask_feature_min_masks, seed=a.augment_seed)
     train(model_name=a.model, train_data_path=a.train_data, test_data_path=a.test_data, output_dir=a.output_dir,
           num_steps=a.steps, batch_size=a.batch_size, learning_rate=a.lr, validate_every=a.validate_every,
           save_every=a.save_every, test_run=a.test_run, audio_root=a.audio_root, exact_f32=a.exact_f32,
           allow_byte_fallback=a.allow_byte_fallback, cache_encoder_features=not a.no_cache_encoder_features,
           feature_cache_clips=a.feature_cache_clips, clip_scope=a.clip_scope, scoring=a.scoring, audio_ctx=a.audio_ctx,
-          train_encoder_layers=a.train_encoder_layers)
+          train_encoder_layers=a.train_encoder_layers, spec_augment=aug)
 
 
 if __name__ == "__main__":

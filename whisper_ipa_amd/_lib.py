@@ -17,6 +17,7 @@ WIPA_F32, WIPA_BF16, WIPA_FP8_E4M3 = 0, 1, 2
 GREEDY_PARTS = 2048  # WIPA_GREEDY_PARTS
 RESAMPLE_TILE = 512  # WIPA_RESAMPLE_TILE
 SCORE_MAX_LEN = 1024  # WIPA_SCORE_MAX_LEN
+SPEC_AUGMENT_MAX_SPANS = 64  # WIPA_SPEC_AUGMENT_MAX_SPANS
 ENC_GLOBAL, ENC_PER_LAYER = 7, 14
 DEC_GLOBAL, DEC_PER_LAYER, DEC_FP8_PER_LAYER = 4, 20, 6
 GEMM_DISPATCH = ("tile128", "tile256", "tile384", "tile384n", "tile256p", "skinny", "skinny_fp8", "skinny_ln", "kmajor", "split_k",
@@ -85,6 +86,11 @@ class PcmClipDesc(C.Structure):
         "n_frames", "n_out", "n_channels", "format", "rate", "S", "D", "K")]
 
 
+class SpecAugmentCfg(C.Structure):
+    """wipa_spec_augment_cfg"""
+    _fields_ = [("length", C.c_int32 * 2), ("min_masks", C.c_int32 * 2), ("rate_q16", C.c_uint32 * 2), ("fill", c_float)]
+
+
 class ModelCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "n_mels", "n_audio_ctx", "n_audio_state", "n_audio_head", "n_audio_layer",
@@ -121,6 +127,9 @@ SIGNATURES = {
     "wipa_logmel_frames_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "wipa_logmel_frames": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "wipa_mel_pad_cast_frames": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "wipa_spec_augment_plan": (c_int, [_P(SpecAugmentCfg), c_void_p, c_void_p, c_int, c_int, c_int, C.c_uint64, c_void_p]),
+    "wipa_spec_augment": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, _P(SpecAugmentCfg), c_void_p, c_void_p, C.c_uint64,
+                                  c_void_p]),
     "wipa_gemm": (c_int, [_P(GemmDesc), c_void_p]),
     "wipa_gemm_dispatch_counts": (c_int, [_P(c_int64), c_int, c_int]),
     "wipa_layernorm": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_int,

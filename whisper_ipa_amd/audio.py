@@ -8,6 +8,9 @@ files directly: the reference shells out to ffmpeg, which this image does not ha
 ``load_audio_batch`` is ``pad_or_trim(load_audio(file))`` for a batch of files on the GPU (K0, csrc/resample.hip): the host only
 reads the PCM bytes (``read_pcm``) and packs them (``PcmBatch``); sample conversion, channel mix-down, resampling to 16 kHz and the
 30 s pad / cut are one copy and one launch.  ``load_audio`` / ``_resample`` stay as the host path and as the kernel's reference.
+
+``SpecAugment`` / ``spec_augment``: time and mel-bin masks for fine-tuning, drawn per clip from a counter-based generator and stored
+into an f32 mel on the GPU (csrc/spec_augment.hip).  Training only: nothing on the inference path calls it.
 """
 from __future__ import annotations
 
@@ -306,10 +309,13 @@ def load_audio_batch(clips: Union[PcmBatch, Sequence[Union[str, PcmClip]]], out:
     stream; 16 kHz input is bit-identical to the host path, other rates agree to f32 rounding of the same filter.
     ``out``: an existing [B, 480000] f32 device tensor to write into (every element is written).
     ``report`` (a dict): receives ``"longer_than_audio_ctx"``, the clips of the batch that exceed ``audio_ctx`` * 320 samples and are
-    therefore CUT by a model running on ``audio_ctx`` positions (``count_longer_than_audio_ctx``)."""
+    therefore CUT by a model running on ``audio_ctx`` positions (``count_longer_than_audio_ctx``), and ``"sample_counts"``, every clip's
+    length in 16 kHz samples, capped at the 30 s window (``PcmBatch.sample_counts``)."""
     batch = clips if isinstance(clips, PcmBatch) else PcmBatch(clips)
     if report is not None:
-        report["longer_than_audio_ctx"] = count_longer_than_audio_ctx(batch.sample_counts(), audio_ctx)
+        counts = batch.sample_counts()
+        report["longer_than_audio_ctx"] = count_longer_than_audio_ctx(counts, audio_ctx)
+        report["sample_counts"] = counts
     return _ingest(batch, out)[0]
 
 
@@ -414,3 +420,102 @@ def log_mel_spectrogram(audio: ArrayLike, n_mels: int = 80, padding: int = 0) ->
     padded = log_mel_padded(audio, n_mels, torch.float32)
     mel = padded[: B * PADDED_FRAMES].view(B, PADDED_FRAMES, n_mels)[:, 1 : N_FRAMES + 1]
     return mel[0] if single else mel
+
+
+# ---- SpecAugment (csrc/spec_augment.hip): time and mel-bin masks for fine-tuning ---------------------------------------------------
+
+SPEC_AUGMENT_MAX_SPANS = _lib.SPEC_AUGMENT_MAX_SPANS
+
+
+class SpecAugment:
+    """Settings of the augmentation, named as in ``transformers`` (``mask_time_prob`` / ``_length`` / ``_min_masks``,
+    ``mask_feature_*``): on each axis about ``prob * L / length`` spans of ``length`` positions (at least ``min_masks``, at most 64)
+    become ``fill``; L is the clip's OWN frame count on the time axis (``n_frames``), so a 3 s clip in the 30 s window is masked over
+    its 300 frames, not over 2700 frames of padding.  The draw is a pure function of (``seed``, the clip's stream, L): include/wipa.h
+    states it in integers, ``plan`` returns it from the host without touching the GPU."""
+
+    def __init__(self, mask_time_prob: float = 0.05, mask_time_length: int = 10, mask_time_min_masks: int = 2,
+                 mask_feature_prob: float = 0.0, mask_feature_length: int = 10, mask_feature_min_masks: int = 0, fill: float = 0.0,
+                 seed: int = 0):
+        self.cfg = _lib.SpecAugmentCfg()
+        for a, axis, prob, length, min_masks in ((0, "time", mask_time_prob, mask_time_length, mask_time_min_masks),
+                                                 (1, "feature", mask_feature_prob, mask_feature_length, mask_feature_min_masks)):
+            if isinstance(length, bool) or int(length) != length or int(length) < 1:
+                raise _lib.WipaError(f"SpecAugment: mask_{axis}_length = {length!r}, must be an integer >= 1")
+            if not 0.0 <= float(prob) <= 1.0:  # also refuses NaN
+                raise _lib.WipaError(f"SpecAugment: mask_{axis}_prob = {prob!r}, outside [0, 1]")
+            if isinstance(min_masks, bool) or int(min_masks) != min_masks or not 0 <= int(min_masks) <= SPEC_AUGMENT_MAX_SPANS:
+                raise _lib.WipaError(f"SpecAugment: mask_{axis}_min_masks = {min_masks!r}, outside 0..{SPEC_AUGMENT_MAX_SPANS}")
+            self.cfg.length[a], self.cfg.min_masks[a] = int(length), int(min_masks)
+            self.cfg.rate_q16[a] = min(65536, round(float(prob) / int(length) * 65536))
+        self.cfg.fill = float(fill)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.settings = dict(mask_time_prob=float(mask_time_prob), mask_time_length=int(mask_time_length),
+                             mask_time_min_masks=int(mask_time_min_masks), mask_feature_prob=float(mask_feature_prob),
+                             mask_feature_length=int(mask_feature_length), mask_feature_min_masks=int(mask_feature_min_masks),
+                             fill=float(fill), seed=self.seed)
+
+    @staticmethod
+    def _host_rows(streams, n_frames) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        st = np.ascontiguousarray((np.asarray(streams, dtype=np.int64).reshape(-1, 2) & 0xFFFFFFFF).astype(np.uint32))
+        if n_frames is None:
+            return st, None
+        nf = np.ascontiguousarray(np.clip(np.asarray(n_frames, dtype=np.int64).reshape(-1), 0, 2 ** 31 - 1).astype(np.int32))
+        if nf.shape[0] != st.shape[0]:
+            raise _lib.WipaError(f"SpecAugment: {st.shape[0]} streams but {nf.shape[0]} frame counts")
+        return st, nf
+
+    def plan(self, streams, n_frames, frames: int, n_mels: int) -> np.ndarray:
+        """The spans every clip draws, from the host (wipa_spec_augment_plan: the text the kernel compiles).  ``streams`` [B, 2]
+        (lo, hi), ``n_frames`` [B] or None -> int32 [B, 2, 65]: per clip and axis (0 time, 1 bins) the count, then the starts (-1
+        in the unused places); every span covers min(length, L) positions."""
+        st, nf = self._host_rows(streams, n_frames)
+        out = np.empty((st.shape[0], 2, SPEC_AUGMENT_MAX_SPANS + 1), dtype=np.int32)
+        _lib.check(_lib.lib().wipa_spec_augment_plan(C.byref(self.cfg), st.ctypes.data, None if nf is None else nf.ctypes.data, st.shape[0],
+                                                     int(frames), int(n_mels), self.seed, out.ctypes.data), "wipa_spec_augment_plan")
+        return out
+
+    def mask_in_place(self, buf: torch.Tensor, offset: int, ld_clip: int, ld_frame: int, B: int, frames: int, n_mels: int, streams,
+                      n_frames=None) -> None:
+        """One launch on the current library stream: element (b, t, m) of the mask lands on the f32 tensor ``buf`` at flat element
+        ``offset + b*ld_clip + t*ld_frame + m``.  Streams and frame counts go up in one non-blocking copy from pinned memory."""
+        st, nf = self._host_rows(streams, n_frames)
+        if st.shape[0] != B:
+            raise _lib.WipaError(f"SpecAugment: {st.shape[0]} streams for {B} clips")
+        assert buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous()
+        assert offset >= 0 and offset + (B - 1) * ld_clip + (frames - 1) * ld_frame + n_mels <= buf.numel()
+        host = np.concatenate([st.reshape(-1).view(np.int32)] + ([] if nf is None else [nf]))
+        with on_stream() as s:
+            dev = torch.from_numpy(host).pin_memory().to(buf.device, non_blocking=True)
+            _lib.check(_lib.lib().wipa_spec_augment(buf.data_ptr() + 4 * offset, ld_clip, ld_frame, B, frames, n_mels, C.byref(self.cfg),
+                                                    dev.data_ptr(), None if nf is None else dev.data_ptr() + 8 * B, self.seed, sptr(s)),
+                       "wipa_spec_augment")
+
+
+def spec_augment(mel: torch.Tensor, aug: SpecAugment, streams, n_frames=None, frames: Optional[int] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A masked copy of ``mel`` [B, T, n_mels] f32 on the GPU; ``out=mel`` masks in place.  ``streams`` [B, 2]: the (lo, hi) stream
+    of every clip; ``n_frames`` [B]: every clip's own length in frames (None: the whole time axis); ``frames`` (default T): the
+    frames the time axis spans -- a model with ``audio_ctx`` = N sees the first 2N."""
+    if not (mel.is_cuda and mel.dtype == torch.float32 and mel.dim() == 3):
+        raise _lib.WipaError(f"spec_augment: an f32 device mel [B, T, n_mels] is expected, got {mel.dtype} {tuple(mel.shape)}")
+    B, T, n_mels = mel.shape
+    frames = T if frames is None else int(frames)
+    if not 1 <= frames <= T:
+        raise _lib.WipaError(f"spec_augment: frames={frames} (1..{T})")
+    with on_stream():
+        if out is None:
+            out = mel.clone(memory_format=torch.contiguous_format)
+        elif out is not mel:
+            if out.shape != mel.shape or out.dtype != mel.dtype or not out.is_cuda:
+                raise _lib.WipaError("spec_augment: out must match mel")
+            out.copy_(mel)
+        if not out.is_contiguous():
+            raise _lib.WipaError("spec_augment: a contiguous tensor is expected")
+        aug.mask_in_place(out, 0, T * n_mels, n_mels, B, frames, n_mels, streams, n_frames)
+    return out
+
+
+def frames_of_samples(n_samples: Iterable[int]) -> List[int]:
+    """log-mel frames that carry a clip's own samples: ceil(samples / 160), capped at the 3000 of the 30 s window"""
+    return [min(N_FRAMES, -(-int(n) // HOP_LENGTH)) for n in n_samples]

@@ -227,8 +227,16 @@ def flat_layout(dims, train_encoder_layers=0) -> Dict:
 class DecoderTrainer:
     def __init__(self, model: Whisper, lr: float = 1e-5, max_grad_norm: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.01, f32_split: Optional[bool] = None, clip_scope: str = "reference",
-                 train_encoder_layers=0):
-        """``train_encoder_layers``: 0 (default) trains the decoder alone, the reference's step (its encoder is frozen,
+                 train_encoder_layers=0, spec_augment=None):
+        """``spec_augment`` (an ``audio.SpecAugment``; default None: the step as it is without one, launch for launch): every training
+        step masks the padded f32 copy of the mel it makes anyway -- the buffer of _encoder_forward, or embed_audio's on a
+        decoder-only trainer -- with one launch (csrc/spec_augment.hip); the caller's mel is never modified.  Row b draws from the
+        stream (clip_keys[b], step_count) when train_step is given ``clip_keys``, else (rank * B + b, step_count): no two ranks
+        share a stream, and a clip draws a new mask every time it returns.  ``n_frames`` (train_step / loss_and_grads_from_mel):
+        every clip's own length in frames, the time axis its masks are drawn over; under ``model.audio_ctx`` = N the axis is the
+        first 2N frames.  Such a trainer refuses the feature cache and loss_and_grads(features): augmented features are not a
+        function of the clip.  Nothing outside the training step augments.
+        ``train_encoder_layers``: 0 (default) trains the decoder alone, the reference's step (its encoder is frozen,
         train_whisper_ipa.py:187).  K in 1..n_audio_layer also trains the last K encoder blocks and ``encoder.ln_post``;
         ``"all"`` every block, ``ln_post`` and the conv stem (``conv1.*``, ``conv2.*``).  The sinusoidal positional table of
         the encoder is never a parameter (as in mlx_whisper).  Such a trainer steps from the mel (train_step /
@@ -313,12 +321,41 @@ class DecoderTrainer:
         self._dw_slabs = None   # split-K partial weight gradients (wipa_gemm k_slices + wipa_sum_slabs)
         self._mm_slabs = None   # split-K partial outputs of the token-row GEMMs (_mm)
         self.feature_cache: Optional[FrozenFeatureCache] = None  # enable_feature_cache()
+        self._spec_augment = None
+        self.spec_augment = spec_augment
         self._leaves = None     # autograd leaves over flat_p (leaves())
         model._trainer = self   # Whisper.logits differentiates through this trainer under torch.enable_grad()
 
     # the encoder's self-attention backward of an f32_split trainer runs the split-product kernels (wipa_attention_bwd_ex); the
     # A/B against the exact kernels at encoder shapes is in profiles/encoder_train_bench.txt
     ENCODER_ATTN_BWD_SPLIT = True
+
+    @property
+    def spec_augment(self):
+        return self._spec_augment
+
+    @spec_augment.setter
+    def spec_augment(self, aug) -> None:
+        if aug is not None and self.feature_cache is not None:
+            raise _lib.WipaError("DecoderTrainer: spec_augment on a trainer with a feature cache: augmented features cannot be cached")
+        self._spec_augment = aug
+
+    def _augment_streams(self, B: int, clip_keys) -> List[Tuple[int, int]]:
+        """row b's stream: (clip_keys[b], step_count), or (rank * B + b, step_count) without keys"""
+        if clip_keys is not None:
+            keys = [int(k) for k in clip_keys]
+            if len(keys) != B:
+                raise _lib.WipaError(f"DecoderTrainer: {len(keys)} clip_keys for {B} clips")
+        else:
+            rank = parallel.world()[0]
+            keys = [rank * B + b for b in range(B)]
+        return [(k, self.step_count) for k in keys]
+
+    def _augment_padded(self, padded: torch.Tensor, B: int, F: int, clip_keys, n_frames) -> None:
+        """mask the padded f32 mel in place: frame t of clip b at row b*(F + 2) + t + 1; halo rows are not touched"""
+        n_mels = self.model.dims.n_mels
+        self._spec_augment.mask_in_place(padded, n_mels, (F + 2) * n_mels, n_mels, B, F, n_mels, self._augment_streams(B, clip_keys),
+                                         n_frames)
 
     def feature_cache_capacity_default(self) -> int:
         return FrozenFeatureCache.clips_that_fit(self.model)
@@ -327,6 +364,8 @@ class DecoderTrainer:
         """Keep the frozen encoder's output per clip in HBM (FrozenFeatureCache); ``max_clips`` defaults to what half of the
         free device memory holds.  Refused by a trainer that trains encoder layers: the features then change with every step."""
         self._decoder_only("enable_feature_cache")
+        if self._spec_augment is not None:
+            raise _lib.WipaError("DecoderTrainer.enable_feature_cache on a trainer with spec_augment: augmented features cannot be cached")
         n = FrozenFeatureCache.clips_that_fit(self.model) if max_clips is None else int(max_clips)
         self.feature_cache = FrozenFeatureCache(self.model, max(0, n))
         return self.feature_cache
@@ -677,7 +716,7 @@ class DecoderTrainer:
         self._ln_bwd(S["x_a"], dh1, P(f"{pre}.attn_ln.weight"), dx, True, G(f"{pre}.attn_ln.weight"), G(f"{pre}.attn_ln.bias"), M, d)
 
     # ---- encoder: training forward (keeps activations) + backward -----------------------------
-    def _encoder_forward(self, mel: torch.Tensor):
+    def _encoder_forward(self, mel: torch.Tensor, clip_keys=None, n_frames=None):
         """AudioEncoder.__call__ in f32 on a mel [B, 3000, n_mels] (or [B, 2N, n_mels] with ``model.audio_ctx`` = N), composed
         from the per-kernel entry points like the decoder's _forward: conv1 and conv2 as GEMMs over overlapping rows of the
         padded layouts wipa_encoder_forward uses (their PRE-GELU values kept), then per block LayerNorm, q, k, v, non-causal
@@ -704,6 +743,8 @@ class DecoderTrainer:
             padded = torch.zeros(max(M1 + 4, Kc1 + 3), n_mels, dtype=torch.float32, device=dev)
             _lib.check(L.wipa_mel_pad_cast_frames(ptr(mel32), mel32.shape[1] * n_mels, B, n_mels, F, ptr(padded), 0, sptr(s)),
                        "wipa_mel_pad_cast_frames")
+            if self._spec_augment is not None:
+                self._augment_padded(padded, B, F, clip_keys, n_frames)
             w1 = torch.zeros(d, K1, dtype=torch.float32, device=dev)  # K padded to whole 32-float steps with zero columns
             w1[:, : 3 * n_mels].copy_(W("encoder.conv1.weight").reshape(d, 3 * n_mels))
             # conv1 (k3, p1), pre-activation: GEMM row g = b*R + t reads the padded rows g..g+2 and lands at row g + 1; the two
@@ -801,14 +842,17 @@ class DecoderTrainer:
             self._wgrad_rows(dz1, padded, n_mels, Kc1, d, 3 * n_mels, G("encoder.conv1.weight").view(d, 3 * n_mels))
         return dz1
 
-    def loss_and_grads_from_mel(self, mel: torch.Tensor, tokens: torch.Tensor, eot: int, group=None):
+    def loss_and_grads_from_mel(self, mel: torch.Tensor, tokens: torch.Tensor, eot: int, group=None, clip_keys=None, n_frames=None):
         """The full path of a trainer that trains encoder layers: mel [B, 3000, n_mels] (or [B, 2N, n_mels] with
         ``model.audio_ctx`` = N), tokens [B, T+1] int.  Encoder forward that keeps its activations, decoder forward and backward
         (which also yields the gradient of the encoder output), encoder backward.  Fills every segment of self.flat_g like
-        loss_and_grads; returns (loss, sum_ce, n_valid).  With train_encoder_layers=0 it is embed_audio + loss_and_grads."""
+        loss_and_grads; returns (loss, sum_ce, n_valid).  With train_encoder_layers=0 it is embed_audio + loss_and_grads.
+        ``clip_keys`` / ``n_frames``: the streams and the time axes of a trainer with ``spec_augment`` (ignored without one)."""
         if not self.trains_encoder:
+            if self._spec_augment is not None:
+                return self._loss_and_grads(self._embed_audio_augmented(mel, clip_keys, n_frames), tokens, eot, group, None)
             return self.loss_and_grads(self.model.embed_audio(mel), tokens, eot, group)
-        feats, ectx = self._encoder_forward(mel)
+        feats, ectx = self._encoder_forward(mel, clip_keys, n_frames)
         self.last_features = feats  # the encoder output of this step (before the update)
         return self._loss_and_grads(feats, tokens, eot, group, ectx)
 
@@ -820,7 +864,17 @@ class DecoderTrainer:
         Features carry no gradient, so only the decoder segments could be filled: a trainer that trains encoder layers
         refuses the call (loss_and_grads_from_mel is its path)."""
         self._decoder_only("loss_and_grads(audio_features, ...)")
+        if self._spec_augment is not None:
+            raise _lib.WipaError("DecoderTrainer.loss_and_grads(audio_features, ...) on a trainer with spec_augment: the masks are "
+                                 "drawn on the mel -- step from it (train_step / loss_and_grads_from_mel)")
         return self._loss_and_grads(audio_features, tokens, eot, group, None)
+
+    def _embed_audio_augmented(self, mel: torch.Tensor, clip_keys, n_frames) -> torch.Tensor:
+        """model.embed_audio with the mask stored into its padded copy of the mel, between the pad and the encoder"""
+        if mel is None:
+            raise _lib.WipaError("DecoderTrainer: a trainer with spec_augment steps from the mel of every clip")
+        B = 1 if mel.dim() == 2 else mel.shape[0]
+        return self.model.embed_audio(mel, _mask_padded=lambda padded, F: self._augment_padded(padded, B, F, clip_keys, n_frames))
 
     def _loss_and_grads(self, audio_features: torch.Tensor, tokens: torch.Tensor, eot: int, group, ectx: Optional[Dict]):
         m, dm, L = self.model, self.model.dims, self.L
@@ -905,14 +959,16 @@ class DecoderTrainer:
         self.model._invalidate()  # fused inference tables are rebuilt lazily from the updated weights
         self.step_count += 1
 
-    def train_step(self, mel: Optional[torch.Tensor], tokens: torch.Tensor, eot: int, group=None, clip_keys=None):
+    def train_step(self, mel: Optional[torch.Tensor], tokens: torch.Tensor, eot: int, group=None, clip_keys=None, n_frames=None):
         """train_whisper_ipa.py:266-311: encoder forward (frozen), loss + grads, clip, AdamW.
         Returns (loss as a device scalar, dict of clipped gradients).
         ``clip_keys`` (one hashable int per clip, e.g. the dataset index) with an enabled feature cache: ``mel`` holds only the
-        clips ``feature_cache.missing(clip_keys)`` marks (or is None when every clip is cached); the others come from HBM."""
-        if self.trains_encoder:
+        clips ``feature_cache.missing(clip_keys)`` marks (or is None when every clip is cached); the others come from HBM.
+        With ``spec_augment``: ``clip_keys`` name the clips' streams and ``n_frames`` (one per clip: its own length in log-mel
+        frames; None: the whole time axis) the span of the time masks."""
+        if self.trains_encoder or self._spec_augment is not None:
             # encoder forward that saves activations, decoder forward / backward, encoder backward (no feature cache: refused)
-            loss, _, _ = self.loss_and_grads_from_mel(mel, tokens, eot, group)
+            loss, _, _ = self.loss_and_grads_from_mel(mel, tokens, eot, group, clip_keys, n_frames)
             self.apply_update()
             return loss, self.grads()
         if clip_keys is not None and self.feature_cache is not None:

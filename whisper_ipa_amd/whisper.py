@@ -609,9 +609,13 @@ class Whisper:
                                               B, sptr(s)), "wipa_encoder_forward")
         return out
 
-    def embed_audio(self, mel: torch.Tensor) -> torch.Tensor:
+    def embed_audio(self, mel: torch.Tensor, _mask_padded=None) -> torch.Tensor:
         """mel [B, 3000, n_mels] (or [3000, n_mels]) -> [B, 1500, d]  (train_whisper_ipa.py:223).  With ``audio_ctx`` = N: the
-        first 2N frames of a [B, 3000, n_mels] mel, or a mel [B, 2N, n_mels], -> [B, N, d]."""
+        first 2N frames of a [B, 3000, n_mels] mel, or a mel [B, 2N, n_mels], -> [B, N, d].
+        ``_mask_padded`` (the fine-tune step of a trainer with SpecAugment, f32 models only; nothing else passes it): called as
+        ``_mask_padded(padded, frames)`` on this call's own padded copy of the mel, between the pad and the encoder."""
+        if _mask_padded is not None and self.dtype != torch.float32:
+            raise _lib.WipaError("embed_audio: the padded mel is masked in float32 only")
         L = _lib.lib()
         if mel.dim() == 2:
             mel = mel[None]
@@ -623,6 +627,8 @@ class Whisper:
                 padded = torch.empty(padded_mel_rows(B), self.dims.n_mels, dtype=self.dtype, device=self.device)
                 _lib.check(L.wipa_mel_pad_cast(ptr(mel32), B, self.dims.n_mels, ptr(padded), dt_code(self.dtype), sptr(s)),
                            "wipa_mel_pad_cast")
+                if _mask_padded is not None:
+                    _mask_padded(padded, N_FRAMES)
             return self.encode_padded(padded, B)
         F = self.n_audio_frames
         if mel.shape[1] not in (N_FRAMES, F) or mel.shape[2] != self.dims.n_mels:
@@ -633,6 +639,8 @@ class Whisper:
             padded = torch.empty(padded_mel_rows(B, F), self.dims.n_mels, dtype=self.dtype, device=self.device)
             _lib.check(L.wipa_mel_pad_cast_frames(ptr(mel32), mel32.shape[1] * mel32.shape[2], B, self.dims.n_mels, F, ptr(padded),
                                                   dt_code(self.dtype), sptr(s)), "wipa_mel_pad_cast_frames")
+            if _mask_padded is not None:
+                _mask_padded(padded, F)
         return self.encode_padded(padded, B)
 
     # ---- teacher-forced decoder ----------------------------------------------------
