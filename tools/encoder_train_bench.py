@@ -3,8 +3,7 @@
 target tokens, synthetic weights, no feature cache) with DecoderTrainer(train_encoder_layers=K) for K = 0, 2, 6, 12 and "all", exact
 and split products.  Per (K, products): ms per step (host wall clock around synchronised steps, as bench.py), the peak of
 torch.cuda.max_memory_allocated over a step, and both next to the K = 0 figure of the SAME run.
-The split rows run the encoder's attention backward on the split-product kernels, as an f32_split trainer does; one more row repeats
-"all" with the exact attention kernels forced (DecoderTrainer.ENCODER_ATTN_BWD_SPLIT = False on the instance): the step-level A/B.
+The split rows run the encoder's attention backward on the split-product kernels, as an f32_split trainer does.
 Then the attention backward alone at encoder shapes -- B = 8, H = 12, Tq = Tk = 1500 and 300, non-causal, f32: the exact f32-MFMA
 kernels against the split-product kernels (wipa_attention_bwd_ex, f32_split 0 / 1), alternating, HIP events, TF/s of the 5 matmuls
 (10 * B * H * T^2 * 64 FLOP): the A/B behind the choice of what the trainer wires in.
@@ -44,10 +43,8 @@ def trainer_for(k, split):
     return DecoderTrainer(m, lr=1e-5, f32_split=split, train_encoder_layers=k), dims
 
 
-def step_times(k, split, steps, exact_attention=False):
+def step_times(k, split, steps):
     tr, dims = trainer_for(k, split)
-    if exact_attention:
-        tr.ENCODER_ATTN_BWD_SPLIT = False
     mel, tok, eot = bench.synthetic_train_batch(TRAIN_B, TRAIN_T, dims.n_mels)
     mel, tok = mel.cuda(), tok.cuda()
     tr.train_step(mel, tok, eot)  # warm-up: workspaces, slabs
@@ -135,12 +132,6 @@ def main():
             print(f"  {mode:<5} train_encoder_layers={k!s:<4} step {mean:9.2f} ms (min {min(r['step_ms']):9.2f}) = {mean / mean0:6.2f} x K=0 "
                   f"({mean0:.2f} ms)   peak {r['peak_GB']:6.2f} GB (K=0 {base['peak_GB']:.2f} GB; held between steps {r['held_GB']:.2f} GB)   "
                   f"trained {r['trained_floats'] / 1e6:.1f} M floats   loss {r['loss']:.6f}")
-        if mode == "split":
-            r = step_times("all", True, args.steps, exact_attention=True)
-            r["encoder_attention_bwd"] = "exact"
-            rows.append(r)
-            print(f"  split train_encoder_layers=all, exact attention backward forced: step {sum(r['step_ms']) / len(r['step_ms']):9.2f} ms "
-                  f"(min {min(r['step_ms']):9.2f})   peak {r['peak_GB']:6.2f} GB")
     attn = [attention_bwd(T) for T in (1500, 300)]
     for r in attn:
         print(f"  attention backward B={r['B']} H={r['H']} Tq=Tk={r['T']}: exact f32 MFMA {min(r['exact_ms']):8.3f} ms (mean "

@@ -21,6 +21,7 @@ from __future__ import annotations
 
 
 import ctypes as C
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -35,6 +36,20 @@ OPT_CHUNK = 4096
 
 def _ceil(x: int, m: int) -> int:
     return (x + m - 1) // m * m
+
+
+def _stem_rows(B: int, N: int) -> SimpleNamespace:
+    """Row counts of the conv stem's training buffers for B clips of N positions, for the forward that fills them and the backward
+    that contracts over them.  ``R`` rows per clip in the padded layouts: 2N frames and a zero halo row either side.  ``M1`` /
+    ``M2``: the rows of conv1's / conv2's GEMM (R, and N + 1 with the last one dead, per clip).  ``Kc1`` / ``Kc2``: those in whole
+    32-row K-steps, the contraction lengths of the two weight-gradient GEMMs and the rows of dz1 / of the padded dz2.
+    ``padded`` / ``z1``: the rows of the padded mel and of conv1's output (and its GELU).  Rows past M1 + 4 exist (as zeros) for
+    the weight gradients' padded contractions, which read them as OVERLAPPING rows (_wgrad_rows): three mel rows from each of
+    Kc1 rows, three rows from every second of 2 Kc2."""
+    R = 2 * N + 2
+    M1, M2 = B * R, B * (N + 1)
+    Kc1, Kc2 = _ceil(M1, 32), _ceil(M2, 32)
+    return SimpleNamespace(R=R, M1=M1, M2=M2, Kc1=Kc1, Kc2=Kc2, padded=max(M1 + 4, Kc1 + 3), z1=max(M1 + 4, 2 * Kc2 + 2))
 
 
 class FrozenFeatureCache:
@@ -267,28 +282,18 @@ class DecoderTrainer:
             raise _lib.WipaError("DecoderTrainer: train_encoder_layers needs an encoder as wide as the decoder")
         layout = flat_layout(d, train_encoder_layers)
         self.names = layout["names"]  # decoder tensors first, as without encoder layers, then the trained encoder tensors
+        self.offsets, sizes, total = layout["offsets"], layout["sizes"], layout["total"]
+        # contiguous gradient segments, in the order the backward finishes them: each is all-reduced (_reduce_segment) while the
+        # earlier blocks still compute
         self.segments = layout["segments"]
+        self._segments_done = 0
         P = model.flat_parameters()
-        assert all(tuple(P[n].shape) == parameter_shape(d, n) for n in self.names)
-        sizes = [P[n].numel() for n in self.names]
+        self.shapes = {n: parameter_shape(d, n) for n in self.names}
+        assert all(tuple(P[n].shape) == self.shapes[n] for n in self.names)
+        # so that every tensor starts 16-byte aligned in the flat buffers: wipa_sum_slabs writes the weight gradients there and
+        # refuses any other address (the optimiser, wipa_clip_adamw, walks its chunks float by float and would not mind)
         assert all(s % 4 == 0 for s in sizes)
-        offs, total = [], 0
-        for s in sizes:
-            offs.append(total)
-            total += s
-        self.offsets = dict(zip(self.names, offs))
-        self.shapes = {n: tuple(P[n].shape) for n in self.names}
         self.n_params = total
-        # contiguous gradient segments in flat order: [embeddings][block 0]...[block L-1][final ln]; the
-        # backward finishes them from the back, so each can be all-reduced while earlier blocks still compute
-        starts = [offs[self.names.index(f"decoder.blocks.{l}.attn.query.weight")] for l in range(d.n_text_layer)]
-        tail = offs[self.names.index("decoder.ln.weight")]
-        self.block_ranges = [(starts[l], starts[l + 1] if l + 1 < d.n_text_layer else tail) for l in range(d.n_text_layer)]
-        dec_total = sum(s for n, s in zip(self.names, sizes) if n.startswith("decoder."))  # == total without encoder layers
-        self.head_range, self.tail_range = (0, starts[0]), (tail, dec_total)
-        seg = {label: (lo, hi) for label, lo, hi in self.segments}
-        self.enc_block_ranges = {l: seg[f"encoder.blocks.{l}"] for l in range(self._enc_first, d.n_audio_layer)}
-        self.enc_ln_post_range, self.enc_stem_range = seg.get("encoder.ln_post"), seg.get("encoder.stem")
         with on_stream():
             dev = model.device
             self.flat_p = torch.empty(total, dtype=torch.float32, device=dev)
@@ -300,7 +305,8 @@ class DecoderTrainer:
                 model._params[n] = self.p(n)  # the model now reads the optimiser's buffer directly
             # chunk tables for the flat multi-tensor optimiser
             ch_off, ch_len, ch_seg, seg_first = [], [], [], [0]
-            for si, (o, s) in enumerate(zip(offs, sizes)):
+            for si, (n, s) in enumerate(zip(self.names, sizes)):
+                o = self.offsets[n]
                 for c0 in range(0, s, OPT_CHUNK):
                     ch_off.append(o + c0)
                     ch_len.append(min(OPT_CHUNK, s - c0))
@@ -318,17 +324,13 @@ class DecoderTrainer:
         model._invalidate()
         self.step_count = 0
         self._colsum_ws = None  # partial sums of the chunked bias-gradient reduction (wipa_colsum)
-        self._dw_slabs = None   # split-K partial weight gradients (wipa_gemm k_slices + wipa_sum_slabs)
-        self._mm_slabs = None   # split-K partial outputs of the token-row GEMMs (_mm)
+        self._slabs = None      # split-K partial outputs (_gemm_k_sliced): one workspace, its uses are ordered on the library stream
+        self._ar_events = None  # HIP events around the last step's exposed all-reduce wait (_join_reductions)
         self.feature_cache: Optional[FrozenFeatureCache] = None  # enable_feature_cache()
         self._spec_augment = None
         self.spec_augment = spec_augment
         self._leaves = None     # autograd leaves over flat_p (leaves())
         model._trainer = self   # Whisper.logits differentiates through this trainer under torch.enable_grad()
-
-    # the encoder's self-attention backward of an f32_split trainer runs the split-product kernels (wipa_attention_bwd_ex); the
-    # A/B against the exact kernels at encoder shapes is in profiles/encoder_train_bench.txt
-    ENCODER_ATTN_BWD_SPLIT = True
 
     @property
     def spec_augment(self):
@@ -405,23 +407,30 @@ class DecoderTrainer:
         are 96 tiles of 128 x 128 -- a third of the chip -- so K is cut into slices computed by separate workgroups (slabs
         summed in a fixed order, then scale / residual: wipa_sum_slabs_ex) whenever the tile grid alone leaves CUs idle."""
         tiles = ((M + 127) // 128) * ((N + 127) // 128)
-        # two workgroups of this kernel fit a CU: aim at (just under) 512 of them, at least four K-steps each.  Measured on the
-        # fine-tune step: 480 workgroups (5 slices of a 96-tile GEMM) 144.9 ms, 288 (3 slices) 147.1, 768 (8 slices) 148.1
-        slices = max(1, min(16, 512 // max(tiles, 1), K // 128)) if M >= 512 else 1
         plain = out.dim() == 2 and out.shape[0] == M and out.shape[1] == N and out.is_contiguous() and (
             residual is None or (residual.is_contiguous() and residual.shape == out.shape))
-        if slices > 1 and plain:
-            need = slices * M * N
-            if self._mm_slabs is None or self._mm_slabs.numel() < need:
-                self._mm_slabs = torch.empty(need, dtype=torch.float32, device=out.device)
-            self._gemm(A, W, self._mm_slabs, M=M, N=N, K=K, lda=lda, ldw=ldw, ldc=N, bias=bias, k_slices=slices, slab_stride=M * N,
-                       w_trans=w_trans)
-            with on_stream() as s:
-                _lib.check(self.L.wipa_sum_slabs_ex(ptr(self._mm_slabs), slices, M * N, ptr(out), M * N, ptr(residual),
+        # two workgroups of this kernel fit a CU: aim at (just under) 512 of them, at least four K-steps each.  Measured on the
+        # fine-tune step: 480 workgroups (5 slices of a 96-tile GEMM) 144.9 ms, 288 (3 slices) 147.1, 768 (8 slices) 148.1
+        slices = max(1, min(16, 512 // max(tiles, 1), K // 128)) if M >= 512 and plain else 1
+        return self._gemm_k_sliced(A, W, out, M, N, K, lda, ldw, slices, bias, scale, residual, epilogue=True, w_trans=w_trans)
+
+    def _gemm_k_sliced(self, A, W, out, M, N, K, lda, ldw, slices, bias=None, scale=None, residual=None, epilogue=False, **trans):
+        """out[M,N] = (A W^T + bias) * scale (+ residual) with K cut into ``slices`` (the caller's rule; more than one needs a
+        contiguous ``out``): wipa_gemm writes one [M, N] slab per slice into the shared workspace and one more launch sums them
+        in a fixed order -- wipa_sum_slabs, or wipa_sum_slabs_ex with scale and residual under ``epilogue``.  One slice: the plain
+        GEMM with everything in its own epilogue."""
+        if slices <= 1:
+            return self._gemm(A, W, out, M=M, N=N, K=K, lda=lda, ldw=ldw, ldc=out.stride(0), bias=bias, residual=residual,
+                              col_scale_n=(N if scale is not None else 0), col_scale=(scale or 1.0), **trans)
+        if self._slabs is None or self._slabs.numel() < slices * M * N:
+            self._slabs = torch.empty(slices * M * N, dtype=torch.float32, device=out.device)
+        self._gemm(A, W, self._slabs, M=M, N=N, K=K, lda=lda, ldw=ldw, ldc=N, bias=bias, k_slices=slices, slab_stride=M * N, **trans)
+        with on_stream() as s:
+            if epilogue:
+                _lib.check(self.L.wipa_sum_slabs_ex(ptr(self._slabs), slices, M * N, ptr(out), M * N, ptr(residual),
                                                     float(scale) if scale is not None else 1.0, sptr(s)), "wipa_sum_slabs_ex")
-        else:
-            self._gemm(A, W, out, M=M, N=N, K=K, lda=lda, ldw=ldw, ldc=out.stride(0), bias=bias, residual=residual,
-                       col_scale_n=(N if scale is not None else 0), col_scale=(scale or 1.0), w_trans=w_trans)
+            else:
+                _lib.check(self.L.wipa_sum_slabs(ptr(self._slabs), slices, M * N, ptr(out), M * N, 0, sptr(s)), "wipa_sum_slabs")
         return out
 
     def _transpose(self, a, rows, cols, rows_pad):
@@ -432,7 +441,7 @@ class DecoderTrainer:
                        "wipa_transpose")
         return out
 
-    def _lin_bwd(self, dy, M, N, x, xT, K, W, dW, db=None, dx=None, accumulate_dx=False, need_dx=True, dy_scaled_ok=True):
+    def _lin_bwd(self, dy, M, N, x, xT, K, W, dW, db=None, dx=None, accumulate_dx=False, need_dx=True):
         """y = x W^T + b:  dx (+)= dy W ; dW = dy^T x ; db = colsum(dy).
         dy [M(+pad), N], x [M, K]; xT = transpose(x) [K, Mp] may be passed to share it between linears."""
         Mp = _ceil(M, 32)
@@ -460,16 +469,8 @@ class DecoderTrainer:
         # weight gradient: small [N, K] output, contraction over all M tokens.  When the tile grid alone cannot fill the
         # chip (768 x 768 over 48 000 encoder positions is 36 tiles), K is split into slabs that are summed in order.
         tiles = ((N + 127) // 128) * ((K + 127) // 128)
-        slices = max(1, min(16, 512 // tiles, (Mp // 32) // 8))
-        if slices > 1 and dW.is_contiguous():
-            need = slices * N * K
-            if self._dw_slabs is None or self._dw_slabs.numel() < need:
-                self._dw_slabs = torch.empty(need, dtype=torch.float32, device=dy.device)
-            self._gemm(A_op, W_op, self._dw_slabs, M=N, N=K, K=Kc, lda=lda, ldw=ldw, ldc=K, k_slices=slices, slab_stride=N * K, **flags)
-            with on_stream() as s:
-                _lib.check(self.L.wipa_sum_slabs(ptr(self._dw_slabs), slices, N * K, ptr(dW), N * K, 0, sptr(s)), "wipa_sum_slabs")
-        else:
-            self._gemm(A_op, W_op, dW, M=N, N=K, K=Kc, lda=lda, ldw=ldw, ldc=dW.stride(0), **flags)
+        slices = max(1, min(16, 512 // tiles, (Mp // 32) // 8)) if dW.is_contiguous() else 1
+        self._gemm_k_sliced(A_op, W_op, dW, N, K, Kc, lda, ldw, slices, **flags)
         if db is not None:
             self._colsum(dy, M, N, db)
         return out_dx
@@ -495,17 +496,7 @@ class DecoderTrainer:
         clip, the padding up to Kc) must be zero, x readable and finite over all Kc rows."""
         tiles = ((n_out + 127) // 128) * ((n_in + 127) // 128)
         slices = max(1, min(16, 512 // tiles, (Kc // 32) // 8))
-        if slices > 1:
-            need = slices * n_out * n_in
-            if self._dw_slabs is None or self._dw_slabs.numel() < need:
-                self._dw_slabs = torch.empty(need, dtype=torch.float32, device=dy.device)
-            self._gemm(dy, x, self._dw_slabs, M=n_out, N=n_in, K=Kc, lda=dy.stride(0), ldw=ldx, ldc=n_in, k_slices=slices,
-                       slab_stride=n_out * n_in, a_trans=True, w_trans=True)
-            with on_stream() as s:
-                _lib.check(self.L.wipa_sum_slabs(ptr(self._dw_slabs), slices, n_out * n_in, ptr(dW), n_out * n_in, 0, sptr(s)),
-                           "wipa_sum_slabs")
-        else:
-            self._gemm(dy, x, dW, M=n_out, N=n_in, K=Kc, lda=dy.stride(0), ldw=ldx, ldc=n_in, a_trans=True, w_trans=True)
+        self._gemm_k_sliced(dy, x, dW, n_out, n_in, Kc, dy.stride(0), ldx, slices, a_trans=True, w_trans=True)
 
     def _ln(self, x, w, b):
         return ops.layernorm(x, w, b, out_dtype=torch.float32)
@@ -516,7 +507,7 @@ class DecoderTrainer:
             _lib.check(self.L.wipa_layernorm_bwd(ptr(x), ptr(dy), ptr(w), ptr(dx), int(accumulate), ptr(dw), ptr(db), ptr(stats),
                                                  stats.numel(), M, D, 1e-5, sptr(s)), "wipa_layernorm_bwd")
 
-    def _attn(self, q, k, v, B, H, Tq, Tk, causal, k_rows_per_batch):
+    def _attn(self, q, k, v, B, H, Tq, Tk, causal):
         """q [B*Tq, d], k/v [B*Tk, d] row-major -> (out [B*Tq, d], lse [B,H,Tq], desc)"""
         d = H * 64
         with on_stream() as s:
@@ -545,6 +536,32 @@ class DecoderTrainer:
                                                  ptr(dvec), QK_SCALE, sptr(s)), "wipa_attention_bwd")
 
     # ---- forward + backward ------------------------------------------------------------
+    def _self_attn_fwd(self, pre: str, S: Dict, x: torch.Tensor, B: int, T: int, H: int, causal: bool) -> torch.Tensor:
+        """the self-attention half of block ``pre`` (decoder or encoder) on x [B*T, d]: LayerNorm, q, k, v, attention, out +
+        residual.  Fills what _self_attn_bwd reads (x_a, h1, q, k, v, a, lse1, desc1) and returns x_b."""
+        W = self.w
+        M, d = B * T, H * 64
+        S["x_a"] = x
+        S["h1"] = self._ln(x, W(f"{pre}.attn_ln.weight"), W(f"{pre}.attn_ln.bias"))
+        S["q"] = self._lin(S["h1"], M, d, W(f"{pre}.attn.query.weight"), d, W(f"{pre}.attn.query.bias"), QK_SCALE)
+        S["k"] = self._lin(S["h1"], M, d, W(f"{pre}.attn.key.weight"), d, None, QK_SCALE)
+        S["v"] = self._lin(S["h1"], M, d, W(f"{pre}.attn.value.weight"), d, W(f"{pre}.attn.value.bias"))
+        S["a"], S["lse1"], S["desc1"] = self._attn(S["q"], S["k"], S["v"], B, H, T, T, causal)
+        return self._lin(S["a"], M, d, W(f"{pre}.attn.out.weight"), d, W(f"{pre}.attn.out.bias"), residual=x)
+
+    def _mlp_fwd(self, pre: str, S: Dict, x_c: torch.Tensor) -> torch.Tensor:
+        """the MLP half of block ``pre`` (decoder or encoder) on x_c [M, d]: LayerNorm, mlp1, GELU, mlp2 + residual.  Fills what
+        _mlp_bwd reads (x_c, h3, z, u) and returns the block's output."""
+        W = self.w
+        M, d = x_c.shape
+        S["x_c"] = x_c
+        S["h3"] = self._ln(x_c, W(f"{pre}.mlp_ln.weight"), W(f"{pre}.mlp_ln.bias"))
+        S["z"] = self._lin(S["h3"], M, d, W(f"{pre}.mlp1.weight"), 4 * d, W(f"{pre}.mlp1.bias"))
+        S["u"] = torch.empty_like(S["z"])
+        with on_stream() as s:
+            _lib.check(self.L.wipa_gelu(ptr(S["z"]), ptr(S["u"]), S["z"].numel(), sptr(s)), "wipa_gelu")
+        return self._lin(S["u"], M, 4 * d, W(f"{pre}.mlp2.weight"), d, W(f"{pre}.mlp2.bias"), residual=x_c)
+
     def _forward(self, audio_features: torch.Tensor, tok_in: torch.Tensor):
         """Teacher-forced decoder on ``tok_in`` [B, T] int32 (device, contiguous) and features [B, 1500, d]: returns the
         zero-padded logits [ceil32(B*T), ceil32(V)] f32 and the saved activations the backward needs."""
@@ -568,13 +585,8 @@ class DecoderTrainer:
             saved = []
             for l in range(dm.n_text_layer):
                 pre = f"decoder.blocks.{l}"
-                S = {"x_a": x}
-                S["h1"] = self._ln(x, P(f"{pre}.attn_ln.weight"), P(f"{pre}.attn_ln.bias"))
-                S["q"] = self._lin(S["h1"], M, d, P(f"{pre}.attn.query.weight"), d, P(f"{pre}.attn.query.bias"), QK_SCALE)
-                S["k"] = self._lin(S["h1"], M, d, P(f"{pre}.attn.key.weight"), d, None, QK_SCALE)
-                S["v"] = self._lin(S["h1"], M, d, P(f"{pre}.attn.value.weight"), d, P(f"{pre}.attn.value.bias"))
-                S["a"], S["lse1"], S["desc1"] = self._attn(S["q"], S["k"], S["v"], B, H, T, T, True, T)
-                S["x_b"] = self._lin(S["a"], M, d, P(f"{pre}.attn.out.weight"), d, P(f"{pre}.attn.out.bias"), residual=x)
+                S = {}
+                S["x_b"] = self._self_attn_fwd(pre, S, x, B, T, H, causal=True)
                 S["h2"] = self._ln(S["x_b"], P(f"{pre}.cross_attn_ln.weight"), P(f"{pre}.cross_attn_ln.bias"))
                 S["qc"] = self._lin(S["h2"], M, d, P(f"{pre}.cross_attn.query.weight"), d, P(f"{pre}.cross_attn.query.bias"), QK_SCALE)
                 # cross key | value as ONE projection over the B*1500 encoder rows: key.weight and value.weight are adjacent in
@@ -585,14 +597,9 @@ class DecoderTrainer:
                 self._gemm(feats, self._kv_pair(self.flat_p, pre), kv, M=B * Ta, N=2 * d, K=d, lda=d, ldw=d, ldc=2 * d, bias=bkv,
                            col_scale_n=d, col_scale=QK_SCALE)
                 S["kc"], S["vc"] = kv[:, :d], kv[:, d:]
-                S["c"], S["lse2"], S["desc2"] = self._attn(S["qc"], S["kc"], S["vc"], B, H, T, Ta, False, Ta)
-                S["x_c"] = self._lin(S["c"], M, d, P(f"{pre}.cross_attn.out.weight"), d, P(f"{pre}.cross_attn.out.bias"),
-                                     residual=S["x_b"])
-                S["h3"] = self._ln(S["x_c"], P(f"{pre}.mlp_ln.weight"), P(f"{pre}.mlp_ln.bias"))
-                S["z"] = self._lin(S["h3"], M, d, P(f"{pre}.mlp1.weight"), 4 * d, P(f"{pre}.mlp1.bias"))
-                S["u"] = torch.empty_like(S["z"])
-                _lib.check(L.wipa_gelu(ptr(S["z"]), ptr(S["u"]), S["z"].numel(), sptr(s)), "wipa_gelu")
-                x = self._lin(S["u"], M, 4 * d, P(f"{pre}.mlp2.weight"), d, P(f"{pre}.mlp2.bias"), residual=S["x_c"])
+                S["c"], S["lse2"], S["desc2"] = self._attn(S["qc"], S["kc"], S["vc"], B, H, T, Ta, False)
+                x_c = self._lin(S["c"], M, d, P(f"{pre}.cross_attn.out.weight"), d, P(f"{pre}.cross_attn.out.bias"), residual=S["x_b"])
+                x = self._mlp_fwd(pre, S, x_c)
                 saved.append(S)
             x_L = x
             hf = self._ln(x_L, P("decoder.ln.weight"), P("decoder.ln.bias"))
@@ -602,13 +609,28 @@ class DecoderTrainer:
         ctx = dict(saved=saved, x_L=x_L, hf=hf, feats=feats, featsT=featsT, tok_in=tok_in, B=B, T=T)
         return logits, ctx
 
-    def _backward(self, ctx: Dict, dlogits: torch.Tensor, group=None, d_feats: Optional[torch.Tensor] = None):
+    def _new_reducer(self, group) -> "parallel.SegmentReducer":
+        """the reducer of one backward over self.flat_g, no segment handed over yet"""
+        self._segments_done = 0
+        return parallel.SegmentReducer(self.flat_g, group)
+
+    def _reduce_segment(self, reducer, label: str) -> None:
+        """Hand the finished gradient segment ``label`` of self.segments to ``reducer``.  DP: it is all-reduced (SUM; every rank
+        already divided by the GLOBAL count) asynchronously on RCCL's stream while the earlier blocks are still in their
+        backward.  The backward finishes the segments in flat_layout's order, nothing else."""
+        i = self._segments_done
+        due = self.segments[i][0] if i < len(self.segments) else None
+        if label != due:
+            raise _lib.WipaError(f"DecoderTrainer: the backward finished gradient segment {label!r} where flat_layout has {due!r} next")
+        self._segments_done = i + 1
+        reducer.reduce(*self.segments[i][1:])
+
+    def _backward(self, ctx: Dict, dlogits: torch.Tensor, reducer, d_feats: Optional[torch.Tensor] = None) -> None:
         """Reverse pass from ``dlogits`` [ceil32(B*T), ceil32(V)] f32 (zero in the padding; consumed) into self.flat_g: the
-        gradient of every ``decoder.*`` tensor, tied embedding included.  Under DP every finished segment of the flat
-        buffer is all-reduced (SUM) asynchronously while the earlier blocks are still in their backward.
+        gradient of every ``decoder.*`` tensor, tied embedding included.  Every finished segment goes to ``reducer``
+        (_reduce_segment), which the caller made (_new_reducer) and joins (_join_reductions).
         ``d_feats`` [B*N, d] (trainers that train encoder layers): receives the gradient of the encoder output, summed over the
-        decoder layers in the order the backward visits them; the SegmentReducer is then returned with its reductions still in
-        flight, for _encoder_backward to go on with."""
+        decoder layers in the order the backward visits them."""
         m, dm, L = self.model, self.model.dims, self.L
         P, G = self.p, self.g
         saved, x_L, hf, feats, featsT, tok_in = ctx["saved"], ctx["x_L"], ctx["hf"], ctx["feats"], ctx["featsT"], ctx["tok_in"]
@@ -630,14 +652,7 @@ class DecoderTrainer:
             del dlT, dlogits
             dx = torch.empty(M, d, dtype=torch.float32, device=dev)
             self._ln_bwd(x_L, dhf, P("decoder.ln.weight"), dx, False, G("decoder.ln.weight"), G("decoder.ln.bias"), M, d)
-            # DP: each finished gradient segment is all-reduced (SUM; every rank already divided by the GLOBAL
-            # count) asynchronously on RCCL's stream while the earlier blocks are still in their backward
-            reducer = parallel.SegmentReducer(self.flat_g, group)
-
-            def reduce_segment(rng):
-                reducer.reduce(rng[0], rng[1])
-
-            reduce_segment(self.tail_range)
+            self._reduce_segment(reducer, "decoder.tail")
             for l in reversed(range(dm.n_text_layer)):
                 pre = f"decoder.blocks.{l}"
                 S = saved[l]
@@ -649,13 +664,10 @@ class DecoderTrainer:
                 dkv = torch.empty(B * Ta, 2 * d, dtype=torch.float32, device=dev)  # d(key) | d(value), strides of the forward's kv
                 dkc, dvc = dkv[:, :d], dkv[:, d:]
                 self._attn_bwd(S["desc2"], S["c"], dc, S["lse2"], dqc, dkc, dvc)
-                if d_feats is None:
-                    # one weight-gradient GEMM for the [2d, d] pair (no input gradient: the encoder is frozen); value bias apart
-                    self._lin_bwd(dkv, B * Ta, 2 * d, feats, featsT, d, self._kv_pair(self.flat_p, pre), self._kv_pair(self.flat_g, pre),
-                                  None, need_dx=False)
-                else:  # ... and the pair's input gradient, which is the encoder output's: the last decoder layer writes it, the others add
-                    self._lin_bwd(dkv, B * Ta, 2 * d, feats, featsT, d, self._kv_pair(self.flat_p, pre), self._kv_pair(self.flat_g, pre),
-                                  None, dx=d_feats, accumulate_dx=(l != dm.n_text_layer - 1))
+                # one weight-gradient GEMM for the [2d, d] pair, value bias apart.  Its input gradient is the encoder output's: none
+                # while the encoder is frozen; else the last decoder layer writes d_feats and the others add
+                self._lin_bwd(dkv, B * Ta, 2 * d, feats, featsT, d, self._kv_pair(self.flat_p, pre), self._kv_pair(self.flat_g, pre),
+                              None, dx=d_feats, accumulate_dx=(l != dm.n_text_layer - 1), need_dx=d_feats is not None)
                 self._colsum(dvc, B * Ta, d, G(f"{pre}.cross_attn.value.bias"))
                 del dkv, dkc, dvc
                 dh2 = self._lin_bwd(dqc, M, d, S["h2"], None, d, P(f"{pre}.cross_attn.query.weight"), G(f"{pre}.cross_attn.query.weight"),
@@ -664,20 +676,19 @@ class DecoderTrainer:
                              G(f"{pre}.cross_attn_ln.bias"), M, d)
                 self._self_attn_bwd(pre, S, dx, B, M, Mp, d)
                 saved[l] = None
-                reduce_segment(self.block_ranges[l])
+                self._reduce_segment(reducer, pre)
             _lib.check(L.wipa_embed_bwd(ptr(tok_in), ptr(dx), B, T, d, ptr(G("decoder.token_embedding.weight")),
                                         ptr(G("decoder.positional_embedding")), sptr(s)), "wipa_embed_bwd")
             if T < dm.n_text_ctx:
                 G("decoder.positional_embedding")[T:].zero_()
-            reduce_segment(self.head_range)
-            if d_feats is not None:
-                return reducer
-            # the time the compute stream stalls here is the all-reduce time the backward did NOT hide
-            self._ar_events = None
-            self._join_reductions(reducer, s)
-        return None
+            self._reduce_segment(reducer, "decoder.head")
 
     def _join_reductions(self, reducer, s) -> None:
+        """wait for every segment's all-reduce on the compute stream ``s``: the time it stalls here is the all-reduce time the
+        backward did NOT hide (last_allreduce_exposed_ms)"""
+        self._ar_events = None
+        if self._segments_done != len(self.segments):
+            raise _lib.WipaError(f"DecoderTrainer: the backward finished {self._segments_done} of {len(self.segments)} gradient segments")
         if reducer.pending:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(s)
@@ -719,8 +730,8 @@ class DecoderTrainer:
     def _encoder_forward(self, mel: torch.Tensor, clip_keys=None, n_frames=None):
         """AudioEncoder.__call__ in f32 on a mel [B, 3000, n_mels] (or [B, 2N, n_mels] with ``model.audio_ctx`` = N), composed
         from the per-kernel entry points like the decoder's _forward: conv1 and conv2 as GEMMs over overlapping rows of the
-        padded layouts wipa_encoder_forward uses (their PRE-GELU values kept), then per block LayerNorm, q, k, v, non-causal
-        wipa_attention (log-sum-exp saved), out + residual, LayerNorm, mlp1, GELU, mlp2 + residual, then ln_post.  Blocks below
+        padded layouts wipa_encoder_forward uses (their PRE-GELU values kept), then per block the two halves the decoder's blocks
+        have as well (_self_attn_fwd, non-causal, and _mlp_fwd), then ln_post.  Blocks below
         the first trained one are not saved (their buffers go back to the allocator as the walk leaves them), and the stem's
         only under "all".  Returns (features [B, N, d], what _encoder_backward needs)."""
         m, dm, L = self.model, self.model.dims, self.L
@@ -728,19 +739,18 @@ class DecoderTrainer:
         d, H, N, n_mels = dm.n_audio_state, dm.n_audio_head, m.n_audio_ctx, dm.n_mels
         if mel.dim() == 2:
             mel = mel[None]
-        B, F, R = mel.shape[0], 2 * N, 2 * N + 2  # R rows per clip in the padded layouts: a zero halo row either side
+        B, F = mel.shape[0], 2 * N
         full = 2 * dm.n_audio_ctx
         if mel.shape[1] not in (full, F) or mel.shape[2] != n_mels:
             raise _lib.WipaError(f"DecoderTrainer: a mel of shape {tuple(mel.shape)}, expected [B, {full}, {n_mels}]"
                                  + (f" or [B, {F}, {n_mels}] (audio_ctx={m.audio_ctx})" if F != full else ""))
-        M, M1, M2 = B * N, B * R, B * (N + 1)
-        Kc1, Kc2 = _ceil(M1, 32), _ceil(M2, 32)  # contraction lengths of the two weight-gradient GEMMs (_stem_backward)
-        K1 = _ceil(3 * n_mels, 32)
+        M, K1 = B * N, _ceil(3 * n_mels, 32)
+        rows = _stem_rows(B, N)
+        R, M1, M2 = rows.R, rows.M1, rows.M2
         with on_stream() as s:
             dev = m.device
             mel32 = mel.to(device=dev, dtype=torch.float32).contiguous()
-            # frame t of clip b at row b*R + t + 1; rows past B*R + 4 exist (as zeros) for the weight gradient's padded contraction
-            padded = torch.zeros(max(M1 + 4, Kc1 + 3), n_mels, dtype=torch.float32, device=dev)
+            padded = torch.zeros(rows.padded, n_mels, dtype=torch.float32, device=dev)  # frame t of clip b at row b*R + t + 1
             _lib.check(L.wipa_mel_pad_cast_frames(ptr(mel32), mel32.shape[1] * n_mels, B, n_mels, F, ptr(padded), 0, sptr(s)),
                        "wipa_mel_pad_cast_frames")
             if self._spec_augment is not None:
@@ -749,7 +759,7 @@ class DecoderTrainer:
             w1[:, : 3 * n_mels].copy_(W("encoder.conv1.weight").reshape(d, 3 * n_mels))
             # conv1 (k3, p1), pre-activation: GEMM row g = b*R + t reads the padded rows g..g+2 and lands at row g + 1; the two
             # dead rows of each clip are written as zero -- gelu(0) = 0, so one GELU over the buffer leaves conv2's halos zero
-            z1 = torch.zeros(max(M1 + 4, 2 * Kc2 + 2), d, dtype=torch.float32, device=dev)
+            z1 = torch.zeros(rows.z1, d, dtype=torch.float32, device=dev)
             self._gemm(padded, w1, z1, M=M1, N=d, K=K1, lda=n_mels, ldw=K1, ldc=d, bias=W("encoder.conv1.bias"), rg_in=R, rg_valid=F,
                        rg_stride=R * d, c_offset=d, zero_invalid_rows=True)
             c1 = torch.empty_like(z1)
@@ -765,21 +775,11 @@ class DecoderTrainer:
             saved = {}
             for l in range(dm.n_audio_layer):
                 pre = f"encoder.blocks.{l}"
-                S = {"x_a": x}
-                S["h1"] = self._ln(x, W(f"{pre}.attn_ln.weight"), W(f"{pre}.attn_ln.bias"))
-                S["q"] = self._lin(S["h1"], M, d, W(f"{pre}.attn.query.weight"), d, W(f"{pre}.attn.query.bias"), QK_SCALE)
-                S["k"] = self._lin(S["h1"], M, d, W(f"{pre}.attn.key.weight"), d, None, QK_SCALE)
-                S["v"] = self._lin(S["h1"], M, d, W(f"{pre}.attn.value.weight"), d, W(f"{pre}.attn.value.bias"))
-                S["a"], S["lse1"], S["desc1"] = self._attn(S["q"], S["k"], S["v"], B, H, N, N, False, N)
-                S["x_c"] = self._lin(S["a"], M, d, W(f"{pre}.attn.out.weight"), d, W(f"{pre}.attn.out.bias"), residual=x)
-                S["h3"] = self._ln(S["x_c"], W(f"{pre}.mlp_ln.weight"), W(f"{pre}.mlp_ln.bias"))
-                S["z"] = self._lin(S["h3"], M, d, W(f"{pre}.mlp1.weight"), 4 * d, W(f"{pre}.mlp1.bias"))
-                S["u"] = torch.empty_like(S["z"])
-                _lib.check(L.wipa_gelu(ptr(S["z"]), ptr(S["u"]), S["z"].numel(), sptr(s)), "wipa_gelu")
-                x = self._lin(S["u"], M, 4 * d, W(f"{pre}.mlp2.weight"), d, W(f"{pre}.mlp2.bias"), residual=S["x_c"])
+                S = {}
+                x = self._mlp_fwd(pre, S, self._self_attn_fwd(pre, S, x, B, N, H, causal=False))
                 if l >= self._enc_first:
                     saved[l] = S
-                del S
+                del S  # of a block that is not trained: its buffers go back to the allocator here
             feats = self._ln(x, W("encoder.ln_post.weight"), W("encoder.ln_post.bias"))
         return feats.view(B, N, d), dict(saved=saved, x_L=x, stem=stem, B=B, N=N)
 
@@ -795,18 +795,20 @@ class DecoderTrainer:
         with on_stream():
             dx = torch.empty(M, d, dtype=torch.float32, device=d_feats.device)
             self._ln_bwd(x_L, d_feats, P("encoder.ln_post.weight"), dx, False, G("encoder.ln_post.weight"), G("encoder.ln_post.bias"), M, d)
-            reducer.reduce(*self.enc_ln_post_range)
+            self._reduce_segment(reducer, "encoder.ln_post")
             for l in reversed(range(self._enc_first, dm.n_audio_layer)):
                 pre = f"encoder.blocks.{l}"
                 S = saved[l]
                 self._mlp_bwd(pre, S, dx, M, d)
-                self._self_attn_bwd(pre, S, dx, B, M, Mp, d, split=self.f32_split and self.ENCODER_ATTN_BWD_SPLIT)
+                # an f32_split trainer takes the split-product attention kernels here: faster at encoder shapes, the A/B against the
+                # exact kernels is in profiles/encoder_train_bench.txt
+                self._self_attn_bwd(pre, S, dx, B, M, Mp, d, split=self.f32_split)
                 saved[l] = None
                 del S
-                reducer.reduce(*self.enc_block_ranges[l])
+                self._reduce_segment(reducer, pre)
             if self._train_stem:
                 self._stem_backward(ectx["stem"], dx, B, N)
-                reducer.reduce(*self.enc_stem_range)
+                self._reduce_segment(reducer, "encoder.stem")
 
     def _stem_backward(self, stem: Dict, dx: torch.Tensor, B: int, N: int) -> torch.Tensor:
         """conv2 and conv1 from ``dx`` [B*N, d], the gradient of the stem's output x = gelu(z2) + positional table (the table is
@@ -817,9 +819,9 @@ class DecoderTrainer:
         dm, L = self.model.dims, self.L
         P, G = self.w, self.g
         d, n_mels = dm.n_audio_state, dm.n_mels
-        R = 2 * N + 2
-        M, M1, M2 = B * N, B * R, B * (N + 1)
-        Kc1, Kc2 = _ceil(M1, 32), _ceil(M2, 32)
+        M = B * N
+        rows = _stem_rows(B, N)
+        R, M1, M2, Kc1, Kc2 = rows.R, rows.M1, rows.M2, rows.Kc1, rows.Kc2
         padded, z1, c1, z2 = stem["padded"], stem["z1"], stem["c1"], stem["z2"]
         with on_stream() as s:
             dev = dx.device
@@ -896,15 +898,13 @@ class DecoderTrainer:
             loss = sum_ce / torch.clamp(n_valid, min=1.0)
             _lib.check(L.wipa_masked_ce_bwd(ptr(logits), Vp, ptr(tok), T1, B, T, V, ptr(row_buf[M:]), ptr(count), sptr(s)),
                        "wipa_masked_ce_bwd")
-            if ectx is None:
-                self._backward(ctx, logits, group)
-            else:
-                d_feats = torch.empty_like(ctx["feats"])
-                reducer = self._backward(ctx, logits, group, d_feats=d_feats)
-                del ctx, logits
+            reducer = self._new_reducer(group)
+            d_feats = None if ectx is None else torch.empty_like(ctx["feats"])
+            self._backward(ctx, logits, reducer, d_feats)
+            del ctx, logits
+            if ectx is not None:
                 self._encoder_backward(ectx, d_feats, reducer)
-                self._ar_events = None
-                self._join_reductions(reducer, s)
+            self._join_reductions(reducer, s)
         return loss, sum_ce, n_valid
 
     # ---- torch.autograd surface: Whisper.logits differentiable w.r.t. the decoder tensors (train_whisper_ipa.py:232,284) ----
@@ -924,8 +924,6 @@ class DecoderTrainer:
         torch.autograd.Function, so ANY torch-written loss on the logits gets exact decoder gradients.  The backward WRITES
         self.flat_g (zeroed first: gradients accumulated there by loss_and_grads are lost) and returns clones of every decoder
         gradient as the leaves' .grad (one more copy of the decoder's size); it reduces over no process group."""
-        from . import parallel
-
         self._decoder_only("differentiable_logits")
         if parallel.world()[1] != 1:
             raise _lib.WipaError("differentiable_logits is single-process (its backward runs without the data-parallel group); "
@@ -938,7 +936,7 @@ class DecoderTrainer:
     def last_allreduce_exposed_ms(self) -> float:
         """Exposed (not overlapped with the backward) gradient all-reduce time of the last step, from HIP events on the
         compute stream around the final waits; 0 for a single process.  Synchronises."""
-        ev = getattr(self, "_ar_events", None)
+        ev = self._ar_events
         if not ev:
             return 0.0
         ev[1].synchronize()
@@ -969,13 +967,10 @@ class DecoderTrainer:
         if self.trains_encoder or self._spec_augment is not None:
             # encoder forward that saves activations, decoder forward / backward, encoder backward (no feature cache: refused)
             loss, _, _ = self.loss_and_grads_from_mel(mel, tokens, eot, group, clip_keys, n_frames)
-            self.apply_update()
-            return loss, self.grads()
-        if clip_keys is not None and self.feature_cache is not None:
-            feats = self.feature_cache.assemble(clip_keys, mel)
         else:
-            feats = self.model.embed_audio(mel)
-        loss, _, _ = self.loss_and_grads(feats, tokens, eot, group)
+            cached = clip_keys is not None and self.feature_cache is not None
+            feats = self.feature_cache.assemble(clip_keys, mel) if cached else self.model.embed_audio(mel)
+            loss, _, _ = self.loss_and_grads(feats, tokens, eot, group)
         self.apply_update()
         return loss, self.grads()
 
@@ -1003,12 +998,13 @@ class _DecoderLogits(torch.autograd.Function):
         tr = ctx.trainer
         B, T, Mp, Vp = ctx.shape
         V = tr.model.dims.n_vocab
-        with on_stream():
+        with on_stream() as s:
             dl = torch.zeros(Mp, Vp, dtype=torch.float32, device=tr.model.device)
             dl[: B * T].view(B, T, Vp)[:, :, :V].copy_(dlogits)
-        tr._backward(ctx.saved_acts, dl)
-        ctx.saved_acts = None
-        with on_stream():
+            reducer = tr._new_reducer(None)  # single-process (differentiable_logits refuses anything else): nothing to reduce
+            tr._backward(ctx.saved_acts, dl, reducer)
+            tr._join_reductions(reducer, s)
+            ctx.saved_acts = None
             grads = tuple(tr.g(n).clone() for n in tr.names)
         return (None, None, None) + grads
 
