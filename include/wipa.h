@@ -499,7 +499,7 @@ typedef struct wipa_decode_rules {
 int wipa_timestamp_step(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
                         int32_t* tokens, int64_t ld_tok, const int32_t* pos_dev, int n_init, int eot, const wipa_decode_rules* rules,
                         float* sum_logprobs, int32_t* not_done, wipa_stream_t s);
-/* wipa_greedy_step_embed with the rules: the tail of a decode step under wipa_decoder_run_rules */
+/* wipa_greedy_step_embed with the rules: the tail of a decode step with wipa_decode_call.rules */
 int wipa_timestamp_step_embed(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always,
                               int32_t* tokens, int64_t ld_tok, int32_t* pos_dev, int64_t* posd_dev, int32_t* done_counter, int n_init,
                               int eot, const wipa_decode_rules* rules, float* sum_logprobs, int32_t* not_done, const void* tok_emb,
@@ -529,7 +529,7 @@ size_t wipa_sample_record_bytes(int B);
 int wipa_sample_record_fill(void* host_record, size_t record_bytes, uint64_t seed, int attempt, float temperature,
                             const uint32_t* streams, int B);
 /* The SAMPLING RECORD WITH A ROW PART: a second form, for a decode whose rows differ in temperature and attempt (continuous batching
- * with the temperature fallback: wipa_decoder_run_continuous_rows).  One caller-owned DEVICE buffer of wipa_sample_rows_bytes(B)
+ * with the temperature fallback: wipa_decode_call.sample_rows).  One caller-owned DEVICE buffer of wipa_sample_rows_bytes(B)
  * = 16 + 16 * B bytes, 16-byte aligned:
  *   offset  0  uint32 seed_lo          offset  8  uint32 B (the rows the buffer holds)
  *   offset  4  uint32 seed_hi          offset 12  uint32 0
@@ -581,7 +581,7 @@ int wipa_embed_layernorm(const int32_t* tokens, int64_t ld_tok, int B, const int
                          const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b,
                          void* y, int y_dtype, int D, float eps, wipa_stream_t s);
 
-/* Ragged prompts (prompt conditioning: wipa_decoder_begin_ragged / wipa_decoder_run_ragged below).  The rows of a batch carry prompts
+/* Ragged prompts (prompt conditioning: wipa_decoder_begin_ragged / wipa_decode_call.starts_dev below).  The rows of a batch carry prompts
  * of different lengths RIGHT-ALIGNED to one common width P: row b's own tokens sit in columns [start[b], P) of tokens[b], columns below
  * start[b] are padding (token 0, never looked at), generation starts at column P for every row, and ONE position counter serves the
  * batch.  starts_dev: int32 [B] on the device, required by every *_ragged entry point.  Per row then:
@@ -829,29 +829,83 @@ int wipa_decoder_run(const wipa_model_cfg* cfg, const void* const* weights, void
  * prompt through the decoder in one forward).  Continue with wipa_decoder_run for the remaining steps. */
 int wipa_decoder_prefill(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
                          int eot, const float* mask_first, const float* mask_always, int use_graph, wipa_stream_t s);
-/* wipa_decoder_run / wipa_decoder_prefill with the timestamp rules (wipa_decode_rules above) in every greedy update: the step's
- * tail is wipa_timestamp_step_embed, the prompt pass ends with wipa_timestamp_step (rule 4 acts on the first sampled token).
- * rules == NULL enqueues exactly what the plain entry points enqueue.  The rules are part of the step graph's and the prefill
- * graph's key.  With rules every step writes its logits and the row-scan tail reads them (the per-wave partials of
- * wipa_logits_greedy cannot carry rules that depend on the row's history).  A configuration whose step does not end in the fused
- * tail (WIPA_DECODE_TAIL=0, WIPA_DECODE_FUSED=1) is refused with WIPA_ERR_ARG: it is never decoded without the rules. */
-int wipa_decoder_run_rules(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int n_init,
-                           int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
-                           const wipa_decode_rules* rules, wipa_stream_t s);
-int wipa_decoder_prefill_rules(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
-                               int eot, const float* mask_first, const float* mask_always, int use_graph,
-                               const wipa_decode_rules* rules, wipa_stream_t s);
-/* wipa_decoder_run_rules / wipa_decoder_prefill_rules at a temperature above 0: `sample` is the device sampling record
- * (wipa_sample_record_bytes above), rules may be NULL.  The step's tail is wipa_sample_step_embed, the prompt pass ends with
- * wipa_sample_step; sampling steps write their logits and use the row-scan tail, like steps with rules.  sample == NULL enqueues
- * exactly what wipa_decoder_run[_rules] / wipa_decoder_prefill[_rules] enqueue.  The graph key holds the record's ADDRESS, not its
- * contents: rewriting seed, attempt, temperature or streams replays the same graph.  wipa_dec_layout does not change. */
-int wipa_decoder_run_sample(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int n_init,
-                            int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
-                            const wipa_decode_rules* rules, const void* sample, wipa_stream_t s);
-int wipa_decoder_prefill_sample(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
-                                int eot, const float* mask_first, const float* mask_always, int use_graph,
-                                const wipa_decode_rules* rules, const void* sample, wipa_stream_t s);
+/* ONE DECODE CALL: what a call asks of its steps beyond the plain greedy update.  Every optional field is 0 / NULL for "not used"; a
+ * call that holds only n_init, eot and the masks enqueues exactly what wipa_decoder_run / wipa_decoder_prefill enqueue.  The library
+ * reads the struct during the call only and keeps no pointer to it: the step and prefill graphs are keyed on the VALUES of its fields
+ * (integers, and the addresses the pointers hold), never on the address of the struct.  What the configuration's step cannot serve is
+ * refused (WIPA_ERR_ARG, nothing enqueued) in a message that names the entry point and the field -- it is never decoded without it:
+ *   rules, sample, sample_rows, starts_dev, beam and cfg.dec_n_group > 1 need the unfused step with the fused tail (not WIPA_DECODE_TAIL=0,
+ *   not WIPA_DECODE_FUSED=1);  starts_dev, continuous and beam need bf16 / f32 decoder tables (cfg.dec_w_dtype == 0);  continuous needs
+ *   cfg.dec_n_group == 1;  B is a multiple of cfg.dec_n_group.
+ * Fields that exclude or need each other: sample and sample_rows exclude each other; sample_rows, no_speech_dev and prompted need
+ * continuous; continuous needs starts_dev; no_speech_dev needs rules; beam excludes sample, sample_rows, starts_dev and continuous;
+ * wipa_decoder_prefill_ex takes none of starts_dev, continuous, prompted, sample_rows, no_speech_dev (the prompt pass of rows with
+ * their own prompts is wipa_decoder_prefill_ragged, that of an admitted clip belongs to wipa_decoder_admit_rows_prompted). */
+typedef struct wipa_decode_call {
+    /* prompt columns (with starts_dev: the common prompt width P, 1..n_text_ctx; continuous: 1..4 initial tokens per clip; the prompt pass:
+     * 1..4) and the end-of-text id */
+    int32_t n_init, eot;
+    /* additive f32 [n_vocab] masks of the first generated token and of every later one */
+    const float *mask_first, *mask_always;
+    /* The timestamp rules (wipa_decode_rules above) in every greedy update: the step's tail is wipa_timestamp_step_embed, the prompt pass
+     * ends with wipa_timestamp_step (rule 4 acts on the first sampled token).  The three values are part of the step graph's and the prefill
+     * graph's key.  With rules every step writes its logits and the row-scan tail reads them (the per-wave partials of wipa_logits_greedy
+     * cannot carry rules that depend on the row's history), so no step of the call is lean. */
+    const wipa_decode_rules* rules;
+    /* A temperature above 0: the device sampling record (wipa_sample_record_bytes above); rules may be given or not.  The step's tail is
+     * wipa_sample_step_embed, the prompt pass ends with wipa_sample_step; sampling steps write their logits and use the row-scan tail, like
+     * steps with rules: the draw needs every alive column of the row.  The graph key holds the record's ADDRESS, not its contents: rewriting
+     * seed, attempt, temperature or streams replays the same graph.  wipa_dec_layout does not change. */
+    const void* sample;
+    /* continuous with a TEMPERATURE PER ROW: the sampling record with a row part (wipa_sample_rows_bytes above, 16-byte aligned).  It takes
+     * the place of `sample`, and the steps end in the rows_tail_continuous kernels: the four cases per row, the rules on the row's own
+     * sequence, the no-speech store and the counter's own position p - start[b] stay; a row whose 1 / temperature is 0 takes the greedy
+     * pick, every other row the draw at its own temperature, attempt and stream -- a retried window beside first attempts and beside
+     * retries at other temperatures, in ONE launch.  wipa_decoder_admit_rows is called with sample == NULL, and wipa_sample_rows_set for the
+     * same slots.  The step graph's key is that of the call without the record plus a variant bit and the record's address.  On bf16 the
+     * logits projection writes the logits.  Without rules a greedy row's pick is row_pick's arg-max (the same token as without the record;
+     * its log-probability sums the exponentials in the rules tails' order). */
+    const void* sample_rows;
+    /* Rows with their own first column, on the device, caller-owned; its ADDRESS is part of the step graph's key, the replayed kernels read
+     * it.  With it the step's self-attention, its tail and its head are the RAGGED instantiations, and every step writes its logits and
+     * ends in the row-scan tail (as with rules).  What it holds follows the call:
+     *   int32 [B]     per-row prompts (after wipa_decoder_begin_ragged): the rows' first own columns; n_init = P.  The prompt is walked one
+     *                 column per step ("p + 1 < n_init: the given token is taken"); column P is the first generated one for every row.
+     *                 n_steps <= n_text_ctx - 1 (the position lives on the device and a call may include the P - 1 steps of the prompt walk,
+     *                 so this is the bound that holds at every position; the caller keeps P + new tokens <= n_text_ctx).
+     *   int32 [2][B]  continuous: first own columns, then the tokens each row may generate (see "Continuous batching" below)
+     *   int32 [3][B]  continuous and prompted: window starts, token limits, prompt columns (see "a PROMPT PER ROW" below) */
+    const int32_t* starts_dev;
+    /* Continuous batching: the B rows are slots and the step ends in the CONTINUOUS tails (a prompt end per row); everything before the
+     * tail is the ragged step.  The step graph's key is that of the ragged call plus a variant bit; admissions and shifts replay the same
+     * graph.  With rules the pick applies them to the row's OWN sequence, the tokens of columns own .. p: its length is p + 1 - own, the pick at
+     * p + 1 == own is the first one (mask_first; text dead, timestamps capped by max_initial_timestamp_index), and no token below own is
+     * looked at -- those are the slot's previous clip, which usually ended in timestamps, or the prompt.  A shift moves the starts and the
+     * tokens together, so a pick cannot see it.  With a sampling record the draw's counter takes the row's own position p - start[b]. */
+    int32_t continuous;
+    /* continuous with a prompt per row: the step ends in the PROMPTED tails (the sot sequence stands behind the row's prompt): own =
+     * start + L + n_init, the no-speech store at column start + L, the rules on tk[own .. p], the draw's counter p - start (the row's position
+     * in its own unpadded sequence).  Head and attention are the RAGGED kernels as they are.  The key gains a variant bit of its own. */
+    int32_t prompted;
+    /* continuous with rules: float [B] on the device, caller-owned.  At the step whose column is a row's first own one (p == start[b],
+     * limit > 0: the row's <|startoftranscript|>, upstream's logits[:, sot_index]) the tail writes softmax(logits row)[no_speech_token] of
+     * the UNFILTERED row to no_speech_dev[b], with a plain store; the value stays until the slot's next admission reaches that step.  Its
+     * address and no_speech_token (a vocabulary column) are part of the step graph's key. */
+    float* no_speech_dev;
+    int32_t no_speech_token;
+    /* Beam search (below): the caller's beam buffer, its size (at least wipa_beam_bytes) and the size of a clip's finished store (1..64).
+     * The rows are clips x cfg.dec_n_group beams (1..16); the self-attention reads the cache through the buffer's ancestor table
+     * (wipa_decode_attn_beam) and the step ends in the beam tail on the written logits; rules may be given.  The step graph is keyed on
+     * the buffer's address and on beam_max_candidates. */
+    void* beam;
+    size_t beam_bytes;
+    int32_t beam_max_candidates;
+} wipa_decode_call;
+/* wipa_decoder_run / wipa_decoder_prefill for a wipa_decode_call; those two are these with a call of n_init, eot and the masks. */
+int wipa_decoder_run_ex(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B,
+                        const wipa_decode_call* call, int n_steps, int use_graph, wipa_stream_t s);
+int wipa_decoder_prefill_ex(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
+                            const wipa_decode_call* call, int use_graph, wipa_stream_t s);
 /* Beam search (upstream's BeamSearchDecoder + MaximumLikelihoodRanker; DecodingOptions.beam_size / patience / length_penalty).  The B rows
  * of a call are B / n_group clips x n_group beams, clip-major, with cfg.dec_n_group = n_group = beam_size (1..16; 1 is one row per clip).
  * Per step and clip, every beam offers the n_group + 1 best columns of its FILTERED row (the row the greedy / rules tails reduce;
@@ -877,10 +931,8 @@ int wipa_decoder_prefill_sample(const wipa_model_cfg* cfg, const void* const* w,
  * wipa_beam_begin clears the counts and the counters and writes the identity table (after wipa_decoder_begin, before the prompt pass).
  * wipa_beam_step is the selection alone on any rows (no embedding, no position advance), like wipa_sample_step: tokens column
  * *pos_dev + 1, the gathered token rows and table, sum_logprobs, the store, and *not_done = the clips whose store is not full after
- * this step.  rules may be NULL.  wipa_decoder_prefill_beam / wipa_decoder_run_beam are wipa_decoder_prefill_sample / _run_sample with
- * beams: beam == NULL enqueues exactly what those enqueue; with beam, sample must be NULL.  The step graph is keyed on the buffer's
- * address and on max_candidates.  Refused (WIPA_ERR_ARG, nothing enqueued): fp8 decoder tables, WIPA_DECODE_TAIL=0,
- * WIPA_DECODE_FUSED=1, B % n_group != 0, n_group outside 1..16, max_candidates outside 1..64, a buffer below wipa_beam_bytes.
+ * this step.  rules may be NULL.  The prompt pass and the steps of a beam decode are wipa_decoder_prefill_ex / wipa_decoder_run_ex with
+ * wipa_decode_call.beam.
  * wipa_beam_finalize (after the last step; n = generated columns): a clip with fewer than n_group finished sequences is filled with its
  * live beams + eot in descending sum_logprobs; then wipa_rank_groups' arithmetic over the store -- (double)sum / penalty[length],
  * penalty f64 [n + 1], first maximum -- and per clip the winner's columns [0, sample_begin + length) followed by eot up to column
@@ -893,12 +945,6 @@ int wipa_beam_step(const float* logits, int64_t ldl, int B, int V, const float* 
 int wipa_beam_finalize(void* beam, const int32_t* tokens, int64_t ld_tok, int B, int n_group, int max_candidates, int sample_begin, int n,
                        int eot, const float* sum_logprobs, const double* penalty, int32_t* best_tokens, int64_t ld_out, float* best_sum,
                        int32_t* best_len, wipa_stream_t s);
-int wipa_decoder_run_beam(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int n_init, int eot,
-                          const float* mask_first, const float* mask_always, int n_steps, int use_graph, const wipa_decode_rules* rules,
-                          void* beam, size_t beam_bytes, int max_candidates, wipa_stream_t s);
-int wipa_decoder_prefill_beam(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init, int eot,
-                              const float* mask_first, const float* mask_always, int use_graph, const wipa_decode_rules* rules,
-                              const void* sample, void* beam, size_t beam_bytes, int max_candidates, wipa_stream_t s);
 /* Per-row prompts (mlx_whisper.transcribe's condition_on_previous_text / initial_prompt, DecodingOptions.prompt / prefix: each row's
  * initial tokens are [sot_prev] + history + sot_sequence + prefix, 1..n_text_ctx of them), in the layout described at
  * wipa_embed_layernorm_ragged above.
@@ -907,15 +953,9 @@ int wipa_decoder_prefill_beam(const wipa_model_cfg* cfg, const void* const* w, v
  *   caller-owned DEVICE array starts_dev int32 [B], which the later calls take).  pos = 0, counters and log-prob sums cleared.
  *   Refused (WIPA_ERR_ARG, nothing enqueued): P outside 1..n_text_ctx, a start outside 0..P-1 (every row holds at least one token), a
  *   token outside the vocabulary, fp8 decoder tables.
- * wipa_decoder_run_ragged: wipa_decoder_run_sample (rules and sample may be NULL) with n_init = P and the rows' starts.  The prompt is
- *   walked one column per step ("p + 1 < n_init: the given token is taken"); column P is the first generated one for every row.
- *   starts_dev == NULL enqueues exactly what wipa_decoder_run_sample enqueues.  With starts every step writes its logits and ends
- *   in the row-scan tail (as with rules); the address of starts_dev is part of the step graph's key.  Refused: a configuration whose
- *   step is not the unfused one with the fused tail (WIPA_DECODE_TAIL=0, WIPA_DECODE_FUSED=1), fp8 decoder tables, P outside
- *   1..n_text_ctx, n_steps > n_text_ctx - 1 (the position lives on the device and a call may include the P - 1 steps of the prompt
- *   walk, so this is the bound that holds at every position; the caller keeps P + new tokens <= n_text_ctx). */
+ * The steps of such rows are wipa_decoder_run_ex with wipa_decode_call.starts_dev = starts_dev and n_init = P. */
 /* wipa_decoder_prefill_ragged: the first P steps (columns 0 .. P-1 and the first generated token) as ONE batched pass, right after
- *   wipa_decoder_begin_ragged; continue with wipa_decoder_run_ragged.  The state it leaves is what stepping the prompt leaves, up to
+ *   wipa_decoder_begin_ragged; continue with wipa_decoder_run_ex (starts_dev).  The state it leaves is what stepping the prompt leaves, up to
  *   the rounding of the batched kernels: the pass is the teacher-forced layer body (GEMMs over B * P rows, wipa_attention for both
  *   attentions) writing K / V of every column into the blob's self-attention cache; cross K / V come from the blob's cache, or with
  *   absorbed projections are projected per layer from the blob's copy of the encoder output into the workspace.  Logits exist for two
@@ -923,7 +963,7 @@ int wipa_decoder_prefill_beam(const wipa_model_cfg* cfg, const void* const* w, v
  *   rows' <|startoftranscript|>, the same column for every row; -1: none) goes to f32 [B, ld_logits] at OFFSET 0 of the workspace
  *   (upstream's logits[:, sot_index], for no_speech_prob).  workspace: caller-owned, wipa_decoder_prompt_workspace_bytes(cfg, B, P)
  *   bytes, 256-byte aligned; the blob layout does not change.  Captured into a graph like wipa_decoder_prefill: P, sot_col and the
- *   addresses of starts_dev and of the workspace are part of its key.  Refused: what wipa_decoder_run_ragged refuses, a workspace
+ *   addresses of starts_dev and of the workspace are part of its key.  Refused: what a call with starts_dev is refused for, a workspace
  *   that is too small, P + 1 > n_text_ctx, sot_col outside -1 .. P-1. */
 size_t wipa_decoder_prompt_workspace_bytes(const wipa_model_cfg* cfg, int B, int P);
 int wipa_decoder_prefill_ragged(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int P,
@@ -932,9 +972,6 @@ int wipa_decoder_prefill_ragged(const wipa_model_cfg* cfg, const void* const* we
                                 size_t workspace_bytes, wipa_stream_t s);
 int wipa_decoder_begin_ragged(const wipa_model_cfg* cfg, void* state, size_t state_bytes, int B, const int32_t* tokens_host,
                               const int32_t* starts_host, int P, int32_t* starts_dev, wipa_stream_t s);
-int wipa_decoder_run_ragged(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int n_init,
-                            int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
-                            const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, wipa_stream_t s);
 /* Continuous batching: the B rows of a state are SLOTS.  A clip is admitted into a slot at the column the state
  * stands at, decodes there with its own position embeddings, attention window, sampling counter AND prompt end, and when it has
  * finished the next clip takes the slot while the other rows go on.  starts_dev is int32 [2][B] on the device, caller-owned: starts_dev[b]
@@ -945,8 +982,8 @@ int wipa_decoder_run_ragged(const wipa_model_cfg* cfg, const void* const* weight
  *   p + 1 >= own + limit: column p + 1 takes eot, without a log-probability, and the EOT latch holds the row from there on.
  * The latch is the token of column p: a slot leaves it when an admission writes initial tokens over the finished row's last column.
  * Served: both cross-attention forms, bf16 / f32 decoder tables, one row per clip, 1..4 initial tokens.  Refused by name
- * (WIPA_ERR_ARG, nothing enqueued): fp8 tables, candidate groups, a step without the fused tail; wipa_decoder_run_continuous also refuses
- * timestamp rules, which wipa_decoder_run_continuous_rules serves.
+ * (WIPA_ERR_ARG, nothing enqueued): fp8 tables, candidate groups, a step without the fused tail.  The steps are wipa_decoder_run_ex with
+ * wipa_decode_call.continuous (and rules, sample or sample_rows, no_speech_dev as wanted).
  * wipa_decoder_admit_rows: in stream order, for row i of n_rows: features_host[i] (a DEVICE pointer to the clip's encoder output
  *   [n_audio_ctx, d] in cfg.dtype; the array of pointers is on the host) is copied into slot slots_host[i] of the blob's audio copy
  *   (absorbed form), or projected into the slot's K / V of every layer as wipa_decoder_set_audio projects it (cached form: n_text_layer
@@ -963,49 +1000,13 @@ int wipa_decoder_run_ragged(const wipa_model_cfg* cfg, const void* const* weight
  *   source, so no store reaches bytes a later chunk still has to load.  Plain vector loads and stores.  Position embedding, attention
  *   window and sampling counter are relative to the row's start, and the attention kernel walks a row's keys from its start in the
  *   same partition wherever that start lies, so a shift changes no bit of what a row computes.  Refused: shift outside
- *   1..n_text_ctx-1; a shift above the position is not carried out.
- * wipa_decoder_run_continuous: wipa_decoder_run_ragged with the CONTINUOUS tails and rules == NULL.  The step graph's key is that of
- *   wipa_decoder_run_ragged plus the variant; the replayed kernels read starts_dev, so admissions and shifts replay the same graph.
- *   It refuses rules: the call with rules is the next one.
- * wipa_decoder_run_continuous_rules: wipa_decoder_run_continuous with the timestamp rules; rules is required (NULL is refused by name).
- *   The four cases per row stay.  The pick applies the rules to the row's OWN sequence, the tokens of columns own .. p: its length is
- *   p + 1 - own, the pick at p + 1 == own is the first one (mask_first; text dead, timestamps capped by max_initial_timestamp_index), and
- *   no token below own is looked at -- those are the slot's previous clip, which usually ended in timestamps, or the prompt.  A shift
- *   moves the starts and the tokens together, so a pick cannot see it.  With a sampling record the draw's counter takes the row's own
- *   position p - start[b], as in wipa_decoder_run_continuous.
- *   no_speech_dev (float [B] on the device, caller-owned, may be NULL): at the step whose column is a row's first own one (p == start[b],
- *   limit > 0: the row's <|startoftranscript|>, upstream's logits[:, sot_index]) the tail writes softmax(logits row)[no_speech_token] of
- *   the UNFILTERED row to no_speech_dev[b], with a plain store; the value stays until the slot's next admission reaches that step.
- *   The step graph's key is that of wipa_decoder_run_continuous plus the variant, the address of no_speech_dev and no_speech_token.  On
- *   bf16 the logits projection writes the logits, as for wipa_decoder_run_rules.  Refused by name (WIPA_ERR_ARG, nothing enqueued):
- *   rules == NULL, fp8 tables, candidate groups, a step without the fused tail, no_speech_token outside the vocabulary.
- * wipa_decoder_run_continuous_rows: wipa_decoder_run_continuous_rules (rules given) or wipa_decoder_run_continuous (rules == NULL) with a
- *   TEMPERATURE PER ROW: sample_rows is the sampling record with a row part (wipa_sample_rows_bytes above; required), and the steps end
- *   in the rows_tail_continuous kernels.  The four cases per row, the rules on the row's own sequence, the no-speech store and the
- *   counter's own position p - start[b] stay; a row whose 1 / temperature is 0 takes the greedy pick, every other row the draw at its own
- *   temperature, attempt and stream -- a retried window beside first attempts and beside retries at other temperatures, in ONE launch.
- *   wipa_decoder_admit_rows is called with sample == NULL, and wipa_sample_rows_set for the same slots.  The step graph's key is that
- *   of the call without the record plus the variant and the record's address.  On bf16 the logits projection writes the logits.
- *   Without rules a greedy row's pick is row_pick's arg-max (the same token as wipa_decoder_run_continuous; its log-probability sums
- *   the exponentials in the rules tails' order).  no_speech_dev needs rules.  Refused by name (WIPA_ERR_ARG, nothing enqueued):
- *   sample_rows == NULL or unaligned, fp8 tables, candidate groups, a step without the fused tail, and what the two calls above refuse. */
+ *   1..n_text_ctx-1; a shift above the position is not carried out. */
 int wipa_decoder_admit_rows(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int n_rows,
                             const int32_t* slots_host,
                             const void* const* features_host, const int32_t* initial_tokens_host, int n_init, const int32_t* limits_host,
                             int32_t* starts_dev, void* sample, const uint32_t* streams_host, wipa_stream_t s);
 int wipa_decoder_shift_columns(const wipa_model_cfg* cfg, void* state, size_t state_bytes, int B, int32_t* starts_dev, int shift,
                                wipa_stream_t s);
-int wipa_decoder_run_continuous(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int n_init,
-                                int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
-                                const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, wipa_stream_t s);
-int wipa_decoder_run_continuous_rules(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B,
-                                      int n_init, int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
-                                      const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, float* no_speech_dev,
-                                      int no_speech_token, wipa_stream_t s);
-int wipa_decoder_run_continuous_rows(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B,
-                                     int n_init, int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
-                                     const wipa_decode_rules* rules, const void* sample_rows, const int32_t* starts_dev, float* no_speech_dev,
-                                     int no_speech_token, wipa_stream_t s);
 
 /* Continuous batching with a PROMPT PER ROW.  A clip is still admitted at the state's column c; its prompt of L
  * columns ([sot_prev] + history; L = 0: none) stands IN FRONT of that column, at [c - L, c), and its n_init initial tokens at
@@ -1026,11 +1027,7 @@ int wipa_decoder_run_continuous_rows(const wipa_model_cfg* cfg, const void* cons
  *   computed (the step at column c produces the sot-column logits itself).  Host arrays may be freed when the call returns.
  *   Refused by name (WIPA_ERR_ARG, nothing enqueued): what wipa_decoder_admit_rows refuses, W or an L_i outside
  *   0 .. n_text_ctx - n_init - 1, L_i > W, a prompt token outside the vocabulary, a workspace that is too small.
- * wipa_decoder_run_continuous_prompted: the three continuous run calls in ONE, for a [3][B] starts_dev (required): rules, sample,
- *   sample_rows and no_speech_dev may each be NULL (sample and sample_rows exclude each other; no_speech_dev needs rules).  The steps
- *   end in the PROMPTED tails: own = start + L + n_init, the no-speech store at column start + L, the rules on tk[own .. p], the
- *   draw's counter p - start (the row's position in its own unpadded sequence).  Head and attention are the RAGGED kernels as they
- *   are.  The step graph's key is that of the unprompted call plus a variant bit. */
+ * The steps of a prompted state are wipa_decoder_run_ex with wipa_decode_call.continuous and .prompted, on the [3][B] starts_dev. */
 int wipa_decoder_seek(const wipa_model_cfg* cfg, void* state, size_t state_bytes, int B, int column, wipa_stream_t s);
 size_t wipa_decoder_admit_prompted_workspace_bytes(const wipa_model_cfg* cfg, int n_rows, int W);
 int wipa_decoder_admit_rows_prompted(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int n_rows,
@@ -1038,10 +1035,6 @@ int wipa_decoder_admit_rows_prompted(const wipa_model_cfg* cfg, const void* cons
                                      int n_init, const int32_t* limits_host, const int32_t* prompt_lens_host,
                                      const int32_t* prompt_tokens_host, int W, int32_t* starts_dev, void* sample,
                                      const uint32_t* streams_host, void* workspace, size_t workspace_bytes, wipa_stream_t s);
-int wipa_decoder_run_continuous_prompted(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B,
-                                         int n_init, int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
-                                         const wipa_decode_rules* rules, const void* sample, const void* sample_rows,
-                                         const int32_t* starts_dev, float* no_speech_dev, int no_speech_token, wipa_stream_t s);
 /* drop the cached step graphs that reference this state blob (call before freeing it). */
 int wipa_decoder_release(void* state);
 

@@ -1,6 +1,6 @@
 """CPU restatement of prompt conditioning: every row is decoded ALONE, batch of one, with its own unpadded initial tokens
 ([sot_prev] + history + sot_sequence) through tests/timestamp_ref.greedy_with_rules on the CPU oracle -- padding, a common prompt width
-and per-row starts do not exist here.  What the ragged decode (include/wipa.h: wipa_decoder_begin_ragged / wipa_decoder_run_ragged;
+and per-row starts do not exist here.  What the ragged decode (include/wipa.h: wipa_decoder_begin_ragged / wipa_decode_call.starts_dev;
 whisper_ipa_amd.decoding.ragged_decode_tokens) and transcribe's conditioning are tested against."""
 from dataclasses import dataclass
 from typing import List, Sequence

@@ -56,6 +56,9 @@ def test_struct_layouts_match_c(built, tmp_path):
         'printf("%zu %zu %zu %zu %zu %zu %zu\\n", sizeof(wipa_self_block_desc), sizeof(wipa_cross_block_desc), offsetof(wipa_self_block_desc, B), '
         'offsetof(wipa_self_block_desc, qk_scale), offsetof(wipa_cross_block_desc, n_slabs), offsetof(wipa_cross_block_desc, qk_scale), '
         'offsetof(wipa_gemm_desc, ln_eps));\n'
+        'printf("%zu %zu %zu %zu %zu %zu %zu\\n", sizeof(wipa_decode_call), offsetof(wipa_decode_call, mask_first), offsetof(wipa_decode_call, rules), '
+        'offsetof(wipa_decode_call, starts_dev), offsetof(wipa_decode_call, no_speech_token), offsetof(wipa_decode_call, beam_bytes), '
+        'offsetof(wipa_decode_call, beam_max_candidates));\n'
         "return 0;}\n"
     )
     exe = tmp_path / "lay"
@@ -71,6 +74,9 @@ def test_struct_layouts_match_c(built, tmp_path):
     assert f == [C.sizeof(built.SelfBlockDesc), C.sizeof(built.CrossBlockDesc), built.SelfBlockDesc.B.offset,
                  built.SelfBlockDesc.qk_scale.offset, built.CrossBlockDesc.n_slabs.offset, built.CrossBlockDesc.qk_scale.offset,
                  built.GemmDesc.ln_eps.offset]
+    d, K = [int(x) for x in out[4].split()], built.DecodeCall
+    assert d == [C.sizeof(K), K.mask_first.offset, K.rules.offset, K.starts_dev.offset, K.no_speech_token.offset, K.beam_bytes.offset,
+                 K.beam_max_candidates.offset]
 
 
 def test_missing_library_fails_loudly(monkeypatch, built):
@@ -112,5 +118,42 @@ def test_decoder_entry_points_refuse_a_state_blob_smaller_than_the_layout(built)
     assert rc != 0 and b"state blob" in lib.wipa_last_error()
     rc = lib.wipa_decoder_prefill(C.byref(cached), tab, fake, la.total_bytes, 64, 4, 50257, fake, fake, 0, None)
     assert rc != 0 and b"state blob" in lib.wipa_last_error()
+    call = built.DecodeCall(n_init=4, eot=50257, mask_first=0x1000, mask_always=0x1000)
+    rc = lib.wipa_decoder_run_ex(C.byref(cached), tab, fake, la.total_bytes, 64, C.byref(call), 1, 0, None)
+    assert rc != 0 and b"wipa_decoder_run_ex: the state blob" in lib.wipa_last_error()
+    rc = lib.wipa_decoder_prefill_ex(C.byref(cached), tab, fake, la.total_bytes, 64, C.byref(call), 0, None)
+    assert rc != 0 and b"wipa_decoder_prefill_ex: the state blob" in lib.wipa_last_error()
     rc = lib.wipa_decoder_set_audio(C.byref(cached), tab, fake, fake, la.total_bytes, 64, None)
     assert rc != 0 and b"state blob" in lib.wipa_last_error()
+
+
+def test_decode_call_refuses_what_no_entry_point_could_express_before(built):
+    """wipa_decoder_run_ex / wipa_decoder_prefill_ex take every field at once, so combinations that had no spelling are refused by name
+    (WIPA_ERR_ARG, entry point and field in the message) before any launch, never served by accident.  No GPU: fake pointers."""
+    from decode_call_util import FAKE, refusal, small_cfg
+
+    cfg = small_cfg(built)
+    cont = dict(continuous=1, starts_dev=FAKE)
+    assert "call.sample_rows takes the place of call.sample" in refusal(built, "run", cfg, **cont, sample=FAKE, sample_rows=FAKE)
+    for field, more in (("sample_rows", {}), ("no_speech_dev", dict(rules=True)), ("prompted", dict(starts_dev=FAKE))):
+        msg = refusal(built, "run", cfg, **{field: FAKE if field != "prompted" else 1}, **more)
+        assert f"call.{field}" in msg and "need call.continuous" in msg
+    assert "call.continuous needs call.starts_dev" in refusal(built, "run", cfg, continuous=1)
+    beam = dict(beam=FAKE, beam_bytes=1 << 40, beam_max_candidates=2)
+    for field in ("sample", "sample_rows"):
+        msg = refusal(built, "run", cfg, **beam, **{field: FAKE}, **(cont if field == "sample_rows" else {}))
+        assert "call.beam" in msg and f"call.{field}" in msg
+    for more in (dict(starts_dev=FAKE), cont):
+        msg = refusal(built, "run", cfg, **beam, **more)
+        assert "call.beam" in msg and "call.starts_dev" in msg and "call.continuous" in msg
+    assert "call.beam and call.sample" in refusal(built, "prefill", cfg, **beam, sample=FAKE)
+    for more in (dict(starts_dev=FAKE), cont, dict(**cont, prompted=1), dict(**cont, sample_rows=FAKE), dict(**cont, rules=True, no_speech_dev=FAKE),
+                 dict(prompted=1), dict(sample_rows=FAKE), dict(rules=True, no_speech_dev=FAKE)):
+        msg = refusal(built, "prefill", cfg, **more)
+        assert "not served by the prompt pass" in msg and all(f"call.{f}" in msg for f in more if f != "rules"), (more, msg)
+    # and what the plain and the _ex prompt pass refused before: the prompt width, a NULL call
+    assert "call.n_init: 1..4 prompt tokens" in refusal(built, "prefill", cfg, n_init=5)
+    lib = built.lib()
+    tab, fake = (C.c_void_p * 4)(), C.c_void_p(FAKE)
+    assert lib.wipa_decoder_run_ex(C.byref(cfg), tab, fake, 1 << 40, 4, None, 1, 0, None) == -1 and b"wipa_decoder_run_ex: call" in lib.wipa_last_error()
+    assert lib.wipa_decoder_prefill_ex(C.byref(cfg), tab, fake, 1 << 40, 4, None, 0, None) == -1 and b"wipa_decoder_prefill_ex: call" in lib.wipa_last_error()

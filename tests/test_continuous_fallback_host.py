@@ -2,7 +2,7 @@
 temperature, an attempt and a stream of its own) against a scripted stepper; ``transcribe(seed=S)`` on both schedules with scripted
 decodes -- a fake ``decode_fn`` + ``fallback_fn`` on the rounds side, a fake ``stream_fn`` that declares ``retries`` on the continuous
 side; what stays refused; the host image of the sampling record with a row part; and the refusals of
-wipa_decoder_run_continuous_rows.  No GPU."""
+wipa_decoder_run_ex with wipa_decode_call.sample_rows.  No GPU."""
 import ctypes as C
 import struct
 import warnings
@@ -370,38 +370,29 @@ def test_rows_record_refuses_by_the_arguments_name(lib):
 def test_abi_has_the_entry_points(lib):
     from whisper_ipa_amd import _lib
 
-    for name in ("wipa_decoder_run_continuous_rows", "wipa_sample_rows_bytes", "wipa_sample_rows_fill", "wipa_sample_rows_fill_row",
+    assert "sample_rows" in {f for f, _ in _lib.DecodeCall._fields_}
+    for name in ("wipa_decoder_run_ex", "wipa_sample_rows_bytes", "wipa_sample_rows_fill", "wipa_sample_rows_fill_row",
                  "wipa_sample_rows_set"):
         assert name in _lib.SIGNATURES and hasattr(lib, name)
 
 
 def test_run_continuous_rows_refuses_by_name_before_any_launch(lib):
-    """a NULL record, fp8 tables, candidate groups and a missing starts array are refused with a message that names them; rules may be
-    NULL; the pointers are never dereferenced"""
+    """With a temperature per row: a record beside the single-temperature one, an unaligned record, fp8 tables, candidate groups, a missing
+    starts array, a wrong count of initial tokens and a bad no-speech column are refused with a message that names the entry point and the
+    field; rules may be NULL; the pointers are never dereferenced"""
+    from decode_call_util import FAKE, fp8_cfg, refusal, small_cfg
     from whisper_ipa_amd import _lib
 
-    small = dict(n_mels=80, n_audio_ctx=1500, n_audio_state=384, n_audio_head=6, n_audio_layer=2, n_vocab=51865, n_text_ctx=448, n_text_state=384,
-                 n_text_head=6, n_text_layer=2, dtype=_lib.WIPA_BF16, dec_cross_absorbed=1)
-    cfg = _lib.ModelCfg(**small)
-    fake = C.c_void_p(0x1000)
-    tab = (C.c_void_p * 64)()
-    rules = _lib.DecodeRules(50364, 50363, 50)
-    run = lib.wipa_decoder_run_continuous_rows
-    for r in (C.byref(rules), None):
-        rc = run(C.byref(cfg), tab, fake, 1 << 40, 4, 3, 50257, fake, fake, 1, 0, r, None, fake, None, 0, None)
-        assert rc != 0 and b"sample_rows is required" in lib.wipa_last_error()
-        rc = run(C.byref(cfg), tab, fake, 1 << 40, 4, 3, 50257, fake, fake, 1, 0, r, fake, None, None, 0, None)
-        assert rc != 0 and b"starts_dev" in lib.wipa_last_error()
-        fp8 = _lib.ModelCfg(**{**small, "dec_cross_absorbed": 0, "dec_w_dtype": _lib.WIPA_FP8_E4M3})
-        rc = run(C.byref(fp8), tab, fake, 1 << 40, 4, 3, 50257, fake, fake, 1, 0, r, fake, fake, None, 0, None)
-        assert rc != 0 and b"fp8" in lib.wipa_last_error()
-        grouped = _lib.ModelCfg(**{**small, "dec_n_group": 2})
-        rc = run(C.byref(grouped), tab, fake, 1 << 40, 4, 3, 50257, fake, fake, 1, 0, r, fake, fake, None, 0, None)
-        assert rc != 0 and b"candidate groups" in lib.wipa_last_error()
-        rc = run(C.byref(cfg), tab, fake, 1 << 40, 4, 5, 50257, fake, fake, 1, 0, r, fake, fake, None, 0, None)
-        assert rc != 0 and b"initial tokens" in lib.wipa_last_error()
-    rc = run(C.byref(cfg), tab, fake, 1 << 40, 4, 3, 50257, fake, fake, 1, 0, C.byref(rules), fake, fake, fake, 51865, None)
-    assert rc != 0 and b"no_speech_token" in lib.wipa_last_error()
-    rc = run(C.byref(cfg), tab, fake, 1 << 40, 4, 3, 50257, fake, fake, 1, 0, C.byref(rules), C.c_void_p(0x1004), fake, None, 0, None)
-    assert rc != 0 and b"sample_rows" in lib.wipa_last_error()  # unaligned
-    assert b"wipa_decoder_run_continuous_rows" in lib.wipa_last_error()
+    cfg = small_cfg(_lib)
+    for r in (True, False):
+        on = dict(rules=r, continuous=1, starts_dev=FAKE, sample_rows=FAKE)
+        assert "call.continuous needs call.starts_dev" in refusal(_lib, "run", cfg, **{**on, "starts_dev": None})
+        assert "fp8" in refusal(_lib, "run", fp8_cfg(_lib), **on)
+        assert "candidate groups" in refusal(_lib, "run", small_cfg(_lib, dec_n_group=2), **on)
+        assert "initial tokens" in refusal(_lib, "run", cfg, **{**on, "n_init": 5})
+        assert "call.sample_rows takes the place of call.sample" in refusal(_lib, "run", cfg, **{**on, "sample": FAKE})
+    on = dict(rules=True, continuous=1, starts_dev=FAKE, sample_rows=FAKE)
+    assert "call.no_speech_token=51865" in refusal(_lib, "run", cfg, **on, no_speech_dev=FAKE, no_speech_token=51865)
+    assert "call.no_speech_dev needs call.rules" in refusal(_lib, "run", cfg, **{**on, "rules": False}, no_speech_dev=FAKE)
+    msg = refusal(_lib, "run", cfg, **{**on, "sample_rows": 0x1004})
+    assert "call.sample_rows" in msg and "16-byte aligned" in msg

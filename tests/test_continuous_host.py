@@ -291,19 +291,20 @@ def test_abi_has_the_three_entry_points():
     from whisper_ipa_amd import _lib
 
     lib = _lib.lib()
-    for name in ("wipa_decoder_admit_rows", "wipa_decoder_shift_columns", "wipa_decoder_run_continuous"):
+    for name in ("wipa_decoder_admit_rows", "wipa_decoder_shift_columns", "wipa_decoder_run_ex"):
         assert name in _lib.SIGNATURES and hasattr(lib, name)
     assert callable(whisper_ipa_amd.decode_continuous)
 
 
 def test_entry_points_refuse_by_name_before_any_launch():
-    """rules, fp8 tables, candidate groups and a missing starts array are refused with WIPA_ERR_ARG and a message that names them; the
-    pointers are never dereferenced"""
+    """fp8 tables, candidate groups and a missing starts array are refused with WIPA_ERR_ARG and a message that names the entry point and
+    the field; the pointers are never dereferenced"""
     import ctypes as C
 
     import __graft_entry__ as g
 
     g.build()
+    from decode_call_util import FAKE, fp8_cfg, refusal, small_cfg
     from whisper_ipa_amd import _lib
 
     lib = _lib.lib()
@@ -312,14 +313,15 @@ def test_entry_points_refuse_by_name_before_any_launch():
     cfg = _lib.ModelCfg(**small)
     fake = C.c_void_p(0x1000)
     tab = (C.c_void_p * 64)()
-    rules = _lib.DecodeRules(50364, 50363, 50)
-    rc = lib.wipa_decoder_run_continuous(C.byref(cfg), tab, fake, 1 << 40, 4, 4, 50257, fake, fake, 1, 0, C.byref(rules), None, fake, None)
-    assert rc != 0 and b"rules" in lib.wipa_last_error()
-    rc = lib.wipa_decoder_run_continuous(C.byref(cfg), tab, fake, 1 << 40, 4, 4, 50257, fake, fake, 1, 0, None, None, None, None)
-    assert rc != 0 and b"starts_dev" in lib.wipa_last_error()
-    fp8 = _lib.ModelCfg(**{**small, "dec_cross_absorbed": 0, "dec_w_dtype": _lib.WIPA_FP8_E4M3})
-    rc = lib.wipa_decoder_run_continuous(C.byref(fp8), tab, fake, 1 << 40, 4, 4, 50257, fake, fake, 1, 0, None, None, fake, None)
-    assert rc != 0 and b"fp8" in lib.wipa_last_error()
+    assert "call.continuous needs call.starts_dev" in refusal(_lib, "run", cfg, continuous=1)
+    msg = refusal(_lib, "run", fp8_cfg(_lib), continuous=1, starts_dev=FAKE, n_init=4)
+    assert "fp8" in msg and "dec_w_dtype" in msg
+    assert "candidate groups" in refusal(_lib, "run", small_cfg(_lib, dec_n_group=2), continuous=1, starts_dev=FAKE)
+    assert "call.n_init: 1..4 initial tokens" in refusal(_lib, "run", cfg, continuous=1, starts_dev=FAKE, n_init=5)
+    # fields that need a continuous call, one by one
+    for field in ("sample_rows", "no_speech_dev"):
+        assert f"call.{field}" in refusal(_lib, "run", cfg, rules=True, **{field: FAKE}) and "need call.continuous" in lib.wipa_last_error().decode()
+    assert "call.prompted" in refusal(_lib, "run", cfg, prompted=1, starts_dev=FAKE) and "need call.continuous" in lib.wipa_last_error().decode()
     grouped = _lib.ModelCfg(**{**small, "dec_n_group": 2})
     rc = lib.wipa_decoder_shift_columns(C.byref(grouped), fake, 1 << 40, 4, fake, 1, None)
     assert rc != 0 and b"candidate groups" in lib.wipa_last_error()

@@ -345,8 +345,7 @@ def test_decode_continuous_refuses_by_name():
 
 
 # ---------------------------------------------------------------- the C ABI
-NEW = ("wipa_decoder_seek", "wipa_decoder_admit_prompted_workspace_bytes", "wipa_decoder_admit_rows_prompted",
-       "wipa_decoder_run_continuous_prompted")
+NEW = ("wipa_decoder_seek", "wipa_decoder_admit_prompted_workspace_bytes", "wipa_decoder_admit_rows_prompted", "wipa_decoder_run_ex")
 
 
 def _lib_and_cfg():
@@ -364,6 +363,7 @@ def test_abi_has_the_new_entry_points():
     _lib, lib, small = _lib_and_cfg()
     for name in NEW:
         assert name in _lib.SIGNATURES and hasattr(lib, name), name
+    assert "prompted" in {f for f, _ in _lib.DecodeCall._fields_}
     cfg = _lib.ModelCfg(**small)
     size = lib.wipa_decoder_admit_prompted_workspace_bytes
     assert size(C.byref(cfg), 0, 4) == 0 and size(C.byref(cfg), 2, -1) == 0
@@ -386,15 +386,19 @@ def test_new_entry_points_refuse_by_name_before_any_launch():
         assert seek(C.byref(cfg), fake, 1 << 40, 4, column, None) != 0 and b"column" in err()
     assert seek(C.byref(cfg), fake, 16, 4, 5, None) != 0  # a state blob that is too small
 
-    run = lib.wipa_decoder_run_continuous_prompted
-    ok = (C.byref(cfg), tab, fake, 1 << 40, 4, 3, 50257, fake, fake, 1, 0)
-    assert run(*ok, C.byref(rules), None, None, None, fake, 50362, None) != 0 and b"starts_dev (int32 [3][B]" in err()
-    assert run(*ok, C.byref(rules), fake, fake, fake, fake, 50362, None) != 0 and b"sample_rows" in err()
-    assert run(*ok, None, None, None, fake, fake, 50362, None) != 0 and b"no_speech_dev needs rules" in err()
-    assert run(*ok, C.byref(rules), None, None, fake, fake, 51865, None) != 0 and b"no_speech_token" in err()
-    assert run(C.byref(fp8), *ok[1:], C.byref(rules), None, None, fake, fake, 50362, None) != 0 and b"fp8" in err()
-    assert run(C.byref(grouped), *ok[1:], C.byref(rules), None, None, fake, fake, 50362, None) != 0 and b"candidate groups" in err()
-    assert run(*ok[:5], 5, *ok[6:], C.byref(rules), None, None, fake, None, 0, None) != 0 and b"initial tokens" in err()
+    from decode_call_util import FAKE, refusal
+
+    on = dict(rules=True, continuous=1, prompted=1, starts_dev=FAKE, no_speech_dev=FAKE, no_speech_token=50362)
+    msg = refusal(_lib, "run", cfg, **{**on, "starts_dev": None})
+    assert "call.continuous needs call.starts_dev" in msg and "[3][B] with call.prompted" in msg
+    assert "call.sample_rows takes the place of call.sample" in refusal(_lib, "run", cfg, **on, sample=FAKE, sample_rows=FAKE)
+    assert "call.sample_rows" in refusal(_lib, "run", cfg, **on, sample_rows=0x1008) and b"16-byte aligned" in err()
+    assert "call.no_speech_dev needs call.rules" in refusal(_lib, "run", cfg, **{**on, "rules": False})
+    assert "call.no_speech_token=51865" in refusal(_lib, "run", cfg, **{**on, "no_speech_token": 51865})
+    assert "fp8" in refusal(_lib, "run", fp8, **on)
+    assert "candidate groups" in refusal(_lib, "run", grouped, **on)
+    assert "initial tokens" in refusal(_lib, "run", cfg, **{**on, "no_speech_dev": None, "n_init": 5})
+    assert "call.prompted" in refusal(_lib, "run", cfg, **{**on, "continuous": 0}) and b"need call.continuous" in err()
 
     admit = lib.wipa_decoder_admit_rows_prompted
     slots = (C.c_int32 * 2)(0, 1)

@@ -1,7 +1,7 @@
 """CPU: the streaming scheduler of the continuous decode (whisper_ipa_amd.continuous.run_stream) against a fake stepper and a source of
 files whose windows exist one at a time; the keyword that lets ``refuse_unserved`` pass ``without_timestamps=False``; what
 ``transcribe(schedule="continuous")`` refuses; the window bookkeeping both schedules of ``transcribe`` share, through a fake continuous
-decoder at the ``stream_fn`` seam; and the refusals of wipa_decoder_run_continuous_rules.  No GPU."""
+decoder at the ``stream_fn`` seam; and the refusals of a continuous wipa_decoder_run_ex call with rules.  No GPU."""
 import warnings
 import zlib
 from types import SimpleNamespace
@@ -340,41 +340,26 @@ def test_abi_has_the_entry_point():
     g.build()
     from whisper_ipa_amd import _lib
 
-    assert "wipa_decoder_run_continuous_rules" in _lib.SIGNATURES and hasattr(_lib.lib(), "wipa_decoder_run_continuous_rules")
+    assert "wipa_decoder_run_ex" in _lib.SIGNATURES and hasattr(_lib.lib(), "wipa_decoder_run_ex")
+    assert {"continuous", "rules", "no_speech_dev", "no_speech_token"} <= {f for f, _ in _lib.DecodeCall._fields_}
 
 
 def test_run_continuous_rules_refuses_by_name_before_any_launch():
-    """rules = NULL, fp8 tables, candidate groups, a missing starts array and a no-speech column outside the vocabulary are refused with
-    a message that names them; the pointers are never dereferenced"""
-    import ctypes as C
-
+    """With rules on a continuous call: fp8 tables, candidate groups, a missing starts array, a no-speech column outside the vocabulary,
+    a no-speech array without rules and a wrong count of initial tokens are refused with a message that names the entry point and the
+    field; the pointers are never dereferenced"""
     import __graft_entry__ as g
 
     g.build()
+    from decode_call_util import FAKE, fp8_cfg, refusal, small_cfg
     from whisper_ipa_amd import _lib
 
-    lib = _lib.lib()
-    small = dict(n_mels=80, n_audio_ctx=1500, n_audio_state=384, n_audio_head=6, n_audio_layer=2, n_vocab=51865, n_text_ctx=448, n_text_state=384,
-                 n_text_head=6, n_text_layer=2, dtype=_lib.WIPA_BF16, dec_cross_absorbed=1)
-    cfg = _lib.ModelCfg(**small)
-    fake = C.c_void_p(0x1000)
-    tab = (C.c_void_p * 64)()
-    rules = _lib.DecodeRules(50364, 50363, 50)
-    run = lib.wipa_decoder_run_continuous_rules
-    rc = run(C.byref(cfg), tab, fake, 1 << 40, 4, 3, 50257, fake, fake, 1, 0, None, None, fake, fake, 50362, None)
-    assert rc != 0 and b"rules is required" in lib.wipa_last_error()
-    rc = run(C.byref(cfg), tab, fake, 1 << 40, 4, 3, 50257, fake, fake, 1, 0, C.byref(rules), None, None, fake, 50362, None)
-    assert rc != 0 and b"starts_dev" in lib.wipa_last_error()
-    fp8 = _lib.ModelCfg(**{**small, "dec_cross_absorbed": 0, "dec_w_dtype": _lib.WIPA_FP8_E4M3})
-    rc = run(C.byref(fp8), tab, fake, 1 << 40, 4, 3, 50257, fake, fake, 1, 0, C.byref(rules), None, fake, fake, 50362, None)
-    assert rc != 0 and b"fp8" in lib.wipa_last_error()
-    grouped = _lib.ModelCfg(**{**small, "dec_n_group": 2})
-    rc = run(C.byref(grouped), tab, fake, 1 << 40, 4, 3, 50257, fake, fake, 1, 0, C.byref(rules), None, fake, fake, 50362, None)
-    assert rc != 0 and b"candidate groups" in lib.wipa_last_error()
-    rc = run(C.byref(cfg), tab, fake, 1 << 40, 4, 3, 50257, fake, fake, 1, 0, C.byref(rules), None, fake, fake, 51865, None)
-    assert rc != 0 and b"no_speech_token" in lib.wipa_last_error()
-    rc = run(C.byref(cfg), tab, fake, 1 << 40, 4, 5, 50257, fake, fake, 1, 0, C.byref(rules), None, fake, None, 0, None)
-    assert rc != 0 and b"initial tokens" in lib.wipa_last_error()
-    # and wipa_decoder_run_continuous still refuses rules
-    rc = lib.wipa_decoder_run_continuous(C.byref(cfg), tab, fake, 1 << 40, 4, 3, 50257, fake, fake, 1, 0, C.byref(rules), None, fake, None)
-    assert rc != 0 and b"rules" in lib.wipa_last_error()
+    cfg = small_cfg(_lib)
+    on = dict(rules=True, continuous=1, starts_dev=FAKE, no_speech_dev=FAKE, no_speech_token=50362)
+    assert "call.continuous needs call.starts_dev" in refusal(_lib, "run", cfg, **{**on, "starts_dev": None})
+    assert "fp8" in refusal(_lib, "run", fp8_cfg(_lib), **on)
+    assert "candidate groups" in refusal(_lib, "run", small_cfg(_lib, dec_n_group=2), **on)
+    assert "call.no_speech_token=51865" in refusal(_lib, "run", cfg, **{**on, "no_speech_token": 51865})
+    assert "call.no_speech_token=-1" in refusal(_lib, "run", cfg, **{**on, "no_speech_token": -1})
+    assert "call.no_speech_dev needs call.rules" in refusal(_lib, "run", cfg, **{**on, "rules": False})
+    assert "initial tokens" in refusal(_lib, "run", cfg, **{**on, "no_speech_dev": None, "n_init": 5})

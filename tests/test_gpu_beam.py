@@ -342,11 +342,15 @@ def test_beam_entry_points_refuse_before_anything_is_enqueued(models, monkeypatc
         buf = st.beam_buffer(G, 2)
 
         def run(nbytes=None, maxc=2, rows=B):
-            rc = L.wipa_decoder_run_beam(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), rows, 3, SP.eot, ptr(m), ptr(m), 1, 0, None,
-                                         ptr(buf), buf.numel() if nbytes is None else nbytes, maxc, sptr(s))
-            return rc, L.wipa_last_error().decode()
+            call = _lib.DecodeCall(n_init=3, eot=SP.eot, mask_first=ptr(m), mask_always=ptr(m), beam=ptr(buf),
+                                   beam_bytes=buf.numel() if nbytes is None else nbytes, beam_max_candidates=maxc)
+            rc = L.wipa_decoder_run_ex(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), rows, C.byref(call), 1, 0, sptr(s))
+            msg = L.wipa_last_error().decode()
+            assert rc == 0 or msg.startswith("wipa_decoder_run_ex: "), msg
+            return rc, msg
 
-        for kw, word in ((dict(nbytes=int(L.wipa_beam_bytes(B, G, 2, st.layout.ld_tok)) - 1), "beam buffer"), (dict(maxc=0), "max_candidates"), (dict(maxc=65), "max_candidates"),
+        for kw, word in ((dict(nbytes=int(L.wipa_beam_bytes(B, G, 2, st.layout.ld_tok)) - 1), "call.beam_bytes"), (dict(maxc=0), "call.beam_max_candidates"),
+                         (dict(maxc=65), "call.beam_max_candidates"),
                          (dict(rows=3), "multiple")):
             rc, msg = run(**kw)
             assert rc != 0 and word in msg, (kw, rc, msg)

@@ -1,5 +1,5 @@
 """GPU: continuous-batching decode (whisper_ipa_amd.continuous.decode_continuous; include/wipa.h: wipa_decoder_admit_rows /
-wipa_decoder_shift_columns / wipa_decoder_run_continuous and the CONTINUOUS step tails) against the CPU oracle's loop with every clip
+wipa_decoder_shift_columns / wipa_decode_call.continuous and the CONTINUOUS step tails) against the CPU oracle's loop with every clip
 decoded ALONE, batch of one, to its own length -- slots, refill, admission columns and shifts do not exist there.  ``pytest -m gpu`` on
 an MI355X.
 

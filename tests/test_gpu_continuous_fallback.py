@@ -1,5 +1,5 @@
 """GPU: the temperature fallback on the continuous schedule -- a TEMPERATURE PER ROW (include/wipa.h: the sampling record with a row
-part, wipa_sample_rows_set, wipa_decoder_run_continuous_rows and the rows_tail_continuous kernels;
+part, wipa_sample_rows_set, wipa_decode_call.sample_rows and the rows_tail_continuous kernels;
 whisper_ipa_amd.continuous.decode_continuous(temperatures=, attempts=); transcribe(schedule="continuous", seed=S)) against the CPU
 restatements of tests/timestamp_ref.py (greedy rows) and tests/prompt_ref.py / tests/sampling_ref.py (sampled rows) with every clip
 decoded ALONE -- slots, refill, neighbours at other temperatures, admission columns and shifts do not exist there.  ``pytest -m gpu`` on
@@ -192,7 +192,7 @@ def test_uniform_rows_equal_the_existing_paths_bit_for_bit(model):
 
 def test_admit_set_rows_run_and_shift_through_the_c_abi(refs, model):
     """DeviceStepper with a row record drives admit + wipa_sample_rows_set, steps, a second admission of THE SAME clip into THE SAME slot
-    at a later column with another temperature and attempt, a shift and more steps through wipa_decoder_run_continuous_rows, 3 slots:
+    at a later column with another temperature and attempt, a shift and more steps with wipa_decode_call.sample_rows, 3 slots:
     each occupancy's columns equal that clip decoded alone at that temperature and attempt, and the no-speech probability is written
     again at the retry's first column"""
     from whisper_ipa_amd.continuous import DeviceStepper

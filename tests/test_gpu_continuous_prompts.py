@@ -1,5 +1,5 @@
 """GPU: continuous batching with a PROMPT PER CLIP (include/wipa.h: wipa_decoder_seek, wipa_decoder_admit_rows_prompted,
-wipa_decoder_run_continuous_prompted and the PROMPTED tails; whisper_ipa_amd.continuous.decode_continuous(prompts=)) against the CPU
+wipa_decoder_run_ex with wipa_decode_call.prompted and the PROMPTED tails; whisper_ipa_amd.continuous.decode_continuous(prompts=)) against the CPU
 restatement with every clip decoded ALONE, batch of one, on its own unpadded ``[sot_prev] + history + sot_sequence`` -- slots, the
 prompt room, admission columns, the prompt pass and shifts do not exist there.  ``pytest -m gpu`` on an MI355X.
 
@@ -282,23 +282,34 @@ def test_seek_admit_run_and_shift_through_the_c_abi(refs):
 
 
 class _Spy:
-    """the library with every function that is looked up recorded by name"""
+    """the library with every function that is looked up recorded by name, and the wipa_decode_call of every wipa_decoder_run_ex call
+    recorded as (continuous, rules, prompted, rows of the starts array it was built for)"""
 
-    def __init__(self, lib, seen):
-        self._lib, self._seen = lib, seen
+    def __init__(self, lib, seen, run_calls):
+        self._lib, self._seen, self._run_calls = lib, seen, run_calls
 
     def __getattr__(self, name):
         self._seen.append(name)
-        return getattr(self._lib, name)
+        fn = getattr(self._lib, name)
+        if name != "wipa_decoder_run_ex":
+            return fn
+
+        def recorded(*a):
+            k = a[5]._obj  # the DecodeCall behind C.byref
+            self._run_calls.append((bool(k.continuous), bool(k.rules), bool(k.prompted), bool(k.starts_dev)))
+            return fn(*a)
+
+        return recorded
 
 
-NEW_ENTRY_POINTS = ("wipa_decoder_seek", "wipa_decoder_admit_rows_prompted", "wipa_decoder_admit_prompted_workspace_bytes",
-                    "wipa_decoder_run_continuous_prompted")
+NEW_ENTRY_POINTS = ("wipa_decoder_seek", "wipa_decoder_admit_rows_prompted", "wipa_decoder_admit_prompted_workspace_bytes")
+UNPROMPTED, PROMPTED = (True, True, False, True), (True, True, True, True)  # continuous with rules on a starts array, without / with .prompted
 
 
 def test_without_prompts_nothing_else_moved(refs, monkeypatch):
-    """decode_continuous and transcribe(schedule="continuous") without prompts call none of the new entry points and no seek, and their
-    admissions start at column 0; with prompts the same spy sees the new entry points (so it would have seen them)"""
+    """decode_continuous and transcribe(schedule="continuous") without prompts call none of the new entry points and no seek, every
+    run call they make is continuous with rules and NOT prompted, and their admissions start at column 0; with prompts the same spy sees
+    the new entry points and prompted run calls only (so it would have seen them)"""
     import warnings
 
     import whisper_ipa_amd as wipa
@@ -308,26 +319,26 @@ def test_without_prompts_nothing_else_moved(refs, monkeypatch):
     W, feats, histories, _, _ = refs["scripted"]
     m = _model(MICRO, W, torch.float32)
     dev = feats.cuda()
-    real, seen = _lib.lib(), []
-    monkeypatch.setattr(CT._lib, "lib", lambda: _Spy(real, seen))
+    real, seen, run_calls = _lib.lib(), [], []
+    monkeypatch.setattr(CT._lib, "lib", lambda: _Spy(real, seen, run_calls))
     stats = []
     CT.decode_continuous(m, dev, _options(), slots=3, sample_lens=LENS, check_every=4, stats_out=stats)
-    assert "wipa_decoder_admit_rows" in seen and "wipa_decoder_run_continuous_rules" in seen
+    assert "wipa_decoder_admit_rows" in seen and run_calls and set(run_calls) == {UNPROMPTED}, run_calls
     assert not [name for name in seen if name in NEW_ENTRY_POINTS], seen
     assert stats[0].admissions[0][2] == 0 and min(col for _, _, col in stats[0].admissions) == 0
-    del seen[:]
+    del seen[:], run_calls[:]
     tstats = []
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")  # the random-init model's average log-probability is below upstream's fallback threshold
         wipa.transcribe(m, _files(), language="en", sample_len=20, fp16=False, schedule="continuous", slots=2, check_every=8, stats_out=tstats)
-    assert "wipa_decoder_admit_rows" in seen and "wipa_decoder_run_continuous_rules" in seen
+    assert "wipa_decoder_admit_rows" in seen and run_calls and set(run_calls) == {UNPROMPTED}, run_calls
     assert not [name for name in seen if name in NEW_ENTRY_POINTS], seen
     assert tstats[0].prompt_budget is None and tstats[0].prompts == []
     assert tstats[0].schedule.admissions[0][2] == 0 and min(col for _, _, col in tstats[0].schedule.admissions) == 0
-    del seen[:]
+    del seen[:], run_calls[:]
     CT.decode_continuous(m, dev, _options(), slots=3, sample_lens=LENS, check_every=4, prompts=histories)
     assert all(name in seen for name in NEW_ENTRY_POINTS), seen
-    assert "wipa_decoder_admit_rows" not in seen and "wipa_decoder_run_continuous_rules" not in seen
+    assert "wipa_decoder_admit_rows" not in seen and run_calls and set(run_calls) == {PROMPTED}, run_calls
 
 
 # ---------------------------------------------------------------- transcribe(): conditioning on both schedules

@@ -1,4 +1,4 @@
-"""GPU: continuous batching under the timestamp rules (include/wipa.h: wipa_decoder_run_continuous_rules and the CONTINUOUS tails with
+"""GPU: continuous batching under the timestamp rules (include/wipa.h: wipa_decode_call.continuous with .rules and the CONTINUOUS tails with
 rules; whisper_ipa_amd.continuous.decode_continuous(without_timestamps=False), run_stream; transcribe(schedule="continuous")) against
 the CPU restatement of tests/timestamp_ref.py with every clip decoded ALONE, batch of one, to its own limit -- slots, refill, admission
 columns and shifts do not exist there.  ``pytest -m gpu`` on an MI355X.
@@ -251,7 +251,7 @@ def test_bf16_d384_follows_the_rules_on_its_own_logits():
 
 def test_admit_run_and_shift_through_the_c_abi(refs):
     """DeviceStepper with rules drives admit, steps, a second admission at a later column, a shift and more steps through
-    wipa_decoder_run_continuous_rules, 3 slots: the token columns of each row equal the same clip decoded alone"""
+    continuous wipa_decoder_run_ex calls with rules, 3 slots: the token columns of each row equal the same clip decoded alone"""
     from whisper_ipa_amd.continuous import DeviceStepper
     from whisper_ipa_amd.runtime import on_stream
 

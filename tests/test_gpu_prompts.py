@@ -1,5 +1,5 @@
 """GPU: prompt conditioning -- per-row prompts right-aligned to one prompt width (include/wipa.h: wipa_decoder_begin_ragged /
-wipa_decoder_run_ragged; the RAGGED instantiations of decode_attn_kernel and of the step tails) against tests/prompt_ref.py, where every
+wipa_decoder_run_ex with wipa_decode_call.starts_dev; the RAGGED instantiations of decode_attn_kernel and of the step tails) against tests/prompt_ref.py, where every
 row is decoded alone with its unpadded initial tokens.  Reference: mlx_whisper.transcribe's condition_on_previous_text
 (scripts/evaluate_model.py:112-119 of the reference calls it with upstream's defaults).  ``pytest -m gpu`` on an MI355X.
 
@@ -118,7 +118,7 @@ def test_ragged_batch_f32_vs_per_row_cpu_loop(refs, monkeypatch, weights, use_gr
 # ---------------------------------------------------------------- 2. the batched prompt pass equals stepping the prompt
 @pytest.mark.parametrize("dims,dtype,cross", [(MICRO, torch.float32, "cached"), (W384, torch.bfloat16, "cached"), (W384, torch.bfloat16, "absorbed")])
 def test_prompt_pass_equals_stepping_the_prompt(mels, monkeypatch, dims, dtype, cross):
-    """wipa_decoder_prefill_ragged + wipa_decoder_run_ragged against the prompt walked column by column, for the same ragged batch:
+    """wipa_decoder_prefill_ragged + wipa_decoder_run_ex (starts_dev) against the prompt walked column by column, for the same ragged batch:
     f32: the same tokens, log-prob sums and first-column logits within 1e-3 (the bound of test_prompt_prefill_equals_stepwise_prompt:
     the pass batches B * P rows into other GEMM and attention kernels than the step's).  bf16, both cross-attention forms (the pass
     projects the absorbed form's K / V itself): the figures are printed; the logits must agree to 2^-5 of the largest logit -- bf16
@@ -220,8 +220,8 @@ def test_ragged_sampling_draws_at_the_rows_own_position(refs):
 # ---------------------------------------------------------------- 5. starts of zero and rows without prompts
 @pytest.mark.parametrize("with_rules", [True, False])
 def test_zero_starts_reproduce_the_plain_entry_points(refs, monkeypatch, with_rules):
-    """wipa_decoder_begin_ragged with every start 0 and P = 3, then the ragged entry points.  Stepping (wipa_decoder_run_ragged against
-    wipa_decoder_begin + wipa_decoder_run, both with WIPA_NO_PREFILL=1) runs the RAGGED instantiations of the same kernels on the same
+    """wipa_decoder_begin_ragged with every start 0 and P = 3, then the ragged entry points.  Stepping (wipa_decoder_run_ex with starts_dev against
+    wipa_decoder_begin and the call without it, both with WIPA_NO_PREFILL=1) runs the RAGGED instantiations of the same kernels on the same
     numbers: tokens and log-prob sums bit for bit.  The batched passes are different kernels by design (wipa_decoder_prefill_ragged is
     the teacher-forced body, wipa_decoder_prefill the four-row one), so there the comparison is the one the project makes between
     wipa_decoder_prefill and stepping: the same tokens, sums within 1e-3."""
@@ -245,21 +245,36 @@ def test_zero_starts_reproduce_the_plain_entry_points(refs, monkeypatch, with_ru
     assert (got.sum_logprobs == want.sum_logprobs).all(), (got.sum_logprobs.tolist(), want.sum_logprobs.tolist())
 
 
+def _call_fields(k):
+    """a DecodeCall as plain values: integers as they are, pointers as addresses (None: NULL), the rules as their three numbers"""
+    out = {}
+    for name, _ in k._fields_:
+        v = getattr(k, name)
+        out[name] = v if v is None or type(v) is int else ((v.contents.timestamp_begin, v.contents.no_timestamps, v.contents.max_initial_timestamp_index) if v else None)
+    return out
+
+
 class _Spy:
     """libwipa behind a recorder: every call of an entry point is recorded by name (``calls``) and with every plain-int argument
-    (``records``: (name, ints) -- sizes, batch, prompt width, eot, step count, use_graph, and the addresses ``ptr()`` hands over)"""
+    (``records``: (name, ints) -- sizes, batch, prompt width, eot, step count, use_graph, and the addresses ``ptr()`` hands over); a
+    wipa_decoder_run_ex / wipa_decoder_prefill_ex call also with the fields of its wipa_decode_call (``fields``, and in ``records``)"""
 
     def __init__(self, real):
-        self._real, self.calls, self.records, self.run_steps = real, [], [], []
+        self._real, self.calls, self.records, self.run_steps, self.fields = real, [], [], [], []
 
     def __getattr__(self, name):
         fn = getattr(self._real, name)
 
         def counted(*a):
             self.calls.append(name)
-            self.records.append((name, tuple(v for v in a if type(v) is int)))
+            ints = tuple(v for v in a if type(v) is int)
+            if name in ("wipa_decoder_run_ex", "wipa_decoder_prefill_ex"):
+                k = _call_fields(a[5]._obj)  # the DecodeCall behind C.byref
+                self.fields.append((name, k))
+                ints += tuple(sorted(k.items()))
+            self.records.append((name, ints))
             if name.startswith("wipa_decoder_run"):
-                self.run_steps.append(a[9])  # n_steps: the tenth argument of all four run entry points
+                self.run_steps.append(a[6] if name == "wipa_decoder_run_ex" else a[9])  # n_steps
             return fn(*a)
 
         return counted
@@ -283,6 +298,8 @@ def test_decode_without_prompts_makes_the_calls_it_made(refs, monkeypatch):
     b = wipa.decode(m, feats, opts, prompts=[None, None])
     monkeypatch.setattr(_lib, "_lib", real)
     assert spy_a.calls == spy_b.calls and not any("ragged" in c for c in spy_b.calls), (spy_a.calls, spy_b.calls)
+    assert spy_b.fields and all(k["starts_dev"] is None for _, k in spy_b.fields), spy_b.fields  # no row has a start of its own
+    assert any(k["rules"] is not None for _, k in spy_b.fields)  # the decode itself runs under the timestamp rules
     assert spy_a.records == spy_b.records, (spy_a.records, spy_b.records)  # ... with the same integer arguments, step counts included
     assert [r.tokens for r in a] == [r.tokens for r in b]
     # and a prompt takes the ragged entry points
@@ -290,7 +307,9 @@ def test_decode_without_prompts_makes_the_calls_it_made(refs, monkeypatch):
     monkeypatch.setattr(_lib, "_lib", spy_c)
     c = wipa.decode(m, feats, opts, prompts=[None, PR.histories()[2]])
     monkeypatch.setattr(_lib, "_lib", real)
-    assert "wipa_decoder_begin_ragged" in spy_c.calls and "wipa_decoder_run_ragged" in spy_c.calls and "wipa_decoder_begin" not in spy_c.calls
+    runs = [k for name, k in spy_c.fields if name == "wipa_decoder_run_ex"]
+    assert "wipa_decoder_begin_ragged" in spy_c.calls and runs and all(k["starts_dev"] is not None for k in runs) and "wipa_decoder_begin" not in spy_c.calls
+    assert "wipa_decoder_prefill_ex" not in spy_c.calls and "wipa_decoder_prefill_ragged" in spy_c.calls
     assert all(np.isfinite(r.no_speech_prob) for r in c)
 
 
@@ -312,7 +331,7 @@ def test_decode_loop_step_schedule(refs, monkeypatch, prefill):
     rows = [list(ROWS[1][-5:]), list(PR.SOT_SEQUENCE)]
     assert [len(r) for r in rows] == [5, 3] and len(PR.SOT_SEQUENCE) == 3
     kw = dict(max_new_tokens=12)
-    cases = [("wipa_decoder_prefill", lambda: greedy_decode_tokens(m, feats, PR.SOT_SEQUENCE, always, first, -1, **kw), [8, 3], [10, 4]),
+    cases = [("wipa_decoder_prefill_ex", lambda: greedy_decode_tokens(m, feats, PR.SOT_SEQUENCE, always, first, -1, **kw), [8, 3], [10, 4]),
              ("wipa_decoder_prefill_ragged", lambda: ragged_decode_tokens(m, feats, rows, always, first, -1, pad_to=6, **kw), [8, 3], [13, 4]),
              ("wipa_decoder_prefill_ragged", lambda: ragged_decode_tokens(m, feats, rows, always, first, -1, pad_to=6, sot_back=3, **kw),
               [8, 3], [4, 9, 4])]
@@ -329,6 +348,8 @@ def test_decode_loop_step_schedule(refs, monkeypatch, prefill):
         assert passes == ([prefill_name] if prefill else []), passes
         if prefill:
             assert spy.calls.index(prefill_name) < min(i for i, c in enumerate(spy.calls) if c.startswith("wipa_decoder_run"))
+        ragged = prefill_name == "wipa_decoder_prefill_ragged"  # the run calls of the ragged loop carry the rows' starts, the others none
+        assert all((k["starts_dev"] is not None) == ragged and k["n_init"] == (6 if ragged else 3) for name, k in spy.fields if name == "wipa_decoder_run_ex")
 
 
 # ---------------------------------------------------------------- 6. refusals that need a live state

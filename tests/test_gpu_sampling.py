@@ -1,5 +1,5 @@
 """GPU: temperature sampling in the decode step's tail (csrc/elementwise.hip: row_pick<.., SAMPLE> behind wipa_sample_step /
-wipa_sample_step_embed / wipa_sample_noise; wipa_decoder_run_sample / _prefill_sample; decode(temperature=, seed=);
+wipa_sample_step_embed / wipa_sample_noise; wipa_decode_call.sample; decode(temperature=, seed=);
 transcribe(seed=)) against the float64 restatement of tests/sampling_ref.py.  Reference: upstream's GreedyDecoder.update with
 temperature > 0 under mlx_whisper.transcribe's fallback schedule.  ``pytest -m gpu`` on an MI355X."""
 import ctypes as C

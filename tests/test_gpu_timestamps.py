@@ -1,5 +1,5 @@
 """GPU: the timestamp rules in the decode step's tail (csrc/elementwise.hip: rules_row_pick behind wipa_timestamp_step /
-wipa_timestamp_step_embed; wipa_decoder_run_rules / _prefill_rules) against the numpy restatement of tests/timestamp_ref.py.
+wipa_timestamp_step_embed; wipa_decoder_run_ex / wipa_decoder_prefill_ex with wipa_decode_call.rules) against the numpy restatement of tests/timestamp_ref.py.
 Reference: ApplyTimestampRules as mlx_whisper.transcribe applies it (the reference's scripts/evaluate_model.py:112-119).
 ``pytest -m gpu`` on an MI355X."""
 import ctypes as C
@@ -223,35 +223,44 @@ def test_decode_with_rules_f32_bit_exact_vs_cpu_loop(micro_refs, monkeypatch, we
 
 
 def test_null_rules_reproduce_the_plain_entry_points(micro_refs):
-    """wipa_decoder_prefill_rules / wipa_decoder_run_rules with rules = NULL: the tokens and log-prob sums of wipa_decoder_prefill /
-    wipa_decoder_run, bit for bit"""
+    """wipa_decoder_prefill_ex / wipa_decoder_run_ex with a call that holds only n_init, eot and the masks (rules = NULL, nothing else)
+    against wipa_decoder_prefill / wipa_decoder_run: tokens, log-prob sums and last-step logits bit for bit.  The micro f32 model of
+    tests/golden/micro_model.npz, B = 3, 6 steps, replayed and eager."""
     from whisper_ipa_amd import _lib
-    from whisper_ipa_amd.decoding import _mask, _packed_for, _state_for, greedy_decode_tokens
+    from whisper_ipa_amd.decoding import _mask, _packed_for, _state_for
     from whisper_ipa_amd.runtime import on_stream, ptr, sptr
 
     W, xa, _ = micro_refs["lively"]
     always, first = R.suppress_lists(SP)
     init = list(SP.sot_sequence_including_notimestamps(0))
     m = _model(MICRO, W, torch.float32)
-    want = greedy_decode_tokens(m, xa.cuda(), init, always, first, EOT, max_new_tokens=STEPS, stop_on_eot=False)
     L = _lib.lib()
-    B, n_init = 2, len(init)
-    pk = _packed_for(m, B, STEPS)
+    B, n_init, steps = 3, len(init), 6
+    pk = _packed_for(m, B, steps)
     st = _state_for(m, B, pk)
     m_always, m_first = _mask(m, always), _mask(m, list(always) + list(first))
     host_init = (C.c_int32 * n_init)(*init)
+    feats = torch.cat([xa, xa[:1].flip(1)]).cuda().contiguous()  # a third clip: the first one's frames backwards
+    assert feats.shape[0] == B
     with on_stream() as s:
-        feats = xa.cuda().contiguous()
         cfg, tab, blob, nb = C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel()
-        _lib.check(L.wipa_decoder_set_audio(cfg, tab, ptr(feats), blob, nb, B, sptr(s)), "set_audio")
-        _lib.check(L.wipa_decoder_begin(cfg, blob, nb, B, host_init, n_init, sptr(s)), "begin")
-        _lib.check(L.wipa_decoder_prefill_rules(cfg, tab, blob, nb, B, n_init, EOT, ptr(m_first), ptr(m_always), 1, None, sptr(s)), "prefill_rules")
-        _lib.check(L.wipa_decoder_run_rules(cfg, tab, blob, nb, B, n_init, EOT, ptr(m_first), ptr(m_always), STEPS - 1, 1, None, sptr(s)),
-                   "run_rules")
-        toks = st.tokens[:, : n_init + STEPS].cpu().numpy().astype(np.int64)
-        slp = st.sum_logprobs.cpu().numpy().copy()
-    assert (toks == want.tokens).all()
-    assert (slp == want.sum_logprobs).all()
+        for use_graph in (1, 0):  # replayed and eager
+            out = {}
+            for which in ("plain", "ex"):
+                _lib.check(L.wipa_decoder_set_audio(cfg, tab, ptr(feats), blob, nb, B, sptr(s)), "set_audio")
+                _lib.check(L.wipa_decoder_begin(cfg, blob, nb, B, host_init, n_init, sptr(s)), "begin")
+                if which == "plain":
+                    _lib.check(L.wipa_decoder_prefill(cfg, tab, blob, nb, B, n_init, EOT, ptr(m_first), ptr(m_always), use_graph, sptr(s)), "prefill")
+                    _lib.check(L.wipa_decoder_run(cfg, tab, blob, nb, B, n_init, EOT, ptr(m_first), ptr(m_always), steps - 1, use_graph, sptr(s)), "run")
+                else:
+                    call = _lib.DecodeCall(n_init=n_init, eot=EOT, mask_first=ptr(m_first), mask_always=ptr(m_always))
+                    _lib.check(L.wipa_decoder_prefill_ex(cfg, tab, blob, nb, B, C.byref(call), use_graph, sptr(s)), "prefill_ex")
+                    _lib.check(L.wipa_decoder_run_ex(cfg, tab, blob, nb, B, C.byref(call), steps - 1, use_graph, sptr(s)), "run_ex")
+                out[which] = (st.tokens[:, : n_init + steps].cpu().numpy().copy(), st.sum_logprobs.cpu().numpy().copy(), st.logits.cpu().numpy().copy())
+            toks, slp, logits = out["plain"]
+            assert len({tuple(r) for r in toks[:, n_init:].tolist()}) > 1 and np.isfinite(logits).all()  # the rows differ: not a trivial comparison
+            for name, a, b in zip(("tokens", "sum_logprobs", "logits"), out["plain"], out["ex"]):
+                assert a.tobytes() == b.tobytes(), (use_graph, name)
 
 
 def test_rules_are_refused_where_the_step_has_no_fused_tail(micro_refs, monkeypatch):

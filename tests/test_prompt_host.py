@@ -264,8 +264,11 @@ def test_run_ragged_refuses_what_the_step_cannot_serve(built, monkeypatch):
     lay = built.DecLayout()
     assert lib.wipa_decoder_layout(C.byref(cfg), 2, C.byref(lay)) == 0
 
-    def run(cfg, n_init, n_steps, starts=fake):
-        return lib.wipa_decoder_run_ragged(C.byref(cfg), tab, fake, lay.total_bytes, 2, n_init, EOT, fake, fake, n_steps, 0, None, None, starts, None)
+    def run(cfg, n_init, n_steps, starts=0x1000):
+        call = built.DecodeCall(n_init=n_init, eot=EOT, mask_first=0x1000, mask_always=0x1000, starts_dev=starts)
+        rc = lib.wipa_decoder_run_ex(C.byref(cfg), tab, fake, lay.total_bytes, 2, C.byref(call), n_steps, 0, None)
+        assert rc == 0 or lib.wipa_last_error().startswith(b"wipa_decoder_run_ex: ")
+        return rc
 
     assert run(cfg, 227, 448) != 0 and b"n_steps" in lib.wipa_last_error() and b"n_text_ctx" in lib.wipa_last_error()
     assert run(cfg, 449, 1) != 0 and b"P=449" in lib.wipa_last_error()

@@ -3,12 +3,12 @@
 tools/continuous_rules_bench.py.
   step       one continuous step with rules over 64 rows, columns 8 .. 72: (a call of 72 steps - a call of 8 steps) / 64 between HIP
              events, median of the repeats, the variants alternating --
-               rules       wipa_decoder_run_continuous_rules, the tail without a sampling record (what a decode without per-row
+               rules       a continuous call with rules, the tail without a sampling record (what a decode without per-row
                            temperatures launches)
-               sample_0.6  the same entry point with the one-temperature sampling record at 0.6 (the existing sampling tail)
-               rows_0      wipa_decoder_run_continuous_rows, every row greedy
-               rows_0.6    the same entry point, every row at temperature 0.6
-               rows_half   the same entry point, every second row at 0.6, the others greedy
+               sample_0.6  the same call with the one-temperature sampling record at 0.6 (the existing sampling tail)
+               rows_0      the call with wipa_decode_call.sample_rows, every row greedy
+               rows_0.6    the same call, every row at temperature 0.6
+               rows_half   the same call, every second row at 0.6, the others greedy
   schedules  wipa.transcribe(seed=3) on the 24 files of tools/continuous_rules_bench.py (sample_len 32): schedule="rounds" against
              schedule="continuous" with 24 and with 8 slots -- wall time, decoder steps, retries per window.  With random weights the
              average log-probability of nearly every window lies far below the threshold, so nearly every window runs the whole

@@ -2,10 +2,10 @@
 """Prompts on the continuous schedule: whisper-small bf16, synthetic weights, the setting of tools/continuous_rules_bench.py and
 tools/prompt_bench.py.  HIP events on the library stream, after warm-up, the variants alternating within every repeat.
   step        one continuous step with rules over 64 rows: (a call of 72 steps - a call of 8 steps) / 64, median of the repeats --
-                rules           wipa_decoder_run_continuous_rules, columns 8 .. 72 (the unprompted step, unchanged kernels)
-                prompted_empty  wipa_decoder_run_continuous_prompted on the same columns: prompt room 0, no row has a prompt -- the
+                rules           a continuous call with rules, columns 8 .. 72 (the unprompted step, unchanged kernels)
+                prompted_empty  the same call with wipa_decode_call.prompted on the same columns: prompt room 0, no row has a prompt -- the
                                 PROMPTED tail against the CONTINUOUS one and nothing else
-                prompted_197    the same entry point, every row behind a 197-column prompt (prompt room 197): the steps stand at columns
+                prompted_197    the same prompted call, every row behind a 197-column prompt (prompt room 197): the steps stand at columns
                                 205 .. 269 and every row's self-attention sees 197 more keys -- what a conditioned row pays per step
   admission   one wipa_decoder_admit_rows_prompted call (cross-attention input + tokens + the prompt pass + the K / V scatter) for 1, 4
               and 16 rows x W = 32 and 197 prompt columns, against wipa_decoder_admit_rows of the same rows; the difference is the pass.

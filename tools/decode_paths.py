@@ -10,6 +10,11 @@ whose token rows feed the teacher-forced paths -- the wide one with cached and w
   forced                        forced_decode_logits (step logits, chosen ids)
   logits                        Whisper.logits (teacher-forced)
   align                         the alignment pass (matrix, DTW paths, token probabilities)
+  beam_cached / _absorbed       beam search, beam_size 3 and patience 2, with the rules (winners, sums, lengths); micro on both
+  continuous_plain              decode_continuous: five clips of unequal length through two slots, without timestamps
+  continuous_rules              the same with the timestamp rules and the no-speech probabilities
+  continuous_rows               the same with a temperature and an attempt per clip
+  continuous_prompts            the same with a prompt per clip (two of the five without one)
 and, unless --no-switches, greedy_graph again in a fresh child process under each A/B switch (the switches are read per call, the
 init passes run once per process).  A torch.flip launch separates the paths in a kernel trace.
 usage: python tools/decode_paths.py [--no-switches] [--only PATH]     prints "<path> <array> <sha256>" lines
@@ -26,7 +31,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SWITCHES = ["WIPA_DECODE_FUSED=0", "WIPA_DECODE_FUSED=1", "WIPA_DECODE_TAIL=0", "WIPA_LOGITS_FUSED=0", "WIPA_ABS_FUSED_PROLOGUE=0",
             "WIPA_ABS_MERGE_OUT=1"]
 PATHS = ["greedy_graph", "greedy_eager", "greedy_rules", "sampled", "ragged_pass", "ragged_walk", "best_of_cached", "best_of_absorbed",
-         "forced", "logits", "align"]
+         "forced", "logits", "align", "beam_cached", "beam_absorbed", "continuous_plain", "continuous_rules", "continuous_rows",
+         "continuous_prompts"]
 MARKER = "flip"  # in the name of the kernel torch.flip launches; no path launches it
 
 
@@ -63,7 +69,8 @@ def main():
     import torch
     from oracle import whisper_ref as R
     from whisper_ipa_amd import _lib
-    from whisper_ipa_amd.decoding import Sampling, forced_decode_logits, greedy_decode_tokens, ragged_decode_tokens
+    from whisper_ipa_amd.continuous import decode_continuous
+    from whisper_ipa_amd.decoding import Beams, DecodingOptions, Sampling, forced_decode_logits, greedy_decode_tokens, ragged_decode_tokens
     from whisper_ipa_amd.timing import align_tokens
     from whisper_ipa_amd.whisper import ModelDimensions, Whisper
 
@@ -156,7 +163,33 @@ def main():
             for b, (ti, tj) in enumerate(paths):
                 sha(path, f"{k}_path{b}", np.stack([ti, tj]))
 
-    run = {"greedy_graph": lambda p: greedy(p), "greedy_eager": lambda p: greedy(p, use_graph=False), "greedy_rules": lambda p: greedy(p, init3, rules=rules),
+    def beam(path, wide):
+        for k in ("micro", wide):
+            m, f = models[k]
+            tokens_out(path, k, greedy_decode_tokens(m, f, init3, always, first, sp.eot, max_new_tokens=20, stop_on_eot=False, rules=rules,
+                                                     n_group=3, beams=Beams(6), length_penalty=None))
+
+    lens5 = [9, 4, 12, 6, 8]
+
+    def backwards(x, dim):  # torch.flip's values by a gather: the flip kernel is the marker between the paths
+        return x.index_select(dim, torch.arange(x.shape[dim] - 1, -1, -1, device=x.device))
+
+    def continuous(path, timestamps=True, **kw):
+        for k, (m, f) in models.items():
+            five = torch.cat([f, backwards(f, 1), backwards(f[:1], 2)]).contiguous()  # five clips from the two: frames, then channels backwards
+            opts = DecodingOptions(language="en", without_timestamps=not timestamps, fp16=False, **({"seed": 5} if "temperatures" in kw else {}))
+            res = decode_continuous(m, five, opts, slots=2, sample_lens=lens5, check_every=4, **kw)
+            width = max(len(r.tokens) for r in res)
+            sha(path, f"{k}_tokens", np.array([list(r.tokens) + [-1] * (width - len(r.tokens)) for r in res], dtype=np.int64))
+            sha(path, f"{k}_lengths", np.array([len(r.tokens) for r in res], dtype=np.int64))
+            sha(path, f"{k}_avg_logprob", np.array([r.avg_logprob for r in res], dtype=np.float64))
+            sha(path, f"{k}_no_speech_prob", np.array([r.no_speech_prob for r in res], dtype=np.float64))
+
+    run = {"beam_cached": lambda p: beam(p, "wide_cached"), "beam_absorbed": lambda p: beam(p, "wide_absorbed"),
+           "continuous_plain": lambda p: continuous(p, timestamps=False), "continuous_rules": continuous,
+           "continuous_rows": lambda p: continuous(p, temperatures=[0.0, 0.6, 0.8, 0.0, 0.6], attempts=[0, 1, 2, 0, 1]),
+           "continuous_prompts": lambda p: continuous(p, prompts=[history[:9], [], history[5:21], [], history[:3]]),
+           "greedy_graph": lambda p: greedy(p), "greedy_eager": lambda p: greedy(p, use_graph=False), "greedy_rules": lambda p: greedy(p, init3, rules=rules),
            "sampled": sampled, "ragged_pass": lambda p: ragged(p, False), "ragged_walk": lambda p: ragged(p, True),
            "best_of_cached": lambda p: best_of(p, "wide_cached"), "best_of_absorbed": lambda p: best_of(p, "wide_absorbed"),
            "forced": forced, "logits": logits, "align": align}

@@ -2,7 +2,7 @@
 """Cost of temperature sampling in the replayed decode step: whisper-small bf16, synthetic weights, B clips (default 64), one pass in
 flight, the timestamp rules on in both variants.  Per repeat and variant: prompt prefill, two warm steps, then N steps replayed from
 the captured graph between two HIP events; the variants alternate within a repeat so that drift hits both.  Temperature 0 is
-wipa_decoder_run_rules, unchanged by the sampling work; the sampled step is wipa_decoder_run_sample with the same rules: the same
+the call with rules alone, unchanged by the sampling work; the sampled step adds wipa_decode_call.sample to the same rules: the same
 logits GEMM and written logits, and a tail that adds one Philox4x32-10 call per alive quad, two logf per alive column and a third
 (max, lowest column) reduction.  A second table times the two tails ALONE on B x 51 865 random logits (wipa_timestamp_step against
 wipa_sample_step, no embedding), which is what to hold against the step's logits GEMM.  Prints means and run-to-run spreads in us
@@ -20,7 +20,7 @@ import whisper_ipa_amd as wipa  # noqa: E402,F401  (before the first torch.cuda 
 import torch  # noqa: E402
 import bench  # noqa: E402
 from whisper_ipa_amd import _lib  # noqa: E402
-from whisper_ipa_amd.decoding import Sampling, _mask, _packed_for, _state_for  # noqa: E402
+from whisper_ipa_amd.decoding import Sampling, _mask, _packed_for, _state_for, decode_call  # noqa: E402
 from whisper_ipa_amd.runtime import on_stream, ptr, sptr  # noqa: E402
 
 
@@ -54,16 +54,14 @@ def main():
     cfg, tab, blob, nb = C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel()
 
     def one(sampled: bool, s, rec) -> float:
-        tail = (C.byref(rules), ptr(rec), sptr(s)) if sampled else (C.byref(rules), sptr(s))
-        run = L.wipa_decoder_run_sample if sampled else L.wipa_decoder_run_rules
-        pre = L.wipa_decoder_prefill_sample if sampled else L.wipa_decoder_prefill_rules
-        args9 = (cfg, tab, blob, nb, B, n_init, eot, ptr(m_first), ptr(m_always))
+        call = decode_call(n_init, eot, m_first, m_always, rules, rec if sampled else None)
+        head = (cfg, tab, blob, nb, B, C.byref(call))
         _lib.check(L.wipa_decoder_begin(cfg, blob, nb, B, host_init, n_init, sptr(s)), "wipa_decoder_begin")
-        _lib.check(pre(*args9, 1, *tail), "prefill")
-        _lib.check(run(*args9, 2, 1, *tail), "warm steps")
+        _lib.check(L.wipa_decoder_prefill_ex(*head, 1, sptr(s)), "prefill")
+        _lib.check(L.wipa_decoder_run_ex(*head, 2, 1, sptr(s)), "warm steps")
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(s)
-        _lib.check(run(*args9, args.steps, 1, *tail), "timed steps")
+        _lib.check(L.wipa_decoder_run_ex(*head, args.steps, 1, sptr(s)), "timed steps")
         e1.record(s)
         e1.synchronize()
         return e0.elapsed_time(e1) * 1e3 / args.steps

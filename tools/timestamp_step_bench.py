@@ -2,10 +2,9 @@
 """Cost of the timestamp rules in the replayed decode step: whisper-small bf16, synthetic weights, B clips (default 64), one pass in
 flight.  Per repeat and variant: prompt prefill, two warm steps, then N steps replayed from the captured graph between two HIP events;
 the variants alternate within a repeat so that drift hits both.  Rules off is the plain step (the logits projection carries the greedy
-partials and no step but the last writes its logits); rules on is wipa_decoder_run_rules: every step writes its logits (B x 51 865 f32)
+partials and no step but the last writes its logits); rules on is a call with wipa_decode_call.rules: every step writes its logits (B x 51 865 f32)
 and the row-scan tail reads them back, scans the row's history and makes two reductions.  Both variants use the same three-token
 prompt, so they time the same positions.  Prints the mean and the run-to-run spread in us per step and one JSON line.
-On a tree without the rules entry points (the parent commit) only the rules-off figure is measured.
 usage: python tools/timestamp_step_bench.py [--batch 64] [--steps 48] [--repeats 7]"""
 import argparse
 import ctypes as C
@@ -19,7 +18,7 @@ import whisper_ipa_amd as wipa  # noqa: E402,F401  (before the first torch.cuda 
 import torch  # noqa: E402
 import bench  # noqa: E402
 from whisper_ipa_amd import _lib  # noqa: E402
-from whisper_ipa_amd.decoding import _mask, _packed_for, _state_for  # noqa: E402
+from whisper_ipa_amd.decoding import _mask, _packed_for, _state_for, decode_call  # noqa: E402
 from whisper_ipa_amd.runtime import on_stream, ptr, sptr  # noqa: E402
 
 
@@ -35,8 +34,7 @@ def main():
     model = bench.build_model("small")
     init4, always, first, eot = bench.decode_setup()
     init = init4[:3]  # sot, language, task: the timestamp path's prompt, used for both variants
-    has_rules = hasattr(_lib, "DecodeRules")
-    rules = _lib.DecodeRules(init4[3] + 1, init4[3], 50) if has_rules else None
+    rules = _lib.DecodeRules(init4[3] + 1, init4[3], 50)
     n_init = len(init)
     pk = _packed_for(model, B, args.steps + 4)
     st = _state_for(model, B, pk)
@@ -47,21 +45,19 @@ def main():
     cfg, tab, blob, nb = C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel()
 
     def one(with_rules: bool, s) -> float:
-        tail = (C.byref(rules), sptr(s)) if with_rules else (sptr(s),)
-        run = L.wipa_decoder_run_rules if with_rules else L.wipa_decoder_run
-        pre = L.wipa_decoder_prefill_rules if with_rules else L.wipa_decoder_prefill
-        args9 = (cfg, tab, blob, nb, B, n_init, eot, ptr(m_first), ptr(m_always))
+        call = decode_call(n_init, eot, m_first, m_always, rules if with_rules else None)
+        head = (cfg, tab, blob, nb, B, C.byref(call))
         _lib.check(L.wipa_decoder_begin(cfg, blob, nb, B, host_init, n_init, sptr(s)), "wipa_decoder_begin")
-        _lib.check(pre(*args9, 1, *tail), "prefill")
-        _lib.check(run(*args9, 2, 1, *tail), "warm steps")
+        _lib.check(L.wipa_decoder_prefill_ex(*head, 1, sptr(s)), "prefill")
+        _lib.check(L.wipa_decoder_run_ex(*head, 2, 1, sptr(s)), "warm steps")
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(s)
-        _lib.check(run(*args9, args.steps, 1, *tail), "timed steps")
+        _lib.check(L.wipa_decoder_run_ex(*head, args.steps, 1, sptr(s)), "timed steps")
         e1.record(s)
         e1.synchronize()
         return e0.elapsed_time(e1) * 1e3 / args.steps
 
-    variants = [False, True] if has_rules else [False]
+    variants = [False, True]
     times = {v: [] for v in variants}
     with on_stream() as s:
         _lib.check(L.wipa_decoder_set_audio(cfg, tab, ptr(feats), blob, nb, B, sptr(s)), "wipa_decoder_set_audio")
@@ -78,9 +74,8 @@ def main():
         name = "rules_on" if v else "rules_off"
         out[name + "_us"] = {"mean": sum(t) / len(t), "min": t[0], "max": t[-1]}
         print(f"  {name:<9} {sum(t) / len(t):8.1f} us per step   (min {t[0]:.1f}, max {t[-1]:.1f} over {len(t)} repeats)")
-    if has_rules:
-        out["rules_cost_us"] = out["rules_on_us"]["mean"] - out["rules_off_us"]["mean"]
-        print(f"  the rules cost {out['rules_cost_us']:+.1f} us per step ({100.0 * out['rules_cost_us'] / out['rules_off_us']['mean']:+.1f} %)")
+    out["rules_cost_us"] = out["rules_on_us"]["mean"] - out["rules_off_us"]["mean"]
+    print(f"  the rules cost {out['rules_cost_us']:+.1f} us per step ({100.0 * out['rules_cost_us'] / out['rules_off_us']['mean']:+.1f} %)")
     print(json.dumps({"timestamp_step_bench": out}))
 
 

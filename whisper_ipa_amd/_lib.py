@@ -103,6 +103,14 @@ class DecodeRules(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("timestamp_begin", "no_timestamps", "max_initial_timestamp_index")]
 
 
+class DecodeCall(C.Structure):
+    """wipa_decode_call: what wipa_decoder_run_ex / wipa_decoder_prefill_ex take; every optional field is 0 / None for "not used" """
+    _fields_ = [("n_init", C.c_int32), ("eot", C.c_int32), ("mask_first", c_void_p), ("mask_always", c_void_p),
+                ("rules", C.POINTER(DecodeRules)), ("sample", c_void_p), ("sample_rows", c_void_p), ("starts_dev", c_void_p),
+                ("continuous", C.c_int32), ("prompted", C.c_int32), ("no_speech_dev", c_void_p), ("no_speech_token", C.c_int32),
+                ("beam", c_void_p), ("beam_bytes", c_size_t), ("beam_max_candidates", C.c_int32)]
+
+
 class DecLayout(C.Structure):
     _fields_ = [(n, c_int64) for n in (
         "total_bytes", "tokens", "ld_tok", "pos", "not_done", "sum_logprobs", "logits", "ld_logits",
@@ -217,14 +225,8 @@ SIGNATURES = {
                                  c_int, c_void_p]),
     "wipa_decoder_prefill": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                      c_void_p]),
-    "wipa_decoder_run_rules": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
-                                       c_int, _P(DecodeRules), c_void_p]),
-    "wipa_decoder_prefill_rules": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
-                                           _P(DecodeRules), c_void_p]),
-    "wipa_decoder_run_sample": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
-                                        c_int, _P(DecodeRules), c_void_p, c_void_p]),
-    "wipa_decoder_prefill_sample": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
-                                            _P(DecodeRules), c_void_p, c_void_p]),
+    "wipa_decoder_run_ex": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, _P(DecodeCall), c_int, c_int, c_void_p]),
+    "wipa_decoder_prefill_ex": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, _P(DecodeCall), c_int, c_void_p]),
     "wipa_embed_layernorm_ragged": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                             c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "wipa_step_embed_ragged": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
@@ -238,10 +240,6 @@ SIGNATURES = {
                                c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "wipa_beam_finalize": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64,
                                    c_void_p, c_void_p, c_void_p]),
-    "wipa_decoder_run_beam": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
-                                      _P(DecodeRules), c_void_p, c_size_t, c_int, c_void_p]),
-    "wipa_decoder_prefill_beam": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
-                                          _P(DecodeRules), c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "wipa_embed_tokens_ragged": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "wipa_attention_ragged": (c_int, [_P(AttnDesc), c_void_p, c_void_p]),
     "wipa_sample_step_ragged": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int,
@@ -250,14 +248,6 @@ SIGNATURES = {
     "wipa_decoder_prefill_ragged": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                             _P(DecodeRules), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "wipa_decoder_begin_ragged": (c_int, [_P(ModelCfg), c_void_p, c_size_t, c_int, _P(C.c_int32), _P(C.c_int32), c_int, c_void_p, c_void_p]),
-    "wipa_decoder_run_ragged": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
-                                        c_int, _P(DecodeRules), c_void_p, c_void_p, c_void_p]),
-    "wipa_decoder_run_continuous": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
-                                            c_int, _P(DecodeRules), c_void_p, c_void_p, c_void_p]),
-    "wipa_decoder_run_continuous_rules": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
-                                                  c_int, _P(DecodeRules), c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "wipa_decoder_run_continuous_rows": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
-                                                 c_int, _P(DecodeRules), c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "wipa_sample_rows_bytes": (c_size_t, [c_int]),
     "wipa_sample_rows_fill": (c_int, [c_void_p, c_size_t, C.c_uint64, c_int]),
     "wipa_sample_rows_fill_row": (c_int, [c_void_p, c_size_t, c_int, c_int, C.c_uint32, C.c_uint32, c_int, c_float]),
@@ -270,8 +260,6 @@ SIGNATURES = {
     "wipa_decoder_admit_rows_prompted": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, _P(C.c_int32), _P(c_void_p),
                                                  _P(C.c_int32), c_int, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), c_int, c_void_p, c_void_p,
                                                  _P(C.c_uint32), c_void_p, c_size_t, c_void_p]),
-    "wipa_decoder_run_continuous_prompted": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p,
-                                                     c_int, c_int, _P(DecodeRules), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "wipa_decode_cross_attn_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "wipa_decode_cross_attn_grouped": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "wipa_cross_absorbed_attention_grouped": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,

@@ -1,6 +1,6 @@
 """Continuous-batching decode: the rows of one decode state are SLOTS, and a slot whose clip has finished takes the next clip while the
 other rows go on (include/wipa.h: wipa_decoder_admit_rows / wipa_decoder_shift_columns /
-wipa_decoder_run_continuous).
+wipa_decode_call.continuous).
 
 ``decode`` runs a batch in lockstep: every row steps until the last one has reached EOT, and a row that ended early sits EOT-latched
 in its slot, its encoder output still streamed through every cross-attention layer of every step.  Here the host looks at the last
@@ -12,7 +12,7 @@ counter nears the end of the table, all columns move down by the smallest start 
 The scheduler (``run_schedule``) is plain Python against a small stepper interface, so it is tested without a GPU; ``DeviceStepper`` is
 the stepper on the library.
 
-With ``without_timestamps=False`` the steps end in the CONTINUOUS tails with the timestamp rules (wipa_decoder_run_continuous_rules;
+With ``without_timestamps=False`` the steps end in the CONTINUOUS tails with the timestamp rules (wipa_decode_call.rules;
 DESIGN.md section 14): the rules run on every row's own sequence, from its own first column, and the tail leaves the row's no-speech
 probability at its <|startoftranscript|> column.  ``run_stream`` is the scheduler for clips that are not all known when the run starts
 -- the windows of files, of which ``transcribe(schedule="continuous")`` keeps one per file in flight (``stream_windows``); a check is
@@ -20,14 +20,14 @@ one device-to-host copy (``DeviceStepper.snapshot``).
 
 A TEMPERATURE PER ROW: ``decode_continuous(temperatures=, attempts=)`` and ``transcribe(schedule="continuous",
 seed=S)`` keep the state's sampling record with a row part (wipa_sample_rows_set: stream, attempt and 1 / temperature per slot, 0 for a
-greedy row) and end the steps in the tails that read it (wipa_decoder_run_continuous_rows), so a window retried at a higher temperature
+greedy row) and end the steps in the tails that read it (wipa_decode_call.sample_rows), so a window retried at a higher temperature
 sits beside greedy first attempts and beside retries of other windows at other temperatures.  ``run_stream``'s source may hand a clip
 out again, with its draw; ``_GroupStepper`` admits it from the encoder features its first admission left.
 
 A PROMPT PER ROW: ``decode_continuous(prompts=)`` and ``transcribe(schedule="continuous",
 condition_on_previous_text=True)``.  A clip is still admitted at the column the state stands at; its prompt ([sot_prev] + history)
 stands IN FRONT of that column and goes through one batched pass over the admitted rows only (wipa_decoder_admit_rows_prompted), and
-the steps end in the PROMPTED tails (wipa_decoder_run_continuous_prompted).  So that a prompt always has room, a prompted run opens its
+the steps end in the PROMPTED tails (wipa_decode_call.prompted).  So that a prompt always has room, a prompted run opens its
 state at column ``prompt_room`` (wipa_decoder_seek) and the loop never shifts below it.
 """
 from __future__ import annotations
@@ -41,8 +41,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .decoding import (DecoderState, DecodingOptions, DecodingResult, Sampling, _mask, _suppress_lists, compression_ratio, detect_language,
-                       timestamp_rules)
+from .decoding import (DecoderState, DecodingOptions, DecodingResult, Sampling, _mask, _suppress_lists, compression_ratio, decode_call,
+                       detect_language, timestamp_rules)
 from .runtime import on_stream, ptr, sptr, stream_id
 from .tokenizer import get_tokenizer
 
@@ -255,15 +255,15 @@ class DeviceStepper:
                  suppress_always: Sequence[int], suppress_first: Sequence[int], sample: Optional[Sampling], s, use_graph: bool = True,
                  rules: Optional["_lib.DecodeRules"] = None, no_speech_token: Optional[int] = None, row_seed: Optional[int] = None,
                  draws=None, prompts=None, prompt_room: Optional[int] = None):
-        """``rules``: the timestamp rules (wipa_decoder_run_continuous_rules; None: wipa_decoder_run_continuous).  With them and
+        """``rules``: the timestamp rules (wipa_decode_call.rules; None: the plain continuous tails).  With them and
         ``no_speech_token`` the step's tail leaves every row's no-speech probability in ``self.no_speech``.
-        ``row_seed``: a TEMPERATURE PER ROW (wipa_decoder_run_continuous_rows; ``sample`` is then None): the state's sampling record
+        ``row_seed``: a TEMPERATURE PER ROW (wipa_decode_call.sample_rows; ``sample`` is then None): the state's sampling record
         with a row part is filled with this seed, and every admission writes the admitted clips' entries -- ``draws(clip)`` or the
         fourth element of an admitted tuple, (temperature, attempt, (stream_lo, stream_hi)); None is a greedy row.
         ``prompt_room`` (None: no prompts, the calls and the [2][B] starts buffer of the unprompted stepper): a PROMPTED stepper -- the
         state is opened at that column (wipa_decoder_seek), admissions go through wipa_decoder_admit_rows_prompted with the clips' prompt
-        columns (``prompts(clip)`` or the fifth element of an admitted tuple: [sot_prev] + history, empty for none), the steps through
-        wipa_decoder_run_continuous_prompted, on a [3][B] starts buffer of its own"""
+        columns (``prompts(clip)`` or the fifth element of an admitted tuple: [sot_prev] + history, empty for none), the steps end in
+        the prompted tails (wipa_decode_call.prompted), on a [3][B] starts buffer of its own"""
         self.L = _lib.lib()
         self.model, self.B, self.s, self.eot, self.use_graph = model, int(slots), s, int(eot), use_graph
         self.features = features  # clip -> device tensor [n_audio_ctx, d] in the model's dtype, contiguous
@@ -319,6 +319,10 @@ class DeviceStepper:
         self.pos = 0
         self._keep = []  # what enqueued work reads
         self._begin()
+        # every run of this stepper makes the same call: its buffers are one per state
+        self.call = decode_call(self.n_init, self.eot, self.m_first, self.m_always, rules, self.rec, self.starts, continuous=True,
+                                prompted=self.prompt_room is not None, sample_rows=self.rows, no_speech=self.no_speech,
+                                no_speech_token=self.no_speech_token)
 
     def _begin(self):
         L, pk, st = self.L, self.pk, self.st
@@ -390,19 +394,8 @@ class DeviceStepper:
 
     def run(self, n: int):
         pk, st = self.pk, self.st
-        common = (C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), self.B, self.n_init, self.eot, ptr(self.m_first),
-                  ptr(self.m_always), n, int(self.use_graph), C.byref(self.rules) if self.rules is not None else None)
-        rec = ptr(self.rec) if self.rec is not None else None
-        no_speech = (ptr(self.no_speech) if self.no_speech is not None else None, self.no_speech_token)
-        if self.prompt_room is not None:
-            name, args = "wipa_decoder_run_continuous_prompted", (rec, ptr(self.rows) if self.rows is not None else None, ptr(self.starts), *no_speech)
-        elif self.rows is not None:
-            name, args = "wipa_decoder_run_continuous_rows", (ptr(self.rows), ptr(self.starts), *no_speech)
-        elif self.rules is not None:
-            name, args = "wipa_decoder_run_continuous_rules", (rec, ptr(self.starts), *no_speech)
-        else:
-            name, args = "wipa_decoder_run_continuous", (rec, ptr(self.starts))
-        _lib.check(getattr(self.L, name)(*common, *args, sptr(self.s)), name)
+        _lib.check(self.L.wipa_decoder_run_ex(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), self.B, C.byref(self.call), n,
+                                              int(self.use_graph), sptr(self.s)), "wipa_decoder_run_ex")
         self.pos += n
 
     def last_tokens(self) -> np.ndarray:
@@ -448,7 +441,7 @@ def _layout_key(pk, B: int) -> tuple:
 # ---------------------------------------------------------------- the public entry point
 def refuse_unserved(model, options: DecodingOptions, timestamps: bool = False) -> None:
     """what a continuous decode does not serve, each refused by the option's name.  ``timestamps``: the caller serves
-    ``without_timestamps=False`` (``decode_continuous`` does, on wipa_decoder_run_continuous_rules)"""
+    ``without_timestamps=False`` (``decode_continuous`` does, with wipa_decode_call.rules)"""
     if not options.without_timestamps and not timestamps:
         raise NotImplementedError("decode_continuous: without_timestamps=False is not implemented (the timestamp rules scan a row from a "
                                   "common first column); pass without_timestamps=True")
@@ -604,7 +597,7 @@ def decode_continuous(model, mels_or_features: torch.Tensor, options: DecodingOp
     sequence, and ``no_speech_prob`` is what the step's tail left at the row's <|startoftranscript|> column.
     ``temperatures``: a temperature >= 0 PER CLIP (0: a greedy clip), with ``attempts`` (default 0 for every clip) the clip's index in a
     fallback schedule; needs ``options.seed`` and ``options.temperature == 0``.  Clip i draws what ``decode`` draws for it at that
-    temperature and attempt on its stream; the steps end in the tails with a temperature per row (wipa_decoder_run_continuous_rows).
+    temperature and attempt on its stream; the steps end in the tails with a temperature per row (wipa_decode_call.sample_rows).
     ``prompts``: the previous-text token ids PER CLIP, without ``sot_prev`` ([]: no prompt) -- clip i is decoded as ``decode`` decodes a row
     whose initial tokens are ``[sot_prev] + prompts[i] + sot_sequence`` (the last ``n_text_ctx // 2 - 1`` ids of a longer history, as
     there): its prompt stands in front of its admission column and goes through one batched pass when the clip is admitted (DESIGN.md

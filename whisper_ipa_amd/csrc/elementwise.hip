@@ -726,7 +726,7 @@ __global__ __launch_bounds__(GS_THREADS) void sample_tail_kernel(TailArgs<RAGGED
 }
 
 // ------------------------------------------------------------------ continuous batching: the CONTINUOUS tails
-// The RAGGED tails with a prompt end PER ROW (wipa_decoder_run_continuous): the rows of a state are slots, and a slot's clip was admitted
+// The RAGGED tails with a prompt end PER ROW (wipa_decode_call.continuous): the rows of a state are slots, and a slot's clip was admitted
 // at its own column.  q.start is int32 [2][B]: start[b] is the row's first own column, start[B + b] the number of tokens it may generate.
 // With own = start[b] + n_init (the row's first generated column), the step at column p
 //   p + 1 <  own          the row is idle or in its prompt: the token of column p + 1 is taken as it stands, nothing is written, nothing
@@ -798,7 +798,7 @@ __global__ __launch_bounds__(GS_THREADS) void sample_tail_continuous_kernel(Tail
     tail_finish<TO>(q, p, next, s_red);
 }
 
-// The CONTINUOUS tails with the timestamp rules (wipa_decoder_run_continuous_rules).  The four cases above stay; the pick is
+// The CONTINUOUS tails with the timestamp rules (wipa_decode_call.continuous and .rules).  The four cases above stay; the pick is
 // row_pick<true, SAMPLE> on the row's OWN sequence tk[own .. p]: row_pick's n_init argument is nothing but the first column of the sequence
 // it scans, so `own` in its place states the rule -- len = p + 1 - own, the pick is "first" (text dead, timestamps capped) when p + 1 == own,
 // and no token below own is looked at: those belong to the slot's previous clip, which usually ended in timestamps, or to the prompt.  A
@@ -868,7 +868,7 @@ __global__ __launch_bounds__(GS_THREADS) void rules_tail_continuous_kernel(TailA
     tail_finish<TO>(q, p, next, s_red);
 }
 
-// The CONTINUOUS tails with a TEMPERATURE PER ROW (wipa_decoder_run_continuous_rows): rules_tail_continuous_kernel<TO, true> (RULES) and
+// The CONTINUOUS tails with a TEMPERATURE PER ROW (wipa_decode_call.sample_rows): rules_tail_continuous_kernel<TO, true> (RULES) and
 // sample_tail_continuous_kernel (no rules) with the row's 1/T, attempt and stream read from the row's entry of the record with a row part
 // (row_pick<RULES, true, true>).  The four cases, the no-speech store at p == start[b], `commit` and `tail_finish` are those kernels'.  A
 // greedy row (1/T == 0) leaves row_pick with the greedy answer before the draw: the branch is uniform over the workgroup because one
@@ -908,7 +908,7 @@ __global__ __launch_bounds__(GS_THREADS) void rows_tail_continuous_kernel(TailAr
     tail_finish<TO>(q, p, next, s_red);
 }
 
-// The PROMPTED tails (wipa_decoder_run_continuous_prompted): the CONTINUOUS tails for rows that carry a PROMPT in front of their
+// The PROMPTED tails (wipa_decode_call.prompted): the CONTINUOUS tails for rows that carry a PROMPT in front of their
 // admission column.  q.start is int32 [3][B]: start[b] is the row's window start (its first prompt column: what the RAGGED attention,
 // the position rows and tail_finish read, as they read it in every continuous step), start[B + b] the tokens it may generate and
 // start[2 B + b] its prompt columns L (0: no prompt).  The row's sot sequence stands at [start + L, start + L + n_init), so
@@ -1549,8 +1549,8 @@ static void launch_tail_prompted_as(const TailArgs<true>& q, int B, bool rules, 
 
 // The CONTINUOUS tails (declared in wipa_common.h for the runtime; not exported): the checks of wipa_step_tail; starts_dev is int32 [2][B],
 // the rows' first own columns and then the tokens each may generate.  rules, sample, sample_rows and no_speech_dev may each be NULL;
-// rules and sample_rows name the exported entry point whose error prefix applies (prompted: wipa_decoder_run_continuous_prompted, whose
-// starts_dev is int32 [3][B] with the rows' prompt columns last, and whose tails are the PROMPTED ones).  With rules the tails are the rules_tail_continuous
+// the error prefix is that of wipa_decoder_run_ex, the one entry point that ends its steps here (prompted: starts_dev is int32 [3][B]
+// with the rows' prompt columns last, and the tails are the PROMPTED ones).  With rules the tails are the rules_tail_continuous
 // kernels, and no_speech_dev (float [B]) receives softmax(row)[no_speech_token] at a row's first column; sample_rows (the sampling record
 // with a row part) takes the place of sample and selects the rows_tail_continuous kernels: a temperature per row.
 int wipa_step_tail_continuous(const float* logits, int64_t ldl, int B, int V, const float* mask_first, const float* mask_always, int32_t* tokens,
@@ -1559,7 +1559,7 @@ int wipa_step_tail_continuous(const float* logits, int64_t ldl, int B, int V, co
                               int prompted, float* no_speech_dev, int no_speech_token, float* sum_logprobs, int32_t* not_done, const void* tok_emb,
                               int emb_dtype, const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b,
                               void* y, int y_dtype, int D, float eps, wipa_stream_t stream) {
-    const char* who = prompted ? "wipa_decoder_run_continuous_prompted" : sample_rows ? "wipa_decoder_run_continuous_rows" : rules ? "wipa_decoder_run_continuous_rules" : "wipa_decoder_run_continuous";
+    const char* who = "wipa_decoder_run_ex";
     WIPA_REQUIRE(logits && mask_first && mask_always && tokens && pos_dev && posd_dev && done_counter && sum_logprobs && not_done && tok_emb &&
                      pos_emb && x && ln_w && ln_b && y && starts_dev && B > 0 && n_ctx > 0 && n_init >= 1 && ld_tok >= n_ctx,
                  "%s: bad arguments of the step's tail (starts_dev is required)", who);

@@ -27,7 +27,7 @@ void wipa_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* wipa_last_error(void) { return g_err; }
-extern "C" int wipa_version(void) { return 100; }
+extern "C" int wipa_version(void) { return 101; }
 
 extern "C" int wipa_stream_create_cu_limited(int n_cus, wipa_stream_t* out) {
     int dev = 0, total = 0;
@@ -446,43 +446,30 @@ bool tail_fused() {
     const char* e = getenv("WIPA_DECODE_TAIL");
     return !(e && atoi(e) == 0);
 }
-// What one decode call asks of its steps.  The entry point fills it from its arguments and hands it down by const reference to
-// everything that enqueues a step or keys a graph: nothing about a call is ambient.
+// What one decode call asks of its steps: the caller's wipa_decode_call (include/wipa.h documents every field: which tail, which
+// attention instantiation, what `starts` holds) plus `lean`.  step_ctx() builds it, and it goes down by const reference to everything
+// that enqueues a step or keys a graph: nothing about a call is ambient, and nothing below reads the public struct.
 struct StepCtx {
-    // the timestamp rules (wipa_decoder_run_rules / _prefill_rules; NULL: the plain greedy update).  With rules the step ends in
-    // wipa_timestamp_step_embed on the written logits: the per-wave partials cannot carry rules that depend on the row's own history,
-    // so logits_fused() is off and no step of the call is lean.
     const wipa_decode_rules* rules;
-    // the sampling record (wipa_decoder_run_sample / _prefill_sample; NULL: temperature 0).  A sampling step ends in
-    // wipa_sample_step_embed on the written logits, like a step with rules: the draw needs every alive column of the row.
     const void* sample;
-    // ragged prompts (wipa_decoder_run_ragged): the device array int32 [B] of the rows' first own column (NULL: every row starts at
-    // column 0).  With it the step's self-attention, its tail and its head are the RAGGED instantiations, and the tail is the row
-    // scan on written logits, like a step with rules (the per-wave partials path stays what it is).
     const int32_t* starts;
-    int n_init, eot;  // prompt columns (the prompt width P of a ragged call) and the end-of-text id
+    int n_init, eot;
     const float *mask_first, *mask_always;
-    // a step whose logits nobody reads (every step of a wipa_decoder_run call but the last) does not write them at all
+    // a step whose logits nobody reads (every step of a run call but the last) does not write them at all
     bool lean;
-    // continuous batching (wipa_decoder_run_continuous): `starts` is int32 [2][B] -- first own columns, then the tokens each row may
-    // generate -- and the step ends in the CONTINUOUS tail (a prompt end per row); everything before the tail is the ragged step
     bool continuous;
-    // wipa_decoder_run_continuous_rules (continuous with rules): float [B], a row's no-speech probability is written at the step of its first
-    // own column (NULL: not wanted), and the vocabulary column it is read at
     float* no_speech;
     int no_speech_token;
-    // wipa_decoder_run_continuous_rows (continuous with a temperature per row): the sampling record with a row part (wipa_sample_rows_bytes;
-    // NULL otherwise).  It takes the place of `sample`, which is NULL then, and the step ends in the rows_tail_continuous kernels.
     const void* sample_rows;
-    // wipa_decoder_run_continuous_prompted: `starts` is int32 [3][B] -- window starts, token limits, prompt columns -- and the step ends
-    // in the PROMPTED tails (the sot sequence stands behind the row's prompt); everything before the tail is the continuous step
     bool prompted;
-    // beams (wipa_decoder_run_beam / _prefill_beam): the caller's beam buffer (wipa_beam_bytes; NULL: no beams) and the size of a clip's
-    // finished store.  The rows are clips x cfg.dec_n_group beams; the self-attention reads the cache through the buffer's ancestor
-    // table and the step ends in the beam tail (csrc/beam.hip) on the written logits.
-    void* beam = nullptr;
-    int beam_max_candidates = 0;
+    void* beam;
+    size_t beam_bytes;
+    int beam_max_candidates;
 };
+StepCtx step_ctx(const wipa_decode_call& k) {
+    return StepCtx{k.rules, k.sample, k.starts_dev, k.n_init, k.eot, k.mask_first, k.mask_always, false, k.continuous != 0, k.no_speech_dev,
+                   k.no_speech_token, k.sample_rows, k.prompted != 0, k.beam, k.beam_bytes, k.beam ? k.beam_max_candidates : 0};
+}
 // The logits projection with the greedy partials in its epilogue + a tail that merges them (round 4; WIPA_LOGITS_FUSED=0 restores
 // the plain GEMM + the row-scanning tail): bf16 models without fp8 decoder tables, <= 64 rows, tail-fused steps.  Measured on
 // whisper-small, 64 clips: the logits' 64-byte stores were 8 of the GEMM's 32 us, the tail's read-back of the 13 MB another ~10.
@@ -681,7 +668,7 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
         // counter at the row's own position)
         const void* const* lw0 = w + WIPA_DEC_GLOBAL;
         if (ctx.beam)  // top G + 1 per row, then per clip: selection, gather, finished store, the next input rows, the position advance
-            return wipa_beam_tail("wipa_decoder_run_beam", logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos,
+            return wipa_beam_tail("wipa_decoder_run_ex", logits, L.ld_logits, B, cfg->n_vocab, ctx.mask_first, ctx.mask_always, tokens, L.ld_tok, pos,
                                   posd, ctx.n_init, ctx.eot, ctx.rules, ctx.beam, G, ctx.beam_max_candidates, (float*)(st + L.sum_logprobs),
                                   (int32_t*)(st + L.not_done), w[0], emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1], nctx, x_first,
                                   (const float*)lw0[0], (const float*)lw0[1], ln, dt, d, 1e-5f, stream);
@@ -1023,6 +1010,68 @@ int rules_servable(const char* who, const wipa_model_cfg* cfg, int B, int eot, c
                  "no_timestamps=%d n_vocab=%d)", who, eot, r->timestamp_begin, r->no_timestamps, cfg->n_vocab);
     return WIPA_OK;
 }
+// what a continuous decode serves, in the words of its entry points: bf16 / f32 decoder tables, one row per clip
+int continuous_servable(const char* who, const wipa_model_cfg* cfg, int B, const int32_t* starts_dev) {
+    WIPA_REQUIRE(starts_dev, "%s: starts_dev (int32 [2][B]: first own columns, then token limits) is required", who);
+    WIPA_REQUIRE(cfg->dec_w_dtype == 0, "%s: fp8 decoder tables are not served (cfg.dec_w_dtype)", who);
+    WIPA_REQUIRE(group_of(cfg) == 1, "%s: candidate groups are not served (cfg.dec_n_group=%d)", who, cfg->dec_n_group);
+    WIPA_REQUIRE(B > 0, "%s: bad batch", who);
+    return WIPA_OK;
+}
+// what a beam call serves, in the words of its entry point; refused before anything is enqueued
+int beam_servable(const char* who, const wipa_model_cfg* cfg, int B, const StepCtx& c) {
+    if (!c.beam) return WIPA_OK;
+    const int G = group_of(cfg);
+    WIPA_REQUIRE(!c.sample && !c.sample_rows, "%s: call.beam and call.sample / call.sample_rows cannot be given together (beams run at temperature 0)", who);
+    WIPA_REQUIRE(!c.starts && !c.continuous, "%s: call.beam is not served with call.starts_dev / call.continuous (the beams of a clip share one prompt)", who);
+    WIPA_REQUIRE(cfg->dec_w_dtype == 0, "%s: call.beam is not served on fp8 decoder tables (cfg.dec_w_dtype)", who);
+    WIPA_REQUIRE(tail_fused() && !use_fused_step(cfg, B), "%s: call.beam needs the unfused step with the fused tail; WIPA_DECODE_TAIL=0 / WIPA_DECODE_FUSED=1 cannot serve it", who);
+    WIPA_REQUIRE(G >= 1 && G <= 16, "%s: cfg.dec_n_group=%d (n_group) outside 1..16", who, G);
+    WIPA_REQUIRE(B % G == 0, "%s: B=%d rows are no multiple of cfg.dec_n_group=%d (n_group)", who, B, G);
+    WIPA_REQUIRE(c.beam_max_candidates >= 1 && c.beam_max_candidates <= 64, "%s: call.beam_max_candidates=%d outside 1..64", who, c.beam_max_candidates);
+    WIPA_REQUIRE(cfg->n_vocab <= 65536, "%s: need n_vocab <= 65536 (n_vocab=%d)", who, cfg->n_vocab);
+    const size_t need = wipa_beam_bytes(B, G, c.beam_max_candidates, dec_layout(cfg, B).ld_tok);
+    WIPA_REQUIRE(c.beam_bytes >= need, "%s: call.beam_bytes: the beam buffer holds %zu bytes, this shape needs %zu (wipa_beam_bytes)", who, c.beam_bytes, need);
+    return WIPA_OK;
+}
+// what the steps of a call with rules, a sampling record, starts or candidate groups must be able to serve
+int step_servable(const char* who, const wipa_model_cfg* cfg, int B, const StepCtx& c) {
+    RT_CALL(rules_servable(who, cfg, B, c.eot, c.rules));
+    RT_CALL(sample_servable(who, cfg, B, c.sample ? c.sample : c.sample_rows));
+    RT_CALL(starts_servable(who, cfg, B, c.n_init, c.starts));
+    return group_servable(who, cfg, B);
+}
+// Every refusal of wipa_decoder_run_ex (prefill = false) and wipa_decoder_prefill_ex (n_steps = 1), in order: null pointers and ranges,
+// fields that exclude or need each other, then what the configuration's step cannot serve.  Nothing is enqueued before it returns.
+int decode_call_checks(const char* who, const wipa_model_cfg* cfg, const void* const* w, const void* state, int B, const StepCtx& c, int n_steps,
+                       bool prefill) {
+    WIPA_REQUIRE(w && state && c.mask_first && c.mask_always && B > 0 && n_steps >= 0,
+                 "%s: bad arguments (weights, state, call.mask_first and call.mask_always are required; B > 0, n_steps >= 0)", who);
+    WIPA_REQUIRE(!c.sample || !c.sample_rows, "%s: call.sample_rows takes the place of call.sample: pass one of them", who);
+    WIPA_REQUIRE(!prefill || (!c.starts && !c.continuous && !c.prompted && !c.sample_rows && !c.no_speech),
+                 "%s: call.starts_dev, call.continuous, call.prompted, call.sample_rows and call.no_speech_dev are not served by the prompt pass "
+                 "(rows with their own prompts: wipa_decoder_prefill_ragged; an admitted clip's prompt: wipa_decoder_admit_rows_prompted)", who);
+    WIPA_REQUIRE(c.continuous || (!c.sample_rows && !c.no_speech && !c.prompted),
+                 "%s: call.sample_rows, call.no_speech_dev and call.prompted need call.continuous", who);
+    WIPA_REQUIRE(!c.continuous || c.starts, "%s: call.continuous needs call.starts_dev (int32 [2][B]: first own columns, then token limits; "
+                 "[3][B] with call.prompted: window starts, token limits, prompt columns)", who);
+    WIPA_REQUIRE(!c.no_speech || c.rules, "%s: call.no_speech_dev needs call.rules", who);
+    WIPA_REQUIRE(((uintptr_t)c.sample_rows % 16) == 0, "%s: call.sample_rows (wipa_sample_rows_bytes) must be 16-byte aligned", who);
+    if (c.continuous) {
+        RT_CALL(continuous_servable(who, cfg, B, c.starts));
+        WIPA_REQUIRE(c.n_init >= 1 && c.n_init <= 4, "%s: call.n_init: 1..4 initial tokens per clip (got %d)", who, c.n_init);
+    }
+    WIPA_REQUIRE(!c.no_speech || (c.no_speech_token >= 0 && c.no_speech_token < cfg->n_vocab),
+                 "%s: call.no_speech_token=%d outside the vocabulary of %d", who, c.no_speech_token, cfg->n_vocab);
+    RT_CALL(beam_servable(who, cfg, B, c));
+    RT_CALL(step_servable(who, cfg, B, c));
+    WIPA_REQUIRE(!prefill || (c.n_init >= 1 && c.n_init <= MAX_PROMPT), "%s: call.n_init: 1..%d prompt tokens (got %d)", who, MAX_PROMPT, c.n_init);
+    // the position lives on the device: a call may carry the prompt walk (P - 1 steps) besides the new tokens, so what can be
+    // refused here is a step count that no position admits
+    WIPA_REQUIRE(!c.starts || n_steps <= cfg->n_text_ctx - 1, "%s: n_steps=%d with call.starts_dev and P=%d runs past n_text_ctx=%d", who, n_steps,
+                 c.n_init, cfg->n_text_ctx);
+    return WIPA_OK;
+}
 std::mutex g_graph_mu;
 std::map<GraphKey, hipGraphExec_t> g_graphs;
 
@@ -1085,25 +1134,16 @@ int replay_or_enqueue(bool use_graph, hipStream_t s, const GraphKey& key, Enqueu
     return WIPA_OK;
 }
 
-// The names an entry point's refusals carry: its own, and those of the forwarding entry points whose argument a check is about.
-struct EntryNames {
-    const char *own, *rules, *sample, *starts;
-};
-EntryNames entry_names(const char* own) { return EntryNames{own, own, own, own}; }  // an entry point that nothing forwards to
-// What wipa_decoder_run_ragged, wipa_decoder_prefill_sample and wipa_decoder_prefill_ragged do between their argument checks and
-// their first launch, in this order: what the steps cannot serve is refused, then the entry point's `own_checks`, then a state blob
-// too small for the layout (*L); every kernel attribute is set outside any capture; a call that will enqueue steps (n_steps > 0)
-// starts the greedy tail's arrival counter at zero (4 bytes, outside the step graph).
-template <typename OwnChecks>
-int decode_prologue(const EntryNames& who, const wipa_model_cfg* cfg, int B, const StepCtx& c, char* st, size_t state_bytes, int n_steps,
-                    hipStream_t s, wipa_dec_layout* L, OwnChecks&& own_checks) {
-    RT_CALL(rules_servable(who.rules, cfg, B, c.eot, c.rules));
-    RT_CALL(sample_servable(who.sample, cfg, B, c.sample));
-    RT_CALL(starts_servable(who.starts, cfg, B, c.n_init, c.starts));
-    RT_CALL(group_servable(who.own, cfg, B));
-    RT_CALL(own_checks());
+// What wipa_decoder_run_ex, wipa_decoder_prefill_ex and wipa_decoder_prefill_ragged do between their argument checks and their first
+// launch, in this order: the entry point's `checks` refuse what it cannot serve, then a state blob too small for the layout (*L); every
+// kernel attribute is set outside any capture; a call that will enqueue steps (n_steps > 0) starts the greedy tail's arrival counter
+// at zero (4 bytes, outside the step graph).
+template <typename Checks>
+int decode_prologue(const char* who, const wipa_model_cfg* cfg, int B, char* st, size_t state_bytes, int n_steps, hipStream_t s,
+                    wipa_dec_layout* L, Checks&& checks) {
+    RT_CALL(checks());
     *L = dec_layout(cfg, B);
-    RT_CALL(state_fits(who.own, *L, state_bytes));
+    RT_CALL(state_fits(who, *L, state_bytes));
     RT_CALL(init_before_capture(cfg));
     if (n_steps > 0) WIPA_CHECK_HIP(hipMemsetAsync(done_counter_of(st, *L), 0, sizeof(int32_t), s));
     return WIPA_OK;
@@ -1243,32 +1283,11 @@ extern "C" int wipa_decoder_begin_ragged(const wipa_model_cfg* cfg, void* state,
     return WIPA_OK;
 }
 
-extern "C" int wipa_decoder_run(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
-                                int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
-                                wipa_stream_t stream) {
-    return wipa_decoder_run_rules(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, n_steps, use_graph, nullptr, stream);
-}
-
-extern "C" int wipa_decoder_run_rules(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
-                                      int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
-                                      const wipa_decode_rules* rules, wipa_stream_t stream) {
-    return wipa_decoder_run_sample(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, n_steps, use_graph, rules, nullptr, stream);
-}
-
-extern "C" int wipa_decoder_run_sample(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
-                                       int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
-                                       const wipa_decode_rules* rules, const void* sample, wipa_stream_t stream) {
-    return wipa_decoder_run_ragged(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, n_steps, use_graph, rules, sample, nullptr,
-                                   stream);
-}
-
-// wipa_decoder_run_ragged and, with full.continuous, the continuous entry points: the same call but for the tail the steps end in.
 // `full` is the call's context as its last step sees it (lean = false); `who` names the entry point in the refusals.
-static int decoder_run(const EntryNames& who, const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
+static int decoder_run(const char* who, const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
                        const StepCtx& full, int n_steps, int use_graph, wipa_stream_t stream) {
     RT_CALL(cfg_check(cfg));
     SplitScope split_scope(cfg);
-    WIPA_REQUIRE(w && state && full.mask_first && full.mask_always && B > 0 && n_steps >= 0, "wipa_decoder_run: bad arguments");
     // every step of the call but the LAST is "lean" when the logits projection carries the greedy partials: its logits are not
     // written (state.logits holds those of the last step of a call, which is what callers read)
     StepCtx lean = full;
@@ -1276,13 +1295,7 @@ static int decoder_run(const EntryNames& who, const wipa_model_cfg* cfg, const v
     char* st = (char*)state;
     hipStream_t s = (hipStream_t)stream;
     wipa_dec_layout L;
-    RT_CALL(decode_prologue(who, cfg, B, full, st, state_bytes, n_steps, s, &L, [&]() -> int {
-        // the position lives on the device: a call may carry the prompt walk (P - 1 steps) besides the new tokens, so what can be
-        // refused here is a step count that no position admits
-        WIPA_REQUIRE(!full.starts || n_steps <= cfg->n_text_ctx - 1, "wipa_decoder_run_ragged: n_steps=%d with P=%d runs past n_text_ctx=%d", n_steps,
-                     full.n_init, cfg->n_text_ctx);
-        return WIPA_OK;
-    }));
+    RT_CALL(decode_prologue(who, cfg, B, st, state_bytes, n_steps, s, &L, [&]() -> int { return decode_call_checks(who, cfg, w, state, B, full, n_steps, false); }));
     if (n_steps == 0) return WIPA_OK;
     W8Scope w8_scope(cfg, w);
     // the first step's input rows (embedding + first LayerNorm of the token at the current position): every later step gets
@@ -1294,7 +1307,7 @@ static int decoder_run(const EntryNames& who, const wipa_model_cfg* cfg, const v
         for (int i = 0; i < n_steps; ++i) RT_CALL(enqueue_decode_step(cfg, w, st, L, B, (lean_ok && i + 1 < n_steps) ? lean : full, stream));
         return WIPA_OK;
     }
-    WIPA_REQUIRE(s != nullptr, "wipa_decoder_run: graph capture needs a non-default stream");
+    WIPA_REQUIRE(s != nullptr, "%s: graph capture needs a non-default stream", who);
     const int variant = step_variant(cfg, B, full);
     auto step_graph = [&](const StepCtx& c, hipGraphExec_t* out) -> int {  // kind 0: the full step, 2: the lean one
         return cached_graph(graph_key(cfg, w, state, B, c, variant, c.lean ? 2 : 0, nullptr), s,
@@ -1307,25 +1320,49 @@ static int decoder_run(const EntryNames& who, const wipa_model_cfg* cfg, const v
     return WIPA_OK;
 }
 
-extern "C" int wipa_decoder_run_ragged(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
-                                       int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
-                                       const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, wipa_stream_t stream) {
-    static const EntryNames who = {"wipa_decoder_run", "wipa_decoder_run_rules", "wipa_decoder_run_sample", "wipa_decoder_run_ragged"};
-    const StepCtx full{rules, sample, starts_dev, n_init, eot, mask_first, mask_always, false, false, nullptr, 0, nullptr};
-    return decoder_run(who, cfg, w, state, state_bytes, B, full, n_steps, use_graph, stream);
+extern "C" int wipa_decoder_run_ex(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
+                                   const wipa_decode_call* call, int n_steps, int use_graph, wipa_stream_t stream) {
+    WIPA_REQUIRE(call, "wipa_decoder_run_ex: call is required");
+    return decoder_run("wipa_decoder_run_ex", cfg, w, state, state_bytes, B, step_ctx(*call), n_steps, use_graph, stream);
+}
+
+extern "C" int wipa_decoder_run(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
+                                int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
+                                wipa_stream_t stream) {
+    const wipa_decode_call call = {n_init, eot, mask_first, mask_always};
+    return wipa_decoder_run_ex(cfg, w, state, state_bytes, B, &call, n_steps, use_graph, stream);
+}
+
+extern "C" int wipa_decoder_prefill_ex(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
+                                       const wipa_decode_call* call, int use_graph, wipa_stream_t stream) {
+    const char* who = "wipa_decoder_prefill_ex";
+    WIPA_REQUIRE(call, "%s: call is required", who);
+    RT_CALL(cfg_check(cfg));
+    SplitScope split_scope(cfg);
+    const StepCtx ctx = step_ctx(*call);
+    char* st = (char*)state;
+    hipStream_t s = (hipStream_t)stream;
+    wipa_dec_layout L;
+    RT_CALL(decode_prologue(who, cfg, B, st, state_bytes, 1, s, &L, [&]() -> int { return decode_call_checks(who, cfg, w, state, B, ctx, 1, true); }));
+    W8Scope w8_scope(cfg, w);
+    return replay_or_enqueue(use_graph, s, graph_key(cfg, w, state, B, ctx, step_variant(cfg, B, ctx), 1, nullptr), [&]() -> int {
+        if (ctx.n_init == 1) {  // a bare [sot] prompt: one ordinary step at position 0 (with its head when the step is tail-fused)
+            if (step_needs_head(cfg, B)) RT_CALL(enqueue_step_head(cfg, w, st, L, B, ctx, stream));
+            return enqueue_decode_step(cfg, w, st, L, B, ctx, stream);
+        }
+        return enqueue_prefill(cfg, w, st, L, B, ctx, stream);
+    });
+}
+
+extern "C" int wipa_decoder_prefill(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
+                                    int n_init, int eot, const float* mask_first, const float* mask_always, int use_graph,
+                                    wipa_stream_t stream) {
+    const wipa_decode_call call = {n_init, eot, mask_first, mask_always};
+    return wipa_decoder_prefill_ex(cfg, w, state, state_bytes, B, &call, use_graph, stream);
 }
 
 // ------------------------------------------------------------------ continuous batching: slots, admission, column shift
 namespace {
-
-// what a continuous decode serves, in the words of its entry points: bf16 / f32 decoder tables, one row per clip
-int continuous_servable(const char* who, const wipa_model_cfg* cfg, int B, const int32_t* starts_dev) {
-    WIPA_REQUIRE(starts_dev, "%s: starts_dev (int32 [2][B]: first own columns, then token limits) is required", who);
-    WIPA_REQUIRE(cfg->dec_w_dtype == 0, "%s: fp8 decoder tables are not served (cfg.dec_w_dtype)", who);
-    WIPA_REQUIRE(group_of(cfg) == 1, "%s: candidate groups are not served (cfg.dec_n_group=%d)", who, cfg->dec_n_group);
-    WIPA_REQUIRE(B > 0, "%s: bad batch", who);
-    return WIPA_OK;
-}
 
 // one admitted clip: its initial tokens into columns [*pos, *pos + n_init) of the slot's row, the slot's start, limit and log-probability
 // sum, and (with a sampling record) the Philox stream of its draws.  One thread; a column range that does not fit the table is not written.
@@ -1491,56 +1528,6 @@ __global__ __launch_bounds__(256) void scatter_prompt_kv_kernel(const char* __re
 
 }  // namespace
 
-// What the three continuous entry points share once each has refused what is its own to refuse: what a continuous decode serves, the
-// n_init range and the no-speech column, then the run.  c: the call's context (continuous; no_speech NULL where the entry point has none).
-static int decoder_run_continuous(const char* who, const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
-                                  const StepCtx& c, int n_steps, int use_graph, wipa_stream_t stream) {
-    RT_CALL(continuous_servable(who, cfg, B, c.starts));
-    RT_CALL(sample_servable(who, cfg, B, c.sample_rows));
-    WIPA_REQUIRE(c.n_init >= 1 && c.n_init <= 4, "%s: 1..4 initial tokens per clip (got %d)", who, c.n_init);
-    WIPA_REQUIRE(!c.no_speech || (c.rules && c.no_speech_token >= 0 && c.no_speech_token < cfg->n_vocab),
-                 "%s: no_speech_token=%d outside the vocabulary of %d%s", who, c.no_speech_token, cfg->n_vocab,
-                 c.sample_rows ? " (no_speech_dev needs rules)" : "");
-    return decoder_run(entry_names(who), cfg, w, state, state_bytes, B, c, n_steps, use_graph, stream);
-}
-
-extern "C" int wipa_decoder_run_continuous(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
-                                           int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
-                                           const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, wipa_stream_t stream) {
-    RT_CALL(cfg_check(cfg));
-    WIPA_REQUIRE(!rules, "wipa_decoder_run_continuous: the timestamp rules are not served (they scan the row from a common column n_init; "
-                 "rules must be NULL)");
-    const StepCtx c{nullptr, sample, starts_dev, n_init, eot, mask_first, mask_always, false, true, nullptr, 0, nullptr};
-    return decoder_run_continuous("wipa_decoder_run_continuous", cfg, w, state, state_bytes, B, c, n_steps, use_graph, stream);
-}
-
-extern "C" int wipa_decoder_run_continuous_rules(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
-                                                 int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
-                                                 const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev,
-                                                 float* no_speech_dev, int no_speech_token, wipa_stream_t stream) {
-    RT_CALL(cfg_check(cfg));
-    const char* who = "wipa_decoder_run_continuous_rules";
-    WIPA_REQUIRE(rules, "%s: rules is required (the timestamp rules on every row's own sequence; without rules the call is "
-                 "wipa_decoder_run_continuous)", who);
-    const StepCtx c{rules, sample, starts_dev, n_init, eot, mask_first, mask_always, false, true, no_speech_dev, no_speech_token, nullptr};
-    return decoder_run_continuous(who, cfg, w, state, state_bytes, B, c, n_steps, use_graph, stream);
-}
-
-// wipa_decoder_run_continuous_rules (rules) / wipa_decoder_run_continuous (rules == NULL) with a temperature per row: the steps end in the
-// rows_tail_continuous kernels, which read every row's 1 / temperature, attempt and stream from sample_rows when they run
-extern "C" int wipa_decoder_run_continuous_rows(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
-                                                int eot, const float* mask_first, const float* mask_always, int n_steps, int use_graph,
-                                                const wipa_decode_rules* rules, const void* sample_rows, const int32_t* starts_dev,
-                                                float* no_speech_dev, int no_speech_token, wipa_stream_t stream) {
-    RT_CALL(cfg_check(cfg));
-    const char* who = "wipa_decoder_run_continuous_rows";
-    WIPA_REQUIRE(sample_rows && ((uintptr_t)sample_rows % 16) == 0,
-                 "%s: sample_rows is required (the sampling record with a row part, wipa_sample_rows_bytes, 16-byte aligned; without it the call "
-                 "is wipa_decoder_run_continuous / _rules)", who);
-    const StepCtx c{rules, nullptr, starts_dev, n_init, eot, mask_first, mask_always, false, true, no_speech_dev, no_speech_token, sample_rows};
-    return decoder_run_continuous(who, cfg, w, state, state_bytes, B, c, n_steps, use_graph, stream);
-}
-
 extern "C" int wipa_decoder_admit_rows(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_rows,
                                        const int32_t* slots_host,
                                        const void* const* features_host, const int32_t* initial_tokens_host, int n_init,
@@ -1593,85 +1580,6 @@ extern "C" int wipa_decoder_shift_columns(const wipa_model_cfg* cfg, void* state
                        starts_dev, B, nctx, shift);
     WIPA_LAUNCH_CHECK();
     return WIPA_OK;
-}
-
-extern "C" int wipa_decoder_prefill(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
-                                    int n_init, int eot, const float* mask_first, const float* mask_always, int use_graph,
-                                    wipa_stream_t stream) {
-    return wipa_decoder_prefill_rules(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, use_graph, nullptr, stream);
-}
-
-extern "C" int wipa_decoder_prefill_rules(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
-                                          int n_init, int eot, const float* mask_first, const float* mask_always, int use_graph,
-                                          const wipa_decode_rules* rules, wipa_stream_t stream) {
-    return wipa_decoder_prefill_sample(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, use_graph, rules, nullptr, stream);
-}
-
-extern "C" int wipa_decoder_prefill_sample(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
-                                           int n_init, int eot, const float* mask_first, const float* mask_always, int use_graph,
-                                           const wipa_decode_rules* rules, const void* sample, wipa_stream_t stream) {
-    return wipa_decoder_prefill_beam(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, use_graph, rules, sample, nullptr, 0, 0,
-                                     stream);
-}
-
-namespace {
-// what a beam call serves, in the words of its entry point; refused before anything is enqueued
-int beam_servable(const char* who, const wipa_model_cfg* cfg, int B, const void* sample, const void* beam, size_t beam_bytes, int max_candidates) {
-    if (!beam) return WIPA_OK;
-    const int G = group_of(cfg);
-    WIPA_REQUIRE(!sample, "%s: beam and sample cannot be given together (beams run at temperature 0)", who);
-    WIPA_REQUIRE(cfg->dec_w_dtype == 0, "%s: beam is not served on fp8 decoder tables (cfg.dec_w_dtype)", who);
-    WIPA_REQUIRE(tail_fused() && !use_fused_step(cfg, B), "%s: beam needs the unfused step with the fused tail; WIPA_DECODE_TAIL=0 / WIPA_DECODE_FUSED=1 cannot serve it", who);
-    WIPA_REQUIRE(G >= 1 && G <= 16, "%s: cfg.dec_n_group=%d (n_group) outside 1..16", who, G);
-    WIPA_REQUIRE(B % G == 0, "%s: B=%d rows are no multiple of cfg.dec_n_group=%d (n_group)", who, B, G);
-    WIPA_REQUIRE(max_candidates >= 1 && max_candidates <= 64, "%s: max_candidates=%d outside 1..64", who, max_candidates);
-    WIPA_REQUIRE(cfg->n_vocab <= 65536, "%s: need n_vocab <= 65536 (n_vocab=%d)", who, cfg->n_vocab);
-    const size_t need = wipa_beam_bytes(B, G, max_candidates, dec_layout(cfg, B).ld_tok);
-    WIPA_REQUIRE(beam_bytes >= need, "%s: the beam buffer holds %zu bytes, this shape needs %zu (wipa_beam_bytes)", who, beam_bytes, need);
-    return WIPA_OK;
-}
-}  // namespace
-
-extern "C" int wipa_decoder_run_beam(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init, int eot,
-                                     const float* mask_first, const float* mask_always, int n_steps, int use_graph, const wipa_decode_rules* rules,
-                                     void* beam, size_t beam_bytes, int max_candidates, wipa_stream_t stream) {
-    if (!beam) return wipa_decoder_run_sample(cfg, w, state, state_bytes, B, n_init, eot, mask_first, mask_always, n_steps, use_graph, rules, nullptr, stream);
-    RT_CALL(cfg_check(cfg));
-    RT_CALL(beam_servable("wipa_decoder_run_beam", cfg, B, nullptr, beam, beam_bytes, max_candidates));
-    static const EntryNames who = entry_names("wipa_decoder_run_beam");
-    StepCtx full{rules, nullptr, nullptr, n_init, eot, mask_first, mask_always, false, false, nullptr, 0, nullptr};
-    full.beam = beam;
-    full.beam_max_candidates = max_candidates;
-    return decoder_run(who, cfg, w, state, state_bytes, B, full, n_steps, use_graph, stream);
-}
-
-extern "C" int wipa_decoder_prefill_beam(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_init,
-                                         int eot, const float* mask_first, const float* mask_always, int use_graph,
-                                         const wipa_decode_rules* rules, const void* sample, void* beam, size_t beam_bytes, int max_candidates,
-                                         wipa_stream_t stream) {
-    RT_CALL(cfg_check(cfg));
-    SplitScope split_scope(cfg);
-    WIPA_REQUIRE(w && state && mask_first && mask_always && B > 0, "wipa_decoder_prefill: bad arguments");
-    RT_CALL(beam_servable("wipa_decoder_prefill_beam", cfg, B, sample, beam, beam_bytes, max_candidates));
-    StepCtx ctx{rules, sample, nullptr, n_init, eot, mask_first, mask_always, false};
-    ctx.beam = beam;
-    ctx.beam_max_candidates = beam ? max_candidates : 0;
-    static const EntryNames who = {"wipa_decoder_prefill", "wipa_decoder_prefill_rules", "wipa_decoder_prefill_sample", "wipa_decoder_prefill"};
-    char* st = (char*)state;
-    hipStream_t s = (hipStream_t)stream;
-    wipa_dec_layout L;
-    RT_CALL(decode_prologue(who, cfg, B, ctx, st, state_bytes, 1, s, &L, [&]() -> int {
-        WIPA_REQUIRE(n_init >= 1 && n_init <= MAX_PROMPT, "wipa_decoder_prefill: 1..%d prompt tokens (got %d)", MAX_PROMPT, n_init);
-        return WIPA_OK;
-    }));
-    W8Scope w8_scope(cfg, w);
-    return replay_or_enqueue(use_graph, s, graph_key(cfg, w, state, B, ctx, step_variant(cfg, B, ctx), 1, nullptr), [&]() -> int {
-        if (n_init == 1) {  // a bare [sot] prompt: one ordinary step at position 0 (with its head when the step is tail-fused)
-            if (step_needs_head(cfg, B)) RT_CALL(enqueue_step_head(cfg, w, st, L, B, ctx, stream));
-            return enqueue_decode_step(cfg, w, st, L, B, ctx, stream);
-        }
-        return enqueue_prefill(cfg, w, st, L, B, ctx, stream);
-    });
 }
 
 // ------------------------------------------------------------------ ragged prompt pass
@@ -1868,12 +1776,13 @@ extern "C" int wipa_decoder_prefill_ragged(const wipa_model_cfg* cfg, const void
     WIPA_REQUIRE(cfg->dec_w_dtype == 0, "wipa_decoder_prefill_ragged: the prompt pass runs on a bf16 / f32 weight table (cfg.dec_w_dtype: fp8 tables "
                                         "serve the decode step)");
     const StepCtx ctx{rules, sample, starts_dev, P, eot, mask_first, mask_always, false};
-    const EntryNames who = entry_names("wipa_decoder_prefill_ragged");
+    const char* who = "wipa_decoder_prefill_ragged";
     char* st = (char*)state;
     hipStream_t s = (hipStream_t)stream;
     wipa_dec_layout L;
     const PromptWs W = prompt_ws(cfg, B, P);  // offsets only: nothing is touched before the checks
-    RT_CALL(decode_prologue(who, cfg, B, ctx, st, state_bytes, 1, s, &L, [&]() -> int {
+    RT_CALL(decode_prologue(who, cfg, B, st, state_bytes, 1, s, &L, [&]() -> int {
+        RT_CALL(step_servable(who, cfg, B, ctx));
         WIPA_REQUIRE(P + 1 <= cfg->n_text_ctx, "wipa_decoder_prefill_ragged: P=%d leaves no column to generate in n_text_ctx=%d", P, cfg->n_text_ctx);
         WIPA_REQUIRE(sot_col >= -1 && sot_col < P, "wipa_decoder_prefill_ragged: sot_col=%d outside -1..P-1 (P=%d)", sot_col, P);
         WIPA_REQUIRE(workspace_bytes >= W.total, "wipa_decoder_prefill_ragged: workspace too small (%zu < %zu: wipa_decoder_prompt_workspace_bytes)",
@@ -2022,23 +1931,6 @@ extern "C" int wipa_decoder_admit_rows_prompted(const wipa_model_cfg* cfg, const
     k.n_group = 1;
     k.qkv_hook = &hook; k.kv_only = true;
     return batched_layers(cfg, w, k, stream);
-}
-
-// ONE entry point for the PROMPTED steps: rules, sample, sample_rows and no_speech_dev may each be NULL (sample and sample_rows exclude
-// each other); starts_dev is int32 [3][B].  The call of wipa_decoder_run_continuous / _rules / _rows but for the tails the steps end in.
-extern "C" int wipa_decoder_run_continuous_prompted(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
-                                                    int n_init, int eot, const float* mask_first, const float* mask_always, int n_steps,
-                                                    int use_graph, const wipa_decode_rules* rules, const void* sample, const void* sample_rows,
-                                                    const int32_t* starts_dev, float* no_speech_dev, int no_speech_token, wipa_stream_t stream) {
-    RT_CALL(cfg_check(cfg));
-    const char* who = "wipa_decoder_run_continuous_prompted";
-    WIPA_REQUIRE(starts_dev, "%s: starts_dev (int32 [3][B]: window starts, token limits, prompt columns) is required", who);
-    WIPA_REQUIRE(!sample_rows || (!sample && ((uintptr_t)sample_rows % 16) == 0),
-                 "%s: sample_rows (16-byte aligned) takes the place of sample: pass one of them", who);
-    WIPA_REQUIRE(!no_speech_dev || rules, "%s: no_speech_dev needs rules", who);
-    StepCtx c{rules, sample, starts_dev, n_init, eot, mask_first, mask_always, false, true, no_speech_dev, no_speech_token, sample_rows};
-    c.prompted = true;
-    return decoder_run_continuous(who, cfg, w, state, state_bytes, B, c, n_steps, use_graph, stream);
 }
 
 extern "C" int wipa_decoder_release(void* state) {

@@ -29,7 +29,7 @@ int wipa_step_tail(const float* logits, int64_t ldl, int B, int V, const float* 
                    const void* sample, const int32_t* starts_dev, float* sum_logprobs, int32_t* not_done, const void* tok_emb, int emb_dtype,
                    const float* emb_scale, const float* pos_emb, int n_ctx, float* x, const float* ln_w, const float* ln_b, void* y, int y_dtype,
                    int D, float eps, wipa_stream_t stream);
-// the same launch for wipa_decoder_run_continuous / _rules / _rows: the CONTINUOUS tails (a prompt end per row; starts_dev int32 [2][B]).
+// the same launch for a wipa_decode_call with continuous: the CONTINUOUS tails (a prompt end per row; starts_dev int32 [2][B]).
 // rules, sample, sample_rows and no_speech_dev may each be NULL: with rules the pick runs on the row's own sequence and no_speech_dev
 // (float [B]) receives softmax(logits row)[no_speech_token] at the step of a row's first own column; sample_rows (the sampling record with
 // a row part) takes the place of sample and gives every row its own temperature

@@ -17,7 +17,7 @@ initial tokens are ``[sot_prev] + history + sot_sequence + prefix`` (upstream's 
 in length.  They are packed RIGHT-ALIGNED to one prompt width P (``pack_prompts``): row b's tokens sit in columns [P - n_b, P), the
 columns before them are padding, one position counter serves the batch and generation starts at column P for every row; the device
 kernels take the rows' first columns (``starts``) and give every row its own position embeddings, its own attention window and its
-own sampling counter (include/wipa.h: wipa_decoder_begin_ragged / wipa_decoder_run_ragged).  P is the longest row rounded up to a
+own sampling counter (include/wipa.h: wipa_decoder_begin_ragged / wipa_decode_call.starts_dev).  P is the longest row rounded up to a
 multiple of 16 where that leaves room to generate.  ONE documented deviation from upstream: ``sample_len`` is clamped to
 ``n_text_ctx - P`` for the whole batch, so a row with a short prompt decoded next to one with the full 223-token history can generate
 448 - 227 = 221 tokens, not 224.  Without any prompt or prefix ``decode`` makes exactly the library calls it made before.
@@ -354,38 +354,28 @@ def timestamp_rules(tok: Tokenizer, max_initial_timestamp: Optional[float] = 1.0
     return _lib.DecodeRules(int(tok.timestamp_begin), int(tok.no_timestamps), index)
 
 
+def decode_call(n_init: int, eot: int, m_first, m_always, rules=None, sample_rec=None, starts=None, beam=None, continuous: bool = False,
+                prompted: bool = False, sample_rows=None, no_speech=None, no_speech_token: int = 0) -> "_lib.DecodeCall":
+    """The wipa_decode_call (include/wipa.h) of a decode: the masks, ``rules`` (``timestamp_rules``), ``sample_rec`` (the state's device
+    sampling record), ``starts`` (the state's device array of first columns; ``n_init`` is then the prompt width P), ``beam`` (the state's
+    beam buffer, max_candidates), and what a continuous stepper adds.  None / 0 / False: not used.  It holds addresses only: the tensors
+    stay the caller's to keep alive."""
+    buf, max_candidates = beam if beam is not None else (None, 0)
+    return _lib.DecodeCall(int(n_init), int(eot), ptr(m_first), ptr(m_always), C.pointer(rules) if rules is not None else None, ptr(sample_rec),
+                           ptr(sample_rows), ptr(starts), int(continuous), int(prompted), ptr(no_speech), int(no_speech_token), ptr(buf),
+                           buf.numel() if buf is not None else 0, int(max_candidates))
+
+
 def _dec_run(L, pk, st, B, n_init, eot, m_first, m_always, n, use_graph, rules, s, sample_rec=None, starts=None, beam=None):
-    """wipa_decoder_run, or wipa_decoder_run_rules when the greedy update carries the timestamp rules; wipa_decoder_run_sample
-    (rules or not) when ``sample_rec``, the state's device sampling record, is given; wipa_decoder_run_ragged when ``starts``, the
-    state's device array of first columns, is given (``n_init`` is then the prompt width P)"""
-    args = (C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, n_init, eot, ptr(m_first), ptr(m_always), n, int(use_graph))
-    if beam is not None:  # (the state's beam buffer, max_candidates): wipa_decoder_run_beam
-        _lib.check(L.wipa_decoder_run_beam(*args, C.byref(rules) if rules is not None else None, ptr(beam[0]), beam[0].numel(), beam[1], sptr(s)),
-                   "wipa_decoder_run_beam")
-    elif starts is not None:
-        _lib.check(L.wipa_decoder_run_ragged(*args, C.byref(rules) if rules is not None else None,
-                                             ptr(sample_rec) if sample_rec is not None else None, ptr(starts), sptr(s)), "wipa_decoder_run_ragged")
-    elif sample_rec is not None:
-        _lib.check(L.wipa_decoder_run_sample(*args, C.byref(rules) if rules is not None else None, ptr(sample_rec), sptr(s)),
-                   "wipa_decoder_run_sample")
-    elif rules is None:
-        _lib.check(L.wipa_decoder_run(*args, sptr(s)), "wipa_decoder_run")
-    else:
-        _lib.check(L.wipa_decoder_run_rules(*args, C.byref(rules), sptr(s)), "wipa_decoder_run_rules")
+    call = decode_call(n_init, eot, m_first, m_always, rules, sample_rec, starts, beam)
+    _lib.check(L.wipa_decoder_run_ex(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, C.byref(call), n, int(use_graph), sptr(s)),
+               "wipa_decoder_run_ex")
 
 
 def _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s, sample_rec=None, beam=None):
-    args = (C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, n_init, eot, ptr(m_first), ptr(m_always), int(use_graph))
-    if beam is not None:
-        _lib.check(L.wipa_decoder_prefill_beam(*args, C.byref(rules) if rules is not None else None, None, ptr(beam[0]), beam[0].numel(), beam[1],
-                                               sptr(s)), "wipa_decoder_prefill_beam")
-    elif sample_rec is not None:
-        _lib.check(L.wipa_decoder_prefill_sample(*args, C.byref(rules) if rules is not None else None, ptr(sample_rec), sptr(s)),
-                   "wipa_decoder_prefill_sample")
-    elif rules is None:
-        _lib.check(L.wipa_decoder_prefill(*args, sptr(s)), "wipa_decoder_prefill")
-    else:
-        _lib.check(L.wipa_decoder_prefill_rules(*args, C.byref(rules), sptr(s)), "wipa_decoder_prefill_rules")
+    call = decode_call(n_init, eot, m_first, m_always, rules, sample_rec, None, beam)
+    _lib.check(L.wipa_decoder_prefill_ex(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, C.byref(call), int(use_graph), sptr(s)),
+               "wipa_decoder_prefill_ex")
 
 
 def _begin_with(initial_tokens: Sequence[int]):

@@ -198,7 +198,7 @@ class TranscribePipeline:
         self.tok = get_tokenizer(model.is_multilingual, num_languages=model.num_languages, language=options.language or "en",
                                  task=options.task)
         # without_timestamps=False (mlx_whisper.transcribe's decode): the three-token prompt, ApplyTimestampRules in every greedy
-        # update on the device (wipa_decoder_run_rules) and the no-speech probability of a [sot] pass.  Same schedule, same probes.
+        # update on the device (wipa_decode_call.rules) and the no-speech probability of a [sot] pass.  Same schedule, same probes.
         self.timed = not options.without_timestamps
         self.rules = timestamp_rules(self.tok, options.max_initial_timestamp) if self.timed else None
         self.initial = list(self.tok.sot_sequence) if self.timed else list(self.tok.sot_sequence_including_notimestamps)

@@ -42,7 +42,7 @@ What differs from upstream, on purpose:
     schedules draw the same tokens.  It is admitted at the check that retired the failed attempt, from the encoder features its first
     admission left (no second log-mel, encoder or language detection), into a row that sits beside greedy first attempts and beside
     retries of other windows at other temperatures: the decode state's sampling record holds a temperature per row
-    (wipa_decoder_run_continuous_rows).  The window is booked when it passes or the schedule ends (the last attempt is kept).
+    (wipa_decode_call.sample_rows).  The window is booked when it passes or the schedule ends (the last attempt is kept).
     Conditioning (``condition_on_previous_text`` / ``initial_prompt``) runs on this schedule too: a file's next window exists once its
     previous one is booked, so ``_WindowSource.pending`` hands it out with the prompt the rounds loop would build, and the prompt stands
     in front of the window's admission column (continuous.py).  ``prompt_budget`` bounds the history kept.
