@@ -292,7 +292,7 @@ int wipa_attention(const wipa_attn_desc* d, wipa_stream_t s);
 /* K5 encoder self-attention, bf16 MFMA flash kernel (non-causal, T keys).
  * qk  [B*T, ldqk] bf16: q of head h at column h*64, k at column D + h*64;
  * vt  [B][D][ldvt] bf16: V transposed per clip (row h*64+d, column t), ldvt >= ceil64(T),
- *     columns >= T must hold finite values (zero);
+ *     columns >= T must hold finite values;
  * out [B*T, ldo] bf16. */
 int wipa_flash_attn_enc_bf16(const void* qk, int64_t ldqk, const void* vt, int64_t ldvt, void* out, int64_t ldo,
                              int B, int H, int T, wipa_stream_t s);

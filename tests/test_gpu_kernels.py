@@ -1,5 +1,6 @@
 """GPU parity tests, kernel level: every HIP kernel through the C ABI (ctypes) against a plain
-torch fp32 statement of the same op.  Run with ``pytest -m gpu`` on an MI355X."""
+torch fp32 statement of the same op (the forward attention kernels also per query row against float64,
+at their tile edges and strides, in tests/test_gpu_attention_forward.py).  Run with ``pytest -m gpu`` on an MI355X."""
 import math
 
 import numpy as np
