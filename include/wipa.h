@@ -1146,6 +1146,33 @@ int wipa_clip_adamw(float* params, float* grads, float* m, float* v, const int64
                     float* coef, float* norms, const int32_t* seg_clip, double max_norm, double lr, double beta1, double beta2,
                     double eps, double weight_decay, wipa_stream_t s);
 
+/* ------------------------------------------------------------------ low-rank adapters (csrc/lora.hip; no reference counterpart)
+ * A frozen linear y = (x W^T + b) c gains the term c s (x A^T) Bm^T with A [r, K] and Bm [N, r] contiguous f32, s = alpha / r; only A
+ * and Bm are trained.  All operands are f32; every product is an exact f32 product accumulated in f32 (the f32 MFMA, bit-equal to an
+ * fmaf chain), never the split-bf16 path.  r is a multiple of 4 in 4..64, K and N are multiples of 4, every pointer and every row is
+ * 16-byte aligned (leading dimensions in floats, multiples of 4); anything else is refused with a message that names the argument.
+ * No float atomics: the same call gives the same bits twice.
+ *
+ * wipa_lora_workspace_bytes: the scratch wipa_lora_bwd needs for M rows -- du [M, r] and the fixed-order partial sums of dA and dB, one
+ *   [r, K] and one [r, N] block per row chunk (chunks of at least 64 rows, at most 128 of them). */
+size_t wipa_lora_workspace_bytes(int M, int K, int N, int r);
+/* Forward, two launches.  y [M, ldy] already holds the base output (x W^T + b) c.  Writes u[m][j] = sum_k x[m][k] A[j][k] into u [M, r]
+ * (contiguous; kept for the backward), then y[m][n] += gain * sum_j u[m][j] Bm[n][j] with gain = c s (the caller's column scale sits
+ * inside it).  ldy may exceed N (the cross key | value halves of one [rows, 2d] buffer): columns >= N of a y row are never touched. */
+int wipa_lora_fwd(const float* x, int64_t ldx, const float* A, const float* Bm, float* y, int64_t ldy, float* u, int M, int K, int N,
+                  int r, float gain, wipa_stream_t s);
+/* Backward, three launches.  du[m][j] = gain sum_n dy[m][n] Bm[n][j] (kept in the workspace);  dB[n][j] = gain sum_m dy[m][n] u[m][j];
+ * dA[j][k] = sum_m du[m][j] x[m][k];  with dx != NULL: dx[m][k] (+)= sum_j du[m][j] A[j][k] (accumulate_dx: added to what dx holds);
+ * dx == NULL skips that term (an input that carries no gradient: the frozen encoder output).  dA [r, K] and dB [N, r] are overwritten.
+ * The sums over m run over row chunks whose partials land in the workspace and are added in ascending chunk order. */
+int wipa_lora_bwd(const float* dy, int64_t ldy, const float* x, int64_t ldx, const float* u, const float* A, const float* Bm, float* dA,
+                  float* dB, float* dx, int64_t lddx, int accumulate_dx, int M, int K, int N, int r, float gain, void* workspace,
+                  size_t workspace_bytes, wipa_stream_t s);
+/* W[n][k] = cast(float(base[n][k]) + s sum_j Bm[n][j] A[j][k]) for W, base [N, K] of dtype WIPA_F32 or WIPA_BF16 (leading dimensions in
+ * elements): the sum over j ascending as an fmaf chain from zero, one fmaf with the base, one rounding at the end.  W may be base. */
+int wipa_lora_merge(void* W, int64_t ldw, int dtype, const void* base, int64_t ld_base, const float* A, const float* Bm, int N, int K,
+                    int r, float s, wipa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,14 @@ def load_checkpoint_model(checkpoint_path: str, base_model: str = "mlx-community
         print(warning)
     model = load_model(base_model, audio_ctx=audio_ctx)
     model.set_dtype(torch.float32)
+    if checkpoint_path and os.path.exists(os.path.join(checkpoint_path, "adapter_config.json")):
+        # a LoRA run's checkpoint (or --adapter DIR): adapter files instead of a decoder overlay, merged into the base weights
+        from whisper_ipa_amd.lora import load_adapter
+
+        tensors, lora_cfg, _ = load_adapter(checkpoint_path)
+        model.set_adapter(tensors, lora_cfg)
+        print(f"✓ LoRA adapter applied: rank {lora_cfg.rank}, alpha {lora_cfg.alpha:g}, targets {','.join(lora_cfg.targets)} ({len(tensors)} tensors)")
+        return model
     try:
         n = overlay_decoder_weights(model, checkpoint_path)
     except FileNotFoundError:
@@ -358,7 +366,12 @@ def main(argv=None) -> Dict:
     ap.add_argument("--allow-byte-fallback", action="store_true",
                     help="run without the Whisper vocabulary (WIPA_TIKTOKEN unset): hypotheses render ids >= 256 as <|idN|>; "
                          "synthetic weights only")
+    ap.add_argument("--adapter", type=str, default=None, metavar="DIR",
+                    help="score the base model with the LoRA adapter of DIR (adapter_model.safetensors + adapter_config.json, as a "
+                         "--lora-rank training run writes them into its checkpoint directories) in place of --checkpoint")
     args = ap.parse_args(argv)
+    if args.adapter is not None:
+        args.checkpoint = args.adapter  # load_checkpoint_model applies the adapter files it finds there
     from whisper_ipa_amd.tokenizer import get_tokenizer, require_real_vocabulary
 
     require_real_vocabulary(get_tokenizer(True), args.allow_byte_fallback, "scoring a model's transcriptions")

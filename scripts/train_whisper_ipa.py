@@ -13,6 +13,7 @@ all-reduced over RCCL, the per-tensor clip and AdamW run on the reduced gradient
 from __future__ import annotations
 
 import argparse
+import contextlib
 import csv
 import json
 import os
@@ -38,6 +39,7 @@ from whisper_ipa_amd import parallel  # noqa: E402
 from whisper_ipa_amd.audio import SpecAugment  # noqa: E402
 from whisper_ipa_amd.decoding import DecodingOptions  # noqa: E402
 from whisper_ipa_amd.load_models import load_model, save_safetensors  # noqa: E402
+from whisper_ipa_amd.lora import LoRAConfig  # noqa: E402
 from whisper_ipa_amd.pipeline import transcribe_batches  # noqa: E402
 from whisper_ipa_amd.training import DecoderTrainer  # noqa: E402
 
@@ -286,11 +288,20 @@ def validate(model, dataset, tokenizer, num_samples: int = 100, scoring: str = "
     return metrics
 
 
+def save_weights(model, trainer, directory: Path, base_model: Optional[str] = None) -> None:
+    """what a checkpoint directory holds: ALL weights as model.safetensors (reference :421), or -- a LoRA run -- the adapter files
+    (adapter_model.safetensors + adapter_config.json, a few MB) instead of it"""
+    if getattr(trainer, "lora", None) is not None:
+        trainer.save_adapter(str(directory), extra={"base_model": base_model})
+    else:
+        save_safetensors(str(directory / "model.safetensors"), flatten_params(model.parameters()))
+
+
 def save_checkpoint(model, optimizer, step: int, loss, output_dir: Path, logger: Optional[TrainingLogger] = None,
-                    start_time: Optional[float] = None, learning_rate: Optional[float] = None) -> None:
+                    start_time: Optional[float] = None, learning_rate: Optional[float] = None, base_model: Optional[str] = None) -> None:
     ckpt = output_dir / f"checkpoint-{step}"
     ckpt.mkdir(parents=True, exist_ok=True)
-    save_safetensors(str(ckpt / "model.safetensors"), flatten_params(model.parameters()))  # ALL weights (reference :421)
+    save_weights(model, optimizer, ckpt, base_model)
     state = {"step": step, "loss": float(loss.item()) if hasattr(loss, "item") else float(loss)}
     if start_time is not None:
         state["wall_clock_sec"] = time.time() - start_time
@@ -326,8 +337,11 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
           test_run: bool = False, audio_root: str = "", seed: Optional[int] = None, exact_f32: bool = False,
           allow_byte_fallback: bool = False, cache_encoder_features: bool = True, feature_cache_clips: Optional[int] = None,
           clip_scope: str = "reference", scoring: str = "device", audio_ctx: Optional[int] = None, train_encoder_layers=0,
-          spec_augment: Optional[Dict] = None):
-    """``spec_augment``: None (default: no augmentation, nothing changes), or the keyword arguments of
+          spec_augment: Optional[Dict] = None, lora: Optional[Dict] = None):
+    """``lora``: None (default: nothing changes), or the keyword arguments of ``whisper_ipa_amd.lora.LoRAConfig`` (``--lora-rank`` ...):
+    the base model stays frozen and low-rank adapters on the targeted decoder linears are trained; checkpoints hold the adapter
+    files instead of the decoder overlay, validation runs with the adapter merged (``trainer.adapter_applied()``).
+    ``spec_augment``: None (default: no augmentation, nothing changes), or the keyword arguments of
     ``whisper_ipa_amd.audio.SpecAugment`` (``--spec-augment``): every training step masks time and mel-bin spans of its own copy of
     the mel, each clip over its own frames, from the stream (dataset index, step).  Runs without the feature cache.
     ``train_encoder_layers``: 0 (the reference: encoder frozen), a number K of top encoder blocks to train with ln_post, or
@@ -337,6 +351,9 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
     if spec_augment is not None and feature_cache_clips is not None:
         raise SystemExit("--spec-augment with --feature-cache-clips: augmented features differ every time a clip returns and cannot be cached")
     augmenter = SpecAugment(**spec_augment) if spec_augment is not None else None  # bad settings are refused here, by name
+    if lora is not None and train_encoder_layers != 0:
+        raise SystemExit("--lora-rank with --train-encoder-layers: adapters sit on a frozen model")
+    lora_cfg = LoRAConfig(**lora) if lora is not None else None  # a bad rank or target is refused here, by name
     rank, world = _init_distributed()
     try:
         parallel.require_even_shards(batch_size, world)  # every rank gets clips; no mismatched collectives
@@ -356,6 +373,8 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
                      "train_encoder_layers": train_encoder_layers}
         if augmenter is not None:
             args_dict["spec_augment"] = dict(augmenter.settings)
+        if lora_cfg is not None:
+            args_dict["lora"] = {"rank": lora_cfg.rank, "alpha": lora_cfg.alpha, "targets": list(lora_cfg.targets), "seed": lora_cfg.seed}
         save_training_config(output_dir, args_dict, get_hardware_info())
     logger = TrainingLogger(output_dir) if main else None
     print(f"Loading model: {model_name}")
@@ -367,7 +386,12 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
     # mlx AdamW defaults (reference :513); the clip reaches what the reference's clip_grad_dict reaches (:287-303: dicts only,
     # the decoder.blocks list passes through) unless --clip-scope all
     trainer = DecoderTrainer(model, lr=learning_rate, f32_split=not exact_f32, clip_scope=clip_scope,
-                             train_encoder_layers=train_encoder_layers, spec_augment=augmenter)
+                             train_encoder_layers=train_encoder_layers, spec_augment=augmenter, lora=lora_cfg)
+    if lora_cfg is not None and main:
+        print(f"  ✓ LoRA: rank {lora_cfg.rank}, alpha {lora_cfg.alpha:g}, targets {','.join(lora_cfg.targets)}: "
+              f"{trainer.n_params:,} trainable parameters, the base model is frozen")
+    # validation decodes with the model's packed tables: a LoRA run merges its current adapter into them for the duration
+    applied = trainer.adapter_applied if lora_cfg is not None else contextlib.nullcontext
     if augmenter is not None and main:
         st = augmenter.settings
         print(f"  ✓ SpecAugment: time spans of {st['mask_time_length']} frames (prob {st['mask_time_prob']}, at least "
@@ -442,21 +466,22 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
                       f"Samples/sec: {batch_size / step_time:.1f}")
                 logger.log_train_step(step, loss_value, learning_rate, step_time, batch_size, time.time() - start_time)
             if step % validate_every == 0:
-                metrics = validate(model, test_dataset, tokenizer, num_samples=min(100, len(test_dataset)), scoring=scoring)  # collective
+                with applied():
+                    metrics = validate(model, test_dataset, tokenizer, num_samples=min(100, len(test_dataset)), scoring=scoring)  # collective
             if main and step % validate_every == 0:
                 if logger.log_validation(step, metrics, time.time() - start_time):
                     best = output_dir / "best-checkpoint"
                     if best.exists():
                         shutil.rmtree(best)
                     best.mkdir(parents=True, exist_ok=True)
-                    save_safetensors(str(best / "model.safetensors"), flatten_params(model.parameters()))
+                    save_weights(model, trainer, best, model_name)
                     with open(best / "training_state.json", "w") as f:
                         json.dump({"step": step, "pfer": metrics["pfer"], "per": metrics["per"],
                                    "timestamp": datetime.now().isoformat()}, f, indent=2)
                     print(f"  ✓ New best PFER {metrics['pfer']:.2f}% at step {step}")
             if main and step % save_every == 0:
                 save_checkpoint(model, trainer, step, loss, output_dir, logger=logger, start_time=start_time,
-                                learning_rate=learning_rate)
+                                learning_rate=learning_rate, base_model=model_name)
         except Exception as e:  # reference :598-602
             print(f"\n✗ Error at step {step}: {e}")
             import traceback
@@ -469,13 +494,14 @@ def train(model_name: str, train_data_path: str, test_data_path: str, output_dir
 
     if main:
         print("\n" + "=" * 70 + "\nTraining complete! Running final validation...\n" + "=" * 70)
-    metrics = validate(model, test_dataset, tokenizer, num_samples=min(500, len(test_dataset)), scoring=scoring)  # collective
+    with applied():
+        metrics = validate(model, test_dataset, tokenizer, num_samples=min(500, len(test_dataset)), scoring=scoring)  # collective
     if main:
         logger.log_validation(num_steps, metrics, time.time() - start_time)
         if latest_loss is not None:
             print("\nSaving final model...")
             save_checkpoint(model, trainer, num_steps, latest_loss, output_dir, logger=logger, start_time=start_time,
-                            learning_rate=learning_rate)
+                            learning_rate=learning_rate, base_model=model_name)
             total = time.time() - start_time
             with open(output_dir / "training_summary.json", "w") as f:
                 json.dump({"total_wall_clock_sec": total, "total_wall_clock_min": total / 60,
@@ -548,7 +574,20 @@ def main():
     p.add_argument("--mask-feature-length", type=int, default=10, help="bins per bin span")
     p.add_argument("--mask-feature-min-masks", type=int, default=0, help="at least this many bin spans per clip")
     p.add_argument("--augment-seed", type=int, default=0, help="seed of the masks (with the dataset index and the step)")
+    p.add_argument("--lora-rank", type=int, default=0, metavar="R",
+                   help="train low-rank adapters of rank R (a multiple of 4 in 4..64) on a frozen model instead of the decoder itself; "
+                        "checkpoints then hold adapter_model.safetensors + adapter_config.json.  Recorded in training_config.json.  "
+                        "Default 0: off")
+    p.add_argument("--lora-alpha", type=float, default=None, help="the adapter's scale is alpha / rank (default: 2 x rank)")
+    p.add_argument("--lora-targets", type=str, default="query,value",
+                   help="comma-separated: query, key, value, out, mlp1, mlp2; a bare query / key / value / out means both attn and "
+                        "cross_attn, attn.query or cross_attn.value names one")
+    p.add_argument("--lora-seed", type=int, default=0, help="seed of the adapter initialisation")
     a = p.parse_args()
+    lora = None
+    if a.lora_rank:
+        lora = dict(rank=a.lora_rank, alpha=a.lora_alpha if a.lora_alpha is not None else 2.0 * a.lora_rank,
+                    targets=tuple(t.strip() for t in a.lora_targets.split(",") if t.strip()), seed=a.lora_seed)
     aug = None
     if a.spec_augment:
         aug = dict(mask_time_prob=a.mask_time_prob, mask_time_length=a.mask_time_length, mask_time_min_masks=a.mask_time_min_masks,
@@ -559,7 +598,7 @@ def main():
           save_every=a.save_every, test_run=a.test_run, audio_root=a.audio_root, exact_f32=a.exact_f32,
           allow_byte_fallback=a.allow_byte_fallback, cache_encoder_features=not a.no_cache_encoder_features,
           feature_cache_clips=a.feature_cache_clips, clip_scope=a.clip_scope, scoring=a.scoring, audio_ctx=a.audio_ctx,
-          train_encoder_layers=a.train_encoder_layers, spec_augment=aug)
+          train_encoder_layers=a.train_encoder_layers, spec_augment=aug, lora=lora)
 
 
 if __name__ == "__main__":

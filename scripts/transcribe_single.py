@@ -32,6 +32,14 @@ def load_checkpoint_model(checkpoint_path: str, base_model: str = "mlx-community
         print(warning)
     model = load_model(base_model, audio_ctx=audio_ctx)
     model.set_dtype(torch.float32)
+    if checkpoint_path and os.path.exists(os.path.join(checkpoint_path, "adapter_config.json")):
+        # a LoRA run's checkpoint (or --adapter DIR): adapter files instead of a decoder overlay, merged into the base weights
+        from whisper_ipa_amd.lora import load_adapter
+
+        tensors, lora_cfg, _ = load_adapter(checkpoint_path)
+        model.set_adapter(tensors, lora_cfg)
+        print(f"✓ LoRA adapter applied: rank {lora_cfg.rank}, alpha {lora_cfg.alpha:g}, targets {','.join(lora_cfg.targets)} ({len(tensors)} tensors)")
+        return model
     if checkpoint_path:
         try:
             n = overlay_decoder_weights(model, checkpoint_path)
@@ -81,7 +89,12 @@ def main(argv=None):
     ap.add_argument("--audio-ctx", type=int, default=None,
                     help="run the model on its first N audio positions of 20 ms (default: what the checkpoint's training_config.json "
                          "records, else all 1500); a clip longer than N * 20 ms is cut, with a warning")
+    ap.add_argument("--adapter", default=None, metavar="DIR",
+                    help="transcribe with the base model and the LoRA adapter of DIR (adapter_model.safetensors + adapter_config.json) "
+                         "in place of --checkpoint")
     args = ap.parse_args(argv)
+    if args.adapter is not None:
+        args.checkpoint = args.adapter  # load_checkpoint_model applies the adapter files it finds there
     from whisper_ipa_amd.tokenizer import get_tokenizer, require_real_vocabulary
 
     require_real_vocabulary(get_tokenizer(True), args.allow_byte_fallback, "transcribing with a trained checkpoint")

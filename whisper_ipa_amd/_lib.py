@@ -291,6 +291,12 @@ SIGNATURES = {
     "wipa_clip_adamw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                 c_void_p, c_void_p, c_void_p, c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                 C.c_double, c_void_p]),
+    "wipa_lora_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "wipa_lora_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_float,
+                              c_void_p]),
+    "wipa_lora_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                              c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
+    "wipa_lora_merge": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
 }
 
 _lib = None

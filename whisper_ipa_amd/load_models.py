@@ -87,8 +87,10 @@ def save_safetensors(path: str, flat: Dict[str, torch.Tensor]) -> None:
 
 
 def load_model(path_or_name: str, dtype: torch.dtype = torch.float32, sinusoid_rounding: str = "f32",
-               audio_ctx: Optional[int] = None) -> Whisper:
+               audio_ctx: Optional[int] = None, adapter: Optional[str] = None) -> Whisper:
     """Local directory -> Whisper.  Raises with a clear message for hub names (offline).
+    ``adapter``: a directory written by lora.save_adapter (adapter_model.safetensors + adapter_config.json): the base model is
+    loaded and the adapter applied (Whisper.set_adapter).
     ``sinusoid_rounding="fp16"`` reproduces mlx_whisper's fp16-built encoder sinusoid table (Whisper.__init__).
     ``audio_ctx``: run the model on its first N audio positions (Whisper.__init__)."""
     if not os.path.isdir(path_or_name):
@@ -114,6 +116,11 @@ def load_model(path_or_name: str, dtype: torch.dtype = torch.float32, sinusoid_r
         raise FileNotFoundError(f"load_model: no weights.safetensors / model.safetensors in {path_or_name}")
     model = Whisper(dims, dtype=dtype, sinusoid_rounding=sinusoid_rounding, audio_ctx=audio_ctx)
     model.load_weights(weights)
+    if adapter is not None:
+        from .lora import load_adapter
+
+        tensors, lcfg, _ = load_adapter(adapter)
+        model.set_adapter(tensors, lcfg)
     return model
 
 

@@ -26,7 +26,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import _lib, ops, parallel
+from . import _lib, lora as lora_mod, ops, parallel
 from .runtime import on_stream, ptr, sptr
 from .whisper import Whisper, parameter_names
 
@@ -242,8 +242,20 @@ def flat_layout(dims, train_encoder_layers=0) -> Dict:
 class DecoderTrainer:
     def __init__(self, model: Whisper, lr: float = 1e-5, max_grad_norm: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.01, f32_split: Optional[bool] = None, clip_scope: str = "reference",
-                 train_encoder_layers=0, spec_augment=None):
-        """``spec_augment`` (an ``audio.SpecAugment``; default None: the step as it is without one, launch for launch): every training
+                 train_encoder_layers=0, spec_augment=None, lora=None):
+        """``lora`` (a ``lora.LoRAConfig``; default None: the trainer as it is without one, launch for launch): low-rank adapters on the
+        targeted decoder linears.  The flat p / g / m / v buffers hold the adapter tensors only (``lora.adapter_layout``); the base
+        tensors stay where ``model._params`` has them and are never written.  The forward adds every adapted linear's term with
+        wipa_lora_fwd after its base GEMM (after the split-K sum where there is one; one call per adapted half of the fused cross
+        key | value projection), the backward calls wipa_lora_bwd and computes no weight, bias or LayerNorm-parameter gradient of the
+        base: the input-gradient GEMMs, attention and LayerNorm backward stay, the tied-embedding gradient, its transposes and the
+        embedding scatter are skipped.  A data-parallel step all-reduces adapter bytes only.  ``clip_scope`` applies by name as it
+        stands: adapter names contain a block index, so ``"reference"`` clips none of them and ``"all"`` clips each.  The feature
+        cache and ``spec_augment`` work as on any decoder-only trainer.  Refused: ``train_encoder_layers != 0``, ``leaves()`` and
+        ``differentiable_logits``, a step while the model has an adapter applied (Whisper.set_adapter).  ``adapter()`` /
+        ``save_adapter(dir)`` / ``adapter_applied()`` are the way out.  Not built: adapters on encoder blocks or the embedding,
+        dropout on the adapter path.
+        ``spec_augment`` (an ``audio.SpecAugment``; default None: the step as it is without one, launch for launch): every training
         step masks the padded f32 copy of the mel it makes anyway -- the buffer of _encoder_forward, or embed_audio's on a
         decoder-only trainer -- with one launch (csrc/spec_augment.hip); the caller's mel is never modified.  Row b draws from the
         stream (clip_keys[b], step_count) when train_step is given ``clip_keys``, else (rank * B + b, step_count): no two ranks
@@ -280,15 +292,29 @@ class DecoderTrainer:
         self.trains_encoder = self._enc_first < d.n_audio_layer
         if self.trains_encoder and d.n_audio_state != d.n_text_state:
             raise _lib.WipaError("DecoderTrainer: train_encoder_layers needs an encoder as wide as the decoder")
-        layout = flat_layout(d, train_encoder_layers)
+        self.lora = lora
+        if lora is not None:
+            if not isinstance(lora, lora_mod.LoRAConfig):
+                raise _lib.WipaError(f"DecoderTrainer: lora must be a LoRAConfig, got {type(lora).__name__}")
+            if self.trains_encoder:
+                raise _lib.WipaError(f"DecoderTrainer: lora together with train_encoder_layers={train_encoder_layers!r}: adapters sit on "
+                                     "a frozen model (train_encoder_layers must be 0)")
+            if getattr(model, "_adapter", None) is not None:
+                raise _lib.WipaError("DecoderTrainer: lora on a model that has an adapter applied: set_adapter(None) first")
+        self._lora_sites = frozenset(lora.sites()) if lora is not None else frozenset()
+        layout = flat_layout(d, train_encoder_layers) if lora is None else lora_mod.adapter_layout(d, lora)
         self.names = layout["names"]  # decoder tensors first, as without encoder layers, then the trained encoder tensors
         self.offsets, sizes, total = layout["offsets"], layout["sizes"], layout["total"]
         # contiguous gradient segments, in the order the backward finishes them: each is all-reduced (_reduce_segment) while the
         # earlier blocks still compute
         self.segments = layout["segments"]
         self._segments_done = 0
-        P = model.flat_parameters()
-        self.shapes = {n: parameter_shape(d, n) for n in self.names}
+        if lora is None:
+            P = model.flat_parameters()
+            self.shapes = {n: parameter_shape(d, n) for n in self.names}
+        else:
+            P = lora_mod.init_adapter(d, lora)
+            self.shapes = {n: lora_mod.adapter_shape(d, lora, n) for n in self.names}
         assert all(tuple(P[n].shape) == self.shapes[n] for n in self.names)
         # so that every tensor starts 16-byte aligned in the flat buffers: wipa_sum_slabs writes the weight gradients there and
         # refuses any other address (the optimiser, wipa_clip_adamw, walks its chunks float by float and would not mind)
@@ -302,7 +328,8 @@ class DecoderTrainer:
             self.flat_v = torch.zeros(total, dtype=torch.float32, device=dev)
             for n in self.names:
                 self.p(n).copy_(P[n])
-                model._params[n] = self.p(n)  # the model now reads the optimiser's buffer directly
+                if lora is None:
+                    model._params[n] = self.p(n)  # the model now reads the optimiser's buffer directly
             # chunk tables for the flat multi-tensor optimiser
             ch_off, ch_len, ch_seg, seg_first = [], [], [], [0]
             for si, (n, s) in enumerate(zip(self.names, sizes)):
@@ -330,6 +357,9 @@ class DecoderTrainer:
         self._spec_augment = None
         self.spec_augment = spec_augment
         self._leaves = None     # autograd leaves over flat_p (leaves())
+        self._lora_ws = None    # wipa_lora_bwd's scratch, sized by the largest call so far
+        self._ln_scratch = None  # where wipa_layernorm_bwd leaves the dw / db a LoRA trainer does not keep
+        self._kv_frozen = {}    # block -> (the tensors it was made of, cross key | value weight as one [2d, d] matrix) of a LoRA trainer
         model._trainer = self   # Whisper.logits differentiates through this trainer under torch.enable_grad()
 
     @property
@@ -392,6 +422,97 @@ class DecoderTrainer:
 
     def grads(self) -> Dict[str, torch.Tensor]:
         return {n: self.g(n) for n in self.names}
+
+    def _gw(self, name: str) -> Optional[torch.Tensor]:
+        """where the backward leaves the gradient of ``name``: its view of flat_g, or None for a tensor this trainer does not train
+        (every base tensor of a LoRA trainer) -- the backward then skips that gradient"""
+        return self.g(name) if name in self.offsets else None
+
+    # ---- low-rank adapters (lora=...)
+    def adapter(self) -> Dict[str, torch.Tensor]:
+        """name -> the current adapter tensor (a view of the flat parameter buffer)"""
+        self._lora_only("adapter")
+        return {n: self.p(n) for n in self.names}
+
+    def load_adapter(self, adapter: Dict[str, torch.Tensor]) -> None:
+        """overwrite the adapter tensors (e.g. with lora.load_adapter's); the optimiser moments are kept"""
+        self._lora_only("load_adapter")
+        lora_mod.check_adapter(self.model.dims, self.lora, adapter)
+        with on_stream():
+            for n in self.names:
+                self.p(n).copy_(torch.as_tensor(adapter[n]).to(device=self.model.device, dtype=torch.float32))
+
+    def save_adapter(self, directory: str, extra: Optional[Dict] = None) -> None:
+        """adapter_model.safetensors + adapter_config.json (lora.save_adapter); audio_ctx is the model's"""
+        self._lora_only("save_adapter")
+        with on_stream():
+            cpu = {n: t.detach().cpu() for n, t in self.adapter().items()}
+        lora_mod.save_adapter(directory, cpu, self.lora, dict(dict(audio_ctx=self.model.audio_ctx), **(extra or {})))
+
+    def adapter_applied(self):
+        """``with trainer.adapter_applied():`` the model runs with the trainer's current adapter merged into its weights
+        (Whisper.set_adapter) -- validation -- and is the base model again on exit.  No step may run inside."""
+        self._lora_only("adapter_applied")
+        trainer = self
+
+        class _Applied:
+            def __enter__(self):
+                trainer.model.set_adapter(trainer.adapter(), trainer.lora)
+                return trainer.model
+
+            def __exit__(self, *exc):
+                trainer.model.set_adapter(None)
+                return False
+
+        return _Applied()
+
+    def _lora_only(self, what: str) -> None:
+        if self.lora is None:
+            raise _lib.WipaError(f"DecoderTrainer.{what} needs a trainer built with lora=LoRAConfig(...)")
+
+    def _no_lora(self, what: str) -> None:
+        if self.lora is not None:
+            raise _lib.WipaError(f"DecoderTrainer.{what} on a LoRA trainer: the base tensors are no leaves here; step with train_step / "
+                                 "loss_and_grads")
+
+    def _lora_fwd(self, site: str, S: Dict, key: str, x, y, M: int, K: int, N: int, c: float = 1.0) -> None:
+        """y [M, N] (row stride y.stride(0)) += c s (x A^T) B^T for the adapted linear ``site`` (decoder.blocks.l.attn.query ...); nothing
+        when it carries no adapter.  ``c``: the column scale of the base linear, which the term sits inside.  Keeps u in S[key]."""
+        if site.split(".", 3)[-1] not in self._lora_sites or not site.startswith("decoder."):
+            return
+        r = self.lora.rank
+        with on_stream() as s:
+            u = torch.empty(M, r, dtype=torch.float32, device=y.device)
+            _lib.check(self.L.wipa_lora_fwd(ptr(x), x.stride(0), ptr(self.p(site + ".lora_A")), ptr(self.p(site + ".lora_B")), ptr(y),
+                                            y.stride(0), ptr(u), M, K, N, r, float(c) * self.lora.scale, sptr(s)), "wipa_lora_fwd")
+        S[key] = u
+
+    def _lora_bwd(self, site: str, S: Dict, key: str, dy, x, dx, M: int, K: int, N: int) -> None:
+        """the adapter gradients of ``site`` into flat_g, and dx += its input gradient (dx None: an input that carries none).  ``dy`` is
+        the gradient of the linear BEFORE its column scale, as _lin_bwd takes it (the attention backward has multiplied dq and dk by
+        QK_SCALE already), so the gain is s alone."""
+        if key not in S:
+            return
+        r = self.lora.rank
+        need = self.L.wipa_lora_workspace_bytes(M, K, N, r)
+        with on_stream() as s:
+            if self._lora_ws is None or self._lora_ws.numel() * 4 < need:
+                self._lora_ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=dy.device)
+            _lib.check(self.L.wipa_lora_bwd(ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(S[key]), ptr(self.p(site + ".lora_A")),
+                                            ptr(self.p(site + ".lora_B")), ptr(self.g(site + ".lora_A")), ptr(self.g(site + ".lora_B")),
+                                            ptr(dx), 0 if dx is None else dx.stride(0), 1, M, K, N, r, self.lora.scale,
+                                            ptr(self._lora_ws), self._lora_ws.numel() * 4, sptr(s)), "wipa_lora_bwd")
+
+    def _kv_weight(self, pre: str) -> torch.Tensor:
+        """cross_attn.key.weight | cross_attn.value.weight of block ``pre`` as one [2d, d] matrix: the pair's view of the flat
+        parameter buffer, or for a LoRA trainer (whose base tensors lie apart) a copy made once per pair of base tensors"""
+        if self.lora is None:
+            return self._kv_pair(self.flat_p, pre)
+        k, v = self.model._params[f"{pre}.cross_attn.key.weight"], self.model._params[f"{pre}.cross_attn.value.weight"]
+        hit = self._kv_frozen.get(pre)
+        if hit is None or hit[0] is not k or hit[1] is not v:
+            hit = self._kv_frozen[pre] = (k, v, torch.cat([k, v]))
+        return hit[2]
 
     # ---- kernel helpers (all on the library stream)
     def _gemm(self, *a, **kw):
@@ -459,6 +580,8 @@ class DecoderTrainer:
                 WT = self._transpose(W, N, K, Np)  # [K, Np]
                 # contraction over n: A = dy (row stride ld, first Np columns must be readable and zero beyond N)
                 self._mm(dy, WT, out_dx, M, K, Np, dy.stride(0), Np, residual=(out_dx if accumulate_dx else None))
+        if dW is None:  # a frozen weight (the base of a LoRA trainer): no weight gradient, no bias gradient
+            return out_dx
         if kmajor:
             A_op, W_op, lda, ldw, Kc, flags = dy, x, dy.stride(0), x.stride(0), M, dict(a_trans=True, w_trans=True)
         else:
@@ -503,6 +626,10 @@ class DecoderTrainer:
 
     def _ln_bwd(self, x, dy, w, dx, accumulate, dw, db, M, D):
         with on_stream() as s:
+            if dw is None:  # a frozen LayerNorm (LoRA trainer): the kernel's dw / db go to a scratch nobody reads
+                if self._ln_scratch is None or self._ln_scratch.numel() < 2 * D:
+                    self._ln_scratch = torch.empty(2 * D, dtype=torch.float32, device=x.device)
+                dw, db = self._ln_scratch[:D], self._ln_scratch[D:2 * D]
             stats = torch.empty(2 * M + 64 * D, dtype=torch.float32, device=x.device)  # (mean, rstd) + chunked dw / db partials
             _lib.check(self.L.wipa_layernorm_bwd(ptr(x), ptr(dy), ptr(w), ptr(dx), int(accumulate), ptr(dw), ptr(db), ptr(stats),
                                                  stats.numel(), M, D, 1e-5, sptr(s)), "wipa_layernorm_bwd")
@@ -546,8 +673,15 @@ class DecoderTrainer:
         S["q"] = self._lin(S["h1"], M, d, W(f"{pre}.attn.query.weight"), d, W(f"{pre}.attn.query.bias"), QK_SCALE)
         S["k"] = self._lin(S["h1"], M, d, W(f"{pre}.attn.key.weight"), d, None, QK_SCALE)
         S["v"] = self._lin(S["h1"], M, d, W(f"{pre}.attn.value.weight"), d, W(f"{pre}.attn.value.bias"))
+        if self._lora_sites:
+            self._lora_fwd(f"{pre}.attn.query", S, "u_q", S["h1"], S["q"], M, d, d, QK_SCALE)
+            self._lora_fwd(f"{pre}.attn.key", S, "u_k", S["h1"], S["k"], M, d, d, QK_SCALE)
+            self._lora_fwd(f"{pre}.attn.value", S, "u_v", S["h1"], S["v"], M, d, d)
         S["a"], S["lse1"], S["desc1"] = self._attn(S["q"], S["k"], S["v"], B, H, T, T, causal)
-        return self._lin(S["a"], M, d, W(f"{pre}.attn.out.weight"), d, W(f"{pre}.attn.out.bias"), residual=x)
+        x_b = self._lin(S["a"], M, d, W(f"{pre}.attn.out.weight"), d, W(f"{pre}.attn.out.bias"), residual=x)
+        if self._lora_sites:
+            self._lora_fwd(f"{pre}.attn.out", S, "u_o", S["a"], x_b, M, d, d)
+        return x_b
 
     def _mlp_fwd(self, pre: str, S: Dict, x_c: torch.Tensor) -> torch.Tensor:
         """the MLP half of block ``pre`` (decoder or encoder) on x_c [M, d]: LayerNorm, mlp1, GELU, mlp2 + residual.  Fills what
@@ -557,16 +691,21 @@ class DecoderTrainer:
         S["x_c"] = x_c
         S["h3"] = self._ln(x_c, W(f"{pre}.mlp_ln.weight"), W(f"{pre}.mlp_ln.bias"))
         S["z"] = self._lin(S["h3"], M, d, W(f"{pre}.mlp1.weight"), 4 * d, W(f"{pre}.mlp1.bias"))
+        if self._lora_sites:
+            self._lora_fwd(f"{pre}.mlp1", S, "u_m1", S["h3"], S["z"], M, d, 4 * d)
         S["u"] = torch.empty_like(S["z"])
         with on_stream() as s:
             _lib.check(self.L.wipa_gelu(ptr(S["z"]), ptr(S["u"]), S["z"].numel(), sptr(s)), "wipa_gelu")
-        return self._lin(S["u"], M, 4 * d, W(f"{pre}.mlp2.weight"), d, W(f"{pre}.mlp2.bias"), residual=x_c)
+        x_next = self._lin(S["u"], M, 4 * d, W(f"{pre}.mlp2.weight"), d, W(f"{pre}.mlp2.bias"), residual=x_c)
+        if self._lora_sites:
+            self._lora_fwd(f"{pre}.mlp2", S, "u_m2", S["u"], x_next, M, 4 * d, d)
+        return x_next
 
     def _forward(self, audio_features: torch.Tensor, tok_in: torch.Tensor):
         """Teacher-forced decoder on ``tok_in`` [B, T] int32 (device, contiguous) and features [B, 1500, d]: returns the
         zero-padded logits [ceil32(B*T), ceil32(V)] f32 and the saved activations the backward needs."""
         m, dm, L = self.model, self.model.dims, self.L
-        P = self.p
+        P = self.w  # every decoder tensor is in the flat buffer (self.p) unless this is a LoRA trainer, whose base is the model's own
         B, T = tok_in.shape
         d, H, V, Ta = dm.n_text_state, dm.n_text_head, dm.n_vocab, self.model.n_audio_ctx
         M, Mp = B * T, _ceil(B * T, 32)
@@ -578,7 +717,8 @@ class DecoderTrainer:
             dev = m.device
             feats = audio_features.to(device=dev, dtype=torch.float32).contiguous().view(B * Ta, d)
             # [d, ceil32(B*Ta)], shared by all layers; not needed when the weight-gradient GEMM reads feats K-major
-            featsT = None if (B * Ta) % 32 == 0 else self._transpose(feats, B * Ta, d, _ceil(B * Ta, 32))
+            # (nor by a LoRA trainer, which has no such GEMM)
+            featsT = None if (B * Ta) % 32 == 0 or self.lora is not None else self._transpose(feats, B * Ta, d, _ceil(B * Ta, 32))
             x = torch.empty(M, d, dtype=torch.float32, device=dev)
             _lib.check(L.wipa_embed_tokens(ptr(tok_in), T, B, T, 0, None, ptr(P("decoder.token_embedding.weight")), 0, None,
                                            ptr(P("decoder.positional_embedding")), ptr(x), d, sptr(s)), "wipa_embed_tokens")
@@ -589,16 +729,23 @@ class DecoderTrainer:
                 S["x_b"] = self._self_attn_fwd(pre, S, x, B, T, H, causal=True)
                 S["h2"] = self._ln(S["x_b"], P(f"{pre}.cross_attn_ln.weight"), P(f"{pre}.cross_attn_ln.bias"))
                 S["qc"] = self._lin(S["h2"], M, d, P(f"{pre}.cross_attn.query.weight"), d, P(f"{pre}.cross_attn.query.bias"), QK_SCALE)
+                if self._lora_sites:
+                    self._lora_fwd(f"{pre}.cross_attn.query", S, "u_qc", S["h2"], S["qc"], M, d, d, QK_SCALE)
                 # cross key | value as ONE projection over the B*1500 encoder rows: key.weight and value.weight are adjacent in
                 # the flat parameter buffer, i.e. one [2d, d] matrix (grid of 750 instead of two of 375 tiles: 2.9 rounds on
                 # the 256 CUs instead of 1.5 twice); the key half is scaled in the epilogue, the value half carries its bias
                 kv = torch.empty(B * Ta, 2 * d, dtype=torch.float32, device=dev)
                 bkv = torch.cat([torch.zeros_like(P(f"{pre}.cross_attn.value.bias")), P(f"{pre}.cross_attn.value.bias")])
-                self._gemm(feats, self._kv_pair(self.flat_p, pre), kv, M=B * Ta, N=2 * d, K=d, lda=d, ldw=d, ldc=2 * d, bias=bkv,
+                self._gemm(feats, self._kv_weight(pre), kv, M=B * Ta, N=2 * d, K=d, lda=d, ldw=d, ldc=2 * d, bias=bkv,
                            col_scale_n=d, col_scale=QK_SCALE)
                 S["kc"], S["vc"] = kv[:, :d], kv[:, d:]
+                if self._lora_sites:  # one call per adapted half, on the half's strided view of kv
+                    self._lora_fwd(f"{pre}.cross_attn.key", S, "u_kc", feats, S["kc"], B * Ta, d, d, QK_SCALE)
+                    self._lora_fwd(f"{pre}.cross_attn.value", S, "u_vc", feats, S["vc"], B * Ta, d, d)
                 S["c"], S["lse2"], S["desc2"] = self._attn(S["qc"], S["kc"], S["vc"], B, H, T, Ta, False)
                 x_c = self._lin(S["c"], M, d, P(f"{pre}.cross_attn.out.weight"), d, P(f"{pre}.cross_attn.out.bias"), residual=S["x_b"])
+                if self._lora_sites:
+                    self._lora_fwd(f"{pre}.cross_attn.out", S, "u_oc", S["c"], x_c, M, d, d)
                 x = self._mlp_fwd(pre, S, x_c)
                 saved.append(S)
             x_L = x
@@ -632,7 +779,8 @@ class DecoderTrainer:
         ``d_feats`` [B*N, d] (trainers that train encoder layers): receives the gradient of the encoder output, summed over the
         decoder layers in the order the backward visits them."""
         m, dm, L = self.model, self.model.dims, self.L
-        P, G = self.p, self.g
+        P, G = self.w, self._gw  # G gives None for a tensor that is not trained (a LoRA trainer's base): that gradient is skipped
+        lora = self.lora is not None
         saved, x_L, hf, feats, featsT, tok_in = ctx["saved"], ctx["x_L"], ctx["hf"], ctx["feats"], ctx["featsT"], ctx["tok_in"]
         B, T = ctx["B"], ctx["T"]
         d, H, V, Ta = dm.n_text_state, dm.n_text_head, dm.n_vocab, self.model.n_audio_ctx
@@ -646,13 +794,16 @@ class DecoderTrainer:
             ET = self._transpose(E, V, d, Vp)  # [d, Vp]
             dhf = torch.empty(M, d, dtype=torch.float32, device=dev)
             self._mm(dlogits, ET, dhf, M, d, Vp, Vp, Vp)  # 96 tiles over a 51 872-long contraction: eight K slices
-            dlT = self._transpose(dlogits, M, V, Mp)  # [V, Mp]
-            hfT = self._transpose(hf, M, d, Mp)
-            self._gemm(dlT, hfT, G("decoder.token_embedding.weight"), M=V, N=d, K=Mp, lda=Mp, ldw=Mp, ldc=d)
-            del dlT, dlogits
+            if not lora:  # the embedding is frozen under LoRA: no dE GEMM and neither of its transposes
+                dlT = self._transpose(dlogits, M, V, Mp)  # [V, Mp]
+                hfT = self._transpose(hf, M, d, Mp)
+                self._gemm(dlT, hfT, G("decoder.token_embedding.weight"), M=V, N=d, K=Mp, lda=Mp, ldw=Mp, ldc=d)
+                del dlT
+            del dlogits
             dx = torch.empty(M, d, dtype=torch.float32, device=dev)
             self._ln_bwd(x_L, dhf, P("decoder.ln.weight"), dx, False, G("decoder.ln.weight"), G("decoder.ln.bias"), M, d)
-            self._reduce_segment(reducer, "decoder.tail")
+            if not lora:
+                self._reduce_segment(reducer, "decoder.tail")
             for l in reversed(range(dm.n_text_layer)):
                 pre = f"decoder.blocks.{l}"
                 S = saved[l]
@@ -660,23 +811,33 @@ class DecoderTrainer:
                 # x_c = x_b + c Wco^T + bco
                 dc = self._lin_bwd(dx, M, d, S["c"], None, d, P(f"{pre}.cross_attn.out.weight"), G(f"{pre}.cross_attn.out.weight"),
                                    G(f"{pre}.cross_attn.out.bias"))
+                if lora:
+                    self._lora_bwd(f"{pre}.cross_attn.out", S, "u_oc", dx, S["c"], dc, M, d, d)
                 dqc = torch.empty(M, d, dtype=torch.float32, device=dev)
                 dkv = torch.empty(B * Ta, 2 * d, dtype=torch.float32, device=dev)  # d(key) | d(value), strides of the forward's kv
                 dkc, dvc = dkv[:, :d], dkv[:, d:]
                 self._attn_bwd(S["desc2"], S["c"], dc, S["lse2"], dqc, dkc, dvc)
                 # one weight-gradient GEMM for the [2d, d] pair, value bias apart.  Its input gradient is the encoder output's: none
                 # while the encoder is frozen; else the last decoder layer writes d_feats and the others add
-                self._lin_bwd(dkv, B * Ta, 2 * d, feats, featsT, d, self._kv_pair(self.flat_p, pre), self._kv_pair(self.flat_g, pre),
-                              None, dx=d_feats, accumulate_dx=(l != dm.n_text_layer - 1), need_dx=d_feats is not None)
-                self._colsum(dvc, B * Ta, d, G(f"{pre}.cross_attn.value.bias"))
+                if not lora:
+                    self._lin_bwd(dkv, B * Ta, 2 * d, feats, featsT, d, self._kv_pair(self.flat_p, pre), self._kv_pair(self.flat_g, pre),
+                                  None, dx=d_feats, accumulate_dx=(l != dm.n_text_layer - 1), need_dx=d_feats is not None)
+                    self._colsum(dvc, B * Ta, d, G(f"{pre}.cross_attn.value.bias"))
+                else:  # the input of these two is the frozen encoder output: adapter gradients only, no dx
+                    self._lora_bwd(f"{pre}.cross_attn.key", S, "u_kc", dkc, feats, None, B * Ta, d, d)
+                    self._lora_bwd(f"{pre}.cross_attn.value", S, "u_vc", dvc, feats, None, B * Ta, d, d)
                 del dkv, dkc, dvc
                 dh2 = self._lin_bwd(dqc, M, d, S["h2"], None, d, P(f"{pre}.cross_attn.query.weight"), G(f"{pre}.cross_attn.query.weight"),
                                     G(f"{pre}.cross_attn.query.bias"))
+                if lora:
+                    self._lora_bwd(f"{pre}.cross_attn.query", S, "u_qc", dqc, S["h2"], dh2, M, d, d)
                 self._ln_bwd(S["x_b"], dh2, P(f"{pre}.cross_attn_ln.weight"), dx, True, G(f"{pre}.cross_attn_ln.weight"),
                              G(f"{pre}.cross_attn_ln.bias"), M, d)
                 self._self_attn_bwd(pre, S, dx, B, M, Mp, d)
                 saved[l] = None
                 self._reduce_segment(reducer, pre)
+            if lora:  # no embedding scatter, no head segment: adapter_layout ends with block 0
+                return
             _lib.check(L.wipa_embed_bwd(ptr(tok_in), ptr(dx), B, T, d, ptr(G("decoder.token_embedding.weight")),
                                         ptr(G("decoder.positional_embedding")), sptr(s)), "wipa_embed_bwd")
             if T < dm.n_text_ctx:
@@ -699,20 +860,23 @@ class DecoderTrainer:
     def _mlp_bwd(self, pre: str, S: Dict, dx: torch.Tensor, M: int, d: int) -> None:
         """the MLP half of block ``pre`` (decoder or encoder), x_next = x_c + u W2^T + b2: its parameter gradients, and dx += the
         gradient through mlp_ln"""
-        P, G = self.w, self.g
+        P, G = self.w, self._gw
         du = self._lin_bwd(dx, M, d, S["u"], None, 4 * d, P(f"{pre}.mlp2.weight"), G(f"{pre}.mlp2.weight"), G(f"{pre}.mlp2.bias"))
+        self._lora_bwd(f"{pre}.mlp2", S, "u_m2", dx, S["u"], du, M, 4 * d, d)
         dz = torch.empty_like(du)
         with on_stream() as s:
             _lib.check(self.L.wipa_gelu_bwd(ptr(S["z"]), ptr(du), ptr(dz), dz.numel(), sptr(s)), "wipa_gelu_bwd")
         dh3 = self._lin_bwd(dz, M, 4 * d, S["h3"], None, d, P(f"{pre}.mlp1.weight"), G(f"{pre}.mlp1.weight"), G(f"{pre}.mlp1.bias"))
+        self._lora_bwd(f"{pre}.mlp1", S, "u_m1", dz, S["h3"], dh3, M, d, 4 * d)
         self._ln_bwd(S["x_c"], dh3, P(f"{pre}.mlp_ln.weight"), dx, True, G(f"{pre}.mlp_ln.weight"), G(f"{pre}.mlp_ln.bias"), M, d)
 
     def _self_attn_bwd(self, pre: str, S: Dict, dx: torch.Tensor, B: int, M: int, Mp: int, d: int, split: bool = False) -> None:
         """the self-attention half of block ``pre`` (decoder or encoder), x_b = x_a + a Wo^T + bo: its parameter gradients, and
         dx += the gradient through attn_ln"""
-        P, G = self.w, self.g
+        P, G = self.w, self._gw
         dev = dx.device
         da = self._lin_bwd(dx, M, d, S["a"], None, d, P(f"{pre}.attn.out.weight"), G(f"{pre}.attn.out.weight"), G(f"{pre}.attn.out.bias"))
+        self._lora_bwd(f"{pre}.attn.out", S, "u_o", dx, S["a"], da, M, d, d)
         dq = torch.empty(M, d, dtype=torch.float32, device=dev)
         dk = torch.empty(M, d, dtype=torch.float32, device=dev)
         dv = torch.empty(M, d, dtype=torch.float32, device=dev)
@@ -724,6 +888,9 @@ class DecoderTrainer:
                       accumulate_dx=True)
         self._lin_bwd(dv, M, d, S["h1"], h1T, d, P(f"{pre}.attn.value.weight"), G(f"{pre}.attn.value.weight"),
                       G(f"{pre}.attn.value.bias"), dx=dh1, accumulate_dx=True)
+        self._lora_bwd(f"{pre}.attn.query", S, "u_q", dq, S["h1"], dh1, M, d, d)
+        self._lora_bwd(f"{pre}.attn.key", S, "u_k", dk, S["h1"], dh1, M, d, d)
+        self._lora_bwd(f"{pre}.attn.value", S, "u_v", dv, S["h1"], dh1, M, d, d)
         self._ln_bwd(S["x_a"], dh1, P(f"{pre}.attn_ln.weight"), dx, True, G(f"{pre}.attn_ln.weight"), G(f"{pre}.attn_ln.bias"), M, d)
 
     # ---- encoder: training forward (keeps activations) + backward -----------------------------
@@ -880,6 +1047,9 @@ class DecoderTrainer:
 
     def _loss_and_grads(self, audio_features: torch.Tensor, tokens: torch.Tensor, eot: int, group, ectx: Optional[Dict]):
         m, dm, L = self.model, self.model.dims, self.L
+        if self.lora is not None and getattr(m, "_adapter", None) is not None:
+            raise _lib.WipaError("DecoderTrainer: a step while the model has an adapter applied: its weights are base + adapter, and the "
+                                 "step would add the adapter a second time -- set_adapter(None) (or leave adapter_applied()) first")
         B, T1 = tokens.shape
         T = T1 - 1
         V = dm.n_vocab
@@ -913,6 +1083,7 @@ class DecoderTrainer:
         against under torch.enable_grad().  ``.grad`` is filled by ``loss.backward()``; apply_update() reads self.flat_g, so a
         custom training loop copies / accumulates the leaves' gradients there (value_and_grad in scripts/train_whisper_ipa.py)."""
         self._decoder_only("leaves")
+        self._no_lora("leaves")
         if self._leaves is None:
             self._leaves = {n: self.p(n).detach().requires_grad_(True) for n in self.names}
         return self._leaves
@@ -925,6 +1096,7 @@ class DecoderTrainer:
         self.flat_g (zeroed first: gradients accumulated there by loss_and_grads are lost) and returns clones of every decoder
         gradient as the leaves' .grad (one more copy of the decoder's size); it reduces over no process group."""
         self._decoder_only("differentiable_logits")
+        self._no_lora("differentiable_logits")
         if parallel.world()[1] != 1:
             raise _lib.WipaError("differentiable_logits is single-process (its backward runs without the data-parallel group); "
                                  "use DecoderTrainer.train_step / loss_and_grads(group=...) under torch.distributed")
@@ -954,7 +1126,8 @@ class DecoderTrainer:
             # encoder tensors moved: the packed encoder tables die with _invalidate() below, and whatever is a function of the
             # encoder weights (a FrozenFeatureCache, cached features) watches this count
             self.model._enc_generation += 1
-        self.model._invalidate()  # fused inference tables are rebuilt lazily from the updated weights
+        if self.lora is None:  # a LoRA step moves no tensor of the model
+            self.model._invalidate()  # fused inference tables are rebuilt lazily from the updated weights
         self.step_count += 1
 
     def train_step(self, mel: Optional[torch.Tensor], tokens: torch.Tensor, eot: int, group=None, clip_keys=None, n_frames=None):

@@ -302,6 +302,7 @@ class Whisper:
         """Matrices (and activations / KV caches) switch to ``dtype``; biases, LayerNorm and
         positional tables stay f32 (train_whisper_ipa.py:505, transcribe_single.py:13)."""
         dt_code(dtype)
+        self._no_adapter("set_dtype")
         self.dtype = dtype
         self._fp8 = {}  # fp8 codes belong to the bf16 configuration they were made for (quantize_weights again if wanted)
         self._fp8_enc = {}
@@ -315,6 +316,7 @@ class Whisper:
 
     def load_weights(self, flat: Dict[str, torch.Tensor], strict: bool = True):
         """``flat``: mlx_whisper key names (App. A.5 of SURVEY.md).  Conv weights [d,3,c_in]."""
+        self._no_adapter("load_weights")
         names = parameter_names(self.dims)
         missing = [n for n in names if n not in flat and n not in self._params]
         if strict and missing:
@@ -356,6 +358,7 @@ class Whisper:
         the encoder, the cross-K/V projection and the teacher-forced decoder -- both forms multiply by the same values."""
         if fmt != "fp8_e4m3":
             raise _lib.WipaError(f"quantize_weights: unknown format {fmt!r} (fp8_e4m3)")
+        self._no_adapter("quantize_weights")
         if self.dtype != torch.bfloat16:
             raise _lib.WipaError("quantize_weights: fp8 weights run with bf16 activations: call set_dtype(torch.bfloat16) first")
         if activations not in ("bf16", "fp8"):
@@ -385,6 +388,56 @@ class Whisper:
         self._fp8 = fp8
         self._fp8_enc = fp8_enc
         return self
+
+    # ---- low-rank adapters ------------------------------------------------------------------------
+    def set_adapter(self, adapter: Optional[Dict[str, torch.Tensor]], cfg=None):
+        """Run the model with a LoRA adapter (``lora.LoRAConfig`` ``cfg``; tensors named ``decoder.blocks.{l}.attn.query.lora_A`` ...)
+        merged into its weights: every targeted tensor of ``_params`` becomes ``base + s B A`` by one wipa_lora_merge (one rounding, in the
+        tensor's own dtype, f32 or bf16), so every inference path -- decode, transcribe, continuous, align -- runs the adapted model
+        at no extra cost.  The first application keeps a device copy of each targeted tensor; another adapter merges from those
+        bases again and ``set_adapter(None)`` copies them back bit for bit, so switching among adapters never drifts.  A model with
+        fp8 tables is refused.  While an adapter is applied the weights must not be replaced (load_weights / set_dtype /
+        quantize_weights are refused) and a LoRA trainer on this model refuses to step."""
+        from . import lora as lora_mod
+
+        bases = getattr(self, "_adapter_base", {})
+        if adapter is None:
+            with on_stream():
+                for n, b in bases.items():
+                    self._params[n].copy_(b)
+            self._adapter_base, self._adapter = {}, None
+            if bases:
+                self._invalidate()
+            return self
+        if self._fp8 or self._fp8_enc:
+            raise _lib.WipaError("set_adapter: a model with fp8 tables is not supported (the codes would not follow the merged weights): "
+                                 "apply the adapter to the bf16 model")
+        if self.dtype not in (torch.float32, torch.bfloat16):
+            raise _lib.WipaError(f"set_adapter: a model of dtype {self.dtype}: float32 or bfloat16")
+        if not isinstance(cfg, lora_mod.LoRAConfig):
+            raise _lib.WipaError("set_adapter: cfg must be the adapter's LoRAConfig")
+        lora_mod.check_adapter(self.dims, cfg, adapter)
+        L = _lib.lib()
+        with on_stream() as s:
+            for n, b in bases.items():  # tensors the previous adapter sat on and this one may not
+                self._params[n].copy_(b)
+            for wn in lora_mod.adapted_weights(adapter):
+                W = self._params[wn]
+                if wn not in bases:
+                    bases[wn] = W.clone()
+                pre = wn[: -len("weight")]
+                A = torch.as_tensor(adapter[pre + "lora_A"]).to(device=self.device, dtype=torch.float32).contiguous()
+                Bm = torch.as_tensor(adapter[pre + "lora_B"]).to(device=self.device, dtype=torch.float32).contiguous()
+                N, K = W.shape
+                _lib.check(L.wipa_lora_merge(ptr(W), W.stride(0), dt_code(W.dtype), ptr(bases[wn]), K, ptr(A), ptr(Bm), N, K, cfg.rank,
+                                             cfg.scale, sptr(s)), "wipa_lora_merge")
+        self._adapter_base, self._adapter = bases, cfg
+        self._invalidate()
+        return self
+
+    def _no_adapter(self, what: str) -> None:
+        if getattr(self, "_adapter", None) is not None:
+            raise _lib.WipaError(f"{what} while an adapter is applied: set_adapter(None) first (the kept base tensors would go stale)")
 
     def parameters(self) -> Dict:
         return _unflatten(self._params)
