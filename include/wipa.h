@@ -841,6 +841,26 @@ int wipa_decoder_prefill(const wipa_model_cfg* cfg, const void* const* w, void* 
  * continuous; continuous needs starts_dev; no_speech_dev needs rules; beam excludes sample, sample_rows, starts_dev and continuous;
  * wipa_decoder_prefill_ex takes none of starts_dev, continuous, prompted, sample_rows, no_speech_dev (the prompt pass of rows with
  * their own prompts is wipa_decoder_prefill_ragged, that of an admitted clip belongs to wipa_decoder_admit_rows_prompted). */
+/* An ADAPTER BANK on a decode call (wipa_decode_call.bank; csrc/lora_bank.hip, "adapter banks" at the end of this header): n unmerged
+ * adapters of one rank on one set of sites, a different one per row.  Behind every targeted linear of a step and of the prompt pass
+ * stands one wipa_lora_bank_apply (attn.query | key | value share one call over the 3d columns; the term of a residual site -- attn.out,
+ * cross_attn.out, mlp2 -- is added into split-K slab 0 and folded in by the next wipa_add_slabs_layernorm; mlp1's GEMM runs without its
+ * GELU and the apply call performs it).  With a bank the cross block takes its separate launches (LayerNorm, query GEMM, attention, out
+ * GEMM) on both cross-attention forms; the logits projection is untouched.  The terms of cross_attn.key / cross_attn.value are added to
+ * the CACHED cross K / V by wipa_decoder_adapt_cross; on the absorbed form (cfg.dec_cross_absorbed) a bank that targets them is refused.
+ * Site s of a block, in the order its forward runs them: 0 attn.query, 1 attn.key, 2 attn.value, 3 attn.out, 4 cross_attn.query,
+ * 5 cross_attn.key, 6 cross_attn.value, 7 cross_attn.out, 8 mlp1, 9 mlp2.
+ * The struct and the two pointer arrays are HOST memory that the caller keeps alive and unchanged while graphs keyed on it may replay;
+ * wipa_dec_layout and the state's scratch do not change (the kernels need no workspace). */
+#define WIPA_BANK_SITES 10
+typedef struct wipa_adapter_bank {
+    int32_t n, rank;          /* adapters (1..64), their common rank (a multiple of 4 in 4..64) */
+    uint32_t site_mask;       /* bit s: site s carries adapters */
+    const float* const* A;    /* host [n_text_layer][WIPA_BANK_SITES] of device pointers: A [n, rank, in] f32; NULL at the other sites */
+    const float* const* B;    /* likewise: B [n, out, rank] f32 */
+    const float* gain;        /* device f32 [n]: alpha / rank of each adapter */
+    const int32_t* ids_dev;   /* device int32 [B]: the adapter of every row, -1 for none; read by the replayed kernels */
+} wipa_adapter_bank;
 typedef struct wipa_decode_call {
     /* prompt columns (with starts_dev: the common prompt width P, 1..n_text_ctx; continuous: 1..4 initial tokens per clip; the prompt pass:
      * 1..4) and the end-of-text id */
@@ -900,12 +920,30 @@ typedef struct wipa_decode_call {
     void* beam;
     size_t beam_bytes;
     int32_t beam_max_candidates;
+    /* An adapter bank (above): every row decodes under the adapter bank->ids_dev names for it.  NULL: the call of a model without a bank,
+     * launch for launch.  The bank's address, ids_dev's address and (n, rank, site_mask) are part of the step graph's and the prefill
+     * graph's key; the ids are not: rewriting them replays the same graph.  Rows with their own prompts take wipa_decoder_prefill_ragged_bank, a
+     * prompted admission wipa_decoder_admit_rows_prompted_bank; behind an unprompted admission the caller writes the slot's id and calls
+     * wipa_decoder_adapt_cross.  Refused by name, nothing enqueued: with beam, on fp8 decoder tables, with WIPA_DECODE_FUSED=1 or
+     * WIPA_DECODE_TAIL=0, and a bank on cross_attn.key / cross_attn.value with cfg.dec_cross_absorbed. */
+    const wipa_adapter_bank* bank;
 } wipa_decode_call;
 /* wipa_decoder_run / wipa_decoder_prefill for a wipa_decode_call; those two are these with a call of n_init, eot and the masks. */
 int wipa_decoder_run_ex(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B,
                         const wipa_decode_call* call, int n_steps, int use_graph, wipa_stream_t s);
 int wipa_decoder_prefill_ex(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
                             const wipa_decode_call* call, int use_graph, wipa_stream_t s);
+/* Measurement / test aid: the number of captured decode graphs (steps and prompt passes) this process holds.  Two calls that differ
+ * only in what a device array of their key holds (the sampling record, the starts, an adapter bank's ids) leave it unchanged. */
+int wipa_decoder_graph_count(void);
+/* The cross_attn.key / cross_attn.value terms of an adapter bank, added to the CACHED cross K / V behind wipa_decoder_set_audio (all
+ * clips: slots_host NULL, n_rows = B / cfg.dec_n_group, features as wipa_decoder_set_audio took them) or wipa_decoder_admit_rows (the
+ * n_rows listed slots; features [n_rows, n_audio_ctx, d] T in that order): K[clip] += 64^-0.25 gain[id] (xa A_k[id]^T) B_k[id]^T and
+ * V[clip] += gain[id] (xa A_v[id]^T) B_v[id]^T in the layout [clip][K|V][H][Ta][64], one wipa_lora_bank_apply per layer (per layer and
+ * slot with slots_host) with rows_per_id = n_audio_ctx.  A clip's id is bank->ids_dev[clip * cfg.dec_n_group]: that of its first row.
+ * A bank without those two sites enqueues nothing.  Refused: cfg.dec_cross_absorbed with such a bank, fp8 decoder tables. */
+int wipa_decoder_adapt_cross(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, const void* features,
+                             int n_rows, const int32_t* slots_host, const wipa_adapter_bank* bank, wipa_stream_t s);
 /* Beam search (upstream's BeamSearchDecoder + MaximumLikelihoodRanker; DecodingOptions.beam_size / patience / length_penalty).  The B rows
  * of a call are B / n_group clips x n_group beams, clip-major, with cfg.dec_n_group = n_group = beam_size (1..16; 1 is one row per clip).
  * Per step and clip, every beam offers the n_group + 1 best columns of its FILTERED row (the row the greedy / rules tails reduce;
@@ -970,6 +1008,14 @@ int wipa_decoder_prefill_ragged(const wipa_model_cfg* cfg, const void* const* we
                                 int sot_col, int eot, const float* mask_first, const float* mask_always, int use_graph,
                                 const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, void* workspace,
                                 size_t workspace_bytes, wipa_stream_t s);
+/* wipa_decoder_prefill_ragged with an adapter bank (wipa_decode_call.bank; NULL: that call): row b's prompt columns run under the adapter
+ * bank->ids_dev[b], one wipa_lora_bank_apply behind every targeted GEMM of the batched pass (rows_per_id = P; the residual sites add into
+ * the f32 stream).  On the absorbed form the per-layer K / V workspace is projected without adapters: a bank on cross_attn.key / .value is
+ * refused there as everywhere.  The steps behind it are wipa_decoder_run_ex with the same bank and starts_dev. */
+int wipa_decoder_prefill_ragged_bank(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int P,
+                                int sot_col, int eot, const float* mask_first, const float* mask_always, int use_graph,
+                                const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, void* workspace,
+                                size_t workspace_bytes, const wipa_adapter_bank* bank, wipa_stream_t s);
 int wipa_decoder_begin_ragged(const wipa_model_cfg* cfg, void* state, size_t state_bytes, int B, const int32_t* tokens_host,
                               const int32_t* starts_host, int P, int32_t* starts_dev, wipa_stream_t s);
 /* Continuous batching: the B rows of a state are SLOTS.  A clip is admitted into a slot at the column the state
@@ -1035,6 +1081,15 @@ int wipa_decoder_admit_rows_prompted(const wipa_model_cfg* cfg, const void* cons
                                      int n_init, const int32_t* limits_host, const int32_t* prompt_lens_host,
                                      const int32_t* prompt_tokens_host, int W, int32_t* starts_dev, void* sample,
                                      const uint32_t* streams_host, void* workspace, size_t workspace_bytes, wipa_stream_t s);
+/* wipa_decoder_admit_rows_prompted with an adapter bank: ids_host int32 [n_rows] (HOST) names the admitted clips' adapters (-1: none).
+ * The call writes bank->ids_dev[slot] with a plain copy before the slot's first step, adds the clip's cross K / V terms to the cached
+ * K / V behind its projection (wipa_decoder_adapt_cross) and runs the prompt pass of the admitted rows under their adapters. */
+int wipa_decoder_admit_rows_prompted_bank(const wipa_model_cfg* cfg, const void* const* weights, void* state, size_t state_bytes, int B, int n_rows,
+                                     const int32_t* slots_host, const void* const* features_host, const int32_t* initial_tokens_host,
+                                     int n_init, const int32_t* limits_host, const int32_t* prompt_lens_host,
+                                     const int32_t* prompt_tokens_host, int W, int32_t* starts_dev, void* sample,
+                                     const uint32_t* streams_host, void* workspace, size_t workspace_bytes, const wipa_adapter_bank* bank,
+                                          const int32_t* ids_host, wipa_stream_t s);
 /* drop the cached step graphs that reference this state blob (call before freeing it). */
 int wipa_decoder_release(void* state);
 
@@ -1172,6 +1227,51 @@ int wipa_lora_bwd(const float* dy, int64_t ldy, const float* x, int64_t ldx, con
  * elements): the sum over j ascending as an fmaf chain from zero, one fmaf with the base, one rounding at the end.  W may be base. */
 int wipa_lora_merge(void* W, int64_t ldw, int dtype, const void* base, int64_t ld_base, const float* A, const float* Bm, int N, int K,
                     int r, float s, wipa_stream_t stream);
+
+/* ------------------------------------------------------------------ adapter banks (csrc/lora_bank.hip; no reference counterpart)
+ * n adapters (1..64) of one rank r and one set of sites, kept UNMERGED and applied per row behind a linear whose base output is in place:
+ *   out[m, :] = cast(act(float(y[m, :]) + c gain[id] (x[m, :] A[id]^T) B[id]^T)),   id = ids[(m / rows_per_id) * ids_stride]
+ * A [n, r, K] and B [n, N, r] are the site's adapters stacked, contiguous f32; gain [n] f32 holds alpha / r of each adapter; ids is an
+ * int32 DEVICE array with one entry per rows_per_id rows, read by the kernel -- a captured graph serves any assignment.  A row whose id is
+ * -1 gets act alone, and with act none its bytes are left alone; an id outside -1..n-1 is refused when ids_host (the same array in HOST
+ * memory, optional) shows it, and treated as -1 by the kernel.  x [M, K] has x_dtype (f32 or bf16, row stride ldx); y and out have
+ * y_dtype (f32 or x_dtype) and share one addressing, that of wipa_gemm_desc: element (m, n) lives at
+ *   c_offset + (*c_offset_dev) + (m / rg_in) * rg_stride + (m % rg_in) * ld + (n / cg_in) * cg_stride + (n % cg_in)
+ * (rg_in = 0: M, cg_in = 0: N: plain rows of ld elements), so the term lands where the base GEMM wrote -- the self K / V cache at the
+ * current position, packed q|k|v rows, the cached cross K / V layout [clip][K|V][H][Ta][64], split-K slab 0 of a residual GEMM.  out may
+ * be y.  act: 0 none, 1 the gelu(erf) of wipa_gemm's epilogue (a linear whose GEMM ran without it).  Accumulation is f32, exact f32
+ * products; one rounding to y_dtype at the end.
+ * Column segments: the N columns are n_seg (1..3) segments of N / n_seg columns that share x (a layer's query | key | value), segment s
+ * with its own A[s], B[s] ([n, N / n_seg, r]) and column scale col_scale[s] (the c of the linear: 64^-0.25 on query and key columns);
+ * A[s] == B[s] == NULL: the segment carries no adapter.
+ * One launch.  rows_per_id < 16 and M <= 1024 (decode rows, the four-row prompt pass): one workgroup per row and 512 columns, u = A[id] x
+ * recomputed per column chunk.  Everything else (prompt passes, the cross K / V projection with rows_per_id = Ta): tiles of 16 rows of
+ * ONE id on the exact f32 MFMA; a tile never straddles two ids, a segment length that is no multiple of 16 is served.  No float atomics,
+ * one writer per output element, the same bits on two calls, and a row's bits do not depend on any other row's id.
+ * r a multiple of 4 in 4..64, K and N / n_seg multiples of 4; ld, ldx, rg_stride, cg_stride, cg_in, c_offset and *c_offset_dev multiples
+ * of 4; x, y, out, A[s], B[s] 16-byte aligned.  Anything else is refused with a message that names the argument. */
+#define WIPA_LORA_BANK_MAX_ADAPTERS 64
+#define WIPA_LORA_BANK_MAX_SEG 3
+typedef struct wipa_lora_bank_desc {
+    const void* x;
+    const void* y;
+    void* out;
+    const float* A[WIPA_LORA_BANK_MAX_SEG];
+    const float* B[WIPA_LORA_BANK_MAX_SEG];
+    const float* gain;
+    const int32_t* ids;      /* device */
+    const int32_t* ids_host; /* host, optional: checked before the launch */
+    const int64_t* c_offset_dev;
+    int64_t ldx, ld, rg_stride, cg_stride, c_offset;
+    float col_scale[WIPA_LORA_BANK_MAX_SEG];
+    int32_t M, K, N, r, n;
+    int32_t rows_per_id, n_seg;
+    int32_t ids_stride; /* row group g reads ids[g * ids_stride]; 0: 1 */
+    int32_t x_dtype, y_dtype;
+    int32_t rg_in, cg_in;
+    int32_t act; /* 0 none, 1 gelu(erf) */
+} wipa_lora_bank_desc;
+int wipa_lora_bank_apply(const wipa_lora_bank_desc* d, wipa_stream_t s);
 
 #ifdef __cplusplus
 }

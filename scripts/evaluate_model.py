@@ -73,6 +73,37 @@ def load_checkpoint_model(checkpoint_path: str, base_model: str = "mlx-community
     return model
 
 
+def parse_adapter_bank(spec: str) -> Dict[str, str]:
+    """``--adapter-bank lang=DIR[,lang=DIR...]`` -> {language: adapter directory}, in the order given (the order of the bank's ids)"""
+    out: Dict[str, str] = {}
+    for part in [p for p in spec.split(",") if p.strip()]:
+        lang, sep, directory = part.partition("=")
+        if not sep or not lang.strip() or not directory.strip():
+            raise ValueError(f"--adapter-bank: {part!r} is not lang=DIR")
+        if lang.strip() in out:
+            raise ValueError(f"--adapter-bank: language {lang.strip()!r} is given twice")
+        out[lang.strip()] = directory.strip()
+    if not out:
+        raise ValueError("--adapter-bank: no lang=DIR pair")
+    return out
+
+
+def sample_adapters(samples: List[Dict], languages) -> List[Optional[str]]:
+    """every sample's adapter: its language field (``locale``, else ``language``) where the bank holds that language, else None (the base)"""
+    names = set(languages)
+    return [(s.get("locale") or s.get("language")) if (s.get("locale") or s.get("language")) in names else None for s in samples]
+
+
+def set_adapter_bank_from(model, bank_dirs: Dict[str, str]):
+    """load the adapters of ``bank_dirs`` and keep them beside the base weights, unmerged (Whisper.set_adapter_bank)"""
+    from whisper_ipa_amd.lora import AdapterBank, load_adapter
+
+    loaded = {lang: load_adapter(directory)[:2] for lang, directory in bank_dirs.items()}
+    model.set_adapter_bank(AdapterBank(model.dims, loaded))
+    print(f"✓ adapter bank: {len(loaded)} adapters ({', '.join(loaded)}), rank {model.adapter_bank.rank}, sites {', '.join(model.adapter_bank.sites)}")
+    return model
+
+
 INGEST_MODES = ("device", "host")
 
 
@@ -136,7 +167,7 @@ DECODE_MODES = ("lockstep", "continuous")
 
 
 def transcribe_clips_continuous(model, audio_paths: List[str], options: DecodingOptions, slots: int = 64, progress=None,
-                                ingest: str = "device") -> List[str]:
+                                ingest: str = "device", row_adapters: Optional[List[Optional[str]]] = None) -> List[str]:
     """``transcribe_clips`` through whisper_ipa_amd.decode_continuous: the clips' log-mels, ``slots`` files at a time, then ONE
     continuous decode of all of them -- ``slots`` rows, and a row whose clip has reached EOT takes the next pending clip (the encoder runs
     in chunks of ``slots`` clips ahead of need).  One text per path, "" where the file could not be read."""
@@ -155,7 +186,8 @@ def transcribe_clips_continuous(model, audio_paths: List[str], options: Decoding
         if progress is not None:
             progress(min(b + slots, len(audio_paths)))
     if mels:
-        for i, r in zip(where, decode_continuous(model, torch.cat(mels), options, slots=slots)):
+        adapters = {"row_adapters": [row_adapters[i] for i in where]} if row_adapters is not None else {}  # per clip that could be read
+        for i, r in zip(where, decode_continuous(model, torch.cat(mels), options, slots=slots, **adapters)):
             texts[i] = r.text.strip()
     return texts
 
@@ -212,7 +244,9 @@ def evaluate_model(model_path: str, test_data_path: str, num_samples: Optional[i
                    batch_size: int = 64, passes_in_flight: int = 4, ingest: str = "device", scoring: str = "device",
                    base_decode: str = "decode", seed: Optional[int] = None, condition_on_previous_text: bool = False,
                    initial_prompt: Optional[str] = None, decode: str = "lockstep", beams: Optional[dict] = None,
-                   audio_ctx: Optional[int] = None) -> Dict:
+                   audio_ctx: Optional[int] = None, adapter_bank: Optional[Dict[str, str]] = None) -> Dict:
+    """``adapter_bank`` ({language: adapter directory}): the base model with those adapters unmerged, every sample decoded under the
+    adapter of its language field in ONE mixed continuous decode (samples without a match on the base)"""
     if decode not in DECODE_MODES:
         raise ValueError(f"decode must be one of {DECODE_MODES}, got {decode!r}")
     rank, world_size = parallel.world()
@@ -229,7 +263,11 @@ def evaluate_model(model_path: str, test_data_path: str, num_samples: Optional[i
     else:
         say(f"Evaluating on all {len(test_data)} samples")
     say(f"\nModel: {model_path}")
-    if is_checkpoint:
+    if adapter_bank is not None:
+        model = load_model(base_model, audio_ctx=audio_ctx)  # the base architecture in fp32, as the checkpoint leg loads it
+        model.set_dtype(torch.float32)
+        set_adapter_bank_from(model, adapter_bank)
+    elif is_checkpoint:
         say("\nLoading checkpoint...")
         model = load_checkpoint_model(model_path, base_model=base_model, audio_ctx=audio_ctx)
     else:
@@ -252,6 +290,12 @@ def evaluate_model(model_path: str, test_data_path: str, num_samples: Optional[i
                                      condition_on_previous_text=condition_on_previous_text, initial_prompt=initial_prompt,
                                      schedule="continuous" if decode == "continuous" else "rounds", beams=beams,
                                      progress=lambda n: say(f"  {n}/{len(mine)} clips on rank 0", flush=True))
+    elif adapter_bank is not None:  # per-row adapters ride the continuous decode: one mixed-language stream through all slots
+        picked = sample_adapters(mine, adapter_bank)
+        say(f"  adapters: {sum(p is not None for p in picked)} of {len(mine)} samples match a language of the bank, the rest decode on the base")
+        local_hyp = transcribe_clips_continuous(model, [s["audio_path"] for s in mine], options, slots=batch_size, ingest=ingest,
+                                                row_adapters=picked,
+                                                progress=lambda n: say(f"  {n}/{len(mine)} clips read on rank 0", flush=True))
     elif decode == "continuous":
         local_hyp = transcribe_clips_continuous(model, [s["audio_path"] for s in mine], options, slots=batch_size, ingest=ingest,
                                                 progress=lambda n: say(f"  {n}/{len(mine)} clips read on rank 0", flush=True))
@@ -369,7 +413,14 @@ def main(argv=None) -> Dict:
     ap.add_argument("--adapter", type=str, default=None, metavar="DIR",
                     help="score the base model with the LoRA adapter of DIR (adapter_model.safetensors + adapter_config.json, as a "
                          "--lora-rank training run writes them into its checkpoint directories) in place of --checkpoint")
+    ap.add_argument("--adapter-bank", type=str, default=None, metavar="lang=DIR[,lang=DIR...]",
+                    help="score the base model with one LoRA adapter per language kept unmerged (Whisper.set_adapter_bank): every sample "
+                         "decodes under the adapter of its language field (locale), samples without a match on the base, all in one "
+                         "mixed continuous decode; takes the place of the checkpoint leg")
     args = ap.parse_args(argv)
+    bank_dirs = parse_adapter_bank(args.adapter_bank) if args.adapter_bank is not None else None
+    if bank_dirs is not None and args.adapter is not None:
+        ap.error("--adapter-bank and --adapter cannot be given together")
     if args.adapter is not None:
         args.checkpoint = args.adapter  # load_checkpoint_model applies the adapter files it finds there
     from whisper_ipa_amd.tokenizer import get_tokenizer, require_real_vocabulary
@@ -402,7 +453,7 @@ def main(argv=None) -> Dict:
     trained_results = evaluate_model(args.checkpoint, args.test_data, num_samples, model_name="Trained Checkpoint",
                                      is_checkpoint=True, n_mels=args.n_mels, base_model=args.base_model, batch_size=args.batch_size,
                                      passes_in_flight=args.passes_in_flight, ingest=args.ingest, scoring=args.scoring, decode=args.decode,
-                                     audio_ctx=audio_ctx)
+                                     audio_ctx=audio_ctx, adapter_bank=bank_dirs)
     if rank == 0:
         if base_results:
             compare_models(base_results, trained_results)

@@ -23,6 +23,7 @@ DEC_GLOBAL, DEC_PER_LAYER, DEC_FP8_PER_LAYER = 4, 20, 6
 GEMM_DISPATCH = ("tile128", "tile256", "tile384", "tile384n", "tile256p", "skinny", "skinny_fp8", "skinny_ln", "kmajor", "split_k",
                  "tile_fp8", "tile_fp8_384")
 ENC_FP8_PER_LAYER = 8
+LORA_BANK_MAX_ADAPTERS, LORA_BANK_MAX_SEG = 64, 3  # WIPA_LORA_BANK_MAX_ADAPTERS, WIPA_LORA_BANK_MAX_SEG
 DEC_ABSORBED_PER_LAYER = 1
 
 c_void_p, c_int, c_int64, c_size_t, c_float = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_float
@@ -103,12 +104,30 @@ class DecodeRules(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("timestamp_begin", "no_timestamps", "max_initial_timestamp_index")]
 
 
+BANK_SITES = 10  # WIPA_BANK_SITES
+
+
+class AdapterBankC(C.Structure):
+    """wipa_adapter_bank"""
+    _fields_ = [("n", C.c_int32), ("rank", C.c_int32), ("site_mask", C.c_uint32), ("A", C.POINTER(c_void_p)), ("B", C.POINTER(c_void_p)),
+                ("gain", c_void_p), ("ids_dev", c_void_p)]
+
+
 class DecodeCall(C.Structure):
     """wipa_decode_call: what wipa_decoder_run_ex / wipa_decoder_prefill_ex take; every optional field is 0 / None for "not used" """
     _fields_ = [("n_init", C.c_int32), ("eot", C.c_int32), ("mask_first", c_void_p), ("mask_always", c_void_p),
                 ("rules", C.POINTER(DecodeRules)), ("sample", c_void_p), ("sample_rows", c_void_p), ("starts_dev", c_void_p),
                 ("continuous", C.c_int32), ("prompted", C.c_int32), ("no_speech_dev", c_void_p), ("no_speech_token", C.c_int32),
-                ("beam", c_void_p), ("beam_bytes", c_size_t), ("beam_max_candidates", C.c_int32)]
+                ("beam", c_void_p), ("beam_bytes", c_size_t), ("beam_max_candidates", C.c_int32), ("bank", C.POINTER(AdapterBankC))]
+
+
+class LoraBankDesc(C.Structure):
+    """wipa_lora_bank_desc"""
+    _fields_ = [("x", c_void_p), ("y", c_void_p), ("out", c_void_p), ("A", c_void_p * LORA_BANK_MAX_SEG), ("B", c_void_p * LORA_BANK_MAX_SEG),
+                ("gain", c_void_p), ("ids", c_void_p), ("ids_host", C.POINTER(C.c_int32)), ("c_offset_dev", c_void_p),
+                ("ldx", c_int64), ("ld", c_int64), ("rg_stride", c_int64), ("cg_stride", c_int64), ("c_offset", c_int64),
+                ("col_scale", c_float * LORA_BANK_MAX_SEG)] + [(n, C.c_int32) for n in (
+                    "M", "K", "N", "r", "n", "rows_per_id", "n_seg", "ids_stride", "x_dtype", "y_dtype", "rg_in", "cg_in", "act")]
 
 
 class DecLayout(C.Structure):
@@ -227,6 +246,9 @@ SIGNATURES = {
                                      c_void_p]),
     "wipa_decoder_run_ex": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, _P(DecodeCall), c_int, c_int, c_void_p]),
     "wipa_decoder_prefill_ex": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, _P(DecodeCall), c_int, c_void_p]),
+    "wipa_decoder_graph_count": (c_int, []),
+    "wipa_decoder_adapt_cross": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_void_p, c_int, _P(C.c_int32), _P(AdapterBankC),
+                                         c_void_p]),
     "wipa_embed_layernorm_ragged": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                             c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "wipa_step_embed_ragged": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
@@ -247,6 +269,8 @@ SIGNATURES = {
     "wipa_decoder_prompt_workspace_bytes": (c_size_t, [_P(ModelCfg), c_int, c_int]),
     "wipa_decoder_prefill_ragged": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                             _P(DecodeRules), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wipa_decoder_prefill_ragged_bank": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                            _P(DecodeRules), c_void_p, c_void_p, c_void_p, c_size_t, _P(AdapterBankC), c_void_p]),
     "wipa_decoder_begin_ragged": (c_int, [_P(ModelCfg), c_void_p, c_size_t, c_int, _P(C.c_int32), _P(C.c_int32), c_int, c_void_p, c_void_p]),
     "wipa_sample_rows_bytes": (c_size_t, [c_int]),
     "wipa_sample_rows_fill": (c_int, [c_void_p, c_size_t, C.c_uint64, c_int]),
@@ -260,6 +284,9 @@ SIGNATURES = {
     "wipa_decoder_admit_rows_prompted": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, _P(C.c_int32), _P(c_void_p),
                                                  _P(C.c_int32), c_int, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), c_int, c_void_p, c_void_p,
                                                  _P(C.c_uint32), c_void_p, c_size_t, c_void_p]),
+    "wipa_decoder_admit_rows_prompted_bank": (c_int, [_P(ModelCfg), _P(c_void_p), c_void_p, c_size_t, c_int, c_int, _P(C.c_int32), _P(c_void_p),
+                                                 _P(C.c_int32), c_int, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), c_int, c_void_p, c_void_p,
+                                                 _P(C.c_uint32), c_void_p, c_size_t, _P(AdapterBankC), _P(C.c_int32), c_void_p]),
     "wipa_decode_cross_attn_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "wipa_decode_cross_attn_grouped": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "wipa_cross_absorbed_attention_grouped": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
@@ -297,6 +324,7 @@ SIGNATURES = {
     "wipa_lora_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                               c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
     "wipa_lora_merge": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
+    "wipa_lora_bank_apply": (c_int, [_P(LoraBankDesc), c_void_p]),
 }
 
 _lib = None

@@ -41,8 +41,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .decoding import (DecoderState, DecodingOptions, DecodingResult, Sampling, _mask, _suppress_lists, compression_ratio, decode_call,
-                       detect_language, timestamp_rules)
+from .decoding import (DecoderState, DecodingOptions, DecodingResult, Sampling, _bank_of, _mask, _suppress_lists, compression_ratio,
+                       decode_call, detect_language, timestamp_rules)
 from .runtime import on_stream, ptr, sptr, stream_id
 from .tokenizer import get_tokenizer
 
@@ -254,7 +254,7 @@ class DeviceStepper:
     def __init__(self, model, slots: int, features, initial, n_init: int, limits: Sequence[int], eot: int,
                  suppress_always: Sequence[int], suppress_first: Sequence[int], sample: Optional[Sampling], s, use_graph: bool = True,
                  rules: Optional["_lib.DecodeRules"] = None, no_speech_token: Optional[int] = None, row_seed: Optional[int] = None,
-                 draws=None, prompts=None, prompt_room: Optional[int] = None):
+                 draws=None, prompts=None, prompt_room: Optional[int] = None, row_ids=None):
         """``rules``: the timestamp rules (wipa_decode_call.rules; None: the plain continuous tails).  With them and
         ``no_speech_token`` the step's tail leaves every row's no-speech probability in ``self.no_speech``.
         ``row_seed``: a TEMPERATURE PER ROW (wipa_decode_call.sample_rows; ``sample`` is then None): the state's sampling record
@@ -263,7 +263,11 @@ class DeviceStepper:
         ``prompt_room`` (None: no prompts, the calls and the [2][B] starts buffer of the unprompted stepper): a PROMPTED stepper -- the
         state is opened at that column (wipa_decoder_seek), admissions go through wipa_decoder_admit_rows_prompted with the clips' prompt
         columns (``prompts(clip)`` or the fifth element of an admitted tuple: [sot_prev] + history, empty for none), the steps end in
-        the prompted tails (wipa_decode_call.prompted), on a [3][B] starts buffer of its own"""
+        the prompted tails (wipa_decode_call.prompted), on a [3][B] starts buffer of its own.
+        ``row_ids`` (clip -> an id of the model's adapter bank, -1 for none): the steps carry the bank (wipa_decode_call.bank); an admission
+        writes the slot's id with a plain device copy and adds the clip's cross K / V terms (wipa_decoder_adapt_cross) before the slot's
+        first step; a prompted admission does all of that itself (wipa_decoder_admit_rows_prompted_bank) and runs the prompt pass of the
+        admitted rows under their adapters."""
         self.L = _lib.lib()
         self.model, self.B, self.s, self.eot, self.use_graph = model, int(slots), s, int(eot), use_graph
         self.features = features  # clip -> device tensor [n_audio_ctx, d] in the model's dtype, contiguous
@@ -275,6 +279,7 @@ class DeviceStepper:
         if row_seed is not None and sample is not None:
             raise ValueError("decode_continuous: a temperature per row takes the place of the single-temperature sampling record")
         self.row_seed, self.draws = row_seed, draws
+        self.row_ids = row_ids
         self.prompts, self.prompt_room = prompts, (int(prompt_room) if prompt_room is not None else None)
         if self.prompt_room is not None and not 0 <= self.prompt_room < model.dims.n_text_ctx - 1:
             raise ValueError(f"decode_continuous: prompt_room = {prompt_room} outside 0 .. n_text_ctx - 2")
@@ -318,11 +323,12 @@ class DeviceStepper:
         self.out_no_speech = torch.full((max(n, 1),), float("nan"), dtype=torch.float32, device=model.device)
         self.pos = 0
         self._keep = []  # what enqueued work reads
+        self.bank = _bank_of(model, st, [-1] * self.B) if row_ids is not None else None  # every slot on the base until a clip is admitted
         self._begin()
         # every run of this stepper makes the same call: its buffers are one per state
         self.call = decode_call(self.n_init, self.eot, self.m_first, self.m_always, rules, self.rec, self.starts, continuous=True,
                                 prompted=self.prompt_room is not None, sample_rows=self.rows, no_speech=self.no_speech,
-                                no_speech_token=self.no_speech_token)
+                                no_speech_token=self.no_speech_token, bank=self.bank)
 
     def _begin(self):
         L, pk, st = self.L, self.pk, self.st
@@ -366,6 +372,11 @@ class DeviceStepper:
             flat = [int(v) & 0xFFFFFFFF for _, clip in pairs for v in (own[clip] if own is not None else (clip, 0))]
             streams = (C.c_uint32 * (2 * n))(*flat)
         pk, st = self.pk, self.st
+        ids = None
+        if self.bank is not None:
+            ids = [int(self.row_ids(clip)) for _, clip in pairs]
+            if any(not -1 <= i < self.bank.n for i in ids):
+                raise _lib.WipaError(f"row_adapters: ids {ids} outside -1 .. {self.bank.n - 1}")
         if self.prompt_room is not None:
             W = max(len(r) for r in prompt_rows)
             lens = (C.c_int32 * n)(*[len(r) for r in prompt_rows])
@@ -373,16 +384,25 @@ class DeviceStepper:
             nbytes = int(self.L.wipa_decoder_admit_prompted_workspace_bytes(C.byref(pk["cfg"]), n, W))
             ws = torch.empty(nbytes, dtype=torch.uint8, device=self.model.device)
             self._keep.append(ws)
-            _lib.check(self.L.wipa_decoder_admit_rows_prompted(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), self.B, n, slots,
-                                                               fptr, init, self.n_init, lim, lens, flat, W, ptr(self.starts),
-                                                               ptr(self.rec) if self.rec is not None else None, streams, ptr(ws), nbytes,
-                                                               sptr(self.s)), "wipa_decoder_admit_rows_prompted")
+            args = (C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), self.B, n, slots, fptr, init, self.n_init, lim, lens, flat, W,
+                    ptr(self.starts), ptr(self.rec) if self.rec is not None else None, streams, ptr(ws), nbytes)
+            if self.bank is None:
+                _lib.check(self.L.wipa_decoder_admit_rows_prompted(*args, sptr(self.s)), "wipa_decoder_admit_rows_prompted")
+            else:  # the slots' ids, the clips' cross K / V terms and the prompt pass under the adapters: one call
+                _lib.check(self.L.wipa_decoder_admit_rows_prompted_bank(*args, C.byref(self.bank), (C.c_int32 * n)(*ids), sptr(self.s)),
+                           "wipa_decoder_admit_rows_prompted_bank")
         else:
             if any(prompt_rows):
                 raise ValueError("decode_continuous: a clip came with a prompt, but the stepper was not built for prompts (prompt_room)")
             _lib.check(self.L.wipa_decoder_admit_rows(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), self.B, n, slots, fptr,
                                                       init, self.n_init, lim, ptr(self.starts), ptr(self.rec) if self.rec is not None else None,
                                                       streams, sptr(self.s)), "wipa_decoder_admit_rows")
+        if self.bank is not None and self.prompt_room is None:  # the slots' ids, then the clips' cross K / V terms behind the projection
+            st._bank_ids[torch.tensor([slot for slot, _ in pairs], device=st._bank_ids.device)] = torch.tensor(ids, dtype=torch.int32, device=st._bank_ids.device)
+            for (slot, _), f in zip(pairs, feats):
+                one = (C.c_int32 * 1)(slot)
+                _lib.check(self.L.wipa_decoder_adapt_cross(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), self.B, ptr(f), 1, one,
+                                                           C.byref(self.bank), sptr(self.s)), "wipa_decoder_adapt_cross")
         if self.rows is not None:  # the admitted slots' entries of the row record, in stream order behind the admission
             draws = [d if d is not None else (0.0, 0, (slot, 0)) for d, (slot, _) in zip(given, pairs)]
             flat = (C.c_uint32 * (2 * n))(*[int(v) & 0xFFFFFFFF for _, _, stream in draws for v in stream])
@@ -587,7 +607,7 @@ def decode_continuous(model, mels_or_features: torch.Tensor, options: DecodingOp
                       slots: int = 64, sample_lens: Optional[Sequence[int]] = None, check_every: int = 8,
                       column_limit: Optional[int] = None, stats_out: Optional[list] = None, temperatures: Optional[Sequence[float]] = None,
                       attempts: Optional[Sequence[int]] = None, prompts: Optional[Sequence[Sequence[int]]] = None,
-                      prompt_room: Optional[int] = None) -> List[DecodingResult]:
+                      prompt_room: Optional[int] = None, row_adapters: Optional[Sequence[Optional[str]]] = None) -> List[DecodingResult]:
     """``decode`` for a stream of clips through ``slots`` rows with refill: mels [N, 3000, n_mels] or encoded features [N, 1500, d];
     results in input order.  ``sample_lens``: the tokens clip i may generate (default ``options.sample_len`` or n_text_ctx // 2 for
     every clip).  Served: greedy, and ``temperature > 0`` with ``seed`` -- clip i draws from ``options.sample_streams[i]`` or from
@@ -607,7 +627,19 @@ def decode_continuous(model, mels_or_features: torch.Tensor, options: DecodingOp
     ``column_limit``.  So a full 223-token history (room 224) leaves 197 tokens to generate at ``check_every`` 8, not the default
     ``sample_len`` of 224: pass ``sample_lens`` / ``options.sample_len`` of at most 197, or shorter histories (196 tokens fit beside 224;
     ``transcribe``'s ``prompt_budget`` makes that cut).  Works with ``temperatures=`` / ``attempts=``; refused with ``best_of`` and on
-    an fp8-quantised model."""
+    an fp8-quantised model.
+    ``row_adapters``: an adapter name of the model's bank (``Whisper.set_adapter_bank``), or None, PER CLIP: the clip decodes under it
+    in whichever slot it lands (the admission writes the slot's id and adds the clip's cross K / V terms); with ``prompts`` the
+    clip's prompt pass runs under its adapter too."""
+    row_ids = None
+    if row_adapters is not None or options.row_adapters is not None:
+        bank = getattr(model, "_bank", None)
+        if bank is None:
+            raise _lib.WipaError("row_adapters needs an adapter bank on the model: Whisper.set_adapter_bank(lora.AdapterBank(...))")
+        names = list(row_adapters if row_adapters is not None else options.row_adapters)
+        if len(names) != mels_or_features.shape[0]:
+            raise ValueError(f"row_adapters: {len(names)} names for {mels_or_features.shape[0]} clips")
+        row_ids = bank.ids(names)
     if prompts is not None:
         if options.best_of is not None and options.best_of > 1:
             raise NotImplementedError("decode_continuous: prompts with best_of is not implemented (candidate groups are served by decode())")
@@ -690,7 +722,8 @@ def decode_continuous(model, mels_or_features: torch.Tensor, options: DecodingOp
         stepper = DeviceStepper(model, slots, feats, initial, len(base), limits, tok.eot, always, first, sample, s, rules=rules,
                                 no_speech_token=tok.no_speech if timed else None, row_seed=int(options.seed) if draws is not None else None,
                                 draws=draws, prompts=(lambda clip: prompt_rows[clip]) if prompt_rows is not None else None,
-                                prompt_room=room if prompt_rows is not None else None)
+                                prompt_room=room if prompt_rows is not None else None,
+                                row_ids=(lambda clip: row_ids[clip]) if row_ids is not None else None)
         if prompt_rows is None:
             stats = run_schedule(stepper, N, slots, len(base), limits, tok.eot, d.n_text_ctx, check_every, column_limit)
         else:

@@ -465,10 +465,11 @@ struct StepCtx {
     void* beam;
     size_t beam_bytes;
     int beam_max_candidates;
+    const wipa_adapter_bank* bank;
 };
 StepCtx step_ctx(const wipa_decode_call& k) {
     return StepCtx{k.rules, k.sample, k.starts_dev, k.n_init, k.eot, k.mask_first, k.mask_always, false, k.continuous != 0, k.no_speech_dev,
-                   k.no_speech_token, k.sample_rows, k.prompted != 0, k.beam, k.beam_bytes, k.beam ? k.beam_max_candidates : 0};
+                   k.no_speech_token, k.sample_rows, k.prompted != 0, k.beam, k.beam_bytes, k.beam ? k.beam_max_candidates : 0, k.bank};
 }
 // The logits projection with the greedy partials in its epilogue + a tail that merges them (round 4; WIPA_LOGITS_FUSED=0 restores
 // the plain GEMM + the row-scanning tail): bf16 models without fp8 decoder tables, <= 64 rows, tail-fused steps.  Measured on
@@ -525,6 +526,39 @@ struct SlabStream {
     }
 };
 
+// Sites of a decoder block in a wipa_adapter_bank (include/wipa.h)
+enum { SITE_Q = 0, SITE_K, SITE_V, SITE_O, SITE_CQ, SITE_CK, SITE_CV, SITE_CO, SITE_MLP1, SITE_MLP2 };
+inline bool bank_on(const wipa_adapter_bank* bk, int site) { return bk && (bk->site_mask >> site & 1u); }
+// One wipa_lora_bank_apply behind the GEMM of `n_seg` consecutive sites from `site0` that share the input x [M, K] (x_dt): the adapters'
+// terms land in y (y_dt) where the GEMM wrote -- `addr` is that GEMM's descriptor (row / column groups and the device offset), NULL for
+// plain rows of ld elements.  scales: the sites' column scales.  Nothing is enqueued when none of the sites is targeted and act is 0.
+int bank_apply(const wipa_adapter_bank* bk, int layer, int site0, int n_seg, const float* scales, const void* x, int64_t ldx, int x_dt, void* y,
+               int y_dt, int64_t ld, const wipa_gemm_desc* addr, int M, int K, int N, int rows_per_id, int ids_stride, const int32_t* ids, int act,
+               wipa_stream_t stream) {
+    wipa_lora_bank_desc b;
+    memset(&b, 0, sizeof(b));
+    bool any = false;
+    for (int s = 0; s < n_seg; ++s) {
+        b.col_scale[s] = scales[s];
+        if (!bank_on(bk, site0 + s)) continue;
+        b.A[s] = bk->A[(size_t)layer * WIPA_BANK_SITES + site0 + s];
+        b.B[s] = bk->B[(size_t)layer * WIPA_BANK_SITES + site0 + s];
+        WIPA_REQUIRE(b.A[s] && b.B[s], "call.bank: layer %d site %d is in site_mask but has no A / B", layer, site0 + s);
+        any = true;
+    }
+    if (!any && !act) return WIPA_OK;
+    b.x = x; b.y = y; b.out = y; b.gain = bk->gain; b.ids = ids; b.ldx = ldx; b.ld = ld;
+    b.M = M; b.K = K; b.N = N; b.r = bk->rank; b.n = bk->n; b.rows_per_id = rows_per_id; b.n_seg = n_seg; b.ids_stride = ids_stride;
+    b.x_dtype = x_dt; b.y_dtype = y_dt; b.act = act;
+    if (addr) {
+        b.rg_in = addr->rg_in; b.rg_stride = addr->rg_stride; b.cg_in = addr->cg_in; b.cg_stride = addr->cg_stride;
+        b.c_offset = addr->c_offset; b.c_offset_dev = addr->c_offset_dev;
+    }
+    return wipa_lora_bank_apply(&b, stream);
+}
+const float SCALES_QKV[3] = {QK_SCALE, QK_SCALE, 1.f};
+const float SCALE_ONE[1] = {1.f};
+
 int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, const wipa_dec_layout& L, int B, const StepCtx& ctx,
                  wipa_stream_t stream) {
     const int dt = cfg->dtype;
@@ -535,7 +569,9 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
     char* sc = st + L.scratch;
     float* x_other = (float*)(sc + S.x2);
     const bool absorbed = cfg->dec_cross_absorbed != 0;
-    const bool cross_fused = !absorbed && decode_mode(cfg, B) == 2;
+    const wipa_adapter_bank* bk = ctx.bank;
+    // with a bank the cross block takes its separate launches: the fused prologues compute the cross query inside a launch
+    const bool cross_fused = !bk && !absorbed && decode_mode(cfg, B) == 2;
     const int G = group_of(cfg), Bc = clips_of(cfg, B);
     void* ln = sc + S.ln;
     void* q = sc + S.q;
@@ -566,6 +602,7 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
             g.cg_in = d; g.cg_stride = (int64_t)B * nctx * d;
             g.c_offset_dev = posd;
             RT_CALL(gemm(ln, d, lw[2], d, skv, d, B, 3 * d, d, dt, dt, (const float*)lw[3], 0, nullptr, stream, &g));
+            if (bk) RT_CALL(bank_apply(bk, l, SITE_Q, 3, SCALES_QKV, ln, d, dt, skv, dt, d, &g, B, d, 3 * d, 1, 1, bk->ids_dev, 0, stream));
         }
         {
             wipa_attn_desc a;
@@ -583,6 +620,7 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
             else RT_CALL(wipa_decode_attn(&a, stream));
         }
         RT_CALL(r.residual_gemm(ao, d, lw[4], lw[5]));
+        if (bk) RT_CALL(bank_apply(bk, l, SITE_O, 1, SCALE_ONE, ao, d, dt, slabs, WIPA_F32, d, nullptr, B, d, d, 1, 1, bk->ids_dev, 0, stream));
         if (cross_fused) {
             // one launch for [slab sum + residual + cross_attn_ln + cross query + cross-attention]; the residual row moves to
             // the other buffer (H workgroups read the row that one of them writes)
@@ -596,7 +634,7 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
             RT_CALL(wipa_decode_cross_block(&c, stream));
             r.pend = 0;
             std::swap(r.x, x_other);
-        } else if (absorbed && absorbed_block_fused() && r.pend <= 4) {
+        } else if (!bk && absorbed && absorbed_block_fused() && r.pend <= 4) {
             // three launches: [slab sum + residual + cross_attn_ln + cross query + absorbed query] -> stream over the encoder output
             // -> [merge + value projection]; the residual row moves to the other buffer like in the fused cross block
             const void* wkT = w[WIPA_DEC_GLOBAL + WIPA_DEC_PER_LAYER * cfg->n_text_layer + WIPA_DEC_ABSORBED_PER_LAYER * l];
@@ -629,6 +667,7 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
                 memset(&g, 0, sizeof(g));
                 g.col_scale_n = d; g.col_scale = QK_SCALE;
                 RT_CALL(gemm(ln, d, lw[8], d, q, d, B, d, d, dt, dt, (const float*)lw[9], 0, nullptr, stream, &g));
+                if (bk) RT_CALL(bank_apply(bk, l, SITE_CQ, 1, SCALES_QKV, ln, d, dt, q, dt, d, nullptr, B, d, d, 1, 1, bk->ids_dev, 0, stream));
             }
             if (absorbed) {
                 // scores and values from ONE pass over the encoder output: Wk absorbed into the query, Wv into the output
@@ -644,9 +683,14 @@ int enqueue_step(const wipa_model_cfg* cfg, const void* const* w, char* st, cons
             }
         }
         if (!cross_out_done) RT_CALL(r.residual_gemm(ao, d, lw[12], lw[13]));
+        if (bk) RT_CALL(bank_apply(bk, l, SITE_CO, 1, SCALE_ONE, ao, d, dt, slabs, WIPA_F32, d, nullptr, B, d, d, 1, 1, bk->ids_dev, 0, stream));
         RT_CALL(r.ln_step(lw[14], lw[15]));
-        RT_CALL(gemm(ln, d, lw[16], d, hb, 4 * d, B, 4 * d, d, dt, dt, (const float*)lw[17], 1, nullptr, stream));
+        // mlp1 with adapters: the GEMM without its GELU, which the apply call performs behind the adapters' term
+        const bool mlp1_bank = bank_on(bk, SITE_MLP1);
+        RT_CALL(gemm(ln, d, lw[16], d, hb, 4 * d, B, 4 * d, d, dt, dt, (const float*)lw[17], mlp1_bank ? 0 : 1, nullptr, stream));
+        if (mlp1_bank) RT_CALL(bank_apply(bk, l, SITE_MLP1, 1, SCALE_ONE, ln, d, dt, hb, dt, 4 * d, nullptr, B, d, 4 * d, 1, 1, bk->ids_dev, 1, stream));
         RT_CALL(r.residual_gemm(hb, 4 * d, lw[18], lw[19]));
+        if (bk) RT_CALL(bank_apply(bk, l, SITE_MLP2, 1, SCALE_ONE, hb, 4 * d, dt, slabs, WIPA_F32, d, nullptr, B, 4 * d, d, 1, 1, bk->ids_dev, 0, stream));
     }
     RT_CALL(r.ln_step(w[2], w[3]));
     float* logits = (float*)(st + L.logits);
@@ -841,6 +885,8 @@ int enqueue_prefill(const wipa_model_cfg* cfg, const void* const* w, char* st, c
     void* ao = sc + S.ao;
     void* hb = sc + S.h;
     SlabStream r{(float*)(sc + S.x), (float*)(sc + S.slabs), ln, M, d, dt, 1024, 1, stream};
+    const wipa_adapter_bank* bk = ctx.bank;  // rows (b, t): P rows per id
+    float* slabs = r.slabs;
     RT_CALL(wipa_embed_tokens((const int32_t*)(st + L.tokens), L.ld_tok, B, P, 0, nullptr, w[0], emb_dtype(cfg), emb_scale(cfg, w), (const float*)w[1],
                               r.x, d, stream));
     for (int l = 0; l < cfg->n_text_layer; ++l) {
@@ -857,6 +903,7 @@ int enqueue_prefill(const wipa_model_cfg* cfg, const void* const* w, char* st, c
             g.rg_in = P; g.rg_valid = P; g.rg_stride = (int64_t)nctx * d;
             g.cg_in = d; g.cg_stride = (int64_t)B * nctx * d;
             RT_CALL(gemm(ln, d, lw[2], d, skv, d, M, 3 * d, d, dt, dt, (const float*)lw[3], 0, nullptr, stream, &g));
+            if (bk) RT_CALL(bank_apply(bk, l, SITE_Q, 3, SCALES_QKV, ln, d, dt, skv, dt, d, &g, M, d, 3 * d, P, 1, bk->ids_dev, 0, stream));
         }
         {
             wipa_attn_desc a;
@@ -871,6 +918,7 @@ int enqueue_prefill(const wipa_model_cfg* cfg, const void* const* w, char* st, c
             RT_CALL(wipa_attention(&a, stream));
         }
         RT_CALL(r.residual_gemm(ao, d, lw[4], lw[5]));
+        if (bk) RT_CALL(bank_apply(bk, l, SITE_O, 1, SCALE_ONE, ao, d, dt, slabs, WIPA_F32, d, nullptr, M, d, d, P, 1, bk->ids_dev, 0, stream));
         RT_CALL(r.ln_step(lw[6], lw[7]));
         {
             wipa_gemm_desc g;
@@ -878,6 +926,7 @@ int enqueue_prefill(const wipa_model_cfg* cfg, const void* const* w, char* st, c
             g.stream_weights = 1;
             g.col_scale_n = d; g.col_scale = QK_SCALE;
             RT_CALL(gemm(ln, d, lw[8], d, q, d, M, d, d, dt, dt, (const float*)lw[9], 0, nullptr, stream, &g));
+            if (bk) RT_CALL(bank_apply(bk, l, SITE_CQ, 1, SCALES_QKV, ln, d, dt, q, dt, d, nullptr, M, d, d, P, 1, bk->ids_dev, 0, stream));
         }
         if (cfg->dec_cross_absorbed) {
             // one absorbed pass per prompt position: rows (b, t) of q / ao with row stride P * d
@@ -893,14 +942,18 @@ int enqueue_prefill(const wipa_model_cfg* cfg, const void* const* w, char* st, c
             RT_CALL(wipa_decode_cross_attn_multi(q, ckv, ao, B, H, Ta, P, dt, stream));
         }
         RT_CALL(r.residual_gemm(ao, d, lw[12], lw[13]));
+        if (bk) RT_CALL(bank_apply(bk, l, SITE_CO, 1, SCALE_ONE, ao, d, dt, slabs, WIPA_F32, d, nullptr, M, d, d, P, 1, bk->ids_dev, 0, stream));
         RT_CALL(r.ln_step(lw[14], lw[15]));
         {
+            const bool mlp1_bank = bank_on(bk, SITE_MLP1);  // as in enqueue_step: the apply call performs the GELU
             wipa_gemm_desc g;
             memset(&g, 0, sizeof(g));
             g.stream_weights = 1;
-            RT_CALL(gemm(ln, d, lw[16], d, hb, 4 * d, M, 4 * d, d, dt, dt, (const float*)lw[17], 1, nullptr, stream, &g));
+            RT_CALL(gemm(ln, d, lw[16], d, hb, 4 * d, M, 4 * d, d, dt, dt, (const float*)lw[17], mlp1_bank ? 0 : 1, nullptr, stream, &g));
+            if (mlp1_bank) RT_CALL(bank_apply(bk, l, SITE_MLP1, 1, SCALE_ONE, ln, d, dt, hb, dt, 4 * d, nullptr, M, d, 4 * d, P, 1, bk->ids_dev, 1, stream));
         }
         RT_CALL(r.residual_gemm(hb, 4 * d, lw[18], lw[19]));
+        if (bk) RT_CALL(bank_apply(bk, l, SITE_MLP2, 1, SCALE_ONE, hb, 4 * d, dt, slabs, WIPA_F32, d, nullptr, M, 4 * d, d, P, 1, bk->ids_dev, 0, stream));
     }
     RT_CALL(r.ln_step(w[2], w[3]));
     // logits of the LAST prompt position only: rows (b, P-1) of ln, i.e. row stride P*d
@@ -970,7 +1023,9 @@ int state_fits(const char* who, const wipa_dec_layout& L, size_t state_bytes) {
 // A PROMPTED continuous step is the continuous key plus a variant bit of its own (candidate groups, which share that range of the word,
 // are not served by a continuous call).
 // A BEAM step bakes in the beam buffer's address and max_candidates: the last two terms, of their own (NULL and 0 without beams).
-typedef std::tuple<const void*, const void*, const void*, const void*, int, int, int, int, int, int, int, int, int, const void*, const void*, const void*, const void*, int, const void*, int> GraphKey;  // ..., generation, kind: 0 step, 1 prefill, 2 lean step (no logit stores), rules, sampling record, starts, workspace, no-speech array, no-speech column
+// An ADAPTER BANK bakes in its address, its ids array's address and (n, rank, site_mask): the last three terms (NULL, NULL and 0 without
+// a bank).  The ids themselves are read by the replayed kernels.
+typedef std::tuple<const void*, const void*, const void*, const void*, int, int, int, int, int, int, int, int, int, const void*, const void*, const void*, const void*, int, const void*, int, const void*, const void*, int64_t> GraphKey;  // ..., generation, kind: 0 step, 1 prefill, 2 lean step (no logit stores), rules, sampling record, starts, workspace, no-speech array, no-speech column
 // sampling lives in the fused step tail, like the rules: refused before anything is enqueued where the step cannot carry it
 int sample_servable(const char* who, const wipa_model_cfg* cfg, int B, const void* sample) {
     if (!sample) return WIPA_OK;
@@ -1035,7 +1090,33 @@ int beam_servable(const char* who, const wipa_model_cfg* cfg, int B, const StepC
     return WIPA_OK;
 }
 // what the steps of a call with rules, a sampling record, starts or candidate groups must be able to serve
+// what an adapter bank needs of its struct and of the configuration; `who` may be an entry point that takes the bank itself
+int bank_servable(const char* who, const wipa_model_cfg* cfg, const wipa_adapter_bank* bk) {
+    if (!bk) return WIPA_OK;
+    WIPA_REQUIRE(bk->n >= 1 && bk->n <= WIPA_LORA_BANK_MAX_ADAPTERS, "%s: call.bank: n = %d: a bank holds 1..%d adapters", who, bk->n,
+                 WIPA_LORA_BANK_MAX_ADAPTERS);
+    WIPA_REQUIRE(bk->rank >= 4 && bk->rank <= 64 && bk->rank % 4 == 0, "%s: call.bank: rank = %d: a multiple of 4 in 4..64", who, bk->rank);
+    WIPA_REQUIRE(bk->site_mask != 0 && bk->site_mask < (1u << WIPA_BANK_SITES), "%s: call.bank: site_mask = 0x%x: 1..%d sites of a block", who,
+                 bk->site_mask, WIPA_BANK_SITES);
+    WIPA_REQUIRE(bk->A && bk->B && bk->gain && bk->ids_dev, "%s: call.bank: A, B, gain and ids_dev are required", who);
+    WIPA_REQUIRE(cfg->dec_w_dtype == 0, "%s: call.bank is not served on fp8 decoder tables (cfg.dec_w_dtype)", who);
+    WIPA_REQUIRE(!cfg->dec_cross_absorbed || !(bank_on(bk, SITE_CK) || bank_on(bk, SITE_CV)),
+                 "%s: call.bank targets cross_attn.key / cross_attn.value, which the absorbed cross-attention form (cfg.dec_cross_absorbed) "
+                 "does not serve: the cached form adds their terms to the cached K / V (wipa_decoder_adapt_cross)", who);
+    return WIPA_OK;
+}
+int bank_call_servable(const char* who, const wipa_model_cfg* cfg, int B, const StepCtx& c) {
+    if (!c.bank) return WIPA_OK;
+    WIPA_REQUIRE(!c.beam, "%s: call.bank is not served with call.beam (beam search decodes one adapter at a time: Whisper.set_adapter)", who);
+    // rows with their own first column: the steps carry a bank as any step does; the ragged prompt pass and the prompted admission take
+    // it themselves (wipa_decoder_prefill_ragged_bank, wipa_decoder_admit_rows_prompted_bank), an unprompted admission is followed by the
+    // slot's id and wipa_decoder_adapt_cross
+    WIPA_REQUIRE(tail_fused() && !use_fused_step(cfg, B),
+                 "%s: call.bank needs the unfused step with the fused tail; WIPA_DECODE_TAIL=0 / WIPA_DECODE_FUSED=1 cannot serve it", who);
+    return bank_servable(who, cfg, c.bank);
+}
 int step_servable(const char* who, const wipa_model_cfg* cfg, int B, const StepCtx& c) {
+    RT_CALL(bank_call_servable(who, cfg, B, c));
     RT_CALL(rules_servable(who, cfg, B, c.eot, c.rules));
     RT_CALL(sample_servable(who, cfg, B, c.sample ? c.sample : c.sample_rows));
     RT_CALL(starts_servable(who, cfg, B, c.n_init, c.starts));
@@ -1093,7 +1174,9 @@ GraphKey graph_key(const wipa_model_cfg* cfg, const void* const* w, const void* 
     return GraphKey(state, (const void*)w, (const void*)c.mask_first, (const void*)c.mask_always, B, c.n_init, c.eot, variant,
                     cfg->weights_generation, kind, c.rules ? c.rules->timestamp_begin : 0, c.rules ? c.rules->no_timestamps : 0,
                     c.rules ? c.rules->max_initial_timestamp_index : 0, c.sample ? c.sample : c.sample_rows, (const void*)c.starts, workspace,
-                    (const void*)c.no_speech, c.no_speech ? c.no_speech_token : 0, (const void*)c.beam, c.beam ? c.beam_max_candidates : 0);
+                    (const void*)c.no_speech, c.no_speech ? c.no_speech_token : 0, (const void*)c.beam, c.beam ? c.beam_max_candidates : 0,
+                    (const void*)c.bank, c.bank ? (const void*)c.bank->ids_dev : nullptr,
+                    c.bank ? ((int64_t)c.bank->site_mask | (int64_t)c.bank->n << 16 | (int64_t)c.bank->rank << 24) : 0);
 }
 // The executable graph cached under `key`.  When there is none, `enqueue` is captured on s (relaxed mode, nothing but kernel launches
 // between begin and end), instantiated and inserted; an enqueue that fails ends the capture, destroys the graph and hands its code back.
@@ -1359,6 +1442,49 @@ extern "C" int wipa_decoder_prefill(const wipa_model_cfg* cfg, const void* const
                                     wipa_stream_t stream) {
     const wipa_decode_call call = {n_init, eot, mask_first, mask_always};
     return wipa_decoder_prefill_ex(cfg, w, state, state_bytes, B, &call, use_graph, stream);
+}
+
+extern "C" int wipa_decoder_graph_count(void) {
+    std::lock_guard<std::mutex> lk(g_graph_mu);
+    return (int)g_graphs.size();
+}
+
+extern "C" int wipa_decoder_adapt_cross(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
+                                        const void* features, int n_rows, const int32_t* slots_host, const wipa_adapter_bank* bank,
+                                        wipa_stream_t stream) {
+    const char* who = "wipa_decoder_adapt_cross";
+    RT_CALL(cfg_check(cfg));
+    WIPA_REQUIRE(w && state && features && bank && B > 0, "%s: weights, state, features and bank are required; B > 0", who);
+    WIPA_REQUIRE(B % group_of(cfg) == 0, "%s: B=%d rows are no multiple of cfg.dec_n_group=%d", who, B, cfg->dec_n_group);
+    RT_CALL(bank_servable(who, cfg, bank));
+    const int G = group_of(cfg), Bc = clips_of(cfg, B);
+    WIPA_REQUIRE(slots_host ? (n_rows >= 1 && n_rows <= Bc) : n_rows == Bc, "%s: n_rows=%d: %s", who, n_rows,
+                 slots_host ? "1..B / cfg.dec_n_group listed slots" : "without slots_host every clip is adapted: B / cfg.dec_n_group");
+    for (int i = 0; slots_host && i < n_rows; ++i)
+        WIPA_REQUIRE(slots_host[i] >= 0 && slots_host[i] < Bc, "%s: slots_host[%d]=%d outside 0..%d", who, i, slots_host[i], Bc - 1);
+    const wipa_dec_layout L = dec_layout(cfg, B);
+    RT_CALL(state_fits(who, L, state_bytes));
+    if (!bank_on(bank, SITE_CK) && !bank_on(bank, SITE_CV)) return WIPA_OK;
+    const size_t e = wipa_dtype_size(cfg->dtype);
+    const int d = cfg->n_text_state, H = cfg->n_text_head, Ta = cfg->n_audio_ctx, dt = cfg->dtype;
+    const float scales[2] = {QK_SCALE, 1.f};  // the key half is scaled like cross_kv_gemm's
+    wipa_gemm_desc g;  // cross_kv_gemm's addressing: [clip][K | V][H][Ta][64]
+    memset(&g, 0, sizeof(g));
+    g.rg_in = Ta; g.rg_stride = (int64_t)2 * H * Ta * 64;
+    g.cg_in = 64; g.cg_stride = (int64_t)Ta * 64;
+    for (int l = 0; l < cfg->n_text_layer; ++l) {
+        char* ckv = (char*)state + L.cross_kv + (size_t)l * Bc * 2 * H * Ta * 64 * e;
+        if (!slots_host) {
+            RT_CALL(bank_apply(bank, l, SITE_CK, 2, scales, features, d, dt, ckv, dt, 64, &g, Bc * Ta, d, 2 * d, Ta, G, bank->ids_dev, 0, stream));
+            continue;
+        }
+        for (int i = 0; i < n_rows; ++i) {
+            g.c_offset = (int64_t)slots_host[i] * g.rg_stride;
+            RT_CALL(bank_apply(bank, l, SITE_CK, 2, scales, (const char*)features + (size_t)i * Ta * d * e, d, dt, ckv, dt, 64, &g, Ta, d, 2 * d, Ta,
+                               1, bank->ids_dev + (size_t)slots_host[i] * G, 0, stream));
+        }
+    }
+    return WIPA_OK;
 }
 
 // ------------------------------------------------------------------ continuous batching: slots, admission, column shift
@@ -1642,6 +1768,9 @@ struct BatchedWalk {
     const TfHook* hook;     // 5. NULL, or what runs between the cross projections and the cross-attention
     const QkvHook* qkv_hook;  // 6. NULL, or what runs behind a layer's q|k|v GEMM; with kv_only the walk is wanted for the K / V of its
     bool kv_only;             //    columns alone, and the last layer stops there (nothing reads what lies behind)
+    const wipa_adapter_bank* bank;  // 7. NULL, or an adapter bank: one wipa_lora_bank_apply behind every targeted GEMM, row b of the walk
+    const int32_t* ids;             //    (all its T columns) under the adapter ids[b * ids_stride]; residual sites add into x itself
+    int ids_stride;
 };
 int batched_layers(const wipa_model_cfg* cfg, const void* const* w, const BatchedWalk& k, wipa_stream_t stream) {
     const int dt = cfg->dtype;
@@ -1651,6 +1780,7 @@ int batched_layers(const wipa_model_cfg* cfg, const void* const* w, const Batche
     float* x = k.x;
     char* ln = k.ln;
     void *q = k.q, *ao = k.ao, *hb = k.hb;
+    const wipa_adapter_bank* bk = k.bank;
     if (k.starts) RT_CALL(wipa_embed_tokens_ragged(k.tokens, k.ld_tok, B, T, k.starts, w[0], dt, (const float*)w[1], x, d, stream));
     else RT_CALL(wipa_embed_tokens(k.tokens, k.ld_tok, B, T, 0, nullptr, w[0], dt, nullptr, (const float*)w[1], x, d, stream));
     for (int l = 0; l < cfg->n_text_layer; ++l) {
@@ -1669,6 +1799,7 @@ int batched_layers(const wipa_model_cfg* cfg, const void* const* w, const Batche
                 g.cg_in = d; g.cg_stride = (int64_t)B * nctx * d;
             }
             RT_CALL(gemm(ln, d, lw[2], d, qkv, qkv_rs, M, 3 * d, d, dt, dt, (const float*)lw[3], 0, nullptr, stream, &g));
+            if (bk) RT_CALL(bank_apply(bk, l, SITE_Q, 3, SCALES_QKV, ln, d, dt, qkv, dt, qkv_rs, k.qkv ? nullptr : &g, M, d, 3 * d, T, k.ids_stride, k.ids, 0, stream));
         }
         if (k.qkv_hook) RT_CALL(k.qkv_hook->after_qkv(l, qkv));
         if (k.kv_only && l + 1 == cfg->n_text_layer) break;
@@ -1685,12 +1816,14 @@ int batched_layers(const wipa_model_cfg* cfg, const void* const* w, const Batche
             else RT_CALL(wipa_attention(&a, stream));
         }
         RT_CALL(gemm(ao, d, lw[4], d, x, d, M, d, d, dt, WIPA_F32, (const float*)lw[5], 0, x, stream));
+        if (bk) RT_CALL(bank_apply(bk, l, SITE_O, 1, SCALE_ONE, ao, d, dt, x, WIPA_F32, d, nullptr, M, d, d, T, k.ids_stride, k.ids, 0, stream));
         RT_CALL(wipa_layernorm(x, WIPA_F32, d, ln, dt, d, (const float*)lw[6], (const float*)lw[7], M, d, 1e-5f, stream));
         {
             wipa_gemm_desc g;
             memset(&g, 0, sizeof(g));
             g.col_scale_n = d; g.col_scale = QK_SCALE;
             RT_CALL(gemm(ln, d, lw[8], d, q, d, M, d, d, dt, dt, (const float*)lw[9], 0, nullptr, stream, &g));
+            if (bk) RT_CALL(bank_apply(bk, l, SITE_CQ, 1, SCALES_QKV, ln, d, dt, q, dt, d, nullptr, M, d, d, T, k.ids_stride, k.ids, 0, stream));
         }
         const int64_t ckv_bs = (int64_t)2 * H * Ta * 64, ckv_hs = (int64_t)Ta * 64;
         const char* ckv = k.ckv_ws;
@@ -1701,6 +1834,8 @@ int batched_layers(const wipa_model_cfg* cfg, const void* const* w, const Batche
             g.rg_in = Ta; g.rg_valid = Ta; g.rg_stride = ckv_bs;
             g.cg_in = 64; g.cg_stride = ckv_hs;
             RT_CALL(gemm(k.features, d, lw[10], d, k.ckv_ws, 64, Bc * Ta, 2 * d, d, dt, dt, (const float*)lw[11], 0, nullptr, stream, &g));
+            // a clip's id is that of its first row (a cached K / V of the blob carries its terms already: wipa_decoder_adapt_cross)
+            if (bk) RT_CALL(bank_apply(bk, l, SITE_CK, 2, SCALES_QKV + 1, k.features, d, dt, k.ckv_ws, dt, 64, &g, Bc * Ta, d, 2 * d, Ta, k.ids_stride * G, k.ids, 0, stream));
         } else {
             ckv = k.ckv_cache + (size_t)l * Bc * ckv_bs * e;
         }
@@ -1725,9 +1860,13 @@ int batched_layers(const wipa_model_cfg* cfg, const void* const* w, const Batche
             }
         }
         RT_CALL(gemm(ao, d, lw[12], d, x, d, M, d, d, dt, WIPA_F32, (const float*)lw[13], 0, x, stream));
+        if (bk) RT_CALL(bank_apply(bk, l, SITE_CO, 1, SCALE_ONE, ao, d, dt, x, WIPA_F32, d, nullptr, M, d, d, T, k.ids_stride, k.ids, 0, stream));
         RT_CALL(wipa_layernorm(x, WIPA_F32, d, ln, dt, d, (const float*)lw[14], (const float*)lw[15], M, d, 1e-5f, stream));
-        RT_CALL(gemm(ln, d, lw[16], d, hb, 4 * d, M, 4 * d, d, dt, dt, (const float*)lw[17], 1, nullptr, stream));
+        const bool mlp1_bank = bank_on(bk, SITE_MLP1);  // as in enqueue_step: the apply call performs the GELU
+        RT_CALL(gemm(ln, d, lw[16], d, hb, 4 * d, M, 4 * d, d, dt, dt, (const float*)lw[17], mlp1_bank ? 0 : 1, nullptr, stream));
+        if (mlp1_bank) RT_CALL(bank_apply(bk, l, SITE_MLP1, 1, SCALE_ONE, ln, d, dt, hb, dt, 4 * d, nullptr, M, d, 4 * d, T, k.ids_stride, k.ids, 1, stream));
         RT_CALL(gemm(hb, 4 * d, lw[18], 4 * d, x, d, M, d, 4 * d, dt, WIPA_F32, (const float*)lw[19], 0, x, stream));
+        if (bk) RT_CALL(bank_apply(bk, l, SITE_MLP2, 1, SCALE_ONE, hb, 4 * d, dt, x, WIPA_F32, d, nullptr, M, 4 * d, d, T, k.ids_stride, k.ids, 0, stream));
     }
     return WIPA_OK;
 }
@@ -1747,6 +1886,7 @@ int enqueue_prefill_ragged(const wipa_model_cfg* cfg, const void* const* w, char
     if (cfg->dec_cross_absorbed) { k.features = st + L.cross_kv; k.ckv_ws = ws + W.ckv; }
     else k.ckv_cache = st + L.cross_kv;
     k.n_group = group_of(cfg);
+    if (ctx.bank) { k.bank = ctx.bank; k.ids = ctx.bank->ids_dev; k.ids_stride = 1; }
     RT_CALL(batched_layers(cfg, w, k, stream));
     RT_CALL(wipa_layernorm(k.x, WIPA_F32, d, k.ln, dt, d, (const float*)w[2], (const float*)w[3], M, d, 1e-5f, stream));
     // logits of two columns per clip: the last prompt column (rows (b, P-1) of ln, row stride P * d) into the state, and the
@@ -1765,18 +1905,36 @@ extern "C" size_t wipa_decoder_prompt_workspace_bytes(const wipa_model_cfg* cfg,
     return prompt_ws(cfg, B, P).total;
 }
 
+static int prefill_ragged(const char* who, const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int P,
+                          int sot_col, int eot, const float* mask_first, const float* mask_always, int use_graph,
+                          const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, void* workspace,
+                          size_t workspace_bytes, const wipa_adapter_bank* bank, wipa_stream_t stream);
 extern "C" int wipa_decoder_prefill_ragged(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int P,
                                            int sot_col, int eot, const float* mask_first, const float* mask_always, int use_graph,
                                            const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, void* workspace,
                                            size_t workspace_bytes, wipa_stream_t stream) {
+    return prefill_ragged("wipa_decoder_prefill_ragged", cfg, w, state, state_bytes, B, P, sot_col, eot, mask_first, mask_always, use_graph, rules,
+                          sample, starts_dev, workspace, workspace_bytes, nullptr, stream);
+}
+extern "C" int wipa_decoder_prefill_ragged_bank(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int P,
+                                                int sot_col, int eot, const float* mask_first, const float* mask_always, int use_graph,
+                                                const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev,
+                                                void* workspace, size_t workspace_bytes, const wipa_adapter_bank* bank, wipa_stream_t stream) {
+    return prefill_ragged("wipa_decoder_prefill_ragged_bank", cfg, w, state, state_bytes, B, P, sot_col, eot, mask_first, mask_always, use_graph,
+                          rules, sample, starts_dev, workspace, workspace_bytes, bank, stream);
+}
+static int prefill_ragged(const char* who, const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int P,
+                          int sot_col, int eot, const float* mask_first, const float* mask_always, int use_graph,
+                          const wipa_decode_rules* rules, const void* sample, const int32_t* starts_dev, void* workspace,
+                          size_t workspace_bytes, const wipa_adapter_bank* bank, wipa_stream_t stream) {
     RT_CALL(cfg_check(cfg));
     SplitScope split_scope(cfg);
     WIPA_REQUIRE(w && state && mask_first && mask_always && B > 0, "wipa_decoder_prefill_ragged: bad arguments");
     WIPA_REQUIRE(starts_dev && workspace, "wipa_decoder_prefill_ragged: starts_dev and workspace are required");
     WIPA_REQUIRE(cfg->dec_w_dtype == 0, "wipa_decoder_prefill_ragged: the prompt pass runs on a bf16 / f32 weight table (cfg.dec_w_dtype: fp8 tables "
                                         "serve the decode step)");
-    const StepCtx ctx{rules, sample, starts_dev, P, eot, mask_first, mask_always, false};
-    const char* who = "wipa_decoder_prefill_ragged";
+    StepCtx ctx{rules, sample, starts_dev, P, eot, mask_first, mask_always, false};
+    ctx.bank = bank;
     char* st = (char*)state;
     hipStream_t s = (hipStream_t)stream;
     wipa_dec_layout L;
@@ -1858,15 +2016,42 @@ extern "C" size_t wipa_decoder_admit_prompted_workspace_bytes(const wipa_model_c
     return admit_ws(cfg, n_rows, W).total;
 }
 
+static int admit_rows_prompted(const char* who, const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
+                               int n_rows, const int32_t* slots_host, const void* const* features_host, const int32_t* initial_tokens_host,
+                               int n_init, const int32_t* limits_host, const int32_t* prompt_lens_host, const int32_t* prompt_tokens_host,
+                               int W, int32_t* starts_dev, void* sample, const uint32_t* streams_host, void* workspace,
+                               size_t workspace_bytes, const wipa_adapter_bank* bank, const int32_t* ids_host, wipa_stream_t stream);
 extern "C" int wipa_decoder_admit_rows_prompted(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B, int n_rows,
                                                 const int32_t* slots_host, const void* const* features_host,
                                                 const int32_t* initial_tokens_host, int n_init, const int32_t* limits_host,
                                                 const int32_t* prompt_lens_host, const int32_t* prompt_tokens_host, int W, int32_t* starts_dev,
                                                 void* sample, const uint32_t* streams_host, void* workspace, size_t workspace_bytes,
                                                 wipa_stream_t stream) {
+    return admit_rows_prompted("wipa_decoder_admit_rows_prompted", cfg, w, state, state_bytes, B, n_rows, slots_host, features_host,
+                               initial_tokens_host, n_init, limits_host, prompt_lens_host, prompt_tokens_host, W, starts_dev, sample, streams_host,
+                               workspace, workspace_bytes, nullptr, nullptr, stream);
+}
+extern "C" int wipa_decoder_admit_rows_prompted_bank(const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
+                                                     int n_rows, const int32_t* slots_host, const void* const* features_host,
+                                                     const int32_t* initial_tokens_host, int n_init, const int32_t* limits_host,
+                                                     const int32_t* prompt_lens_host, const int32_t* prompt_tokens_host, int W,
+                                                     int32_t* starts_dev, void* sample, const uint32_t* streams_host, void* workspace,
+                                                     size_t workspace_bytes, const wipa_adapter_bank* bank, const int32_t* ids_host,
+                                                     wipa_stream_t stream) {
+    const char* who = "wipa_decoder_admit_rows_prompted_bank";
+    WIPA_REQUIRE(bank && (ids_host || n_rows == 0), "%s: bank and ids_host (int32 [n_rows]: the admitted clips' adapters, -1 for none) are required", who);
+    return admit_rows_prompted(who, cfg, w, state, state_bytes, B, n_rows, slots_host, features_host, initial_tokens_host, n_init, limits_host,
+                               prompt_lens_host, prompt_tokens_host, W, starts_dev, sample, streams_host, workspace, workspace_bytes, bank,
+                               ids_host, stream);
+}
+static int admit_rows_prompted(const char* who, const wipa_model_cfg* cfg, const void* const* w, void* state, size_t state_bytes, int B,
+                               int n_rows, const int32_t* slots_host, const void* const* features_host, const int32_t* initial_tokens_host,
+                               int n_init, const int32_t* limits_host, const int32_t* prompt_lens_host, const int32_t* prompt_tokens_host,
+                               int W, int32_t* starts_dev, void* sample, const uint32_t* streams_host, void* workspace,
+                               size_t workspace_bytes, const wipa_adapter_bank* bank, const int32_t* ids_host, wipa_stream_t stream) {
     RT_CALL(cfg_check(cfg));
     SplitScope split_scope(cfg);
-    const char* who = "wipa_decoder_admit_rows_prompted";
+    RT_CALL(bank_servable(who, cfg, bank));
     WIPA_REQUIRE(starts_dev, "%s: starts_dev (int32 [3][B]: window starts, token limits, prompt columns) is required", who);
     RT_CALL(admit_checks(who, cfg, w, state, B, n_rows, slots_host, features_host, initial_tokens_host, n_init, limits_host, starts_dev, sample,
                          streams_host));
@@ -1881,6 +2066,9 @@ extern "C" int wipa_decoder_admit_rows_prompted(const wipa_model_cfg* cfg, const
             WIPA_REQUIRE(prompt_tokens_host[(size_t)i * W + j] >= 0 && prompt_tokens_host[(size_t)i * W + j] < cfg->n_vocab,
                          "%s: prompt token [%d][%d]=%d outside the vocabulary of %d", who, i, j, prompt_tokens_host[(size_t)i * W + j], cfg->n_vocab);
     }
+    for (int i = 0; bank && i < n_rows; ++i)
+        WIPA_REQUIRE(ids_host[i] >= -1 && ids_host[i] < bank->n, "%s: ids_host[%d]=%d: -1 or an adapter of the bank (n = %d)", who, i, ids_host[i],
+                     bank->n);
     if (n_rows == 0) return WIPA_OK;
     const AdmitWs A = admit_ws(cfg, n_rows, W);
     WIPA_REQUIRE(workspace && workspace_bytes >= A.total, "%s: workspace too small (%zu < %zu: wipa_decoder_admit_prompted_workspace_bytes)", who,
@@ -1902,6 +2090,7 @@ extern "C" int wipa_decoder_admit_rows_prompted(const wipa_model_cfg* cfg, const
         for (int t = 0; t < n_init; ++t) m[3 + t] = initial_tokens_host[i * n_init + t];
         m[7] = sample ? (int32_t)streams_host[2 * i] : 0;
         m[8] = sample ? (int32_t)streams_host[2 * i + 1] : 0;
+        m[9] = bank ? ids_host[i] : -1;  // the admitted clip's adapter: what the prompt pass below reads, row by row
         for (int j = W - prompt_lens_host[i]; j < W; ++j) image[A.tokens / 4 + (size_t)i * W + j] = prompt_tokens_host[(size_t)i * W + j];
         image[A.starts / 4 + i] = W - prompt_lens_host[i];
     }
@@ -1909,6 +2098,11 @@ extern "C" int wipa_decoder_admit_rows_prompted(const wipa_model_cfg* cfg, const
     const int32_t* meta = (const int32_t*)(ws + A.meta);
     const int32_t* pos = (const int32_t*)(st + L.pos);
     for (int i = 0; i < n_rows; ++i) RT_CALL(admit_cross(cfg, w, st, L, B, slots_host[i], features_host[i], stream));
+    for (int i = 0; bank && i < n_rows; ++i) {
+        // the slot's id for the steps (a plain copy, before the slot's first step), then the clip's cross K / V terms behind admit_cross
+        WIPA_CHECK_HIP(hipMemcpyAsync((void*)(bank->ids_dev + slots_host[i]), ids_host + i, sizeof(int32_t), hipMemcpyHostToDevice, s));
+        RT_CALL(wipa_decoder_adapt_cross(cfg, w, state, state_bytes, B, features_host[i], 1, slots_host + i, bank, stream));
+    }
     hipLaunchKernelGGL(admit_rows_prompted_kernel, dim3(n_rows), dim3(256), 0, s, (int32_t*)(st + L.tokens), L.ld_tok, pos, cfg->n_text_ctx, B, n_init,
                        W, meta, (const int32_t*)(ws + A.tokens), starts_dev, (float*)(st + L.sum_logprobs), (uint32_t*)sample);
     WIPA_LAUNCH_CHECK();
@@ -1929,6 +2123,7 @@ extern "C" int wipa_decoder_admit_rows_prompted(const wipa_model_cfg* cfg, const
     k.starts = (const int32_t*)(ws + A.starts);
     k.features = ws + A.feat; k.ckv_ws = ws + A.ckv;  // projected per layer from the admitted clips' features, in both cross forms
     k.n_group = 1;
+    if (bank) { k.bank = bank; k.ids = meta + 9; k.ids_stride = ADMIT_META; }
     k.qkv_hook = &hook; k.kv_only = true;
     return batched_layers(cfg, w, k, stream);
 }

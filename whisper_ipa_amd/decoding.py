@@ -71,6 +71,7 @@ class DecodingOptions:
     max_initial_timestamp: Optional[float] = 1.0
     fp16: bool = True
     prompts: Optional[Sequence[Optional[Sequence[int]]]] = None  # one prompt (token ids, or None) PER ROW: what transcribe's conditioning uses
+    row_adapters: Optional[Sequence[Optional[str]]] = None  # one adapter name of the model's bank (Whisper.set_adapter_bank), or None, PER ROW (per clip with best_of)
     seed: Optional[int] = None          # temperature > 0 needs one: sampling is opt-in and reproducible
     sample_streams: Optional[Sequence] = None  # per-row (lo, hi) Philox streams; default (row, 0)
     sample_attempt: int = 0             # which retry of the row this is (transcribe's fallback schedule index)
@@ -181,6 +182,33 @@ class DecoderState:
         if getattr(self, "_starts", None) is None:
             self._starts = torch.zeros(self.B, dtype=torch.int32, device=self.blob.device)
         return self._starts
+
+    def adapter_bank(self, bank, ids: Sequence[int]) -> "_lib.AdapterBankC":
+        """the wipa_adapter_bank of this state for ``bank`` (lora.AdapterBank), its device array of row ids rewritten in stream order with
+        ``ids`` (one per row, -1: no adapter).  ONE struct and ONE id array per (state, bank): the step graph is keyed on their addresses,
+        so another assignment of adapters to rows replays the captured graph.  The state keeps every bank it has been used with alive
+        (its A / B device pointers are baked into the graphs captured under the struct's address): a replaced bank's tensors are
+        freed with the state (``Whisper._invalidate`` releases the states), not before."""
+        if len(ids) != self.B or any(not -1 <= int(i) < len(bank) for i in ids):
+            raise _lib.WipaError(f"row_adapters: {len(ids)} ids for {self.B} rows, each -1 or below {len(bank)}: {list(ids)[:8]}")
+        if getattr(self, "_bank_ids", None) is None:
+            self._bank_ids = torch.full((self.B,), -1, dtype=torch.int32, device=self.blob.device)
+            self._bank_structs = {}
+        self._bank_ids.copy_(torch.tensor([int(i) for i in ids], dtype=torch.int32))  # a plain copy on the caller's library stream
+        held = self._bank_structs.get(id(bank))
+        if held is None or held[0] is not bank:
+            from .lora import SITES
+
+            n_layer = bank.n_layer
+            A, B = (C.c_void_p * (n_layer * _lib.BANK_SITES))(), (C.c_void_p * (n_layer * _lib.BANK_SITES))()
+            mask = 0
+            for (l, site), t in bank.A.items():
+                i = SITES.index(site)
+                mask |= 1 << i
+                A[l * _lib.BANK_SITES + i], B[l * _lib.BANK_SITES + i] = t.data_ptr(), bank.B[(l, site)].data_ptr()
+            struct = _lib.AdapterBankC(len(bank), bank.rank, mask, A, B, bank.gain.data_ptr(), self._bank_ids.data_ptr())
+            held = self._bank_structs[id(bank)] = (bank, struct, A, B)
+        return held[1]
 
     def prompt_workspace(self, pk, P: int) -> torch.Tensor:
         """the caller-owned workspace of wipa_decoder_prefill_ragged for a prompt width of P; kept, and re-made only to grow (its
@@ -355,25 +383,26 @@ def timestamp_rules(tok: Tokenizer, max_initial_timestamp: Optional[float] = 1.0
 
 
 def decode_call(n_init: int, eot: int, m_first, m_always, rules=None, sample_rec=None, starts=None, beam=None, continuous: bool = False,
-                prompted: bool = False, sample_rows=None, no_speech=None, no_speech_token: int = 0) -> "_lib.DecodeCall":
+                prompted: bool = False, sample_rows=None, no_speech=None, no_speech_token: int = 0, bank=None) -> "_lib.DecodeCall":
     """The wipa_decode_call (include/wipa.h) of a decode: the masks, ``rules`` (``timestamp_rules``), ``sample_rec`` (the state's device
     sampling record), ``starts`` (the state's device array of first columns; ``n_init`` is then the prompt width P), ``beam`` (the state's
-    beam buffer, max_candidates), and what a continuous stepper adds.  None / 0 / False: not used.  It holds addresses only: the tensors
+    beam buffer, max_candidates), ``bank`` (the state's wipa_adapter_bank: ``DecoderState.adapter_bank``) and what a continuous stepper
+    adds.  None / 0 / False: not used.  It holds addresses only: the tensors
     stay the caller's to keep alive."""
     buf, max_candidates = beam if beam is not None else (None, 0)
     return _lib.DecodeCall(int(n_init), int(eot), ptr(m_first), ptr(m_always), C.pointer(rules) if rules is not None else None, ptr(sample_rec),
                            ptr(sample_rows), ptr(starts), int(continuous), int(prompted), ptr(no_speech), int(no_speech_token), ptr(buf),
-                           buf.numel() if buf is not None else 0, int(max_candidates))
+                           buf.numel() if buf is not None else 0, int(max_candidates), C.pointer(bank) if bank is not None else None)
 
 
-def _dec_run(L, pk, st, B, n_init, eot, m_first, m_always, n, use_graph, rules, s, sample_rec=None, starts=None, beam=None):
-    call = decode_call(n_init, eot, m_first, m_always, rules, sample_rec, starts, beam)
+def _dec_run(L, pk, st, B, n_init, eot, m_first, m_always, n, use_graph, rules, s, sample_rec=None, starts=None, beam=None, bank=None):
+    call = decode_call(n_init, eot, m_first, m_always, rules, sample_rec, starts, beam, bank=bank)
     _lib.check(L.wipa_decoder_run_ex(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, C.byref(call), n, int(use_graph), sptr(s)),
                "wipa_decoder_run_ex")
 
 
-def _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s, sample_rec=None, beam=None):
-    call = decode_call(n_init, eot, m_first, m_always, rules, sample_rec, None, beam)
+def _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s, sample_rec=None, beam=None, bank=None):
+    call = decode_call(n_init, eot, m_first, m_always, rules, sample_rec, None, beam, bank=bank)
     _lib.check(L.wipa_decoder_prefill_ex(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, C.byref(call), int(use_graph), sptr(s)),
                "wipa_decoder_prefill_ex")
 
@@ -390,16 +419,29 @@ def _begin_with(initial_tokens: Sequence[int]):
     return begin
 
 
-def _open(model, L, pk, st, audio_features: torch.Tensor, B: int, s, begin):
+def _bank_of(model, st, row_ids: Optional[Sequence[int]], n_group: int = 1):
+    """the state's wipa_adapter_bank for a decode whose rows carry ``row_ids`` (one per clip; candidates share their clip's), or None"""
+    if row_ids is None:
+        return None
+    bank = getattr(model, "_bank", None)
+    if bank is None:
+        raise _lib.WipaError("row_adapters needs an adapter bank on the model: Whisper.set_adapter_bank(lora.AdapterBank(...))")
+    return st.adapter_bank(bank, [int(i) for i in row_ids for _ in range(n_group)])
+
+
+def _open(model, L, pk, st, audio_features: torch.Tensor, B: int, s, begin, bank=None):
     """the opening of every decode, on the library stream ``s``: the features in the model's dtype into the state
-    (wipa_decoder_set_audio), then ``begin``.  Returns (the features, which must outlive the enqueued work, and what ``begin`` returns:
-    the state's device array of first columns, or None)"""
+    (wipa_decoder_set_audio; with ``bank`` its cross K / V terms behind it: wipa_decoder_adapt_cross), then ``begin``.  Returns (the
+    features, which must outlive the enqueued work, and what ``begin`` returns: the state's device array of first columns, or None)"""
     feats = audio_features.to(device=model.device, dtype=model.dtype).contiguous()
     if tuple(feats.shape[-2:]) != (model.n_audio_ctx, model.dims.n_text_state):  # the state is sized for the effective N
         raise _lib.WipaError(f"decode: audio features of shape {tuple(feats.shape)} given to a model that runs on "
                              f"[.., {model.n_audio_ctx}, {model.dims.n_text_state}] (audio_ctx={model.audio_ctx!r})")
     _lib.check(L.wipa_decoder_set_audio(C.byref(pk["cfg"]), pk["dec_tab"], ptr(feats), ptr(st.blob), st.blob.numel(), B, sptr(s)),
                "wipa_decoder_set_audio")
+    if bank is not None:
+        _lib.check(L.wipa_decoder_adapt_cross(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, ptr(feats), feats.shape[0], None,
+                                              C.byref(bank), sptr(s)), "wipa_decoder_adapt_cross")
     return feats, begin(L, pk, st, B, s)
 
 
@@ -448,7 +490,8 @@ def _for_candidates(sample: Optional[Sampling], clips: int, n_group: int) -> Opt
 
 def _decode_loop(model, audio_features: torch.Tensor, P: int, max_new_tokens: int, begin, run_prompt, suppress_always, suppress_first,
                  eot: int, stop_on_eot: bool, use_graph: bool, check_every: int, rules, sample: Optional[Sampling], n_group: int, rank: bool,
-                 length_penalty: Optional[float], sot_back: Optional[int] = None, beams: Optional[Beams] = None) -> GreedyTokens:
+                 length_penalty: Optional[float], sot_back: Optional[int] = None, beams: Optional[Beams] = None,
+                 row_ids: Optional[Sequence[int]] = None) -> GreedyTokens:
     """The decode loop of ``greedy_decode_tokens`` and ``ragged_decode_tokens``, for a prompt of ``P`` columns and ``max_new_tokens``
     already clamped to n_text_ctx - P.  The caller supplies how to begin -- ``begin(L, pk, st, B, s)`` returns the state's device array
     of first columns, or None -- and how the batched prompt pass is run: ``run_prompt(L, pk, st, B, m_first, m_always, rec, starts, s)``
@@ -466,7 +509,8 @@ def _decode_loop(model, audio_features: torch.Tensor, P: int, max_new_tokens: in
     done_steps = 0
     sot_logits = None
     with on_stream() as s:
-        feats, starts = _open(model, L, pk, st, audio_features, B, s, begin)
+        bank = _bank_of(model, st, row_ids, n_group)  # ``row_ids``: an adapter of the model's bank per clip (-1: none)
+        feats, starts = _open(model, L, pk, st, audio_features, B, s, begin, bank)
         rec = st.sample_record(sample) if sample is not None else None
         beam = None
         if beams is not None:
@@ -474,18 +518,19 @@ def _decode_loop(model, audio_features: torch.Tensor, P: int, max_new_tokens: in
             _lib.check(L.wipa_beam_begin(ptr(buf), buf.numel(), B, n_group, beams.max_candidates, st.layout.ld_tok, sptr(s)), "wipa_beam_begin")
             beam = (buf, beams.max_candidates)
         if _use_prefill(P, total):  # the whole prompt and the first new token in one batched pass
-            sot_logits = run_prompt(L, pk, st, B, m_first, m_always, rec, starts, s, **({"beam": beam} if beam is not None else {}))
+            sot_logits = run_prompt(L, pk, st, B, m_first, m_always, rec, starts, s, **({"beam": beam} if beam is not None else {}),
+                                    **({"bank": bank} if bank is not None else {}))
             done_steps = P
         elif sot_back is not None:  # the steps up to the <|startoftranscript|> column: its logits are those of the call's last step
             n = P - sot_back + 1
-            _dec_run(L, pk, st, B, P, eot, m_first, m_always, n, use_graph, rules, s, rec, starts)
+            _dec_run(L, pk, st, B, P, eot, m_first, m_always, n, use_graph, rules, s, rec, starts, bank=bank)
             sot_logits = st.logits.clone()
             done_steps = n
         while done_steps < total:
             n = min(check_every if stop_on_eot else total, total - done_steps)
             if done_steps < P - 1:  # the rest of the prompt walk rides with the first generated columns
                 n = min(total - done_steps, n + (P - 1 - done_steps))
-            _dec_run(L, pk, st, B, P, eot, m_first, m_always, n, use_graph, rules, s, rec, starts, beam)
+            _dec_run(L, pk, st, B, P, eot, m_first, m_always, n, use_graph, rules, s, rec, starts, beam, bank)
             done_steps += n
             if stop_on_eot and done_steps >= P:
                 if beam is not None:  # live beams never hold EOT: the step's tail counts the clips whose finished store is not full
@@ -522,8 +567,10 @@ def greedy_decode_tokens(model, audio_features: torch.Tensor, initial_tokens: Se
                          suppress_first: Sequence[int], eot: int, max_new_tokens: Optional[int] = None,
                          stop_on_eot: bool = True, use_graph: bool = True, check_every: int = 8, rules=None,
                          sample: Optional[Sampling] = None, n_group: int = 1, rank: bool = False,
-                         length_penalty: Optional[float] = None, beams: Optional[Beams] = None) -> GreedyTokens:
+                         length_penalty: Optional[float] = None, beams: Optional[Beams] = None,
+                         row_ids: Optional[Sequence[int]] = None) -> GreedyTokens:
     """DecodingTask._main_loop (see module docstring): temperature 0, or a Categorical draw per step with ``sample``.
+    ``row_ids``: one id of the model's adapter bank per clip (-1: the base model): every row decodes under its own adapter.
     ``audio_features`` [B, 1500, d] in the model dtype.  ``rules`` (``timestamp_rules``): ApplyTimestampRules in every greedy
     update, on the device; ``initial_tokens`` is then the prompt without <|notimestamps|>.
     ``n_group`` > 1 (upstream's n_group = best_of): every clip is decoded as ``n_group`` candidate rows, clip-major, that share the
@@ -541,11 +588,11 @@ def greedy_decode_tokens(model, audio_features: torch.Tensor, initial_tokens: Se
         max_new_tokens = model.dims.n_text_ctx // 2
     max_new_tokens = min(max_new_tokens, model.dims.n_text_ctx - n_init)
 
-    def run_prompt(L, pk, st, B, m_first, m_always, rec, starts, s, beam=None):
-        _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s, rec, beam)
+    def run_prompt(L, pk, st, B, m_first, m_always, rec, starts, s, beam=None, bank=None):
+        _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s, rec, beam, bank)
 
     return _decode_loop(model, audio_features, n_init, max_new_tokens, _begin_with(initial_tokens), run_prompt, suppress_always, suppress_first,
-                        eot, stop_on_eot, use_graph, check_every, rules, sample, n_group, rank, length_penalty, beams=beams)
+                        eot, stop_on_eot, use_graph, check_every, rules, sample, n_group, rank, length_penalty, beams=beams, row_ids=row_ids)
 
 
 # ---------------------------------------------------------------- prompt conditioning: per-row prompts
@@ -622,7 +669,7 @@ def ragged_decode_tokens(model, audio_features: torch.Tensor, rows: Sequence[Seq
                          suppress_first: Sequence[int], eot: int, max_new_tokens: Optional[int] = None, stop_on_eot: bool = True,
                          use_graph: bool = True, check_every: int = 8, rules=None, sample: Optional[Sampling] = None,
                          pad_to: Optional[int] = None, sot_back: Optional[int] = None, n_group: int = 1, rank: bool = False,
-                         length_penalty: Optional[float] = None) -> GreedyTokens:
+                         length_penalty: Optional[float] = None, row_ids: Optional[Sequence[int]] = None) -> GreedyTokens:
     """``greedy_decode_tokens`` for rows with their OWN initial tokens (``rows[b]``: [sot_prev] + history + sot_sequence + prefix), packed
     by ``pack_prompts``.  ``tokens`` of the result are [B, P + n_steps] with the padding in front; ``n_init`` = P.  The prompt goes through
     one batched pass (wipa_decoder_prefill_ragged); with WIPA_NO_PREFILL=1 it is walked column by column by the replayed decode step,
@@ -630,7 +677,9 @@ def ragged_decode_tokens(model, audio_features: torch.Tensor, rows: Sequence[Seq
     (len(sot_sequence) + len(prefix)); the unfiltered logits of that column come back as ``sot_logits`` (upstream's
     ``logits[:, sot_index]`` for no_speech_prob).  ``max_new_tokens`` is clamped to n_text_ctx - P.
     ``n_group`` / ``rank`` / ``length_penalty``: candidate groups as in ``greedy_decode_tokens``: ``rows`` and ``sample.streams`` are per
-    clip, every candidate of a clip starts from the clip's own initial tokens, ``sot_logits`` and ``starts`` stay per clip."""
+    clip, every candidate of a clip starts from the clip's own initial tokens, ``sot_logits`` and ``starts`` stay per clip.
+    ``row_ids``: one id of the model's adapter bank per clip (-1: the base model); the prompt pass is then
+    wipa_decoder_prefill_ragged_bank and the prompt columns of a row run under the row's adapter like its steps."""
     clips = audio_features.shape[0]
     n_ctx = model.dims.n_text_ctx
     if getattr(model, "_fp8", None):
@@ -660,26 +709,28 @@ def ragged_decode_tokens(model, audio_features: torch.Tensor, rows: Sequence[Seq
                                                starts_h.ctypes.data_as(i32p), P, ptr(starts), sptr(s)), "wipa_decoder_begin_ragged")
         return starts
 
-    def run_prompt(L, pk, st, B, m_first, m_always, rec, starts, s):
+    def run_prompt(L, pk, st, B, m_first, m_always, rec, starts, s, bank=None):
         ws = st.prompt_workspace(pk, P)
-        _lib.check(L.wipa_decoder_prefill_ragged(C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, P,
-                                                 P - sot_back if sot_back is not None else -1, eot, ptr(m_first), ptr(m_always),
-                                                 int(use_graph), C.byref(rules) if rules is not None else None,
-                                                 ptr(rec) if rec is not None else None, ptr(starts), ptr(ws), ws.numel(), sptr(s)),
-                   "wipa_decoder_prefill_ragged")
+        args = (C.byref(pk["cfg"]), pk["dec_tab"], ptr(st.blob), st.blob.numel(), B, P, P - sot_back if sot_back is not None else -1, eot,
+                ptr(m_first), ptr(m_always), int(use_graph), C.byref(rules) if rules is not None else None,
+                ptr(rec) if rec is not None else None, ptr(starts), ptr(ws), ws.numel())
+        if bank is None:
+            _lib.check(L.wipa_decoder_prefill_ragged(*args, sptr(s)), "wipa_decoder_prefill_ragged")
+        else:
+            _lib.check(L.wipa_decoder_prefill_ragged_bank(*args, C.byref(bank), sptr(s)), "wipa_decoder_prefill_ragged_bank")
         if sot_back is None:
             return None
         ld = st.layout.ld_logits  # the pass leaves the <|startoftranscript|> column's logits at the head of its workspace
         return ws[: B * ld * 4].view(torch.float32).view(B, ld)[:, : model.dims.n_vocab].clone()
 
     g = _decode_loop(model, audio_features, P, max_new_tokens, begin, run_prompt, suppress_always, suppress_first, eot, stop_on_eot, use_graph,
-                     check_every, rules, sample, n_group, rank, length_penalty, sot_back)
+                     check_every, rules, sample, n_group, rank, length_penalty, sot_back, row_ids=row_ids)
     g.n_init, g.starts = P, (clip_starts_h if rank and n_group > 1 else starts_h).copy()
     return g
 
 
 def forced_decode_logits(model, audio_features: torch.Tensor, tokens: np.ndarray, n_init: int, suppress_always: Sequence[int],
-                         suppress_first: Sequence[int], eot: int, use_graph: bool = True, rules=None):
+                         suppress_first: Sequence[int], eot: int, use_graph: bool = True, rules=None, row_ids: Optional[Sequence[int]] = None):
     """The KV-cached decode-step path (prompt prefill + replayed step graph -- the kernels greedy_decode_tokens runs) driven
     along a GIVEN token history: after every step the greedy choice is read and then overwritten with ``tokens[:, p + 1]``.
     ``tokens`` [B, n_init + n_steps] int (host).  Returns (step logits [B, n_steps, V] f32 on the device, unfiltered, and the
@@ -701,15 +752,16 @@ def forced_decode_logits(model, audio_features: torch.Tensor, tokens: np.ndarray
         forced = torch.from_numpy(tokens.astype(np.int32)).to(model.device)
         trace = torch.empty(B, n_steps, V, dtype=torch.float32, device=model.device)
         chosen = torch.empty(B, n_steps, dtype=torch.int32, device=model.device)
-        feats, _ = _open(model, L, pk, st, audio_features, B, s, _begin_with(tokens[0, :n_init]))
-        _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s)
+        bank = _bank_of(model, st, row_ids)  # ``row_ids``: an adapter of the model's bank per row (-1: none)
+        feats, _ = _open(model, L, pk, st, audio_features, B, s, _begin_with(tokens[0, :n_init]), bank)
+        _dec_prefill(L, pk, st, B, n_init, eot, m_first, m_always, use_graph, rules, s, bank=bank)
         for i in range(n_steps):
             p = n_init + i  # the token position the last step has just filled
             trace[:, i].copy_(st.logits)
             chosen[:, i].copy_(st.tokens[:, p])
             st.tokens[:, p].copy_(forced[:, p])
             if i + 1 < n_steps:
-                _dec_run(L, pk, st, B, n_init, eot, m_first, m_always, 1, use_graph, rules, s)
+                _dec_run(L, pk, st, B, n_init, eot, m_first, m_always, 1, use_graph, rules, s, bank=bank)
         out_chosen = chosen.cpu().numpy().astype(np.int64)
     return trace, out_chosen
 
@@ -836,6 +888,23 @@ def _refuse_unsupported(options: DecodingOptions) -> None:
         raise NotImplementedError("prompt / prefix conditioning is not implemented on the timestamp path")
     if getattr(options, "prompts", None) is not None:
         raise NotImplementedError("prompts (per-row prompt conditioning) is served by decode() only")
+    if getattr(options, "row_adapters", None) is not None:
+        raise NotImplementedError("row_adapters (an adapter of the model's bank per row) is served by decode() and decode_continuous() only")
+
+
+def _row_adapter_ids(model, options: DecodingOptions, n_rows: int, beams: bool) -> Optional[List[int]]:
+    """``options.row_adapters`` as ids of the model's adapter bank, one per clip (None without it).  Refused by name: no bank on the
+    model, a count that differs from the clips', an unknown name, beam search."""
+    if options.row_adapters is None:
+        return None
+    bank = getattr(model, "_bank", None)
+    if bank is None:
+        raise _lib.WipaError("row_adapters needs an adapter bank on the model: Whisper.set_adapter_bank(lora.AdapterBank(...))")
+    if beams:
+        raise NotImplementedError("row_adapters with beam_size is not implemented: beam search decodes one adapter at a time (Whisper.set_adapter)")
+    if len(options.row_adapters) != n_rows:
+        raise ValueError(f"row_adapters: {len(options.row_adapters)} names for {n_rows} clips")
+    return bank.ids(options.row_adapters)
 
 
 def decode(model, mel: torch.Tensor, options: DecodingOptions = DecodingOptions(), **kwargs):
@@ -851,7 +920,8 @@ def decode(model, mel: torch.Tensor, options: DecodingOptions = DecodingOptions(
     beam = beam_group(options, model)  # ... and beams, before it touches the features: groups of beam_size rows
     if beam is not None:
         n_group = beam[0]
-    _refuse_unsupported(replace(options, prompt=None, prefix=None, prompts=None, best_of=None, beam_size=None))
+    _refuse_unsupported(replace(options, prompt=None, prefix=None, prompts=None, best_of=None, beam_size=None, row_adapters=None))
+    row_ids = _row_adapter_ids(model, options, n_rows, beam is not None)
     if (prompts is not None or prefix is not None) and getattr(model, "_fp8", None):
         raise NotImplementedError("prompt / prefix conditioning is not implemented for an fp8-quantised model: the ragged decode step "
                                   "runs on bf16 / f32 decoder tables")
@@ -916,13 +986,14 @@ def decode(model, mel: torch.Tensor, options: DecodingOptions = DecodingOptions(
                                                            int(options.sample_attempt))
             if prompts is None and prefix is None:  # no row has a prompt: the path without prompts, call for call
                 g = greedy_decode_tokens(model, sub, init, always, first, tok.eot, max_new_tokens=sample_len, rules=rules, sample=sample,
-                                         **group_kw)
+                                         **group_kw, **({"row_ids": [row_ids[i] for i in rows]} if row_ids is not None else {}))
                 n_init = len(init)
             else:
                 own = [initial_tokens(tok, init, prompts[i] if prompts is not None else None, prefix, d.n_text_ctx, sample_len) for i in rows]
                 sot_back = len(initial_tokens(tok, init, None, prefix, d.n_text_ctx, sample_len))  # sot_sequence + prefix: the same for every row
                 g = ragged_decode_tokens(model, sub, own, always, first, tok.eot, max_new_tokens=sample_len, rules=rules, sample=sample,
-                                         sot_back=sot_back if timed else None, **group_kw)
+                                         sot_back=sot_back if timed else None, **group_kw,
+                                         **({"row_ids": [row_ids[i] for i in rows]} if row_ids is not None else {}))
                 n_init = g.n_init
                 if timed:  # upstream's logits[:, sot_index] of the prompted pass
                     nsp = _no_speech_from(g.sot_logits, tok)

@@ -1,12 +1,13 @@
 """Low-rank adapters (LoRA) on the decoder's linears: configuration, names, flat layout, initialisation, the torch statement of the
 merged weight and the adapter files.  Everything here runs on the CPU; the kernels are csrc/lora.hip, the trainer is
-``DecoderTrainer(model, lora=LoRAConfig(...))`` and inference is ``Whisper.set_adapter``.
+``DecoderTrainer(model, lora=LoRAConfig(...))`` and inference is ``Whisper.set_adapter`` (one adapter, merged) or ``AdapterBank`` +
+``Whisper.set_adapter_bank`` + ``DecodingOptions.row_adapters`` (a different adapter per row, unmerged: csrc/lora_bank.hip).
 
 An adapted linear ``y = (x W^T + b) c`` gains ``c s (x A^T) B^T`` with ``A [r, in]``, ``B [out, r]`` and ``s = alpha / r``; the base
 stays frozen.  Adapter tensors are named after the weight they sit on: ``decoder.blocks.{l}.attn.query.lora_A`` / ``.lora_B``.
 
-Out of scope: adapters on encoder blocks or on the embedding, dropout on the adapter path, rows with different adapters in one batch,
-fp8 tables.  The files are this project's own (``format: "wipa-lora-1"``); compatibility with PEFT is not claimed."""
+Out of scope: adapters on encoder blocks or on the embedding, dropout on the adapter path, fp8 tables; with a bank: cross key / value
+adapters on the absorbed cross-attention form, banks with mixed ranks or mixed site sets.  The files are this project's own (``format: "wipa-lora-1"``); compatibility with PEFT is not claimed."""
 from __future__ import annotations
 
 import json
@@ -167,3 +168,51 @@ def load_adapter(directory: str):
         raise WipaError(f"load_adapter: {cp}: format {conf.get('format')!r}, expected {FORMAT!r}")
     cfg = LoRAConfig(rank=int(conf["r"]), alpha=float(conf["lora_alpha"]), targets=tuple(conf["target_modules"]), seed=int(conf.get("seed", 0)))
     return load_safetensors(wp), cfg, conf
+
+
+class AdapterBank:
+    """``n`` adapters (1..64) of one rank and one set of sites, kept unmerged and stacked for wipa_lora_bank_apply (csrc/lora_bank.hip):
+    ``A[(layer, site)]`` float32 ``[n, r, in]``, ``B[(layer, site)]`` float32 ``[n, out, r]`` and ``gain`` float32 ``[n]`` = alpha / r of each
+    adapter (alpha may differ from one adapter to the next), on ``device``.  ``adapters`` maps a name (a language, say) to ``(adapter
+    tensors, LoRAConfig)``; the order of the mapping is the order of the ids.  Every adapter is checked with check_adapter; a rank or a
+    set of sites that differs from the first adapter's is refused by name."""
+
+    def __init__(self, dims, adapters: Dict[str, Tuple[Dict[str, torch.Tensor], LoRAConfig]], device="cuda"):
+        from ._lib import LORA_BANK_MAX_ADAPTERS
+
+        if not adapters or len(adapters) > LORA_BANK_MAX_ADAPTERS:
+            raise WipaError(f"AdapterBank: {len(adapters)} adapters: a bank holds 1..{LORA_BANK_MAX_ADAPTERS}")
+        self.names: Tuple[str, ...] = tuple(adapters)
+        first = self.names[0]
+        cfg0 = adapters[first][1]
+        for name, (tensors, cfg) in adapters.items():
+            if cfg.rank != cfg0.rank:
+                raise WipaError(f"AdapterBank: adapter {name!r} has rank {cfg.rank}, adapter {first!r} has rank {cfg0.rank}: one rank per bank")
+            if cfg.sites() != cfg0.sites():
+                raise WipaError(f"AdapterBank: adapter {name!r} sits on {cfg.sites()}, adapter {first!r} on {cfg0.sites()}: one set of sites per bank")
+            check_adapter(dims, cfg, tensors)
+        self.rank, self.sites, self.n_layer = cfg0.rank, cfg0.sites(), dims.n_text_layer
+        self.configs = {name: cfg for name, (_, cfg) in adapters.items()}
+        stack = lambda l, s, ab: torch.stack([torch.as_tensor(adapters[n][0][f"decoder.blocks.{l}.{s}.{ab}"]).detach().to(torch.float32)
+                                              for n in self.names]).contiguous().to(device)
+        self.A = {(l, s): stack(l, s, "lora_A") for l in range(self.n_layer) for s in self.sites}
+        self.B = {(l, s): stack(l, s, "lora_B") for l in range(self.n_layer) for s in self.sites}
+        self.gain = torch.tensor([self.configs[n].scale for n in self.names], dtype=torch.float32).to(device)
+
+    def __len__(self) -> int:
+        return len(self.names)
+
+    @property
+    def targets_cross_kv(self) -> bool:
+        """whether the bank sits on cross_attn.key or cross_attn.value: their terms live in the cached cross K / V"""
+        return "cross_attn.key" in self.sites or "cross_attn.value" in self.sites
+
+    def ids(self, rows) -> List[int]:
+        """one int32 id per row: the index of the row's adapter name, -1 for None (no adapter); an unknown name is refused"""
+        index = {n: i for i, n in enumerate(self.names)}
+        out = []
+        for b, name in enumerate(rows):
+            if name is not None and name not in index:
+                raise WipaError(f"AdapterBank.ids: row {b}: no adapter {name!r} in the bank ({', '.join(self.names)})")
+            out.append(-1 if name is None else index[name])
+        return out

@@ -1047,6 +1047,9 @@ class DecoderTrainer:
 
     def _loss_and_grads(self, audio_features: torch.Tensor, tokens: torch.Tensor, eot: int, group, ectx: Optional[Dict]):
         m, dm, L = self.model, self.model.dims, self.L
+        if getattr(m, "_bank", None) is not None:
+            raise _lib.WipaError("DecoderTrainer: a step while the model has an adapter bank set: set_adapter_bank(None) first (a bank "
+                                 "serves inference; its adapters are trained one at a time, without it)")
         if self.lora is not None and getattr(m, "_adapter", None) is not None:
             raise _lib.WipaError("DecoderTrainer: a step while the model has an adapter applied: its weights are base + adapter, and the "
                                  "step would add the adapter a second time -- set_adapter(None) (or leave adapter_applied()) first")

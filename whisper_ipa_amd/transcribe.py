@@ -168,20 +168,27 @@ def _model_decoder(model, decode_options: dict) -> Callable:
             opts["prompts"] = [list(prompts[i]) for i in rows]
         return opts
 
-    def run(windows: np.ndarray, languages: List[Optional[str]], prompts=None):
+    def with_adapters(opts: dict, row_adapters, rows) -> dict:
+        """the rows' adapters of the model's bank (transcribe(row_adapters=[per file]): a window carries its file's)"""
+        if row_adapters is not None:
+            opts["row_adapters"] = [row_adapters[i] for i in rows]
+        return opts
+
+    def run(windows: np.ndarray, languages: List[Optional[str]], prompts=None, row_adapters=None):
         out = [None] * len(languages)
         dev_audio = torch.from_numpy(np.ascontiguousarray(windows)).to(model.device)
         mel = A.log_mel_spectrogram(dev_audio, n_mels=model.dims.n_mels)
         for lang in sorted(set(languages), key=lambda l: (l is not None, l or "")):
             rows = [i for i, l in enumerate(languages) if l == lang]
-            opts = DecodingOptions(**with_prompts({**decode_options, "language": lang, "without_timestamps": False, "temperature": 0.0},
-                                                  prompts, rows))
+            opts = DecodingOptions(**with_adapters(with_prompts({**decode_options, "language": lang, "without_timestamps": False,
+                                                                 "temperature": 0.0}, prompts, rows), row_adapters, rows))
             res = decode(model, mel[rows] if len(rows) != len(languages) else mel, opts)
             for i, r in zip(rows, res):
                 out[i] = r
         return out
 
-    def retry(results, languages: List[str], *, temperature: float, attempt: int, streams, seed: int, prompts=None, best_of=None):
+    def retry(results, languages: List[str], *, temperature: float, attempt: int, streams, seed: int, prompts=None, best_of=None,
+              row_adapters=None):
         """the default ``fallback_fn``: the rows' encoder features (``DecodingResult.audio_features``) decoded again at
         ``temperature``, each row on its own stream and with the prompt it was first decoded with; ``best_of``: as that many
         candidates per row, of which decode() keeps the best"""
@@ -191,10 +198,11 @@ def _model_decoder(model, decode_options: dict) -> Callable:
         sampling_options = {k: v for k, v in decode_options.items() if k not in ("beam_size", "patience")}
         for lang in sorted(set(languages)):
             rows = [i for i, l in enumerate(languages) if l == lang]
-            opts = DecodingOptions(**with_prompts({**sampling_options, "language": lang, "without_timestamps": False,
+            opts = DecodingOptions(**with_adapters(with_prompts({**sampling_options, "language": lang, "without_timestamps": False,
                                                    "temperature": float(temperature), "seed": int(seed),
                                                    "sample_streams": [streams[i] for i in rows], "sample_attempt": int(attempt),
-                                                   **({"best_of": int(best_of)} if best_of is not None else {})}, prompts, rows))
+                                                   **({"best_of": int(best_of)} if best_of is not None else {})}, prompts, rows),
+                                                   row_adapters, rows))
             res = decode(model, feats[rows] if len(rows) != len(languages) else feats, opts)
             for i, r in zip(rows, res):
                 out[i] = r
@@ -565,6 +573,19 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
     if getattr(model, "audio_ctx", None) is not None:
         raise NotImplementedError(f"transcribe() on a model with audio_ctx={model.audio_ctx} is not implemented: its window loop, seek "
                                   "arithmetic and timestamp range assume 30 s windows; decode() / decode_continuous() serve audio_ctx")
+    # an adapter of the model's bank per FILE: every window of a file carries it, and retries and conditioning keep it
+    file_adapters = decode_options.pop("row_adapters", None)
+    if file_adapters is not None:
+        if model is None or decode_fn is not None or getattr(model, "adapter_bank", None) is None:
+            raise NotImplementedError("transcribe(row_adapters=...) is served by the model's own decoder on a model with an adapter bank "
+                                      "(Whisper.set_adapter_bank); a custom decode_fn takes no row_adapters")
+        if schedule == "continuous":
+            raise NotImplementedError("transcribe(schedule='continuous'): row_adapters is not implemented (its window source hands out no "
+                                      "adapter with a window yet); use schedule='rounds'")
+        if word_timestamps:
+            raise NotImplementedError("word_timestamps=True with row_adapters is not implemented: the alignment pass takes no adapter bank")
+        file_adapters = list(file_adapters)
+        model.adapter_bank.ids(file_adapters)  # an unknown name is refused before anything is decoded
     _refuse(condition_on_previous_text, initial_prompt, word_timestamps, clip_timestamps, hallucination_silence_threshold, temperature,
             decode_options, can_align=align_fn is not None or (model is not None and decode_fn is None),
             can_retry=decode_fn is None or fallback_fn is not None,
@@ -611,6 +632,8 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
         fallback_fn = None  # as ever: the flag and the warning
 
     n = len(clips)
+    if file_adapters is not None and len(file_adapters) != n:
+        raise ValueError(f"transcribe: row_adapters holds {len(file_adapters)} names for {n} files")
     content_frames = [len(a) // HOP_LENGTH for a in clips]
     initial_ids = [int(t) for t in tok.encode(" " + initial_prompt.strip())] if initial_prompt is not None else []
     books = _Books(tok, n, language, initial_ids, (compression_ratio_threshold, logprob_threshold, no_speech_threshold),
@@ -634,10 +657,11 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
         prompts = [list(all_tokens[i][prompt_reset_since[i]:]) for i in live] if conditioning else None
         if conditioning and prompt_budget is not None:  # None: decode() keeps upstream's last n_text_ctx // 2 - 1
             prompts = [_last_tokens(p, int(prompt_budget)) for p in prompts]
+        adapters = {"row_adapters": [file_adapters[i] for i in live]} if file_adapters is not None else {}
         if conditioning:
-            results = list(decode_fn(windows, [languages[i] for i in live], prompts=prompts))
+            results = list(decode_fn(windows, [languages[i] for i in live], prompts=prompts, **adapters))
         else:
-            results = list(decode_fn(windows, [languages[i] for i in live]))
+            results = list(decode_fn(windows, [languages[i] for i in live], **adapters))
         to_align = []  # (result, the window's segments, content frames, time offset, language, the segments' decoded tokens): rows not skipped
         retried = set()  # rows of this round that went through the schedule
         if fallback_fn is not None:
@@ -650,6 +674,8 @@ def transcribe(model, audio, *, verbose: Optional[bool] = None, temperature: Uni
                 more = {"prompts": [prompts[r] for r in failing]} if conditioning else {}  # the retry keeps the window's prompt
                 if best_of is not None:
                     more["best_of"] = best_of
+                if file_adapters is not None:
+                    more["row_adapters"] = [file_adapters[live[r]] for r in failing]
                 again = fallback_fn([results[r] for r in failing], [languages[live[r]] or results[r].language for r in failing],
                                     temperature=temps[attempt], attempt=attempt, streams=[(seek[live[r]], live[r]) for r in failing], seed=seed,
                                     **more)

@@ -401,6 +401,8 @@ class Whisper:
         from . import lora as lora_mod
 
         bases = getattr(self, "_adapter_base", {})
+        if adapter is not None and getattr(self, "_bank", None) is not None:
+            raise _lib.WipaError("set_adapter while an adapter bank is set: set_adapter_bank(None) first (a bank's adapters apply to the base weights)")
         if adapter is None:
             with on_stream():
                 for n, b in bases.items():
@@ -438,6 +440,41 @@ class Whisper:
     def _no_adapter(self, what: str) -> None:
         if getattr(self, "_adapter", None) is not None:
             raise _lib.WipaError(f"{what} while an adapter is applied: set_adapter(None) first (the kept base tensors would go stale)")
+        if getattr(self, "_bank", None) is not None:
+            raise _lib.WipaError(f"{what} while an adapter bank is set: set_adapter_bank(None) first")
+
+    def set_adapter_bank(self, bank):
+        """Keep ``bank`` (``lora.AdapterBank``) beside the base weights, UNMERGED: a decode with ``DecodingOptions.row_adapters`` then runs
+        every row under its own adapter -- ``y[b] += gain[id[b]] B[id[b]] (A[id[b]] x[b])`` behind each adapted linear of the decode
+        step (csrc/lora_bank.hip), the ids read from a device array, so one captured step graph serves any assignment.  A decode
+        without ``row_adapters`` runs the base model, launch for launch as without a bank.  ``None`` removes the bank.  Refused: while
+        ``set_adapter`` has an adapter merged (and the other way round), fp8 tables, a bank built for other dimensions or on another
+        device.  A bank on ``cross_attn.key`` / ``cross_attn.value`` adds its terms to the CACHED cross K / V: ``cross_attention="auto"``
+        resolves to ``cached`` while it is set and ``"absorbed"`` is refused (``use_absorbed``)."""
+        from . import lora as lora_mod
+
+        if bank is None:
+            self._bank = None
+            return self
+        if not isinstance(bank, lora_mod.AdapterBank):
+            raise _lib.WipaError("set_adapter_bank: bank must be a lora.AdapterBank (or None)")
+        if getattr(self, "_adapter", None) is not None:
+            raise _lib.WipaError("set_adapter_bank while an adapter is applied: set_adapter(None) first (a bank's adapters apply to the base weights)")
+        if self._fp8 or self._fp8_enc:
+            raise _lib.WipaError("set_adapter_bank: a model with fp8 tables is not supported: the adapted linears run on bf16 / f32 decoder tables")
+        if self.dtype not in (torch.float32, torch.bfloat16):
+            raise _lib.WipaError(f"set_adapter_bank: a model of dtype {self.dtype}: float32 or bfloat16")
+        d = self.dims.n_text_state
+        if bank.n_layer != self.dims.n_text_layer or any(A.shape[2] != lora_mod.site_shape(self.dims, s)[1] for (_, s), A in bank.A.items()):
+            raise _lib.WipaError(f"set_adapter_bank: the bank was built for other dimensions than n_text_layer={self.dims.n_text_layer}, n_text_state={d}")
+        if bank.gain.device.type != torch.device(self.device).type:
+            raise _lib.WipaError(f"set_adapter_bank: the bank lives on {bank.gain.device}, the model on {self.device}")
+        self._bank = bank
+        return self
+
+    @property
+    def adapter_bank(self):
+        return getattr(self, "_bank", None)
 
     def parameters(self) -> Dict:
         return _unflatten(self._params)
@@ -494,6 +531,12 @@ class Whisper:
         import os
 
         eligible = self.cross_absorbed_eligible
+        bank = getattr(self, "_bank", None)
+        if bank is not None and bank.targets_cross_kv:
+            if self.cross_attention == "absorbed":
+                raise _lib.WipaError("cross_attention='absorbed' with an adapter bank on cross_attn.key / cross_attn.value is not supported: the "
+                                     "absorbed form keeps no K / V to adapt -- use cross_attention='cached' or 'auto'")
+            return False
         if self.cross_attention == "absorbed":
             if not eligible:
                 raise _lib.WipaError("cross_attention='absorbed' needs a bf16 model without fp8 tables, <= 16 heads, d in {384, 512, 768, 1024}")
